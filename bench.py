@@ -14,8 +14,10 @@ are generated on rank 0 and SCATTERED over RCCL, every rank ticks its own shard 
 rank 0 over RCCL, where every shard is checked bit for bit against a single-GPU run of the same
 scenes.  Scatter / gather / check are outside the timed region (inputs resident in HBM when timing starts).
 
-Timing: W warm-up steps, barrier + device sync, K steps, barrier + device sync, MAX over ranks.
-Per-kernel durations come from HIP events recorded by the library on the streams its kernels run on.
+Timing: W warm-up steps, barrier + device sync, K steps, barrier + device sync, MAX over ranks.  A plain run stops there:
+it writes the outputs of the last timed step (--dump-outputs DIR) and prints the headline line.  Everything else moves behind
+--full: per-kernel durations (HIP events recorded by the library on the streams its kernels run on, in untimed passes), the
+roofline, the other legs and configurations, the CPU baseline and, for N > 1, the gather and the shard check.
 """
 import argparse
 import json
@@ -41,17 +43,27 @@ def parse():
     ap.add_argument("--grid", type=int, default=512)
     ap.add_argument("--obstacles", type=int, default=64)
     ap.add_argument("--dynamic", type=int, default=0, help="1: BASELINE configs[3] (dynamic obstacles, replan every tick)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--latency-ticks", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel times and roofline, Part R alone, the streamed / one-shot / configs[3] / configs[4] "
+                         "legs, batch-1 latency, the CPU baseline and, for N > 1, the gather and shard check (without it: the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the PlanOut / SceneState / GridOut of the last timed step to DIR/<record>.<field>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: length of the CPU baseline")
+    ap.add_argument("--latency-ticks", type=int, default=200, help="with --full: ticks of the batch-1 latency (0: none)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearsal of the N > 1 path with ranks sharing the GPUs of a smaller box (never a measured number)")
-    ap.add_argument("--dump-gathered", default=None, help="rank 0 writes the gathered PlanOut / SceneState / GridOut of all ranks to this .npz (tests)")
-    ap.add_argument("--no-verify-gather", action="store_true", help="skip the bit-for-bit check of the gathered shards on rank 0")
+    ap.add_argument("--dump-gathered", default=None, help="with --full: rank 0 writes the gathered PlanOut / SceneState / GridOut of all ranks to this .npz (tests)")
+    ap.add_argument("--no-verify-gather", action="store_true", help="with --full: skip the bit-for-bit check of the gathered shards on rank 0")
     ap.add_argument("--bucket-cap", type=int, default=0, help="experiment: PlannerConfig.bucket_cap (0: the default); <= 512 means no open-list spill area and no retry kernel")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the streamed / one-shot / configs[3] / configs[4] legs behind the timed region")
-    ap.add_argument("--no-kernel-events", action="store_true", help="experiment: no HIP events around the kernels of the timed region (no per-kernel times, no roofline)")
-    return ap.parse_args()
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the streamed / one-shot / configs[3] / configs[4] legs")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: no passes with HIP events around the kernels (no per-kernel times, no roofline)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_gathered and not args.full:
+        ap.error("--dump-gathered needs --full")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -130,6 +142,42 @@ def pmc_instructions(path=os.path.join(ROOT, "profiles", "r3_pmc_insts.txt")):
             d = ast.literal_eval(ln[ln.index("{"):].strip())
             out[name] = (d.get("SQ_INSTS_VALU", 0), d.get("SQ_INSTS_SALU", 0))
     return out or None
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, np, records):
+    """Every numeric field of the output records ({"plan": PlanOut[], ...}, one entry per scene) as out_dir/<record>.<field>.npy:
+    float32 fields as they are, every other field as float64 (exact for the 32-bit integers); a uint64 field becomes two float64
+    files, <field>.hi32 and <field>.lo32.  Above DUMP_LIMIT_BYTES a fixed seeded sample of scenes is written, their indices
+    in out_dir/scene_index.npy."""
+    cols = []
+
+    def walk(name, a):
+        if a.dtype.names:
+            for f in a.dtype.names:
+                if not f.startswith("_pad"):
+                    walk(name + "." + f, a[f])
+        elif a.dtype.kind == "f" and a.itemsize == 4:
+            cols.append((name, a))
+        elif a.dtype.kind == "u" and a.itemsize == 8:
+            cols.append((name + ".hi32", (a >> np.uint64(32)).astype(np.float64)))
+            cols.append((name + ".lo32", (a & np.uint64(0xFFFFFFFF)).astype(np.float64)))
+        else:
+            cols.append((name, a.astype(np.float64)))
+    for k, v in records.items():
+        walk(k, v)
+    n = len(next(iter(records.values())))
+    per_scene = sum(a.nbytes for _, a in cols) / max(n, 1) + 8             # + its entry in scene_index.npy
+    budget = DUMP_LIMIT_BYTES - 128 * (len(cols) + 1)                       # .npy headers
+    idx = np.arange(n)
+    if per_scene * n > budget:
+        idx = np.sort(np.random.default_rng(0).choice(n, int(budget // per_scene), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scene_index.npy"), idx.astype(np.float64))
+    for name, a in cols:
+        np.save(os.path.join(out_dir, name + ".npy"), a[idx])
 
 
 def time_ticks(pl, steps, warmup, events=True):
@@ -294,36 +342,101 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    def gather_outputs():
+        """PlanOut + SceneState + GridOut of every rank's scenes, gathered on rank 0 over RCCL: ({record: [one array per rank]}
+        on rank 0, None elsewhere; milliseconds of the gather)."""
+        mine = sharding.result_tensors(dm, torch, pl, n, comm_dev)      # device-to-device copies out of the handle's buffers
+        torch.cuda.synchronize()
+        if not rehearsal:
+            dist.barrier()
+        g0 = time.perf_counter()
+        allg = {k: sharding.gather_results(dist, torch, v, rank, world) for k, v in mine.items()}
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - g0) * 1e3
+        if rank != 0:
+            return None, ms
+        dts = {"plan": dm.PlanOut, "state": dm.SceneState, "grid_out": dm.GridOut}
+        return {k: [np.frombuffer(t.cpu().numpy().tobytes(), dts[k]) for t in allg[k]] for k in dts}, ms
+
     for _ in range(args.warmup):
         pl.tick()
     barrier()
-    # HIP events around the search kernel only inside the timed region (the dominant kernel: roofline); the other kernels' average
-    # durations come from a second, untimed pass of the same K steps with events around every launch (an event pair costs queue time)
-    pl.set_profile(0 if args.no_kernel_events else 2)
-    pl.reset_kernel_ms()
+    # no HIP events inside the timed region (an event pair costs queue time): with --full, the search kernel's average duration
+    # (the dominant kernel: roofline) comes from an untimed pass of the same K steps with events around its launches only, the
+    # other kernels' from a second one with events around every launch
+    pl.set_profile(0)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         pl.tick()
     barrier()
     dt_local = dt = time.perf_counter() - t0
-    kms = pl.kernel_ms()
     ticks_run = args.warmup + args.steps
+    if dist is not None:
+        t = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+
+    # ---- what the timed path computed in its last step: the records a caller of pp_plan_tick receives ----
+    if args.dump_outputs:
+        if dist is None:
+            outputs = {"plan": pl.get_plan(), "state": pl.get_state(), "grid_out": pl.get_grid_out()}
+        else:
+            outputs, _ = gather_outputs()
+            outputs = outputs and {k: np.concatenate(v) for k, v in outputs.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, np, outputs)
+
+    b_r, b_g, per_kernel = algorithmic_bytes(cfg, n_obs)
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "planning ticks/sec (batched scenes), %dx%d grid" % (args.grid, args.grid),
+            "value": n * world * args.steps / dt,
+            "unit": "ticks/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ticks_run": ticks_run,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": "BASELINE configs[%d]: %d scenes/GPU, %dx%d grid, %d %s obstacles"
+                                   % (3 if args.dynamic else (4 if args.grid == 2048 else (2 if world > 1 else 1)), n, args.grid, args.grid, n_obs,
+                                      "dynamic" if args.dynamic else "static"),
+                       "scenes_per_gpu": n, "global_scenes": n * world, "grid": args.grid, "obstacles": n_obs,
+                       "parallelism": ("scene-sharded x%d, RCCL scatter/gather outside the timed region" % world)
+                                      + (" [REHEARSAL: gloo, ranks share GPUs - not a measurement]" if rehearsal else ""),
+                       "algorithmic_bytes_per_tick": b_r + b_g,
+                       "tick_GBps": (b_r + b_g) * n * world * args.steps / dt / 1e9},
+        }
+    if not args.full:
+        if line:
+            print(json.dumps(line))
+        pl.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    kms = pl.kernel_ms()
     if not args.no_kernel_events:
-        ticks_run += args.steps
+        ticks_run += 2 * args.steps
+        pl.set_profile(2)
+        pl.reset_kernel_ms()
+        for _ in range(args.steps):
+            pl.tick()
+        barrier()
+        kms_search = pl.kernel_ms()
         pl.set_profile(1)
         pl.reset_kernel_ms()
         for _ in range(args.steps):
             pl.tick()
         barrier()
         kms_all = pl.kernel_ms()
-        kms = {k: (kms[k] if k == "k_search" else v) for k, v in kms_all.items()}
+        kms = {k: (kms_search[k] if k == "k_search" else v) for k, v in kms_all.items()}
     pl.set_profile(0)
-    if dist is not None:
-        t = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-
-    b_r, b_g, per_kernel = algorithmic_bytes(cfg, n_obs)
 
     def roofline_of(kms_):
         dom = max(kms_, key=lambda k: kms_[k][0])
@@ -334,30 +447,19 @@ def main():
 
     # ---- results gathered over RCCL: PlanOut + SceneState + GridOut of every scene, checked on rank 0 ----
     gout = pl.get_grid_out()
-    gathered = None
     multi = None
     if dist is not None:
-        from dmpp_amd_pkg import sharding
-        mine = sharding.result_tensors(dm, torch, pl, n, comm_dev)      # device-to-device copies out of the handle's buffers
-        torch.cuda.synchronize()
-        if not rehearsal:
-            dist.barrier()
-        g0 = time.perf_counter()
-        allg = {k: sharding.gather_results(dist, torch, v, rank, world) for k, v in mine.items()}
-        torch.cuda.synchronize()
-        gather_ms = (time.perf_counter() - g0) * 1e3
+        gathered, gather_ms = gather_outputs()
         dom, avg_ms, achieved = roofline_of(kms)
         stats = [None] * world
         dist.all_gather_object(stats, {"rank": rank, "ms_per_step": dt_local / args.steps * 1e3, "kernel": dom, "avg_launch_ms": avg_ms,
                                        "achieved": achieved, "frac": achieved / HBM_PEAK_GBPS,
                                        "search_status_counts": np.bincount(gout["status"], minlength=dm.G_STATUS_COUNT).tolist()})
         if rank == 0:
-            dts = {"plan": dm.PlanOut, "state": dm.SceneState, "grid_out": dm.GridOut}
-            gathered = {k: [np.frombuffer(t.cpu().numpy().tobytes(), dts[k]) for t in allg[k]] for k in dts}
-            gathered_bytes = sum(t.numel() for k in allg for t in allg[k])
+            gathered_bytes = sum(a.nbytes for k in gathered for a in gathered[k])
             checked, mism = 0, []
             if not args.no_verify_gather:
-                # every shard again on THIS GPU alone, the same W + K ticks from the same generated scenes: the gathered
+                # every shard again on THIS GPU alone, the same ticks_run ticks from the same generated scenes: the gathered
                 # records must be identical (integers and floats bit for bit; NaN == NaN)
                 sys.path.insert(0, os.path.join(ROOT, "tests"))
                 from parity_util import compare
@@ -388,7 +490,7 @@ def main():
 
     # ---- Part R alone (Decision + Planning ticks, grid engine off) on the same scenes, rank 0; SURVEY 8(d) asks for
     #      the two parts separately as well as combined.  Part G's kernels never run without Part R's inputs, so its
-    #      figure is the serial sum of its kernels' average launch times from the timed region above. ----
+    #      figure is the serial sum of its kernels' average launch times from the event passes above. ----
     parts = None
     if rank == 0:
         cfg_r = cfg.copy()
@@ -556,7 +658,6 @@ def main():
         if multi:
             status_counts = np.sum([s["search_status_counts"] for s in multi["per_rank"]], axis=0)
         searched = int(status_counts.sum() - status_counts[dm.G_GOAL_BLOCKED])
-        total = n * world
         # how busy the vector units are over the whole tick: instructions of every kernel of the tick (committed PMC pass, configs[1]
         # at 1024 scenes) x 4 cycles per wave64 instruction, over the SIMD-cycles of the tick time (1024 SIMDs, 2.4 GHz)
         issue = None
@@ -566,28 +667,8 @@ def main():
             issue = {"valu_insts_per_tick": valu, "salu_insts_per_tick": salu,
                      "frac_of_valu_issue_slots": valu * 4.0 / (1024 * 2.4e9 * (dt / args.steps)),
                      "source": "profiles/r3_pmc_insts.txt (rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU, per launch of each kernel of the tick)"}
-        line = {
-            "metric": "planning ticks/sec (batched scenes), %dx%d grid" % (args.grid, args.grid),
-            "value": total * args.steps / dt,
-            "unit": "ticks/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ticks_run": ticks_run,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[%d]: %d scenes/GPU, %dx%d grid, %d %s obstacles"
-                                   % (3 if args.dynamic else (4 if args.grid == 2048 else (2 if world > 1 else 1)), n, args.grid, args.grid, n_obs,
-                                      "dynamic" if args.dynamic else "static"),
-                       "scenes_per_gpu": n, "global_scenes": total, "grid": args.grid, "obstacles": n_obs,
-                       "parallelism": ("scene-sharded x%d, RCCL scatter/gather outside the timed region" % world)
-                                      + (" [REHEARSAL: gloo, ranks share GPUs - not a measurement]" if rehearsal else ""),
-                       "algorithmic_bytes_per_tick": b_r + b_g,
-                       "tick_GBps": (b_r + b_g) * total * args.steps / dt / 1e9},
+        line["ticks_run"] = ticks_run
+        line.update({
             "p50_plan_latency_ms_batch1": p50_ms,
             "p50_class_surface_ms": p50_class_ms,
             "parts": parts,
@@ -622,7 +703,7 @@ def main():
             "plan_tick_batch": batch_call,
             "other_configs": other,
             "cpu_baseline": cpu,
-        }
+        })
         if multi:
             line["multi_gpu"] = multi
         print(json.dumps(line))

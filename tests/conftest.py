@@ -3,6 +3,12 @@ import subprocess
 import sys
 
 import pytest
+# Before anything loads libdmpp.so: the library needs libamdhip64.so.7, torch's libraries need its bundled copy under the
+# name libamdhip64.so, and the loader matches names, not files.  Loaded first, the library pulls in the system ROCm runtime
+# and torch then adds a second HIP runtime to the process; whichever of the two opens the GPU first keeps it, and the other
+# reports "no ROCm-capable device" (a suite that asks torch.cuda.is_available() before creating a planner fails).  With
+# torch first, libamdhip64.so.7 is already loaded and the library binds to it: one runtime per test process.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -754,7 +754,7 @@ def test_bench_two_ranks_rehearsal(dm, oracle, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     dump = str(tmp_path / "gathered.npz")
     n, grid, n_obs, warm, steps = 1024, 512, 64, 1, 2
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", str(warm),
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", str(warm), "--full",
            "--scenes", str(n), "--grid", str(grid), "--obstacles", str(n_obs), "--backend", "gloo", "--no-cpu-baseline",
            "--latency-ticks", "0", "--dump-gathered", dump]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
@@ -783,6 +783,56 @@ def test_bench_two_ranks_rehearsal(dm, oracle, tmp_path):
         counts += np.bincount(gout_o["status"], minlength=dm.G_STATUS_COUNT)
     assert line["search_status_counts"] == counts.tolist()
     assert line["searched_scenes"] == int(counts.sum() - counts[dm.G_GOAL_BLOCKED])
+
+
+def _leaf_fields(name, a):
+    if a.dtype.names:
+        for f in a.dtype.names:
+            if not f.startswith("_pad"):
+                yield from _leaf_fields(name + "." + f, a[f])
+    else:
+        yield name, a
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(dm, oracle, tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline line alone, and --dump-outputs writes the records of its last
+    timed step: every field must match the oracle ticking the same generated scenes W + K times."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    n, grid, n_obs, warm, steps = 64, 128, 8, 2, 3
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
+           "--scenes", str(n), "--grid", str(grid), "--obstacles", str(n_obs), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    print(r.stdout[-2000:], r.stderr[-1500:])
+    assert r.returncode == 0
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == steps and line["ticks_run"] == warm + steps
+    assert line["unit"] == "ticks/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert "cpu_baseline" not in line and "kernel_ms_avg" not in line
+    assert np.array_equal(np.load(out / "scene_index.npy"), np.arange(n, dtype=np.float64))
+    cfg = dm.default_config(grid)
+    sc = dm.gen_scenes(cfg, 0, n, n_obs, junction_every=8)
+    st = sc["state"].copy()
+    plan_o, gout_o, _ = oracle.plan_tick_batch(cfg, sc, st, n_threads=8, want_grid=True, n_ticks=warm + steps)
+    bad = []
+    for rec, want_rec in (("plan", plan_o), ("state", st), ("grid_out", gout_o)):
+        for name, want in _leaf_fields(rec, want_rec):
+            if want.dtype.kind == "u" and want.itemsize == 8:
+                hi, lo = np.load(out / (name + ".hi32.npy")), np.load(out / (name + ".lo32.npy"))
+                ok = np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), want)
+                bad += [] if ok else [name]
+                continue
+            got = np.load(out / (name + ".npy"))
+            assert got.dtype in (np.float32, np.float64), name
+            if want.dtype.kind == "f":
+                bad += compare(got, want, name)
+            elif not np.array_equal(got, want.astype(np.float64)):
+                bad.append(name)
+    assert not bad, "\n".join(bad[:10])
 
 
 @pytest.mark.parametrize("dx,dy", [(25.0, 0.0), (-30.0, 0.0), (0.0, -40.0)])
