@@ -1,8 +1,8 @@
 // dmpp_hip.hip — the C-ABI of include/dmpp_planner.h over the HIP kernels (gfx950 only).
 //
 // One handle = one device and all device buffers.  Streams: the handle's stream (copies, stand-alone operators, the whole
-// tick of a small batch), kBuf search streams (stream_m[0] is the handle's stream: the searches of consecutive ticks run
-// side by side, each preceded by its launch order and followed by its own scoring pass), the FRONT stream stream_r (obstacle
+// tick of a small batch), kBuf search streams (stream_m[0] is the handle's stream: the searches of consecutive tick groups
+// run side by side, each preceded by its launch order and followed by its own scoring pass; a group is G ticks in one launch), the FRONT stream stream_r (obstacle
 // snapshot, Decision, Planning: highest priority, running ahead of the searches), stream_s (scoring on its own stream: a measurement knob), and - once streamed
 // ticks are in use (pp_update_async / pp_fetch_async) - one upload and two download streams.  pp_plan_tick describes the
 // launch order and the events between the chains; batches below pipeline_min scenes run on the handle's stream with only
@@ -34,24 +34,40 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
             return fail(PP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));      \
     } while (0)
 
-struct EvPair { hipEvent_t a, b; int k; };
+struct EvPair { hipEvent_t a, b; int k; int w; };      // w: the ticks the launch between a and b stands for (a tick group's)
 
-// Buffers that a tick's search and scoring touch exist kBuf times, used round-robin ("parity"): up to kBuf searches of
-// consecutive ticks are in flight at once, each on its own stream, and scoring of tick t never holds up the search of t + 1.
+// Tick groups.  The piped tick (pp_plan_tick) launches the searches and scoring passes of G consecutive ticks together: one
+// k_search, one k_search_spill and one k_score over G * n work items (dmpp::TickGroup), G <= kGroupMax.  A search launch ends with
+// its slowest scenes; with more work items than workgroup slots the freed slots take the remaining items while those run, so
+// that tail is paid once per group instead of once per tick.
+constexpr int kGroupMax = dmpp::kGroupMax;
+// Work buffers that a group's search and scoring touch exist kBuf times, used round-robin ("parity"): up to kBuf groups' searches
+// are in flight at once, each on its own stream, and the scoring of one group never holds up the search of the next.  Each set
+// holds up to gcap * caps.max_scenes work items (gcap: the largest G the handle allocates for, see pp_create).
 #ifndef DMPP_KBUF
 #define DMPP_KBUF 3
 #endif
 constexpr int kBuf = DMPP_KBUF;
-// The obstacle snapshot exists 2 * kBuf times: the front chain of tick t writes its snapshot while the scoring pass of tick
-// t - kBuf still reads its own, so that chain need not wait for that pass (only for the search before it, see pp_plan_tick).
-constexpr int kObs = 2 * kBuf;
+// The obstacle snapshot (with the path cells and the LDS need of its search) exists once per (group position, tick slot): kRing =
+// 2 * kBuf group positions of kGroupMax slots.  The front chain of a tick writes the set of its slot in group k while the groups
+// k - 1 .. k - 2 kBuf + 1 may still read theirs; it waits for the scoring pass of group k - 2 kBuf, the last reader of that set
+// (events, since that pass ran on another stream), so it may run up to 2 kBuf groups ahead of the scoring.
+constexpr int kRing = 2 * kBuf;
+constexpr int kObs = kRing * kGroupMax;
 // Streamed ticks (pp_update_async / pp_fetch_async): the per-tick inputs - SceneIn records, obstacle pool, motion pool - exist
 // kIn times.  An update is copied into the set after the current one while the ticks in flight still read theirs (a search
 // runs up to kBuf ticks behind the front chain of its tick); a set is written again only after every kernel of the ticks that
 // read it (TickRec) has finished.  PlanOut exists kPlan times, so that Planning(t + 1) does not wait for the download of tick t.
 constexpr int kIn = 12;
 constexpr int kPlan = 12;
-constexpr int kGout = 12;          // GridOut sets: a download is issued when its scoring pass has finished, up to ~8 ticks behind the newest front chain
+// GridOut sets: one per (GridOut group position, tick slot), kGoutRing = 4 kBuf group positions.  Group k and group k + kGoutRing
+// use the same search stream (a multiple of kBuf apart), so a set is rewritten behind the scoring pass of its last writer in
+// stream order; a download is issued when its scoring pass has finished, up to ~8 groups behind the newest front chain.
+constexpr int kGoutRing = 4 * kBuf;
+constexpr int kGout = kGoutRing * kGroupMax;
+// Work buffers of one search set: at most this many bytes per set for the slots of a tick group (beyond it, fewer slots: G = 1
+// at 2048 x 2048, where one scene has 8 MiB of closed-set spill area)
+constexpr size_t kGroupBytes = size_t(4) << 30;
 constexpr int kDone = 32;          // ticks whose downloads pp_wait_tick can still name
 
 struct InputSet {
@@ -89,11 +105,11 @@ struct pp_planner {
     ObPoint* d_obs = nullptr; ObMotion* d_mot = nullptr; ObPoint* d_obs_now[kObs] = {};
     bool have_motion = false;
     // state / outputs
-    SceneState* d_state = nullptr; PlanOut* d_plan = nullptr; GridOut* d_gout[kGout] = {}; int gout_set = 0;   // GridOut: kGout sets (a download of tick t must not hold up the search of tick t + kBuf); gout_set: the last grid tick's
+    SceneState* d_state = nullptr; PlanOut* d_plan = nullptr; GridOut* d_gout[kGout] = {}; int gout_set = 0;   // GridOut: kGout sets (a download of tick t must not hold up the searches after it); gout_set: the last grid tick's
     GlobalPoint2D* d_dec_ref = nullptr;
     // grid engine
     uint8_t* d_grid = nullptr; uint16_t* d_pinfo[kBuf] = {}; uint32_t* d_closed[kBuf] = {};
-    int32_t* d_order[kBuf] = {}; int32_t* d_path[kObs] = {}; uint32_t* d_gbm[kBuf] = {};     // d_path, d_need: per snapshot set (the scoring pass of tick t reads them beside the search of tick t + kBuf)
+    int32_t* d_order[kBuf] = {}; int32_t* d_path[kObs] = {}; uint32_t* d_gbm[kBuf] = {};     // d_path, d_need: per snapshot set (the scoring pass of a group reads them beside the searches of the next groups)
     int path_set = 0;                                  // the set of the last tick with the grid stage
     int32_t* d_perm[kBuf] = {}; int32_t* d_cost[kBuf] = {};
     uint2* d_ospill[kBuf] = {}; int spill_cap = 0; int32_t* d_retry[kBuf] = {};     // open-list spill areas (bucket_cap0 entries per scene; none when bucket_cap0 <= the LDS list)
@@ -108,6 +124,16 @@ struct pp_planner {
     int32_t* d_ovf[kBuf] = {}; int32_t* d_need[kObs] = {}; int32_t* h_need = nullptr;   // h_need: pinned, [kObs], written by k_score (-1: nothing yet)
     int need_seen = 0;
     int* d_gridbad = nullptr;
+    // tick groups: gcap = the most tick slots the work buffers hold (each set: gcap * caps.max_scenes work items); tick_group =
+    // env DMPP_TICK_GROUP (0: G derived from n and the search's workgroup slots).  The open group: grp_ticks ticks enqueued on the
+    // front chain whose searches wait for grp_G of them (flush_group launches them; so does every entry point that reads
+    // results, waits or changes state).
+    int gcap = 1, tick_group = 0;
+    int grp_ticks = 0, grp_G = 1, grp_n = 0, grp_p_prev = 0; bool grp_piped = false, grp_overlap = false;
+    int grp_set[kGroupMax] = {}, grp_gs[kGroupMax] = {}; const SceneIn* grp_in = nullptr;      // (the ticks of a group read one input set: a new one - streamed ticks - comes with G = 1)
+    int ring = 0, gring = 0;     // group positions of the last group: snapshot sets (kRing), GridOut sets (kGoutRing)
+    int item_off = 0;            // work item of scene 0 of the last grid tick in its group's buffers (pp_get_order / pp_get_search_info)
+    int need_set = 0;            // the snapshot set whose d_need / h_need the last group's search and scoring used
 
     hipStream_t stream_r = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the R kernels run beside the grid engine
     // k_score of tick t runs on its own stream beside the rasterise / search of tick t+1: the obstacle snapshot, the path
@@ -269,35 +295,63 @@ int prune_inflight(pp_planner* h)
 
 constexpr int kScoreWideMaxScenes = 128;     // up to here k_score runs 16 waves per scene (one scene per CU at most)
 
+// Tick slots the work buffers of a handle are allocated for: kGroupMax when its batches can run piped (max_scenes >= pipeline_min)
+// and the knob does not pin G to 1, fewer when a set of kGroupMax * max_scenes work items would exceed kGroupBytes.
+int group_cap(int max_scenes, int pipeline_min, int forced, size_t item_bytes)
+{
+    if (max_scenes < pipeline_min || forced == 1) return 1;
+    int g = kGroupMax;
+    while (g > 1 && (size_t)g * (size_t)max_scenes * item_bytes > kGroupBytes) g--;
+    return g;
+}
+// Ticks per group for a batch of n scenes: the knob if set (DMPP_TICK_GROUP), else the smallest G whose G * n work items are at
+// least twice the search's workgroup slots (the slots freed by the short scenes then have work while the long ones run);
+// at most the slots the handle's buffers hold (gcap <= kGroupMax).
+int group_size(int n, int search_slots, int gcap, int forced)
+{
+    int g = forced;
+    if (g <= 0) {
+        g = 1;
+        while (g < kGroupMax && (long long)g * n < 2ll * search_slots) g++;
+    }
+    return std::max(1, std::min({ g, gcap, kGroupMax }));
+}
+
+int flush_group(pp_planner* h);
+
 // Everything the ticks enqueued so far started - on any of the four streams - is ordered before whatever the handle's
-// stream does next: ev_score[q] closes the raster -> search -> score chain of the last tick of parity q, ev_join the
-// Decision -> Planning chain (stream order covers the earlier ticks).  No host wait.
+// stream does next: ev_score[q] closes the raster -> search -> score chain of the last group that used snapshot set q, ev_join
+// the Decision -> Planning chain (stream order covers the earlier ticks).  An open tick group is launched first.  No host wait.
 int join_all(pp_planner* h)
 {
+    { int r = flush_group(h); if (r) return r; }
     for (int q = 0; q < kObs; q++) if (h->score_recorded[q]) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_score[q], 0));
     if (h->front_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
     return PP_OK;
 }
 
+// HIP events around a launch.  A launch for a tick group counts as its w ticks: w launches, its time spread over them (the
+// averages of pp_get_kernel_ms stay per tick).
 struct Timed {
-    pp_planner* h; int k; hipStream_t st; hipEvent_t a = nullptr, b = nullptr; bool on = false;
-    Timed(pp_planner* h_, int k_, hipStream_t st_ = nullptr) : h(h_), k(k_), st(st_ ? st_ : h_->stream) {
+    pp_planner* h; int k; hipStream_t st; int w; hipEvent_t a = nullptr, b = nullptr; bool on = false;
+    Timed(pp_planner* h_, int k_, hipStream_t st_ = nullptr, int w_ = 1) : h(h_), k(k_), st(st_ ? st_ : h_->stream), w(w_) {
         on = h->profile == 1 || (h->profile == 2 && k == PP_K_SEARCH);
         if (on) { a = get_event(h); b = get_event(h); if (a) (void)hipEventRecord(a, st); }
     }
     ~Timed() {
-        if (on && a && b) { (void)hipEventRecord(b, st); h->pending.push_back({a, b, k}); }
+        if (on && a && b) { (void)hipEventRecord(b, st); h->pending.push_back({a, b, k, w}); }
     }
 };
 
 int drain_events(pp_planner* h)
 {
+    { int r = flush_group(h); if (r) return r; }         // (a profile switch applies from the next group on)
     if (h->pending.empty()) return PP_OK;
     { int r = join_all(h); if (r) return r; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (auto& p : h->pending) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { h->k_ms[p.k] += ms; h->k_launches[p.k] += 1; }
+        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { h->k_ms[p.k] += ms; h->k_launches[p.k] += p.w; }
         h->free_events.push_back(p.a); h->free_events.push_back(p.b);
     }
     h->pending.clear();
@@ -353,12 +407,13 @@ int setup_grid_launch(pp_planner* h)
     if (const char* e = std::getenv("DMPP_LDS_BUDGET")) {                                                // ... a fixed budget (words per view)
         h->lds_budget = std::max(1, std::min(std::atoi(e), h->lds_budget_max)); h->lds_budget_fixed = true;
     } else h->lds_budget = 0;                                                                            // chosen at the first tick (obstacle density), then adaptive
+    const size_t items = (size_t)h->gcap * h->caps.max_scenes;          // work items of a search set
     for (int q = 0; q < kBuf; q++) {
         if (!h->d_ovf[q]) {
-            int r = dmalloc(&h->d_ovf[q], (size_t)h->caps.max_scenes); if (r) return r;
-            HIP_TRY(hipMemsetAsync(h->d_ovf[q], 0, (size_t)h->caps.max_scenes * sizeof(int32_t), h->stream));
+            int r = dmalloc(&h->d_ovf[q], items); if (r) return r;
+            HIP_TRY(hipMemsetAsync(h->d_ovf[q], 0, items * sizeof(int32_t), h->stream));
         }
-        if (!h->d_retry[q]) { int r = dmalloc(&h->d_retry[q], (size_t)h->caps.max_scenes); if (r) return r; }
+        if (!h->d_retry[q]) { int r = dmalloc(&h->d_retry[q], items); if (r) return r; }
     }
     for (int q = 0; q < kObs; q++)
         if (!h->d_need[q]) { int r = dmalloc(&h->d_need[q], (size_t)2); if (r) return r; HIP_TRY(hipMemsetAsync(h->d_need[q], 0, 2 * sizeof(int32_t), h->stream)); }   // [0] LDS need of the search, [1] its retry count
@@ -369,14 +424,17 @@ int setup_grid_launch(pp_planner* h)
     if (sizeof(dmpp::ScoreShared<16>) > 48u * 1024u)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dmpp::k_score<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(dmpp::ScoreShared<16>));
     for (int q = 0; q < kBuf; q++) {
-        if (!h->d_perm[q]) { int r = dmalloc(&h->d_perm[q], (size_t)h->caps.max_scenes); if (r) return r; }
+        if (!h->d_perm[q]) {
+            int r = dmalloc(&h->d_perm[q], items); if (r) return r;
+            HIP_TRY(hipMemsetAsync(h->d_perm[q], 0, items * sizeof(int32_t), h->stream));
+        }
         if (!h->d_cost[q]) {
-            int r = dmalloc(&h->d_cost[q], (size_t)h->caps.max_scenes); if (r) return r;
-            HIP_TRY(hipMemsetAsync(h->d_cost[q], 0, (size_t)h->caps.max_scenes * sizeof(int32_t), h->stream));
+            int r = dmalloc(&h->d_cost[q], items); if (r) return r;
+            HIP_TRY(hipMemsetAsync(h->d_cost[q], 0, items * sizeof(int32_t), h->stream));
         }
     }
     for (int q = 0; q < kBuf; q++) if (!h->d_gbm[q]) {   // the dense form of the two views (row- then column-major), only written by the scenes that do not fit the LDS budget
-        int r = dmalloc(&h->d_gbm[q], (size_t)h->caps.max_scenes * 2 * (h->grid_cells / 32));
+        int r = dmalloc(&h->d_gbm[q], items * 2 * (h->grid_cells / 32));
         if (r) return r;
     }
     return PP_OK;
@@ -403,6 +461,14 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     if (!h) return fail(PP_ERR_HIP, "out of host memory");
     h->cfg = *cfg; h->caps = *caps; h->device = device;
     if (const char* e = std::getenv("DMPP_PIPELINE_MIN")) h->pipeline_min = std::atoi(e);      // tuning knob: 0 = always, large = never
+    if (const char* e = std::getenv("DMPP_TICK_GROUP")) h->tick_group = std::atoi(e);          // A/B knob: ticks per search launch (1: one, as before groups)
+    if (cfg->grid_stage) {
+        // tick slots the work buffers hold: kGroupMax for a handle that runs piped ticks, as long as a set stays within kGroupBytes
+        const size_t cells = (size_t)cfg->grid_w * cfg->grid_h;
+        const size_t item_bytes = cells * sizeof(uint16_t) + 3 * (cells / 32) * sizeof(uint32_t) + (size_t)std::max(caps->order_cap, 0) * sizeof(int32_t) +
+                                  (cfg->bucket_cap > DMPP_OPEN_CAP ? (size_t)cfg->bucket_cap * sizeof(uint2) : 0) + 4 * sizeof(int32_t);
+        h->gcap = group_cap(caps->max_scenes, h->pipeline_min, h->tick_group, item_bytes);
+    }
     auto bail = [&](int code) { pp_destroy(h); return code; };
     // Queue priorities.  The FRONT chain (obstacle snapshot, Decision, Planning) is a short serial chain that every tick's
     // search waits for: it gets the highest dispatch priority (and its waves raise their issue priority, s_setprio).  The
@@ -454,29 +520,41 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     if (hipMemsetAsync(h->d_mot, 0, (size_t)(caps->max_obs_total > 0 ? caps->max_obs_total : 1) * sizeof(ObMotion), h->stream) != hipSuccess)
         return bail(fail(PP_ERR_HIP, "memset failed"));     // velocities nobody uploaded are zero, never uninitialised
     if ((r = dmalloc(&h->d_bad, (size_t)1))) return bail(r);
-    for (int q = 0; q < kObs; q++) if ((r = dmalloc(&h->d_obs_now[q], (size_t)caps->max_obs_total))) return bail(r);
+    // the sets of the tick slots of a group position lie at a fixed stride in one allocation (dmpp::TickGroup); slots beyond gcap: none
+    const size_t obs_stride = (size_t)std::max(caps->max_obs_total, 1);
+    for (int q = 0; q < kObs; q += kGroupMax) {
+        if ((r = dmalloc(&h->d_obs_now[q], h->gcap * obs_stride))) return bail(r);
+        for (int i = 1; i < h->gcap; i++) h->d_obs_now[q + i] = h->d_obs_now[q] + i * obs_stride;
+    }
     if ((r = dmalloc(&h->d_state, ns))) return bail(r);
     if ((r = dmalloc(&h->d_plan_ring[0], ns))) return bail(r);
     h->d_plan = h->d_plan_ring[0];
     if (hipMemsetAsync(h->d_plan, 0, ns * sizeof(PlanOut), h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "memset failed"));
     for (int q = 0; q < kDone; q++) h->done_tick[q] = -1;
-    for (int q = 0; q < kGout; q++) if ((r = dmalloc(&h->d_gout[q], ns))) return bail(r);
+    for (int q = 0; q < kGout; q += kGroupMax) {
+        if ((r = dmalloc(&h->d_gout[q], h->gcap * ns))) return bail(r);
+        for (int i = 1; i < h->gcap; i++) h->d_gout[q + i] = h->d_gout[q] + i * ns;
+    }
     if ((r = dmalloc(&h->d_dec_ref, ns * DMPP_MAX_REFPATH))) return bail(r);
-    for (int q = 0; q < kGout; q++)
-        if (hipMemsetAsync(h->d_gout[q], 0, ns * sizeof(GridOut), h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "memset failed"));
+    for (int q = 0; q < kGout; q += kGroupMax)
+        if (hipMemsetAsync(h->d_gout[q], 0, h->gcap * ns * sizeof(GridOut), h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "memset failed"));
     if (cfg->grid_stage) {
         h->grid_cells = (size_t)cfg->grid_w * cfg->grid_h;
         h->bucket_cap0 = cfg->bucket_cap; h->max_path0 = cfg->max_path;
         if ((r = dmalloc(&h->d_grid, h->grid_cells))) return bail(r);             // one scene as bytes, filled on demand (pp_get_grid)
+        const size_t items = (size_t)h->gcap * ns;          // work items of a search set
         for (int q = 0; q < kBuf; q++) {
-            if ((r = dmalloc(&h->d_pinfo[q], ns * h->grid_cells))) return bail(r);
-            if ((r = dmalloc(&h->d_closed[q], ns * (h->grid_cells / 32)))) return bail(r);
+            if ((r = dmalloc(&h->d_pinfo[q], items * h->grid_cells))) return bail(r);
+            if ((r = dmalloc(&h->d_closed[q], items * (h->grid_cells / 32)))) return bail(r);
         }
-        for (int q = 0; q < kObs; q++) if ((r = dmalloc(&h->d_path[q], ns * (size_t)cfg->max_path))) return bail(r);
-        for (int q = 0; q < kBuf; q++) if (caps->order_cap > 0 && (r = dmalloc(&h->d_order[q], ns * (size_t)caps->order_cap))) return bail(r);
+        for (int q = 0; q < kObs; q += kGroupMax) {
+            if ((r = dmalloc(&h->d_path[q], h->gcap * ns * (size_t)cfg->max_path))) return bail(r);
+            for (int i = 1; i < h->gcap; i++) h->d_path[q + i] = h->d_path[q] + i * ns * (size_t)cfg->max_path;
+        }
+        for (int q = 0; q < kBuf; q++) if (caps->order_cap > 0 && (r = dmalloc(&h->d_order[q], items * (size_t)caps->order_cap))) return bail(r);
         if (cfg->bucket_cap > DMPP_OPEN_CAP) {
             h->spill_cap = cfg->bucket_cap;
-            for (int q = 0; q < kBuf; q++) if ((r = dmalloc(&h->d_ospill[q], ns * (size_t)h->spill_cap))) return bail(r);
+            for (int q = 0; q < kBuf; q++) if ((r = dmalloc(&h->d_ospill[q], items * (size_t)h->spill_cap))) return bail(r);
         }
         if ((r = setup_grid_launch(h))) return bail(r);
     }
@@ -491,6 +569,7 @@ int pp_destroy(pp_handle h)
 {
     if (!h) return PP_OK;
     (void)hipSetDevice(h->device);
+    (void)flush_group(h);                     // (the open group's work buffers are freed below: its launches are enqueued and waited for)
     for (hipStream_t st : { h->stream, h->stream_r, h->stream_s }) if (st) (void)hipStreamSynchronize(st);
     for (int q = 1; q < kBuf; q++) if (h->stream_m[q]) (void)hipStreamSynchronize(h->stream_m[q]);
     for (auto& p : h->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -499,14 +578,14 @@ int pp_destroy(pp_handle h)
     if (h->stream_dg == h->stream_dp) h->stream_dg = nullptr;
     if (h->stream_dp == h->stream_up) h->stream_dp = nullptr;
     for (hipStream_t st : { h->stream_up, h->stream_dp, h->stream_dg }) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    for (int q = 0; q < kObs; q++) if (h->d_obs_now[q]) (void)hipFree(h->d_obs_now[q]);
+    for (int q = 0; q < kObs; q += kGroupMax) if (h->d_obs_now[q]) (void)hipFree(h->d_obs_now[q]);      // (one allocation per group position)
     for (int q = 0; q < kIn; q++) {
         InputSet& I = h->in_sets[q];
         for (void* b : { (void*)I.d_in, (void*)I.d_obs, (void*)I.d_mot }) if (b) (void)hipFree(b);
         if (I.ev_up) (void)hipEventDestroy(I.ev_up);
     }
     for (int q = 0; q < kPlan; q++) { if (h->d_plan_ring[q]) (void)hipFree(h->d_plan_ring[q]); if (h->ev_fetched_plan[q]) (void)hipEventDestroy(h->ev_fetched_plan[q]); }
-    for (int q = 0; q < kGout; q++) { if (h->ev_fetched_grid[q]) (void)hipEventDestroy(h->ev_fetched_grid[q]); if (h->d_gout[q]) (void)hipFree(h->d_gout[q]); }
+    for (int q = 0; q < kGout; q++) { if (h->ev_fetched_grid[q]) (void)hipEventDestroy(h->ev_fetched_grid[q]); if (q % kGroupMax == 0 && h->d_gout[q]) (void)hipFree(h->d_gout[q]); }
     for (int q = 0; q < kDone; q++) { if (h->ev_done_p[q]) (void)hipEventDestroy(h->ev_done_p[q]); if (h->ev_done_g[q]) (void)hipEventDestroy(h->ev_done_g[q]); }
     for (auto e : h->sync_events) (void)hipEventDestroy(e);
     for (auto& r : h->inflight) { (void)hipEventDestroy(r.ev_front); if (r.ev_tail) (void)hipEventDestroy(r.ev_tail); }
@@ -519,7 +598,7 @@ int pp_destroy(pp_handle h)
         for (void* b : { (void*)h->d_ospill[q], (void*)h->d_retry[q], (void*)h->d_pinfo[q], (void*)h->d_closed[q], (void*)h->d_order[q],
                          (void*)h->d_gbm[q], (void*)h->d_perm[q], (void*)h->d_cost[q], (void*)h->d_ovf[q] })
             if (b) (void)hipFree(b);
-    for (int q = 0; q < kObs; q++) for (void* b : { (void*)h->d_path[q], (void*)h->d_need[q] }) if (b) (void)hipFree(b);
+    for (int q = 0; q < kObs; q++) for (void* b : { q % kGroupMax == 0 ? (void*)h->d_path[q] : nullptr, (void*)h->d_need[q] }) if (b) (void)hipFree(b);
     for (int q = 0; q < kBuf; q++) if (h->ev_search[q]) (void)hipEventDestroy(h->ev_search[q]);
     for (int q = 0; q < kObs; q++) if (h->ev_score[q]) (void)hipEventDestroy(h->ev_score[q]);
     if (h->ev_raster) (void)hipEventDestroy(h->ev_raster);
@@ -714,6 +793,97 @@ int pp_set_state(pp_handle h, const SceneState* state, int n)
     return PP_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// Launches the searches and scoring passes of the open tick group (nothing when no group is open): one k_order (when the work
+// items outnumber the search's workgroup slots), one k_search, one k_search_spill and one k_score over the G * n work items.
+//   search(group k) follows score(group k - kBuf) on its stream (and waits for it when scoring has a stream of its own) and
+//   waits for the snapshot of its last tick's front chain [ev_raster] - the front chain is one stream, so that covers all G.
+int flush_group(pp_planner* h)
+{
+    const int G = h->grp_ticks;
+    if (G == 0) return PP_OK;
+    h->grp_ticks = 0;
+    const PlannerConfig& c = h->cfg;
+    const int n = h->grp_n, items = G * n, p = h->parity;
+    const bool piped = h->grp_piped, overlap = h->grp_overlap;
+    hipStream_t sm = overlap ? h->stream_m[p] : h->stream;             // search chain
+    hipStream_t sf = piped ? h->stream_r : h->stream;                  // front chain
+    hipStream_t ss = piped ? ((overlap && !h->score_own_stream) ? sm : h->stream_s) : h->stream; // score chain: behind its own search when the searches overlap
+    hipStream_t sr = h->stream_r;                                      // Decision + Planning (grid stage)
+    // Work buffers p were last used by group k - kBuf (its tick slot 0 used snapshot set set_b)
+    const int set0 = h->grp_set[0], set_b = ((h->ring + kBuf) % kRing) * kGroupMax;
+    if (h->score_recorded[set_b] && ss == sm) HIP_TRY(hipStreamWaitEvent(sm, h->ev_score[set_b], 0));     // (own scoring stream: path cells and LDS need exist per snapshot set, the search does not wait for that scoring)
+    if (!overlap)                                                      // one search at a time (also after a switch of mode)
+        for (int q = 0; q < kBuf; q++) if (q != p && h->search_recorded[q]) HIP_TRY(hipStreamWaitEvent(sm, h->ev_search[q], 0));
+    if (sf != sm) HIP_TRY(hipStreamWaitEvent(sm, h->ev_raster, 0));
+    auto wait_unless_done = [](hipStream_t st, hipEvent_t e) { if (hipEventQuery(e) == hipSuccess) return hipSuccess; (void)hipGetLastError(); return hipStreamWaitEvent(st, e, 0); };
+    for (int i = 0; i < G; i++)
+        if (h->streaming && h->fetched_grid_rec[h->grp_gs[i]]) HIP_TRY(wait_unless_done(sm, h->ev_fetched_grid[h->grp_gs[i]]));   // GridOut set still being downloaded
+    dmpp::TickGroup tg;                                                // slot i: sets grp_set[0] + i, grp_gs[0] + i
+    tg.n = n; tg.in = h->grp_in;
+    tg.obs_now = h->d_obs_now[set0]; tg.obs_stride = std::max(h->caps.max_obs_total, 1);
+    tg.paths = h->d_path[set0]; tg.path_stride = (long long)h->caps.max_scenes * h->max_path0;
+    tg.gout = h->d_gout[h->grp_gs[0]]; tg.gout_stride = h->caps.max_scenes;
+    // launch order of the search (heaviest work items first) - pointless while every item is resident at once.  Keyed by the
+    // times of the group kBuf back, the one before it on its stream (one-stream tick: by the previous one's).
+    const bool order_scenes = items > h->search_slots;
+    // DMPP_FRONT_WAIT=1: the last front of a FULL group has launched k_order over G * n items (pp_plan_tick); a group flushed
+    // early (pp_sync, a getter, ...) gets its launch order here, over the items it has
+    const bool order_in_front = order_scenes && piped && h->front_wait && G == h->grp_G;
+    const int32_t* perm = order_scenes ? h->d_perm[p] : nullptr;
+    if (perm && !order_in_front)
+        hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sm, items, h->d_cost[overlap ? p : h->grp_p_prev], h->d_perm[p]);
+    int32_t* need = h->d_need[set0];                                   // the group's LDS need and retry count
+    {
+        const int budget = h->search_force_gbm ? 0 : h->lds_budget;
+        const bool wide = items <= kScoreWideMaxScenes;       // a few scenes: sixteen waves set each scene up (the latency-bound tick)
+        const size_t dyn = std::max((size_t)h->search_meta_bytes + 8 * (size_t)budget, (size_t)h->gbm_lds);
+        const bool use_spill = h->d_ospill[p] != nullptr && c.bucket_cap > DMPP_OPEN_CAP;     // scenes whose open list outgrows LDS are searched again, spilling
+        Timed t(h, PP_K_SEARCH, sm, G);
+        switch (h->search_kind) {
+#define DMPP_LAUNCH_SEARCH(K)                                                                                                                  \
+        case K:                                                                                                                                \
+            if (wide) hipLaunchKernelGGL((dmpp::k_search<K, dmpp::kSearchSetupWavesWide>), dim3(items), dim3(dmpp::kSearchSetupWavesWide * DMPP_WAVE), dyn, sm, c, items, tg, \
+                                         h->caps.order_cap, budget, perm, h->d_closed[p], h->d_pinfo[p], h->d_order[p], h->d_gbm[p],                   \
+                                         h->d_cost[p], h->d_ovf[p], need, h->d_ospill[p], h->spill_cap, h->d_retry[p], use_spill ? need + 1 : nullptr); \
+            else hipLaunchKernelGGL((dmpp::k_search<K, dmpp::kSearchSetupWaves>), dim3(items), dim3(dmpp::kSearchBlock), dyn, sm, c, items, tg,        \
+                                    h->caps.order_cap, budget, perm, h->d_closed[p], h->d_pinfo[p], h->d_order[p], h->d_gbm[p],                        \
+                                    h->d_cost[p], h->d_ovf[p], need, h->d_ospill[p], h->spill_cap, h->d_retry[p], use_spill ? need + 1 : nullptr);      \
+            if (use_spill) hipLaunchKernelGGL((dmpp::k_search_spill<K>), dim3(std::min(items, 2)), dim3(dmpp::kSearchBlock), dyn, sm, c, items, tg,    \
+                                              h->caps.order_cap, budget, h->d_closed[p], h->d_pinfo[p], h->d_order[p], h->d_gbm[p],                    \
+                                              h->d_cost[p], h->d_ovf[p], need, h->d_ospill[p], h->spill_cap, h->d_retry[p], need + 1);                  \
+            break;
+        DMPP_LAUNCH_SEARCH(0) DMPP_LAUNCH_SEARCH(1) DMPP_LAUNCH_SEARCH(2)
+#undef DMPP_LAUNCH_SEARCH
+        }
+    }
+    h->search_recorded[p] = piped;                   // (one-stream mode: stream order is enough, no events on the latency path)
+    if (piped) { HIP_TRY(hipEventRecord(h->ev_search[p], sm)); HIP_TRY(hipStreamWaitEvent(ss, h->ev_search[p], 0)); }
+    {
+        Timed t(h, PP_K_SCORE, ss, G);
+        int32_t* need_host = (!h->lds_budget_fixed && !h->search_force_gbm) ? &h->h_need[set0] : nullptr;
+        if (items <= kScoreWideMaxScenes)     // few scenes: sixteen waves per scene (17 candidates in two rounds)
+            hipLaunchKernelGGL(dmpp::k_score<16>, dim3(items), dim3(16 * DMPP_WAVE), sizeof(dmpp::ScoreShared<16>), ss, c, items, tg, need, need_host);
+        else
+            hipLaunchKernelGGL(dmpp::k_score<4>, dim3(items), dim3(4 * DMPP_WAVE), sizeof(dmpp::ScoreShared<4>), ss, c, items, tg, need, need_host);
+    }
+    for (int i = 0; i < G; i++) {                    // the group's scoring pass is the last reader of its G snapshot sets
+        h->score_recorded[h->grp_set[i]] = piped;
+        if (piped) HIP_TRY(hipEventRecord(h->ev_score[h->grp_set[i]], ss));
+    }
+    if (!piped && sr != h->stream) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));   // one-stream mode: the tick is complete on the handle's stream
+    h->need_set = set0; h->item_off = (G - 1) * n;
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int pp_plan_tick(pp_handle h)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
@@ -724,53 +894,68 @@ int pp_plan_tick(pp_handle h)
     if (c.decision_stage && c.lanechg_stage && !h->have_attr)
         return fail(PP_ERR_ARG, "cfg.lanechg_stage needs the lane attribute pool (pp_set_scenes lane_attr_pool)");
     // One tick = two chains.  FRONT (stream_r, highest priority): obstacle snapshot, Decision, Planning - short kernels, serial
-    // from tick to tick through SceneState.  SEARCH (stream_m[t % kBuf]): (launch order,) k_search, k_search_spill, k_score - the
-    // long one; the searches of kBuf consecutive ticks run side by side on their own streams.
-    //   search(t) waits for the snapshot of front(t) [ev_raster] and follows score(t - kBuf) on its stream;
-    //   front(t)  waits for score(t - kObs), whose snapshot set it overwrites - so it may run up to kObs ticks ahead of the scoring.
-    // What a search and its scoring pass write exists kBuf times (closed sets, orders, ...), what the scoring pass reads beside
-    // a later search kObs times (snapshot, path cells, LDS need), GridOut kGout times.
-    // Small batches and ticks without the grid stage stay on one stream (a cross-stream hand-over costs tens of
-    // microseconds; only Decision + Planning run beside the grid engine there).
+    // from tick to tick through SceneState.  SEARCH (stream_m[k % kBuf] for tick group k): (launch order,) k_search,
+    // k_search_spill, k_score - the long one, for the G ticks of the group at once (flush_group); the searches of kBuf
+    // consecutive groups run side by side on their own streams.
+    //   search(k) waits for the snapshot of the front chain of its last tick [ev_raster] and follows score(k - kBuf) on its stream;
+    //   front(t)  waits for score(k - 2 kBuf), the last reader of the snapshot set it overwrites - so it may run up to 2 kBuf
+    //             groups ahead of the scoring.
+    // What a search and its scoring pass write exists kBuf times (closed sets, orders, ...: work buffers of G * n items), what
+    // the scoring pass reads beside later searches once per (group position, slot) - kObs times (snapshot, path cells, LDS need),
+    // GridOut kGout times.  The search of a tick is a function of its inputs and its snapshot alone, so which ticks share a launch
+    // changes no result.
+    // Small batches and ticks without the grid stage stay on one stream, one tick per group (a cross-stream hand-over costs tens
+    // of microseconds; only Decision + Planning run beside the grid engine there); so do streamed ticks (pp_update_async /
+    // pp_fetch_async: every tick is fetched, and its downloads wait for its own scoring pass).
     // (a tick without the grid stage leaves the search buffers alone: pp_get_grid_out / pp_get_path keep returning the last search)
-    const int p = c.grid_stage ? (h->parity + 1) % kBuf : h->parity, p_prev = h->parity;
-    const int gs = c.grid_stage ? (h->gout_set + 1) % kGout : h->gout_set;
     const bool piped = c.grid_stage && n >= h->pipeline_min;
+    const bool open = h->grp_ticks == 0;
     // streamed inputs: the update staged by pp_update_async becomes the set this tick (and the following ones) read
     bool adopted = false;
     if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; adopted = true; }
+    if (open) {
+        h->grp_p_prev = h->parity;
+        if (c.grid_stage) { h->parity = (h->parity + 1) % kBuf; h->gring = (h->gring + 1) % kGoutRing; }
+        h->ring = (h->ring + 1) % kRing;
+        h->grp_G = (piped && !h->streaming) ? group_size(n, h->search_slots, h->gcap, h->tick_group) : 1;
+        h->grp_n = n; h->grp_piped = piped;
+    }
+    const int slot = h->grp_ticks, G = h->grp_G, p = h->parity;
+    const int po = h->ring * kGroupMax + slot;                                        // this tick's snapshot set
+    const int gs = c.grid_stage ? h->gring * kGroupMax + slot : h->gout_set;          // ... and GridOut set
     if (h->streaming) {
         // downloads whose kernels have finished are issued now; one that still reads a set this tick overwrites is issued whatever
-        int r = pump_fetches(h, -1, (h->plan_cur + 1) % kPlan, c.grid_stage ? (h->gout_set + 1) % kGout : -1); if (r) return r;
+        int r = pump_fetches(h, -1, (h->plan_cur + 1) % kPlan, c.grid_stage ? gs : -1); if (r) return r;
         r = prune_inflight(h); if (r) return r;
         h->plan_cur = (h->plan_cur + 1) % kPlan; h->d_plan = h->d_plan_ring[h->plan_cur];
         if (!adopted) h->h_bad[(h->tick_seq + 1) % kDone] = 0;
     }
-    if (c.grid_stage && !h->search_force_gbm) {
-        // LDS budget of the search (data words per view).  First tick: from the obstacle density; afterwards from what the
-        // densest scene of an earlier tick needed (+ 1/8): the scoring pass behind each search stores it in pinned memory, which
-        // is simply read here - whatever has landed; never waited for.
+    if (open && c.grid_stage && !h->search_force_gbm) {
+        // LDS budget of the group's search (data words per view).  First tick: from the obstacle density; afterwards from what
+        // the densest scene of an earlier group needed (+ 1/8): the scoring pass behind each search stores it in pinned memory,
+        // which is simply read here - whatever has landed; never waited for.
+        const int items = G * n;
         if (!h->lds_budget_fixed) {
             int need = -1;
-            for (int q = 0; q < kBuf; q++) need = std::max(need, (int)reinterpret_cast<volatile int32_t*>(h->h_need)[(h->obs_set + kObs - q) % kObs]);     // the last kBuf ticks' sets
+            for (int q = 0; q < kBuf; q++) need = std::max(need, (int)reinterpret_cast<volatile int32_t*>(h->h_need)[((h->ring + kRing - 1 - q) % kRing) * kGroupMax]);     // the last kBuf groups' sets
             int want = h->lds_budget;
             if (need >= 0) {
                 h->need_seen = need;
                 const int fit = std::min(h->lds_budget_max, (need + need / 8 + 64 + 63) / 64 * 64);
                 // Workgroups per CU at a budget (the 160 KB of LDS are handed out in 128 granules of 1,280 bytes - measured: 54,000 bytes per
                 // workgroup are two per CU, 52,976 three, 26,864 six).
-                // When the scenes outnumber the workgroup slots and a smaller - still safe - slack over the need lets one more
+                // When the work items outnumber the workgroup slots and a smaller - still safe - slack over the need lets one more
                 // searching workgroup onto every CU, the largest budget that does is taken: 256 moving obstacles need ~4,650 words,
                 // 5,312 with the usual eighth on top = two workgroups of 55 KB per CU; three fit at <= 5,120 (configs[3]: 1.14 -> 1.23 M
                 // ticks/s); 4096 scenes of 64 obstacles: six of 26.9 KB instead of five of 27.9 (5.17 -> 5.30 M).  With a slot for every
-                // scene the eighth stays: the room it leaves on the CU is what the front kernels start in.  A scene that outgrows the
+                // item the eighth stays: the room it leaves on the CU is what the front kernels start in.  A scene that outgrows the
                 // budget takes the dense form in HBM.
                 const size_t fixed_lds = h->search_static_lds + 64 + (size_t)h->search_meta_bytes;
                 constexpr size_t kLdsGranule = 1280;
                 auto wgs_at = [&](int b) { return (int)std::min<size_t>(8, (160u * 1024u) / ((fixed_lds + 8 * (size_t)b + kLdsGranule - 1) / kLdsGranule * kLdsGranule)); };
                 int target = fit;
                 const int tight = std::min(h->lds_budget_max, (need + std::max(need / 32, 96) + 63) / 64 * 64);
-                if (tight < fit && wgs_at(tight) > wgs_at(fit) && n > wgs_at(fit) * std::max(1, h->n_cus)) {
+                if (tight < fit && wgs_at(tight) > wgs_at(fit) && items > wgs_at(fit) * std::max(1, h->n_cus)) {
                     const size_t room = (160u * 1024u) / (size_t)wgs_at(tight) / kLdsGranule * kLdsGranule;
                     const int lim = room > fixed_lds ? (int)((room - fixed_lds) / 8 / 64 * 64) : 0;
                     target = std::max(tight, std::min(lim, fit));
@@ -790,31 +975,25 @@ int pp_plan_tick(pp_handle h)
         const size_t per_wg = h->search_static_lds + 64 + std::max((size_t)h->search_meta_bytes + 8 * (size_t)h->lds_budget, (size_t)h->gbm_lds);
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / per_wg));       // 4 waves per workgroup while it sets up: <= 8 per CU
         h->search_slots = per_cu * std::max(1, h->n_cus);
-    } else if (c.grid_stage) {
+    } else if (open && c.grid_stage) {
         const size_t per_wg = h->search_static_lds + 64 + (size_t)h->gbm_lds;
         h->search_slots = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / per_wg)) * std::max(1, h->n_cus);
     }
     // Consecutive searches overlap: a search ends with a handful of long scenes and would leave most of the chip idle; the searches
-    // of up to kBuf consecutive ticks run on their own streams (every buffer a search or a scoring pass touches exists kBuf times).
+    // of up to kBuf consecutive groups run on their own streams (every buffer a search or a scoring pass touches exists kBuf times).
     bool overlap = piped;
     if (h->overlap_override >= 0) overlap = piped && h->overlap_override != 0;      // env DMPP_OVERLAP (measurement knob)
+    if (open) h->grp_overlap = overlap;
     hipStream_t sm = overlap ? h->stream_m[p] : h->stream;             // search chain
     hipStream_t sf = piped ? h->stream_r : h->stream;                  // front chain
-    hipStream_t ss = piped ? ((overlap && !h->score_own_stream) ? sm : h->stream_s) : h->stream; // score chain: behind its own search when the searches overlap
     hipStream_t sr = c.grid_stage ? h->stream_r : h->stream;           // Decision + Planning
-    // Buffers p were last used by tick t - kBuf (snapshot set po_b), snapshot set po - and with it the path cells and the LDS need
-    // of the search - by tick t - 2 kBuf.  The search follows the scoring pass of tick t - kBuf on its stream; the front chain waits
-    // for the scoring pass of tick t - 2 kBuf (it overwrites that pass's snapshot) and, see below, for the search of tick t - kBuf.
-    const int po = (h->obs_set + 1) % kObs, po_b = (po + kBuf) % kObs;
-    if (h->score_recorded[po_b] && ss == sm) HIP_TRY(hipStreamWaitEvent(sm, h->ev_score[po_b], 0));     // (own scoring stream: path cells and LDS need exist per snapshot set, the search of tick t does not wait for the scoring of t - kBuf)
+    // The front chain overwrites snapshot set po: it waits for the scoring pass of the last group that read it (2 kBuf groups back).
     if (h->score_recorded[po]) HIP_TRY(hipStreamWaitEvent(sf, h->ev_score[po], 0));
-    // The front chain does not wait for the search of tick t - kBuf: it runs ahead - up to kObs ticks, bounded by the snapshot
+    // The front chain does not wait for the search kBuf groups back: it runs ahead - up to 2 kBuf groups, bounded by the snapshot
     // sets - so its kernels no longer start together with the scoring pass that follows that search (+ 2 %), and the launch order,
     // which needs that search's times, is computed on the search's own stream.  DMPP_FRONT_WAIT=1: the old hand-over (measurement knob).
     const bool front_wait = h->front_wait;
     if (h->search_recorded[p] && front_wait) HIP_TRY(hipStreamWaitEvent(sf, h->ev_search[p], 0));
-    if (!overlap)                                                      // one search at a time (also after a switch of mode)
-        for (int q = 0; q < kBuf; q++) if (q != p && h->search_recorded[q]) HIP_TRY(hipStreamWaitEvent(sm, h->ev_search[q], 0));
     if (h->front_recorded && sf == h->stream && h->front_unjoined) HIP_TRY(hipStreamWaitEvent(sf, h->ev_join, 0));   // Planning(t-1) -> snapshot(t) when not on the same stream
     h->front_unjoined = false;
     if (h->r_on_main && sf != h->stream) {         // Planning(t-1) ran on the handle's stream (grid stage off then): the front chain reads its state
@@ -832,12 +1011,10 @@ int pp_plan_tick(pp_handle h)
                            h->d_obs, h->have_motion ? h->d_mot : nullptr, obs_now);
     }
     if (sr != sf) { HIP_TRY(hipEventRecord(h->ev_fork, sf)); HIP_TRY(hipStreamWaitEvent(sr, h->ev_fork, 0)); }   // small batches: Decision + Planning beside the grid engine
-    // launch order of the search (heaviest scenes first) - pointless while every scene is resident at once.  Keyed by the times of
-    // the search kBuf ticks back, the one before it on its stream (one-stream tick: by the previous tick's).
-    const bool order_scenes = c.grid_stage && n > h->search_slots;
-    const bool order_in_front = order_scenes && piped && front_wait;
-    if (order_in_front) hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sf, n, h->d_cost[p], h->d_perm[p]);
-    if (sf != sm) HIP_TRY(hipEventRecord(h->ev_raster, sf));        // the search rasterises for itself: it only needs the obstacle snapshot (and its launch order)
+    const bool last_of_group = c.grid_stage && slot + 1 == G;
+    if (last_of_group && piped && front_wait && G * n > h->search_slots)        // DMPP_FRONT_WAIT=1: the launch order on the front chain, as in rounds 1 - 2
+        hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sf, G * n, h->d_cost[p], h->d_perm[p]);
+    if (c.grid_stage && sf != sm) HIP_TRY(hipEventRecord(h->ev_raster, sf));        // the search rasterises for itself: it only needs the obstacle snapshot (and its launch order)
     if (c.decision_stage) {
         Timed t(h, PP_K_DECISION, sr);
         hipLaunchKernelGGL(dmpp::k_decision, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, h->d_in, h->d_lane,
@@ -849,61 +1026,20 @@ int pp_plan_tick(pp_handle h)
                            h->d_ref, h->d_dec_ref, obs_now, h->d_state, h->d_plan);
     }
     if (sr != h->stream) { HIP_TRY(hipEventRecord(h->ev_join, sr)); h->front_recorded = true; h->front_unjoined = piped; }
+    h->obs_set = po;
     if (c.grid_stage) {
-        if (sf != sm) HIP_TRY(hipStreamWaitEvent(sm, h->ev_raster, 0));
-        if (h->streaming && h->fetched_grid_rec[gs]) HIP_TRY(wait_unless_done(sm, h->ev_fetched_grid[gs]));   // GridOut set still being downloaded (kGout grid ticks ago)
-        const int32_t* perm = order_scenes ? h->d_perm[p] : nullptr;
-        if (perm && !order_in_front)
-            hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sm, n, h->d_cost[overlap ? p : p_prev], h->d_perm[p]);
-        {
-            const int budget = h->search_force_gbm ? 0 : h->lds_budget;
-            const bool wide = n <= kScoreWideMaxScenes;       // a few scenes: sixteen waves set each scene up (the latency-bound tick)
-            const size_t dyn = std::max((size_t)h->search_meta_bytes + 8 * (size_t)budget, (size_t)h->gbm_lds);
-            const bool use_spill = h->d_ospill[p] != nullptr && c.bucket_cap > DMPP_OPEN_CAP;     // scenes whose open list outgrows LDS are searched again, spilling
-            {
-                Timed t(h, PP_K_SEARCH, sm);
-                switch (h->search_kind) {
-#define DMPP_LAUNCH_SEARCH(K)                                                                                                                  \
-                case K:                                                                                                                        \
-                    if (wide) hipLaunchKernelGGL((dmpp::k_search<K, dmpp::kSearchSetupWavesWide>), dim3(n), dim3(dmpp::kSearchSetupWavesWide * DMPP_WAVE), dyn, sm, c, n, h->caps.order_cap, budget, perm, \
-                                           h->d_in, obs_now, h->d_closed[p], h->d_pinfo[p], h->d_order[p], h->d_path[po], h->d_gout[gs], h->d_gbm[p], \
-                                           h->d_cost[p], h->d_ovf[p], h->d_need[po], h->d_ospill[p], h->spill_cap, h->d_retry[p], use_spill ? h->d_need[po] + 1 : nullptr); \
-                    else hipLaunchKernelGGL((dmpp::k_search<K, dmpp::kSearchSetupWaves>), dim3(n), dim3(dmpp::kSearchBlock), dyn, sm, c, n, h->caps.order_cap, budget, perm,  \
-                                           h->d_in, obs_now, h->d_closed[p], h->d_pinfo[p], h->d_order[p], h->d_path[po], h->d_gout[gs], h->d_gbm[p], \
-                                           h->d_cost[p], h->d_ovf[p], h->d_need[po], h->d_ospill[p], h->spill_cap, h->d_retry[p], use_spill ? h->d_need[po] + 1 : nullptr); \
-                    if (use_spill) hipLaunchKernelGGL((dmpp::k_search_spill<K>), dim3(std::min(n, 2)), dim3(dmpp::kSearchBlock), dyn, sm, c, n, h->caps.order_cap, budget,                       \
-                                           h->d_in, obs_now, h->d_closed[p], h->d_pinfo[p], h->d_order[p], h->d_path[po], h->d_gout[gs], h->d_gbm[p],                              \
-                                           h->d_cost[p], h->d_ovf[p], h->d_need[po], h->d_ospill[p], h->spill_cap, h->d_retry[p], h->d_need[po] + 1);                           \
-                    break;
-                DMPP_LAUNCH_SEARCH(0) DMPP_LAUNCH_SEARCH(1) DMPP_LAUNCH_SEARCH(2)
-#undef DMPP_LAUNCH_SEARCH
-                }
-            }
-        }
-        h->search_recorded[p] = piped;                   // (one-stream mode: stream order is enough, no events on the latency path)
-        if (piped) { HIP_TRY(hipEventRecord(h->ev_search[p], sm)); HIP_TRY(hipStreamWaitEvent(ss, h->ev_search[p], 0)); }
-        {
-            Timed t(h, PP_K_SCORE, ss);
-            int32_t* need_host = (!h->lds_budget_fixed && !h->search_force_gbm) ? &h->h_need[po] : nullptr;
-            if (n <= kScoreWideMaxScenes)     // few scenes: sixteen waves per scene (17 candidates in two rounds)
-                hipLaunchKernelGGL(dmpp::k_score<16>, dim3(n), dim3(16 * DMPP_WAVE), sizeof(dmpp::ScoreShared<16>), ss, c, n, h->d_in, obs_now,
-                                   h->d_path[po], h->d_gout[gs], h->d_need[po], need_host);
-            else
-                hipLaunchKernelGGL(dmpp::k_score<4>, dim3(n), dim3(4 * DMPP_WAVE), sizeof(dmpp::ScoreShared<4>), ss, c, n, h->d_in, obs_now,
-                                   h->d_path[po], h->d_gout[gs], h->d_need[po], need_host);
-        }
-        h->score_recorded[po] = piped;
-        if (piped) HIP_TRY(hipEventRecord(h->ev_score[po], ss));
-        if (!piped && sr != h->stream) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));   // one-stream mode: the tick is complete on the handle's stream
+        h->grp_set[slot] = po; h->grp_gs[slot] = gs; h->grp_in = h->d_in;
+        h->grp_ticks = slot + 1;
+        h->gout_set = gs; h->path_set = po;
+        if (last_of_group) { int r = flush_group(h); if (r) return r; }
     }
-    h->parity = p; h->obs_set = po; h->gout_set = gs; h->last_piped = piped;
-    if (c.grid_stage) h->path_set = po;
+    h->last_piped = piped;
     h->tick_seq++;
     if (h->streaming) {          // what a later update of this tick's input set, and a download of its results, wait for
         TickRec rec = { h->tick_seq, h->in_cur, get_sync_event(h), c.grid_stage ? get_sync_event(h) : nullptr };
         if (!rec.ev_front || (c.grid_stage && !rec.ev_tail)) return fail(PP_ERR_HIP, "hipEventCreate failed");
         HIP_TRY(hipEventRecord(rec.ev_front, sr));
-        if (rec.ev_tail) HIP_TRY(hipEventRecord(rec.ev_tail, piped ? ss : h->stream));
+        if (rec.ev_tail) HIP_TRY(hipEventRecord(rec.ev_tail, piped ? (h->grp_overlap && !h->score_own_stream ? sm : h->stream_s) : h->stream));
         h->inflight.push_back(rec); h->last_rec = rec;
     }
     HIP_TRY(hipGetLastError());
@@ -997,18 +1133,20 @@ int pp_get_search_info(pp_handle h, int32_t* lds_budget_words, int32_t* need_wor
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (!h->d_ovf[0]) return fail(PP_ERR_STATE, "handle was created without the grid stage");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = flush_group(h); if (r) return r; }          // parity / item_off / need_set name the last tick only once its group is launched
     if (lds_budget_words) *lds_budget_words = h->search_force_gbm ? 0 : h->lds_budget;
     if (need_words) {                      // what the densest scene of the last tick needed (its scoring pass has stored it by now)
         HIP_TRY(hipSetDevice(h->device));
         { int r = join_all(h); if (r) return r; }
         HIP_TRY(hipStreamSynchronize(h->stream));
-        const int32_t v = reinterpret_cast<volatile int32_t*>(h->h_need)[h->parity];
+        const int32_t v = reinterpret_cast<volatile int32_t*>(h->h_need)[h->need_set];
         if (v >= 0) h->need_seen = v;
         *need_words = h->need_seen;
     }
     if (dense_scenes) {
         std::vector<int32_t> ovf((size_t)std::max(h->n_scenes, 1));
-        int r = fetch(h, ovf.data(), h->d_ovf[h->parity], (size_t)h->n_scenes * sizeof(int32_t)); if (r) return r;
+        int r = fetch(h, ovf.data(), h->d_ovf[h->parity] + h->item_off, (size_t)h->n_scenes * sizeof(int32_t)); if (r) return r;
         int k = 0; for (int i = 0; i < h->n_scenes; i++) k += ovf[(size_t)i] != 0;
         *dense_scenes = k;
     }
@@ -1019,7 +1157,9 @@ int pp_get_order(pp_handle h, int scene, int32_t* order, int cap)
     if (!h || !order || !h->d_order[0]) return fail(PP_ERR_STATE, "expansion order was not requested (caps.order_cap == 0)");
     if (scene < 0 || scene >= h->n_scenes) return fail(PP_ERR_ARG, "scene out of range");
     if (cap > h->caps.order_cap) cap = h->caps.order_cap;
-    return fetch(h, order, h->d_order[h->parity] + (size_t)scene * h->caps.order_cap, (size_t)cap * sizeof(int32_t));
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = flush_group(h); if (r) return r; }          // (item_off is the last tick's only once its group is launched)
+    return fetch(h, order, h->d_order[h->parity] + ((size_t)h->item_off + scene) * h->caps.order_cap, (size_t)cap * sizeof(int32_t));
 }
 int pp_get_refpath(pp_handle h, int scene, GlobalPoint2D* pts, int cap)
 {
@@ -1108,6 +1248,7 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     if (obs_pool && (n_obs_total < 0 || n_obs_total > h->caps.max_obs_total)) return fail(PP_ERR_CAPACITY, "obstacle pool larger than caps.max_obs_total");
     if (!obs_pool && mot_pool) return fail(PP_ERR_ARG, "a motion pool without its obstacle pool");
     HIP_TRY(hipSetDevice(h->device));
+    { int r = flush_group(h); if (r) return r; }          // the ticks before streaming began are launched as they stand
     { int r = ensure_streaming(h); if (r) return r; }
     { int r = pump_fetches(h); if (r) return r; }
     { int r = prune_inflight(h); if (r) return r; }
@@ -1159,6 +1300,7 @@ static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, Planning
     if (h->tick_seq == 0 || h->n_scenes <= 0) return fail(PP_ERR_STATE, "pp_fetch_async: no tick has been enqueued");
     if (grid && !h->cfg.grid_stage) return fail(PP_ERR_STATE, "pp_fetch_async: the last tick ran without the grid stage");
     HIP_TRY(hipSetDevice(h->device));
+    { int r = flush_group(h); if (r) return r; }          // the downloads follow the last tick's scoring pass: it must be enqueued
     { int r = ensure_streaming(h); if (r) return r; }
     const long long T = h->tick_seq;
     const int slot = (int)(T % kDone), n = h->n_scenes;
@@ -1205,6 +1347,7 @@ int pp_wait_tick(pp_handle h, long long tick_id, int* n_poisoned)
     if (!h->streaming || h->done_tick[slot] != tick_id)
         return fail(PP_ERR_ARG, "pp_wait_tick: no pp_fetch_async was issued for that tick (or more than " + std::to_string(kDone) + " ticks ago)");
     HIP_TRY(hipSetDevice(h->device));
+    { int r = flush_group(h); if (r) return r; }
     { int r = pump_fetches(h, tick_id); if (r) return r; }
     if (h->done_p_rec[slot]) HIP_TRY(hipEventSynchronize(h->ev_done_p[slot]));
     if (h->done_g_rec[slot]) HIP_TRY(hipEventSynchronize(h->ev_done_g[slot]));
@@ -1221,6 +1364,7 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
     if ((io->want & PP_IO_WANT_GRID) && !h->cfg.grid_stage) return fail(PP_ERR_STATE, "PP_IO_WANT_GRID: the handle's configuration has the grid stage off");
     HIP_TRY(hipSetDevice(h->device));
     const int max_obs = std::min(PP_IO_MAX_OBS, h->caps.max_obs_total), max_ref = std::min(DMPP_MAX_REFPATH, h->caps.max_ref_pts_total);
+    { int r = flush_group(h); if (r) return r; }          // (k_io_in rewrites the inputs an open group's searches read)
     h->in_staged = -1;
     hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->d_in, h->d_state, h->d_obs, h->d_ref);
     HIP_TRY(hipGetLastError());
@@ -1492,6 +1636,8 @@ int pp_reset_kernel_ms(pp_handle h)
 void* pp_device_ptr(pp_handle h, int which, size_t* bytes)
 {
     if (!h) return nullptr;
+    if (flush_group(h)) return nullptr;                   // the buffers of the last tick: its group's launches are enqueued
+
     const size_t ns = (size_t)h->caps.max_scenes;
     void* p = nullptr; size_t b = 0;
     switch (which) {
@@ -1506,13 +1652,28 @@ void* pp_device_ptr(pp_handle h, int which, size_t* bytes)
     case PP_BUF_GRID: p = nullptr; b = 0; break;      // no occupancy grid is kept after a tick (the search builds it in LDS): use pp_get_grid
     case PP_BUF_PATH: p = h->d_path[h->path_set]; b = ns * (size_t)h->max_path0 * 4; break;
     case PP_BUF_LANE_ATTR: p = h->d_attr; b = (size_t)h->caps.max_lane_pts_total; break;
-    case PP_BUF_ORDER: p = h->d_order[h->parity]; b = ns * (size_t)h->caps.order_cap * 4; break;
+    case PP_BUF_ORDER: p = h->d_order[h->parity] ? h->d_order[h->parity] + (size_t)h->item_off * h->caps.order_cap : nullptr; b = ns * (size_t)h->caps.order_cap * 4; break;
     default: break;
     }
     if (bytes) *bytes = b;
     return p;
 }
-void* pp_stream(pp_handle h) { return h ? (void*)h->stream : nullptr; }
+// tick-group arithmetic (pp_plan_tick), without a device: the size of a group, the tick slots a handle allocates for, ring sizes
+int pp_tick_group_size(int n_scenes, int search_slots, int gcap, int forced) { return group_size(n_scenes, search_slots, gcap, forced); }
+int pp_tick_group_cap(int max_scenes, int pipeline_min, int forced, size_t item_bytes) { return group_cap(max_scenes, pipeline_min, forced, item_bytes); }
+int pp_tick_group_const(int which)
+{
+    switch (which) {
+    case 0: return kGroupMax;
+    case 1: return kBuf;
+    case 2: return kRing;
+    case 3: return kObs;
+    case 4: return kGoutRing;
+    case 5: return kGout;
+    default: return -1;
+    }
+}
+void* pp_stream(pp_handle h) { return h && !flush_group(h) ? (void*)h->stream : nullptr; }
 
 
 size_t pp_sizeof(int which)

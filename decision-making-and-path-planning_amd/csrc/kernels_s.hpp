@@ -65,6 +65,19 @@ constexpr int kSearchSetupWavesWide = 16;                                       
 constexpr int kOrderShift = 13;                         // search-time classes of 8 Ki cycles (k_order)
 constexpr int kOrderClasses = 1024;
 
+// Tick groups: one launch of k_search / k_search_spill / k_score covers the G <= kGroupMax consecutive ticks of a group.  Work
+// item w is scene w % n of the group's tick slot w / n.  The ticks of a group read the same SceneIn records; what else belongs
+// to a tick - its obstacle snapshot, its path cells, its GridOut - lies slot after slot at a fixed stride, and the work buffers
+// of the search (closed-set spill, dense bitmaps, orders, costs, ...) are indexed by w.
+constexpr int kGroupMax = 4;
+struct TickGroup {
+    int n;                                   // scenes per tick
+    const SceneIn* in;
+    const ObPoint* obs_now; long long obs_stride;       // slot s: obs_now + s * obs_stride, ...
+    int32_t* paths; long long path_stride;
+    GridOut* gout; long long gout_stride;
+};
+
 // minimum over the 64 lanes, returned in every lane: DPP prefix-min inside each row of 16 lanes
 // (row_shr 1,2,4,8), then row_bcast:15 / row_bcast:31 carry the row results to lane 63.
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
@@ -1293,9 +1306,10 @@ __device__ __forceinline__ void publish_debug(int32_t* path, int max_path, const
 //   = 1) rasterises the dense form into gbitmaps (HBM) and is searched there - same loop, slower reads.  budget = 0 sends
 //   every scene that way (test knob).
 //   need_max: running maximum of the words a scene needed (the host sizes the next launches from it).
-//   retry_list / retry_cnt: scenes whose open list outgrew LDS (kStatusRetrySpill): searched again by k_search_spill.
+//   retry_list / retry_cnt: work items (w_base + scene) whose open list outgrew LDS (kStatusRetrySpill): searched again by k_search_spill.
+//   (Tick groups: every pointer comes offset to the scene's tick slot, see group_scene.)
 template <int K, int SW, bool SPILL>
-__device__ __forceinline__ void search_scene(const PlannerConfig& c, int scene, int order_cap, int budget, const SceneIn* __restrict__ in,
+__device__ __forceinline__ void search_scene(const PlannerConfig& c, int scene, int w_base, int order_cap, int budget, const SceneIn* __restrict__ in,
          const ObPoint* __restrict__ obs_now, uint32_t* __restrict__ gclosed, uint16_t* __restrict__ pinfo, int32_t* __restrict__ orders,
          int32_t* __restrict__ paths, GridOut* __restrict__ gout, uint32_t* __restrict__ gbitmaps, int32_t* __restrict__ cost_out,
          int32_t* __restrict__ overflow, int32_t* __restrict__ need_max, uint2* __restrict__ ospill_all, int spill_cap,
@@ -1386,7 +1400,7 @@ __device__ __forceinline__ void search_scene(const PlannerConfig& c, int scene, 
     if (!SPILL && __builtin_expect(R.status == DMPP_G_OVERFLOW && retry_cnt != nullptr && c.bucket_cap > kOpenCap, 0)) {
         // more live open-list entries than LDS holds, and the specification allows more: the scene goes on the list of
         // k_search_spill, which follows on the stream (retry_cnt is null when the handle has no spill area)
-        if (lane == 0) retry_list[atomicAdd(retry_cnt, 1)] = scene;
+        if (lane == 0) retry_list[atomicAdd(retry_cnt, 1)] = w_base + scene;
     }
     (void)t_setup;
     if (lane == 0) {
@@ -1402,19 +1416,24 @@ __device__ __forceinline__ void search_scene(const PlannerConfig& c, int scene, 
 #endif
 template <int K, int SW>
 __global__ void __launch_bounds__(SW * DMPP_WAVE) DMPP_SEARCH_ATTR
-k_search(PlannerConfig c, int n_scenes, int order_cap, int budget, const int32_t* __restrict__ perm, const SceneIn* __restrict__ in,
-         const ObPoint* __restrict__ obs_now, uint32_t* __restrict__ gclosed, uint16_t* __restrict__ pinfo, int32_t* __restrict__ orders,
-         int32_t* __restrict__ paths, GridOut* __restrict__ gout, uint32_t* __restrict__ gbitmaps, int32_t* __restrict__ cost_out,
+k_search(PlannerConfig c, int n_items, const TickGroup g, int order_cap, int budget, const int32_t* __restrict__ perm,
+         uint32_t* __restrict__ gclosed, uint16_t* __restrict__ pinfo, int32_t* __restrict__ orders,
+         uint32_t* __restrict__ gbitmaps, int32_t* __restrict__ cost_out,
          int32_t* __restrict__ overflow, int32_t* __restrict__ need_max, uint2* __restrict__ ospill_all, int spill_cap,
          int32_t* __restrict__ retry_list, int32_t* __restrict__ retry_cnt)
 {
     // static LDS: SearchLds; dynamic LDS: [line metas of both views | `budget` data words per view]
     extern __shared__ __align__(16) unsigned char smem_raw[];
     __shared__ SearchLds<closed_log_of<K>()> L;
-    if ((int)blockIdx.x >= n_scenes) return;
-    const int scene = perm ? perm[blockIdx.x] : (int)blockIdx.x;      // heaviest scenes first (k_order) when they do not all fit at once
-    search_scene<K, SW, false>(c, scene, order_cap, budget, in, obs_now, gclosed, pinfo, orders, paths, gout, gbitmaps, cost_out, overflow, need_max,
-                               ospill_all, spill_cap, retry_list, retry_cnt, L, smem_raw);
+    if ((int)blockIdx.x >= n_items) return;
+    const int w = perm ? perm[blockIdx.x] : (int)blockIdx.x;      // heaviest work items first (k_order) when they do not all fit at once
+    if ((unsigned)w >= (unsigned)n_items) return;                  // (a launch order is a permutation of 0 .. n_items - 1: never taken)
+    const int slot = w / g.n, scene = w - slot * g.n;
+    const size_t base = (size_t)slot * g.n, N = (size_t)c.grid_w * c.grid_h;       // the slot's first work item
+    search_scene<K, SW, false>(c, scene, (int)base, order_cap, budget, g.in, g.obs_now + slot * g.obs_stride, gclosed + base * (N >> 5), pinfo + base * N,
+                               orders ? orders + base * order_cap : nullptr, g.paths + slot * g.path_stride, g.gout + slot * g.gout_stride,
+                               gbitmaps + base * 2 * (N >> 5), cost_out + base, overflow + base, need_max,
+                               ospill_all ? ospill_all + base * spill_cap : nullptr, spill_cap, retry_list, retry_cnt, L, smem_raw);
 }
 
 // The scenes the search kernel put on the retry list (their open list outgrew LDS), once more with the spill area.  Launched
@@ -1425,19 +1444,23 @@ k_search(PlannerConfig c, int n_scenes, int order_cap, int budget, const int32_t
 // common loop: -5 %), and the second attempt as a call from the kernel's tail (scratch + 142 VGPRs: -10 %).
 template <int K>
 __global__ void __launch_bounds__(kSearchBlock)
-k_search_spill(PlannerConfig c, int n_scenes, int order_cap, int budget, const SceneIn* __restrict__ in,
-         const ObPoint* __restrict__ obs_now, uint32_t* __restrict__ gclosed, uint16_t* __restrict__ pinfo, int32_t* __restrict__ orders,
-         int32_t* __restrict__ paths, GridOut* __restrict__ gout, uint32_t* __restrict__ gbitmaps, int32_t* __restrict__ cost_out,
+k_search_spill(PlannerConfig c, int n_items, const TickGroup g, int order_cap, int budget,
+         uint32_t* __restrict__ gclosed, uint16_t* __restrict__ pinfo, int32_t* __restrict__ orders,
+         uint32_t* __restrict__ gbitmaps, int32_t* __restrict__ cost_out,
          int32_t* __restrict__ overflow, int32_t* __restrict__ need_max, uint2* __restrict__ ospill_all, int spill_cap,
          const int32_t* __restrict__ retry_list, const int32_t* __restrict__ retry_cnt)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     __shared__ SearchLds<closed_log_of<K>()> L;
-    const int cnt = min(*retry_cnt, n_scenes);
+    const int cnt = min(*retry_cnt, n_items);
     for (int i = (int)blockIdx.x; i < cnt; i += (int)gridDim.x) {      // (a handful of workgroups: nearly always there is nothing to do, and they must not queue for LDS behind the searches)
-        const int scene = retry_list[i];
-        search_scene<K, kSearchSetupWaves, true>(c, scene, order_cap, budget, in, obs_now, gclosed, pinfo, orders, paths, gout, gbitmaps, cost_out, overflow,
-                                                 need_max, ospill_all, spill_cap, nullptr, nullptr, L, smem_raw);
+        const int w = retry_list[i];
+        const int slot = w / g.n, scene = w - slot * g.n;
+        const size_t base = (size_t)slot * g.n, N = (size_t)c.grid_w * c.grid_h;
+        search_scene<K, kSearchSetupWaves, true>(c, scene, (int)base, order_cap, budget, g.in, g.obs_now + slot * g.obs_stride, gclosed + base * (N >> 5),
+                                                 pinfo + base * N, orders ? orders + base * order_cap : nullptr, g.paths + slot * g.path_stride,
+                                                 g.gout + slot * g.gout_stride, gbitmaps + base * 2 * (N >> 5), cost_out + base, overflow + base,
+                                                 need_max, ospill_all ? ospill_all + base * spill_cap : nullptr, spill_cap, nullptr, nullptr, L, smem_raw);
         __syncthreads();                       // every wave is done with this scene's LDS
     }
 }

@@ -233,6 +233,14 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo */
 size_t pp_sizeof(int which);
+/* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
+ * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);
+ * forced > 0: that many (env DMPP_TICK_GROUP).  pp_tick_group_cap: the tick slots a handle allocates for.
+ * pp_tick_group_const: 0 slots per group at most, 1 search sets, 2 / 3 group positions / sets of the obstacle snapshot,
+ * 4 / 5 group positions / sets of GridOut.  No device needed. */
+int pp_tick_group_size(int n_scenes, int search_slots, int gcap, int forced);
+int pp_tick_group_cap(int max_scenes, int pipeline_min, int forced, size_t item_bytes);
+int pp_tick_group_const(int which);
 /* The search keeps a scene's obstacle bitmaps sparse in LDS; a launch gives every scene `lds_budget_words` words per view
  * (sized from what the densest scene of an earlier tick needed) and a scene that needs more is searched on dense bitmaps
  * in HBM instead.  After a tick: the budget of that tick, the words the densest scene seen so far needed, and how many
