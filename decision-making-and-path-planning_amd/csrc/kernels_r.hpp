@@ -882,7 +882,8 @@ k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
                 if (tid == 0) {
                     if (f >= 0) {
                         sh.aim_far.Aim_point.x = refpath[f].x; sh.aim_far.Aim_point.y = refpath[f].y;
-                        if (f < n - 4) sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[f], refpath[f + 2]);
+                        // :517 is unsigned: n < 4 takes the first branch; f + 2 clamped to n - 1 (n = 3, f = 1 reads refpath[3])
+                        if (n < 4 || f < n - 4) sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[f], refpath[min(f + 2, n - 1)]);
                         else sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[f - 2 < 0 ? 0 : f - 2], refpath[f]);
                         sh.aim_far.Aim_id = f;
                     } else {

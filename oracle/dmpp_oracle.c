@@ -105,6 +105,8 @@ static void aim_set(AimPoint* a, GlobalPoint3D p, int id) { a->Aim_point = p; a-
 
 /* clamp used only where the reference indexes past an array (fences) */
 static int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+static int imin(int a, int b) { return a < b ? a : b; }
+static int imax(int a, int b) { return a > b ? a : b; }
 
 /* Planning.cpp:303-583.  planning_MapData[road][lane] -> LaneView slices of lane_pool;
  * faraim/nearaim are the members written by Calculate_aim_dis (Planning.cpp:118). */
@@ -201,8 +203,10 @@ void orc_SearchAimPoint(const PlannerConfig* c, const SceneIn* in, const Decisio
                 if ((sum_dis - 4) > faraim_dis) {                 /* :512 */
                     aimpoint_far->Aim_point.x = refpath[i].x;
                     aimpoint_far->Aim_point.y = refpath[i].y;
-                    if (i < n - 4) {                              /* :517 */
-                        aimpoint_far->Aim_point.dir = orc_GetRoadAngle(c, refpath[i], refpath[i + 2]);
+                    /* :517 compares unsigned: for n < 4 the right side wraps and the first branch is taken.
+                     * Fence: i + 2 clamped to n - 1 (n = 3, i = 1 reads refpath[3]). */
+                    if (n < 4 || i < n - 4) {
+                        aimpoint_far->Aim_point.dir = orc_GetRoadAngle(c, refpath[i], refpath[imin(i + 2, n - 1)]);
                     } else {
                         int im2 = i - 2 < 0 ? 0 : i - 2;          /* fence: i-2 < 0 */
                         aimpoint_far->Aim_point.dir = orc_GetRoadAngle(c, refpath[im2], refpath[i]);
@@ -440,9 +444,6 @@ typedef struct DecScratch {
     GlobalPoint2D refpath[DMPP_MAX_REFPATH];
     int n_ref;
 } DecScratch;
-
-static int imin(int a, int b) { return a < b ? a : b; }
-static int imax(int a, int b) { return a > b ? a : b; }
 
 /* forward / rearward slices, Decision.cpp:581-596 (and :611-622, :649-660 for the side lanes) */
 static int load_front(const PlannerConfig* c, const GlobalPoint3D* lane, int IdSum, int Id, GlobalPoint2D* out)

@@ -2,8 +2,9 @@
 
 Three parallel straight lanes along +x at 0.5 m spacing (so every arc length is an exact binary
 fraction), the ego on point 50 of its lane, obstacles placed on lane points so that their
-longitudinal distances are known without running any code.  Used by the CPU known-answer tests
-(oracle) and by the GPU parity tests (device vs oracle)."""
+longitudinal distances are known without running any code.  Used by the known-answer tests
+(tests/test_lanechange_kat.py, tests/test_reference_kat.py) and by the GPU parity tests (device vs oracle).
+make_junction_scene builds the same straight run for pos 1 / 2 with a junction polyline."""
 import numpy as np
 
 LANE_W = 3.75
@@ -12,7 +13,8 @@ EGO_ID = 50
 
 def make_scene(dm, cfg, lane_num=2, lane_sum=3, map_attr=1, out_lanes=(2,), period=100.0,
                attr_ahead=None, attr_run=250, obstacles=()):
-    """obstacles: iterable of (lane_no, metres_ahead) — lane_no is 1-based, negative metres = behind the ego.
+    """obstacles: iterable of (lane_no, metres_ahead[, metres_left]) — lane_no is 1-based, negative metres = behind the
+    ego, metres_left = lateral offset from the lane centre (world +y; default 0).
     attr_ahead: lanechg_attribute of the `attr_run` points after the ego point (default: map_attr)."""
     n_obs = len(obstacles)
     sc = dm.gen_scenes(cfg, 0, 1, n_obs, junction_every=0)
@@ -46,9 +48,9 @@ def make_scene(dm, cfg, lane_num=2, lane_sum=3, map_attr=1, out_lanes=(2,), peri
     a[EGO_ID + 1:n] = 0
     a[EGO_ID + 1:min(n, EGO_ID + 1 + attr_run)] = map_attr if attr_ahead is None else attr_ahead
     si["obs_off"], si["obs_n"] = 0, n_obs
-    for j, (lane_no, ahead) in enumerate(obstacles):
+    for j, (lane_no, ahead, *left) in enumerate(obstacles):
         o = sc["obs_pool"][j]
-        o["x"], o["y"], o["type"], o["radius"] = x[EGO_ID] + ahead, lane_y[lane_no], 0, 0.5
+        o["x"], o["y"], o["type"], o["radius"] = x[EGO_ID] + ahead, lane_y[lane_no] + (left[0] if left else 0.0), 0, 0.5
     sc["mot_pool"][:] = 0
     si["goal"]["x"], si["goal"]["y"] = x[EGO_ID] + 20.0, lane_y[lane_num]
     si["grid_origin"]["x"], si["grid_origin"]["y"] = x[EGO_ID] - 5.0, lane_y[lane_num] - 16.0
@@ -116,3 +118,34 @@ SCENARIOS = [
     dict(lane_num=2, map_attr=1, out_lanes=(2,), period=100.0, obstacles=[(2, 25.0)]),
     dict(lane_num=2, map_attr=1, out_lanes=(), period=700.0),
 ]
+
+
+def set_polyline(dm, sc, pts):
+    """The scene's refpath-pool slice (the junction polyline decision_InterMapData[...], or DecisionOut.refpath when the
+    decision stage is off) = `pts`, a list of (x, y); the ego stays where it is."""
+    n = len(pts)
+    assert n <= dm.GEN_REF_PTS
+    pool = sc["ref_pool"]
+    pool[:n]["x"], pool[:n]["y"] = [p[0] for p in pts], [p[1] for p in pts]
+    si = sc["scene_in"]
+    si["ref_off"], si["ref_n"] = 0, n
+
+
+def make_junction_scene(dm, cfg, pos, n_inter=40, obstacles=()):
+    """A scene at pos 1 (before the junction) or pos 2 (in it) on a straight run along +x at 0.5 m spacing, ego at x = 125,
+    y = 200.  pos 1: the ego is on point 50 of its lane (lane points x = 100 + 0.5 k), the junction polyline continues after
+    the lane end.  pos 2: the ego is on point 0 of the junction polyline (x = 125 + 0.5 k, n_inter points), the exit lane
+    follows it (x = 125 + 0.5 (n_inter + k)).  Either way the front refpath of Decision.cpp:352-367 / :438-452 is a straight
+    line from the ego with every point 0.5 m further.  obstacles: (metres_ahead, metres_left)."""
+    sc = make_scene(dm, cfg, lane_num=1, lane_sum=1, map_attr=0, obstacles=[(1, a, l) for a, l in obstacles])
+    n = dm.GEN_LANE_PTS
+    si = sc["scene_in"]
+    y = 200.0
+    if pos == 1:
+        set_polyline(dm, sc, [(100.0 + 0.5 * (n + k), y) for k in range(n_inter)])
+    else:
+        set_polyline(dm, sc, [(125.0 + 0.5 * k, y) for k in range(n_inter)])
+        sc["lane_pool"][:n]["x"] = 125.0 + 0.5 * (n_inter + np.arange(n))
+        si["loc"]["id"][:] = 0
+    si["loc"]["pos"] = pos
+    return sc
