@@ -82,6 +82,10 @@ PlannerConfig = _dt([("ROAD_FARAIM_MAX", f8), ("ROAD_FARAIM_MIN", f8), ("PRE_INT
 PlannerCaps = _dt([("max_scenes", i4), ("max_obs_total", i4), ("max_lane_pts_total", i4), ("max_ref_pts_total", i4),
                    ("order_cap", i4), ("_pad", i4)])
 
+EgoModel = _dt([("dt", f8), ("max_acc", f8), ("max_dec", f8), ("window", i4), ("_pad", i4)])
+EgoTrace = _dt([("pose", GlobalPoint3D), ("velocity", f8), ("id_cur", i4), ("lane_num", i4), ("flags", i4), ("_pad", i4)])
+EGO_PATH_END, EGO_BAD_PATH, EGO_LANE_END, EGO_OFF_GRID = 1, 2, 4, 8      # sticky rollout flags (DMPP_EGO_*)
+
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
 
@@ -167,6 +171,15 @@ def load_library(path=None):
     lib.pp_wait_tick.argtypes = [vp, C.c_longlong, C.POINTER(ci)]
     lib.pp_tick_id.argtypes = [vp]
     lib.pp_tick_id.restype = C.c_longlong
+    # closed-loop rollout.  An OLDER build named through DMPP_LIB / `path` (A/B measurements against a parent commit) may lack
+    # these; the package's own library must have them.
+    rollout = hasattr(lib, "pp_advance_async") or path == LIB_PATH
+    if rollout:
+        lib.pp_default_ego_model.argtypes = [vp]
+        lib.pp_default_ego_model.restype = None
+        lib.pp_advance_async.argtypes = [vp, vp, vp]
+        lib.pp_rollout.argtypes = [vp, ci, vp, vp, C.POINTER(C.c_longlong)]
+        lib.pp_get_ego_flags.argtypes = [vp, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -176,6 +189,9 @@ def load_library(path=None):
     if lib.pp_sizeof(17) != C.sizeof(MapDesc):
         raise PlannerError(f"ABI mismatch for MapDesc: C {lib.pp_sizeof(17)} B, binding {C.sizeof(MapDesc)} B")
     for which, dt in enumerate(_SIZEOF_ORDER):
+        if lib.pp_sizeof(which) != dt.itemsize:
+            raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
+    for which, dt in ((19, EgoModel), (20, EgoTrace)) if rollout else ():
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -201,6 +217,13 @@ def default_config(grid_w=512, grid_h=None):
     cfg = np.zeros(1, PlannerConfig)
     load_library().pp_default_config(_ptr(cfg), grid_w, grid_h or grid_w)
     return cfg
+
+
+def default_ego_model():
+    """EgoModel record of the closed-loop rollout (pp_default_ego_model): dt, acceleration limits, id search window."""
+    m = np.zeros(1, EgoModel)
+    load_library().pp_default_ego_model(_ptr(m))
+    return m
 
 
 def gen_scenes(cfg, first_scene, n_scenes, n_obs, junction_every=8):
@@ -341,6 +364,30 @@ class Planner:
         if n_obs_total is None:
             n_obs_total = len(obs_pool) if obs_pool is not None else 0
         _check(self.lib.pp_update_async(self.h, self.n, _ptr(scene_in), _ptr(obs_pool), _ptr(mot_pool), int(n_obs_total)))
+
+    # ---- closed-loop rollout: the egos follow their own plans on the device ---------------
+    def advance_async(self, model=None, trace=None):
+        """pp_advance_async: the SceneIn records of the next tick from the last tick's plan.  `trace`: EgoTrace array of self.n
+        records in pinned memory (or a device address), written by the kernel; it is complete after the next sync / wait_tick."""
+        m = default_ego_model() if model is None else np.array(model, EgoModel).reshape(1).copy()
+        _check(self.lib.pp_advance_async(self.h, _ptr(m), _ptr(trace)))
+
+    def rollout(self, n_ticks, model=None, trace=False):
+        """pp_rollout: n_ticks times (advance, tick) with no host wait.  Returns the id of the last tick, or - with trace=True -
+        (that id, a pinned EgoTrace array of shape (n_ticks, self.n)): row t is complete once the ticks have finished (sync())."""
+        m = default_ego_model() if model is None else np.array(model, EgoModel).reshape(1).copy()
+        tr = pinned_empty(max(n_ticks * self.n, 1), EgoTrace) if trace else None
+        t = C.c_longlong()
+        _check(self.lib.pp_rollout(self.h, int(n_ticks), _ptr(m), _ptr(tr), C.byref(t)))
+        if trace:
+            return t.value, tr[:n_ticks * self.n].reshape(n_ticks, self.n)
+        return t.value
+
+    def ego_flags(self):
+        """pp_get_ego_flags: the sticky EGO_* flag word of every scene after the last advance (host wait)."""
+        out = np.zeros(self.n, np.int32)
+        _check(self.lib.pp_get_ego_flags(self.h, _ptr(out), self.n))
+        return out
 
     def fetch_async(self, plan=None, grid=None):
         """pp_fetch_async of the last enqueued tick into `plan` / `grid` (pinned arrays of self.n records). Returns the tick id."""

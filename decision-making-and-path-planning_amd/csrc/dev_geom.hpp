@@ -46,6 +46,17 @@ __device__ __forceinline__ double shfl_f64(double v, int src)
     return __hiloint2double(hi, lo);
 }
 
+// (value, index) minimum over the wave that keeps the FIRST minimum: ties go to the lower index, idx < 0 means "none" and never
+// wins, a value is compared with the strict < of the sequential loop it stands for.  Every lane ends with the result.
+__device__ __forceinline__ void wave_first_min(double& v, int& idx)
+{
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1) {
+        const double o_d = shfl_xor_f64(v, sft); const int o_i = __shfl_xor(idx, sft, 64);
+        if (o_i >= 0 && (idx < 0 || o_d < v || (o_d == v && o_i < idx))) { v = o_d; idx = o_i; }
+    }
+}
+
 // Planning.h:54
 __device__ __forceinline__ int Sgn(double a) { return a > 0 ? 1 : -1; }
 

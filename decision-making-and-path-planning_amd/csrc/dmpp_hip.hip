@@ -13,6 +13,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <cmath>
 #include <string>
 #include <cstdlib>
 #include <vector>
@@ -20,6 +21,7 @@
 #include <algorithm>
 #include "../../include/dmpp_planner.h"
 #include "kernels_r.hpp"
+#include "kernels_a.hpp"
 #include "kernels_g.hpp"
 
 namespace {
@@ -167,6 +169,11 @@ struct pp_planner {
     hipEvent_t ev_done_p[kDone] = {}, ev_done_g[kDone] = {}; long long done_tick[kDone]; bool done_p_rec[kDone] = {}, done_g_rec[kDone] = {};
     int32_t* h_bad = nullptr;    // pinned, [kDone]: poisoned scenes of the tick (copied down with its PlanOut)
     long long tick_seq = 0;      // ticks enqueued so far on this handle (the id of the last one)
+    // closed-loop rollout (allocated by the first pp_advance_async): the sticky DMPP_EGO_* word of every scene; ev_adv follows the
+    // last k_advance_egos; staged_by_advance: the staged input set was produced on the device; set_tick: tick_seq when the
+    // resident scenes were last set (an advance needs a tick of THESE scenes behind it)
+    int32_t* d_ego_flags = nullptr; hipEvent_t ev_adv = nullptr; bool adv_recorded = false, staged_by_advance = false;
+    long long set_tick = 0;
     TickRec last_rec = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
@@ -228,6 +235,7 @@ void note_current_set(pp_planner* h)          // after a pp_set_* call changed w
     InputSet& I = h->in_sets[h->in_cur];
     I.have_motion = h->have_motion; I.n_obs_total = h->n_obs_total;
     h->in_staged = -1;                        // an update staged before it is superseded
+    h->staged_by_advance = false; h->set_tick = h->tick_seq;
 }
 
 // Issues the copies of the pending downloads whose kernels have finished.  force_tick: that tick's copies are issued whatever
@@ -590,6 +598,8 @@ int pp_destroy(pp_handle h)
     for (auto e : h->sync_events) (void)hipEventDestroy(e);
     for (auto& r : h->inflight) { (void)hipEventDestroy(r.ev_front); if (r.ev_tail) (void)hipEventDestroy(r.ev_tail); }
     if (h->h_bad) (void)hipHostFree(h->h_bad);
+    if (h->d_ego_flags) (void)hipFree(h->d_ego_flags);
+    if (h->ev_adv) (void)hipEventDestroy(h->ev_adv);
     void* bufs[] = { h->d_lane, h->d_attr, h->d_ref, h->d_state,
                      h->d_dec_ref, h->d_grid, h->d_scratch, h->d_map_first, h->d_map_lanes, h->d_map_width, h->d_map_junc, h->d_map_bad, h->d_bad,
                      h->d_gridbad };
@@ -630,6 +640,15 @@ int pp_set_config(pp_handle h, const PlannerConfig* cfg)
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->cfg = *cfg;
     return setup_grid_launch(h);
+}
+
+// New resident scenes: the rollout flags of the old ones go (behind the last advance; the caller's host wait follows).
+static int reset_ego_flags(pp_handle h)
+{
+    if (!h->d_ego_flags) return PP_OK;
+    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    HIP_TRY(hipMemsetAsync(h->d_ego_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), h->stream));
+    return PP_OK;
 }
 
 // Slices of the resident SceneIn records against the resident pools (k_validate_scenes); syncs the handle's stream.
@@ -677,6 +696,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
     }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->resident_mode = 0; note_current_set(h);
+    { int r = reset_ego_flags(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_scenes");     // syncs: the caller may reuse its buffers
 }
 
@@ -756,6 +776,7 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total;
     h->resident_mode = 1; note_current_set(h);
+    { int r = reset_ego_flags(h); if (r) return r; }
     if (bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, "pp_set_egos: " + std::to_string(bad) + " scene(s) name a road or lane outside the map"); }
     return validate_resident(h, n_scenes, "pp_set_egos");       // the obstacle slices are still the caller's
 }
@@ -764,6 +785,11 @@ int pp_get_scene_in(pp_handle h, SceneIn* out, int n)
 {
     if (!h || !out) return fail(PP_ERR_ARG, "null argument");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
+    if (h->in_staged >= 0 && h->staged_by_advance) {      // the records the advance produced for the next tick exist only on the device
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));
+        return fetch(h, out, h->in_sets[h->in_staged].d_in, (size_t)n * sizeof(SceneIn));
+    }
     return fetch(h, out, h->d_in, (size_t)n * sizeof(SceneIn));
 }
 
@@ -779,6 +805,7 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
     h->resident_mode = 0; note_current_set(h);
+    { int r = reset_ego_flags(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_n_scenes");
 }
 
@@ -912,7 +939,7 @@ int pp_plan_tick(pp_handle h)
     const bool open = h->grp_ticks == 0;
     // streamed inputs: the update staged by pp_update_async becomes the set this tick (and the following ones) read
     bool adopted = false;
-    if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; adopted = true; }
+    if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; h->staged_by_advance = false; adopted = true; }
     if (open) {
         h->grp_p_prev = h->parity;
         if (c.grid_stage) { h->parity = (h->parity + 1) % kBuf; h->gring = (h->gring + 1) % kGoutRing; }
@@ -1247,6 +1274,8 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     if (!in && !obs_pool) return fail(PP_ERR_ARG, "nothing to update");
     if (obs_pool && (n_obs_total < 0 || n_obs_total > h->caps.max_obs_total)) return fail(PP_ERR_CAPACITY, "obstacle pool larger than caps.max_obs_total");
     if (!obs_pool && mot_pool) return fail(PP_ERR_ARG, "a motion pool without its obstacle pool");
+    if (in && h->in_staged >= 0 && h->staged_by_advance)
+        return fail(PP_ERR_STATE, "pp_update_async: the SceneIn records of the next tick were already produced by pp_advance_async");
     HIP_TRY(hipSetDevice(h->device));
     { int r = flush_group(h); if (r) return r; }          // the ticks before streaming began are launched as they stand
     { int r = ensure_streaming(h); if (r) return r; }
@@ -1276,11 +1305,17 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
             if (have_motion) HIP_TRY(hipMemcpyAsync(I.d_mot, P.d_mot, (size_t)n_obs * sizeof(ObMotion), hipMemcpyDeviceToDevice, su));
         }
     }
-    // the count of poisoned scenes is written by the two kernels below straight into pinned host memory (the slot of the tick
-    // that will adopt this update; zeroed here by the host: that tick is not enqueued yet, nothing else writes the slot) - no
-    // memset and no copy command on the upload stream
+    // The count of poisoned scenes is written by the two kernels below straight into pinned host memory: the slot of the tick
+    // that will adopt this update - no memset and no copy command on the upload stream.
+    // OWNER RULE of h_bad[slot of tick T + 1]: the HOST owns the slot while nothing is staged for T + 1 (no kernel that counts
+    // into it has been enqueued: it zeroes it here, at the first update or advance staged for T + 1, or in pp_plan_tick when
+    // T + 1 adopts nothing).  From the first staged update until pp_plan_tick adopts it the UPLOAD STREAM owns the slot:
+    // k_resolve_map / k_sanitise_scenes add to it in stream order, and a repeated update that brings new SceneIn records
+    // restarts the count with k_zero_word on that stream - behind the kernels of the earlier update, which a store from the
+    // host could overtake.  After the adoption nobody writes it; pp_wait_tick reads it behind the tick's downloads.
     int32_t* bad_slot = &h->h_bad[(h->tick_seq + 1) % kDone];
-    if (in || s != h->in_staged) *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;      // (a second, obstacles-only update of a staged set keeps the count of the first)
+    if (s != h->in_staged) *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;
+    else if (in) hipLaunchKernelGGL(dmpp::k_zero_word, dim3(1), dim3(1), 0, su, bad_slot);      // (a second, obstacles-only update of a staged set keeps the count of the first)
     const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
     if (h->resident_mode == 1 && in)      // egos on the resident map: lane views and junction slices from road / lane numbers
         hipLaunchKernelGGL(dmpp::k_resolve_map, grid, block, 0, su, n, I.d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
@@ -1291,6 +1326,85 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     I.up_recorded = true; I.have_motion = have_motion; I.n_obs_total = n_obs;
     h->in_staged = s;
     return PP_OK;
+}
+
+// Closed-loop rollout: the SceneIn records of the next tick are produced on the device.  The same staging as
+// pp_update_async(h, n, in, NULL, NULL, 0) - next input set, obstacles and motion carried over, lane views and slice check behind
+// it, the tick that adopts it waits for ev_up - with k_advance_egos in the place of the copy.  The kernel reads what the last
+// tick's Planning kernel wrote (PlanOut, SceneState): the upload stream waits for that tick's front-chain event, not for its
+// search; the next tick's front chain, the only writer of SceneState, waits for ev_up in turn.
+int pp_advance_async(pp_handle h, const EgoModel* m, EgoTrace* trace)
+{
+    if (!h || !m) return fail(PP_ERR_ARG, "null argument");
+    if (!(m->dt > 0) || !std::isfinite(m->dt) || !(m->max_acc >= 0) || !std::isfinite(m->max_acc) || !(m->max_dec >= 0) || !std::isfinite(m->max_dec) ||
+        m->window < 1 || m->window > (1 << 20))
+        return fail(PP_ERR_ARG, "pp_advance_async: the model needs a finite dt > 0, finite max_acc / max_dec >= 0 and a window of 1 .. 2^20 points");
+    if (h->n_scenes <= 0 || h->tick_seq <= h->set_tick)
+        return fail(PP_ERR_STATE, "pp_advance_async: no tick has been enqueued for the resident scenes (the egos follow the plan of their last tick)");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_advance_async: an update is already staged for the next tick");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = flush_group(h); if (r) return r; }
+    { int r = ensure_streaming(h); if (r) return r; }          // (a tick enqueued before streaming began has finished behind this: one host wait per handle)
+    { int r = pump_fetches(h); if (r) return r; }
+    { int r = prune_inflight(h); if (r) return r; }
+    hipStream_t su = h->stream_up;
+    if (!h->d_ego_flags) {
+        int r = dmalloc(&h->d_ego_flags, (size_t)h->caps.max_scenes); if (r) return r;
+        HIP_TRY(hipMemsetAsync(h->d_ego_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), su));
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_adv, hipEventDisableTiming));
+    }
+    const InputSet& Cur = h->in_sets[h->in_cur];
+    const int s = (h->in_cur + 1) % kIn, n = h->n_scenes;
+    InputSet& I = h->in_sets[s];
+    for (const TickRec& r : h->inflight) if (r.in_set == s) {      // the ticks that still read set s (a whole ring ago)
+        HIP_TRY(hipStreamWaitEvent(su, r.ev_front, 0));
+        if (r.ev_tail) HIP_TRY(hipStreamWaitEvent(su, r.ev_tail, 0));
+    }
+    if (h->last_rec.tick == h->tick_seq && h->last_rec.ev_front) HIP_TRY(hipStreamWaitEvent(su, h->last_rec.ev_front, 0));
+    const int n_obs = Cur.n_obs_total; const bool have_motion = Cur.have_motion;
+    if (n_obs) {
+        HIP_TRY(hipMemcpyAsync(I.d_obs, Cur.d_obs, (size_t)n_obs * sizeof(ObPoint), hipMemcpyDeviceToDevice, su));
+        if (have_motion) HIP_TRY(hipMemcpyAsync(I.d_mot, Cur.d_mot, (size_t)n_obs * sizeof(ObMotion), hipMemcpyDeviceToDevice, su));
+    }
+    int32_t* bad_slot = &h->h_bad[(h->tick_seq + 1) % kDone];
+    *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;          // nothing is staged for that tick: the host owns the slot (owner rule in pp_update_async)
+    hipLaunchKernelGGL(dmpp::k_advance_egos, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
+                       h->cfg, *m, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
+    const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
+    if (h->resident_mode == 1)
+        hipLaunchKernelGGL(dmpp::k_resolve_map, grid, block, 0, su, n, I.d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
+                           h->map_junctions, h->d_map_junc, bad_slot);
+    hipLaunchKernelGGL(dmpp::k_sanitise_scenes, grid, block, 0, su, n, I.d_in, n_obs, h->n_lane_pts, h->n_ref_pts, bad_slot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(I.ev_up, su));
+    HIP_TRY(hipEventRecord(h->ev_adv, su)); h->adv_recorded = true;
+    I.up_recorded = true; I.have_motion = have_motion; I.n_obs_total = n_obs;
+    h->in_staged = s; h->staged_by_advance = true;
+    return PP_OK;
+}
+
+int pp_rollout(pp_handle h, int n_ticks, const EgoModel* m, EgoTrace* trace, long long* last_tick_id)
+{
+    if (!h || !m) return fail(PP_ERR_ARG, "null argument");
+    if (n_ticks < 0) return fail(PP_ERR_ARG, "pp_rollout: negative tick count");
+    if (h->n_scenes <= 0) return fail(PP_ERR_STATE, "pp_rollout: no resident scenes");
+    if (h->tick_seq <= h->set_tick) { int r = pp_plan_tick(h); if (r) return r; }      // the plan the first advance follows
+    for (int t = 0; t < n_ticks; t++) {
+        int r = pp_advance_async(h, m, trace ? trace + (size_t)t * (size_t)h->n_scenes : nullptr); if (r) return r;
+        r = pp_plan_tick(h); if (r) return r;
+    }
+    if (last_tick_id) *last_tick_id = h->tick_seq;
+    return PP_OK;
+}
+
+int pp_get_ego_flags(pp_handle h, int32_t* flags, int n)
+{
+    if (!h || !flags) return fail(PP_ERR_ARG, "null argument");
+    if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
+    if (!h->d_ego_flags) { std::memset(flags, 0, (size_t)n * sizeof(int32_t)); return PP_OK; }
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    return fetch(h, flags, h->d_ego_flags, (size_t)n * sizeof(int32_t));
 }
 
 static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id)
@@ -1365,7 +1479,7 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
     HIP_TRY(hipSetDevice(h->device));
     const int max_obs = std::min(PP_IO_MAX_OBS, h->caps.max_obs_total), max_ref = std::min(DMPP_MAX_REFPATH, h->caps.max_ref_pts_total);
     { int r = flush_group(h); if (r) return r; }          // (k_io_in rewrites the inputs an open group's searches read)
-    h->in_staged = -1;
+    h->in_staged = -1; h->staged_by_advance = false;
     hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->d_in, h->d_state, h->d_obs, h->d_ref);
     HIP_TRY(hipGetLastError());
     h->n_obs_total = std::min(std::max((int)io->n_obs, 0), max_obs); h->have_motion = false;
@@ -1685,6 +1799,7 @@ size_t pp_sizeof(int which)
     case 9: return sizeof(LocationOut); case 10: return sizeof(DecisionOutPod); case 11: return sizeof(LaneView);
     case 12: return sizeof(PlanningOut); case 13: return sizeof(PlanningStatus); case 14: return sizeof(AimPoint);
     case 15: return sizeof(MapLane); case 16: return sizeof(MapJunction); case 17: return sizeof(MapDesc); case 18: return sizeof(PpSceneIo);
+    case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace);
     default: return 0;
     }
 }

@@ -927,11 +927,7 @@ k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
         // never smaller): every lane over its four indices in order, then a (value, index) reduction over the wave
         double mind = 9999; int mid = -1;
         for (int k = 0; k < 4; k++) { const int i = lane + 64 * k; if (i < DMPP_PATH_POINTS && sh.dist[i] < mind) { mind = sh.dist[i]; mid = i; } }
-#pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) {
-            const double o_d = shfl_xor_f64(mind, sft); const int o_i = __shfl_xor(mid, sft, 64);
-            if (o_i >= 0 && (mid < 0 || o_d < mind || (o_d == mind && o_i < mid))) { mind = o_d; mid = o_i; }
-        }
+        wave_first_min(mind, mid);
         if (mid < 0) mid = clampi(st.path_near_id, 0, DMPP_PATH_POINTS - 1);      // nothing within 9999 m: the member keeps its value
         const int fid = mid + 8;
         // remaining length: seg[fid] + ... + seg[198] in index order (Planning.cpp:668-671), one lane, eight reads per block

@@ -57,6 +57,14 @@ extern "C" void pp_default_config(PlannerConfig* c, int grid_w, int grid_h)
     c->dyn_dt = 0.1;
 }
 
+// the ego model of the closed-loop rollout: one tick of the obstacle model (dyn_dt), comfortable limits,
+// 32 lane points = 16 m at the generator's 0.5 m spacing (an ego at 200 km/h moves 5.6 m per tick)
+extern "C" void pp_default_ego_model(EgoModel* m)
+{
+    std::memset(m, 0, sizeof(*m));
+    m->dt = 0.1; m->max_acc = 2.0; m->max_dec = 4.0; m->window = 32;
+}
+
 extern "C" void pp_init_state(SceneState* st, int lane_num)
 {
     std::memset(st, 0, sizeof(*st));

@@ -94,7 +94,8 @@ int  pp_set_map(pp_handle h, const MapDesc* map);
  * out of its vectors). */
 int  pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in,
                  const ObPoint* obs_pool, const ObMotion* mot_pool, int n_obs_total);
-/* The resident SceneIn records (after pp_set_egos: with the derived lane views). */
+/* The resident SceneIn records (after pp_set_egos: with the derived lane views; after pp_advance_async: the records it
+ * produced for the next tick). */
 int  pp_get_scene_in(pp_handle h, SceneIn* out, int n_scenes);
 
 /* One Decision+Planning(+grid) tick for every resident scene: the bodies of
@@ -168,6 +169,30 @@ void  pp_host_free(void* p);
 int   pp_host_register(void* p, size_t bytes);
 int   pp_host_unregister(void* p);
 
+/* ---- closed-loop rollout: every ego follows its own plan, on the device -----------------------------------
+ * pp_advance_async is a DEVICE-GENERATED update: it does what pp_update_async(h, n, in, NULL, NULL, 0) does, except that the
+ * SceneIn records of the next tick are produced by one kernel on the upload stream (k_advance_egos) from the SceneIn, PlanOut
+ * and SceneState of the last tick - speed towards result.desspd (or along result.desacc) within the model's limits, position
+ * and heading along PlanOut.road_points from SceneState.path_near_id, the three lane ids of loc.id[] by a windowed nearest-
+ * point search, and (egos on a resident map only) the lane number.  Obstacles and motion are carried over; the lane views are
+ * derived again (pp_set_egos) and the slices checked (poisoning) as after any update.  After pp_set_scenes lane_num is HELD:
+ * the caller's three lane slices cannot be rotated, so a lane change is only followed after pp_set_egos.  Road and junction
+ * transitions belong to a localisation module and are out of scope: an ego that nears the end of its lane is flagged
+ * (DMPP_EGO_*) and FROZEN - later advances carry its SceneIn over unchanged, it still ticks, its flags are sticky until the
+ * next pp_set_scenes / pp_set_egos / pp_set_n_scenes.
+ * It waits - on the device - for the Planning kernel of the last tick only, never for its search, and never on the host.
+ * PP_ERR_STATE: no tick enqueued since the scenes were set, or an update already staged for the next tick (a pp_update_async
+ * with SceneIn records on top of a staged advance is PP_ERR_STATE too; an obstacles-only one is fine).
+ * trace (may be NULL; device or pinned host memory, n records): the egos the next tick plans from, written by the kernel. */
+void pp_default_ego_model(EgoModel* m);              /* dt 0.1 s, max_acc 2 m/s^2, max_dec 4 m/s^2, window 32 points */
+int  pp_advance_async(pp_handle h, const EgoModel* m, EgoTrace* trace);
+/* n_ticks times (pp_advance_async, pp_plan_tick) with no host wait, after one initial tick if none has run since the scenes
+ * were set.  trace (may be NULL): n_ticks * n records, row t = the egos of the t-th tick enqueued here.  *last_tick_id (may be
+ * NULL): the id of the last tick, for pp_fetch_async / pp_wait_tick.  Rollout ticks are streamed ticks (tick groups of 1). */
+int  pp_rollout(pp_handle h, int n_ticks, const EgoModel* m, EgoTrace* trace, long long* last_tick_id);
+/* The DMPP_EGO_* flag words after the last advance (all zero on a handle that never advanced).  Host wait. */
+int  pp_get_ego_flags(pp_handle h, int32_t* flags, int n_scenes);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -231,7 +256,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
 /* sizeof of an ABI struct, for bindings to check their mirror: 0 PlannerConfig, 1 PlannerCaps,
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
- * 17 MapDesc, 18 PpSceneIo */
+ * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

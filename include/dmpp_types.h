@@ -154,6 +154,27 @@ typedef struct SceneIn {
     GlobalPoint2D goal;       /* goal position, world */
 } SceneIn;
 
+/* ---- closed-loop rollout (build-defined: the reference has no vehicle) ----------------------
+ * pp_advance_async moves every ego along the path its last tick planned.  EgoModel: the time step and the
+ * acceleration limits of the speed ramp, and how many lane points ahead of its id a lane view is searched. */
+typedef struct EgoModel {
+    double  dt;                 /* seconds per tick                                            */
+    double  max_acc, max_dec;   /* m/s^2: most the speed rises / falls towards result.desspd   */
+    int32_t window;             /* lane points searched from each id, [id, id + window)        */
+    int32_t _pad;
+} EgoModel;                                                                 /* 32 B */
+/* sticky per-scene flags of the rollout; a scene that carries any is frozen (its SceneIn is carried over) */
+#define DMPP_EGO_PATH_END  1   /* the step reached past point 199 of the path: the ego stopped there           */
+#define DMPP_EGO_BAD_PATH  2   /* a non-finite coordinate (or step length) on the walked part: loc untouched   */
+#define DMPP_EGO_LANE_END  4   /* the current id came within `window` points of the end of its lane            */
+#define DMPP_EGO_OFF_GRID  8   /* grid stage on and the new position lies outside the scene's grid             */
+/* the ego one tick plans from, as pp_advance_async produced it */
+typedef struct EgoTrace {
+    GlobalPoint3D pose;
+    double  velocity;           /* km/h */
+    int32_t id_cur, lane_num, flags, _pad;
+} EgoTrace;                                                                 /* 48 B */
+
 /* ---- map store ------------------------------------------------------
  * planning_MapData[road][lane][id] / decision_MapData (Planning.cpp:331-356; Decision.cpp:562-578) and
  * planning_InterMapData[last_road][next_road][last_lane][next_lane][id] (Planning.cpp:342; Decision.cpp:348)

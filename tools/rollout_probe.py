@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Runs ON THE GPU BOX: ticks/s of the closed loop on the device (pp_rollout: advance + tick, no per-tick PCIe traffic) against
+the host-fed streamed loop (pp_update_async of prepared pinned inputs + pp_fetch_published_async, what a host-side vehicle
+model needs every tick), same handle size, same build, alternating.
+    python tools/rollout_probe.py [scenes] [timed ticks] [warm-up ticks] [runs]"""
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import dmpp_amd as dm
+from parity_util import move_ego
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+warm = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+runs = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+n_obs, depth = 64, 4
+cfg = dm.default_config(512)
+model = dm.default_ego_model()
+
+
+def fresh():
+    sc = dm.gen_scenes(cfg, 0, n, n_obs, junction_every=8)
+    pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=n * n_obs)
+    pl.set_scenes(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    return pl, sc
+
+
+def rollout_run():
+    pl, _ = fresh()
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    frozen = int((pl.ego_flags() != 0).sum())
+    pl.close()
+    return n * steps / dt, frozen
+
+
+def streamed_run():
+    pl, sc = fresh()
+    snaps = []
+    for _ in range(depth + 2):
+        move_ego(sc, 1)
+        snaps.append(dm.pinned_copy(sc["scene_in"]))
+    ress = [dm.pinned_empty(n, dm.PlanningOut) for _ in range(depth)]
+    shows = [dm.pinned_empty(n, dm.PlanningStatus) for _ in range(depth)]
+
+    def loop(k):
+        ids = []
+        for t in range(k):
+            if len(ids) == depth:
+                pl.wait_tick(ids.pop(0))
+            pl.update_async(snaps[t % len(snaps)])
+            pl.tick()
+            ids.append(pl.fetch_published_async(ress[t % depth], shows[t % depth]))
+        for i in ids:
+            pl.wait_tick(i)
+    loop(warm)
+    pl.sync()
+    t0 = time.perf_counter()
+    loop(steps)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    pl.close()
+    return n * steps / dt
+
+
+ro, stv = [], []
+for r in range(runs):
+    a, frozen = rollout_run()
+    b = streamed_run()
+    ro.append(a), stv.append(b)
+    print("run %d  %d scenes  rollout %.3f M ticks/s (%d scenes frozen at the end)   host-fed streamed %.3f M ticks/s" % (r, n, a / 1e6, frozen, b / 1e6), flush=True)
+print("median  %d scenes  rollout %.3f M ticks/s   host-fed streamed %.3f M ticks/s   ratio %.3f" %
+      (n, statistics.median(ro) / 1e6, statistics.median(stv) / 1e6, statistics.median(ro) / statistics.median(stv)), flush=True)
+if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout alone
+    rollout_run()
