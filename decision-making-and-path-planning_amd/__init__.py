@@ -85,6 +85,12 @@ PlannerCaps = _dt([("max_scenes", i4), ("max_obs_total", i4), ("max_lane_pts_tot
 EgoModel = _dt([("dt", f8), ("max_acc", f8), ("max_dec", f8), ("window", i4), ("_pad", i4)])
 EgoTrace = _dt([("pose", GlobalPoint3D), ("velocity", f8), ("id_cur", i4), ("lane_num", i4), ("flags", i4), ("_pad", i4)])
 EGO_PATH_END, EGO_BAD_PATH, EGO_LANE_END, EGO_OFF_GRID = 1, 2, 4, 8      # sticky rollout flags (DMPP_EGO_*)
+# rollout scorecard: one record per scene, folded on the device over the scored ticks
+RolloutScore = _dt([("min_clearance", f8), ("dist", f8), ("max_speed", f8), ("max_acc", f8), ("max_dec", f8),
+                    ("last_pos", GlobalPoint2D), ("last_speed", f8), ("n_ticks", i4), ("min_clearance_tick", i4),
+                    ("min_clearance_obs", i4), ("first_collision_tick", i4), ("n_collision_ticks", i4), ("n_replans", i4),
+                    ("n_ob_flag", i4), ("n_desacc", i4), ("behavior_ticks", i4, (8,)), ("ego_flags", i4), ("_pad", i4),
+                    ("n_grid_ticks", i4), ("n_grid_path_candidate", i4), ("grid_status_ticks", i4, (G_STATUS_COUNT,))])
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -180,6 +186,11 @@ def load_library(path=None):
         lib.pp_advance_async.argtypes = [vp, vp, vp]
         lib.pp_rollout.argtypes = [vp, ci, vp, vp, C.POINTER(C.c_longlong)]
         lib.pp_get_ego_flags.argtypes = [vp, vp, ci]
+    scorecard = hasattr(lib, "pp_score_begin") or path == LIB_PATH          # (as above: an older build may lack it)
+    if scorecard:
+        lib.pp_score_begin.argtypes = [vp, C.c_double]
+        lib.pp_score_end.argtypes = [vp]
+        lib.pp_get_rollout_score.argtypes = [vp, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -191,7 +202,7 @@ def load_library(path=None):
     for which, dt in enumerate(_SIZEOF_ORDER):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
-    for which, dt in ((19, EgoModel), (20, EgoTrace)) if rollout else ():
+    for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -387,6 +398,24 @@ class Planner:
         """pp_get_ego_flags: the sticky EGO_* flag word of every scene after the last advance (host wait)."""
         out = np.zeros(self.n, np.int32)
         _check(self.lib.pp_get_ego_flags(self.h, _ptr(out), self.n))
+        return out
+
+    # ---- rollout scorecard: per-scene totals of the scored ticks, kept on the device -----
+    def score_begin(self, dt=None):
+        """pp_score_begin: every tick from here on is folded into one RolloutScore record per scene (totals restart).
+        `dt`: seconds between ticks, the divisor of max_acc / max_dec (default: the default ego model's dt)."""
+        if dt is None:
+            dt = float(default_ego_model()["dt"][0])
+        _check(self.lib.pp_score_begin(self.h, float(dt)))
+
+    def score_end(self):
+        """pp_score_end: scoring off; the records stay readable."""
+        _check(self.lib.pp_score_end(self.h))
+
+    def rollout_score(self):
+        """pp_get_rollout_score: the RolloutScore records, the last enqueued tick included (host wait)."""
+        out = np.zeros(self.n, RolloutScore)
+        _check(self.lib.pp_get_rollout_score(self.h, _ptr(out), self.n))
         return out
 
     def fetch_async(self, plan=None, grid=None):

@@ -23,6 +23,7 @@
 #include "kernels_r.hpp"
 #include "kernels_a.hpp"
 #include "kernels_g.hpp"
+#include "kernels_sc.hpp"
 
 namespace {
 
@@ -174,6 +175,10 @@ struct pp_planner {
     // resident scenes were last set (an advance needs a tick of THESE scenes behind it)
     int32_t* d_ego_flags = nullptr; hipEvent_t ev_adv = nullptr; bool adv_recorded = false, staged_by_advance = false;
     long long set_tick = 0;
+    // rollout scorecard (allocated by the first pp_score_begin): the records, one part array of grid counters per
+    // search set, ev_sc behind the last k_score_ego (upload stream); grp_scored: the open group's tick is scored
+    RolloutScore* d_rscore = nullptr; dmpp::ScoreGridPart* d_rgrid[kBuf] = {}; hipEvent_t ev_sc = nullptr;
+    bool scoring = false, sc_recorded = false, grp_scored = false; double score_dt = 0;
     TickRec last_rec = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
@@ -335,6 +340,7 @@ int join_all(pp_planner* h)
     { int r = flush_group(h); if (r) return r; }
     for (int q = 0; q < kObs; q++) if (h->score_recorded[q]) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_score[q], 0));
     if (h->front_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    if (h->sc_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_sc, 0));
     return PP_OK;
 }
 
@@ -600,6 +606,9 @@ int pp_destroy(pp_handle h)
     if (h->h_bad) (void)hipHostFree(h->h_bad);
     if (h->d_ego_flags) (void)hipFree(h->d_ego_flags);
     if (h->ev_adv) (void)hipEventDestroy(h->ev_adv);
+    if (h->d_rscore) (void)hipFree(h->d_rscore);
+    for (int q = 0; q < kBuf; q++) if (h->d_rgrid[q]) (void)hipFree(h->d_rgrid[q]);
+    if (h->ev_sc) (void)hipEventDestroy(h->ev_sc);
     void* bufs[] = { h->d_lane, h->d_attr, h->d_ref, h->d_state,
                      h->d_dec_ref, h->d_grid, h->d_scratch, h->d_map_first, h->d_map_lanes, h->d_map_width, h->d_map_junc, h->d_map_bad, h->d_bad,
                      h->d_gridbad };
@@ -651,6 +660,18 @@ static int reset_ego_flags(pp_handle h)
     return PP_OK;
 }
 
+// The scorecard's starting values, on the handle's stream behind join_all (every scoring kernel enqueued so far has finished
+// before it); the caller's host wait follows.
+static int reset_scores(pp_handle h)
+{
+    if (!h->d_rscore) return PP_OK;
+    const int ns = h->caps.max_scenes;
+    hipLaunchKernelGGL(dmpp::k_score_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->d_rscore);
+    HIP_TRY(hipGetLastError());
+    for (int q = 0; q < kBuf; q++) HIP_TRY(hipMemsetAsync(h->d_rgrid[q], 0, (size_t)ns * sizeof(dmpp::ScoreGridPart), h->stream));
+    return PP_OK;
+}
+
 // Slices of the resident SceneIn records against the resident pools (k_validate_scenes); syncs the handle's stream.
 static int validate_resident(pp_handle h, int n_scenes, const char* who)
 {
@@ -697,6 +718,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->resident_mode = 0; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
+    if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_scenes");     // syncs: the caller may reuse its buffers
 }
 
@@ -777,6 +799,7 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total;
     h->resident_mode = 1; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
+    if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     if (bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, "pp_set_egos: " + std::to_string(bad) + " scene(s) name a road or lane outside the map"); }
     return validate_resident(h, n_scenes, "pp_set_egos");       // the obstacle slices are still the caller's
 }
@@ -806,6 +829,7 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
     h->resident_mode = 0; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
+    if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_n_scenes");
 }
 
@@ -896,6 +920,11 @@ int flush_group(pp_planner* h)
             hipLaunchKernelGGL(dmpp::k_score<16>, dim3(items), dim3(16 * DMPP_WAVE), sizeof(dmpp::ScoreShared<16>), ss, c, items, tg, need, need_host);
         else
             hipLaunchKernelGGL(dmpp::k_score<4>, dim3(items), dim3(4 * DMPP_WAVE), sizeof(dmpp::ScoreShared<4>), ss, c, items, tg, need, need_host);
+    }
+    if (h->grp_scored) {                             // scorecard, grid half: behind the tick's k_score, in front of ev_score / the tick's ev_tail (a scored tick is a group of 1)
+        hipLaunchKernelGGL(dmpp::k_score_grid, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, ss,
+                           n, std::min(c.n_lattice, DMPP_MAX_LATTICE - 1), h->d_gout[h->grp_gs[G - 1]], h->d_rgrid[p]);
+        h->grp_scored = false;
     }
     for (int i = 0; i < G; i++) {                    // the group's scoring pass is the last reader of its G snapshot sets
         h->score_recorded[h->grp_set[i]] = piped;
@@ -1031,6 +1060,13 @@ int pp_plan_tick(pp_handle h)
     auto wait_unless_done = [](hipStream_t st, hipEvent_t e) { if (hipEventQuery(e) == hipSuccess) return hipSuccess; (void)hipGetLastError(); return hipStreamWaitEvent(st, e, 0); };
     if (adopted && h->in_sets[h->in_cur].up_recorded) HIP_TRY(wait_unless_done(sf, h->in_sets[h->in_cur].ev_up));   // every kernel of the tick follows the snapshot kernel
     if (h->streaming && h->fetched_plan_rec[h->plan_cur]) HIP_TRY(wait_unless_done(sr, h->ev_fetched_plan[h->plan_cur]));   // PlanOut set still being downloaded (kPlan ticks ago)
+    // Scorecard: k_score_ego of the last scored tick (upload stream) reads the SceneState this front chain rewrites, and sets of the
+    // PlanOut and snapshot rings that a later one does.  A tick that adopts an update or an advance waits for that set's ev_up,
+    // recorded behind the kernel on the same stream (staging always follows the tick it follows); any other tick waits here.
+    if (h->sc_recorded) {
+        if (hipEventQuery(h->ev_sc) == hipSuccess) h->sc_recorded = false;
+        else { (void)hipGetLastError(); if (!(adopted && h->in_sets[h->in_cur].up_recorded)) HIP_TRY(hipStreamWaitEvent(sf, h->ev_sc, 0)); }
+    }
     ObPoint* obs_now = h->d_obs_now[po];
     {
         Timed t(h, PP_K_OBSTACLES, sf);
@@ -1058,6 +1094,7 @@ int pp_plan_tick(pp_handle h)
         h->grp_set[slot] = po; h->grp_gs[slot] = gs; h->grp_in = h->d_in;
         h->grp_ticks = slot + 1;
         h->gout_set = gs; h->path_set = po;
+        h->grp_scored = h->scoring;
         if (last_of_group) { int r = flush_group(h); if (r) return r; }
     }
     h->last_piped = piped;
@@ -1068,6 +1105,13 @@ int pp_plan_tick(pp_handle h)
         HIP_TRY(hipEventRecord(rec.ev_front, sr));
         if (rec.ev_tail) HIP_TRY(hipEventRecord(rec.ev_tail, piped ? (h->grp_overlap && !h->score_own_stream ? sm : h->stream_s) : h->stream));
         h->inflight.push_back(rec); h->last_rec = rec;
+        if (h->scoring) {        // scorecard, front half: behind this tick's Planning kernel, on the upload stream - in front of the advance that may follow
+            hipStream_t su = h->stream_up;
+            HIP_TRY(hipStreamWaitEvent(su, rec.ev_front, 0));
+            hipLaunchKernelGGL(dmpp::k_score_ego, dim3((unsigned)((n + dmpp::kScScenes - 1) / dmpp::kScScenes)), dim3(dmpp::kBlock), 0, su,
+                               0.5 * c.Vehicle_Width, h->score_dt, n, h->n_obs_total, h->d_in, h->d_plan, h->d_state, obs_now, h->d_ego_flags, h->d_rscore);
+            HIP_TRY(hipEventRecord(h->ev_sc, su)); h->sc_recorded = true;
+        }
     }
     HIP_TRY(hipGetLastError());
     return PP_OK;
@@ -1407,6 +1451,55 @@ int pp_get_ego_flags(pp_handle h, int32_t* flags, int n)
     return fetch(h, flags, h->d_ego_flags, (size_t)n * sizeof(int32_t));
 }
 
+// Rollout scorecard.  Scored ticks are streamed ticks: k_score_ego hangs on the tick's front-chain event.
+int pp_score_begin(pp_handle h, double dt_score)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!(dt_score > 0) || !std::isfinite(dt_score)) return fail(PP_ERR_ARG, "pp_score_begin: dt_score must be finite and > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = flush_group(h); if (r) return r; }
+    { int r = ensure_streaming(h); if (r) return r; }
+    if (!h->d_rscore) {
+        const size_t ns = (size_t)h->caps.max_scenes;
+        int r = dmalloc(&h->d_rscore, ns); if (r) return r;
+        for (int q = 0; q < kBuf; q++) if ((r = dmalloc(&h->d_rgrid[q], ns))) return r;
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_sc, hipEventDisableTiming));
+    }
+    { int r = join_all(h); if (r) return r; }            // the ticks scored so far (a restart) and everything before
+    { int r = reset_scores(h); if (r) return r; }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->scoring = true; h->score_dt = dt_score;
+    return PP_OK;
+}
+
+int pp_score_end(pp_handle h)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    h->scoring = false;
+    return PP_OK;
+}
+
+int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->d_rscore) return fail(PP_ERR_STATE, "pp_get_rollout_score: pp_score_begin was never called on this handle");
+    if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }            // behind both halves: ev_sc (k_score_ego), ev_score / stream order (k_score_grid)
+    std::vector<dmpp::ScoreGridPart> parts((size_t)kBuf * (size_t)std::max(n, 1));
+    HIP_TRY(hipMemcpyAsync(out, h->d_rscore, (size_t)n * sizeof(RolloutScore), hipMemcpyDefault, h->stream));
+    for (int q = 0; q < kBuf && n > 0; q++)
+        HIP_TRY(hipMemcpyAsync(parts.data() + (size_t)q * n, h->d_rgrid[q], (size_t)n * sizeof(dmpp::ScoreGridPart), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < kBuf; q++)                       // the grid half: one part per search set, added here
+        for (int s = 0; s < n; s++) {
+            const dmpp::ScoreGridPart& p = parts[(size_t)q * n + s];
+            out[s].n_grid_ticks += p.n_grid_ticks; out[s].n_grid_path_candidate += p.n_grid_path_candidate;
+            for (int k = 0; k < DMPP_G_STATUS_COUNT; k++) out[s].grid_status_ticks[k] += p.status[k];
+        }
+    return PP_OK;
+}
+
 static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
@@ -1479,6 +1572,7 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
     HIP_TRY(hipSetDevice(h->device));
     const int max_obs = std::min(PP_IO_MAX_OBS, h->caps.max_obs_total), max_ref = std::min(DMPP_MAX_REFPATH, h->caps.max_ref_pts_total);
     { int r = flush_group(h); if (r) return r; }          // (k_io_in rewrites the inputs an open group's searches read)
+    if (h->sc_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_sc, 0));      // ... and the scorecard of the last tick
     h->in_staged = -1; h->staged_by_advance = false;
     hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->d_in, h->d_state, h->d_obs, h->d_ref);
     HIP_TRY(hipGetLastError());
@@ -1799,7 +1893,7 @@ size_t pp_sizeof(int which)
     case 9: return sizeof(LocationOut); case 10: return sizeof(DecisionOutPod); case 11: return sizeof(LaneView);
     case 12: return sizeof(PlanningOut); case 13: return sizeof(PlanningStatus); case 14: return sizeof(AimPoint);
     case 15: return sizeof(MapLane); case 16: return sizeof(MapJunction); case 17: return sizeof(MapDesc); case 18: return sizeof(PpSceneIo);
-    case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace);
+    case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore);
     default: return 0;
     }
 }

@@ -1,0 +1,109 @@
+// kernels_sc.hpp — rollout scorecard (build-defined): per-scene safety and progress totals folded on the
+// device over the scored ticks, so that a closed-loop rollout can be judged without fetching every tick.
+//
+//   k_score_ego   : the front half.  One 64-lane wave per scene, four scenes per 256-thread block, no LDS, no barrier (the
+//                   shape of k_advance_egos).  The lanes stride over the scene's records of the tick's obstacle snapshot; the
+//                   smallest distance is a (value, index) wave minimum that keeps the first minimum (wave_first_min); lane 0
+//                   folds the scalars into the record.  Reads SceneIn_t, PlanOut_t, SceneState after tick t, the snapshot of
+//                   tick t and the ego flag word; writes the front half of RolloutScore.
+//   k_score_grid  : the grid half.  One thread per scene: the header of GridOut_t into a ScoreGridPart.  The searches of
+//                   consecutive ticks run on kBuf streams side by side, so every search stream counts into a part array of
+//                   its own (stream order serialises its ticks) and pp_get_rollout_score adds the parts into the records.
+//   k_score_reset : the starting values (+inf, -1: not all zero bits).
+#pragma once
+#include "dev_geom.hpp"
+
+namespace dmpp {
+
+constexpr int kScScenes = 4;           // scenes (waves) per block of k_score_ego
+
+struct ScoreGridPart { int32_t n_grid_ticks, n_grid_path_candidate, status[DMPP_G_STATUS_COUNT]; };
+
+__global__ void __launch_bounds__(kBlock)
+k_score_reset(int n_scenes, RolloutScore* __restrict__ score)
+{
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_scenes) return;
+    RolloutScore r;
+    r.min_clearance = __builtin_huge_val(); r.dist = 0; r.max_speed = 0; r.max_acc = 0; r.max_dec = 0;
+    r.last_pos.x = 0; r.last_pos.y = 0; r.last_speed = 0;
+    r.n_ticks = 0; r.min_clearance_tick = -1; r.min_clearance_obs = -1; r.first_collision_tick = -1; r.n_collision_ticks = 0;
+    r.n_replans = 0; r.n_ob_flag = 0; r.n_desacc = 0;
+    for (int k = 0; k < 8; k++) r.behavior_ticks[k] = 0;
+    r.ego_flags = 0; r._pad = 0; r.n_grid_ticks = 0; r.n_grid_path_candidate = 0;
+    for (int k = 0; k < DMPP_G_STATUS_COUNT; k++) r.grid_status_ticks[k] = 0;
+    score[s] = r;
+}
+
+// obs_cap: entries of a snapshot set; a slice outside it (no set call and no update lets one through) counts as empty.
+__global__ void __launch_bounds__(kBlock)
+k_score_ego(double half_width, double dt_score, int n_scenes, int obs_cap, const SceneIn* __restrict__ in, const PlanOut* __restrict__ plan,
+            const SceneState* __restrict__ state, const ObPoint* __restrict__ now, const int32_t* __restrict__ flags,
+            RolloutScore* __restrict__ score)
+{
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * kScScenes + (threadIdx.x >> 6);
+    if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
+    const SceneIn& si = in[s];
+    const double x = si.loc.globalpoint.x, y = si.loc.globalpoint.y, v = si.loc.velocity;
+    const int off = si.obs_off;
+    int m = si.obs_n;
+    if (off < 0 || m < 0 || (long long)off + (long long)m > (long long)obs_cap) m = 0;
+    // 1. the nearest obstacle edge: first index of the smallest d_j, a NaN is never the minimum
+    double md = 0; int mi = -1;
+    for (int j = lane; j < m; j += 64) {
+        const ObPoint o = now[off + j];
+        const double dx = o.x - x, dy = o.y - y;
+        const double d = sqrt(dx * dx + dy * dy) - (double)o.radius;
+        if (d == d && (mi < 0 || d < md)) { md = d; mi = j; }
+    }
+    wave_first_min(md, mi);
+    if (lane != 0) return;
+    RolloutScore& r = score[s];
+    const int k = r.n_ticks;                            // this tick's index among the scored ones
+    // 2. clearance and collisions
+    if (mi >= 0) {
+        const double cl = md - half_width;
+        if (cl < r.min_clearance) { r.min_clearance = cl; r.min_clearance_tick = k; r.min_clearance_obs = mi; }
+        if (cl <= 0) {
+            if (r.first_collision_tick < 0) r.first_collision_tick = k;
+            r.n_collision_ticks = r.n_collision_ticks + 1;
+        }
+    }
+    // 3. distance and speed against the ego of the tick before
+    if (k > 0) {
+        const double dx = x - r.last_pos.x, dy = y - r.last_pos.y;
+        r.dist = r.dist + sqrt(dx * dx + dy * dy);
+        const double a = (v - r.last_speed) / 3.6 / dt_score, fall = -a;
+        if (a > r.max_acc) r.max_acc = a;
+        if (fall > r.max_dec) r.max_dec = fall;
+    }
+    if (v > r.max_speed) r.max_speed = v;
+    r.last_pos.x = x; r.last_pos.y = y; r.last_speed = v;
+    // 4. counters of the tick's plan
+    const PlanOut& po = plan[s];
+    if (state[s].afresh_planning != 0) r.n_replans = r.n_replans + 1;
+    if (po.ob_flag != 0) r.n_ob_flag = r.n_ob_flag + 1;
+    if (po.result.desaccVd != 0) r.n_desacc = r.n_desacc + 1;
+    const int b = clampi(po.dec.behavior, 0, 7);
+    r.behavior_ticks[b] = r.behavior_ticks[b] + 1;
+    r.ego_flags = flags ? flags[s] : 0;
+    r.n_ticks = k + 1;
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_score_grid(int n_scenes, int n_lattice, const GridOut* __restrict__ gout, ScoreGridPart* __restrict__ part)
+{
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_scenes) return;
+    const GridOut& g = gout[s];
+    ScoreGridPart& p = part[s];
+    int st = g.status;
+    if (st < 0 || st >= DMPP_G_STATUS_COUNT) st = DMPP_G_INTERNAL;
+    p.n_grid_ticks = p.n_grid_ticks + 1;
+    p.status[st] = p.status[st] + 1;
+    const int nc = g.n_candidates;
+    if (nc == n_lattice + 1 && g.best_candidate == nc - 1) p.n_grid_path_candidate = p.n_grid_path_candidate + 1;
+}
+
+}  // namespace dmpp

@@ -1,6 +1,8 @@
 // example_rollout.cpp — closed-loop evaluation through the C-ABI: 256 generated scenes, every ego follows what the planner
 // tells it for 50 ticks (pp_rollout: advance + tick on the device, no host wait, no per-tick PCIe traffic), then the host looks
-// at where they ended up: how many scenes carry which rollout flag and how far the egos travelled.  Exit code 0 = ran on the GPU.
+// at where they ended up: how many scenes carry which rollout flag and how far the egos travelled.  The rollout is scored on the
+// device (pp_score_begin: one RolloutScore record per scene, nothing fetched per tick): collisions, worst clearance, distance.
+// Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
 #include <cstdio>
@@ -26,6 +28,7 @@ int main()
     EgoTrace* trace = (EgoTrace*)pp_host_alloc(sizeof(EgoTrace) * (size_t)ticks * n);      // pinned: the kernel writes it over PCIe
     if (!trace) { std::fprintf(stderr, "pp_host_alloc: %s\n", pp_last_error()); return 2; }
     long long last = 0;
+    CHECK(pp_score_begin(h, model.dt));
     CHECK(pp_rollout(h, ticks, &model, trace, &last));
     CHECK(pp_sync(h));
     std::vector<int32_t> flags(n);
@@ -46,6 +49,19 @@ int main()
     }
     std::printf("rolled %d scenes out for %d ticks (last tick id %lld): %d free, PATH_END %d, BAD_PATH %d, LANE_END %d, OFF_GRID %d; mean distance travelled %.2f m\n",
                 n, ticks, last, n_free, n_end, n_bad, n_lane, n_grid, dist / n);
+    std::vector<RolloutScore> score(n);
+    CHECK(pp_score_end(h));
+    CHECK(pp_get_rollout_score(h, score.data(), n));
+    int n_hit = 0, hit_ticks = 0, worst = 0; double sdist = 0;
+    for (int s = 0; s < n; s++) {
+        const RolloutScore& r = score[(size_t)s];
+        n_hit += r.n_collision_ticks > 0; hit_ticks += r.n_collision_ticks; sdist += r.dist;
+        if (r.min_clearance < score[(size_t)worst].min_clearance) worst = s;
+    }
+    std::printf("scorecard: %d of %d scenes touched an obstacle (%d collision ticks of %d scored per scene)\n", n_hit, n, hit_ticks, score[0].n_ticks);
+    std::printf("scorecard: worst clearance %.3f m, scene %d, tick %d, obstacle %d\n", score[(size_t)worst].min_clearance, worst,
+                score[(size_t)worst].min_clearance_tick, score[(size_t)worst].min_clearance_obs);
+    std::printf("scorecard: mean distance %.2f m (the trace's odometer above: %.2f m)\n", sdist / n, dist / n);
     pp_host_free(trace);
     pp_destroy(h);
     std::printf("example_rollout ok\n");

@@ -193,6 +193,22 @@ int  pp_rollout(pp_handle h, int n_ticks, const EgoModel* m, EgoTrace* trace, lo
 /* The DMPP_EGO_* flag words after the last advance (all zero on a handle that never advanced).  Host wait. */
 int  pp_get_ego_flags(pp_handle h, int32_t* flags, int n_scenes);
 
+/* ---- rollout scorecard: per-scene safety and progress totals kept on the device -----------------------------------
+ * Between pp_score_begin and pp_score_end EVERY pp_plan_tick is scored exactly once - rollout ticks, ticks fed by pp_update_async
+ * and ticks on unchanged inputs alike - into one RolloutScore record per scene: two small kernels per tick (k_score_ego behind the
+ * tick's Planning kernel on the upload stream, k_score_grid behind its scoring pass), no host wait, nothing downloaded.  Scored
+ * ticks are streamed ticks (tick groups of 1, like rollout ticks; the handle stays in that mode afterwards, as after any streamed
+ * call).  A handle that never calls pp_score_begin allocates and launches none of this.
+ * pp_score_begin: allocates on first use, sets every record to its starting values (a second call restarts the totals) and turns
+ * scoring on (one host wait).  dt_score: seconds between ticks, the divisor of max_acc / max_dec; finite and > 0, else PP_ERR_ARG.
+ * pp_set_scenes / pp_set_egos / pp_set_n_scenes while scoring is on restart the totals, as they clear the ego flags.
+ * pp_score_end: scoring off; the records stay readable and later ticks leave them alone.
+ * pp_get_rollout_score: the records of the first n_scenes scenes into host memory, the last enqueued tick included.  Host wait.
+ * PP_ERR_STATE on a handle that never began. */
+int  pp_score_begin(pp_handle h, double dt_score);
+int  pp_score_end(pp_handle h);
+int  pp_get_rollout_score(pp_handle h, RolloutScore* out, int n_scenes);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -256,7 +272,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
 /* sizeof of an ABI struct, for bindings to check their mirror: 0 PlannerConfig, 1 PlannerCaps,
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
- * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace */
+ * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

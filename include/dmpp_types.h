@@ -255,6 +255,31 @@ typedef struct PlanOut {
     int32_t        navi_lanechg_times;       /* CalcNaviLaneChgTimes, Decision.cpp:498-538 */
 } PlanOut;
 
+/* ---- rollout scorecard (build-defined) ------------------------------------------------------
+ * One record per scene, folded on the device over the ticks scored between pp_score_begin and pp_score_end, in tick
+ * order.  Tick indices are 0-based counts of scored ticks; obstacle indices count within the scene's slice.  Every field is
+ * specified exactly (§4d): a numpy restatement gives the same bytes. */
+typedef struct RolloutScore {
+    double  min_clearance;          /* smallest clearance_t (m); +inf while no tick had one                          */
+    double  dist;                   /* sum over ticks of the distance between successive ego positions (m)           */
+    double  max_speed;              /* largest loc.velocity (km/h); starts at 0                                      */
+    double  max_acc, max_dec;       /* largest rise / fall of the speed between successive ticks (m/s^2, both >= 0)  */
+    GlobalPoint2D last_pos;         /* ego position of the last scored tick                                          */
+    double  last_speed;             /* ... and its loc.velocity (km/h)                                               */
+    int32_t n_ticks;                /* ticks scored                                                                  */
+    int32_t min_clearance_tick, min_clearance_obs;       /* where min_clearance first occurred; -1, -1 while none    */
+    int32_t first_collision_tick, n_collision_ticks;     /* ticks with clearance_t <= 0; first: -1 while none        */
+    int32_t n_replans;              /* ticks that left SceneState.afresh_planning != 0                               */
+    int32_t n_ob_flag, n_desacc;    /* ticks with PlanOut.ob_flag != 0; with PlanOut.result.desaccVd != 0            */
+    int32_t behavior_ticks[8];      /* histogram of PlanOut.dec.behavior clamped to 0..7                             */
+    int32_t ego_flags;              /* DMPP_EGO_* word the ego of the last scored tick carried                       */
+    int32_t _pad;
+    /* grid half (k_score_grid): only ticks that ran the grid stage */
+    int32_t n_grid_ticks;
+    int32_t n_grid_path_candidate;  /* ticks whose grid-path candidate (the last one) was the best                   */
+    int32_t grid_status_ticks[DMPP_G_STATUS_COUNT];      /* histogram of GridOut.status; out of range: DMPP_G_INTERNAL */
+} RolloutScore;                                                             /* 176 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

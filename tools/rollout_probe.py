@@ -2,7 +2,9 @@
 """Runs ON THE GPU BOX: ticks/s of the closed loop on the device (pp_rollout: advance + tick, no per-tick PCIe traffic) against
 the host-fed streamed loop (pp_update_async of prepared pinned inputs + pp_fetch_published_async, what a host-side vehicle
 model needs every tick), same handle size, same build, alternating.
-    python tools/rollout_probe.py [scenes] [timed ticks] [warm-up ticks] [runs]"""
+    python tools/rollout_probe.py [scenes] [timed ticks] [warm-up ticks] [runs]
+SCORE=1: the rollout leg runs with the scorecard on (pp_score_begin) and prints a summary of the records; SCORE=ab: every run has
+a rollout leg without and one with scoring, alternating (the cost of scoring on one build)."""
 import os
 import statistics
 import sys
@@ -32,8 +34,13 @@ def fresh():
     return pl, sc
 
 
-def rollout_run():
+SCORE = os.environ.get("SCORE", "0")
+
+
+def rollout_run(score=SCORE == "1"):
     pl, _ = fresh()
+    if score:
+        pl.score_begin()
     pl.rollout(warm, model)
     pl.sync()
     t0 = time.perf_counter()
@@ -41,6 +48,10 @@ def rollout_run():
     pl.sync()
     dt = time.perf_counter() - t0
     frozen = int((pl.ego_flags() != 0).sum())
+    if score:
+        sc = pl.rollout_score()
+        rollout_run.summary = "%d ticks scored, %d scenes with a collision, worst clearance %.3f m, mean distance %.2f m" % (
+            int(sc["n_ticks"][0]), int((sc["n_collision_ticks"] > 0).sum()), float(sc["min_clearance"].min()), float(sc["dist"].mean()))
     pl.close()
     return n * steps / dt, frozen
 
@@ -74,6 +85,16 @@ def streamed_run():
     return n * steps / dt
 
 
+if SCORE == "ab":
+    off, on = [], []
+    for r in range(runs):
+        a, _ = rollout_run(False)
+        b, _ = rollout_run(True)
+        off.append(a), on.append(b)
+        print("run %d  %d scenes  rollout %.3f M ticks/s   scored rollout %.3f M ticks/s" % (r, n, a / 1e6, b / 1e6), flush=True)
+    print("median  %d scenes  rollout %.3f M ticks/s   scored rollout %.3f M ticks/s   ratio %.3f   (%s)" %
+          (n, statistics.median(off) / 1e6, statistics.median(on) / 1e6, statistics.median(on) / statistics.median(off), rollout_run.summary), flush=True)
+    sys.exit(0)
 ro, stv = [], []
 for r in range(runs):
     a, frozen = rollout_run()
@@ -82,5 +103,7 @@ for r in range(runs):
     print("run %d  %d scenes  rollout %.3f M ticks/s (%d scenes frozen at the end)   host-fed streamed %.3f M ticks/s" % (r, n, a / 1e6, frozen, b / 1e6), flush=True)
 print("median  %d scenes  rollout %.3f M ticks/s   host-fed streamed %.3f M ticks/s   ratio %.3f" %
       (n, statistics.median(ro) / 1e6, statistics.median(stv) / 1e6, statistics.median(ro) / statistics.median(stv)), flush=True)
+if SCORE == "1":
+    print("scorecard:", rollout_run.summary, flush=True)
 if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout alone
     rollout_run()
