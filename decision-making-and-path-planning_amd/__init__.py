@@ -91,6 +91,10 @@ RolloutScore = _dt([("min_clearance", f8), ("dist", f8), ("max_speed", f8), ("ma
                     ("min_clearance_obs", i4), ("first_collision_tick", i4), ("n_collision_ticks", i4), ("n_replans", i4),
                     ("n_ob_flag", i4), ("n_desacc", i4), ("behavior_ticks", i4, (8,)), ("ego_flags", i4), ("_pad", i4),
                     ("n_grid_ticks", i4), ("n_grid_path_candidate", i4), ("grid_status_ticks", i4, (G_STATUS_COUNT,))])
+# fleet coupling: the egos of one world are each other's obstacles during a rollout
+FleetModel = _dt([("range", f8), ("radius", f4), ("max_peers", i4)])
+OB_PEER = 0x40000000          # ObPoint.type of a peer slot: OB_PEER | scene index of the peer (DMPP_OB_PEER)
+FLEET_MAX_PEERS = 64
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -191,6 +195,12 @@ def load_library(path=None):
         lib.pp_score_begin.argtypes = [vp, C.c_double]
         lib.pp_score_end.argtypes = [vp]
         lib.pp_get_rollout_score.argtypes = [vp, vp, ci]
+    fleet = hasattr(lib, "pp_set_fleet") or path == LIB_PATH          # (as above: an older build may lack it)
+    if fleet:
+        lib.pp_default_fleet_model.argtypes = [vp]
+        lib.pp_default_fleet_model.restype = None
+        lib.pp_set_fleet.argtypes = [vp, ci, vp, vp]
+        lib.pp_get_obstacles.argtypes = [vp, ci, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -202,7 +212,8 @@ def load_library(path=None):
     for which, dt in enumerate(_SIZEOF_ORDER):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
-    for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()):
+    for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
+            (((22, FleetModel),) if fleet else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -235,6 +246,13 @@ def default_ego_model():
     m = np.zeros(1, EgoModel)
     load_library().pp_default_ego_model(_ptr(m))
     return m
+
+
+def default_fleet_model():
+    """FleetModel record of the fleet coupling (pp_default_fleet_model): range, peer radius, peer slots per scene."""
+    fm = np.zeros(1, FleetModel)
+    load_library().pp_default_fleet_model(_ptr(fm))
+    return fm
 
 
 def gen_scenes(cfg, first_scene, n_scenes, n_obs, junction_every=8):
@@ -417,6 +435,27 @@ class Planner:
         out = np.zeros(self.n, RolloutScore)
         _check(self.lib.pp_get_rollout_score(self.h, _ptr(out), self.n))
         return out
+
+    # ---- fleet coupling: the egos of one world are each other's obstacles ------------------
+    def set_fleet(self, world_first=None, fm=None):
+        """pp_set_fleet: world w = scenes [world_first[w], world_first[w + 1]); every scene's obstacle slice is pinned and the
+        fm.max_peers pool entries behind it become its peer slots.  world_first None (or one entry): fleet off."""
+        if world_first is None or len(world_first) < 2:
+            _check(self.lib.pp_set_fleet(self.h, 0, None, None))
+            return
+        wf = np.ascontiguousarray(world_first, np.int32)
+        m = default_fleet_model() if fm is None else np.array(fm, FleetModel).reshape(1).copy()
+        _check(self.lib.pp_set_fleet(self.h, len(wf) - 1, _ptr(wf), _ptr(m)))
+
+    def get_obstacles(self, scene, cap=256):
+        """pp_get_obstacles: the scene's obstacle slice - own entries, then peers - of the input set get_scene_in reads."""
+        out = np.zeros(max(cap, 1), ObPoint)
+        n = self.lib.pp_get_obstacles(self.h, int(scene), _ptr(out), cap)
+        if n > cap:
+            return self.get_obstacles(scene, n)
+        if n < 0:
+            _check(n)
+        return out[:n].copy()
 
     def fetch_async(self, plan=None, grid=None):
         """pp_fetch_async of the last enqueued tick into `plan` / `grid` (pinned arrays of self.n records). Returns the tick id."""

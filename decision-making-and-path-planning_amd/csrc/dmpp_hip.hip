@@ -24,6 +24,7 @@
 #include "kernels_a.hpp"
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
+#include "kernels_f.hpp"
 
 namespace {
 
@@ -179,6 +180,12 @@ struct pp_planner {
     // search set, ev_sc behind the last k_score_ego (upload stream); grp_scored: the open group's tick is scored
     RolloutScore* d_rscore = nullptr; dmpp::ScoreGridPart* d_rgrid[kBuf] = {}; hipEvent_t ev_sc = nullptr;
     bool scoring = false, sc_recorded = false, grp_scored = false; double score_dt = 0;
+    // fleet coupling (allocated by the first pp_set_fleet): world_first, the world of every scene and the pinned
+    // slices on the device; the pinned slices on the host too (a second pp_set_fleet starts from the scenes' OWN entries);
+    // fleet_end: the largest end of a peer-slot run, fleet_base: the used pool size before the fleet grew it
+    bool fleet_on = false; FleetModel fleet_fm = { 0, 0, 0 }; int fleet_end = 0, fleet_base = 0, fleet_own_end = 0;      // fleet_own_end: the largest end of a scene's OWN entries
+    int32_t* d_world_first = nullptr; int32_t* d_world_of = nullptr; dmpp::FleetPin* d_fleet_pin = nullptr;
+    std::vector<dmpp::FleetPin> fleet_pin;
     TickRec last_rec = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
@@ -241,6 +248,16 @@ void note_current_set(pp_planner* h)          // after a pp_set_* call changed w
     I.have_motion = h->have_motion; I.n_obs_total = h->n_obs_total;
     h->in_staged = -1;                        // an update staged before it is superseded
     h->staged_by_advance = false; h->set_tick = h->tick_seq;
+}
+
+// Fleet coupling of one input set on the stream that stages it: behind the copies / the advance that produced its
+// SceneIn records and obstacle pool, in front of k_resolve_map / k_sanitise_scenes.  Reads and writes only that set.
+void couple_fleet(pp_planner* h, hipStream_t st, SceneIn* d_in, ObPoint* d_obs, ObMotion* d_mot)
+{
+    const int n = h->n_scenes;
+    hipLaunchKernelGGL(dmpp::k_couple_fleet, dim3((unsigned)((n + dmpp::kFleetScenes - 1) / dmpp::kFleetScenes)), dim3(dmpp::kBlock), 0, st,
+                       n, h->fleet_fm.range * h->fleet_fm.range, h->fleet_fm.radius, h->fleet_fm.max_peers, h->d_world_first, h->d_world_of,
+                       h->d_fleet_pin, d_in, d_obs, d_mot);
 }
 
 // Issues the copies of the pending downloads whose kernels have finished.  force_tick: that tick's copies are issued whatever
@@ -609,6 +626,7 @@ int pp_destroy(pp_handle h)
     if (h->d_rscore) (void)hipFree(h->d_rscore);
     for (int q = 0; q < kBuf; q++) if (h->d_rgrid[q]) (void)hipFree(h->d_rgrid[q]);
     if (h->ev_sc) (void)hipEventDestroy(h->ev_sc);
+    for (void* b : { (void*)h->d_world_first, (void*)h->d_world_of, (void*)h->d_fleet_pin }) if (b) (void)hipFree(b);
     void* bufs[] = { h->d_lane, h->d_attr, h->d_ref, h->d_state,
                      h->d_dec_ref, h->d_grid, h->d_scratch, h->d_map_first, h->d_map_lanes, h->d_map_width, h->d_map_junc, h->d_map_bad, h->d_bad,
                      h->d_gridbad };
@@ -716,7 +734,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
         h->have_motion = true;
     }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
-    h->resident_mode = 0; note_current_set(h);
+    h->resident_mode = 0; h->fleet_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_scenes");     // syncs: the caller may reuse its buffers
@@ -797,7 +815,7 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     HIP_TRY(hipMemcpyAsync(&bad, h->d_map_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total;
-    h->resident_mode = 1; note_current_set(h);
+    h->resident_mode = 1; h->fleet_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     if (bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, "pp_set_egos: " + std::to_string(bad) + " scene(s) name a road or lane outside the map"); }
@@ -827,7 +845,7 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     { int r = join_all(h); if (r) return r; }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
-    h->resident_mode = 0; note_current_set(h);
+    h->resident_mode = 0; h->fleet_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_n_scenes");
@@ -1318,6 +1336,10 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     if (!in && !obs_pool) return fail(PP_ERR_ARG, "nothing to update");
     if (obs_pool && (n_obs_total < 0 || n_obs_total > h->caps.max_obs_total)) return fail(PP_ERR_CAPACITY, "obstacle pool larger than caps.max_obs_total");
     if (!obs_pool && mot_pool) return fail(PP_ERR_ARG, "a motion pool without its obstacle pool");
+    // with a fleet the slices are the pinned ones and the slice check runs against the end of the peer slots: a pool that stops
+    // short of a scene's OWN entries would not be caught there, so it is refused here, before anything is enqueued
+    if (obs_pool && h->fleet_on && n_obs_total < h->fleet_own_end)
+        return fail(PP_ERR_ARG, "pp_update_async: with a fleet set the obstacle pool must cover every scene's own entries (up to entry " + std::to_string(h->fleet_own_end) + ")");
     if (in && h->in_staged >= 0 && h->staged_by_advance)
         return fail(PP_ERR_STATE, "pp_update_async: the SceneIn records of the next tick were already produced by pp_advance_async");
     HIP_TRY(hipSetDevice(h->device));
@@ -1357,6 +1379,10 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     // k_resolve_map / k_sanitise_scenes add to it in stream order, and a repeated update that brings new SceneIn records
     // restarts the count with k_zero_word on that stream - behind the kernels of the earlier update, which a store from the
     // host could overtake.  After the adoption nobody writes it; pp_wait_tick reads it behind the tick's downloads.
+    if (h->fleet_on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
+        n_obs = std::max(n_obs, h->fleet_end);
+        couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);
+    }
     int32_t* bad_slot = &h->h_bad[(h->tick_seq + 1) % kDone];
     if (s != h->in_staged) *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;
     else if (in) hipLaunchKernelGGL(dmpp::k_zero_word, dim3(1), dim3(1), 0, su, bad_slot);      // (a second, obstacles-only update of a staged set keeps the count of the first)
@@ -1414,6 +1440,7 @@ int pp_advance_async(pp_handle h, const EgoModel* m, EgoTrace* trace)
     *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;          // nothing is staged for that tick: the host owns the slot (owner rule in pp_update_async)
     hipLaunchKernelGGL(dmpp::k_advance_egos, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
                        h->cfg, *m, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
+    if (h->fleet_on) couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);      // the peers at the poses just advanced to
     const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
     if (h->resident_mode == 1)
         hipLaunchKernelGGL(dmpp::k_resolve_map, grid, block, 0, su, n, I.d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
@@ -1498,6 +1525,100 @@ int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
             for (int k = 0; k < DMPP_G_STATUS_COUNT; k++) out[s].grid_status_ticks[k] += p.status[k];
         }
     return PP_OK;
+}
+
+// Fleet coupling.  Everything is checked on the host before anything changes.
+int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const FleetModel* fm)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (n_worlds < 0) return fail(PP_ERR_ARG, "pp_set_fleet: negative world count");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_fleet: an update is staged for the next tick (set the fleet before staging, or after the tick)");
+    const int n = h->n_scenes;
+    if (n_worlds == 0) {
+        if (!h->fleet_on) return PP_OK;
+        HIP_TRY(hipSetDevice(h->device));
+        { int r = join_all(h); if (r) return r; }
+        hipLaunchKernelGGL(dmpp::k_fleet_restore, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, n, h->d_fleet_pin, h->d_in);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        // (the slices are the pinned ones again; they were inside fleet_base when they were pinned)
+        const int back = std::max(h->fleet_base, h->fleet_own_end);
+        h->fleet_on = false; h->n_obs_total = back; h->in_sets[h->in_cur].n_obs_total = back;
+        return PP_OK;
+    }
+    if (!world_first || !fm) return fail(PP_ERR_ARG, "null argument");
+    if (n <= 0) return fail(PP_ERR_STATE, "pp_set_fleet: no resident scenes");
+    const int K = fm->max_peers;
+    if (K < 0 || K > DMPP_FLEET_MAX_PEERS) return fail(PP_ERR_ARG, "pp_set_fleet: max_peers must be 0 .. " + std::to_string(DMPP_FLEET_MAX_PEERS));
+    if (!std::isfinite(fm->range) || !(fm->range > 0) || !std::isfinite(fm->radius) || !(fm->radius >= 0))
+        return fail(PP_ERR_ARG, "pp_set_fleet: range must be finite and > 0, radius finite and >= 0");
+    if (n_worlds > n || world_first[0] != 0 || world_first[n_worlds] != n) return fail(PP_ERR_ARG, "pp_set_fleet: world_first must run from 0 to the resident scene count");
+    for (int w = 0; w < n_worlds; w++) if (world_first[w + 1] <= world_first[w]) return fail(PP_ERR_ARG, "pp_set_fleet: world_first must be strictly increasing");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }
+    // the scenes' own slices: of the resident records, or - fleet already on - the ones pinned then (obs_n counts peers now)
+    std::vector<dmpp::FleetPin> pin((size_t)n);
+    if (h->fleet_on) pin = h->fleet_pin;
+    else {
+        std::vector<SceneIn> rec((size_t)n);
+        HIP_TRY(hipMemcpyAsync(rec.data(), h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int s = 0; s < n; s++) { pin[(size_t)s].obs_off = rec[(size_t)s].obs_off; pin[(size_t)s].n_own = rec[(size_t)s].obs_n; }
+    }
+    const int base = h->fleet_on ? h->fleet_base : h->n_obs_total;
+    std::vector<std::pair<long long, long long>> ext;       // non-empty extended slices [off, off + n_own + K)
+    long long end_max = base, own_end = 0;
+    for (int s = 0; s < n; s++) {
+        const long long off = pin[(size_t)s].obs_off, len = (long long)pin[(size_t)s].n_own + K;
+        if (pin[(size_t)s].n_own < 0) return fail(PP_ERR_ARG, "pp_set_fleet: scene " + std::to_string(s) + " has a negative obs_n");
+        if (pin[(size_t)s].n_own > 0) own_end = std::max(own_end, off + pin[(size_t)s].n_own);
+        if (len == 0) continue;
+        if (off < 0) return fail(PP_ERR_ARG, "pp_set_fleet: scene " + std::to_string(s) + " has a negative obs_off");
+        if (off + len > (long long)h->caps.max_obs_total)
+            return fail(PP_ERR_CAPACITY, "pp_set_fleet: the obstacle slice of scene " + std::to_string(s) + " with its peer slots ends beyond caps.max_obs_total");
+        ext.emplace_back(off, off + len);
+        end_max = std::max(end_max, off + len);
+    }
+    std::sort(ext.begin(), ext.end());
+    for (size_t k = 1; k < ext.size(); k++)
+        if (ext[k].first < ext[k - 1].second) return fail(PP_ERR_ARG, "pp_set_fleet: two scenes' obstacle slices overlap once the peer slots are added (leave max_peers free entries behind every slice)");
+    std::vector<int32_t> world_of((size_t)n);
+    for (int w = 0; w < n_worlds; w++) for (int s = world_first[w]; s < world_first[w + 1]; s++) world_of[(size_t)s] = w;
+    {
+        const size_t ns = (size_t)h->caps.max_scenes;
+        int r;
+        if (!h->d_world_first && (r = dmalloc(&h->d_world_first, ns + 1))) return r;
+        if (!h->d_world_of && (r = dmalloc(&h->d_world_of, ns))) return r;
+        if (!h->d_fleet_pin && (r = dmalloc(&h->d_fleet_pin, ns))) return r;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_world_first, world_first, ((size_t)n_worlds + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_world_of, world_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_fleet_pin, pin.data(), (size_t)n * sizeof(dmpp::FleetPin), hipMemcpyHostToDevice, h->stream));
+    h->fleet_pin.swap(pin); h->fleet_fm = *fm; h->fleet_base = base; h->fleet_end = (int)end_max; h->fleet_own_end = (int)std::min(own_end, (long long)h->caps.max_obs_total); h->fleet_on = true;
+    h->n_obs_total = (int)end_max; h->in_sets[h->in_cur].n_obs_total = (int)end_max;
+    couple_fleet(h, h->stream, h->d_in, h->d_obs, h->have_motion ? h->d_mot : nullptr);      // the resident set: the next tick sees the peers
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
+    return PP_OK;
+}
+
+int pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap)
+{
+    if (!h || (!out && cap > 0)) return fail(PP_ERR_ARG, "null argument");
+    if (scene < 0 || scene >= h->n_scenes || cap < 0) return fail(PP_ERR_ARG, "pp_get_obstacles: scene or cap out of range");
+    const bool staged = h->in_staged >= 0 && h->staged_by_advance;      // (the set pp_get_scene_in reads)
+    const InputSet& I = h->in_sets[staged ? h->in_staged : h->in_cur];
+    HIP_TRY(hipSetDevice(h->device));
+    if (staged) HIP_TRY(hipStreamWaitEvent(h->stream, I.ev_up, 0));
+    int32_t sl[2] = { 0, 0 };
+    { int r = fetch(h, sl, &I.d_in[scene].obs_off, sizeof(sl)); if (r) return r; }
+    static_assert(offsetof(SceneIn, obs_n) == offsetof(SceneIn, obs_off) + 4, "obs_off and obs_n are read as one pair");
+    if (sl[1] == 0) return 0;
+    if (sl[0] < 0 || sl[1] < 0 || (long long)sl[0] + sl[1] > (long long)h->caps.max_obs_total)
+        return fail(PP_ERR_STATE, "pp_get_obstacles: the scene's obstacle slice lies outside the pool");
+    const int m = std::min(sl[1], cap);
+    if (m > 0) { int r = fetch(h, out, I.d_obs + sl[0], (size_t)m * sizeof(ObPoint)); if (r) return r; }
+    return sl[1];
 }
 
 static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id)
@@ -1893,7 +2014,7 @@ size_t pp_sizeof(int which)
     case 9: return sizeof(LocationOut); case 10: return sizeof(DecisionOutPod); case 11: return sizeof(LaneView);
     case 12: return sizeof(PlanningOut); case 13: return sizeof(PlanningStatus); case 14: return sizeof(AimPoint);
     case 15: return sizeof(MapLane); case 16: return sizeof(MapJunction); case 17: return sizeof(MapDesc); case 18: return sizeof(PpSceneIo);
-    case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore);
+    case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore); case 22: return sizeof(FleetModel);
     default: return 0;
     }
 }

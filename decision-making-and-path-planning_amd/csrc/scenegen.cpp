@@ -65,6 +65,15 @@ extern "C" void pp_default_ego_model(EgoModel* m)
     m->dt = 0.1; m->max_acc = 2.0; m->max_dec = 4.0; m->window = 32;
 }
 
+// the fleet model: the reach of the reference's front corridor ("120 points ~60m", Decision.cpp:581), a disc of
+// half the default vehicle width (0.9 rounded to float), eight peers
+extern "C" void pp_default_fleet_model(FleetModel* fm)
+{
+    PlannerConfig c; pp_default_config(&c, 32, 32);
+    std::memset(fm, 0, sizeof(*fm));
+    fm->range = 60.0; fm->radius = (float)(0.5 * c.Vehicle_Width); fm->max_peers = 8;
+}
+
 extern "C" void pp_init_state(SceneState* st, int lane_num)
 {
     std::memset(st, 0, sizeof(*st));

@@ -209,6 +209,36 @@ int  pp_score_begin(pp_handle h, double dt_score);
 int  pp_score_end(pp_handle h);
 int  pp_get_rollout_score(pp_handle h, RolloutScore* out, int n_scenes);
 
+/* ---- fleet coupling: the egos of one world see each other during a rollout -----------------------------------
+ * pp_set_fleet groups the resident scenes into WORLDS: world w is the contiguous run of scenes [world_first[w], world_first[w+1]);
+ * world_first has n_worlds + 1 entries, starts at 0, ends at the resident scene count and is strictly increasing (host pointer).
+ * From then on every input set that is staged - by pp_advance_async, by pp_update_async - passes through one more kernel on the
+ * upload stream (k_couple_fleet) that writes, behind every scene's own obstacles, the K = fm->max_peers nearest egos of its world
+ * within fm->range (squared distance <= range * range, ties to the lower scene index) at the poses of that set, as
+ * ObPoint { x, y, type = DMPP_OB_PEER | peer scene, radius = fm->radius } with zero ObMotion, and sets obs_n = own + peers found.
+ * Decision, Planning, search, scoring and the scorecard read the obstacle list and so react to peers with no change.
+ * The call PINS every scene's obstacle slice: (obs_off, n_own = obs_n) of the resident records are recorded and the K pool entries
+ * [obs_off + n_own, obs_off + n_own + K) are the scene's peer slots; obs_off / obs_n of SceneIn records uploaded later are
+ * overwritten by the pinned values, and an obstacle pool uploaded later must leave the peer slots free.  Such a pool must also
+ * cover every scene's own entries: one that ends before them is PP_ERR_ARG from pp_update_async (the device's slice check
+ * runs against the end of the peer slots and would not see it).  The used size of the
+ * obstacle pool grows to the largest slot end.  Checked on the host, with nothing changed on failure: every extended slice
+ * [obs_off, obs_off + n_own + K) inside caps.max_obs_total (PP_ERR_CAPACITY) and disjoint from every other, 0 <= K <=
+ * DMPP_FLEET_MAX_PEERS, range finite and > 0, radius finite and >= 0, world_first as above (PP_ERR_ARG); no resident scenes or an
+ * update staged for the next tick: PP_ERR_STATE.  The resident set is coupled inside the call (the next tick sees the peers); one
+ * host wait.  n_worlds = 0 (pointers may be NULL): fleet off, the resident records get their own slices back.  pp_set_scenes /
+ * pp_set_egos / pp_set_n_scenes switch the fleet off too.  A handle that never calls pp_set_fleet allocates and launches none of
+ * this.  Peers have no velocity and no orientation; a world lives on one handle.  A scene that an earlier streamed update POISONED
+ * carries obs_off = 0, obs_n = 0: its peer slots would be [0, K), which collide with the slice of whichever scene owns the start
+ * of the pool, and the call is refused with the overlap message - set good scenes first. */
+void pp_default_fleet_model(FleetModel* fm);         /* range 60 m, radius half the default Vehicle_Width, 8 peers */
+int  pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const FleetModel* fm);
+/* The obstacle slice of one scene - its own entries, then the peers - of the input set pp_get_scene_in reads (the staged one after
+ * an advance).  At most cap entries are written; returns obs_n (>= 0), or a negative error.  A debugging read-back, not for
+ * per-tick use: two small copies with a host wait each, and it drains the pipeline of overlapping ticks like every pp_get_*.
+ * Only the obs_n entries the tick reads are returned: peer slots beyond them (left as they are) are not. */
+int  pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -272,7 +302,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
 /* sizeof of an ABI struct, for bindings to check their mirror: 0 PlannerConfig, 1 PlannerCaps,
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
- * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore */
+ * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

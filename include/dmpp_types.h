@@ -280,6 +280,20 @@ typedef struct RolloutScore {
     int32_t grid_status_ticks[DMPP_G_STATUS_COUNT];      /* histogram of GridOut.status; out of range: DMPP_G_INTERNAL */
 } RolloutScore;                                                             /* 176 B */
 
+/* ---- fleet coupling (build-defined: the reference has no fleet) ------------------------------
+ * pp_set_fleet groups the resident scenes into worlds; after every staged input set the nearest egos of a scene's own
+ * world are written into the peer slots behind its obstacle slice.  FleetModel: how far an ego sees its peers, the
+ * footprint radius a peer is given as an obstacle, and how many peer slots every scene gets. */
+typedef struct FleetModel {
+    double  range;              /* metres: a peer is a candidate when its squared distance is <= range * range   */
+    float   radius;             /* ObPoint.radius of a peer slot (metres)                                        */
+    int32_t max_peers;          /* K: peer slots per scene, 0 .. DMPP_FLEET_MAX_PEERS                            */
+} FleetModel;                                                               /* 16 B */
+#define DMPP_FLEET_MAX_PEERS 64
+/* ObPoint.type of a peer slot: DMPP_OB_PEER | scene index of the peer (nothing on the device reads `type`; it travels
+ * into PlanOut.ob.type / PlanOut.around[k].Ob_Attr.type and tells the caller WHICH ego was in the way) */
+#define DMPP_OB_PEER 0x40000000
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

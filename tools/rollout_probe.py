@@ -4,7 +4,10 @@ the host-fed streamed loop (pp_update_async of prepared pinned inputs + pp_fetch
 model needs every tick), same handle size, same build, alternating.
     python tools/rollout_probe.py [scenes] [timed ticks] [warm-up ticks] [runs]
 SCORE=1: the rollout leg runs with the scorecard on (pp_score_begin) and prints a summary of the records; SCORE=ab: every run has
-a rollout leg without and one with scoring, alternating (the cost of scoring on one build)."""
+a rollout leg without and one with scoring, alternating (the cost of scoring on one build).
+FLEET=K: every run has a rollout leg with the fleet on (pp_set_fleet, K peer slots per scene; FLEET_WORLD=<scenes per world>, 0 or
+unset: one world of all scenes; FLEET_RANGE=<metres>, default the model's) and one with the fleet off whose scenes carry K far-away
+obstacles more - the same obs_n, or the comparison would charge the fleet for longer obstacle lists -, alternating."""
 import os
 import statistics
 import sys
@@ -35,6 +38,38 @@ def fresh():
 
 
 SCORE = os.environ.get("SCORE", "0")
+FLEET = int(os.environ.get("FLEET", "0"))
+FLEET_WORLD = int(os.environ.get("FLEET_WORLD", "0"))
+
+
+def fleet_run(on):
+    """n_obs own obstacles and FLEET more entries per scene: the peer slots (fleet on), or obstacles 1e6 m away (fleet off)."""
+    K, stride = FLEET, n_obs + FLEET
+    sc = dm.gen_scenes(cfg, 0, n, n_obs, junction_every=8)
+    pool = np.zeros((n, stride), dm.ObPoint)
+    pool[:, :n_obs] = sc["obs_pool"].reshape(n, n_obs)
+    pool[:, n_obs:]["x"], pool[:, n_obs:]["y"], pool[:, n_obs:]["radius"] = 1e6, 1e6, 0.5
+    sc["obs_pool"], sc["n_obs"] = pool.reshape(-1), stride
+    sc["scene_in"]["obs_off"], sc["scene_in"]["obs_n"] = np.arange(n) * stride, n_obs if on else stride
+    pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=n * stride)
+    pl.set_scenes(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    if on:
+        fm = dm.default_fleet_model()
+        fm["max_peers"] = K
+        if os.environ.get("FLEET_RANGE"):
+            fm["range"] = float(os.environ["FLEET_RANGE"])
+        w = FLEET_WORLD if FLEET_WORLD > 0 else n
+        pl.set_fleet(list(range(0, n, w)) + [n], fm)
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    mean_obs = float(pl.get_scene_in()["obs_n"].mean())
+    pl.close()
+    return n * steps / dt, mean_obs
 
 
 def rollout_run(score=SCORE == "1"):
@@ -85,6 +120,20 @@ def streamed_run():
     return n * steps / dt
 
 
+if FLEET > 0:
+    off, on = [], []
+    for r in range(runs):
+        a, na = fleet_run(False)
+        b, nb = fleet_run(True)
+        off.append(a), on.append(b)
+        print("run %d  %d scenes  fleet off (padded, obs_n %.1f) %.3f M ticks/s   fleet on (K %d, worlds of %d, obs_n %.1f) %.3f M ticks/s" %
+              (r, n, na, a / 1e6, FLEET, FLEET_WORLD if FLEET_WORLD > 0 else n, nb, b / 1e6), flush=True)
+    print("median  %d scenes  fleet off %.3f M ticks/s (spread %.3f)   fleet on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more fleet rollout alone
+        fleet_run(True)
+    sys.exit(0)
 if SCORE == "ab":
     off, on = [], []
     for r in range(runs):
