@@ -95,6 +95,10 @@ RolloutScore = _dt([("min_clearance", f8), ("dist", f8), ("max_speed", f8), ("ma
 FleetModel = _dt([("range", f8), ("radius", f4), ("max_peers", i4)])
 OB_PEER = 0x40000000          # ObPoint.type of a peer slot: OB_PEER | scene index of the peer (DMPP_OB_PEER)
 FLEET_MAX_PEERS = 64
+# route following: rollout egos cross junctions onto the next road of their route
+RouteLeg = _dt([("road_num", i4), ("stub_attribute", i4), ("out_lane_no", u2, (LANESUM,))])
+RouteModel = _dt([("pre_points", i4), ("_pad", i4)])
+EGO_ROUTE_END = 16            # the ego came to the end of the last leg of its route (DMPP_EGO_ROUTE_END)
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -201,6 +205,10 @@ def load_library(path=None):
         lib.pp_default_fleet_model.restype = None
         lib.pp_set_fleet.argtypes = [vp, ci, vp, vp]
         lib.pp_get_obstacles.argtypes = [vp, ci, vp, ci]
+    route = hasattr(lib, "pp_set_route") or path == LIB_PATH          # (as above: an older build may lack it)
+    if route:
+        lib.pp_default_route_model.argtypes = [vp]
+        lib.pp_set_route.argtypes = [vp, ci, vp, vp, vp]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -213,7 +221,7 @@ def load_library(path=None):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
-            (((22, FleetModel),) if fleet else ()):
+            (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -253,6 +261,13 @@ def default_fleet_model():
     fm = np.zeros(1, FleetModel)
     load_library().pp_default_fleet_model(_ptr(fm))
     return fm
+
+
+def default_route_model():
+    """RouteModel record of the route following (pp_default_route_model): lane points of pre-junction before a lane's end."""
+    rm = np.zeros(1, RouteModel)
+    _check(load_library().pp_default_route_model(_ptr(rm)))
+    return rm
 
 
 def gen_scenes(cfg, first_scene, n_scenes, n_obs, junction_every=8):
@@ -446,6 +461,20 @@ class Planner:
         wf = np.ascontiguousarray(world_first, np.int32)
         m = default_fleet_model() if fm is None else np.array(fm, FleetModel).reshape(1).copy()
         _check(self.lib.pp_set_fleet(self.h, len(wf) - 1, _ptr(wf), _ptr(m)))
+
+    # ---- route following: routed egos cross junctions onto the next road ------------------
+    def set_route(self, legs=None, route_first=None, model=None):
+        """pp_set_route: the route of scene s is legs[route_first[s] : route_first[s + 1]] (RouteLeg records; an empty run leaves
+        the scene unrouted); loc.path_num indexes the ego's current leg within it.  legs None (or empty): routing off."""
+        if legs is None or len(legs) == 0:
+            _check(self.lib.pp_set_route(self.h, 0, None, None, None))
+            return
+        lg = np.ascontiguousarray(legs, RouteLeg)
+        rf = np.ascontiguousarray(route_first, np.int32)
+        if self.n > 0 and len(rf) != self.n + 1:          # (no resident scenes: the library answers before it reads them)
+            raise PlannerError(f"set_route: route_first needs {self.n + 1} entries (one per resident scene and the end), got {len(rf)}")
+        m = default_route_model() if model is None else np.array(model, RouteModel).reshape(1).copy()
+        _check(self.lib.pp_set_route(self.h, len(lg), _ptr(lg), _ptr(rf), _ptr(m)))
 
     def get_obstacles(self, scene, cap=256):
         """pp_get_obstacles: the scene's obstacle slice - own entries, then peers - of the input set get_scene_in reads."""

@@ -22,6 +22,7 @@
 #include "../../include/dmpp_planner.h"
 #include "kernels_r.hpp"
 #include "kernels_a.hpp"
+#include "kernels_rt.hpp"
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
 #include "kernels_f.hpp"
@@ -186,6 +187,9 @@ struct pp_planner {
     bool fleet_on = false; FleetModel fleet_fm = { 0, 0, 0 }; int fleet_end = 0, fleet_base = 0, fleet_own_end = 0;      // fleet_own_end: the largest end of a scene's OWN entries
     int32_t* d_world_first = nullptr; int32_t* d_world_of = nullptr; dmpp::FleetPin* d_fleet_pin = nullptr;
     std::vector<dmpp::FleetPin> fleet_pin;
+    // route following (allocated by the first pp_set_route): the legs of every scene's route and route_first on the
+    // device; with route_on pp_advance_async launches k_advance_route in the place of k_advance_egos
+    bool route_on = false; RouteModel route_rm = { 0, 0 }; RouteLeg* d_route_legs = nullptr; int32_t* d_route_first = nullptr; size_t route_legs_cap = 0;
     TickRec last_rec = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
@@ -627,6 +631,7 @@ int pp_destroy(pp_handle h)
     for (int q = 0; q < kBuf; q++) if (h->d_rgrid[q]) (void)hipFree(h->d_rgrid[q]);
     if (h->ev_sc) (void)hipEventDestroy(h->ev_sc);
     for (void* b : { (void*)h->d_world_first, (void*)h->d_world_of, (void*)h->d_fleet_pin }) if (b) (void)hipFree(b);
+    for (void* b : { (void*)h->d_route_legs, (void*)h->d_route_first }) if (b) (void)hipFree(b);
     void* bufs[] = { h->d_lane, h->d_attr, h->d_ref, h->d_state,
                      h->d_dec_ref, h->d_grid, h->d_scratch, h->d_map_first, h->d_map_lanes, h->d_map_width, h->d_map_junc, h->d_map_bad, h->d_bad,
                      h->d_gridbad };
@@ -734,7 +739,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
         h->have_motion = true;
     }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
-    h->resident_mode = 0; h->fleet_on = false; note_current_set(h);
+    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_scenes");     // syncs: the caller may reuse its buffers
@@ -767,6 +772,7 @@ int pp_set_map(pp_handle h, const MapDesc* m)
     void* old[] = { h->d_map_first, h->d_map_lanes, h->d_map_junc };
     for (void* b : old) if (b) (void)hipFree(b);
     h->d_map_first = nullptr; h->d_map_lanes = nullptr; h->d_map_junc = nullptr; h->have_map = false;
+    h->route_on = false;                                 // (the routes named roads of the old map)
     int r;
     if ((r = dmalloc(&h->d_map_first, (size_t)m->n_roads + 1))) return r;
     if ((r = dmalloc(&h->d_map_lanes, (size_t)(m->n_lanes > 0 ? m->n_lanes : 1)))) return r;
@@ -815,7 +821,7 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     HIP_TRY(hipMemcpyAsync(&bad, h->d_map_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total;
-    h->resident_mode = 1; h->fleet_on = false; note_current_set(h);
+    h->resident_mode = 1; h->fleet_on = false; h->route_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     if (bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, "pp_set_egos: " + std::to_string(bad) + " scene(s) name a road or lane outside the map"); }
@@ -845,7 +851,7 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     { int r = join_all(h); if (r) return r; }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
-    h->resident_mode = 0; h->fleet_on = false; note_current_set(h);
+    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_n_scenes");
@@ -1438,8 +1444,13 @@ int pp_advance_async(pp_handle h, const EgoModel* m, EgoTrace* trace)
     }
     int32_t* bad_slot = &h->h_bad[(h->tick_seq + 1) % kDone];
     *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;          // nothing is staged for that tick: the host owns the slot (owner rule in pp_update_async)
-    hipLaunchKernelGGL(dmpp::k_advance_egos, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
-                       h->cfg, *m, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
+    if (h->route_on)                      // routed egos cross junctions; the scenes without a route advance as below
+        hipLaunchKernelGGL(dmpp::k_advance_route, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
+                           h->cfg, *m, h->route_rm, n, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
+                           h->d_route_legs, h->d_route_first, h->d_ego_flags, trace);
+    else
+        hipLaunchKernelGGL(dmpp::k_advance_egos, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
+                           h->cfg, *m, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
     if (h->fleet_on) couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);      // the peers at the poses just advanced to
     const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
     if (h->resident_mode == 1)
@@ -1599,6 +1610,48 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     couple_fleet(h, h->stream, h->d_in, h->d_obs, h->have_motion ? h->d_mot : nullptr);      // the resident set: the next tick sees the peers
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
+    return PP_OK;
+}
+
+// Route following.  Everything is checked on the host before anything changes; the resident records are not touched.
+int pp_default_route_model(RouteModel* rm)
+{
+    if (!rm) return fail(PP_ERR_ARG, "null argument");
+    rm->pre_points = 60; rm->_pad = 0;       // 30 m of 0.5 m points: the PRE_INTER distances of the default configuration
+    return PP_OK;
+}
+
+int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int32_t* route_first, const RouteModel* rm)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (n_legs_total < 0) return fail(PP_ERR_ARG, "pp_set_route: negative leg count");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_route: an update is staged for the next tick (set the route before staging, or after the tick)");
+    if (n_legs_total == 0) { h->route_on = false; return PP_OK; }
+    const int n = h->n_scenes;
+    if (n <= 0) return fail(PP_ERR_STATE, "pp_set_route: no resident scenes");
+    if (h->resident_mode != 1 || !h->have_map) return fail(PP_ERR_STATE, "pp_set_route: routes need egos on a resident map (pp_set_map, then pp_set_egos)");
+    if (!legs || !route_first || !rm) return fail(PP_ERR_ARG, "null argument");
+    if (rm->pre_points < 0) return fail(PP_ERR_ARG, "pp_set_route: pre_points must be >= 0");
+    if (route_first[0] != 0 || route_first[n] != n_legs_total) return fail(PP_ERR_ARG, "pp_set_route: route_first must run from 0 to n_legs_total");
+    for (int s = 0; s < n; s++) if (route_first[s + 1] < route_first[s]) return fail(PP_ERR_ARG, "pp_set_route: route_first must not decrease");
+    for (int k = 0; k < n_legs_total; k++)
+        if (legs[k].road_num < 1 || legs[k].road_num > h->map_roads) return fail(PP_ERR_ARG, "pp_set_route: leg " + std::to_string(k) + " names a road outside the map");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the old legs
+    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!h->d_route_first) { int r = dmalloc(&h->d_route_first, (size_t)h->caps.max_scenes + 1); if (r) return r; }
+    if ((size_t)n_legs_total > h->route_legs_cap) {
+        RouteLeg* fresh = nullptr;
+        { int r = dmalloc(&fresh, (size_t)n_legs_total); if (r) return r; }
+        if (h->d_route_legs) (void)hipFree(h->d_route_legs);
+        h->d_route_legs = fresh; h->route_legs_cap = (size_t)n_legs_total;
+    }
+    h->route_on = false;                                  // (until the copies below have landed: a failed copy leaves routing off, not half a route)
+    HIP_TRY(hipMemcpyAsync(h->d_route_legs, legs, (size_t)n_legs_total * sizeof(RouteLeg), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_route_first, route_first, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // (the caller's arrays may go; the upload stream reads the copies from its next launch on)
+    h->route_rm = *rm; h->route_rm._pad = 0; h->route_on = true;
     return PP_OK;
 }
 
@@ -2015,6 +2068,7 @@ size_t pp_sizeof(int which)
     case 12: return sizeof(PlanningOut); case 13: return sizeof(PlanningStatus); case 14: return sizeof(AimPoint);
     case 15: return sizeof(MapLane); case 16: return sizeof(MapJunction); case 17: return sizeof(MapDesc); case 18: return sizeof(PpSceneIo);
     case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore); case 22: return sizeof(FleetModel);
+    case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel);
     default: return 0;
     }
 }

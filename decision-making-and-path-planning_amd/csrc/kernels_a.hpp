@@ -6,7 +6,8 @@
 // path segments ahead of k0 side by side; the sum is then taken in index order - by every lane alike, on values broadcast out
 // of the lane that holds them, so the walk is wave-uniform and its rounding is that of a scalar loop - and stops at s (a
 // handful of segments at 0.5 m spacing).  The three id searches are (value, index) wave minima that keep the first minimum
-// (wave_first_min, the reduction of GetVhclLocalState in k_planning).
+// (wave_first_min, the reduction of GetVhclLocalState in k_planning).  The steps are device functions: the routed form of the kernel
+// (k_advance_route, kernels_rt.hpp) shares the speed, pose, id-search and grid code and replaces §4c 4. - 5. for routed scenes.
 #pragma once
 #include "dev_geom.hpp"
 
@@ -15,9 +16,11 @@ namespace dmpp {
 constexpr int kAdvScenes = 4;          // scenes (waves) per block of k_advance_egos
 
 __device__ __forceinline__ bool finite_f64(double v) { return __builtin_isfinite(v); }
-// First index of the smallest squared distance to (x, y) over the points [max(id0, 0), min(id0 + window, n)) of one lane view;
-// a NaN distance is never the minimum.  idx < 0: no such point (the id keeps its value).  The result is the same in every lane.
-__device__ __forceinline__ void wave_view_nearest(const GlobalPoint3D* __restrict__ pts, int n, int id0, int window, double x, double y,
+// First index of the smallest squared distance to (x, y) over the points [max(id0, 0), min(id0 + window, n)) of one lane view (or
+// junction polyline: P is GlobalPoint3D or GlobalPoint2D); a NaN distance is never the minimum.  idx < 0: no such point (the id
+// keeps its value).  The result is the same in every lane.
+template <class P>
+__device__ __forceinline__ void wave_view_nearest(const P* __restrict__ pts, int n, int id0, int window, double x, double y,
                                                   int lane, double& best_d2, int& best_idx)
 {
     const int lo = max(id0, 0);
@@ -33,6 +36,144 @@ __device__ __forceinline__ void wave_view_nearest(const GlobalPoint3D* __restric
     best_d2 = md; best_idx = mi;
 }
 
+// The record travels as 32-bit words, one per lane: lane k holds word k of SceneIn[s] and stores word k of the new record, so
+// every word is written once and nothing is indexed in registers.  loc.id[j] is word kIdWord + j, held by that lane.
+constexpr int kSiWords = (int)(sizeof(SceneIn) / 4), kIdWord = (int)(offsetof(LocationOut, id) / 4), kLaneNumWord = (int)(offsetof(LocationOut, lane_num) / 4);
+static_assert(sizeof(SceneIn) % 4 == 0 && kSiWords <= 64 && offsetof(SceneIn, loc) == 0, "SceneIn is moved as 32-bit words, one per lane");
+static_assert(offsetof(LocationOut, globalpoint) == 0 && offsetof(LocationOut, velocity) == 24, "x, y, dir, velocity are words 0 .. 7");
+__device__ __forceinline__ int adv_get_id(int w, int slot) { return __shfl(w, kIdWord + slot, 64); }      // (a shuffle: every lane takes part)
+__device__ __forceinline__ void adv_set_id(int& w, int lane, int slot, int v) { if (lane == kIdWord + slot) w = v; }
+
+// §4c 1. - 3.: the new speed and pose of one scene (the same in every lane).  bad: BAD_PATH, nothing else is defined.
+struct AdvPose { double x, y, dir, vn; bool bad, path_end; };
+__device__ __forceinline__ AdvPose adv_speed_pose(const PlannerConfig& c, const EgoModel& m, const SceneIn& si, const PlanOut& po, const SceneState& st, int lane)
+{
+    const PlanningOut& R = po.result;
+    const GlobalPoint2D* __restrict__ P = po.road_points;
+    // 1. speed (km/h)
+    const double v = si.loc.velocity;
+    double vn;
+    if (R.desaccVd) { vn = v + R.desacc * m.dt * 3.6; if (!(vn > 0)) vn = 0; }
+    else {
+        const double tgt = R.desspd;
+        if (!finite_f64(tgt)) vn = v;
+        else if (tgt > v) { vn = v + m.max_acc * m.dt * 3.6; if (vn > tgt) vn = tgt; }
+        else { vn = v - m.max_dec * m.dt * 3.6; if (vn < tgt) vn = tgt; }
+    }
+    // 2. distance (m)
+    const double dist = 0.5 * (v + vn) / 3.6 * m.dt;
+    // 3. pose
+    // (path_near_id is the ego's index on the path the tick LOCALISED on; a tick that replanned published a new path that starts at the ego)
+    const int k0 = st.afresh_planning ? 0 : clampi(st.path_near_id, 0, DMPP_PATH_POINTS - 1);
+    const GlobalPoint2D p0 = P[k0];
+    bool bad = !finite_f64(dist) || !finite_f64(p0.x) || !finite_f64(p0.y);
+    double x = p0.x, y = p0.y, dir = si.loc.globalpoint.dir;
+    bool path_end = false;
+    if (!bad && dist > 0) {
+        double acc = 0; bool done = false; int last_seg = -1;
+        for (int c0 = k0; c0 < DMPP_PATH_POINTS - 1 && !done && !bad; c0 += 64) {
+            const int i = c0 + lane;
+            double L = 0;
+            if (i < DMPP_PATH_POINTS - 1) { const double dx = P[i + 1].x - P[i].x, dy = P[i + 1].y - P[i].y; L = sqrt(dx * dx + dy * dy); }
+            const int cnt = min(64, DMPP_PATH_POINTS - 1 - c0);
+            for (int j = 0; j < cnt; j++) {
+                const double Lj = shfl_f64(L, j);
+                if (!finite_f64(Lj)) { bad = true; break; }
+                if (Lj == 0) continue;
+                last_seg = c0 + j;
+                if (acc + Lj >= dist) {
+                    const GlobalPoint2D a = P[last_seg], b = P[last_seg + 1];
+                    const double t = (dist - acc) / Lj;
+                    x = a.x + t * (b.x - a.x); y = a.y + t * (b.y - a.y);
+                    dir = GetRoadAngle(c, a, b);
+                    done = true; break;
+                }
+                acc = acc + Lj;
+            }
+        }
+        if (!bad && !done) {
+            path_end = true;
+            x = P[DMPP_PATH_POINTS - 1].x; y = P[DMPP_PATH_POINTS - 1].y;
+            if (last_seg >= 0) dir = GetRoadAngle(c, P[last_seg], P[last_seg + 1]);
+        }
+    }
+    AdvPose r; r.x = x; r.y = y; r.dir = dir; r.vn = vn; r.bad = bad; r.path_end = path_end;
+    return r;
+}
+__device__ __forceinline__ void adv_store_pose(int& w, int lane, const AdvPose& p)
+{
+    if (lane < 8) {
+        const int q = lane >> 1;
+        const double d = q == 0 ? p.x : q == 1 ? p.y : q == 2 ? p.dir : p.vn;
+        w = (lane & 1) ? __double2hiint(d) : __double2loint(d);
+    }
+}
+
+// §4c 4.: the localisation ids of the current, left and right view (the slots k_planning reads), searched from the ids the record
+// words hold and written back into them.  i* < 0: the view is absent or has no nearest point.
+struct AdvIds { double dc, dl, dr; int ic, il, ir; bool has_c; };
+__device__ __forceinline__ AdvIds adv_search_ids(const GlobalPoint3D* __restrict__ lane_pool, const LaneView& lv, int ln, int window, double x, double y,
+                                                 int lane, int& w)
+{
+    AdvIds r;
+    r.has_c = ln >= 1 && ln <= DMPP_LANESUM && lv.cur_n > 0;
+    const bool has_l = ln > 1 && ln - 2 < DMPP_LANESUM && lv.left_n > 0;
+    const bool has_r = ln < lv.lane_sum && ln >= 0 && ln < DMPP_LANESUM && lv.right_n > 0;
+    r.dc = 0; r.dl = 0; r.dr = 0; r.ic = -1; r.il = -1; r.ir = -1;
+    if (r.has_c) wave_view_nearest(lane_pool + lv.cur_off, lv.cur_n, adv_get_id(w, ln - 1), window, x, y, lane, r.dc, r.ic);
+    if (has_l) wave_view_nearest(lane_pool + lv.left_off, lv.left_n, adv_get_id(w, ln - 2), window, x, y, lane, r.dl, r.il);
+    if (has_r) wave_view_nearest(lane_pool + lv.right_off, lv.right_n, adv_get_id(w, ln), window, x, y, lane, r.dr, r.ir);
+    return r;
+}
+__device__ __forceinline__ void adv_store_ids(int& w, int lane, int ln, const AdvIds& r)
+{
+    if (r.ic >= 0) adv_set_id(w, lane, ln - 1, r.ic);
+    if (r.il >= 0) adv_set_id(w, lane, ln - 2, r.il);
+    if (r.ir >= 0) adv_set_id(w, lane, ln, r.ir);
+}
+// §4c 5.: the lane number the nearest points give (the current view has one: r.ic >= 0)
+__device__ __forceinline__ int adv_lane_number(const LaneView& lv, int ln, const AdvIds& r)
+{
+    const double margin = 0.25 * lv.lane_width, rc = sqrt(r.dc);
+    if (r.il >= 0 && rc - sqrt(r.dl) > margin) return ln - 1;
+    if (r.ir >= 0 && rc - sqrt(r.dr) > margin) return ln + 1;
+    return ln;
+}
+// §4c 6.: the grid does not follow the ego
+__device__ __forceinline__ bool adv_off_grid(const PlannerConfig& c, const SceneIn& si, double x, double y)
+{
+    const double fx = floor((x - si.grid_origin.x) / c.cell), fy = floor((y - si.grid_origin.y) / c.cell);
+    return !(fx >= 0 && fx < (double)c.grid_w && fy >= 0 && fy < (double)c.grid_h);
+}
+__device__ __forceinline__ void adv_store_trace(EgoTrace* __restrict__ trace, int s, int lane, int w, int ln_new, int f)
+{                                                       // (shuffles: every lane takes part)
+    const int id_cur = adv_get_id(w, clampi(ln_new - 1, 0, DMPP_LANESUM - 1));
+    const double tx = __hiloint2double(__shfl(w, 1, 64), __shfl(w, 0, 64)), ty = __hiloint2double(__shfl(w, 3, 64), __shfl(w, 2, 64));
+    const double td = __hiloint2double(__shfl(w, 5, 64), __shfl(w, 4, 64)), tv = __hiloint2double(__shfl(w, 7, 64), __shfl(w, 6, 64));
+    if (lane == 0) {
+        EgoTrace t;
+        t.pose.x = tx; t.pose.y = ty; t.pose.dir = td; t.velocity = tv;
+        t.id_cur = id_cur; t.lane_num = ln_new; t.flags = f; t._pad = 0;
+        trace[s] = t;
+    }
+}
+// §4c 4. - 5. for a scene that follows no route: ids, LANE_END, lane number
+__device__ __forceinline__ void adv_lane_step(const GlobalPoint3D* __restrict__ lane_pool, const LaneView& lv, int ln, int window, int map_mode,
+                                              double x, double y, int lane, int& w, int& f, int& ln_new)
+{
+    const AdvIds r = adv_search_ids(lane_pool, lv, ln, window, x, y, lane, w);
+    if (r.has_c) {
+        const int idc = r.ic >= 0 ? r.ic : adv_get_id(w, ln - 1);
+        if ((long long)idc + window >= (long long)lv.cur_n) f |= DMPP_EGO_LANE_END;
+    }
+    adv_store_ids(w, lane, ln, r);
+    // 5. lane number: only on a resident map, where k_resolve_map derives the new views
+    if (map_mode && r.ic >= 0) {
+        ln_new = adv_lane_number(lv, ln, r);
+        if (lane == kLaneNumWord) w = ln_new;
+    }
+}
+
 __global__ void __launch_bounds__(kBlock)
 k_advance_egos(PlannerConfig c, EgoModel m, int n_scenes, int map_mode, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
                const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const GlobalPoint3D* __restrict__ lane_pool,
@@ -42,118 +183,22 @@ k_advance_egos(PlannerConfig c, EgoModel m, int n_scenes, int map_mode, const Sc
     const int s = blockIdx.x * kAdvScenes + (threadIdx.x >> 6);
     if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
     const SceneIn& si = in[s];
-    // The record travels as 32-bit words, one per lane: lane k holds word k of SceneIn[s] and stores word k of the new record, so
-    // every word is written once and nothing is indexed in registers.  loc.id[j] is word kIdWord + j, held by that lane.
-    constexpr int kWords = (int)(sizeof(SceneIn) / 4), kIdWord = (int)(offsetof(LocationOut, id) / 4), kLaneNumWord = (int)(offsetof(LocationOut, lane_num) / 4);
-    static_assert(sizeof(SceneIn) % 4 == 0 && kWords <= 64 && offsetof(SceneIn, loc) == 0, "SceneIn is moved as 32-bit words, one per lane");
-    static_assert(offsetof(LocationOut, globalpoint) == 0 && offsetof(LocationOut, velocity) == 24, "x, y, dir, velocity are words 0 .. 7");
-    int w = lane < kWords ? reinterpret_cast<const int*>(&si)[lane] : 0;
-    auto get_id = [&](int slot) { return __shfl(w, kIdWord + slot, 64); };
-    auto set_id = [&](int slot, int v) { if (lane == kIdWord + slot) w = v; };
+    int w = lane < kSiWords ? reinterpret_cast<const int*>(&si)[lane] : 0;
     const int f_in = flags[s];
     const int ln = si.loc.lane_num;
     int f = f_in, ln_new = ln;
     if (f_in == 0) {
-        const PlanningOut& R = plan[s].result;
-        const GlobalPoint2D* __restrict__ P = plan[s].road_points;
-        // 1. speed (km/h)
-        const double v = si.loc.velocity;
-        double vn;
-        if (R.desaccVd) { vn = v + R.desacc * m.dt * 3.6; if (!(vn > 0)) vn = 0; }
+        const AdvPose p = adv_speed_pose(c, m, si, plan[s], state[s], lane);
+        if (p.bad) f |= DMPP_EGO_BAD_PATH;
         else {
-            const double tgt = R.desspd;
-            if (!finite_f64(tgt)) vn = v;
-            else if (tgt > v) { vn = v + m.max_acc * m.dt * 3.6; if (vn > tgt) vn = tgt; }
-            else { vn = v - m.max_dec * m.dt * 3.6; if (vn < tgt) vn = tgt; }
-        }
-        // 2. distance (m)
-        const double dist = 0.5 * (v + vn) / 3.6 * m.dt;
-        // 3. pose
-        // (path_near_id is the ego's index on the path the tick LOCALISED on; a tick that replanned published a new path that starts at the ego)
-        const int k0 = state[s].afresh_planning ? 0 : clampi(state[s].path_near_id, 0, DMPP_PATH_POINTS - 1);
-        const GlobalPoint2D p0 = P[k0];
-        bool bad = !finite_f64(dist) || !finite_f64(p0.x) || !finite_f64(p0.y);
-        double x = p0.x, y = p0.y, dir = si.loc.globalpoint.dir;
-        bool path_end = false;
-        if (!bad && dist > 0) {
-            double acc = 0; bool done = false; int last_seg = -1;
-            for (int c0 = k0; c0 < DMPP_PATH_POINTS - 1 && !done && !bad; c0 += 64) {
-                const int i = c0 + lane;
-                double L = 0;
-                if (i < DMPP_PATH_POINTS - 1) { const double dx = P[i + 1].x - P[i].x, dy = P[i + 1].y - P[i].y; L = sqrt(dx * dx + dy * dy); }
-                const int cnt = min(64, DMPP_PATH_POINTS - 1 - c0);
-                for (int j = 0; j < cnt; j++) {
-                    const double Lj = shfl_f64(L, j);
-                    if (!finite_f64(Lj)) { bad = true; break; }
-                    if (Lj == 0) continue;
-                    last_seg = c0 + j;
-                    if (acc + Lj >= dist) {
-                        const GlobalPoint2D a = P[last_seg], b = P[last_seg + 1];
-                        const double t = (dist - acc) / Lj;
-                        x = a.x + t * (b.x - a.x); y = a.y + t * (b.y - a.y);
-                        dir = GetRoadAngle(c, a, b);
-                        done = true; break;
-                    }
-                    acc = acc + Lj;
-                }
-            }
-            if (!bad && !done) {
-                path_end = true;
-                x = P[DMPP_PATH_POINTS - 1].x; y = P[DMPP_PATH_POINTS - 1].y;
-                if (last_seg >= 0) dir = GetRoadAngle(c, P[last_seg], P[last_seg + 1]);
-            }
-        }
-        if (bad) f |= DMPP_EGO_BAD_PATH;
-        else {
-            if (path_end) f |= DMPP_EGO_PATH_END;
-            if (lane < 8) {
-                const int q = lane >> 1;
-                const double d = q == 0 ? x : q == 1 ? y : q == 2 ? dir : vn;
-                w = (lane & 1) ? __double2hiint(d) : __double2loint(d);
-            }
-            // 4. localisation ids of the current, left and right view (the slots k_planning reads)
-            const int window = m.window;
-            const LaneView lv = si.lanes;
-            const bool has_c = ln >= 1 && ln <= DMPP_LANESUM && lv.cur_n > 0;
-            const bool has_l = ln > 1 && ln - 2 < DMPP_LANESUM && lv.left_n > 0;
-            const bool has_r = ln < lv.lane_sum && ln >= 0 && ln < DMPP_LANESUM && lv.right_n > 0;
-            double dc = 0, dl = 0, dr = 0; int ic = -1, il = -1, ir = -1;
-            if (has_c) wave_view_nearest(lane_pool + lv.cur_off, lv.cur_n, get_id(ln - 1), window, x, y, lane, dc, ic);
-            if (has_l) wave_view_nearest(lane_pool + lv.left_off, lv.left_n, get_id(ln - 2), window, x, y, lane, dl, il);
-            if (has_r) wave_view_nearest(lane_pool + lv.right_off, lv.right_n, get_id(ln), window, x, y, lane, dr, ir);
-            if (has_c) {
-                const int idc = ic >= 0 ? ic : get_id(ln - 1);
-                if ((long long)idc + window >= (long long)lv.cur_n) f |= DMPP_EGO_LANE_END;
-            }
-            if (ic >= 0) set_id(ln - 1, ic);
-            if (il >= 0) set_id(ln - 2, il);
-            if (ir >= 0) set_id(ln, ir);
-            // 5. lane number: only on a resident map, where k_resolve_map derives the new views
-            if (map_mode && ic >= 0) {
-                const double margin = 0.25 * lv.lane_width, rc = sqrt(dc);
-                if (il >= 0 && rc - sqrt(dl) > margin) ln_new = ln - 1;
-                else if (ir >= 0 && rc - sqrt(dr) > margin) ln_new = ln + 1;
-                if (lane == kLaneNumWord) w = ln_new;
-            }
-            // 6. the grid does not follow the ego
-            if (c.grid_stage) {
-                const double fx = floor((x - si.grid_origin.x) / c.cell), fy = floor((y - si.grid_origin.y) / c.cell);
-                if (!(fx >= 0 && fx < (double)c.grid_w && fy >= 0 && fy < (double)c.grid_h)) f |= DMPP_EGO_OFF_GRID;
-            }
+            if (p.path_end) f |= DMPP_EGO_PATH_END;
+            adv_store_pose(w, lane, p);
+            adv_lane_step(lane_pool, si.lanes, ln, m.window, map_mode, p.x, p.y, lane, w, f, ln_new);
+            if (c.grid_stage && adv_off_grid(c, si, p.x, p.y)) f |= DMPP_EGO_OFF_GRID;
         }
     }
-    if (lane < kWords) reinterpret_cast<int*>(&out[s])[lane] = w;
-    if (trace) {                                        // (shuffles: every lane takes part)
-        const int id_cur = get_id(clampi(ln_new - 1, 0, DMPP_LANESUM - 1));
-        const double tx = __hiloint2double(__shfl(w, 1, 64), __shfl(w, 0, 64)), ty = __hiloint2double(__shfl(w, 3, 64), __shfl(w, 2, 64));
-        const double td = __hiloint2double(__shfl(w, 5, 64), __shfl(w, 4, 64)), tv = __hiloint2double(__shfl(w, 7, 64), __shfl(w, 6, 64));
-        if (lane == 0) {
-            EgoTrace t;
-            t.pose.x = tx; t.pose.y = ty; t.pose.dir = td; t.velocity = tv;
-            t.id_cur = id_cur; t.lane_num = ln_new; t.flags = f; t._pad = 0;
-            trace[s] = t;
-        }
-    }
+    if (lane < kSiWords) reinterpret_cast<int*>(&out[s])[lane] = w;
+    if (trace) adv_store_trace(trace, s, lane, w, ln_new, f);
     if (lane == 0) flags[s] = f;
 }
 

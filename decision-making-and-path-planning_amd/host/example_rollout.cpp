@@ -4,6 +4,8 @@
 // device (pp_score_begin: one RolloutScore record per scene, nothing fetched per tick): collisions, worst clearance, distance.
 // With --fleet the egos share one world (pp_set_fleet): every scene keeps 8 free pool entries behind its own
 // obstacles, the nearest egos are written there after every advance, and the scorecard tells ego-ego contact from the rest.
+// With --route the egos drive a ring of four roads on the map store (pp_set_map + pp_set_egos) along a route each (pp_set_route,
+// DESIGN.md §4f): the advance step takes them road -> pre-junction -> junction -> next road, and the host prints the legs completed.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -13,8 +15,92 @@
 
 #define CHECK(expr) do { int rc__ = (expr); if (rc__) { std::fprintf(stderr, "%s: %s\n", #expr, pp_last_error()); return 2; } } while (0)
 
+// --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
+// degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off.
+static int run_route()
+{
+    const int n = 64, ticks = 1200, P = 260, JP = 40, n_lanes = 2;
+    const double kPi = 3.14159265358979323846, step = 0.5, w = 3.75;
+    const double kr = (70.0 * kPi / 180.0) / ((P - 1) * step), kj = (20.0 * kPi / 180.0) / ((JP + 1) * step);
+    std::vector<GlobalPoint3D> pts; std::vector<GlobalPoint2D> jpts; std::vector<MapLane> lanes; std::vector<MapJunction> junc;
+    std::vector<int32_t> first = { 0 };
+    auto arc = [](double x0, double y0, double th0, double k, double s, double d, double* x, double* y, double* th) {
+        *th = th0 + k * s;
+        *x = x0 + (std::sin(*th) - std::sin(th0)) / k - d * std::sin(*th); *y = y0 - (std::cos(*th) - std::cos(th0)) / k + d * std::cos(*th);
+    };
+    double x0 = 300, y0 = 200, th0 = 0;
+    for (int r = 0; r < 4; r++) {
+        double ex, ey, eth;
+        for (int l = 0; l < n_lanes; l++) {
+            lanes.push_back({ (int32_t)pts.size(), P, n_lanes, 0 });
+            for (int i = 0; i < P; i++) { GlobalPoint3D q; arc(x0, y0, th0, kr, step * i, w * (1 - l), &q.x, &q.y, &eth); q.dir = std::fmod(eth * 180.0 / kPi, 360.0); pts.push_back(q); }
+        }
+        first.push_back((int32_t)lanes.size());
+        arc(x0, y0, th0, kr, step * (P - 1), 0, &ex, &ey, &eth);
+        for (int l = 0; l < n_lanes; l++) {
+            junc.push_back({ r + 1, (r + 1) % 4 + 1, l + 1, l + 1, (int32_t)jpts.size(), JP });
+            for (int i = 0; i < JP; i++) { GlobalPoint2D q; double t; arc(ex, ey, eth, kj, step * (i + 1), w * (1 - l), &q.x, &q.y, &t); jpts.push_back(q); }
+        }
+        arc(ex, ey, eth, kj, step * (JP + 1), 0, &x0, &y0, &th0);
+    }
+    std::vector<uint8_t> attr(pts.size(), 0); std::vector<uint16_t> width(pts.size(), 375);
+    MapDesc map{}; map.n_roads = 4; map.n_lanes = (int32_t)lanes.size(); map.n_points = (int32_t)pts.size(); map.n_junctions = (int32_t)junc.size(); map.n_jpoints = (int32_t)jpts.size();
+    map.road_first_lane = first.data(); map.lanes = lanes.data(); map.points = pts.data(); map.lanechg_attribute = attr.data(); map.lane_width_cm = width.data();
+    map.junctions = junc.data(); map.jpoints = jpts.data();
+
+    PlannerConfig cfg; pp_default_config(&cfg, 128, 128); cfg.grid_stage = 0;      // (the grid does not follow the ego: DESIGN.md §4f)
+    PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = 1; caps.max_lane_pts_total = (int32_t)pts.size(); caps.max_ref_pts_total = (int32_t)jpts.size();
+    std::vector<SceneIn> in(n); std::vector<SceneState> st(n);
+    {   // generated records for everything the map does not decide (DecisionOut, state), then the egos onto the ring
+        std::vector<GlobalPoint3D> gl((size_t)n * 3 * PP_GEN_LANE_PTS); std::vector<uint8_t> ga(gl.size()); std::vector<GlobalPoint2D> gr((size_t)n * PP_GEN_REF_PTS);
+        std::vector<ObPoint> go(1); std::vector<ObMotion> gm(1);
+        CHECK(pp_gen_scenes(&cfg, 0, n, 0, 0, in.data(), gl.data(), ga.data(), gr.data(), go.data(), gm.data(), st.data()));
+    }
+    std::vector<RouteLeg> legs; std::vector<int32_t> route_first = { 0 };
+    for (int s = 0; s < n; s++) {
+        const int road = s % 4 + 1, lane = (s / 4) % n_lanes + 1, id = 100 + (s * 7) % 80, n_legs = 3 + s % 4;
+        const GlobalPoint3D& q = pts[(size_t)lanes[(size_t)first[(size_t)road - 1] + lane - 1].point_off + id];
+        SceneIn& e = in[(size_t)s];
+        e.loc.globalpoint = q; e.loc.velocity = 20; e.loc.pos = 0; e.loc.road_num = road; e.loc.lane_num = lane; e.loc.path_num = 0;
+        e.loc.last_roadnum = road; e.loc.next_roadnum = road % 4 + 1; e.loc.last_lanenum = lane; e.loc.next_lanenum = lane;
+        for (int k = 0; k < DMPP_LANESUM; k++) { e.loc.id[k] = id; e.out_lane_no[k] = k < n_lanes ? (uint16_t)(k + 1) : 0; }
+        e.lanes = LaneView{}; e.ref_off = e.ref_n = e.obs_off = e.obs_n = 0; e.stub_attribute = 1; e.period_last = 100;
+        st[(size_t)s].z_target_lanenum = lane; st[(size_t)s].d_his_target_lanenum = lane;
+        for (int k = 0; k < n_legs; k++) { RouteLeg g{}; g.road_num = (road - 1 + k) % 4 + 1; g.stub_attribute = 1; for (int l = 0; l < n_lanes; l++) g.out_lane_no[l] = (uint16_t)(l + 1); legs.push_back(g); }
+        route_first.push_back((int32_t)legs.size());
+    }
+    pp_handle h = nullptr;
+    CHECK(pp_create(&cfg, 0, &caps, &h));
+    CHECK(pp_set_map(h, &map));
+    CHECK(pp_set_egos(h, n, in.data(), nullptr, nullptr, 0));
+    CHECK(pp_set_state(h, st.data(), n));
+    RouteModel rm; CHECK(pp_default_route_model(&rm));
+    CHECK(pp_set_route(h, (int)legs.size(), legs.data(), route_first.data(), &rm));
+    EgoModel model; pp_default_ego_model(&model);
+    long long last = 0;
+    CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
+    CHECK(pp_sync(h));
+    std::vector<int32_t> flags(n); std::vector<SceneIn> end(n);
+    CHECK(pp_get_ego_flags(h, flags.data(), n));
+    CHECK(pp_get_scene_in(h, end.data(), n));
+    int arrived = 0, missed = 0, other = 0, legs_done = 0;
+    std::printf("route: legs completed per ego (of its route):");
+    for (int s = 0; s < n; s++) {
+        const int f = flags[(size_t)s], total = route_first[(size_t)s + 1] - route_first[(size_t)s];
+        const int done = end[(size_t)s].loc.path_num + ((f & DMPP_EGO_ROUTE_END) ? 1 : 0);
+        std::printf(" %d/%d", done, total);
+        legs_done += done; arrived += (f & DMPP_EGO_ROUTE_END) != 0; missed += f == DMPP_EGO_LANE_END; other += (f & ~(DMPP_EGO_LANE_END | DMPP_EGO_ROUTE_END)) != 0;
+    }
+    std::printf("\nroute: %d egos on a ring of 4 roads for %d ticks (last tick id %lld): %d legs completed, %d arrived (ROUTE_END), %d missed an exit, %d with another flag\n",
+                n, ticks, last, legs_done, arrived, missed, other);
+    pp_destroy(h);
+    std::printf("example_rollout ok\n");
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && std::strcmp(argv[1], "--route") == 0) return run_route();
     const bool fleet = argc > 1 && std::strcmp(argv[1], "--fleet") == 0;
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);

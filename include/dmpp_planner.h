@@ -239,6 +239,24 @@ int  pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const F
  * Only the obs_n entries the tick reads are returned: peer slots beyond them (left as they are) are not. */
 int  pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap);
 
+/* ---- route following: rollout egos cross junctions onto the next road -----------------------------------------
+ * pp_set_route gives every resident scene a ROUTE: the legs [route_first[s], route_first[s+1]) of `legs` (host pointers;
+ * route_first has n_scenes + 1 entries, starts at 0, ends at n_legs_total and never decreases; an empty run leaves the scene
+ * unrouted).  loc.path_num is the 0-based index of the ego's current leg within its own route.  From then on pp_advance_async
+ * runs the routed form of its kernel (k_advance_route): an unfrozen scene with a route and 0 <= path_num < its leg count is moved
+ * road -> pre-junction (pos 1, from rm->pre_points lane points before the end of its lane, when the map has a junction from its
+ * lane to the next leg's road) -> junction (pos 2, on the last lane point) -> next road (pos 0, at the end of the polyline;
+ * path_num, out_lane_no and stub_attribute become those of the next leg), and the lane end only freezes an ego that has no
+ * junction to take: DMPP_EGO_LANE_END alone when it missed its exit lane, DMPP_EGO_LANE_END | DMPP_EGO_ROUTE_END on the last leg.
+ * Every other scene advances as before.  The resident records are not touched: the first tick reads what the caller uploaded.
+ * PP_ERR_STATE: the scenes are not resident from pp_set_map + pp_set_egos, there are none, or an update is staged for the next
+ * tick.  PP_ERR_ARG: a bad route_first, a road_num outside the map, pre_points < 0.  Nothing changes on these.  (A device error
+ * during the upload itself, PP_ERR_HIP, leaves routing off: never half a route.)  One host wait.
+ * n_legs_total = 0 (pointers may be NULL): routing off; pp_set_scenes / pp_set_egos / pp_set_n_scenes / pp_set_map switch it off
+ * too.  A handle that never calls pp_set_route allocates and launches none of this. */
+int  pp_default_route_model(RouteModel* rm);         /* pre_points 60: 30 m of 0.5 m points */
+int  pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int32_t* route_first, const RouteModel* rm);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -302,7 +320,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
 /* sizeof of an ABI struct, for bindings to check their mirror: 0 PlannerConfig, 1 PlannerCaps,
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
- * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel */
+ * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -294,6 +294,21 @@ typedef struct FleetModel {
  * into PlanOut.ob.type / PlanOut.around[k].Ob_Attr.type and tells the caller WHICH ego was in the way) */
 #define DMPP_OB_PEER 0x40000000
 
+/* ---- route following (build-defined: the simulated localisation module of a rollout) --------
+ * pp_set_route gives every scene a route: a run of RouteLeg records, one per road it drives.  The advance step then
+ * moves a routed ego road -> pre-junction -> junction -> next road; loc.path_num is the 0-based index of the ego's
+ * current leg within its own route. */
+typedef struct RouteLeg {               /* one z_RoadNavi entry (PathInfo): what Decision.cpp reads of it */
+    int32_t  road_num;                  /* 1-based road of this leg                                       */
+    int32_t  stub_attribute;            /* Decision.cpp:385,470                                           */
+    uint16_t out_lane_no[DMPP_LANESUM]; /* exit lanes of this road, 0-terminated (Decision.cpp:696)       */
+} RouteLeg;                                                                 /* 24 B */
+typedef struct RouteModel {
+    int32_t pre_points;                 /* lane points before the end of a lane from which the ego is in the pre-junction */
+    int32_t _pad;
+} RouteModel;                                                               /* 8 B */
+#define DMPP_EGO_ROUTE_END 16  /* the ego came to the end of the LAST leg of its route: it arrived                */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

@@ -7,7 +7,9 @@ SCORE=1: the rollout leg runs with the scorecard on (pp_score_begin) and prints 
 a rollout leg without and one with scoring, alternating (the cost of scoring on one build).
 FLEET=K: every run has a rollout leg with the fleet on (pp_set_fleet, K peer slots per scene; FLEET_WORLD=<scenes per world>, 0 or
 unset: one world of all scenes; FLEET_RANGE=<metres>, default the model's) and one with the fleet off whose scenes carry K far-away
-obstacles more - the same obs_n, or the comparison would charge the fleet for longer obstacle lists -, alternating."""
+obstacles more - the same obs_n, or the comparison would charge the fleet for longer obstacle lists -, alternating.
+ROUTE=1: every run has a rollout leg of obstacle-free egos on the ring of tests/route_scenes.py (map store, grid stage off) with
+their routes set (pp_set_route: k_advance_route) and one without (k_advance_egos: the egos freeze at their lane ends), alternating."""
 import os
 import statistics
 import sys
@@ -72,6 +74,29 @@ def fleet_run(on):
     return n * steps / dt, mean_obs
 
 
+def route_run(on):
+    import route_scenes as rs
+    rcfg = dm.default_config(128)
+    rcfg["grid_stage"] = 0
+    m = rs.build_ring(dm)
+    sc, legs, rf = rs.make_egos(dm, rcfg, m, n, seed=5, ids=(10, 250), legs=(6, 10))
+    pl = dm.Planner(rcfg, device=0, **rs.caps(m, n))
+    pl.set_map(m)
+    pl.set_egos(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    if on:
+        pl.set_route(legs, rf)
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    frozen = int((pl.ego_flags() != 0).sum())
+    pl.close()
+    return n * steps / dt, frozen
+
+
 def rollout_run(score=SCORE == "1"):
     pl, _ = fresh()
     if score:
@@ -133,6 +158,19 @@ if FLEET > 0:
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more fleet rollout alone
         fleet_run(True)
+    sys.exit(0)
+if os.environ.get("ROUTE", "0") == "1":
+    off, on = [], []
+    for r in range(runs):
+        a, fa = route_run(False)
+        b, fb = route_run(True)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos  route off %.3f M ticks/s (%d frozen at the end)   route on %.3f M ticks/s (%d frozen)" % (r, n, a / 1e6, fa, b / 1e6, fb), flush=True)
+    print("median  %d ring egos  route off %.3f M ticks/s (spread %.3f)   route on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more routed rollout alone
+        route_run(True)
     sys.exit(0)
 if SCORE == "ab":
     off, on = [], []
