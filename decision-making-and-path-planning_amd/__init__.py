@@ -120,6 +120,7 @@ class _P3(C.Structure):          # GlobalPoint3D passed by value
 
 
 _lib = None
+_hip = None          # the HIP runtime itself, for Planner.write_device only
 
 
 class PlannerError(RuntimeError):
@@ -626,3 +627,19 @@ class Planner:
         sz = C.c_size_t()
         p = self.lib.pp_device_ptr(self.h, which, C.byref(sz))
         return p, sz.value
+
+    def write_device(self, which, array):
+        """Host wait (pp_sync), then a blocking hipMemcpy of `array` over the start of the handle's buffer `which` (pp_device_ptr):
+        inputs written where an RCCL scatter would put them, or records a test puts in the place of a finished tick's."""
+        global _hip
+        self.sync()
+        ptr, size = self.device_ptr(which)
+        raw = np.frombuffer(np.ascontiguousarray(array).tobytes(), np.uint8)
+        if not ptr or raw.size > size:
+            raise PlannerError(f"write_device: buffer {which} holds {size} B, the array has {raw.size} B")
+        if _hip is None:
+            _hip = C.CDLL("libamdhip64.so")          # the runtime the process already has (libdmpp.so is loaded)
+            _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        rc = _hip.hipMemcpy(ptr, raw.ctypes.data, raw.size, 1)          # hipMemcpyHostToDevice
+        if rc != 0:
+            raise PlannerError(f"write_device: hipMemcpy failed with {rc}")

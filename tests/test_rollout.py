@@ -8,7 +8,9 @@ import math
 import numpy as np
 import pytest
 
+import advance_backends as ab
 import ego_model as em
+import map_scenes as ms
 from parity_util import compare
 
 gpu = pytest.mark.gpu
@@ -51,11 +53,48 @@ def _scene(dm, cfg, lane_num=2, lane_sum=3, n_pts=320, ego_id=50, v=36.0, lane_w
     return si, pool
 
 
-def _adv(dm, cfg, si, po, pool, near_id=10, afresh=0, flag=0, map_mode=False, model=None):
+def _map3(dm, n_pts=320, lane_w=3.75):
+    """The three lanes of _scene as a map store: one road, lane 1 leftmost (y = +lane_w), lane 2 at 0, lane 3 at -lane_w."""
+    pts = np.zeros(3 * n_pts, dm.GlobalPoint3D)
+    for k, dy in enumerate((lane_w, 0.0, -lane_w)):
+        pts["x"][k * n_pts:(k + 1) * n_pts] = 100.0 + 0.5 * np.arange(n_pts)
+        pts["y"][k * n_pts:(k + 1) * n_pts] = dy
+    return dict(road_first_lane=np.array([0, 3], np.int32), lanes=np.array([(k * n_pts, n_pts, 3, 0) for k in range(3)], dm.MapLane), points=pts,
+                lanechg_attribute=np.zeros(3 * n_pts, np.uint8), lane_width_cm=np.full(3 * n_pts, int(round(lane_w * 100)), np.uint16),
+                junctions=np.zeros(0, dm.MapJunction), jpoints=np.zeros(1, dm.GlobalPoint2D))
+
+
+def _state(dm, near_id=10, afresh=0):
     st = np.zeros(1, dm.SceneState)
     st["path_near_id"], st["afresh_planning"] = near_id, afresh
-    out, f, _ = em.advance(cfg, dm.default_ego_model() if model is None else model, si, po, st, np.array([flag], np.int32), pool, map_mode)
-    return out[0], int(f[0])
+    return st
+
+
+class _Adv:
+    """One advance of one scene on a backend of tests/advance_backends.py: the known answers below are written once against it."""
+    def __init__(self, dm, runner):
+        self.dm, self.run, self.name = dm, runner, runner.name
+
+    def steps(self, cfg, si, steps, pool, model=None, map_mode=False):
+        """steps: (PlanOut, near_id, afresh) one after the other on one handle.  map_mode: `pool` is a map, the views are its."""
+        dm = self.dm
+        if map_mode:
+            si = si.copy()
+            si["loc"]["road_num"] = 1
+            si = ms.resolve(dm, pool, si)
+        res = self.run(cfg, dm.default_ego_model() if model is None else model, si, [(po, _state(dm, k, a)) for po, k, a in steps],
+                       dict(map=pool) if map_mode else dict(lane_pool=pool))
+        return [(r.out[0], int(r.flags[0])) for r in res]
+
+    def __call__(self, cfg, si, po, pool, near_id=10, afresh=0, map_mode=False, model=None):
+        return self.steps(cfg, si, [(po, near_id, afresh)], pool, model, map_mode)[0]
+
+
+_LOG = []
+
+
+def _runner(name, log=None):
+    return ab.Runner(ab.ModelBackend() if name == "model" else ab.DeviceBackend(), log)
 
 
 @pytest.fixture()
@@ -65,97 +104,121 @@ def cfg0(dm):
     return cfg
 
 
-def test_kat_speed(dm):
+def _kat_speed(dm, cfg0, adv):
     # defaults: dt 0.1 s, max_acc 2, max_dec 4 -> at most 2*0.1*3.6 = 0.72 km/h up, 4*0.1*3.6 = 1.44 km/h down per tick
-    assert em.next_speed(36.0, 0, 0.0, 36.0, 0.1, 2.0, 4.0) == 36.0                 # at the target: held
-    assert em.next_speed(0.0, 0, 0.0, 30.0, 0.1, 2.0, 4.0) == 2.0 * 0.1 * 3.6       # rate limit up: 0 + 0.72
-    assert em.next_speed(29.5, 0, 0.0, 30.0, 0.1, 2.0, 4.0) == 30.0                 # 29.5 + 0.72 > 30: the target
-    assert em.next_speed(30.0, 0, 0.0, 0.0, 0.1, 2.0, 4.0) == 30.0 - 4.0 * 0.1 * 3.6   # rate limit down: 30 - 1.44
-    assert em.next_speed(1.0, 0, 0.0, 0.0, 0.1, 2.0, 4.0) == 0.0                    # 1 - 1.44 < 0: the target
-    assert em.next_speed(20.0, 0, 0.0, math.inf, 0.1, 2.0, 4.0) == 20.0             # a non-finite desspd holds v
-    assert em.next_speed(20.0, 0, 0.0, -math.inf, 0.1, 2.0, 4.0) == 20.0
+    assert [float(dm.default_ego_model()[k][0]) for k in ("dt", "max_acc", "max_dec")] == [0.1, 2.0, 4.0]
+    si, pool = _scene(dm, cfg0)
+
+    def next_speed(v, desaccVd, desacc, desspd):
+        """The speed one advance gives (path from x = 0 at 0.5 m: with k0 = 0 the ego's x is t * 0.5 = s, the length gone, exactly)."""
+        si["loc"]["velocity"] = v
+        po = _straight(dm, x0=0.0)
+        po["result"]["desaccVd"], po["result"]["desacc"], po["result"]["desspd"] = desaccVd, desacc, desspd
+        out, f = adv(cfg0, si, po, pool, near_id=0)
+        assert f == 0
+        return float(out["loc"]["velocity"]), float(out["loc"]["globalpoint"]["x"])
+    assert next_speed(36.0, 0, 0.0, 36.0)[0] == 36.0                 # at the target: held
+    assert next_speed(0.0, 0, 0.0, 30.0)[0] == 2.0 * 0.1 * 3.6       # rate limit up: 0 + 0.72
+    assert next_speed(29.5, 0, 0.0, 30.0)[0] == 30.0                 # 29.5 + 0.72 > 30: the target
+    assert next_speed(30.0, 0, 0.0, 0.0)[0] == 30.0 - 4.0 * 0.1 * 3.6   # rate limit down: 30 - 1.44
+    assert next_speed(1.0, 0, 0.0, 0.0)[0] == 0.0                    # 1 - 1.44 < 0: the target
+    assert next_speed(20.0, 0, 0.0, math.inf)[0] == 20.0             # a non-finite desspd holds v
+    assert next_speed(20.0, 0, 0.0, -math.inf)[0] == 20.0
     # desaccVd: v + desacc*dt*3.6, never below 0: 5 - 3*0.1*3.6 = 3.92; 1 - 1.08 < 0 -> 0 (the rate limits do not apply)
-    assert em.next_speed(5.0, 1, -3.0, 99.0, 0.1, 2.0, 4.0) == 5.0 + -3.0 * 0.1 * 3.6
-    assert abs(em.next_speed(5.0, 1, -3.0, 99.0, 0.1, 2.0, 4.0) - 3.92) < 1e-12
-    assert em.next_speed(1.0, 1, -3.0, 99.0, 0.1, 2.0, 4.0) == 0.0
+    assert next_speed(5.0, 1, -3.0, 99.0)[0] == 5.0 + -3.0 * 0.1 * 3.6
+    assert abs(next_speed(5.0, 1, -3.0, 99.0)[0] - 3.92) < 1e-12
+    assert next_speed(1.0, 1, -3.0, 99.0)[0] == 0.0
     # distance: mean of the two speeds over dt: (36 + 36)/2 km/h = 10 m/s for 0.1 s = 1 m; braking 1 -> 0 km/h: 0.5/3.6*0.1 m
-    assert em.step_length(36.0, 36.0, 0.1) == 1.0
-    assert abs(em.step_length(1.0, 0.0, 0.1) - 0.5 / 36.0) < 1e-15
+    assert next_speed(36.0, 0, 0.0, 36.0)[1] == 1.0
+    assert abs(next_speed(1.0, 0, 0.0, 0.0)[1] - 0.5 / 36.0) < 1e-15
+    if adv.name == "model":                                          # ... and the two functions of the model by themselves
+        assert em.next_speed(29.5, 0, 0.0, 30.0, 0.1, 2.0, 4.0) == 30.0 and em.next_speed(1.0, 1, -3.0, 99.0, 0.1, 2.0, 4.0) == 0.0
+        assert em.step_length(36.0, 36.0, 0.1) == 1.0 and abs(em.step_length(1.0, 0.0, 0.1) - 0.5 / 36.0) < 1e-15
 
 
-def test_kat_straight_path_lands_on_a_point(dm, cfg0):
+def _kat_straight_path_lands_on_a_point(dm, cfg0, adv):
     # v = v' = 36 km/h -> s = 1 m.  Start P[10] = (105, 0); segments of 0.5 m: a = 0.5 after segment 10, a + L = 1.0 >= s on
     # segment 11 with t = (1 - 0.5)/0.5 = 1 -> x = 105.5 + 1*0.5 = 106 exactly (the ego ends ON point 12, on segment 11), dir 0
     si, pool = _scene(dm, cfg0)
     po = _straight(dm)
     po["result"]["desspd"] = 36.0
-    out, f = _adv(dm, cfg0, si, po, pool)
+    out, f = adv(cfg0, si, po, pool)
     g = out["loc"]["globalpoint"]
     assert (float(g["x"]), float(g["y"]), float(g["dir"]), float(out["loc"]["velocity"]), f) == (106.0, 0.0, 0.0, 36.0, 0)
     # ids: lane points x = 100 + 0.5 k -> point 12 of every view, searched over [50, 82)?  No: the ids start at 50 = x 125, ahead
     # of the ego; ids never go backwards, the nearest point of [50, 82) to x = 106 is 50 itself
     assert out["loc"]["id"].tolist() == [50, 50, 50, 50, 50, 50, 50, 50]
     # a path that was replanned starts at the ego: k0 = 0 whatever the (old-path) index says -> 100 + 1 = 101
-    out, f = _adv(dm, cfg0, si, po, pool, near_id=150, afresh=1)
+    out, f = adv(cfg0, si, po, pool, near_id=150, afresh=1)
     assert float(out["loc"]["globalpoint"]["x"]) == 101.0 and f == 0
     # between two points: v = 18 -> s = 0.5*(18 + 18)/3.6*0.1 = 0.5 m ... and 27 km/h -> 0.75 m: segment 11, t = 0.5 -> 105.75
     si["loc"]["velocity"] = 27.0
     po["result"]["desspd"] = 27.0
-    out, f = _adv(dm, cfg0, si, po, pool)
+    out, f = adv(cfg0, si, po, pool)
     assert abs(float(out["loc"]["globalpoint"]["x"]) - 105.75) < 1e-12 and f == 0
     # everything else is carried over
     for name in ("dec", "lanes", "ref_off", "ref_n", "obs_off", "obs_n", "stub_attribute", "out_lane_no", "period_last", "grid_origin", "goal"):
         assert out[name].tobytes() == si[0][name].tobytes()
 
 
-def test_kat_zero_length_segment_and_standstill(dm, cfg0):
+def _kat_zero_length_segment_and_standstill(dm, cfg0, adv):
     si, pool = _scene(dm, cfg0)
     po = _straight(dm)
     po["result"]["desspd"] = 36.0
     # points 11 and 12 coincide (segment 11 has length 0 and is skipped): from P[10] = 105: segment 10 -> a = 0.5, segment 11
     # skipped, segment 12 runs from 105.5 (P[12] moved onto P[11]) to 106.5: L = 1, t = (1 - 0.5)/1 = 0.5 -> x = 106.0
     po["road_points"]["x"][0, 12] = po["road_points"]["x"][0, 11]
-    out, f = _adv(dm, cfg0, si, po, pool)
+    out, f = adv(cfg0, si, po, pool)
     assert float(out["loc"]["globalpoint"]["x"]) == 106.0 and float(out["loc"]["globalpoint"]["dir"]) == 0.0 and f == 0
     # standstill: v = v' = 0 -> s = 0: the ego sits on P[k0] and keeps its heading (no segment)
     si["loc"]["velocity"] = 0.0
     po["result"]["desspd"] = 0.0
-    out, f = _adv(dm, cfg0, si, po, pool)
+    out, f = adv(cfg0, si, po, pool)
     assert (float(out["loc"]["globalpoint"]["x"]), float(out["loc"]["globalpoint"]["dir"]), f) == (105.0, 77.0, 0)
 
 
-def test_kat_path_end_and_bad_path(dm, cfg0):
+def _kat_path_end_and_bad_path(dm, cfg0, adv):
     si, pool = _scene(dm, cfg0)
     po = _straight(dm)
     po["result"]["desspd"] = 36.0
     # from P[198] = 199 only one segment of 0.5 m is left, s = 1 m: the ego stops on P[199] = 199.5, heading of segment 198
-    out, f = _adv(dm, cfg0, si, po, pool, near_id=198)
+    out, f = adv(cfg0, si, po, pool, near_id=198)
     assert (float(out["loc"]["globalpoint"]["x"]), float(out["loc"]["globalpoint"]["dir"]), f) == (199.5, 0.0, em.PATH_END)
     assert float(out["loc"]["velocity"]) == 36.0
     # from P[197]: a + L = 1.0 >= s on segment 198: the step ENDS on point 199, it does not reach past it
-    out, f = _adv(dm, cfg0, si, po, pool, near_id=197)
+    out, f = adv(cfg0, si, po, pool, near_id=197)
     assert (float(out["loc"]["globalpoint"]["x"]), f) == (199.5, 0)
     # a NaN two points ahead (P[12]) is on the walked part (segment 11 is needed for s = 1): loc untouched, BAD_PATH
     po["road_points"]["y"][0, 12] = np.nan
-    out, f = _adv(dm, cfg0, si, po, pool)
+    out, f = adv(cfg0, si, po, pool)
     assert f == em.BAD_PATH and out["loc"].tobytes() == si[0]["loc"].tobytes()
     # the same NaN beyond the walked part (s = 0.5 m ends on segment 10) does not matter
     si["loc"]["velocity"] = 18.0
     po["result"]["desspd"] = 18.0
-    out, f = _adv(dm, cfg0, si, po, pool)
+    out, f = adv(cfg0, si, po, pool)
     assert (float(out["loc"]["globalpoint"]["x"]), f) == (105.5, 0)
-    # a frozen scene is carried over unchanged and keeps its flags
-    out, f = _adv(dm, cfg0, si, _straight(dm), pool, flag=em.LANE_END)
-    assert f == em.LANE_END and out.tobytes() == si[0].tobytes()
+    # a frozen scene is carried over unchanged and keeps its flags.  The flag is reached the honest way: the step of
+    # test_kat_lane_end (100 lane points, from 133 to 134 = point 68: 68 + 32 >= 100) sets LANE_END, the next step finds it set
+    se, _ = _scene(dm, cfg0, ego_id=60)
+    se["lanes"]["cur_n"] = 100
+    pe = _straight(dm, x0=133.0)
+    pe["result"]["desspd"] = 36.0
+    (mid, f0), (out, f) = adv.steps(cfg0, se, [(pe, 0, 0), (_straight(dm), 10, 0)], pool)
+    assert (f0, float(mid["loc"]["globalpoint"]["x"]), int(mid["loc"]["id"][1])) == (em.LANE_END, 134.0, 68)
+    assert f == em.LANE_END and out.tobytes() == mid.tobytes()
+    if adv.name == "model":                                          # the model takes the flag word as it is given
+        st = _state(dm)
+        o, fl, _ = em.advance(cfg0, dm.default_ego_model(), si, _straight(dm), st, np.array([em.LANE_END], np.int32), pool, False)
+        assert int(fl[0]) == em.LANE_END and o[0].tobytes() == si[0].tobytes()
 
 
-def test_kat_ids(dm, cfg0):
+def _kat_ids(dm, cfg0, adv):
     si, pool = _scene(dm, cfg0, ego_id=50, v=36.0)
     # ego to x = 125.25 + 1.0: path from x0 = 125.25, k0 = 0, s = 1 -> x = 126.25, exactly between lane points 52 (126.0) and
     # 53 (126.5): d2 = 0.0625 for both in the current view -> the FIRST minimum, 52.  Left / right views (|dy| = 3.75): 52 too.
     po = _straight(dm, x0=125.25)
     po["result"]["desspd"] = 36.0
-    out, f = _adv(dm, cfg0, si, po, pool, near_id=0)
+    out, f = adv(cfg0, si, po, pool, near_id=0)
     assert float(out["loc"]["globalpoint"]["x"]) == 126.25
     assert out["loc"]["id"].tolist() == [52, 52, 52, 50, 50, 50, 50, 50] and f == 0       # slots 1 (cur), 0 (left), 2 (right)
     # window edge: window 4 searches [50, 54) only; the ego at x = 131 (point 62) gets the last point of the window, 53
@@ -163,52 +226,114 @@ def test_kat_ids(dm, cfg0):
     model["window"] = 4
     po = _straight(dm, x0=130.0)
     po["result"]["desspd"] = 36.0
-    out, f = _adv(dm, cfg0, si, po, pool, near_id=0, model=model)
+    out, f = adv(cfg0, si, po, pool, near_id=0, model=model)
     assert out["loc"]["id"].tolist() == [53, 53, 53, 50, 50, 50, 50, 50]
     # an empty view keeps its id: no right lane (right_n = 0), and an id at / beyond the end of its view
     si2 = si.copy()
     si2["lanes"]["right_n"] = 0
     si2["loc"]["id"][0, 0] = 400                                     # left view: [400, ...) of 320 points is empty
-    out, f = _adv(dm, cfg0, si2, po, pool, near_id=0)
+    out, f = adv(cfg0, si2, po, pool, near_id=0)
     assert out["loc"]["id"].tolist() == [400, 62, 50, 50, 50, 50, 50, 50]
     # lane 1 has no left view, lane 3 (= lane_sum) no right view: slots 0 / 1 and 1 / 2 only
     si3, _ = _scene(dm, cfg0, lane_num=1)
-    out, f = _adv(dm, cfg0, si3, po, pool, near_id=0)
+    out, f = adv(cfg0, si3, po, pool, near_id=0)
     assert out["loc"]["id"].tolist() == [62, 62, 50, 50, 50, 50, 50, 50]
     si3, _ = _scene(dm, cfg0, lane_num=3)
-    out, f = _adv(dm, cfg0, si3, po, pool, near_id=0)
+    out, f = adv(cfg0, si3, po, pool, near_id=0)
     assert out["loc"]["id"].tolist() == [50, 62, 62, 50, 50, 50, 50, 50]
 
 
-def test_kat_lane_end(dm, cfg0):
+def _kat_lane_end(dm, cfg0, adv):
     # 100 points in the current lane, window 32: LANE_END once id' + 32 >= 100, i.e. from id' = 68 on
     si, pool = _scene(dm, cfg0, ego_id=60)
     si["lanes"]["cur_n"] = 100
     for x0, want_id, want_f in ((132.5, 67, 0), (133.0, 68, em.LANE_END)):      # + 1 m: x = 133.5 = point 67, 134.0 = point 68
         po = _straight(dm, x0=x0)
         po["result"]["desspd"] = 36.0
-        out, f = _adv(dm, cfg0, si, po, pool, near_id=0)
+        out, f = adv(cfg0, si, po, pool, near_id=0)
         assert (int(out["loc"]["id"][1]), f) == (want_id, want_f)
 
 
-def test_kat_lane_switch_margin(dm, cfg0):
+def _kat_lane_switch_margin(dm, cfg0, adv):
     # lane width 3.75 -> margin 0.9375.  The ego at lateral offset e from the current lane (same x as a lane point, so the
-    # distances are |e| and 3.75 - |e| exactly): switch when |e| - (3.75 - |e|) > 0.9375, i.e. |e| > 2.34375 (= 75/32, exact)
+    # distances are |e| and 3.75 - |e| exactly): switch when |e| - (3.75 - |e|) > 0.9375, i.e. |e| > 2.34375 (= 75/32, exact).
+    # Map mode is a resident map: the three lanes of _scene as one road of a map store (_map3), the views resolved from it
     si, pool = _scene(dm, cfg0, ego_id=50, v=36.0)
+    m = _map3(dm)
     for e, want in ((2.34375, 2), (2.375, 1), (-2.34375, 2), (-2.375, 3), (0.0, 2)):
         po = _straight(dm, x0=125.0, y=e)
         po["result"]["desspd"] = 36.0
-        out, f = _adv(dm, cfg0, si, po, pool, near_id=0, map_mode=True)
+        out, f = adv(cfg0, si, po, m, near_id=0, map_mode=True)
         assert (int(out["loc"]["lane_num"]), f) == (want, 0), e
-        out, f = _adv(dm, cfg0, si, po, pool, near_id=0, map_mode=False)          # slice mode: held
+        assert int(out["lanes"]["cur_off"]) == 320 * (want - 1)                   # the views are those of the new lane
+        out, f = adv(cfg0, si, po, pool, near_id=0, map_mode=False)          # slice mode: held
         assert int(out["loc"]["lane_num"]) == 2
+    if adv.name == "model":                                          # the model's map mode on the slices themselves, without a map
+        po = _straight(dm, x0=125.0, y=2.375)
+        po["result"]["desspd"] = 36.0
+        o, fl, _ = em.advance(cfg0, dm.default_ego_model(), si, po, _state(dm, 0), np.zeros(1, np.int32), pool, True)
+        assert (int(o["loc"]["lane_num"][0]), int(fl[0])) == (1, 0)
     # off grid: a 128 x 128 grid of 0.25 m cells from the origin (100, -16): x = 126 is cell 104, x = 132.5 would be cell 130
+    # (the goal lies on the grid: the tick the device's advance follows searches it)
     cfg = dm.default_config(128)
     si["grid_origin"]["x"], si["grid_origin"]["y"] = 100.0, -16.0
+    si["goal"]["x"], si["goal"]["y"] = 128.0, 0.0
     for x0, want in ((125.0, 0), (131.5, em.OFF_GRID)):
         po = _straight(dm, x0=x0)
         po["result"]["desspd"] = 36.0
-        assert _adv(dm, cfg, si, po, pool, near_id=0)[1] == want
+        assert adv(cfg, si, po, pool, near_id=0)[1] == want
+
+
+KATS = [_kat_speed, _kat_straight_path_lands_on_a_point, _kat_zero_length_segment_and_standstill, _kat_path_end_and_bad_path, _kat_ids, _kat_lane_end, _kat_lane_switch_margin]
+
+
+def test_kat_speed(dm, cfg0):
+    _kat_speed(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_straight_path_lands_on_a_point(dm, cfg0):
+    _kat_straight_path_lands_on_a_point(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_zero_length_segment_and_standstill(dm, cfg0):
+    _kat_zero_length_segment_and_standstill(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_path_end_and_bad_path(dm, cfg0):
+    _kat_path_end_and_bad_path(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_ids(dm, cfg0):
+    _kat_ids(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_lane_end(dm, cfg0):
+    _kat_lane_end(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_lane_switch_margin(dm, cfg0):
+    _kat_lane_switch_margin(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+@gpu
+@pytest.mark.parametrize("kat", KATS, ids=lambda f: f.__name__[5:])
+def test_kat_on_the_device(dm, cfg0, kat):
+    """The known answers above on k_advance_egos (injected PlanOut / SceneState), each also held against the model step by step."""
+    kat(dm, cfg0, _Adv(dm, _runner("device")))
+
+
+@gpu
+def test_kat_batch_equals_each_case_alone(dm, cfg0):
+    """Every known answer above once more on the device, logged, then all of them as distinct scenes of one launch per group of
+    calls that can share a launch (advance_backends.batched): batch sizes that are no multiple of four, more than one block;
+    every scene gives the bytes it gave alone."""
+    log = []
+    a = _Adv(dm, _runner("device", log))
+    for kat in KATS:
+        kat(dm, cfg0, a)
+    sizes = ab.batched(ab.DeviceBackend(), log)
+    print(f"{len(log)} calls in batches of {sizes}; device against model: {ab.STATS}")
+    assert sum(sizes) >= len(log) and all(n % 4 != 0 and n > 4 for n in sizes)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ the CPU loop."""
 import numpy as np
 import pytest
 
+import advance_backends as ab
 import ego_model as em
 import map_scenes as ms
 import route_model as rmod
@@ -79,110 +80,122 @@ def _path(dm, x0, y=0.0):
     return po
 
 
-def _adv(dm, cfg, m, si, po, legs, flag=0, pre_points=60):
-    st = np.zeros(1, dm.SceneState)
-    rm = dm.default_route_model()
-    rm["pre_points"] = pre_points
-    rf = np.array([0, 0 if legs is None else len(legs)], np.int32)
-    out, f, _ = rmod.advance(dm, cfg, dm.default_ego_model(), rm, legs, rf, m, si, po, st, np.array([flag], np.int32))
-    return out[0], int(f[0])
+class _Adv:
+    """One routed advance of one scene on a backend of tests/advance_backends.py: the known answers below are written once against it."""
+    def __init__(self, dm, runner):
+        self.dm, self.run, self.name = dm, runner, runner.name
+
+    def steps(self, cfg, m, si, pos, legs, pre_points=60):
+        dm = self.dm
+        rm = dm.default_route_model()
+        rm["pre_points"] = pre_points
+        route = None if legs is None else (legs, np.array([0, len(legs)], np.int32), rm)
+        res = self.run(cfg, dm.default_ego_model(), si, [(po, np.zeros(1, dm.SceneState)) for po in pos], dict(map=m), route)
+        return [(r.out[0], int(r.flags[0])) for r in res]
+
+    def __call__(self, cfg, m, si, po, legs, pre_points=60):
+        return self.steps(cfg, m, si, [po], legs, pre_points)[0]
+
+
+def _runner(name, log=None):
+    return ab.Runner(ab.ModelBackend() if name == "model" else ab.DeviceBackend(), log)
 
 
 def _four(loc):
     return tuple(int(loc[k]) for k in ("last_roadnum", "next_roadnum", "last_lanenum", "next_lanenum"))
 
 
-def test_kat_pre_junction_starts_at_pre_points(dm, cfg0):
+def _kat_pre_junction_starts_at_pre_points(dm, cfg0, adv):
     # n_c = 100, pre_points = 60: 0 -> 1 when 99 - id' <= 60, i.e. from id' = 39 (x = 119.5) on.  The ego goes 1 m: from 118.5 it
     # lands on 119.5 = point 39 -> pos 1; from 118.0 on 119.0 = point 38 (99 - 38 = 61 > 60) -> pos 0.  Jn = J(1, 2, lane 2): next_lane 1.
     m = _tiny_map(dm)
     si = _ego(dm, m)
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 118.5), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 118.5), _legs(dm))
     assert (int(out["loc"]["pos"]), int(out["loc"]["id"][1]), f) == (1, 39, 0)
     assert _four(out["loc"]) == (1, 2, 2, 1)                          # last road, next road (leg 1), last lane, Jn.next_lane
     assert (int(out["loc"]["road_num"]), int(out["loc"]["lane_num"]), int(out["loc"]["path_num"])) == (1, 2, 0)
     assert (int(out["ref_off"]), int(out["ref_n"])) == (0, 10)         # the polyline of the four indices, derived behind the step
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 118.0), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 118.0), _legs(dm))
     assert (int(out["loc"]["pos"]), int(out["loc"]["id"][1]), f) == (0, 38, 0) and _four(out["loc"]) == (0, 0, 0, 0)
     # pre_points = 61 takes point 38 in; pre_points = 0 only the last point
-    assert int(_adv(dm, cfg0, m, si, _path(dm, 118.0), _legs(dm), pre_points=61)[0]["loc"]["pos"]) == 1
-    assert int(_adv(dm, cfg0, m, si, _path(dm, 118.5), _legs(dm), pre_points=0)[0]["loc"]["pos"]) == 0
+    assert int(adv(cfg0, m, si, _path(dm, 118.0), _legs(dm), pre_points=61)[0]["loc"]["pos"]) == 1
+    assert int(adv(cfg0, m, si, _path(dm, 118.5), _legs(dm), pre_points=0)[0]["loc"]["pos"]) == 0
 
 
-def test_kat_junction_is_entered_on_the_last_lane_point(dm, cfg0):
+def _kat_junction_is_entered_on_the_last_lane_point(dm, cfg0, adv):
     # pos 1 on lane 2 of road 1, id 90.  From 149.25 the ego lands on 150.25: the nearest lane point of [90, 100) is the last, 99
     # (149.5) = n_c - 1 -> pos 2, road_num / lane_num = next_roadnum / next_lanenum = 2 / 1, every id 0 except slot
     # last_lanenum - 1 = 1: the nearest polyline point of [0, 10) to 150.25 - 150.0 (0.25 away) and 150.5 (0.25 away) tie, the first wins: 0.
     m = _tiny_map(dm)
     si = _ego(dm, m, pos=1, ego_id=90, four=(1, 2, 2, 1))
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 149.25), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 149.25), _legs(dm))
     assert float(out["loc"]["globalpoint"]["x"]) == 150.25
     assert (int(out["loc"]["pos"]), int(out["loc"]["road_num"]), int(out["loc"]["lane_num"]), f) == (2, 2, 1, 0)
     assert out["loc"]["id"].tolist() == [0, 0, 0, 0, 0, 0, 0, 0] and _four(out["loc"]) == (1, 2, 2, 1) and int(out["loc"]["path_num"]) == 0
     # from 149.5 it lands on 150.5 = polyline point 1
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 149.5), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 149.5), _legs(dm))
     assert (int(out["loc"]["pos"]), out["loc"]["id"].tolist(), f) == (2, [0, 1, 0, 0, 0, 0, 0, 0], 0)
     assert (int(out["lanes"]["cur_off"]), int(out["lanes"]["cur_n"])) == (200, 100)        # the views are those of road 2 from here on
     # one point short of the end (from 148.0 to 149.0 = point 98): still pos 1, and no LANE_END although 98 + 32 >= 100 - Jn exists
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 148.0), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 148.0), _legs(dm))
     assert (int(out["loc"]["pos"]), int(out["loc"]["id"][1]), f) == (1, 98, 0)
     # pos 1 without a polyline (the four indices name no junction): "no Jn" -> LANE_END at the lane end, pos held
     si2 = _ego(dm, m, pos=1, ego_id=90, four=(1, 2, 1, 1))
-    out, f = _adv(dm, cfg0, m, si2, _path(dm, 149.5), _legs(dm))
+    out, f = adv(cfg0, m, si2, _path(dm, 149.5), _legs(dm))
     assert (int(out["loc"]["pos"]), int(out["ref_n"]), f) == (1, 0, em.LANE_END)
 
 
-def test_kat_junction_is_left_at_the_end_of_the_polyline(dm, cfg0):
+def _kat_junction_is_left_at_the_end_of_the_polyline(dm, cfg0, adv):
     # pos 2: road 2, lane 1, polyline id in slot last_lanenum - 1 = 1, j = 6; window 32 -> searched [6, 10).  From 154.6 the ego lands
     # on 155.6: nearest polyline point 9 (154.5) = ref_n - 1 -> pos 0, path_num 1, out_lane_no / stub_attribute of leg 1, ids zeroed
     # and the view of lane 1 of road 2 (x = 155 + 0.5 k) searched over [0, 32): 155.5 = point 1 (0.1 away; 156.0 is 0.4 away).
     m = _tiny_map(dm)
     si = _ego(dm, m, pos=2, road=2, lane=1, ego_id=0, four=(1, 2, 2, 1))
     si["loc"]["id"][0, 1] = 6
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 154.6), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 154.6), _legs(dm))
     assert (int(out["loc"]["pos"]), int(out["loc"]["path_num"]), f) == (0, 1, 0)
     assert out["loc"]["id"].tolist() == [1, 0, 0, 0, 0, 0, 0, 0]
     assert (int(out["stub_attribute"]), out["out_lane_no"].tolist()) == (2, [1, 0, 0, 0, 0, 0, 0, 0])
     assert (int(out["loc"]["road_num"]), int(out["loc"]["lane_num"])) == (2, 1) and _four(out["loc"]) == (1, 2, 2, 1)
     # from 152.9 it lands on 153.9: polyline point 8 (154.0) < ref_n - 1 -> still in the junction, the leg index has NOT moved
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 152.9), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 152.9), _legs(dm))
     assert (int(out["loc"]["pos"]), int(out["loc"]["path_num"]), out["loc"]["id"].tolist(), f) == (2, 0, [0, 8, 0, 0, 0, 0, 0, 0], 0)
     assert (int(out["stub_attribute"]), int(out["out_lane_no"][0])) == (1, 2)
     # a junction behind the LAST leg (a caller error): everything is held, ROUTE_END
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 154.6), _legs(dm, 1))
+    out, f = adv(cfg0, m, si, _path(dm, 154.6), _legs(dm, 1))
     assert (int(out["loc"]["pos"]), int(out["loc"]["path_num"]), out["loc"]["id"].tolist(), f) == (2, 0, [0, 9, 0, 0, 0, 0, 0, 0], rmod.ROUTE_END)
 
 
-def test_kat_lane_end_missed_exit_and_arrival(dm, cfg0):
+def _kat_lane_end_missed_exit_and_arrival(dm, cfg0, adv):
     m = _tiny_map(dm)
     # lane 1 of road 1 has no junction: the ego at id' = 68 (x = 134.0; 68 + 32 >= 100) missed its exit lane -> LANE_END alone
     si = _ego(dm, m, lane=1, ego_id=60)
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 133.0, y=3.75), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 133.0, y=3.75), _legs(dm))
     assert (int(out["loc"]["pos"]), int(out["loc"]["id"][0]), f) == (0, 68, em.LANE_END)
     # one point before (id' = 67): nothing yet
-    assert _adv(dm, cfg0, m, si, _path(dm, 132.5, y=3.75), _legs(dm))[1] == 0
+    assert adv(cfg0, m, si, _path(dm, 132.5, y=3.75), _legs(dm))[1] == 0
     # the same pose on lane 2, which has its junction: no flag, and pos 1 (99 - 68 <= 60)
     si = _ego(dm, m, lane=2, ego_id=60)
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 133.0), _legs(dm))
+    out, f = adv(cfg0, m, si, _path(dm, 133.0), _legs(dm))
     assert (int(out["loc"]["pos"]), f) == (1, 0)
     # the last leg (a route of one leg): LANE_END | ROUTE_END = 4 | 16, the ego arrived
-    out, f = _adv(dm, cfg0, m, si, _path(dm, 133.0), _legs(dm, 1))
+    out, f = adv(cfg0, m, si, _path(dm, 133.0), _legs(dm, 1))
     assert (int(out["loc"]["pos"]), f) == (0, em.LANE_END | rmod.ROUTE_END) and f == 20
 
 
-def test_kat_pre_junction_holds_the_lane_number(dm, cfg0):
+def _kat_pre_junction_holds_the_lane_number(dm, cfg0, adv):
     # lane width 3.75 -> margin 0.9375; the ego 2.8 m to the left of lane 2 is 0.95 m from lane 1: 2.8 - 0.95 = 1.85 > 0.9375.
     # On the road (pos 0) the lane number follows (§4c 5.); in the pre-junction it is held - the polyline was chosen by lane
     m = _tiny_map(dm)
     po = _path(dm, 110.0, y=2.8)
-    out, f = _adv(dm, cfg0, m, _ego(dm, m, pos=0, ego_id=20), po, _legs(dm))
+    out, f = adv(cfg0, m, _ego(dm, m, pos=0, ego_id=20), po, _legs(dm))
     assert (int(out["loc"]["lane_num"]), int(out["loc"]["pos"]), f) == (1, 0, 0)
-    out, f = _adv(dm, cfg0, m, _ego(dm, m, pos=1, ego_id=20, four=(1, 2, 2, 1)), po, _legs(dm))
+    out, f = adv(cfg0, m, _ego(dm, m, pos=1, ego_id=20, four=(1, 2, 2, 1)), po, _legs(dm))
     assert (int(out["loc"]["lane_num"]), int(out["loc"]["pos"]), f) == (2, 1, 0)
     assert out["loc"]["id"].tolist()[:2] == [22, 22]                   # the ids of both views are found all the same (x = 111 = point 22)
 
 
-def test_kat_scenes_without_a_route_take_the_plain_step(dm, cfg0):
+def _kat_scenes_without_a_route_take_the_plain_step(dm, cfg0, adv):
     # an unrouted scene, a path_num outside the route, a frozen scene: bytes of ego_model.advance (map mode) + resolve
     m = _tiny_map(dm)
     model = dm.default_ego_model()
@@ -191,9 +204,74 @@ def test_kat_scenes_without_a_route_take_the_plain_step(dm, cfg0):
                            (_ego(dm, m, ego_id=60, path_num=-1), _legs(dm), 0), (_ego(dm, m, ego_id=60), _legs(dm), em.OFF_GRID)):
         po = _path(dm, 133.0)
         want, wf, _ = em.advance(cfg0, model, si, po, st, np.array([flag], np.int32), m["points"], map_mode=True)
-        out, f = _adv(dm, cfg0, m, si, po, legs, flag=flag)
+        if flag == 0:
+            out, f = adv(cfg0, m, si, po, legs)
+        elif adv.name == "model":                                    # the model takes the flag word as it is given
+            o, fl, _ = rmod.advance(dm, cfg0, model, dm.default_route_model(), legs, np.array([0, len(legs)], np.int32), m, si, po, st,
+                                    np.array([flag], np.int32))
+            out, f = o[0], int(fl[0])
+        else:
+            continue                                                 # (the device reaches a flag by a step of its own: below)
         assert out.tobytes() == ms.resolve(dm, m, want)[0].tobytes() and f == int(wf[0])
         assert f == (flag if flag else em.LANE_END)                  # (§4c: the lane end freezes it)
+    # the frozen scene with its flag reached the honest way, on both backends: the grid stage on, a grid of 32 m at the origin
+    # (100, 100), far from the road at y = 0 - the routed ego goes from 120 to 121 = point 42 (99 - 42 <= 60: pos 1) and is off the
+    # grid; the next step finds OFF_GRID set and is the plain step of a frozen scene: the record as it stands, the flag kept
+    cfg = dm.default_config(128)
+    si = _ego(dm, m, ego_id=30)
+    si["grid_origin"]["x"], si["grid_origin"]["y"], si["goal"]["x"], si["goal"]["y"] = 100.0, 100.0, 116.0, 116.0
+    (mid, f0), (out, f) = adv.steps(cfg, m, si, [_path(dm, 120.0), _path(dm, 133.0)], _legs(dm))
+    assert (f0, int(mid["loc"]["pos"]), int(mid["loc"]["id"][1]), float(mid["loc"]["globalpoint"]["x"])) == (em.OFF_GRID, 1, 42, 121.0)
+    want, wf, _ = em.advance(cfg, model, mid.reshape(1), _path(dm, 133.0), st, np.array([f0], np.int32), m["points"], map_mode=True)
+    assert out.tobytes() == ms.resolve(dm, m, want)[0].tobytes() == mid.tobytes() and f == int(wf[0]) == em.OFF_GRID
+
+
+KATS = [_kat_pre_junction_starts_at_pre_points, _kat_junction_is_entered_on_the_last_lane_point, _kat_junction_is_left_at_the_end_of_the_polyline, _kat_lane_end_missed_exit_and_arrival, _kat_pre_junction_holds_the_lane_number, _kat_scenes_without_a_route_take_the_plain_step]
+
+
+def test_kat_pre_junction_starts_at_pre_points(dm, cfg0):
+    _kat_pre_junction_starts_at_pre_points(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_junction_is_entered_on_the_last_lane_point(dm, cfg0):
+    _kat_junction_is_entered_on_the_last_lane_point(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_junction_is_left_at_the_end_of_the_polyline(dm, cfg0):
+    _kat_junction_is_left_at_the_end_of_the_polyline(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_lane_end_missed_exit_and_arrival(dm, cfg0):
+    _kat_lane_end_missed_exit_and_arrival(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_pre_junction_holds_the_lane_number(dm, cfg0):
+    _kat_pre_junction_holds_the_lane_number(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+def test_kat_scenes_without_a_route_take_the_plain_step(dm, cfg0):
+    _kat_scenes_without_a_route_take_the_plain_step(dm, cfg0, _Adv(dm, _runner("model")))
+
+
+@gpu
+@pytest.mark.parametrize("kat", KATS, ids=lambda f: f.__name__[5:])
+def test_kat_on_the_device(dm, cfg0, kat):
+    """The known answers above on k_advance_route / k_advance_egos (injected PlanOut / SceneState), each also held against the model."""
+    kat(dm, cfg0, _Adv(dm, _runner("device")))
+
+
+@gpu
+def test_kat_batch_equals_each_case_alone(dm, cfg0):
+    """Every known answer above once more on the device, logged, then all of them as distinct scenes of one launch per group of
+    calls that can share a launch (advance_backends.batched): batch sizes that are no multiple of four, more than one block;
+    every scene gives the bytes it gave alone."""
+    log = []
+    a = _Adv(dm, _runner("device", log))
+    for kat in KATS:
+        kat(dm, cfg0, a)
+    sizes = ab.batched(ab.DeviceBackend(), log)
+    print(f"{len(log)} calls in batches of {sizes}; device against model: {ab.STATS}")
+    assert sum(sizes) >= len(log) and all(n % 4 != 0 and n > 4 for n in sizes)
 
 
 # ---- the ring ------------------------------------------------------------------------------------------------
