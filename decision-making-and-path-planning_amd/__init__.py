@@ -643,3 +643,22 @@ class Planner:
         rc = _hip.hipMemcpy(ptr, raw.ctypes.data, raw.size, 1)          # hipMemcpyHostToDevice
         if rc != 0:
             raise PlannerError(f"write_device: hipMemcpy failed with {rc}")
+
+    def read_device(self, which, dtype, count):
+        """The counterpart of write_device: host wait (pp_sync), then a blocking hipMemcpy of the first `count` records of the
+        handle's buffer `which` (pp_device_ptr) into a new array - pool entries no getter returns (a test reads the peer slots
+        beyond obs_n and the motion pool of the current input set)."""
+        global _hip
+        self.sync()
+        ptr, size = self.device_ptr(which)
+        out = np.zeros(int(count), dtype)
+        if not ptr or out.nbytes > size:
+            raise PlannerError(f"read_device: buffer {which} holds {size} B, {out.nbytes} B were asked for")
+        if _hip is None:
+            _hip = C.CDLL("libamdhip64.so")
+            _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        if out.nbytes:
+            rc = _hip.hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2)          # hipMemcpyDeviceToHost
+            if rc != 0:
+                raise PlannerError(f"read_device: hipMemcpy failed with {rc}")
+        return out

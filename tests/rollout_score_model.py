@@ -40,7 +40,8 @@ def clearance(x, y, ox, oy, radius, vehicle_width):
         return None, -1
     dx = np.asarray(ox, np.float64) - x
     dy = np.asarray(oy, np.float64) - y
-    d = np.sqrt(dx * dx + dy * dy) - np.asarray(radius, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):          # (inf - inf is a NaN d_j, not a warning)
+        d = np.sqrt(dx * dx + dy * dy) - np.asarray(radius, np.float32).astype(np.float64)
     ok = ~np.isnan(d)
     if not ok.any():
         return None, -1

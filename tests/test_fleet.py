@@ -10,6 +10,7 @@ import math
 import numpy as np
 import pytest
 
+import coupling_backends as cb
 import ego_model as em
 import fleet_model as fl
 import rollout_score_model as sm
@@ -31,20 +32,7 @@ def test_abi_mirror_and_default_model(dm):
     assert dm.OB_PEER == fl.OB_PEER == 0x40000000 and dm.FLEET_MAX_PEERS == 64
 
 
-FILL = 0x5A          # every byte of the pools before the step: an untouched slot still holds it
-
-
-def _egos(dm, xy, K, n_own=0, motion=False):
-    """SceneIn records at the positions xy, scene s owning the pool entries [s (n_own + K), ..) - n_own own entries, K peer slots;
-    the incoming obs_off / obs_n are rubbish (the step overwrites them with the pinned values)."""
-    n = len(xy)
-    si = np.zeros(n, dm.SceneIn)
-    si["loc"]["globalpoint"]["x"], si["loc"]["globalpoint"]["y"] = [p[0] for p in xy], [p[1] for p in xy]
-    si["obs_off"], si["obs_n"] = 12345, -7
-    stride = n_own + K
-    pool = np.frombuffer(bytes([FILL]) * (max(n * stride, 1) * dm.ObPoint.itemsize), dm.ObPoint).copy()
-    mot = np.frombuffer(bytes([FILL]) * (max(n * stride, 1) * dm.ObMotion.itemsize), dm.ObMotion).copy() if motion else None
-    return si, pool, mot, np.arange(n) * stride, np.full(n, n_own)
+FILL = cb.FILL          # every byte of the pools before the step: an untouched slot still holds it
 
 
 def _fm(dm, rng=60.0, K=8, radius=0.9):
@@ -53,21 +41,27 @@ def _fm(dm, rng=60.0, K=8, radius=0.9):
     return fm
 
 
-def _peers(out, pool, s, off, own):
-    """(obs_n - n_own, [peer scene of every filled slot]) of scene s."""
-    c = int(out["obs_n"][s]) - int(own[s])
-    sl = pool[int(off[s]) + int(own[s]):int(off[s]) + int(own[s]) + c]
-    assert ((sl["type"] & fl.OB_PEER) != 0).all()
-    return c, [int(t) & ~fl.OB_PEER for t in sl["type"]]
+def _runner(name, log=None):
+    return cb.FleetRunner(cb.FleetModelBackend() if name == "model" else cb.FleetDeviceBackend(), log)
 
 
-def test_kat_three_on_a_line(dm):
+@pytest.fixture()
+def cfg0(dm):
+    return cb.config()
+
+
+# The known answers are written once against a runner of tests/coupling_backends.py: run(cfg, fm, world_first, positions, n_own,
+# motion) puts scene s on pool entries [s (n_own + K), ..) - n_own own entries, K peer slots - and returns SceneIn, the pinned slices
+# and the whole pools after the step, from the numpy model (CPU; the incoming obs_off / obs_n are rubbish, the step overwrites
+# them with the pinned values) and from pp_set_fleet on a resident set (test_kat_on_the_device), where SceneIn, every slice and
+# every pool byte are also held against the model.
+def _kat_three_on_a_line(dm, cfg0, run):
     # egos at x = 0, 3, 4 on y = 0, one world, K = 2, range 60.
     # scene 0: d2 to 1 = 3*3 = 9, to 2 = 4*4 = 16 -> slots (1, 2);  scene 1: d2 to 0 = 9, to 2 = 1 -> slots (2, 0);
     # scene 2: d2 to 0 = 16, to 1 = 1 -> slots (1, 0)
-    si, pool, mot, off, own = _egos(dm, [(0.0, 0.0), (3.0, 0.0), (4.0, 0.0)], K=2, n_own=1, motion=True)
-    out, p2, m2 = fl.couple(_fm(dm, K=2), [0, 3], off, own, si, pool, mot)
-    assert [_peers(out, p2, s, off, own) for s in range(3)] == [(2, [1, 2]), (2, [2, 0]), (2, [1, 0])]
+    r = run(cfg0, _fm(dm, K=2), [0, 3], [(0.0, 0.0), (3.0, 0.0), (4.0, 0.0)], n_own=1, motion=True)
+    out, p2, m2, off = r.out, r.pool, r.mot, r.off
+    assert [r.peers(s) for s in range(3)] == [(2, [1, 2]), (2, [2, 0]), (2, [1, 0])]
     assert out["obs_off"].tolist() == [0, 3, 6] and out["obs_n"].tolist() == [3, 3, 3]
     # a slot is the peer's position, OB_PEER | its scene and the model's radius (0.9 rounded to float); its motion is zero;
     # the scene's own entry (index 0 of its slice) and its motion keep their bytes
@@ -77,71 +71,111 @@ def test_kat_three_on_a_line(dm):
     for s in range(3):
         assert p2[off[s]].tobytes() == bytes([FILL]) * 24 and m2[off[s]].tobytes() == bytes([FILL]) * 16
     # nothing else of SceneIn changes
-    a, b = out.copy(), si.copy()
+    a, b = out.copy(), r.si.copy()
     a["obs_off"], a["obs_n"], b["obs_off"], b["obs_n"] = 0, 0, 0, 0
     assert a.tobytes() == b.tobytes()
-    # the inputs are not written
-    assert pool.tobytes() == bytes([FILL]) * pool.nbytes and int(si["obs_n"][0]) == -7
+    # the inputs are not written (model: the rubbish the records came with; device: the slices that were pinned)
+    assert r.pool_in.tobytes() == bytes([FILL]) * r.pool_in.nbytes and int(r.si["obs_n"][0]) == (-7 if run.name == "model" else 1)
 
 
-def test_kat_tie_goes_to_the_lower_scene(dm):
+def _kat_tie_goes_to_the_lower_scene(dm, cfg0, run):
     # 3-4-5 triangles: scene 1 at the origin, scene 0 at (3, 4), scene 2 at (4, 3), scene 3 at (-5, 0): d2 = 9 + 16 = 16 + 9 =
     # 25 + 0 = 25 for all three, exactly -> order 0, 2, 3 by scene index; with K = 2 scene 3 is left out
-    si, pool, _, off, own = _egos(dm, [(3.0, 4.0), (0.0, 0.0), (4.0, 3.0), (-5.0, 0.0)], K=3)
-    out, p2, _ = fl.couple(_fm(dm, K=3), [0, 4], off, own, si, pool)
-    assert _peers(out, p2, 1, off, own) == (3, [0, 2, 3])
-    si, pool, _, off, own = _egos(dm, [(3.0, 4.0), (0.0, 0.0), (4.0, 3.0), (-5.0, 0.0)], K=2)
-    out, p2, _ = fl.couple(_fm(dm, K=2), [0, 4], off, own, si, pool)
-    assert _peers(out, p2, 1, off, own) == (2, [0, 2])
+    xy = [(3.0, 4.0), (0.0, 0.0), (4.0, 3.0), (-5.0, 0.0)]
+    assert run(cfg0, _fm(dm, K=3), [0, 4], xy).peers(1) == (3, [0, 2, 3])
+    assert run(cfg0, _fm(dm, K=2), [0, 4], xy).peers(1) == (2, [0, 2])
 
 
-def test_kat_range_edge(dm):
+def _kat_range_edge(dm, cfg0, run):
     # range 5: a peer at (3, 4) has d2 = 25 = 5*5 exactly: in (<=); one at (0, nextafter(5)) has d2 = y*y > 25: out
     y = math.nextafter(5.0, 6.0)
     assert y * y > 25.0
-    si, pool, _, off, own = _egos(dm, [(0.0, 0.0), (3.0, 4.0), (0.0, y)], K=4)
-    out, p2, _ = fl.couple(_fm(dm, rng=5.0, K=4), [0, 3], off, own, si, pool)
-    assert _peers(out, p2, 0, off, own) == (1, [1])
+    r = run(cfg0, _fm(dm, rng=5.0, K=4), [0, 3], [(0.0, 0.0), (3.0, 4.0), (0.0, y)])
+    assert r.peers(0) == (1, [1])
     # untouched slots c .. K - 1 keep their bytes
-    assert p2[off[0] + 1:off[0] + 4].tobytes() == bytes([FILL]) * (3 * 24)
+    assert r.pool[r.off[0] + 1:r.off[0] + 4].tobytes() == bytes([FILL]) * (3 * 24)
     # from scene 2 the others are sqrt(0 + y*y) = y > 5 and sqrt(9 + (y - 4)^2) ~ 3.16 away: only scene 1
-    assert _peers(out, p2, 2, off, own) == (1, [1])
+    assert r.peers(2) == (1, [1])
 
 
-def test_kat_fewer_slots_than_candidates_and_none(dm):
+def _kat_fewer_slots_than_candidates_and_none(dm, cfg0, run):
     # five egos 1 m apart on a line, K = 2: scene 2 (the middle) takes 1 and 3 (d2 = 1 both, lower index first), not 0 and 4 (d2 = 4)
     xy = [(float(k), 0.0) for k in range(5)]
-    si, pool, _, off, own = _egos(dm, xy, K=2)
-    out, p2, _ = fl.couple(_fm(dm, K=2), [0, 5], off, own, si, pool)
-    assert _peers(out, p2, 2, off, own) == (2, [1, 3])
-    assert _peers(out, p2, 0, off, own) == (2, [1, 2]) and _peers(out, p2, 4, off, own) == (2, [3, 2])
+    r = run(cfg0, _fm(dm, K=2), [0, 5], xy)
+    assert r.peers(2) == (2, [1, 3])
+    assert r.peers(0) == (2, [1, 2]) and r.peers(4) == (2, [3, 2])
     # K = 0: no slot, obs_off / obs_n are still the pinned values
-    si, pool, _, off, own = _egos(dm, xy, K=0, n_own=2)
-    out, p2, _ = fl.couple(_fm(dm, K=0), [0, 5], off, own, si, pool)
-    assert out["obs_n"].tolist() == [2] * 5 and out["obs_off"].tolist() == [0, 2, 4, 6, 8] and p2.tobytes() == pool.tobytes()
+    r = run(cfg0, _fm(dm, K=0), [0, 5], xy, n_own=2)
+    assert r.out["obs_n"].tolist() == [2] * 5 and r.out["obs_off"].tolist() == [0, 2, 4, 6, 8] and r.pool.tobytes() == r.pool_in.tobytes()
 
 
-def test_kat_nan_peer_and_nan_self(dm):
+def _kat_nan_peer_and_nan_self(dm, cfg0, run):
     # scene 1 has a NaN x: its d2 is NaN for everyone - no candidate - and it sees nobody itself; the others see each other
-    si, pool, _, off, own = _egos(dm, [(0.0, 0.0), (math.nan, 0.0), (2.0, 0.0), (0.0, math.inf)], K=3)
-    out, p2, _ = fl.couple(_fm(dm, K=3), [0, 4], off, own, si, pool)
-    assert _peers(out, p2, 0, off, own) == (1, [2]) and _peers(out, p2, 2, off, own) == (1, [0])
-    assert _peers(out, p2, 1, off, own) == (0, []) and _peers(out, p2, 3, off, own) == (0, [])      # (inf: not finite either)
-    assert int(out["obs_off"][1]) == int(off[1]) and int(out["obs_n"][1]) == 0
-    assert p2[off[1]:off[1] + 3].tobytes() == bytes([FILL]) * (3 * 24)
+    r = run(cfg0, _fm(dm, K=3), [0, 4], [(0.0, 0.0), (math.nan, 0.0), (2.0, 0.0), (0.0, math.inf)])
+    assert r.peers(0) == (1, [2]) and r.peers(2) == (1, [0])
+    assert r.peers(1) == (0, []) and r.peers(3) == (0, [])      # (inf: not finite either)
+    assert int(r.out["obs_off"][1]) == int(r.off[1]) and int(r.out["obs_n"][1]) == 0
+    assert r.pool[r.off[1]:r.off[1] + 3].tobytes() == bytes([FILL]) * (3 * 24)
 
 
-def test_kat_worlds_do_not_see_each_other(dm):
+def _kat_worlds_do_not_see_each_other(dm, cfg0, run):
     # scenes 0, 1 | 2, 3: scenes 1 and 2 share a position, scenes 0 and 3 are 1 m from it - each sees only its own world's member
-    si, pool, _, off, own = _egos(dm, [(1.0, 0.0), (0.0, 0.0), (0.0, 0.0), (0.0, 1.0)], K=3)
-    out, p2, _ = fl.couple(_fm(dm, K=3), [0, 2, 4], off, own, si, pool)
-    assert [_peers(out, p2, s, off, own) for s in range(4)] == [(1, [1]), (1, [0]), (1, [3]), (1, [2])]
+    xy = [(1.0, 0.0), (0.0, 0.0), (0.0, 0.0), (0.0, 1.0)]
+    r = run(cfg0, _fm(dm, K=3), [0, 2, 4], xy)
+    assert [r.peers(s) for s in range(4)] == [(1, [1]), (1, [0]), (1, [3]), (1, [2])]
     # one world of all four: scene 1 sees 2 (d2 = 0), then 0 and 3 (d2 = 1, lower index first)
-    out, p2, _ = fl.couple(_fm(dm, K=3), [0, 4], off, own, si, pool)
-    assert _peers(out, p2, 1, off, own) == (3, [2, 0, 3])
+    assert run(cfg0, _fm(dm, K=3), [0, 4], xy).peers(1) == (3, [2, 0, 3])
     # a world of one sees nobody
-    out, p2, _ = fl.couple(_fm(dm, K=3), [0, 1, 4], off, own, si, pool)
-    assert _peers(out, p2, 0, off, own) == (0, []) and _peers(out, p2, 1, off, own) == (2, [2, 3])
+    r = run(cfg0, _fm(dm, K=3), [0, 1, 4], xy)
+    assert r.peers(0) == (0, []) and r.peers(1) == (2, [2, 3])
+
+
+KATS = [_kat_three_on_a_line, _kat_tie_goes_to_the_lower_scene, _kat_range_edge, _kat_fewer_slots_than_candidates_and_none, _kat_nan_peer_and_nan_self,
+        _kat_worlds_do_not_see_each_other]
+
+
+def test_kat_three_on_a_line(dm, cfg0):
+    _kat_three_on_a_line(dm, cfg0, _runner("model"))
+
+
+def test_kat_tie_goes_to_the_lower_scene(dm, cfg0):
+    _kat_tie_goes_to_the_lower_scene(dm, cfg0, _runner("model"))
+
+
+def test_kat_range_edge(dm, cfg0):
+    _kat_range_edge(dm, cfg0, _runner("model"))
+
+
+def test_kat_fewer_slots_than_candidates_and_none(dm, cfg0):
+    _kat_fewer_slots_than_candidates_and_none(dm, cfg0, _runner("model"))
+
+
+def test_kat_nan_peer_and_nan_self(dm, cfg0):
+    _kat_nan_peer_and_nan_self(dm, cfg0, _runner("model"))
+
+
+def test_kat_worlds_do_not_see_each_other(dm, cfg0):
+    _kat_worlds_do_not_see_each_other(dm, cfg0, _runner("model"))
+
+
+@gpu
+@pytest.mark.parametrize("kat", KATS, ids=lambda f: f.__name__[5:])
+def test_kat_on_the_device(dm, cfg0, kat):
+    """The known answers above on k_couple_fleet (pp_set_fleet on a resident set), each also held byte for byte against the model."""
+    kat(dm, cfg0, _runner("device"))
+
+
+@gpu
+def test_kat_batch_equals_each_case_alone(dm, cfg0):
+    """Every known answer once more on the device, logged, then the calls that share a FleetModel as worlds of one launch
+    (coupling_backends.fleet_batched): every scene gives the bytes it gave alone, scene indices and pool offsets moved."""
+    log = []
+    run = _runner("device", log)
+    for kat in KATS:
+        kat(dm, cfg0, run)
+    sizes = cb.fleet_batched(cb.FleetDeviceBackend(), log)
+    print(f"{len(log)} calls in batches of {sizes} scenes")
+    assert sum(sizes) >= sum(len(c["xy"]) for c in log) and all(n % 4 != 0 and n > 4 for n in sizes)
 
 
 # ---- the platoon: a standing leader and a follower approaching it in the same lane -------------------------------

@@ -10,6 +10,7 @@ import math
 import numpy as np
 import pytest
 
+import coupling_backends as cb
 import ego_model as em
 import rollout_score_model as sm
 
@@ -26,109 +27,108 @@ def test_abi_mirror(dm):
     assert (sm.G_STATUS_COUNT, sm.G_INTERNAL, sm.MAX_LATTICE) == (dm.G_STATUS_COUNT, dm.G_INTERNAL, dm.MAX_LATTICE)
 
 
-def _one(dm, x, y, v, obs=(), behavior=1, afresh=0, ob_flag=0, desaccVd=0):
-    """Inputs of one scored tick of one scene: ego at (x, y) with speed v, obstacles (x, y, radius)."""
-    si, po, st = np.zeros(1, dm.SceneIn), np.zeros(1, dm.PlanOut), np.zeros(1, dm.SceneState)
-    si["loc"]["globalpoint"]["x"], si["loc"]["globalpoint"]["y"], si["loc"]["velocity"] = x, y, v
-    si["obs_off"], si["obs_n"] = 0, len(obs)
-    pool = np.zeros(max(len(obs), 1), dm.ObPoint)
-    for j, (ox, oy, r) in enumerate(obs):
-        pool[j]["x"], pool[j]["y"], pool[j]["radius"] = ox, oy, r
-    po["dec"]["behavior"], po["ob_flag"], po["result"]["desaccVd"], st["afresh_planning"] = behavior, ob_flag, desaccVd, afresh
-    return si, po, st, pool
+def _one(cfg, x, y, v, obs=(), behavior=1, afresh=0, ob_flag=0, desaccVd=0, flags=0, grid=None):
+    """One scored tick of one scene (coupling_backends.Tick): ego at (x, y) with speed v, obstacles (x, y, radius)."""
+    return cb.tick(cfg, [(x, y, v, list(obs))], behavior=behavior, afresh=afresh, ob_flag=ob_flag, desaccVd=desaccVd, flags=flags, grid=grid)
 
 
-def _fold(dm, cfg, r, tick, dt=0.1, flags=0, grid=None):
-    si, po, st, pool = tick
-    return sm.fold(r, cfg, dt, si, po, st, pool, np.array([flags], np.int32), grid)
+def _runner(name, log=None):
+    return cb.ScoreRunner(cb.ScoreModelBackend() if name == "model" else cb.ScoreDeviceBackend(), log)
 
 
 @pytest.fixture()
 def cfg(dm):
-    c = dm.default_config(128)
+    c = cb.config()                                                          # (grid stage, decision stage, moving obstacles off: the device leg)
     assert float(c["Vehicle_Width"][0]) == 1.8 and 0.5 * 1.8 == 0.9          # the ego disc: radius 0.9 m
     return c
 
 
-def test_kat_start_values_and_empty_slice(dm, cfg):
-    r = sm.new_scores(dm.RolloutScore, 1)
+# The known answers are written once against a runner of tests/coupling_backends.py: the numpy model (CPU) and k_score_ego inside a
+# tick of crafted records (test_kat_on_the_device), where every record is also held byte for byte against the model folded over
+# the device's own PlanOut and SceneState.  run(cfg, dt, ticks) -> .start, .after[k]: the records before the first / after tick k.
+def _kat_start_values_and_empty_slice(dm, cfg, run):
+    # a tick without obstacles, then one whose only distance is a NaN
+    res = run(cfg, 0.1, [_one(cfg, 10.0, 0.0, 36.0), _one(cfg, 10.0, 0.0, 36.0, obs=[(math.nan, 0.0, 0.5)])])
+    r = res.start
     assert (float(r["min_clearance"][0]), int(r["min_clearance_tick"][0]), int(r["min_clearance_obs"][0])) == (math.inf, -1, -1)
     assert int(r["first_collision_tick"][0]) == -1 and int(r["n_ticks"][0]) == 0
     # a tick without obstacles has no clearance: the three fields and the collision fields stay, the tick is counted
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0))
+    r = res.after[0]
     assert (float(r["min_clearance"][0]), int(r["min_clearance_tick"][0]), int(r["min_clearance_obs"][0])) == (math.inf, -1, -1)
     assert (int(r["first_collision_tick"][0]), int(r["n_collision_ticks"][0]), int(r["n_ticks"][0])) == (-1, 0, 1)
     # ... and so has one whose only distance is a NaN
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=[(math.nan, 0.0, 0.5)]))
+    r = res.after[1]
     assert (float(r["min_clearance"][0]), int(r["min_clearance_tick"][0]), int(r["min_clearance_obs"][0])) == (math.inf, -1, -1)
     assert int(r["n_ticks"][0]) == 2
 
 
-def test_kat_obstacle_abeam_tie_and_nan(dm, cfg):
+def _kat_obstacle_abeam_tie_and_nan(dm, cfg, run):
     # straight drive along +x at y = 0, one obstacle of radius 0.5 three metres to the left of x = 10: abeam the centre
     # distance is the offset, d = 3 - 0.5, clearance = offset - radius - 0.9 = 1.6; one metre before it sqrt(1 + 9) - 0.5 - 0.9
-    r = sm.new_scores(dm.RolloutScore, 1)
     ob = [(10.0, 3.0, 0.5)]
-    _fold(dm, cfg, r, _one(dm, 9.0, 0.0, 36.0, obs=ob))
+    res = run(cfg, 0.1, [_one(cfg, x, 0.0, 36.0, obs=ob) for x in (9.0, 10.0, 11.0, 10.0)])
+    r = res.after[0]
     assert float(r["min_clearance"][0]) == math.sqrt(1.0 * 1.0 + 3.0 * 3.0) - 0.5 - 0.9
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=ob))
+    r = res.after[1]
     assert float(r["min_clearance"][0]) == 3.0 - 0.5 - 0.9 and abs(float(r["min_clearance"][0]) - 1.6) < 1e-15
     assert (int(r["min_clearance_tick"][0]), int(r["min_clearance_obs"][0])) == (1, 0)
-    _fold(dm, cfg, r, _one(dm, 11.0, 0.0, 36.0, obs=ob))          # past it: the minimum and its tick stay
+    r = res.after[2]                                              # past it: the minimum and its tick stay
     assert float(r["min_clearance"][0]) == 3.0 - 0.5 - 0.9 and int(r["min_clearance_tick"][0]) == 1
     assert int(r["n_collision_ticks"][0]) == 0 and int(r["first_collision_tick"][0]) == -1
     # the same clearance again later does not move the tick (strict <)
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=ob))
+    r = res.after[3]
     assert int(r["min_clearance_tick"][0]) == 1
     # two obstacles at the same distance (left and right of the ego): the first index; a NaN in front of them is ignored
-    r = sm.new_scores(dm.RolloutScore, 1)
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=[(10.0, 5.0, 0.5), (10.0, 3.0, 0.5), (10.0, -3.0, 0.5)]))
+    r = run(cfg, 0.1, [_one(cfg, 10.0, 0.0, 36.0, obs=[(10.0, 5.0, 0.5), (10.0, 3.0, 0.5), (10.0, -3.0, 0.5)])]).after[0]
     assert (float(r["min_clearance"][0]), int(r["min_clearance_obs"][0])) == (3.0 - 0.5 - 0.9, 1)
-    r = sm.new_scores(dm.RolloutScore, 1)
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=[(math.nan, 0.0, 0.5), (10.0, -3.0, 0.5), (10.0, 3.0, 0.5)]))
+    r = run(cfg, 0.1, [_one(cfg, 10.0, 0.0, 36.0, obs=[(math.nan, 0.0, 0.5), (10.0, -3.0, 0.5), (10.0, 3.0, 0.5)])]).after[0]
     assert (float(r["min_clearance"][0]), int(r["min_clearance_obs"][0])) == (3.0 - 0.5 - 0.9, 1)
     # the radius is an f32 widened to double: 1.7f = 1.7000000476837158
-    r = sm.new_scores(dm.RolloutScore, 1)
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=[(10.0, 2.5, 1.7)]))
+    r = run(cfg, 0.1, [_one(cfg, 10.0, 0.0, 36.0, obs=[(10.0, 2.5, 1.7)])]).after[0]
     assert float(r["min_clearance"][0]) == 2.5 - float(np.float32(1.7)) - 0.9 and float(r["min_clearance"][0]) < -0.1
 
 
-def test_kat_collision_exactly_at_zero(dm, cfg):
+def _kat_collision_exactly_at_zero(dm, cfg, run):
     # a point obstacle (radius 0) exactly 0.9 m beside the ego: sqrt(0*0 + 0.9*0.9) = 0.9 (sqrt(x*x) = |x| in IEEE arithmetic),
     # clearance = 0.9 - 0 - 0.9 = 0: touching counts as a collision (<=); one ulp further away it does not
-    r = sm.new_scores(dm.RolloutScore, 1)
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=[(10.0, math.nextafter(0.9, 1.0), 0.0)]))
+    res = run(cfg, 0.1, [_one(cfg, 10.0, 0.0, 36.0, obs=[(10.0, y, 0.0)]) for y in (math.nextafter(0.9, 1.0), 0.9, 0.5)])
+    r = res.after[0]
     assert float(r["min_clearance"][0]) > 0 and int(r["n_collision_ticks"][0]) == 0 and int(r["first_collision_tick"][0]) == -1
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=[(10.0, 0.9, 0.0)]))
+    r = res.after[1]
     assert float(r["min_clearance"][0]) == 0.0
     assert (int(r["first_collision_tick"][0]), int(r["n_collision_ticks"][0]), int(r["min_clearance_tick"][0])) == (1, 1, 1)
-    _fold(dm, cfg, r, _one(dm, 10.0, 0.0, 36.0, obs=[(10.0, 0.5, 0.0)]))          # deeper: counted, the first tick stays
+    r = res.after[2]                                                              # deeper: counted, the first tick stays
     assert (int(r["first_collision_tick"][0]), int(r["n_collision_ticks"][0]), int(r["min_clearance_tick"][0])) == (1, 2, 2)
     assert float(r["min_clearance"][0]) == 0.5 - 0.0 - 0.9
 
 
-def test_kat_distance_and_speed_ramp(dm, cfg):
+def _kat_distance_and_speed_ramp(dm, cfg, run):
     # three ticks: (0, 0) at 10 km/h, (3, 4) at 13.6 km/h, (9, 12) at 10 km/h, dt 0.1 s.
     # dist = sqrt(9 + 16) + sqrt(36 + 64) = 5 + 10 = 15 m; rise (13.6 - 10)/3.6/0.1 = 10 m/s^2, fall the same; max speed 13.6
-    r = sm.new_scores(dm.RolloutScore, 1)
-    _fold(dm, cfg, r, _one(dm, 0.0, 0.0, 10.0))
+    # ... then a NaN speed (the Planning kernel only scales its aim distance by it: every loop over it is bounded by a count, and
+    # the CPU oracle returns for the record: test_crafted_records_pass_the_cpu_oracle) and 5 km/h standing still
+    res = run(cfg, 0.1, [_one(cfg, 0.0, 0.0, 10.0), _one(cfg, 3.0, 4.0, 13.6), _one(cfg, 9.0, 12.0, 10.0), _one(cfg, 9.0, 12.0, math.nan),
+                         _one(cfg, 9.0, 12.0, 5.0)])
+    r = res.after[0]
     assert (float(r["dist"][0]), float(r["max_acc"][0]), float(r["max_dec"][0]), float(r["max_speed"][0])) == (0.0, 0.0, 0.0, 10.0)
-    _fold(dm, cfg, r, _one(dm, 3.0, 4.0, 13.6))
+    r = res.after[1]
     assert float(r["dist"][0]) == 5.0 and float(r["max_acc"][0]) == (13.6 - 10.0) / 3.6 / 0.1 and float(r["max_dec"][0]) == 0.0
-    _fold(dm, cfg, r, _one(dm, 9.0, 12.0, 10.0))
+    r = res.after[2]
     assert float(r["dist"][0]) == 15.0 and float(r["max_speed"][0]) == 13.6
     assert float(r["max_acc"][0]) == (13.6 - 10.0) / 3.6 / 0.1 and abs(float(r["max_acc"][0]) - 10.0) < 1e-12
     assert float(r["max_dec"][0]) == -((10.0 - 13.6) / 3.6 / 0.1) and abs(float(r["max_dec"][0]) - 10.0) < 1e-12
     assert (float(r["last_pos"]["x"][0]), float(r["last_pos"]["y"][0]), float(r["last_speed"][0]), int(r["n_ticks"][0])) == (9.0, 12.0, 10.0, 3)
     # a NaN speed never replaces a maximum
-    _fold(dm, cfg, r, _one(dm, 9.0, 12.0, math.nan))
-    _fold(dm, cfg, r, _one(dm, 9.0, 12.0, 5.0))
+    r = res.after[4]
     assert float(r["max_speed"][0]) == 13.6 and abs(float(r["max_acc"][0]) - 10.0) < 1e-12 and abs(float(r["max_dec"][0]) - 10.0) < 1e-12
     assert float(r["dist"][0]) == 15.0                                    # standing still adds 0
 
 
-def test_kat_counters_and_histograms(dm, cfg):
-    r = sm.new_scores(dm.RolloutScore, 1)
+def _kat_counters_and_histograms(dm, cfg, run):
+    """behavior_ticks holds on both backends: with the decision stage off PlanOut.dec is the caller's record, out-of-range values
+    included (kernels_r.hpp, `po.dec = dec`; on the oracle: test_crafted_records_pass_the_cpu_oracle).  Model leg only: the counters
+    of a crafted PlanOut / SceneState (n_replans, n_ob_flag, n_desacc, ego_flags) and the grid half with its status clamp - no API
+    hands the device such records, and k_score_grid has no wave structure."""
     go = np.zeros(1, dm.GridOut)
     nl = int(cfg["n_lattice"][0])
     assert nl == 16
@@ -136,18 +136,81 @@ def test_kat_counters_and_histograms(dm, cfg):
     # The grid path is candidate 16 of 17: it won only on the tick with n_candidates = 17 and best = 16 - with 16 candidates
     # (no path found) the last Bezier candidate, index 15 = n_candidates - 1, is not the grid path.
     ticks = [(1, 0, 17, 16, 1, 0, 0), (6, 5, 17, 3, 0, 1, 1), (-3, 99, 16, 15, 1, 1, 0), (11, -1, 17, 16, 0, 0, 1)]
+    crafted = []
     for k, (beh, status, nc, best, afresh, ob_flag, dv) in enumerate(ticks):
         go["status"], go["n_candidates"], go["best_candidate"] = status, nc, best
-        _fold(dm, cfg, r, _one(dm, 0.0, 0.0, 0.0, behavior=beh, afresh=afresh, ob_flag=ob_flag, desaccVd=dv), flags=k, grid=go)
+        crafted.append(_one(cfg, 0.0, 0.0, 0.0, behavior=beh, afresh=afresh, ob_flag=ob_flag, desaccVd=dv, flags=k, grid=go.copy()))
+    crafted.append(_one(cfg, 0.0, 0.0, 0.0))
+    res = run(cfg, 0.1, crafted)
+    r = res.after[3]
     assert r["behavior_ticks"][0].tolist() == [1, 1, 0, 0, 0, 0, 1, 1]
-    want = [0] * dm.G_STATUS_COUNT
-    want[dm.G_FOUND], want[dm.G_PATH_TRUNC], want[dm.G_INTERNAL] = 1, 1, 2
-    assert r["grid_status_ticks"][0].tolist() == want
-    assert (int(r["n_grid_ticks"][0]), int(r["n_grid_path_candidate"][0]), int(r["n_ticks"][0])) == (4, 2, 4)
-    assert (int(r["n_replans"][0]), int(r["n_ob_flag"][0]), int(r["n_desacc"][0]), int(r["ego_flags"][0])) == (2, 2, 2, 3)
+    assert int(r["n_ticks"][0]) == 4
+    if run.name == "model":
+        want = [0] * dm.G_STATUS_COUNT
+        want[dm.G_FOUND], want[dm.G_PATH_TRUNC], want[dm.G_INTERNAL] = 1, 1, 2
+        assert r["grid_status_ticks"][0].tolist() == want
+        assert (int(r["n_grid_ticks"][0]), int(r["n_grid_path_candidate"][0]), int(r["n_ticks"][0])) == (4, 2, 4)
+        assert (int(r["n_replans"][0]), int(r["n_ob_flag"][0]), int(r["n_desacc"][0]), int(r["ego_flags"][0])) == (2, 2, 2, 3)
     # a tick without the grid stage leaves the grid half alone
-    _fold(dm, cfg, r, _one(dm, 0.0, 0.0, 0.0))
-    assert (int(r["n_grid_ticks"][0]), int(r["n_ticks"][0])) == (4, 5)
+    r = res.after[4]
+    assert int(r["n_ticks"][0]) == 5 and r["behavior_ticks"][0].tolist() == [1, 2, 0, 0, 0, 0, 1, 1]
+    if run.name == "model":
+        assert (int(r["n_grid_ticks"][0]), int(r["n_ticks"][0])) == (4, 5)
+
+
+KATS = [_kat_start_values_and_empty_slice, _kat_obstacle_abeam_tie_and_nan, _kat_collision_exactly_at_zero, _kat_distance_and_speed_ramp,
+        _kat_counters_and_histograms]
+
+
+def test_kat_start_values_and_empty_slice(dm, cfg):
+    _kat_start_values_and_empty_slice(dm, cfg, _runner("model"))
+
+
+def test_kat_obstacle_abeam_tie_and_nan(dm, cfg):
+    _kat_obstacle_abeam_tie_and_nan(dm, cfg, _runner("model"))
+
+
+def test_kat_collision_exactly_at_zero(dm, cfg):
+    _kat_collision_exactly_at_zero(dm, cfg, _runner("model"))
+
+
+def test_kat_distance_and_speed_ramp(dm, cfg):
+    _kat_distance_and_speed_ramp(dm, cfg, _runner("model"))
+
+
+def test_kat_counters_and_histograms(dm, cfg):
+    _kat_counters_and_histograms(dm, cfg, _runner("model"))
+
+
+def test_crafted_records_pass_the_cpu_oracle(dm, oracle, cfg):
+    """What the device leg sends through a real tick, on the CPU oracle first: a NaN ego speed, behaviours outside 0 .. 7, and
+    obstacles that are NaN, infinite or 200 to a scene.  The tick returns, and PlanOut.dec.behavior is the caller's value."""
+    inf = math.inf
+    odd = [(math.nan, 0.0, 0.5), (inf, 0.0, 0.5), (inf, 0.0, inf), (10.0, 3.0, math.nan), (-inf, inf, 0.0)] + [(10.0 + 0.25 * j, 3.0, 0.5) for j in range(195)]
+    sc = cb.road(cfg)
+    for t in (_one(cfg, 9.0, 12.0, math.nan), _one(cfg, 0.0, 0.0, 0.0, behavior=-3), _one(cfg, 0.0, 0.0, 0.0, behavior=11), _one(cfg, 10.0, 0.0, 36.0, obs=odd)):
+        plan, _, _ = oracle.plan_tick_batch(cfg, dict(sc, scene_in=t.si, obs_pool=t.pool, mot_pool=None, n_obs=len(t.pool)), sc["state"].copy(), want_grid=False)
+        assert int(plan["dec"]["behavior"][0]) == int(t.si["dec"]["behavior"][0])
+
+
+@gpu
+@pytest.mark.parametrize("kat", KATS, ids=lambda f: f.__name__[5:])
+def test_kat_on_the_device(dm, cfg, kat):
+    """The known answers above on k_score_ego, each record also held byte for byte against the model (coupling_backends)."""
+    kat(dm, cfg, _runner("device"))
+
+
+@gpu
+def test_kat_batch_equals_each_case_alone(dm, cfg):
+    """Every known answer once more on the device, logged, then as distinct scenes of one launch per group of calls that can share
+    one (coupling_backends.score_batched): more than one block, no multiple of four; every scene gives the bytes it gave alone."""
+    log = []
+    run = _runner("device", log)
+    for kat in KATS:
+        kat(dm, cfg, run)
+    sizes = cb.score_batched(cb.ScoreDeviceBackend(), log)
+    print(f"{len(log)} calls in batches of {sizes}")
+    assert sum(sizes) >= len(log) and all(n % 4 != 0 and n > 4 for n in sizes)
 
 
 # ---- the collision scene: the speed-ramp road with one obstacle beside the lane ----------------------------------
