@@ -99,6 +99,8 @@ FLEET_MAX_PEERS = 64
 RouteLeg = _dt([("road_num", i4), ("stub_attribute", i4), ("out_lane_no", u2, (LANESUM,))])
 RouteModel = _dt([("pre_points", i4), ("_pad", i4)])
 EGO_ROUTE_END = 16            # the ego came to the end of the last leg of its route (DMPP_EGO_ROUTE_END)
+# a grid that follows the ego: the advance step re-centres grid_origin and goal
+GridFollow = _dt([("goal_point", i4), ("margin_cells", i4)])
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -210,6 +212,11 @@ def load_library(path=None):
     if route:
         lib.pp_default_route_model.argtypes = [vp]
         lib.pp_set_route.argtypes = [vp, ci, vp, vp, vp]
+    follow = hasattr(lib, "pp_set_grid_follow") or path == LIB_PATH          # (as above: an older build may lack it)
+    if follow:
+        lib.pp_default_grid_follow.argtypes = [vp]
+        lib.pp_default_grid_follow.restype = None
+        lib.pp_set_grid_follow.argtypes = [vp, vp]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -222,7 +229,8 @@ def load_library(path=None):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
-            (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()):
+            (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
+            (((25, GridFollow),) if follow else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -269,6 +277,13 @@ def default_route_model():
     rm = np.zeros(1, RouteModel)
     _check(load_library().pp_default_route_model(_ptr(rm)))
     return rm
+
+
+def default_grid_follow():
+    """GridFollow record of the grid that follows the ego (pp_default_grid_follow): the path point the goal is taken from, the margin in cells."""
+    gf = np.zeros(1, GridFollow)
+    load_library().pp_default_grid_follow(_ptr(gf))
+    return gf
 
 
 def gen_scenes(cfg, first_scene, n_scenes, n_obs, junction_every=8):
@@ -476,6 +491,17 @@ class Planner:
             raise PlannerError(f"set_route: route_first needs {self.n + 1} entries (one per resident scene and the end), got {len(rf)}")
         m = default_route_model() if model is None else np.array(model, RouteModel).reshape(1).copy()
         _check(self.lib.pp_set_route(self.h, len(lg), _ptr(lg), _ptr(rf), _ptr(m)))
+
+    # ---- a grid that follows the ego: the advance step re-centres grid_origin and goal ------
+    def set_grid_follow(self, gf=None):
+        """pp_set_grid_follow: from the next advance on the goal is point gf.goal_point of the followed path and the grid frame is
+        held or re-centred on whole cells about ego and goal.  The model belongs to the handle: it survives
+        set_scenes / set_egos / set_map.  gf None: following off."""
+        if gf is None:
+            _check(self.lib.pp_set_grid_follow(self.h, None))
+            return
+        m = np.array(gf, GridFollow).reshape(1).copy()
+        _check(self.lib.pp_set_grid_follow(self.h, _ptr(m)))
 
     def get_obstacles(self, scene, cap=256):
         """pp_get_obstacles: the scene's obstacle slice - own entries, then peers - of the input set get_scene_in reads."""

@@ -190,6 +190,9 @@ struct pp_planner {
     // route following (allocated by the first pp_set_route): the legs of every scene's route and route_first on the
     // device; with route_on pp_advance_async launches k_advance_route in the place of k_advance_egos
     bool route_on = false; RouteModel route_rm = { 0, 0 }; RouteLeg* d_route_legs = nullptr; int32_t* d_route_first = nullptr; size_t route_legs_cap = 0;
+    // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
+    // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
+    GridFollow grid_follow = { 0, 0 };
     TickRec last_rec = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
@@ -659,6 +662,8 @@ int pp_set_config(pp_handle h, const PlannerConfig* cfg)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     int r = check_cfg(cfg); if (r) return r;
+    if (h->grid_follow.goal_point > 0 && 2LL * h->grid_follow.margin_cells >= (long long)std::min(cfg->grid_w, cfg->grid_h))
+        return fail(PP_ERR_ARG, "pp_set_config: the margin of the grid-follow model no longer fits the grid (2 * margin_cells < min(grid_w, grid_h)): switch following off first");
     if (cfg->grid_stage) {
         if (!h->d_grid) return fail(PP_ERR_STATE, "handle was created without the grid stage");
         if ((size_t)cfg->grid_w * cfg->grid_h > h->grid_cells || cfg->max_path > h->max_path0)
@@ -1446,11 +1451,11 @@ int pp_advance_async(pp_handle h, const EgoModel* m, EgoTrace* trace)
     *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;          // nothing is staged for that tick: the host owns the slot (owner rule in pp_update_async)
     if (h->route_on)                      // routed egos cross junctions; the scenes without a route advance as below
         hipLaunchKernelGGL(dmpp::k_advance_route, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
-                           h->cfg, *m, h->route_rm, n, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
+                           h->cfg, *m, h->route_rm, h->grid_follow, n, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
                            h->d_route_legs, h->d_route_first, h->d_ego_flags, trace);
     else
         hipLaunchKernelGGL(dmpp::k_advance_egos, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
-                           h->cfg, *m, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
+                           h->cfg, *m, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
     if (h->fleet_on) couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);      // the peers at the poses just advanced to
     const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
     if (h->resident_mode == 1)
@@ -1652,6 +1657,26 @@ int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int3
     HIP_TRY(hipMemcpyAsync(h->d_route_first, route_first, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the caller's arrays may go; the upload stream reads the copies from its next launch on)
     h->route_rm = *rm; h->route_rm._pad = 0; h->route_on = true;
+    return PP_OK;
+}
+
+// A grid that follows the ego: host checks only; the model is a kernel argument of the next advance.
+void pp_default_grid_follow(GridFollow* gf)
+{
+    if (!gf) return;
+    gf->goal_point = DMPP_PATH_POINTS - 1; gf->margin_cells = 32;       // the end of the planned path; 8 m at the default 0.25 m cell
+}
+
+int pp_set_grid_follow(pp_handle h, const GridFollow* gf)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!gf) { h->grid_follow = GridFollow{ 0, 0 }; return PP_OK; }
+    if (gf->goal_point < 1 || gf->goal_point > DMPP_PATH_POINTS - 1)
+        return fail(PP_ERR_ARG, "pp_set_grid_follow: goal_point must be 1 .. " + std::to_string(DMPP_PATH_POINTS - 1));
+    if (gf->margin_cells < 0) return fail(PP_ERR_ARG, "pp_set_grid_follow: margin_cells must be >= 0");
+    if (2LL * gf->margin_cells >= (long long)std::min(h->cfg.grid_w, h->cfg.grid_h))
+        return fail(PP_ERR_ARG, "pp_set_grid_follow: 2 * margin_cells must be smaller than min(grid_w, grid_h)");
+    h->grid_follow = *gf;
     return PP_OK;
 }
 
@@ -2068,7 +2093,7 @@ size_t pp_sizeof(int which)
     case 12: return sizeof(PlanningOut); case 13: return sizeof(PlanningStatus); case 14: return sizeof(AimPoint);
     case 15: return sizeof(MapLane); case 16: return sizeof(MapJunction); case 17: return sizeof(MapDesc); case 18: return sizeof(PpSceneIo);
     case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore); case 22: return sizeof(FleetModel);
-    case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel);
+    case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel); case 25: return sizeof(GridFollow);
     default: return 0;
     }
 }

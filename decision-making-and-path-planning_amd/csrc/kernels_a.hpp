@@ -139,10 +139,43 @@ __device__ __forceinline__ int adv_lane_number(const LaneView& lv, int ln, const
     if (r.ir >= 0 && rc - sqrt(r.dr) > margin) return ln + 1;
     return ln;
 }
-// §4c 6.: the grid does not follow the ego
+// §4c 6.: the grid does not follow the ego (a handle without a GridFollow model; with one: adv_follow_grid below)
 __device__ __forceinline__ bool adv_off_grid(const PlannerConfig& c, const SceneIn& si, double x, double y)
 {
     const double fx = floor((x - si.grid_origin.x) / c.cell), fy = floor((y - si.grid_origin.y) / c.cell);
+    return !(fx >= 0 && fx < (double)c.grid_w && fy >= 0 && fy < (double)c.grid_h);
+}
+// §4g: the grid follows the ego.  In the place of §4c 6. for a handle with a GridFollow model (gf.goal_point > 0): the goal becomes
+// point gf.goal_point of the path the advance followed and the frame is held, or re-centred on whole cells about the midpoint of
+// ego and goal; the eight words of grid_origin and goal are replaced in the lanes that hold them, OFF_GRID is tested on the new
+// frame.  A non-finite goal point skips the step: the frame is carried over and tested as in §4c 6.  Every operand is the same
+// in all lanes.  Returns the OFF_GRID verdict.
+constexpr int kOriginWord = (int)(offsetof(SceneIn, grid_origin) / 4), kGoalWord = (int)(offsetof(SceneIn, goal) / 4);
+static_assert(offsetof(SceneIn, grid_origin) % 8 == 0 && kGoalWord == kOriginWord + 4 && kGoalWord + 4 <= kSiWords && sizeof(GlobalPoint2D) == 16,
+              "origin.x, origin.y, goal.x, goal.y are the eight words from kOriginWord, each double on an even word");
+__device__ __forceinline__ bool adv_follow_grid(const PlannerConfig& c, const GridFollow& gf, const SceneIn& si, const PlanOut& po, double x, double y,
+                                                int lane, int& w)
+{
+    GlobalPoint2D o = si.grid_origin;
+    const GlobalPoint2D g = po.road_points[gf.goal_point];
+    if (finite_f64(g.x) && finite_f64(g.y)) {
+        const double lo = (double)gf.margin_cells, hx = (double)(c.grid_w - gf.margin_cells), hy = (double)(c.grid_h - gf.margin_cells);
+        const double ex = floor((x - o.x) / c.cell), gx = floor((g.x - o.x) / c.cell);
+        const double ey = floor((y - o.y) / c.cell), gy = floor((g.y - o.y) / c.cell);
+        const bool hold = lo <= ex && ex < hx && lo <= gx && gx < hx && lo <= ey && ey < hy && lo <= gy && gy < hy;      // (a NaN: not held)
+        if (!hold) {
+            const double mx = 0.5 * (x + g.x), my = 0.5 * (y + g.y);
+            o.x = (floor(mx / c.cell) - (double)(c.grid_w / 2)) * c.cell;
+            o.y = (floor(my / c.cell) - (double)(c.grid_h / 2)) * c.cell;
+        }
+        if (lane >= kOriginWord && lane < kOriginWord + 8) {
+            const int q = (lane - kOriginWord) >> 1;
+            const double d = q == 0 ? o.x : q == 1 ? o.y : q == 2 ? g.x : g.y;
+            w = (lane & 1) ? __double2hiint(d) : __double2loint(d);
+        }
+    }
+    if (!c.grid_stage) return false;
+    const double fx = floor((x - o.x) / c.cell), fy = floor((y - o.y) / c.cell);
     return !(fx >= 0 && fx < (double)c.grid_w && fy >= 0 && fy < (double)c.grid_h);
 }
 __device__ __forceinline__ void adv_store_trace(EgoTrace* __restrict__ trace, int s, int lane, int w, int ln_new, int f)
@@ -175,7 +208,7 @@ __device__ __forceinline__ void adv_lane_step(const GlobalPoint3D* __restrict__ 
 }
 
 __global__ void __launch_bounds__(kBlock)
-k_advance_egos(PlannerConfig c, EgoModel m, int n_scenes, int map_mode, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
+k_advance_egos(PlannerConfig c, EgoModel m, GridFollow gf, int n_scenes, int map_mode, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
                const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const GlobalPoint3D* __restrict__ lane_pool,
                int32_t* __restrict__ flags, EgoTrace* __restrict__ trace)
 {
@@ -194,7 +227,8 @@ k_advance_egos(PlannerConfig c, EgoModel m, int n_scenes, int map_mode, const Sc
             if (p.path_end) f |= DMPP_EGO_PATH_END;
             adv_store_pose(w, lane, p);
             adv_lane_step(lane_pool, si.lanes, ln, m.window, map_mode, p.x, p.y, lane, w, f, ln_new);
-            if (c.grid_stage && adv_off_grid(c, si, p.x, p.y)) f |= DMPP_EGO_OFF_GRID;
+            if (gf.goal_point > 0 ? adv_follow_grid(c, gf, si, plan[s], p.x, p.y, lane, w) : (c.grid_stage && adv_off_grid(c, si, p.x, p.y)))
+                f |= DMPP_EGO_OFF_GRID;
         }
     }
     if (lane < kSiWords) reinterpret_cast<int*>(&out[s])[lane] = w;

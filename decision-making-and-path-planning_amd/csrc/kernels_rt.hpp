@@ -38,7 +38,7 @@ __device__ __forceinline__ int wave_find_junction(const MapJunction* __restrict_
 __device__ __forceinline__ void rt_zero_ids(int& w, int lane) { if (lane >= kIdWord && lane < kIdWord + DMPP_LANESUM) w = 0; }
 
 __global__ void __launch_bounds__(kBlock)
-k_advance_route(PlannerConfig c, EgoModel m, RouteModel rm, int n_scenes, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
+k_advance_route(PlannerConfig c, EgoModel m, RouteModel rm, GridFollow gf, int n_scenes, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
                 const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const GlobalPoint3D* __restrict__ lane_pool,
                 const GlobalPoint2D* __restrict__ ref_pool, int n_junctions, const MapJunction* __restrict__ junctions,
                 const RouteLeg* __restrict__ legs, const int32_t* __restrict__ route_first, int32_t* __restrict__ flags, EgoTrace* __restrict__ trace)
@@ -124,7 +124,8 @@ k_advance_route(PlannerConfig c, EgoModel m, RouteModel rm, int n_scenes, const 
                     }
                 }
             }
-            if (c.grid_stage && adv_off_grid(c, si, p.x, p.y)) f |= DMPP_EGO_OFF_GRID;
+            if (gf.goal_point > 0 ? adv_follow_grid(c, gf, si, plan[s], p.x, p.y, lane, w) : (c.grid_stage && adv_off_grid(c, si, p.x, p.y)))
+                f |= DMPP_EGO_OFF_GRID;
         }
     }
     if (lane < kSiWords) reinterpret_cast<int*>(&out[s])[lane] = w;

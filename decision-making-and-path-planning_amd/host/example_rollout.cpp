@@ -6,6 +6,9 @@
 // obstacles, the nearest egos are written there after every advance, and the scorecard tells ego-ego contact from the rest.
 // With --route the egos drive a ring of four roads on the map store (pp_set_map + pp_set_egos) along a route each (pp_set_route,
 // DESIGN.md §4f): the advance step takes them road -> pre-junction -> junction -> next road, and the host prints the legs completed.
+// With --follow the grid follows the ego (pp_set_grid_follow): the advance step re-centres grid_origin and goal.
+// Combined with --route the ring is driven with the grid stage ON, on a grid of 64 m, and the host prints how many egos carry
+// OFF_GRID at the end (without --follow a routed run keeps the grid stage off: every ego would leave its grid on its first road).
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -16,8 +19,9 @@
 #define CHECK(expr) do { int rc__ = (expr); if (rc__) { std::fprintf(stderr, "%s: %s\n", #expr, pp_last_error()); return 2; } } while (0)
 
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
-// degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off.
-static int run_route()
+// degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
+// follow, on: 256 x 256 cells that follow the ego.
+static int run_route(bool follow)
 {
     const int n = 64, ticks = 1200, P = 260, JP = 40, n_lanes = 2;
     const double kPi = 3.14159265358979323846, step = 0.5, w = 3.75;
@@ -48,7 +52,8 @@ static int run_route()
     map.road_first_lane = first.data(); map.lanes = lanes.data(); map.points = pts.data(); map.lanechg_attribute = attr.data(); map.lane_width_cm = width.data();
     map.junctions = junc.data(); map.jpoints = jpts.data();
 
-    PlannerConfig cfg; pp_default_config(&cfg, 128, 128); cfg.grid_stage = 0;      // (the grid does not follow the ego: DESIGN.md §4f)
+    PlannerConfig cfg; pp_default_config(&cfg, follow ? 256 : 128, follow ? 256 : 128);
+    if (!follow) cfg.grid_stage = 0;                  // (a grid that does not follow the ego bounds the run: DESIGN.md §4c 6., §4g)
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = 1; caps.max_lane_pts_total = (int32_t)pts.size(); caps.max_ref_pts_total = (int32_t)jpts.size();
     std::vector<SceneIn> in(n); std::vector<SceneState> st(n);
     {   // generated records for everything the map does not decide (DecisionOut, state), then the egos onto the ring
@@ -65,6 +70,8 @@ static int run_route()
         e.loc.last_roadnum = road; e.loc.next_roadnum = road % 4 + 1; e.loc.last_lanenum = lane; e.loc.next_lanenum = lane;
         for (int k = 0; k < DMPP_LANESUM; k++) { e.loc.id[k] = id; e.out_lane_no[k] = k < n_lanes ? (uint16_t)(k + 1) : 0; }
         e.lanes = LaneView{}; e.ref_off = e.ref_n = e.obs_off = e.obs_n = 0; e.stub_attribute = 1; e.period_last = 100;
+        const double half = 0.5 * cfg.grid_w * cfg.cell, th = q.dir * kPi / 180.0;      // the first tick's frame: the ego in the middle, the goal 15 m ahead
+        e.grid_origin.x = q.x - half; e.grid_origin.y = q.y - half; e.goal.x = q.x + 15.0 * std::cos(th); e.goal.y = q.y + 15.0 * std::sin(th);
         st[(size_t)s].z_target_lanenum = lane; st[(size_t)s].d_his_target_lanenum = lane;
         for (int k = 0; k < n_legs; k++) { RouteLeg g{}; g.road_num = (road - 1 + k) % 4 + 1; g.stub_attribute = 1; for (int l = 0; l < n_lanes; l++) g.out_lane_no[l] = (uint16_t)(l + 1); legs.push_back(g); }
         route_first.push_back((int32_t)legs.size());
@@ -76,6 +83,7 @@ static int run_route()
     CHECK(pp_set_state(h, st.data(), n));
     RouteModel rm; CHECK(pp_default_route_model(&rm));
     CHECK(pp_set_route(h, (int)legs.size(), legs.data(), route_first.data(), &rm));
+    if (follow) { GridFollow gf; pp_default_grid_follow(&gf); CHECK(pp_set_grid_follow(h, &gf)); }
     EgoModel model; pp_default_ego_model(&model);
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
@@ -83,16 +91,17 @@ static int run_route()
     std::vector<int32_t> flags(n); std::vector<SceneIn> end(n);
     CHECK(pp_get_ego_flags(h, flags.data(), n));
     CHECK(pp_get_scene_in(h, end.data(), n));
-    int arrived = 0, missed = 0, other = 0, legs_done = 0;
+    int arrived = 0, missed = 0, other = 0, legs_done = 0, off_grid = 0;
     std::printf("route: legs completed per ego (of its route):");
     for (int s = 0; s < n; s++) {
         const int f = flags[(size_t)s], total = route_first[(size_t)s + 1] - route_first[(size_t)s];
         const int done = end[(size_t)s].loc.path_num + ((f & DMPP_EGO_ROUTE_END) ? 1 : 0);
         std::printf(" %d/%d", done, total);
-        legs_done += done; arrived += (f & DMPP_EGO_ROUTE_END) != 0; missed += f == DMPP_EGO_LANE_END; other += (f & ~(DMPP_EGO_LANE_END | DMPP_EGO_ROUTE_END)) != 0;
+        legs_done += done; arrived += (f & DMPP_EGO_ROUTE_END) != 0; missed += f == DMPP_EGO_LANE_END; off_grid += (f & DMPP_EGO_OFF_GRID) != 0; other += (f & ~(DMPP_EGO_LANE_END | DMPP_EGO_ROUTE_END)) != 0;
     }
     std::printf("\nroute: %d egos on a ring of 4 roads for %d ticks (last tick id %lld): %d legs completed, %d arrived (ROUTE_END), %d missed an exit, %d with another flag\n",
                 n, ticks, last, legs_done, arrived, missed, other);
+    if (follow) std::printf("follow: the grid stage ran on %d x %d cells that followed the ego: %d of %d egos carry OFF_GRID\n", cfg.grid_w, cfg.grid_h, off_grid, n);
     pp_destroy(h);
     std::printf("example_rollout ok\n");
     return 0;
@@ -100,8 +109,14 @@ static int run_route()
 
 int main(int argc, char** argv)
 {
-    if (argc > 1 && std::strcmp(argv[1], "--route") == 0) return run_route();
-    const bool fleet = argc > 1 && std::strcmp(argv[1], "--fleet") == 0;
+    bool fleet = false, route = false, follow = false;
+    for (int a = 1; a < argc; a++) {
+        if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
+        else if (std::strcmp(argv[a], "--route") == 0) route = true;
+        else if (std::strcmp(argv[a], "--follow") == 0) follow = true;
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route] [--follow]\n"); return 2; }
+    }
+    if (route) return run_route(follow);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;
@@ -124,6 +139,7 @@ int main(int argc, char** argv)
     CHECK(pp_set_scenes(h, n, in.data(), lanes.data(), attr.data(), (int)lanes.size(), ref.data(), (int)ref.size(), obs.data(), nullptr, (int)obs.size()));
     CHECK(pp_set_state(h, st.data(), n));
     if (fleet) { const int32_t world_first[2] = { 0, n }; CHECK(pp_set_fleet(h, 1, world_first, &fm)); }      // one world of all egos
+    if (follow) { GridFollow gf; pp_default_grid_follow(&gf); CHECK(pp_set_grid_follow(h, &gf)); }              // OFF_GRID below: the egos the frame could not hold
 
     EgoModel model; pp_default_ego_model(&model);
     EgoTrace* trace = (EgoTrace*)pp_host_alloc(sizeof(EgoTrace) * (size_t)ticks * n);      // pinned: the kernel writes it over PCIe

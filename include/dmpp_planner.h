@@ -257,6 +257,25 @@ int  pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap);
 int  pp_default_route_model(RouteModel* rm);         /* pre_points 60: 30 m of 0.5 m points */
 int  pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int32_t* route_first, const RouteModel* rm);
 
+/* ---- a grid that follows the ego: the advance step re-centres grid and goal ------------------------------------
+ * Without it SceneIn.grid_origin and SceneIn.goal are carried over by every advance, and an ego that runs the grid stage leaves the
+ * caller's grid after a few dozen metres (DMPP_EGO_OFF_GRID, frozen).  pp_set_grid_follow switches following on: every advance
+ * (k_advance_egos and k_advance_route alike) then gives a scene that entered it unfrozen and did not get BAD_PATH
+ *     goal        = PlanOut.road_points[gf->goal_point] of the plan it followed (skipped for a non-finite point), and
+ *     grid_origin = the old one while ego and goal both lie at least gf->margin_cells cells inside the grid, otherwise
+ *                   (floor(m / cell) - W / 2) * cell per axis, m the midpoint of ego and goal: a whole number of cells,
+ * and tests DMPP_EGO_OFF_GRID against the new frame.  Every bit of the eight words is specified (§4g).  Nothing else of the record
+ * changes; frozen scenes keep their frame; records that arrive through pp_update_async are the caller's and are not touched.
+ * The model belongs to the HANDLE and holds no per-scene data: it survives pp_set_scenes / pp_set_egos / pp_set_n_scenes /
+ * pp_set_map (unlike the fleet and the routes) and takes effect from the next pp_advance_async on, a staged update or not.
+ * gf == NULL: following off - the advance is then the one of a handle that never set it, byte for byte.
+ * PP_ERR_ARG, with nothing changed: goal_point outside 1 .. DMPP_PATH_POINTS - 1, margin_cells < 0, or
+ * 2 * margin_cells >= min(grid_w, grid_h) of the handle's configuration (pp_set_config refuses, with PP_ERR_ARG, a grid the
+ * margin of a model that is switched on no longer fits).  Legal with grid_stage = 0: the frame is maintained, nothing reads
+ * it, and there is no OFF_GRID test.  No device work, no host wait. */
+void pp_default_grid_follow(GridFollow* gf);         /* goal_point 199 (the end of the planned path), margin_cells 32 (8 m at 0.25 m) */
+int  pp_set_grid_follow(pp_handle h, const GridFollow* gf);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -320,7 +339,8 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
 /* sizeof of an ABI struct, for bindings to check their mirror: 0 PlannerConfig, 1 PlannerCaps,
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
- * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel */
+ * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
+ * 25 GridFollow */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -309,6 +309,15 @@ typedef struct RouteModel {
 } RouteModel;                                                               /* 8 B */
 #define DMPP_EGO_ROUTE_END 16  /* the ego came to the end of the LAST leg of its route: it arrived                */
 
+/* ---- a grid that follows the ego (build-defined) ---------------------------------------------
+ * pp_set_grid_follow makes the advance step keep SceneIn.grid_origin and SceneIn.goal with the ego: the goal is a point of
+ * the path the last tick planned, and the grid frame is re-centred - on whole cells - on the midpoint of ego and goal
+ * whenever either of them comes within margin_cells of its edge. */
+typedef struct GridFollow {
+    int32_t goal_point;    /* index into PlanOut.road_points the goal is taken from, 1 .. DMPP_PATH_POINTS - 1 */
+    int32_t margin_cells;  /* the frame is held while ego and goal lie at least this many cells inside it      */
+} GridFollow;              /* 8 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

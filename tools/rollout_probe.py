@@ -9,7 +9,11 @@ FLEET=K: every run has a rollout leg with the fleet on (pp_set_fleet, K peer slo
 unset: one world of all scenes; FLEET_RANGE=<metres>, default the model's) and one with the fleet off whose scenes carry K far-away
 obstacles more - the same obs_n, or the comparison would charge the fleet for longer obstacle lists -, alternating.
 ROUTE=1: every run has a rollout leg of obstacle-free egos on the ring of tests/route_scenes.py (map store, grid stage off) with
-their routes set (pp_set_route: k_advance_route) and one without (k_advance_egos: the egos freeze at their lane ends), alternating."""
+their routes set (pp_set_route: k_advance_route) and one without (k_advance_egos: the egos freeze at their lane ends), alternating.
+FOLLOW=1: every run has a rollout leg of routed ring egos with the grid stage ON (256 x 256 cells) whose grid follows the ego
+(pp_set_grid_follow, default model) and one without (the egos leave their grids and freeze with OFF_GRID), alternating.
+FOLLOW=trace_on / trace_off: for rocprofv3 --kernel-trace --stats - one such ring rollout (k_advance_route) and one rollout of the
+generated scenes (k_advance_egos), both with following on / both with it off, and nothing else."""
 import os
 import statistics
 import sys
@@ -97,8 +101,33 @@ def route_run(on):
     return n * steps / dt, frozen
 
 
-def rollout_run(score=SCORE == "1"):
+def follow_run(on):
+    import route_scenes as rs
+    rcfg = dm.default_config(256)
+    m = rs.build_ring(dm)
+    sc, legs, rf = rs.make_egos(dm, rcfg, m, n, seed=5, ids=(10, 250), legs=(6, 10))
+    pl = dm.Planner(rcfg, device=0, **rs.caps(m, n))
+    pl.set_map(m)
+    pl.set_egos(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    pl.set_route(legs, rf)
+    if on:
+        pl.set_grid_follow(dm.default_grid_follow())
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    off_grid = int(((pl.ego_flags() & dm.EGO_OFF_GRID) != 0).sum())
+    pl.close()
+    return n * steps / dt, off_grid
+
+
+def rollout_run(score=SCORE == "1", follow=False):
     pl, _ = fresh()
+    if follow:
+        pl.set_grid_follow(dm.default_grid_follow())
     if score:
         pl.score_begin()
     pl.rollout(warm, model)
@@ -171,6 +200,25 @@ if os.environ.get("ROUTE", "0") == "1":
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more routed rollout alone
         route_run(True)
+    sys.exit(0)
+if os.environ.get("FOLLOW", "0").startswith("trace_"):
+    on = os.environ["FOLLOW"] == "trace_on"
+    a, fa = follow_run(on)
+    b, fb = rollout_run(False, follow=on)
+    print("following %s  %d ring egos %.3f M ticks/s (%d OFF_GRID)   %d generated scenes %.3f M ticks/s (%d frozen)" % ("on" if on else "off", n, a / 1e6, fa, n, b / 1e6, fb), flush=True)
+    sys.exit(0)
+if os.environ.get("FOLLOW", "0") == "1":
+    off, on = [], []
+    for r in range(runs):
+        a, fa = follow_run(False)
+        b, fb = follow_run(True)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos, grid stage on  follow off %.3f M ticks/s (%d OFF_GRID at the end)   follow on %.3f M ticks/s (%d OFF_GRID)" % (r, n, a / 1e6, fa, b / 1e6, fb), flush=True)
+    print("median  %d ring egos  follow off %.3f M ticks/s (spread %.3f)   follow on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more following rollout alone
+        follow_run(True)
     sys.exit(0)
 if SCORE == "ab":
     off, on = [], []
