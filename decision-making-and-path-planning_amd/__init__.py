@@ -101,6 +101,9 @@ RouteModel = _dt([("pre_points", i4), ("_pad", i4)])
 EGO_ROUTE_END = 16            # the ego came to the end of the last leg of its route (DMPP_EGO_ROUTE_END)
 # a grid that follows the ego: the advance step re-centres grid_origin and goal
 GridFollow = _dt([("goal_point", i4), ("margin_cells", i4)])
+# lane traffic: scripted vehicles that drive a polyline and sit in their scene's own obstacle entries
+TrafficTrack = _dt([("point_off", i4), ("n_points", i4), ("closed", i4), ("_pad", i4)])
+TrafficActor = _dt([("s0", f8), ("speed", f8), ("scene", i4), ("slot", i4), ("track", i4), ("type", i4), ("radius", f4), ("_pad", i4)])
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -217,6 +220,10 @@ def load_library(path=None):
         lib.pp_default_grid_follow.argtypes = [vp]
         lib.pp_default_grid_follow.restype = None
         lib.pp_set_grid_follow.argtypes = [vp, vp]
+    traffic = hasattr(lib, "pp_set_traffic") or path == LIB_PATH          # (as above: an older build may lack it)
+    if traffic:
+        lib.pp_set_traffic.argtypes = [vp, ci, vp, vp, ci, ci, vp]
+        lib.pp_get_traffic_state.argtypes = [vp, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -230,7 +237,7 @@ def load_library(path=None):
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
             (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
-            (((25, GridFollow),) if follow else ()):
+            (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -502,6 +509,26 @@ class Planner:
             return
         m = np.array(gf, GridFollow).reshape(1).copy()
         _check(self.lib.pp_set_grid_follow(self.h, _ptr(m)))
+
+    # ---- lane traffic: scripted vehicles in the scenes' own obstacle entries -----------------
+    def set_traffic(self, tracks=None, points=None, actors=None):
+        """pp_set_traffic: TrafficTrack records (slices of `points`, GlobalPoint2D) and TrafficActor records; every staged input
+        set then carries the actors at their arc length.  tracks / actors None (or no actors): traffic off."""
+        if tracks is None or actors is None or len(actors) == 0:
+            _check(self.lib.pp_set_traffic(self.h, 0, None, None, 0, 0, None))
+            self.n_traffic = 0
+            return
+        tr = np.ascontiguousarray(tracks, TrafficTrack)
+        pt = np.ascontiguousarray(points, GlobalPoint2D)
+        ac = np.ascontiguousarray(actors, TrafficActor)
+        _check(self.lib.pp_set_traffic(self.h, len(tr), _ptr(tr), _ptr(pt), len(pt), len(ac), _ptr(ac)))
+        self.n_traffic = len(ac)
+
+    def traffic_state(self):
+        """pp_get_traffic_state: the arc length of every actor in the input set get_scene_in reads (host wait)."""
+        out = np.zeros(getattr(self, "n_traffic", 0), np.float64)
+        _check(self.lib.pp_get_traffic_state(self.h, _ptr(out), len(out)))
+        return out
 
     def get_obstacles(self, scene, cap=256):
         """pp_get_obstacles: the scene's obstacle slice - own entries, then peers - of the input set get_scene_in reads."""

@@ -26,6 +26,7 @@
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
 #include "kernels_f.hpp"
+#include "kernels_t.hpp"
 
 namespace {
 
@@ -193,6 +194,13 @@ struct pp_planner {
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
+    // lane traffic (allocated by the first pp_set_traffic): the actors with their pinned pool entries, the tracks, the
+    // compact point array and the cumulative-length table; d_traffic_s: the arc length of every actor, SINGLE-COPY like d_ego_flags
+    // (the advances that step it are serial on the upload stream).  traffic_end: the largest pinned pool entry + 1
+    bool traffic_on = false; int traffic_actors = 0, traffic_end = 0;
+    dmpp::TrafficPin* d_traffic_pin = nullptr; dmpp::TrafficTrackDev* d_traffic_tracks = nullptr; double* d_traffic_cum = nullptr;
+    GlobalPoint2D* d_traffic_pts = nullptr; double* d_traffic_s = nullptr;
+    size_t traffic_actor_cap = 0, traffic_track_cap = 0, traffic_cum_cap = 0, traffic_pts_cap = 0;
     TickRec last_rec = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
@@ -265,6 +273,16 @@ void couple_fleet(pp_planner* h, hipStream_t st, SceneIn* d_in, ObPoint* d_obs, 
     hipLaunchKernelGGL(dmpp::k_couple_fleet, dim3((unsigned)((n + dmpp::kFleetScenes - 1) / dmpp::kFleetScenes)), dim3(dmpp::kBlock), 0, st,
                        n, h->fleet_fm.range * h->fleet_fm.range, h->fleet_fm.radius, h->fleet_fm.max_peers, h->d_world_first, h->d_world_of,
                        h->d_fleet_pin, d_in, d_obs, d_mot);
+}
+
+// Lane traffic of one input set on the stream that stages it: behind the copies of its obstacle pool, in front of
+// k_couple_fleet (the two write disjoint entries: traffic a scene's own, the fleet the peer slots behind them) and of
+// k_resolve_map / k_sanitise_scenes.  step: 0 places the actors where they are, EgoModel.dt moves them first.
+void move_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot, double step)
+{
+    const int n = h->traffic_actors;
+    hipLaunchKernelGGL(dmpp::k_move_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
+                       n, step, h->d_traffic_pin, h->d_traffic_tracks, h->d_traffic_cum, h->d_traffic_pts, h->d_traffic_s, d_obs, d_mot);
 }
 
 // Issues the copies of the pending downloads whose kernels have finished.  force_tick: that tick's copies are issued whatever
@@ -635,6 +653,7 @@ int pp_destroy(pp_handle h)
     if (h->ev_sc) (void)hipEventDestroy(h->ev_sc);
     for (void* b : { (void*)h->d_world_first, (void*)h->d_world_of, (void*)h->d_fleet_pin }) if (b) (void)hipFree(b);
     for (void* b : { (void*)h->d_route_legs, (void*)h->d_route_first }) if (b) (void)hipFree(b);
+    for (void* b : { (void*)h->d_traffic_pin, (void*)h->d_traffic_tracks, (void*)h->d_traffic_cum, (void*)h->d_traffic_pts, (void*)h->d_traffic_s }) if (b) (void)hipFree(b);
     void* bufs[] = { h->d_lane, h->d_attr, h->d_ref, h->d_state,
                      h->d_dec_ref, h->d_grid, h->d_scratch, h->d_map_first, h->d_map_lanes, h->d_map_width, h->d_map_junc, h->d_map_bad, h->d_bad,
                      h->d_gridbad };
@@ -744,7 +763,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
         h->have_motion = true;
     }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
-    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; note_current_set(h);
+    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; h->traffic_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_scenes");     // syncs: the caller may reuse its buffers
@@ -826,7 +845,7 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     HIP_TRY(hipMemcpyAsync(&bad, h->d_map_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total;
-    h->resident_mode = 1; h->fleet_on = false; h->route_on = false; note_current_set(h);
+    h->resident_mode = 1; h->fleet_on = false; h->route_on = false; h->traffic_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     if (bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, "pp_set_egos: " + std::to_string(bad) + " scene(s) name a road or lane outside the map"); }
@@ -856,7 +875,7 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     { int r = join_all(h); if (r) return r; }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
-    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; note_current_set(h);
+    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; h->traffic_on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->scoring) { int r = reset_scores(h); if (r) return r; }
     return validate_resident(h, n_scenes, "pp_set_n_scenes");
@@ -1351,6 +1370,9 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     // short of a scene's OWN entries would not be caught there, so it is refused here, before anything is enqueued
     if (obs_pool && h->fleet_on && n_obs_total < h->fleet_own_end)
         return fail(PP_ERR_ARG, "pp_update_async: with a fleet set the obstacle pool must cover every scene's own entries (up to entry " + std::to_string(h->fleet_own_end) + ")");
+    // with traffic set every actor's pool entry is pinned: a pool that stops short of one is refused here, like the one above
+    if (obs_pool && h->traffic_on && n_obs_total < h->traffic_end)
+        return fail(PP_ERR_ARG, "pp_update_async: with traffic set the obstacle pool must cover every actor's entry (up to entry " + std::to_string(h->traffic_end) + ")");
     if (in && h->in_staged >= 0 && h->staged_by_advance)
         return fail(PP_ERR_STATE, "pp_update_async: the SceneIn records of the next tick were already produced by pp_advance_async");
     HIP_TRY(hipSetDevice(h->device));
@@ -1390,6 +1412,7 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     // k_resolve_map / k_sanitise_scenes add to it in stream order, and a repeated update that brings new SceneIn records
     // restarts the count with k_zero_word on that stream - behind the kernels of the earlier update, which a store from the
     // host could overtake.  After the adoption nobody writes it; pp_wait_tick reads it behind the tick's downloads.
+    if (h->traffic_on) move_traffic(h, su, I.d_obs, have_motion ? I.d_mot : nullptr, 0.0);      // the actors where they are: no step
     if (h->fleet_on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
         n_obs = std::max(n_obs, h->fleet_end);
         couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);
@@ -1456,6 +1479,7 @@ int pp_advance_async(pp_handle h, const EgoModel* m, EgoTrace* trace)
     else
         hipLaunchKernelGGL(dmpp::k_advance_egos, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
                            h->cfg, *m, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
+    if (h->traffic_on) move_traffic(h, su, I.d_obs, have_motion ? I.d_mot : nullptr, m->dt);      // the actors one step on (first: the fleet's slots are disjoint)
     if (h->fleet_on) couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);      // the peers at the poses just advanced to
     const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
     if (h->resident_mode == 1)
@@ -1616,6 +1640,117 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
     return PP_OK;
+}
+
+// Lane traffic.  Everything is checked on the host before anything changes; the cumulative lengths are computed
+// here, in order (+, * and sqrt round as on the device), and uploaded.
+int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points, int n_actors, const TrafficActor* actors)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (n_tracks < 0 || n_points < 0 || n_actors < 0) return fail(PP_ERR_ARG, "pp_set_traffic: negative count");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_traffic: an update is staged for the next tick (set the traffic before staging, or after the tick)");
+    if (n_actors == 0) { h->traffic_on = false; return PP_OK; }
+    const int n = h->n_scenes;
+    if (n <= 0) return fail(PP_ERR_STATE, "pp_set_traffic: no resident scenes");
+    if (!tracks || !points || !actors || n_tracks == 0) return fail(PP_ERR_ARG, "pp_set_traffic: actors need tracks and points");
+    // tracks: compact copies of their points, and the cumulative lengths (closed: one more segment, back to the first point)
+    std::vector<dmpp::TrafficTrackDev> tdev((size_t)n_tracks);
+    std::vector<GlobalPoint2D> pts; std::vector<double> cum;
+    for (int k = 0; k < n_tracks; k++) {
+        const TrafficTrack& T = tracks[k];
+        const std::string who = "pp_set_traffic: track " + std::to_string(k);
+        if (T.n_points < 2) return fail(PP_ERR_ARG, who + " has fewer than 2 points");
+        if (T.point_off < 0 || (long long)T.point_off + T.n_points > (long long)n_points) return fail(PP_ERR_ARG, who + " lies outside the point array");
+        if (pts.size() + (size_t)T.n_points > (size_t)INT32_MAX / 2) return fail(PP_ERR_ARG, "pp_set_traffic: more than 2^30 track points");
+        const GlobalPoint2D* P = points + T.point_off;
+        for (int i = 0; i < T.n_points; i++)
+            if (!std::isfinite(P[i].x) || !std::isfinite(P[i].y)) return fail(PP_ERR_ARG, who + " has a non-finite point");
+        const bool closed = T.closed != 0;
+        const int nseg = closed ? T.n_points : T.n_points - 1;
+        tdev[(size_t)k] = { (int32_t)pts.size(), T.n_points, closed ? 1 : 0, (int32_t)cum.size() };
+        pts.insert(pts.end(), P, P + T.n_points);
+        double c = 0; cum.push_back(c);
+        for (int i = 0; i < nseg; i++) {
+            const GlobalPoint2D& A = P[i]; const GlobalPoint2D& B = P[i + 1 < T.n_points ? i + 1 : 0];
+            const double dx = B.x - A.x, dy = B.y - A.y;
+            const double xx = dx * dx, yy = dy * dy;      // (separate statements: no contraction, whatever the compiler flags)
+            c = c + std::sqrt(xx + yy); cum.push_back(c);
+        }
+        if (closed && !(c > 0)) return fail(PP_ERR_ARG, who + " is closed and has no length");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }
+    // the scenes' own entries: of the resident records, or - fleet on - the ones pinned then (obs_n counts peers now)
+    std::vector<dmpp::FleetPin> own((size_t)n);
+    if (h->fleet_on) own = h->fleet_pin;
+    else {
+        std::vector<SceneIn> rec((size_t)n);
+        HIP_TRY(hipMemcpyAsync(rec.data(), h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int s = 0; s < n; s++) { own[(size_t)s].obs_off = rec[(size_t)s].obs_off; own[(size_t)s].n_own = rec[(size_t)s].obs_n; }
+    }
+    std::vector<dmpp::TrafficPin> pin((size_t)n_actors); std::vector<double> s0((size_t)n_actors); std::vector<long long> taken((size_t)n_actors);
+    long long end_max = 0;
+    for (int a = 0; a < n_actors; a++) {
+        const TrafficActor& A = actors[a];
+        const std::string who = "pp_set_traffic: actor " + std::to_string(a);
+        if (!std::isfinite(A.s0) || !std::isfinite(A.speed)) return fail(PP_ERR_ARG, who + " has a non-finite s0 or speed");
+        if (!std::isfinite(A.radius) || !(A.radius >= 0)) return fail(PP_ERR_ARG, who + ": radius must be finite and >= 0");
+        if (A.scene < 0 || A.scene >= n) return fail(PP_ERR_ARG, who + " names a scene that is not resident");
+        if (A.track < 0 || A.track >= n_tracks) return fail(PP_ERR_ARG, who + " names a track that was not given");
+        const dmpp::FleetPin& O = own[(size_t)A.scene];
+        const long long pool = (long long)O.obs_off + A.slot;
+        if (A.slot < 0 || A.slot >= O.n_own || O.obs_off < 0 || pool >= (long long)h->caps.max_obs_total)
+            return fail(PP_ERR_ARG, who + ": slot " + std::to_string(A.slot) + " is not one of the " + std::to_string(std::max(O.n_own, 0)) + " own obstacle entries of scene " + std::to_string(A.scene));
+        pin[(size_t)a] = { A.speed, (int32_t)pool, A.track, A.type, A.radius };
+        s0[(size_t)a] = A.s0; taken[(size_t)a] = ((long long)A.scene << 32) | (long long)A.slot;
+        end_max = std::max(end_max, pool + 1);
+    }
+    std::sort(taken.begin(), taken.end());
+    for (size_t k = 1; k < taken.size(); k++)
+        if (taken[k] == taken[k - 1]) return fail(PP_ERR_ARG, "pp_set_traffic: two actors on slot " + std::to_string((int)(taken[k] & 0xffffffff)) + " of scene " + std::to_string((int)(taken[k] >> 32)));
+    // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the old arrays
+    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    // room first (a failed allocation leaves the old arrays, and the old traffic, as they were)
+    {
+        dmpp::TrafficPin* np_ = nullptr; double* ns_ = nullptr; dmpp::TrafficTrackDev* nt_ = nullptr; double* nc_ = nullptr; GlobalPoint2D* npt_ = nullptr;
+        const bool ga = (size_t)n_actors > h->traffic_actor_cap, gt = (size_t)n_tracks > h->traffic_track_cap, gc = cum.size() > h->traffic_cum_cap, gp = pts.size() > h->traffic_pts_cap;
+        int r = PP_OK;
+        if (ga) { r = dmalloc(&np_, (size_t)n_actors); if (!r) r = dmalloc(&ns_, (size_t)n_actors); }
+        if (!r && gt) r = dmalloc(&nt_, (size_t)n_tracks);
+        if (!r && gc) r = dmalloc(&nc_, cum.size());
+        if (!r && gp) r = dmalloc(&npt_, pts.size());
+        if (r) { for (void* b : { (void*)np_, (void*)ns_, (void*)nt_, (void*)nc_, (void*)npt_ }) if (b) (void)hipFree(b); return r; }
+        if (ga) { (void)hipFree(h->d_traffic_pin); (void)hipFree(h->d_traffic_s); h->d_traffic_pin = np_; h->d_traffic_s = ns_; h->traffic_actor_cap = (size_t)n_actors; }
+        if (gt) { (void)hipFree(h->d_traffic_tracks); h->d_traffic_tracks = nt_; h->traffic_track_cap = (size_t)n_tracks; }
+        if (gc) { (void)hipFree(h->d_traffic_cum); h->d_traffic_cum = nc_; h->traffic_cum_cap = cum.size(); }
+        if (gp) { (void)hipFree(h->d_traffic_pts); h->d_traffic_pts = npt_; h->traffic_pts_cap = pts.size(); }
+    }
+    h->traffic_on = false;                                // (until everything below has landed: a device error leaves traffic off, never half a set)
+    HIP_TRY(hipMemcpyAsync(h->d_traffic_pin, pin.data(), (size_t)n_actors * sizeof(dmpp::TrafficPin), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_traffic_s, s0.data(), (size_t)n_actors * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_traffic_tracks, tdev.data(), (size_t)n_tracks * sizeof(dmpp::TrafficTrackDev), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_traffic_cum, cum.data(), cum.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_traffic_pts, pts.data(), pts.size() * sizeof(GlobalPoint2D), hipMemcpyHostToDevice, h->stream));
+    h->traffic_actors = n_actors; h->traffic_end = (int)end_max;
+    move_traffic(h, h->stream, h->d_obs, h->have_motion ? h->d_mot : nullptr, 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
+    h->traffic_on = true;
+    return PP_OK;
+}
+
+int pp_get_traffic_state(pp_handle h, double* s, int n)
+{
+    if (!h || (!s && n > 0)) return fail(PP_ERR_ARG, "null argument");
+    if (!h->traffic_on) return fail(PP_ERR_STATE, "pp_get_traffic_state: no traffic is set");
+    if (n < 0 || n > h->traffic_actors) return fail(PP_ERR_ARG, "n exceeds the actors");
+    if (n == 0) return PP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    if (h->in_staged >= 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));      // (a staged update rewrites the same values)
+    return fetch(h, s, h->d_traffic_s, (size_t)n * sizeof(double));
 }
 
 // Route following.  Everything is checked on the host before anything changes; the resident records are not touched.
@@ -2094,6 +2229,7 @@ size_t pp_sizeof(int which)
     case 15: return sizeof(MapLane); case 16: return sizeof(MapJunction); case 17: return sizeof(MapDesc); case 18: return sizeof(PpSceneIo);
     case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore); case 22: return sizeof(FleetModel);
     case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel); case 25: return sizeof(GridFollow);
+    case 26: return sizeof(TrafficTrack); case 27: return sizeof(TrafficActor);
     default: return 0;
     }
 }

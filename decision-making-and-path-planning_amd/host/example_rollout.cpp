@@ -9,6 +9,9 @@
 // With --follow the grid follows the ego (pp_set_grid_follow): the advance step re-centres grid_origin and goal.
 // Combined with --route the ring is driven with the grid stage ON, on a grid of 64 m, and the host prints how many egos carry
 // OFF_GRID at the end (without --follow a routed run keeps the grid stage off: every ego would leave its grid on its first road).
+// With --route --traffic every ring ego has a slower vehicle 20 m ahead of it (pp_set_traffic): a scripted actor at
+// 1.5 m/s on the closed track of the ego's lane, written into the ego's one obstacle entry on every staged input set; the run is
+// scored, and the host prints how many egos saw their vehicle, the worst clearance and the distance travelled.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -21,7 +24,7 @@
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow)
+static int run_route(bool follow, bool traffic)
 {
     const int n = 64, ticks = 1200, P = 260, JP = 40, n_lanes = 2;
     const double kPi = 3.14159265358979323846, step = 0.5, w = 3.75;
@@ -54,7 +57,7 @@ static int run_route(bool follow)
 
     PlannerConfig cfg; pp_default_config(&cfg, follow ? 256 : 128, follow ? 256 : 128);
     if (!follow) cfg.grid_stage = 0;                  // (a grid that does not follow the ego bounds the run: DESIGN.md §4c 6., §4g)
-    PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = 1; caps.max_lane_pts_total = (int32_t)pts.size(); caps.max_ref_pts_total = (int32_t)jpts.size();
+    PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = traffic ? n : 1; caps.max_lane_pts_total = (int32_t)pts.size(); caps.max_ref_pts_total = (int32_t)jpts.size();
     std::vector<SceneIn> in(n); std::vector<SceneState> st(n);
     {   // generated records for everything the map does not decide (DecisionOut, state), then the egos onto the ring
         std::vector<GlobalPoint3D> gl((size_t)n * 3 * PP_GEN_LANE_PTS); std::vector<uint8_t> ga(gl.size()); std::vector<GlobalPoint2D> gr((size_t)n * PP_GEN_REF_PTS);
@@ -76,18 +79,61 @@ static int run_route(bool follow)
         for (int k = 0; k < n_legs; k++) { RouteLeg g{}; g.road_num = (road - 1 + k) % 4 + 1; g.stub_attribute = 1; for (int l = 0; l < n_lanes; l++) g.out_lane_no[l] = (uint16_t)(l + 1); legs.push_back(g); }
         route_first.push_back((int32_t)legs.size());
     }
+    // --traffic: one closed track per lane number - the lane's points on road 1, its junction polyline, road 2 ... - and one vehicle
+    // per ego, 20 m ahead of it along that track, in the ego's single obstacle entry
+    std::vector<TrafficTrack> tracks; std::vector<GlobalPoint2D> tpts; std::vector<TrafficActor> actors; std::vector<ObPoint> obs((size_t)n);
+    if (traffic) {
+        const int per_road = P + JP;
+        for (int l = 0; l < n_lanes; l++) {
+            tracks.push_back({ (int32_t)tpts.size(), 4 * per_road, 1, 0 });
+            for (int r = 0; r < 4; r++) {
+                const MapLane& L = lanes[(size_t)first[(size_t)r] + l];
+                for (int i = 0; i < P; i++) tpts.push_back({ pts[(size_t)L.point_off + i].x, pts[(size_t)L.point_off + i].y });
+                const MapJunction& J = junc[(size_t)r * n_lanes + l];
+                for (int i = 0; i < JP; i++) tpts.push_back(jpts[(size_t)J.point_off + i]);
+            }
+        }
+        for (int s = 0; s < n; s++) {
+            SceneIn& e = in[(size_t)s];
+            const int lane = e.loc.lane_num, at = per_road * (e.loc.road_num - 1) + e.loc.id[lane - 1];
+            const GlobalPoint2D* T = tpts.data() + tracks[(size_t)lane - 1].point_off;
+            double here = 0;                              // arc length of the ego's lane point along its track
+            for (int i = 0; i < at; i++) here += std::sqrt((T[i + 1].x - T[i].x) * (T[i + 1].x - T[i].x) + (T[i + 1].y - T[i].y) * (T[i + 1].y - T[i].y));
+            e.obs_off = s; e.obs_n = 1;
+            obs[(size_t)s] = ObPoint{ 0, 0, 0, 0.9f };    // (placed by pp_set_traffic)
+            actors.push_back(TrafficActor{ here + 20.0, 1.5, s, 0, lane - 1, 1, 0.9f, 0 });
+        }
+    }
     pp_handle h = nullptr;
     CHECK(pp_create(&cfg, 0, &caps, &h));
     CHECK(pp_set_map(h, &map));
-    CHECK(pp_set_egos(h, n, in.data(), nullptr, nullptr, 0));
+    CHECK(pp_set_egos(h, n, in.data(), traffic ? obs.data() : nullptr, nullptr, traffic ? n : 0));
     CHECK(pp_set_state(h, st.data(), n));
     RouteModel rm; CHECK(pp_default_route_model(&rm));
     CHECK(pp_set_route(h, (int)legs.size(), legs.data(), route_first.data(), &rm));
     if (follow) { GridFollow gf; pp_default_grid_follow(&gf); CHECK(pp_set_grid_follow(h, &gf)); }
     EgoModel model; pp_default_ego_model(&model);
+    if (traffic) {
+        CHECK(pp_set_traffic(h, (int)tracks.size(), tracks.data(), tpts.data(), (int)tpts.size(), n, actors.data()));
+        CHECK(pp_score_begin(h, model.dt));
+    }
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
+    if (traffic) {
+        std::vector<RolloutScore> score(n); std::vector<double> arc(n);
+        CHECK(pp_get_rollout_score(h, score.data(), n));
+        CHECK(pp_get_traffic_state(h, arc.data(), n));
+        int saw = 0, hit = 0; double worst = INFINITY, dist = 0, driven = 0;
+        for (int s = 0; s < n; s++) {
+            const RolloutScore& r = score[(size_t)s];
+            saw += r.n_ob_flag > 0; hit += r.n_collision_ticks > 0; dist += r.dist; if (r.min_clearance < worst) worst = r.min_clearance;
+            driven += arc[(size_t)s];
+        }
+        std::printf("traffic: %d vehicles at %.1f m/s, 20 m ahead of their egos: %d of %d egos saw theirs (ob_flag), %d touched it, worst clearance %.2f m, "
+                    "mean distance travelled %.1f m (a vehicle covers %.1f m; mean arc length now %.1f m)\n",
+                    n, actors[0].speed, saw, n, hit, worst, dist / n, actors[0].speed * model.dt * ticks, driven / n);
+    }
     std::vector<int32_t> flags(n); std::vector<SceneIn> end(n);
     CHECK(pp_get_ego_flags(h, flags.data(), n));
     CHECK(pp_get_scene_in(h, end.data(), n));
@@ -109,14 +155,16 @@ static int run_route(bool follow)
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false;
+    bool fleet = false, route = false, follow = false, traffic = false;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
         else if (std::strcmp(argv[a], "--follow") == 0) follow = true;
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route] [--follow]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--traffic") == 0) traffic = true;
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--traffic]] [--follow]\n"); return 2; }
     }
-    if (route) return run_route(follow);
+    if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
+    if (route) return run_route(follow, traffic);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

@@ -276,6 +276,33 @@ int  pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int
 void pp_default_grid_follow(GridFollow* gf);         /* goal_point 199 (the end of the planned path), margin_cells 32 (8 m at 0.25 m) */
 int  pp_set_grid_follow(pp_handle h, const GridFollow* gf);
 
+/* ---- lane traffic: scripted vehicles that drive the map during a rollout ------------------------------------------
+ * pp_set_traffic gives the handle n_tracks TRACKS (polylines: slices of `points`, host pointers; a closed track has one more
+ * segment from its last point back to its first) and n_actors ACTORS.  Actor a drives tracks[a.track] at a.speed m/s from arc
+ * length a.s0 and owns entry a.slot of scene a.scene's OWN obstacle entries.  From then on every input set that is staged passes
+ * through one more kernel on the upload stream (k_move_traffic, one thread per actor) that writes
+ * ObPoint { x, y, a.type, a.radius } - the point at arc length s of the track - into that entry, with zero ObMotion when the set
+ * carries a motion pool: pp_advance_async steps s by speed * EgoModel.dt first (an open track clamps at its ends, a closed one
+ * wraps), pp_update_async places the actors at the current s.  The resident set is placed inside the call: the next tick sees the
+ * traffic.  Decision, Planning, search, scoring and the scorecard read the obstacle list and so react with no change; SceneIn is
+ * never written.  Every arithmetic step is specified (§4h): a numpy restatement gives the same bytes.
+ * The call PINS every actor's pool entry, obs_off[scene] + slot of the resident records: SceneIn records uploaded later must keep
+ * the slices, and an obstacle pool uploaded later must cover every pinned entry (else PP_ERR_ARG from pp_update_async; whatever it
+ * holds in those entries is overwritten).  pp_set_fleet and pp_set_traffic may be called in either order: the fleet only adds
+ * slots behind a scene's own entries.
+ * Checked on the host, with nothing changed on failure.  PP_ERR_STATE: no resident scenes, or an update staged for the next tick.
+ * PP_ERR_ARG: a track slice outside `points` or with n_points < 2, a non-finite point, a closed track whose length is not > 0;
+ * a non-finite s0 or speed, a radius that is not finite or is negative, a scene or track out of range, a slot outside the scene's
+ * own entries (the resident obs_n, or - fleet set - the pinned n_own), two actors on one (scene, slot).  One host wait.
+ * n_actors = 0 (pointers may be NULL): traffic off - the entries keep the last pose written and are plain obstacles again.
+ * pp_set_scenes / pp_set_egos / pp_set_n_scenes switch it off too; pp_set_map and pp_set_config do not.  A handle that never calls
+ * pp_set_traffic allocates and launches none of this. */
+int  pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points,
+                    int n_actors, const TrafficActor* actors);
+/* The arc length of actors 0 .. n - 1 in the input set pp_get_scene_in reads (the staged one after an advance).  Host wait.
+ * PP_ERR_STATE while traffic is off. */
+int  pp_get_traffic_state(pp_handle h, double* s, int n);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -340,7 +367,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
- * 25 GridFollow */
+ * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

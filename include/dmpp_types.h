@@ -318,6 +318,23 @@ typedef struct GridFollow {
     int32_t margin_cells;  /* the frame is held while ego and goal lie at least this many cells inside it      */
 } GridFollow;              /* 8 B */
 
+/* ---- lane traffic (build-defined: scripted vehicles that drive a polyline during a rollout) ------
+ * pp_set_traffic gives the handle TRACKS - polylines, each a slice of one point array, closed ones with one more segment
+ * from the last point back to the first - and ACTORS: each drives one track at its own constant speed and is written, on
+ * every staged input set, into one of its scene's OWN obstacle entries.  Actors react to nothing. */
+typedef struct TrafficTrack {
+    int32_t point_off, n_points;   /* points [point_off, point_off + n_points) of the array given with the tracks; n_points >= 2 */
+    int32_t closed;                /* != 0: one more segment, from the last point back to the first                       */
+    int32_t _pad;
+} TrafficTrack;                                                             /* 16 B */
+typedef struct TrafficActor {
+    double  s0, speed;             /* metres along the track at set time; m/s (negative: backwards)                        */
+    int32_t scene, slot;           /* slot: index inside the scene's OWN obstacle entries (never a peer slot)              */
+    int32_t track, type;           /* type: ObPoint.type of the slot (nothing on the device reads it)                      */
+    float   radius;                /* ObPoint.radius of the slot (metres), finite and >= 0                                 */
+    int32_t _pad;
+} TrafficActor;                                                             /* 40 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

@@ -13,7 +13,10 @@ their routes set (pp_set_route: k_advance_route) and one without (k_advance_egos
 FOLLOW=1: every run has a rollout leg of routed ring egos with the grid stage ON (256 x 256 cells) whose grid follows the ego
 (pp_set_grid_follow, default model) and one without (the egos leave their grids and freeze with OFF_GRID), alternating.
 FOLLOW=trace_on / trace_off: for rocprofv3 --kernel-trace --stats - one such ring rollout (k_advance_route) and one rollout of the
-generated scenes (k_advance_egos), both with following on / both with it off, and nothing else."""
+generated scenes (k_advance_egos), both with following on / both with it off, and nothing else.
+TRAFFIC=A: every run has a rollout leg with lane traffic on (pp_set_traffic: A actors per scene, default 8 for TRAFFIC=1, in the first
+A of the scene's own obstacle entries, driving the scene's current lane as an open track at 1 .. 8 m/s) and one with it off: the same
+scenes after the same pp_set_traffic, switched off again, so both legs start from the same pool with the same obs_n - alternating."""
 import os
 import statistics
 import sys
@@ -76,6 +79,35 @@ def fleet_run(on):
     mean_obs = float(pl.get_scene_in()["obs_n"].mean())
     pl.close()
     return n * steps / dt, mean_obs
+
+
+TRAFFIC = int(os.environ.get("TRAFFIC", "0"))
+if TRAFFIC == 1:
+    TRAFFIC = 8
+
+
+def traffic_run(on):
+    pl, sc = fresh()
+    lanes = sc["scene_in"]["lanes"]
+    tracks, actors = np.zeros(n, dm.TrafficTrack), np.zeros(n * TRAFFIC, dm.TrafficActor)
+    tracks["point_off"], tracks["n_points"] = lanes["cur_off"], lanes["cur_n"]
+    pts = np.zeros(len(sc["lane_pool"]), dm.GlobalPoint2D)
+    pts["x"], pts["y"] = sc["lane_pool"]["x"], sc["lane_pool"]["y"]
+    k = np.arange(n * TRAFFIC)
+    actors["scene"], actors["slot"], actors["track"] = k // TRAFFIC, k % TRAFFIC, k // TRAFFIC
+    actors["s0"], actors["speed"], actors["type"], actors["radius"] = 10.0 + 12.0 * (k % TRAFFIC), 1.0 + (k % 8), 1, 0.9
+    pl.set_traffic(tracks, pts, actors)
+    if not on:
+        pl.set_traffic(None)          # the entries stay where the set call put them: plain obstacles
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    frozen = int((pl.ego_flags() != 0).sum())
+    pl.close()
+    return n * steps / dt, frozen
 
 
 def route_run(on):
@@ -187,6 +219,20 @@ if FLEET > 0:
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more fleet rollout alone
         fleet_run(True)
+    sys.exit(0)
+if TRAFFIC > 0:
+    off, on = [], []
+    for r in range(runs):
+        a, fa = traffic_run(False)
+        b, fb = traffic_run(True)
+        off.append(a), on.append(b)
+        print("run %d  %d scenes, obs_n %d  traffic off %.3f M ticks/s (%d frozen at the end)   traffic on (%d actors per scene) %.3f M ticks/s (%d frozen)" %
+              (r, n, n_obs, a / 1e6, fa, TRAFFIC, b / 1e6, fb), flush=True)
+    print("median  %d scenes  traffic off %.3f M ticks/s (spread %.3f)   traffic on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with traffic alone
+        traffic_run(True)
     sys.exit(0)
 if os.environ.get("ROUTE", "0") == "1":
     off, on = [], []
