@@ -27,6 +27,7 @@
 #include "kernels_sc.hpp"
 #include "kernels_f.hpp"
 #include "kernels_t.hpp"
+#include "kernels_op.hpp"
 
 namespace {
 
@@ -39,6 +40,42 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
         if (e__ != hipSuccess)                                                                \
             return fail(PP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));      \
     } while (0)
+
+// A device allocation that belongs to the handle and goes with it.  reserve() is grow-only and does not keep the contents; the new
+// block is allocated before the old one is released, so a failed allocation leaves the old block - and what it holds - in place.
+// Converts to T*: a buffer is passed to kernels and copies like the pointer it owns.
+template <class T> struct DevBuf {
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
+    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t capacity() const { return cap_; }              // in elements
+    int reserve(size_t count)
+    {
+        if (count == 0) count = 1;
+        if (count <= cap_) return PP_OK;
+        T* fresh = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&fresh), count * sizeof(T)));
+        if (p_) (void)hipFree(p_);
+        p_ = fresh; cap_ = count;
+        return PP_OK;
+    }
+private:
+    T* p_ = nullptr; size_t cap_ = 0;
+};
+// ... and of a pinned host array, allocated once and never handed on
+template <class T> struct HostPin {
+    HostPin() = default;
+    HostPin(const HostPin&) = delete; HostPin& operator=(const HostPin&) = delete;
+    ~HostPin() { if (p_) (void)hipHostFree(p_); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    int alloc(size_t count) { if (!p_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p_), count * sizeof(T), hipHostMallocDefault)); return PP_OK; }
+private:
+    T* p_ = nullptr;
+};
 
 struct EvPair { hipEvent_t a, b; int k; int w; };      // w: the ticks the launch between a and b stands for (a tick group's)
 
@@ -77,7 +114,7 @@ constexpr size_t kGroupBytes = size_t(4) << 30;
 constexpr int kDone = 32;          // ticks whose downloads pp_wait_tick can still name
 
 struct InputSet {
-    SceneIn* d_in = nullptr; ObPoint* d_obs = nullptr; ObMotion* d_mot = nullptr;
+    DevBuf<SceneIn> d_in; DevBuf<ObPoint> d_obs; DevBuf<ObMotion> d_mot;
     bool have_motion = false; int n_obs_total = 0;
     hipEvent_t ev_up = nullptr; bool up_recorded = false;
 };
@@ -98,38 +135,80 @@ struct PendingFetch {
     size_t n;
 };
 
+// closed-loop rollout (first pp_advance_async): the sticky DMPP_EGO_* word of every scene; ev_adv follows the last advance kernel;
+// staged_by_advance: the staged input set was produced on the device; set_tick: tick_seq when the resident scenes were last set
+// (an advance needs a tick of THESE scenes behind it)
+struct RolloutState {
+    DevBuf<int32_t> d_flags; hipEvent_t ev_adv = nullptr; bool adv_recorded = false, staged_by_advance = false;
+    long long set_tick = 0;
+};
+// rollout scorecard (first pp_score_begin): the records, one part array of grid counters per search set, ev
+// behind the last k_score_ego (upload stream); grp_scored: the open group's tick is scored
+struct ScoreState {
+    DevBuf<RolloutScore> d_score; DevBuf<dmpp::ScoreGridPart> d_grid[kBuf]; hipEvent_t ev = nullptr;
+    bool on = false, recorded = false, grp_scored = false; double dt = 0;
+};
+// fleet coupling (first pp_set_fleet): world_first, the world of every scene and the pinned slices on the device;
+// the pinned slices on the host too (a second pp_set_fleet starts from the scenes' OWN entries); end: the largest end of a
+// peer-slot run, base: the used pool size before the fleet grew it, own_end: the largest end of a scene's OWN entries
+struct FleetState {
+    bool on = false; FleetModel fm = { 0, 0, 0 }; int end = 0, base = 0, own_end = 0;
+    DevBuf<int32_t> d_world_first, d_world_of; DevBuf<dmpp::FleetPin> d_pin;
+    std::vector<dmpp::FleetPin> pin;
+};
+// route following (first pp_set_route): the legs of every scene's route and route_first on the device; while on,
+// pp_advance_async launches k_advance_route in the place of k_advance_egos
+struct RouteState { bool on = false; RouteModel rm = { 0, 0 }; DevBuf<RouteLeg> d_legs; DevBuf<int32_t> d_first; };
+// lane traffic (first pp_set_traffic): the actors with their pinned pool entries, the tracks, the compact point
+// array and the cumulative-length table; d_s: the arc length of every actor, SINGLE-COPY like the rollout flags (the advances
+// that step it are serial on the upload stream).  end: the largest pinned pool entry + 1
+struct TrafficState {
+    bool on = false; int actors = 0, end = 0;
+    DevBuf<dmpp::TrafficPin> d_pin; DevBuf<dmpp::TrafficTrackDev> d_tracks; DevBuf<double> d_cum; DevBuf<GlobalPoint2D> d_pts; DevBuf<double> d_s;
+};
+
 }  // namespace
 
+// The handle: the engine (inputs, outputs, grid engine, tick groups, streams and events), the streamed ticks, one block per
+// rollout feature, profiling.  Every device buffer is a DevBuf, released with the handle; plain pointers are views.
 struct pp_planner {
     PlannerConfig cfg;
     PlannerCaps caps;
     int device = 0;
     int n_scenes = 0;
     hipStream_t stream = nullptr;
-    // inputs
-    SceneIn* d_in = nullptr; GlobalPoint3D* d_lane = nullptr; uint8_t* d_attr = nullptr; bool have_attr = false; GlobalPoint2D* d_ref = nullptr;
-    ObPoint* d_obs = nullptr; ObMotion* d_mot = nullptr; ObPoint* d_obs_now[kObs] = {};
-    bool have_motion = false;
-    // state / outputs
-    SceneState* d_state = nullptr; PlanOut* d_plan = nullptr; GridOut* d_gout[kGout] = {}; int gout_set = 0;   // GridOut: kGout sets (a download of tick t must not hold up the searches after it); gout_set: the last grid tick's
-    GlobalPoint2D* d_dec_ref = nullptr;
-    // grid engine
-    uint8_t* d_grid = nullptr; uint16_t* d_pinfo[kBuf] = {}; uint32_t* d_closed[kBuf] = {};
-    int32_t* d_order[kBuf] = {}; int32_t* d_path[kObs] = {}; uint32_t* d_gbm[kBuf] = {};     // d_path, d_need: per snapshot set (the scoring pass of a group reads them beside the searches of the next groups)
+    // inputs: d_in / d_obs / d_mot / have_motion / n_obs_total are views of in_sets[in_cur]
+    SceneIn* d_in = nullptr; ObPoint* d_obs = nullptr; ObMotion* d_mot = nullptr; bool have_motion = false; int n_obs_total = 0;
+    DevBuf<GlobalPoint3D> d_lane; DevBuf<uint8_t> d_attr; bool have_attr = false; DevBuf<GlobalPoint2D> d_ref;
+    int n_lane_pts = 0, n_ref_pts = 0;   // pool sizes of the resident scenes (slice validation)
+    int resident_mode = 0;       // 0: scenes with their own slices (pp_set_scenes), 1: egos on the resident map (pp_set_egos)
+    DevBuf<int> d_bad;           // k_validate_scenes: scenes with a slice outside its pool
+    // map store (pp_set_map): lane / junction tables; the point pools are d_lane / d_attr / d_ref
+    DevBuf<int32_t> d_map_first; DevBuf<MapLane> d_map_lanes; DevBuf<uint16_t> d_map_width; DevBuf<MapJunction> d_map_junc;
+    DevBuf<int> d_map_bad; int map_roads = 0, map_lanes = 0, map_junctions = 0; bool have_map = false;
+    // state / outputs.  The obstacle snapshot, GridOut and the path cells are rings of sets: one allocation per group position
+    // (*_mem), the sets of its tick slots at a fixed stride inside it (dmpp::TickGroup; slots beyond gcap: none)
+    DevBuf<SceneState> d_state; PlanOut* d_plan = nullptr;       // d_plan: a view of d_plan_ring[plan_cur]
+    DevBuf<ObPoint> obs_now_mem[kRing]; ObPoint* d_obs_now[kObs] = {};
+    DevBuf<GridOut> gout_mem[kGoutRing]; GridOut* d_gout[kGout] = {}; int gout_set = 0;   // kGout sets (a download of tick t must not hold up the searches after it); gout_set: the last grid tick's
+    DevBuf<GlobalPoint2D> d_dec_ref;
+    // grid engine.  Consecutive searches overlap their tails: a search and its scoring pass run on stream_m[k % kBuf] for tick
+    // group k, and every work buffer they touch exists kBuf times (stream_m[0] is the handle's stream)
+    DevBuf<uint8_t> d_grid; DevBuf<uint16_t> d_pinfo[kBuf]; DevBuf<uint32_t> d_closed[kBuf];
+    DevBuf<int32_t> d_order[kBuf]; DevBuf<uint32_t> d_gbm[kBuf];
+    DevBuf<int32_t> path_mem[kRing]; int32_t* d_path[kObs] = {};       // d_path, d_need: per snapshot set (the scoring pass of a group reads them beside the searches of the next groups)
     int path_set = 0;                                  // the set of the last tick with the grid stage
-    int32_t* d_perm[kBuf] = {}; int32_t* d_cost[kBuf] = {};
-    uint2* d_ospill[kBuf] = {}; int spill_cap = 0; int32_t* d_retry[kBuf] = {};     // open-list spill areas (bucket_cap0 entries per scene; none when bucket_cap0 <= the LDS list)
-    // Long searches (many obstacles, large grids) overlap their tails: the searches of odd ticks run on a second stream, and
-    // every buffer a search touches exists per tick parity
-    hipStream_t stream_m[kBuf] = {}; int n_obs_total = 0; int overlap_override = -1;     // stream_m[0] is the handle's stream int overlap_override = -1;
+    DevBuf<int32_t> d_perm[kBuf], d_cost[kBuf];
+    DevBuf<uint2> d_ospill[kBuf]; int spill_cap = 0; DevBuf<int32_t> d_retry[kBuf];     // open-list spill areas (bucket_cap0 entries per scene; none when bucket_cap0 <= the LDS list)
+    hipStream_t stream_m[kBuf] = {}; int overlap_override = -1;     // env DMPP_OVERLAP (measurement knob)
     size_t grid_cells = 0;       // per scene, at creation
     int bucket_cap0 = 0, max_path0 = 0;
     // search: k_search_lds<kind> with `lds_budget` data words per view in LDS; scenes that need more go to k_search_gbm
     int search_kind = 0; int search_meta_bytes = 0; int lds_budget = 0, lds_budget_max = 0; bool lds_budget_fixed = false, search_force_gbm = false, budget_from_need = false;
     int gbm_lds = 0; int search_slots = 512; size_t search_static_lds = 0;   // static LDS of k_search<kind>
-    int32_t* d_ovf[kBuf] = {}; int32_t* d_need[kObs] = {}; int32_t* h_need = nullptr;   // h_need: pinned, [kObs], written by k_score (-1: nothing yet)
+    DevBuf<int32_t> d_ovf[kBuf], d_need[kObs]; HostPin<int32_t> h_need;   // h_need: pinned, [kObs], written by k_score (-1: nothing yet)
     int need_seen = 0;
-    int* d_gridbad = nullptr;
+    DevBuf<int> d_gridbad;
     // tick groups: gcap = the most tick slots the work buffers hold (each set: gcap * caps.max_scenes work items); tick_group =
     // env DMPP_TICK_GROUP (0: G derived from n and the search's workgroup slots).  The open group: grp_ticks ticks enqueued on the
     // front chain whose searches wait for grp_G of them (flush_group launches them; so does every entry point that reads
@@ -142,12 +221,13 @@ struct pp_planner {
     int need_set = 0;            // the snapshot set whose d_need / h_need the last group's search and scoring used
 
     hipStream_t stream_r = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the R kernels run beside the grid engine
-    // k_score of tick t runs on its own stream beside the rasterise / search of tick t+1: the obstacle snapshot, the path
-    // cells and GridOut are double-buffered by tick parity; ev_score[p] = the last k_score that used the buffers p
-    hipStream_t stream_s = nullptr; hipEvent_t ev_search[kBuf] = {}, ev_score[kObs] = {};      // ev_score: per snapshot set
+    // the scoring pass of a group runs behind its search, beside the front chains and searches of the next groups: the obstacle
+    // snapshot, the path cells and GridOut exist per (group position, tick slot); ev_search[p] = the last search that used the
+    // work buffers p, ev_score[q] = the last scoring pass that read snapshot set q
+    hipStream_t stream_s = nullptr; hipEvent_t ev_search[kBuf] = {}, ev_score[kObs] = {};
     hipEvent_t ev_raster = nullptr;
     bool score_recorded[kObs] = {}, search_recorded[kBuf] = {}, front_recorded = false, front_unjoined = false;
-    int parity = 0;              // buffers of the last tick
+    int parity = 0;              // work buffers of the last group
     bool last_piped = false;     // the last tick ran as three chains on several streams (else it ended on the handle's stream)
     int obs_set = 0;             // obstacle snapshot of the last tick (d_obs_now[obs_set])
     bool score_own_stream = false;   // env DMPP_SCORE_STREAM=1 | 2 (measurement knob): k_score on one stream of its own, lowest | highest queue priority
@@ -156,54 +236,29 @@ struct pp_planner {
     int n_cus = 256;
     int pipeline_min = 256;      // batches at least this large run the three chains on three streams (env DMPP_PIPELINE_MIN)
     bool r_on_main = false;      // the last tick ran Decision + Planning on the handle's stream (grid stage off)
-    int n_lane_pts = 0, n_ref_pts = 0;   // pool sizes of the resident scenes (slice validation)
-    int* d_bad = nullptr;        // k_validate_scenes: scenes with a slice outside its pool
-    // map store (pp_set_map): lane / junction tables; the point pools are d_lane / d_attr / d_ref
-    int32_t* d_map_first = nullptr; MapLane* d_map_lanes = nullptr; uint16_t* d_map_width = nullptr; MapJunction* d_map_junc = nullptr;
-    int* d_map_bad = nullptr; int map_roads = 0, map_lanes = 0, map_junctions = 0; bool have_map = false;
-    // op scratch (stand-alone operators)
-    void* d_scratch = nullptr; size_t scratch_bytes = 0;
+    // op scratch (stand-alone operators), in bytes
+    DevBuf<char> d_scratch;
     // streamed ticks (allocated by the first pp_update_async / pp_fetch_async)
     bool streaming = false;
-    InputSet in_sets[kIn]; int in_cur = 0, in_staged = -1;       // d_in / d_obs / d_mot / have_motion / n_obs_total alias in_sets[in_cur]
-    int resident_mode = 0;       // 0: scenes with their own slices (pp_set_scenes), 1: egos on the resident map (pp_set_egos)
-    PlanOut* d_plan_ring[kPlan] = {}; int plan_cur = 0;          // d_plan aliases d_plan_ring[plan_cur]
+    InputSet in_sets[kIn]; int in_cur = 0, in_staged = -1;
+    DevBuf<PlanOut> d_plan_ring[kPlan]; int plan_cur = 0;
     hipStream_t stream_up = nullptr, stream_dp = nullptr, stream_dg = nullptr;   // upload; download of PlanOut; download of GridOut
     hipEvent_t ev_fetched_plan[kPlan] = {}, ev_fetched_grid[kGout] = {}; bool fetched_plan_rec[kPlan] = {}, fetched_grid_rec[kGout] = {};
     hipEvent_t ev_done_p[kDone] = {}, ev_done_g[kDone] = {}; long long done_tick[kDone]; bool done_p_rec[kDone] = {}, done_g_rec[kDone] = {};
-    int32_t* h_bad = nullptr;    // pinned, [kDone]: poisoned scenes of the tick (copied down with its PlanOut)
+    HostPin<int32_t> h_bad;      // pinned, [kDone]: poisoned scenes of the tick (copied down with its PlanOut)
     long long tick_seq = 0;      // ticks enqueued so far on this handle (the id of the last one)
-    // closed-loop rollout (allocated by the first pp_advance_async): the sticky DMPP_EGO_* word of every scene; ev_adv follows the
-    // last k_advance_egos; staged_by_advance: the staged input set was produced on the device; set_tick: tick_seq when the
-    // resident scenes were last set (an advance needs a tick of THESE scenes behind it)
-    int32_t* d_ego_flags = nullptr; hipEvent_t ev_adv = nullptr; bool adv_recorded = false, staged_by_advance = false;
-    long long set_tick = 0;
-    // rollout scorecard (allocated by the first pp_score_begin): the records, one part array of grid counters per
-    // search set, ev_sc behind the last k_score_ego (upload stream); grp_scored: the open group's tick is scored
-    RolloutScore* d_rscore = nullptr; dmpp::ScoreGridPart* d_rgrid[kBuf] = {}; hipEvent_t ev_sc = nullptr;
-    bool scoring = false, sc_recorded = false, grp_scored = false; double score_dt = 0;
-    // fleet coupling (allocated by the first pp_set_fleet): world_first, the world of every scene and the pinned
-    // slices on the device; the pinned slices on the host too (a second pp_set_fleet starts from the scenes' OWN entries);
-    // fleet_end: the largest end of a peer-slot run, fleet_base: the used pool size before the fleet grew it
-    bool fleet_on = false; FleetModel fleet_fm = { 0, 0, 0 }; int fleet_end = 0, fleet_base = 0, fleet_own_end = 0;      // fleet_own_end: the largest end of a scene's OWN entries
-    int32_t* d_world_first = nullptr; int32_t* d_world_of = nullptr; dmpp::FleetPin* d_fleet_pin = nullptr;
-    std::vector<dmpp::FleetPin> fleet_pin;
-    // route following (allocated by the first pp_set_route): the legs of every scene's route and route_first on the
-    // device; with route_on pp_advance_async launches k_advance_route in the place of k_advance_egos
-    bool route_on = false; RouteModel route_rm = { 0, 0 }; RouteLeg* d_route_legs = nullptr; int32_t* d_route_first = nullptr; size_t route_legs_cap = 0;
-    // a grid that follows the ego (DESIGN.md §4g): the model travels to both advance kernels as an argument; goal_point 0 = off.
-    // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
-    GridFollow grid_follow = { 0, 0 };
-    // lane traffic (allocated by the first pp_set_traffic): the actors with their pinned pool entries, the tracks, the
-    // compact point array and the cumulative-length table; d_traffic_s: the arc length of every actor, SINGLE-COPY like d_ego_flags
-    // (the advances that step it are serial on the upload stream).  traffic_end: the largest pinned pool entry + 1
-    bool traffic_on = false; int traffic_actors = 0, traffic_end = 0;
-    dmpp::TrafficPin* d_traffic_pin = nullptr; dmpp::TrafficTrackDev* d_traffic_tracks = nullptr; double* d_traffic_cum = nullptr;
-    GlobalPoint2D* d_traffic_pts = nullptr; double* d_traffic_s = nullptr;
-    size_t traffic_actor_cap = 0, traffic_track_cap = 0, traffic_cum_cap = 0, traffic_pts_cap = 0;
     TickRec last_rec = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
+    // one block per rollout feature
+    RolloutState rollout;
+    ScoreState score;
+    FleetState fleet;
+    RouteState route;
+    TrafficState traffic;
+    // a grid that follows the ego (DESIGN.md §4g): the model travels to both advance kernels as an argument; goal_point 0 = off.
+    // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
+    GridFollow grid_follow = { 0, 0 };
     // profiling
     int profile = 0;             // 0 off, 1 every kernel of a tick between HIP events, 2 only the search kernel
     std::vector<EvPair> pending; std::vector<hipEvent_t> free_events;
@@ -211,13 +266,6 @@ struct pp_planner {
 };
 
 namespace {
-
-template <class T> int dmalloc(T** p, size_t count)
-{
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-    return PP_OK;
-}
 
 int check_cfg(const PlannerConfig* c)
 {
@@ -262,7 +310,7 @@ void note_current_set(pp_planner* h)          // after a pp_set_* call changed w
     InputSet& I = h->in_sets[h->in_cur];
     I.have_motion = h->have_motion; I.n_obs_total = h->n_obs_total;
     h->in_staged = -1;                        // an update staged before it is superseded
-    h->staged_by_advance = false; h->set_tick = h->tick_seq;
+    h->rollout.staged_by_advance = false; h->rollout.set_tick = h->tick_seq;
 }
 
 // Fleet coupling of one input set on the stream that stages it: behind the copies / the advance that produced its
@@ -271,8 +319,8 @@ void couple_fleet(pp_planner* h, hipStream_t st, SceneIn* d_in, ObPoint* d_obs, 
 {
     const int n = h->n_scenes;
     hipLaunchKernelGGL(dmpp::k_couple_fleet, dim3((unsigned)((n + dmpp::kFleetScenes - 1) / dmpp::kFleetScenes)), dim3(dmpp::kBlock), 0, st,
-                       n, h->fleet_fm.range * h->fleet_fm.range, h->fleet_fm.radius, h->fleet_fm.max_peers, h->d_world_first, h->d_world_of,
-                       h->d_fleet_pin, d_in, d_obs, d_mot);
+                       n, h->fleet.fm.range * h->fleet.fm.range, h->fleet.fm.radius, h->fleet.fm.max_peers, h->fleet.d_world_first, h->fleet.d_world_of,
+                       h->fleet.d_pin, d_in, d_obs, d_mot);
 }
 
 // Lane traffic of one input set on the stream that stages it: behind the copies of its obstacle pool, in front of
@@ -280,9 +328,9 @@ void couple_fleet(pp_planner* h, hipStream_t st, SceneIn* d_in, ObPoint* d_obs, 
 // k_resolve_map / k_sanitise_scenes.  step: 0 places the actors where they are, EgoModel.dt moves them first.
 void move_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot, double step)
 {
-    const int n = h->traffic_actors;
+    const int n = h->traffic.actors;
     hipLaunchKernelGGL(dmpp::k_move_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
-                       n, step, h->d_traffic_pin, h->d_traffic_tracks, h->d_traffic_cum, h->d_traffic_pts, h->d_traffic_s, d_obs, d_mot);
+                       n, step, h->traffic.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s, d_obs, d_mot);
 }
 
 // Issues the copies of the pending downloads whose kernels have finished.  force_tick: that tick's copies are issued whatever
@@ -374,6 +422,15 @@ int group_size(int n, int search_slots, int gcap, int forced)
 
 int flush_group(pp_planner* h);
 
+// A stream wait for an event - unless it has completed: then no barrier packet is needed (uploads and downloads run ticks ahead /
+// behind the chains that wait for them)
+hipError_t wait_unless_done(hipStream_t st, hipEvent_t e)
+{
+    if (hipEventQuery(e) == hipSuccess) return hipSuccess;
+    (void)hipGetLastError();
+    return hipStreamWaitEvent(st, e, 0);
+}
+
 // Everything the ticks enqueued so far started - on any of the four streams - is ordered before whatever the handle's
 // stream does next: ev_score[q] closes the raster -> search -> score chain of the last group that used snapshot set q, ev_join
 // the Decision -> Planning chain (stream order covers the earlier ticks).  An open tick group is launched first.  No host wait.
@@ -382,7 +439,7 @@ int join_all(pp_planner* h)
     { int r = flush_group(h); if (r) return r; }
     for (int q = 0; q < kObs; q++) if (h->score_recorded[q]) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_score[q], 0));
     if (h->front_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-    if (h->sc_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_sc, 0));
+    if (h->score.recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->score.ev, 0));
     return PP_OK;
 }
 
@@ -466,33 +523,31 @@ int setup_grid_launch(pp_planner* h)
     const size_t items = (size_t)h->gcap * h->caps.max_scenes;          // work items of a search set
     for (int q = 0; q < kBuf; q++) {
         if (!h->d_ovf[q]) {
-            int r = dmalloc(&h->d_ovf[q], items); if (r) return r;
+            int r = h->d_ovf[q].reserve(items); if (r) return r;
             HIP_TRY(hipMemsetAsync(h->d_ovf[q], 0, items * sizeof(int32_t), h->stream));
         }
-        if (!h->d_retry[q]) { int r = dmalloc(&h->d_retry[q], items); if (r) return r; }
+        if (!h->d_retry[q]) { int r = h->d_retry[q].reserve(items); if (r) return r; }
     }
     for (int q = 0; q < kObs; q++)
-        if (!h->d_need[q]) { int r = dmalloc(&h->d_need[q], (size_t)2); if (r) return r; HIP_TRY(hipMemsetAsync(h->d_need[q], 0, 2 * sizeof(int32_t), h->stream)); }   // [0] LDS need of the search, [1] its retry count
-    if (!h->h_need) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_need), kObs * sizeof(int32_t), hipHostMallocDefault));
+        if (!h->d_need[q]) { int r = h->d_need[q].reserve((size_t)2); if (r) return r; HIP_TRY(hipMemsetAsync(h->d_need[q], 0, 2 * sizeof(int32_t), h->stream)); }   // [0] LDS need of the search, [1] its retry count
+    { int r = h->h_need.alloc(kObs); if (r) return r; }
     for (int q = 0; q < kObs; q++) h->h_need[q] = -1;       // (a new configuration: what earlier searches needed says nothing; no search is in flight here)
     h->budget_from_need = false;
-    if (!h->d_gridbad) { int r = dmalloc(&h->d_gridbad, (size_t)2); if (r) return r; }
+    if (!h->d_gridbad) { int r = h->d_gridbad.reserve((size_t)2); if (r) return r; }
     if (sizeof(dmpp::ScoreShared<16>) > 48u * 1024u)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dmpp::k_score<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(dmpp::ScoreShared<16>));
     for (int q = 0; q < kBuf; q++) {
         if (!h->d_perm[q]) {
-            int r = dmalloc(&h->d_perm[q], items); if (r) return r;
+            int r = h->d_perm[q].reserve(items); if (r) return r;
             HIP_TRY(hipMemsetAsync(h->d_perm[q], 0, items * sizeof(int32_t), h->stream));
         }
         if (!h->d_cost[q]) {
-            int r = dmalloc(&h->d_cost[q], items); if (r) return r;
+            int r = h->d_cost[q].reserve(items); if (r) return r;
             HIP_TRY(hipMemsetAsync(h->d_cost[q], 0, items * sizeof(int32_t), h->stream));
         }
     }
-    for (int q = 0; q < kBuf; q++) if (!h->d_gbm[q]) {   // the dense form of the two views (row- then column-major), only written by the scenes that do not fit the LDS budget
-        int r = dmalloc(&h->d_gbm[q], items * 2 * (h->grid_cells / 32));
-        if (r) return r;
-    }
+    // the dense form of the two views (row- then column-major), only written by the scenes that do not fit the LDS budget
+    for (int q = 0; q < kBuf; q++) { int r = h->d_gbm[q].reserve(items * 2 * (h->grid_cells / 32)); if (r) return r; }
     return PP_OK;
 }
 
@@ -564,58 +619,55 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     for (int q = 0; q < kObs; q++)
         if (hipEventCreateWithFlags(&h->ev_score[q], hipEventDisableTiming) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipEventCreate failed"));
     const size_t ns = (size_t)caps->max_scenes;
-    if ((r = dmalloc(&h->in_sets[0].d_in, ns))) return bail(r);
-    h->d_in = h->in_sets[0].d_in;
-    if ((r = dmalloc(&h->d_lane, (size_t)caps->max_lane_pts_total))) return bail(r);
-    if ((r = dmalloc(&h->d_attr, (size_t)caps->max_lane_pts_total + 1))) return bail(r);
-    if ((r = dmalloc(&h->d_ref, (size_t)caps->max_ref_pts_total))) return bail(r);
-    if ((r = dmalloc(&h->in_sets[0].d_obs, (size_t)caps->max_obs_total))) return bail(r);
-    h->d_obs = h->in_sets[0].d_obs;
-    if ((r = dmalloc(&h->in_sets[0].d_mot, (size_t)caps->max_obs_total))) return bail(r);
-    h->d_mot = h->in_sets[0].d_mot;
+    if ((r = h->in_sets[0].d_in.reserve(ns))) return bail(r);
+    if ((r = h->d_lane.reserve((size_t)caps->max_lane_pts_total))) return bail(r);
+    if ((r = h->d_attr.reserve((size_t)caps->max_lane_pts_total + 1))) return bail(r);
+    if ((r = h->d_ref.reserve((size_t)caps->max_ref_pts_total))) return bail(r);
+    if ((r = h->in_sets[0].d_obs.reserve((size_t)caps->max_obs_total))) return bail(r);
+    if ((r = h->in_sets[0].d_mot.reserve((size_t)caps->max_obs_total))) return bail(r);
+    adopt_input_set(h, 0);
     if (hipMemsetAsync(h->d_mot, 0, (size_t)(caps->max_obs_total > 0 ? caps->max_obs_total : 1) * sizeof(ObMotion), h->stream) != hipSuccess)
         return bail(fail(PP_ERR_HIP, "memset failed"));     // velocities nobody uploaded are zero, never uninitialised
-    if ((r = dmalloc(&h->d_bad, (size_t)1))) return bail(r);
+    if ((r = h->d_bad.reserve((size_t)1))) return bail(r);
     // the sets of the tick slots of a group position lie at a fixed stride in one allocation (dmpp::TickGroup); slots beyond gcap: none
     const size_t obs_stride = (size_t)std::max(caps->max_obs_total, 1);
     for (int q = 0; q < kObs; q += kGroupMax) {
-        if ((r = dmalloc(&h->d_obs_now[q], h->gcap * obs_stride))) return bail(r);
-        for (int i = 1; i < h->gcap; i++) h->d_obs_now[q + i] = h->d_obs_now[q] + i * obs_stride;
+        if ((r = h->obs_now_mem[q / kGroupMax].reserve(h->gcap * obs_stride))) return bail(r);
+        for (int i = 0; i < h->gcap; i++) h->d_obs_now[q + i] = h->obs_now_mem[q / kGroupMax] + i * obs_stride;
     }
-    if ((r = dmalloc(&h->d_state, ns))) return bail(r);
-    if ((r = dmalloc(&h->d_plan_ring[0], ns))) return bail(r);
+    if ((r = h->d_state.reserve(ns))) return bail(r);
+    if ((r = h->d_plan_ring[0].reserve(ns))) return bail(r);
     h->d_plan = h->d_plan_ring[0];
     if (hipMemsetAsync(h->d_plan, 0, ns * sizeof(PlanOut), h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "memset failed"));
     for (int q = 0; q < kDone; q++) h->done_tick[q] = -1;
     for (int q = 0; q < kGout; q += kGroupMax) {
-        if ((r = dmalloc(&h->d_gout[q], h->gcap * ns))) return bail(r);
-        for (int i = 1; i < h->gcap; i++) h->d_gout[q + i] = h->d_gout[q] + i * ns;
+        if ((r = h->gout_mem[q / kGroupMax].reserve(h->gcap * ns))) return bail(r);
+        for (int i = 0; i < h->gcap; i++) h->d_gout[q + i] = h->gout_mem[q / kGroupMax] + i * ns;
     }
-    if ((r = dmalloc(&h->d_dec_ref, ns * DMPP_MAX_REFPATH))) return bail(r);
+    if ((r = h->d_dec_ref.reserve(ns * DMPP_MAX_REFPATH))) return bail(r);
     for (int q = 0; q < kGout; q += kGroupMax)
         if (hipMemsetAsync(h->d_gout[q], 0, h->gcap * ns * sizeof(GridOut), h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "memset failed"));
     if (cfg->grid_stage) {
         h->grid_cells = (size_t)cfg->grid_w * cfg->grid_h;
         h->bucket_cap0 = cfg->bucket_cap; h->max_path0 = cfg->max_path;
-        if ((r = dmalloc(&h->d_grid, h->grid_cells))) return bail(r);             // one scene as bytes, filled on demand (pp_get_grid)
+        if ((r = h->d_grid.reserve(h->grid_cells))) return bail(r);             // one scene as bytes, filled on demand (pp_get_grid)
         const size_t items = (size_t)h->gcap * ns;          // work items of a search set
         for (int q = 0; q < kBuf; q++) {
-            if ((r = dmalloc(&h->d_pinfo[q], items * h->grid_cells))) return bail(r);
-            if ((r = dmalloc(&h->d_closed[q], items * (h->grid_cells / 32)))) return bail(r);
+            if ((r = h->d_pinfo[q].reserve(items * h->grid_cells))) return bail(r);
+            if ((r = h->d_closed[q].reserve(items * (h->grid_cells / 32)))) return bail(r);
         }
         for (int q = 0; q < kObs; q += kGroupMax) {
-            if ((r = dmalloc(&h->d_path[q], h->gcap * ns * (size_t)cfg->max_path))) return bail(r);
-            for (int i = 1; i < h->gcap; i++) h->d_path[q + i] = h->d_path[q] + i * ns * (size_t)cfg->max_path;
+            if ((r = h->path_mem[q / kGroupMax].reserve(h->gcap * ns * (size_t)cfg->max_path))) return bail(r);
+            for (int i = 0; i < h->gcap; i++) h->d_path[q + i] = h->path_mem[q / kGroupMax] + i * ns * (size_t)cfg->max_path;
         }
-        for (int q = 0; q < kBuf; q++) if (caps->order_cap > 0 && (r = dmalloc(&h->d_order[q], items * (size_t)caps->order_cap))) return bail(r);
+        for (int q = 0; q < kBuf; q++) if (caps->order_cap > 0 && (r = h->d_order[q].reserve(items * (size_t)caps->order_cap))) return bail(r);
         if (cfg->bucket_cap > DMPP_OPEN_CAP) {
             h->spill_cap = cfg->bucket_cap;
-            for (int q = 0; q < kBuf; q++) if ((r = dmalloc(&h->d_ospill[q], items * (size_t)h->spill_cap))) return bail(r);
+            for (int q = 0; q < kBuf; q++) if ((r = h->d_ospill[q].reserve(items * (size_t)h->spill_cap))) return bail(r);
         }
         if ((r = setup_grid_launch(h))) return bail(r);
     }
-    h->scratch_bytes = 4u << 20;
-    if (hipMalloc(&h->d_scratch, h->scratch_bytes) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipMalloc(scratch) failed"));
+    if ((r = h->d_scratch.reserve(4u << 20))) return bail(r);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "sync failed"));
     *out = h;
     return PP_OK;
@@ -625,54 +677,23 @@ int pp_destroy(pp_handle h)
 {
     if (!h) return PP_OK;
     (void)hipSetDevice(h->device);
-    (void)flush_group(h);                     // (the open group's work buffers are freed below: its launches are enqueued and waited for)
-    for (hipStream_t st : { h->stream, h->stream_r, h->stream_s }) if (st) (void)hipStreamSynchronize(st);
-    for (int q = 1; q < kBuf; q++) if (h->stream_m[q]) (void)hipStreamSynchronize(h->stream_m[q]);
-    for (auto& p : h->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    for (auto e : h->free_events) (void)hipEventDestroy(e);
-    if (h->stream_s) (void)hipStreamSynchronize(h->stream_s);
+    (void)flush_group(h);                     // (the open group's work buffers go with the handle: its launches are enqueued and waited for)
     if (h->stream_dg == h->stream_dp) h->stream_dg = nullptr;
     if (h->stream_dp == h->stream_up) h->stream_dp = nullptr;
-    for (hipStream_t st : { h->stream_up, h->stream_dp, h->stream_dg }) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    for (int q = 0; q < kObs; q += kGroupMax) if (h->d_obs_now[q]) (void)hipFree(h->d_obs_now[q]);      // (one allocation per group position)
-    for (int q = 0; q < kIn; q++) {
-        InputSet& I = h->in_sets[q];
-        for (void* b : { (void*)I.d_in, (void*)I.d_obs, (void*)I.d_mot }) if (b) (void)hipFree(b);
-        if (I.ev_up) (void)hipEventDestroy(I.ev_up);
-    }
-    for (int q = 0; q < kPlan; q++) { if (h->d_plan_ring[q]) (void)hipFree(h->d_plan_ring[q]); if (h->ev_fetched_plan[q]) (void)hipEventDestroy(h->ev_fetched_plan[q]); }
-    for (int q = 0; q < kGout; q++) { if (h->ev_fetched_grid[q]) (void)hipEventDestroy(h->ev_fetched_grid[q]); if (q % kGroupMax == 0 && h->d_gout[q]) (void)hipFree(h->d_gout[q]); }
-    for (int q = 0; q < kDone; q++) { if (h->ev_done_p[q]) (void)hipEventDestroy(h->ev_done_p[q]); if (h->ev_done_g[q]) (void)hipEventDestroy(h->ev_done_g[q]); }
-    for (auto e : h->sync_events) (void)hipEventDestroy(e);
-    for (auto& r : h->inflight) { (void)hipEventDestroy(r.ev_front); if (r.ev_tail) (void)hipEventDestroy(r.ev_tail); }
-    if (h->h_bad) (void)hipHostFree(h->h_bad);
-    if (h->d_ego_flags) (void)hipFree(h->d_ego_flags);
-    if (h->ev_adv) (void)hipEventDestroy(h->ev_adv);
-    if (h->d_rscore) (void)hipFree(h->d_rscore);
-    for (int q = 0; q < kBuf; q++) if (h->d_rgrid[q]) (void)hipFree(h->d_rgrid[q]);
-    if (h->ev_sc) (void)hipEventDestroy(h->ev_sc);
-    for (void* b : { (void*)h->d_world_first, (void*)h->d_world_of, (void*)h->d_fleet_pin }) if (b) (void)hipFree(b);
-    for (void* b : { (void*)h->d_route_legs, (void*)h->d_route_first }) if (b) (void)hipFree(b);
-    for (void* b : { (void*)h->d_traffic_pin, (void*)h->d_traffic_tracks, (void*)h->d_traffic_cum, (void*)h->d_traffic_pts, (void*)h->d_traffic_s }) if (b) (void)hipFree(b);
-    void* bufs[] = { h->d_lane, h->d_attr, h->d_ref, h->d_state,
-                     h->d_dec_ref, h->d_grid, h->d_scratch, h->d_map_first, h->d_map_lanes, h->d_map_width, h->d_map_junc, h->d_map_bad, h->d_bad,
-                     h->d_gridbad };
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    for (int q = 0; q < kBuf; q++)
-        for (void* b : { (void*)h->d_ospill[q], (void*)h->d_retry[q], (void*)h->d_pinfo[q], (void*)h->d_closed[q], (void*)h->d_order[q],
-                         (void*)h->d_gbm[q], (void*)h->d_perm[q], (void*)h->d_cost[q], (void*)h->d_ovf[q] })
-            if (b) (void)hipFree(b);
-    for (int q = 0; q < kObs; q++) for (void* b : { q % kGroupMax == 0 ? (void*)h->d_path[q] : nullptr, (void*)h->d_need[q] }) if (b) (void)hipFree(b);
-    for (int q = 0; q < kBuf; q++) if (h->ev_search[q]) (void)hipEventDestroy(h->ev_search[q]);
-    for (int q = 0; q < kObs; q++) if (h->ev_score[q]) (void)hipEventDestroy(h->ev_score[q]);
-    if (h->ev_raster) (void)hipEventDestroy(h->ev_raster);
-    if (h->h_need) (void)hipHostFree(h->h_need);
-    if (h->stream_s) (void)hipStreamDestroy(h->stream_s);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->stream_r) { (void)hipStreamSynchronize(h->stream_r); (void)hipStreamDestroy(h->stream_r); }
-    for (int q = 1; q < kBuf; q++) if (h->stream_m[q]) (void)hipStreamDestroy(h->stream_m[q]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    // every stream is idle before the first buffer is released (the buffers go last, with the handle)
+    std::vector<hipStream_t> streams = { h->stream, h->stream_r, h->stream_s, h->stream_up, h->stream_dp, h->stream_dg };
+    for (int q = 1; q < kBuf; q++) streams.push_back(h->stream_m[q]);      // (stream_m[0] is the handle's stream)
+    for (hipStream_t st : streams) if (st) (void)hipStreamSynchronize(st);
+    for (auto& p : h->pending) { h->free_events.push_back(p.a); h->free_events.push_back(p.b); }
+    for (auto& r : h->inflight) { h->sync_events.push_back(r.ev_front); h->sync_events.push_back(r.ev_tail); }
+    for (const InputSet& I : h->in_sets) h->sync_events.push_back(I.ev_up);
+    for (auto* evs : { &h->free_events, &h->sync_events }) for (hipEvent_t e : *evs) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : { h->ev_fork, h->ev_join, h->ev_raster, h->rollout.ev_adv, h->score.ev }) if (e) (void)hipEventDestroy(e);
+    auto destroy_all = [](hipEvent_t* ev, int count) { for (int q = 0; q < count; q++) if (ev[q]) (void)hipEventDestroy(ev[q]); };
+    destroy_all(h->ev_search, kBuf); destroy_all(h->ev_score, kObs);
+    destroy_all(h->ev_fetched_plan, kPlan); destroy_all(h->ev_fetched_grid, kGout);
+    destroy_all(h->ev_done_p, kDone); destroy_all(h->ev_done_g, kDone);
+    for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
     delete h;
     return PP_OK;
 }
@@ -701,9 +722,9 @@ int pp_set_config(pp_handle h, const PlannerConfig* cfg)
 // New resident scenes: the rollout flags of the old ones go (behind the last advance; the caller's host wait follows).
 static int reset_ego_flags(pp_handle h)
 {
-    if (!h->d_ego_flags) return PP_OK;
-    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
-    HIP_TRY(hipMemsetAsync(h->d_ego_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), h->stream));
+    if (!h->rollout.d_flags) return PP_OK;
+    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    HIP_TRY(hipMemsetAsync(h->rollout.d_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), h->stream));
     return PP_OK;
 }
 
@@ -711,11 +732,11 @@ static int reset_ego_flags(pp_handle h)
 // before it); the caller's host wait follows.
 static int reset_scores(pp_handle h)
 {
-    if (!h->d_rscore) return PP_OK;
+    if (!h->score.d_score) return PP_OK;
     const int ns = h->caps.max_scenes;
-    hipLaunchKernelGGL(dmpp::k_score_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->d_rscore);
+    hipLaunchKernelGGL(dmpp::k_score_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->score.d_score);
     HIP_TRY(hipGetLastError());
-    for (int q = 0; q < kBuf; q++) HIP_TRY(hipMemsetAsync(h->d_rgrid[q], 0, (size_t)ns * sizeof(dmpp::ScoreGridPart), h->stream));
+    for (int q = 0; q < kBuf; q++) HIP_TRY(hipMemsetAsync(h->score.d_grid[q], 0, (size_t)ns * sizeof(dmpp::ScoreGridPart), h->stream));
     return PP_OK;
 }
 
@@ -738,6 +759,30 @@ static int validate_resident(pp_handle h, int n_scenes, const char* who)
     return PP_OK;
 }
 
+// The obstacle and motion pools of new resident scenes, into the current input set (handle's stream).
+static int upload_pools(pp_handle h, const ObPoint* obs_pool, const ObMotion* mot_pool, int n_obs_total)
+{
+    if (n_obs_total && obs_pool) HIP_TRY(hipMemcpyAsync(h->d_obs, obs_pool, (size_t)n_obs_total * sizeof(ObPoint), hipMemcpyDefault, h->stream));
+    h->have_motion = false;
+    if (n_obs_total && mot_pool) {
+        HIP_TRY(hipMemcpyAsync(h->d_mot, mot_pool, (size_t)n_obs_total * sizeof(ObMotion), hipMemcpyDefault, h->stream));
+        h->have_motion = true;
+    }
+    return PP_OK;
+}
+
+// The end of every call that replaces the resident scenes (h->n_scenes and the pool sizes are the new ones): the features that
+// hold per-scene data of the old scenes go off, the rollout flags and the scorecard start again, the slices are checked
+// last (which syncs: the caller may reuse its buffers).  map_bad: scenes that k_resolve_map could not place (pp_set_egos).
+static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad = 0)
+{
+    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; note_current_set(h);
+    { int r = reset_ego_flags(h); if (r) return r; }
+    if (h->score.on) { int r = reset_scores(h); if (r) return r; }
+    if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
+    return validate_resident(h, h->n_scenes, who);
+}
+
 int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoint3D* lane_pool, const uint8_t* lane_attr_pool,
                   int n_lane_pts, const GlobalPoint2D* ref_pool, int n_ref_pts, const ObPoint* obs_pool, const ObMotion* mot_pool, int n_obs_total)
 {
@@ -756,17 +801,9 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
         h->have_attr = true;
     }
     if (n_ref_pts && ref_pool) HIP_TRY(hipMemcpyAsync(h->d_ref, ref_pool, (size_t)n_ref_pts * sizeof(GlobalPoint2D), hipMemcpyDefault, h->stream));
-    if (n_obs_total && obs_pool) HIP_TRY(hipMemcpyAsync(h->d_obs, obs_pool, (size_t)n_obs_total * sizeof(ObPoint), hipMemcpyDefault, h->stream));
-    h->have_motion = false;
-    if (n_obs_total && mot_pool) {
-        HIP_TRY(hipMemcpyAsync(h->d_mot, mot_pool, (size_t)n_obs_total * sizeof(ObMotion), hipMemcpyDefault, h->stream));
-        h->have_motion = true;
-    }
+    { int r = upload_pools(h, obs_pool, mot_pool, n_obs_total); if (r) return r; }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
-    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; h->traffic_on = false; note_current_set(h);
-    { int r = reset_ego_flags(h); if (r) return r; }
-    if (h->scoring) { int r = reset_scores(h); if (r) return r; }
-    return validate_resident(h, n_scenes, "pp_set_scenes");     // syncs: the caller may reuse its buffers
+    return resident_replaced(h, 0, "pp_set_scenes");
 }
 
 static int fetch(pp_handle h, void* dst, const void* src, size_t bytes);
@@ -793,16 +830,11 @@ int pp_set_map(pp_handle h, const MapDesc* m)
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }
     HIP_TRY(hipStreamSynchronize(h->stream));
-    void* old[] = { h->d_map_first, h->d_map_lanes, h->d_map_junc };
-    for (void* b : old) if (b) (void)hipFree(b);
-    h->d_map_first = nullptr; h->d_map_lanes = nullptr; h->d_map_junc = nullptr; h->have_map = false;
-    h->route_on = false;                                 // (the routes named roads of the old map)
+    h->have_map = false;                                 // (until the new tables have landed)
+    h->route.on = false;                                 // (the routes named roads of the old map)
     int r;
-    if ((r = dmalloc(&h->d_map_first, (size_t)m->n_roads + 1))) return r;
-    if ((r = dmalloc(&h->d_map_lanes, (size_t)(m->n_lanes > 0 ? m->n_lanes : 1)))) return r;
-    if ((r = dmalloc(&h->d_map_junc, (size_t)(m->n_junctions > 0 ? m->n_junctions : 1)))) return r;
-    if (!h->d_map_width && (r = dmalloc(&h->d_map_width, (size_t)h->caps.max_lane_pts_total + 1))) return r;
-    if (!h->d_map_bad && (r = dmalloc(&h->d_map_bad, (size_t)1))) return r;
+    if ((r = h->d_map_first.reserve((size_t)m->n_roads + 1)) || (r = h->d_map_lanes.reserve((size_t)m->n_lanes)) || (r = h->d_map_junc.reserve((size_t)m->n_junctions)) ||
+        (r = h->d_map_width.reserve((size_t)h->caps.max_lane_pts_total + 1)) || (r = h->d_map_bad.reserve((size_t)1))) return r;
     if (m->n_roads) HIP_TRY(hipMemcpyAsync(h->d_map_first, m->road_first_lane, ((size_t)m->n_roads + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     else HIP_TRY(hipMemsetAsync(h->d_map_first, 0, sizeof(int32_t), h->stream));
     if (m->n_lanes) HIP_TRY(hipMemcpyAsync(h->d_map_lanes, m->lanes, (size_t)m->n_lanes * sizeof(MapLane), hipMemcpyHostToDevice, h->stream));
@@ -829,12 +861,7 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }
     HIP_TRY(hipMemcpyAsync(h->d_in, in, (size_t)n_scenes * sizeof(SceneIn), hipMemcpyDefault, h->stream));
-    if (n_obs_total && obs_pool) HIP_TRY(hipMemcpyAsync(h->d_obs, obs_pool, (size_t)n_obs_total * sizeof(ObPoint), hipMemcpyDefault, h->stream));
-    h->have_motion = false;
-    if (n_obs_total && mot_pool) {
-        HIP_TRY(hipMemcpyAsync(h->d_mot, mot_pool, (size_t)n_obs_total * sizeof(ObMotion), hipMemcpyDefault, h->stream));
-        h->have_motion = true;
-    }
+    { int r = upload_pools(h, obs_pool, mot_pool, n_obs_total); if (r) return r; }
     HIP_TRY(hipMemsetAsync(h->d_map_bad, 0, sizeof(int), h->stream));
     if (n_scenes)
         hipLaunchKernelGGL(dmpp::k_resolve_map, dim3((unsigned)((n_scenes + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream,
@@ -845,18 +872,14 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     HIP_TRY(hipMemcpyAsync(&bad, h->d_map_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total;
-    h->resident_mode = 1; h->fleet_on = false; h->route_on = false; h->traffic_on = false; note_current_set(h);
-    { int r = reset_ego_flags(h); if (r) return r; }
-    if (h->scoring) { int r = reset_scores(h); if (r) return r; }
-    if (bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, "pp_set_egos: " + std::to_string(bad) + " scene(s) name a road or lane outside the map"); }
-    return validate_resident(h, n_scenes, "pp_set_egos");       // the obstacle slices are still the caller's
+    return resident_replaced(h, 1, "pp_set_egos", bad);         // (the obstacle slices are still the caller's: checked there)
 }
 
 int pp_get_scene_in(pp_handle h, SceneIn* out, int n)
 {
     if (!h || !out) return fail(PP_ERR_ARG, "null argument");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
-    if (h->in_staged >= 0 && h->staged_by_advance) {      // the records the advance produced for the next tick exist only on the device
+    if (h->in_staged >= 0 && h->rollout.staged_by_advance) {      // the records the advance produced for the next tick exist only on the device
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));
         return fetch(h, out, h->in_sets[h->in_staged].d_in, (size_t)n * sizeof(SceneIn));
@@ -875,10 +898,7 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     { int r = join_all(h); if (r) return r; }
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
-    h->resident_mode = 0; h->fleet_on = false; h->route_on = false; h->traffic_on = false; note_current_set(h);
-    { int r = reset_ego_flags(h); if (r) return r; }
-    if (h->scoring) { int r = reset_scores(h); if (r) return r; }
-    return validate_resident(h, n_scenes, "pp_set_n_scenes");
+    return resident_replaced(h, 0, "pp_set_n_scenes");
 }
 
 int pp_set_state(pp_handle h, const SceneState* state, int n)
@@ -918,7 +938,6 @@ int flush_group(pp_planner* h)
     if (!overlap)                                                      // one search at a time (also after a switch of mode)
         for (int q = 0; q < kBuf; q++) if (q != p && h->search_recorded[q]) HIP_TRY(hipStreamWaitEvent(sm, h->ev_search[q], 0));
     if (sf != sm) HIP_TRY(hipStreamWaitEvent(sm, h->ev_raster, 0));
-    auto wait_unless_done = [](hipStream_t st, hipEvent_t e) { if (hipEventQuery(e) == hipSuccess) return hipSuccess; (void)hipGetLastError(); return hipStreamWaitEvent(st, e, 0); };
     for (int i = 0; i < G; i++)
         if (h->streaming && h->fetched_grid_rec[h->grp_gs[i]]) HIP_TRY(wait_unless_done(sm, h->ev_fetched_grid[h->grp_gs[i]]));   // GridOut set still being downloaded
     dmpp::TickGroup tg;                                                // slot i: sets grp_set[0] + i, grp_gs[0] + i
@@ -969,10 +988,10 @@ int flush_group(pp_planner* h)
         else
             hipLaunchKernelGGL(dmpp::k_score<4>, dim3(items), dim3(4 * DMPP_WAVE), sizeof(dmpp::ScoreShared<4>), ss, c, items, tg, need, need_host);
     }
-    if (h->grp_scored) {                             // scorecard, grid half: behind the tick's k_score, in front of ev_score / the tick's ev_tail (a scored tick is a group of 1)
+    if (h->score.grp_scored) {                             // scorecard, grid half: behind the tick's k_score, in front of ev_score / the tick's ev_tail (a scored tick is a group of 1)
         hipLaunchKernelGGL(dmpp::k_score_grid, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, ss,
-                           n, std::min(c.n_lattice, DMPP_MAX_LATTICE - 1), h->d_gout[h->grp_gs[G - 1]], h->d_rgrid[p]);
-        h->grp_scored = false;
+                           n, std::min(c.n_lattice, DMPP_MAX_LATTICE - 1), h->d_gout[h->grp_gs[G - 1]], h->score.d_grid[p]);
+        h->score.grp_scored = false;
     }
     for (int i = 0; i < G; i++) {                    // the group's scoring pass is the last reader of its G snapshot sets
         h->score_recorded[h->grp_set[i]] = piped;
@@ -1016,7 +1035,7 @@ int pp_plan_tick(pp_handle h)
     const bool open = h->grp_ticks == 0;
     // streamed inputs: the update staged by pp_update_async becomes the set this tick (and the following ones) read
     bool adopted = false;
-    if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; h->staged_by_advance = false; adopted = true; }
+    if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; h->rollout.staged_by_advance = false; adopted = true; }
     if (open) {
         h->grp_p_prev = h->parity;
         if (c.grid_stage) { h->parity = (h->parity + 1) % kBuf; h->gring = (h->gring + 1) % kGoutRing; }
@@ -1041,7 +1060,7 @@ int pp_plan_tick(pp_handle h)
         const int items = G * n;
         if (!h->lds_budget_fixed) {
             int need = -1;
-            for (int q = 0; q < kBuf; q++) need = std::max(need, (int)reinterpret_cast<volatile int32_t*>(h->h_need)[((h->ring + kRing - 1 - q) % kRing) * kGroupMax]);     // the last kBuf groups' sets
+            for (int q = 0; q < kBuf; q++) need = std::max(need, (int)reinterpret_cast<volatile int32_t*>(h->h_need.get())[((h->ring + kRing - 1 - q) % kRing) * kGroupMax]);     // the last kBuf groups' sets
             int want = h->lds_budget;
             if (need >= 0) {
                 h->need_seen = need;
@@ -1104,16 +1123,14 @@ int pp_plan_tick(pp_handle h)
         HIP_TRY(hipEventRecord(h->ev_fork, h->stream)); HIP_TRY(hipStreamWaitEvent(sf, h->ev_fork, 0));
     }
     h->r_on_main = sr == h->stream;
-    // (an event that has completed needs no barrier packet on the front chain: uploads and downloads run ticks ahead / behind)
-    auto wait_unless_done = [](hipStream_t st, hipEvent_t e) { if (hipEventQuery(e) == hipSuccess) return hipSuccess; (void)hipGetLastError(); return hipStreamWaitEvent(st, e, 0); };
     if (adopted && h->in_sets[h->in_cur].up_recorded) HIP_TRY(wait_unless_done(sf, h->in_sets[h->in_cur].ev_up));   // every kernel of the tick follows the snapshot kernel
     if (h->streaming && h->fetched_plan_rec[h->plan_cur]) HIP_TRY(wait_unless_done(sr, h->ev_fetched_plan[h->plan_cur]));   // PlanOut set still being downloaded (kPlan ticks ago)
     // Scorecard: k_score_ego of the last scored tick (upload stream) reads the SceneState this front chain rewrites, and sets of the
     // PlanOut and snapshot rings that a later one does.  A tick that adopts an update or an advance waits for that set's ev_up,
     // recorded behind the kernel on the same stream (staging always follows the tick it follows); any other tick waits here.
-    if (h->sc_recorded) {
-        if (hipEventQuery(h->ev_sc) == hipSuccess) h->sc_recorded = false;
-        else { (void)hipGetLastError(); if (!(adopted && h->in_sets[h->in_cur].up_recorded)) HIP_TRY(hipStreamWaitEvent(sf, h->ev_sc, 0)); }
+    if (h->score.recorded) {
+        if (hipEventQuery(h->score.ev) == hipSuccess) h->score.recorded = false;
+        else { (void)hipGetLastError(); if (!(adopted && h->in_sets[h->in_cur].up_recorded)) HIP_TRY(hipStreamWaitEvent(sf, h->score.ev, 0)); }
     }
     ObPoint* obs_now = h->d_obs_now[po];
     {
@@ -1142,7 +1159,7 @@ int pp_plan_tick(pp_handle h)
         h->grp_set[slot] = po; h->grp_gs[slot] = gs; h->grp_in = h->d_in;
         h->grp_ticks = slot + 1;
         h->gout_set = gs; h->path_set = po;
-        h->grp_scored = h->scoring;
+        h->score.grp_scored = h->score.on;
         if (last_of_group) { int r = flush_group(h); if (r) return r; }
     }
     h->last_piped = piped;
@@ -1153,12 +1170,12 @@ int pp_plan_tick(pp_handle h)
         HIP_TRY(hipEventRecord(rec.ev_front, sr));
         if (rec.ev_tail) HIP_TRY(hipEventRecord(rec.ev_tail, piped ? (h->grp_overlap && !h->score_own_stream ? sm : h->stream_s) : h->stream));
         h->inflight.push_back(rec); h->last_rec = rec;
-        if (h->scoring) {        // scorecard, front half: behind this tick's Planning kernel, on the upload stream - in front of the advance that may follow
+        if (h->score.on) {        // scorecard, front half: behind this tick's Planning kernel, on the upload stream - in front of the advance that may follow
             hipStream_t su = h->stream_up;
             HIP_TRY(hipStreamWaitEvent(su, rec.ev_front, 0));
             hipLaunchKernelGGL(dmpp::k_score_ego, dim3((unsigned)((n + dmpp::kScScenes - 1) / dmpp::kScScenes)), dim3(dmpp::kBlock), 0, su,
-                               0.5 * c.Vehicle_Width, h->score_dt, n, h->n_obs_total, h->d_in, h->d_plan, h->d_state, obs_now, h->d_ego_flags, h->d_rscore);
-            HIP_TRY(hipEventRecord(h->ev_sc, su)); h->sc_recorded = true;
+                               0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total, h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score);
+            HIP_TRY(hipEventRecord(h->score.ev, su)); h->score.recorded = true;
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1259,7 +1276,7 @@ int pp_get_search_info(pp_handle h, int32_t* lds_budget_words, int32_t* need_wor
         HIP_TRY(hipSetDevice(h->device));
         { int r = join_all(h); if (r) return r; }
         HIP_TRY(hipStreamSynchronize(h->stream));
-        const int32_t v = reinterpret_cast<volatile int32_t*>(h->h_need)[h->need_set];
+        const int32_t v = reinterpret_cast<volatile int32_t*>(h->h_need.get())[h->need_set];
         if (v >= 0) h->need_seen = v;
         *need_words = h->need_seen;
     }
@@ -1322,13 +1339,13 @@ static int ensure_streaming(pp_handle h)
     int r;
     for (int q = 0; q < kIn; q++) {
         InputSet& I = h->in_sets[q];
-        if (!I.d_in && (r = dmalloc(&I.d_in, ns))) return r;
-        if (!I.d_obs && (r = dmalloc(&I.d_obs, no))) return r;
-        if (!I.d_mot) { if ((r = dmalloc(&I.d_mot, no))) return r; HIP_TRY(hipMemsetAsync(I.d_mot, 0, no * sizeof(ObMotion), h->stream)); }
+        if (!I.d_in && (r = I.d_in.reserve(ns))) return r;
+        if (!I.d_obs && (r = I.d_obs.reserve(no))) return r;
+        if (!I.d_mot) { if ((r = I.d_mot.reserve(no))) return r; HIP_TRY(hipMemsetAsync(I.d_mot, 0, no * sizeof(ObMotion), h->stream)); }
         if (!I.ev_up) HIP_TRY(hipEventCreateWithFlags(&I.ev_up, hipEventDisableTiming));
     }
     for (int q = 1; q < kPlan; q++) if (!h->d_plan_ring[q]) {
-        if ((r = dmalloc(&h->d_plan_ring[q], ns))) return r;
+        if ((r = h->d_plan_ring[q].reserve(ns))) return r;
         HIP_TRY(hipMemsetAsync(h->d_plan_ring[q], 0, ns * sizeof(PlanOut), h->stream));
     }
     int prio_least = 0, prio_greatest = 0;
@@ -1345,7 +1362,7 @@ static int ensure_streaming(pp_handle h)
         if (!h->ev_done_p[q]) HIP_TRY(hipEventCreateWithFlags(&h->ev_done_p[q], hipEventDisableTiming));
         if (!h->ev_done_g[q]) HIP_TRY(hipEventCreateWithFlags(&h->ev_done_g[q], hipEventDisableTiming));
     }
-    if (!h->h_bad) { HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_bad), kDone * sizeof(int32_t), hipHostMallocDefault)); for (int q = 0; q < kDone; q++) h->h_bad[q] = 0; }
+    if (!h->h_bad) { int r2 = h->h_bad.alloc(kDone); if (r2) return r2; for (int q = 0; q < kDone; q++) h->h_bad[q] = 0; }
     // everything enqueued before streaming began (ticks, the memsets above) is ordered before the three new streams
     { int r2 = join_all(h); if (r2) return r2; }
     hipEvent_t e = get_sync_event(h);
@@ -1355,6 +1372,98 @@ static int ensure_streaming(pp_handle h)
     HIP_TRY(hipStreamSynchronize(h->stream));      // (once per handle) so that e can go back to the pool
     h->sync_events.push_back(e);
     h->streaming = true;
+    return PP_OK;
+}
+
+// What the next tick reads, staged on the upload stream by pp_update_async (host arrays: `in` and / or `obs_pool`) or by
+// pp_advance_async (`ego`: the SceneIn records are produced on the device)
+struct StageSource {
+    const SceneIn* in = nullptr; const ObPoint* obs_pool = nullptr; const ObMotion* mot_pool = nullptr; int n_obs_total = 0;
+    const EgoModel* ego = nullptr; EgoTrace* trace = nullptr;
+};
+
+// Stages an input set for the next tick; the callers have checked their arguments.  An update goes into the set after the current
+// one, or - a second update - onto the set already staged, and carries over from that set what it leaves alone.  An advance
+// (closed-loop rollout) always takes the set after the current one - its caller refuses while something is
+// staged - and puts k_advance_egos / k_advance_route in the place of the copy of the SceneIn records: the kernel reads what the
+// last tick's Planning kernel wrote (PlanOut, SceneState), so the upload stream waits for that tick's front-chain event, not for
+// its search; the next tick's front chain, the only writer of SceneState, waits for ev_up in turn.
+// Order on the upload stream: SceneIn records and obstacle pool -> k_move_traffic -> k_couple_fleet (the two write disjoint pool
+// entries: traffic a scene's own, the fleet the peer slots behind them, at the poses just staged) -> k_resolve_map ->
+// k_sanitise_scenes -> ev_up, which the tick that adopts the set waits for.
+static int stage_inputs(pp_handle h, const StageSource& src)
+{
+    const bool advance = src.ego != nullptr;
+    { int r = flush_group(h); if (r) return r; }          // the ticks before streaming began are launched as they stand
+    { int r = ensure_streaming(h); if (r) return r; }     // (a tick enqueued before streaming began has finished behind this: one host wait per handle)
+    { int r = pump_fetches(h); if (r) return r; }
+    { int r = prune_inflight(h); if (r) return r; }
+    hipStream_t su = h->stream_up;
+    if (advance && !h->rollout.d_flags) {
+        int r = h->rollout.d_flags.reserve((size_t)h->caps.max_scenes); if (r) return r;
+        HIP_TRY(hipMemsetAsync(h->rollout.d_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), su));
+        HIP_TRY(hipEventCreateWithFlags(&h->rollout.ev_adv, hipEventDisableTiming));
+    }
+    const bool restage = h->in_staged >= 0;
+    const int s = restage ? h->in_staged : (h->in_cur + 1) % kIn, n = h->n_scenes;
+    // what the call leaves alone is carried over from the set it replaces (the staged one if there is one)
+    const InputSet& P = h->in_sets[restage ? h->in_staged : h->in_cur];
+    InputSet& I = h->in_sets[s];
+    for (const TickRec& r : h->inflight) if (r.in_set == s) {      // the ticks that still read set s (a whole ring ago: long finished, as a rule)
+        HIP_TRY(hipStreamWaitEvent(su, r.ev_front, 0));
+        if (r.ev_tail) HIP_TRY(hipStreamWaitEvent(su, r.ev_tail, 0));
+    }
+    if (advance && h->last_rec.tick == h->tick_seq && h->last_rec.ev_front) HIP_TRY(hipStreamWaitEvent(su, h->last_rec.ev_front, 0));
+    if (src.in) HIP_TRY(hipMemcpyAsync(I.d_in, src.in, (size_t)n * sizeof(SceneIn), hipMemcpyDefault, su));
+    else if (!advance && &P != &I) HIP_TRY(hipMemcpyAsync(I.d_in, P.d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, su));
+    int n_obs = src.n_obs_total; bool have_motion = false;
+    if (src.obs_pool) {
+        if (n_obs) HIP_TRY(hipMemcpyAsync(I.d_obs, src.obs_pool, (size_t)n_obs * sizeof(ObPoint), hipMemcpyDefault, su));
+        if (n_obs && src.mot_pool) { HIP_TRY(hipMemcpyAsync(I.d_mot, src.mot_pool, (size_t)n_obs * sizeof(ObMotion), hipMemcpyDefault, su)); have_motion = true; }
+    } else {
+        n_obs = P.n_obs_total; have_motion = P.have_motion;
+        if (&P != &I && n_obs) {
+            HIP_TRY(hipMemcpyAsync(I.d_obs, P.d_obs, (size_t)n_obs * sizeof(ObPoint), hipMemcpyDeviceToDevice, su));
+            if (have_motion) HIP_TRY(hipMemcpyAsync(I.d_mot, P.d_mot, (size_t)n_obs * sizeof(ObMotion), hipMemcpyDeviceToDevice, su));
+        }
+    }
+    SceneIn* d_in = I.d_in; ObPoint* d_obs = I.d_obs; ObMotion* d_mot = have_motion ? I.d_mot.get() : nullptr;
+    if (advance) {
+        const dim3 agrid((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes));
+        if (h->route.on)                  // routed egos cross junctions; the scenes without a route advance as below
+            hipLaunchKernelGGL(dmpp::k_advance_route, agrid, dim3(dmpp::kBlock), 0, su,
+                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
+                               h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace);
+        else
+            hipLaunchKernelGGL(dmpp::k_advance_egos, agrid, dim3(dmpp::kBlock), 0, su,
+                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace);
+    }
+    if (h->traffic.on) move_traffic(h, su, d_obs, d_mot, advance ? src.ego->dt : 0.0);      // an advance moves the actors one step on, an update places them where they are
+    if (h->fleet.on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
+        if (!advance) n_obs = std::max(n_obs, h->fleet.end);      // (an advance inherits the count of the current set)
+        couple_fleet(h, su, d_in, d_obs, d_mot);
+    }
+    // The count of poisoned scenes is written by the two kernels below straight into pinned host memory: the slot of the tick
+    // that will adopt this set - no memset and no copy command on the upload stream.
+    // OWNER RULE of h_bad[slot of tick T + 1]: the HOST owns the slot while nothing is staged for T + 1 (no kernel that counts
+    // into it has been enqueued: it zeroes it here, at the first update or advance staged for T + 1, or in pp_plan_tick when
+    // T + 1 adopts nothing).  From the first staged update until pp_plan_tick adopts it the UPLOAD STREAM owns the slot:
+    // k_resolve_map / k_sanitise_scenes add to it in stream order, and a repeated update that brings new SceneIn records
+    // restarts the count with k_zero_word on that stream - behind the kernels of the earlier update, which a store from the
+    // host could overtake.  After the adoption nobody writes it; pp_wait_tick reads it behind the tick's downloads.
+    int32_t* bad_slot = &h->h_bad[(h->tick_seq + 1) % kDone];
+    if (!restage) *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;
+    else if (src.in) hipLaunchKernelGGL(dmpp::k_zero_word, dim3(1), dim3(1), 0, su, bad_slot);      // (a second, obstacles-only update of a staged set keeps the count of the first)
+    const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
+    if (h->resident_mode == 1 && (advance || src.in))      // egos on the resident map: lane views and junction slices from road / lane numbers (new records only)
+        hipLaunchKernelGGL(dmpp::k_resolve_map, grid, block, 0, su, n, d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
+                           h->map_junctions, h->d_map_junc, bad_slot);
+    hipLaunchKernelGGL(dmpp::k_sanitise_scenes, grid, block, 0, su, n, d_in, n_obs, h->n_lane_pts, h->n_ref_pts, bad_slot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(I.ev_up, su));
+    if (advance) { HIP_TRY(hipEventRecord(h->rollout.ev_adv, su)); h->rollout.adv_recorded = true; }
+    I.up_recorded = true; I.have_motion = have_motion; I.n_obs_total = n_obs;
+    h->in_staged = s; if (advance) h->rollout.staged_by_advance = true;
     return PP_OK;
 }
 
@@ -1368,130 +1477,32 @@ int pp_update_async(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint*
     if (!obs_pool && mot_pool) return fail(PP_ERR_ARG, "a motion pool without its obstacle pool");
     // with a fleet the slices are the pinned ones and the slice check runs against the end of the peer slots: a pool that stops
     // short of a scene's OWN entries would not be caught there, so it is refused here, before anything is enqueued
-    if (obs_pool && h->fleet_on && n_obs_total < h->fleet_own_end)
-        return fail(PP_ERR_ARG, "pp_update_async: with a fleet set the obstacle pool must cover every scene's own entries (up to entry " + std::to_string(h->fleet_own_end) + ")");
+    if (obs_pool && h->fleet.on && n_obs_total < h->fleet.own_end)
+        return fail(PP_ERR_ARG, "pp_update_async: with a fleet set the obstacle pool must cover every scene's own entries (up to entry " + std::to_string(h->fleet.own_end) + ")");
     // with traffic set every actor's pool entry is pinned: a pool that stops short of one is refused here, like the one above
-    if (obs_pool && h->traffic_on && n_obs_total < h->traffic_end)
-        return fail(PP_ERR_ARG, "pp_update_async: with traffic set the obstacle pool must cover every actor's entry (up to entry " + std::to_string(h->traffic_end) + ")");
-    if (in && h->in_staged >= 0 && h->staged_by_advance)
+    if (obs_pool && h->traffic.on && n_obs_total < h->traffic.end)
+        return fail(PP_ERR_ARG, "pp_update_async: with traffic set the obstacle pool must cover every actor's entry (up to entry " + std::to_string(h->traffic.end) + ")");
+    if (in && h->in_staged >= 0 && h->rollout.staged_by_advance)
         return fail(PP_ERR_STATE, "pp_update_async: the SceneIn records of the next tick were already produced by pp_advance_async");
     HIP_TRY(hipSetDevice(h->device));
-    { int r = flush_group(h); if (r) return r; }          // the ticks before streaming began are launched as they stand
-    { int r = ensure_streaming(h); if (r) return r; }
-    { int r = pump_fetches(h); if (r) return r; }
-    { int r = prune_inflight(h); if (r) return r; }
-    const InputSet& C = h->in_sets[h->in_cur];
-    const int s = h->in_staged >= 0 ? h->in_staged : (h->in_cur + 1) % kIn;
-    // what the update leaves alone is carried over from the set it replaces (the staged one if there is one)
-    const InputSet& P = h->in_staged >= 0 ? h->in_sets[h->in_staged] : C;
-    InputSet& I = h->in_sets[s];
-    hipStream_t su = h->stream_up;
-    for (const TickRec& r : h->inflight) if (r.in_set == s) {      // the ticks that still read set s (a whole ring ago: long finished, as a rule)
-        HIP_TRY(hipStreamWaitEvent(su, r.ev_front, 0));
-        if (r.ev_tail) HIP_TRY(hipStreamWaitEvent(su, r.ev_tail, 0));
-    }
-    const int n = n_scenes;
-    if (in) HIP_TRY(hipMemcpyAsync(I.d_in, in, (size_t)n * sizeof(SceneIn), hipMemcpyDefault, su));
-    else if (&P != &I) HIP_TRY(hipMemcpyAsync(I.d_in, P.d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, su));
-    int n_obs = n_obs_total; bool have_motion = false;
-    if (obs_pool) {
-        if (n_obs) HIP_TRY(hipMemcpyAsync(I.d_obs, obs_pool, (size_t)n_obs * sizeof(ObPoint), hipMemcpyDefault, su));
-        if (n_obs && mot_pool) { HIP_TRY(hipMemcpyAsync(I.d_mot, mot_pool, (size_t)n_obs * sizeof(ObMotion), hipMemcpyDefault, su)); have_motion = true; }
-    } else {
-        n_obs = P.n_obs_total; have_motion = P.have_motion;
-        if (&P != &I && n_obs) {
-            HIP_TRY(hipMemcpyAsync(I.d_obs, P.d_obs, (size_t)n_obs * sizeof(ObPoint), hipMemcpyDeviceToDevice, su));
-            if (have_motion) HIP_TRY(hipMemcpyAsync(I.d_mot, P.d_mot, (size_t)n_obs * sizeof(ObMotion), hipMemcpyDeviceToDevice, su));
-        }
-    }
-    // The count of poisoned scenes is written by the two kernels below straight into pinned host memory: the slot of the tick
-    // that will adopt this update - no memset and no copy command on the upload stream.
-    // OWNER RULE of h_bad[slot of tick T + 1]: the HOST owns the slot while nothing is staged for T + 1 (no kernel that counts
-    // into it has been enqueued: it zeroes it here, at the first update or advance staged for T + 1, or in pp_plan_tick when
-    // T + 1 adopts nothing).  From the first staged update until pp_plan_tick adopts it the UPLOAD STREAM owns the slot:
-    // k_resolve_map / k_sanitise_scenes add to it in stream order, and a repeated update that brings new SceneIn records
-    // restarts the count with k_zero_word on that stream - behind the kernels of the earlier update, which a store from the
-    // host could overtake.  After the adoption nobody writes it; pp_wait_tick reads it behind the tick's downloads.
-    if (h->traffic_on) move_traffic(h, su, I.d_obs, have_motion ? I.d_mot : nullptr, 0.0);      // the actors where they are: no step
-    if (h->fleet_on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
-        n_obs = std::max(n_obs, h->fleet_end);
-        couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);
-    }
-    int32_t* bad_slot = &h->h_bad[(h->tick_seq + 1) % kDone];
-    if (s != h->in_staged) *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;
-    else if (in) hipLaunchKernelGGL(dmpp::k_zero_word, dim3(1), dim3(1), 0, su, bad_slot);      // (a second, obstacles-only update of a staged set keeps the count of the first)
-    const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
-    if (h->resident_mode == 1 && in)      // egos on the resident map: lane views and junction slices from road / lane numbers
-        hipLaunchKernelGGL(dmpp::k_resolve_map, grid, block, 0, su, n, I.d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
-                           h->map_junctions, h->d_map_junc, bad_slot);
-    hipLaunchKernelGGL(dmpp::k_sanitise_scenes, grid, block, 0, su, n, I.d_in, n_obs, h->n_lane_pts, h->n_ref_pts, bad_slot);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(I.ev_up, su));
-    I.up_recorded = true; I.have_motion = have_motion; I.n_obs_total = n_obs;
-    h->in_staged = s;
-    return PP_OK;
+    StageSource src;
+    src.in = in; src.obs_pool = obs_pool; src.mot_pool = mot_pool; src.n_obs_total = n_obs_total;
+    return stage_inputs(h, src);
 }
 
-// Closed-loop rollout: the SceneIn records of the next tick are produced on the device.  The same staging as
-// pp_update_async(h, n, in, NULL, NULL, 0) - next input set, obstacles and motion carried over, lane views and slice check behind
-// it, the tick that adopts it waits for ev_up - with k_advance_egos in the place of the copy.  The kernel reads what the last
-// tick's Planning kernel wrote (PlanOut, SceneState): the upload stream waits for that tick's front-chain event, not for its
-// search; the next tick's front chain, the only writer of SceneState, waits for ev_up in turn.
 int pp_advance_async(pp_handle h, const EgoModel* m, EgoTrace* trace)
 {
     if (!h || !m) return fail(PP_ERR_ARG, "null argument");
     if (!(m->dt > 0) || !std::isfinite(m->dt) || !(m->max_acc >= 0) || !std::isfinite(m->max_acc) || !(m->max_dec >= 0) || !std::isfinite(m->max_dec) ||
         m->window < 1 || m->window > (1 << 20))
         return fail(PP_ERR_ARG, "pp_advance_async: the model needs a finite dt > 0, finite max_acc / max_dec >= 0 and a window of 1 .. 2^20 points");
-    if (h->n_scenes <= 0 || h->tick_seq <= h->set_tick)
+    if (h->n_scenes <= 0 || h->tick_seq <= h->rollout.set_tick)
         return fail(PP_ERR_STATE, "pp_advance_async: no tick has been enqueued for the resident scenes (the egos follow the plan of their last tick)");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_advance_async: an update is already staged for the next tick");
     HIP_TRY(hipSetDevice(h->device));
-    { int r = flush_group(h); if (r) return r; }
-    { int r = ensure_streaming(h); if (r) return r; }          // (a tick enqueued before streaming began has finished behind this: one host wait per handle)
-    { int r = pump_fetches(h); if (r) return r; }
-    { int r = prune_inflight(h); if (r) return r; }
-    hipStream_t su = h->stream_up;
-    if (!h->d_ego_flags) {
-        int r = dmalloc(&h->d_ego_flags, (size_t)h->caps.max_scenes); if (r) return r;
-        HIP_TRY(hipMemsetAsync(h->d_ego_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), su));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_adv, hipEventDisableTiming));
-    }
-    const InputSet& Cur = h->in_sets[h->in_cur];
-    const int s = (h->in_cur + 1) % kIn, n = h->n_scenes;
-    InputSet& I = h->in_sets[s];
-    for (const TickRec& r : h->inflight) if (r.in_set == s) {      // the ticks that still read set s (a whole ring ago)
-        HIP_TRY(hipStreamWaitEvent(su, r.ev_front, 0));
-        if (r.ev_tail) HIP_TRY(hipStreamWaitEvent(su, r.ev_tail, 0));
-    }
-    if (h->last_rec.tick == h->tick_seq && h->last_rec.ev_front) HIP_TRY(hipStreamWaitEvent(su, h->last_rec.ev_front, 0));
-    const int n_obs = Cur.n_obs_total; const bool have_motion = Cur.have_motion;
-    if (n_obs) {
-        HIP_TRY(hipMemcpyAsync(I.d_obs, Cur.d_obs, (size_t)n_obs * sizeof(ObPoint), hipMemcpyDeviceToDevice, su));
-        if (have_motion) HIP_TRY(hipMemcpyAsync(I.d_mot, Cur.d_mot, (size_t)n_obs * sizeof(ObMotion), hipMemcpyDeviceToDevice, su));
-    }
-    int32_t* bad_slot = &h->h_bad[(h->tick_seq + 1) % kDone];
-    *reinterpret_cast<volatile int32_t*>(bad_slot) = 0;          // nothing is staged for that tick: the host owns the slot (owner rule in pp_update_async)
-    if (h->route_on)                      // routed egos cross junctions; the scenes without a route advance as below
-        hipLaunchKernelGGL(dmpp::k_advance_route, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
-                           h->cfg, *m, h->route_rm, h->grid_follow, n, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
-                           h->d_route_legs, h->d_route_first, h->d_ego_flags, trace);
-    else
-        hipLaunchKernelGGL(dmpp::k_advance_egos, dim3((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), dim3(dmpp::kBlock), 0, su,
-                           h->cfg, *m, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, Cur.d_in, I.d_in, h->d_plan, h->d_state, h->d_lane, h->d_ego_flags, trace);
-    if (h->traffic_on) move_traffic(h, su, I.d_obs, have_motion ? I.d_mot : nullptr, m->dt);      // the actors one step on (first: the fleet's slots are disjoint)
-    if (h->fleet_on) couple_fleet(h, su, I.d_in, I.d_obs, have_motion ? I.d_mot : nullptr);      // the peers at the poses just advanced to
-    const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
-    if (h->resident_mode == 1)
-        hipLaunchKernelGGL(dmpp::k_resolve_map, grid, block, 0, su, n, I.d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
-                           h->map_junctions, h->d_map_junc, bad_slot);
-    hipLaunchKernelGGL(dmpp::k_sanitise_scenes, grid, block, 0, su, n, I.d_in, n_obs, h->n_lane_pts, h->n_ref_pts, bad_slot);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(I.ev_up, su));
-    HIP_TRY(hipEventRecord(h->ev_adv, su)); h->adv_recorded = true;
-    I.up_recorded = true; I.have_motion = have_motion; I.n_obs_total = n_obs;
-    h->in_staged = s; h->staged_by_advance = true;
-    return PP_OK;
+    StageSource src;
+    src.ego = m; src.trace = trace;
+    return stage_inputs(h, src);
 }
 
 int pp_rollout(pp_handle h, int n_ticks, const EgoModel* m, EgoTrace* trace, long long* last_tick_id)
@@ -1499,7 +1510,7 @@ int pp_rollout(pp_handle h, int n_ticks, const EgoModel* m, EgoTrace* trace, lon
     if (!h || !m) return fail(PP_ERR_ARG, "null argument");
     if (n_ticks < 0) return fail(PP_ERR_ARG, "pp_rollout: negative tick count");
     if (h->n_scenes <= 0) return fail(PP_ERR_STATE, "pp_rollout: no resident scenes");
-    if (h->tick_seq <= h->set_tick) { int r = pp_plan_tick(h); if (r) return r; }      // the plan the first advance follows
+    if (h->tick_seq <= h->rollout.set_tick) { int r = pp_plan_tick(h); if (r) return r; }      // the plan the first advance follows
     for (int t = 0; t < n_ticks; t++) {
         int r = pp_advance_async(h, m, trace ? trace + (size_t)t * (size_t)h->n_scenes : nullptr); if (r) return r;
         r = pp_plan_tick(h); if (r) return r;
@@ -1512,10 +1523,10 @@ int pp_get_ego_flags(pp_handle h, int32_t* flags, int n)
 {
     if (!h || !flags) return fail(PP_ERR_ARG, "null argument");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
-    if (!h->d_ego_flags) { std::memset(flags, 0, (size_t)n * sizeof(int32_t)); return PP_OK; }
+    if (!h->rollout.d_flags) { std::memset(flags, 0, (size_t)n * sizeof(int32_t)); return PP_OK; }
     HIP_TRY(hipSetDevice(h->device));
-    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
-    return fetch(h, flags, h->d_ego_flags, (size_t)n * sizeof(int32_t));
+    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    return fetch(h, flags, h->rollout.d_flags, (size_t)n * sizeof(int32_t));
 }
 
 // Rollout scorecard.  Scored ticks are streamed ticks: k_score_ego hangs on the tick's front-chain event.
@@ -1526,37 +1537,37 @@ int pp_score_begin(pp_handle h, double dt_score)
     HIP_TRY(hipSetDevice(h->device));
     { int r = flush_group(h); if (r) return r; }
     { int r = ensure_streaming(h); if (r) return r; }
-    if (!h->d_rscore) {
+    if (!h->score.d_score) {
         const size_t ns = (size_t)h->caps.max_scenes;
-        int r = dmalloc(&h->d_rscore, ns); if (r) return r;
-        for (int q = 0; q < kBuf; q++) if ((r = dmalloc(&h->d_rgrid[q], ns))) return r;
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_sc, hipEventDisableTiming));
+        int r = h->score.d_score.reserve(ns); if (r) return r;
+        for (int q = 0; q < kBuf; q++) if ((r = h->score.d_grid[q].reserve(ns))) return r;
+        HIP_TRY(hipEventCreateWithFlags(&h->score.ev, hipEventDisableTiming));
     }
     { int r = join_all(h); if (r) return r; }            // the ticks scored so far (a restart) and everything before
     { int r = reset_scores(h); if (r) return r; }
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->scoring = true; h->score_dt = dt_score;
+    h->score.on = true; h->score.dt = dt_score;
     return PP_OK;
 }
 
 int pp_score_end(pp_handle h)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    h->scoring = false;
+    h->score.on = false;
     return PP_OK;
 }
 
 int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
 {
     if (!h || !out) return fail(PP_ERR_ARG, "null argument");
-    if (!h->d_rscore) return fail(PP_ERR_STATE, "pp_get_rollout_score: pp_score_begin was never called on this handle");
+    if (!h->score.d_score) return fail(PP_ERR_STATE, "pp_get_rollout_score: pp_score_begin was never called on this handle");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
     HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }            // behind both halves: ev_sc (k_score_ego), ev_score / stream order (k_score_grid)
+    { int r = join_all(h); if (r) return r; }            // behind both halves: score.ev (k_score_ego), ev_score / stream order (k_score_grid)
     std::vector<dmpp::ScoreGridPart> parts((size_t)kBuf * (size_t)std::max(n, 1));
-    HIP_TRY(hipMemcpyAsync(out, h->d_rscore, (size_t)n * sizeof(RolloutScore), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipMemcpyAsync(out, h->score.d_score, (size_t)n * sizeof(RolloutScore), hipMemcpyDefault, h->stream));
     for (int q = 0; q < kBuf && n > 0; q++)
-        HIP_TRY(hipMemcpyAsync(parts.data() + (size_t)q * n, h->d_rgrid[q], (size_t)n * sizeof(dmpp::ScoreGridPart), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(parts.data() + (size_t)q * n, h->score.d_grid[q], (size_t)n * sizeof(dmpp::ScoreGridPart), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (int q = 0; q < kBuf; q++)                       // the grid half: one part per search set, added here
         for (int s = 0; s < n; s++) {
@@ -1567,6 +1578,22 @@ int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
     return PP_OK;
 }
 
+// Every resident scene's OWN obstacle entries (obs_off, obs_n): of the resident records, or - fleet on - the ones pinned then
+// (obs_n counts the peers now).  Behind join_all; waits on the host.  *rc: PP_OK, or the error (the vector is empty then).
+static std::vector<dmpp::FleetPin> own_slices(pp_handle h, int* rc)
+{
+    *rc = PP_OK;
+    if (h->fleet.on) return h->fleet.pin;
+    const size_t n = (size_t)h->n_scenes;
+    std::vector<SceneIn> rec(n);
+    hipError_t e = hipMemcpyAsync(rec.data(), h->d_in, n * sizeof(SceneIn), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { *rc = fail(PP_ERR_HIP, std::string("reading the resident SceneIn records: ") + hipGetErrorString(e)); return {}; }
+    std::vector<dmpp::FleetPin> pin(n);
+    for (size_t s = 0; s < n; s++) { pin[s].obs_off = rec[s].obs_off; pin[s].n_own = rec[s].obs_n; }
+    return pin;
+}
+
 // Fleet coupling.  Everything is checked on the host before anything changes.
 int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const FleetModel* fm)
 {
@@ -1575,15 +1602,15 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_fleet: an update is staged for the next tick (set the fleet before staging, or after the tick)");
     const int n = h->n_scenes;
     if (n_worlds == 0) {
-        if (!h->fleet_on) return PP_OK;
+        if (!h->fleet.on) return PP_OK;
         HIP_TRY(hipSetDevice(h->device));
         { int r = join_all(h); if (r) return r; }
-        hipLaunchKernelGGL(dmpp::k_fleet_restore, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, n, h->d_fleet_pin, h->d_in);
+        hipLaunchKernelGGL(dmpp::k_fleet_restore, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, n, h->fleet.d_pin, h->d_in);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(h->stream));
-        // (the slices are the pinned ones again; they were inside fleet_base when they were pinned)
-        const int back = std::max(h->fleet_base, h->fleet_own_end);
-        h->fleet_on = false; h->n_obs_total = back; h->in_sets[h->in_cur].n_obs_total = back;
+        // (the slices are the pinned ones again; they were inside fleet.base when they were pinned)
+        const int back = std::max(h->fleet.base, h->fleet.own_end);
+        h->fleet.on = false; h->n_obs_total = back; h->in_sets[h->in_cur].n_obs_total = back;
         return PP_OK;
     }
     if (!world_first || !fm) return fail(PP_ERR_ARG, "null argument");
@@ -1596,16 +1623,9 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     for (int w = 0; w < n_worlds; w++) if (world_first[w + 1] <= world_first[w]) return fail(PP_ERR_ARG, "pp_set_fleet: world_first must be strictly increasing");
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }
-    // the scenes' own slices: of the resident records, or - fleet already on - the ones pinned then (obs_n counts peers now)
-    std::vector<dmpp::FleetPin> pin((size_t)n);
-    if (h->fleet_on) pin = h->fleet_pin;
-    else {
-        std::vector<SceneIn> rec((size_t)n);
-        HIP_TRY(hipMemcpyAsync(rec.data(), h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        for (int s = 0; s < n; s++) { pin[(size_t)s].obs_off = rec[(size_t)s].obs_off; pin[(size_t)s].n_own = rec[(size_t)s].obs_n; }
-    }
-    const int base = h->fleet_on ? h->fleet_base : h->n_obs_total;
+    int rc;
+    std::vector<dmpp::FleetPin> pin = own_slices(h, &rc); if (rc) return rc;
+    const int base = h->fleet.on ? h->fleet.base : h->n_obs_total;
     std::vector<std::pair<long long, long long>> ext;       // non-empty extended slices [off, off + n_own + K)
     long long end_max = base, own_end = 0;
     for (int s = 0; s < n; s++) {
@@ -1624,17 +1644,12 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
         if (ext[k].first < ext[k - 1].second) return fail(PP_ERR_ARG, "pp_set_fleet: two scenes' obstacle slices overlap once the peer slots are added (leave max_peers free entries behind every slice)");
     std::vector<int32_t> world_of((size_t)n);
     for (int w = 0; w < n_worlds; w++) for (int s = world_first[w]; s < world_first[w + 1]; s++) world_of[(size_t)s] = w;
-    {
-        const size_t ns = (size_t)h->caps.max_scenes;
-        int r;
-        if (!h->d_world_first && (r = dmalloc(&h->d_world_first, ns + 1))) return r;
-        if (!h->d_world_of && (r = dmalloc(&h->d_world_of, ns))) return r;
-        if (!h->d_fleet_pin && (r = dmalloc(&h->d_fleet_pin, ns))) return r;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_world_first, world_first, ((size_t)n_worlds + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_world_of, world_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_fleet_pin, pin.data(), (size_t)n * sizeof(dmpp::FleetPin), hipMemcpyHostToDevice, h->stream));
-    h->fleet_pin.swap(pin); h->fleet_fm = *fm; h->fleet_base = base; h->fleet_end = (int)end_max; h->fleet_own_end = (int)std::min(own_end, (long long)h->caps.max_obs_total); h->fleet_on = true;
+    const size_t ns = (size_t)h->caps.max_scenes;
+    if ((rc = h->fleet.d_world_first.reserve(ns + 1)) || (rc = h->fleet.d_world_of.reserve(ns)) || (rc = h->fleet.d_pin.reserve(ns))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->fleet.d_world_first, world_first, ((size_t)n_worlds + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->fleet.d_world_of, world_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->fleet.d_pin, pin.data(), (size_t)n * sizeof(dmpp::FleetPin), hipMemcpyHostToDevice, h->stream));
+    h->fleet.pin.swap(pin); h->fleet.fm = *fm; h->fleet.base = base; h->fleet.end = (int)end_max; h->fleet.own_end = (int)std::min(own_end, (long long)h->caps.max_obs_total); h->fleet.on = true;
     h->n_obs_total = (int)end_max; h->in_sets[h->in_cur].n_obs_total = (int)end_max;
     couple_fleet(h, h->stream, h->d_in, h->d_obs, h->have_motion ? h->d_mot : nullptr);      // the resident set: the next tick sees the peers
     HIP_TRY(hipGetLastError());
@@ -1649,7 +1664,7 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (n_tracks < 0 || n_points < 0 || n_actors < 0) return fail(PP_ERR_ARG, "pp_set_traffic: negative count");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_traffic: an update is staged for the next tick (set the traffic before staging, or after the tick)");
-    if (n_actors == 0) { h->traffic_on = false; return PP_OK; }
+    if (n_actors == 0) { h->traffic.on = false; return PP_OK; }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_traffic: no resident scenes");
     if (!tracks || !points || !actors || n_tracks == 0) return fail(PP_ERR_ARG, "pp_set_traffic: actors need tracks and points");
@@ -1680,15 +1695,8 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     }
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }
-    // the scenes' own entries: of the resident records, or - fleet on - the ones pinned then (obs_n counts peers now)
-    std::vector<dmpp::FleetPin> own((size_t)n);
-    if (h->fleet_on) own = h->fleet_pin;
-    else {
-        std::vector<SceneIn> rec((size_t)n);
-        HIP_TRY(hipMemcpyAsync(rec.data(), h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        for (int s = 0; s < n; s++) { own[(size_t)s].obs_off = rec[(size_t)s].obs_off; own[(size_t)s].n_own = rec[(size_t)s].obs_n; }
-    }
+    int rc;
+    const std::vector<dmpp::FleetPin> own = own_slices(h, &rc); if (rc) return rc;
     std::vector<dmpp::TrafficPin> pin((size_t)n_actors); std::vector<double> s0((size_t)n_actors); std::vector<long long> taken((size_t)n_actors);
     long long end_max = 0;
     for (int a = 0; a < n_actors; a++) {
@@ -1710,47 +1718,36 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     for (size_t k = 1; k < taken.size(); k++)
         if (taken[k] == taken[k - 1]) return fail(PP_ERR_ARG, "pp_set_traffic: two actors on slot " + std::to_string((int)(taken[k] & 0xffffffff)) + " of scene " + std::to_string((int)(taken[k] >> 32)));
     // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the old arrays
-    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    // room first (a failed allocation leaves the old arrays, and the old traffic, as they were)
-    {
-        dmpp::TrafficPin* np_ = nullptr; double* ns_ = nullptr; dmpp::TrafficTrackDev* nt_ = nullptr; double* nc_ = nullptr; GlobalPoint2D* npt_ = nullptr;
-        const bool ga = (size_t)n_actors > h->traffic_actor_cap, gt = (size_t)n_tracks > h->traffic_track_cap, gc = cum.size() > h->traffic_cum_cap, gp = pts.size() > h->traffic_pts_cap;
-        int r = PP_OK;
-        if (ga) { r = dmalloc(&np_, (size_t)n_actors); if (!r) r = dmalloc(&ns_, (size_t)n_actors); }
-        if (!r && gt) r = dmalloc(&nt_, (size_t)n_tracks);
-        if (!r && gc) r = dmalloc(&nc_, cum.size());
-        if (!r && gp) r = dmalloc(&npt_, pts.size());
-        if (r) { for (void* b : { (void*)np_, (void*)ns_, (void*)nt_, (void*)nc_, (void*)npt_ }) if (b) (void)hipFree(b); return r; }
-        if (ga) { (void)hipFree(h->d_traffic_pin); (void)hipFree(h->d_traffic_s); h->d_traffic_pin = np_; h->d_traffic_s = ns_; h->traffic_actor_cap = (size_t)n_actors; }
-        if (gt) { (void)hipFree(h->d_traffic_tracks); h->d_traffic_tracks = nt_; h->traffic_track_cap = (size_t)n_tracks; }
-        if (gc) { (void)hipFree(h->d_traffic_cum); h->d_traffic_cum = nc_; h->traffic_cum_cap = cum.size(); }
-        if (gp) { (void)hipFree(h->d_traffic_pts); h->d_traffic_pts = npt_; h->traffic_pts_cap = pts.size(); }
-    }
-    h->traffic_on = false;                                // (until everything below has landed: a device error leaves traffic off, never half a set)
-    HIP_TRY(hipMemcpyAsync(h->d_traffic_pin, pin.data(), (size_t)n_actors * sizeof(dmpp::TrafficPin), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_traffic_s, s0.data(), (size_t)n_actors * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_traffic_tracks, tdev.data(), (size_t)n_tracks * sizeof(dmpp::TrafficTrackDev), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_traffic_cum, cum.data(), cum.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_traffic_pts, pts.data(), pts.size() * sizeof(GlobalPoint2D), hipMemcpyHostToDevice, h->stream));
-    h->traffic_actors = n_actors; h->traffic_end = (int)end_max;
+    // room first.  An allocation that fails leaves its own array as it was, but may follow one that replaced another: the old
+    // traffic then goes off rather than run on half a set
+    if ((rc = h->traffic.d_pin.reserve((size_t)n_actors)) || (rc = h->traffic.d_s.reserve((size_t)n_actors)) || (rc = h->traffic.d_tracks.reserve((size_t)n_tracks)) ||
+        (rc = h->traffic.d_cum.reserve(cum.size())) || (rc = h->traffic.d_pts.reserve(pts.size()))) { h->traffic.on = false; return rc; }
+    h->traffic.on = false;                                // (until everything below has landed: a device error leaves traffic off, never half a set)
+    HIP_TRY(hipMemcpyAsync(h->traffic.d_pin, pin.data(), (size_t)n_actors * sizeof(dmpp::TrafficPin), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->traffic.d_s, s0.data(), (size_t)n_actors * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->traffic.d_tracks, tdev.data(), (size_t)n_tracks * sizeof(dmpp::TrafficTrackDev), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->traffic.d_cum, cum.data(), cum.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->traffic.d_pts, pts.data(), pts.size() * sizeof(GlobalPoint2D), hipMemcpyHostToDevice, h->stream));
+    h->traffic.actors = n_actors; h->traffic.end = (int)end_max;
     move_traffic(h, h->stream, h->d_obs, h->have_motion ? h->d_mot : nullptr, 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
-    h->traffic_on = true;
+    h->traffic.on = true;
     return PP_OK;
 }
 
 int pp_get_traffic_state(pp_handle h, double* s, int n)
 {
     if (!h || (!s && n > 0)) return fail(PP_ERR_ARG, "null argument");
-    if (!h->traffic_on) return fail(PP_ERR_STATE, "pp_get_traffic_state: no traffic is set");
-    if (n < 0 || n > h->traffic_actors) return fail(PP_ERR_ARG, "n exceeds the actors");
+    if (!h->traffic.on) return fail(PP_ERR_STATE, "pp_get_traffic_state: no traffic is set");
+    if (n < 0 || n > h->traffic.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
     HIP_TRY(hipSetDevice(h->device));
-    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
     if (h->in_staged >= 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));      // (a staged update rewrites the same values)
-    return fetch(h, s, h->d_traffic_s, (size_t)n * sizeof(double));
+    return fetch(h, s, h->traffic.d_s, (size_t)n * sizeof(double));
 }
 
 // Route following.  Everything is checked on the host before anything changes; the resident records are not touched.
@@ -1766,7 +1763,7 @@ int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int3
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (n_legs_total < 0) return fail(PP_ERR_ARG, "pp_set_route: negative leg count");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_route: an update is staged for the next tick (set the route before staging, or after the tick)");
-    if (n_legs_total == 0) { h->route_on = false; return PP_OK; }
+    if (n_legs_total == 0) { h->route.on = false; return PP_OK; }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_route: no resident scenes");
     if (h->resident_mode != 1 || !h->have_map) return fail(PP_ERR_STATE, "pp_set_route: routes need egos on a resident map (pp_set_map, then pp_set_egos)");
@@ -1778,20 +1775,15 @@ int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int3
         if (legs[k].road_num < 1 || legs[k].road_num > h->map_roads) return fail(PP_ERR_ARG, "pp_set_route: leg " + std::to_string(k) + " names a road outside the map");
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the old legs
-    if (h->adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_adv, 0));
+    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (!h->d_route_first) { int r = dmalloc(&h->d_route_first, (size_t)h->caps.max_scenes + 1); if (r) return r; }
-    if ((size_t)n_legs_total > h->route_legs_cap) {
-        RouteLeg* fresh = nullptr;
-        { int r = dmalloc(&fresh, (size_t)n_legs_total); if (r) return r; }
-        if (h->d_route_legs) (void)hipFree(h->d_route_legs);
-        h->d_route_legs = fresh; h->route_legs_cap = (size_t)n_legs_total;
-    }
-    h->route_on = false;                                  // (until the copies below have landed: a failed copy leaves routing off, not half a route)
-    HIP_TRY(hipMemcpyAsync(h->d_route_legs, legs, (size_t)n_legs_total * sizeof(RouteLeg), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_route_first, route_first, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    { int r = h->route.d_first.reserve((size_t)h->caps.max_scenes + 1); if (r) return r; }      // room first: a failed allocation leaves the old route
+    { int r = h->route.d_legs.reserve((size_t)n_legs_total); if (r) return r; }
+    h->route.on = false;                                  // (until the copies below have landed: a failed copy leaves routing off, not half a route)
+    HIP_TRY(hipMemcpyAsync(h->route.d_legs, legs, (size_t)n_legs_total * sizeof(RouteLeg), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->route.d_first, route_first, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the caller's arrays may go; the upload stream reads the copies from its next launch on)
-    h->route_rm = *rm; h->route_rm._pad = 0; h->route_on = true;
+    h->route.rm = *rm; h->route.rm._pad = 0; h->route.on = true;
     return PP_OK;
 }
 
@@ -1819,7 +1811,7 @@ int pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap)
 {
     if (!h || (!out && cap > 0)) return fail(PP_ERR_ARG, "null argument");
     if (scene < 0 || scene >= h->n_scenes || cap < 0) return fail(PP_ERR_ARG, "pp_get_obstacles: scene or cap out of range");
-    const bool staged = h->in_staged >= 0 && h->staged_by_advance;      // (the set pp_get_scene_in reads)
+    const bool staged = h->in_staged >= 0 && h->rollout.staged_by_advance;      // (the set pp_get_scene_in reads)
     const InputSet& I = h->in_sets[staged ? h->in_staged : h->in_cur];
     HIP_TRY(hipSetDevice(h->device));
     if (staged) HIP_TRY(hipStreamWaitEvent(h->stream, I.ev_up, 0));
@@ -1892,7 +1884,7 @@ int pp_wait_tick(pp_handle h, long long tick_id, int* n_poisoned)
     { int r = pump_fetches(h, tick_id); if (r) return r; }
     if (h->done_p_rec[slot]) HIP_TRY(hipEventSynchronize(h->ev_done_p[slot]));
     if (h->done_g_rec[slot]) HIP_TRY(hipEventSynchronize(h->ev_done_g[slot]));
-    const int bad = (int)reinterpret_cast<volatile int32_t*>(h->h_bad)[slot];
+    const int bad = (int)reinterpret_cast<volatile int32_t*>(h->h_bad.get())[slot];
     if (n_poisoned) *n_poisoned = bad;
     if (bad) return fail(PP_ERR_ARG, "tick " + std::to_string(tick_id) + ": " + std::to_string(bad) + " scene(s) of its update had a slice outside its pool (or a road / lane outside the map) and ran with empty inputs");
     return PP_OK;
@@ -1906,8 +1898,8 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
     HIP_TRY(hipSetDevice(h->device));
     const int max_obs = std::min(PP_IO_MAX_OBS, h->caps.max_obs_total), max_ref = std::min(DMPP_MAX_REFPATH, h->caps.max_ref_pts_total);
     { int r = flush_group(h); if (r) return r; }          // (k_io_in rewrites the inputs an open group's searches read)
-    if (h->sc_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_sc, 0));      // ... and the scorecard of the last tick
-    h->in_staged = -1; h->staged_by_advance = false;
+    if (h->score.recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->score.ev, 0));      // ... and the scorecard of the last tick
+    h->in_staged = -1; h->rollout.staged_by_advance = false;
     hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->d_in, h->d_state, h->d_obs, h->d_ref);
     HIP_TRY(hipGetLastError());
     h->n_obs_total = std::min(std::max((int)io->n_obs, 0), max_obs); h->have_motion = false;
@@ -1949,94 +1941,11 @@ int pp_host_unregister(void* p) { if (!p) return PP_OK; HIP_TRY(hipHostUnregiste
 
 // ---------------------------------------------------------------------------------------
 // stand-alone operators
-}  // extern "C"
-
-namespace dmpp {
-
-constexpr int kSoMaxPts = 2048;
-
-__global__ void __launch_bounds__(DMPP_WAVE)
-k_search_obstacle_batch(PlannerConfig c, int nq, const GlobalPoint2D* __restrict__ paths, const int32_t* __restrict__ path_off,
-                        const ObPoint* __restrict__ obs, const int32_t* __restrict__ obs_off, const double* __restrict__ lo,
-                        const double* __restrict__ hi, Path_Obs* __restrict__ out)
-{
-    __shared__ double s[kSoMaxPts];
-    const int q = blockIdx.x;
-    if (q >= nq) return;
-    const int lane = threadIdx.x;
-    const int p0 = path_off[q], n = path_off[q + 1] - p0, o0 = obs_off[q], m = obs_off[q + 1] - o0;
-    SoResult r = wave_search_obstacle(c, paths + p0, n, s, obs + o0, m, lo[q], hi[q], lane);
-    if (lane == 0) store_path_obs(&out[q], r, obs + o0, true);
-}
-
-__global__ void k_geom_batch(PlannerConfig c, int op, int n, const GlobalPoint2D* a, const GlobalPoint2D* b, const GlobalPoint2D* cc, double* out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (op == 0) out[i] = GetLatDis(c, a[i], b[i], cc[i]);
-    else if (op == 1) out[i] = GetRoadAngle(c, a[i], b[i]);
-    else if (op == 2) out[i] = GetAngleErr(a[i].x, a[i].y);
-    else if (op == 3) out[i] = CalcDistance(a[i], b[i]);
-    else if (op == 4) out[i] = c.wgs_lat0 + a[i].y * c.wgs_deg_per_m_lat;      // GlobalToWGS84 .lat
-    else out[i] = c.wgs_lng0 + a[i].x * c.wgs_deg_per_m_lng;                   // GlobalToWGS84 .lng
-}
-
-// One scalar stage of the planning tick on explicit arguments (the CPlanning methods of the same name).
-//   op 0 UpdatePlanJudge : in = {last_behavior, behavior, pos, path_lat_dis, path_dir_err, remain_dis} -> out = {afresh, cause}
-//   op 1 SpeedPlanning   : in = {pos, ob_flag, mindist_lon, faraim_dis, velocity_expect, brake_speed, acc_flag, des_acc} -> out = {brake_speed, acc_flag, des_acc}
-//   op 2 CalculateRadius : in = {path_near_id, path_front_near_id}, pts = last_Bpoints[200] -> out = {radius}
-__global__ void k_scalar_stage(PlannerConfig c, int op, const double* in, const GlobalPoint2D* pts, double* out)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (op == 0) {
-        int cause = 0;
-        const int afresh = d_UpdatePlanJudge(c, (int)in[0], (int)in[1], (int)in[2], in[3], in[4], in[5], cause);
-        out[0] = afresh; out[1] = cause;
-    } else if (op == 1) {
-        double bs = in[5], da = in[7]; int af = (int)in[6];
-        d_SpeedPlanning((int)in[0], (int)in[1], in[2], (float)in[3], in[4], bs, af, da);
-        out[0] = bs; out[1] = af; out[2] = da;
-    } else {
-        out[0] = d_CalculateRadius(pts, (int)in[0], (int)in[1]);
-    }
-}
-
-__global__ void k_bezier(PlannerConfig c, GlobalPoint3D s, GlobalPoint3D e, GlobalPoint2D* out, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Bezier bz = bezier_setup(c, s, e);
-    out[i] = bezier_point(bz, i, n);
-}
-
-__global__ void __launch_bounds__(DMPP_WAVE)
-k_cumlen(const GlobalPoint2D* in, int n, double* cum) { wave_cumlen(in, n, cum, threadIdx.x); }
-
-__global__ void k_mean_points(PlannerConfig c, const GlobalPoint2D* in, const double* cum, int n_in, GlobalPoint2D* out, int n_out)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n_out) out[k] = mean_point(c, in, cum, n_in, k, n_out);
-}
-
-__global__ void k_create_new_path(PlannerConfig c, const GlobalPoint2D* path, int n, double offset, GlobalPoint2D* out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = offset_point(c, path, n, i, offset);
-}
-
-}  // namespace dmpp
-
-extern "C" {
-
 static int need_scratch(pp_handle h, size_t bytes)
 {
-    if (bytes <= h->scratch_bytes) return PP_OK;
+    if (bytes <= h->d_scratch.capacity()) return PP_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->d_scratch) HIP_TRY(hipFree(h->d_scratch));
-    h->d_scratch = nullptr; h->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_scratch, bytes));
-    h->scratch_bytes = bytes;
-    return PP_OK;
+    return h->d_scratch.reserve(bytes);
 }
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -2111,7 +2020,7 @@ int pp_bezier(pp_handle h, GlobalPoint3D s, GlobalPoint3D e, GlobalPoint2D* out,
     if (!h || !out || n <= 0) return fail(PP_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
     int r = need_scratch(h, (size_t)n * sizeof(GlobalPoint2D)); if (r) return r;
-    hipLaunchKernelGGL(dmpp::k_bezier, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->cfg, s, e, (GlobalPoint2D*)h->d_scratch, n);
+    hipLaunchKernelGGL(dmpp::k_bezier, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->cfg, s, e, (GlobalPoint2D*)h->d_scratch.get(), n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, h->d_scratch, (size_t)n * sizeof(GlobalPoint2D), hipMemcpyDefault, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2179,7 +2088,6 @@ void* pp_device_ptr(pp_handle h, int which, size_t* bytes)
 {
     if (!h) return nullptr;
     if (flush_group(h)) return nullptr;                   // the buffers of the last tick: its group's launches are enqueued
-
     const size_t ns = (size_t)h->caps.max_scenes;
     void* p = nullptr; size_t b = 0;
     switch (which) {
@@ -2216,7 +2124,6 @@ int pp_tick_group_const(int which)
     }
 }
 void* pp_stream(pp_handle h) { return h && !flush_group(h) ? (void*)h->stream : nullptr; }
-
 
 size_t pp_sizeof(int which)
 {

@@ -275,3 +275,53 @@ def test_streamed_published_records_only(dm, oracle):
         if grid is not None:
             assert not compare(grid, gout_o, "grid"), t
     pl.close()
+
+
+def _same_bits(a, b, path=""):
+    """Mismatch strings of two record arrays, every field compared bit for bit (padding excepted)."""
+    if a.dtype.names:
+        return [m for f in a.dtype.names if not f.startswith("_pad") for m in _same_bits(a[f], b[f], path + "." + f)]
+    same = np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+    return [] if same else [path + ": bits differ"]
+
+
+def test_staged_set_hand_over_keeps_or_restarts_the_poisoned_count(dm):
+    """A second update onto an already staged set, egos on a resident map (k_resolve_map counts too).  Obstacles only: the set
+    keeps the SceneIn records of the first update and its count of poisoned scenes.  New SceneIn records: the count starts
+    again on the upload stream (k_zero_word), and the tick equals, bit for bit, the tick of a handle that got the final
+    inputs in one update."""
+    import map_scenes as ms
+    cfg = dm.default_config(128)
+    m = ms.build_map(dm, n_roads=5)
+    n, n_obs = 4, 8
+    sc = ms.make_egos(dm, cfg, m, n, n_obs)
+    bad_in = sc["scene_in"].copy()
+    bad_in["loc"]["lane_num"][2] = 99                       # a lane outside the map
+    ob_last = sc["obs_pool"].copy()
+    ob_last["x"] += 0.25                                    # the final obstacles
+
+    def run(*updates):
+        pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=n * n_obs, max_lane_pts_total=len(m["points"]),
+                        max_ref_pts_total=max(len(m["jpoints"]), 1))
+        pl.set_map(m)
+        pl.set_egos(sc, with_motion=False)
+        pl.set_state(sc["state"])
+        keep = [tuple(None if a is None else dm.pinned_copy(a) for a in u) for u in updates]
+        for a, b in keep:
+            pl.update_async(a, b)
+        pl.tick()
+        plan, gout = dm.pinned_empty(n, dm.PlanOut), dm.pinned_empty(n, dm.GridOut)
+        bad = pl.wait_tick(pl.fetch_async(plan, gout), allow_poisoned=True)
+        pl.sync()
+        out = (bad, np.array(plan), pl.get_state(), np.array(gout))
+        pl.close()
+        return out
+
+    kept = run((bad_in, sc["obs_pool"]), (None, ob_last))
+    restarted = run((bad_in, sc["obs_pool"]), (sc["scene_in"], ob_last))
+    once = run((sc["scene_in"], ob_last))
+    assert kept[0] == 1, "an obstacles-only second update keeps the count of the first"
+    assert restarted[0] == 0, "new SceneIn records on a staged set restart the count"
+    assert once[0] == 0
+    bad = [m_ for got, want, tag in zip(restarted[1:], once[1:], ("plan", "state", "grid")) for m_ in _same_bits(got, want, tag)]
+    assert not bad, "\n".join(bad[:20])
