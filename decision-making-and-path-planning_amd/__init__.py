@@ -104,6 +104,8 @@ GridFollow = _dt([("goal_point", i4), ("margin_cells", i4)])
 # lane traffic: scripted vehicles that drive a polyline and sit in their scene's own obstacle entries
 TrafficTrack = _dt([("point_off", i4), ("n_points", i4), ("closed", i4), ("_pad", i4)])
 TrafficActor = _dt([("s0", f8), ("speed", f8), ("scene", i4), ("slot", i4), ("track", i4), ("type", i4), ("radius", f4), ("_pad", i4)])
+# car-following traffic: actors with speed > 0 keep a gap to the ego and to each other
+TrafficFollow = _dt([("look", f8), ("lateral", f8), ("gap", f8), ("headway", f8), ("max_acc", f8), ("comfort_dec", f8), ("max_dec", f8), ("min_net", f8)])
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -224,6 +226,12 @@ def load_library(path=None):
     if traffic:
         lib.pp_set_traffic.argtypes = [vp, ci, vp, vp, ci, ci, vp]
         lib.pp_get_traffic_state.argtypes = [vp, vp, ci]
+    react = hasattr(lib, "pp_set_traffic_follow") or path == LIB_PATH          # (as above: an older build may lack it)
+    if react:
+        lib.pp_default_traffic_follow.argtypes = [vp]
+        lib.pp_default_traffic_follow.restype = None
+        lib.pp_set_traffic_follow.argtypes = [vp, vp]
+        lib.pp_get_traffic_speed.argtypes = [vp, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -237,7 +245,8 @@ def load_library(path=None):
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
             (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
-            (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()):
+            (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()) + \
+            (((28, TrafficFollow),) if react else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -291,6 +300,14 @@ def default_grid_follow():
     gf = np.zeros(1, GridFollow)
     load_library().pp_default_grid_follow(_ptr(gf))
     return gf
+
+
+def default_traffic_follow():
+    """TrafficFollow record of the car-following traffic (pp_default_traffic_follow): look 60 m, lateral 1.5 m, gap 2 m, headway 1.5 s,
+    max_acc 1, comfort_dec 2, max_dec 6 m/s^2, min_net 0.1 m."""
+    tf = np.zeros(1, TrafficFollow)
+    load_library().pp_default_traffic_follow(_ptr(tf))
+    return tf
 
 
 def gen_scenes(cfg, first_scene, n_scenes, n_obs, junction_every=8):
@@ -523,6 +540,22 @@ class Planner:
         ac = np.ascontiguousarray(actors, TrafficActor)
         _check(self.lib.pp_set_traffic(self.h, len(tr), _ptr(tr), _ptr(pt), len(pt), len(ac), _ptr(ac)))
         self.n_traffic = len(ac)
+
+    def set_traffic_follow(self, tf=None):
+        """pp_set_traffic_follow: from the next advance on every actor with speed > 0 follows the vehicle ahead of it on its track -
+        an actor of its scene or the scene's ego - by the intelligent-driver model; speed is its desired speed.
+        The model belongs to the handle and takes effect while traffic is set.  tf None: following off."""
+        if tf is None:
+            _check(self.lib.pp_set_traffic_follow(self.h, None))
+            return
+        m = np.array(tf, TrafficFollow).reshape(1).copy()
+        _check(self.lib.pp_set_traffic_follow(self.h, _ptr(m)))
+
+    def traffic_speed(self):
+        """pp_get_traffic_speed: the speed (m/s) of every actor, as traffic_state gives the arc lengths (host wait)."""
+        out = np.zeros(getattr(self, "n_traffic", 0), np.float64)
+        _check(self.lib.pp_get_traffic_speed(self.h, _ptr(out), len(out)))
+        return out
 
     def traffic_state(self):
         """pp_get_traffic_state: the arc length of every actor in the input set get_scene_in reads (host wait)."""

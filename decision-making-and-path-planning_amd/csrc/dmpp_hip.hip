@@ -165,6 +165,16 @@ struct RouteState { bool on = false; RouteModel rm = { 0, 0 }; DevBuf<RouteLeg> 
 struct TrafficState {
     bool on = false; int actors = 0, end = 0;
     DevBuf<dmpp::TrafficPin> d_pin; DevBuf<dmpp::TrafficTrackDev> d_tracks; DevBuf<double> d_cum; DevBuf<GlobalPoint2D> d_pts; DevBuf<double> d_s;
+    std::vector<int32_t> scene_of, track_of;      // host: what a later pp_set_traffic_follow groups the actors by
+    int cur = 0;                                  // which arc-length array is current: 0 d_s, 1 FollowState::d_s_alt (only while following)
+};
+// car-following traffic (pp_set_traffic_follow): the model, and - allocated only while traffic AND following are on -
+// the second arc-length array, the two speed arrays (the step is a Jacobi step: an advance reads pair traffic.cur and writes the
+// other, then flips cur; the advances are serial on the upload stream) and the group tables: every actor's scene and group, the
+// first member of every group and the actor indices sorted by (scene, track, index)
+struct FollowState {
+    bool on = false; TrafficFollow tf = {};
+    DevBuf<double> d_s_alt, d_v[2]; DevBuf<dmpp::TrafficRef> d_ref; DevBuf<int32_t> d_first, d_members;
 };
 
 }  // namespace
@@ -256,6 +266,7 @@ struct pp_planner {
     FleetState fleet;
     RouteState route;
     TrafficState traffic;
+    FollowState follow;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
@@ -323,6 +334,9 @@ void couple_fleet(pp_planner* h, hipStream_t st, SceneIn* d_in, ObPoint* d_obs, 
                        h->fleet.d_pin, d_in, d_obs, d_mot);
 }
 
+// the arc-length array `which` of the traffic (1 exists only while following is on)
+double* traffic_s(pp_planner* h, int which) { return which ? h->follow.d_s_alt.get() : h->traffic.d_s.get(); }
+
 // Lane traffic of one input set on the stream that stages it: behind the copies of its obstacle pool, in front of
 // k_couple_fleet (the two write disjoint entries: traffic a scene's own, the fleet the peer slots behind them) and of
 // k_resolve_map / k_sanitise_scenes.  step: 0 places the actors where they are, EgoModel.dt moves them first.
@@ -330,7 +344,55 @@ void move_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot
 {
     const int n = h->traffic.actors;
     hipLaunchKernelGGL(dmpp::k_move_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
-                       n, step, h->traffic.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s, d_obs, d_mot);
+                       n, step, h->traffic.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, h->traffic.cur), d_obs, d_mot);
+}
+
+// Car-following traffic of the input set an advance stages, in the place of move_traffic: behind k_advance_*, whose
+// SceneIn records and flag words it reads.  Reads the current (s, v) pair, writes the other one and - once the launch is accepted -
+// makes that the current one.
+int follow_traffic(pp_planner* h, hipStream_t st, const SceneIn* d_in, ObPoint* d_obs, ObMotion* d_mot, double dt)
+{
+    const int n = h->traffic.actors, cur = h->traffic.cur;
+    hipLaunchKernelGGL(dmpp::k_follow_traffic, dim3((unsigned)((n + dmpp::kFollowActors - 1) / dmpp::kFollowActors)), dim3(dmpp::kBlock), 0, st,
+                       n, dt, h->follow.tf, 0.5 * h->cfg.Vehicle_Width, h->traffic.d_pin, h->follow.d_ref, h->follow.d_first, h->follow.d_members,
+                       h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, cur), h->follow.d_v[cur], traffic_s(h, cur ^ 1), h->follow.d_v[cur ^ 1],
+                       d_in, h->rollout.d_flags, d_obs, d_mot);
+    HIP_TRY(hipGetLastError());
+    h->traffic.cur = cur ^ 1;
+    return PP_OK;
+}
+
+// The buffers of following for the actors pp_set_traffic has just uploaded, and v = speed.  The caller has joined the chains and
+// the handle's stream is idle; traffic.cur stays.  On failure the caller switches traffic off.
+int build_follow(pp_planner* h)
+{
+    const size_t n = (size_t)h->traffic.actors;
+    std::vector<int32_t> members(n);
+    for (size_t a = 0; a < n; a++) members[a] = (int32_t)a;
+    const std::vector<int32_t>& sc = h->traffic.scene_of; const std::vector<int32_t>& tr = h->traffic.track_of;
+    std::sort(members.begin(), members.end(), [&](int32_t p, int32_t q) {
+        if (sc[(size_t)p] != sc[(size_t)q]) return sc[(size_t)p] < sc[(size_t)q];
+        if (tr[(size_t)p] != tr[(size_t)q]) return tr[(size_t)p] < tr[(size_t)q];
+        return p < q;
+    });
+    std::vector<dmpp::TrafficRef> ref(n); std::vector<int32_t> first;
+    for (size_t m = 0; m < n; m++) {
+        const size_t a = (size_t)members[m];
+        if (m == 0 || sc[a] != sc[(size_t)members[m - 1]] || tr[a] != tr[(size_t)members[m - 1]]) first.push_back((int32_t)m);
+        ref[a] = { sc[a], (int32_t)first.size() - 1 };
+    }
+    first.push_back((int32_t)n);
+    int rc;
+    if ((rc = h->follow.d_s_alt.reserve(n)) || (rc = h->follow.d_v[0].reserve(n)) || (rc = h->follow.d_v[1].reserve(n)) || (rc = h->follow.d_ref.reserve(n)) ||
+        (rc = h->follow.d_first.reserve(first.size())) || (rc = h->follow.d_members.reserve(n))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->follow.d_ref, ref.data(), n * sizeof(dmpp::TrafficRef), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->follow.d_first, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->follow.d_members, members.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    // v = speed: the first 8 bytes of every 24-byte pin
+    static_assert(offsetof(dmpp::TrafficPin, speed) == 0, "the speeds are copied out of the pins at their stride");
+    HIP_TRY(hipMemcpy2DAsync(h->follow.d_v[h->traffic.cur], sizeof(double), h->traffic.d_pin, sizeof(dmpp::TrafficPin), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
+    return PP_OK;
 }
 
 // Issues the copies of the pending downloads whose kernels have finished.  force_tick: that tick's copies are issued whatever
@@ -1438,7 +1500,10 @@ static int stage_inputs(pp_handle h, const StageSource& src)
             hipLaunchKernelGGL(dmpp::k_advance_egos, agrid, dim3(dmpp::kBlock), 0, su,
                                h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace);
     }
-    if (h->traffic.on) move_traffic(h, su, d_obs, d_mot, advance ? src.ego->dt : 0.0);      // an advance moves the actors one step on, an update places them where they are
+    if (h->traffic.on) {                  // an advance moves the actors one step on - by the car-following law while that is on (§4i) -, an update places them where they are
+        if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }
+        else move_traffic(h, su, d_obs, d_mot, advance ? src.ego->dt : 0.0);
+    }
     if (h->fleet.on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
         if (!advance) n_obs = std::max(n_obs, h->fleet.end);      // (an advance inherits the count of the current set)
         couple_fleet(h, su, d_in, d_obs, d_mot);
@@ -1698,6 +1763,7 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     int rc;
     const std::vector<dmpp::FleetPin> own = own_slices(h, &rc); if (rc) return rc;
     std::vector<dmpp::TrafficPin> pin((size_t)n_actors); std::vector<double> s0((size_t)n_actors); std::vector<long long> taken((size_t)n_actors);
+    std::vector<int32_t> scene_of((size_t)n_actors), track_of((size_t)n_actors);
     long long end_max = 0;
     for (int a = 0; a < n_actors; a++) {
         const TrafficActor& A = actors[a];
@@ -1711,6 +1777,7 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
         if (A.slot < 0 || A.slot >= O.n_own || O.obs_off < 0 || pool >= (long long)h->caps.max_obs_total)
             return fail(PP_ERR_ARG, who + ": slot " + std::to_string(A.slot) + " is not one of the " + std::to_string(std::max(O.n_own, 0)) + " own obstacle entries of scene " + std::to_string(A.scene));
         pin[(size_t)a] = { A.speed, (int32_t)pool, A.track, A.type, A.radius };
+        scene_of[(size_t)a] = A.scene; track_of[(size_t)a] = A.track;
         s0[(size_t)a] = A.s0; taken[(size_t)a] = ((long long)A.scene << 32) | (long long)A.slot;
         end_max = std::max(end_max, pool + 1);
     }
@@ -1730,10 +1797,12 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     HIP_TRY(hipMemcpyAsync(h->traffic.d_tracks, tdev.data(), (size_t)n_tracks * sizeof(dmpp::TrafficTrackDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_cum, cum.data(), cum.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_pts, pts.data(), pts.size() * sizeof(GlobalPoint2D), hipMemcpyHostToDevice, h->stream));
-    h->traffic.actors = n_actors; h->traffic.end = (int)end_max;
+    h->traffic.actors = n_actors; h->traffic.end = (int)end_max; h->traffic.cur = 0;
+    h->traffic.scene_of.swap(scene_of); h->traffic.track_of.swap(track_of);
     move_traffic(h, h->stream, h->d_obs, h->have_motion ? h->d_mot : nullptr, 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
+    if (h->follow.on) { int r = build_follow(h); if (r) return r; }      // following is on: its tables for these actors, v = speed (§4i)
     h->traffic.on = true;
     return PP_OK;
 }
@@ -1747,7 +1816,59 @@ int pp_get_traffic_state(pp_handle h, double* s, int n)
     HIP_TRY(hipSetDevice(h->device));
     if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
     if (h->in_staged >= 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));      // (a staged update rewrites the same values)
-    return fetch(h, s, h->traffic.d_s, (size_t)n * sizeof(double));
+    return fetch(h, s, traffic_s(h, h->traffic.cur), (size_t)n * sizeof(double));
+}
+
+// Car-following traffic: host checks first; the model is a kernel argument of the next advance.
+void pp_default_traffic_follow(TrafficFollow* tf)
+{
+    if (!tf) return;
+    tf->look = 60.0; tf->lateral = 1.5; tf->gap = 2.0; tf->headway = 1.5; tf->max_acc = 1.0; tf->comfort_dec = 2.0; tf->max_dec = 6.0; tf->min_net = 0.1;
+}
+
+int pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (tf) {
+        const double f[8] = { tf->look, tf->lateral, tf->gap, tf->headway, tf->max_acc, tf->comfort_dec, tf->max_dec, tf->min_net };
+        for (double x : f) if (!std::isfinite(x)) return fail(PP_ERR_ARG, "pp_set_traffic_follow: every field must be finite");
+        if (!(tf->look > 0) || !(tf->gap > 0) || !(tf->max_acc > 0) || !(tf->comfort_dec > 0) || !(tf->max_dec > 0) || !(tf->min_net > 0))
+            return fail(PP_ERR_ARG, "pp_set_traffic_follow: look, gap, max_acc, comfort_dec, max_dec and min_net must be > 0");
+        if (tf->lateral < 0 || tf->headway < 0) return fail(PP_ERR_ARG, "pp_set_traffic_follow: lateral and headway must be >= 0");
+    }
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_traffic_follow: an update is staged for the next tick (set the model before staging, or after the tick)");
+    if (!h->traffic.on) {                                 // takes effect with the next pp_set_traffic
+        h->follow.on = tf != nullptr; if (tf) h->follow.tf = *tf;
+        return PP_OK;
+    }
+    // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the arrays
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }
+    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!tf) {                                            // off: the arc lengths go back to the one array of §4h
+        if (h->follow.on && h->traffic.cur == 1) {
+            HIP_TRY(hipMemcpyAsync(h->traffic.d_s, h->follow.d_s_alt, (size_t)h->traffic.actors * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        h->traffic.cur = 0; h->follow.on = false;
+        return PP_OK;
+    }
+    { int r = build_follow(h); if (r) return r; }         // (a failed allocation or copy leaves the model that was set, or none)
+    h->follow.tf = *tf; h->follow.on = true;
+    return PP_OK;
+}
+
+int pp_get_traffic_speed(pp_handle h, double* v, int n)
+{
+    if (!h || (!v && n > 0)) return fail(PP_ERR_ARG, "null argument");
+    if (!h->traffic.on || !h->follow.on) return fail(PP_ERR_STATE, "pp_get_traffic_speed: traffic or following is off");
+    if (n < 0 || n > h->traffic.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
+    if (n == 0) return PP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    if (h->in_staged >= 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));
+    return fetch(h, v, h->follow.d_v[h->traffic.cur], (size_t)n * sizeof(double));
 }
 
 // Route following.  Everything is checked on the host before anything changes; the resident records are not touched.
@@ -2136,7 +2257,7 @@ size_t pp_sizeof(int which)
     case 15: return sizeof(MapLane); case 16: return sizeof(MapJunction); case 17: return sizeof(MapDesc); case 18: return sizeof(PpSceneIo);
     case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore); case 22: return sizeof(FleetModel);
     case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel); case 25: return sizeof(GridFollow);
-    case 26: return sizeof(TrafficTrack); case 27: return sizeof(TrafficActor);
+    case 26: return sizeof(TrafficTrack); case 27: return sizeof(TrafficActor); case 28: return sizeof(TrafficFollow);
     default: return 0;
     }
 }

@@ -69,4 +69,148 @@ k_move_traffic(int n_actors, double step, const TrafficPin* __restrict__ actors,
     if (mot) { ObMotion z; z.vx = 0; z.vy = 0; mot[pin.pool] = z; }
 }
 
+// ---- car-following traffic: k_follow_traffic takes the place of k_move_traffic in an advance while following is on.
+//
+// One 64-lane wave per actor, four actors per 256-thread block, no LDS, no barrier, no scratch (the shape of k_couple_fleet).  The
+// step is a Jacobi step: the wave reads s and v of the arrays all actors had BEFORE the advance and writes the other pair, so the
+// waves of a launch do not depend on each other.  An actor with !(speed > 0) steps exactly as k_move_traffic does.  A follower
+//   1. strides the members of its (scene, track) group - actor indices sorted by (scene, track, index), built by the host - for
+//      the nearest actor ahead within `look`: a (gap, index) wave minimum that keeps the lower index (wave_first_min);
+//   2. strides the vertices ahead of its segment, 64 per pass, for the one nearest its scene's ego as k_advance_* has just staged
+//      it, stopping after the first pass in which no lane is within `look` (the gaps never decrease): a (d2, k) wave minimum;
+//   3. - 5. picks the leader, takes the intelligent-driver acceleration, integrates - wave-uniform - and lane 0 stores s, v, the
+//      ObPoint and, with a motion pool, a zero ObMotion.
+// Only + - * / sqrt floor on doubles, every one rounded once (-ffp-contract=off), and both orders are total: the result is specified
+// to the last bit.
+constexpr int kFollowActors = 4;       // actors (waves) per block of k_follow_traffic
+
+struct TrafficRef { int32_t scene, group; };       // what a follower needs beside its pin: its scene's records, its group's members
+
+// §4h 4. - 5. for k_follow_traffic (k_move_traffic keeps its own copy: its code and registers are those of §4h's record)
+__device__ __forceinline__ void traffic_place(const TrafficPin& pin, const TrafficTrackDev& tk, const double* __restrict__ c, int i,
+                                              double s, const GlobalPoint2D* __restrict__ pts, ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const double c0 = c[i], d = c[i + 1] - c0;
+    const double t = d > 0 ? (s - c0) / d : 0.0;
+    const GlobalPoint2D P = pts[tk.point_off + i];
+    const GlobalPoint2D Q = pts[tk.point_off + (i + 1 < tk.n_points ? i + 1 : 0)];
+    ObPoint o;
+    o.x = P.x + t * (Q.x - P.x); o.y = P.y + t * (Q.y - P.y); o.type = pin.type; o.radius = pin.radius;
+    obs[pin.pool] = o;
+    if (mot) { ObMotion z; z.vx = 0; z.vy = 0; mot[pin.pool] = z; }
+}
+
+// §4h 4., first line: the largest i in [0, nseg) with cum[i] <= s
+__device__ __forceinline__ int traffic_locate(const double* __restrict__ c, int nseg, double s)
+{
+    int lo = 0, hi = nseg;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (c[mid] <= s) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// in: the SceneIn records being staged (read: loc.globalpoint, loc.velocity); flags: the ego flag words as the advance left them.
+// s_in / v_in and s_out / v_out are different arrays.  half_w = 0.5 * Vehicle_Width (rounded once, on the host: exact).
+__global__ void __launch_bounds__(kBlock)
+k_follow_traffic(int n_actors, double dt, TrafficFollow tf, double half_w, const TrafficPin* __restrict__ actors, const TrafficRef* __restrict__ refs,
+                 const int32_t* __restrict__ group_first, const int32_t* __restrict__ members, const TrafficTrackDev* __restrict__ tracks,
+                 const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts, const double* __restrict__ s_in, const double* __restrict__ v_in,
+                 double* __restrict__ s_out, double* __restrict__ v_out, const SceneIn* __restrict__ in, const int32_t* __restrict__ flags,
+                 ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const int lane = threadIdx.x & 63;
+    const int a = blockIdx.x * kFollowActors + (threadIdx.x >> 6);
+    if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
+    const TrafficPin pin = actors[a];
+    const TrafficTrackDev tk = tracks[pin.track];
+    const bool closed = tk.closed != 0;
+    const int n = tk.n_points, nseg = closed ? n : n - 1;
+    const double* c = cum + tk.cum_off;
+    const double L = c[nseg];
+    const double s = s_in[a];
+    if (!(pin.speed > 0)) {                             // parked or reversing: §4h's step, v = speed
+        if (lane == 0) {
+            const double s1 = traffic_wrap(s + pin.speed * dt, L, closed);
+            s_out[a] = s1; v_out[a] = pin.speed;
+            traffic_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, obs, mot);
+        }
+        return;
+    }
+    const double v = v_in[a];
+    const TrafficRef ref = refs[a];
+    // 1. the actor ahead: the smallest (g, b) over the group
+    double bg = 0; int bi = -1;
+    for (int m = group_first[ref.group] + lane, m1 = group_first[ref.group + 1]; m < m1; m += 64) {
+        const int b = members[m];
+        if (b == a) continue;
+        double g = s_in[b] - s;
+        bool ok = true;
+        if (closed) { if (g < 0 || (g == 0 && b > a)) g = g + L; }
+        else ok = g > 0 || (g == 0 && b < a);
+        if (ok && g <= tf.look && (bi < 0 || g < bg)) { bg = g; bi = b; }       // (b rises within a lane: ties keep the lower index; a NaN compares false)
+    }
+    wave_first_min(bg, bi);
+    // 2. the ego: the first nearest vertex of the window ahead
+    const double x = in[ref.scene].loc.globalpoint.x, y = in[ref.scene].loc.globalpoint.y;
+    const int i0 = traffic_locate(c, nseg, s);
+    const int kmax = closed ? n : n - 1 - i0;
+    auto gap_of = [&](int k, int& pj) {
+        const int j = i0 + k;
+        if (j <= n - 1) { pj = j; return c[j] - s; }
+        pj = j - n; return (L - s) + c[pj];
+    };
+    double ed = 0; int ek = -1;
+    for (int k0 = 1; k0 <= kmax; k0 += 64) {
+        const int k = k0 + lane;
+        bool within = false;
+        if (k <= kmax) {
+            int pj; const double g = gap_of(k, pj);
+            if (g <= tf.look) {
+                within = true;
+                const GlobalPoint2D P = pts[tk.point_off + pj];
+                const double ex = P.x - x, ey = P.y - y;
+                const double d2 = ex * ex + ey * ey;
+                if ((ek < 0 && d2 == d2) || d2 < ed) { ed = d2; ek = k; }       // (k rises within a lane; a NaN is never the minimum)
+            }
+        }
+        if (!__any(within)) break;
+    }
+    wave_first_min(ed, ek);
+    // 3. the leader (wave-uniform from here on)
+    bool lead = false; double g = 0, vl = 0, rl = 0;
+    if (bi >= 0) { lead = true; g = bg; vl = v_in[bi]; rl = (double)actors[bi].radius; }
+    if (ek >= 0 && ed <= tf.lateral * tf.lateral) {
+        int pj; const double ge = gap_of(ek, pj);
+        if (!lead || ge <= g) {
+            lead = true; g = ge; rl = half_w;
+            vl = flags[ref.scene] != 0 ? 0.0 : in[ref.scene].loc.velocity / 3.6;
+        }
+    }
+    // 4. the acceleration
+    const double r = v / pin.speed, r2 = r * r, fr = 1 - r2 * r2;
+    double acc;
+    if (!lead) acc = tf.max_acc * fr;
+    else {
+        double net = g - (double)pin.radius - rl;
+        if (!(net > tf.min_net)) net = tf.min_net;
+        const double dv = v - vl;
+        const double c2 = 2 * sqrt(tf.max_acc * tf.comfort_dec);
+        double dyn = v * tf.headway + (v * dv) / c2;
+        if (!(dyn > 0)) dyn = 0;
+        const double star = tf.gap + dyn, q = star / net;
+        acc = tf.max_acc * (fr - q * q);
+    }
+    if (!(acc >= -tf.max_dec)) acc = -tf.max_dec;       // (a NaN brakes)
+    // 5. integrate and place
+    double v1 = v + acc * dt;
+    if (!(v1 > 0)) v1 = 0;
+    const double s1 = traffic_wrap(s + 0.5 * (v + v1) * dt, L, closed);
+    if (lane == 0) {
+        s_out[a] = s1; v_out[a] = v1;
+        traffic_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, obs, mot);
+    }
+}
+
 }  // namespace dmpp

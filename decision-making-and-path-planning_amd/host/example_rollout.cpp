@@ -12,6 +12,9 @@
 // With --route --traffic every ring ego has a slower vehicle 20 m ahead of it (pp_set_traffic): a scripted actor at
 // 1.5 m/s on the closed track of the ego's lane, written into the ego's one obstacle entry on every staged input set; the run is
 // scored, and the host prints how many egos saw their vehicle, the worst clearance and the distance travelled.
+// With --route --traffic --react the vehicle starts 15 m BEHIND its ego at a desired 8 m/s instead and the car-following law is on
+// (pp_set_traffic_follow with the default model): it closes up, finds the ego as its leader and keeps a gap; the host
+// prints the smallest ego-actor clearance of the run and the vehicles' mean speed at the end.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -24,7 +27,7 @@
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic)
+static int run_route(bool follow, bool traffic, bool react)
 {
     const int n = 64, ticks = 1200, P = 260, JP = 40, n_lanes = 2;
     const double kPi = 3.14159265358979323846, step = 0.5, w = 3.75;
@@ -101,7 +104,8 @@ static int run_route(bool follow, bool traffic)
             for (int i = 0; i < at; i++) here += std::sqrt((T[i + 1].x - T[i].x) * (T[i + 1].x - T[i].x) + (T[i + 1].y - T[i].y) * (T[i + 1].y - T[i].y));
             e.obs_off = s; e.obs_n = 1;
             obs[(size_t)s] = ObPoint{ 0, 0, 0, 0.9f };    // (placed by pp_set_traffic)
-            actors.push_back(TrafficActor{ here + 20.0, 1.5, s, 0, lane - 1, 1, 0.9f, 0 });
+            if (react) actors.push_back(TrafficActor{ here - 15.0, 8.0, s, 0, lane - 1, 1, 0.9f, 0 });      // (a closed track: a negative s0 wraps)
+            else actors.push_back(TrafficActor{ here + 20.0, 1.5, s, 0, lane - 1, 1, 0.9f, 0 });
         }
     }
     pp_handle h = nullptr;
@@ -115,6 +119,7 @@ static int run_route(bool follow, bool traffic)
     EgoModel model; pp_default_ego_model(&model);
     if (traffic) {
         CHECK(pp_set_traffic(h, (int)tracks.size(), tracks.data(), tpts.data(), (int)tpts.size(), n, actors.data()));
+        if (react) { TrafficFollow tf; pp_default_traffic_follow(&tf); CHECK(pp_set_traffic_follow(h, &tf)); }
         CHECK(pp_score_begin(h, model.dt));
     }
     long long last = 0;
@@ -130,6 +135,13 @@ static int run_route(bool follow, bool traffic)
             saw += r.n_ob_flag > 0; hit += r.n_collision_ticks > 0; dist += r.dist; if (r.min_clearance < worst) worst = r.min_clearance;
             driven += arc[(size_t)s];
         }
+        if (react) {
+            std::vector<double> v(n); double vsum = 0;
+            CHECK(pp_get_traffic_speed(h, v.data(), n));
+            for (int s = 0; s < n; s++) vsum += v[(size_t)s];
+            std::printf("react: %d vehicles that want %.1f m/s, 15 m behind their egos, following on: %d egos were touched, smallest ego-actor clearance of the run %.2f m, "
+                        "mean distance travelled by the egos %.1f m, mean vehicle speed now %.2f m/s\n", n, actors[0].speed, hit, worst, dist / n, vsum / n);
+        } else
         std::printf("traffic: %d vehicles at %.1f m/s, 20 m ahead of their egos: %d of %d egos saw theirs (ob_flag), %d touched it, worst clearance %.2f m, "
                     "mean distance travelled %.1f m (a vehicle covers %.1f m; mean arc length now %.1f m)\n",
                     n, actors[0].speed, saw, n, hit, worst, dist / n, actors[0].speed * model.dt * ticks, driven / n);
@@ -155,16 +167,18 @@ static int run_route(bool follow, bool traffic)
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
         else if (std::strcmp(argv[a], "--follow") == 0) follow = true;
         else if (std::strcmp(argv[a], "--traffic") == 0) traffic = true;
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--traffic]] [--follow]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--react") == 0) react = true;
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--traffic [--react]]] [--follow]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
-    if (route) return run_route(follow, traffic);
+    if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
+    if (route) return run_route(follow, traffic, react);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

@@ -303,6 +303,27 @@ int  pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const
  * PP_ERR_STATE while traffic is off. */
 int  pp_get_traffic_state(pp_handle h, double* s, int n);
 
+/* ---- car-following traffic: actors keep a gap to the ego and to each other ---------------------------------------
+ * Without it an actor drives its track at a constant speed whatever is in front of it.  pp_set_traffic_follow switches a
+ * deterministic car-following law on: while traffic is set, pp_advance_async launches k_follow_traffic (one wave per actor) in the
+ * place of k_move_traffic.  Every actor carries a speed v beside its arc length s; an actor with speed > 0 takes speed as its
+ * desired speed, looks tf->look metres ahead along its track for the nearest actor of its own scene on the same track and for
+ * its scene's ego (the ego counts when it lies within tf->lateral of the nearest track vertex of that window), and accelerates by
+ * the intelligent-driver model, clamped at -max_dec; v never goes below 0.  An actor with speed <= 0 steps as before.  The step is
+ * a Jacobi step: every actor reads the s and v all actors had before the advance, and the ego pose the advance has just staged.
+ * Every arithmetic step is specified (§4i): a numpy restatement gives the same bytes.
+ * v is set to the actors' speed by pp_set_traffic while following is on and by pp_set_traffic_follow(non-NULL) while traffic is
+ * on; pp_update_async leaves it alone.  The model belongs to the handle: it survives pp_set_scenes / pp_set_egos /
+ * pp_set_n_scenes / pp_set_map / pp_set_config and takes effect only while traffic is on.  tf NULL: off (the actors go on at
+ * their constant speed from where they are).  A handle that never switches it on allocates and launches none of this.
+ * PP_ERR_ARG (nothing changes): a field that is not finite; look, gap, max_acc, comfort_dec, max_dec or min_net not > 0; lateral
+ * or headway < 0.  PP_ERR_STATE: an update is staged for the next tick.  One host wait while traffic is on, none otherwise. */
+void pp_default_traffic_follow(TrafficFollow* tf);   /* { 60, 1.5, 2, 1.5, 1, 2, 6, 0.1 } */
+int  pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf);
+/* The speed of actors 0 .. n - 1, as pp_get_traffic_state gives their arc length (same set, same wait).  PP_ERR_STATE while
+ * traffic or following is off. */
+int  pp_get_traffic_speed(pp_handle h, double* v, int n);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -367,7 +388,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
- * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor */
+ * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -335,6 +335,20 @@ typedef struct TrafficActor {
     int32_t _pad;
 } TrafficActor;                                                             /* 40 B */
 
+/* ---- car-following traffic (build-defined) ----------------------------------------------------
+ * pp_set_traffic_follow makes every actor with speed > 0 keep a gap to the vehicle ahead of it on its track - another
+ * actor of its scene, or the scene's ego - by the intelligent-driver model; speed is then its DESIRED speed. */
+typedef struct TrafficFollow {
+    double look;         /* m: how far ahead along its track an actor sees                     */
+    double lateral;      /* m: the ego counts as on the track within this distance of a vertex */
+    double gap;          /* m: standstill gap                                                  */
+    double headway;      /* s: time headway                                                    */
+    double max_acc;      /* m/s^2: free-road acceleration                                      */
+    double comfort_dec;  /* m/s^2: comfortable deceleration                                    */
+    double max_dec;      /* m/s^2: hardest braking (the clamp)                                 */
+    double min_net;      /* m: the net gap is never taken smaller than this                    */
+} TrafficFollow;                                                            /* 64 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

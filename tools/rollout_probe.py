@@ -84,6 +84,7 @@ def fleet_run(on):
 TRAFFIC = int(os.environ.get("TRAFFIC", "0"))
 if TRAFFIC == 1:
     TRAFFIC = 8
+REACT = os.environ.get("REACT", "0") == "1"
 
 
 def traffic_run(on):
@@ -97,7 +98,10 @@ def traffic_run(on):
     actors["scene"], actors["slot"], actors["track"] = k // TRAFFIC, k % TRAFFIC, k // TRAFFIC
     actors["s0"], actors["speed"], actors["type"], actors["radius"] = 10.0 + 12.0 * (k % TRAFFIC), 1.0 + (k % 8), 1, 0.9
     pl.set_traffic(tracks, pts, actors)
-    if not on:
+    if REACT:                         # REACT=1: traffic stays on in both legs; "on" = the car-following law too
+        if on:
+            pl.set_traffic_follow(dm.default_traffic_follow())
+    elif not on:
         pl.set_traffic(None)          # the entries stay where the set call put them: plain obstacles
     pl.rollout(warm, model)
     pl.sync()
@@ -228,8 +232,8 @@ if TRAFFIC > 0:
         off.append(a), on.append(b)
         print("run %d  %d scenes, obs_n %d  traffic off %.3f M ticks/s (%d frozen at the end)   traffic on (%d actors per scene) %.3f M ticks/s (%d frozen)" %
               (r, n, n_obs, a / 1e6, fa, TRAFFIC, b / 1e6, fb), flush=True)
-    print("median  %d scenes  traffic off %.3f M ticks/s (spread %.3f)   traffic on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
-          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+    print("median  %d scenes  %s off %.3f M ticks/s (spread %.3f)   %s on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, "following (traffic on)" if REACT else "traffic", statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, "following" if REACT else "traffic", statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with traffic alone
         traffic_run(True)
