@@ -226,6 +226,8 @@ def load_library(path=None):
     if traffic:
         lib.pp_set_traffic.argtypes = [vp, ci, vp, vp, ci, ci, vp]
         lib.pp_get_traffic_state.argtypes = [vp, vp, ci]
+    if hasattr(lib, "pp_set_world_traffic") or path == LIB_PATH:          # (as above: an older build may lack it)
+        lib.pp_set_world_traffic.argtypes = [vp, ci, vp, vp, ci, ci, vp]
     react = hasattr(lib, "pp_set_traffic_follow") or path == LIB_PATH          # (as above: an older build may lack it)
     if react:
         lib.pp_default_traffic_follow.argtypes = [vp]
@@ -539,6 +541,21 @@ class Planner:
         pt = np.ascontiguousarray(points, GlobalPoint2D)
         ac = np.ascontiguousarray(actors, TrafficActor)
         _check(self.lib.pp_set_traffic(self.h, len(tr), _ptr(tr), _ptr(pt), len(pt), len(ac), _ptr(ac)))
+        self.n_traffic = len(ac)
+
+    def set_world_traffic(self, tracks=None, points=None, actors=None):
+        """pp_set_world_traffic: as set_traffic, with TrafficActor.scene a WORLD of the fleet in force and TrafficActor.slot an own
+        entry of every member scene of that world - one vehicle per world, written into every member and, with following on, led by
+        the nearest of all the world's egos.  Needs set_fleet first; replaces whatever traffic the handle had.
+        tracks / actors None (or no actors): traffic off."""
+        if tracks is None or actors is None or len(actors) == 0:
+            _check(self.lib.pp_set_world_traffic(self.h, 0, None, None, 0, 0, None))
+            self.n_traffic = 0
+            return
+        tr = np.ascontiguousarray(tracks, TrafficTrack)
+        pt = np.ascontiguousarray(points, GlobalPoint2D)
+        ac = np.ascontiguousarray(actors, TrafficActor)
+        _check(self.lib.pp_set_world_traffic(self.h, len(tr), _ptr(tr), _ptr(pt), len(pt), len(ac), _ptr(ac)))
         self.n_traffic = len(ac)
 
     def set_traffic_follow(self, tf=None):

@@ -152,7 +152,7 @@ struct ScoreState {
 // the pinned slices on the host too (a second pp_set_fleet starts from the scenes' OWN entries); end: the largest end of a
 // peer-slot run, base: the used pool size before the fleet grew it, own_end: the largest end of a scene's OWN entries
 struct FleetState {
-    bool on = false; FleetModel fm = { 0, 0, 0 }; int end = 0, base = 0, own_end = 0;
+    bool on = false; FleetModel fm = { 0, 0, 0 }; int end = 0, base = 0, own_end = 0, n_worlds = 0;
     DevBuf<int32_t> d_world_first, d_world_of; DevBuf<dmpp::FleetPin> d_pin;
     std::vector<dmpp::FleetPin> pin;
 };
@@ -161,9 +161,12 @@ struct FleetState {
 struct RouteState { bool on = false; RouteModel rm = { 0, 0 }; DevBuf<RouteLeg> d_legs; DevBuf<int32_t> d_first; };
 // lane traffic (first pp_set_traffic): the actors with their pinned pool entries, the tracks, the compact point
 // array and the cumulative-length table; d_s: the arc length of every actor, SINGLE-COPY like the rollout flags (the advances
-// that step it are serial on the upload stream).  end: the largest pinned pool entry + 1
+// that step it are serial on the upload stream).  end: the largest pinned pool entry + 1.
+// world (pp_set_world_traffic): one vehicle per WORLD of the fleet in force - d_pin[a].pool is then the SLOT, d_world
+// (allocated by that call only) every vehicle's world, scene_of the worlds, and the pins are the fleet's FleetPin table
 struct TrafficState {
-    bool on = false; int actors = 0, end = 0;
+    bool on = false, world = false; int actors = 0, end = 0;
+    DevBuf<int32_t> d_world;
     DevBuf<dmpp::TrafficPin> d_pin; DevBuf<dmpp::TrafficTrackDev> d_tracks; DevBuf<double> d_cum; DevBuf<GlobalPoint2D> d_pts; DevBuf<double> d_s;
     std::vector<int32_t> scene_of, track_of;      // host: what a later pp_set_traffic_follow groups the actors by
     int cur = 0;                                  // which arc-length array is current: 0 d_s, 1 FollowState::d_s_alt (only while following)
@@ -343,6 +346,12 @@ double* traffic_s(pp_planner* h, int which) { return which ? h->follow.d_s_alt.g
 void move_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot, double step)
 {
     const int n = h->traffic.actors;
+    if (h->traffic.world) {               // one vehicle per world, written into every member scene (§4j)
+        hipLaunchKernelGGL(dmpp::k_move_world_traffic, dim3((unsigned)((n + dmpp::kWorldActors - 1) / dmpp::kWorldActors)), dim3(dmpp::kBlock), 0, st,
+                           n, step, h->traffic.d_pin, h->traffic.d_world, h->fleet.d_world_first, h->fleet.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts,
+                           traffic_s(h, h->traffic.cur), d_obs, d_mot);
+        return;
+    }
     hipLaunchKernelGGL(dmpp::k_move_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
                        n, step, h->traffic.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, h->traffic.cur), d_obs, d_mot);
 }
@@ -353,6 +362,12 @@ void move_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot
 int follow_traffic(pp_planner* h, hipStream_t st, const SceneIn* d_in, ObPoint* d_obs, ObMotion* d_mot, double dt)
 {
     const int n = h->traffic.actors, cur = h->traffic.cur;
+    if (h->traffic.world)                 // the leader is the nearest of all the world's egos (§4j)
+        hipLaunchKernelGGL(dmpp::k_follow_world_traffic, dim3((unsigned)((n + dmpp::kWorldActors - 1) / dmpp::kWorldActors)), dim3(dmpp::kBlock), 0, st,
+                           n, dt, h->follow.tf, 0.5 * h->cfg.Vehicle_Width, h->traffic.d_pin, h->follow.d_ref, h->follow.d_first, h->follow.d_members,
+                           h->fleet.d_world_first, h->fleet.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, cur), h->follow.d_v[cur],
+                           traffic_s(h, cur ^ 1), h->follow.d_v[cur ^ 1], d_in, h->rollout.d_flags, d_obs, d_mot);
+    else
     hipLaunchKernelGGL(dmpp::k_follow_traffic, dim3((unsigned)((n + dmpp::kFollowActors - 1) / dmpp::kFollowActors)), dim3(dmpp::kBlock), 0, st,
                        n, dt, h->follow.tf, 0.5 * h->cfg.Vehicle_Width, h->traffic.d_pin, h->follow.d_ref, h->follow.d_first, h->follow.d_members,
                        h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, cur), h->follow.d_v[cur], traffic_s(h, cur ^ 1), h->follow.d_v[cur ^ 1],
@@ -1676,6 +1691,7 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
         // (the slices are the pinned ones again; they were inside fleet.base when they were pinned)
         const int back = std::max(h->fleet.base, h->fleet.own_end);
         h->fleet.on = false; h->n_obs_total = back; h->in_sets[h->in_cur].n_obs_total = back;
+        if (h->traffic.world) h->traffic.on = false;      // (the worlds it was pinned to are gone: §4j)
         return PP_OK;
     }
     if (!world_first || !fm) return fail(PP_ERR_ARG, "null argument");
@@ -1715,6 +1731,8 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     HIP_TRY(hipMemcpyAsync(h->fleet.d_world_of, world_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->fleet.d_pin, pin.data(), (size_t)n * sizeof(dmpp::FleetPin), hipMemcpyHostToDevice, h->stream));
     h->fleet.pin.swap(pin); h->fleet.fm = *fm; h->fleet.base = base; h->fleet.end = (int)end_max; h->fleet.own_end = (int)std::min(own_end, (long long)h->caps.max_obs_total); h->fleet.on = true;
+    h->fleet.n_worlds = n_worlds;
+    if (h->traffic.world) h->traffic.on = false;          // world traffic was pinned to the worlds this call replaces (§4j)
     h->n_obs_total = (int)end_max; h->in_sets[h->in_cur].n_obs_total = (int)end_max;
     couple_fleet(h, h->stream, h->d_in, h->d_obs, h->have_motion ? h->d_mot : nullptr);      // the resident set: the next tick sees the peers
     HIP_TRY(hipGetLastError());
@@ -1723,25 +1741,28 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
 }
 
 // Lane traffic.  Everything is checked on the host before anything changes; the cumulative lengths are computed
-// here, in order (+, * and sqrt round as on the device), and uploaded.
-int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points, int n_actors, const TrafficActor* actors)
+// here, in order (+, * and sqrt round as on the device), and uploaded.  world: pp_set_world_traffic - an actor's
+// `scene` is a world of the fleet in force and its slot an own entry of EVERY member scene of that world.
+static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points, int n_actors, const TrafficActor* actors)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    if (n_tracks < 0 || n_points < 0 || n_actors < 0) return fail(PP_ERR_ARG, "pp_set_traffic: negative count");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_traffic: an update is staged for the next tick (set the traffic before staging, or after the tick)");
+    const std::string fn = world ? "pp_set_world_traffic" : "pp_set_traffic";
+    if (n_tracks < 0 || n_points < 0 || n_actors < 0) return fail(PP_ERR_ARG, fn + ": negative count");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, fn + ": an update is staged for the next tick (set the traffic before staging, or after the tick)");
     if (n_actors == 0) { h->traffic.on = false; return PP_OK; }
     const int n = h->n_scenes;
-    if (n <= 0) return fail(PP_ERR_STATE, "pp_set_traffic: no resident scenes");
-    if (!tracks || !points || !actors || n_tracks == 0) return fail(PP_ERR_ARG, "pp_set_traffic: actors need tracks and points");
+    if (n <= 0) return fail(PP_ERR_STATE, fn + ": no resident scenes");
+    if (world && !h->fleet.on) return fail(PP_ERR_STATE, fn + ": no fleet is set (the worlds are those of pp_set_fleet; max_peers = 0 is a legal fleet)");
+    if (!tracks || !points || !actors || n_tracks == 0) return fail(PP_ERR_ARG, fn + ": actors need tracks and points");
     // tracks: compact copies of their points, and the cumulative lengths (closed: one more segment, back to the first point)
     std::vector<dmpp::TrafficTrackDev> tdev((size_t)n_tracks);
     std::vector<GlobalPoint2D> pts; std::vector<double> cum;
     for (int k = 0; k < n_tracks; k++) {
         const TrafficTrack& T = tracks[k];
-        const std::string who = "pp_set_traffic: track " + std::to_string(k);
+        const std::string who = fn + ": track " + std::to_string(k);
         if (T.n_points < 2) return fail(PP_ERR_ARG, who + " has fewer than 2 points");
         if (T.point_off < 0 || (long long)T.point_off + T.n_points > (long long)n_points) return fail(PP_ERR_ARG, who + " lies outside the point array");
-        if (pts.size() + (size_t)T.n_points > (size_t)INT32_MAX / 2) return fail(PP_ERR_ARG, "pp_set_traffic: more than 2^30 track points");
+        if (pts.size() + (size_t)T.n_points > (size_t)INT32_MAX / 2) return fail(PP_ERR_ARG, fn + ": more than 2^30 track points");
         const GlobalPoint2D* P = points + T.point_off;
         for (int i = 0; i < T.n_points; i++)
             if (!std::isfinite(P[i].x) || !std::isfinite(P[i].y)) return fail(PP_ERR_ARG, who + " has a non-finite point");
@@ -1764,14 +1785,35 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     const std::vector<dmpp::FleetPin> own = own_slices(h, &rc); if (rc) return rc;
     std::vector<dmpp::TrafficPin> pin((size_t)n_actors); std::vector<double> s0((size_t)n_actors); std::vector<long long> taken((size_t)n_actors);
     std::vector<int32_t> scene_of((size_t)n_actors), track_of((size_t)n_actors);
+    std::vector<int32_t> world_first;                     // world: the fleet's, read back (the host keeps no copy of it)
+    if (world) {
+        world_first.resize((size_t)h->fleet.n_worlds + 1);
+        HIP_TRY(hipMemcpyAsync(world_first.data(), h->fleet.d_world_first, world_first.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
     long long end_max = 0;
     for (int a = 0; a < n_actors; a++) {
         const TrafficActor& A = actors[a];
-        const std::string who = "pp_set_traffic: actor " + std::to_string(a);
+        const std::string who = fn + ": actor " + std::to_string(a);
         if (!std::isfinite(A.s0) || !std::isfinite(A.speed)) return fail(PP_ERR_ARG, who + " has a non-finite s0 or speed");
         if (!std::isfinite(A.radius) || !(A.radius >= 0)) return fail(PP_ERR_ARG, who + ": radius must be finite and >= 0");
-        if (A.scene < 0 || A.scene >= n) return fail(PP_ERR_ARG, who + " names a scene that is not resident");
+        if (world && (A.scene < 0 || A.scene >= h->fleet.n_worlds)) return fail(PP_ERR_ARG, who + " names a world that the fleet does not have");
+        if (!world && (A.scene < 0 || A.scene >= n)) return fail(PP_ERR_ARG, who + " names a scene that is not resident");
         if (A.track < 0 || A.track >= n_tracks) return fail(PP_ERR_ARG, who + " names a track that was not given");
+        if (world) {                                      // the slot must be an own entry of every member scene; the pin keeps the slot
+            for (int m = world_first[(size_t)A.scene]; m < world_first[(size_t)A.scene + 1]; m++) {
+                const dmpp::FleetPin& O = own[(size_t)m];
+                const long long pool = (long long)O.obs_off + A.slot;
+                if (A.slot < 0 || A.slot >= O.n_own || O.obs_off < 0 || pool >= (long long)h->caps.max_obs_total)
+                    return fail(PP_ERR_ARG, who + ": slot " + std::to_string(A.slot) + " is not one of the " + std::to_string(std::max(O.n_own, 0)) + " own obstacle entries of scene " + std::to_string(m) +
+                                            " (world " + std::to_string(A.scene) + ")");
+                end_max = std::max(end_max, pool + 1);
+            }
+            pin[(size_t)a] = { A.speed, A.slot, A.track, A.type, A.radius };
+            scene_of[(size_t)a] = A.scene; track_of[(size_t)a] = A.track;
+            s0[(size_t)a] = A.s0; taken[(size_t)a] = ((long long)A.scene << 32) | (long long)A.slot;
+            continue;
+        }
         const dmpp::FleetPin& O = own[(size_t)A.scene];
         const long long pool = (long long)O.obs_off + A.slot;
         if (A.slot < 0 || A.slot >= O.n_own || O.obs_off < 0 || pool >= (long long)h->caps.max_obs_total)
@@ -1783,21 +1825,23 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     }
     std::sort(taken.begin(), taken.end());
     for (size_t k = 1; k < taken.size(); k++)
-        if (taken[k] == taken[k - 1]) return fail(PP_ERR_ARG, "pp_set_traffic: two actors on slot " + std::to_string((int)(taken[k] & 0xffffffff)) + " of scene " + std::to_string((int)(taken[k] >> 32)));
+        if (taken[k] == taken[k - 1]) return fail(PP_ERR_ARG, fn + ": two actors on slot " + std::to_string((int)(taken[k] & 0xffffffff)) + (world ? " of world " : " of scene ") + std::to_string((int)(taken[k] >> 32)));
     // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the old arrays
     if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
     HIP_TRY(hipStreamSynchronize(h->stream));
     // room first.  An allocation that fails leaves its own array as it was, but may follow one that replaced another: the old
     // traffic then goes off rather than run on half a set
     if ((rc = h->traffic.d_pin.reserve((size_t)n_actors)) || (rc = h->traffic.d_s.reserve((size_t)n_actors)) || (rc = h->traffic.d_tracks.reserve((size_t)n_tracks)) ||
-        (rc = h->traffic.d_cum.reserve(cum.size())) || (rc = h->traffic.d_pts.reserve(pts.size()))) { h->traffic.on = false; return rc; }
+        (rc = h->traffic.d_cum.reserve(cum.size())) || (rc = h->traffic.d_pts.reserve(pts.size())) ||
+        (world && (rc = h->traffic.d_world.reserve((size_t)n_actors)))) { h->traffic.on = false; return rc; }
     h->traffic.on = false;                                // (until everything below has landed: a device error leaves traffic off, never half a set)
     HIP_TRY(hipMemcpyAsync(h->traffic.d_pin, pin.data(), (size_t)n_actors * sizeof(dmpp::TrafficPin), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_s, s0.data(), (size_t)n_actors * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_tracks, tdev.data(), (size_t)n_tracks * sizeof(dmpp::TrafficTrackDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_cum, cum.data(), cum.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_pts, pts.data(), pts.size() * sizeof(GlobalPoint2D), hipMemcpyHostToDevice, h->stream));
-    h->traffic.actors = n_actors; h->traffic.end = (int)end_max; h->traffic.cur = 0;
+    if (world) HIP_TRY(hipMemcpyAsync(h->traffic.d_world, scene_of.data(), (size_t)n_actors * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    h->traffic.actors = n_actors; h->traffic.end = (int)end_max; h->traffic.cur = 0; h->traffic.world = world;
     h->traffic.scene_of.swap(scene_of); h->traffic.track_of.swap(track_of);
     move_traffic(h, h->stream, h->d_obs, h->have_motion ? h->d_mot : nullptr, 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
     HIP_TRY(hipGetLastError());
@@ -1805,6 +1849,17 @@ int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const 
     if (h->follow.on) { int r = build_follow(h); if (r) return r; }      // following is on: its tables for these actors, v = speed (§4i)
     h->traffic.on = true;
     return PP_OK;
+}
+
+int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points, int n_actors, const TrafficActor* actors)
+{
+    return set_traffic(h, false, n_tracks, tracks, points, n_points, n_actors, actors);
+}
+
+// World traffic: the same records, read per world of the fleet in force; replaces whatever traffic the handle had.
+int pp_set_world_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points, int n_actors, const TrafficActor* actors)
+{
+    return set_traffic(h, true, n_tracks, tracks, points, n_points, n_actors, actors);
 }
 
 int pp_get_traffic_state(pp_handle h, double* s, int n)

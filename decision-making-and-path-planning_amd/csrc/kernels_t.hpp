@@ -10,6 +10,7 @@
 // the last bit.
 #pragma once
 #include "dev_geom.hpp"
+#include "kernels_f.hpp"
 
 namespace dmpp {
 
@@ -211,6 +212,160 @@ k_follow_traffic(int n_actors, double dt, TrafficFollow tf, double half_w, const
         s_out[a] = s1; v_out[a] = v1;
         traffic_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, obs, mot);
     }
+}
+
+// ---- world traffic: one vehicle per WORLD of the fleet in force, written into entry pin[m].obs_off + slot of
+// every member scene m and - following - led by the nearest of all the world's egos.  k_move_world_traffic and
+// k_follow_world_traffic take the places of k_move_traffic and k_follow_traffic while the handle's traffic was set with
+// pp_set_world_traffic; a TrafficPin then carries the SLOT in `pool` and a TrafficRef the WORLD in `scene`.
+//
+// One 64-lane wave per vehicle, four per 256-thread block, no LDS, no barrier, no scratch.  The vehicle index is made wave-uniform
+// (readfirstlane), so its record, its track and its state are scalar loads and the pose is computed once per wave; the lanes
+// stride the world's members to store it - the same bytes into every member's entry, plain vector stores.  The follow kernel
+//   1. strides its (world, track) group exactly as k_follow_traffic strides its (scene, track) group;
+//   2. strides the member EGOS, 64 per pass: every lane walks the window vertices k = 1, 2, .. while g_k <= look (the trip count
+//      and the vertex loads are wave-uniform), keeps the first minimum d2 of its own ego, applies the lateral test and keeps its
+//      best (g_e, e) across passes (e rises within a lane: a tie keeps the lower scene); one wave_first_min picks the leader;
+//   3. - 5. as k_follow_traffic, wave-uniform.
+// Only + - * / sqrt floor on doubles, every one rounded once (-ffp-contract=off), and both orders are total: the result is specified
+// to the last bit.
+constexpr int kWorldActors = 4;        // vehicles (waves) per block of the two world-traffic kernels
+
+// §4h 4. - 5. for the world kernels: the pose once per wave, then one entry per member scene (lanes stride [p0, p1))
+__device__ __forceinline__ void world_place(const TrafficPin& pin, const TrafficTrackDev& tk, const double* __restrict__ c, int i, double s,
+                                            const GlobalPoint2D* __restrict__ pts, int lane, int p0, int p1, const FleetPin* __restrict__ fpin,
+                                            ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const double c0 = c[i], d = c[i + 1] - c0;
+    const double t = d > 0 ? (s - c0) / d : 0.0;
+    const GlobalPoint2D P = pts[tk.point_off + i];
+    const GlobalPoint2D Q = pts[tk.point_off + (i + 1 < tk.n_points ? i + 1 : 0)];
+    ObPoint o;
+    o.x = P.x + t * (Q.x - P.x); o.y = P.y + t * (Q.y - P.y); o.type = pin.type; o.radius = pin.radius;
+    for (int m = p0 + lane; m < p1; m += 64) {
+        const int e = fpin[m].obs_off + pin.pool;        // (the slot is an own entry of every member: checked by pp_set_world_traffic)
+        obs[e] = o;
+        if (mot) { ObMotion z; z.vx = 0; z.vy = 0; mot[e] = z; }
+    }
+}
+
+// step: 0 (pp_set_world_traffic, pp_update_async) or EgoModel.dt (pp_advance_async with following off).  world: every vehicle's world.
+__global__ void __launch_bounds__(kBlock)
+k_move_world_traffic(int n_actors, double step, const TrafficPin* __restrict__ actors, const int32_t* __restrict__ world,
+                     const int32_t* __restrict__ world_first, const FleetPin* __restrict__ fpin, const TrafficTrackDev* __restrict__ tracks,
+                     const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts, double* __restrict__ s_arr,
+                     ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const int lane = threadIdx.x & 63;
+    const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * kWorldActors + (threadIdx.x >> 6));
+    if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
+    const TrafficPin pin = actors[a];
+    const TrafficTrackDev tk = tracks[pin.track];
+    const bool closed = tk.closed != 0;
+    const int nseg = closed ? tk.n_points : tk.n_points - 1;
+    const double* c = cum + tk.cum_off;
+    const double L = c[nseg];
+    double s = s_arr[a];
+    if (step != 0) s = s + pin.speed * step;
+    s = traffic_wrap(s, L, closed);
+    if (lane == 0) s_arr[a] = s;
+    const int w = world[a];
+    world_place(pin, tk, c, traffic_locate(c, nseg, s), s, pts, lane, world_first[w], world_first[w + 1], fpin, obs, mot);
+}
+
+// As k_follow_traffic, with refs[a].scene = the vehicle's WORLD and the groups those of (world, track); in / flags: the records and
+// ego flag words of every scene as staged.
+__global__ void __launch_bounds__(kBlock)
+k_follow_world_traffic(int n_actors, double dt, TrafficFollow tf, double half_w, const TrafficPin* __restrict__ actors, const TrafficRef* __restrict__ refs,
+                       const int32_t* __restrict__ group_first, const int32_t* __restrict__ members, const int32_t* __restrict__ world_first,
+                       const FleetPin* __restrict__ fpin, const TrafficTrackDev* __restrict__ tracks, const double* __restrict__ cum,
+                       const GlobalPoint2D* __restrict__ pts, const double* __restrict__ s_in, const double* __restrict__ v_in,
+                       double* __restrict__ s_out, double* __restrict__ v_out, const SceneIn* __restrict__ in, const int32_t* __restrict__ flags,
+                       ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const int lane = threadIdx.x & 63;
+    const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * kWorldActors + (threadIdx.x >> 6));
+    if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
+    const TrafficPin pin = actors[a];
+    const TrafficTrackDev tk = tracks[pin.track];
+    const bool closed = tk.closed != 0;
+    const int n = tk.n_points, nseg = closed ? n : n - 1;
+    const double* c = cum + tk.cum_off;
+    const double L = c[nseg];
+    const double s = s_in[a];
+    const TrafficRef ref = refs[a];
+    const int p0 = world_first[ref.scene], p1 = world_first[ref.scene + 1];
+    if (!(pin.speed > 0)) {                             // parked or reversing: §4h's step, v = speed
+        const double s1 = traffic_wrap(s + pin.speed * dt, L, closed);
+        if (lane == 0) { s_out[a] = s1; v_out[a] = pin.speed; }
+        world_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, lane, p0, p1, fpin, obs, mot);
+        return;
+    }
+    const double v = v_in[a];
+    // 1. the actor ahead: the smallest (g, b) over the (world, track) group
+    double bg = 0; int bi = -1;
+    for (int m = group_first[ref.group] + lane, m1 = group_first[ref.group + 1]; m < m1; m += 64) {
+        const int b = members[m];
+        if (b == a) continue;
+        double g = s_in[b] - s;
+        bool ok = true;
+        if (closed) { if (g < 0 || (g == 0 && b > a)) g = g + L; }
+        else ok = g > 0 || (g == 0 && b < a);
+        if (ok && g <= tf.look && (bi < 0 || g < bg)) { bg = g; bi = b; }       // (b rises within a lane: ties keep the lower index; a NaN compares false)
+    }
+    wave_first_min(bg, bi);
+    // 2. the egos of the world: every lane its own, 64 per pass, over the same window
+    const int i0 = traffic_locate(c, nseg, s);
+    const int kmax = closed ? n : n - 1 - i0;
+    const double lat2 = tf.lateral * tf.lateral;
+    double eg = 0; int ee = -1;
+    for (int e0 = p0; e0 < p1; e0 += 64) {
+        const int e = e0 + lane;
+        const bool mine = e < p1;
+        double x = 0, y = 0;
+        if (mine) { x = in[e].loc.globalpoint.x; y = in[e].loc.globalpoint.y; }
+        double md = 0, mg = 0; bool have = false;
+        for (int k = 1; k <= kmax; k++) {               // (wave-uniform: g depends on the vehicle alone)
+            const int j = i0 + k;
+            const int pj = j <= n - 1 ? j : j - n;
+            const double g = j <= n - 1 ? c[j] - s : (L - s) + c[pj];
+            if (!(g <= tf.look)) break;                 // (the gaps never decrease with k: the vertices that take part are a prefix)
+            const GlobalPoint2D P = pts[tk.point_off + pj];
+            const double ex = P.x - x, ey = P.y - y;
+            const double d2 = ex * ex + ey * ey;
+            if ((!have && d2 == d2) || d2 < md) { md = d2; mg = g; have = true; }      // (k rises: the first minimum; a NaN is never the minimum)
+        }
+        if (mine && have && md <= lat2 && (ee < 0 || mg < eg)) { eg = mg; ee = e; }      // (e rises within a lane: ties keep the lower scene)
+    }
+    wave_first_min(eg, ee);
+    // 3. the leader (wave-uniform from here on)
+    bool lead = false; double g = 0, vl = 0, rl = 0;
+    if (bi >= 0) { lead = true; g = bg; vl = v_in[bi]; rl = (double)actors[bi].radius; }
+    if (ee >= 0 && (!lead || eg <= g)) {
+        lead = true; g = eg; rl = half_w;
+        vl = flags[ee] != 0 ? 0.0 : in[ee].loc.velocity / 3.6;
+    }
+    // 4. the acceleration
+    const double r = v / pin.speed, r2 = r * r, fr = 1 - r2 * r2;
+    double acc;
+    if (!lead) acc = tf.max_acc * fr;
+    else {
+        double net = g - (double)pin.radius - rl;
+        if (!(net > tf.min_net)) net = tf.min_net;
+        const double dv = v - vl;
+        const double c2 = 2 * sqrt(tf.max_acc * tf.comfort_dec);
+        double dyn = v * tf.headway + (v * dv) / c2;
+        if (!(dyn > 0)) dyn = 0;
+        const double star = tf.gap + dyn, q = star / net;
+        acc = tf.max_acc * (fr - q * q);
+    }
+    if (!(acc >= -tf.max_dec)) acc = -tf.max_dec;       // (a NaN brakes)
+    // 5. integrate and place
+    double v1 = v + acc * dt;
+    if (!(v1 > 0)) v1 = 0;
+    const double s1 = traffic_wrap(s + 0.5 * (v + v1) * dt, L, closed);
+    if (lane == 0) { s_out[a] = s1; v_out[a] = v1; }
+    world_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, lane, p0, p1, fpin, obs, mot);
 }
 
 }  // namespace dmpp

@@ -15,6 +15,9 @@
 // With --route --traffic --react the vehicle starts 15 m BEHIND its ego at a desired 8 m/s instead and the car-following law is on
 // (pp_set_traffic_follow with the default model): it closes up, finds the ego as its leader and keeps a gap; the host
 // prints the smallest ego-actor clearance of the run and the vehicles' mean speed at the end.
+// With --route --fleet --traffic --shared (and --react for following) the 64 egos form 8 worlds of 8 - each world a platoon on one lane,
+// 12 m apart, 4 peer slots per scene - and there is ONE vehicle per world in the place of one per scene (pp_set_world_traffic,
+// DESIGN.md §4j): it is written into slot 0 of all 8 member scenes and follows the nearest of the world's 8 egos.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -27,8 +30,9 @@
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react)
+static int run_route(bool follow, bool traffic, bool react, bool shared)
 {
+    const int W = 8, K = shared ? 4 : 0, stride = 1 + K;      // --shared: worlds of W scenes, K peer slots behind every scene's one own entry
     const int n = 64, ticks = 1200, P = 260, JP = 40, n_lanes = 2;
     const double kPi = 3.14159265358979323846, step = 0.5, w = 3.75;
     const double kr = (70.0 * kPi / 180.0) / ((P - 1) * step), kj = (20.0 * kPi / 180.0) / ((JP + 1) * step);
@@ -60,7 +64,7 @@ static int run_route(bool follow, bool traffic, bool react)
 
     PlannerConfig cfg; pp_default_config(&cfg, follow ? 256 : 128, follow ? 256 : 128);
     if (!follow) cfg.grid_stage = 0;                  // (a grid that does not follow the ego bounds the run: DESIGN.md §4c 6., §4g)
-    PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = traffic ? n : 1; caps.max_lane_pts_total = (int32_t)pts.size(); caps.max_ref_pts_total = (int32_t)jpts.size();
+    PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = traffic ? n * stride : 1; caps.max_lane_pts_total = (int32_t)pts.size(); caps.max_ref_pts_total = (int32_t)jpts.size();
     std::vector<SceneIn> in(n); std::vector<SceneState> st(n);
     {   // generated records for everything the map does not decide (DecisionOut, state), then the egos onto the ring
         std::vector<GlobalPoint3D> gl((size_t)n * 3 * PP_GEN_LANE_PTS); std::vector<uint8_t> ga(gl.size()); std::vector<GlobalPoint2D> gr((size_t)n * PP_GEN_REF_PTS);
@@ -69,7 +73,8 @@ static int run_route(bool follow, bool traffic, bool react)
     }
     std::vector<RouteLeg> legs; std::vector<int32_t> route_first = { 0 };
     for (int s = 0; s < n; s++) {
-        const int road = s % 4 + 1, lane = (s / 4) % n_lanes + 1, id = 100 + (s * 7) % 80, n_legs = 3 + s % 4;
+        int road = s % 4 + 1, lane = (s / 4) % n_lanes + 1, id = 100 + (s * 7) % 80; const int n_legs = 3 + s % 4;
+        if (shared) { const int w = s / W; road = w % 4 + 1; lane = (w / 4) % n_lanes + 1; id = 60 + 24 * (s % W); }      // a platoon per world: member 0 at the rear
         const GlobalPoint3D& q = pts[(size_t)lanes[(size_t)first[(size_t)road - 1] + lane - 1].point_off + id];
         SceneIn& e = in[(size_t)s];
         e.loc.globalpoint = q; e.loc.velocity = 20; e.loc.pos = 0; e.loc.road_num = road; e.loc.lane_num = lane; e.loc.path_num = 0;
@@ -84,7 +89,7 @@ static int run_route(bool follow, bool traffic, bool react)
     }
     // --traffic: one closed track per lane number - the lane's points on road 1, its junction polyline, road 2 ... - and one vehicle
     // per ego, 20 m ahead of it along that track, in the ego's single obstacle entry
-    std::vector<TrafficTrack> tracks; std::vector<GlobalPoint2D> tpts; std::vector<TrafficActor> actors; std::vector<ObPoint> obs((size_t)n);
+    std::vector<TrafficTrack> tracks; std::vector<GlobalPoint2D> tpts; std::vector<TrafficActor> actors; std::vector<ObPoint> obs((size_t)n * stride, ObPoint{ -500, -500, 0, 0.5f });
     if (traffic) {
         const int per_road = P + JP;
         for (int l = 0; l < n_lanes; l++) {
@@ -102,8 +107,13 @@ static int run_route(bool follow, bool traffic, bool react)
             const GlobalPoint2D* T = tpts.data() + tracks[(size_t)lane - 1].point_off;
             double here = 0;                              // arc length of the ego's lane point along its track
             for (int i = 0; i < at; i++) here += std::sqrt((T[i + 1].x - T[i].x) * (T[i + 1].x - T[i].x) + (T[i + 1].y - T[i].y) * (T[i + 1].y - T[i].y));
-            e.obs_off = s; e.obs_n = 1;
-            obs[(size_t)s] = ObPoint{ 0, 0, 0, 0.9f };    // (placed by pp_set_traffic)
+            e.obs_off = s * stride; e.obs_n = 1;
+            obs[(size_t)s * stride] = ObPoint{ 0, 0, 0, 0.9f };    // (placed by pp_set_traffic / pp_set_world_traffic)
+            if (shared) {                                 // one vehicle per world: behind its rear ego (member 0), or ahead of its front ego (member W - 1)
+                if (react && s % W == 0) actors.push_back(TrafficActor{ here - 15.0, 8.0, s / W, 0, lane - 1, 1, 0.9f, 0 });
+                if (!react && s % W == W - 1) actors.push_back(TrafficActor{ here + 20.0, 1.5, s / W, 0, lane - 1, 1, 0.9f, 0 });
+                continue;
+            }
             if (react) actors.push_back(TrafficActor{ here - 15.0, 8.0, s, 0, lane - 1, 1, 0.9f, 0 });      // (a closed track: a negative s0 wraps)
             else actors.push_back(TrafficActor{ here + 20.0, 1.5, s, 0, lane - 1, 1, 0.9f, 0 });
         }
@@ -111,13 +121,19 @@ static int run_route(bool follow, bool traffic, bool react)
     pp_handle h = nullptr;
     CHECK(pp_create(&cfg, 0, &caps, &h));
     CHECK(pp_set_map(h, &map));
-    CHECK(pp_set_egos(h, n, in.data(), traffic ? obs.data() : nullptr, nullptr, traffic ? n : 0));
+    CHECK(pp_set_egos(h, n, in.data(), traffic ? obs.data() : nullptr, nullptr, traffic ? n * stride : 0));
     CHECK(pp_set_state(h, st.data(), n));
     RouteModel rm; CHECK(pp_default_route_model(&rm));
     CHECK(pp_set_route(h, (int)legs.size(), legs.data(), route_first.data(), &rm));
     if (follow) { GridFollow gf; pp_default_grid_follow(&gf); CHECK(pp_set_grid_follow(h, &gf)); }
     EgoModel model; pp_default_ego_model(&model);
     if (traffic) {
+        if (shared) {
+            std::vector<int32_t> world_first; for (int s = 0; s <= n; s += W) world_first.push_back(s);
+            FleetModel fm; pp_default_fleet_model(&fm); fm.max_peers = K;
+            CHECK(pp_set_fleet(h, n / W, world_first.data(), &fm));
+            CHECK(pp_set_world_traffic(h, (int)tracks.size(), tracks.data(), tpts.data(), (int)tpts.size(), (int)actors.size(), actors.data()));
+        } else
         CHECK(pp_set_traffic(h, (int)tracks.size(), tracks.data(), tpts.data(), (int)tpts.size(), n, actors.data()));
         if (react) { TrafficFollow tf; pp_default_traffic_follow(&tf); CHECK(pp_set_traffic_follow(h, &tf)); }
         CHECK(pp_score_begin(h, model.dt));
@@ -126,25 +142,27 @@ static int run_route(bool follow, bool traffic, bool react)
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
     if (traffic) {
-        std::vector<RolloutScore> score(n); std::vector<double> arc(n);
+        const int nv = (int)actors.size();
+        std::vector<RolloutScore> score(n); std::vector<double> arc((size_t)nv);
         CHECK(pp_get_rollout_score(h, score.data(), n));
-        CHECK(pp_get_traffic_state(h, arc.data(), n));
+        CHECK(pp_get_traffic_state(h, arc.data(), nv));
+        if (shared) std::printf("shared: %d worlds of %d egos, one vehicle per world in slot 0 of every member scene (%d records in the place of %d)\n", n / W, W, nv, n);
         int saw = 0, hit = 0; double worst = INFINITY, dist = 0, driven = 0;
         for (int s = 0; s < n; s++) {
             const RolloutScore& r = score[(size_t)s];
             saw += r.n_ob_flag > 0; hit += r.n_collision_ticks > 0; dist += r.dist; if (r.min_clearance < worst) worst = r.min_clearance;
-            driven += arc[(size_t)s];
         }
+        for (int a = 0; a < nv; a++) driven += arc[(size_t)a];
         if (react) {
-            std::vector<double> v(n); double vsum = 0;
-            CHECK(pp_get_traffic_speed(h, v.data(), n));
-            for (int s = 0; s < n; s++) vsum += v[(size_t)s];
+            std::vector<double> v((size_t)nv); double vsum = 0;
+            CHECK(pp_get_traffic_speed(h, v.data(), nv));
+            for (int a = 0; a < nv; a++) vsum += v[(size_t)a];
             std::printf("react: %d vehicles that want %.1f m/s, 15 m behind their egos, following on: %d egos were touched, smallest ego-actor clearance of the run %.2f m, "
-                        "mean distance travelled by the egos %.1f m, mean vehicle speed now %.2f m/s\n", n, actors[0].speed, hit, worst, dist / n, vsum / n);
+                        "mean distance travelled by the egos %.1f m, mean vehicle speed now %.2f m/s\n", nv, actors[0].speed, hit, worst, dist / n, vsum / nv);
         } else
         std::printf("traffic: %d vehicles at %.1f m/s, 20 m ahead of their egos: %d of %d egos saw theirs (ob_flag), %d touched it, worst clearance %.2f m, "
                     "mean distance travelled %.1f m (a vehicle covers %.1f m; mean arc length now %.1f m)\n",
-                    n, actors[0].speed, saw, n, hit, worst, dist / n, actors[0].speed * model.dt * ticks, driven / n);
+                    nv, actors[0].speed, saw, n, hit, worst, dist / n, actors[0].speed * model.dt * ticks, driven / nv);
     }
     std::vector<int32_t> flags(n); std::vector<SceneIn> end(n);
     CHECK(pp_get_ego_flags(h, flags.data(), n));
@@ -167,18 +185,20 @@ static int run_route(bool follow, bool traffic, bool react)
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
         else if (std::strcmp(argv[a], "--follow") == 0) follow = true;
         else if (std::strcmp(argv[a], "--traffic") == 0) traffic = true;
         else if (std::strcmp(argv[a], "--react") == 0) react = true;
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--traffic [--react]]] [--follow]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--shared") == 0) shared = true;
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
-    if (route) return run_route(follow, traffic, react);
+    if (shared && !(route && fleet && traffic)) { std::fprintf(stderr, "--shared puts one vehicle into every world: use it with --route --fleet --traffic\n"); return 2; }
+    if (route) return run_route(follow, traffic, react, shared);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

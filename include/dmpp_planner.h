@@ -324,6 +324,34 @@ int  pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf);
  * traffic or following is off. */
 int  pp_get_traffic_speed(pp_handle h, double* v, int n);
 
+/* ---- world traffic: one vehicle per world, seen by and seeing every ego of it --------------------------------------
+ * pp_set_traffic gives a vehicle to ONE scene: a world of W scenes (pp_set_fleet) has to list it W times, and with following on
+ * every copy sees only its own scene's ego, so the copies drift apart.  pp_set_world_traffic takes the same records and reads two
+ * fields differently:
+ *     TrafficActor.scene is a WORLD index of the fleet in force, 0 <= scene < n_worlds;
+ *     TrafficActor.slot  indexes the own entries of EVERY member scene m of that world: 0 <= slot < n_own[m] (the fleet's pinned
+ *                        counts), and the vehicle's pool entry in member m is pin[m].obs_off + slot.
+ * There is one record and one (s, v) state per vehicle.  k_move_world_traffic / k_follow_world_traffic (one wave per vehicle) take
+ * the places of k_move_traffic / k_follow_traffic: the same ObPoint bytes - and a zero ObMotion when the set carries a motion pool -
+ * go into that entry of every member scene, and with following on (pp_set_traffic_follow, either order) the ego leader is the
+ * nearest of ALL egos of the world: the smallest (g_e, e), a tie in the gap going to the lower scene index; a flagged ego leads
+ * with speed 0.  Actor leaders are the vehicles of the same world on the same track.  Every arithmetic step is specified (§4j): a
+ * numpy restatement gives the same bytes, and with worlds of one scene each the bytes are those of pp_set_traffic.
+ * ONE TRAFFIC SET PER HANDLE: per scene or per world.  Either set call replaces the whole traffic; n_actors = 0 through either call
+ * switches it off (the entries keep the last pose written).  pp_get_traffic_state / pp_get_traffic_speed return one value per
+ * vehicle; pp_set_traffic_follow and pp_update_async (the vehicles placed at the current s in every member, no step; the pool must
+ * reach the last pinned entry of any member) work as for scene traffic.
+ * REQUIRES A FLEET: the worlds and the pinned slices are the fleet's (max_peers = 0 is a legal fleet for callers who want shared
+ * traffic without peer obstacles).  Every SUCCESSFUL later pp_set_fleet switches world traffic off, n_worlds = 0 included - the
+ * worlds it was pinned to are gone -; a refused pp_set_fleet changes nothing; pp_set_scenes / pp_set_egos / pp_set_n_scenes
+ * switch it off as they do scene traffic and the fleet.  (Scene traffic keeps its relation to pp_set_fleet: either order.)
+ * Checked on the host, with nothing changed on failure.  PP_ERR_STATE: no resident scenes, an update staged for the next tick, no
+ * fleet.  PP_ERR_ARG: everything pp_set_traffic refuses in tracks, points, s0, speed and radius; a world out of range; a slot that
+ * is not an own entry of some member scene (the message names the first such scene); two actors on one (world, slot).  One host
+ * wait.  A handle that never calls pp_set_world_traffic allocates and launches none of this. */
+int  pp_set_world_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points,
+                          int n_actors, const TrafficActor* actors);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that

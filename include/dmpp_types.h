@@ -330,6 +330,7 @@ typedef struct TrafficTrack {
 typedef struct TrafficActor {
     double  s0, speed;             /* metres along the track at set time; m/s (negative: backwards)                        */
     int32_t scene, slot;           /* slot: index inside the scene's OWN obstacle entries (never a peer slot)              */
+                                   /* (pp_set_world_traffic, §4j: scene = a WORLD of the fleet, slot = own entry of every member) */
     int32_t track, type;           /* type: ObPoint.type of the slot (nothing on the device reads it)                      */
     float   radius;                /* ObPoint.radius of the slot (metres), finite and >= 0                                 */
     int32_t _pad;
