@@ -160,24 +160,25 @@ struct FleetState {
 // pp_advance_async launches k_advance_route in the place of k_advance_egos
 struct RouteState { bool on = false; RouteModel rm = { 0, 0 }; DevBuf<RouteLeg> d_legs; DevBuf<int32_t> d_first; };
 // lane traffic (first pp_set_traffic): the actors with their pinned pool entries, the tracks, the compact point
-// array and the cumulative-length table; d_s: the arc length of every actor, SINGLE-COPY like the rollout flags (the advances
-// that step it are serial on the upload stream).  end: the largest pinned pool entry + 1.
+// array and the cumulative-length table; d_s[cur]: the arc length of every actor, SINGLE-COPY like the rollout flags (the advances
+// that step it are serial on the upload stream; d_s[1] exists only while following is on, and cur is 0 without it).  end: the
+// largest pinned pool entry + 1.
 // world (pp_set_world_traffic): one vehicle per WORLD of the fleet in force - d_pin[a].pool is then the SLOT, d_world
 // (allocated by that call only) every vehicle's world, scene_of the worlds, and the pins are the fleet's FleetPin table
 struct TrafficState {
     bool on = false, world = false; int actors = 0, end = 0;
     DevBuf<int32_t> d_world;
-    DevBuf<dmpp::TrafficPin> d_pin; DevBuf<dmpp::TrafficTrackDev> d_tracks; DevBuf<double> d_cum; DevBuf<GlobalPoint2D> d_pts; DevBuf<double> d_s;
+    DevBuf<dmpp::TrafficPin> d_pin; DevBuf<dmpp::TrafficTrackDev> d_tracks; DevBuf<double> d_cum; DevBuf<GlobalPoint2D> d_pts; DevBuf<double> d_s[2];
     std::vector<int32_t> scene_of, track_of;      // host: what a later pp_set_traffic_follow groups the actors by
-    int cur = 0;                                  // which arc-length array is current: 0 d_s, 1 FollowState::d_s_alt (only while following)
+    int cur = 0;                                  // which arc-length array is current
 };
 // car-following traffic (pp_set_traffic_follow): the model, and - allocated only while traffic AND following are on -
-// the second arc-length array, the two speed arrays (the step is a Jacobi step: an advance reads pair traffic.cur and writes the
+// TrafficState::d_s[1], the two speed arrays (the step is a Jacobi step: an advance reads pair traffic.cur and writes the
 // other, then flips cur; the advances are serial on the upload stream) and the group tables: every actor's scene and group, the
 // first member of every group and the actor indices sorted by (scene, track, index)
 struct FollowState {
     bool on = false; TrafficFollow tf = {};
-    DevBuf<double> d_s_alt, d_v[2]; DevBuf<dmpp::TrafficRef> d_ref; DevBuf<int32_t> d_first, d_members;
+    DevBuf<double> d_v[2]; DevBuf<dmpp::TrafficRef> d_ref; DevBuf<int32_t> d_first, d_members;
 };
 
 }  // namespace
@@ -337,8 +338,8 @@ void couple_fleet(pp_planner* h, hipStream_t st, SceneIn* d_in, ObPoint* d_obs, 
                        h->fleet.d_pin, d_in, d_obs, d_mot);
 }
 
-// the arc-length array `which` of the traffic (1 exists only while following is on)
-double* traffic_s(pp_planner* h, int which) { return which ? h->follow.d_s_alt.get() : h->traffic.d_s.get(); }
+// every wave-per-actor traffic kernel runs kTrafficWaves actors per block
+unsigned traffic_wave_blocks(int n) { return (unsigned)((n + dmpp::kTrafficWaves - 1) / dmpp::kTrafficWaves); }
 
 // Lane traffic of one input set on the stream that stages it: behind the copies of its obstacle pool, in front of
 // k_couple_fleet (the two write disjoint entries: traffic a scene's own, the fleet the peer slots behind them) and of
@@ -347,13 +348,13 @@ void move_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot
 {
     const int n = h->traffic.actors;
     if (h->traffic.world) {               // one vehicle per world, written into every member scene (§4j)
-        hipLaunchKernelGGL(dmpp::k_move_world_traffic, dim3((unsigned)((n + dmpp::kWorldActors - 1) / dmpp::kWorldActors)), dim3(dmpp::kBlock), 0, st,
+        hipLaunchKernelGGL(dmpp::k_move_world_traffic, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
                            n, step, h->traffic.d_pin, h->traffic.d_world, h->fleet.d_world_first, h->fleet.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts,
-                           traffic_s(h, h->traffic.cur), d_obs, d_mot);
+                           h->traffic.d_s[h->traffic.cur], d_obs, d_mot);
         return;
     }
     hipLaunchKernelGGL(dmpp::k_move_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
-                       n, step, h->traffic.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, h->traffic.cur), d_obs, d_mot);
+                       n, step, h->traffic.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[h->traffic.cur], d_obs, d_mot);
 }
 
 // Car-following traffic of the input set an advance stages, in the place of move_traffic: behind k_advance_*, whose
@@ -363,14 +364,14 @@ int follow_traffic(pp_planner* h, hipStream_t st, const SceneIn* d_in, ObPoint* 
 {
     const int n = h->traffic.actors, cur = h->traffic.cur;
     if (h->traffic.world)                 // the leader is the nearest of all the world's egos (§4j)
-        hipLaunchKernelGGL(dmpp::k_follow_world_traffic, dim3((unsigned)((n + dmpp::kWorldActors - 1) / dmpp::kWorldActors)), dim3(dmpp::kBlock), 0, st,
+        hipLaunchKernelGGL(dmpp::k_follow_world_traffic, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
                            n, dt, h->follow.tf, 0.5 * h->cfg.Vehicle_Width, h->traffic.d_pin, h->follow.d_ref, h->follow.d_first, h->follow.d_members,
-                           h->fleet.d_world_first, h->fleet.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, cur), h->follow.d_v[cur],
-                           traffic_s(h, cur ^ 1), h->follow.d_v[cur ^ 1], d_in, h->rollout.d_flags, d_obs, d_mot);
+                           h->fleet.d_world_first, h->fleet.d_pin, h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], h->follow.d_v[cur],
+                           h->traffic.d_s[cur ^ 1], h->follow.d_v[cur ^ 1], d_in, h->rollout.d_flags, d_obs, d_mot);
     else
-    hipLaunchKernelGGL(dmpp::k_follow_traffic, dim3((unsigned)((n + dmpp::kFollowActors - 1) / dmpp::kFollowActors)), dim3(dmpp::kBlock), 0, st,
+    hipLaunchKernelGGL(dmpp::k_follow_traffic, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
                        n, dt, h->follow.tf, 0.5 * h->cfg.Vehicle_Width, h->traffic.d_pin, h->follow.d_ref, h->follow.d_first, h->follow.d_members,
-                       h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, traffic_s(h, cur), h->follow.d_v[cur], traffic_s(h, cur ^ 1), h->follow.d_v[cur ^ 1],
+                       h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], h->follow.d_v[cur], h->traffic.d_s[cur ^ 1], h->follow.d_v[cur ^ 1],
                        d_in, h->rollout.d_flags, d_obs, d_mot);
     HIP_TRY(hipGetLastError());
     h->traffic.cur = cur ^ 1;
@@ -398,7 +399,7 @@ int build_follow(pp_planner* h)
     }
     first.push_back((int32_t)n);
     int rc;
-    if ((rc = h->follow.d_s_alt.reserve(n)) || (rc = h->follow.d_v[0].reserve(n)) || (rc = h->follow.d_v[1].reserve(n)) || (rc = h->follow.d_ref.reserve(n)) ||
+    if ((rc = h->traffic.d_s[1].reserve(n)) || (rc = h->follow.d_v[0].reserve(n)) || (rc = h->follow.d_v[1].reserve(n)) || (rc = h->follow.d_ref.reserve(n)) ||
         (rc = h->follow.d_first.reserve(first.size())) || (rc = h->follow.d_members.reserve(n))) return rc;
     HIP_TRY(hipMemcpyAsync(h->follow.d_ref, ref.data(), n * sizeof(dmpp::TrafficRef), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->follow.d_first, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
@@ -1800,28 +1801,20 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
         if (world && (A.scene < 0 || A.scene >= h->fleet.n_worlds)) return fail(PP_ERR_ARG, who + " names a world that the fleet does not have");
         if (!world && (A.scene < 0 || A.scene >= n)) return fail(PP_ERR_ARG, who + " names a scene that is not resident");
         if (A.track < 0 || A.track >= n_tracks) return fail(PP_ERR_ARG, who + " names a track that was not given");
-        if (world) {                                      // the slot must be an own entry of every member scene; the pin keeps the slot
-            for (int m = world_first[(size_t)A.scene]; m < world_first[(size_t)A.scene + 1]; m++) {
-                const dmpp::FleetPin& O = own[(size_t)m];
-                const long long pool = (long long)O.obs_off + A.slot;
-                if (A.slot < 0 || A.slot >= O.n_own || O.obs_off < 0 || pool >= (long long)h->caps.max_obs_total)
-                    return fail(PP_ERR_ARG, who + ": slot " + std::to_string(A.slot) + " is not one of the " + std::to_string(std::max(O.n_own, 0)) + " own obstacle entries of scene " + std::to_string(m) +
-                                            " (world " + std::to_string(A.scene) + ")");
-                end_max = std::max(end_max, pool + 1);
-            }
-            pin[(size_t)a] = { A.speed, A.slot, A.track, A.type, A.radius };
-            scene_of[(size_t)a] = A.scene; track_of[(size_t)a] = A.track;
-            s0[(size_t)a] = A.s0; taken[(size_t)a] = ((long long)A.scene << 32) | (long long)A.slot;
-            continue;
+        // the slot must be an own entry of the scene or, per world, of every member scene; the pin keeps the entry or the slot
+        const int m0 = world ? world_first[(size_t)A.scene] : A.scene, m1 = world ? world_first[(size_t)A.scene + 1] : A.scene + 1;
+        long long pool = 0;
+        for (int m = m0; m < m1; m++) {
+            const dmpp::FleetPin& O = own[(size_t)m];
+            pool = (long long)O.obs_off + A.slot;
+            if (A.slot < 0 || A.slot >= O.n_own || O.obs_off < 0 || pool >= (long long)h->caps.max_obs_total)
+                return fail(PP_ERR_ARG, who + ": slot " + std::to_string(A.slot) + " is not one of the " + std::to_string(std::max(O.n_own, 0)) + " own obstacle entries of scene " + std::to_string(m) +
+                                        (world ? " (world " + std::to_string(A.scene) + ")" : ""));
+            end_max = std::max(end_max, pool + 1);
         }
-        const dmpp::FleetPin& O = own[(size_t)A.scene];
-        const long long pool = (long long)O.obs_off + A.slot;
-        if (A.slot < 0 || A.slot >= O.n_own || O.obs_off < 0 || pool >= (long long)h->caps.max_obs_total)
-            return fail(PP_ERR_ARG, who + ": slot " + std::to_string(A.slot) + " is not one of the " + std::to_string(std::max(O.n_own, 0)) + " own obstacle entries of scene " + std::to_string(A.scene));
-        pin[(size_t)a] = { A.speed, (int32_t)pool, A.track, A.type, A.radius };
+        pin[(size_t)a] = { A.speed, world ? A.slot : (int32_t)pool, A.track, A.type, A.radius };
         scene_of[(size_t)a] = A.scene; track_of[(size_t)a] = A.track;
         s0[(size_t)a] = A.s0; taken[(size_t)a] = ((long long)A.scene << 32) | (long long)A.slot;
-        end_max = std::max(end_max, pool + 1);
     }
     std::sort(taken.begin(), taken.end());
     for (size_t k = 1; k < taken.size(); k++)
@@ -1831,12 +1824,12 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     HIP_TRY(hipStreamSynchronize(h->stream));
     // room first.  An allocation that fails leaves its own array as it was, but may follow one that replaced another: the old
     // traffic then goes off rather than run on half a set
-    if ((rc = h->traffic.d_pin.reserve((size_t)n_actors)) || (rc = h->traffic.d_s.reserve((size_t)n_actors)) || (rc = h->traffic.d_tracks.reserve((size_t)n_tracks)) ||
+    if ((rc = h->traffic.d_pin.reserve((size_t)n_actors)) || (rc = h->traffic.d_s[0].reserve((size_t)n_actors)) || (rc = h->traffic.d_tracks.reserve((size_t)n_tracks)) ||
         (rc = h->traffic.d_cum.reserve(cum.size())) || (rc = h->traffic.d_pts.reserve(pts.size())) ||
         (world && (rc = h->traffic.d_world.reserve((size_t)n_actors)))) { h->traffic.on = false; return rc; }
     h->traffic.on = false;                                // (until everything below has landed: a device error leaves traffic off, never half a set)
     HIP_TRY(hipMemcpyAsync(h->traffic.d_pin, pin.data(), (size_t)n_actors * sizeof(dmpp::TrafficPin), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->traffic.d_s, s0.data(), (size_t)n_actors * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->traffic.d_s[0], s0.data(), (size_t)n_actors * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_tracks, tdev.data(), (size_t)n_tracks * sizeof(dmpp::TrafficTrackDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_cum, cum.data(), cum.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_pts, pts.data(), pts.size() * sizeof(GlobalPoint2D), hipMemcpyHostToDevice, h->stream));
@@ -1871,7 +1864,7 @@ int pp_get_traffic_state(pp_handle h, double* s, int n)
     HIP_TRY(hipSetDevice(h->device));
     if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
     if (h->in_staged >= 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));      // (a staged update rewrites the same values)
-    return fetch(h, s, traffic_s(h, h->traffic.cur), (size_t)n * sizeof(double));
+    return fetch(h, s, h->traffic.d_s[h->traffic.cur], (size_t)n * sizeof(double));
 }
 
 // Car-following traffic: host checks first; the model is a kernel argument of the next advance.
@@ -1903,7 +1896,7 @@ int pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf)
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (!tf) {                                            // off: the arc lengths go back to the one array of §4h
         if (h->follow.on && h->traffic.cur == 1) {
-            HIP_TRY(hipMemcpyAsync(h->traffic.d_s, h->follow.d_s_alt, (size_t)h->traffic.actors * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->traffic.d_s[0], h->traffic.d_s[1], (size_t)h->traffic.actors * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
         }
         h->traffic.cur = 0; h->follow.on = false;

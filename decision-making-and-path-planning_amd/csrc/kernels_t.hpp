@@ -35,73 +35,30 @@ __device__ inline double traffic_wrap(double s, double L, bool closed)
     return s;
 }
 
-// step: 0 (pp_set_traffic, pp_update_async: the actors are placed where they are) or EgoModel.dt (pp_advance_async).
-// mot: nullptr when the set carries no motion pool.
-__global__ void __launch_bounds__(kBlock)
-k_move_traffic(int n_actors, double step, const TrafficPin* __restrict__ actors, const TrafficTrackDev* __restrict__ tracks,
-               const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts, double* __restrict__ s_arr,
-               ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+// ---- the steps every traffic kernel shares, each written once (the kernels below are thin over them)
+
+// a track as one thread or wave sees it: the header, its cumulative lengths c[0 .. nseg], nseg (= n, closed, or n - 1) and L = c[nseg]
+struct TrackView { TrafficTrackDev tk; const double* c; int n, nseg; bool closed; double L; };
+
+__device__ __forceinline__ TrackView traffic_view(const TrafficTrackDev* __restrict__ tracks, const double* __restrict__ cum, int track)
 {
-    const int a = blockIdx.x * kBlock + threadIdx.x;
-    if (a >= n_actors) return;
-    const TrafficPin pin = actors[a];
-    const TrafficTrackDev tk = tracks[pin.track];
-    const bool closed = tk.closed != 0;
-    const int nseg = closed ? tk.n_points : tk.n_points - 1;
-    const double* c = cum + tk.cum_off;
-    const double L = c[nseg];
-    double s = s_arr[a];
-    if (step != 0) s = s + pin.speed * step;             // (the product is rounded, then the sum: no contraction)
-    s = traffic_wrap(s, L, closed);
-    s_arr[a] = s;
-    // the largest i in [0, nseg) with cum[i] <= s: cum is non-decreasing and cum[0] = 0 <= s
-    int lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (c[mid] <= s) lo = mid; else hi = mid;
-    }
-    const double c0 = c[lo], d = c[lo + 1] - c0;
-    const double t = d > 0 ? (s - c0) / d : 0.0;
-    const GlobalPoint2D P = pts[tk.point_off + lo];
-    const GlobalPoint2D Q = pts[tk.point_off + (lo + 1 < tk.n_points ? lo + 1 : 0)];      // (the closing segment ends on point 0)
-    ObPoint o;
-    o.x = P.x + t * (Q.x - P.x); o.y = P.y + t * (Q.y - P.y); o.type = pin.type; o.radius = pin.radius;
-    obs[pin.pool] = o;
-    if (mot) { ObMotion z; z.vx = 0; z.vy = 0; mot[pin.pool] = z; }
+    TrackView t;
+    t.tk = tracks[track];
+    t.closed = t.tk.closed != 0;
+    t.n = t.tk.n_points; t.nseg = t.closed ? t.n : t.n - 1;
+    t.c = cum + t.tk.cum_off;
+    t.L = t.c[t.nseg];
+    return t;
 }
 
-// ---- car-following traffic (DESIGN.md §4i): k_follow_traffic takes the place of k_move_traffic in an advance while following is on.
-//
-// One 64-lane wave per actor, four actors per 256-thread block, no LDS, no barrier, no scratch (the shape of k_couple_fleet).  The
-// step is a Jacobi step: the wave reads s and v of the arrays all actors had BEFORE the advance and writes the other pair, so the
-// waves of a launch do not depend on each other.  An actor with !(speed > 0) steps exactly as k_move_traffic does.  A follower
-//   1. strides the members of its (scene, track) group - actor indices sorted by (scene, track, index), built by the host - for
-//      the nearest actor ahead within `look`: a (gap, index) wave minimum that keeps the lower index (wave_first_min);
-//   2. strides the vertices ahead of its segment, 64 per pass, for the one nearest its scene's ego as k_advance_* has just staged
-//      it, stopping after the first pass in which no lane is within `look` (the gaps never decrease): a (d2, k) wave minimum;
-//   3. - 5. picks the leader, takes the intelligent-driver acceleration, integrates - wave-uniform - and lane 0 stores s, v, the
-//      ObPoint and, with a motion pool, a zero ObMotion.
-// Only + - * / sqrt floor on doubles, every one rounded once (-ffp-contract=off), and both orders are total: the result is specified
-// to the last bit.
-constexpr int kFollowActors = 4;       // actors (waves) per block of k_follow_traffic
-
-struct TrafficRef { int32_t scene, group; };       // what a follower needs beside its pin: its scene's records, its group's members
-
-// §4h 4. - 5. for k_follow_traffic (k_move_traffic keeps its own copy: its code and registers are those of §4h's record)
-__device__ __forceinline__ void traffic_place(const TrafficPin& pin, const TrafficTrackDev& tk, const double* __restrict__ c, int i,
-                                              double s, const GlobalPoint2D* __restrict__ pts, ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+// §4h 2. - 3.: the step of a scripted actor; step = 0 places it where it is (the product is rounded, then the sum: no contraction)
+__device__ __forceinline__ double traffic_step(const TrackView& t, double s, double speed, double step)
 {
-    const double c0 = c[i], d = c[i + 1] - c0;
-    const double t = d > 0 ? (s - c0) / d : 0.0;
-    const GlobalPoint2D P = pts[tk.point_off + i];
-    const GlobalPoint2D Q = pts[tk.point_off + (i + 1 < tk.n_points ? i + 1 : 0)];
-    ObPoint o;
-    o.x = P.x + t * (Q.x - P.x); o.y = P.y + t * (Q.y - P.y); o.type = pin.type; o.radius = pin.radius;
-    obs[pin.pool] = o;
-    if (mot) { ObMotion z; z.vx = 0; z.vy = 0; mot[pin.pool] = z; }
+    if (step != 0) s = s + speed * step;
+    return traffic_wrap(s, t.L, t.closed);
 }
 
-// §4h 4., first line: the largest i in [0, nseg) with cum[i] <= s
+// §4h 4., first line: the largest i in [0, nseg) with cum[i] <= s (cum is non-decreasing and cum[0] = 0 <= s)
 __device__ __forceinline__ int traffic_locate(const double* __restrict__ c, int nseg, double s)
 {
     int lo = 0, hi = nseg;
@@ -112,82 +69,74 @@ __device__ __forceinline__ int traffic_locate(const double* __restrict__ c, int 
     return lo;
 }
 
-// in: the SceneIn records being staged (read: loc.globalpoint, loc.velocity); flags: the ego flag words as the advance left them.
-// s_in / v_in and s_out / v_out are different arrays.  half_w = 0.5 * Vehicle_Width (rounded once, on the host: exact).
-__global__ void __launch_bounds__(kBlock)
-k_follow_traffic(int n_actors, double dt, TrafficFollow tf, double half_w, const TrafficPin* __restrict__ actors, const TrafficRef* __restrict__ refs,
-                 const int32_t* __restrict__ group_first, const int32_t* __restrict__ members, const TrafficTrackDev* __restrict__ tracks,
-                 const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts, const double* __restrict__ s_in, const double* __restrict__ v_in,
-                 double* __restrict__ s_out, double* __restrict__ v_out, const SceneIn* __restrict__ in, const int32_t* __restrict__ flags,
-                 ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+// §4h 4. - 5.: the obstacle of an actor at arc length s
+__device__ __forceinline__ ObPoint traffic_pose(const TrackView& t, const GlobalPoint2D* __restrict__ pts, const TrafficPin& pin, double s)
 {
-    const int lane = threadIdx.x & 63;
-    const int a = blockIdx.x * kFollowActors + (threadIdx.x >> 6);
-    if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
-    const TrafficPin pin = actors[a];
-    const TrafficTrackDev tk = tracks[pin.track];
-    const bool closed = tk.closed != 0;
-    const int n = tk.n_points, nseg = closed ? n : n - 1;
-    const double* c = cum + tk.cum_off;
-    const double L = c[nseg];
-    const double s = s_in[a];
-    if (!(pin.speed > 0)) {                             // parked or reversing: §4h's step, v = speed
-        if (lane == 0) {
-            const double s1 = traffic_wrap(s + pin.speed * dt, L, closed);
-            s_out[a] = s1; v_out[a] = pin.speed;
-            traffic_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, obs, mot);
-        }
-        return;
-    }
-    const double v = v_in[a];
-    const TrafficRef ref = refs[a];
-    // 1. the actor ahead: the smallest (g, b) over the group
+    const int i = traffic_locate(t.c, t.nseg, s);
+    const double c0 = t.c[i], d = t.c[i + 1] - c0;
+    const double u = d > 0 ? (s - c0) / d : 0.0;
+    const GlobalPoint2D P = pts[t.tk.point_off + i];
+    const GlobalPoint2D Q = pts[t.tk.point_off + (i + 1 < t.n ? i + 1 : 0)];             // (the closing segment ends on point 0)
+    ObPoint o;
+    o.x = P.x + u * (Q.x - P.x); o.y = P.y + u * (Q.y - P.y); o.type = pin.type; o.radius = pin.radius;
+    return o;
+}
+
+// pool entry e of the set being staged; mot: nullptr when the set carries no motion pool
+__device__ __forceinline__ void traffic_store(ObPoint* __restrict__ obs, ObMotion* __restrict__ mot, int e, const ObPoint& o)
+{
+    obs[e] = o;
+    if (mot) { ObMotion z; z.vx = 0; z.vy = 0; mot[e] = z; }
+}
+
+// §4j: the same entry of every member scene [p0, p1) of a world; the lanes stride the members
+__device__ __forceinline__ void world_store(ObPoint* __restrict__ obs, ObMotion* __restrict__ mot, const FleetPin* __restrict__ fpin, int lane, int p0, int p1,
+                                            int slot, const ObPoint& o)
+{
+    for (int m = p0 + lane; m < p1; m += 64)
+        traffic_store(obs, mot, fpin[m].obs_off + slot, o);      // (the slot is an own entry of every member: checked by pp_set_world_traffic)
+}
+
+// §4i 1. the actor ahead: the smallest (g, b) over the members of `group`, the same in every lane; i < 0: none
+struct TrafficAhead { double g; int i; };
+
+__device__ __forceinline__ TrafficAhead follow_actor_ahead(const TrackView& t, int group, int a, double s, double look, const int32_t* __restrict__ group_first,
+                                                           const int32_t* __restrict__ members, const double* __restrict__ s_in, int lane)
+{
     double bg = 0; int bi = -1;
-    for (int m = group_first[ref.group] + lane, m1 = group_first[ref.group + 1]; m < m1; m += 64) {
+    for (int m = group_first[group] + lane, m1 = group_first[group + 1]; m < m1; m += 64) {
         const int b = members[m];
         if (b == a) continue;
         double g = s_in[b] - s;
         bool ok = true;
-        if (closed) { if (g < 0 || (g == 0 && b > a)) g = g + L; }
+        if (t.closed) { if (g < 0 || (g == 0 && b > a)) g = g + t.L; }
         else ok = g > 0 || (g == 0 && b < a);
-        if (ok && g <= tf.look && (bi < 0 || g < bg)) { bg = g; bi = b; }       // (b rises within a lane: ties keep the lower index; a NaN compares false)
+        if (ok && g <= look && (bi < 0 || g < bg)) { bg = g; bi = b; }       // (b rises within a lane: ties keep the lower index; a NaN compares false)
     }
     wave_first_min(bg, bi);
-    // 2. the ego: the first nearest vertex of the window ahead
-    const double x = in[ref.scene].loc.globalpoint.x, y = in[ref.scene].loc.globalpoint.y;
-    const int i0 = traffic_locate(c, nseg, s);
-    const int kmax = closed ? n : n - 1 - i0;
-    auto gap_of = [&](int k, int& pj) {
-        const int j = i0 + k;
-        if (j <= n - 1) { pj = j; return c[j] - s; }
-        pj = j - n; return (L - s) + c[pj];
-    };
-    double ed = 0; int ek = -1;
-    for (int k0 = 1; k0 <= kmax; k0 += 64) {
-        const int k = k0 + lane;
-        bool within = false;
-        if (k <= kmax) {
-            int pj; const double g = gap_of(k, pj);
-            if (g <= tf.look) {
-                within = true;
-                const GlobalPoint2D P = pts[tk.point_off + pj];
-                const double ex = P.x - x, ey = P.y - y;
-                const double d2 = ex * ex + ey * ey;
-                if ((ek < 0 && d2 == d2) || d2 < ed) { ed = d2; ek = k; }       // (k rises within a lane; a NaN is never the minimum)
-            }
-        }
-        if (!__any(within)) break;
-    }
-    wave_first_min(ed, ek);
-    // 3. the leader (wave-uniform from here on)
+    return { bg, bi };
+}
+
+// §4i 2., the window: the gap g_k to the k-th vertex past segment i0 and that vertex's index pj (a closed track runs on over point 0)
+__device__ __forceinline__ double follow_window_gap(const TrackView& t, int i0, double s, int k, int& pj)
+{
+    const int j = i0 + k;
+    if (j <= t.n - 1) { pj = j; return t.c[j] - s; }
+    pj = j - t.n; return (t.L - s) + t.c[pj];
+}
+
+// §4i 3. - 5., wave-uniform: the leader - actor `ahead` (i < 0: none) or the ego of scene e at gap g_e (e < 0: none; the ego wins a
+// tie) -, the intelligent-driver acceleration and the integration; returns s1 and sets v1
+__device__ __forceinline__ double follow_drive(const TrackView& t, const TrafficFollow& tf, const TrafficPin& pin, double s, double v, double dt, double half_w,
+                                               TrafficAhead ahead, int e, double g_e, const TrafficPin* __restrict__ actors, const double* __restrict__ v_in,
+                                               const SceneIn* __restrict__ in, const int32_t* __restrict__ flags, double& v1)
+{
+    // 3. the leader
     bool lead = false; double g = 0, vl = 0, rl = 0;
-    if (bi >= 0) { lead = true; g = bg; vl = v_in[bi]; rl = (double)actors[bi].radius; }
-    if (ek >= 0 && ed <= tf.lateral * tf.lateral) {
-        int pj; const double ge = gap_of(ek, pj);
-        if (!lead || ge <= g) {
-            lead = true; g = ge; rl = half_w;
-            vl = flags[ref.scene] != 0 ? 0.0 : in[ref.scene].loc.velocity / 3.6;
-        }
+    if (ahead.i >= 0) { lead = true; g = ahead.g; vl = v_in[ahead.i]; rl = (double)actors[ahead.i].radius; }
+    if (e >= 0 && (!lead || g_e <= g)) {
+        lead = true; g = g_e; rl = half_w;
+        vl = flags[e] != 0 ? 0.0 : in[e].loc.velocity / 3.6;
     }
     // 4. the acceleration
     const double r = v / pin.speed, r2 = r * r, fr = 1 - r2 * r2;
@@ -204,13 +153,101 @@ k_follow_traffic(int n_actors, double dt, TrafficFollow tf, double half_w, const
         acc = tf.max_acc * (fr - q * q);
     }
     if (!(acc >= -tf.max_dec)) acc = -tf.max_dec;       // (a NaN brakes)
-    // 5. integrate and place
-    double v1 = v + acc * dt;
+    // 5. integrate
+    v1 = v + acc * dt;
     if (!(v1 > 0)) v1 = 0;
-    const double s1 = traffic_wrap(s + 0.5 * (v + v1) * dt, L, closed);
+    return traffic_wrap(s + 0.5 * (v + v1) * dt, t.L, t.closed);
+}
+
+// step: 0 (pp_set_traffic, pp_update_async: the actors are placed where they are) or EgoModel.dt (pp_advance_async).
+// mot: nullptr when the set carries no motion pool.
+__global__ void __launch_bounds__(kBlock)
+k_move_traffic(int n_actors, double step, const TrafficPin* __restrict__ actors, const TrafficTrackDev* __restrict__ tracks,
+               const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts, double* __restrict__ s_arr,
+               ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const int a = blockIdx.x * kBlock + threadIdx.x;
+    if (a >= n_actors) return;
+    const TrafficPin pin = actors[a];
+    const TrackView t = traffic_view(tracks, cum, pin.track);
+    const double s = traffic_step(t, s_arr[a], pin.speed, step);
+    s_arr[a] = s;
+    traffic_store(obs, mot, pin.pool, traffic_pose(t, pts, pin, s));
+}
+
+// ---- car-following traffic (DESIGN.md §4i): k_follow_traffic takes the place of k_move_traffic in an advance while following is on.
+//
+// One 64-lane wave per actor, four actors per 256-thread block, no LDS, no barrier, no scratch (the shape of k_couple_fleet).  The
+// step is a Jacobi step: the wave reads s and v of the arrays all actors had BEFORE the advance and writes the other pair, so the
+// waves of a launch do not depend on each other.  An actor with !(speed > 0) steps exactly as k_move_traffic does.  A follower
+//   1. strides the members of its (scene, track) group - actor indices sorted by (scene, track, index), built by the host - for
+//      the nearest actor ahead within `look` (follow_actor_ahead);
+//   2. strides the vertices ahead of its segment, 64 per pass, for the one nearest its scene's ego as k_advance_* has just staged
+//      it, stopping after the first pass in which no lane is within `look` (the gaps never decrease): a (d2, k) wave minimum;
+//   3. - 5. follow_drive, and lane 0 stores s, v, the ObPoint and, with a motion pool, a zero ObMotion.
+// Only + - * / sqrt floor on doubles, every one rounded once (-ffp-contract=off), and both orders are total: the result is specified
+// to the last bit.
+constexpr int kTrafficWaves = 4;       // actors or vehicles (waves) per block of k_follow_traffic and the two world-traffic kernels
+
+struct TrafficRef { int32_t scene, group; };       // what a follower needs beside its pin: its scene's records, its group's members
+
+// §4i 2. per scene: the first nearest vertex to the ego at (x, y) among the window's, the same in every lane; k < 0: none
+__device__ __forceinline__ int follow_scene_ego(const TrackView& t, const GlobalPoint2D* __restrict__ pts, int i0, int kmax, double s, double look,
+                                                double x, double y, int lane, double& ed)
+{
+    int ek = -1; ed = 0;
+    for (int k0 = 1; k0 <= kmax; k0 += 64) {
+        const int k = k0 + lane;
+        bool within = false;
+        if (k <= kmax) {
+            int pj; const double g = follow_window_gap(t, i0, s, k, pj);
+            if (g <= look) {
+                within = true;
+                const GlobalPoint2D P = pts[t.tk.point_off + pj];
+                const double ex = P.x - x, ey = P.y - y;
+                const double d2 = ex * ex + ey * ey;
+                if ((ek < 0 && d2 == d2) || d2 < ed) { ed = d2; ek = k; }       // (k rises within a lane; a NaN is never the minimum)
+            }
+        }
+        if (!__any(within)) break;
+    }
+    wave_first_min(ed, ek);
+    return ek;
+}
+
+// in: the SceneIn records being staged (read: loc.globalpoint, loc.velocity); flags: the ego flag words as the advance left them.
+// s_in / v_in and s_out / v_out are different arrays.  half_w = 0.5 * Vehicle_Width (rounded once, on the host: exact).
+__global__ void __launch_bounds__(kBlock)
+k_follow_traffic(int n_actors, double dt, TrafficFollow tf, double half_w, const TrafficPin* __restrict__ actors, const TrafficRef* __restrict__ refs,
+                 const int32_t* __restrict__ group_first, const int32_t* __restrict__ members, const TrafficTrackDev* __restrict__ tracks,
+                 const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts, const double* __restrict__ s_in, const double* __restrict__ v_in,
+                 double* __restrict__ s_out, double* __restrict__ v_out, const SceneIn* __restrict__ in, const int32_t* __restrict__ flags,
+                 ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const int lane = threadIdx.x & 63;
+    const int a = blockIdx.x * kTrafficWaves + (threadIdx.x >> 6);
+    if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
+    const TrafficPin pin = actors[a];
+    const TrackView t = traffic_view(tracks, cum, pin.track);
+    const double s = s_in[a];
+    double s1, v1;
+    if (!(pin.speed > 0)) {                             // parked or reversing: §4h's step, v = speed
+        s1 = traffic_step(t, s, pin.speed, dt); v1 = pin.speed;
+    } else {
+        const double v = v_in[a];
+        const TrafficRef ref = refs[a];
+        const TrafficAhead ahead = follow_actor_ahead(t, ref.group, a, s, tf.look, group_first, members, s_in, lane);
+        // 2. the ego: the first nearest vertex of the window ahead, a leader if it is within `lateral` of it
+        const int i0 = traffic_locate(t.c, t.nseg, s);
+        double ed;
+        const int ek = follow_scene_ego(t, pts, i0, t.closed ? t.n : t.n - 1 - i0, s, tf.look, in[ref.scene].loc.globalpoint.x, in[ref.scene].loc.globalpoint.y, lane, ed);
+        int e = -1, pj; double g_e = 0;
+        if (ek >= 0 && ed <= tf.lateral * tf.lateral) { e = ref.scene; g_e = follow_window_gap(t, i0, s, ek, pj); }
+        s1 = follow_drive(t, tf, pin, s, v, dt, half_w, ahead, e, g_e, actors, v_in, in, flags, v1);
+    }
     if (lane == 0) {
         s_out[a] = s1; v_out[a] = v1;
-        traffic_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, obs, mot);
+        traffic_store(obs, mot, pin.pool, traffic_pose(t, pts, pin, s1));
     }
 }
 
@@ -221,32 +258,38 @@ k_follow_traffic(int n_actors, double dt, TrafficFollow tf, double half_w, const
 //
 // One 64-lane wave per vehicle, four per 256-thread block, no LDS, no barrier, no scratch.  The vehicle index is made wave-uniform
 // (readfirstlane), so its record, its track and its state are scalar loads and the pose is computed once per wave; the lanes
-// stride the world's members to store it - the same bytes into every member's entry, plain vector stores.  The follow kernel
+// stride the world's members to store it - the same bytes into every member's entry, plain vector stores (world_store).  The
+// follow kernel
 //   1. strides its (world, track) group exactly as k_follow_traffic strides its (scene, track) group;
 //   2. strides the member EGOS, 64 per pass: every lane walks the window vertices k = 1, 2, .. while g_k <= look (the trip count
 //      and the vertex loads are wave-uniform), keeps the first minimum d2 of its own ego, applies the lateral test and keeps its
 //      best (g_e, e) across passes (e rises within a lane: a tie keeps the lower scene); one wave_first_min picks the leader;
 //   3. - 5. as k_follow_traffic, wave-uniform.
-// Only + - * / sqrt floor on doubles, every one rounded once (-ffp-contract=off), and both orders are total: the result is specified
-// to the last bit.
-constexpr int kWorldActors = 4;        // vehicles (waves) per block of the two world-traffic kernels
 
-// §4h 4. - 5. for the world kernels: the pose once per wave, then one entry per member scene (lanes stride [p0, p1))
-__device__ __forceinline__ void world_place(const TrafficPin& pin, const TrafficTrackDev& tk, const double* __restrict__ c, int i, double s,
-                                            const GlobalPoint2D* __restrict__ pts, int lane, int p0, int p1, const FleetPin* __restrict__ fpin,
-                                            ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+// §4i 2. per world: the member ego [p0, p1) with the smallest (g_e, e) that is within `lateral` of its first nearest window vertex,
+// the same in every lane; e < 0: none
+__device__ __forceinline__ int follow_world_ego(const TrackView& t, const GlobalPoint2D* __restrict__ pts, int i0, int kmax, double s, double look,
+                                                double lat2, const SceneIn* __restrict__ in, int p0, int p1, int lane, double& eg)
 {
-    const double c0 = c[i], d = c[i + 1] - c0;
-    const double t = d > 0 ? (s - c0) / d : 0.0;
-    const GlobalPoint2D P = pts[tk.point_off + i];
-    const GlobalPoint2D Q = pts[tk.point_off + (i + 1 < tk.n_points ? i + 1 : 0)];
-    ObPoint o;
-    o.x = P.x + t * (Q.x - P.x); o.y = P.y + t * (Q.y - P.y); o.type = pin.type; o.radius = pin.radius;
-    for (int m = p0 + lane; m < p1; m += 64) {
-        const int e = fpin[m].obs_off + pin.pool;        // (the slot is an own entry of every member: checked by pp_set_world_traffic)
-        obs[e] = o;
-        if (mot) { ObMotion z; z.vx = 0; z.vy = 0; mot[e] = z; }
+    int ee = -1; eg = 0;
+    for (int e0 = p0; e0 < p1; e0 += 64) {
+        const int e = e0 + lane;
+        const bool mine = e < p1;
+        double x = 0, y = 0;
+        if (mine) { x = in[e].loc.globalpoint.x; y = in[e].loc.globalpoint.y; }
+        double md = 0, mg = 0; bool have = false;
+        for (int k = 1; k <= kmax; k++) {               // (wave-uniform: g depends on the vehicle alone)
+            int pj; const double g = follow_window_gap(t, i0, s, k, pj);
+            if (!(g <= look)) break;                    // (the gaps never decrease with k: the vertices that take part are a prefix)
+            const GlobalPoint2D P = pts[t.tk.point_off + pj];
+            const double ex = P.x - x, ey = P.y - y;
+            const double d2 = ex * ex + ey * ey;
+            if ((!have && d2 == d2) || d2 < md) { md = d2; mg = g; have = true; }      // (k rises: the first minimum; a NaN is never the minimum)
+        }
+        if (mine && have && md <= lat2 && (ee < 0 || mg < eg)) { eg = mg; ee = e; }      // (e rises within a lane: ties keep the lower scene)
     }
+    wave_first_min(eg, ee);
+    return ee;
 }
 
 // step: 0 (pp_set_world_traffic, pp_update_async) or EgoModel.dt (pp_advance_async with following off).  world: every vehicle's world.
@@ -257,20 +300,14 @@ k_move_world_traffic(int n_actors, double step, const TrafficPin* __restrict__ a
                      ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
 {
     const int lane = threadIdx.x & 63;
-    const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * kWorldActors + (threadIdx.x >> 6));
+    const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * kTrafficWaves + (threadIdx.x >> 6));
     if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
     const TrafficPin pin = actors[a];
-    const TrafficTrackDev tk = tracks[pin.track];
-    const bool closed = tk.closed != 0;
-    const int nseg = closed ? tk.n_points : tk.n_points - 1;
-    const double* c = cum + tk.cum_off;
-    const double L = c[nseg];
-    double s = s_arr[a];
-    if (step != 0) s = s + pin.speed * step;
-    s = traffic_wrap(s, L, closed);
+    const TrackView t = traffic_view(tracks, cum, pin.track);
+    const double s = traffic_step(t, s_arr[a], pin.speed, step);
     if (lane == 0) s_arr[a] = s;
     const int w = world[a];
-    world_place(pin, tk, c, traffic_locate(c, nseg, s), s, pts, lane, world_first[w], world_first[w + 1], fpin, obs, mot);
+    world_store(obs, mot, fpin, lane, world_first[w], world_first[w + 1], pin.pool, traffic_pose(t, pts, pin, s));
 }
 
 // As k_follow_traffic, with refs[a].scene = the vehicle's WORLD and the groups those of (world, track); in / flags: the records and
@@ -284,88 +321,26 @@ k_follow_world_traffic(int n_actors, double dt, TrafficFollow tf, double half_w,
                        ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
 {
     const int lane = threadIdx.x & 63;
-    const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * kWorldActors + (threadIdx.x >> 6));
+    const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * kTrafficWaves + (threadIdx.x >> 6));
     if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
     const TrafficPin pin = actors[a];
-    const TrafficTrackDev tk = tracks[pin.track];
-    const bool closed = tk.closed != 0;
-    const int n = tk.n_points, nseg = closed ? n : n - 1;
-    const double* c = cum + tk.cum_off;
-    const double L = c[nseg];
+    const TrackView t = traffic_view(tracks, cum, pin.track);
     const double s = s_in[a];
     const TrafficRef ref = refs[a];
     const int p0 = world_first[ref.scene], p1 = world_first[ref.scene + 1];
+    double s1, v1;
     if (!(pin.speed > 0)) {                             // parked or reversing: §4h's step, v = speed
-        const double s1 = traffic_wrap(s + pin.speed * dt, L, closed);
-        if (lane == 0) { s_out[a] = s1; v_out[a] = pin.speed; }
-        world_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, lane, p0, p1, fpin, obs, mot);
-        return;
+        s1 = traffic_step(t, s, pin.speed, dt); v1 = pin.speed;
+    } else {
+        const double v = v_in[a];
+        const TrafficAhead ahead = follow_actor_ahead(t, ref.group, a, s, tf.look, group_first, members, s_in, lane);
+        const int i0 = traffic_locate(t.c, t.nseg, s);
+        double g_e;
+        const int e = follow_world_ego(t, pts, i0, t.closed ? t.n : t.n - 1 - i0, s, tf.look, tf.lateral * tf.lateral, in, p0, p1, lane, g_e);
+        s1 = follow_drive(t, tf, pin, s, v, dt, half_w, ahead, e, g_e, actors, v_in, in, flags, v1);
     }
-    const double v = v_in[a];
-    // 1. the actor ahead: the smallest (g, b) over the (world, track) group
-    double bg = 0; int bi = -1;
-    for (int m = group_first[ref.group] + lane, m1 = group_first[ref.group + 1]; m < m1; m += 64) {
-        const int b = members[m];
-        if (b == a) continue;
-        double g = s_in[b] - s;
-        bool ok = true;
-        if (closed) { if (g < 0 || (g == 0 && b > a)) g = g + L; }
-        else ok = g > 0 || (g == 0 && b < a);
-        if (ok && g <= tf.look && (bi < 0 || g < bg)) { bg = g; bi = b; }       // (b rises within a lane: ties keep the lower index; a NaN compares false)
-    }
-    wave_first_min(bg, bi);
-    // 2. the egos of the world: every lane its own, 64 per pass, over the same window
-    const int i0 = traffic_locate(c, nseg, s);
-    const int kmax = closed ? n : n - 1 - i0;
-    const double lat2 = tf.lateral * tf.lateral;
-    double eg = 0; int ee = -1;
-    for (int e0 = p0; e0 < p1; e0 += 64) {
-        const int e = e0 + lane;
-        const bool mine = e < p1;
-        double x = 0, y = 0;
-        if (mine) { x = in[e].loc.globalpoint.x; y = in[e].loc.globalpoint.y; }
-        double md = 0, mg = 0; bool have = false;
-        for (int k = 1; k <= kmax; k++) {               // (wave-uniform: g depends on the vehicle alone)
-            const int j = i0 + k;
-            const int pj = j <= n - 1 ? j : j - n;
-            const double g = j <= n - 1 ? c[j] - s : (L - s) + c[pj];
-            if (!(g <= tf.look)) break;                 // (the gaps never decrease with k: the vertices that take part are a prefix)
-            const GlobalPoint2D P = pts[tk.point_off + pj];
-            const double ex = P.x - x, ey = P.y - y;
-            const double d2 = ex * ex + ey * ey;
-            if ((!have && d2 == d2) || d2 < md) { md = d2; mg = g; have = true; }      // (k rises: the first minimum; a NaN is never the minimum)
-        }
-        if (mine && have && md <= lat2 && (ee < 0 || mg < eg)) { eg = mg; ee = e; }      // (e rises within a lane: ties keep the lower scene)
-    }
-    wave_first_min(eg, ee);
-    // 3. the leader (wave-uniform from here on)
-    bool lead = false; double g = 0, vl = 0, rl = 0;
-    if (bi >= 0) { lead = true; g = bg; vl = v_in[bi]; rl = (double)actors[bi].radius; }
-    if (ee >= 0 && (!lead || eg <= g)) {
-        lead = true; g = eg; rl = half_w;
-        vl = flags[ee] != 0 ? 0.0 : in[ee].loc.velocity / 3.6;
-    }
-    // 4. the acceleration
-    const double r = v / pin.speed, r2 = r * r, fr = 1 - r2 * r2;
-    double acc;
-    if (!lead) acc = tf.max_acc * fr;
-    else {
-        double net = g - (double)pin.radius - rl;
-        if (!(net > tf.min_net)) net = tf.min_net;
-        const double dv = v - vl;
-        const double c2 = 2 * sqrt(tf.max_acc * tf.comfort_dec);
-        double dyn = v * tf.headway + (v * dv) / c2;
-        if (!(dyn > 0)) dyn = 0;
-        const double star = tf.gap + dyn, q = star / net;
-        acc = tf.max_acc * (fr - q * q);
-    }
-    if (!(acc >= -tf.max_dec)) acc = -tf.max_dec;       // (a NaN brakes)
-    // 5. integrate and place
-    double v1 = v + acc * dt;
-    if (!(v1 > 0)) v1 = 0;
-    const double s1 = traffic_wrap(s + 0.5 * (v + v1) * dt, L, closed);
     if (lane == 0) { s_out[a] = s1; v_out[a] = v1; }
-    world_place(pin, tk, c, traffic_locate(c, nseg, s1), s1, pts, lane, p0, p1, fpin, obs, mot);
+    world_store(obs, mot, fpin, lane, p0, p1, pin.pool, traffic_pose(t, pts, pin, s1));
 }
 
 }  // namespace dmpp

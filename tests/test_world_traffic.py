@@ -28,8 +28,8 @@ import world_traffic_model as wm
 
 gpu = pytest.mark.gpu
 FAR = (4096.0, 4096.0, 0.0, False)          # an ego nowhere near a track
-FILL_OB = bytes([wb.FILL]) * 24
-FILL_MOT = bytes([wb.FILL]) * 16
+FILL_OB = bytes([ts.FILL]) * 24
+FILL_MOT = bytes([ts.FILL]) * 16
 
 
 def _runner(dm, name, log=None):
@@ -350,7 +350,7 @@ def _one_on_the_device(dm, polylines, scenes, follow, world):
         pl.set_traffic_follow(dm.default_traffic_follow())
     model = dm.default_ego_model()
     model["dt"], model["window"] = 0.5, 1
-    po = wb.staging_plan(dm, lay.egos, 0.5)
+    po = fb.staging_plan(dm, lay.egos, 0.5)
     out = []
     for k in range(ONE_STEPS + 1):
         if k > 0:
@@ -410,7 +410,7 @@ def _advance(dm, pl, lay, dt=0.5):
     pl.tick()
     st = pl.get_state()
     st["afresh_planning"] = 1
-    pl.write_device(dm.BUF_PLAN_OUT, wb.staging_plan(dm, lay.egos, dt))
+    pl.write_device(dm.BUF_PLAN_OUT, fb.staging_plan(dm, lay.egos, dt))
     pl.write_device(dm.BUF_STATE, st)
     pl.advance_async(model)
 

@@ -9,8 +9,6 @@ import numpy as np
 import traffic_model as tm
 import traffic_scenes as ts
 
-FILL = 0xA5
-
 
 class Result:
     def __init__(self, s, ob):
@@ -29,7 +27,7 @@ class ModelBackend:
         n = len(rows)
         act = ts.actors(dm, [(r[0], r[1], a, 0, r[2], r[3], r[4]) for a, r in enumerate(rows)])
         tr = tm.Traffic(tracks, pts, act, np.arange(n))
-        pool = np.frombuffer(bytes([FILL]) * (n * dm.ObPoint.itemsize), dm.ObPoint).copy()
+        pool = ts.filled(dm.ObPoint, n)
         s, ob = [], []
         for step in [0.0] + list(steps):
             pool, _ = tr.place(pool, None, step)
@@ -48,7 +46,7 @@ class DeviceBackend:
         cfg = dm.default_config(128)
         cfg["grid_stage"] = 0
         sc = dm.gen_scenes(cfg, 0, n, 1, junction_every=0)
-        sc["obs_pool"] = np.frombuffer(bytes([FILL]) * (n * dm.ObPoint.itemsize), dm.ObPoint).copy()
+        sc["obs_pool"] = ts.filled(dm.ObPoint, n)
         pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=n)
         pl.set_scenes(sc, with_motion=False)
         pl.set_state(sc["state"])

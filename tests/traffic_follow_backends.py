@@ -16,8 +16,6 @@ import numpy as np
 import traffic_follow_model as fm
 import traffic_scenes as ts
 
-FILL = 0xA5
-
 
 class Result:
     def __init__(self, s, v, ob, info):
@@ -53,7 +51,7 @@ def _run_model(dm, polylines, act, stride, si_of_step, flags_of_step, tf, dt, st
     n_sc = int(act["scene"].max()) + 1 if len(act) else 0
     n_sc = max(n_sc, len(si_of_step(1)))
     tr = fm.Follow(tracks, pts, act, np.arange(n_sc) * stride)
-    pool = np.frombuffer(bytes([FILL]) * (n_sc * stride * dm.ObPoint.itemsize), dm.ObPoint).copy()
+    pool = ts.filled(dm.ObPoint, n_sc * stride)
     pool, _ = tr.place(pool, None, 0.0)
     s, v, ob, info = [tr.s.copy()], [tr.v.copy()], [pool[tr.pool_index].copy()], [None]
     width = float(dm.default_config(128)["Vehicle_Width"][0])
@@ -76,6 +74,45 @@ class ModelBackend:
         return _unpermute(_run_model(dm, polylines, act, stride, lambda k: si, lambda k: flags, tf, dt, steps), inv)
 
 
+def staging_plan(dm, egos, dt):
+    """The PlanOut that makes k_advance_egos stage every ego (x, y, v, flagged) at its pose: vn = v + 0 (desaccVd with desacc = 0),
+    dist = 0.5 (v + vn) / 3.6 dt, walked from point 0; a flagged ego: a NaN path point (DMPP_EGO_BAD_PATH)."""
+    po = np.zeros(len(egos), dm.PlanOut)
+    po["result"]["desaccVd"] = 1
+    with np.errstate(all="ignore"):
+        for c, (x, y, v, flagged) in enumerate(egos):
+            d = np.float64(0.5) * (np.float64(v) + np.float64(v)) / np.float64(3.6) * np.float64(dt)
+            d = d if d > 0 else np.float64(0.0)
+            po["road_points"]["x"][c] = x + (np.arange(dm.PATH_POINTS) - 1.0) * d
+            po["road_points"]["y"][c] = y
+            if flagged:
+                po["road_points"]["x"][c, 0] = np.nan
+    return po
+
+
+def staged_step(dm, pl, model, po, after_tick=None):
+    """One step of the device loop: the tick an advance follows, `po` and a fresh SceneState in the place of what it wrote, the
+    advance; returns the SceneIn records and the ego flag words the device staged."""
+    pl.tick()
+    if after_tick is not None:
+        after_tick()
+    st = pl.get_state()
+    st["afresh_planning"] = 1                                   # (the ego stands on point 0 of the path)
+    pl.write_device(dm.BUF_PLAN_OUT, po)
+    pl.write_device(dm.BUF_STATE, st)
+    pl.advance_async(model)
+    return pl.get_scene_in(), pl.ego_flags()
+
+
+def check_staged_egos(seen_si, seen_flags, want_si, want_flags, steps):
+    """The egos came out as the case wants them (else its known answers mean nothing)."""
+    for k in range(1, steps + 1):
+        for f in ("x", "y"):
+            assert seen_si[k]["loc"]["globalpoint"][f].tobytes() == want_si["loc"]["globalpoint"][f].tobytes(), f"step {k}: staged ego {f}"
+        assert seen_si[k]["loc"]["velocity"].tobytes() == want_si["loc"]["velocity"].tobytes(), f"step {k}: staged ego velocity"
+        assert np.array_equal(seen_flags[k] != 0, want_flags != 0), f"step {k}: ego flags {seen_flags[k].tolist()}"
+
+
 class DeviceBackend:
     name = "device"
 
@@ -87,7 +124,7 @@ class DeviceBackend:
         cfg = dm.default_config(128)
         cfg["grid_stage"] = 0
         sc = dm.gen_scenes(cfg, 0, n, stride, junction_every=0)
-        sc["obs_pool"] = np.frombuffer(bytes([FILL]) * (n * stride * dm.ObPoint.itemsize), dm.ObPoint).copy()
+        sc["obs_pool"] = ts.filled(dm.ObPoint, n * stride)
         sc["scene_in"]["obs_off"], sc["scene_in"]["obs_n"] = np.arange(n) * stride, stride
         sc["scene_in"]["loc"]["globalpoint"]["x"], sc["scene_in"]["loc"]["globalpoint"]["y"] = want_si["loc"]["globalpoint"]["x"], want_si["loc"]["globalpoint"]["y"]
         sc["scene_in"]["loc"]["velocity"] = want_si["loc"]["velocity"]
@@ -98,29 +135,12 @@ class DeviceBackend:
         pl.set_traffic_follow(fm_record(dm, tf))
         model = dm.default_ego_model()
         model["dt"], model["window"] = dt, 1                        # (a window of one point: the ids stay, no DMPP_EGO_LANE_END)
-        # the plan that stages the wanted pose: vn = v + 0 (desaccVd with desacc = 0), dist = 0.5 (v + vn) / 3.6 dt, walked from point 0
-        po = np.zeros(n, dm.PlanOut)
-        po["result"]["desaccVd"] = 1
-        with np.errstate(all="ignore"):
-            for c, e in enumerate(scenes):
-                x, y, v, flagged = e["ego"]
-                d = np.float64(0.5) * (np.float64(v) + np.float64(v)) / np.float64(3.6) * np.float64(dt)
-                d = d if d > 0 else np.float64(0.0)
-                po["road_points"]["x"][c] = x + (np.arange(dm.PATH_POINTS) - 1.0) * d
-                po["road_points"]["y"][c] = y
-                if flagged:
-                    po["road_points"]["x"][c, 0] = np.nan
+        po = staging_plan(dm, [sc["ego"] for sc in scenes], dt)
         seen_si, seen_flags = {}, {}
         s, v, ob = [], [], []
         for k in range(steps + 1):
             if k > 0:
-                pl.tick()                                           # the tick an advance follows; what it wrote is replaced below
-                st = pl.get_state()
-                st["afresh_planning"] = 1                           # (the ego stands on point 0 of the path)
-                pl.write_device(dm.BUF_PLAN_OUT, po)
-                pl.write_device(dm.BUF_STATE, st)
-                pl.advance_async(model)
-                seen_si[k], seen_flags[k] = pl.get_scene_in(), pl.ego_flags()
+                seen_si[k], seen_flags[k] = staged_step(dm, pl, model, po)
             s.append(pl.traffic_state()), v.append(pl.traffic_speed())
             got = np.zeros(na, dm.ObPoint)
             slices = [pl.get_obstacles(c, cap=stride) for c in range(n)]
@@ -128,11 +148,7 @@ class DeviceBackend:
                 got[a] = slices[int(act["scene"][a])][int(act["slot"][a])]
             ob.append(got)
         pl.close()
-        for k in range(1, steps + 1):                               # the ego came out as the case wants it (else its known answers mean nothing)
-            for f in ("x", "y"):
-                assert seen_si[k]["loc"]["globalpoint"][f].tobytes() == want_si["loc"]["globalpoint"][f].tobytes(), f"step {k}: staged ego {f}"
-            assert seen_si[k]["loc"]["velocity"].tobytes() == want_si["loc"]["velocity"].tobytes(), f"step {k}: staged ego velocity"
-            assert np.array_equal(seen_flags[k] != 0, want_flags != 0), f"step {k}: ego flags {seen_flags[k].tolist()}"
+        check_staged_egos(seen_si, seen_flags, want_si, want_flags, steps)
         want = _run_model(dm, polylines, act, stride, lambda k: seen_si[k], lambda k: seen_flags[k], tf, dt, steps)
         for k in range(steps + 1):
             assert s[k].tobytes() == want.s[k].tobytes(), f"stage {k}: arc lengths differ from the model's at actors {np.flatnonzero(s[k] != want.s[k]).tolist()[:20]}"

@@ -39,6 +39,39 @@ class Info:
         self.kstar, self.d2, self.actor_g, self.ego_g, self.vl = -1, None, None, None, None
 
 
+def idm(p, v, speed, radius, lead, info):
+    """§4i 4.: the acceleration of a follower at speed v that wants `speed`, behind lead = (kind, g, vl, rl, index) or None."""
+    r = v / speed
+    r2 = r * r
+    free = 1 - r2 * r2
+    if lead is None:
+        acc = p["max_acc"] * free
+    else:
+        info.kind, g, vl, rl, info.leader = lead
+        info.g, info.vl = g, vl
+        net = g - radius - rl
+        if not (net > p["min_net"]):
+            net, info.floored = p["min_net"], True
+        dv = v - vl
+        c2 = 2 * np.sqrt(p["max_acc"] * p["comfort_dec"])
+        dyn = v * p["headway"] + (v * dv) / c2
+        if not (dyn > 0):
+            dyn = np.float64(0.0)
+        star = p["gap"] + dyn
+        q = star / net
+        acc = p["max_acc"] * (free - q * q)
+        info.net, info.dyn = net, dyn
+    if not (acc >= -p["max_dec"]):                               # (a NaN brakes)
+        acc, info.clamped = -p["max_dec"], True
+    info.acc = acc
+    return acc
+
+
+def ego_speed(scene_in, flags, c):
+    """§4i 2.: vl_e of scene c's ego - a frozen ego stands."""
+    return np.float64(0.0) if int(flags[c]) != 0 else np.float64(scene_in["loc"]["velocity"][c]) / np.float64(3.6)
+
+
 class Follow(tm.Traffic):
     def __init__(self, tracks, points, actors, obs_off):
         super().__init__(tracks, points, actors, obs_off)
@@ -101,6 +134,13 @@ class Follow(tm.Traffic):
                 return None
         return g[m], int(ks[m]), d2[m]
 
+    # §4i 2. - 3.: (g_e, vl_e) of the ego that may lead actor a - the ego of its own scene - or None
+    def _ego_leader(self, a, k, closed, L, p, s_a, scene_in, flags, info):
+        c = int(self.actors["scene"][a])
+        gp = scene_in["loc"]["globalpoint"][c]
+        eg = self._ego(a, k, closed, L, p["look"], p["lateral"], s_a, np.float64(gp["x"]), np.float64(gp["y"]), info)
+        return None if eg is None else (eg[0], ego_speed(scene_in, flags, c))
+
     def step(self, obs_pool, mot_pool, dt, tf, scene_in, flags, vehicle_width):
         """One k_follow_traffic launch on one staged set: returns (obs_pool', mot_pool'), updates self.s, self.v, self.info.
         scene_in: the SceneIn records BEING staged (loc.globalpoint, loc.velocity are read); flags: the ego flag words as staged."""
@@ -119,48 +159,22 @@ class Follow(tm.Traffic):
             with np.errstate(all="ignore"):
                 if not (speed > 0):                              # parked or reversing: §4h's step, v = speed
                     info = Info("plain")
-                    raw = s0[a] + speed * dt
-                    s1, v1 = tm.wrap(raw, L, closed), speed
+                    (raw, s1), v1 = self._plain(a, s0[a], dt), speed
                 else:
                     info = Info("free")
-                    c = int(A["scene"])
                     v = v0s[a]
                     lead = None
-                    al = self._actor_leader(a, k, closed, L, p["look"], s0, info)
+                    al = self._actor_leader(a, k, closed, L, p["look"], s0, info)          # 1.
                     if al is not None:
                         info.actor_g = al[0]
                         lead = ("actor", al[0], v0s[al[1]], np.float64(self.actors["radius"][al[1]]), al[1])
-                    loc = scene_in["loc"][c]
-                    eg = self._ego(a, k, closed, L, p["look"], p["lateral"], s0[a], np.float64(loc["globalpoint"]["x"]), np.float64(loc["globalpoint"]["y"]), info)
-                    if eg is not None:
-                        info.ego_g = eg[0]
-                        if lead is None or eg[0] <= lead[1]:     # the ego wins a tie
-                            vl = np.float64(0.0) if int(flags[c]) != 0 else np.float64(loc["velocity"]) / np.float64(3.6)
-                            lead = ("ego", eg[0], vl, half_w, -1)
-                    r = v / speed
-                    r2 = r * r
-                    free = 1 - r2 * r2
-                    if lead is None:
-                        acc = p["max_acc"] * free
-                    else:
-                        info.kind, g, vl, rl, info.leader = lead
-                        info.g, info.vl = g, vl
-                        net = g - np.float64(A["radius"]) - rl
-                        if not (net > p["min_net"]):
-                            net, info.floored = p["min_net"], True
-                        dv = v - vl
-                        c2 = 2 * np.sqrt(p["max_acc"] * p["comfort_dec"])
-                        dyn = v * p["headway"] + (v * dv) / c2
-                        if not (dyn > 0):
-                            dyn = np.float64(0.0)
-                        star = p["gap"] + dyn
-                        q = star / net
-                        acc = p["max_acc"] * (free - q * q)
-                        info.net, info.dyn = net, dyn
-                    if not (acc >= -p["max_dec"]):               # (a NaN brakes)
-                        acc, info.clamped = -p["max_dec"], True
-                    info.acc = acc
-                    v1 = v + acc * dt
+                    el = self._ego_leader(a, k, closed, L, p, s0[a], scene_in, flags, info)          # 2.
+                    if el is not None:
+                        info.ego_g = el[0]
+                        if lead is None or el[0] <= lead[1]:     # 3.: the ego wins a tie
+                            lead = ("ego", el[0], el[1], half_w, -1)
+                    acc = idm(p, v, speed, np.float64(A["radius"]), lead, info)          # 4.
+                    v1 = v + acc * dt                            # 5.
                     if not (v1 > 0):
                         v1, info.stopped = np.float64(0.0), True
                     raw = s0[a] + 0.5 * (v + v1) * dt
@@ -168,9 +182,5 @@ class Follow(tm.Traffic):
                 info.wrapped = bool(s1 != raw)
             self.s[a], self.v[a] = s1, v1
             self.info.append(info)
-            _, _, x, y = tm.point_at(self.px[k], self.py[k], self.cum[k], s1)
-            o = obs[int(self.pool_index[a])]
-            o["x"], o["y"], o["type"], o["radius"] = x, y, A["type"], A["radius"]
-            if mot is not None:
-                mot[int(self.pool_index[a])]["vx"], mot[int(self.pool_index[a])]["vy"] = 0.0, 0.0
+            self._write(obs, mot, a, s1)
         return obs, mot

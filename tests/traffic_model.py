@@ -72,7 +72,7 @@ def point_at(px, py, cum, s):
 
 class Traffic:
     """The state pp_set_traffic builds.  pool_index: the absolute pool entry of every actor, obs_off[scene] + slot of the
-    resident records at set time (the pin)."""
+    resident records at set time (the pin); entries[a]: the entries actor a is written into (that one)."""
 
     def __init__(self, tracks, points, actors, obs_off):
         self.tracks, self.actors = np.array(tracks).copy(), np.array(actors).copy()
@@ -83,29 +83,36 @@ class Traffic:
             self.py.append(np.ascontiguousarray(points["y"][a:a + n], np.float64))
             self.cum.append(cumulative(self.px[-1], self.py[-1], int(T["closed"]) != 0))
         self.pool_index = np.asarray(obs_off)[self.actors["scene"]].astype(np.int64) + self.actors["slot"]
+        self.entries = self.pool_index[:, None]
         self.s = np.ascontiguousarray(self.actors["s0"], np.float64).copy()          # wrapped by the first place(.., 0.0)
 
     def length(self, k):
         return self.cum[k][-1]
+
+    def _plain(self, a, s, step):
+        """§4h 2. - 3.: one step of a scripted actor (none for step = 0); returns (the sum, its wrap)."""
+        k = int(self.actors["track"][a])
+        with np.errstate(over="ignore"):
+            raw = s + np.float64(self.actors["speed"][a]) * step if step != 0 else s          # the product is rounded, then the sum
+        return raw, wrap(raw, self.cum[k][-1], int(self.tracks["closed"][k]) != 0)
+
+    def _write(self, obs, mot, a, s):
+        """§4h 4. - 5.: the ObPoint of arc length s into the actor's entries, and a zero ObMotion with a motion pool."""
+        A = self.actors[a]
+        k = int(A["track"])
+        _, _, x, y = point_at(self.px[k], self.py[k], self.cum[k], s)
+        for e in self.entries[a]:
+            o = obs[int(e)]
+            o["x"], o["y"], o["type"], o["radius"] = x, y, A["type"], A["radius"]
+            if mot is not None:
+                mot[int(e)]["vx"], mot[int(e)]["vy"] = 0.0, 0.0
 
     def place(self, obs_pool, mot_pool=None, step=0.0):
         """One launch on one staged set: returns (obs_pool', mot_pool') and updates self.s.  step = 0: pp_set_traffic and
         pp_update_async (s = wrap(s), which leaves a wrapped s as it is); step = EgoModel.dt: pp_advance_async."""
         obs = obs_pool.copy()
         mot = None if mot_pool is None else mot_pool.copy()
-        step = np.float64(step)
-        for a, A in enumerate(self.actors):
-            k = int(A["track"])
-            closed = int(self.tracks["closed"][k]) != 0
-            s = self.s[a]
-            if step != 0:
-                with np.errstate(over="ignore"):
-                    s = s + np.float64(A["speed"]) * step          # the product is rounded, then the sum
-            s = wrap(s, self.cum[k][-1], closed)
-            self.s[a] = s
-            _, _, x, y = point_at(self.px[k], self.py[k], self.cum[k], s)
-            o = obs[int(self.pool_index[a])]
-            o["x"], o["y"], o["type"], o["radius"] = x, y, A["type"], A["radius"]
-            if mot is not None:
-                mot[int(self.pool_index[a])]["vx"], mot[int(self.pool_index[a])]["vy"] = 0.0, 0.0
+        for a in range(len(self.actors)):
+            self.s[a] = self._plain(a, self.s[a], np.float64(step))[1]
+            self._write(obs, mot, a, self.s[a])
         return obs, mot

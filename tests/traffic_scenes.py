@@ -9,6 +9,11 @@ import numpy as np
 import route_scenes as rs
 
 SEG = rs.PTS + rs.JPTS          # points one road and the junction behind it add to a ring track
+FILL = 0xA5                     # every byte of a pool before traffic is set: an entry nobody pinned still holds it
+
+
+def filled(dtype, count):
+    return np.frombuffer(bytes([FILL]) * (count * np.dtype(dtype).itemsize), dtype).copy()
 
 
 def lane_points(dm, m, road, lane):

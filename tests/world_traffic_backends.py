@@ -22,7 +22,6 @@ import traffic_follow_model as fm
 import traffic_scenes as ts
 import world_traffic_model as wm
 
-FILL = 0xA5
 RANGE = 60.0           # the fleet's range (it matters only with K > 0)
 PEER_RADIUS = 0.9
 
@@ -64,7 +63,7 @@ class Layout:
         self.entries = [self.off[self.world_first[int(A["scene"])]:self.world_first[int(A["scene"]) + 1]] + int(A["slot"]) for A in self.act]
 
     def filled(self, dtype):
-        return np.frombuffer(bytes([FILL]) * (max(self.total, 1) * np.dtype(dtype).itemsize), dtype).copy()
+        return ts.filled(dtype, max(self.total, 1))
 
     def scene_in(self, si):
         """The loc fields of `si` on records whose slices are the layout's (what the model's couple starts from)."""
@@ -111,22 +110,6 @@ def set_scenes(pl, sc, si, obs, mot, n_obs_total):
     pl.n = len(si)
 
 
-def staging_plan(dm, egos, dt):
-    """The PlanOut that makes k_advance_egos stage every ego at its pose: vn = v + 0 (desaccVd with desacc = 0),
-    dist = 0.5 (v + vn) / 3.6 dt, walked from point 0; a flagged ego: a NaN path point (DMPP_EGO_BAD_PATH)."""
-    po = np.zeros(len(egos), dm.PlanOut)
-    po["result"]["desaccVd"] = 1
-    with np.errstate(all="ignore"):
-        for c, (x, y, v, flagged) in enumerate(egos):
-            d = np.float64(0.5) * (np.float64(v) + np.float64(v)) / np.float64(3.6) * np.float64(dt)
-            d = d if d > 0 else np.float64(0.0)
-            po["road_points"]["x"][c] = x + (np.arange(dm.PATH_POINTS) - 1.0) * d
-            po["road_points"]["y"][c] = y
-            if flagged:
-                po["road_points"]["x"][c, 0] = np.nan
-    return po
-
-
 class DeviceBackend:
     name = "device"
 
@@ -151,7 +134,7 @@ class DeviceBackend:
             pl.set_traffic_follow(fb.fm_record(dm, tf))
         model = dm.default_ego_model()
         model["dt"], model["window"] = dt, 1
-        po = staging_plan(dm, lay.egos, dt)
+        po = fb.staging_plan(dm, lay.egos, dt)
         seen_si, seen_flags = {0: pl.get_scene_in()}, {0: np.zeros(n, np.int32)}
         s, v, sl, pools, mots = [], [], [], [], []
 
@@ -161,24 +144,13 @@ class DeviceBackend:
 
         for k in range(steps + 1):
             if k > 0:
-                pl.tick()
-                whole_pools()
-                st = pl.get_state()
-                st["afresh_planning"] = 1
-                pl.write_device(dm.BUF_PLAN_OUT, po)
-                pl.write_device(dm.BUF_STATE, st)
-                pl.advance_async(model)
-                seen_si[k], seen_flags[k] = pl.get_scene_in(), pl.ego_flags()
+                seen_si[k], seen_flags[k] = fb.staged_step(dm, pl, model, po, whole_pools)
             s.append(pl.traffic_state()), v.append(pl.traffic_speed() if follow else np.ascontiguousarray(lay.act["speed"]).copy())
             sl.append([pl.get_obstacles(c, cap=int(lay.own[c]) + K) for c in range(n)])
         pl.tick()
         whole_pools()
         pl.close()
-        for k in range(1, steps + 1):                            # the egos came out as the case wants them (else its known answers mean nothing)
-            for f in ("x", "y"):
-                assert seen_si[k]["loc"]["globalpoint"][f].tobytes() == lay.si["loc"]["globalpoint"][f].tobytes(), f"step {k}: staged ego {f}"
-            assert seen_si[k]["loc"]["velocity"].tobytes() == lay.si["loc"]["velocity"].tobytes(), f"step {k}: staged ego velocity"
-            assert np.array_equal(seen_flags[k] != 0, lay.flags != 0), f"step {k}: ego flags {seen_flags[k].tolist()}"
+        fb.check_staged_egos(seen_si, seen_flags, lay.si, lay.flags, steps)
         want = _run_model(dm, polylines, lay, lambda k: seen_si[k], lambda k: seen_flags[k], tf, dt, steps, follow, motion)
         for k in range(steps + 1):
             assert s[k].tobytes() == want.s[k].tobytes(), f"stage {k}: arc lengths differ from the model's at vehicles {np.flatnonzero(s[k] != want.s[k]).tolist()[:20]}"
