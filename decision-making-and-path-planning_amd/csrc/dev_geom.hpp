@@ -317,10 +317,11 @@ __device__ __forceinline__ SoResult wave_search_obstacle(const PlannerConfig& c,
 
 // CShare::SearchObstacle for one polyline by a TEAM of TW waves of a 256-thread block (TW = 4: the whole block on one
 // polyline; TW = 2: two polylines side by side).  The team's first wave sums the arc lengths while every wave of the team
-// scans its share [n*k/TW, n*(k+1)/TW) of the points for all obstacles; the shares are merged per obstacle in point order
-// with the strict < of the sequential loop (so the first minimum wins), and the first wave finishes as wave_search_obstacle
-// does.  EVERY thread of the block must call it (block-wide barriers), with the same m; a team without a job passes
-// active = false.  part_d2 / part_bi: 256 entries each.  The result is valid in the team's first wave.
+// scans its share of the points for all obstacles: consecutive ranges in rank order, the leader's the smallest.  The
+// shares are merged per obstacle in point order with the strict < of the sequential loop (so the first minimum wins), and
+// the first wave finishes as wave_search_obstacle does.  EVERY thread of the block must call it (block-wide barriers), with
+// the same m; a team without a job passes active = false.  part_d2 / part_bi: 256 entries each.  The result is valid in the
+// team's first wave.
 template <int TW>
 __device__ __forceinline__ SoResult team_search_obstacle(const PlannerConfig& c, const GlobalPoint2D* path, int n, double* s,
                                                          const ObPoint* obs, int m, double lat_lo, double lat_hi, bool active,
@@ -332,7 +333,19 @@ __device__ __forceinline__ SoResult team_search_obstacle(const PlannerConfig& c,
     r.flag = 0; r.path_id = 0; r.ob_index = -1; r.dis_lat = c.NO_OBSTACLE_DIS; r.dis_lng = c.NO_OBSTACLE_DIS;
     const bool run = active && n >= 2 && m >= 1;
     if (run && leader) wave_cumlen(path, n, s, lane);
-    const int q0 = run ? (int)((long long)n * rank / TW) : 0, q1 = run ? (int)((long long)n * (rank + 1) / TW) : 0;
+    // The leader's arc-length sum is one lane adding in index order, the longest chain of the call (about 60 cycles per point
+    // with four workgroups on the CU, profiles/r17_front_cull.txt), so the leader takes a small share of the scan:
+    // four waves: the leader nothing, ranks 1..3 a third each; two waves: the leader a quarter, the other wave the rest.
+    static_assert(TW == 2 || TW == 4, "the shares are written out for teams of two and of four waves");
+    int q0 = 0, q1 = 0;
+    if (run) {
+        if constexpr (TW == 4) {
+            if (!leader) { q0 = (int)((long long)n * (rank - 1) / 3); q1 = (int)((long long)n * rank / 3); }
+        } else {
+            const int cut = n / 4;
+            q0 = leader ? 0 : cut; q1 = leader ? cut : n;
+        }
+    }
     double best_lng = __builtin_inf(), best_lat = 0;
     int best_j = 0x7fffffff, best_id = 0;
     for (int j0 = 0; j0 < m; j0 += DMPP_WAVE) {
