@@ -3,8 +3,8 @@
 // One handle = one device and all device buffers.  Streams: the handle's stream (copies, stand-alone operators, the whole
 // tick of a small batch), kBuf search streams (stream_m[0] is the handle's stream: the searches of consecutive tick groups
 // run side by side, each preceded by its launch order and followed by its own scoring pass; a group is G ticks in one launch), the FRONT stream stream_r (obstacle
-// snapshot, Decision, Planning: highest priority, running ahead of the searches), stream_s (scoring on its own stream: a measurement knob), and - once streamed
-// ticks are in use (pp_update_async / pp_fetch_async) - one upload and two download streams.  pp_plan_tick describes the
+// snapshot, Decision, Planning: highest priority, running ahead of the searches), and - once streamed
+// ticks are in use (pp_update_async / pp_fetch_async) - one upload and two download streams.  tick_streams describes the
 // launch order and the events between the chains; batches below pipeline_min scenes run on the handle's stream with only
 // Decision + Planning forked beside the grid engine.  pp_set_* / pp_get_* join the chains first (join_all) and wait on
 // the host; the streamed calls never wait on the host (pp_wait_tick waits for one tick's downloads only).
@@ -28,6 +28,7 @@
 #include "kernels_f.hpp"
 #include "kernels_t.hpp"
 #include "kernels_op.hpp"
+#include "search_budget.hpp"
 
 namespace {
 
@@ -76,6 +77,28 @@ template <class T> struct HostPin {
 private:
     T* p_ = nullptr;
 };
+// ... and of a timing-disabled event that orders one stream behind another, with the fact that it has been recorded: a point that
+// was never recorded - or was forgotten - is waited for by nobody.  Created at the first record (or by create(), off the latency path).
+struct SyncPoint {
+    SyncPoint() = default;
+    SyncPoint(const SyncPoint&) = delete; SyncPoint& operator=(const SyncPoint&) = delete;
+    ~SyncPoint() { if (ev_) (void)hipEventDestroy(ev_); }
+    int create() { if (!ev_) HIP_TRY(hipEventCreateWithFlags(&ev_, hipEventDisableTiming)); return PP_OK; }
+    int record(hipStream_t st) { if (int r = create()) return r; HIP_TRY(hipEventRecord(ev_, st)); rec_ = true; return PP_OK; }
+    int wait(hipStream_t st) const { if (rec_) HIP_TRY(hipStreamWaitEvent(st, ev_, 0)); return PP_OK; }
+    // A stream wait - unless the point has completed: then no barrier packet is needed (uploads and downloads run ticks ahead /
+    // behind the chains that wait for them)
+    int wait_unless_done(hipStream_t st) const { return done() ? PP_OK : wait(st); }
+    int host_wait() const { if (rec_) HIP_TRY(hipEventSynchronize(ev_)); return PP_OK; }
+    void forget() { rec_ = false; }
+    bool recorded() const { return rec_; }
+    // nothing recorded, or what was has completed (hipErrorNotReady is not an error here)
+    bool done() const { if (!rec_ || hipEventQuery(ev_) == hipSuccess) return true; (void)hipGetLastError(); return false; }
+private:
+    hipEvent_t ev_ = nullptr; bool rec_ = false;
+};
+// (a call that returns the project's error code, inside a function that does)
+#define PP_TRY(expr) do { if (int r__ = (expr)) return r__; } while (0)
 
 struct EvPair { hipEvent_t a, b; int k; int w; };      // w: the ticks the launch between a and b stands for (a tick group's)
 
@@ -116,7 +139,7 @@ constexpr int kDone = 32;          // ticks whose downloads pp_wait_tick can sti
 struct InputSet {
     DevBuf<SceneIn> d_in; DevBuf<ObPoint> d_obs; DevBuf<ObMotion> d_mot;
     bool have_motion = false; int n_obs_total = 0;
-    hipEvent_t ev_up = nullptr; bool up_recorded = false;
+    SyncPoint up;                                     // behind the kernels that staged the set (upload stream)
 };
 // one tick in flight: which input set it reads, and the events that close its front chain and its last kernel
 struct TickRec { long long tick; int in_set; hipEvent_t ev_front, ev_tail; };
@@ -135,18 +158,18 @@ struct PendingFetch {
     size_t n;
 };
 
-// closed-loop rollout (first pp_advance_async): the sticky DMPP_EGO_* word of every scene; ev_adv follows the last advance kernel;
+// closed-loop rollout (first pp_advance_async): the sticky DMPP_EGO_* word of every scene; adv follows the last advance kernel;
 // staged_by_advance: the staged input set was produced on the device; set_tick: tick_seq when the resident scenes were last set
 // (an advance needs a tick of THESE scenes behind it)
 struct RolloutState {
-    DevBuf<int32_t> d_flags; hipEvent_t ev_adv = nullptr; bool adv_recorded = false, staged_by_advance = false;
+    DevBuf<int32_t> d_flags; SyncPoint adv; bool staged_by_advance = false;
     long long set_tick = 0;
 };
-// rollout scorecard (first pp_score_begin): the records, one part array of grid counters per search set, ev
+// rollout scorecard (first pp_score_begin): the records, one part array of grid counters per search set, ego
 // behind the last k_score_ego (upload stream); grp_scored: the open group's tick is scored
 struct ScoreState {
-    DevBuf<RolloutScore> d_score; DevBuf<dmpp::ScoreGridPart> d_grid[kBuf]; hipEvent_t ev = nullptr;
-    bool on = false, recorded = false, grp_scored = false; double dt = 0;
+    DevBuf<RolloutScore> d_score; DevBuf<dmpp::ScoreGridPart> d_grid[kBuf]; SyncPoint ego;
+    bool on = false, grp_scored = false; double dt = 0;
 };
 // fleet coupling (first pp_set_fleet): world_first, the world of every scene and the pinned slices on the device;
 // the pinned slices on the host too (a second pp_set_fleet starts from the scenes' OWN entries); end: the largest end of a
@@ -214,7 +237,7 @@ struct pp_planner {
     int path_set = 0;                                  // the set of the last tick with the grid stage
     DevBuf<int32_t> d_perm[kBuf], d_cost[kBuf];
     DevBuf<uint2> d_ospill[kBuf]; int spill_cap = 0; DevBuf<int32_t> d_retry[kBuf];     // open-list spill areas (bucket_cap0 entries per scene; none when bucket_cap0 <= the LDS list)
-    hipStream_t stream_m[kBuf] = {}; int overlap_override = -1;     // env DMPP_OVERLAP (measurement knob)
+    hipStream_t stream_m[kBuf] = {};
     size_t grid_cells = 0;       // per scene, at creation
     int bucket_cap0 = 0, max_path0 = 0;
     // search: k_search_lds<kind> with `lds_budget` data words per view in LDS; scenes that need more go to k_search_gbm
@@ -228,25 +251,21 @@ struct pp_planner {
     // front chain whose searches wait for grp_G of them (flush_group launches them; so does every entry point that reads
     // results, waits or changes state).
     int gcap = 1, tick_group = 0;
-    int grp_ticks = 0, grp_G = 1, grp_n = 0, grp_p_prev = 0; bool grp_piped = false, grp_overlap = false;
+    int grp_ticks = 0, grp_G = 1, grp_n = 0, grp_p_prev = 0; bool grp_piped = false;
     int grp_set[kGroupMax] = {}, grp_gs[kGroupMax] = {}; const SceneIn* grp_in = nullptr;      // (the ticks of a group read one input set: a new one - streamed ticks - comes with G = 1)
     int ring = 0, gring = 0;     // group positions of the last group: snapshot sets (kRing), GridOut sets (kGoutRing)
     int item_off = 0;            // work item of scene 0 of the last grid tick in its group's buffers (pp_get_order / pp_get_search_info)
     int need_set = 0;            // the snapshot set whose d_need / h_need the last group's search and scoring used
 
-    hipStream_t stream_r = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the R kernels run beside the grid engine
+    hipStream_t stream_r = nullptr; SyncPoint fork, join;   // the R kernels run beside the grid engine; join: behind the last Planning kernel
     // the scoring pass of a group runs behind its search, beside the front chains and searches of the next groups: the obstacle
-    // snapshot, the path cells and GridOut exist per (group position, tick slot); ev_search[p] = the last search that used the
-    // work buffers p, ev_score[q] = the last scoring pass that read snapshot set q
-    hipStream_t stream_s = nullptr; hipEvent_t ev_search[kBuf] = {}, ev_score[kObs] = {};
-    hipEvent_t ev_raster = nullptr;
-    bool score_recorded[kObs] = {}, search_recorded[kBuf] = {}, front_recorded = false, front_unjoined = false;
+    // snapshot, the path cells and GridOut exist per (group position, tick slot); searched[p] = the last search that used the
+    // work buffers p, scored[q] = the last scoring pass that read snapshot set q; raster: the snapshot of the group's last tick
+    SyncPoint searched[kBuf], scored[kObs], raster;
+    bool front_unjoined = false;  // the last Planning kernel ran beside a piped tick: a one-stream front chain has yet to wait for it
     int parity = 0;              // work buffers of the last group
     bool last_piped = false;     // the last tick ran as three chains on several streams (else it ended on the handle's stream)
     int obs_set = 0;             // obstacle snapshot of the last tick (d_obs_now[obs_set])
-    bool score_own_stream = false;   // env DMPP_SCORE_STREAM=1 | 2 (measurement knob): k_score on one stream of its own, lowest | highest queue priority
-    bool score_stream_high = false;
-    bool front_wait = false;         // env DMPP_FRONT_WAIT=1 (measurement knob): the front chain waits for the search kBuf ticks back, as in rounds 1 - 2
     int n_cus = 256;
     int pipeline_min = 256;      // batches at least this large run the three chains on three streams (env DMPP_PIPELINE_MIN)
     bool r_on_main = false;      // the last tick ran Decision + Planning on the handle's stream (grid stage off)
@@ -257,11 +276,11 @@ struct pp_planner {
     InputSet in_sets[kIn]; int in_cur = 0, in_staged = -1;
     DevBuf<PlanOut> d_plan_ring[kPlan]; int plan_cur = 0;
     hipStream_t stream_up = nullptr, stream_dp = nullptr, stream_dg = nullptr;   // upload; download of PlanOut; download of GridOut
-    hipEvent_t ev_fetched_plan[kPlan] = {}, ev_fetched_grid[kGout] = {}; bool fetched_plan_rec[kPlan] = {}, fetched_grid_rec[kGout] = {};
-    hipEvent_t ev_done_p[kDone] = {}, ev_done_g[kDone] = {}; long long done_tick[kDone]; bool done_p_rec[kDone] = {}, done_g_rec[kDone] = {};
+    SyncPoint fetched_plan[kPlan], fetched_grid[kGout];       // behind the last download that read that PlanOut / GridOut set
+    SyncPoint done_p[kDone], done_g[kDone]; long long done_tick[kDone];      // behind the downloads of tick done_tick[slot]
     HostPin<int32_t> h_bad;      // pinned, [kDone]: poisoned scenes of the tick (copied down with its PlanOut)
     long long tick_seq = 0;      // ticks enqueued so far on this handle (the id of the last one)
-    TickRec last_rec = { -1, 0, nullptr, nullptr };
+    TickRec rec_last = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
     // one block per rollout feature
@@ -426,8 +445,8 @@ int pump_fetches(pp_planner* h, long long force_tick = -1, int force_plan_set = 
                 const char* base = reinterpret_cast<const char*>(f.plan_src);
                 if (f.res_dst) HIP_TRY(hipMemcpy2DAsync(f.res_dst, sizeof(PlanningOut), base + offsetof(PlanOut, result), sizeof(PlanOut), sizeof(PlanningOut), f.n, hipMemcpyDefault, h->stream_dp));
                 if (f.show_dst) HIP_TRY(hipMemcpy2DAsync(f.show_dst, sizeof(PlanningStatus), base + offsetof(PlanOut, show), sizeof(PlanOut), sizeof(PlanningStatus), f.n, hipMemcpyDefault, h->stream_dp));
-                HIP_TRY(hipEventRecord(h->ev_fetched_plan[f.plan_set], h->stream_dp)); h->fetched_plan_rec[f.plan_set] = true;
-                HIP_TRY(hipEventRecord(h->ev_done_p[f.slot], h->stream_dp));
+                PP_TRY(h->fetched_plan[f.plan_set].record(h->stream_dp));
+                PP_TRY(h->done_p[f.slot].record(h->stream_dp));
                 f.plan_issued = true;
             }
         }
@@ -438,8 +457,8 @@ int pump_fetches(pp_planner* h, long long force_tick = -1, int force_plan_set = 
                 (void)hipGetLastError();
                 if (!ready) HIP_TRY(hipStreamWaitEvent(h->stream_dg, dep, 0));
                 HIP_TRY(hipMemcpyAsync(f.grid_dst, f.grid_src, f.n * sizeof(GridOut), hipMemcpyDefault, h->stream_dg));
-                HIP_TRY(hipEventRecord(h->ev_fetched_grid[f.grid_set], h->stream_dg)); h->fetched_grid_rec[f.grid_set] = true;
-                HIP_TRY(hipEventRecord(h->ev_done_g[f.slot], h->stream_dg));
+                PP_TRY(h->fetched_grid[f.grid_set].record(h->stream_dg));
+                PP_TRY(h->done_g[f.slot].record(h->stream_dg));
                 f.grid_issued = true;
             }
         }
@@ -453,8 +472,8 @@ int pump_fetches(pp_planner* h, long long force_tick = -1, int force_plan_set = 
 }
 
 // ticks whose kernels have all finished leave the in-flight list (oldest first; the list stays short: a tick's front chain
-// waits for the scoring pass 2 * kBuf ticks before it).  Their events go back to the pool: last_rec may still name the
-// events of the last tick, which are recorded again by the next tick at the earliest - and then last_rec names that one.
+// waits for the scoring pass 2 * kBuf ticks before it).  Their events go back to the pool: rec_last may still name the
+// events of the last tick, which are recorded again by the next tick at the earliest - and then rec_last names that one.
 int prune_inflight(pp_planner* h)
 {
     size_t k = 0;
@@ -500,24 +519,15 @@ int group_size(int n, int search_slots, int gcap, int forced)
 
 int flush_group(pp_planner* h);
 
-// A stream wait for an event - unless it has completed: then no barrier packet is needed (uploads and downloads run ticks ahead /
-// behind the chains that wait for them)
-hipError_t wait_unless_done(hipStream_t st, hipEvent_t e)
-{
-    if (hipEventQuery(e) == hipSuccess) return hipSuccess;
-    (void)hipGetLastError();
-    return hipStreamWaitEvent(st, e, 0);
-}
-
 // Everything the ticks enqueued so far started - on any of the four streams - is ordered before whatever the handle's
-// stream does next: ev_score[q] closes the raster -> search -> score chain of the last group that used snapshot set q, ev_join
+// stream does next: scored[q] closes the raster -> search -> score chain of the last group that used snapshot set q, join
 // the Decision -> Planning chain (stream order covers the earlier ticks).  An open tick group is launched first.  No host wait.
 int join_all(pp_planner* h)
 {
     { int r = flush_group(h); if (r) return r; }
-    for (int q = 0; q < kObs; q++) if (h->score_recorded[q]) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_score[q], 0));
-    if (h->front_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-    if (h->score.recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->score.ev, 0));
+    for (const SyncPoint& sp : h->scored) PP_TRY(sp.wait(h->stream));
+    PP_TRY(h->join.wait(h->stream));
+    PP_TRY(h->score.ego.wait(h->stream));
     return PP_OK;
 }
 
@@ -567,7 +577,7 @@ int setup_grid_launch(pp_planner* h)
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess && (size_t)v > lds_max) lds_max = (size_t)v;
     }
-    if (lds_max > 160u * 1024u) lds_max = 160u * 1024u;
+    lds_max = std::min(lds_max, dmpp::kLdsPerCu);
     h->gbm_lds = (int)(((size_t)c.grid_w + c.grid_h) * 8);
     if (std::max((size_t)h->search_meta_bytes + 2 * 64 * 4, (size_t)h->gbm_lds) + static_lds > lds_max)
         return fail(PP_ERR_CAPACITY, "grid too large for the search kernel's LDS tables");
@@ -599,31 +609,23 @@ int setup_grid_launch(pp_planner* h)
         h->lds_budget = std::max(1, std::min(std::atoi(e), h->lds_budget_max)); h->lds_budget_fixed = true;
     } else h->lds_budget = 0;                                                                            // chosen at the first tick (obstacle density), then adaptive
     const size_t items = (size_t)h->gcap * h->caps.max_scenes;          // work items of a search set
+    auto zeroed_once = [&](DevBuf<int32_t>& b, size_t count) {           // allocated - and cleared - by the first configuration with the grid stage
+        if (b) return (int)PP_OK;
+        PP_TRY(b.reserve(count));
+        HIP_TRY(hipMemsetAsync(b, 0, count * sizeof(int32_t), h->stream));
+        return (int)PP_OK;
+    };
     for (int q = 0; q < kBuf; q++) {
-        if (!h->d_ovf[q]) {
-            int r = h->d_ovf[q].reserve(items); if (r) return r;
-            HIP_TRY(hipMemsetAsync(h->d_ovf[q], 0, items * sizeof(int32_t), h->stream));
-        }
-        if (!h->d_retry[q]) { int r = h->d_retry[q].reserve(items); if (r) return r; }
+        PP_TRY(zeroed_once(h->d_ovf[q], items)); PP_TRY(zeroed_once(h->d_perm[q], items)); PP_TRY(zeroed_once(h->d_cost[q], items));
+        if (!h->d_retry[q]) PP_TRY(h->d_retry[q].reserve(items));
     }
-    for (int q = 0; q < kObs; q++)
-        if (!h->d_need[q]) { int r = h->d_need[q].reserve((size_t)2); if (r) return r; HIP_TRY(hipMemsetAsync(h->d_need[q], 0, 2 * sizeof(int32_t), h->stream)); }   // [0] LDS need of the search, [1] its retry count
+    for (int q = 0; q < kObs; q++) PP_TRY(zeroed_once(h->d_need[q], 2));   // [0] LDS need of the search, [1] its retry count
     { int r = h->h_need.alloc(kObs); if (r) return r; }
     for (int q = 0; q < kObs; q++) h->h_need[q] = -1;       // (a new configuration: what earlier searches needed says nothing; no search is in flight here)
     h->budget_from_need = false;
     if (!h->d_gridbad) { int r = h->d_gridbad.reserve((size_t)2); if (r) return r; }
     if (sizeof(dmpp::ScoreShared<16>) > 48u * 1024u)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dmpp::k_score<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(dmpp::ScoreShared<16>));
-    for (int q = 0; q < kBuf; q++) {
-        if (!h->d_perm[q]) {
-            int r = h->d_perm[q].reserve(items); if (r) return r;
-            HIP_TRY(hipMemsetAsync(h->d_perm[q], 0, items * sizeof(int32_t), h->stream));
-        }
-        if (!h->d_cost[q]) {
-            int r = h->d_cost[q].reserve(items); if (r) return r;
-            HIP_TRY(hipMemsetAsync(h->d_cost[q], 0, items * sizeof(int32_t), h->stream));
-        }
-    }
     // the dense form of the two views (row- then column-major), only written by the scenes that do not fit the LDS budget
     for (int q = 0; q < kBuf; q++) { int r = h->d_gbm[q].reserve(items * 2 * (h->grid_cells / 32)); if (r) return r; }
     return PP_OK;
@@ -661,7 +663,7 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     auto bail = [&](int code) { pp_destroy(h); return code; };
     // Queue priorities.  The FRONT chain (obstacle snapshot, Decision, Planning) is a short serial chain that every tick's
     // search waits for: it gets the highest dispatch priority (and its waves raise their issue priority, s_setprio).  The
-    // searches are the bulk of the work and overlap each other: normal priority.  Scoring fills what is left: lowest.
+    // searches are the bulk of the work and overlap each other, each followed on its stream by its scoring pass: normal priority.
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     const int prio_normal = (prio_least + prio_greatest) / 2;
@@ -669,33 +671,12 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     h->stream_m[0] = h->stream;
     for (int q = 1; q < kBuf; q++)
         if (hipStreamCreateWithPriority(&h->stream_m[q], hipStreamNonBlocking, prio_normal) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipStreamCreate failed"));
-    // DMPP_SIDE_CUS=<n>: measurement knob - the front and score streams may only use the first n CUs (0 / unset: all of them)
-    int side_cus = 0;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->n_cus = prop.multiProcessorCount;
-        if (const char* e = std::getenv("DMPP_SIDE_CUS")) side_cus = std::atoi(e);
-    }
-    uint32_t cu_mask[32] = { 0 };
-    if (side_cus > 1024) side_cus = 1024;
-    for (int i = 0; i < side_cus; i++) cu_mask[i >> 5] |= 1u << (i & 31);
-    const uint32_t cu_words = (uint32_t)((side_cus + 31) / 32);
-    if (side_cus > 0 && hipExtStreamCreateWithCUMask(&h->stream_r, cu_words, cu_mask) != hipSuccess) { (void)hipGetLastError(); h->stream_r = nullptr; side_cus = 0; }
-    if (side_cus > 0 && hipExtStreamCreateWithCUMask(&h->stream_s, cu_words, cu_mask) != hipSuccess) { (void)hipGetLastError(); h->stream_s = nullptr; }
-    if (const char* e = std::getenv("DMPP_OVERLAP")) h->overlap_override = std::atoi(e);
-    if (const char* e = std::getenv("DMPP_SCORE_STREAM")) { h->score_own_stream = std::atoi(e) != 0; h->score_stream_high = std::atoi(e) == 2; }
-    if (const char* e = std::getenv("DMPP_FRONT_WAIT")) h->front_wait = std::atoi(e) != 0;
-    if (!h->stream_r)
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->n_cus = prop.multiProcessorCount;
     if (hipStreamCreateWithPriority(&h->stream_r, hipStreamNonBlocking, prio_greatest) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipStreamCreate failed"));
-    if (!h->stream_s)
-    if (hipStreamCreateWithPriority(&h->stream_s, hipStreamNonBlocking, h->score_stream_high ? prio_greatest : prio_least) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipStreamCreate failed"));
-    if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_raster, hipEventDisableTiming) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipEventCreate failed"));
-    for (int q = 0; q < kBuf; q++)
-        if (hipEventCreateWithFlags(&h->ev_search[q], hipEventDisableTiming) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipEventCreate failed"));
-    for (int q = 0; q < kObs; q++)
-        if (hipEventCreateWithFlags(&h->ev_score[q], hipEventDisableTiming) != hipSuccess) return bail(fail(PP_ERR_HIP, "hipEventCreate failed"));
+    // the one-stream tick records these two every tick: created here, off the latency path (the piped, streamed and rollout paths
+    // create theirs at the first record)
+    if ((r = h->fork.create()) || (r = h->join.create())) return bail(r);
     const size_t ns = (size_t)caps->max_scenes;
     if ((r = h->in_sets[0].d_in.reserve(ns))) return bail(r);
     if ((r = h->d_lane.reserve((size_t)caps->max_lane_pts_total))) return bail(r);
@@ -756,21 +737,13 @@ int pp_destroy(pp_handle h)
     if (!h) return PP_OK;
     (void)hipSetDevice(h->device);
     (void)flush_group(h);                     // (the open group's work buffers go with the handle: its launches are enqueued and waited for)
-    if (h->stream_dg == h->stream_dp) h->stream_dg = nullptr;
-    if (h->stream_dp == h->stream_up) h->stream_dp = nullptr;
     // every stream is idle before the first buffer is released (the buffers go last, with the handle)
-    std::vector<hipStream_t> streams = { h->stream, h->stream_r, h->stream_s, h->stream_up, h->stream_dp, h->stream_dg };
+    std::vector<hipStream_t> streams = { h->stream, h->stream_r, h->stream_up, h->stream_dp, h->stream_dg };
     for (int q = 1; q < kBuf; q++) streams.push_back(h->stream_m[q]);      // (stream_m[0] is the handle's stream)
     for (hipStream_t st : streams) if (st) (void)hipStreamSynchronize(st);
     for (auto& p : h->pending) { h->free_events.push_back(p.a); h->free_events.push_back(p.b); }
     for (auto& r : h->inflight) { h->sync_events.push_back(r.ev_front); h->sync_events.push_back(r.ev_tail); }
-    for (const InputSet& I : h->in_sets) h->sync_events.push_back(I.ev_up);
-    for (auto* evs : { &h->free_events, &h->sync_events }) for (hipEvent_t e : *evs) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : { h->ev_fork, h->ev_join, h->ev_raster, h->rollout.ev_adv, h->score.ev }) if (e) (void)hipEventDestroy(e);
-    auto destroy_all = [](hipEvent_t* ev, int count) { for (int q = 0; q < count; q++) if (ev[q]) (void)hipEventDestroy(ev[q]); };
-    destroy_all(h->ev_search, kBuf); destroy_all(h->ev_score, kObs);
-    destroy_all(h->ev_fetched_plan, kPlan); destroy_all(h->ev_fetched_grid, kGout);
-    destroy_all(h->ev_done_p, kDone); destroy_all(h->ev_done_g, kDone);
+    for (auto* evs : { &h->free_events, &h->sync_events }) for (hipEvent_t e : *evs) if (e) (void)hipEventDestroy(e);      // the two pools; every SyncPoint goes with the handle
     for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
     delete h;
     return PP_OK;
@@ -801,7 +774,7 @@ int pp_set_config(pp_handle h, const PlannerConfig* cfg)
 static int reset_ego_flags(pp_handle h)
 {
     if (!h->rollout.d_flags) return PP_OK;
-    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    PP_TRY(h->rollout.adv.wait(h->stream));
     HIP_TRY(hipMemsetAsync(h->rollout.d_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), h->stream));
     return PP_OK;
 }
@@ -959,7 +932,7 @@ int pp_get_scene_in(pp_handle h, SceneIn* out, int n)
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
     if (h->in_staged >= 0 && h->rollout.staged_by_advance) {      // the records the advance produced for the next tick exist only on the device
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));
+        PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
         return fetch(h, out, h->in_sets[h->in_staged].d_in, (size_t)n * sizeof(SceneIn));
     }
     return fetch(h, out, h->d_in, (size_t)n * sizeof(SceneIn));
@@ -994,10 +967,32 @@ int pp_set_state(pp_handle h, const SceneState* state, int n)
 
 namespace {
 
+// One tick = two chains.  FRONT (stream_r, highest priority): obstacle snapshot, Decision, Planning - short kernels, serial
+// from tick to tick through SceneState.  SEARCH (stream_m[k % kBuf] for tick group k): launch order, k_search,
+// k_search_spill, k_score - the long one, for the G ticks of the group at once (flush_group).  Consecutive searches overlap: a
+// search ends with a handful of long scenes and would leave most of the chip idle, so the searches of kBuf consecutive groups
+// run side by side on their own streams, each followed on its stream by its own scoring pass.
+//   search(k) waits for the snapshot of the front chain of its last tick [raster] - the front chain is one stream, so that covers
+//             all G - and follows score(k - kBuf) on its stream;
+//   front(t)  waits for score(k - 2 kBuf), the last reader of the snapshot set it overwrites - so it may run up to 2 kBuf
+//             groups ahead of the scoring.
+// What a search and its scoring pass write exists kBuf times (closed sets, orders, ...: work buffers of G * n items), what
+// the scoring pass reads beside later searches once per (group position, slot) - kObs times (snapshot, path cells, LDS need),
+// GridOut kGout times.  The search of a tick is a function of its inputs and its snapshot alone, so which ticks share a launch
+// changes no result.
+// Small batches and ticks without the grid stage stay on one stream, one tick per group (a cross-stream hand-over costs tens
+// of microseconds; only Decision + Planning run beside the grid engine there); so do streamed ticks (pp_update_async /
+// pp_fetch_async: every tick is fetched, and its downloads wait for its own scoring pass).
+// (a tick without the grid stage leaves the search buffers alone: pp_get_grid_out / pp_get_path keep returning the last search)
+struct TickStreams { hipStream_t front, dp, search, score; };          // dp: Decision + Planning
+TickStreams tick_streams(const pp_planner* h, bool piped, bool grid_stage, int parity)
+{
+    hipStream_t search = piped ? h->stream_m[parity] : h->stream;
+    return { piped ? h->stream_r : h->stream, grid_stage ? h->stream_r : h->stream, search, search };
+}
+
 // Launches the searches and scoring passes of the open tick group (nothing when no group is open): one k_order (when the work
 // items outnumber the search's workgroup slots), one k_search, one k_search_spill and one k_score over the G * n work items.
-//   search(group k) follows score(group k - kBuf) on its stream (and waits for it when scoring has a stream of its own) and
-//   waits for the snapshot of its last tick's front chain [ev_raster] - the front chain is one stream, so that covers all G.
 int flush_group(pp_planner* h)
 {
     const int G = h->grp_ticks;
@@ -1005,19 +1000,17 @@ int flush_group(pp_planner* h)
     h->grp_ticks = 0;
     const PlannerConfig& c = h->cfg;
     const int n = h->grp_n, items = G * n, p = h->parity;
-    const bool piped = h->grp_piped, overlap = h->grp_overlap;
-    hipStream_t sm = overlap ? h->stream_m[p] : h->stream;             // search chain
-    hipStream_t sf = piped ? h->stream_r : h->stream;                  // front chain
-    hipStream_t ss = piped ? ((overlap && !h->score_own_stream) ? sm : h->stream_s) : h->stream; // score chain: behind its own search when the searches overlap
-    hipStream_t sr = h->stream_r;                                      // Decision + Planning (grid stage)
+    const bool piped = h->grp_piped;
+    const TickStreams T = tick_streams(h, piped, true, p);
+    hipStream_t sm = T.search, ss = T.score;
     // Work buffers p were last used by group k - kBuf (its tick slot 0 used snapshot set set_b)
     const int set0 = h->grp_set[0], set_b = ((h->ring + kBuf) % kRing) * kGroupMax;
-    if (h->score_recorded[set_b] && ss == sm) HIP_TRY(hipStreamWaitEvent(sm, h->ev_score[set_b], 0));     // (own scoring stream: path cells and LDS need exist per snapshot set, the search does not wait for that scoring)
-    if (!overlap)                                                      // one search at a time (also after a switch of mode)
-        for (int q = 0; q < kBuf; q++) if (q != p && h->search_recorded[q]) HIP_TRY(hipStreamWaitEvent(sm, h->ev_search[q], 0));
-    if (sf != sm) HIP_TRY(hipStreamWaitEvent(sm, h->ev_raster, 0));
+    PP_TRY(h->scored[set_b].wait(sm));
+    if (!piped)                                                        // one search at a time (also after a switch of mode)
+        for (int q = 0; q < kBuf; q++) if (q != p) PP_TRY(h->searched[q].wait(sm));
+    if (T.front != sm) PP_TRY(h->raster.wait(sm));
     for (int i = 0; i < G; i++)
-        if (h->streaming && h->fetched_grid_rec[h->grp_gs[i]]) HIP_TRY(wait_unless_done(sm, h->ev_fetched_grid[h->grp_gs[i]]));   // GridOut set still being downloaded
+        if (h->streaming) PP_TRY(h->fetched_grid[h->grp_gs[i]].wait_unless_done(sm));   // GridOut set still being downloaded
     dmpp::TickGroup tg;                                                // slot i: sets grp_set[0] + i, grp_gs[0] + i
     tg.n = n; tg.in = h->grp_in;
     tg.obs_now = h->d_obs_now[set0]; tg.obs_stride = std::max(h->caps.max_obs_total, 1);
@@ -1026,12 +1019,9 @@ int flush_group(pp_planner* h)
     // launch order of the search (heaviest work items first) - pointless while every item is resident at once.  Keyed by the
     // times of the group kBuf back, the one before it on its stream (one-stream tick: by the previous one's).
     const bool order_scenes = items > h->search_slots;
-    // DMPP_FRONT_WAIT=1: the last front of a FULL group has launched k_order over G * n items (pp_plan_tick); a group flushed
-    // early (pp_sync, a getter, ...) gets its launch order here, over the items it has
-    const bool order_in_front = order_scenes && piped && h->front_wait && G == h->grp_G;
     const int32_t* perm = order_scenes ? h->d_perm[p] : nullptr;
-    if (perm && !order_in_front)
-        hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sm, items, h->d_cost[overlap ? p : h->grp_p_prev], h->d_perm[p]);
+    if (perm)
+        hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sm, items, h->d_cost[piped ? p : h->grp_p_prev], h->d_perm[p]);
     int32_t* need = h->d_need[set0];                                   // the group's LDS need and retry count
     {
         const int budget = h->search_force_gbm ? 0 : h->lds_budget;
@@ -1056,8 +1046,8 @@ int flush_group(pp_planner* h)
 #undef DMPP_LAUNCH_SEARCH
         }
     }
-    h->search_recorded[p] = piped;                   // (one-stream mode: stream order is enough, no events on the latency path)
-    if (piped) { HIP_TRY(hipEventRecord(h->ev_search[p], sm)); HIP_TRY(hipStreamWaitEvent(ss, h->ev_search[p], 0)); }
+    if (piped) PP_TRY(h->searched[p].record(sm));     // (what a later one-stream group waits for)
+    else h->searched[p].forget();                     // (one-stream mode: stream order is enough, no events on the latency path)
     {
         Timed t(h, PP_K_SCORE, ss, G);
         int32_t* need_host = (!h->lds_budget_fixed && !h->search_force_gbm) ? &h->h_need[set0] : nullptr;
@@ -1066,19 +1056,41 @@ int flush_group(pp_planner* h)
         else
             hipLaunchKernelGGL(dmpp::k_score<4>, dim3(items), dim3(4 * DMPP_WAVE), sizeof(dmpp::ScoreShared<4>), ss, c, items, tg, need, need_host);
     }
-    if (h->score.grp_scored) {                             // scorecard, grid half: behind the tick's k_score, in front of ev_score / the tick's ev_tail (a scored tick is a group of 1)
+    if (h->score.grp_scored) {                             // scorecard, grid half: behind the tick's k_score, in front of scored[] / the tick's ev_tail (a scored tick is a group of 1)
         hipLaunchKernelGGL(dmpp::k_score_grid, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, ss,
                            n, std::min(c.n_lattice, DMPP_MAX_LATTICE - 1), h->d_gout[h->grp_gs[G - 1]], h->score.d_grid[p]);
         h->score.grp_scored = false;
     }
     for (int i = 0; i < G; i++) {                    // the group's scoring pass is the last reader of its G snapshot sets
-        h->score_recorded[h->grp_set[i]] = piped;
-        if (piped) HIP_TRY(hipEventRecord(h->ev_score[h->grp_set[i]], ss));
+        if (piped) PP_TRY(h->scored[h->grp_set[i]].record(ss));
+        else h->scored[h->grp_set[i]].forget();
     }
-    if (!piped && sr != h->stream) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));   // one-stream mode: the tick is complete on the handle's stream
+    if (!piped) PP_TRY(h->join.wait(h->stream));     // one-stream mode: the tick is complete on the handle's stream
     h->need_set = set0; h->item_off = (G - 1) * n;
     HIP_TRY(hipGetLastError());
     return PP_OK;
+}
+
+// Opens a tick group at the next ring positions: its size G - from the workgroup slots the last group's budget gave -, then the
+// LDS budget of its search (dmpp::search_budget).  The need of the densest scene of an earlier group: the scoring pass behind
+// each search stores it in pinned memory, which is simply read here - whatever has landed; never waited for.
+void open_group(pp_planner* h, int n, bool piped)
+{
+    const bool grid = h->cfg.grid_stage != 0;
+    h->grp_p_prev = h->parity;
+    if (grid) { h->parity = (h->parity + 1) % kBuf; h->gring = (h->gring + 1) % kGoutRing; }
+    h->ring = (h->ring + 1) % kRing;
+    h->grp_G = (piped && !h->streaming) ? group_size(n, h->search_slots, h->gcap, h->tick_group) : 1;
+    h->grp_n = n; h->grp_piped = piped;
+    if (!grid) return;
+    int need = -1;
+    if (!h->lds_budget_fixed && !h->search_force_gbm) {
+        for (int q = 0; q < kBuf; q++) need = std::max(need, (int)reinterpret_cast<volatile int32_t*>(h->h_need.get())[((h->ring + kRing - 1 - q) % kRing) * kGroupMax]);     // the last kBuf groups' sets
+        if (need >= 0) h->need_seen = need;
+    }
+    const dmpp::SearchBudget b = dmpp::search_budget(h->search_static_lds, h->search_meta_bytes, h->gbm_lds, h->lds_budget_max, h->n_cus, n, h->grp_G, h->n_obs_total,
+                                                     need, h->lds_budget, h->budget_from_need, h->lds_budget_fixed, h->search_force_gbm);
+    h->lds_budget = b.budget; h->budget_from_need = b.from_need; h->search_slots = b.slots;
 }
 
 }  // namespace
@@ -1094,34 +1106,12 @@ int pp_plan_tick(pp_handle h)
     const PlannerConfig& c = h->cfg;
     if (c.decision_stage && c.lanechg_stage && !h->have_attr)
         return fail(PP_ERR_ARG, "cfg.lanechg_stage needs the lane attribute pool (pp_set_scenes lane_attr_pool)");
-    // One tick = two chains.  FRONT (stream_r, highest priority): obstacle snapshot, Decision, Planning - short kernels, serial
-    // from tick to tick through SceneState.  SEARCH (stream_m[k % kBuf] for tick group k): (launch order,) k_search,
-    // k_search_spill, k_score - the long one, for the G ticks of the group at once (flush_group); the searches of kBuf
-    // consecutive groups run side by side on their own streams.
-    //   search(k) waits for the snapshot of the front chain of its last tick [ev_raster] and follows score(k - kBuf) on its stream;
-    //   front(t)  waits for score(k - 2 kBuf), the last reader of the snapshot set it overwrites - so it may run up to 2 kBuf
-    //             groups ahead of the scoring.
-    // What a search and its scoring pass write exists kBuf times (closed sets, orders, ...: work buffers of G * n items), what
-    // the scoring pass reads beside later searches once per (group position, slot) - kObs times (snapshot, path cells, LDS need),
-    // GridOut kGout times.  The search of a tick is a function of its inputs and its snapshot alone, so which ticks share a launch
-    // changes no result.
-    // Small batches and ticks without the grid stage stay on one stream, one tick per group (a cross-stream hand-over costs tens
-    // of microseconds; only Decision + Planning run beside the grid engine there); so do streamed ticks (pp_update_async /
-    // pp_fetch_async: every tick is fetched, and its downloads wait for its own scoring pass).
-    // (a tick without the grid stage leaves the search buffers alone: pp_get_grid_out / pp_get_path keep returning the last search)
-    const bool piped = c.grid_stage && n >= h->pipeline_min;
-    const bool open = h->grp_ticks == 0;
+    const bool piped = c.grid_stage && n >= h->pipeline_min;           // the chains and their streams: tick_streams
     // streamed inputs: the update staged by pp_update_async becomes the set this tick (and the following ones) read
     bool adopted = false;
     if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; h->rollout.staged_by_advance = false; adopted = true; }
-    if (open) {
-        h->grp_p_prev = h->parity;
-        if (c.grid_stage) { h->parity = (h->parity + 1) % kBuf; h->gring = (h->gring + 1) % kGoutRing; }
-        h->ring = (h->ring + 1) % kRing;
-        h->grp_G = (piped && !h->streaming) ? group_size(n, h->search_slots, h->gcap, h->tick_group) : 1;
-        h->grp_n = n; h->grp_piped = piped;
-    }
-    const int slot = h->grp_ticks, G = h->grp_G, p = h->parity;
+    if (h->grp_ticks == 0) open_group(h, n, piped);
+    const int slot = h->grp_ticks, G = h->grp_G;
     const int po = h->ring * kGroupMax + slot;                                        // this tick's snapshot set
     const int gs = c.grid_stage ? h->gring * kGroupMax + slot : h->gout_set;          // ... and GridOut set
     if (h->streaming) {
@@ -1131,96 +1121,36 @@ int pp_plan_tick(pp_handle h)
         h->plan_cur = (h->plan_cur + 1) % kPlan; h->d_plan = h->d_plan_ring[h->plan_cur];
         if (!adopted) h->h_bad[(h->tick_seq + 1) % kDone] = 0;
     }
-    if (open && c.grid_stage && !h->search_force_gbm) {
-        // LDS budget of the group's search (data words per view).  First tick: from the obstacle density; afterwards from what
-        // the densest scene of an earlier group needed (+ 1/8): the scoring pass behind each search stores it in pinned memory,
-        // which is simply read here - whatever has landed; never waited for.
-        const int items = G * n;
-        if (!h->lds_budget_fixed) {
-            int need = -1;
-            for (int q = 0; q < kBuf; q++) need = std::max(need, (int)reinterpret_cast<volatile int32_t*>(h->h_need.get())[((h->ring + kRing - 1 - q) % kRing) * kGroupMax]);     // the last kBuf groups' sets
-            int want = h->lds_budget;
-            if (need >= 0) {
-                h->need_seen = need;
-                const int fit = std::min(h->lds_budget_max, (need + need / 8 + 64 + 63) / 64 * 64);
-                // Workgroups per CU at a budget (the 160 KB of LDS are handed out in 128 granules of 1,280 bytes - measured: 54,000 bytes per
-                // workgroup are two per CU, 52,976 three, 26,864 six).
-                // When the work items outnumber the workgroup slots and a smaller - still safe - slack over the need lets one more
-                // searching workgroup onto every CU, the largest budget that does is taken: 256 moving obstacles need ~4,650 words,
-                // 5,312 with the usual eighth on top = two workgroups of 55 KB per CU; three fit at <= 5,120 (configs[3]: 1.14 -> 1.23 M
-                // ticks/s); 4096 scenes of 64 obstacles: six of 26.9 KB instead of five of 27.9 (5.17 -> 5.30 M).  With a slot for every
-                // item the eighth stays: the room it leaves on the CU is what the front kernels start in.  A scene that outgrows the
-                // budget takes the dense form in HBM.
-                const size_t fixed_lds = h->search_static_lds + 64 + (size_t)h->search_meta_bytes;
-                constexpr size_t kLdsGranule = 1280;
-                auto wgs_at = [&](int b) { return (int)std::min<size_t>(8, (160u * 1024u) / ((fixed_lds + 8 * (size_t)b + kLdsGranule - 1) / kLdsGranule * kLdsGranule)); };
-                int target = fit;
-                const int tight = std::min(h->lds_budget_max, (need + std::max(need / 32, 96) + 63) / 64 * 64);
-                if (tight < fit && wgs_at(tight) > wgs_at(fit) && items > wgs_at(fit) * std::max(1, h->n_cus)) {
-                    const size_t room = (160u * 1024u) / (size_t)wgs_at(tight) / kLdsGranule * kLdsGranule;
-                    const int lim = room > fixed_lds ? (int)((room - fixed_lds) / 8 / 64 * 64) : 0;
-                    target = std::max(tight, std::min(lim, fit));
-                }
-                // (the first need that arrives replaces the first tick's guess outright: 64 obstacles were guessed at 2,048 words, need
-                // 1,635, and the hysteresis kept the guess - 28.2 KB per workgroup, 18.8 KB free beside five of them, 0.5 KB short of
-                // a k_decision workgroup; at 1,920 it fits: +1 % at 1024 scenes, +3 % at 4096)
-                if (!h->budget_from_need || target > h->lds_budget || target < h->lds_budget - h->lds_budget / 4 || (h->lds_budget > 0 && wgs_at(target) > wgs_at(h->lds_budget))) want = target;
-                h->budget_from_need = true;
-            }
-            if (want <= 0) {
-                const long long per_scene = ((long long)h->n_obs_total + n - 1) / n;
-                want = (int)std::min<long long>(h->lds_budget_max, (28 * per_scene + 256 + 63) / 64 * 64);
-            }
-            h->lds_budget = std::max(64, std::min(want, h->lds_budget_max));
-        }
-        const size_t per_wg = h->search_static_lds + 64 + std::max((size_t)h->search_meta_bytes + 8 * (size_t)h->lds_budget, (size_t)h->gbm_lds);
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / per_wg));       // 4 waves per workgroup while it sets up: <= 8 per CU
-        h->search_slots = per_cu * std::max(1, h->n_cus);
-    } else if (open && c.grid_stage) {
-        const size_t per_wg = h->search_static_lds + 64 + (size_t)h->gbm_lds;
-        h->search_slots = (int)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / per_wg)) * std::max(1, h->n_cus);
-    }
-    // Consecutive searches overlap: a search ends with a handful of long scenes and would leave most of the chip idle; the searches
-    // of up to kBuf consecutive groups run on their own streams (every buffer a search or a scoring pass touches exists kBuf times).
-    bool overlap = piped;
-    if (h->overlap_override >= 0) overlap = piped && h->overlap_override != 0;      // env DMPP_OVERLAP (measurement knob)
-    if (open) h->grp_overlap = overlap;
-    hipStream_t sm = overlap ? h->stream_m[p] : h->stream;             // search chain
-    hipStream_t sf = piped ? h->stream_r : h->stream;                  // front chain
-    hipStream_t sr = c.grid_stage ? h->stream_r : h->stream;           // Decision + Planning
+    const TickStreams T = tick_streams(h, piped, c.grid_stage != 0, h->parity);
+    hipStream_t sf = T.front, sr = T.dp;
     // The front chain overwrites snapshot set po: it waits for the scoring pass of the last group that read it (2 kBuf groups back).
-    if (h->score_recorded[po]) HIP_TRY(hipStreamWaitEvent(sf, h->ev_score[po], 0));
-    // The front chain does not wait for the search kBuf groups back: it runs ahead - up to 2 kBuf groups, bounded by the snapshot
+    // It does not wait for the search kBuf groups back: it runs ahead - up to 2 kBuf groups, bounded by the snapshot
     // sets - so its kernels no longer start together with the scoring pass that follows that search (+ 2 %), and the launch order,
-    // which needs that search's times, is computed on the search's own stream.  DMPP_FRONT_WAIT=1: the old hand-over (measurement knob).
-    const bool front_wait = h->front_wait;
-    if (h->search_recorded[p] && front_wait) HIP_TRY(hipStreamWaitEvent(sf, h->ev_search[p], 0));
-    if (h->front_recorded && sf == h->stream && h->front_unjoined) HIP_TRY(hipStreamWaitEvent(sf, h->ev_join, 0));   // Planning(t-1) -> snapshot(t) when not on the same stream
+    // which needs that search's times, is computed on the search's own stream.
+    PP_TRY(h->scored[po].wait(sf));
+    if (sf == h->stream && h->front_unjoined) PP_TRY(h->join.wait(sf));   // Planning(t-1) -> snapshot(t) when not on the same stream
     h->front_unjoined = false;
     if (h->r_on_main && sf != h->stream) {         // Planning(t-1) ran on the handle's stream (grid stage off then): the front chain reads its state
-        HIP_TRY(hipEventRecord(h->ev_fork, h->stream)); HIP_TRY(hipStreamWaitEvent(sf, h->ev_fork, 0));
+        PP_TRY(h->fork.record(h->stream)); PP_TRY(h->fork.wait(sf));
     }
     h->r_on_main = sr == h->stream;
-    if (adopted && h->in_sets[h->in_cur].up_recorded) HIP_TRY(wait_unless_done(sf, h->in_sets[h->in_cur].ev_up));   // every kernel of the tick follows the snapshot kernel
-    if (h->streaming && h->fetched_plan_rec[h->plan_cur]) HIP_TRY(wait_unless_done(sr, h->ev_fetched_plan[h->plan_cur]));   // PlanOut set still being downloaded (kPlan ticks ago)
+    const SyncPoint& up = h->in_sets[h->in_cur].up;
+    const bool behind_upload = adopted && up.recorded();
+    if (behind_upload) PP_TRY(up.wait_unless_done(sf));                   // every kernel of the tick follows the snapshot kernel
+    if (h->streaming) PP_TRY(h->fetched_plan[h->plan_cur].wait_unless_done(sr));   // PlanOut set still being downloaded (kPlan ticks ago)
     // Scorecard: k_score_ego of the last scored tick (upload stream) reads the SceneState this front chain rewrites, and sets of the
-    // PlanOut and snapshot rings that a later one does.  A tick that adopts an update or an advance waits for that set's ev_up,
+    // PlanOut and snapshot rings that a later one does.  A tick that adopts an update or an advance waits for that set's `up`,
     // recorded behind the kernel on the same stream (staging always follows the tick it follows); any other tick waits here.
-    if (h->score.recorded) {
-        if (hipEventQuery(h->score.ev) == hipSuccess) h->score.recorded = false;
-        else { (void)hipGetLastError(); if (!(adopted && h->in_sets[h->in_cur].up_recorded)) HIP_TRY(hipStreamWaitEvent(sf, h->score.ev, 0)); }
-    }
+    if (h->score.ego.done()) h->score.ego.forget();
+    else if (!behind_upload) PP_TRY(h->score.ego.wait(sf));
     ObPoint* obs_now = h->d_obs_now[po];
     {
         Timed t(h, PP_K_OBSTACLES, sf);
         hipLaunchKernelGGL(dmpp::k_effective_obstacles, dim3(n), dim3(dmpp::kBlock), 0, sf, c, n, h->d_in, h->d_state,
                            h->d_obs, h->have_motion ? h->d_mot : nullptr, obs_now);
     }
-    if (sr != sf) { HIP_TRY(hipEventRecord(h->ev_fork, sf)); HIP_TRY(hipStreamWaitEvent(sr, h->ev_fork, 0)); }   // small batches: Decision + Planning beside the grid engine
-    const bool last_of_group = c.grid_stage && slot + 1 == G;
-    if (last_of_group && piped && front_wait && G * n > h->search_slots)        // DMPP_FRONT_WAIT=1: the launch order on the front chain, as in rounds 1 - 2
-        hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sf, G * n, h->d_cost[p], h->d_perm[p]);
-    if (c.grid_stage && sf != sm) HIP_TRY(hipEventRecord(h->ev_raster, sf));        // the search rasterises for itself: it only needs the obstacle snapshot (and its launch order)
+    if (sr != sf) { PP_TRY(h->fork.record(sf)); PP_TRY(h->fork.wait(sr)); }   // small batches: Decision + Planning beside the grid engine
+    if (c.grid_stage && sf != T.search) PP_TRY(h->raster.record(sf));        // the search rasterises for itself: it only needs the obstacle snapshot
     if (c.decision_stage) {
         Timed t(h, PP_K_DECISION, sr);
         hipLaunchKernelGGL(dmpp::k_decision, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, h->d_in, h->d_lane,
@@ -1231,29 +1161,29 @@ int pp_plan_tick(pp_handle h)
         hipLaunchKernelGGL(dmpp::k_planning, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::PlanShared), sr, c, n, h->d_in, h->d_lane,
                            h->d_ref, h->d_dec_ref, obs_now, h->d_state, h->d_plan);
     }
-    if (sr != h->stream) { HIP_TRY(hipEventRecord(h->ev_join, sr)); h->front_recorded = true; h->front_unjoined = piped; }
+    if (sr != h->stream) { PP_TRY(h->join.record(sr)); h->front_unjoined = piped; }
     h->obs_set = po;
     if (c.grid_stage) {
         h->grp_set[slot] = po; h->grp_gs[slot] = gs; h->grp_in = h->d_in;
         h->grp_ticks = slot + 1;
         h->gout_set = gs; h->path_set = po;
         h->score.grp_scored = h->score.on;
-        if (last_of_group) { int r = flush_group(h); if (r) return r; }
+        if (slot + 1 == G) { int r = flush_group(h); if (r) return r; }
     }
     h->last_piped = piped;
     h->tick_seq++;
     if (h->streaming) {          // what a later update of this tick's input set, and a download of its results, wait for
         TickRec rec = { h->tick_seq, h->in_cur, get_sync_event(h), c.grid_stage ? get_sync_event(h) : nullptr };
-        if (!rec.ev_front || (c.grid_stage && !rec.ev_tail)) return fail(PP_ERR_HIP, "hipEventCreate failed");
+        if (!rec.ev_front || (c.grid_stage && !rec.ev_tail)) return fail(PP_ERR_HIP, "event creation failed");
         HIP_TRY(hipEventRecord(rec.ev_front, sr));
-        if (rec.ev_tail) HIP_TRY(hipEventRecord(rec.ev_tail, piped ? (h->grp_overlap && !h->score_own_stream ? sm : h->stream_s) : h->stream));
-        h->inflight.push_back(rec); h->last_rec = rec;
+        if (rec.ev_tail) HIP_TRY(hipEventRecord(rec.ev_tail, T.score));
+        h->inflight.push_back(rec); h->rec_last = rec;
         if (h->score.on) {        // scorecard, front half: behind this tick's Planning kernel, on the upload stream - in front of the advance that may follow
             hipStream_t su = h->stream_up;
             HIP_TRY(hipStreamWaitEvent(su, rec.ev_front, 0));
             hipLaunchKernelGGL(dmpp::k_score_ego, dim3((unsigned)((n + dmpp::kScScenes - 1) / dmpp::kScScenes)), dim3(dmpp::kBlock), 0, su,
                                0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total, h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score);
-            HIP_TRY(hipEventRecord(h->score.ev, su)); h->score.recorded = true;
+            PP_TRY(h->score.ego.record(su));
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1351,7 +1281,6 @@ int pp_get_search_info(pp_handle h, int32_t* lds_budget_words, int32_t* need_wor
     { int r = flush_group(h); if (r) return r; }          // parity / item_off / need_set name the last tick only once its group is launched
     if (lds_budget_words) *lds_budget_words = h->search_force_gbm ? 0 : h->lds_budget;
     if (need_words) {                      // what the densest scene of the last tick needed (its scoring pass has stored it by now)
-        HIP_TRY(hipSetDevice(h->device));
         { int r = join_all(h); if (r) return r; }
         HIP_TRY(hipStreamSynchronize(h->stream));
         const int32_t v = reinterpret_cast<volatile int32_t*>(h->h_need.get())[h->need_set];
@@ -1420,7 +1349,6 @@ static int ensure_streaming(pp_handle h)
         if (!I.d_in && (r = I.d_in.reserve(ns))) return r;
         if (!I.d_obs && (r = I.d_obs.reserve(no))) return r;
         if (!I.d_mot) { if ((r = I.d_mot.reserve(no))) return r; HIP_TRY(hipMemsetAsync(I.d_mot, 0, no * sizeof(ObMotion), h->stream)); }
-        if (!I.ev_up) HIP_TRY(hipEventCreateWithFlags(&I.ev_up, hipEventDisableTiming));
     }
     for (int q = 1; q < kPlan; q++) if (!h->d_plan_ring[q]) {
         if ((r = h->d_plan_ring[q].reserve(ns))) return r;
@@ -1429,22 +1357,14 @@ static int ensure_streaming(pp_handle h)
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     // the upload carries two small kernels (map views, slice check) that the next front chain waits for: top priority
-    int io_streams = 3;
-    if (const char* e = std::getenv("DMPP_IO_STREAMS")) io_streams = std::atoi(e);       // measurement knob: 1 = one stream for upload and both downloads, 2 = one for the downloads
     if (!h->stream_up) HIP_TRY(hipStreamCreateWithPriority(&h->stream_up, hipStreamNonBlocking, prio_greatest));
-    if (!h->stream_dp) { if (io_streams <= 1) h->stream_dp = h->stream_up; else HIP_TRY(hipStreamCreateWithPriority(&h->stream_dp, hipStreamNonBlocking, prio_least)); }
-    if (!h->stream_dg) { if (io_streams <= 2) h->stream_dg = h->stream_dp; else HIP_TRY(hipStreamCreateWithPriority(&h->stream_dg, hipStreamNonBlocking, prio_least)); }
-    for (int q = 0; q < kPlan; q++) if (!h->ev_fetched_plan[q]) HIP_TRY(hipEventCreateWithFlags(&h->ev_fetched_plan[q], hipEventDisableTiming));
-    for (int q = 0; q < kGout; q++) if (!h->ev_fetched_grid[q]) HIP_TRY(hipEventCreateWithFlags(&h->ev_fetched_grid[q], hipEventDisableTiming));
-    for (int q = 0; q < kDone; q++) {
-        if (!h->ev_done_p[q]) HIP_TRY(hipEventCreateWithFlags(&h->ev_done_p[q], hipEventDisableTiming));
-        if (!h->ev_done_g[q]) HIP_TRY(hipEventCreateWithFlags(&h->ev_done_g[q], hipEventDisableTiming));
-    }
+    if (!h->stream_dp) HIP_TRY(hipStreamCreateWithPriority(&h->stream_dp, hipStreamNonBlocking, prio_least));
+    if (!h->stream_dg) HIP_TRY(hipStreamCreateWithPriority(&h->stream_dg, hipStreamNonBlocking, prio_least));
     if (!h->h_bad) { int r2 = h->h_bad.alloc(kDone); if (r2) return r2; for (int q = 0; q < kDone; q++) h->h_bad[q] = 0; }
     // everything enqueued before streaming began (ticks, the memsets above) is ordered before the three new streams
     { int r2 = join_all(h); if (r2) return r2; }
     hipEvent_t e = get_sync_event(h);
-    if (!e) return fail(PP_ERR_HIP, "hipEventCreate failed");
+    if (!e) return fail(PP_ERR_HIP, "event creation failed");
     HIP_TRY(hipEventRecord(e, h->stream));
     for (hipStream_t st : { h->stream_up, h->stream_dp, h->stream_dg }) HIP_TRY(hipStreamWaitEvent(st, e, 0));
     HIP_TRY(hipStreamSynchronize(h->stream));      // (once per handle) so that e can go back to the pool
@@ -1465,10 +1385,10 @@ struct StageSource {
 // (closed-loop rollout) always takes the set after the current one - its caller refuses while something is
 // staged - and puts k_advance_egos / k_advance_route in the place of the copy of the SceneIn records: the kernel reads what the
 // last tick's Planning kernel wrote (PlanOut, SceneState), so the upload stream waits for that tick's front-chain event, not for
-// its search; the next tick's front chain, the only writer of SceneState, waits for ev_up in turn.
+// its search; the next tick's front chain, the only writer of SceneState, waits for the set's `up` in turn.
 // Order on the upload stream: SceneIn records and obstacle pool -> k_move_traffic -> k_couple_fleet (the two write disjoint pool
 // entries: traffic a scene's own, the fleet the peer slots behind them, at the poses just staged) -> k_resolve_map ->
-// k_sanitise_scenes -> ev_up, which the tick that adopts the set waits for.
+// k_sanitise_scenes -> `up`, which the tick that adopts the set waits for.
 static int stage_inputs(pp_handle h, const StageSource& src)
 {
     const bool advance = src.ego != nullptr;
@@ -1480,7 +1400,6 @@ static int stage_inputs(pp_handle h, const StageSource& src)
     if (advance && !h->rollout.d_flags) {
         int r = h->rollout.d_flags.reserve((size_t)h->caps.max_scenes); if (r) return r;
         HIP_TRY(hipMemsetAsync(h->rollout.d_flags, 0, (size_t)h->caps.max_scenes * sizeof(int32_t), su));
-        HIP_TRY(hipEventCreateWithFlags(&h->rollout.ev_adv, hipEventDisableTiming));
     }
     const bool restage = h->in_staged >= 0;
     const int s = restage ? h->in_staged : (h->in_cur + 1) % kIn, n = h->n_scenes;
@@ -1491,7 +1410,7 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         HIP_TRY(hipStreamWaitEvent(su, r.ev_front, 0));
         if (r.ev_tail) HIP_TRY(hipStreamWaitEvent(su, r.ev_tail, 0));
     }
-    if (advance && h->last_rec.tick == h->tick_seq && h->last_rec.ev_front) HIP_TRY(hipStreamWaitEvent(su, h->last_rec.ev_front, 0));
+    if (advance && h->rec_last.tick == h->tick_seq && h->rec_last.ev_front) HIP_TRY(hipStreamWaitEvent(su, h->rec_last.ev_front, 0));
     if (src.in) HIP_TRY(hipMemcpyAsync(I.d_in, src.in, (size_t)n * sizeof(SceneIn), hipMemcpyDefault, su));
     else if (!advance && &P != &I) HIP_TRY(hipMemcpyAsync(I.d_in, P.d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, su));
     int n_obs = src.n_obs_total; bool have_motion = false;
@@ -1541,9 +1460,9 @@ static int stage_inputs(pp_handle h, const StageSource& src)
                            h->map_junctions, h->d_map_junc, bad_slot);
     hipLaunchKernelGGL(dmpp::k_sanitise_scenes, grid, block, 0, su, n, d_in, n_obs, h->n_lane_pts, h->n_ref_pts, bad_slot);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(I.ev_up, su));
-    if (advance) { HIP_TRY(hipEventRecord(h->rollout.ev_adv, su)); h->rollout.adv_recorded = true; }
-    I.up_recorded = true; I.have_motion = have_motion; I.n_obs_total = n_obs;
+    PP_TRY(I.up.record(su));
+    if (advance) PP_TRY(h->rollout.adv.record(su));
+    I.have_motion = have_motion; I.n_obs_total = n_obs;
     h->in_staged = s; if (advance) h->rollout.staged_by_advance = true;
     return PP_OK;
 }
@@ -1606,7 +1525,7 @@ int pp_get_ego_flags(pp_handle h, int32_t* flags, int n)
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
     if (!h->rollout.d_flags) { std::memset(flags, 0, (size_t)n * sizeof(int32_t)); return PP_OK; }
     HIP_TRY(hipSetDevice(h->device));
-    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    PP_TRY(h->rollout.adv.wait(h->stream));
     return fetch(h, flags, h->rollout.d_flags, (size_t)n * sizeof(int32_t));
 }
 
@@ -1622,7 +1541,6 @@ int pp_score_begin(pp_handle h, double dt_score)
         const size_t ns = (size_t)h->caps.max_scenes;
         int r = h->score.d_score.reserve(ns); if (r) return r;
         for (int q = 0; q < kBuf; q++) if ((r = h->score.d_grid[q].reserve(ns))) return r;
-        HIP_TRY(hipEventCreateWithFlags(&h->score.ev, hipEventDisableTiming));
     }
     { int r = join_all(h); if (r) return r; }            // the ticks scored so far (a restart) and everything before
     { int r = reset_scores(h); if (r) return r; }
@@ -1644,7 +1562,7 @@ int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
     if (!h->score.d_score) return fail(PP_ERR_STATE, "pp_get_rollout_score: pp_score_begin was never called on this handle");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
     HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }            // behind both halves: score.ev (k_score_ego), ev_score / stream order (k_score_grid)
+    { int r = join_all(h); if (r) return r; }            // behind both halves: score.ego (k_score_ego), scored[] / stream order (k_score_grid)
     std::vector<dmpp::ScoreGridPart> parts((size_t)kBuf * (size_t)std::max(n, 1));
     HIP_TRY(hipMemcpyAsync(out, h->score.d_score, (size_t)n * sizeof(RolloutScore), hipMemcpyDefault, h->stream));
     for (int q = 0; q < kBuf && n > 0; q++)
@@ -1820,7 +1738,7 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     for (size_t k = 1; k < taken.size(); k++)
         if (taken[k] == taken[k - 1]) return fail(PP_ERR_ARG, fn + ": two actors on slot " + std::to_string((int)(taken[k] & 0xffffffff)) + (world ? " of world " : " of scene ") + std::to_string((int)(taken[k] >> 32)));
     // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the old arrays
-    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    PP_TRY(h->rollout.adv.wait(h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     // room first.  An allocation that fails leaves its own array as it was, but may follow one that replaced another: the old
     // traffic then goes off rather than run on half a set
@@ -1862,8 +1780,8 @@ int pp_get_traffic_state(pp_handle h, double* s, int n)
     if (n < 0 || n > h->traffic.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
     HIP_TRY(hipSetDevice(h->device));
-    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
-    if (h->in_staged >= 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));      // (a staged update rewrites the same values)
+    PP_TRY(h->rollout.adv.wait(h->stream));
+    if (h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));      // (a staged update rewrites the same values)
     return fetch(h, s, h->traffic.d_s[h->traffic.cur], (size_t)n * sizeof(double));
 }
 
@@ -1892,7 +1810,7 @@ int pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf)
     // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the arrays
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }
-    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    PP_TRY(h->rollout.adv.wait(h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (!tf) {                                            // off: the arc lengths go back to the one array of §4h
         if (h->follow.on && h->traffic.cur == 1) {
@@ -1914,8 +1832,8 @@ int pp_get_traffic_speed(pp_handle h, double* v, int n)
     if (n < 0 || n > h->traffic.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
     HIP_TRY(hipSetDevice(h->device));
-    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
-    if (h->in_staged >= 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->in_sets[h->in_staged].ev_up, 0));
+    PP_TRY(h->rollout.adv.wait(h->stream));
+    if (h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
     return fetch(h, v, h->follow.d_v[h->traffic.cur], (size_t)n * sizeof(double));
 }
 
@@ -1944,7 +1862,7 @@ int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int3
         if (legs[k].road_num < 1 || legs[k].road_num > h->map_roads) return fail(PP_ERR_ARG, "pp_set_route: leg " + std::to_string(k) + " names a road outside the map");
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the old legs
-    if (h->rollout.adv_recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->rollout.ev_adv, 0));
+    PP_TRY(h->rollout.adv.wait(h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     { int r = h->route.d_first.reserve((size_t)h->caps.max_scenes + 1); if (r) return r; }      // room first: a failed allocation leaves the old route
     { int r = h->route.d_legs.reserve((size_t)n_legs_total); if (r) return r; }
@@ -1983,7 +1901,7 @@ int pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap)
     const bool staged = h->in_staged >= 0 && h->rollout.staged_by_advance;      // (the set pp_get_scene_in reads)
     const InputSet& I = h->in_sets[staged ? h->in_staged : h->in_cur];
     HIP_TRY(hipSetDevice(h->device));
-    if (staged) HIP_TRY(hipStreamWaitEvent(h->stream, I.ev_up, 0));
+    if (staged) PP_TRY(I.up.wait(h->stream));
     int32_t sl[2] = { 0, 0 };
     { int r = fetch(h, sl, &I.d_in[scene].obs_off, sizeof(sl)); if (r) return r; }
     static_assert(offsetof(SceneIn, obs_n) == offsetof(SceneIn, obs_off) + 4, "obs_off and obs_n are read as one pair");
@@ -2006,22 +1924,22 @@ static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, Planning
     { int r = ensure_streaming(h); if (r) return r; }
     const long long T = h->tick_seq;
     const int slot = (int)(T % kDone), n = h->n_scenes;
-    if (h->last_rec.tick != T) {
+    if (h->rec_last.tick != T) {
         // the last tick was enqueued before streaming began: one event behind everything stands in for its two
         { int r = join_all(h); if (r) return r; }
         hipEvent_t e = get_sync_event(h);
-        if (!e) return fail(PP_ERR_HIP, "hipEventCreate failed");
+        if (!e) return fail(PP_ERR_HIP, "event creation failed");
         HIP_TRY(hipEventRecord(e, h->stream));
         TickRec rec = { T, h->in_cur, e, nullptr };
-        h->inflight.push_back(rec); h->last_rec = rec;
+        h->inflight.push_back(rec); h->rec_last = rec;
     }
-    const TickRec& R = h->last_rec;
-    if (h->done_tick[slot] != T) { h->done_tick[slot] = T; h->done_g_rec[slot] = false; h->done_p_rec[slot] = false; }
+    const TickRec& R = h->rec_last;
+    if (h->done_tick[slot] != T) { h->done_tick[slot] = T; h->done_g[slot].forget(); h->done_p[slot].forget(); }      // (an earlier tick's downloads)
     const bool want_plan = plan || result || show;
     PendingFetch f{};
     f.tick = T; f.slot = slot; f.n = (size_t)n; f.ev_front = R.ev_front; f.ev_tail = R.ev_tail;
-    if (want_plan) { f.plan_dst = plan; f.res_dst = result; f.show_dst = show; f.plan_src = h->d_plan; f.plan_set = h->plan_cur; h->done_p_rec[slot] = true; }
-    if (grid) { f.grid_dst = grid; f.grid_src = h->d_gout[h->gout_set]; f.grid_set = h->gout_set; h->done_g_rec[slot] = true; }
+    if (want_plan) { f.plan_dst = plan; f.res_dst = result; f.show_dst = show; f.plan_src = h->d_plan; f.plan_set = h->plan_cur; }
+    if (grid) { f.grid_dst = grid; f.grid_src = h->d_gout[h->gout_set]; f.grid_set = h->gout_set; }
     // a second request for the same tick (PlanOut and GridOut asked for separately) joins the first
     bool joined = false;
     for (PendingFetch& g : h->fetches) if (g.tick == T) {
@@ -2051,8 +1969,8 @@ int pp_wait_tick(pp_handle h, long long tick_id, int* n_poisoned)
     HIP_TRY(hipSetDevice(h->device));
     { int r = flush_group(h); if (r) return r; }
     { int r = pump_fetches(h, tick_id); if (r) return r; }
-    if (h->done_p_rec[slot]) HIP_TRY(hipEventSynchronize(h->ev_done_p[slot]));
-    if (h->done_g_rec[slot]) HIP_TRY(hipEventSynchronize(h->ev_done_g[slot]));
+    PP_TRY(h->done_p[slot].host_wait());                  // (recorded by pump_fetches above, behind the copies it issued - if any were asked for)
+    PP_TRY(h->done_g[slot].host_wait());
     const int bad = (int)reinterpret_cast<volatile int32_t*>(h->h_bad.get())[slot];
     if (n_poisoned) *n_poisoned = bad;
     if (bad) return fail(PP_ERR_ARG, "tick " + std::to_string(tick_id) + ": " + std::to_string(bad) + " scene(s) of its update had a slice outside its pool (or a road / lane outside the map) and ran with empty inputs");
@@ -2067,7 +1985,7 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
     HIP_TRY(hipSetDevice(h->device));
     const int max_obs = std::min(PP_IO_MAX_OBS, h->caps.max_obs_total), max_ref = std::min(DMPP_MAX_REFPATH, h->caps.max_ref_pts_total);
     { int r = flush_group(h); if (r) return r; }          // (k_io_in rewrites the inputs an open group's searches read)
-    if (h->score.recorded) HIP_TRY(hipStreamWaitEvent(h->stream, h->score.ev, 0));      // ... and the scorecard of the last tick
+    PP_TRY(h->score.ego.wait(h->stream));                 // ... and the scorecard of the last tick
     h->in_staged = -1; h->rollout.staged_by_advance = false;
     hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->d_in, h->d_state, h->d_obs, h->d_ref);
     HIP_TRY(hipGetLastError());
@@ -2277,7 +2195,8 @@ void* pp_device_ptr(pp_handle h, int which, size_t* bytes)
     if (bytes) *bytes = b;
     return p;
 }
-// tick-group arithmetic (pp_plan_tick), without a device: the size of a group, the tick slots a handle allocates for, ring sizes
+// tick-group arithmetic (pp_plan_tick), without a device: the size of a group, the tick slots a handle allocates for, ring sizes,
+// the LDS budget of a group's search (mode: bit 0 fixed budget, bit 1 dense forced)
 int pp_tick_group_size(int n_scenes, int search_slots, int gcap, int forced) { return group_size(n_scenes, search_slots, gcap, forced); }
 int pp_tick_group_cap(int max_scenes, int pipeline_min, int forced, size_t item_bytes) { return group_cap(max_scenes, pipeline_min, forced, item_bytes); }
 int pp_tick_group_const(int which)
@@ -2291,6 +2210,16 @@ int pp_tick_group_const(int which)
     case 5: return kGout;
     default: return -1;
     }
+}
+int pp_search_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget_max, int n_cus, int n_scenes, int group, int n_obs_total,
+                     int need, int budget, int from_need, int mode, int32_t* budget_out, int32_t* from_need_out, int32_t* slots_out)
+{
+    const dmpp::SearchBudget b = dmpp::search_budget((size_t)static_lds, meta_bytes, gbm_lds, lds_budget_max, n_cus, n_scenes, group, n_obs_total,
+                                                     need, budget, from_need != 0, (mode & 1) != 0, (mode & 2) != 0);
+    if (budget_out) *budget_out = b.budget;
+    if (from_need_out) *from_need_out = b.from_need;
+    if (slots_out) *slots_out = b.slots;
+    return PP_OK;
 }
 void* pp_stream(pp_handle h) { return h && !flush_group(h) ? (void*)h->stream : nullptr; }
 

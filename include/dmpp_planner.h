@@ -426,6 +426,13 @@ size_t pp_sizeof(int which);
 int pp_tick_group_size(int n_scenes, int search_slots, int gcap, int forced);
 int pp_tick_group_cap(int max_scenes, int pipeline_min, int forced, size_t item_bytes);
 int pp_tick_group_const(int which);
+/* The LDS budget of a tick group's search (data words per view) and the workgroup slots it gives, from plain integers: the search
+ * kernel's static LDS, per-line meta bytes and dense-form LDS, the largest budget, the CUs; scenes per tick, ticks per group, the
+ * obstacle pool size; what the densest scene of an earlier group needed (-1: nothing yet); the budget in force (0: none) and
+ * whether it came from a need; mode: bit 0 a fixed budget (env DMPP_LDS_BUDGET), bit 1 dense forced (env DMPP_SEARCH_GBM).
+ * Out (any may be NULL): the new budget, whether it now comes from a need, the slots.  No device needed. */
+int pp_search_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget_max, int n_cus, int n_scenes, int group, int n_obs_total,
+                     int need, int budget, int from_need, int mode, int32_t* budget_out, int32_t* from_need_out, int32_t* slots_out);
 /* The search keeps a scene's obstacle bitmaps sparse in LDS; a launch gives every scene `lds_budget_words` words per view
  * (sized from what the densest scene of an earlier tick needed) and a scene that needs more is searched on dense bitmaps
  * in HBM instead.  After a tick: the budget of that tick, the words the densest scene seen so far needed, and how many

@@ -2,7 +2,7 @@
 once (one k_search / k_score over G * n work items).  Which ticks share a launch must change no result: every case below runs
 the same ticks on a grouped handle and on one with DMPP_TICK_GROUP=1 (one tick per launch, the pipeline before groups) and
 compares the outputs bit for bit - with the groups cut short by every kind of call that has to flush an open group.
-The first test checks the group arithmetic on the CPU."""
+The first two tests check the group arithmetic and the LDS budget arithmetic of a group's search on the CPU."""
 import ctypes
 import os
 
@@ -46,6 +46,35 @@ def test_group_arithmetic(dm):
     assert cap(4096, 256, 0, item) == 1                 # a set of 4 x 4096 work items would exceed the byte cap
     big = 2048 * 2048 * 2 + 3 * 2048 * 2048 // 8
     assert cap(1024, 256, 0, big) == 1
+
+
+def test_search_budget_arithmetic(dm):
+    """CPU: the LDS budget of a group's search and the workgroup slots it gives (pp_search_budget, no device needed).  Every row:
+    static LDS 7344, metas 4096, dense-form LDS 8192, at most 8192 words, 256 CUs - the figures of a 512 x 512 grid.  The expected
+    values are those of the expressions as they stood inline in pp_plan_tick."""
+    lib = dm.load_library()
+    i32 = ctypes.c_int32
+    lib.pp_search_budget.argtypes = [ctypes.c_int] * 12 + [ctypes.POINTER(i32)] * 3
+    FIXED, DENSE = 1, 2
+    rows = [  # n, G, n_obs_total, need, budget, from_need, mode -> budget, from_need, slots
+        ((1024, 1, 65536, -1, 0, 0, 0), (2048, 0, 1280)),          # first tick, 64 obstacles
+        ((1024, 3, 65536, 1635, 2048, 0, 0), (1920, 1, 1536)),     # the first need replaces the guess
+        ((1024, 3, 65536, 1500, 1920, 1, 0), (1920, 1, 1536)),     # hysteresis keeps
+        ((1024, 3, 65536, 900, 1920, 1, 0), (1088, 1, 2048)),      # shrinks by more than a quarter
+        ((1024, 3, 65536, 2500, 1920, 1, 0), (2880, 1, 1024)),     # grows
+        ((1024, 2, 262144, 4650, 5312, 1, 0), (5248, 1, 768)),     # 256 obstacles, items outnumber slots: tight slack
+        ((256, 1, 65536, 4650, 5312, 1, 0), (5312, 1, 768)),       # ... a slot for every item: the eighth stays (768: the unrounded count; the granule rule gives two per CU)
+        ((1024, 1, 262144, -1, 0, 0, 0), (7424, 0, 512)),          # first tick, 256 obstacles
+        ((64, 1, 12800, 9000, 2048, 1, 0), (8192, 1, 512)),        # need above the maximum
+        ((64, 1, 0, 0, 256, 1, 0), (64, 1, 2048)),                 # need 0
+        ((64, 1, 0, -1, 0, 0, 0), (256, 0, 2048)),                 # no obstacles, first tick
+        ((96, 1, 6144, 3000, 600, 0, FIXED), (600, 0, 2048)),      # fixed budget
+        ((96, 1, 6144, 3000, 0, 0, DENSE), (0, 0, 2048)),          # dense forced
+    ]
+    for args, want in rows:
+        out = [i32(-7) for _ in range(3)]
+        assert lib.pp_search_budget(7344, 4096, 8192, 8192, 256, *args, *(ctypes.byref(o) for o in out)) == 0
+        assert tuple(o.value for o in out) == want, (args, want)
 
 
 def _planner(dm, cfg, n, group, n_obs=256, **kw):
@@ -228,17 +257,15 @@ def test_spilling_scene_inside_a_group(dm):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("front_wait", ["0", "1"])
-def test_launch_order_over_a_group(dm, front_wait):
+def test_launch_order_over_a_group(dm):
     """1024 scenes in groups of two: 2048 work items outnumber the search's workgroup slots, so k_order sorts the items of both
-    ticks.  Odd tick counts leave a group of one flushed by pp_sync, whose launch order must cover its own items - also with
-    DMPP_FRONT_WAIT=1, where a full group's order is launched on the front chain."""
+    ticks.  Odd tick counts leave a group of one flushed by pp_sync, whose launch order must cover its own items."""
     cfg = dm.default_config(512)
     sc = _scenes(dm, cfg, 37, 1024, 32)
-    pls = _pair(dm, cfg, sc, 2, env={"DMPP_FRONT_WAIT": front_wait})
+    pls = _pair(dm, cfg, sc, 2)
     for k in (3, 1, 4, 5):
         for pl in pls:
             for _ in range(k):
                 pl.tick()
             pl.sync()
-        _same(pls, f"DMPP_FRONT_WAIT={front_wait}, {k} ticks", paths=(0, 511, 1023))
+        _same(pls, f"{k} ticks", paths=(0, 511, 1023))
