@@ -106,6 +106,12 @@ TrafficTrack = _dt([("point_off", i4), ("n_points", i4), ("closed", i4), ("_pad"
 TrafficActor = _dt([("s0", f8), ("speed", f8), ("scene", i4), ("slot", i4), ("track", i4), ("type", i4), ("radius", f4), ("_pad", i4)])
 # car-following traffic: actors with speed > 0 keep a gap to the ego and to each other
 TrafficFollow = _dt([("look", f8), ("lateral", f8), ("gap", f8), ("headway", f8), ("max_acc", f8), ("comfort_dec", f8), ("max_dec", f8), ("min_net", f8)])
+# episodic rollouts: ended egos restart on the device from start records; how every episode ended is counted
+EpisodeModel = _dt([("end_mask", i4), ("max_ticks", i4)])
+EpisodeStats = _dt([("n_episodes", i4), ("age", i4), ("n_end", i4, (6,)), ("last_cause", i4), ("last_age", i4), ("min_age", i4), ("max_age", i4),
+                    ("ticks_total", np.int64), ("dist", f8), ("last_dist", f8), ("dist_total", f8)])
+EGO_RESPAWNED = 32            # EgoTrace.flags only: the record is the start of a new episode (DMPP_EGO_RESPAWNED)
+EGO_TIMEOUT = 64              # cause word only: the episode reached EpisodeModel.max_ticks (DMPP_EGO_TIMEOUT)
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -234,6 +240,12 @@ def load_library(path=None):
         lib.pp_default_traffic_follow.restype = None
         lib.pp_set_traffic_follow.argtypes = [vp, vp]
         lib.pp_get_traffic_speed.argtypes = [vp, vp, ci]
+    episodes = hasattr(lib, "pp_set_episodes") or path == LIB_PATH          # (as above: an older build may lack it)
+    if episodes:
+        lib.pp_default_episode_model.argtypes = [vp]
+        lib.pp_default_episode_model.restype = None
+        lib.pp_set_episodes.argtypes = [vp, vp]
+        lib.pp_get_episode_stats.argtypes = [vp, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -248,7 +260,7 @@ def load_library(path=None):
     for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
             (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
             (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()) + \
-            (((28, TrafficFollow),) if react else ()):
+            (((28, TrafficFollow),) if react else ()) + (((29, EpisodeModel), (30, EpisodeStats)) if episodes else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -302,6 +314,13 @@ def default_grid_follow():
     gf = np.zeros(1, GridFollow)
     load_library().pp_default_grid_follow(_ptr(gf))
     return gf
+
+
+def default_episode_model():
+    """EpisodeModel record of the episodic rollouts (pp_default_episode_model): end_mask 31 (all five EGO_* flags), max_ticks 0 (no timeout)."""
+    em = np.zeros(1, EpisodeModel)
+    load_library().pp_default_episode_model(_ptr(em))
+    return em
 
 
 def default_traffic_follow():
@@ -567,6 +586,25 @@ class Planner:
             return
         m = np.array(tf, TrafficFollow).reshape(1).copy()
         _check(self.lib.pp_set_traffic_follow(self.h, _ptr(m)))
+
+    # ---- episodic rollouts: ended egos restart on the device from start records ----------------
+    def set_episodes(self, model=None, off=False):
+        """pp_set_episodes: captures the resident SceneIn records and the SceneState array as start records, zeroes the stats and
+        switches episodes on - from the next advance on an ego whose flag word meets model.end_mask, or whose episode reached
+        model.max_ticks advances, restarts from them.  Call it after set_route / set_state / set_fleet /
+        set_traffic: they do not touch the captured records.  model None: the default model.  off=True: episodes off, the stats
+        stay readable and flagged egos freeze again."""
+        if off:
+            _check(self.lib.pp_set_episodes(self.h, None))
+            return
+        m = default_episode_model() if model is None else np.array(model, EpisodeModel).reshape(1).copy()
+        _check(self.lib.pp_set_episodes(self.h, _ptr(m)))
+
+    def episode_stats(self):
+        """pp_get_episode_stats: one EpisodeStats record per scene, a staged advance included (host wait)."""
+        out = np.zeros(self.n, EpisodeStats)
+        _check(self.lib.pp_get_episode_stats(self.h, _ptr(out), self.n))
+        return out
 
     def traffic_speed(self):
         """pp_get_traffic_speed: the speed (m/s) of every actor, as traffic_state gives the arc lengths (host wait)."""

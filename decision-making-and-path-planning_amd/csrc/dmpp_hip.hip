@@ -23,6 +23,7 @@
 #include "kernels_r.hpp"
 #include "kernels_a.hpp"
 #include "kernels_rt.hpp"
+#include "kernels_ep.hpp"
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
 #include "kernels_f.hpp"
@@ -199,6 +200,13 @@ struct TrafficState {
 // TrafficState::d_s[1], the two speed arrays (the step is a Jacobi step: an advance reads pair traffic.cur and writes the
 // other, then flips cur; the advances are serial on the upload stream) and the group tables: every actor's scene and group, the
 // first member of every group and the actor indices sorted by (scene, track, index)
+// episodic rollouts (first pp_set_episodes): the model, every scene's start records - its SceneIn and SceneState as
+// captured by the call - and the stats; while on, pp_advance_async launches k_respawn_egos behind its advance kernel.  The stats
+// stay readable after episodes went off
+struct EpisodeState {
+    bool on = false; EpisodeModel em = { 0, 0 };
+    DevBuf<SceneIn> d_start_in; DevBuf<SceneState> d_start_state; DevBuf<EpisodeStats> d_stats;
+};
 struct FollowState {
     bool on = false; TrafficFollow tf = {};
     DevBuf<double> d_v[2]; DevBuf<dmpp::TrafficRef> d_ref; DevBuf<int32_t> d_first, d_members;
@@ -290,6 +298,7 @@ struct pp_planner {
     RouteState route;
     TrafficState traffic;
     FollowState follow;
+    EpisodeState episode;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
@@ -827,7 +836,7 @@ static int upload_pools(pp_handle h, const ObPoint* obs_pool, const ObMotion* mo
 // last (which syncs: the caller may reuse its buffers).  map_bad: scenes that k_resolve_map could not place (pp_set_egos).
 static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad = 0)
 {
-    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; note_current_set(h);
+    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->score.on) { int r = reset_scores(h); if (r) return r; }
     if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
@@ -958,6 +967,7 @@ int pp_set_state(pp_handle h, const SceneState* state, int n)
     if (n < 0 || n > h->caps.max_scenes) return fail(PP_ERR_CAPACITY, "n exceeds caps.max_scenes");
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }
+    if (h->episode.on) PP_TRY(h->rollout.adv.wait(h->stream));      // (episodes: a staged advance may still be restoring start states on the upload stream)
     HIP_TRY(hipMemcpyAsync(h->d_state, state, (size_t)n * sizeof(SceneState), hipMemcpyDefault, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return PP_OK;
@@ -1238,6 +1248,10 @@ int pp_get_state(pp_handle h, SceneState* st, int n)
 {
     if (!h || !st) return fail(PP_ERR_ARG, "null argument");
     if (n < 0 || n > h->caps.max_scenes) return fail(PP_ERR_ARG, "n exceeds capacity");
+    if (h->episode.on) {      // episodes: the upload stream writes SceneState too (a staged advance restores start states), and fetch only joins the tick streams
+        HIP_TRY(hipSetDevice(h->device));
+        PP_TRY(h->rollout.adv.wait(h->stream));
+    }
     return fetch(h, st, h->d_state, (size_t)n * sizeof(SceneState));
 }
 int pp_get_grid_out(pp_handle h, GridOut* out, int n)
@@ -1434,6 +1448,10 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         else
             hipLaunchKernelGGL(dmpp::k_advance_egos, agrid, dim3(dmpp::kBlock), 0, su,
                                h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace);
+        if (h->episode.on)                // ended egos restart from their start records: the traffic, the peers and the views below see the restarted ego
+            hipLaunchKernelGGL(dmpp::k_respawn_egos, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
+                               h->episode.em, n, P.d_in, d_in, h->d_state, h->episode.d_start_in, h->episode.d_start_state, h->rollout.d_flags, h->episode.d_stats,
+                               src.trace, h->score.on ? h->score.d_score.get() : nullptr);
     }
     if (h->traffic.on) {                  // an advance moves the actors one step on - by the car-following law while that is on (§4i) -, an update places them where they are
         if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }
@@ -1563,6 +1581,7 @@ int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }            // behind both halves: score.ego (k_score_ego), scored[] / stream order (k_score_grid)
+    if (h->episode.on) PP_TRY(h->rollout.adv.wait(h->stream));      // (episodes: a staged advance may have moved last_pos / last_speed to a start record)
     std::vector<dmpp::ScoreGridPart> parts((size_t)kBuf * (size_t)std::max(n, 1));
     HIP_TRY(hipMemcpyAsync(out, h->score.d_score, (size_t)n * sizeof(RolloutScore), hipMemcpyDefault, h->stream));
     for (int q = 0; q < kBuf && n > 0; q++)
@@ -1872,6 +1891,51 @@ int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int3
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the caller's arrays may go; the upload stream reads the copies from its next launch on)
     h->route.rm = *rm; h->route.rm._pad = 0; h->route.on = true;
     return PP_OK;
+}
+
+// Episodic rollouts.  Everything is checked on the host before anything changes.
+void pp_default_episode_model(EpisodeModel* em)
+{
+    if (!em) return;
+    em->end_mask = DMPP_EGO_PATH_END | DMPP_EGO_BAD_PATH | DMPP_EGO_LANE_END | DMPP_EGO_OFF_GRID | DMPP_EGO_ROUTE_END; em->max_ticks = 0;
+}
+
+int pp_set_episodes(pp_handle h, const EpisodeModel* em)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episodes: an update is staged for the next tick (set the episodes before staging, or after the tick)");
+    if (!em) { h->episode.on = false; return PP_OK; }
+    const int n = h->n_scenes;
+    if (n <= 0) return fail(PP_ERR_STATE, "pp_set_episodes: no resident scenes");
+    if ((em->end_mask & ~31) != 0) return fail(PP_ERR_ARG, "pp_set_episodes: end_mask holds bits outside the five DMPP_EGO_* flags (31)");
+    if (em->max_ticks < 0) return fail(PP_ERR_ARG, "pp_set_episodes: max_ticks must be >= 0");
+    if (em->end_mask == 0 && em->max_ticks == 0) return fail(PP_ERR_ARG, "pp_set_episodes: a model with no end flag and no timeout ends no episode");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the old start records
+    PP_TRY(h->rollout.adv.wait(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t ns = (size_t)h->caps.max_scenes;         // room first, sized once: a failed allocation leaves the old records
+    { int r = h->episode.d_start_in.reserve(ns); if (r) return r; }
+    { int r = h->episode.d_start_state.reserve(ns); if (r) return r; }
+    { int r = h->episode.d_stats.reserve(ns); if (r) return r; }
+    h->episode.on = false;                                // (until the copies below have landed: a failed copy leaves episodes off, not half a capture)
+    HIP_TRY(hipMemcpyAsync(h->episode.d_start_in, h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->episode.d_start_state, h->d_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
+    hipLaunchKernelGGL(dmpp::k_episode_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, (int)ns, h->episode.d_stats);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));            // (the upload stream reads the copies from its next launch on)
+    h->episode.em = *em; h->episode.on = true;
+    return PP_OK;
+}
+
+int pp_get_episode_stats(pp_handle h, EpisodeStats* out, int n)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->episode.d_stats) return fail(PP_ERR_STATE, "pp_get_episode_stats: pp_set_episodes was never called on this handle");
+    if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_ego_flags
+    return fetch(h, out, h->episode.d_stats, (size_t)n * sizeof(EpisodeStats));
 }
 
 // A grid that follows the ego: host checks only; the model is a kernel argument of the next advance.
@@ -2235,6 +2299,7 @@ size_t pp_sizeof(int which)
     case 19: return sizeof(EgoModel); case 20: return sizeof(EgoTrace); case 21: return sizeof(RolloutScore); case 22: return sizeof(FleetModel);
     case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel); case 25: return sizeof(GridFollow);
     case 26: return sizeof(TrafficTrack); case 27: return sizeof(TrafficActor); case 28: return sizeof(TrafficFollow);
+    case 29: return sizeof(EpisodeModel); case 30: return sizeof(EpisodeStats);
     default: return 0;
     }
 }

@@ -18,6 +18,8 @@
 // With --route --fleet --traffic --shared (and --react for following) the 64 egos form 8 worlds of 8 - each world a platoon on one lane,
 // 12 m apart, 4 peer slots per scene - and there is ONE vehicle per world in the place of one per scene (pp_set_world_traffic,
 // DESIGN.md §4j): it is written into slot 0 of all 8 member scenes and follows the nearest of the world's 8 egos.
+// With --route --episodes every ego gets a route of ONE leg and episodes are on (pp_set_episodes with the default model):
+// an ego that arrives restarts on the device from its start records, and the host prints episodes, causes and mean age per ego.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -30,7 +32,7 @@
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes)
 {
     const int W = 8, K = shared ? 4 : 0, stride = 1 + K;      // --shared: worlds of W scenes, K peer slots behind every scene's one own entry
     const int n = 64, ticks = 1200, P = 260, JP = 40, n_lanes = 2;
@@ -73,7 +75,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared)
     }
     std::vector<RouteLeg> legs; std::vector<int32_t> route_first = { 0 };
     for (int s = 0; s < n; s++) {
-        int road = s % 4 + 1, lane = (s / 4) % n_lanes + 1, id = 100 + (s * 7) % 80; const int n_legs = 3 + s % 4;
+        int road = s % 4 + 1, lane = (s / 4) % n_lanes + 1, id = 100 + (s * 7) % 80; const int n_legs = episodes ? 1 : 3 + s % 4;
         if (shared) { const int w = s / W; road = w % 4 + 1; lane = (w / 4) % n_lanes + 1; id = 60 + 24 * (s % W); }      // a platoon per world: member 0 at the rear
         const GlobalPoint3D& q = pts[(size_t)lanes[(size_t)first[(size_t)road - 1] + lane - 1].point_off + id];
         SceneIn& e = in[(size_t)s];
@@ -138,9 +140,26 @@ static int run_route(bool follow, bool traffic, bool react, bool shared)
         if (react) { TrafficFollow tf; pp_default_traffic_follow(&tf); CHECK(pp_set_traffic_follow(h, &tf)); }
         CHECK(pp_score_begin(h, model.dt));
     }
+    if (episodes) { EpisodeModel em; pp_default_episode_model(&em); CHECK(pp_set_episodes(h, &em)); }      // last: it captures what the calls above set up
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
+    if (episodes) {
+        static const char* const cause[6] = { "PATH_END", "BAD_PATH", "LANE_END", "OFF_GRID", "ROUTE_END", "TIMEOUT" };
+        std::vector<EpisodeStats> es(n);
+        CHECK(pp_get_episode_stats(h, es.data(), n));
+        long long total = 0, by[6] = { 0, 0, 0, 0, 0, 0 }; double metres = 0;
+        std::printf("episodes: ended per ego (mean age in advances):");
+        for (int s = 0; s < n; s++) {
+            const EpisodeStats& e = es[(size_t)s];
+            std::printf(" %d (%.1f)", e.n_episodes, e.n_episodes ? (double)e.ticks_total / e.n_episodes : 0.0);
+            total += e.n_episodes; metres += e.dist_total;
+            for (int b = 0; b < 6; b++) by[b] += e.n_end[b];
+        }
+        std::printf("\nepisodes: %lld ended in %d advances of %d egos, %.1f m driven in them; causes:", total, ticks, n, metres);
+        for (int b = 0; b < 6; b++) if (by[b]) std::printf(" %s %lld", cause[b], by[b]);
+        std::printf("\n");
+    }
     if (traffic) {
         const int nv = (int)actors.size();
         std::vector<RolloutScore> score(n); std::vector<double> arc((size_t)nv);
@@ -185,7 +204,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared)
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -193,12 +212,14 @@ int main(int argc, char** argv)
         else if (std::strcmp(argv[a], "--traffic") == 0) traffic = true;
         else if (std::strcmp(argv[a], "--react") == 0) react = true;
         else if (std::strcmp(argv[a], "--shared") == 0) shared = true;
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--episodes") == 0) episodes = true;
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
     if (shared && !(route && fleet && traffic)) { std::fprintf(stderr, "--shared puts one vehicle into every world: use it with --route --fleet --traffic\n"); return 2; }
-    if (route) return run_route(follow, traffic, react, shared);
+    if (episodes && !route) { std::fprintf(stderr, "--episodes restarts egos that arrive: use it with --route\n"); return 2; }
+    if (route) return run_route(follow, traffic, react, shared, episodes);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

@@ -179,7 +179,7 @@ int   pp_host_unregister(void* p);
  * the caller's three lane slices cannot be rotated, so a lane change is only followed after pp_set_egos.  Road and junction
  * transitions belong to a localisation module and are out of scope: an ego that nears the end of its lane is flagged
  * (DMPP_EGO_*) and FROZEN - later advances carry its SceneIn over unchanged, it still ticks, its flags are sticky until the
- * next pp_set_scenes / pp_set_egos / pp_set_n_scenes.
+ * next pp_set_scenes / pp_set_egos / pp_set_n_scenes (or, with pp_set_episodes, until the ego restarts: DESIGN.md §4k).
  * It waits - on the device - for the Planning kernel of the last tick only, never for its search, and never on the host.
  * PP_ERR_STATE: no tick enqueued since the scenes were set, or an update already staged for the next tick (a pp_update_async
  * with SceneIn records on top of a staged advance is PP_ERR_STATE too; an obstacles-only one is fine).
@@ -352,6 +352,33 @@ int  pp_get_traffic_speed(pp_handle h, double* v, int n);
 int  pp_set_world_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points,
                           int n_actors, const TrafficActor* actors);
 
+/* ---- episodic rollouts: ended egos restart on the device from start records ---------------------------------------
+ * Without it every DMPP_EGO_* flag is sticky: an ego that arrived (ROUTE_END), ran out of lane or path or left its grid is frozen
+ * until the host uploads new scenes.  pp_set_episodes captures every resident scene's START RECORDS - the SceneIn records of the
+ * current input set, as the next tick would read them, and the SceneState array - as device copies, sets the stats to their starting
+ * values and switches episodes on.  From then on every pp_advance_async runs one more kernel on the upload stream (k_respawn_egos,
+ * one wave per scene) directly behind its advance kernel: it counts the advance into the running episode (age, distance), and a
+ * scene whose flag word meets em->end_mask, or whose episode has reached em->max_ticks advances (DMPP_EGO_TIMEOUT in the cause word;
+ * 0: no timeout), ends its episode: the stats record how, the staged SceneIn and the SceneState become the start records - every
+ * byte, SceneState.tick included -, the flag word becomes 0, the trace record of the call (if any) is the start record's with
+ * flags = old flags | DMPP_EGO_RESPAWNED | (cause & DMPP_EGO_TIMEOUT), and - scorecard on - RolloutScore.last_pos / last_speed move
+ * to the start record, so the jump adds nothing to dist, max_acc or max_dec.  The traffic kernels, k_couple_fleet, k_resolve_map and
+ * k_sanitise_scenes run behind it and see the restarted ego in the same set.  A scene frozen by a flag outside the mask stays
+ * frozen until a timeout.  Every step is specified (§4k): a numpy restatement gives the same bytes.
+ * A second call captures again and restarts the stats.  em NULL: episodes off - the stats stay readable and flagged egos freeze
+ * again as in §4c.  pp_set_scenes / pp_set_egos / pp_set_n_scenes switch episodes off, like the fleet.
+ * CALL IT LAST: later pp_set_route / pp_set_state / pp_set_grid_follow / pp_set_fleet / pp_set_traffic* / pp_set_world_traffic do
+ * not touch the captured records - a restart puts back the slices, the state and the leg index of the capture.
+ * PP_ERR_STATE: no resident scenes, or an update staged for the next tick.  PP_ERR_ARG: bits outside 31 in end_mask, max_ticks < 0,
+ * or end_mask == 0 && max_ticks == 0 (no episode would ever end).  Nothing changes on these.  One host wait, behind every tick and
+ * advance enqueued so far.  A handle that never calls pp_set_episodes allocates and launches none of this.
+ * With episodes on the upload stream writes SceneState: pp_get_state / pp_set_state order themselves behind a staged advance.
+ * pp_get_episode_stats: the records of the first n_scenes scenes, a staged advance included (host wait, as pp_get_ego_flags).
+ * PP_ERR_STATE on a handle that never set episodes. */
+void pp_default_episode_model(EpisodeModel* em);     /* end_mask 31 (all five flags), max_ticks 0 (no timeout) */
+int  pp_set_episodes(pp_handle h, const EpisodeModel* em);
+int  pp_get_episode_stats(pp_handle h, EpisodeStats* out, int n_scenes);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -416,7 +443,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
- * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow */
+ * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -350,6 +350,26 @@ typedef struct TrafficFollow {
     double min_net;      /* m: the net gap is never taken smaller than this                    */
 } TrafficFollow;                                                            /* 64 B */
 
+/* ---- episodic rollouts (build-defined) ---------------------------------------------------------
+ * pp_set_episodes captures every scene's START RECORDS - its SceneIn and its SceneState - and from then on an ego whose flag
+ * word meets end_mask, or whose episode reached max_ticks advances, is put back on them inside the advance that ended it:
+ * the scene plays episode after episode with no host in the loop, and EpisodeStats counts how each one ended. */
+#define DMPP_EGO_RESPAWNED 32   /* EgoTrace.flags only: this record is the start of a new episode          */
+#define DMPP_EGO_TIMEOUT   64   /* cause word only: the episode reached EpisodeModel.max_ticks              */
+typedef struct EpisodeModel {
+    int32_t end_mask;           /* the DMPP_EGO_* flags (bits 1 .. 16) that end an episode                  */
+    int32_t max_ticks;          /* > 0: an episode also ends with its max_ticks-th advance; 0: no timeout   */
+} EpisodeModel;                                                             /* 8 B */
+typedef struct EpisodeStats {
+    int32_t n_episodes;         /* episodes ended                                                          */
+    int32_t age;                /* advances of the running episode                                         */
+    int32_t n_end[6];           /* ended episodes whose cause word had PATH_END, BAD_PATH, LANE_END, OFF_GRID, ROUTE_END, TIMEOUT (one count per bit set) */
+    int32_t last_cause, last_age;
+    int32_t min_age, max_age;   /* over ended episodes; -1, -1 while none                                  */
+    int64_t ticks_total;        /* sum of the ages of ended episodes                                       */
+    double  dist, last_dist, dist_total;   /* metres: running episode, last ended one, all ended ones      */
+} EpisodeStats;                                                             /* 80 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

@@ -16,7 +16,10 @@ FOLLOW=trace_on / trace_off: for rocprofv3 --kernel-trace --stats - one such rin
 generated scenes (k_advance_egos), both with following on / both with it off, and nothing else.
 TRAFFIC=A: every run has a rollout leg with lane traffic on (pp_set_traffic: A actors per scene, default 8 for TRAFFIC=1, in the first
 A of the scene's own obstacle entries, driving the scene's current lane as an open track at 1 .. 8 m/s) and one with it off: the same
-scenes after the same pp_set_traffic, switched off again, so both legs start from the same pool with the same obs_n - alternating."""
+scenes after the same pp_set_traffic, switched off again, so both legs start from the same pool with the same obs_n - alternating.
+EPISODES=1: every run has a rollout leg of routed ring egos with ONE-leg routes and episodes on (pp_set_episodes, default model:
+k_respawn_egos behind k_advance_route, arrived egos restart) and one with them off on the same scenes (arrived egos freeze),
+alternating; with ONE_ROLLOUT one more leg with episodes on alone, for rocprofv3 --kernel-trace --stats."""
 import os
 import statistics
 import sys
@@ -137,6 +140,31 @@ def route_run(on):
     return n * steps / dt, frozen
 
 
+def episodes_run(on):
+    import route_scenes as rs
+    rcfg = dm.default_config(128)
+    rcfg["grid_stage"] = 0
+    m = rs.build_ring(dm)
+    sc, legs, rf = rs.make_egos(dm, rcfg, m, n, seed=5, ids=(10, 250), legs=(1, 1))
+    pl = dm.Planner(rcfg, device=0, **rs.caps(m, n))
+    pl.set_map(m)
+    pl.set_egos(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    pl.set_route(legs, rf)
+    if on:
+        pl.set_episodes()
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    frozen = int((pl.ego_flags() != 0).sum())
+    ended = int(pl.episode_stats()["n_episodes"].sum()) if on else 0
+    pl.close()
+    return n * steps / dt, frozen, ended
+
+
 def follow_run(on):
     import route_scenes as rs
     rcfg = dm.default_config(256)
@@ -237,6 +265,20 @@ if TRAFFIC > 0:
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with traffic alone
         traffic_run(True)
+    sys.exit(0)
+if os.environ.get("EPISODES", "0") == "1":
+    off, on = [], []
+    for r in range(runs):
+        a, fa, _ = episodes_run(False)
+        b, fb, eb = episodes_run(True)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos, one-leg routes  episodes off %.3f M ticks/s (%d frozen at the end)   episodes on %.3f M ticks/s (%d frozen, %d episodes ended)" %
+              (r, n, a / 1e6, fa, b / 1e6, fb, eb), flush=True)
+    print("median  %d ring egos  episodes off %.3f M ticks/s (spread %.3f)   episodes on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with episodes alone
+        episodes_run(True)
     sys.exit(0)
 if os.environ.get("ROUTE", "0") == "1":
     off, on = [], []
