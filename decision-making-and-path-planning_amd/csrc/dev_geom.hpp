@@ -182,9 +182,13 @@ __device__ __forceinline__ GlobalPoint2D mean_point(const PlannerConfig& c, cons
 }
 
 
-// Order-dependent sums (arc lengths) are carried by ONE lane in index order, so their rounding equals a sequential host loop's;
-// what makes them fast is that the lane works on blocks of eight values: the eight LDS reads are issued together (one wait),
-// then eight dependent adds follow - ~10 cycles per element instead of an LDS round trip per element.
+// Order-dependent sums (arc lengths) are carried by ONE lane in index order, so their rounding equals a sequential host loop's.
+// The lane works on blocks of eight values: the eight LDS reads are issued together (one wait), then eight dependent adds
+// follow - ~10 cycles per element with the CU to itself instead of an LDS round trip per element, about 60 beside three
+// searching workgroups (profiles/r17_front_cull.txt).  No form of the chain measured faster (readlane chains, register
+// feeds), so what pays is adding fewer values: team_search_obstacle sums only up to the vertex its answer needs
+// (serial_sum_lean), and only wave_cumlen - MeanPoints, the scoring pass, the stand-alone operators and the second pass of
+// team_search_obstacle - still builds a whole prefix (serial_prefix_inplace).
 
 // in place: v[i] <- v[lo] + ... + v[i] for i in [lo, hi), starting from `acc`; returns the total.  One lane.
 __device__ __forceinline__ double serial_prefix_inplace(double* v, int lo, int hi, double acc)
@@ -207,6 +211,21 @@ __device__ __forceinline__ double serial_sum(const double* v, int lo, int hi, do
         const double a0 = v[i], a1 = v[i + 1], a2 = v[i + 2], a3 = v[i + 3], a4 = v[i + 4], a5 = v[i + 5], a6 = v[i + 6], a7 = v[i + 7];
         acc += a0; acc += a1; acc += a2; acc += a3; acc += a4; acc += a5; acc += a6; acc += a7;
     }
+    for (; i < hi; i++) acc += v[i];
+    return acc;
+}
+// serial_sum for a kernel short of registers: left alone, the compiler unrolls the loop above four times - 32 values in flight,
+// 64 registers - which is what k_decision / k_planning would then be sized by (two blocks in flight still cost k_decision its
+// fifth wave per SIMD: 98 registers).  One block of eight in flight here, as in serial_prefix_inplace.
+__device__ __forceinline__ double serial_sum_lean(const double* v, int lo, int hi, double acc)
+{
+    int i = lo;
+#pragma unroll 1
+    for (; i + 8 <= hi; i += 8) {
+        const double a0 = v[i], a1 = v[i + 1], a2 = v[i + 2], a3 = v[i + 3], a4 = v[i + 4], a5 = v[i + 5], a6 = v[i + 6], a7 = v[i + 7];
+        acc += a0; acc += a1; acc += a2; acc += a3; acc += a4; acc += a5; acc += a6; acc += a7;
+    }
+#pragma unroll 1
     for (; i < hi; i++) acc += v[i];
     return acc;
 }
@@ -256,6 +275,9 @@ __device__ __forceinline__ double readlane_f64(double v, int src)       // src m
 struct SoResult {
     double dis_lat, dis_lng;
     int flag, path_id, ob_index;
+#ifdef DMPP_DEBUG_SEARCH
+    int adds;                   // in-order additions of the call, negative when it took the second pass (debug build only, tools/dbg_front.py)
+#endif
 };
 
 // CShare::SearchObstacle for one polyline, executed by one full wave (all 64 lanes active).
@@ -315,39 +337,19 @@ __device__ __forceinline__ SoResult wave_search_obstacle(const PlannerConfig& c,
     return r;
 }
 
-// CShare::SearchObstacle for one polyline by a TEAM of TW waves of a 256-thread block (TW = 4: the whole block on one
-// polyline; TW = 2: two polylines side by side).  The team's first wave sums the arc lengths while every wave of the team
-// scans its share of the points for all obstacles: consecutive ranges in rank order, the leader's the smallest.  The
-// shares are merged per obstacle in point order with the strict < of the sequential loop (so the first minimum wins), and
-// the first wave finishes as wave_search_obstacle does.  EVERY thread of the block must call it (block-wide barriers), with
-// the same m; a team without a job passes active = false.  part_d2 / part_bi: 256 entries each.  The result is valid in the
-// team's first wave.
-template <int TW>
-__device__ __forceinline__ SoResult team_search_obstacle(const PlannerConfig& c, const GlobalPoint2D* path, int n, double* s,
-                                                         const ObPoint* obs, int m, double lat_lo, double lat_hi, bool active,
-                                                         double* part_d2, int* part_bi)
+// The scan, the merge and the accept tests of team_search_obstacle for all m obstacles, and each lane's pick among its own
+// accepted ones.  FULL = false (first pass): the first obstacle on the lane's smallest vertex, no arc length read;
+// FULL = true (second pass): the sequential loop's `first, or strictly smaller lng = s[bi]`.
+template <int TW, bool FULL>
+__device__ __forceinline__ void team_scan_obstacles(const PlannerConfig& c, const GlobalPoint2D* path, int n, const double* s,
+                                                    const ObPoint* obs, int m, double lat_lo, double lat_hi, bool run, double* part_d2,
+                                                    int* part_bi, double& best_lng, double& best_lat, int& best_j, int& best_id)
 {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, rank = wave % TW;
+    constexpr int kNone = 0x7fffffff;
+    const int tid = threadIdx.x, lane = tid & 63, rank = (tid >> 6) % TW;
     const bool leader = rank == 0;
-    SoResult r;
-    r.flag = 0; r.path_id = 0; r.ob_index = -1; r.dis_lat = c.NO_OBSTACLE_DIS; r.dis_lng = c.NO_OBSTACLE_DIS;
-    const bool run = active && n >= 2 && m >= 1;
-    if (run && leader) wave_cumlen(path, n, s, lane);
-    // The leader's arc-length sum is one lane adding in index order, the longest chain of the call (about 60 cycles per point
-    // with four workgroups on the CU, profiles/r17_front_cull.txt), so the leader takes a small share of the scan:
-    // four waves: the leader nothing, ranks 1..3 a third each; two waves: the leader a quarter, the other wave the rest.
-    static_assert(TW == 2 || TW == 4, "the shares are written out for teams of two and of four waves");
-    int q0 = 0, q1 = 0;
-    if (run) {
-        if constexpr (TW == 4) {
-            if (!leader) { q0 = (int)((long long)n * (rank - 1) / 3); q1 = (int)((long long)n * rank / 3); }
-        } else {
-            const int cut = n / 4;
-            q0 = leader ? 0 : cut; q1 = leader ? cut : n;
-        }
-    }
-    double best_lng = __builtin_inf(), best_lat = 0;
-    int best_j = 0x7fffffff, best_id = 0;
+    const int q0 = n * rank / TW, q1 = n * (rank + 1) / TW;             // even shares in rank order (n <= DMPP_MAX_REFPATH)
+    best_lng = __builtin_inf(); best_lat = 0; best_j = kNone; best_id = 0;
     for (int j0 = 0; j0 < m; j0 += DMPP_WAVE) {
         const int j = j0 + lane;
         double best = __builtin_inf(); int bi = 0;
@@ -355,6 +357,7 @@ __device__ __forceinline__ SoResult team_search_obstacle(const PlannerConfig& c,
         if (run && j < m) {
             ox = obs[j].x; oy = obs[j].y;
             int i = q0;
+            if constexpr (!FULL)                             // (the rare second pass goes point by point: less code, fewer registers)
             for (; i + 4 <= q1; i += 4) {                    // four points per round: the (broadcast) reads are issued together
                 const GlobalPoint2D p0 = path[i], p1 = path[i + 1], p2 = path[i + 2], p3 = path[i + 3];
                 const double a0 = ox - p0.x, b0 = oy - p0.y, a1 = ox - p1.x, b1 = oy - p1.y, a2 = ox - p2.x, b2 = oy - p2.y, a3 = ox - p3.x, b3 = oy - p3.y;
@@ -364,6 +367,7 @@ __device__ __forceinline__ SoResult team_search_obstacle(const PlannerConfig& c,
                 if (e2 < best) { best = e2; bi = i + 2; }
                 if (e3 < best) { best = e3; bi = i + 3; }
             }
+#pragma unroll 1
             for (; i < q1; i++) {
                 const double dx = ox - path[i].x, dy = oy - path[i].y, d2 = dx * dx + dy * dy;
                 if (d2 < best) { best = d2; bi = i; }
@@ -383,24 +387,136 @@ __device__ __forceinline__ SoResult team_search_obstacle(const PlannerConfig& c,
             if (ok) {
                 const double lat = GetLatDis(c, o, a, b);
                 if (!(lat < lat_lo || lat > lat_hi)) {
-                    const double lng = s[bi];
-                    if (best_j == 0x7fffffff || lng < best_lng) { best_lng = lng; best_lat = lat; best_j = j; best_id = bi; }
+                    if constexpr (FULL) {
+                        const double lng = s[bi];
+                        if (best_j == kNone || lng < best_lng) { best_lng = lng; best_lat = lat; best_j = j; best_id = bi; }
+                    } else {                                 // j rises within a lane: the first obstacle on the smallest vertex
+                        if (best_j == kNone || bi < best_id) { best_lat = lat; best_j = j; best_id = bi; }
+                    }
                 }
             }
         }
         __syncthreads();
     }
+}
+
+// CShare::SearchObstacle for one polyline by a TEAM of TW waves of a 256-thread block (TW = 4: the whole block on one
+// polyline; TW = 2: two polylines side by side).  Every wave of the team scans an even share of the points for all
+// obstacles: consecutive ranges in rank order.  The shares are merged per obstacle in point order with the strict < of the
+// sequential loop (so the first minimum wins), and the team's first wave applies the accept tests of the sequential loop.
+//
+// The arc length is NOT summed beside the scan.  The sequential loop uses s[] only to compare lng = s[bi] between the accepted
+// obstacles (strict <, the first j wins) and to report the winner's s[bi]; while every segment length is finite s never
+// decreases, so the winner is the lexicographic minimum of (s[bi], j) and the one in-order sum the answer needs is
+// S = s[b*], b* the smallest bi among the accepted obstacles (tests/search_obstacle_rule.py is the rule in plain numpy):
+//   1. every lane keeps, of its own accepted obstacles, the first with the smallest bi; b* is the minimum over the wave;
+//   2. the wave computes all n - 1 segment lengths in parallel into s[1 .. n) (no sum yet), one lane adds s[1 .. b*] in index
+//      order (serial_sum_lean: b* additions instead of n - 1; none at all when nothing is accepted);
+//   3. the tie run: e >= b* is the last index with fl(S + s[k]) == S for every b* < k <= e - the additions a sequential sum
+//      absorbs, so that s[k] == S there.  S is the running sum at every index of the run, hence each test stands alone: a
+//      ballot.  (Repeated points, or a length below half an ulp of S; a sum that overflowed to inf absorbs everything that
+//      follows, which is what the sequential loop sees as well.)
+//   4. the winner is the smallest j among the accepted obstacles with b* <= bi <= e; dis_lng = S.
+// SECOND PASS - the sequence as it was before the sum was deferred, kept whole: wave_cumlen over all n points, the scan again
+// (point by point, in the same order), per-lane selection on lng = s[bi] with the sequential loop's `first, or strictly
+// smaller`, and the xor reduction on (lng, j).
+// A call takes it when
+//   * a segment length is not finite (the ballot of step 2).  A NaN in s makes every later comparison false and the first
+//     accepted obstacle keeps a NaN lng, whatever bi the others have: the rule above does not hold, the sequence does, with its
+//     behaviour under NaN exactly as it was.  Lane points reach the kernels unfiltered (k_validate_scenes / k_sanitise_scenes
+//     test offsets and counts, not coordinates), so this can happen;
+//   * the tie run is not empty and m > 64: a lane that scanned several obstacles kept only its first on the smallest bi, and an
+//     earlier j of the same lane on a later vertex of the run would be lost.  (With m <= 64 a lane has one obstacle and step 4
+//     is exact.)
+// The flag travels to the other waves through part_bi[kBlock + rank of the team in the block] and one more barrier per call.
+//
+// EVERY thread of the block must call it (block-wide barriers), with the same m; a team without a job passes active = false.
+// part_d2: 256 entries, part_bi: 256 + 2.  s: n doubles of scratch, undefined afterwards.  The result is valid in the team's
+// first wave.
+template <int TW>
+__device__ __forceinline__ SoResult team_search_obstacle(const PlannerConfig& c, const GlobalPoint2D* path, int n, double* s,
+                                                         const ObPoint* obs, int m, double lat_lo, double lat_hi, bool active,
+                                                         double* part_d2, int* part_bi)
+{
+    static_assert(TW == 2 || TW == 4, "teams of two or of four waves of a 256-thread block");
+    constexpr int kNone = 0x7fffffff, kThreads = 4 * DMPP_WAVE;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const bool leader = wave % TW == 0;
+    int* const again_flag = part_bi + kThreads;            // one word per team of the block
+    SoResult r;
+    r.flag = 0; r.path_id = 0; r.ob_index = -1; r.dis_lat = c.NO_OBSTACLE_DIS; r.dis_lng = c.NO_OBSTACLE_DIS;
+#ifdef DMPP_DEBUG_SEARCH
+    r.adds = 0;
+#endif
+    const bool run = active && n >= 2 && m >= 1;
+    double best_lng, best_lat;
+    int best_j, best_id;
+    team_scan_obstacles<TW, false>(c, path, n, s, obs, m, lat_lo, lat_hi, run, part_d2, part_bi, best_lng, best_lat, best_j, best_id);
+    bool again = false;
     if (run && leader) {
-        // reduce on (lng, j): the sequential loop keeps the first obstacle with the smallest lng
+        int bs = best_j != kNone ? best_id : kNone;          // b*
 #pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) {
-            double o_lng = shfl_xor_f64(best_lng, sft);
-            double o_lat = shfl_xor_f64(best_lat, sft);
-            int o_j = __shfl_xor(best_j, sft, 64), o_id = __shfl_xor(best_id, sft, 64);
-            bool take = (o_j != 0x7fffffff) && (best_j == 0x7fffffff || o_lng < best_lng || (o_lng == best_lng && o_j < best_j));
-            if (take) { best_lng = o_lng; best_lat = o_lat; best_j = o_j; best_id = o_id; }
+        for (int sft = 32; sft >= 1; sft >>= 1) bs = min(bs, __shfl_xor(bs, sft, 64));
+        bs = __builtin_amdgcn_readfirstlane(bs);
+        if (bs != kNone) {
+            bool bad = false;
+#pragma unroll 1
+            for (int k = 1 + lane; k < n; k += DMPP_WAVE) { const double d = CalcDistance(path[k], path[k - 1]); s[k] = d; bad |= !__builtin_isfinite(d); }
+            wave_sync();
+            if (wave_ballot(bad) != 0) again = true;
+            else {
+                double S = 0.0;
+                if (lane == 0) S = serial_sum_lean(s, 1, bs + 1, 0.0);
+                S = readlane_f64(S, 0);
+                int e = bs;
+#pragma unroll 1
+                for (int k0 = bs + 1; k0 < n; k0 += DMPP_WAVE) {             // the tie run; nearly always it ends at once
+                    const int k = k0 + lane;
+                    const bool absorbed = k < n && S + s[k] == S;
+                    const unsigned long long stop = wave_ballot(!absorbed);
+                    if (stop != 0) { e += __ffsll((long long)stop) - 1; break; }
+                    e += DMPP_WAVE;
+                }
+                if (e > bs && m > DMPP_WAVE) again = true;
+                else {
+                    int wj = (best_j != kNone && best_id <= e) ? best_j : kNone;
+#pragma unroll
+                    for (int sft = 32; sft >= 1; sft >>= 1) wj = min(wj, __shfl_xor(wj, sft, 64));
+                    wj = __builtin_amdgcn_readfirstlane(wj);
+                    const int wl = wj & (DMPP_WAVE - 1);             // j = j0 + lane: the lane that holds the winner
+                    r.flag = 1; r.dis_lat = readlane_f64(best_lat, wl); r.dis_lng = S;
+                    r.path_id = __builtin_amdgcn_readlane(best_id, wl); r.ob_index = wj;
+#ifdef DMPP_DEBUG_SEARCH
+                    r.adds = bs;
+#endif
+                }
+            }
         }
-        if (best_j != 0x7fffffff) { r.flag = 1; r.dis_lat = best_lat; r.dis_lng = best_lng; r.path_id = best_id; r.ob_index = best_j; }
+    }
+    if (leader && lane == 0) again_flag[wave / TW] = again;
+    __syncthreads();
+    const bool mine = again_flag[wave / TW] != 0;
+    const bool any = TW == 4 ? mine : (again_flag[0] | again_flag[1]) != 0;
+    if (any) {                                                           // (uniform over the block) the second pass, rare
+        // (no barrier of its own: the flags sit behind the partials, and the next write to them follows the barriers of this scan)
+        const bool run2 = run && mine;                                   // a team that needs none goes through the barriers only
+        if (run2 && leader) wave_cumlen(path, n, s, lane);
+        team_scan_obstacles<TW, true>(c, path, n, s, obs, m, lat_lo, lat_hi, run2, part_d2, part_bi, best_lng, best_lat, best_j, best_id);
+        if (run2 && leader) {
+            // reduce on (lng, j): the sequential loop keeps the first obstacle with the smallest lng
+#pragma unroll
+            for (int sft = 32; sft >= 1; sft >>= 1) {
+                double o_lng = shfl_xor_f64(best_lng, sft);
+                double o_lat = shfl_xor_f64(best_lat, sft);
+                int o_j = __shfl_xor(best_j, sft, 64), o_id = __shfl_xor(best_id, sft, 64);
+                bool take = (o_j != kNone) && (best_j == kNone || o_lng < best_lng || (o_lng == best_lng && o_j < best_j));
+                if (take) { best_lng = o_lng; best_lat = o_lat; best_j = o_j; best_id = o_id; }
+            }
+            if (best_j != kNone) { r.flag = 1; r.dis_lat = best_lat; r.dis_lng = best_lng; r.path_id = best_id; r.ob_index = best_j; }
+#ifdef DMPP_DEBUG_SEARCH
+            r.adds = -(n - 1);           // negative: the call took the second pass
+#endif
+        }
     }
     return r;
 }

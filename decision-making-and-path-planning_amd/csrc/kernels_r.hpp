@@ -138,7 +138,7 @@ struct DecShared {                                 // 19 KB: small enough to sit
             double s0[DMPP_MAX_REFPATH];
         } junc;
     } u;
-    double part_d2[kBlock]; int part_bi[kBlock];      // team_search_obstacle
+    double part_d2[kBlock]; int part_bi[kBlock + 2];  // team_search_obstacle (+2: its teams' second-pass flags)
     SoResult around[6];
     double sweep_lng[2 * DMPP_MAX_SWEEP];
     int n[6];
@@ -146,6 +146,7 @@ struct DecShared {                                 // 19 KB: small enough to sit
     int rem_go, rem_flags;                        // remaining lane-change length tests (lane-change rule tree)
     int rem_w[2][kBlock / 64]; double rem_s[2][kBlock / 64];   // ... their per-wave run ends and partial sums
 };
+static_assert(sizeof(DecShared) <= 16 * 1280, "k_decision sits beside five searching workgroups with 16 LDS granules of 1,280 bytes");
 
 
 __device__ inline int dev_load_front(const PlannerConfig& c, const GlobalPoint3D* lane, int IdSum, int Id, GlobalPoint2D* out)
@@ -505,6 +506,9 @@ k_decision(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
         __syncthreads();
         if (tid < 6) store_path_obs(&po.around[tid], sh.around[tid], obs, sh.n[tid] != 0);
         FRONT_MARK(2)
+#ifdef DMPP_DEBUG_SEARCH
+        if (tid < 6) dbg_stamp[6 + tid] = (double)sh.around[tid].adds;       // in-order additions of the six corridor searches
+#endif
         // ---- BehaviorDecision, no-lane-change map: Decision.cpp:920-1010 ----
         // (an empty front path leaves dis_lng = 0 from the memset at Decision.cpp:794)
         const double F_lng = (nF != 0) ? sh.around[0].dis_lng : 0.0;
@@ -730,6 +734,9 @@ k_decision(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
         {
             const SoResult r = team_search_obstacle<4>(c, sh.u.junc.ref, n, sh.u.junc.s0, obs, m, -hv, hv, true, sh.part_d2, sh.part_bi);
             if (tid == 0) sh.around[0] = r;
+#ifdef DMPP_DEBUG_SEARCH
+            if (tid == 0) dbg_stamp[6] = (double)r.adds;
+#endif
         }
         __syncthreads();
         if (tid < 6) {
@@ -770,12 +777,13 @@ struct PlanShared {
     double dist[kBlock];           // also the 256-wide segment buffer of block_aim_walk
     double seg[DMPP_PATH_POINTS];
     double s[DMPP_PATH_POINTS + 8];
-    double part_d2[kBlock]; int part_bi[kBlock];      // team_search_obstacle
+    double part_d2[kBlock]; int part_bi[kBlock + 2];  // team_search_obstacle (+2: its teams' second-pass flags)
     AimPoint aim_far;
     SoResult so;
     double sh_sum;
     int sh_found, afresh, near_id, na;
 };
+static_assert(sizeof(PlanShared) <= 12 * 1280, "k_planning: 12 LDS granules of 1,280 bytes");
 
 __global__ void __launch_bounds__(kBlock)
 k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const GlobalPoint3D* __restrict__ lane_pool,
@@ -983,6 +991,9 @@ k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
         const SoResult r = team_search_obstacle<4>(c, sh.road + near_id, DMPP_PATH_POINTS - near_id, sh.s, obs, m,
                                                    (double)(float)(-1.1), (double)(float)(1.1), true, sh.part_d2, sh.part_bi);
         if (tid == 0) sh.so = r;
+#ifdef DMPP_DEBUG_SEARCH
+        if (tid == 0) dbg_stamp[6] = (double)r.adds;                          // in-order additions of the search
+#endif
     }
     __syncthreads();
 
