@@ -112,6 +112,11 @@ EpisodeStats = _dt([("n_episodes", i4), ("age", i4), ("n_end", i4, (6,)), ("last
                     ("ticks_total", np.int64), ("dist", f8), ("last_dist", f8), ("dist_total", f8)])
 EGO_RESPAWNED = 32            # EgoTrace.flags only: the record is the start of a new episode (DMPP_EGO_RESPAWNED)
 EGO_TIMEOUT = 64              # cause word only: the episode reached EpisodeModel.max_ticks (DMPP_EGO_TIMEOUT)
+# episode spawn model: a pool of start records per scene, contact ends an episode, a start record must be clear
+EPISODE_MAX_STARTS = 16
+EpisodeSpawn = _dt([("seed", np.uint64), ("clearance", f8), ("n_starts", i4), ("order", i4), ("contact", i4), ("check", i4)])
+EpisodeSpawnStats = _dt([("n_contact", i4), ("n_blocked", i4), ("n_rejected", i4), ("cur_start", i4), ("n_used", i4, (EPISODE_MAX_STARTS,))])
+EGO_CONTACT = 128             # cause words only: the ego touched an obstacle of its slice (DMPP_EGO_CONTACT)
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -246,6 +251,12 @@ def load_library(path=None):
         lib.pp_default_episode_model.restype = None
         lib.pp_set_episodes.argtypes = [vp, vp]
         lib.pp_get_episode_stats.argtypes = [vp, vp, ci]
+    spawn = hasattr(lib, "pp_set_episode_spawn") or path == LIB_PATH          # (as above: an older build may lack it)
+    if spawn:
+        lib.pp_default_episode_spawn.argtypes = [vp]
+        lib.pp_default_episode_spawn.restype = None
+        lib.pp_set_episode_spawn.argtypes = [vp, vp, vp, vp]
+        lib.pp_get_episode_spawn_stats.argtypes = [vp, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -260,7 +271,8 @@ def load_library(path=None):
     for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
             (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
             (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()) + \
-            (((28, TrafficFollow),) if react else ()) + (((29, EpisodeModel), (30, EpisodeStats)) if episodes else ()):
+            (((28, TrafficFollow),) if react else ()) + (((29, EpisodeModel), (30, EpisodeStats)) if episodes else ()) + \
+            (((31, EpisodeSpawn), (32, EpisodeSpawnStats)) if spawn else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -321,6 +333,14 @@ def default_episode_model():
     em = np.zeros(1, EpisodeModel)
     load_library().pp_default_episode_model(_ptr(em))
     return em
+
+
+def default_episode_spawn():
+    """EpisodeSpawn record of the episode spawn model (pp_default_episode_spawn): seed 1, clearance 2 m, n_starts 1, order 0 (hashed),
+    contact 1, check 3 (the obstacle slice and the egos of the world)."""
+    sp = np.zeros(1, EpisodeSpawn)
+    load_library().pp_default_episode_spawn(_ptr(sp))
+    return sp
 
 
 def default_traffic_follow():
@@ -604,6 +624,29 @@ class Planner:
         """pp_get_episode_stats: one EpisodeStats record per scene, a staged advance included (host wait)."""
         out = np.zeros(self.n, EpisodeStats)
         _check(self.lib.pp_get_episode_stats(self.h, _ptr(out), self.n))
+        return out
+
+    def set_episode_spawn(self, sp, starts_in=None, starts_state=None):
+        """pp_set_episode_spawn, after set_episodes: contact ends an episode (sp.contact), a restart draws one of
+        sp.n_starts start records and skips those within sp.clearance of an obstacle of the scene's slice or an ego of its world
+        (sp.check).  starts_in / starts_state: SceneIn / SceneState arrays of (n_starts - 1) * n records, record k (1 ..) of scene s
+        at (k - 1) * n + s; record 0 is the capture of set_episodes.  sp None: the spawn model off, the stats stay readable."""
+        if sp is None:
+            _check(self.lib.pp_set_episode_spawn(self.h, None, None, None))
+            return
+        m = np.array(sp, EpisodeSpawn).reshape(1).copy()
+        want = (int(m["n_starts"][0]) - 1) * self.n
+        si = None if starts_in is None else np.ascontiguousarray(starts_in, SceneIn).reshape(-1)
+        st = None if starts_state is None else np.ascontiguousarray(starts_state, SceneState).reshape(-1)
+        for a, name in ((si, "starts_in"), (st, "starts_state")):
+            if a is not None and 1 <= int(m["n_starts"][0]) <= EPISODE_MAX_STARTS and len(a) != want:          # (the library refuses the other counts)
+                raise ValueError(f"{name}: {len(a)} records, n_starts and the resident scenes ask for {want}")
+        _check(self.lib.pp_set_episode_spawn(self.h, _ptr(m), _ptr(si), _ptr(st)))
+
+    def episode_spawn_stats(self):
+        """pp_get_episode_spawn_stats: one EpisodeSpawnStats record per scene, a staged advance included (host wait)."""
+        out = np.zeros(self.n, EpisodeSpawnStats)
+        _check(self.lib.pp_get_episode_spawn_stats(self.h, _ptr(out), self.n))
         return out
 
     def traffic_speed(self):

@@ -24,6 +24,7 @@
 #include "kernels_a.hpp"
 #include "kernels_rt.hpp"
 #include "kernels_ep.hpp"
+#include "kernels_es.hpp"
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
 #include "kernels_f.hpp"
@@ -207,6 +208,14 @@ struct EpisodeState {
     bool on = false; EpisodeModel em = { 0, 0 };
     DevBuf<SceneIn> d_start_in; DevBuf<SceneState> d_start_state; DevBuf<EpisodeStats> d_stats;
 };
+// episode spawn model (first pp_set_episode_spawn): the model, the pool of start records - record k of scene s at
+// k * stride + s, stride even - and the stats; two sets of all three, so that a refused call leaves the one in force untouched (cur:
+// the one in force, or the last that was).  A pool is M * stride * (248 + 3424) B - 0.24 GB at 4096 scenes and M = 16 - and stays allocated
+// while the model is off; the second one exists only during a set call (and after a refused one, until the next): the pool it replaces is released once the new one is in force.  While on (only with episodes on), pp_advance_async launches k_respawn_spawn in the place of k_respawn_egos
+struct SpawnState {
+    bool on = false, ever = false; EpisodeSpawn sp = {}; int stride = 0, cur = 0;      // ever: a set call succeeded on this handle (the stats are readable)
+    DevBuf<SceneIn> d_in[2]; DevBuf<SceneState> d_state[2]; DevBuf<EpisodeSpawnStats> d_stats[2];
+};
 struct FollowState {
     bool on = false; TrafficFollow tf = {};
     DevBuf<double> d_v[2]; DevBuf<dmpp::TrafficRef> d_ref; DevBuf<int32_t> d_first, d_members;
@@ -299,6 +308,7 @@ struct pp_planner {
     TrafficState traffic;
     FollowState follow;
     EpisodeState episode;
+    SpawnState spawn;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
@@ -836,7 +846,7 @@ static int upload_pools(pp_handle h, const ObPoint* obs_pool, const ObMotion* mo
 // last (which syncs: the caller may reuse its buffers).  map_bad: scenes that k_resolve_map could not place (pp_set_egos).
 static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad = 0)
 {
-    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; note_current_set(h);
+    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; h->spawn.on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->score.on) { int r = reset_scores(h); if (r) return r; }
     if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
@@ -1448,7 +1458,13 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         else
             hipLaunchKernelGGL(dmpp::k_advance_egos, agrid, dim3(dmpp::kBlock), 0, su,
                                h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace);
-        if (h->episode.on)                // ended egos restart from their start records: the traffic, the peers and the views below see the restarted ego
+        if (h->episode.on && h->spawn.on)      // ... with the spawn model of §4l: contact ends an episode, the start record is drawn from a pool and checked for clearance
+            hipLaunchKernelGGL(dmpp::k_respawn_spawn, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
+                               h->episode.em, h->spawn.sp, 0.5 * h->cfg.Vehicle_Width, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state,
+                               h->spawn.d_in[h->spawn.cur], h->spawn.d_state[h->spawn.cur], h->fleet.on ? h->fleet.d_world_first.get() : nullptr,
+                               h->fleet.on ? h->fleet.d_world_of.get() : nullptr, h->rollout.d_flags, h->episode.d_stats, h->spawn.d_stats[h->spawn.cur],
+                               src.trace, h->score.on ? h->score.d_score.get() : nullptr);
+        else if (h->episode.on)           // ended egos restart from their start records: the traffic, the peers and the views below see the restarted ego
             hipLaunchKernelGGL(dmpp::k_respawn_egos, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
                                h->episode.em, n, P.d_in, d_in, h->d_state, h->episode.d_start_in, h->episode.d_start_state, h->rollout.d_flags, h->episode.d_stats,
                                src.trace, h->score.on ? h->score.d_score.get() : nullptr);
@@ -1904,7 +1920,7 @@ int pp_set_episodes(pp_handle h, const EpisodeModel* em)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episodes: an update is staged for the next tick (set the episodes before staging, or after the tick)");
-    if (!em) { h->episode.on = false; return PP_OK; }
+    if (!em) { h->episode.on = false; h->spawn.on = false; return PP_OK; }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_episodes: no resident scenes");
     if ((em->end_mask & ~31) != 0) return fail(PP_ERR_ARG, "pp_set_episodes: end_mask holds bits outside the five DMPP_EGO_* flags (31)");
@@ -1919,6 +1935,7 @@ int pp_set_episodes(pp_handle h, const EpisodeModel* em)
     { int r = h->episode.d_start_state.reserve(ns); if (r) return r; }
     { int r = h->episode.d_stats.reserve(ns); if (r) return r; }
     h->episode.on = false;                                // (until the copies below have landed: a failed copy leaves episodes off, not half a capture)
+    h->spawn.on = false;                                  // (record 0 of the spawn model's pool was the old capture: §4l)
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_in, h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_state, h->d_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(dmpp::k_episode_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, (int)ns, h->episode.d_stats);
@@ -1936,6 +1953,81 @@ int pp_get_episode_stats(pp_handle h, EpisodeStats* out, int n)
     HIP_TRY(hipSetDevice(h->device));
     PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_ego_flags
     return fetch(h, out, h->episode.d_stats, (size_t)n * sizeof(EpisodeStats));
+}
+
+// Episode spawn model.  Everything the host can check is checked before anything changes; the new pool is built
+// beside the one in force and takes its place only once every record is on the map.
+void pp_default_episode_spawn(EpisodeSpawn* sp)
+{
+    if (!sp) return;
+    sp->seed = 1; sp->clearance = 2.0; sp->n_starts = 1; sp->order = 0; sp->contact = 1; sp->check = 3;
+}
+
+int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* starts_in, const SceneState* starts_state)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_spawn: an update is staged for the next tick (set the spawn model before staging, or after the tick)");
+    if (!sp) { h->spawn.on = false; return PP_OK; }
+    if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_spawn: episodes are off (pp_set_episodes comes first: its capture is start record 0)");
+    const int n = h->n_scenes, M = sp->n_starts;
+    if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts must be 1 .. DMPP_EPISODE_MAX_STARTS");
+    if (!std::isfinite(sp->clearance) || sp->clearance < 0) return fail(PP_ERR_ARG, "pp_set_episode_spawn: clearance must be finite and >= 0");
+    if (sp->order != 0 && sp->order != 1) return fail(PP_ERR_ARG, "pp_set_episode_spawn: order must be 0 (hashed) or 1 (round robin)");
+    if ((sp->check & ~3) != 0) return fail(PP_ERR_ARG, "pp_set_episode_spawn: check holds bits outside 3");
+    if (M > 1 && (!starts_in || !starts_state)) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts > 1 needs the start records");
+    if (M > 1 && (h->resident_mode != 1 || !h->have_map))
+        return fail(PP_ERR_STATE, "pp_set_episode_spawn: start records are placed on the resident map (pp_set_map + pp_set_egos come first)");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the pool in force
+    PP_TRY(h->rollout.adv.wait(h->stream));
+    // The new pool, its stats included, is built in the set that is NOT in force (or was last): a refusal below leaves the one in
+    // force - and the readable stats of a model that went off - untouched
+    const int o = h->spawn.ever ? 1 - h->spawn.cur : h->spawn.cur, stride = (n + 1) & ~1;
+    const size_t recs = (size_t)M * (size_t)stride;       // room first: a failed allocation changes nothing
+    { int r = h->spawn.d_in[o].reserve(recs); if (r) return r; }
+    { int r = h->spawn.d_state[o].reserve(recs); if (r) return r; }
+    { int r = h->spawn.d_stats[o].reserve((size_t)h->caps.max_scenes); if (r) return r; }
+    const bool was_on = h->spawn.on;
+    h->spawn.on = false;                                  // (until everything below has landed: a failed copy leaves the spawn model off, not half a pool)
+    SceneIn* pin = h->spawn.d_in[o]; SceneState* pst = h->spawn.d_state[o];
+    HIP_TRY(hipMemcpyAsync(pin, h->episode.d_start_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(pst, h->episode.d_start_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->spawn.d_stats[o], 0, (size_t)h->caps.max_scenes * sizeof(EpisodeSpawnStats), h->stream));
+    int bad = 0;
+    if (M > 1) {
+        const dim3 grid((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), block(dmpp::kBlock);
+        HIP_TRY(hipMemsetAsync(h->d_map_bad, 0, sizeof(int), h->stream));
+        for (int k = 1; k < M; k++) {                     // views and junction slices from the resident map, as pp_set_egos derives them
+            SceneIn* rec = pin + (size_t)k * stride;
+            HIP_TRY(hipMemcpyAsync(rec, starts_in + (size_t)(k - 1) * n, (size_t)n * sizeof(SceneIn), hipMemcpyDefault, h->stream));
+            HIP_TRY(hipMemcpyAsync(pst + (size_t)k * stride, starts_state + (size_t)(k - 1) * n, (size_t)n * sizeof(SceneState), hipMemcpyDefault, h->stream));
+            hipLaunchKernelGGL(dmpp::k_resolve_map, grid, block, 0, h->stream, n, rec, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
+                               h->map_junctions, h->d_map_junc, h->d_map_bad);
+        }
+        hipLaunchKernelGGL(dmpp::k_spawn_pin_slices, dim3((unsigned)(((size_t)n * (M - 1) + dmpp::kBlock - 1) / dmpp::kBlock)), block, 0, h->stream, n, M, stride, pin);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&bad, h->d_map_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's arrays may go; the upload stream reads the pool from its next launch on
+    if (bad) {
+        h->spawn.on = was_on;                             // (nothing in force was touched)
+        return fail(PP_ERR_ARG, "pp_set_episode_spawn: " + std::to_string(bad) + " start record(s) name a road or lane outside the map");
+    }
+    if (o != h->spawn.cur) {                              // the pool that was in force goes (nobody reads it: joined and waited above); its stats are 80 B a scene and stay
+        h->spawn.d_in[h->spawn.cur] = DevBuf<SceneIn>(); h->spawn.d_state[h->spawn.cur] = DevBuf<SceneState>();
+    }
+    h->spawn.sp = *sp; h->spawn.stride = stride; h->spawn.cur = o; h->spawn.on = true; h->spawn.ever = true;
+    return PP_OK;
+}
+
+int pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->spawn.ever) return fail(PP_ERR_STATE, "pp_get_episode_spawn_stats: pp_set_episode_spawn was never called on this handle");
+    if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_episode_stats
+    return fetch(h, out, h->spawn.d_stats[h->spawn.cur], (size_t)n * sizeof(EpisodeSpawnStats));
 }
 
 // A grid that follows the ego: host checks only; the model is a kernel argument of the next advance.
@@ -2300,6 +2392,7 @@ size_t pp_sizeof(int which)
     case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel); case 25: return sizeof(GridFollow);
     case 26: return sizeof(TrafficTrack); case 27: return sizeof(TrafficActor); case 28: return sizeof(TrafficFollow);
     case 29: return sizeof(EpisodeModel); case 30: return sizeof(EpisodeStats);
+    case 31: return sizeof(EpisodeSpawn); case 32: return sizeof(EpisodeSpawnStats);
     default: return 0;
     }
 }

@@ -1,0 +1,154 @@
+// kernels_es.hpp — episode spawn model (build-defined): k_respawn_spawn runs in the place of k_respawn_egos while
+// pp_set_episode_spawn is in force - same point of the upload stream, same shape: one 64-lane wave per scene, four scenes per
+// 256-thread block, no LDS, no barrier.  On top of §4k it ends an episode on contact with an obstacle of the scene's slice, draws
+// the start record of a restart from a pool of M per scene and skips the candidates that are not clear of the slice and of the
+// egos of the scene's world.
+//
+// The scene index is wave-uniform (readfirstlane), so everything up to the cause word is scalar but the contact scan: there the
+// lanes stride the slice and one ballot per pass of 64 entries tells the wave whether any of them touches (only the predicate is
+// needed: subtraction is monotone, so "some d_j - hw <= 0" needs no minimum).  A scene that goes on costs lane 0 two stores.  The
+// candidate loop is wave-uniform too: per candidate the lanes stride the slice, then the member range of the world, one ballot per
+// pass, and the loop leaves on the first clear candidate.  The pool holds record k of scene s at k * stride + s with an even
+// stride: a record of the pool and the staged record it replaces share their phase within 16 bytes (wave_copy_record).
+#pragma once
+#include "kernels_ep.hpp"
+
+namespace dmpp {
+
+static_assert(sizeof(EpisodeSpawn) == 32 && sizeof(EpisodeSpawnStats) == 80 && offsetof(EpisodeSpawnStats, n_used) == 16, "spawn records (DESIGN.md §4l)");
+static_assert(DMPP_EGO_CONTACT == 128, "cause bit of §4l");
+
+// §4l 3a. mix: uint64 arithmetic mod 2^64
+__device__ __forceinline__ unsigned long long spawn_mix(unsigned long long z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// some entry j of obs[0 .. n) has (sqrt(dx dx + dy dy) - (double)radius) - hw <= lim (a NaN compares false); wave-uniform result
+__device__ __forceinline__ bool wave_slice_within(const ObPoint* __restrict__ obs, int n, double x, double y, double hw, double lim, int lane)
+{
+    for (int base = 0; base < n; base += 64) {
+        const int j = base + lane;
+        bool hit = false;
+        if (j < n) {
+            const double dx = obs[j].x - x, dy = obs[j].y - y;
+            hit = (sqrt(dx * dx + dy * dy) - (double)obs[j].radius) - hw <= lim;
+        }
+        if (wave_ballot(hit)) return true;
+    }
+    return false;
+}
+
+// some scene t != s of [p0, p1) has (sqrt(dx dx + dy dy) - hw) - hw <= lim at the pose the advance read
+__device__ __forceinline__ bool wave_world_within(const SceneIn* __restrict__ prev, int p0, int p1, int s, double x, double y, double hw, double lim, int lane)
+{
+    for (int base = p0; base < p1; base += 64) {
+        const int t = base + lane;
+        bool hit = false;
+        if (t < p1 && t != s) {
+            const double dx = prev[t].loc.globalpoint.x - x, dy = prev[t].loc.globalpoint.y - y;
+            hit = (sqrt(dx * dx + dy * dy) - hw) - hw <= lim;
+        }
+        if (wave_ballot(hit)) return true;
+    }
+    return false;
+}
+
+// prev / obs: the SceneIn records and the obstacle pool (n_obs entries) of the input set the advance read; staged, state, flags, stats,
+// trace, score: as k_respawn_egos.  pool_in / pool_state: the start records, record k of scene s at k * stride + s.  world_first /
+// world_of: the fleet's tables, or null without a fleet.  hw = 0.5 * Vehicle_Width (rounded once, on the host: exact).
+__global__ void __launch_bounds__(kBlock)
+k_respawn_spawn(EpisodeModel em, EpisodeSpawn sp, double hw, int n_scenes, int stride, const SceneIn* __restrict__ prev, const ObPoint* __restrict__ obs, int n_obs,
+                SceneIn* __restrict__ staged, SceneState* __restrict__ state, const SceneIn* __restrict__ pool_in, const SceneState* __restrict__ pool_state,
+                const int32_t* __restrict__ world_first, const int32_t* __restrict__ world_of, int32_t* __restrict__ flags,
+                EpisodeStats* __restrict__ stats, EpisodeSpawnStats* __restrict__ sstats, EgoTrace* __restrict__ trace, RolloutScore* __restrict__ score)
+{
+    const int lane = threadIdx.x & 63;
+    const int s = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kEpScenes + (threadIdx.x >> 6)));
+    if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
+    // 1. age and distance of the running episode
+    const int f = flags[s];
+    const int age = stats[s].age + 1;
+    const double px = prev[s].loc.globalpoint.x, py = prev[s].loc.globalpoint.y;
+    const double ex = staged[s].loc.globalpoint.x - px, ey = staged[s].loc.globalpoint.y - py;
+    const double dist = stats[s].dist + sqrt(ex * ex + ey * ey);
+    // the slice of the record the advance read (a sanitised record: inside the pool; anything else is taken as empty)
+    int off = prev[s].obs_off, on = prev[s].obs_n;
+    if (on <= 0 || off < 0 || (long long)off + on > (long long)n_obs) { off = 0; on = 0; }
+    const ObPoint* slice = obs + off;
+    // 1a. contact
+    const bool touch = sp.contact != 0 && wave_slice_within(slice, on, px, py, hw, 0.0, lane);
+    // 2. cause word
+    const int c = (f & em.end_mask) | ((em.max_ticks > 0 && age >= em.max_ticks) ? DMPP_EGO_TIMEOUT : 0) | (touch ? DMPP_EGO_CONTACT : 0);
+    if (c == 0) {
+        if (lane == 0) { stats[s].age = age; stats[s].dist = dist; }
+        return;
+    }
+    // 3a. start record
+    const int M = sp.n_starts;
+    const int e = stats[s].n_episodes + 1;
+    int k0;
+    if (sp.order == 0) {
+        const unsigned long long u = spawn_mix(spawn_mix(sp.seed + (unsigned long long)s) + (unsigned long long)e);
+        k0 = (int)(((u >> 32) * (unsigned long long)M) >> 32);
+    } else k0 = e % M;
+    int p0 = 0, p1 = 0;
+    if ((sp.check & 2) && world_of) { const int w = world_of[s]; p0 = world_first[w]; p1 = world_first[w + 1]; }
+    int k = k0, rejected = M, blocked = 1;
+    for (int i = 0; i < M; i++) {
+        const int cand = (k0 + i) % M;
+        const GlobalPoint3D P = pool_in[(size_t)cand * stride + s].loc.globalpoint;
+        if ((sp.check & 1) && wave_slice_within(slice, on, P.x, P.y, hw, sp.clearance, lane)) continue;
+        if (wave_world_within(prev, p0, p1, s, P.x, P.y, hw, sp.clearance, lane)) continue;
+        k = cand; rejected = i; blocked = 0;
+        break;
+    }
+    // 4. restart: SceneIn and SceneState of the scene become start record k, every byte
+    const SceneIn* start_in = pool_in + (size_t)k * stride;
+    wave_copy_record(&staged[s], &start_in[s], lane);
+    wave_copy_record(&state[s], &pool_state[(size_t)k * stride + s], lane);
+    if (lane != 0) return;
+    // 3. stats
+    EpisodeStats E = stats[s];
+    E.n_episodes = e;
+    for (int b = 0; b < 5; b++) if (c & (1 << b)) E.n_end[b] = E.n_end[b] + 1;
+    if (c & DMPP_EGO_TIMEOUT) E.n_end[5] = E.n_end[5] + 1;
+    E.last_cause = c; E.last_age = age;
+    if (E.min_age < 0 || age < E.min_age) E.min_age = age;
+    if (E.max_age < 0 || age > E.max_age) E.max_age = age;
+    E.ticks_total = E.ticks_total + (int64_t)age;
+    E.last_dist = dist; E.dist_total = E.dist_total + dist;
+    E.age = 0; E.dist = 0;
+    stats[s] = E;
+    flags[s] = 0;
+    EpisodeSpawnStats& S = sstats[s];
+    if (c & DMPP_EGO_CONTACT) S.n_contact = S.n_contact + 1;
+    S.n_blocked = S.n_blocked + blocked; S.n_rejected = S.n_rejected + rejected;
+    S.cur_start = k; S.n_used[k] = S.n_used[k] + 1;
+    // 5. trace of the start record   6. the scorecard's last ego is the one of the start record
+    const LocationOut& L = start_in[s].loc;
+    if (trace) {
+        EgoTrace t;
+        t.pose = L.globalpoint; t.velocity = L.velocity;
+        t.id_cur = L.id[clampi(L.lane_num - 1, 0, DMPP_LANESUM - 1)]; t.lane_num = L.lane_num;
+        t.flags = f | DMPP_EGO_RESPAWNED | (c & (DMPP_EGO_TIMEOUT | DMPP_EGO_CONTACT)); t._pad = 0;
+        trace[s] = t;
+    }
+    if (score) { score[s].last_pos.x = L.globalpoint.x; score[s].last_pos.y = L.globalpoint.y; score[s].last_speed = L.velocity; }
+}
+
+// obs_off / obs_n of start records 1 .. M - 1 become those of the scene's record 0 (one thread per record)
+__global__ void __launch_bounds__(kBlock)
+k_spawn_pin_slices(int n_scenes, int M, int stride, SceneIn* __restrict__ pool_in)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_scenes * (M - 1)) return;
+    const int k = 1 + i / n_scenes, s = i % n_scenes;
+    SceneIn& r = pool_in[(size_t)k * stride + s];
+    r.obs_off = pool_in[s].obs_off; r.obs_n = pool_in[s].obs_n;
+}
+
+}  // namespace dmpp

@@ -20,10 +20,15 @@
 // DESIGN.md §4j): it is written into slot 0 of all 8 member scenes and follows the nearest of the world's 8 egos.
 // With --route --episodes every ego gets a route of ONE leg and episodes are on (pp_set_episodes with the default model):
 // an ego that arrives restarts on the device from its start records, and the host prints episodes, causes and mean age per ego.
+// With --route --episodes --starts M --contact the spawn model is on as well (pp_set_episode_spawn): every ego has M start
+// records - record k is 5 k lane points behind its first one -, --contact puts a vehicle 20 m ahead of every ego that drives TOWARDS it at
+// 3 m/s and lets contact end an episode, and a restart skips the start records the vehicle stands on (the default clearance, 2 m); the
+// host prints episodes, contacts, blocked restarts and the use of each start record.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -32,8 +37,10 @@
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact)
 {
+    const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
+    if (contact) traffic = true;                      // (the vehicle to touch)
     const int W = 8, K = shared ? 4 : 0, stride = 1 + K;      // --shared: worlds of W scenes, K peer slots behind every scene's one own entry
     const int n = 64, ticks = 1200, P = 260, JP = 40, n_lanes = 2;
     const double kPi = 3.14159265358979323846, step = 0.5, w = 3.75;
@@ -117,7 +124,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
                 continue;
             }
             if (react) actors.push_back(TrafficActor{ here - 15.0, 8.0, s, 0, lane - 1, 1, 0.9f, 0 });      // (a closed track: a negative s0 wraps)
-            else actors.push_back(TrafficActor{ here + 20.0, 1.5, s, 0, lane - 1, 1, 0.9f, 0 });
+            else actors.push_back(TrafficActor{ here + 20.0, contact ? -3.0 : 1.5, s, 0, lane - 1, 1, 0.9f, 0 });
         }
     }
     pp_handle h = nullptr;
@@ -141,6 +148,17 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         CHECK(pp_score_begin(h, model.dt));
     }
     if (episodes) { EpisodeModel em; pp_default_episode_model(&em); CHECK(pp_set_episodes(h, &em)); }      // last: it captures what the calls above set up
+    if (spawn) {                                      // M start records per ego: record k stands 5 k lane points behind record 0, on the same lane
+        EpisodeSpawn sp; pp_default_episode_spawn(&sp); sp.n_starts = M; sp.contact = contact ? 1 : 0;
+        std::vector<SceneIn> in_k; std::vector<SceneState> st_k;
+        for (int k = 1; k < M; k++) for (int s = 0; s < n; s++) {
+            SceneIn e = in[(size_t)s]; const int id = e.loc.id[0] > 5 * k ? e.loc.id[0] - 5 * k : 0;      // (the egos start at point 100 or later: never clamped here)
+            const GlobalPoint3D& q = pts[(size_t)lanes[(size_t)first[(size_t)e.loc.road_num - 1] + e.loc.lane_num - 1].point_off + id];
+            e.loc.globalpoint = q; for (int l = 0; l < DMPP_LANESUM; l++) e.loc.id[l] = id;
+            in_k.push_back(e); st_k.push_back(st[(size_t)s]);
+        }
+        CHECK(pp_set_episode_spawn(h, &sp, M > 1 ? in_k.data() : nullptr, M > 1 ? st_k.data() : nullptr));
+    }
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
@@ -158,6 +176,19 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         }
         std::printf("\nepisodes: %lld ended in %d advances of %d egos, %.1f m driven in them; causes:", total, ticks, n, metres);
         for (int b = 0; b < 6; b++) if (by[b]) std::printf(" %s %lld", cause[b], by[b]);
+        std::printf("\n");
+    }
+    if (spawn) {
+        std::vector<EpisodeSpawnStats> ss(n);
+        CHECK(pp_get_episode_spawn_stats(h, ss.data(), n));
+        long long nc = 0, nb = 0, nr = 0, used[DMPP_EPISODE_MAX_STARTS] = {};
+        for (int s = 0; s < n; s++) {
+            nc += ss[(size_t)s].n_contact; nb += ss[(size_t)s].n_blocked; nr += ss[(size_t)s].n_rejected;
+            for (int k = 0; k < M; k++) used[k] += ss[(size_t)s].n_used[k];
+        }
+        std::printf("spawn: %d start records per ego, contact %s: %lld episodes ended on contact, %lld restarts found no clear record, %lld records rejected; restarts per record:",
+                    M, contact ? "ends an episode" : "off", nc, nb, nr);
+        for (int k = 0; k < M; k++) std::printf(" %lld", used[k]);
         std::printf("\n");
     }
     if (traffic) {
@@ -204,7 +235,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false; int starts = 0;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -213,13 +244,19 @@ int main(int argc, char** argv)
         else if (std::strcmp(argv[a], "--react") == 0) react = true;
         else if (std::strcmp(argv[a], "--shared") == 0) shared = true;
         else if (std::strcmp(argv[a], "--episodes") == 0) episodes = true;
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--contact") == 0) contact = true;
+        else if (std::strcmp(argv[a], "--starts") == 0 && a + 1 < argc) starts = std::atoi(argv[++a]);
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
     if (shared && !(route && fleet && traffic)) { std::fprintf(stderr, "--shared puts one vehicle into every world: use it with --route --fleet --traffic\n"); return 2; }
     if (episodes && !route) { std::fprintf(stderr, "--episodes restarts egos that arrive: use it with --route\n"); return 2; }
-    if (route) return run_route(follow, traffic, react, shared, episodes);
+    if ((starts || contact) && !episodes) { std::fprintf(stderr, "--starts / --contact shape the restarts: use them with --route --episodes\n"); return 2; }
+    if (starts < 0 || starts > DMPP_EPISODE_MAX_STARTS) { std::fprintf(stderr, "--starts takes 1 .. %d\n", DMPP_EPISODE_MAX_STARTS); return 2; }
+    if (contact && (react || shared)) { std::fprintf(stderr, "--contact brings its own oncoming vehicle: not with --react / --shared\n"); return 2; }
+    if (starts && shared) { std::fprintf(stderr, "--starts places its records behind each ego on its lane: not with the platoons of --shared\n"); return 2; }
+    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

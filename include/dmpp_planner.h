@@ -379,6 +379,28 @@ void pp_default_episode_model(EpisodeModel* em);     /* end_mask 31 (all five fl
 int  pp_set_episodes(pp_handle h, const EpisodeModel* em);
 int  pp_get_episode_stats(pp_handle h, EpisodeStats* out, int n_scenes);
 
+/* ---- episode spawn model: start-record pools, contact ending, spawn clearance -------------------------------------
+ * On top of pp_set_episodes, which it requires to be on (PP_ERR_STATE otherwise).  While the spawn model is on, k_respawn_spawn runs
+ * in the place of k_respawn_egos: with sp->contact != 0 an ego whose position lies within half a vehicle width of an obstacle of its
+ * slice - the plain pool entries of the set the advance read, the motion pool ignored - ends its episode with DMPP_EGO_CONTACT in
+ * the cause word; a restart draws one of sp->n_starts start records (order 0: a hash of seed, scene and episode number; 1: round
+ * robin), skips the candidates that stand within sp->clearance of an obstacle of the slice (check bit 0) or of an ego of the scene's
+ * world at the pose the advance read (check bit 1, only while a fleet is on), and takes the first clear one - or its first
+ * choice if none is clear (EpisodeSpawnStats.n_blocked).  The restart itself is that of §4k with the chosen record.
+ * starts_in / starts_state: (n_starts - 1) * n records each, record k (1 .. n_starts - 1) of scene s at index (k - 1) * n + s, so
+ * that every k is a plain array of n records as pp_set_egos / pp_set_state take them; both may be NULL with n_starts == 1.  Record 0
+ * is the capture of pp_set_episodes.  Lane views and junction slices of the records are derived from the resident map as for
+ * pp_set_egos, obs_off / obs_n become those of the scene's record 0.  n_starts > 1 needs scenes resident from pp_set_map +
+ * pp_set_egos (PP_ERR_STATE).  A staged update: PP_ERR_STATE.  PP_ERR_ARG: n_starts outside 1 .. DMPP_EPISODE_MAX_STARTS, a clearance
+ * that is not finite or is negative, order outside 0 | 1, check & ~3, NULL arrays with n_starts > 1, a record that names a road or
+ * lane outside the map.  Nothing changes on any of these.  One host wait.
+ * sp NULL: the spawn model off, k_respawn_egos runs again, the stats stay readable.  Every successful pp_set_episodes - NULL
+ * included - switches it off (its record 0 is gone), and so do pp_set_scenes / pp_set_egos / pp_set_n_scenes.
+ * pp_get_episode_spawn_stats waits as pp_get_episode_stats does; PP_ERR_STATE on a handle that never set a spawn model. */
+void pp_default_episode_spawn(EpisodeSpawn* sp);     /* seed 1, clearance 2 m, n_starts 1, order 0, contact 1, check 3 */
+int  pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* starts_in, const SceneState* starts_state);
+int  pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n_scenes);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -443,7 +465,8 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 2 SceneIn, 3 SceneState, 4 PlanOut, 5 GridOut, 6 ObPoint, 7 ObMotion, 8 Path_Obs, 9 LocationOut,
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
- * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats */
+ * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
+ * 31 EpisodeSpawn, 32 EpisodeSpawnStats */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -370,6 +370,28 @@ typedef struct EpisodeStats {
     double  dist, last_dist, dist_total;   /* metres: running episode, last ended one, all ended ones      */
 } EpisodeStats;                                                             /* 80 B */
 
+/* ---- episode spawn model (build-defined), on top of pp_set_episodes -------------------------------
+ * pp_set_episode_spawn gives every scene a POOL of up to 16 start records (record 0 is the capture of pp_set_episodes), lets
+ * contact with an obstacle of the scene's slice end an episode, and checks a start record's pose against the slice and the
+ * egos of the scene's world before a restart takes it. */
+#define DMPP_EPISODE_MAX_STARTS 16
+#define DMPP_EGO_CONTACT 128    /* cause words only (last_cause, EgoTrace.flags of a restart): the ego touched an obstacle */
+typedef struct EpisodeSpawn {
+    uint64_t seed;              /* of the hashed start choice                                              */
+    double   clearance;         /* metres, finite, >= 0: a start record this close to an obstacle or ego is blocked */
+    int32_t  n_starts;          /* M: 1 .. DMPP_EPISODE_MAX_STARTS; record 0 is the capture of pp_set_episodes */
+    int32_t  order;             /* 0: hashed, 1: round robin                                               */
+    int32_t  contact;           /* != 0: contact ends an episode                                           */
+    int32_t  check;             /* bit 0: the scene's obstacle slice; bit 1: the egos of its world         */
+} EpisodeSpawn;                                                             /* 32 B */
+typedef struct EpisodeSpawnStats {
+    int32_t n_contact;          /* ended episodes whose cause word had CONTACT                             */
+    int32_t n_blocked;          /* restarts for which no start record was clear                            */
+    int32_t n_rejected;         /* start records rejected by the clearance check, all restarts             */
+    int32_t cur_start;          /* start record of the running episode (0 after the set call)              */
+    int32_t n_used[DMPP_EPISODE_MAX_STARTS];   /* restarts onto record k (the first episode is not counted) */
+} EpisodeSpawnStats;                                                        /* 80 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

@@ -19,7 +19,12 @@ A of the scene's own obstacle entries, driving the scene's current lane as an op
 scenes after the same pp_set_traffic, switched off again, so both legs start from the same pool with the same obs_n - alternating.
 EPISODES=1: every run has a rollout leg of routed ring egos with ONE-leg routes and episodes on (pp_set_episodes, default model:
 k_respawn_egos behind k_advance_route, arrived egos restart) and one with them off on the same scenes (arrived egos freeze),
-alternating; with ONE_ROLLOUT one more leg with episodes on alone, for rocprofv3 --kernel-trace --stats."""
+alternating; with ONE_ROLLOUT one more leg with episodes on alone, for rocprofv3 --kernel-trace --stats.
+EPISODES=1 with SPAWN=M and / or CONTACT=1: both legs have episodes on, on the ring with traffic - OBS obstacle entries per scene
+(default 1), the first a vehicle that drives the ego's lane towards it at 3 m/s from 20 m ahead (pp_set_traffic), the others far away -
+and the second leg has the spawn model on as well (pp_set_episode_spawn, DESIGN.md §4l: k_respawn_spawn in the place of
+k_respawn_egos) with M start records per scene - record k of scene s is the start of scene (s + k) mod n - and contact ending an
+episode if CONTACT=1; the default clearance and check."""
 import os
 import statistics
 import sys
@@ -165,6 +170,55 @@ def episodes_run(on):
     return n * steps / dt, frozen, ended
 
 
+SPAWN = int(os.environ.get("SPAWN", "0"))
+CONTACT = os.environ.get("CONTACT", "0") == "1"
+
+
+def spawn_run(on):
+    import route_scenes as rs
+    import traffic_model as tm
+    import traffic_scenes as ts
+    k_obs, M = int(os.environ.get("OBS", "1")), max(SPAWN, 1)
+    rcfg = dm.default_config(128)
+    rcfg["grid_stage"] = 0
+    m = rs.build_ring(dm)
+    sc, legs, rf = rs.make_egos(dm, rcfg, m, n, seed=5, lanes=(1, 2), ids=(10, 250), legs=(1, 1), n_obs=k_obs)
+    sc["mot_pool"] = None
+    sc["obs_pool"]["x"], sc["obs_pool"]["y"], sc["obs_pool"]["radius"] = 1e6, 1e6, 0.5
+    sc["scene_in"]["obs_n"] = k_obs
+    polylines = [(ts.ring_track(dm, m, 1), True), (ts.ring_track(dm, m, 2), True)]
+    tracks, pts = ts.pack(dm, polylines)
+    cums = [tm.cumulative(p["x"], p["y"], True) for p, _ in polylines]
+    rows = []
+    for s in range(n):
+        loc = sc["scene_in"]["loc"][s]
+        lane = int(loc["lane_num"])
+        here = cums[lane - 1][ts.SEG * (int(loc["road_num"]) - 1) + int(loc["id"][lane - 1])]
+        rows.append((here + 20.0, -3.0, s, 0, lane - 1, 7, 0.9))
+    pl = dm.Planner(rcfg, device=0, **rs.caps(m, n, k_obs))
+    pl.set_map(m)
+    pl.set_egos(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    pl.set_route(legs, rf)
+    pl.set_traffic(tracks, pts, ts.actors(dm, rows))
+    pl.set_episodes()
+    if on:
+        sp = dm.default_episode_spawn()
+        sp["n_starts"], sp["contact"] = M, int(CONTACT)
+        roll = lambda a: np.concatenate([np.roll(a, -k, axis=0) for k in range(1, M)]) if M > 1 else None
+        pl.set_episode_spawn(sp, roll(sc["scene_in"]), roll(sc["state"]))
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    ended = int(pl.episode_stats()["n_episodes"].sum())
+    ss = pl.episode_spawn_stats() if on else None
+    pl.close()
+    return n * steps / dt, ended, (0, 0, 0) if ss is None else (int(ss["n_contact"].sum()), int(ss["n_blocked"].sum()), int(ss["n_rejected"].sum()))
+
+
 def follow_run(on):
     import route_scenes as rs
     rcfg = dm.default_config(256)
@@ -265,6 +319,21 @@ if TRAFFIC > 0:
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with traffic alone
         traffic_run(True)
+    sys.exit(0)
+if os.environ.get("EPISODES", "0") == "1" and (SPAWN > 0 or CONTACT):
+    off, on = [], []
+    for r in range(runs):
+        a, ea, _ = spawn_run(False)
+        b, eb, (nc, nb, nr) = spawn_run(True)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos with traffic, obs_n %s  episodes alone %.3f M ticks/s (%d episodes ended)   spawn model on (M %d, contact %d) %.3f M ticks/s "
+              "(%d episodes ended, %d on contact, %d blocked restarts, %d rejected records)" %
+              (r, n, os.environ.get("OBS", "1"), a / 1e6, ea, max(SPAWN, 1), int(CONTACT), b / 1e6, eb, nc, nb, nr), flush=True)
+    print("median  %d ring egos  episodes alone %.3f M ticks/s (spread %.3f)   spawn model on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with the spawn model alone
+        spawn_run(True)
     sys.exit(0)
 if os.environ.get("EPISODES", "0") == "1":
     off, on = [], []
