@@ -117,6 +117,8 @@ EPISODE_MAX_STARTS = 16
 EpisodeSpawn = _dt([("seed", np.uint64), ("clearance", f8), ("n_starts", i4), ("order", i4), ("contact", i4), ("check", i4)])
 EpisodeSpawnStats = _dt([("n_contact", i4), ("n_blocked", i4), ("n_rejected", i4), ("cur_start", i4), ("n_used", i4, (EPISODE_MAX_STARTS,))])
 EGO_CONTACT = 128             # cause words only: the ego touched an obstacle of its slice (DMPP_EGO_CONTACT)
+# episode traffic reset: the actors of a restarted scene go back to a start state, one set per start record
+TrafficStart = _dt([("s", f8), ("v", f8)])
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -257,6 +259,10 @@ def load_library(path=None):
         lib.pp_default_episode_spawn.restype = None
         lib.pp_set_episode_spawn.argtypes = [vp, vp, vp, vp]
         lib.pp_get_episode_spawn_stats.argtypes = [vp, vp, ci]
+    treset = hasattr(lib, "pp_set_episode_traffic") or path == LIB_PATH          # (as above: an older build may lack it)
+    if treset:
+        lib.pp_set_episode_traffic.argtypes = [vp, ci, vp]
+        lib.pp_get_episode_traffic_resets.argtypes = [vp, vp, ci]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -272,7 +278,7 @@ def load_library(path=None):
             (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
             (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()) + \
             (((28, TrafficFollow),) if react else ()) + (((29, EpisodeModel), (30, EpisodeStats)) if episodes else ()) + \
-            (((31, EpisodeSpawn), (32, EpisodeSpawnStats)) if spawn else ()):
+            (((31, EpisodeSpawn), (32, EpisodeSpawnStats)) if spawn else ()) + (((33, TrafficStart),) if treset else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -647,6 +653,26 @@ class Planner:
         """pp_get_episode_spawn_stats: one EpisodeSpawnStats record per scene, a staged advance included (host wait)."""
         out = np.zeros(self.n, EpisodeSpawnStats)
         _check(self.lib.pp_get_episode_spawn_stats(self.h, _ptr(out), self.n))
+        return out
+
+    def set_episode_traffic(self, n_sets, starts=None):
+        """pp_set_episode_traffic, after set_traffic, set_traffic_follow, set_episodes and set_episode_spawn: from
+        the next advance on the actors of a scene whose ego restarts go back to a start state.  Set 0 is captured by the call (the
+        current s and v of every actor); starts: TrafficStart records of sets 1 .. n_sets - 1, set k of actor a at
+        (k - 1) * n_actors + a.  n_sets is 1 or the n_starts of the spawn model in force; 0: the reset off, the counters stay readable."""
+        st = None if starts is None else np.ascontiguousarray(starts, TrafficStart).reshape(-1)
+        want = (int(n_sets) - 1) * getattr(self, "n_traffic", 0)
+        if st is not None and int(n_sets) >= 1 and len(st) != want:          # (the library refuses the other counts)
+            raise ValueError(f"starts: {len(st)} records, n_sets and the actors ask for {want}")
+        _check(self.lib.pp_set_episode_traffic(self.h, int(n_sets), _ptr(st)))
+        if int(n_sets) > 0:
+            self.n_traffic_reset = getattr(self, "n_traffic", 0)          # (the counters outlive the traffic they counted)
+
+    def episode_traffic_resets(self):
+        """pp_get_episode_traffic_resets: how often every actor was put back on a start state since set_episode_traffic, a staged
+        advance included (host wait)."""
+        out = np.zeros(getattr(self, "n_traffic_reset", 0), np.int32)
+        _check(self.lib.pp_get_episode_traffic_resets(self.h, _ptr(out), len(out)))
         return out
 
     def traffic_speed(self):

@@ -220,6 +220,14 @@ struct FollowState {
     bool on = false; TrafficFollow tf = {};
     DevBuf<double> d_v[2]; DevBuf<dmpp::TrafficRef> d_ref; DevBuf<int32_t> d_first, d_members;
 };
+// episode traffic reset (first pp_set_episode_traffic): every actor's scene, the table of start states - set k of
+// actor a at k * actors + a - and the counters; two sets of table and counters, so that a failed call leaves the ones in force
+// untouched (cur: the ones in force, or the last that were).  While on (only with per-scene traffic and episodes on),
+// pp_advance_async launches k_reset_traffic behind its traffic kernel.  The counters stay readable after the reset went off
+struct TrafficResetState {
+    bool on = false, ever = false; int n_sets = 0, actors = 0, cur = 0;      // ever: a set call succeeded on this handle (the counters are readable)
+    DevBuf<int32_t> d_scene; DevBuf<TrafficStart> d_starts[2]; DevBuf<int32_t> d_resets[2];
+};
 
 }  // namespace
 
@@ -309,6 +317,7 @@ struct pp_planner {
     FollowState follow;
     EpisodeState episode;
     SpawnState spawn;
+    TrafficResetState treset;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
@@ -414,6 +423,19 @@ int follow_traffic(pp_planner* h, hipStream_t st, const SceneIn* d_in, ObPoint* 
     HIP_TRY(hipGetLastError());
     h->traffic.cur = cur ^ 1;
     return PP_OK;
+}
+
+// Episode traffic reset of the input set an advance stages: behind the episode step, whose EpisodeStats.age and
+// EpisodeSpawnStats.cur_start it reads, and behind the traffic kernel of the advance, whose arrays - the current ones: with
+// following the pair follow_traffic has just flipped to - and pool entries it overwrites for the actors of restarted scenes.
+void reset_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot)
+{
+    const int n = h->treset.actors, cur = h->traffic.cur;
+    hipLaunchKernelGGL(dmpp::k_reset_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
+                       n, h->treset.n_sets, h->traffic.d_pin, h->treset.d_scene, h->episode.d_stats,
+                       h->treset.n_sets > 1 ? h->spawn.d_stats[h->spawn.cur].get() : nullptr, h->treset.d_starts[h->treset.cur],
+                       h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], h->follow.on ? h->follow.d_v[cur].get() : nullptr,
+                       h->treset.d_resets[h->treset.cur], d_obs, d_mot);
 }
 
 // The buffers of following for the actors pp_set_traffic has just uploaded, and v = speed.  The caller has joined the chains and
@@ -846,7 +868,7 @@ static int upload_pools(pp_handle h, const ObPoint* obs_pool, const ObMotion* mo
 // last (which syncs: the caller may reuse its buffers).  map_bad: scenes that k_resolve_map could not place (pp_set_egos).
 static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad = 0)
 {
-    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; h->spawn.on = false; note_current_set(h);
+    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; h->spawn.on = false; h->treset.on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->score.on) { int r = reset_scores(h); if (r) return r; }
     if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
@@ -1410,7 +1432,7 @@ struct StageSource {
 // staged - and puts k_advance_egos / k_advance_route in the place of the copy of the SceneIn records: the kernel reads what the
 // last tick's Planning kernel wrote (PlanOut, SceneState), so the upload stream waits for that tick's front-chain event, not for
 // its search; the next tick's front chain, the only writer of SceneState, waits for the set's `up` in turn.
-// Order on the upload stream: SceneIn records and obstacle pool -> k_move_traffic -> k_couple_fleet (the two write disjoint pool
+// Order on the upload stream: SceneIn records and obstacle pool -> k_move_traffic (-> k_reset_traffic, §4m) -> k_couple_fleet (the two write disjoint pool
 // entries: traffic a scene's own, the fleet the peer slots behind them, at the poses just staged) -> k_resolve_map ->
 // k_sanitise_scenes -> `up`, which the tick that adopts the set waits for.
 static int stage_inputs(pp_handle h, const StageSource& src)
@@ -1473,6 +1495,7 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }
         else move_traffic(h, su, d_obs, d_mot, advance ? src.ego->dt : 0.0);
     }
+    if (advance && h->treset.on) reset_traffic(h, su, d_obs, d_mot);      // the actors of a scene that has just restarted go back to a start state (§4m)
     if (h->fleet.on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
         if (!advance) n_obs = std::max(n_obs, h->fleet.end);      // (an advance inherits the count of the current set)
         couple_fleet(h, su, d_in, d_obs, d_mot);
@@ -1703,7 +1726,7 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     const std::string fn = world ? "pp_set_world_traffic" : "pp_set_traffic";
     if (n_tracks < 0 || n_points < 0 || n_actors < 0) return fail(PP_ERR_ARG, fn + ": negative count");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, fn + ": an update is staged for the next tick (set the traffic before staging, or after the tick)");
-    if (n_actors == 0) { h->traffic.on = false; return PP_OK; }
+    if (n_actors == 0) { h->traffic.on = false; h->treset.on = false; return PP_OK; }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, fn + ": no resident scenes");
     if (world && !h->fleet.on) return fail(PP_ERR_STATE, fn + ": no fleet is set (the worlds are those of pp_set_fleet; max_peers = 0 is a legal fleet)");
@@ -1777,6 +1800,7 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     HIP_TRY(hipStreamSynchronize(h->stream));
     // room first.  An allocation that fails leaves its own array as it was, but may follow one that replaced another: the old
     // traffic then goes off rather than run on half a set
+    h->treset.on = false;                                 // (the start states of §4m were captured from the actors this call replaces)
     if ((rc = h->traffic.d_pin.reserve((size_t)n_actors)) || (rc = h->traffic.d_s[0].reserve((size_t)n_actors)) || (rc = h->traffic.d_tracks.reserve((size_t)n_tracks)) ||
         (rc = h->traffic.d_cum.reserve(cum.size())) || (rc = h->traffic.d_pts.reserve(pts.size())) ||
         (world && (rc = h->traffic.d_world.reserve((size_t)n_actors)))) { h->traffic.on = false; return rc; }
@@ -1838,6 +1862,7 @@ int pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf)
         if (tf->lateral < 0 || tf->headway < 0) return fail(PP_ERR_ARG, "pp_set_traffic_follow: lateral and headway must be >= 0");
     }
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_traffic_follow: an update is staged for the next tick (set the model before staging, or after the tick)");
+    h->treset.on = false;                                 // (nothing below refuses: the start states of §4m were captured under the model this call replaces)
     if (!h->traffic.on) {                                 // takes effect with the next pp_set_traffic
         h->follow.on = tf != nullptr; if (tf) h->follow.tf = *tf;
         return PP_OK;
@@ -1920,7 +1945,7 @@ int pp_set_episodes(pp_handle h, const EpisodeModel* em)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episodes: an update is staged for the next tick (set the episodes before staging, or after the tick)");
-    if (!em) { h->episode.on = false; h->spawn.on = false; return PP_OK; }
+    if (!em) { h->episode.on = false; h->spawn.on = false; h->treset.on = false; return PP_OK; }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_episodes: no resident scenes");
     if ((em->end_mask & ~31) != 0) return fail(PP_ERR_ARG, "pp_set_episodes: end_mask holds bits outside the five DMPP_EGO_* flags (31)");
@@ -1936,6 +1961,7 @@ int pp_set_episodes(pp_handle h, const EpisodeModel* em)
     { int r = h->episode.d_stats.reserve(ns); if (r) return r; }
     h->episode.on = false;                                // (until the copies below have landed: a failed copy leaves episodes off, not half a capture)
     h->spawn.on = false;                                  // (record 0 of the spawn model's pool was the old capture: §4l)
+    h->treset.on = false;                                 // (... and set 0 of the traffic reset went with it: §4m)
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_in, h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_state, h->d_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(dmpp::k_episode_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, (int)ns, h->episode.d_stats);
@@ -1967,7 +1993,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_spawn: an update is staged for the next tick (set the spawn model before staging, or after the tick)");
-    if (!sp) { h->spawn.on = false; return PP_OK; }
+    if (!sp) { h->spawn.on = false; h->treset.on = false; return PP_OK; }
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_spawn: episodes are off (pp_set_episodes comes first: its capture is start record 0)");
     const int n = h->n_scenes, M = sp->n_starts;
     if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts must be 1 .. DMPP_EPISODE_MAX_STARTS");
@@ -1987,8 +2013,9 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     { int r = h->spawn.d_in[o].reserve(recs); if (r) return r; }
     { int r = h->spawn.d_state[o].reserve(recs); if (r) return r; }
     { int r = h->spawn.d_stats[o].reserve((size_t)h->caps.max_scenes); if (r) return r; }
-    const bool was_on = h->spawn.on;
+    const bool was_on = h->spawn.on, reset_was_on = h->treset.on;
     h->spawn.on = false;                                  // (until everything below has landed: a failed copy leaves the spawn model off, not half a pool)
+    h->treset.on = false;                                 // (the traffic reset of §4m reads cur_start of the model in force: it goes with it)
     SceneIn* pin = h->spawn.d_in[o]; SceneState* pst = h->spawn.d_state[o];
     HIP_TRY(hipMemcpyAsync(pin, h->episode.d_start_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(pst, h->episode.d_start_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
@@ -2010,7 +2037,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     }
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's arrays may go; the upload stream reads the pool from its next launch on
     if (bad) {
-        h->spawn.on = was_on;                             // (nothing in force was touched)
+        h->spawn.on = was_on; h->treset.on = reset_was_on;      // (nothing in force was touched)
         return fail(PP_ERR_ARG, "pp_set_episode_spawn: " + std::to_string(bad) + " start record(s) name a road or lane outside the map");
     }
     if (o != h->spawn.cur) {                              // the pool that was in force goes (nobody reads it: joined and waited above); its stats are 80 B a scene and stay
@@ -2028,6 +2055,62 @@ int pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n)
     HIP_TRY(hipSetDevice(h->device));
     PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_episode_stats
     return fetch(h, out, h->spawn.d_stats[h->spawn.cur], (size_t)n * sizeof(EpisodeSpawnStats));
+}
+
+// Episode traffic reset.  Everything is checked on the host before anything changes; the new table and its counters
+// are built beside the ones in force and take their place only once every copy has landed.
+int pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_traffic: an update is staged for the next tick (set the traffic reset before staging, or after the tick)");
+    if (n_sets == 0) { h->treset.on = false; return PP_OK; }
+    if (!h->traffic.on) return fail(PP_ERR_STATE, "pp_set_episode_traffic: no traffic is set (pp_set_traffic comes first)");
+    if (h->traffic.world) return fail(PP_ERR_STATE, "pp_set_episode_traffic: world traffic is in force (one vehicle belongs to many egos: a reset has no owner)");
+    if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_traffic: episodes are off (pp_set_episodes comes first)");
+    const int M = h->spawn.on ? h->spawn.sp.n_starts : 1;
+    if (n_sets < 0 || (n_sets != 1 && n_sets != M))
+        return fail(PP_ERR_ARG, "pp_set_episode_traffic: n_sets must be 1 or the n_starts of the spawn model in force (" + std::to_string(M) + ")");
+    if (n_sets > 1 && !starts) return fail(PP_ERR_ARG, "pp_set_episode_traffic: n_sets > 1 needs the start states");
+    const size_t n = (size_t)h->traffic.actors, given = starts ? (size_t)(n_sets - 1) * n : 0;
+    for (size_t i = 0; i < given; i++) {
+        if (!std::isfinite(starts[i].s)) return fail(PP_ERR_ARG, "pp_set_episode_traffic: start state " + std::to_string(i) + " has a non-finite s");
+        if (!std::isfinite(starts[i].v) || starts[i].v < 0) return fail(PP_ERR_ARG, "pp_set_episode_traffic: start state " + std::to_string(i) + ": v must be finite and >= 0");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged) ...
+    PP_TRY(h->rollout.adv.wait(h->stream));               // ... and the upload stream, which writes s / v, is behind the last of them
+    const int o = h->treset.ever ? 1 - h->treset.cur : h->treset.cur;
+    { int r = h->treset.d_scene.reserve(n); if (r) return r; }      // room first: a failed allocation changes nothing
+    { int r = h->treset.d_starts[o].reserve((size_t)n_sets * n); if (r) return r; }
+    { int r = h->treset.d_resets[o].reserve(n); if (r) return r; }
+    // (d_scene is single: while the reset is on it holds the scenes of the traffic in force, which is what is written again)
+    HIP_TRY(hipMemcpyAsync(h->treset.d_scene, h->traffic.scene_of.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    TrafficStart* tab = h->treset.d_starts[o];
+    static_assert(sizeof(TrafficStart) == 16 && offsetof(TrafficStart, s) == 0 && offsetof(TrafficStart, v) == 8, "set 0 is gathered field by field");
+    // set 0, the capture: s of the current array; v of the current array while following is on, else the speed of every pin
+    HIP_TRY(hipMemcpy2DAsync(&tab->s, sizeof(TrafficStart), h->traffic.d_s[h->traffic.cur], sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
+    if (h->follow.on)
+        HIP_TRY(hipMemcpy2DAsync(&tab->v, sizeof(TrafficStart), h->follow.d_v[h->traffic.cur], sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
+    else
+        HIP_TRY(hipMemcpy2DAsync(&tab->v, sizeof(TrafficStart), h->traffic.d_pin, sizeof(dmpp::TrafficPin), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
+    if (given) HIP_TRY(hipMemcpyAsync(tab + n, starts, given * sizeof(TrafficStart), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->treset.d_resets[o], 0, n * sizeof(int32_t), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's array may go; the upload stream reads the table from its next launch on
+    if (o != h->treset.cur) h->treset.d_starts[h->treset.cur] = DevBuf<TrafficStart>();      // the table that was in force goes; its counters are 4 B an actor and stay
+    h->treset.n_sets = n_sets; h->treset.actors = (int)n; h->treset.cur = o; h->treset.on = true; h->treset.ever = true;
+    return PP_OK;
+}
+
+int pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n)
+{
+    if (!h || (!n_resets && n > 0)) return fail(PP_ERR_ARG, "null argument");
+    if (!h->treset.ever) return fail(PP_ERR_STATE, "pp_get_episode_traffic_resets: pp_set_episode_traffic was never called on this handle");
+    if (n < 0 || n > h->treset.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
+    if (n == 0) return PP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_traffic_state
+    if (h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
+    return fetch(h, n_resets, h->treset.d_resets[h->treset.cur], (size_t)n * sizeof(int32_t));
 }
 
 // A grid that follows the ego: host checks only; the model is a kernel argument of the next advance.
@@ -2392,7 +2475,7 @@ size_t pp_sizeof(int which)
     case 23: return sizeof(RouteLeg); case 24: return sizeof(RouteModel); case 25: return sizeof(GridFollow);
     case 26: return sizeof(TrafficTrack); case 27: return sizeof(TrafficActor); case 28: return sizeof(TrafficFollow);
     case 29: return sizeof(EpisodeModel); case 30: return sizeof(EpisodeStats);
-    case 31: return sizeof(EpisodeSpawn); case 32: return sizeof(EpisodeSpawnStats);
+    case 31: return sizeof(EpisodeSpawn); case 32: return sizeof(EpisodeSpawnStats); case 33: return sizeof(TrafficStart);
     default: return 0;
     }
 }

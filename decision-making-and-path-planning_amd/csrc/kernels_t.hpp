@@ -175,6 +175,37 @@ k_move_traffic(int n_actors, double step, const TrafficPin* __restrict__ actors,
     traffic_store(obs, mot, pin.pool, traffic_pose(t, pts, pin, s));
 }
 
+// ---- episode traffic reset: k_reset_traffic runs in an advance behind k_move_traffic / k_follow_traffic while
+// pp_set_episode_traffic is in force and puts the actors of every scene that RESTARTED in this advance - EpisodeStats.age == 0
+// behind the episode step - back on a start state: set cur_start of the scene's spawn record (n_sets > 1) or set 0.
+//
+// One thread per actor, 256-thread blocks, no LDS, no barrier, no scratch: the shape of k_move_traffic.  A thread whose scene
+// goes on leaves after two loads (its scene, the scene's age).  The others discard the step the traffic kernel has just made:
+// s' = wrap(s*) and - following on - v' = v* (speed > 0) or speed go into the CURRENT arrays (the ones that kernel wrote), the
+// pose of s' into the pinned pool entry with a zero ObMotion, and the actor's counter goes up by one.  Table: set k of actor a
+// at k * n_actors + a.  v_arr: nullptr while following is off; sstats: read only with n_sets > 1.
+__global__ void __launch_bounds__(kBlock)
+k_reset_traffic(int n_actors, int n_sets, const TrafficPin* __restrict__ actors, const int32_t* __restrict__ scene_of,
+                const EpisodeStats* __restrict__ stats, const EpisodeSpawnStats* __restrict__ sstats, const TrafficStart* __restrict__ starts,
+                const TrafficTrackDev* __restrict__ tracks, const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts,
+                double* __restrict__ s_arr, double* __restrict__ v_arr, int32_t* __restrict__ n_resets, ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const int a = blockIdx.x * kBlock + threadIdx.x;
+    if (a >= n_actors) return;
+    const int c = scene_of[a];
+    if (stats[c].age != 0) return;                      // the scene goes on: its actors stay as the traffic kernel wrote them
+    int k = 0;
+    if (n_sets > 1) { k = sstats[c].cur_start; if (k < 0 || k >= n_sets) k = 0; }      // (the set call checked n_sets == n_starts: never taken)
+    const TrafficStart st = starts[(size_t)k * (size_t)n_actors + (size_t)a];
+    const TrafficPin pin = actors[a];
+    const TrackView t = traffic_view(tracks, cum, pin.track);
+    const double s = traffic_wrap(st.s, t.L, t.closed);
+    s_arr[a] = s;
+    if (v_arr) v_arr[a] = pin.speed > 0 ? st.v : pin.speed;      // (§4i: a parked or reversing actor keeps v = speed)
+    traffic_store(obs, mot, pin.pool, traffic_pose(t, pts, pin, s));
+    n_resets[a] = n_resets[a] + 1;
+}
+
 // ---- car-following traffic: k_follow_traffic takes the place of k_move_traffic in an advance while following is on.
 //
 // One 64-lane wave per actor, four actors per 256-thread block, no LDS, no barrier, no scratch (the shape of k_couple_fleet).  The

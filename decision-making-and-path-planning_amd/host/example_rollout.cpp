@@ -24,6 +24,10 @@
 // records - record k is 5 k lane points behind its first one -, --contact puts a vehicle 20 m ahead of every ego that drives TOWARDS it at
 // 3 m/s and lets contact end an episode, and a restart skips the start records the vehicle stands on (the default clearance, 2 m); the
 // host prints episodes, contacts, blocked restarts and the use of each start record.
+// With --route --episodes --traffic --reset-traffic (or --contact for the traffic) the vehicle of a restarted ego goes back to a start state
+// (pp_set_episode_traffic): with --contact the run of §4l loses its episodes of age 1 - no ego restarts into the vehicle
+// that drove on over its start pose -, and with --starts M every start record has its own set: the vehicle at its offset from THAT record.
+// The host prints the resets and the shortest episode.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -37,7 +41,7 @@
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset)
 {
     const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
     if (contact) traffic = true;                      // (the vehicle to touch)
@@ -99,8 +103,15 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
     // --traffic: one closed track per lane number - the lane's points on road 1, its junction polyline, road 2 ... - and one vehicle
     // per ego, 20 m ahead of it along that track, in the ego's single obstacle entry
     std::vector<TrafficTrack> tracks; std::vector<GlobalPoint2D> tpts; std::vector<TrafficActor> actors; std::vector<ObPoint> obs((size_t)n * stride, ObPoint{ -500, -500, 0, 0.5f });
+    const int per_road = P + JP;
+    auto arc_of = [&](int lane, int road, int id) {      // arc length of lane point `id` of `road` along the closed track of `lane`
+        const GlobalPoint2D* T = tpts.data() + tracks[(size_t)lane - 1].point_off;
+        double here = 0;
+        for (int i = 0, at = per_road * (road - 1) + id; i < at; i++) here += std::sqrt((T[i + 1].x - T[i].x) * (T[i + 1].x - T[i].x) + (T[i + 1].y - T[i].y) * (T[i + 1].y - T[i].y));
+        return here;
+    };
+    const double ahead = react ? -15.0 : 20.0;           // where a vehicle starts along its track, seen from its ego
     if (traffic) {
-        const int per_road = P + JP;
         for (int l = 0; l < n_lanes; l++) {
             tracks.push_back({ (int32_t)tpts.size(), 4 * per_road, 1, 0 });
             for (int r = 0; r < 4; r++) {
@@ -112,10 +123,8 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         }
         for (int s = 0; s < n; s++) {
             SceneIn& e = in[(size_t)s];
-            const int lane = e.loc.lane_num, at = per_road * (e.loc.road_num - 1) + e.loc.id[lane - 1];
-            const GlobalPoint2D* T = tpts.data() + tracks[(size_t)lane - 1].point_off;
-            double here = 0;                              // arc length of the ego's lane point along its track
-            for (int i = 0; i < at; i++) here += std::sqrt((T[i + 1].x - T[i].x) * (T[i + 1].x - T[i].x) + (T[i + 1].y - T[i].y) * (T[i + 1].y - T[i].y));
+            const int lane = e.loc.lane_num;
+            const double here = arc_of(lane, e.loc.road_num, e.loc.id[lane - 1]);      // arc length of the ego's lane point along its track
             e.obs_off = s * stride; e.obs_n = 1;
             obs[(size_t)s * stride] = ObPoint{ 0, 0, 0, 0.9f };    // (placed by pp_set_traffic / pp_set_world_traffic)
             if (shared) {                                 // one vehicle per world: behind its rear ego (member 0), or ahead of its front ego (member W - 1)
@@ -159,6 +168,14 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         }
         CHECK(pp_set_episode_spawn(h, &sp, M > 1 ? in_k.data() : nullptr, M > 1 ? st_k.data() : nullptr));
     }
+    if (reset) {                                      // last of all: set 0 is captured here; set k puts the vehicle at its offset from start record k (5 k points back)
+        std::vector<TrafficStart> sets;
+        for (int k = 1; k < M; k++) for (int s = 0; s < n; s++) {
+            const SceneIn& e = in[(size_t)s]; const int lane = e.loc.lane_num, id = e.loc.id[0] > 5 * k ? e.loc.id[0] - 5 * k : 0;
+            sets.push_back(TrafficStart{ arc_of(lane, e.loc.road_num, id) + ahead, actors[(size_t)s].speed > 0 ? actors[(size_t)s].speed : 0.0 });
+        }
+        CHECK(pp_set_episode_traffic(h, M, M > 1 ? sets.data() : nullptr));
+    }
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
@@ -190,6 +207,17 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
                     M, contact ? "ends an episode" : "off", nc, nb, nr);
         for (int k = 0; k < M; k++) std::printf(" %lld", used[k]);
         std::printf("\n");
+    }
+    if (reset) {
+        std::vector<int32_t> nr(n); std::vector<EpisodeStats> es(n);
+        CHECK(pp_get_episode_traffic_resets(h, nr.data(), n));
+        CHECK(pp_get_episode_stats(h, es.data(), n));
+        long long resets = 0; int shortest = -1;
+        for (int s = 0; s < n; s++) {
+            resets += nr[(size_t)s];
+            if (es[(size_t)s].min_age >= 0 && (shortest < 0 || es[(size_t)s].min_age < shortest)) shortest = es[(size_t)s].min_age;
+        }
+        std::printf("reset-traffic: %d set(s) of start states per vehicle, %lld vehicle resets; the shortest episode of the run took %d advances\n", M, resets, shortest);
     }
     if (traffic) {
         const int nv = (int)actors.size();
@@ -235,7 +263,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false; int starts = 0;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -245,8 +273,9 @@ int main(int argc, char** argv)
         else if (std::strcmp(argv[a], "--shared") == 0) shared = true;
         else if (std::strcmp(argv[a], "--episodes") == 0) episodes = true;
         else if (std::strcmp(argv[a], "--contact") == 0) contact = true;
+        else if (std::strcmp(argv[a], "--reset-traffic") == 0) reset = true;
         else if (std::strcmp(argv[a], "--starts") == 0 && a + 1 < argc) starts = std::atoi(argv[++a]);
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--reset-traffic]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
@@ -256,7 +285,9 @@ int main(int argc, char** argv)
     if (starts < 0 || starts > DMPP_EPISODE_MAX_STARTS) { std::fprintf(stderr, "--starts takes 1 .. %d\n", DMPP_EPISODE_MAX_STARTS); return 2; }
     if (contact && (react || shared)) { std::fprintf(stderr, "--contact brings its own oncoming vehicle: not with --react / --shared\n"); return 2; }
     if (starts && shared) { std::fprintf(stderr, "--starts places its records behind each ego on its lane: not with the platoons of --shared\n"); return 2; }
-    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact);
+    if (reset && !(route && episodes && (traffic || contact))) { std::fprintf(stderr, "--reset-traffic puts a restarted ego's vehicle back: use it with --route --episodes --traffic (or --contact)\n"); return 2; }
+    if (reset && shared) { std::fprintf(stderr, "--reset-traffic resets per-scene traffic: a vehicle of --shared belongs to a whole world\n"); return 2; }
+    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

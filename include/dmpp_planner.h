@@ -401,6 +401,35 @@ void pp_default_episode_spawn(EpisodeSpawn* sp);     /* seed 1, clearance 2 m, n
 int  pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* starts_in, const SceneState* starts_state);
 int  pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n_scenes);
 
+/* ---- episode traffic reset: a restarted scene puts its traffic back on a start state ------------------------------
+ * Without it a restart restores SceneIn and SceneState and leaves the scene's actors (pp_set_traffic) wherever the last episode
+ * drove them: later episodes do not repeat the first.  pp_set_episode_traffic gives every actor n_sets START STATES and switches the
+ * reset on: from then on every pp_advance_async runs one more kernel on the upload stream (k_reset_traffic, one thread per actor)
+ * behind its traffic kernel and in front of k_couple_fleet.  For every scene that restarted in this advance (EpisodeStats.age == 0
+ * behind the episode step) it discards the step the traffic kernel has just made for the scene's actors and writes
+ *     s' = wrap(s*),  v' = v* (an actor with speed > 0; otherwise v' = speed),
+ * (s*, v*) = set k of the actor, k = EpisodeSpawnStats.cur_start of the scene with n_sets > 1 and 0 with n_sets == 1: s' into the
+ * current arc lengths, v' - following on - into the current speeds, the ObPoint at s' (zero ObMotion with a motion pool) into the
+ * actor's pinned pool entry, and counts the reset.  The restarted ego is staged AT its start record and its traffic AT its start
+ * states; actors of scenes that go on keep the bytes the traffic kernel wrote.  Every step is specified (§4m): a numpy restatement
+ * gives the same bytes.  The clearance check of §4l still reads the pool the advance READ: the actors where they stood before.
+ * SET 0 IS A CAPTURE made by the call, on the device: the current s of every actor and - following on - its current v, else its
+ * speed.  Sets 1 .. n_sets - 1 come from `starts`, set k of actor a at index (k - 1) * n_actors + a; `starts` may be NULL with
+ * n_sets == 1.  n_sets is 1 or EpisodeSpawn.n_starts of the spawn model in force (without one: 1); with n_sets == 1 and n_starts > 1
+ * every start record uses set 0.  n_sets == 0: the reset off.  A second call builds a new table and restarts the counters.
+ * CALL IT LAST: every successful pp_set_traffic / pp_set_world_traffic / pp_set_traffic_follow / pp_set_episodes /
+ * pp_set_episode_spawn (NULL or n = 0 included), and pp_set_scenes / pp_set_egos / pp_set_n_scenes through them, switches the reset
+ * off - each invalidates what the table was captured from.
+ * Refused with nothing changed - PP_ERR_STATE: no per-scene traffic on (world traffic, §4j, has no owning scene: out of scope),
+ * episodes off, an update staged for the next tick.  PP_ERR_ARG: n_sets < 0 or neither 1 nor n_starts, NULL starts with n_sets > 1,
+ * an s that is not finite, a v that is not finite or is < 0.  One host wait, behind every tick and advance enqueued so far.
+ * A handle that never makes the call allocates and launches none of this.
+ * pp_get_episode_traffic_resets: how often actors 0 .. n - 1 were reset since the last successful set call; readable after the
+ * reset went off.  Waits as pp_get_traffic_state does.  PP_ERR_STATE on a handle that never made the set call, PP_ERR_ARG for n
+ * outside 0 .. n_actors. */
+int  pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts);
+int  pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that
@@ -466,7 +495,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
  * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
- * 31 EpisodeSpawn, 32 EpisodeSpawnStats */
+ * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

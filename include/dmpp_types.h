@@ -392,6 +392,14 @@ typedef struct EpisodeSpawnStats {
     int32_t n_used[DMPP_EPISODE_MAX_STARTS];   /* restarts onto record k (the first episode is not counted) */
 } EpisodeSpawnStats;                                                        /* 80 B */
 
+/* ---- episode traffic reset (build-defined), on top of pp_set_traffic and pp_set_episodes ----------------
+ * pp_set_episode_traffic gives every actor of the per-scene traffic one START STATE per start record of its scene (set 0 is
+ * captured by the call, like start record 0); when an ego restarts, the actors of its scene go back to the set of the start
+ * record the restart took: start record k plus traffic set k is scenario k. */
+typedef struct TrafficStart {
+    double s, v;                /* arc length (m, wrapped / clamped onto the actor's track); speed (m/s, finite, >= 0) */
+} TrafficStart;                                                             /* 16 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

@@ -24,7 +24,12 @@ EPISODES=1 with SPAWN=M and / or CONTACT=1: both legs have episodes on, on the r
 (default 1), the first a vehicle that drives the ego's lane towards it at 3 m/s from 20 m ahead (pp_set_traffic), the others far away -
 and the second leg has the spawn model on as well (pp_set_episode_spawn, DESIGN.md §4l: k_respawn_spawn in the place of
 k_respawn_egos) with M start records per scene - record k of scene s is the start of scene (s + k) mod n - and contact ending an
-episode if CONTACT=1; the default clearance and check."""
+episode if CONTACT=1; the default clearance and check.
+EPISODES=1 RESET=1 (with SPAWN=M and / or CONTACT=1): both legs have that spawn model on, and the second leg the episode traffic reset as
+well (pp_set_episode_traffic, DESIGN.md §4m: k_reset_traffic behind k_move_traffic) - with M > 1 one set of start states per start record,
+the vehicle 20 m ahead of that record along its own track.  The workloads differ: without the reset the egos spend advances restarting
+into the vehicle that drove on over their start pose (the egos with an episode of age 1 are printed); k_reset_traffic's own cost is
+what a kernel trace of the ONE_ROLLOUT leg gives."""
 import os
 import statistics
 import sys
@@ -172,9 +177,10 @@ def episodes_run(on):
 
 SPAWN = int(os.environ.get("SPAWN", "0"))
 CONTACT = os.environ.get("CONTACT", "0") == "1"
+RESET = os.environ.get("RESET", "0") == "1"
 
 
-def spawn_run(on):
+def spawn_run(on, reset=False):
     import route_scenes as rs
     import traffic_model as tm
     import traffic_scenes as ts
@@ -207,6 +213,15 @@ def spawn_run(on):
         sp["n_starts"], sp["contact"] = M, int(CONTACT)
         roll = lambda a: np.concatenate([np.roll(a, -k, axis=0) for k in range(1, M)]) if M > 1 else None
         pl.set_episode_spawn(sp, roll(sc["scene_in"]), roll(sc["state"]))
+    if reset:                             # last: set 0 is captured here; set k puts the vehicle 20 m ahead of start record k along its OWN track
+        sets = None
+        if on and M > 1:
+            sets = np.zeros((M - 1, n), dm.TrafficStart)
+            for k in range(1, M):
+                for s in range(n):
+                    loc = sc["scene_in"]["loc"][(s + k) % n]
+                    sets["s"][k - 1, s] = cums[rows[s][4]][ts.SEG * (int(loc["road_num"]) - 1) + int(loc["id"][int(loc["lane_num"]) - 1])] + 20.0
+        pl.set_episode_traffic(M if on else 1, sets)
     pl.rollout(warm, model)
     pl.sync()
     t0 = time.perf_counter()
@@ -215,6 +230,8 @@ def spawn_run(on):
     dt = time.perf_counter() - t0
     ended = int(pl.episode_stats()["n_episodes"].sum())
     ss = pl.episode_spawn_stats() if on else None
+    spawn_run.resets = int(pl.episode_traffic_resets().sum()) if reset else 0
+    spawn_run.age1 = int((pl.episode_stats()["min_age"] == 1).sum())
     pl.close()
     return n * steps / dt, ended, (0, 0, 0) if ss is None else (int(ss["n_contact"].sum()), int(ss["n_blocked"].sum()), int(ss["n_rejected"].sum()))
 
@@ -319,6 +336,22 @@ if TRAFFIC > 0:
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with traffic alone
         traffic_run(True)
+    sys.exit(0)
+if os.environ.get("EPISODES", "0") == "1" and RESET:
+    off, on = [], []
+    for r in range(runs):
+        a, ea, _ = spawn_run(True)
+        a1 = spawn_run.age1
+        b, eb, (nc, _, _) = spawn_run(True, reset=True)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos with traffic, spawn model on (M %d, contact %d)  reset off %.3f M ticks/s (%d episodes ended, %d egos with an episode of age 1)   "
+              "reset on %.3f M ticks/s (%d episodes ended, %d on contact, %d egos with an episode of age 1, %d vehicle resets)" %
+              (r, n, max(SPAWN, 1), int(CONTACT), a / 1e6, ea, a1, b / 1e6, eb, nc, spawn_run.age1, spawn_run.resets), flush=True)
+    print("median  %d ring egos  reset off %.3f M ticks/s (spread %.3f)   reset on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with the reset alone
+        spawn_run(True, reset=True)
     sys.exit(0)
 if os.environ.get("EPISODES", "0") == "1" and (SPAWN > 0 or CONTACT):
     off, on = [], []
