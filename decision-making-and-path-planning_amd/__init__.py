@@ -22,7 +22,7 @@ G_FOUND, G_NO_PATH, G_LIMIT, G_OVERFLOW, G_GOAL_BLOCKED, G_PATH_TRUNC, G_INTERNA
 G_STATUS_COUNT = 8
 K_NAMES = ["k_effective_obstacles", "k_decision", "k_planning", "k_search", "k_score"]
 (BUF_SCENE_IN, BUF_LANE_POOL, BUF_REF_POOL, BUF_OBS_POOL, BUF_MOT_POOL, BUF_STATE, BUF_PLAN_OUT, BUF_GRID_OUT,
- BUF_GRID, BUF_PATH, BUF_ORDER, BUF_LANE_ATTR) = range(12)
+ BUF_GRID, BUF_PATH, BUF_ORDER, BUF_LANE_ATTR, BUF_OBS_NOW) = range(13)
 
 
 def _dt(fields):

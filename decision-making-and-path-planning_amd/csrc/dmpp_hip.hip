@@ -291,6 +291,7 @@ struct pp_planner {
     int parity = 0;              // work buffers of the last group
     bool last_piped = false;     // the last tick ran as three chains on several streams (else it ended on the handle's stream)
     int obs_set = 0;             // obstacle snapshot of the last tick (d_obs_now[obs_set])
+    bool front_snapshot = true;  // k_decision writes the snapshot itself where both share a stream (env DMPP_FRONT_SNAPSHOT=0: never)
     int n_cus = 256;
     int pipeline_min = 256;      // batches at least this large run the three chains on three streams (env DMPP_PIPELINE_MIN)
     bool r_on_main = false;      // the last tick ran Decision + Planning on the handle's stream (grid stage off)
@@ -694,6 +695,7 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     h->cfg = *cfg; h->caps = *caps; h->device = device;
     if (const char* e = std::getenv("DMPP_PIPELINE_MIN")) h->pipeline_min = std::atoi(e);      // tuning knob: 0 = always, large = never
     if (const char* e = std::getenv("DMPP_TICK_GROUP")) h->tick_group = std::atoi(e);          // A/B knob: ticks per search launch (1: one, as before groups)
+    if (const char* e = std::getenv("DMPP_FRONT_SNAPSHOT")) h->front_snapshot = std::atoi(e) != 0;   // A/B knob: 0 = the snapshot stays a launch of its own (k_effective_obstacles) on every path
     if (cfg->grid_stage) {
         // tick slots the work buffers hold: kGroupMax for a handle that runs piped ticks, as long as a set stays within kGroupBytes
         const size_t cells = (size_t)cfg->grid_w * cfg->grid_h;
@@ -1186,18 +1188,32 @@ int pp_plan_tick(pp_handle h)
     if (h->score.ego.done()) h->score.ego.forget();
     else if (!behind_upload) PP_TRY(h->score.ego.wait(sf));
     ObPoint* obs_now = h->d_obs_now[po];
-    {
+    // Snapshot and Decision on one stream (piped ticks, ticks without the grid stage): the snapshot is the head of k_decision<true>,
+    // one launch less per tick.  Every reader of the set waits for something behind that kernel: the searches for `raster`,
+    // recorded behind it; Planning, k_score_ego (ev_front) and join_all for stream order on sr.  (`raster` behind k_planning
+    // instead, beside `join`, was measured: the gap an event costs between two kernels moves with it and doubles there, and the
+    // 20-step leg loses 2 % to the later start of its searches - profiles/r25_front_two_launch.txt.)
+    // Streamed handles keep the separate launch: their groups are single ticks, every search waits for its own tick's `raster`, and
+    // starting each one k_decision later cost the streamed leg 1.3 %, more than its spread (same file).
+    const bool snap_fused = h->front_snapshot && c.decision_stage && sf == sr && !h->streaming;
+    const ObMotion* mot = h->have_motion ? h->d_mot : nullptr;
+    if (!snap_fused) {
         Timed t(h, PP_K_OBSTACLES, sf);
-        hipLaunchKernelGGL(dmpp::k_effective_obstacles, dim3(n), dim3(dmpp::kBlock), 0, sf, c, n, h->d_in, h->d_state,
-                           h->d_obs, h->have_motion ? h->d_mot : nullptr, obs_now);
+        hipLaunchKernelGGL(dmpp::k_effective_obstacles, dim3(n), dim3(dmpp::kBlock), 0, sf, c, n, h->d_in, h->d_state, h->d_obs, mot, obs_now);
     }
     if (sr != sf) { PP_TRY(h->fork.record(sf)); PP_TRY(h->fork.wait(sr)); }   // small batches: Decision + Planning beside the grid engine
-    if (c.grid_stage && sf != T.search) PP_TRY(h->raster.record(sf));        // the search rasterises for itself: it only needs the obstacle snapshot
+    const bool search_waits = c.grid_stage && sf != T.search;                // the search rasterises for itself: it only needs the obstacle snapshot
+    if (search_waits && !snap_fused) PP_TRY(h->raster.record(sf));
     if (c.decision_stage) {
         Timed t(h, PP_K_DECISION, sr);
-        hipLaunchKernelGGL(dmpp::k_decision, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, h->d_in, h->d_lane,
-                           h->d_attr, h->d_ref, obs_now, h->d_state, h->d_plan, h->d_dec_ref);
+        if (snap_fused)
+            hipLaunchKernelGGL(dmpp::k_decision<true>, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, h->d_in, h->d_lane,
+                               h->d_attr, h->d_ref, h->d_obs, mot, obs_now, h->d_state, h->d_plan, h->d_dec_ref);
+        else
+            hipLaunchKernelGGL(dmpp::k_decision<false>, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, h->d_in, h->d_lane,
+                               h->d_attr, h->d_ref, h->d_obs, mot, obs_now, h->d_state, h->d_plan, h->d_dec_ref);
     }
+    if (search_waits && snap_fused) PP_TRY(h->raster.record(sf));
     {
         Timed t(h, PP_K_PLANNING, sr);
         hipLaunchKernelGGL(dmpp::k_planning, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::PlanShared), sr, c, n, h->d_in, h->d_lane,
@@ -2428,6 +2444,7 @@ void* pp_device_ptr(pp_handle h, int which, size_t* bytes)
     case PP_BUF_GRID: p = nullptr; b = 0; break;      // no occupancy grid is kept after a tick (the search builds it in LDS): use pp_get_grid
     case PP_BUF_PATH: p = h->d_path[h->path_set]; b = ns * (size_t)h->max_path0 * 4; break;
     case PP_BUF_LANE_ATTR: p = h->d_attr; b = (size_t)h->caps.max_lane_pts_total; break;
+    case PP_BUF_OBS_NOW: p = h->d_obs_now[h->obs_set]; b = (size_t)h->caps.max_obs_total * sizeof(ObPoint); break;   // the last tick's snapshot
     case PP_BUF_ORDER: p = h->d_order[h->parity] ? h->d_order[h->parity] + (size_t)h->item_off * h->caps.order_cap : nullptr; b = ns * (size_t)h->caps.order_cap * 4; break;
     default: break;
     }

@@ -31,6 +31,19 @@ constexpr int kBlock = 256;
 constexpr int kMaxObsLds = 512;   // obstacle records staged in LDS; longer lists are read from HBM
 
 // ---------------------------------------------------------------------------------------
+// One record of the tick's snapshot (G4 constant-velocity model): pool entry i moved by t = dyn_dt * tick.  The one copy of the
+// step: k_effective_obstacles and the snapshot at the head of k_decision<true> both store what this returns.
+__device__ inline ObPoint effective_obstacle(const PlannerConfig& c, const ObPoint* __restrict__ obs, const ObMotion* __restrict__ mot, int i, double t)
+{
+    ObPoint o = obs[i];
+    if (c.dynamic_obstacles && mot) {
+        ObMotion v = mot[i];
+        o.x = o.x + v.vx * t;
+        o.y = o.y + v.vy * t;
+    }
+    return o;
+}
+
 __global__ void __launch_bounds__(kBlock)
 k_effective_obstacles(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const SceneState* __restrict__ st,
                       const ObPoint* __restrict__ obs, const ObMotion* __restrict__ mot, ObPoint* __restrict__ now)
@@ -40,15 +53,7 @@ k_effective_obstacles(PlannerConfig c, int n_scenes, const SceneIn* __restrict__
     __builtin_amdgcn_s_setprio(3);             // the front chain is short and every search waits for it: issue ahead of the searching waves
     const int off = in[s].obs_off, m = in[s].obs_n;
     const double t = c.dyn_dt * (double)st[s].tick;
-    for (int j = threadIdx.x; j < m; j += kBlock) {
-        ObPoint o = obs[off + j];
-        if (c.dynamic_obstacles && mot) {
-            ObMotion v = mot[off + j];
-            o.x = o.x + v.vx * t;
-            o.y = o.y + v.vy * t;
-        }
-        now[off + j] = o;
-    }
+    for (int j = threadIdx.x; j < m; j += kBlock) now[off + j] = effective_obstacle(c, obs, mot, off + j, t);
 }
 
 // ---- scalar stages of the planning tick, shared by k_planning and the stand-alone stage operator ----
@@ -94,33 +99,36 @@ __device__ inline double d_CalculateRadius(const GlobalPoint2D* last, int near_i
 // Block-wide arc-length walk shared by every branch of SearchAimPoint (Planning.cpp:410-432,
 // 448-469,478-499,507-538): accumulate |P[i+1]-P[i]| for i = i0 .. iend-1 in index order and
 // stop at the first i with sum - 4 > faraim.  Segment lengths are computed 256 at a time in
-// parallel; thread 0 adds them in order, eight per block of reads (serial_walk), so the rounding equals the scalar loop.
-// base/stride: point i is (base[i*stride], base[i*stride+1]).  Returns the index or -1.
-__device__ inline int block_aim_walk(const double* base, int stride, int i0, int iend, double faraim,
-                                     double* seg, int* sh_found, double* sh_sum)
+// parallel (aim_walk_lengths); ONE lane adds them in order, eight per block of reads (aim_walk_add: serial_walk), so the
+// rounding equals the scalar loop.  base/stride: point i is (base[i*stride], base[i*stride+1]).
+// *sh_found: the index or -1, *sh_sum: the running sum - set to -1 and 0 by the caller, behind a barrier, before the first block.
+__device__ inline void aim_walk_lengths(const double* base, int stride, int c0, int iend, double* seg)
 {
-    const int tid = threadIdx.x;
-    if (i0 < 0) i0 = 0;
-    if (tid == 0) { *sh_found = -1; *sh_sum = 0; }
-    __syncthreads();
-    for (int c0 = i0; c0 < iend; c0 += kBlock) {
-        const int i = c0 + tid;
-        if (i < iend) {
-            double dx = base[(size_t)(i + 1) * stride] - base[(size_t)i * stride];
-            double dy = base[(size_t)(i + 1) * stride + 1] - base[(size_t)i * stride + 1];
-            seg[tid] = sqrt(dx * dx + dy * dy);
-        }
+    const int i = c0 + threadIdx.x;
+    if (i < iend) {
+        double dx = base[(size_t)(i + 1) * stride] - base[(size_t)i * stride];
+        double dy = base[(size_t)(i + 1) * stride + 1] - base[(size_t)i * stride + 1];
+        seg[threadIdx.x] = sqrt(dx * dx + dy * dy);
+    }
+}
+__device__ inline void aim_walk_add(const double* seg, int c0, int iend, double faraim, int* sh_found, double* sh_sum)
+{
+    double sum = *sh_sum;
+    const int k = serial_walk(seg, iend - c0 < kBlock ? iend - c0 : kBlock, faraim, sum);
+    if (k >= 0) *sh_found = c0 + k;
+    *sh_sum = sum;
+}
+// the blocks from segment c0 on, by the whole workgroup (k_planning runs the first block of a later tick itself, beside localise)
+__device__ inline void block_aim_walk(const double* base, int stride, int c0, int iend, double faraim,
+                                      double* seg, int* sh_found, double* sh_sum)
+{
+    for (; c0 < iend; c0 += kBlock) {
+        aim_walk_lengths(base, stride, c0, iend, seg);
         __syncthreads();
-        if (tid == 0) {
-            double sum = *sh_sum;
-            const int k = serial_walk(seg, iend - c0 < kBlock ? iend - c0 : kBlock, faraim, sum);
-            if (k >= 0) *sh_found = c0 + k;
-            *sh_sum = sum;
-        }
+        if (threadIdx.x == 0) aim_walk_add(seg, c0, iend, faraim, sh_found, sh_sum);
         __syncthreads();
         if (*sh_found >= 0) break;
     }
-    return *sh_found;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -421,9 +429,18 @@ __device__ inline void lane_change_tree(const SceneIn& si, int LaneNum_Cur, int 
     st.leftlight_time = left_t; st.rightlight_time = right_t; st.frontobs_time = frontobs;
 }
 
+// SNAP: the workgroup first writes its scene's slice of the tick's snapshot (what k_effective_obstacles would have stored, from
+// obs_pool / mot_pool), then reads it back like the plain form reads the launch before it.  In that form obs_now is read and
+// written, so it is neither const nor __restrict__ (its loads must not take the scalar cache, which no vector store reaches).
+// Slices of two scenes may overlap: every workgroup stores the same bytes to a shared slot, and reads only slots it has itself
+// stored and waited for, so whichever store lands last changes nothing it sees.
+template <bool SNAP> struct SnapshotPtr { typedef const ObPoint* __restrict__ type; };
+template <> struct SnapshotPtr<true> { typedef ObPoint* type; };
+template <bool SNAP>
 __global__ void __launch_bounds__(kBlock)
 k_decision(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const GlobalPoint3D* __restrict__ lane_pool,
-           const uint8_t* __restrict__ attr_pool, const GlobalPoint2D* __restrict__ ref_pool, const ObPoint* __restrict__ obs_now,
+           const uint8_t* __restrict__ attr_pool, const GlobalPoint2D* __restrict__ ref_pool,
+           const ObPoint* __restrict__ obs_pool, const ObMotion* __restrict__ mot_pool, typename SnapshotPtr<SNAP>::type obs_now,
            SceneState* __restrict__ state, PlanOut* __restrict__ plan, GlobalPoint2D* __restrict__ dec_ref)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -441,6 +458,12 @@ k_decision(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
     PlanOut& po = plan[scene];
     const LocationOut& loc = si.loc;
     const int m = si.obs_n;
+    if constexpr (SNAP) {                            // the tick's snapshot of this scene, then visible to the whole block
+        const double t = c.dyn_dt * (double)st.tick;
+        for (int j = tid; j < m; j += kBlock) obs_now[si.obs_off + j] = effective_obstacle(c, obs_pool, mot_pool, si.obs_off + j, t);
+        __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): this thread's stores have left before the barrier
+        __syncthreads();
+    }
     const ObPoint* obs = obs_now + si.obs_off;       // read where they are: every lane needs its obstacle once per query
     FRONT_MARK(0)
     const double hv = 0.5 * c.Vehicle_Width;
@@ -499,6 +522,16 @@ k_decision(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
             const int team = wave >> 1;
             for (int rd = 0; rd < 3; rd++) {
                 const int t = 2 * rd + team;
+                if (N[2 * rd] == 0 && N[2 * rd + 1] == 0) {       // (block-uniform) a scene that may not change lanes has no side corridors:
+                    if ((tid & 127) == 0) {                       // what the search returns for an empty path, without its barriers
+                        SoResult z; z.flag = 0; z.path_id = 0; z.ob_index = -1; z.dis_lat = c.NO_OBSTACLE_DIS; z.dis_lng = c.NO_OBSTACLE_DIS;
+#ifdef DMPP_DEBUG_SEARCH
+                        z.adds = 0;
+#endif
+                        sh.around[t] = z; sh.n[t] = 0;
+                    }
+                    continue;
+                }
                 const SoResult r = team_search_obstacle<2>(c, P[t], N[t], team == 0 ? sh.u.road.s0 : sh.u.road.s1, obs, m, LO[t], HI[t], true, sh.part_d2, sh.part_bi);
                 if ((tid & 127) == 0) { sh.around[t] = r; sh.n[t] = N[t]; }
             }
@@ -774,10 +807,10 @@ k_decision(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
 struct PlanShared {
     GlobalPoint2D last[DMPP_PATH_POINTS];
     GlobalPoint2D road[DMPP_PATH_POINTS];
-    double dist[kBlock];           // also the 256-wide segment buffer of block_aim_walk
+    double dist[kBlock];
     double seg[DMPP_PATH_POINTS];
     double s[DMPP_PATH_POINTS + 8];
-    double part_d2[kBlock]; int part_bi[kBlock + 2];  // team_search_obstacle (+2: its teams' second-pass flags)
+    double part_d2[kBlock]; int part_bi[kBlock + 2];  // team_search_obstacle (+2: its teams' second-pass flags); part_d2 before it: the 256 lengths of block_aim_walk
     AimPoint aim_far;
     SoResult so;
     double sh_sum;
@@ -833,114 +866,130 @@ k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
     default: break;
     }
 
-    // ---- SearchAimPoint, Planning.cpp:303-583 ----
-    if (tid == 0) sh.aim_far = st.aimpoint_far;
-    AimPoint aim_near_new = st.aimpoint_near;
+    // ---- SearchAimPoint, Planning.cpp:303-583: which walk this tick does (block-uniform) ----
+    // kind 1: the current lane (:410-434), 2: the left lane (:448-469), 3: the right lane (:478-499), 4: the refpath (:507-538);
+    // point i of the walk is (base[i * stride], base[i * stride + 1]), its segments are i0 .. iend - 1.
+    const int LaneNum_Cur = loc.lane_num, LaneSum = si.lanes.lane_sum;
+    const int curpoint_id = loc.id[clampi(LaneNum_Cur - 1, 0, DMPP_LANESUM - 1)];
+    const int curpoint_sum = si.lanes.cur_n;
+    int leftpoint_id = 0, leftpoint_sum = 0, rightpoint_id = 0, rightpoint_sum = 0;
+    if (LaneNum_Cur > 1) { leftpoint_id = loc.id[clampi(LaneNum_Cur - 2, 0, DMPP_LANESUM - 1)]; leftpoint_sum = si.lanes.left_n; }
+    if (LaneNum_Cur < LaneSum) { rightpoint_id = loc.id[clampi(LaneNum_Cur, 0, DMPP_LANESUM - 1)]; rightpoint_sum = si.lanes.right_n; }
+    const bool plan_div = !(fabs(faraim - nearaim) < 1);
+    const GlobalPoint3D* cur = lane_pool + si.lanes.cur_off;
+    const GlobalPoint3D* left = lane_pool + si.lanes.left_off;
+    const GlobalPoint3D* right = lane_pool + si.lanes.right_off;
+    int kind = 0, w_i0 = 0, w_iend = 0, w_stride = 3;
+    const double* w_base = nullptr;
     bool near_follows_far = false;
-    {
-        const int LaneNum_Cur = loc.lane_num, LaneSum = si.lanes.lane_sum;
-        const int curpoint_id = loc.id[clampi(LaneNum_Cur - 1, 0, DMPP_LANESUM - 1)];
-        const int curpoint_sum = si.lanes.cur_n;
-        int leftpoint_id = 0, leftpoint_sum = 0, rightpoint_id = 0, rightpoint_sum = 0;
-        if (LaneNum_Cur > 1) { leftpoint_id = loc.id[clampi(LaneNum_Cur - 2, 0, DMPP_LANESUM - 1)]; leftpoint_sum = si.lanes.left_n; }
-        if (LaneNum_Cur < LaneSum) { rightpoint_id = loc.id[clampi(LaneNum_Cur, 0, DMPP_LANESUM - 1)]; rightpoint_sum = si.lanes.right_n; }
-        const bool plan_div = !(fabs(faraim - nearaim) < 1);
-        const GlobalPoint3D* cur = lane_pool + si.lanes.cur_off;
-        const GlobalPoint3D* left = lane_pool + si.lanes.left_off;
-        const GlobalPoint3D* right = lane_pool + si.lanes.right_off;
-        __syncthreads();
-        if (pos == 0) {
-            if (dec.target_lanenum == loc.lane_num) {
-                if (dec.behavior == 1 && !plan_div) {
-                    int iend = curpoint_sum - 1;
-                    int f = block_aim_walk(&cur[0].x, 3, curpoint_id, iend, (double)faraim, sh.dist, &sh.sh_found, &sh.sh_sum);
-                    if (tid == 0) {
-                        if (f >= 0) { sh.aim_far.Aim_point = cur[f]; sh.aim_far.Aim_id = f; }
-                        else if (max(curpoint_id, 0) < iend) { sh.aim_far.Aim_point = cur[curpoint_sum - 1]; sh.aim_far.Aim_id = curpoint_sum - 1; }
-                    }
-                    near_follows_far = true;                               // Planning.cpp:434
-                }
-            } else if (dec.behavior == 2) {
-                if (!plan_div) {
-                    int iend = leftpoint_sum - 1;
-                    int f = block_aim_walk(&left[0].x, 3, leftpoint_id, iend, (double)faraim, sh.dist, &sh.sh_found, &sh.sh_sum);
-                    if (tid == 0) {
-                        if (f >= 0) { sh.aim_far.Aim_point = left[f]; sh.aim_far.Aim_id = f; }
-                        else if (max(leftpoint_id, 0) < iend) {             // quirk Planning.cpp:464-467
-                            int q = clampi(leftpoint_sum - 2, 0, curpoint_sum > 0 ? curpoint_sum - 1 : 0);
-                            sh.aim_far.Aim_point = cur[q]; sh.aim_far.Aim_id = leftpoint_sum - 1;
-                        }
-                    }
-                }
-            } else if (dec.behavior == 3) {
-                if (!plan_div) {
-                    int iend = min(leftpoint_sum - 1, rightpoint_sum - 1);   // quirk Planning.cpp:478 + fence
-                    int i0 = rightpoint_id;
-                    int f = (i0 >= 0) ? block_aim_walk(&right[0].x, 3, i0, iend, (double)faraim, sh.dist, &sh.sh_found, &sh.sh_sum) : -1;
-                    if (tid == 0) {
-                        if (f >= 0) { sh.aim_far.Aim_point = right[f]; sh.aim_far.Aim_id = f; }
-                        else if (i0 >= 0 && i0 < iend) { sh.aim_far.Aim_point = right[rightpoint_sum - 1]; sh.aim_far.Aim_id = rightpoint_sum - 1; }
-                    }
-                }
+    if (pos == 0) {
+        if (dec.target_lanenum == loc.lane_num) {
+            if (dec.behavior == 1 && !plan_div) {
+                kind = 1; w_base = &cur[0].x; w_i0 = curpoint_id; w_iend = curpoint_sum - 1;
+                near_follows_far = true;                                   // Planning.cpp:434
             }
-        } else if (pos == 1 || pos == 2) {
+        } else if (dec.behavior == 2) {
+            if (!plan_div) { kind = 2; w_base = &left[0].x; w_i0 = leftpoint_id; w_iend = leftpoint_sum - 1; }
+        } else if (dec.behavior == 3) {
+            if (!plan_div) { kind = 3; w_base = &right[0].x; w_i0 = rightpoint_id; w_iend = min(leftpoint_sum - 1, rightpoint_sum - 1); }   // quirk Planning.cpp:478 + fence
+        }
+    } else if (pos == 1 || pos == 2) {
+        if (dec.refpath_n >= 3) { kind = 4; w_base = &refpath[0].x; w_stride = 2; w_i0 = 0; w_iend = dec.refpath_n - 1; }
+        near_follows_far = true;                                           // Planning.cpp:539,577
+    }
+    const int w_first = max(w_i0, 0);                                      // the walks of kinds 1 and 2 start at 0 for a negative id; kind 3 does not walk then
+    const bool walks = kind != 0 && !(kind == 3 && w_i0 < 0) && w_first < w_iend;
+    const double limit = (double)faraim;
+    double* const w_seg = sh.part_d2;                                      // the walk's 256 lengths: idle until SearchObstacle
+    // What the branch makes of the walk's answer f (the index, or -1), with its fallback and quirk.  One thread.
+    auto finish_aim = [&](int f) {
+        if (kind == 1) {
+            if (f >= 0) { sh.aim_far.Aim_point = cur[f]; sh.aim_far.Aim_id = f; }
+            else if (max(curpoint_id, 0) < w_iend) { sh.aim_far.Aim_point = cur[curpoint_sum - 1]; sh.aim_far.Aim_id = curpoint_sum - 1; }
+        } else if (kind == 2) {
+            if (f >= 0) { sh.aim_far.Aim_point = left[f]; sh.aim_far.Aim_id = f; }
+            else if (max(leftpoint_id, 0) < w_iend) {                       // quirk Planning.cpp:464-467
+                int q = clampi(leftpoint_sum - 2, 0, curpoint_sum > 0 ? curpoint_sum - 1 : 0);
+                sh.aim_far.Aim_point = cur[q]; sh.aim_far.Aim_id = leftpoint_sum - 1;
+            }
+        } else if (kind == 3) {
+            if (f >= 0) { sh.aim_far.Aim_point = right[f]; sh.aim_far.Aim_id = f; }
+            else if (w_i0 >= 0 && w_i0 < w_iend) { sh.aim_far.Aim_point = right[rightpoint_sum - 1]; sh.aim_far.Aim_id = rightpoint_sum - 1; }
+        } else if (kind == 4) {
             const int n = dec.refpath_n;
-            if (n >= 3) {
-                int f = block_aim_walk(&refpath[0].x, 2, 0, n - 1, (double)faraim, sh.dist, &sh.sh_found, &sh.sh_sum);
-                if (tid == 0) {
-                    if (f >= 0) {
-                        sh.aim_far.Aim_point.x = refpath[f].x; sh.aim_far.Aim_point.y = refpath[f].y;
-                        // :517 is unsigned: n < 4 takes the first branch; f + 2 clamped to n - 1 (n = 3, f = 1 reads refpath[3])
-                        if (n < 4 || f < n - 4) sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[f], refpath[min(f + 2, n - 1)]);
-                        else sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[f - 2 < 0 ? 0 : f - 2], refpath[f]);
-                        sh.aim_far.Aim_id = f;
-                    } else {
-                        sh.aim_far.Aim_point.x = refpath[n - 1].x; sh.aim_far.Aim_point.y = refpath[n - 1].y;
-                        sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[n - 3], refpath[n - 1]);
-                        sh.aim_far.Aim_id = n - 1;
-                    }
-                }
+            if (f >= 0) {
+                sh.aim_far.Aim_point.x = refpath[f].x; sh.aim_far.Aim_point.y = refpath[f].y;
+                // :517 is unsigned: n < 4 takes the first branch; f + 2 clamped to n - 1 (n = 3, f = 1 reads refpath[3])
+                if (n < 4 || f < n - 4) sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[f], refpath[min(f + 2, n - 1)]);
+                else sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[f - 2 < 0 ? 0 : f - 2], refpath[f]);
+                sh.aim_far.Aim_id = f;
+            } else {
+                sh.aim_far.Aim_point.x = refpath[n - 1].x; sh.aim_far.Aim_point.y = refpath[n - 1].y;
+                sh.aim_far.Aim_point.dir = GetRoadAngle(c, refpath[n - 3], refpath[n - 1]);
+                sh.aim_far.Aim_id = n - 1;
             }
-            near_follows_far = true;                                       // Planning.cpp:539,577
         }
-    }
-    __syncthreads();
-    const AimPoint aim_far = sh.aim_far;
-    if (near_follows_far) aim_near_new = aim_far;
-
-    FRONT_MARK(0)
-    // ---- first tick: InitialPlanning, Planning.cpp:124-128,596-611 ----
-    const int count = st.count;
-    if (count == 0) {
-        Bezier bz = bezier_setup(c, ego, aim_far.Aim_point);
-        if (tid < DMPP_PATH_POINTS) sh.last[tid] = bezier_point(bz, tid, DMPP_PATH_POINTS);
-    } else {
-        if (tid < DMPP_PATH_POINTS) sh.last[tid] = st.last_Bpoints[tid];
-    }
-    __syncthreads();
-
-    FRONT_MARK(1)
-    // ---- GetVhclLocalState, Planning.cpp:623-676 ----
-    if (tid < DMPP_PATH_POINTS) {
-        double dx = ego.x - sh.last[tid].x, dy = ego.y - sh.last[tid].y;
-        sh.dist[tid] = sqrt(dx * dx + dy * dy);
-        if (tid < DMPP_PATH_POINTS - 1) {
-            double sx = sh.last[tid + 1].x - sh.last[tid].x, sy = sh.last[tid + 1].y - sh.last[tid].y;
-            sh.seg[tid] = sqrt(sx * sx + sy * sy);
+    };
+    // ---- GetVhclLocalState, Planning.cpp:623-676, in its parallel parts ----
+    auto local_lengths = [&]() {                                           // needs sh.last; a barrier follows
+        if (tid < DMPP_PATH_POINTS) {
+            double dx = ego.x - sh.last[tid].x, dy = ego.y - sh.last[tid].y;
+            sh.dist[tid] = sqrt(dx * dx + dy * dy);
+            if (tid < DMPP_PATH_POINTS - 1) {
+                double sx = sh.last[tid + 1].x - sh.last[tid].x, sy = sh.last[tid + 1].y - sh.last[tid].y;
+                sh.seg[tid] = sqrt(sx * sx + sy * sy);
+            }
         }
-    }
-    __syncthreads();
-    if (wave == 0) {
+    };
+    int mid = -1; double remain = 0;                                       // thread 0's: nearest point, remaining length
+    auto local_nearest = [&]() {                                           // wave 0
         // first minimum of the 200 distances below 9999 (Planning.cpp:640-650: strict <, so ties keep the lower index; a NaN is
         // never smaller): every lane over its four indices in order, then a (value, index) reduction over the wave
-        double mind = 9999; int mid = -1;
+        double mind = 9999;
         for (int k = 0; k < 4; k++) { const int i = lane + 64 * k; if (i < DMPP_PATH_POINTS && sh.dist[i] < mind) { mind = sh.dist[i]; mid = i; } }
         wave_first_min(mind, mid);
         if (mid < 0) mid = clampi(st.path_near_id, 0, DMPP_PATH_POINTS - 1);      // nothing within 9999 m: the member keeps its value
-        const int fid = mid + 8;
         // remaining length: seg[fid] + ... + seg[198] in index order (Planning.cpp:668-671), one lane, eight reads per block
-      if (lane == 0) {
-        const double remain = serial_sum(sh.seg, min(fid, DMPP_PATH_POINTS - 1), DMPP_PATH_POINTS - 1, 0.0);
+        if (lane == 0) remain = serial_sum(sh.seg, min(mid + 8, DMPP_PATH_POINTS - 1), DMPP_PATH_POINTS - 1, 0.0);
+    };
+
+    const int count = st.count;
+    if (tid == 0) { sh.aim_far = st.aimpoint_far; sh.sh_found = -1; sh.sh_sum = 0; }
+    if (count == 0) {
+        // first tick: InitialPlanning (Planning.cpp:124-128,596-611) needs the aim point, so the steps run one after the other
+        __syncthreads();
+        if (walks) block_aim_walk(w_base, w_stride, w_first, w_iend, limit, w_seg, &sh.sh_found, &sh.sh_sum);
+        if (tid == 0) finish_aim(sh.sh_found);
+        __syncthreads();
+        FRONT_MARK(0)
+        Bezier bz = bezier_setup(c, ego, sh.aim_far.Aim_point);
+        if (tid < DMPP_PATH_POINTS) sh.last[tid] = bezier_point(bz, tid, DMPP_PATH_POINTS);
+        __syncthreads();
+        local_lengths();
+        __syncthreads();
+        if (wave == 0) local_nearest();
+        FRONT_MARK(1)
+    } else {
+        // every later tick: the walk and the local state share no input (lane or refpath, dec, aimpoint_far | last_Bpoints, ego)
+        // and each is one lane adding in index order, so they run side by side on two waves - two SIMDs - and both sets of
+        // loads are issued here, together
+        if (tid < DMPP_PATH_POINTS) sh.last[tid] = st.last_Bpoints[tid];
+        if (walks) aim_walk_lengths(w_base, w_stride, w_first, w_iend, w_seg);
+        __syncthreads();
+        local_lengths();
+        __syncthreads();
+        FRONT_MARK(0)
+        if (wave == 0) local_nearest();
+        else if (tid == 64 && walks) aim_walk_add(w_seg, w_first, w_iend, limit, &sh.sh_found, &sh.sh_sum);
+        __syncthreads();
+        if (walks && sh.sh_found < 0)                                      // not within its first 256 segments: block by block
+            block_aim_walk(w_base, w_stride, w_first + kBlock, w_iend, limit, w_seg, &sh.sh_found, &sh.sh_sum);
+        if (tid == 0) finish_aim(sh.sh_found);
+        FRONT_MARK(1)
+    }
+    if (tid == 0) {
+        const AimPoint aim_far = sh.aim_far;
+        const int fid = mid + 8;
         const int index = (mid == 199) ? mid - 1 : mid;
         const GlobalPoint2D pt = sh.last[index], pt_next = sh.last[index + 1], vp = { ego.x, ego.y };
         const double lat = GetLatDis(c, vp, pt, pt_next);
@@ -954,15 +1003,16 @@ k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
         st.path_near_id = mid; st.path_front_near_id = fid;
         st.afresh_planning = afresh; st.afresh_cause = cause;
         st.faraim_dis = faraim; st.nearaim_dis = nearaim;
-        st.aimpoint_far = aim_far; st.aimpoint_near = aim_near_new;
+        st.aimpoint_far = aim_far;
+        if (near_follows_far) st.aimpoint_near = aim_far;                   // (else the member keeps its value)
         sh.afresh = afresh; sh.near_id = mid;
         int na = aim_far.Aim_id; if (na > 200) na = 200; if (na > dec.refpath_n) na = dec.refpath_n; if (na < 0) na = 0;
         sh.na = na;
         // CalculateRadius, Planning.cpp:1000-1019: runs on the OLD path (called at :199, path saved at :217)
         po.result.radius = d_CalculateRadius(sh.last, mid, fid);
-      }
     }
     __syncthreads();
+    const AimPoint aim_far = sh.aim_far;
 
     FRONT_MARK(2)
     // ---- PathPlanning, Planning.cpp:845-877 (or reuse of the last path, :144-145) ----

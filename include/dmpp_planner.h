@@ -47,9 +47,10 @@ typedef struct PlannerCaps {
 
 /* kernels of one tick, in launch order; index into pp_get_kernel_ms */
 enum { PP_K_OBSTACLES = 0, PP_K_DECISION, PP_K_PLANNING, PP_K_SEARCH, PP_K_SCORE, PP_K_COUNT };
-/* device buffers addressable through pp_device_ptr (for RCCL scatter/gather by the caller) */
+/* device buffers addressable through pp_device_ptr (for RCCL scatter/gather by the caller); PP_BUF_OBS_NOW: the last tick's
+ * obstacle snapshot (max_obs_total records, only the slots some scene's slice covers are written) */
 enum { PP_BUF_SCENE_IN = 0, PP_BUF_LANE_POOL, PP_BUF_REF_POOL, PP_BUF_OBS_POOL, PP_BUF_MOT_POOL, PP_BUF_STATE,
-       PP_BUF_PLAN_OUT, PP_BUF_GRID_OUT, PP_BUF_GRID, PP_BUF_PATH, PP_BUF_ORDER, PP_BUF_LANE_ATTR, PP_BUF_COUNT };
+       PP_BUF_PLAN_OUT, PP_BUF_GRID_OUT, PP_BUF_GRID, PP_BUF_PATH, PP_BUF_ORDER, PP_BUF_LANE_ATTR, PP_BUF_OBS_NOW, PP_BUF_COUNT };
 
 const char* pp_last_error(void);
 

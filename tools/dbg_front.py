@@ -25,8 +25,9 @@ pos = sc["scene_in"]["loc"]["pos"]
 attr = sc["scene_in"]["lanes"]["lanechg_attribute"]
 for name, sel in (("road, no lane change", (pos == 0) & (attr == 0)), ("road, lane change allowed", (pos == 0) & (attr != 0)), ("junction", pos != 0)):
     print(name, int(sel.sum()), "scenes")
-    print("  k_decision stamps (cycles): stage obs, LoadRefPath, AroundObstacle, sweep, rem-length, tree, end: median", np.median(D[sel], axis=0).astype(int).tolist())
-    print("  k_planning stamps (cycles): aim, initial, localise, path, SearchObstacle, end: median", np.median(P[sel], axis=0).astype(int).tolist())
+    print("  k_decision stamps (cycles): snapshot, LoadRefPath, AroundObstacle, sweep, rem-length, tree, end: median", np.median(D[sel], axis=0).astype(int).tolist())
+    # (third tick, count != 0: loads and lengths of both | aim walk beside nearest point + remain, joined | aim finished, local state stored)
+    print("  k_planning stamps (cycles): head, aim walk || localise, local state, path, SearchObstacle, end: median", np.median(P[sel], axis=0).astype(int).tolist())
     # (a build from before the deferred sum does not write these slots: it always adds n - 1 lengths per search)
     absA = np.abs(A)
     tot = absA[sel].sum(axis=1) if (pos[sel] == 0).all() else absA[sel][:, 0]

@@ -18,6 +18,9 @@ for x in ev:
     if x["n"].startswith("k_effective"):
         cur = {"eff": x}
         ticks.append(cur)
+    elif x["n"].startswith("k_decision<true>"):       # the snapshot is the head of this kernel: "eff" = its start, no time of its own
+        cur = {"eff": dict(x, e=x["s"]), "k_decision": x}
+        ticks.append(cur)
     elif cur is not None:
         for key in ("k_decision", "k_planning", "k_search", "k_score"):
             if x["n"].startswith(key) and key not in cur:
