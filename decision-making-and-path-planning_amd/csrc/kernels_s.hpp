@@ -360,166 +360,280 @@ __device__ __forceinline__ int block_excl_scan(int v, int tid, int* s_wave /* [S
     return base + incl - v;
 }
 
-// Walks the exact spans of every footprint of a scene: emit(colhalf, line, a, b) is called, by the lane that owns the line,
-// for every line a footprint touches, [a, b] being its first and last occupied position on that line (row-major half:
-// line = y, positions x; column-major half: line = x, positions y).  All kSearchBlock threads.
-// A wave owns the obstacles wv, wv + 4, ...; it computes 64 footprints at once (one per lane: the divisions are paid once
-// per obstacle, not per line) and then walks them, lanes 0..31 on a footprint's rows and lanes 32..63 on its columns.
-template <int SW, class Emit>
-__device__ __forceinline__ void for_each_span(const PlannerConfig& c, const SceneIn& si, const ObPoint* __restrict__ obs, int m, Emit&& emit)
+// the same for a pair of counts at once (two shuffles per step, but one set of barriers): v0 / v1 become the exclusive sums,
+// tot0 / tot1 the totals.  s_wave0 and s_wave1: [SW] each.
+template <int SW>
+__device__ __forceinline__ void block_excl_scan2(int& v0, int& v1, int& tot0, int& tot1, int tid, int* s_wave0, int* s_wave1)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int W = c.grid_w, H = c.grid_h;
-    const bool colhalf = lane >= 32;
-    const int l32 = lane & 31;
-    const double cell = c.cell, inv_cell = 1.0 / c.cell;
-    const GlobalPoint2D origin = si.grid_origin;
-    const double org_u = colhalf ? origin.y : origin.x, org_v = colhalf ? origin.x : origin.y;
-    // the scene's share of the error bound that certifies span ends (exact_span): coordinate rounding, with both axes' origins
-    const double cq_scene = 0x1p-47 * (2.0 * (fabs(origin.x) + fabs(origin.y)) + (double)max(W, H) * cell) + 0x1p-36 * cell;
-    auto bcast_d = [](double v, int src) {
-        const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-        return __hiloint2double(hi, lo);
-    };
-    for (int base = 0; base < m; base += SW * DMPP_WAVE) {
-        // this lane's obstacle of the chunk
-        Footprint f; f.ox = f.oy = f.R2 = 0; f.ix0 = f.iy0 = 0; f.ix1 = f.iy1 = -1;
-        int icx = 0, icy = 0;
-        const int j = base + wv + SW * lane;
-        if (j < m) {
-            f = footprint_of(c, origin, obs[j], W, H);
-            icx = (int)floor((f.ox - origin.x) / cell);
-            icy = (int)floor((f.oy - origin.y) / cell);
-        }
-        const unsigned long long anym = wave_ballot(j < m && f.ix1 >= f.ix0 && f.iy1 >= f.iy0);
-        const int left = m - base - wv;
-        const int cnt = left <= 0 ? 0 : min(DMPP_WAVE, (left + SW - 1) / SW);
-        for (int q = 0; q < cnt; q++) {
-            if (!((anym >> q) & 1ull)) continue;
-            const double fx = bcast_d(f.ox, q), fy = bcast_d(f.oy, q), R2 = bcast_d(f.R2, q);
-            const int ix0 = __builtin_amdgcn_readlane(f.ix0, q), ix1 = __builtin_amdgcn_readlane(f.ix1, q);
-            const int iy0 = __builtin_amdgcn_readlane(f.iy0, q), iy1 = __builtin_amdgcn_readlane(f.iy1, q);
-            const int jcx = __builtin_amdgcn_readlane(icx, q), jcy = __builtin_amdgcn_readlane(icy, q);
-            const double ou = colhalf ? fy : fx, ov = colhalf ? fx : fy;
-            const int ic = colhalf ? jcy : jcx, l0 = colhalf ? ix0 : iy0, l1 = colhalf ? ix1 : iy1, lo = colhalf ? iy0 : ix0, hi = colhalf ? iy1 : ix1;
-            const double cq = cq_scene + 0x1p-30 * (1.0 + R2);
-            for (int l = l0 + l32; l <= l1; l += 32) {
-                const double dv = (org_v + ((double)l + 0.5) * cell) - ov;
-                int a, b;
-                const bool any = exact_span(ou, org_u, cell, inv_cell, dv * dv, R2, cq, ic, lo, hi, a, b);
-                if (any) emit(colhalf, l, a, b);
-            }
-        }
+    const int lane = tid & 63, wv = tid >> 6;
+    int i0 = v0, i1 = v1;
+#pragma unroll
+    for (int sft = 1; sft < DMPP_WAVE; sft <<= 1) {
+        const int t0 = __shfl_up(i0, sft, 64), t1 = __shfl_up(i1, sft, 64);
+        if (lane >= sft) { i0 += t0; i1 += t1; }
     }
+    if (lane == DMPP_WAVE - 1) { s_wave0[wv] = i0; s_wave1[wv] = i1; }
+    __syncthreads();
+    int b0 = 0, b1 = 0;
+    tot0 = 0; tot1 = 0;
+    for (int q = 0; q < SW; q++) {
+        const int t0 = s_wave0[q], t1 = s_wave1[q];
+        if (q < wv) { b0 += t0; b1 += t1; }
+        tot0 += t0; tot1 += t1;
+    }
+    v0 = b0 + i0 - v0; v1 = b1 + i1 - v1;
 }
 
-// Pass 1 of build_sparse_views: a SUPERSET of every exact span, in single precision.  The coordinates are taken relative to
-// the grid's origin first (|rel| <= S = grid extent + R), so their rounding is <= 2^-24 S; the squared radius carries a margin
-// that covers what this does to R2 - dv^2 (<= 2 R * 2^-22 S + 2^-23 R2, taken four times over), so the half-chord is never
-// shorter than the exact one, and the two cells the run is widened by on both sides absorb the rounding of the division
-// (<= 2^-22 * grid width cells).  emit() as for_each_span.
-template <int SW, class Emit>
-__device__ __forceinline__ void for_each_rough_span(const PlannerConfig& c, const SceneIn& si, const ObPoint* __restrict__ obs, int m, Emit&& emit)
+// ---- the footprints of a scene as a flat list of (obstacle, line) items ---------------------------------------------------
+// Up to kRasterChunk obstacles at a time are staged in LDS: one thread per obstacle computes the footprint (the divisions are
+// paid once per obstacle, not per line) and the obstacle's item count - its rows plus its columns, 0 when the clipped box is
+// empty; first[] is the exclusive prefix sum of the counts.  Item e of a chunk is then one line of one axis of one
+// obstacle: obstacle j with first[j] <= e < first[j + 1], and with k = e - first[j] row iy0 + k for k < rows, column
+// ix0 + (k - rows) otherwise.  The threads of the block take the items in contiguous runs of per = ceil(total / threads);
+// a thread finds its first obstacle by bisection and then only steps (ItemCursor), re-reading the record when it crosses to
+// the next obstacle that has items.
+constexpr int kRasterChunk = 128;                       // obstacles staged at a time
+constexpr int kRasterKeep = 12;                         // spans of a thread's first items that stay in registers from pass 1 to pass 2
+constexpr uint32_t kNoSpan = 0xFFFFu;                   // a | b << 16 of an empty span (a > b)
+struct RasterStage {
+    double ox[kRasterChunk], oy[kRasterChunk], R2[kRasterChunk];
+    int ix0[kRasterChunk], ix1[kRasterChunk], iy0[kRasterChunk], iy1[kRasterChunk];      // the clipped box
+    int icx[kRasterChunk], icy[kRasterChunk];                                            // the cell of the centre (may lie outside the grid)
+    int first[kRasterChunk + 1];
+};
+struct ItemRec { double ox, oy, R2; int ix0, ix1, iy0, iy1, icx, icy; };
+
+__device__ __forceinline__ ItemRec load_rec(const DMPP_LDS RasterStage* S, int j)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    ItemRec r;
+    r.ox = S->ox[j]; r.oy = S->oy[j]; r.R2 = S->R2[j];
+    r.ix0 = S->ix0[j]; r.ix1 = S->ix1[j]; r.iy0 = S->iy0[j]; r.iy1 = S->iy1[j]; r.icx = S->icx[j]; r.icy = S->icy[j];
+    return r;
+}
+
+// Stages obstacles base .. base + kRasterChunk - 1 (as far as the list goes); returns the chunk's items.  All threads of the
+// block; the records and first[] are visible to all of them on return.  The caller keeps the block from staging again while
+// any thread still reads the records.
+template <int SW>
+__device__ __forceinline__ int stage_footprints(const PlannerConfig& c, const SceneIn& si, const ObPoint* __restrict__ obs, int base, int m,
+                                                DMPP_LDS RasterStage* S, int* s_wave)
+{
+    static_assert(SW * DMPP_WAVE > kRasterChunk, "one thread per staged obstacle, and one more for the total");
+    const int tid = threadIdx.x;
     const int W = c.grid_w, H = c.grid_h;
-    const bool colhalf = lane >= 32;
-    const int l32 = lane & 31;
-    const float cellf = (float)c.cell, inv_cellf = (float)(1.0 / c.cell);
     const GlobalPoint2D origin = si.grid_origin;
-    const double extent = (double)max(W, H) * c.cell;
-    auto bcast_f = [](float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); };
-    for (int base = 0; base < m; base += SW * DMPP_WAVE) {
-        float rx = 0, ry = 0, r2m = -1.0f;
-        int ix0 = 0, ix1 = -1, iy0 = 0, iy1 = -1;
-        const int j = base + wv + SW * lane;
-        if (j < m) {
-            const Footprint f = footprint_of(c, origin, obs[j], W, H);
-            ix0 = f.ix0; ix1 = f.ix1; iy0 = f.iy0; iy1 = f.iy1;
-            const double R = sqrt(f.R2), S = extent + R;
-            rx = (float)(f.ox - origin.x); ry = (float)(f.oy - origin.y);
-            r2m = (float)((f.R2 + 4.0 * (R * S * 0x1p-21 + f.R2 * 0x1p-23)) * (1.0 + 0x1p-22));
-        }
-        const unsigned long long anym = wave_ballot(j < m && ix1 >= ix0 && iy1 >= iy0);
-        const int left = m - base - wv;
-        const int cnt = left <= 0 ? 0 : min(DMPP_WAVE, (left + SW - 1) / SW);
-        for (int q = 0; q < cnt; q++) {
-            if (!((anym >> q) & 1ull)) continue;
-            const float fx = bcast_f(rx, q), fy = bcast_f(ry, q), R2 = bcast_f(r2m, q);
-            const int jx0 = __builtin_amdgcn_readlane(ix0, q), jx1 = __builtin_amdgcn_readlane(ix1, q);
-            const int jy0 = __builtin_amdgcn_readlane(iy0, q), jy1 = __builtin_amdgcn_readlane(iy1, q);
-            const float ou = colhalf ? fy : fx, ov = colhalf ? fx : fy;
-            const int l0 = colhalf ? jx0 : jy0, l1 = colhalf ? jx1 : jy1, lo = colhalf ? jy0 : jx0, hi = colhalf ? jy1 : jx1;
-            for (int l = l0 + l32; l <= l1; l += 32) {
-                const float dv = ((float)l + 0.5f) * cellf - ov;
-                const float h2 = R2 - dv * dv;
-                if (h2 < 0.0f) continue;
-                const float half = __builtin_sqrtf(h2);
-                const int a = max((int)floorf((ou - half) * inv_cellf) - 2, lo), b = min((int)floorf((ou + half) * inv_cellf) + 2, hi);
-                if (a <= b) emit(colhalf, l, a, b);
-            }
+    const int cn = min(m - base, kRasterChunk);
+    int cnt = 0;
+    if (tid < cn) {
+        const Footprint f = footprint_of(c, origin, obs[base + tid], W, H);
+        S->ox[tid] = f.ox; S->oy[tid] = f.oy; S->R2[tid] = f.R2;
+        S->ix0[tid] = f.ix0; S->ix1[tid] = f.ix1; S->iy0[tid] = f.iy0; S->iy1[tid] = f.iy1;
+        S->icx[tid] = (int)floor((f.ox - origin.x) / c.cell);
+        S->icy[tid] = (int)floor((f.oy - origin.y) / c.cell);
+        if (f.ix1 >= f.ix0 && f.iy1 >= f.iy0) cnt = (f.iy1 - f.iy0 + 1) + (f.ix1 - f.ix0 + 1);
+    }
+    const int off = block_excl_scan<SW>(cnt, tid, s_wave);
+    if (tid <= cn) S->first[tid] = off;                  // (thread cn has no obstacle: its sum is the total)
+    const int total = s_wave[SW];
+    __syncthreads();
+    return total;
+}
+
+struct ItemCursor {
+    int j, fj, nx;                                       // the obstacle of the current item, its first item, the next obstacle's first item
+    // e < first[cn]: the obstacle that holds item e
+    __device__ __forceinline__ void seek(const DMPP_LDS RasterStage* S, int cn, int e)
+    {
+        int lo = 0, hi = cn - 1;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (S->first[mid + 1] > e) hi = mid; else lo = mid + 1; }
+        j = lo; fj = S->first[lo]; nx = S->first[lo + 1];
+    }
+    // on to item e (not before the current one, and < first[cn]); true when that is another obstacle.  Obstacles without items are stepped over.
+    __device__ __forceinline__ bool step_to(const DMPP_LDS RasterStage* S, int e)
+    {
+        if (e < nx) return false;
+        do { j++; fj = nx; nx = S->first[j + 1]; } while (nx <= e);
+        return true;
+    }
+};
+
+// what the spans of a scene share
+struct SpanScene { double cell, inv_cell, cq_scene, orgx, orgy; };
+__device__ __forceinline__ SpanScene span_scene(const PlannerConfig& c, const SceneIn& si)
+{
+    SpanScene w;
+    w.cell = c.cell; w.inv_cell = 1.0 / c.cell; w.orgx = si.grid_origin.x; w.orgy = si.grid_origin.y;
+    // the scene's share of the error bound that certifies span ends (exact_span): coordinate rounding, with both axes' origins
+    w.cq_scene = 0x1p-47 * (2.0 * (fabs(w.orgx) + fabs(w.orgy)) + (double)max(c.grid_w, c.grid_h) * w.cell) + 0x1p-36 * w.cell;
+    return w;
+}
+
+// Item k of the obstacle r: which half (colhalf: a column), which line l, and the exact span [a, b] on it (false: empty).
+__device__ __forceinline__ bool item_span(const SpanScene& w, const ItemRec& r, int k, bool& colhalf, int& l, int& a, int& b)
+{
+    const int nr = r.iy1 - r.iy0 + 1;
+    colhalf = k >= nr;
+    l = colhalf ? r.ix0 + (k - nr) : r.iy0 + k;
+    const double ou = colhalf ? r.oy : r.ox, ov = colhalf ? r.ox : r.oy;
+    const double org_u = colhalf ? w.orgy : w.orgx, org_v = colhalf ? w.orgx : w.orgy;
+    const int ic = colhalf ? r.icy : r.icx, lo = colhalf ? r.iy0 : r.ix0, hi = colhalf ? r.iy1 : r.ix1;
+    const double cq = w.cq_scene + 0x1p-30 * (1.0 + r.R2);
+    const double dv = (org_v + ((double)l + 0.5) * w.cell) - ov;
+    return exact_span(ou, org_u, w.cell, w.inv_cell, dv * dv, r.R2, cq, ic, lo, hi, a, b);
+}
+
+// Walks the exact spans of every footprint of a scene: emit(colhalf, line, a, b) is called once for every line a footprint
+// touches, [a, b] being its first and last occupied position on that line (row-major half: line = y, positions x;
+// column-major half: line = x, positions y).  All threads of the block; nobody may be reading S when it is called.
+template <int SW, class Emit>
+__device__ __forceinline__ void for_each_span(const PlannerConfig& c, const SceneIn& si, const ObPoint* __restrict__ obs, int m,
+                                              DMPP_LDS RasterStage* S, int* s_wave, Emit&& emit)
+{
+    const int tid = threadIdx.x;
+    const SpanScene w = span_scene(c, si);
+    for (int base = 0; base < m; base += kRasterChunk) {
+        if (base) __syncthreads();
+        const int total = stage_footprints<SW>(c, si, obs, base, m, S, s_wave);
+        const int per = (total + SW * DMPP_WAVE - 1) / (SW * DMPP_WAVE), e0 = min(tid * per, total), e1 = min(e0 + per, total);
+        if (e0 >= e1) continue;
+        ItemCursor cu; cu.seek(S, min(m - base, kRasterChunk), e0);
+        ItemRec r = load_rec(S, cu.j);
+        for (int e = e0; e < e1; e++) {
+            if (cu.step_to(S, e)) r = load_rec(S, cu.j);
+            bool colhalf; int l, a, b;
+            if (item_span(w, r, e - cu.fj, colhalf, l, a, b)) emit(colhalf, l, a, b);
         }
     }
 }
 
 // Builds both sparse views of a scene from its obstacle list.  All kSearchBlock threads; returns the words the larger view
 // needs (> budget: nothing was filled, the views are unusable).
-//   pass 1: which words of which lines the footprints can touch (single-precision span estimates, widened: a superset);
-//   offsets: exclusive prefix sum of the word counts over the lines;  pass 2: the exact spans, OR-ed into the words.
+//   pass 1: the exact span of every item, and which words of which lines the spans touch; the spans of a thread's first
+//           kRasterKeep items of the first chunk stay in registers (a | b << 16: positions are < 2048);
+//   offsets: exclusive prefix sum of the word counts over the lines, both views in one scan;
+//   pass 2: the same items by the same threads; the kept spans are only OR-ed into the words, the others are computed again
+//           (same function, same arguments, same span).
+// S: the staging area (not in the views' data: pass 2 writes there while records are still read); s_wave [SW + 1], s_wave2 [SW].
 template <int K, int SW>
 __device__ __forceinline__ int build_sparse_views(const PlannerConfig& c, const SceneIn& si, const ObPoint* __restrict__ obs, int m,
-                                                  const SparseView<K>& vr, const SparseView<K>& vc, int budget, int* s_wave,
-                                                  long long* tmark = nullptr)
+                                                  const SparseView<K>& vr, const SparseView<K>& vc, int budget,
+                                                  DMPP_LDS RasterStage* S, int* s_wave, int* s_wave2, long long* tmark = nullptr)
 {
     using M = typename SparseView<K>::M;
+    constexpr int NT = SW * DMPP_WAVE;
     const int tid = threadIdx.x;
     const int W = c.grid_w, H = c.grid_h;
     int tm_i = 0;
     auto mark = [&]() { if (tmark) tmark[tm_i++] = clock64(); };
     mark();
-    for (int l = tid; l < H; l += (SW * DMPP_WAVE)) vr.clear_line(l);
-    for (int l = tid; l < W; l += (SW * DMPP_WAVE)) vc.clear_line(l);
-    __syncthreads();
-    mark(); mark();
-    auto mark_words = [&](bool colhalf, int l, int a, int b) {
-        const int wa = a >> 5, wb = b >> 5;
-        const M bits = (M)((((M)2) << (wb - wa)) - (M)1) << wa;
-        if (colhalf) vc.or_mask(l, bits); else vr.or_mask(l, bits);
-    };
-#ifdef DMPP_EXACT_PASS1          // experiment: the exact spans in pass 1 too (fewer words allocated, more arithmetic)
-    for_each_span<SW>(c, si, obs, m, mark_words);
-#else
-    for_each_rough_span<SW>(c, si, obs, m, mark_words);
-#endif
+    for (int l = tid; l < H; l += NT) vr.clear_line(l);
+    for (int l = tid; l < W; l += NT) vc.clear_line(l);
     __syncthreads();
     mark();
-    // ---- offsets: exclusive prefix sum of the word counts over the lines, per view ----
-    auto place = [&](const SparseView<K>& vw) {
-        const int NL = vw.NL, per = (NL + (SW * DMPP_WAVE) - 1) / (SW * DMPP_WAVE);
-        const int l0 = tid * per, l1 = min(l0 + per, NL);
-        int cnt = 0;
-        for (int l = l0; l < l1; l++) cnt += popc_m(vw.mask_of(l));
-        int off = block_excl_scan<SW>(cnt, tid, s_wave);
-        const int total = s_wave[SW];
-        for (int l = l0; l < l1; l++) { const int k = popc_m(vw.mask_of(l)); vw.set_off(l, (uint32_t)off); off += k; }
-        __syncthreads();
-        return total;
+    if (m <= 0) mark();
+    const SpanScene w = span_scene(c, si);
+    uint32_t keep[kRasterKeep];                              // a shift register: only ever indexed by constants
+#pragma unroll
+    for (int q = 0; q < kRasterKeep; q++) keep[q] = kNoSpan;
+    auto push = [&](uint32_t v) {                            // after kRasterKeep pushes the first one is keep[0]
+#pragma unroll
+        for (int q = 0; q + 1 < kRasterKeep; q++) keep[q] = keep[q + 1];
+        keep[kRasterKeep - 1] = v;
     };
-    const int total_r = place(vr), total_c = place(vc);
+    int total0 = 0;
+    for (int base = 0; base < m; base += kRasterChunk) {
+        if (base) __syncthreads();
+        const int total = stage_footprints<SW>(c, si, obs, base, m, S, s_wave);
+        if (base == 0) { total0 = total; mark(); }
+        const int per = (total + NT - 1) / NT, e0 = min(tid * per, total), e1 = min(e0 + per, total);
+        ItemCursor cu; cu.j = 0; cu.fj = 0; cu.nx = 0;
+        ItemRec r; r.ox = r.oy = r.R2 = 0; r.ix0 = r.iy0 = 0; r.ix1 = r.iy1 = -1; r.icx = r.icy = 0;
+        if (e0 < e1) { cu.seek(S, min(m - base, kRasterChunk), e0); r = load_rec(S, cu.j); }
+        for (int i = 0; i < per; i++) {
+            const int e = e0 + i;
+            uint32_t v = kNoSpan;
+            if (e < e1) {
+                if (cu.step_to(S, e)) r = load_rec(S, cu.j);
+                bool colhalf; int l, a, b;
+                if (item_span(w, r, e - cu.fj, colhalf, l, a, b)) {
+                    const int wa = a >> 5, wb = b >> 5;
+                    const M bits = (M)((((M)2) << (wb - wa)) - (M)1) << wa;
+                    const SparseView<K> vw = colhalf ? vc : vr;          // (by value: per-lane field selects, no stack object)
+                    vw.or_mask(l, bits);
+                    v = (uint32_t)a | ((uint32_t)b << 16);
+                }
+            }
+            if (base == 0 && i < kRasterKeep) push(v);       // (uniform)
+        }
+        if (base == 0) for (int i = per; i < kRasterKeep; i++) push(kNoSpan);
+    }
+    __syncthreads();
+    mark();
+    // ---- offsets: exclusive prefix sum of the word counts over the lines, both views at once ----
+    int total_r, total_c;
+    {
+        const int per_r = (H + NT - 1) / NT, per_c = (W + NT - 1) / NT;
+        const int r0 = min(tid * per_r, H), r1 = min(r0 + per_r, H), c0 = min(tid * per_c, W), c1 = min(c0 + per_c, W);
+        int off_r = 0, off_c = 0;
+        for (int l = r0; l < r1; l++) off_r += popc_m(vr.mask_of(l));
+        for (int l = c0; l < c1; l++) off_c += popc_m(vc.mask_of(l));
+        block_excl_scan2<SW>(off_r, off_c, total_r, total_c, tid, s_wave, s_wave2);
+        for (int l = r0; l < r1; l++) { const int k = popc_m(vr.mask_of(l)); vr.set_off(l, (uint32_t)off_r); off_r += k; }
+        for (int l = c0; l < c1; l++) { const int k = popc_m(vc.mask_of(l)); vc.set_off(l, (uint32_t)off_c); off_c += k; }
+        __syncthreads();
+    }
     const int need = max(total_r, total_c);
     mark();
     if (need > budget) return need;
-    for (int i = tid; i < total_r; i += (SW * DMPP_WAVE)) vr.data[i] = 0;
-    for (int i = tid; i < total_c; i += (SW * DMPP_WAVE)) vc.data[i] = 0;
+    for (int i = tid; i < total_r; i += NT) vr.data[i] = 0;
+    for (int i = tid; i < total_c; i += NT) vc.data[i] = 0;
     __syncthreads();
     mark();
-    const SparseView<K> vw = (tid & 32) ? vc : vr;           // this lane's half, selected once (by value: per-lane field selects, no stack object)
-    for_each_span<SW>(c, si, obs, m, [&](bool, int l, int a, int b) {
+    auto or_span = [&](bool colhalf, int l, int a, int b) {
+        const SparseView<K> vw = colhalf ? vc : vr;
         const LineM<M> lm = vw.line(l);
-        for_words(a, b, [&](int w, uint32_t bits) {
-            __hip_atomic_fetch_or(&vw.data[lm.off + popc_m((M)(lm.mask & ((((M)1) << w) - (M)1)))], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        for_words(a, b, [&](int wd, uint32_t bits) {
+            __hip_atomic_fetch_or(&vw.data[lm.off + popc_m((M)(lm.mask & ((((M)1) << wd) - (M)1)))], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         });
-    });
+    };
+    for (int base = 0; base < m; base += kRasterChunk) {
+        int total = total0;
+        if (m > kRasterChunk) {                              // (a single chunk is still staged from pass 1)
+            if (base) __syncthreads();
+            total = stage_footprints<SW>(c, si, obs, base, m, S, s_wave);
+        }
+        const int per = (total + NT - 1) / NT, e0 = min(tid * per, total), e1 = min(e0 + per, total);
+        const int nk = base == 0 ? min(per, kRasterKeep) : 0;
+        ItemCursor cu; cu.j = 0; cu.fj = 0; cu.nx = 0;
+        if (e0 < e1) cu.seek(S, min(m - base, kRasterChunk), e0);
+        {   // the kept spans: only the line has to be found again
+            int iy0 = 0, nr = 0, ix0 = 0;
+            bool fresh = true;
+            for (int i = 0; i < nk; i++) {
+                const uint32_t v = keep[0];
+                push(kNoSpan);
+                if (v != kNoSpan) {                          // (never for an item beyond e1)
+                    const int e = e0 + i;
+                    const bool moved = cu.step_to(S, e);
+                    if (moved || fresh) { iy0 = S->iy0[cu.j]; nr = S->iy1[cu.j] - iy0 + 1; ix0 = S->ix0[cu.j]; fresh = false; }
+                    const int k = e - cu.fj;
+                    const bool colhalf = k >= nr;
+                    or_span(colhalf, colhalf ? ix0 + (k - nr) : iy0 + k, (int)(v & 0xFFFFu), (int)(v >> 16));
+                }
+            }
+        }
+        ItemRec r; r.ox = r.oy = r.R2 = 0; r.ix0 = r.iy0 = 0; r.ix1 = r.iy1 = -1; r.icx = r.icy = 0;
+        bool fresh = true;
+        for (int i = nk; i < per; i++) {
+            const int e = e0 + i;
+            if (e < e1) {
+                const bool moved = cu.step_to(S, e);
+                if (moved || fresh) { r = load_rec(S, cu.j); fresh = false; }
+                bool colhalf; int l, a, b;
+                if (item_span(w, r, e - cu.fj, colhalf, l, a, b)) or_span(colhalf, l, a, b);
+            }
+        }
+    }
     __syncthreads();
     mark();
     return need;
@@ -530,7 +644,8 @@ __device__ __forceinline__ int build_sparse_views(const PlannerConfig& c, const 
 // budget of the launch.  All kSearchBlock threads.
 template <int SW>
 __device__ __forceinline__ void build_dense_views(const PlannerConfig& c, const SceneIn& si, const ObPoint* __restrict__ obs, int m,
-                                                  uint32_t* __restrict__ bm, DMPP_LDS uint64_t* nz_row, DMPP_LDS uint64_t* nz_col)
+                                                  uint32_t* __restrict__ bm, DMPP_LDS uint64_t* nz_row, DMPP_LDS uint64_t* nz_col,
+                                                  DMPP_LDS RasterStage* S, int* s_wave)
 {
     const int tid = threadIdx.x;
     const int W = c.grid_w, H = c.grid_h, WW = W >> 5, HW = H >> 5, NW = (W * H) >> 5;
@@ -542,7 +657,7 @@ __device__ __forceinline__ void build_dense_views(const PlannerConfig& c, const 
     }
     __threadfence();
     __syncthreads();
-    for_each_span<SW>(c, si, obs, m, [&](bool colhalf, int l, int a, int b) {
+    for_each_span<SW>(c, si, obs, m, S, s_wave, [&](bool colhalf, int l, int a, int b) {
         uint32_t* line = colhalf ? bmT + (size_t)l * HW : bm + (size_t)l * WW;
         for_words(a, b, [&](int w, uint32_t bits) { atomicOr(&line[w], bits); });
     });
@@ -621,7 +736,7 @@ constexpr uint32_t kCodeStart = start_row();
 template <int CL>
 struct SearchLds {                               // the static LDS of a searching workgroup (8.2 KB at CL = 9)
     static constexpr int kClosedLog = CL, kClosedTab = 1 << CL, kClosedMax = 3 << (CL - 2);
-    uint32_t o_ent[kOpenCap];       // x | y << 12 | arriving direction << 24 | kEntry* flags << 28
+    alignas(8) uint32_t o_ent[kOpenCap];       // (8: the set-up stages footprints here, RasterStage)  x | y << 12 | arriving direction << 24 | kEntry* flags << 28
     uint16_t o_f2[kOpenCap];        // f / 2, 0xFFFF = dead slot
     uint16_t o_run[kOpenCap];       // run length of the move that reached the cell
     uint32_t c_tab[kClosedTab];     // closed cells (cell + 1, 0 = empty): open addressing, linear probing
@@ -1340,21 +1455,28 @@ __device__ __forceinline__ void search_scene(const PlannerConfig& c, int scene, 
         vr.data = (DMPP_LDS uint32_t*)(p + used); vc.data = vr.data + budget;
         vr.LW = WW; vr.NL = H; vc.LW = HW; vc.NL = W;
     }
-    for (int i = tid; i < LdsT::kClosedTab; i += (SW * DMPP_WAVE)) L.c_tab[i] = 0;
-    for (int i = tid; i < kOpenCap; i += (SW * DMPP_WAVE)) L.o_f2[i] = 0xFFFFu;      // dead slots everywhere: the pop never range-checks
+    // the open list and the closed set are idle until the views stand: the footprints are staged in their place (the job
+    // list and s_wave lie behind it), and they are initialised behind the build
+    static_assert(sizeof(RasterStage) <= offsetof(LdsT, job), "the staged footprints must fit the open list and the closed set");
+    DMPP_LDS RasterStage* stage = (DMPP_LDS RasterStage*)(DMPP_LDS unsigned char*)(unsigned char*)&L;
+    int* s_wave2 = (int*)L.job;
+    static_assert(sizeof(L.job) >= kSearchSetupWavesWide * sizeof(int), "second row of wave sums");
     const ObPoint* obs = obs_now + si.obs_off;
 #ifdef DMPP_DEBUG_SEARCH
     long long tmark[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const int need = budget > 0 ? build_sparse_views<K, SW>(c, si, obs, si.obs_n, vr, vc, budget, L.s_wave, tmark) : 1;
+    const int need = budget > 0 ? build_sparse_views<K, SW>(c, si, obs, si.obs_n, vr, vc, budget, stage, L.s_wave, s_wave2, tmark) : 1;
 #else
-    const int need = budget > 0 ? build_sparse_views<K, SW>(c, si, obs, si.obs_n, vr, vc, budget, L.s_wave) : 1;
+    const int need = budget > 0 ? build_sparse_views<K, SW>(c, si, obs, si.obs_n, vr, vc, budget, stage, L.s_wave, s_wave2) : 1;
 #endif
     const bool dense = need > budget;          // uniform over the block
     if (tid == 0) { if (budget > 0) atomicMax(need_max, need); overflow[scene] = dense ? 1 : 0; }
     uint32_t* bm = gbitmaps + (size_t)scene * 2 * (N >> 5);
     DMPP_LDS uint64_t* nz_row = (DMPP_LDS uint64_t*)((DMPP_LDS unsigned char*)smem_raw + kViewsAt);
     DMPP_LDS uint64_t* nz_col = nz_row + H;
-    if (dense) { __syncthreads(); build_dense_views<SW>(c, si, obs, si.obs_n, bm, nz_row, nz_col); }
+    if (dense) { __syncthreads(); build_dense_views<SW>(c, si, obs, si.obs_n, bm, nz_row, nz_col, stage, L.s_wave); }
+    // (every thread is past a barrier behind its last read of the staged footprints)
+    for (int i = tid; i < LdsT::kClosedTab; i += (SW * DMPP_WAVE)) L.c_tab[i] = 0;
+    for (int i = tid; i < kOpenCap; i += (SW * DMPP_WAVE)) L.o_f2[i] = 0xFFFFu;      // dead slots everywhere: the pop never range-checks
     const DenseView dr{ bm, nz_row, WW, H }, dc{ bm + (N >> 5), nz_col, HW, W };
     const int start = cell_of(c, si.grid_origin, si.loc.globalpoint.x, si.loc.globalpoint.y);
     const int goal = cell_of(c, si.grid_origin, si.goal.x, si.goal.y);
@@ -1390,7 +1512,7 @@ __device__ __forceinline__ void search_scene(const PlannerConfig& c, int scene, 
                                  : search_core<SPILL>(c, L, vr, vc, start, goal, order_cap, closed, pin, order, path, SPILL ? ospill : nullptr, lane, dbg_t, dbg_c);
     if (lane == 0) {
         publish_debug(path, c.max_path, dbg_t, dbg_c, t_setup, clock64() - t_begin);
-        int32_t* d2 = path + c.max_path - 32;      // set-up phases: entry->clear, (unused x2), pass 1, offsets, zero, pass 2, tail
+        int32_t* d2 = path + c.max_path - 32;      // set-up phases: entry, clear, staging of the first chunk, pass 1, offsets, zero, pass 2, tail
         d2[0] = (int)(tmark[0] - t_begin); for (int i = 1; i < 7; i++) d2[i] = (int)(tmark[i] - tmark[i - 1]); d2[7] = (int)(t_begin + t_setup - tmark[6]);
     }
 #else
@@ -1475,7 +1597,11 @@ k_export_grid(PlannerConfig c, int scene, int budget, const SceneIn* __restrict_
               uint8_t* __restrict__ out, int* __restrict__ bad)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    __shared__ int s_wave[kSearchSetupWaves + 1];
+    __shared__ int s_wave[kSearchSetupWaves + 1], s_wave2[kSearchSetupWaves];
+    __shared__ RasterStage stage_mem;
+    // (the host gives this kernel the dynamic LDS of a search, which leaves room for a SearchLds)
+    static_assert(sizeof(RasterStage) + sizeof(int) * (2 * kSearchSetupWaves + 1) <= sizeof(SearchLds<closed_log_of<0>()>), "static LDS of k_export_grid");
+    DMPP_LDS RasterStage* stage = (DMPP_LDS RasterStage*)&stage_mem;
     const int tid = threadIdx.x;
     const int W = c.grid_w, H = c.grid_h, WW = W >> 5, HW = H >> 5;
     const SceneIn& si = in[scene];
@@ -1498,13 +1624,13 @@ k_export_grid(PlannerConfig c, int scene, int budget, const SceneIn* __restrict_
         vr.LW = WW; vr.NL = H; vc.LW = HW; vc.NL = W;
     }
     const ObPoint* obs = obs_now + si.obs_off;
-    const int need = build_sparse_views<K, kSearchSetupWaves>(c, si, obs, si.obs_n, vr, vc, budget, s_wave);
+    const int need = build_sparse_views<K, kSearchSetupWaves>(c, si, obs, si.obs_n, vr, vc, budget, stage, s_wave, s_wave2);
     if (need > budget) {
         if (tid == 0) bad[1] = 1;
         for (int cell = tid; cell < W * H; cell += kSearchBlock) out[cell] = 0;
         __threadfence();
         __syncthreads();
-        for_each_span<kSearchSetupWaves>(c, si, obs, si.obs_n, [&](bool colhalf, int l, int a, int b) {
+        for_each_span<kSearchSetupWaves>(c, si, obs, si.obs_n, stage, s_wave, [&](bool colhalf, int l, int a, int b) {
             if (!colhalf) for (int x = a; x <= b; x++) out[l * W + x] = 1;
         });
         return;

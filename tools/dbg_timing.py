@@ -34,4 +34,4 @@ simd = (hw >> 4) & 3
 print('searching waves per SIMD id:', np.bincount(simd, minlength=4).tolist(), ' wave slot ids:', np.bincount(hw & 15, minlength=16).tolist())
 
 setup=np.array(setup)[g['status']==0]
-print('setup phases (cycles) entry, clear, footprints, pass1, offsets, zero, pass2, tail: median', np.median(setup,axis=0).astype(int).tolist(), 'max', setup.max(axis=0).tolist())
+print('setup phases (cycles) entry, clear, stage, pass1 (exact spans), offsets, zero, pass2 (OR), tail: median', np.median(setup,axis=0).astype(int).tolist(), 'max', setup.max(axis=0).tolist())
