@@ -119,6 +119,10 @@ EpisodeSpawnStats = _dt([("n_contact", i4), ("n_blocked", i4), ("n_rejected", i4
 EGO_CONTACT = 128             # cause words only: the ego touched an obstacle of its slice (DMPP_EGO_CONTACT)
 # episode traffic reset: the actors of a restarted scene go back to a start state, one set per start record
 TrafficStart = _dt([("s", f8), ("v", f8)])
+# episode log: one record per ended episode, appended on the device in the order of the scenes
+EPISODE_LOG_MAX = 1 << 20
+EpisodeRecord = _dt([("scene", i4), ("episode", i4), ("start", i4), ("cause", i4), ("age", i4), ("seq", i4), ("tick", np.int64),
+                     ("dist", f8), ("end_pos", GlobalPoint2D), ("end_speed", f8), ("score", RolloutScore)])
 
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
@@ -263,6 +267,11 @@ def load_library(path=None):
     if treset:
         lib.pp_set_episode_traffic.argtypes = [vp, ci, vp]
         lib.pp_get_episode_traffic_resets.argtypes = [vp, vp, ci]
+    elog = hasattr(lib, "pp_set_episode_log") or path == LIB_PATH          # (as above: an older build may lack it)
+    if elog:
+        lib.pp_set_episode_log.argtypes = [vp, ci]
+        lib.pp_read_episode_log.argtypes = [vp, vp, ci, C.POINTER(C.c_longlong)]
+        lib.pp_get_episode_log_info.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -278,7 +287,8 @@ def load_library(path=None):
             (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
             (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()) + \
             (((28, TrafficFollow),) if react else ()) + (((29, EpisodeModel), (30, EpisodeStats)) if episodes else ()) + \
-            (((31, EpisodeSpawn), (32, EpisodeSpawnStats)) if spawn else ()) + (((33, TrafficStart),) if treset else ()):
+            (((31, EpisodeSpawn), (32, EpisodeSpawnStats)) if spawn else ()) + (((33, TrafficStart),) if treset else ()) + \
+            (((34, EpisodeRecord),) if elog else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -674,6 +684,33 @@ class Planner:
         out = np.zeros(getattr(self, "n_traffic_reset", 0), np.int32)
         _check(self.lib.pp_get_episode_traffic_resets(self.h, _ptr(out), len(out)))
         return out
+
+    # ---- episode log: one record per ended episode, appended on the device ------------------------
+    def set_episode_log(self, cap):
+        """pp_set_episode_log, after set_episodes / set_episode_spawn / set_episode_traffic - call it last: from the
+        next advance on every ended episode appends one EpisodeRecord to a ring of `cap` records on the device, in the order of the
+        scene indices.  A second call starts a new log.  cap 0: the log off; what was logged stays readable."""
+        _check(self.lib.pp_set_episode_log(self.h, int(cap)))
+        if int(cap) > 0:
+            self.episode_log_cap = int(cap)
+
+    def read_episode_log(self, max_records=None):
+        """pp_read_episode_log: (the oldest unread EpisodeRecord records still in the ring - at most max_records, by default all of
+        them -, the number of records that were overwritten before a read saw them, newly counted by this call); a staged advance
+        included (host wait).  What does not fit stays unread."""
+        want = getattr(self, "episode_log_cap", 0) if max_records is None else int(max_records)
+        out, lost = np.zeros(max(want, 1), EpisodeRecord), C.c_longlong()
+        n = self.lib.pp_read_episode_log(self.h, _ptr(out), want, C.byref(lost))
+        if n < 0:
+            _check(n)
+        return out[:n].copy(), lost.value
+
+    def episode_log_info(self):
+        """pp_get_episode_log_info: (records appended since set_episode_log, records overwritten unread so far - those the next
+        read will report included); a staged advance included (host wait)."""
+        total, lost = C.c_longlong(), C.c_longlong()
+        _check(self.lib.pp_get_episode_log_info(self.h, C.byref(total), C.byref(lost)))
+        return total.value, lost.value
 
     def traffic_speed(self):
         """pp_get_traffic_speed: the speed (m/s) of every actor, as traffic_state gives the arc lengths (host wait)."""

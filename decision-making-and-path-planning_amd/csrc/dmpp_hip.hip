@@ -27,6 +27,7 @@
 #include "kernels_es.hpp"
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
+#include "kernels_el.hpp"
 #include "kernels_f.hpp"
 #include "kernels_t.hpp"
 #include "kernels_op.hpp"
@@ -228,6 +229,15 @@ struct TrafficResetState {
     bool on = false, ever = false; int n_sets = 0, actors = 0, cur = 0;      // ever: a set call succeeded on this handle (the counters are readable)
     DevBuf<int32_t> d_scene; DevBuf<TrafficStart> d_starts[2]; DevBuf<int32_t> d_resets[2];
 };
+// episode log (first pp_set_episode_log): the ring of `cap` records, the count of records appended since the set call,
+// every scene's start record and - only on a handle with a scorecard - the scorecard of its running episode; on the host the number
+// of the next advance, the ordinal of the oldest unread record and the records lost so far.  While on (only with episodes on),
+// pp_advance_async launches k_log_episodes behind its respawn kernel and a scored tick runs k_score_ego<true>.  What was logged stays
+// readable after the log went off
+struct EpisodeLogState {
+    bool on = false, ever = false; int cap = 0, seq = 0; long long read = 0, lost = 0;
+    DevBuf<EpisodeRecord> d_ring; DevBuf<long long> d_total; DevBuf<int32_t> d_start_of; DevBuf<RolloutScore> d_score;
+};
 
 }  // namespace
 
@@ -319,6 +329,7 @@ struct pp_planner {
     EpisodeState episode;
     SpawnState spawn;
     TrafficResetState treset;
+    EpisodeLogState elog;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
@@ -831,6 +842,10 @@ static int reset_scores(pp_handle h)
     hipLaunchKernelGGL(dmpp::k_score_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->score.d_score);
     HIP_TRY(hipGetLastError());
     for (int q = 0; q < kBuf; q++) HIP_TRY(hipMemsetAsync(h->score.d_grid[q], 0, (size_t)ns * sizeof(dmpp::ScoreGridPart), h->stream));
+    if (h->elog.d_score) {                              // the scorecards of the running episodes restart with the totals (§4n 3.)
+        hipLaunchKernelGGL(dmpp::k_score_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->elog.d_score);
+        HIP_TRY(hipGetLastError());
+    }
     return PP_OK;
 }
 
@@ -870,7 +885,7 @@ static int upload_pools(pp_handle h, const ObPoint* obs_pool, const ObMotion* mo
 // last (which syncs: the caller may reuse its buffers).  map_bad: scenes that k_resolve_map could not place (pp_set_egos).
 static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad = 0)
 {
-    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; h->spawn.on = false; h->treset.on = false; note_current_set(h);
+    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; h->spawn.on = false; h->treset.on = false; h->elog.on = false; note_current_set(h);
     { int r = reset_ego_flags(h); if (r) return r; }
     if (h->score.on) { int r = reset_scores(h); if (r) return r; }
     if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
@@ -1239,8 +1254,13 @@ int pp_plan_tick(pp_handle h)
         if (h->score.on) {        // scorecard, front half: behind this tick's Planning kernel, on the upload stream - in front of the advance that may follow
             hipStream_t su = h->stream_up;
             HIP_TRY(hipStreamWaitEvent(su, rec.ev_front, 0));
-            hipLaunchKernelGGL(dmpp::k_score_ego, dim3((unsigned)((n + dmpp::kScScenes - 1) / dmpp::kScScenes)), dim3(dmpp::kBlock), 0, su,
-                               0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total, h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score);
+            const dim3 sgrid((unsigned)((n + dmpp::kScScenes - 1) / dmpp::kScScenes));
+            if (h->elog.on && h->elog.d_score)      // episode log: the tick is folded into the scorecards of the running episodes too (§4n 3.)
+                hipLaunchKernelGGL(dmpp::k_score_ego<true>, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total,
+                                   h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, h->elog.d_score);
+            else
+                hipLaunchKernelGGL(dmpp::k_score_ego<false>, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total,
+                                   h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, (RolloutScore*)nullptr);
             PP_TRY(h->score.ego.record(su));
         }
     }
@@ -1506,6 +1526,12 @@ static int stage_inputs(pp_handle h, const StageSource& src)
             hipLaunchKernelGGL(dmpp::k_respawn_egos, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
                                h->episode.em, n, P.d_in, d_in, h->d_state, h->episode.d_start_in, h->episode.d_start_state, h->rollout.d_flags, h->episode.d_stats,
                                src.trace, h->score.on ? h->score.d_score.get() : nullptr);
+        if (h->episode.on && h->elog.on) {      // one record per episode the kernel above ended, in the order of the scenes; the kernels below do not read it
+            hipLaunchKernelGGL(dmpp::k_log_episodes, dim3(1), dim3(dmpp::kLogBlock), 0, su,
+                               n, h->elog.cap, h->elog.seq, h->tick_seq, P.d_in, h->episode.d_stats, h->spawn.on ? h->spawn.d_stats[h->spawn.cur].get() : nullptr,
+                               h->elog.d_ring, h->elog.d_total, h->elog.d_start_of, h->elog.d_score);
+            h->elog.seq++;
+        }
     }
     if (h->traffic.on) {                  // an advance moves the actors one step on - by the car-following law while that is on (§4i) -, an update places them where they are
         if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }
@@ -1615,7 +1641,9 @@ int pp_score_begin(pp_handle h, double dt_score)
         int r = h->score.d_score.reserve(ns); if (r) return r;
         for (int q = 0; q < kBuf; q++) if ((r = h->score.d_grid[q].reserve(ns))) return r;
     }
+    if (h->elog.on) { int r = h->elog.d_score.reserve((size_t)h->caps.max_scenes); if (r) return r; }      // the episode log gets its scorecards once scoring comes on (§4n)
     { int r = join_all(h); if (r) return r; }            // the ticks scored so far (a restart) and everything before
+    if (h->elog.on) PP_TRY(h->rollout.adv.wait(h->stream));      // (... and a staged advance: k_log_episodes writes the scorecards of the episodes it ended)
     { int r = reset_scores(h); if (r) return r; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->score.on = true; h->score.dt = dt_score;
@@ -1961,7 +1989,7 @@ int pp_set_episodes(pp_handle h, const EpisodeModel* em)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episodes: an update is staged for the next tick (set the episodes before staging, or after the tick)");
-    if (!em) { h->episode.on = false; h->spawn.on = false; h->treset.on = false; return PP_OK; }
+    if (!em) { h->episode.on = false; h->spawn.on = false; h->treset.on = false; h->elog.on = false; return PP_OK; }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_episodes: no resident scenes");
     if ((em->end_mask & ~31) != 0) return fail(PP_ERR_ARG, "pp_set_episodes: end_mask holds bits outside the five DMPP_EGO_* flags (31)");
@@ -1978,6 +2006,7 @@ int pp_set_episodes(pp_handle h, const EpisodeModel* em)
     h->episode.on = false;                                // (until the copies below have landed: a failed copy leaves episodes off, not half a capture)
     h->spawn.on = false;                                  // (record 0 of the spawn model's pool was the old capture: §4l)
     h->treset.on = false;                                 // (... and set 0 of the traffic reset went with it: §4m)
+    h->elog.on = false;                                   // (... and the episodes the log numbered: §4n)
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_in, h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_state, h->d_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(dmpp::k_episode_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, (int)ns, h->episode.d_stats);
@@ -2009,7 +2038,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_spawn: an update is staged for the next tick (set the spawn model before staging, or after the tick)");
-    if (!sp) { h->spawn.on = false; h->treset.on = false; return PP_OK; }
+    if (!sp) { h->spawn.on = false; h->treset.on = false; h->elog.on = false; return PP_OK; }
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_spawn: episodes are off (pp_set_episodes comes first: its capture is start record 0)");
     const int n = h->n_scenes, M = sp->n_starts;
     if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts must be 1 .. DMPP_EPISODE_MAX_STARTS");
@@ -2029,9 +2058,10 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     { int r = h->spawn.d_in[o].reserve(recs); if (r) return r; }
     { int r = h->spawn.d_state[o].reserve(recs); if (r) return r; }
     { int r = h->spawn.d_stats[o].reserve((size_t)h->caps.max_scenes); if (r) return r; }
-    const bool was_on = h->spawn.on, reset_was_on = h->treset.on;
+    const bool was_on = h->spawn.on, reset_was_on = h->treset.on, log_was_on = h->elog.on;
     h->spawn.on = false;                                  // (until everything below has landed: a failed copy leaves the spawn model off, not half a pool)
     h->treset.on = false;                                 // (the traffic reset of §4m reads cur_start of the model in force: it goes with it)
+    h->elog.on = false;                                   // (... and so does the episode log of §4n)
     SceneIn* pin = h->spawn.d_in[o]; SceneState* pst = h->spawn.d_state[o];
     HIP_TRY(hipMemcpyAsync(pin, h->episode.d_start_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(pst, h->episode.d_start_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
@@ -2053,7 +2083,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     }
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's arrays may go; the upload stream reads the pool from its next launch on
     if (bad) {
-        h->spawn.on = was_on; h->treset.on = reset_was_on;      // (nothing in force was touched)
+        h->spawn.on = was_on; h->treset.on = reset_was_on; h->elog.on = log_was_on;      // (nothing in force was touched)
         return fail(PP_ERR_ARG, "pp_set_episode_spawn: " + std::to_string(bad) + " start record(s) name a road or lane outside the map");
     }
     if (o != h->spawn.cur) {                              // the pool that was in force goes (nobody reads it: joined and waited above); its stats are 80 B a scene and stay
@@ -2127,6 +2157,73 @@ int pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n)
     PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_traffic_state
     if (h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
     return fetch(h, n_resets, h->treset.d_resets[h->treset.cur], (size_t)n * sizeof(int32_t));
+}
+
+// Episode log.  Everything is checked on the host before anything changes.
+int pp_set_episode_log(pp_handle h, int cap)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (cap < 0 || cap > DMPP_EPISODE_LOG_MAX) return fail(PP_ERR_ARG, "pp_set_episode_log: cap must be 0 .. DMPP_EPISODE_LOG_MAX");
+    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_log: an update is staged for the next tick (set the log before staging, or after the tick)");
+    if (cap == 0) { h->elog.on = false; return PP_OK; }
+    if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_log: episodes are off (pp_set_episodes comes first)");
+    HIP_TRY(hipSetDevice(h->device));
+    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged) ...
+    PP_TRY(h->rollout.adv.wait(h->stream));               // ... and the upload stream, which appends, is behind the last of them
+    const size_t ns = (size_t)h->caps.max_scenes;         // room first: a failed allocation changes nothing
+    { int r = h->elog.d_ring.reserve((size_t)cap); if (r) return r; }
+    { int r = h->elog.d_total.reserve(1); if (r) return r; }
+    { int r = h->elog.d_start_of.reserve(ns); if (r) return r; }
+    if (h->score.on) { int r = h->elog.d_score.reserve(ns); if (r) return r; }
+    HIP_TRY(hipMemsetAsync(h->elog.d_total, 0, sizeof(long long), h->stream));
+    static_assert(sizeof(EpisodeSpawnStats) == 80 && offsetof(EpisodeSpawnStats, cur_start) == 12, "cur_start is gathered out of the spawn stats");
+    if (h->spawn.on)      // the start record every running episode is on
+        HIP_TRY(hipMemcpy2DAsync(h->elog.d_start_of, sizeof(int32_t), &h->spawn.d_stats[h->spawn.cur].get()->cur_start, sizeof(EpisodeSpawnStats), sizeof(int32_t),
+                                 (size_t)h->n_scenes, hipMemcpyDeviceToDevice, h->stream));
+    else HIP_TRY(hipMemsetAsync(h->elog.d_start_of, 0, ns * sizeof(int32_t), h->stream));
+    if (h->elog.d_score) {
+        hipLaunchKernelGGL(dmpp::k_score_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, (int)ns, h->elog.d_score);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the upload stream reads all of it from its next launch on
+    h->elog.cap = cap; h->elog.seq = 0; h->elog.read = 0; h->elog.lost = 0; h->elog.on = true; h->elog.ever = true;
+    return PP_OK;
+}
+
+// records appended since the set call, a staged advance included (host wait)
+static int episode_log_total(pp_handle h, long long* total)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_episode_stats
+    return fetch(h, total, h->elog.d_total, sizeof(long long));
+}
+
+int pp_read_episode_log(pp_handle h, EpisodeRecord* out, int max_records, long long* n_lost)
+{
+    if (!h || max_records < 0 || (!out && max_records > 0)) return fail(PP_ERR_ARG, "pp_read_episode_log: null argument or negative count");
+    if (!h->elog.ever) return fail(PP_ERR_STATE, "pp_read_episode_log: pp_set_episode_log was never called on this handle");
+    long long total = 0;
+    { int r = episode_log_total(h, &total); if (r) return r; }
+    const long long cap = h->elog.cap, oldest = std::max(h->elog.read, total - cap), lost = oldest - h->elog.read;
+    const long long n = std::min(total - oldest, (long long)max_records);
+    const long long i0 = oldest % cap, n0 = std::min(n, cap - i0);      // the run up to the end of the ring, then the run from its start
+    if (n0 > 0) HIP_TRY(hipMemcpyAsync(out, h->elog.d_ring + i0, (size_t)n0 * sizeof(EpisodeRecord), hipMemcpyDeviceToHost, h->stream));
+    if (n > n0) HIP_TRY(hipMemcpyAsync(out + n0, h->elog.d_ring, (size_t)(n - n0) * sizeof(EpisodeRecord), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->elog.read = oldest + n; h->elog.lost += lost;
+    if (n_lost) *n_lost = lost;
+    return (int)n;
+}
+
+int pp_get_episode_log_info(pp_handle h, long long* total, long long* lost_total)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!h->elog.ever) return fail(PP_ERR_STATE, "pp_get_episode_log_info: pp_set_episode_log was never called on this handle");
+    long long t = 0;
+    { int r = episode_log_total(h, &t); if (r) return r; }
+    if (total) *total = t;
+    if (lost_total) *lost_total = h->elog.lost + std::max(0ll, t - (long long)h->elog.cap - h->elog.read);      // (what the next read will report included)
+    return PP_OK;
 }
 
 // A grid that follows the ego: host checks only; the model is a kernel argument of the next advance.
@@ -2493,6 +2590,7 @@ size_t pp_sizeof(int which)
     case 26: return sizeof(TrafficTrack); case 27: return sizeof(TrafficActor); case 28: return sizeof(TrafficFollow);
     case 29: return sizeof(EpisodeModel); case 30: return sizeof(EpisodeStats);
     case 31: return sizeof(EpisodeSpawn); case 32: return sizeof(EpisodeSpawnStats); case 33: return sizeof(TrafficStart);
+    case 34: return sizeof(EpisodeRecord);
     default: return 0;
     }
 }

@@ -10,6 +10,8 @@
 //                   consecutive ticks run on kBuf streams side by side, so every search stream counts into a part array of
 //                   its own (stream order serialises its ticks) and pp_get_rollout_score adds the parts into the records.
 //   k_score_reset : the starting values (+inf, -1: not all zero bits).
+//   score_fold    : steps 2. - 4. of §4d on one record: k_score_ego applies it to the scene's RolloutScore and - k_score_ego<true>,
+//                   while the episode log is on (§4n) - to the scorecard of the scene's running episode.
 #pragma once
 #include "dev_geom.hpp"
 
@@ -19,11 +21,9 @@ constexpr int kScScenes = 4;           // scenes (waves) per block of k_score_eg
 
 struct ScoreGridPart { int32_t n_grid_ticks, n_grid_path_candidate, status[DMPP_G_STATUS_COUNT]; };
 
-__global__ void __launch_bounds__(kBlock)
-k_score_reset(int n_scenes, RolloutScore* __restrict__ score)
+// §4d 0.: the starting values of a record
+__device__ __forceinline__ RolloutScore score_start()
 {
-    const int s = blockIdx.x * kBlock + threadIdx.x;
-    if (s >= n_scenes) return;
     RolloutScore r;
     r.min_clearance = __builtin_huge_val(); r.dist = 0; r.max_speed = 0; r.max_acc = 0; r.max_dec = 0;
     r.last_pos.x = 0; r.last_pos.y = 0; r.last_speed = 0;
@@ -32,33 +32,22 @@ k_score_reset(int n_scenes, RolloutScore* __restrict__ score)
     for (int k = 0; k < 8; k++) r.behavior_ticks[k] = 0;
     r.ego_flags = 0; r._pad = 0; r.n_grid_ticks = 0; r.n_grid_path_candidate = 0;
     for (int k = 0; k < DMPP_G_STATUS_COUNT; k++) r.grid_status_ticks[k] = 0;
-    score[s] = r;
+    return r;
 }
 
-// obs_cap: entries of a snapshot set; a slice outside it (no set call and no update lets one through) counts as empty.
 __global__ void __launch_bounds__(kBlock)
-k_score_ego(double half_width, double dt_score, int n_scenes, int obs_cap, const SceneIn* __restrict__ in, const PlanOut* __restrict__ plan,
-            const SceneState* __restrict__ state, const ObPoint* __restrict__ now, const int32_t* __restrict__ flags,
-            RolloutScore* __restrict__ score)
+k_score_reset(int n_scenes, RolloutScore* __restrict__ score)
 {
-    const int lane = threadIdx.x & 63;
-    const int s = blockIdx.x * kScScenes + (threadIdx.x >> 6);
-    if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
-    const SceneIn& si = in[s];
-    const double x = si.loc.globalpoint.x, y = si.loc.globalpoint.y, v = si.loc.velocity;
-    const int off = si.obs_off;
-    int m = si.obs_n;
-    if (off < 0 || m < 0 || (long long)off + (long long)m > (long long)obs_cap) m = 0;
-    // 1. the nearest obstacle edge: first index of the smallest d_j, a NaN is never the minimum
-    double md = 0; int mi = -1;
-    for (int j = lane; j < m; j += 64) {
-        const ObPoint o = now[off + j];
-        const double dx = o.x - x, dy = o.y - y;
-        const double d = sqrt(dx * dx + dy * dy) - (double)o.radius;
-        if (d == d && (mi < 0 || d < md)) { md = d; mi = j; }
-    }
-    wave_first_min(md, mi);
-    if (lane != 0) return;
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_scenes) return;
+    score[s] = score_start();
+}
+
+// §4d 2. - 4.: one scored tick of scene s folded into record s of `score` (lane 0 of the scene's wave).  x, y, v: the ego of the tick;
+// (md, mi): its nearest obstacle edge, mi < 0 without one; plan, state, flags: as k_score_ego.
+__device__ __forceinline__ void score_fold(RolloutScore* __restrict__ score, int s, double x, double y, double v, double md, int mi, double half_width, double dt_score,
+                                           const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const int32_t* __restrict__ flags)
+{
     RolloutScore& r = score[s];
     const int k = r.n_ticks;                            // this tick's index among the scored ones
     // 2. clearance and collisions
@@ -89,6 +78,37 @@ k_score_ego(double half_width, double dt_score, int n_scenes, int obs_cap, const
     r.behavior_ticks[b] = r.behavior_ticks[b] + 1;
     r.ego_flags = flags ? flags[s] : 0;
     r.n_ticks = k + 1;
+}
+
+// obs_cap: entries of a snapshot set; a slice outside it (no set call and no update lets one through) counts as empty.
+// kLog: the episode log is on and the tick is folded a second time, into the scorecard of the scene's running
+// episode, ep_score[s]; without it ep_score is null and never read.
+template <bool kLog>
+__global__ void __launch_bounds__(kBlock)
+k_score_ego(double half_width, double dt_score, int n_scenes, int obs_cap, const SceneIn* __restrict__ in, const PlanOut* __restrict__ plan,
+            const SceneState* __restrict__ state, const ObPoint* __restrict__ now, const int32_t* __restrict__ flags,
+            RolloutScore* __restrict__ score, RolloutScore* __restrict__ ep_score)
+{
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * kScScenes + (threadIdx.x >> 6);
+    if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
+    const SceneIn& si = in[s];
+    const double x = si.loc.globalpoint.x, y = si.loc.globalpoint.y, v = si.loc.velocity;
+    const int off = si.obs_off;
+    int m = si.obs_n;
+    if (off < 0 || m < 0 || (long long)off + (long long)m > (long long)obs_cap) m = 0;
+    // 1. the nearest obstacle edge: first index of the smallest d_j, a NaN is never the minimum
+    double md = 0; int mi = -1;
+    for (int j = lane; j < m; j += 64) {
+        const ObPoint o = now[off + j];
+        const double dx = o.x - x, dy = o.y - y;
+        const double d = sqrt(dx * dx + dy * dy) - (double)o.radius;
+        if (d == d && (mi < 0 || d < md)) { md = d; mi = j; }
+    }
+    wave_first_min(md, mi);
+    if (lane != 0) return;
+    score_fold(score, s, x, y, v, md, mi, half_width, dt_score, plan, state, flags);
+    if (kLog) score_fold(ep_score, s, x, y, v, md, mi, half_width, dt_score, plan, state, flags);
 }
 
 __global__ void __launch_bounds__(kBlock)

@@ -28,6 +28,9 @@
 // (pp_set_episode_traffic): with --contact the run of §4l loses its episodes of age 1 - no ego restarts into the vehicle
 // that drove on over its start pose -, and with --starts M every start record has its own set: the vehicle at its offset from THAT record.
 // The host prints the resets and the shortest episode.
+// With --route --episodes --log N the episode log is on (pp_set_episode_log): a ring of N records on the device, one
+// record appended per ended episode, drained once behind the run; the scorecard is on, so every record carries its episode's own.
+// The host prints an outcome table per start record: episodes, causes, mean age and metres, worst clearance, episodes with a collision.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -41,7 +44,7 @@
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap)
 {
     const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
     if (contact) traffic = true;                      // (the vehicle to touch)
@@ -156,6 +159,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         if (react) { TrafficFollow tf; pp_default_traffic_follow(&tf); CHECK(pp_set_traffic_follow(h, &tf)); }
         CHECK(pp_score_begin(h, model.dt));
     }
+    if (log_cap && !traffic) CHECK(pp_score_begin(h, model.dt));      // (the records carry their episode's scorecard)
     if (episodes) { EpisodeModel em; pp_default_episode_model(&em); CHECK(pp_set_episodes(h, &em)); }      // last: it captures what the calls above set up
     if (spawn) {                                      // M start records per ego: record k stands 5 k lane points behind record 0, on the same lane
         EpisodeSpawn sp; pp_default_episode_spawn(&sp); sp.n_starts = M; sp.contact = contact ? 1 : 0;
@@ -176,9 +180,35 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         }
         CHECK(pp_set_episode_traffic(h, M, M > 1 ? sets.data() : nullptr));
     }
+    if (log_cap) CHECK(pp_set_episode_log(h, log_cap));      // last of all
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
+    if (log_cap) {
+        std::vector<EpisodeRecord> rec((size_t)log_cap);
+        long long lost = 0, total = 0;
+        const int got = pp_read_episode_log(h, rec.data(), log_cap, &lost);
+        if (got < 0) { std::fprintf(stderr, "pp_read_episode_log: %s\n", pp_last_error()); return 2; }
+        CHECK(pp_get_episode_log_info(h, &total, nullptr));
+        std::printf("log: %lld records appended to a ring of %d, %d read, %lld overwritten unread; per start record:\n", total, log_cap, got, lost);
+        static const char* const bit[8] = { "PATH_END", "BAD_PATH", "LANE_END", "OFF_GRID", "ROUTE_END", "-", "TIMEOUT", "CONTACT" };
+        for (int k = 0; k < M; k++) {
+            long long eps = 0, by[8] = {}, age = 0, hit = 0; double metres = 0, worst = INFINITY;
+            for (int i = 0; i < got; i++) {
+                const EpisodeRecord& r = rec[(size_t)i];
+                if (r.start != k) continue;
+                eps++; age += r.age; metres += r.dist; hit += r.score.n_collision_ticks > 0;
+                if (r.score.min_clearance < worst) worst = r.score.min_clearance;
+                for (int b = 0; b < 8; b++) by[b] += (r.cause >> b) & 1;
+            }
+            std::printf("log:   start %d: %lld episodes", k, eps);
+            if (eps) {
+                std::printf(", mean age %.1f advances, mean %.1f m, worst clearance %.2f m, %lld with a collision; causes:", (double)age / eps, metres / eps, worst, hit);
+                for (int b = 0; b < 8; b++) if (by[b]) std::printf(" %s %lld", bit[b], by[b]);
+            }
+            std::printf("\n");
+        }
+    }
     if (episodes) {
         static const char* const cause[6] = { "PATH_END", "BAD_PATH", "LANE_END", "OFF_GRID", "ROUTE_END", "TIMEOUT" };
         std::vector<EpisodeStats> es(n);
@@ -263,7 +293,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0, log_cap = 0;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -275,7 +305,8 @@ int main(int argc, char** argv)
         else if (std::strcmp(argv[a], "--contact") == 0) contact = true;
         else if (std::strcmp(argv[a], "--reset-traffic") == 0) reset = true;
         else if (std::strcmp(argv[a], "--starts") == 0 && a + 1 < argc) starts = std::atoi(argv[++a]);
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--reset-traffic]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--log") == 0 && a + 1 < argc) log_cap = std::atoi(argv[++a]);
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
@@ -287,7 +318,9 @@ int main(int argc, char** argv)
     if (starts && shared) { std::fprintf(stderr, "--starts places its records behind each ego on its lane: not with the platoons of --shared\n"); return 2; }
     if (reset && !(route && episodes && (traffic || contact))) { std::fprintf(stderr, "--reset-traffic puts a restarted ego's vehicle back: use it with --route --episodes --traffic (or --contact)\n"); return 2; }
     if (reset && shared) { std::fprintf(stderr, "--reset-traffic resets per-scene traffic: a vehicle of --shared belongs to a whole world\n"); return 2; }
-    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset);
+    if (log_cap && !(route && episodes)) { std::fprintf(stderr, "--log records how episodes ended: use it with --route --episodes\n"); return 2; }
+    if (log_cap < 0 || log_cap > DMPP_EPISODE_LOG_MAX) { std::fprintf(stderr, "--log takes 1 .. %d records\n", DMPP_EPISODE_LOG_MAX); return 2; }
+    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

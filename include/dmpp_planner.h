@@ -431,6 +431,34 @@ int  pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n_scene
 int  pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts);
 int  pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n);
 
+/* ---- episode log: one record per ended episode, appended on the device ---------------------------------------------
+ * EpisodeStats is an aggregate per scene and RolloutScore runs across restarts: neither says which episode ended how.  pp_set_episode_log
+ * gives the handle a ring of cap EpisodeRecord on the device and switches the log on: from then on every pp_advance_async runs one
+ * more kernel on the upload stream (k_log_episodes, ONE workgroup of 1024 threads) directly behind k_respawn_egos / k_respawn_spawn, in front of the
+ * traffic kernels.  It appends one record for every scene whose episode the advance ended (EpisodeStats.age == 0 behind the episode
+ * step): scene, episode number, start record, cause, age, metres, the pose and speed of the record the ending advance READ, the number
+ * of the advance (seq, counted from the set call) and of the tick it read, and the episode's OWN scorecard.  The records of one advance
+ * stand in the order of their scene indices, those of successive advances behind each other - a scan, not a race for a counter - so a
+ * log is reproducible byte for byte.  With more endings in one advance than the ring holds only the last cap are written.
+ * The episode's scorecard: while the log AND the scorecard (pp_score_begin) are on, every scored tick is folded a second time
+ * (k_score_ego<true>, §4d steps 2 - 4) into a record per scene that restarts - to the starting values of §4d - whenever the scene's
+ * episode ends, pp_score_begin is called or a set call restarts the totals.  Its grid half stays at the starting values.  Without
+ * pp_score_begin the record carries the starting values (n_ticks == 0).
+ * CALL IT LAST: every successful pp_set_episodes / pp_set_episode_spawn (NULL included), and pp_set_scenes / pp_set_egos /
+ * pp_set_n_scenes through them, switch the log off.  cap == 0: the log off; what was logged stays readable.  A second call with
+ * cap > 0 starts a new log (total 0, seq 0, nothing unread).  PP_ERR_ARG: cap < 0 or > DMPP_EPISODE_LOG_MAX.  PP_ERR_STATE: an update
+ * staged for the next tick; cap > 0 with episodes off.  A refused call changes nothing.  One host wait, behind every tick and advance
+ * enqueued so far.  A handle that never makes the call allocates and launches none of this.
+ * pp_read_episode_log: waits for a staged advance as pp_get_episode_stats does, then copies the oldest unread records still in the ring,
+ * at most max_records of them, oldest first (at most two copies), marks them read and returns their number (>= 0; an error code is
+ * negative).  *n_lost (may be NULL): records that were overwritten before any read saw them, newly counted by this call.  What does
+ * not fit into max_records stays unread.  PP_ERR_STATE on a handle that never made the set call.
+ * pp_get_episode_log_info: *total - records appended since the set call; *lost_total - records overwritten unread so far, those the
+ * next read will report included.  Either may be NULL.  Waits as pp_read_episode_log does. */
+int  pp_set_episode_log(pp_handle h, int cap);
+int  pp_read_episode_log(pp_handle h, EpisodeRecord* out, int max_records, long long* n_lost);
+int  pp_get_episode_log_info(pp_handle h, long long* total, long long* lost_total);
+
 /* ---- one scene, one call, one host wait: the latency path of the class surface ------------------------------------------
  * CPlanning::plan(...) / CDecision::decide(...) take everything by value on every call (Planning.h:57-75) and own the
  * cross-tick state as members.  A PpSceneIo block (pinned host memory: pp_host_alloc(sizeof(PpSceneIo))) carries exactly that

@@ -400,6 +400,22 @@ typedef struct TrafficStart {
     double s, v;                /* arc length (m, wrapped / clamped onto the actor's track); speed (m/s, finite, >= 0) */
 } TrafficStart;                                                             /* 16 B */
 
+/* ---- episode log (build-defined), on top of pp_set_episodes ------------------------------------------
+ * pp_set_episode_log makes every advance append one record per episode it ended to a ring on the device - in the order of the
+ * scene indices, whatever the scheduling - which the host drains whenever it likes (pp_read_episode_log).  No heading: it is
+ * the one field the device and the host round differently (§4c), and a record is comparable byte for byte. */
+#define DMPP_EPISODE_LOG_MAX (1 << 20)
+typedef struct EpisodeRecord {
+    int32_t scene, episode;     /* scene index; number of this episode within the scene, 0-based (EpisodeStats.n_episodes - 1 behind the restart) */
+    int32_t start, cause;       /* start record the ENDED episode ran on (0 without a spawn model); cause word (DMPP_EGO_* | TIMEOUT | CONTACT) */
+    int32_t age, seq;           /* advances of the episode; number of the advance that ended it, counted from pp_set_episode_log (first = 0) */
+    int64_t tick;               /* pp_tick_id of the last tick of the episode: the tick the ending advance read */
+    double  dist;               /* EpisodeStats.last_dist */
+    GlobalPoint2D end_pos;      /* loc.globalpoint.x / .y of the SceneIn record the ending advance READ */
+    double  end_speed;          /* its loc.velocity, km/h */
+    RolloutScore score;         /* the episode's own scorecard: the front half of §4d over the episode's scored ticks; starting values without pp_score_begin */
+} EpisodeRecord;                                                            /* 240 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

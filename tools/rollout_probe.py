@@ -29,7 +29,10 @@ EPISODES=1 RESET=1 (with SPAWN=M and / or CONTACT=1): both legs have that spawn 
 well (pp_set_episode_traffic, DESIGN.md §4m: k_reset_traffic behind k_move_traffic) - with M > 1 one set of start states per start record,
 the vehicle 20 m ahead of that record along its own track.  The workloads differ: without the reset the egos spend advances restarting
 into the vehicle that drove on over their start pose (the egos with an episode of age 1 are printed); k_reset_traffic's own cost is
-what a kernel trace of the ONE_ROLLOUT leg gives."""
+what a kernel trace of the ONE_ROLLOUT leg gives.
+EPISODES=1 LOG=cap: both legs are the ring rollout with episodes on, and the second leg has the episode log on as well
+(pp_set_episode_log(cap), DESIGN.md §4n: k_log_episodes behind k_respawn_egos); it is drained once behind the timed rollout, outside the
+timing.  SCORE=1 puts the scorecard on in both legs (k_score_ego<true> in the second).  With ONE_ROLLOUT one more leg with the log on alone."""
 import os
 import statistics
 import sys
@@ -150,7 +153,10 @@ def route_run(on):
     return n * steps / dt, frozen
 
 
-def episodes_run(on):
+LOG = int(os.environ.get("LOG", "0"))
+
+
+def episodes_run(on, log=0):
     import route_scenes as rs
     rcfg = dm.default_config(128)
     rcfg["grid_stage"] = 0
@@ -161,8 +167,12 @@ def episodes_run(on):
     pl.set_egos(sc, with_motion=False)
     pl.set_state(sc["state"])
     pl.set_route(legs, rf)
+    if LOG > 0 and SCORE == "1":
+        pl.score_begin()
     if on:
         pl.set_episodes()
+    if log > 0:
+        pl.set_episode_log(log)           # last
     pl.rollout(warm, model)
     pl.sync()
     t0 = time.perf_counter()
@@ -171,6 +181,9 @@ def episodes_run(on):
     dt = time.perf_counter() - t0
     frozen = int((pl.ego_flags() != 0).sum())
     ended = int(pl.episode_stats()["n_episodes"].sum()) if on else 0
+    if log > 0:
+        recs, lost = pl.read_episode_log()
+        episodes_run.logged = (pl.episode_log_info()[0], len(recs), lost)
     pl.close()
     return n * steps / dt, frozen, ended
 
@@ -367,6 +380,20 @@ if os.environ.get("EPISODES", "0") == "1" and (SPAWN > 0 or CONTACT):
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with the spawn model alone
         spawn_run(True)
+    sys.exit(0)
+if os.environ.get("EPISODES", "0") == "1" and LOG > 0:
+    off, on = [], []
+    for r in range(runs):
+        a, _, ea = episodes_run(True)
+        b, _, eb = episodes_run(True, LOG)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos, one-leg routes, episodes on%s  log off %.3f M ticks/s (%d episodes ended)   log on (cap %d) %.3f M ticks/s (%d episodes ended; "
+              "%d records appended, %d read, %d lost)" % ((r, n, ", scorecard on" if SCORE == "1" else "", a / 1e6, ea, LOG, b / 1e6, eb) + episodes_run.logged), flush=True)
+    print("median  %d ring egos  log off %.3f M ticks/s (spread %.3f)   log on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with the log alone
+        episodes_run(True, LOG)
     sys.exit(0)
 if os.environ.get("EPISODES", "0") == "1":
     off, on = [], []
