@@ -2361,6 +2361,13 @@ int pp_debug_score_counters(int* out8, int reset)          // debug build only (
     if (reset) { int z[8] = { 0 }; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(dmpp::g_dbg_score), z, sizeof(z))); }
     return PP_OK;
 }
+int pp_debug_score_stamps(unsigned* out, int n_items)      // debug build only (tools/dbg_score_timing.py): [n_items][kDbgScorePhases] cycles
+{
+    if (!out || n_items < 0 || n_items > dmpp::kDbgScoreItems) return fail(PP_ERR_ARG, "pp_debug_score_stamps: bad argument");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(dmpp::g_dbg_score_ph), (size_t)n_items * dmpp::kDbgScorePhases * sizeof(unsigned)));
+    return PP_OK;
+}
 #endif
 
 void* pp_host_alloc(size_t bytes)

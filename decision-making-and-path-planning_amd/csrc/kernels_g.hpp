@@ -49,6 +49,12 @@ k_score(PlannerConfig c, int n_items, const TickGroup g, int32_t* __restrict__ n
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     ScoreShared<NW>& sh = *reinterpret_cast<ScoreShared<NW>*>(smem_raw);
+#ifdef DMPP_DEBUG_SEARCH
+    const long long dbg_t0 = clock64();        // phase stamps of score_body count from here
+#define SCORE_DBG_ARG , dbg_t0
+#else
+#define SCORE_DBG_ARG
+#endif
     const int w = blockIdx.x;                  // work item: scene w % n of tick slot w / n (TickGroup)
     if (w == 0 && threadIdx.x == 0 && need_dev) {
         const int32_t v = need_dev[0];
@@ -63,7 +69,7 @@ k_score(PlannerConfig c, int n_items, const TickGroup g, int32_t* __restrict__ n
     const int slot = w / g.n, scene = w - slot * g.n;
     const SceneIn& si = g.in[scene];
     GridOut& go = g.gout[slot * g.gout_stride + scene];
-    score_body<NW>(c, si, g.obs_now + slot * g.obs_stride + si.obs_off, si.obs_n, g.paths + slot * g.path_stride + (size_t)scene * c.max_path, go, go.status, go.path_len, sh);
+    score_body<NW>(c, si, g.obs_now + slot * g.obs_stride + si.obs_off, si.obs_n, g.paths + slot * g.path_stride + (size_t)scene * c.max_path, go, go.status, go.path_len, sh SCORE_DBG_ARG);
 }
 
 }  // namespace dmpp

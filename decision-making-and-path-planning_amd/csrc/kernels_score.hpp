@@ -1,5 +1,8 @@
 // kernels_score.hpp — G3: candidate scoring (specification: DESIGN.md §5, oracle/dmpp_grid_oracle.c).  One device function,
-// used by the search kernel for the scene it has just searched (all waves of the workgroup) and by the stand-alone k_score.
+// score_body, called by the stand-alone k_score (kernels_g.hpp) for one scene per workgroup; the search kernel does not score.
+// A candidate's points are never stored: a lane computes its own point of the current pass and takes the neighbours i - 1 and
+// i + 1 of the curvature term from the adjacent lanes (a whole-wave DPP shift), so the workgroup's LDS holds only what the
+// candidates are made from: 10 granules of 1,280 bytes, two scoring workgroups in the room a retiring search leaves.
 #pragma once
 #include "dev_geom.hpp"
 
@@ -9,10 +12,9 @@ namespace dmpp {
 // NW waves per scene score the candidates NW at a time: 4 for batches (four scenes per CU), 16 for the few scenes of a
 // latency-bound tick (17 candidates in 2 rounds instead of 5).
 constexpr int kBoxWaves = 4;
-constexpr int kTailRounds = 4, kTailFirst = 190;      // packed fourth pass: candidates per wave, first point kept for it
+constexpr int kTailRounds = 4;                        // packed fourth pass: candidates per wave
 template <int NW> constexpr bool kPackTail = NW <= 4;
-template <int NW> constexpr int kTailWaves = NW <= 4 ? NW : 1;
-static_assert(DMPP_PATH_POINTS - 192 == 8 && kTailFirst == 190 && kTailRounds * 8 <= DMPP_WAVE, "packed fourth pass: lane 8 c + j = point 192 + j of candidate c");
+static_assert(DMPP_PATH_POINTS - 192 == 8 && kTailRounds * 8 <= DMPP_WAVE, "packed fourth pass: lane 8 c + j = point 192 + j of candidate c");
 static_assert(DMPP_PATH_POINTS <= kBoxWaves * DMPP_WAVE && DMPP_MAX_LATTICE <= 32, "score_body: lane layouts");
 constexpr int kMaxRelObs = 128;      // culled obstacle list kept in LDS; a scene with more candidates near its paths reads the whole list from HBM
 // Many obstacles near the candidates (256-obstacle scenes keep ~10 - 30 after the cull): a coarse bucket grid over the box of
@@ -22,24 +24,60 @@ constexpr int kMaxRelObs = 128;      // culled obstacle list kept in LDS; a scen
 constexpr int kBucketN = 12, kBucketCap = 12, kBucketMinObs = 8;
 #ifdef DMPP_DEBUG_SEARCH
 __device__ int g_dbg_score[8];       // debug build: scenes scored, sum of n_rel, bucketed, bucket overflow, not culled, max n_rel
+// debug build: cycles since the kernel's first instruction, thread 0 of each work item, at the END of each phase (tools/dbg_score_timing.py):
+// 0 entry (score_body reached), 1 inputs landed (path prefix converted), 2 set-up (terminal pose, sincos, wave_cumlen, lattice),
+// 3 cull and buckets, 4 whole candidates, 5 packed pass, 6 left-over candidate, 7 winner and stores (= total)
+constexpr int kDbgScoreItems = 4096, kDbgScorePhases = 8;
+__device__ unsigned g_dbg_score_ph[kDbgScoreItems][kDbgScorePhases];
+#define SCORE_MARK(slot) { if (threadIdx.x == 0 && blockIdx.x < kDbgScoreItems) g_dbg_score_ph[blockIdx.x][slot] = (unsigned)(clock64() - dbg_t0); }
+#define SCORE_DBG_PARAM , long long dbg_t0
+#else
+#define SCORE_MARK(slot)
+#define SCORE_DBG_PARAM
 #endif
+// What point_terms reads about the obstacles: the culled list and the bucket grid over it, contiguous.
+struct ScoreLists {
+    double rx[kMaxRelObs], ry[kMaxRelObs], rr[kMaxRelObs], rt2[kMaxRelObs];   // obstacles that can matter: x, y, radius, cutoff^2
+    int bcnt[kBucketN * kBucketN];                             // bucket fill counts (beyond kBucketCap: the bucket's points take the plain loop)
+    unsigned char bent[kBucketN * kBucketN][kBucketCap];       // indices into rx / ry / rr / rt2
+};
+// Per-lane partial sums of one quarter of a left-over candidate (one wave's).  They are written once every wave is past its
+// last point_terms - the lists above are dead by then - and so lie over them.
+struct ScorePart { double pen[DMPP_WAVE], k2[DMPP_WAVE]; int hit[DMPP_WAVE]; };
 template <int NW>
 struct ScoreShared {
-    GlobalPoint2D cand[NW][DMPP_PATH_POINTS];
     GlobalPoint2D pts[DMPP_PATH_POINTS];     // grid-path prefix in metres (lookahead_cells+1 <= 200)
     double cum[DMPP_PATH_POINTS];
-    double rx[kMaxRelObs], ry[kMaxRelObs], rr[kMaxRelObs], rt2[kMaxRelObs];   // obstacles that can matter: x, y, radius, cutoff^2
+    union { ScoreLists ls; ScorePart part[NW]; };              // (16 waves: the partial sums are the larger member)
     Bezier bz[DMPP_MAX_LATTICE];             // control points of the lattice candidates
     double trig[4];                          // cos, sin of the start heading; cos, sin of the terminal heading
     double bb[4];                            // box of all lattice candidates: x0, x1, y0, y1
     GlobalPoint2D T;                         // terminal point
     double cost[DMPP_MAX_LATTICE];
     int box[4][4];                           // per wave: min / max cell column and row of the grid-path prefix
-    GlobalPoint2D tail[kTailWaves<NW>][kTailRounds][DMPP_PATH_POINTS - kTailFirst];   // points 190 .. 199 of a wave's candidates (packed fourth pass)
     int best, n_rel;
-    int bcnt[kBucketN * kBucketN];                             // bucket fill counts (beyond kBucketCap: the bucket's points take the plain loop)
-    unsigned char bent[kBucketN * kBucketN][kBucketCap];       // indices into rx / ry / rr / rt2
 };
+static_assert(sizeof(ScorePart) * 4 <= sizeof(ScoreLists), "k_score<4>: the partial sums of the left-over candidate fit over the obstacle lists and buckets");
+// A searching workgroup of the configs[1] budget holds 21 LDS granules of 1,280 bytes and six of them leave 2 of a CU's 128 free:
+// a retiring search frees room for 23 granules, which is TWO scoring workgroups at 11 granules each (one at 12 or more).
+static_assert(sizeof(ScoreShared<4>) <= 11 * 1280, "k_score<4>: two workgroups per freed search slot at the configs[1] budget");
+
+// The value of the lane below / above in the wave; lane 0 / lane 63 keep their own.  A whole-wave DPP shift (wave_shr:1: lane l
+// reads lane l - 1; wave_shl:1: lane l + 1) is one v_mov per dword, against an LDS-crossbar permute with its address and its wait.
+__device__ __forceinline__ double lane_below_f64(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double lane_above_f64(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
 
 __device__ __forceinline__ double wave_tree_sum(double acc)
 {
@@ -52,12 +90,23 @@ __device__ __forceinline__ double wave_tree_sum(double acc)
 // `path_len` are the search's results for the scene, `path` its cells, `gobs` / `m` the obstacle snapshot of the tick.
 template <int NW>
 __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn& si, const ObPoint* __restrict__ gobs, int m,
-                                           const int32_t* __restrict__ path, GridOut& go, int status, int path_len, ScoreShared<NW>& sh)
+                                           const int32_t* __restrict__ path, GridOut& go, int status, int path_len, ScoreShared<NW>& sh SCORE_DBG_PARAM)
 {
+    SCORE_MARK(0)
     constexpr int kThreads = NW * DMPP_WAVE;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int W = c.grid_w;
+    // Every global input is requested here, before the first of them is waited for: the scene's record, (in the caller) the
+    // search's status and path length, the cell of the path prefix this thread would convert - whether or not there is a path:
+    // the buffer holds max_path cells per scene, and without a path the value is not used - and the thread's obstacle record,
+    // which the cull reads two barriers further down.  One round trip to memory instead of three dependent ones.
+    static_assert(DMPP_PATH_POINTS <= kThreads, "one cell of the path prefix per thread");
     const GlobalPoint3D ego = si.loc.globalpoint;
+    const GlobalPoint2D org = si.grid_origin, goal = si.goal;
+    int pc_mine = 0;
+    if (tid <= min(c.lookahead_cells, DMPP_PATH_POINTS - 1) && tid < c.max_path) pc_mine = path[tid];
+    ObPoint o_mine; o_mine.x = 0; o_mine.y = 0; o_mine.radius = 0;
+    if (tid < m) o_mine = gobs[tid];
     const bool have_path = (status == DMPP_G_FOUND) && path_len >= 1;
     const int nl = min(c.n_lattice, DMPP_MAX_LATTICE - 1);
     const int nc = nl + (have_path ? 1 : 0);
@@ -68,12 +117,11 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
         if (a > DMPP_PATH_POINTS - 1) a = DMPP_PATH_POINTS - 1;
         // the prefix in metres, and the box of its cells (per wave here, combined below): the path candidate lies inside it
         int cx0 = 0x7fffffff, cx1 = -1, cy0 = 0x7fffffff, cy1 = -1;
-        for (int i = tid; i <= a; i += kThreads) {
-            const int pc = path[i];
-            const int px = pc % W, py = pc / W;
-            sh.pts[i].x = si.grid_origin.x + ((double)px + 0.5) * c.cell;
-            sh.pts[i].y = si.grid_origin.y + ((double)py + 0.5) * c.cell;
-            cx0 = min(cx0, px); cx1 = max(cx1, px); cy0 = min(cy0, py); cy1 = max(cy1, py);
+        if (tid <= a) {                    // (a < path_len <= max_path: the cell was read)
+            const int px = pc_mine % W, py = pc_mine / W;
+            sh.pts[tid].x = org.x + ((double)px + 0.5) * c.cell;
+            sh.pts[tid].y = org.y + ((double)py + 0.5) * c.cell;
+            cx0 = px; cx1 = px; cy0 = py; cy1 = py;
         }
         if (wave < kBoxWaves) {            // DMPP_PATH_POINTS <= 256 points: only the first four waves hold any
 #pragma unroll
@@ -84,38 +132,36 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
             if (lane == 0) { sh.box[wave][0] = cx0; sh.box[wave][1] = cx1; sh.box[wave][2] = cy0; sh.box[wave][3] = cy1; }
         }
     }
-    // What is the same for every candidate is computed ONCE, by the last wave (the others have the path prefix to convert):
-    // the terminal pose, and the sine and cosine of the start and terminal headings - lane 0 takes the start heading, lane 1
-    // the terminal one, so one pass through sincos yields all four values.
+    SCORE_MARK(1)
+    __syncthreads();                       // the prefix is in LDS
+    // Between this barrier and the next, side by side: wave 0 sums the arc lengths of the prefix (lane 0's in-order sum of up to
+    // 120 lengths, which only the grid-path candidate and a winning grid path need), and the last wave computes what is the
+    // same for every candidate - the terminal pose, the sine and cosine of the start and terminal headings (lane 0 takes the
+    // start heading, lane 1 the terminal one, so one pass through sincos yields all four values) - and then the lattice.
+    if (have_path && wave == 0) wave_cumlen(sh.pts, a + 1, sh.cum, lane);
     if (wave == NW - 1) {
         GlobalPoint2D T; double thT;
         if (have_path) {
+            // the terminal is the prefix's last cell and the baseline starts four cells before it: sh.pts holds both, by the
+            // expressions that would convert the cells here
             const int a0 = max(a - 4, 0);
-            const int pa = path[a], p0 = path[a0];
-            T.x = si.grid_origin.x + ((double)(pa % W) + 0.5) * c.cell;
-            T.y = si.grid_origin.y + ((double)(pa / W) + 0.5) * c.cell;
+            T = sh.pts[a];
             if (a0 == a) thT = ego.dir;
-            else {
-                GlobalPoint2D P0 = { si.grid_origin.x + ((double)(p0 % W) + 0.5) * c.cell, si.grid_origin.y + ((double)(p0 / W) + 0.5) * c.cell };
-                thT = GetRoadAngle(c, P0, T);
-            }
+            else thT = GetRoadAngle(c, sh.pts[a0], T);
         } else {
-            T = si.goal;
+            T = goal;
             GlobalPoint2D e2 = { ego.x, ego.y };
-            thT = GetRoadAngle(c, e2, si.goal);
+            thT = GetRoadAngle(c, e2, goal);
         }
         const double ang = (lane == 0 ? ego.dir : thT) * c.PI / 180;
         double sv, cv;
         sincos(ang, &sv, &cv);
         if (lane == 0) { sh.trig[0] = cv; sh.trig[1] = sv; sh.T = T; }
         if (lane == 1) { sh.trig[2] = cv; sh.trig[3] = sv; }
-    }
-    __syncthreads();
-    if (have_path && wave == 0) wave_cumlen(sh.pts, a + 1, sh.cum, lane);
-    // ---- the lattice: candidate k is the cubic Bezier of BezierPlanning(ego -> terminal k) (as bezier_setup); lane k of the
-    //      last wave sets it up for every wave to read.  Obstacles that can matter at all lie inside the box of every candidate
-    //      grown by their cutoff: a Bezier lies in the hull of its control points. ----
-    if (wave == NW - 1) {
+        wave_sync();                       // (the same wave reads them back)
+        // ---- the lattice: candidate k is the cubic Bezier of BezierPlanning(ego -> terminal k) (as bezier_setup); lane k of the
+        //      last wave sets it up for every wave to read.  Obstacles that can matter at all lie inside the box of every candidate
+        //      grown by their cutoff: a Bezier lies in the hull of its control points. ----
         double X0 = __builtin_inf(), X1 = -__builtin_inf(), Y0 = __builtin_inf(), Y1 = -__builtin_inf();
         if (lane < nl) {
             const double c0 = sh.trig[0], s0 = sh.trig[1], cs = sh.trig[2], sn = sh.trig[3];
@@ -139,6 +185,7 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
         if (lane == 0) { sh.bb[0] = X0; sh.bb[1] = X1; sh.bb[2] = Y0; sh.bb[3] = Y1; sh.n_rel = 0; }
     }
     __syncthreads();
+    SCORE_MARK(2)
     double X0 = sh.bb[0], X1 = sh.bb[1], Y0 = sh.bb[2], Y1 = sh.bb[3];
     if (have_path) {
         // the box of the path's own cells (not a box around the ego: an ego outside the grid is clamped to a border cell),
@@ -147,17 +194,18 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
         for (int w = 0; w < (NW < kBoxWaves ? NW : kBoxWaves); w++) {
             cx0 = min(cx0, sh.box[w][0]); cx1 = max(cx1, sh.box[w][1]); cy0 = min(cy0, sh.box[w][2]); cy1 = max(cy1, sh.box[w][3]);
         }
-        X0 = fmin(X0, si.grid_origin.x + ((double)cx0 - 0.5) * c.cell); X1 = fmax(X1, si.grid_origin.x + ((double)cx1 + 1.5) * c.cell);
-        Y0 = fmin(Y0, si.grid_origin.y + ((double)cy0 - 0.5) * c.cell); Y1 = fmax(Y1, si.grid_origin.y + ((double)cy1 + 1.5) * c.cell);
+        X0 = fmin(X0, org.x + ((double)cx0 - 0.5) * c.cell); X1 = fmax(X1, org.x + ((double)cx1 + 1.5) * c.cell);
+        Y0 = fmin(Y0, org.y + ((double)cy0 - 0.5) * c.cell); Y1 = fmax(Y1, org.y + ((double)cy1 + 1.5) * c.cell);
     }
     // the obstacles near the candidates, collected in LDS (kMaxRelObs of them); when more qualify, the scoring loop reads the
-    // whole list from HBM instead (the same minimum over the same thresholds either way)
+    // whole list from HBM instead (the same minimum over the same thresholds either way).  A thread's first record was
+    // requested at the top: up to kThreads obstacles there is nothing left to load here.
     for (int j = tid; j < m; j += kThreads) {
-        const ObPoint o = gobs[j];
+        const ObPoint o = j == tid ? o_mine : gobs[j];
         const double thr = (double)o.radius + half_w + c.d_safe;
         if (o.x >= X0 - thr && o.x <= X1 + thr && o.y >= Y0 - thr && o.y <= Y1 + thr) {
             const int q = atomicAdd(&sh.n_rel, 1);           // order is irrelevant: only a minimum is taken
-            if (q < kMaxRelObs) { sh.rx[q] = o.x; sh.ry[q] = o.y; sh.rr[q] = (double)o.radius; sh.rt2[q] = thr * thr; }
+            if (q < kMaxRelObs) { sh.ls.rx[q] = o.x; sh.ls.ry[q] = o.y; sh.ls.rr[q] = (double)o.radius; sh.ls.rt2[q] = thr * thr; }
         }
     }
     __syncthreads();
@@ -172,11 +220,11 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
     // instead of all of them.  A bucket that overflows sends only ITS points to the plain loop.
     const bool bucketed = culled ? n_rel >= kBucketMinObs : m <= 256;
     if (bucketed) {
-        for (int i = tid; i < kBucketN * kBucketN; i += kThreads) sh.bcnt[i] = 0;
+        for (int i = tid; i < kBucketN * kBucketN; i += kThreads) sh.ls.bcnt[i] = 0;
         __syncthreads();
         for (int j = tid; j < n_rel; j += kThreads) {
             double ox, oy, r;
-            if (culled) { ox = sh.rx[j]; oy = sh.ry[j]; r = sh.rr[j]; }
+            if (culled) { ox = sh.ls.rx[j]; oy = sh.ls.ry[j]; r = sh.ls.rr[j]; }
             else { const ObPoint o = gobs[j]; ox = o.x; oy = o.y; r = (double)o.radius; }
             // the cutoff, a hair wider: a point exactly at the cutoff (where the penalty is zero anyway) stays inside
             const double thr = (r + half_w + c.d_safe) * (1.0 + 1e-9) + 1e-9;
@@ -185,8 +233,8 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
             for (int by = by0; by <= by1; by++)
                 for (int bx = bx0; bx <= bx1; bx++) {
                     const int b = by * kBucketN + bx;
-                    const int q = atomicAdd(&sh.bcnt[b], 1);
-                    if (q < kBucketCap) sh.bent[b][q] = (unsigned char)j;
+                    const int q = atomicAdd(&sh.ls.bcnt[b], 1);
+                    if (q < kBucketCap) sh.ls.bent[b][q] = (unsigned char)j;
                 }
         }
         __syncthreads();
@@ -194,32 +242,34 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
 #ifdef DMPP_DEBUG_SEARCH
     if (tid == 0) {
         atomicAdd(&g_dbg_score[0], 1); atomicAdd(&g_dbg_score[1], sh.n_rel); atomicAdd(&g_dbg_score[2], bucketed ? 1 : 0);
-        { int ov = 0; if (bucketed) for (int i = 0; i < kBucketN * kBucketN; i++) ov += sh.bcnt[i] > kBucketCap; atomicAdd(&g_dbg_score[3], ov); }
+        { int ov = 0; if (bucketed) for (int i = 0; i < kBucketN * kBucketN; i++) ov += sh.ls.bcnt[i] > kBucketCap; atomicAdd(&g_dbg_score[3], ov); }
         atomicAdd(&g_dbg_score[4], culled ? 0 : 1);
         atomicMax(&g_dbg_score[5], sh.n_rel);
     }
 #endif
-    GlobalPoint2D* cand = sh.cand[wave];
-    // The Bezier parameter of a point, and with it the four basis weights, are the same for every lattice candidate: each
-    // lane keeps those of its (<= 4) points (bezier_point's own expressions, so the points come out bit for bit the same).
-    double wb0[4], wb1[4], wb2[4], wb3[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int i = lane + 64 * q;
-        const double t = (double)i / (double)(DMPP_PATH_POINTS - 1), u = 1 - t;
-        wb0[q] = u * u * u; wb1[q] = 3 * u * u * t; wb2[q] = 3 * u * t * t; wb3[q] = t * t * t;
-    }
+    SCORE_MARK(3)
+    // Point i of candidate k: a lattice candidate by bezier_point (the basis weights come from t each time - keeping those of a
+    // lane's four points cost 32 registers; keeping t alone, 8 registers, measured slower beside the searches), the grid-path
+    // candidate by mean_point.  The same expressions whichever lane evaluates a point and for whatever it is wanted, so a
+    // point has ONE value: as itself, as a neighbour, in the output.
+    auto cand_point = [&](int k, int i) -> GlobalPoint2D {
+        if (k < nl) return bezier_point(sh.bz[k], i, DMPP_PATH_POINTS);
+        return mean_point(c, sh.pts, sh.cum, a + 1, clampi(i, 0, DMPP_PATH_POINTS - 1), DMPP_PATH_POINTS);
+    };
+    // the point of the lane below / above (all 64 lanes call these together); lane 0 / lane 63 get their own value back
+    auto from_lane_below = [&](const GlobalPoint2D p) -> GlobalPoint2D { GlobalPoint2D r; r.x = lane_below_f64(p.x); r.y = lane_below_f64(p.y); return r; };
+    auto from_lane_above = [&](const GlobalPoint2D p) -> GlobalPoint2D { GlobalPoint2D r; r.x = lane_above_f64(p.x); r.y = lane_above_f64(p.y); return r; };
     const double kk2_fenced = 0.001 * 0.001;           // R fenced to 1000
-    // penalty and squared curvature of point i (= p) of the candidate whose points lie in cnd[]
-    auto point_terms = [&](const GlobalPoint2D* cnd, int i, const GlobalPoint2D p, double& pen, double& kk2, bool& hit) {
+    // penalty and squared curvature of point i (= p) of a candidate; pa, pf: its points i - 1 and i + 1 (read for 1 <= i <= 198 only)
+    auto point_terms = [&](int i, const GlobalPoint2D p, const GlobalPoint2D pa, const GlobalPoint2D pf, double& pen, double& kk2, bool& hit) {
         double clear = __builtin_inf();
         int nb = 0, b = 0;
-        if (bucketed) { b = bucket_y(p.y) * kBucketN + bucket_x(p.x); nb = sh.bcnt[b]; }
+        if (bucketed) { b = bucket_y(p.y) * kBucketN + bucket_x(p.x); nb = sh.ls.bcnt[b]; }
         if (bucketed && nb <= kBucketCap) {
             for (int e = 0; e < nb; e++) {
-                const int j = sh.bent[b][e];
+                const int j = sh.ls.bent[b][e];
                 double ox, oy, r, t2;
-                if (culled) { ox = sh.rx[j]; oy = sh.ry[j]; r = sh.rr[j]; t2 = sh.rt2[j]; }
+                if (culled) { ox = sh.ls.rx[j]; oy = sh.ls.ry[j]; r = sh.ls.rr[j]; t2 = sh.ls.rt2[j]; }
                 else { ox = gobs[j].x; oy = gobs[j].y; r = (double)gobs[j].radius; const double thr = r + half_w + c.d_safe; t2 = thr * thr; }
                 const double dx = p.x - ox, dy = p.y - oy;
                 const double d2 = dx * dx + dy * dy;
@@ -229,10 +279,10 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
             }
         } else if (__builtin_expect(culled, 1)) {
             for (int j = 0; j < n_rel; j++) {
-                const double dx = p.x - sh.rx[j], dy = p.y - sh.ry[j];
+                const double dx = p.x - sh.ls.rx[j], dy = p.y - sh.ls.ry[j];
                 const double d2 = dx * dx + dy * dy;
-                if (d2 > sh.rt2[j]) continue;                 // cannot produce a penalty (no sqrt needed)
-                const double v = sqrt(d2) - sh.rr[j];
+                if (d2 > sh.ls.rt2[j]) continue;                 // cannot produce a penalty (no sqrt needed)
+                const double v = sqrt(d2) - sh.ls.rr[j];
                 if (v < clear) clear = v;
             }
         } else {
@@ -258,7 +308,6 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
             //   (1 / R)^2 = sinA^2 / (0.25 d3) = (4 d1 d2 - (d1 + d2 - d3)^2) / (d1 d2 d3).
             // Against the oracle's sqrt / divide chain this differs by rounding only (<= ~1e-9 relative where sinA is at
             // its fence of 0.001, less elsewhere; the scores are compared to 1e-6) - except AT the fence, see below.
-            const GlobalPoint2D pa = cnd[i - 1], pf = cnd[i + 1];
             const double d1 = (pa.x - p.x) * (pa.x - p.x) + (pa.y - p.y) * (pa.y - p.y);
             const double d2 = (p.x - pf.x) * (p.x - pf.x) + (p.y - pf.y) * (p.y - pf.y);
             const double d3 = (pa.x - pf.x) * (pa.x - pf.x) + (pa.y - pf.y) * (pa.y - pf.y);
@@ -301,37 +350,32 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
     // (lane j, after its three earlier terms: the order of the sums does not change).
     // (The loops over a wave's candidates and over a candidate's passes are NOT unrolled: point_terms is ~1,000 instructions, and
     // eighteen copies of it made this kernel 129 KB of code; rolled it is 36 KB and exactly as fast, alone and beside the searches.)
-    auto whole_candidate = [&](int k, int n_pass, double& off, double& pen_acc, double& k2_acc, int& first_hit, GlobalPoint2D* tail) {
+    // A lane holds point i = lane + 64 q in pass q; its neighbours are the points of the lanes beside it.  What lies across a
+    // pass border is taken from the pass beyond it: the points of pass q + 1 are computed before pass q is scored (lane 0 of
+    // them is point i + 1 of lane 63), and lane 63 of pass q stays behind as point i - 1 of lane 0 of pass q + 1.
+    auto whole_candidate = [&](int k, int n_pass, double& off, double& pen_acc, double& k2_acc, int& first_hit) {
         off = 0;
-        if (k < nl) {
-            const Bezier bz = sh.bz[k];
-            off = (double)(k - (nl - 1) / 2) * c.lattice_step;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                GlobalPoint2D P;
-                P.x = wb0[q] * bz.x0 + wb1[q] * bz.x1 + wb2[q] * bz.x2 + wb3[q] * bz.x3;
-                P.y = wb0[q] * bz.y0 + wb1[q] * bz.y1 + wb2[q] * bz.y2 + wb3[q] * bz.y3;
-                if (lane + 64 * q < DMPP_PATH_POINTS) cand[lane + 64 * q] = P;
-            }
-        } else {
-#pragma nounroll
-            for (int q = 0; q < 4; q++)
-                if (lane + 64 * q < DMPP_PATH_POINTS) cand[lane + 64 * q] = mean_point(c, sh.pts, sh.cum, a + 1, lane + 64 * q, DMPP_PATH_POINTS);
-        }
-        wave_sync();
-        if (tail && lane < DMPP_PATH_POINTS - kTailFirst) tail[lane] = cand[kTailFirst + lane];      // points 190 .. 199 for the packed pass
+        if (k < nl) off = (double)(k - (nl - 1) / 2) * c.lattice_step;
         pen_acc = 0; k2_acc = 0; first_hit = DMPP_PATH_POINTS;
+        GlobalPoint2D P = cand_point(k, lane), below = P;      // below: point 64 q - 1 (pass 0: not read, point 0 has no curvature term)
 #pragma nounroll
         for (int q = 0; q < n_pass; q++) {
             const int i = lane + 64 * q;
+            GlobalPoint2D N = P;
+            if (64 * (q + 1) < DMPP_PATH_POINTS) N = cand_point(k, i + 64);       // (with the packed pass to come: point 192 for lane 63 of pass 2)
+            GlobalPoint2D pa = from_lane_below(P), pf = from_lane_above(P);
+            const GlobalPoint2D above = { readlane_f64(N.x, 0), readlane_f64(N.y, 0) };
+            if (lane == 0) pa = below;
+            if (lane == DMPP_WAVE - 1) pf = above;
             if (i < DMPP_PATH_POINTS) {
                 double pen, kk2; bool hit;
-                point_terms(cand, i, cand[i], pen, kk2, hit);
+                point_terms(i, P, pa, pf, pen, kk2, hit);
                 pen_acc += pen; k2_acc += kk2;
                 if (hit && i < first_hit) first_hit = i;
             }
+            below.x = readlane_f64(P.x, DMPP_WAVE - 1); below.y = readlane_f64(P.y, DMPP_WAVE - 1);
+            P = N;
         }
-        wave_sync();
     };
     const int rounds = (n_whole - wave + NW - 1) / NW;                 // whole candidates of this wave
     const bool pack_tail = kPackTail<NW> && (n_whole + NW - 1) / NW >= 2 && (n_whole + NW - 1) / NW <= kTailRounds;       // (uniform over the block)
@@ -343,21 +387,25 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
         for (int ci = 0; ci < rounds; ci++) {
             const int k = wave + ci * NW;
             double off, pen_acc, k2_acc; int first_hit;
-            whole_candidate(k, pack_tail ? 3 : 4, off, pen_acc, k2_acc, first_hit, pack_tail ? &sh.tail[wave % kTailWaves<NW>][ci][0] : nullptr);
+            whole_candidate(k, pack_tail ? 3 : 4, off, pen_acc, k2_acc, first_hit);
             if (!pack_tail) publish(k, off, pen_acc, k2_acc, first_hit);
             else {
 #pragma unroll
                 for (int t = 0; t < kTailRounds; t++) if (t == ci) { accP[t] = pen_acc; accK[t] = k2_acc; accOff[t] = off; accH[t] = first_hit; }
             }
         }
+        SCORE_MARK(4)
         if (pack_tail) {
-            {   // the packed pass: lane 8 c + j = point 192 + j of candidate c
+            {   // the packed pass: lane 8 c + j = point 192 + j of candidate c.  Point 191, the neighbour of a candidate's first lane, is
+                // evaluated for it; point 199 has no curvature term, so what its lane receives from the next candidate's is not read.
                 const int cl = lane >> 3, i = 192 + (lane & 7);
+                const int kc = wave + (cl < rounds ? cl : 0) * NW;             // lanes beyond the wave's candidates compute (and drop) its first one (rounds >= 1 here)
                 double pen = 0, kk2 = 0; bool hit = false;
-                if (cl < rounds) {
-                    const GlobalPoint2D* cnd = &sh.tail[wave % kTailWaves<NW>][cl][0] - kTailFirst;      // cnd[i] = point i, i = 190 .. 199
-                    point_terms(cnd, i, cnd[i], pen, kk2, hit);
-                }
+                const GlobalPoint2D p = cand_point(kc, i), p191 = cand_point(kc, 191);
+                GlobalPoint2D pa = from_lane_below(p);
+                const GlobalPoint2D pf = from_lane_above(p);
+                if ((lane & 7) == 0) pa = p191;
+                if (cl < rounds) point_terms(i, p, pa, pf, pen, kk2, hit);
                 const int hv = hit ? i : DMPP_PATH_POINTS;
 #pragma unroll
                 for (int ci = 0; ci < kTailRounds; ci++) {
@@ -370,30 +418,22 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
             for (int ci = 0; ci < kTailRounds; ci++) if (ci < rounds) publish(wave + ci * NW, accOff[ci], accP[ci], accK[ci], accH[ci]);
         }
     }
+    SCORE_MARK(5)
     if (n_whole < nc) {
-        struct Part { double pen[DMPP_WAVE], k2[DMPP_WAVE]; int hit[DMPP_WAVE]; };
-        static_assert(sizeof(Part) * NW <= sizeof(GlobalPoint2D) * DMPP_PATH_POINTS * (NW - NW / 4), "the partial sums live in the candidate arrays the left-over candidates do not use");
-        Part* parts = reinterpret_cast<Part*>(&sh.cand[NW / 4][0]);
-        __syncthreads();                                   // every wave is done with its candidate array
+        // A left-over candidate by quarters: wave 4 j + q holds points 64 q .. 64 q + 63 of candidate n_whole + j.  The neighbours
+        // inside the quarter come from the lanes beside; lanes 0 and 63 evaluate the one that belongs to the wave next door.
         const bool mine = wave < 4 * left;
         const int j = wave >> 2, q = wave & 3, k = n_whole + j, i = lane + 64 * q;
-        GlobalPoint2D p = { 0.0, 0.0 };
-        if (mine) {
-            if (k < nl) {
-                const Bezier bz = sh.bz[k];
-                const double b0 = q == 0 ? wb0[0] : q == 1 ? wb0[1] : q == 2 ? wb0[2] : wb0[3], b1 = q == 0 ? wb1[0] : q == 1 ? wb1[1] : q == 2 ? wb1[2] : wb1[3];
-                const double b2 = q == 0 ? wb2[0] : q == 1 ? wb2[1] : q == 2 ? wb2[2] : wb2[3], b3 = q == 0 ? wb3[0] : q == 1 ? wb3[1] : q == 2 ? wb3[2] : wb3[3];
-                p.x = b0 * bz.x0 + b1 * bz.x1 + b2 * bz.x2 + b3 * bz.x3;
-                p.y = b0 * bz.y0 + b1 * bz.y1 + b2 * bz.y2 + b3 * bz.y3;
-            } else p = mean_point(c, sh.pts, sh.cum, a + 1, min(i, DMPP_PATH_POINTS - 1), DMPP_PATH_POINTS);
-            if (i < DMPP_PATH_POINTS) sh.cand[j][i] = p;
+        double pen = 0, kk2 = 0; bool hit = false;
+        if (mine) {                                        // (whole waves)
+            const GlobalPoint2D p = cand_point(k, i), e = cand_point(k, lane == 0 ? i - 1 : i + 1);
+            GlobalPoint2D pa = from_lane_below(p), pf = from_lane_above(p);
+            if (lane == 0) pa = e;
+            if (lane == DMPP_WAVE - 1) pf = e;
+            if (i < DMPP_PATH_POINTS) point_terms(i, p, pa, pf, pen, kk2, hit);
         }
-        __syncthreads();
-        if (mine) {
-            double pen = 0, kk2 = 0; bool hit = false;
-            if (i < DMPP_PATH_POINTS) point_terms(sh.cand[j], i, p, pen, kk2, hit);
-            parts[wave].pen[lane] = pen; parts[wave].k2[lane] = kk2; parts[wave].hit[lane] = hit ? i : DMPP_PATH_POINTS;
-        }
+        __syncthreads();                                   // every wave is past its last point_terms: the obstacle lists and buckets are dead ...
+        if (mine) { sh.part[wave].pen[lane] = pen; sh.part[wave].k2[lane] = kk2; sh.part[wave].hit[lane] = hit ? i : DMPP_PATH_POINTS; }      // ... and the partial sums lie over them
         __syncthreads();
         if (wave < left) {                                 // wave j2 = wave adds the quarters of left-over candidate j2 up, in order
             const int k2i = n_whole + wave;
@@ -401,7 +441,7 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
 #pragma unroll
             for (int qq = 0; qq < 4; qq++) {
                 if (lane + 64 * qq < DMPP_PATH_POINTS) {
-                    const Part& pt = parts[wave * 4 + qq];
+                    const ScorePart& pt = sh.part[wave * 4 + qq];
                     pen_acc += pt.pen[lane]; k2_acc += pt.k2[lane]; first_hit = min(first_hit, pt.hit[lane]);
                 }
             }
@@ -410,6 +450,7 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
         }
     }
     __syncthreads();
+    SCORE_MARK(6)
     if (tid == 0) {
         double best = 0; int bi = 0;
         for (int k = 0; k < nc; k++) if (k == 0 || sh.cost[k] < best) { best = sh.cost[k]; bi = k; }
@@ -427,6 +468,7 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
             go.best_path[tid] = p;
         }
     }
+    SCORE_MARK(7)
 }
 
 }  // namespace dmpp
