@@ -124,6 +124,13 @@ EPISODE_LOG_MAX = 1 << 20
 EpisodeRecord = _dt([("scene", i4), ("episode", i4), ("start", i4), ("cause", i4), ("age", i4), ("seq", i4), ("tick", np.int64),
                      ("dist", f8), ("end_pos", GlobalPoint2D), ("end_speed", f8), ("score", RolloutScore)])
 
+# one scene, one call (pp_tick_io): the pinned block that carries the inputs, the state and the outputs of the latency path
+PP_OK, PP_ERR_ARG, PP_ERR_HIP, PP_ERR_CAPACITY, PP_ERR_STATE = 0, -1, -2, -3, -4
+PP_IO_MAX_OBS, PP_IO_WANT_GRID, PP_IO_WANT_REFPATH = 1024, 1, 2
+PpSceneIo = _dt([("in", SceneIn), ("state", SceneState), ("n_obs", i4), ("n_ref", i4), ("want", i4), ("status", i4),
+                 ("obs", ObPoint, (PP_IO_MAX_OBS,)), ("ref", GlobalPoint2D, (MAX_REFPATH,)), ("plan", PlanOut), ("grid", GridOut),
+                 ("dec_ref", GlobalPoint2D, (MAX_REFPATH,))])
+
 MapLane = _dt([("point_off", i4), ("n_points", i4), ("lane_sum", i4), ("_pad", i4)])
 MapJunction = _dt([("last_road", i4), ("next_road", i4), ("last_lane", i4), ("next_lane", i4), ("point_off", i4), ("n_points", i4)])
 
@@ -210,6 +217,7 @@ def load_library(path=None):
     lib.pp_wait_tick.argtypes = [vp, C.c_longlong, C.POINTER(ci)]
     lib.pp_tick_id.argtypes = [vp]
     lib.pp_tick_id.restype = C.c_longlong
+    lib.pp_tick_io.argtypes = [vp, vp]
     # closed-loop rollout.  An OLDER build named through DMPP_LIB / `path` (A/B measurements against a parent commit) may lack
     # these; the package's own library must have them.
     rollout = hasattr(lib, "pp_advance_async") or path == LIB_PATH
@@ -280,7 +288,7 @@ def load_library(path=None):
     lib.pp_host_unregister.argtypes = [vp]
     if lib.pp_sizeof(17) != C.sizeof(MapDesc):
         raise PlannerError(f"ABI mismatch for MapDesc: C {lib.pp_sizeof(17)} B, binding {C.sizeof(MapDesc)} B")
-    for which, dt in enumerate(_SIZEOF_ORDER):
+    for which, dt in list(enumerate(_SIZEOF_ORDER)) + [(18, PpSceneIo)]:
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
@@ -419,6 +427,16 @@ class _PinnedArray(np.ndarray):
         self._owner = getattr(obj, "_owner", None)
 
 
+def _io_block(io):
+    """Refuses anything but a one-record PpSceneIo array that lies inside a pp_host_alloc block (a copy of one does not)."""
+    if not isinstance(io, np.ndarray) or io.dtype != PpSceneIo or io.shape != (1,) or not io.flags["C_CONTIGUOUS"]:
+        raise ValueError("tick_io: the block must be pinned_empty(1, PpSceneIo): one C-contiguous PpSceneIo record")
+    owner = getattr(io, "_owner", None)
+    first = io.ctypes.data
+    if owner is None or not owner.ptr or first < owner.ptr or first + io.nbytes > owner.ptr + len(owner.buf):
+        raise ValueError("tick_io: the block must lie in pinned host memory (pinned_empty(1, PpSceneIo)): the device reads and writes it")
+
+
 def pinned_copy(a):
     out = pinned_empty(len(a), a.dtype)
     out[...] = a
@@ -497,6 +515,17 @@ class Planner:
 
     def sync(self):
         _check(self.lib.pp_sync(self.h))
+
+    # ---- one scene, one call, one host wait: the latency path of the class surface ----------
+    def tick_io(self, io, check=True):
+        """pp_tick_io: `io` is ONE PpSceneIo record in pinned memory - pinned_empty(1, PpSceneIo) - that carries location + decision,
+        obstacle list, refpath and state in, and PlanOut, state, GridOut and the published refpath out (the kernels of the call read
+        and write the block itself, so nothing else is accepted).  Returns the return code; with check=True a non-zero code raises."""
+        _io_block(io)
+        rc = self.lib.pp_tick_io(self.h, io.ctypes.data)
+        if check:
+            _check(rc)
+        return rc
 
     # ---- streamed ticks (no host wait) ---------------------------------------------------
     def update_async(self, scene_in=None, obs_pool=None, mot_pool=None, n_obs_total=None):

@@ -297,6 +297,7 @@ struct pp_planner {
     // snapshot, the path cells and GridOut exist per (group position, tick slot); searched[p] = the last search that used the
     // work buffers p, scored[q] = the last scoring pass that read snapshot set q; raster: the snapshot of the group's last tick
     SyncPoint searched[kBuf], scored[kObs], raster;
+    SyncPoint io_in;              // pp_tick_io in front of a piped tick: behind k_io_in (handle's stream), waited for by the front chain
     bool front_unjoined = false;  // the last Planning kernel ran beside a piped tick: a one-stream front chain has yet to wait for it
     int parity = 0;              // work buffers of the last group
     bool last_piped = false;     // the last tick ran as three chains on several streams (else it ended on the handle's stream)
@@ -1044,6 +1045,8 @@ namespace {
 // pp_fetch_async: every tick is fetched, and its downloads wait for its own scoring pass).
 // (a tick without the grid stage leaves the search buffers alone: pp_get_grid_out / pp_get_path keep returning the last search)
 struct TickStreams { hipStream_t front, dp, search, score; };          // dp: Decision + Planning
+// whether the next tick of the resident scenes runs piped (pp_plan_tick; pp_tick_io orders the front chain of such a tick behind k_io_in)
+bool tick_piped(const pp_planner* h) { return h->cfg.grid_stage && h->n_scenes >= h->pipeline_min; }
 TickStreams tick_streams(const pp_planner* h, bool piped, bool grid_stage, int parity)
 {
     hipStream_t search = piped ? h->stream_m[parity] : h->stream;
@@ -1165,7 +1168,7 @@ int pp_plan_tick(pp_handle h)
     const PlannerConfig& c = h->cfg;
     if (c.decision_stage && c.lanechg_stage && !h->have_attr)
         return fail(PP_ERR_ARG, "cfg.lanechg_stage needs the lane attribute pool (pp_set_scenes lane_attr_pool)");
-    const bool piped = c.grid_stage && n >= h->pipeline_min;           // the chains and their streams: tick_streams
+    const bool piped = tick_piped(h);                                  // the chains and their streams: tick_streams
     // streamed inputs: the update staged by pp_update_async becomes the set this tick (and the following ones) read
     bool adopted = false;
     if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; h->rollout.staged_by_advance = false; adopted = true; }
@@ -2334,16 +2337,35 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
     if (!h || !io) return fail(PP_ERR_ARG, "null argument");
     if (h->n_scenes != 1) return fail(PP_ERR_STATE, "pp_tick_io moves ONE resident scene (pp_set_scenes with n_scenes = 1 comes first: its lane pool stays)");
     if ((io->want & PP_IO_WANT_GRID) && !h->cfg.grid_stage) return fail(PP_ERR_STATE, "PP_IO_WANT_GRID: the handle's configuration has the grid stage off");
-    HIP_TRY(hipSetDevice(h->device));
+    // The counts are checked here, in front of everything: a refused call launches nothing and leaves block, handle and tick id
+    // as they were.  (k_io_in clamps them again: a fence, never the rule.)
     const int max_obs = std::min(PP_IO_MAX_OBS, h->caps.max_obs_total), max_ref = std::min(DMPP_MAX_REFPATH, h->caps.max_ref_pts_total);
-    { int r = flush_group(h); if (r) return r; }          // (k_io_in rewrites the inputs an open group's searches read)
-    PP_TRY(h->score.ego.wait(h->stream));                 // ... and the scorecard of the last tick
+    const int n_obs = io->n_obs, n_ref = io->n_ref;
+    if (n_obs < 0 || n_ref < 0) return fail(PP_ERR_ARG, "pp_tick_io: io->n_obs and io->n_ref must not be negative");
+    if (n_obs > max_obs)
+        return fail(PP_ERR_CAPACITY, "pp_tick_io: io->n_obs = " + std::to_string(n_obs) + " obstacles, the handle takes " + std::to_string(max_obs) + " (PP_IO_MAX_OBS, caps.max_obs_total)");
+    if (n_ref > max_ref)
+        return fail(PP_ERR_CAPACITY, "pp_tick_io: io->n_ref = " + std::to_string(n_ref) + " refpath points, the handle takes " + std::to_string(max_ref) + " (DMPP_MAX_REFPATH, caps.max_ref_pts_total)");
+    HIP_TRY(hipSetDevice(h->device));
+    // k_io_in rewrites the inputs (and the state) that the kernels of earlier ticks read.  A one-stream tick has ended on the
+    // handle's stream: launching an open group is enough.  A piped one ran on the other streams: all of them are joined first.
+    if (h->last_piped) { int r = join_all(h); if (r) return r; }
+    else {
+        { int r = flush_group(h); if (r) return r; }
+        PP_TRY(h->score.ego.wait(h->stream));             // ... and the scorecard of the last tick
+    }
     h->in_staged = -1; h->rollout.staged_by_advance = false;
     hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->d_in, h->d_state, h->d_obs, h->d_ref);
     HIP_TRY(hipGetLastError());
-    h->n_obs_total = std::min(std::max((int)io->n_obs, 0), max_obs); h->have_motion = false;
+    h->n_obs_total = n_obs; h->have_motion = false;
     h->n_ref_pts = std::max(h->n_ref_pts, max_ref);
     note_current_set(h);
+    // A piped tick (one scene: grid stage on and DMPP_PIPELINE_MIN <= 1) starts its front chain on another stream, which nothing
+    // else orders behind k_io_in.  The one-stream tick starts on the handle's stream: no event and no wait there.
+    if (tick_piped(h)) {
+        const hipStream_t front = tick_streams(h, true, true, h->parity).front;
+        if (front != h->stream) { PP_TRY(h->io_in.record(h->stream)); PP_TRY(h->io_in.wait(front)); }
+    }
     { int r = pp_plan_tick(h); if (r) return r; }
     if (h->last_piped) { int r = join_all(h); if (r) return r; }      // (a one-scene tick ends on the handle's stream, as a rule: nothing to join)
     hipLaunchKernelGGL(dmpp::k_io_out, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, (int)io->want, h->d_plan, h->d_state,

@@ -94,6 +94,7 @@ class HostSurface:
                                    junc.ctypes.data if len(junc) else None, len(junc), int(si["stub_attribute"]), float(si["period_last"]),
                                    dec.ctypes.data, ref.ctypes.data, len(ref), around.ctypes.data, result.ctypes.data, show.ctypes.data,
                                    road.ctypes.data, C.addressof(mem), grid.ctypes.data if want_grid else None)
+        self.last_code = rc          # CShare::LastStatus().code of the call (0, or a PP_ERR_* value)
         if rc:
             raise dm.PlannerError(f"class surface: {self.L.dmpp_host_error().decode()}")
         out = dict(dec=dec[0], refpath=ref[:int(dec["refpath_n"][0])], around=around, result=result[0], show=show[0], road_points=road,

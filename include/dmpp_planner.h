@@ -465,7 +465,22 @@ int  pp_get_episode_log_info(pp_handle h, long long* total, long long* lost_tota
  * - location + decision, obstacle list, refpath / junction polyline, state in; PlanOut, state, GridOut, published refpath
  * out - and pp_tick_io moves it with two small kernels that read / write the block over PCIe on the handle's stream, around
  * one pp_plan_tick: no copy command, one host wait.  The handle must hold ONE resident scene (pp_set_scenes: its lane pool
- * stays; io->in.lanes must lie inside it).  io->in.obs_off / obs_n / ref_off / ref_n are set from n_obs / n_ref. */
+ * stays; io->in.lanes must lie inside it).  io->in.obs_off / obs_n / ref_off / ref_n are set from n_obs / n_ref.
+ * COUNTS.  Nothing is ever dropped: 0 <= n_obs <= min(PP_IO_MAX_OBS, caps.max_obs_total) and 0 <= n_ref <= min(DMPP_MAX_REFPATH,
+ * caps.max_ref_pts_total).  A negative count is PP_ERR_ARG, a count above its limit PP_ERR_CAPACITY; a handle that does not
+ * hold exactly one scene, and PP_IO_WANT_GRID on a handle whose grid stage is off, are PP_ERR_STATE.  A call refused for any of
+ * these launches nothing: the block, the handle and pp_tick_id are as before, and the next call is an ordinary one.  Every call lists ALL obstacles of its tick: nothing
+ * of an earlier, longer list is read again.
+ * A LANE SLICE outside the resident pool (off < 0, n < 0 or off + n past it) is not refused: no slice is dereferenced, the scene
+ * runs with all three lanes empty, status is 1, every output is written as usual and the call returns PP_ERR_ARG.
+ * CALL ORDER.  The call may follow anything on the handle - unsynced pp_plan_tick calls included, which it orders itself behind.
+ * It SUPERSEDES an update staged by pp_update_async / pp_advance_async and not yet adopted by a tick: that update is gone, no later
+ * tick brings it back.  The block carries no ObMotion, so the tick runs WITHOUT a motion pool - its obstacles are static whatever
+ * cfg.dynamic_obstacles says - and the handle keeps that setting afterwards: later pp_plan_tick calls read the block's obstacles,
+ * static, until a pp_set_scenes / pp_set_egos / pp_update_async brings a motion pool again.  pp_get_plan / pp_get_state /
+ * pp_get_grid_out / pp_get_path / pp_get_refpath afterwards return what the block holds.
+ * UNTOUCHED in the block: in, n_obs, n_ref, want, obs, ref always; grid without PP_IO_WANT_GRID; dec_ref without PP_IO_WANT_REFPATH,
+ * and with it every point from plan.dec.refpath_n on.  state, status and plan are written by every call that is not refused. */
 #define PP_IO_MAX_OBS       1024
 #define PP_IO_WANT_GRID     1     /* io->grid is filled (the tick must run the grid stage) */
 #define PP_IO_WANT_REFPATH  2     /* io->dec_ref[0 .. plan.dec.refpath_n) is filled (decision stage) */

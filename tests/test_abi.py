@@ -34,6 +34,19 @@ def test_struct_sizes_match_header(dm):
     assert dm.GlobalPoint2D.itemsize == 16 and dm.ObPoint.itemsize == 24
     assert dm.SceneState.fields["last_Bpoints"][0].itemsize == 3200
     assert dm.PlanningOut.itemsize == 1680
+    # PpSceneIo (pp_tick_io): every member is 8-byte aligned and sized, so the offsets are the running sum of the C sizes
+    io = dm.PpSceneIo
+    assert lib.pp_sizeof(18) == io.itemsize
+    n_obs = lib.pp_sizeof(2) + lib.pp_sizeof(3)                                  # behind SceneIn in, SceneState state
+    obs = n_obs + 4 * 4                                                          # n_obs, n_ref, want, status
+    ref = obs + dm.PP_IO_MAX_OBS * lib.pp_sizeof(6)
+    plan = ref + dm.MAX_REFPATH * dm.GlobalPoint2D.itemsize
+    grid = plan + lib.pp_sizeof(4)
+    dec_ref = grid + lib.pp_sizeof(5)
+    want = dict(n_obs=n_obs, obs=obs, ref=ref, plan=plan, grid=grid, dec_ref=dec_ref)
+    assert {f: io.fields[f][1] for f in want} == want
+    assert dec_ref + dm.MAX_REFPATH * dm.GlobalPoint2D.itemsize == io.itemsize
+    assert io.fields["in"][1] == 0 and io.fields["state"][1] == lib.pp_sizeof(2) and io.fields["status"][1] == n_obs + 12
 
 
 def test_default_config_records_every_undefined_macro(dm):

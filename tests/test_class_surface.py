@@ -136,6 +136,43 @@ def test_plan_with_the_grid_stage(dm, oracle, surface):
             assert not bad, f"scene {s} tick {t}\n" + "\n".join(bad[:10])
 
 
+def test_more_obstacles_than_the_block_carries(dm, oracle, surface):
+    """PP_IO_MAX_OBS + 1 obstacles through decide -> plan: PP_ERR_CAPACITY with its text in CShare::LastStatus(), nothing planned
+    on a part of the list, and the objects stay usable - the next ticks (the whole block's 1024 obstacles, then 40) match the
+    oracle from the state the refused call left alone."""
+    cfg = dm.default_config(128)
+    cfg["grid_stage"] = 0
+    sc = _one(dm.gen_scenes(cfg, 900, 1, 40, junction_every=0), 0, dm)
+    more = dm.gen_scenes(cfg, 900, 1, dm.PP_IO_MAX_OBS + 1, junction_every=0)["obs_pool"]          # the same ego and lane, a longer list
+
+    def with_obstacles(k):
+        out = dict(sc, scene_in=sc["scene_in"].copy(), obs_pool=more[:k].copy(), mot_pool=np.zeros(k, dm.ObMotion), n_obs=k)
+        out["scene_in"]["obs_n"] = k
+        return out
+    hs = surface.HostSurface(dm, cfg)
+    hs.set_scene_map(sc, 0)
+    st_o = sc["state"].copy()
+
+    def tick_and_compare(sc_, tag):
+        got = hs.tick(sc_, 0)
+        assert hs.last_code == 0
+        plan_o, _, _, _, _ = oracle.plan_tick_one(cfg, sc_, 0, st_o)
+        bad = (compare(got["result"], plan_o["result"], "PlanningOut") + compare(got["show"], plan_o["show"], "PlanningStatus")
+               + compare(got["road_points"], plan_o["road_points"], "road_points") + compare(got["around"], plan_o["around"], "around")
+               + compare(got["dec"], plan_o["dec"], "DecisionOut"))
+        for f in PLANNING_STATE:
+            bad += compare(hs.planning_state()[f], st_o[f], "CPlanning." + f)
+        for f in DECISION_STATE:
+            bad += compare(hs.decision_state()[f], st_o[f], "CDecision." + f)
+        assert not bad, tag + "\n" + "\n".join(bad[:10])
+    tick_and_compare(sc, "before")
+    with pytest.raises(dm.PlannerError, match="PP_IO_MAX_OBS"):
+        hs.tick(with_obstacles(dm.PP_IO_MAX_OBS + 1), 0)
+    assert hs.last_code == dm.PP_ERR_CAPACITY
+    tick_and_compare(with_obstacles(dm.PP_IO_MAX_OBS), "the whole block behind the refused call")
+    tick_and_compare(sc, "40 obstacles again")
+
+
 def test_class_surface_latency_helper(dm, surface):
     cfg = dm.default_config(512)
     sc = dm.gen_scenes(cfg, 0, 1, 64, junction_every=0)
