@@ -150,6 +150,32 @@ class _P3(C.Structure):          # GlobalPoint3D passed by value
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("dir", C.c_double)]
 
 
+_vp, _ci, _f8, _pll = C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_longlong)
+# One entry per feature that came after the first release: (probe symbol, {function: (argtypes, restype)}, {pp_sizeof index: dtype}).
+# load_library binds an entry as a whole.  The package's own library must have every entry; an OLDER build named through DMPP_LIB /
+# `path` (A/B measurements against a parent commit) may lack whole entries - those whose probe symbol it does not export.
+_FEATURES = [
+    ("pp_advance_async", {"pp_default_ego_model": ([_vp], None), "pp_advance_async": ([_vp, _vp, _vp], _ci),
+                          "pp_rollout": ([_vp, _ci, _vp, _vp, _pll], _ci), "pp_get_ego_flags": ([_vp, _vp, _ci], _ci)}, {19: EgoModel, 20: EgoTrace}),
+    ("pp_score_begin", {"pp_score_begin": ([_vp, _f8], _ci), "pp_score_end": ([_vp], _ci), "pp_get_rollout_score": ([_vp, _vp, _ci], _ci)}, {21: RolloutScore}),
+    ("pp_set_fleet", {"pp_default_fleet_model": ([_vp], None), "pp_set_fleet": ([_vp, _ci, _vp, _vp], _ci),
+                      "pp_get_obstacles": ([_vp, _ci, _vp, _ci], _ci)}, {22: FleetModel}),
+    ("pp_set_route", {"pp_default_route_model": ([_vp], _ci), "pp_set_route": ([_vp, _ci, _vp, _vp, _vp], _ci)}, {23: RouteLeg, 24: RouteModel}),
+    ("pp_set_grid_follow", {"pp_default_grid_follow": ([_vp], None), "pp_set_grid_follow": ([_vp, _vp], _ci)}, {25: GridFollow}),
+    ("pp_set_traffic", {"pp_set_traffic": ([_vp, _ci, _vp, _vp, _ci, _ci, _vp], _ci), "pp_get_traffic_state": ([_vp, _vp, _ci], _ci)},
+     {26: TrafficTrack, 27: TrafficActor}),
+    ("pp_set_world_traffic", {"pp_set_world_traffic": ([_vp, _ci, _vp, _vp, _ci, _ci, _vp], _ci)}, {}),
+    ("pp_set_traffic_follow", {"pp_default_traffic_follow": ([_vp], None), "pp_set_traffic_follow": ([_vp, _vp], _ci),
+                               "pp_get_traffic_speed": ([_vp, _vp, _ci], _ci)}, {28: TrafficFollow}),
+    ("pp_set_episodes", {"pp_default_episode_model": ([_vp], None), "pp_set_episodes": ([_vp, _vp], _ci),
+                         "pp_get_episode_stats": ([_vp, _vp, _ci], _ci)}, {29: EpisodeModel, 30: EpisodeStats}),
+    ("pp_set_episode_spawn", {"pp_default_episode_spawn": ([_vp], None), "pp_set_episode_spawn": ([_vp, _vp, _vp, _vp], _ci),
+                              "pp_get_episode_spawn_stats": ([_vp, _vp, _ci], _ci)}, {31: EpisodeSpawn, 32: EpisodeSpawnStats}),
+    ("pp_set_episode_traffic", {"pp_set_episode_traffic": ([_vp, _ci, _vp], _ci), "pp_get_episode_traffic_resets": ([_vp, _vp, _ci], _ci)}, {33: TrafficStart}),
+    ("pp_set_episode_log", {"pp_set_episode_log": ([_vp, _ci], _ci), "pp_read_episode_log": ([_vp, _vp, _ci, _pll], _ci),
+                            "pp_get_episode_log_info": ([_vp, _pll, _pll], _ci)}, {34: EpisodeRecord}),
+]
+
 _lib = None
 _hip = None          # the HIP runtime itself, for Planner.write_device only
 
@@ -218,68 +244,15 @@ def load_library(path=None):
     lib.pp_tick_id.argtypes = [vp]
     lib.pp_tick_id.restype = C.c_longlong
     lib.pp_tick_io.argtypes = [vp, vp]
-    # closed-loop rollout.  An OLDER build named through DMPP_LIB / `path` (A/B measurements against a parent commit) may lack
-    # these; the package's own library must have them.
-    rollout = hasattr(lib, "pp_advance_async") or path == LIB_PATH
-    if rollout:
-        lib.pp_default_ego_model.argtypes = [vp]
-        lib.pp_default_ego_model.restype = None
-        lib.pp_advance_async.argtypes = [vp, vp, vp]
-        lib.pp_rollout.argtypes = [vp, ci, vp, vp, C.POINTER(C.c_longlong)]
-        lib.pp_get_ego_flags.argtypes = [vp, vp, ci]
-    scorecard = hasattr(lib, "pp_score_begin") or path == LIB_PATH          # (as above: an older build may lack it)
-    if scorecard:
-        lib.pp_score_begin.argtypes = [vp, C.c_double]
-        lib.pp_score_end.argtypes = [vp]
-        lib.pp_get_rollout_score.argtypes = [vp, vp, ci]
-    fleet = hasattr(lib, "pp_set_fleet") or path == LIB_PATH          # (as above: an older build may lack it)
-    if fleet:
-        lib.pp_default_fleet_model.argtypes = [vp]
-        lib.pp_default_fleet_model.restype = None
-        lib.pp_set_fleet.argtypes = [vp, ci, vp, vp]
-        lib.pp_get_obstacles.argtypes = [vp, ci, vp, ci]
-    route = hasattr(lib, "pp_set_route") or path == LIB_PATH          # (as above: an older build may lack it)
-    if route:
-        lib.pp_default_route_model.argtypes = [vp]
-        lib.pp_set_route.argtypes = [vp, ci, vp, vp, vp]
-    follow = hasattr(lib, "pp_set_grid_follow") or path == LIB_PATH          # (as above: an older build may lack it)
-    if follow:
-        lib.pp_default_grid_follow.argtypes = [vp]
-        lib.pp_default_grid_follow.restype = None
-        lib.pp_set_grid_follow.argtypes = [vp, vp]
-    traffic = hasattr(lib, "pp_set_traffic") or path == LIB_PATH          # (as above: an older build may lack it)
-    if traffic:
-        lib.pp_set_traffic.argtypes = [vp, ci, vp, vp, ci, ci, vp]
-        lib.pp_get_traffic_state.argtypes = [vp, vp, ci]
-    if hasattr(lib, "pp_set_world_traffic") or path == LIB_PATH:          # (as above: an older build may lack it)
-        lib.pp_set_world_traffic.argtypes = [vp, ci, vp, vp, ci, ci, vp]
-    react = hasattr(lib, "pp_set_traffic_follow") or path == LIB_PATH          # (as above: an older build may lack it)
-    if react:
-        lib.pp_default_traffic_follow.argtypes = [vp]
-        lib.pp_default_traffic_follow.restype = None
-        lib.pp_set_traffic_follow.argtypes = [vp, vp]
-        lib.pp_get_traffic_speed.argtypes = [vp, vp, ci]
-    episodes = hasattr(lib, "pp_set_episodes") or path == LIB_PATH          # (as above: an older build may lack it)
-    if episodes:
-        lib.pp_default_episode_model.argtypes = [vp]
-        lib.pp_default_episode_model.restype = None
-        lib.pp_set_episodes.argtypes = [vp, vp]
-        lib.pp_get_episode_stats.argtypes = [vp, vp, ci]
-    spawn = hasattr(lib, "pp_set_episode_spawn") or path == LIB_PATH          # (as above: an older build may lack it)
-    if spawn:
-        lib.pp_default_episode_spawn.argtypes = [vp]
-        lib.pp_default_episode_spawn.restype = None
-        lib.pp_set_episode_spawn.argtypes = [vp, vp, vp, vp]
-        lib.pp_get_episode_spawn_stats.argtypes = [vp, vp, ci]
-    treset = hasattr(lib, "pp_set_episode_traffic") or path == LIB_PATH          # (as above: an older build may lack it)
-    if treset:
-        lib.pp_set_episode_traffic.argtypes = [vp, ci, vp]
-        lib.pp_get_episode_traffic_resets.argtypes = [vp, vp, ci]
-    elog = hasattr(lib, "pp_set_episode_log") or path == LIB_PATH          # (as above: an older build may lack it)
-    if elog:
-        lib.pp_set_episode_log.argtypes = [vp, ci]
-        lib.pp_read_episode_log.argtypes = [vp, vp, ci, C.POINTER(C.c_longlong)]
-        lib.pp_get_episode_log_info.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    for probe, fns, sizes in _FEATURES:
+        if not hasattr(lib, probe) and path != LIB_PATH:          # an OLDER build named through DMPP_LIB / `path` may lack the feature
+            continue
+        for name, (argtypes, restype) in fns.items():            # (the package's own library must have every one: AttributeError)
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
+        for which, dt in sizes.items():
+            if lib.pp_sizeof(which) != dt.itemsize:
+                raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     lib.pp_host_alloc.argtypes = [cz]
     lib.pp_host_alloc.restype = vp
     lib.pp_host_free.argtypes = [vp]
@@ -289,14 +262,6 @@ def load_library(path=None):
     if lib.pp_sizeof(17) != C.sizeof(MapDesc):
         raise PlannerError(f"ABI mismatch for MapDesc: C {lib.pp_sizeof(17)} B, binding {C.sizeof(MapDesc)} B")
     for which, dt in list(enumerate(_SIZEOF_ORDER)) + [(18, PpSceneIo)]:
-        if lib.pp_sizeof(which) != dt.itemsize:
-            raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
-    for which, dt in (((19, EgoModel), (20, EgoTrace)) if rollout else ()) + (((21, RolloutScore),) if scorecard else ()) + \
-            (((22, FleetModel),) if fleet else ()) + (((23, RouteLeg), (24, RouteModel)) if route else ()) + \
-            (((25, GridFollow),) if follow else ()) + (((26, TrafficTrack), (27, TrafficActor)) if traffic else ()) + \
-            (((28, TrafficFollow),) if react else ()) + (((29, EpisodeModel), (30, EpisodeStats)) if episodes else ()) + \
-            (((31, EpisodeSpawn), (32, EpisodeSpawnStats)) if spawn else ()) + (((33, TrafficStart),) if treset else ()) + \
-            (((34, EpisodeRecord),) if elog else ()):
         if lib.pp_sizeof(which) != dt.itemsize:
             raise PlannerError(f"ABI mismatch for struct #{which}: C {lib.pp_sizeof(which)} B, binding {dt.itemsize} B")
     _lib = lib
@@ -317,62 +282,55 @@ def _check(rc):
         raise PlannerError(f"libdmpp error {rc}: {load_library().pp_last_error().decode()}")
 
 
+def _default(dtype, fn_name, *args, checked=False):
+    """One record of `dtype`, filled by the library's pp_default_* function `fn_name`."""
+    rec = np.zeros(1, dtype)
+    rc = getattr(load_library(), fn_name)(_ptr(rec), *args)
+    if checked:
+        _check(rc)
+    return rec
+
+
 def default_config(grid_w=512, grid_h=None):
     """PlannerConfig record with the build-chosen values for every undefined reference macro."""
-    cfg = np.zeros(1, PlannerConfig)
-    load_library().pp_default_config(_ptr(cfg), grid_w, grid_h or grid_w)
-    return cfg
+    return _default(PlannerConfig, "pp_default_config", grid_w, grid_h or grid_w)
 
 
 def default_ego_model():
     """EgoModel record of the closed-loop rollout (pp_default_ego_model): dt, acceleration limits, id search window."""
-    m = np.zeros(1, EgoModel)
-    load_library().pp_default_ego_model(_ptr(m))
-    return m
+    return _default(EgoModel, "pp_default_ego_model")
 
 
 def default_fleet_model():
     """FleetModel record of the fleet coupling (pp_default_fleet_model): range, peer radius, peer slots per scene."""
-    fm = np.zeros(1, FleetModel)
-    load_library().pp_default_fleet_model(_ptr(fm))
-    return fm
+    return _default(FleetModel, "pp_default_fleet_model")
 
 
 def default_route_model():
     """RouteModel record of the route following (pp_default_route_model): lane points of pre-junction before a lane's end."""
-    rm = np.zeros(1, RouteModel)
-    _check(load_library().pp_default_route_model(_ptr(rm)))
-    return rm
+    return _default(RouteModel, "pp_default_route_model", checked=True)
 
 
 def default_grid_follow():
     """GridFollow record of the grid that follows the ego (pp_default_grid_follow): the path point the goal is taken from, the margin in cells."""
-    gf = np.zeros(1, GridFollow)
-    load_library().pp_default_grid_follow(_ptr(gf))
-    return gf
+    return _default(GridFollow, "pp_default_grid_follow")
 
 
 def default_episode_model():
     """EpisodeModel record of the episodic rollouts (pp_default_episode_model): end_mask 31 (all five EGO_* flags), max_ticks 0 (no timeout)."""
-    em = np.zeros(1, EpisodeModel)
-    load_library().pp_default_episode_model(_ptr(em))
-    return em
+    return _default(EpisodeModel, "pp_default_episode_model")
 
 
 def default_episode_spawn():
     """EpisodeSpawn record of the episode spawn model (pp_default_episode_spawn): seed 1, clearance 2 m, n_starts 1, order 0 (hashed),
     contact 1, check 3 (the obstacle slice and the egos of the world)."""
-    sp = np.zeros(1, EpisodeSpawn)
-    load_library().pp_default_episode_spawn(_ptr(sp))
-    return sp
+    return _default(EpisodeSpawn, "pp_default_episode_spawn")
 
 
 def default_traffic_follow():
     """TrafficFollow record of the car-following traffic (pp_default_traffic_follow): look 60 m, lateral 1.5 m, gap 2 m, headway 1.5 s,
     max_acc 1, comfort_dec 2, max_dec 6 m/s^2, min_net 0.1 m."""
-    tf = np.zeros(1, TrafficFollow)
-    load_library().pp_default_traffic_follow(_ptr(tf))
-    return tf
+    return _default(TrafficFollow, "pp_default_traffic_follow")
 
 
 def gen_scenes(cfg, first_scene, n_scenes, n_obs, junction_every=8):

@@ -32,6 +32,7 @@
 #include "kernels_t.hpp"
 #include "kernels_op.hpp"
 #include "search_budget.hpp"
+#include "rollout_features.hpp"
 
 namespace {
 
@@ -320,7 +321,8 @@ struct pp_planner {
     TickRec rec_last = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
     std::vector<PendingFetch> fetches;
-    // one block per rollout feature
+    // one block per rollout feature.  Which call switches which feature off, and what holds between the `on` flags, is the table of
+    // rollout_features.hpp; a set call writes its own flag, retire() every other one, features_ok() checks the result
     RolloutState rollout;
     ScoreState score;
     FleetState fleet;
@@ -585,6 +587,51 @@ int join_all(pp_planner* h)
     return PP_OK;
 }
 
+// Rollout features (rollout_features.hpp; DESIGN.md §7 "Feature life cycle").  The features that are on, as the table's bits ...
+unsigned feature_mask(const pp_planner* h)
+{
+    using namespace dmpp;
+    return (h->fleet.on ? kFleet : 0u) | (h->route.on ? kRoute : 0u) | (h->traffic.on ? (h->traffic.world ? kWorldTraffic : kTraffic) : 0u) | (h->follow.on ? kFollow : 0u) |
+           (h->episode.on ? kEpisodes : 0u) | (h->spawn.on ? kSpawn : 0u) | (h->treset.on ? kTrafficReset : 0u) | (h->elog.on ? kEpisodeLog : 0u);
+}
+// ... and the bits as flags: the ONLY code that writes the flag of a feature other than the caller's own
+void switch_features(pp_planner* h, unsigned m, bool on)
+{
+    using namespace dmpp;
+    if (m & kFleet) h->fleet.on = on;
+    if (m & kRoute) h->route.on = on;
+    if (m & (h->traffic.world ? kWorldTraffic : kTraffic)) h->traffic.on = on;
+    if (m & kFollow) h->follow.on = on;
+    if (m & kEpisodes) h->episode.on = on;
+    if (m & kSpawn) h->spawn.on = on;
+    if (m & kTrafficReset) h->treset.on = on;
+    if (m & kEpisodeLog) h->elog.on = on;
+    static_assert(dmpp::kFeatureCount == 9, "a new feature bit needs its flag here and in feature_mask");
+}
+void retire(pp_planner* h, int cause) { switch_features(h, dmpp::retires(cause), false); }
+// the common success exit of every set call
+int features_ok(const pp_planner* h, const char* fn)
+{
+    if (dmpp::consistent(feature_mask(h), h->have_map, h->resident_mode)) return PP_OK;
+    return fail(PP_ERR_STATE, std::string("internal: rollout feature flags inconsistent after ") + fn);
+}
+// A set call refuses while an update is staged: the staged set was built from what the call would replace.
+int refuse_if_staged(const pp_planner* h, const std::string& fn, const char* what)
+{
+    if (h->in_staged < 0) return PP_OK;
+    return fail(PP_ERR_STATE, fn + ": an update is staged for the next tick (set " + what + " before staging, or after the tick)");
+}
+// In front of what a set call changes: every tick and every advance enqueued so far is ordered before the handle's stream (nothing
+// is staged, or the call supersedes it: every advance was adopted by a tick, and join_all is behind those); host_wait: and has finished.
+int quiesce(pp_planner* h, bool host_wait)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(join_all(h));
+    PP_TRY(h->rollout.adv.wait(h->stream));
+    if (host_wait) HIP_TRY(hipStreamSynchronize(h->stream));
+    return PP_OK;
+}
+
 // HIP events around a launch.  A launch for a tick group counts as its w ticks: w launches, its time spread over them (the
 // averages of pp_get_kernel_ms stay per tick).
 struct Timed {
@@ -807,7 +854,7 @@ int pp_destroy(pp_handle h)
 int pp_set_config(pp_handle h, const PlannerConfig* cfg)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    int r = check_cfg(cfg); if (r) return r;
+    PP_TRY(check_cfg(cfg));
     if (h->grid_follow.goal_point > 0 && 2LL * h->grid_follow.margin_cells >= (long long)std::min(cfg->grid_w, cfg->grid_h))
         return fail(PP_ERR_ARG, "pp_set_config: the margin of the grid-follow model no longer fits the grid (2 * margin_cells < min(grid_w, grid_h)): switch following off first");
     if (cfg->grid_stage) {
@@ -817,12 +864,10 @@ int pp_set_config(pp_handle h, const PlannerConfig* cfg)
         if (cfg->bucket_cap > DMPP_OPEN_CAP && cfg->bucket_cap > h->spill_cap)
             return fail(PP_ERR_CAPACITY, "bucket_cap may not grow after pp_create beyond the larger of its value then and DMPP_OPEN_CAP (it sizes the open list's spill area)");
     }
-    HIP_TRY(hipSetDevice(h->device));
-    // a configuration change may move the next tick's kernels to other streams (grid stage on / off): finish what is queued
-    { int r = join_all(h); if (r) return r; }
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    PP_TRY(quiesce(h, true));      // a configuration change may move the next tick's kernels to other streams (grid stage on / off): finish what is queued
     h->cfg = *cfg;
-    return setup_grid_launch(h);
+    PP_TRY(setup_grid_launch(h));
+    return features_ok(h, "pp_set_config");
 }
 
 // New resident scenes: the rollout flags of the old ones go (behind the last advance; the caller's host wait follows).
@@ -886,11 +931,12 @@ static int upload_pools(pp_handle h, const ObPoint* obs_pool, const ObMotion* mo
 // last (which syncs: the caller may reuse its buffers).  map_bad: scenes that k_resolve_map could not place (pp_set_egos).
 static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad = 0)
 {
-    h->resident_mode = mode; h->fleet.on = false; h->route.on = false; h->traffic.on = false; h->episode.on = false; h->spawn.on = false; h->treset.on = false; h->elog.on = false; note_current_set(h);
-    { int r = reset_ego_flags(h); if (r) return r; }
-    if (h->score.on) { int r = reset_scores(h); if (r) return r; }
+    h->resident_mode = mode; retire(h, dmpp::kResidentReplaced); note_current_set(h);
+    PP_TRY(reset_ego_flags(h));
+    if (h->score.on) PP_TRY(reset_scores(h));
     if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
-    return validate_resident(h, h->n_scenes, who);
+    PP_TRY(validate_resident(h, h->n_scenes, who));
+    return features_ok(h, who);
 }
 
 int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoint3D* lane_pool, const uint8_t* lane_attr_pool,
@@ -901,8 +947,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
     if (n_lane_pts > h->caps.max_lane_pts_total || n_ref_pts > h->caps.max_ref_pts_total || n_obs_total > h->caps.max_obs_total)
         return fail(PP_ERR_CAPACITY, "pool larger than the capacity given to pp_create");
     if (n_lane_pts < 0 || n_ref_pts < 0 || n_obs_total < 0) return fail(PP_ERR_ARG, "negative size");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
+    PP_TRY(quiesce(h, false));
     HIP_TRY(hipMemcpyAsync(h->d_in, in, (size_t)n_scenes * sizeof(SceneIn), hipMemcpyDefault, h->stream));
     if (n_lane_pts && lane_pool) HIP_TRY(hipMemcpyAsync(h->d_lane, lane_pool, (size_t)n_lane_pts * sizeof(GlobalPoint3D), hipMemcpyDefault, h->stream));
     h->have_attr = false;
@@ -911,7 +956,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
         h->have_attr = true;
     }
     if (n_ref_pts && ref_pool) HIP_TRY(hipMemcpyAsync(h->d_ref, ref_pool, (size_t)n_ref_pts * sizeof(GlobalPoint2D), hipMemcpyDefault, h->stream));
-    { int r = upload_pools(h, obs_pool, mot_pool, n_obs_total); if (r) return r; }
+    PP_TRY(upload_pools(h, obs_pool, mot_pool, n_obs_total));
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     return resident_replaced(h, 0, "pp_set_scenes");
 }
@@ -937,11 +982,9 @@ int pp_set_map(pp_handle h, const MapDesc* m)
         const MapJunction& J = m->junctions[j];
         if (J.point_off < 0 || J.n_points < 0 || (long long)J.point_off + J.n_points > m->n_jpoints) return fail(PP_ERR_ARG, "junction slice outside the junction point pool");
     }
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    PP_TRY(quiesce(h, true));
     h->have_map = false;                                 // (until the new tables have landed)
-    h->route.on = false;                                 // (the routes named roads of the old map)
+    retire(h, dmpp::kMapReplaced);                       // (the routes named roads of the old map)
     int r;
     if ((r = h->d_map_first.reserve((size_t)m->n_roads + 1)) || (r = h->d_map_lanes.reserve((size_t)m->n_lanes)) || (r = h->d_map_junc.reserve((size_t)m->n_junctions)) ||
         (r = h->d_map_width.reserve((size_t)h->caps.max_lane_pts_total + 1)) || (r = h->d_map_bad.reserve((size_t)1))) return r;
@@ -959,7 +1002,7 @@ int pp_set_map(pp_handle h, const MapDesc* m)
     h->map_roads = m->n_roads; h->map_lanes = m->n_lanes; h->map_junctions = m->n_junctions;
     h->n_lane_pts = m->n_points; h->n_ref_pts = m->n_jpoints;
     h->have_map = true; h->have_attr = true;
-    return PP_OK;
+    return features_ok(h, "pp_set_map");
 }
 
 int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs_pool, const ObMotion* mot_pool, int n_obs_total)
@@ -968,10 +1011,9 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     if (!h->have_map) return fail(PP_ERR_STATE, "pp_set_egos needs a resident map (pp_set_map)");
     if (n_scenes < 0 || n_scenes > h->caps.max_scenes) return fail(PP_ERR_CAPACITY, "n_scenes exceeds caps.max_scenes");
     if (n_obs_total < 0 || n_obs_total > h->caps.max_obs_total) return fail(PP_ERR_CAPACITY, "obstacle pool larger than caps.max_obs_total");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
+    PP_TRY(quiesce(h, false));
     HIP_TRY(hipMemcpyAsync(h->d_in, in, (size_t)n_scenes * sizeof(SceneIn), hipMemcpyDefault, h->stream));
-    { int r = upload_pools(h, obs_pool, mot_pool, n_obs_total); if (r) return r; }
+    PP_TRY(upload_pools(h, obs_pool, mot_pool, n_obs_total));
     HIP_TRY(hipMemsetAsync(h->d_map_bad, 0, sizeof(int), h->stream));
     if (n_scenes)
         hipLaunchKernelGGL(dmpp::k_resolve_map, dim3((unsigned)((n_scenes + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream,
@@ -1004,8 +1046,7 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     if (n_lane_pts < 0 || n_ref_pts < 0 || n_obs_total < 0) return fail(PP_ERR_ARG, "negative size");
     if (n_lane_pts > h->caps.max_lane_pts_total || n_ref_pts > h->caps.max_ref_pts_total || n_obs_total > h->caps.max_obs_total)
         return fail(PP_ERR_CAPACITY, "pool larger than the capacity given to pp_create");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
+    PP_TRY(quiesce(h, false));
     h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
     return resident_replaced(h, 0, "pp_set_n_scenes");
@@ -1303,10 +1344,18 @@ int pp_device_synchronize(pp_handle h)
 static int fetch(pp_handle h, void* dst, const void* src, size_t bytes)
 {
     HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
+    PP_TRY(join_all(h));
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return PP_OK;
+}
+// ... of what the upload stream writes: behind a staged advance too, and - also_staged_update - behind a staged update, which rewrites the same values
+static int fetch_behind_advance(pp_handle h, void* dst, const void* src, size_t bytes, bool also_staged_update)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(h->rollout.adv.wait(h->stream));
+    if (also_staged_update && h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
+    return fetch(h, dst, src, bytes);
 }
 
 int pp_get_plan(pp_handle h, PlanOut* out, int n)
@@ -1626,9 +1675,7 @@ int pp_get_ego_flags(pp_handle h, int32_t* flags, int n)
     if (!h || !flags) return fail(PP_ERR_ARG, "null argument");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
     if (!h->rollout.d_flags) { std::memset(flags, 0, (size_t)n * sizeof(int32_t)); return PP_OK; }
-    HIP_TRY(hipSetDevice(h->device));
-    PP_TRY(h->rollout.adv.wait(h->stream));
-    return fetch(h, flags, h->rollout.d_flags, (size_t)n * sizeof(int32_t));
+    return fetch_behind_advance(h, flags, h->rollout.d_flags, (size_t)n * sizeof(int32_t), false);
 }
 
 // Rollout scorecard.  Scored ticks are streamed ticks: k_score_ego hangs on the tick's front-chain event.
@@ -1637,27 +1684,27 @@ int pp_score_begin(pp_handle h, double dt_score)
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (!(dt_score > 0) || !std::isfinite(dt_score)) return fail(PP_ERR_ARG, "pp_score_begin: dt_score must be finite and > 0");
     HIP_TRY(hipSetDevice(h->device));
-    { int r = flush_group(h); if (r) return r; }
-    { int r = ensure_streaming(h); if (r) return r; }
+    PP_TRY(flush_group(h));
+    PP_TRY(ensure_streaming(h));
     if (!h->score.d_score) {
         const size_t ns = (size_t)h->caps.max_scenes;
-        int r = h->score.d_score.reserve(ns); if (r) return r;
-        for (int q = 0; q < kBuf; q++) if ((r = h->score.d_grid[q].reserve(ns))) return r;
+        PP_TRY(h->score.d_score.reserve(ns));
+        for (int q = 0; q < kBuf; q++) PP_TRY(h->score.d_grid[q].reserve(ns));
     }
-    if (h->elog.on) { int r = h->elog.d_score.reserve((size_t)h->caps.max_scenes); if (r) return r; }      // the episode log gets its scorecards once scoring comes on (§4n)
-    { int r = join_all(h); if (r) return r; }            // the ticks scored so far (a restart) and everything before
+    if (h->elog.on) PP_TRY(h->elog.d_score.reserve((size_t)h->caps.max_scenes));      // the episode log gets its scorecards once scoring comes on (§4n)
+    PP_TRY(join_all(h));                                 // the ticks scored so far (a restart) and everything before
     if (h->elog.on) PP_TRY(h->rollout.adv.wait(h->stream));      // (... and a staged advance: k_log_episodes writes the scorecards of the episodes it ended)
-    { int r = reset_scores(h); if (r) return r; }
+    PP_TRY(reset_scores(h));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->score.on = true; h->score.dt = dt_score;
-    return PP_OK;
+    return features_ok(h, "pp_score_begin");
 }
 
 int pp_score_end(pp_handle h)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     h->score.on = false;
-    return PP_OK;
+    return features_ok(h, "pp_score_end");
 }
 
 int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
@@ -1703,20 +1750,19 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (n_worlds < 0) return fail(PP_ERR_ARG, "pp_set_fleet: negative world count");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_fleet: an update is staged for the next tick (set the fleet before staging, or after the tick)");
+    PP_TRY(refuse_if_staged(h, "pp_set_fleet", "the fleet"));
     const int n = h->n_scenes;
     if (n_worlds == 0) {
         if (!h->fleet.on) return PP_OK;
-        HIP_TRY(hipSetDevice(h->device));
-        { int r = join_all(h); if (r) return r; }
+        PP_TRY(quiesce(h, false));
         hipLaunchKernelGGL(dmpp::k_fleet_restore, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, n, h->fleet.d_pin, h->d_in);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(h->stream));
         // (the slices are the pinned ones again; they were inside fleet.base when they were pinned)
         const int back = std::max(h->fleet.base, h->fleet.own_end);
         h->fleet.on = false; h->n_obs_total = back; h->in_sets[h->in_cur].n_obs_total = back;
-        if (h->traffic.world) h->traffic.on = false;      // (the worlds it was pinned to are gone: §4j)
-        return PP_OK;
+        retire(h, dmpp::kSetFleet);                       // (the worlds that world traffic was pinned to are gone: §4j)
+        return features_ok(h, "pp_set_fleet");
     }
     if (!world_first || !fm) return fail(PP_ERR_ARG, "null argument");
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_fleet: no resident scenes");
@@ -1726,8 +1772,7 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
         return fail(PP_ERR_ARG, "pp_set_fleet: range must be finite and > 0, radius finite and >= 0");
     if (n_worlds > n || world_first[0] != 0 || world_first[n_worlds] != n) return fail(PP_ERR_ARG, "pp_set_fleet: world_first must run from 0 to the resident scene count");
     for (int w = 0; w < n_worlds; w++) if (world_first[w + 1] <= world_first[w]) return fail(PP_ERR_ARG, "pp_set_fleet: world_first must be strictly increasing");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
+    PP_TRY(quiesce(h, false));
     int rc;
     std::vector<dmpp::FleetPin> pin = own_slices(h, &rc); if (rc) return rc;
     const int base = h->fleet.on ? h->fleet.base : h->n_obs_total;
@@ -1756,12 +1801,12 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     HIP_TRY(hipMemcpyAsync(h->fleet.d_pin, pin.data(), (size_t)n * sizeof(dmpp::FleetPin), hipMemcpyHostToDevice, h->stream));
     h->fleet.pin.swap(pin); h->fleet.fm = *fm; h->fleet.base = base; h->fleet.end = (int)end_max; h->fleet.own_end = (int)std::min(own_end, (long long)h->caps.max_obs_total); h->fleet.on = true;
     h->fleet.n_worlds = n_worlds;
-    if (h->traffic.world) h->traffic.on = false;          // world traffic was pinned to the worlds this call replaces (§4j)
+    retire(h, dmpp::kSetFleet);                           // world traffic was pinned to the worlds this call replaces (§4j)
     h->n_obs_total = (int)end_max; h->in_sets[h->in_cur].n_obs_total = (int)end_max;
     couple_fleet(h, h->stream, h->d_in, h->d_obs, h->have_motion ? h->d_mot : nullptr);      // the resident set: the next tick sees the peers
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
-    return PP_OK;
+    return features_ok(h, "pp_set_fleet");
 }
 
 // Lane traffic.  Everything is checked on the host before anything changes; the cumulative lengths are computed
@@ -1772,8 +1817,8 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     if (!h) return fail(PP_ERR_ARG, "null handle");
     const std::string fn = world ? "pp_set_world_traffic" : "pp_set_traffic";
     if (n_tracks < 0 || n_points < 0 || n_actors < 0) return fail(PP_ERR_ARG, fn + ": negative count");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, fn + ": an update is staged for the next tick (set the traffic before staging, or after the tick)");
-    if (n_actors == 0) { h->traffic.on = false; h->treset.on = false; return PP_OK; }
+    PP_TRY(refuse_if_staged(h, fn, "the traffic"));
+    if (n_actors == 0) { retire(h, dmpp::kTrafficOff); return features_ok(h, fn.c_str()); }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, fn + ": no resident scenes");
     if (world && !h->fleet.on) return fail(PP_ERR_STATE, fn + ": no fleet is set (the worlds are those of pp_set_fleet; max_peers = 0 is a legal fleet)");
@@ -1803,8 +1848,7 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
         }
         if (closed && !(c > 0)) return fail(PP_ERR_ARG, who + " is closed and has no length");
     }
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
+    PP_TRY(quiesce(h, false));                            // nobody reads the old arrays from here on; the host wait follows the checks
     int rc;
     const std::vector<dmpp::FleetPin> own = own_slices(h, &rc); if (rc) return rc;
     std::vector<dmpp::TrafficPin> pin((size_t)n_actors); std::vector<double> s0((size_t)n_actors); std::vector<long long> taken((size_t)n_actors);
@@ -1842,12 +1886,10 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     std::sort(taken.begin(), taken.end());
     for (size_t k = 1; k < taken.size(); k++)
         if (taken[k] == taken[k - 1]) return fail(PP_ERR_ARG, fn + ": two actors on slot " + std::to_string((int)(taken[k] & 0xffffffff)) + (world ? " of world " : " of scene ") + std::to_string((int)(taken[k] >> 32)));
-    // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the old arrays
-    PP_TRY(h->rollout.adv.wait(h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     // room first.  An allocation that fails leaves its own array as it was, but may follow one that replaced another: the old
     // traffic then goes off rather than run on half a set
-    h->treset.on = false;                                 // (the start states of §4m were captured from the actors this call replaces)
+    retire(h, world ? dmpp::kSetWorldTraffic : dmpp::kSetTraffic);      // (the start states of §4m were captured from the actors this call replaces)
     if ((rc = h->traffic.d_pin.reserve((size_t)n_actors)) || (rc = h->traffic.d_s[0].reserve((size_t)n_actors)) || (rc = h->traffic.d_tracks.reserve((size_t)n_tracks)) ||
         (rc = h->traffic.d_cum.reserve(cum.size())) || (rc = h->traffic.d_pts.reserve(pts.size())) ||
         (world && (rc = h->traffic.d_world.reserve((size_t)n_actors)))) { h->traffic.on = false; return rc; }
@@ -1863,21 +1905,16 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     move_traffic(h, h->stream, h->d_obs, h->have_motion ? h->d_mot : nullptr, 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
-    if (h->follow.on) { int r = build_follow(h); if (r) return r; }      // following is on: its tables for these actors, v = speed (§4i)
+    if (h->follow.on) PP_TRY(build_follow(h));           // following is on: its tables for these actors, v = speed (§4i)
     h->traffic.on = true;
-    return PP_OK;
+    return features_ok(h, fn.c_str());
 }
 
 int pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points, int n_actors, const TrafficActor* actors)
-{
-    return set_traffic(h, false, n_tracks, tracks, points, n_points, n_actors, actors);
-}
-
+{ return set_traffic(h, false, n_tracks, tracks, points, n_points, n_actors, actors); }
 // World traffic: the same records, read per world of the fleet in force; replaces whatever traffic the handle had.
 int pp_set_world_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points, int n_actors, const TrafficActor* actors)
-{
-    return set_traffic(h, true, n_tracks, tracks, points, n_points, n_actors, actors);
-}
+{ return set_traffic(h, true, n_tracks, tracks, points, n_points, n_actors, actors); }
 
 int pp_get_traffic_state(pp_handle h, double* s, int n)
 {
@@ -1885,10 +1922,7 @@ int pp_get_traffic_state(pp_handle h, double* s, int n)
     if (!h->traffic.on) return fail(PP_ERR_STATE, "pp_get_traffic_state: no traffic is set");
     if (n < 0 || n > h->traffic.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    PP_TRY(h->rollout.adv.wait(h->stream));
-    if (h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));      // (a staged update rewrites the same values)
-    return fetch(h, s, h->traffic.d_s[h->traffic.cur], (size_t)n * sizeof(double));
+    return fetch_behind_advance(h, s, h->traffic.d_s[h->traffic.cur], (size_t)n * sizeof(double), true);
 }
 
 // Car-following traffic: host checks first; the model is a kernel argument of the next advance.
@@ -1908,28 +1942,24 @@ int pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf)
             return fail(PP_ERR_ARG, "pp_set_traffic_follow: look, gap, max_acc, comfort_dec, max_dec and min_net must be > 0");
         if (tf->lateral < 0 || tf->headway < 0) return fail(PP_ERR_ARG, "pp_set_traffic_follow: lateral and headway must be >= 0");
     }
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_traffic_follow: an update is staged for the next tick (set the model before staging, or after the tick)");
-    h->treset.on = false;                                 // (nothing below refuses: the start states of §4m were captured under the model this call replaces)
+    PP_TRY(refuse_if_staged(h, "pp_set_traffic_follow", "the model"));
+    retire(h, dmpp::kSetFollow);                          // (nothing below refuses: the start states of §4m were captured under the model this call replaces)
     if (!h->traffic.on) {                                 // takes effect with the next pp_set_traffic
         h->follow.on = tf != nullptr; if (tf) h->follow.tf = *tf;
-        return PP_OK;
+        return features_ok(h, "pp_set_traffic_follow");
     }
-    // nothing is staged: every advance so far was adopted by a tick, and join_all is behind those; nobody reads the arrays
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }
-    PP_TRY(h->rollout.adv.wait(h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    PP_TRY(quiesce(h, true));                             // nobody reads the arrays
     if (!tf) {                                            // off: the arc lengths go back to the one array of §4h
         if (h->follow.on && h->traffic.cur == 1) {
             HIP_TRY(hipMemcpyAsync(h->traffic.d_s[0], h->traffic.d_s[1], (size_t)h->traffic.actors * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
         }
         h->traffic.cur = 0; h->follow.on = false;
-        return PP_OK;
+        return features_ok(h, "pp_set_traffic_follow");
     }
-    { int r = build_follow(h); if (r) return r; }         // (a failed allocation or copy leaves the model that was set, or none)
+    PP_TRY(build_follow(h));                              // (a failed allocation or copy leaves the model that was set, or none)
     h->follow.tf = *tf; h->follow.on = true;
-    return PP_OK;
+    return features_ok(h, "pp_set_traffic_follow");
 }
 
 int pp_get_traffic_speed(pp_handle h, double* v, int n)
@@ -1938,10 +1968,7 @@ int pp_get_traffic_speed(pp_handle h, double* v, int n)
     if (!h->traffic.on || !h->follow.on) return fail(PP_ERR_STATE, "pp_get_traffic_speed: traffic or following is off");
     if (n < 0 || n > h->traffic.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    PP_TRY(h->rollout.adv.wait(h->stream));
-    if (h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
-    return fetch(h, v, h->follow.d_v[h->traffic.cur], (size_t)n * sizeof(double));
+    return fetch_behind_advance(h, v, h->follow.d_v[h->traffic.cur], (size_t)n * sizeof(double), true);
 }
 
 // Route following.  Everything is checked on the host before anything changes; the resident records are not touched.
@@ -1956,8 +1983,8 @@ int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int3
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (n_legs_total < 0) return fail(PP_ERR_ARG, "pp_set_route: negative leg count");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_route: an update is staged for the next tick (set the route before staging, or after the tick)");
-    if (n_legs_total == 0) { h->route.on = false; return PP_OK; }
+    PP_TRY(refuse_if_staged(h, "pp_set_route", "the route"));
+    if (n_legs_total == 0) { h->route.on = false; return features_ok(h, "pp_set_route"); }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_route: no resident scenes");
     if (h->resident_mode != 1 || !h->have_map) return fail(PP_ERR_STATE, "pp_set_route: routes need egos on a resident map (pp_set_map, then pp_set_egos)");
@@ -1967,18 +1994,15 @@ int pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int3
     for (int s = 0; s < n; s++) if (route_first[s + 1] < route_first[s]) return fail(PP_ERR_ARG, "pp_set_route: route_first must not decrease");
     for (int k = 0; k < n_legs_total; k++)
         if (legs[k].road_num < 1 || legs[k].road_num > h->map_roads) return fail(PP_ERR_ARG, "pp_set_route: leg " + std::to_string(k) + " names a road outside the map");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the old legs
-    PP_TRY(h->rollout.adv.wait(h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    { int r = h->route.d_first.reserve((size_t)h->caps.max_scenes + 1); if (r) return r; }      // room first: a failed allocation leaves the old route
-    { int r = h->route.d_legs.reserve((size_t)n_legs_total); if (r) return r; }
+    PP_TRY(quiesce(h, true));                             // nobody reads the old legs
+    PP_TRY(h->route.d_first.reserve((size_t)h->caps.max_scenes + 1));      // room first: a failed allocation leaves the old route
+    PP_TRY(h->route.d_legs.reserve((size_t)n_legs_total));
     h->route.on = false;                                  // (until the copies below have landed: a failed copy leaves routing off, not half a route)
     HIP_TRY(hipMemcpyAsync(h->route.d_legs, legs, (size_t)n_legs_total * sizeof(RouteLeg), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->route.d_first, route_first, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the caller's arrays may go; the upload stream reads the copies from its next launch on)
     h->route.rm = *rm; h->route.rm._pad = 0; h->route.on = true;
-    return PP_OK;
+    return features_ok(h, "pp_set_route");
 }
 
 // Episodic rollouts.  Everything is checked on the host before anything changes.
@@ -1991,32 +2015,25 @@ void pp_default_episode_model(EpisodeModel* em)
 int pp_set_episodes(pp_handle h, const EpisodeModel* em)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episodes: an update is staged for the next tick (set the episodes before staging, or after the tick)");
-    if (!em) { h->episode.on = false; h->spawn.on = false; h->treset.on = false; h->elog.on = false; return PP_OK; }
+    PP_TRY(refuse_if_staged(h, "pp_set_episodes", "the episodes"));
+    if (!em) { h->episode.on = false; retire(h, dmpp::kSetEpisodes); return features_ok(h, "pp_set_episodes"); }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, "pp_set_episodes: no resident scenes");
     if ((em->end_mask & ~31) != 0) return fail(PP_ERR_ARG, "pp_set_episodes: end_mask holds bits outside the five DMPP_EGO_* flags (31)");
     if (em->max_ticks < 0) return fail(PP_ERR_ARG, "pp_set_episodes: max_ticks must be >= 0");
     if (em->end_mask == 0 && em->max_ticks == 0) return fail(PP_ERR_ARG, "pp_set_episodes: a model with no end flag and no timeout ends no episode");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the old start records
-    PP_TRY(h->rollout.adv.wait(h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    PP_TRY(quiesce(h, true));                             // nobody reads the old start records
     const size_t ns = (size_t)h->caps.max_scenes;         // room first, sized once: a failed allocation leaves the old records
-    { int r = h->episode.d_start_in.reserve(ns); if (r) return r; }
-    { int r = h->episode.d_start_state.reserve(ns); if (r) return r; }
-    { int r = h->episode.d_stats.reserve(ns); if (r) return r; }
+    PP_TRY(h->episode.d_start_in.reserve(ns)); PP_TRY(h->episode.d_start_state.reserve(ns)); PP_TRY(h->episode.d_stats.reserve(ns));
     h->episode.on = false;                                // (until the copies below have landed: a failed copy leaves episodes off, not half a capture)
-    h->spawn.on = false;                                  // (record 0 of the spawn model's pool was the old capture: §4l)
-    h->treset.on = false;                                 // (... and set 0 of the traffic reset went with it: §4m)
-    h->elog.on = false;                                   // (... and the episodes the log numbered: §4n)
+    retire(h, dmpp::kSetEpisodes);                        // (record 0 of the spawn model's pool was the old capture, set 0 of the traffic reset went with it, and so did the episodes the log numbered: §4l - §4n)
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_in, h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_state, h->d_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(dmpp::k_episode_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, (int)ns, h->episode.d_stats);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the upload stream reads the copies from its next launch on)
     h->episode.em = *em; h->episode.on = true;
-    return PP_OK;
+    return features_ok(h, "pp_set_episodes");
 }
 
 int pp_get_episode_stats(pp_handle h, EpisodeStats* out, int n)
@@ -2024,9 +2041,7 @@ int pp_get_episode_stats(pp_handle h, EpisodeStats* out, int n)
     if (!h || !out) return fail(PP_ERR_ARG, "null argument");
     if (!h->episode.d_stats) return fail(PP_ERR_STATE, "pp_get_episode_stats: pp_set_episodes was never called on this handle");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
-    HIP_TRY(hipSetDevice(h->device));
-    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_ego_flags
-    return fetch(h, out, h->episode.d_stats, (size_t)n * sizeof(EpisodeStats));
+    return fetch_behind_advance(h, out, h->episode.d_stats, (size_t)n * sizeof(EpisodeStats), false);      // a staged advance included, as pp_get_ego_flags
 }
 
 // Episode spawn model.  Everything the host can check is checked before anything changes; the new pool is built
@@ -2040,8 +2055,8 @@ void pp_default_episode_spawn(EpisodeSpawn* sp)
 int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* starts_in, const SceneState* starts_state)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_spawn: an update is staged for the next tick (set the spawn model before staging, or after the tick)");
-    if (!sp) { h->spawn.on = false; h->treset.on = false; h->elog.on = false; return PP_OK; }
+    PP_TRY(refuse_if_staged(h, "pp_set_episode_spawn", "the spawn model"));
+    if (!sp) { h->spawn.on = false; retire(h, dmpp::kSetSpawn); return features_ok(h, "pp_set_episode_spawn"); }
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_spawn: episodes are off (pp_set_episodes comes first: its capture is start record 0)");
     const int n = h->n_scenes, M = sp->n_starts;
     if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts must be 1 .. DMPP_EPISODE_MAX_STARTS");
@@ -2051,20 +2066,15 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     if (M > 1 && (!starts_in || !starts_state)) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts > 1 needs the start records");
     if (M > 1 && (h->resident_mode != 1 || !h->have_map))
         return fail(PP_ERR_STATE, "pp_set_episode_spawn: start records are placed on the resident map (pp_set_map + pp_set_egos come first)");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged): nobody reads the pool in force
-    PP_TRY(h->rollout.adv.wait(h->stream));
+    PP_TRY(quiesce(h, false));                            // nobody reads the pool in force
     // The new pool, its stats included, is built in the set that is NOT in force (or was last): a refusal below leaves the one in
     // force - and the readable stats of a model that went off - untouched
     const int o = h->spawn.ever ? 1 - h->spawn.cur : h->spawn.cur, stride = (n + 1) & ~1;
     const size_t recs = (size_t)M * (size_t)stride;       // room first: a failed allocation changes nothing
-    { int r = h->spawn.d_in[o].reserve(recs); if (r) return r; }
-    { int r = h->spawn.d_state[o].reserve(recs); if (r) return r; }
-    { int r = h->spawn.d_stats[o].reserve((size_t)h->caps.max_scenes); if (r) return r; }
-    const bool was_on = h->spawn.on, reset_was_on = h->treset.on, log_was_on = h->elog.on;
+    PP_TRY(h->spawn.d_in[o].reserve(recs)); PP_TRY(h->spawn.d_state[o].reserve(recs)); PP_TRY(h->spawn.d_stats[o].reserve((size_t)h->caps.max_scenes));
+    const unsigned was = feature_mask(h) & (dmpp::kSpawn | dmpp::retires(dmpp::kSetSpawn));
     h->spawn.on = false;                                  // (until everything below has landed: a failed copy leaves the spawn model off, not half a pool)
-    h->treset.on = false;                                 // (the traffic reset of §4m reads cur_start of the model in force: it goes with it)
-    h->elog.on = false;                                   // (... and so does the episode log of §4n)
+    retire(h, dmpp::kSetSpawn);                           // (the traffic reset of §4m and the episode log of §4n read cur_start of the model in force: they go with it)
     SceneIn* pin = h->spawn.d_in[o]; SceneState* pst = h->spawn.d_state[o];
     HIP_TRY(hipMemcpyAsync(pin, h->episode.d_start_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(pst, h->episode.d_start_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
@@ -2086,14 +2096,14 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     }
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's arrays may go; the upload stream reads the pool from its next launch on
     if (bad) {
-        h->spawn.on = was_on; h->treset.on = reset_was_on; h->elog.on = log_was_on;      // (nothing in force was touched)
+        switch_features(h, was, true);                    // (nothing in force was touched: spawn model, traffic reset and log are as they were)
         return fail(PP_ERR_ARG, "pp_set_episode_spawn: " + std::to_string(bad) + " start record(s) name a road or lane outside the map");
     }
     if (o != h->spawn.cur) {                              // the pool that was in force goes (nobody reads it: joined and waited above); its stats are 80 B a scene and stay
         h->spawn.d_in[h->spawn.cur] = DevBuf<SceneIn>(); h->spawn.d_state[h->spawn.cur] = DevBuf<SceneState>();
     }
     h->spawn.sp = *sp; h->spawn.stride = stride; h->spawn.cur = o; h->spawn.on = true; h->spawn.ever = true;
-    return PP_OK;
+    return features_ok(h, "pp_set_episode_spawn");
 }
 
 int pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n)
@@ -2101,9 +2111,7 @@ int pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n)
     if (!h || !out) return fail(PP_ERR_ARG, "null argument");
     if (!h->spawn.ever) return fail(PP_ERR_STATE, "pp_get_episode_spawn_stats: pp_set_episode_spawn was never called on this handle");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
-    HIP_TRY(hipSetDevice(h->device));
-    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_episode_stats
-    return fetch(h, out, h->spawn.d_stats[h->spawn.cur], (size_t)n * sizeof(EpisodeSpawnStats));
+    return fetch_behind_advance(h, out, h->spawn.d_stats[h->spawn.cur], (size_t)n * sizeof(EpisodeSpawnStats), false);      // a staged advance included, as pp_get_episode_stats
 }
 
 // Episode traffic reset.  Everything is checked on the host before anything changes; the new table and its counters
@@ -2111,8 +2119,8 @@ int pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n)
 int pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_traffic: an update is staged for the next tick (set the traffic reset before staging, or after the tick)");
-    if (n_sets == 0) { h->treset.on = false; return PP_OK; }
+    PP_TRY(refuse_if_staged(h, "pp_set_episode_traffic", "the traffic reset"));
+    if (n_sets == 0) { h->treset.on = false; return features_ok(h, "pp_set_episode_traffic"); }
     if (!h->traffic.on) return fail(PP_ERR_STATE, "pp_set_episode_traffic: no traffic is set (pp_set_traffic comes first)");
     if (h->traffic.world) return fail(PP_ERR_STATE, "pp_set_episode_traffic: world traffic is in force (one vehicle belongs to many egos: a reset has no owner)");
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_traffic: episodes are off (pp_set_episodes comes first)");
@@ -2125,13 +2133,9 @@ int pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
         if (!std::isfinite(starts[i].s)) return fail(PP_ERR_ARG, "pp_set_episode_traffic: start state " + std::to_string(i) + " has a non-finite s");
         if (!std::isfinite(starts[i].v) || starts[i].v < 0) return fail(PP_ERR_ARG, "pp_set_episode_traffic: start state " + std::to_string(i) + ": v must be finite and >= 0");
     }
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged) ...
-    PP_TRY(h->rollout.adv.wait(h->stream));               // ... and the upload stream, which writes s / v, is behind the last of them
+    PP_TRY(quiesce(h, false));                            // (the upload stream, which writes s / v, is behind the last advance)
     const int o = h->treset.ever ? 1 - h->treset.cur : h->treset.cur;
-    { int r = h->treset.d_scene.reserve(n); if (r) return r; }      // room first: a failed allocation changes nothing
-    { int r = h->treset.d_starts[o].reserve((size_t)n_sets * n); if (r) return r; }
-    { int r = h->treset.d_resets[o].reserve(n); if (r) return r; }
+    PP_TRY(h->treset.d_scene.reserve(n)); PP_TRY(h->treset.d_starts[o].reserve((size_t)n_sets * n)); PP_TRY(h->treset.d_resets[o].reserve(n));      // room first: a failed allocation changes nothing
     // (d_scene is single: while the reset is on it holds the scenes of the traffic in force, which is what is written again)
     HIP_TRY(hipMemcpyAsync(h->treset.d_scene, h->traffic.scene_of.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     TrafficStart* tab = h->treset.d_starts[o];
@@ -2147,7 +2151,7 @@ int pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's array may go; the upload stream reads the table from its next launch on
     if (o != h->treset.cur) h->treset.d_starts[h->treset.cur] = DevBuf<TrafficStart>();      // the table that was in force goes; its counters are 4 B an actor and stay
     h->treset.n_sets = n_sets; h->treset.actors = (int)n; h->treset.cur = o; h->treset.on = true; h->treset.ever = true;
-    return PP_OK;
+    return features_ok(h, "pp_set_episode_traffic");
 }
 
 int pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n)
@@ -2156,10 +2160,7 @@ int pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n)
     if (!h->treset.ever) return fail(PP_ERR_STATE, "pp_get_episode_traffic_resets: pp_set_episode_traffic was never called on this handle");
     if (n < 0 || n > h->treset.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_traffic_state
-    if (h->in_staged >= 0) PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
-    return fetch(h, n_resets, h->treset.d_resets[h->treset.cur], (size_t)n * sizeof(int32_t));
+    return fetch_behind_advance(h, n_resets, h->treset.d_resets[h->treset.cur], (size_t)n * sizeof(int32_t), true);      // waits as pp_get_traffic_state does
 }
 
 // Episode log.  Everything is checked on the host before anything changes.
@@ -2167,17 +2168,13 @@ int pp_set_episode_log(pp_handle h, int cap)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (cap < 0 || cap > DMPP_EPISODE_LOG_MAX) return fail(PP_ERR_ARG, "pp_set_episode_log: cap must be 0 .. DMPP_EPISODE_LOG_MAX");
-    if (h->in_staged >= 0) return fail(PP_ERR_STATE, "pp_set_episode_log: an update is staged for the next tick (set the log before staging, or after the tick)");
-    if (cap == 0) { h->elog.on = false; return PP_OK; }
+    PP_TRY(refuse_if_staged(h, "pp_set_episode_log", "the log"));
+    if (cap == 0) { h->elog.on = false; return features_ok(h, "pp_set_episode_log"); }
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_log: episodes are off (pp_set_episodes comes first)");
-    HIP_TRY(hipSetDevice(h->device));
-    { int r = join_all(h); if (r) return r; }             // every advance so far was adopted by a tick (nothing is staged) ...
-    PP_TRY(h->rollout.adv.wait(h->stream));               // ... and the upload stream, which appends, is behind the last of them
+    PP_TRY(quiesce(h, false));                            // (the upload stream, which appends, is behind the last advance)
     const size_t ns = (size_t)h->caps.max_scenes;         // room first: a failed allocation changes nothing
-    { int r = h->elog.d_ring.reserve((size_t)cap); if (r) return r; }
-    { int r = h->elog.d_total.reserve(1); if (r) return r; }
-    { int r = h->elog.d_start_of.reserve(ns); if (r) return r; }
-    if (h->score.on) { int r = h->elog.d_score.reserve(ns); if (r) return r; }
+    PP_TRY(h->elog.d_ring.reserve((size_t)cap)); PP_TRY(h->elog.d_total.reserve(1)); PP_TRY(h->elog.d_start_of.reserve(ns));
+    if (h->score.on) PP_TRY(h->elog.d_score.reserve(ns));
     HIP_TRY(hipMemsetAsync(h->elog.d_total, 0, sizeof(long long), h->stream));
     static_assert(sizeof(EpisodeSpawnStats) == 80 && offsetof(EpisodeSpawnStats, cur_start) == 12, "cur_start is gathered out of the spawn stats");
     if (h->spawn.on)      // the start record every running episode is on
@@ -2190,23 +2187,18 @@ int pp_set_episode_log(pp_handle h, int cap)
     }
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the upload stream reads all of it from its next launch on
     h->elog.cap = cap; h->elog.seq = 0; h->elog.read = 0; h->elog.lost = 0; h->elog.on = true; h->elog.ever = true;
-    return PP_OK;
+    return features_ok(h, "pp_set_episode_log");
 }
 
-// records appended since the set call, a staged advance included (host wait)
-static int episode_log_total(pp_handle h, long long* total)
-{
-    HIP_TRY(hipSetDevice(h->device));
-    PP_TRY(h->rollout.adv.wait(h->stream));               // a staged advance included, as pp_get_episode_stats
-    return fetch(h, total, h->elog.d_total, sizeof(long long));
-}
+// records appended since the set call, a staged advance included as in pp_get_episode_stats (host wait)
+static int episode_log_total(pp_handle h, long long* total) { return fetch_behind_advance(h, total, h->elog.d_total, sizeof(long long), false); }
 
 int pp_read_episode_log(pp_handle h, EpisodeRecord* out, int max_records, long long* n_lost)
 {
     if (!h || max_records < 0 || (!out && max_records > 0)) return fail(PP_ERR_ARG, "pp_read_episode_log: null argument or negative count");
     if (!h->elog.ever) return fail(PP_ERR_STATE, "pp_read_episode_log: pp_set_episode_log was never called on this handle");
     long long total = 0;
-    { int r = episode_log_total(h, &total); if (r) return r; }
+    PP_TRY(episode_log_total(h, &total));
     const long long cap = h->elog.cap, oldest = std::max(h->elog.read, total - cap), lost = oldest - h->elog.read;
     const long long n = std::min(total - oldest, (long long)max_records);
     const long long i0 = oldest % cap, n0 = std::min(n, cap - i0);      // the run up to the end of the ring, then the run from its start
@@ -2223,7 +2215,7 @@ int pp_get_episode_log_info(pp_handle h, long long* total, long long* lost_total
     if (!h) return fail(PP_ERR_ARG, "null handle");
     if (!h->elog.ever) return fail(PP_ERR_STATE, "pp_get_episode_log_info: pp_set_episode_log was never called on this handle");
     long long t = 0;
-    { int r = episode_log_total(h, &t); if (r) return r; }
+    PP_TRY(episode_log_total(h, &t));
     if (total) *total = t;
     if (lost_total) *lost_total = h->elog.lost + std::max(0ll, t - (long long)h->elog.cap - h->elog.read);      // (what the next read will report included)
     return PP_OK;
@@ -2239,14 +2231,14 @@ void pp_default_grid_follow(GridFollow* gf)
 int pp_set_grid_follow(pp_handle h, const GridFollow* gf)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    if (!gf) { h->grid_follow = GridFollow{ 0, 0 }; return PP_OK; }
+    if (!gf) { h->grid_follow = GridFollow{ 0, 0 }; return features_ok(h, "pp_set_grid_follow"); }
     if (gf->goal_point < 1 || gf->goal_point > DMPP_PATH_POINTS - 1)
         return fail(PP_ERR_ARG, "pp_set_grid_follow: goal_point must be 1 .. " + std::to_string(DMPP_PATH_POINTS - 1));
     if (gf->margin_cells < 0) return fail(PP_ERR_ARG, "pp_set_grid_follow: margin_cells must be >= 0");
     if (2LL * gf->margin_cells >= (long long)std::min(h->cfg.grid_w, h->cfg.grid_h))
         return fail(PP_ERR_ARG, "pp_set_grid_follow: 2 * margin_cells must be smaller than min(grid_w, grid_h)");
     h->grid_follow = *gf;
-    return PP_OK;
+    return features_ok(h, "pp_set_grid_follow");
 }
 
 int pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap)
@@ -2603,6 +2595,10 @@ int pp_search_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget
     if (slots_out) *slots_out = b.slots;
     return PP_OK;
 }
+// the rollout feature table (rollout_features.hpp), without a device: the feature bits a cause retires (-1: no such cause), and
+// whether a set of features may be on together
+int pp_feature_retires(int cause) { return cause >= 0 && cause < dmpp::kCauseCount ? (int)dmpp::retires(cause) : -1; }
+int pp_feature_consistent(unsigned mask, int have_map, int resident_mode) { return dmpp::consistent(mask, have_map != 0, resident_mode) ? 1 : 0; }
 void* pp_stream(pp_handle h) { return h && !flush_group(h) ? (void*)h->stream : nullptr; }
 
 size_t pp_sizeof(int which)

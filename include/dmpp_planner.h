@@ -228,8 +228,8 @@ int  pp_get_rollout_score(pp_handle h, RolloutScore* out, int n_scenes);
  * DMPP_FLEET_MAX_PEERS, range finite and > 0, radius finite and >= 0, world_first as above (PP_ERR_ARG); no resident scenes or an
  * update staged for the next tick: PP_ERR_STATE.  The resident set is coupled inside the call (the next tick sees the peers); one
  * host wait.  n_worlds = 0 (pointers may be NULL): fleet off, the resident records get their own slices back.  pp_set_scenes /
- * pp_set_egos / pp_set_n_scenes switch the fleet off too.  A handle that never calls pp_set_fleet allocates and launches none of
- * this.  Peers have no velocity and no orientation; a world lives on one handle.  A scene that an earlier streamed update POISONED
+ * pp_set_egos / pp_set_n_scenes switch the fleet off too (every such rule in one table: DESIGN.md §7, "Feature life cycle").
+ * A handle that never calls pp_set_fleet allocates and launches none of this.  Peers have no velocity and no orientation; a world lives on one handle.  A scene that an earlier streamed update POISONED
  * carries obs_off = 0, obs_n = 0: its peer slots would be [0, K), which collide with the slice of whichever scene owns the start
  * of the pool, and the call is refused with the overlap message - set good scenes first. */
 void pp_default_fleet_model(FleetModel* fm);         /* range 60 m, radius half the default Vehicle_Width, 8 peers */
@@ -254,7 +254,7 @@ int  pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap);
  * tick.  PP_ERR_ARG: a bad route_first, a road_num outside the map, pre_points < 0.  Nothing changes on these.  (A device error
  * during the upload itself, PP_ERR_HIP, leaves routing off: never half a route.)  One host wait.
  * n_legs_total = 0 (pointers may be NULL): routing off; pp_set_scenes / pp_set_egos / pp_set_n_scenes / pp_set_map switch it off
- * too.  A handle that never calls pp_set_route allocates and launches none of this. */
+ * too (§7, "Feature life cycle").  A handle that never calls pp_set_route allocates and launches none of this. */
 int  pp_default_route_model(RouteModel* rm);         /* pre_points 60: 30 m of 0.5 m points */
 int  pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int32_t* route_first, const RouteModel* rm);
 
@@ -296,7 +296,7 @@ int  pp_set_grid_follow(pp_handle h, const GridFollow* gf);
  * a non-finite s0 or speed, a radius that is not finite or is negative, a scene or track out of range, a slot outside the scene's
  * own entries (the resident obs_n, or - fleet set - the pinned n_own), two actors on one (scene, slot).  One host wait.
  * n_actors = 0 (pointers may be NULL): traffic off - the entries keep the last pose written and are plain obstacles again.
- * pp_set_scenes / pp_set_egos / pp_set_n_scenes switch it off too; pp_set_map and pp_set_config do not.  A handle that never calls
+ * pp_set_scenes / pp_set_egos / pp_set_n_scenes switch it off too; pp_set_map and pp_set_config do not (§7, "Feature life cycle").  A handle that never calls
  * pp_set_traffic allocates and launches none of this. */
 int  pp_set_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks, const GlobalPoint2D* points, int n_points,
                     int n_actors, const TrafficActor* actors);
@@ -345,7 +345,7 @@ int  pp_get_traffic_speed(pp_handle h, double* v, int n);
  * REQUIRES A FLEET: the worlds and the pinned slices are the fleet's (max_peers = 0 is a legal fleet for callers who want shared
  * traffic without peer obstacles).  Every SUCCESSFUL later pp_set_fleet switches world traffic off, n_worlds = 0 included - the
  * worlds it was pinned to are gone -; a refused pp_set_fleet changes nothing; pp_set_scenes / pp_set_egos / pp_set_n_scenes
- * switch it off as they do scene traffic and the fleet.  (Scene traffic keeps its relation to pp_set_fleet: either order.)
+ * switch it off as they do scene traffic and the fleet (§7, "Feature life cycle").  (Scene traffic keeps its relation to pp_set_fleet: either order.)
  * Checked on the host, with nothing changed on failure.  PP_ERR_STATE: no resident scenes, an update staged for the next tick, no
  * fleet.  PP_ERR_ARG: everything pp_set_traffic refuses in tracks, points, s0, speed and radius; a world out of range; a slot that
  * is not an own entry of some member scene (the message names the first such scene); two actors on one (world, slot).  One host
@@ -367,7 +367,7 @@ int  pp_set_world_traffic(pp_handle h, int n_tracks, const TrafficTrack* tracks,
  * k_sanitise_scenes run behind it and see the restarted ego in the same set.  A scene frozen by a flag outside the mask stays
  * frozen until a timeout.  Every step is specified (§4k): a numpy restatement gives the same bytes.
  * A second call captures again and restarts the stats.  em NULL: episodes off - the stats stay readable and flagged egos freeze
- * again as in §4c.  pp_set_scenes / pp_set_egos / pp_set_n_scenes switch episodes off, like the fleet.
+ * again as in §4c.  pp_set_scenes / pp_set_egos / pp_set_n_scenes switch episodes off, like the fleet (§7, "Feature life cycle").
  * CALL IT LAST: later pp_set_route / pp_set_state / pp_set_grid_follow / pp_set_fleet / pp_set_traffic* / pp_set_world_traffic do
  * not touch the captured records - a restart puts back the slices, the state and the leg index of the capture.
  * PP_ERR_STATE: no resident scenes, or an update staged for the next tick.  PP_ERR_ARG: bits outside 31 in end_mask, max_ticks < 0,
@@ -396,7 +396,7 @@ int  pp_get_episode_stats(pp_handle h, EpisodeStats* out, int n_scenes);
  * that is not finite or is negative, order outside 0 | 1, check & ~3, NULL arrays with n_starts > 1, a record that names a road or
  * lane outside the map.  Nothing changes on any of these.  One host wait.
  * sp NULL: the spawn model off, k_respawn_egos runs again, the stats stay readable.  Every successful pp_set_episodes - NULL
- * included - switches it off (its record 0 is gone), and so do pp_set_scenes / pp_set_egos / pp_set_n_scenes.
+ * included - switches it off (its record 0 is gone), and so do pp_set_scenes / pp_set_egos / pp_set_n_scenes (§7, "Feature life cycle").
  * pp_get_episode_spawn_stats waits as pp_get_episode_stats does; PP_ERR_STATE on a handle that never set a spawn model. */
 void pp_default_episode_spawn(EpisodeSpawn* sp);     /* seed 1, clearance 2 m, n_starts 1, order 0, contact 1, check 3 */
 int  pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* starts_in, const SceneState* starts_state);
@@ -420,7 +420,7 @@ int  pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n_scene
  * every start record uses set 0.  n_sets == 0: the reset off.  A second call builds a new table and restarts the counters.
  * CALL IT LAST: every successful pp_set_traffic / pp_set_world_traffic / pp_set_traffic_follow / pp_set_episodes /
  * pp_set_episode_spawn (NULL or n = 0 included), and pp_set_scenes / pp_set_egos / pp_set_n_scenes through them, switches the reset
- * off - each invalidates what the table was captured from.
+ * off - each invalidates what the table was captured from (§7, "Feature life cycle").
  * Refused with nothing changed - PP_ERR_STATE: no per-scene traffic on (world traffic, §4j, has no owning scene: out of scope),
  * episodes off, an update staged for the next tick.  PP_ERR_ARG: n_sets < 0 or neither 1 nor n_starts, NULL starts with n_sets > 1,
  * an s that is not finite, a v that is not finite or is < 0.  One host wait, behind every tick and advance enqueued so far.
@@ -445,7 +445,7 @@ int  pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n);
  * episode ends, pp_score_begin is called or a set call restarts the totals.  Its grid half stays at the starting values.  Without
  * pp_score_begin the record carries the starting values (n_ticks == 0).
  * CALL IT LAST: every successful pp_set_episodes / pp_set_episode_spawn (NULL included), and pp_set_scenes / pp_set_egos /
- * pp_set_n_scenes through them, switch the log off.  cap == 0: the log off; what was logged stays readable.  A second call with
+ * pp_set_n_scenes through them, switch the log off (§7, "Feature life cycle").  cap == 0: the log off; what was logged stays readable.  A second call with
  * cap > 0 starts a new log (total 0, seq 0, nothing unread).  PP_ERR_ARG: cap < 0 or > DMPP_EPISODE_LOG_MAX.  PP_ERR_STATE: an update
  * staged for the next tick; cap > 0 with episodes off.  A refused call changes nothing.  One host wait, behind every tick and advance
  * enqueued so far.  A handle that never makes the call allocates and launches none of this.
@@ -539,7 +539,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
  * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
- * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart */
+ * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);
@@ -556,6 +556,16 @@ int pp_tick_group_const(int which);
  * Out (any may be NULL): the new budget, whether it now comes from a need, the slots.  No device needed. */
 int pp_search_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget_max, int n_cus, int n_scenes, int group, int n_obs_total,
                      int need, int budget, int from_need, int mode, int32_t* budget_out, int32_t* from_need_out, int32_t* slots_out);
+/* The rollout feature table ("Feature life cycle"): which features a successful set call switches off, and what holds
+ * between the features that are on.  Feature bits: 1 fleet, 2 route, 4 traffic per scene, 8 world traffic, 16 traffic follow,
+ * 32 episodes, 64 spawn model, 128 traffic reset, 256 episode log.  Causes: 0 pp_set_scenes / pp_set_egos / pp_set_n_scenes, 1 pp_set_map,
+ * 2 pp_set_fleet, 3 pp_set_route, 4 pp_set_traffic, 5 pp_set_world_traffic, 6 pp_set_traffic_follow, 7 pp_set_episodes,
+ * 8 pp_set_episode_spawn, 9 pp_set_episode_traffic, 10 pp_set_episode_log (2 + i: the set call of feature bit i), 11 pp_set_traffic /
+ * pp_set_world_traffic with no actors, 12 pp_set_grid_follow, 13 pp_score_begin / pp_score_end.  pp_feature_retires: the bits the cause switches off, -1 for no such cause.
+ * pp_feature_consistent: 1 when the features in `mask` may be on together on a handle with / without a resident map and with that
+ * resident mode (0 pp_set_scenes, 1 pp_set_egos), else 0.  No device needed. */
+int pp_feature_retires(int cause);
+int pp_feature_consistent(unsigned mask, int have_map, int resident_mode);
 /* The search keeps a scene's obstacle bitmaps sparse in LDS; a launch gives every scene `lds_budget_words` words per view
  * (sized from what the densest scene of an earlier tick needed) and a scene that needs more is searched on dense bitmaps
  * in HBM instead.  After a tick: the budget of that tick, the words the densest scene seen so far needed, and how many
