@@ -123,6 +123,14 @@ TrafficStart = _dt([("s", f8), ("v", f8)])
 EPISODE_LOG_MAX = 1 << 20
 EpisodeRecord = _dt([("scene", i4), ("episode", i4), ("start", i4), ("cause", i4), ("age", i4), ("seq", i4), ("tick", np.int64),
                      ("dist", f8), ("end_pos", GlobalPoint2D), ("end_speed", f8), ("score", RolloutScore)])
+# score trace: a ring of the last scored ticks per scene, frozen shortly after an incident
+SCORE_TRACE_MAX = 256
+TRACE_COLLISION, TRACE_NEAR, TRACE_FLAG, TRACE_BRAKE = 1, 2, 4, 8          # cause bits (DMPP_TRACE_*)
+TICK_REPLAN, TICK_OB_FLAG, TICK_DESACC, TICK_START = 1, 2, 4, 8            # low bits of ScoreTick.marks (DMPP_TICK_*)
+ScoreTraceModel = _dt([("depth", i4), ("post", i4), ("trigger", i4), ("flag_mask", i4), ("near", f8), ("brake", f8)])
+ScoreTick = _dt([("k", i4), ("flags", i4), ("tick", np.int64), ("x", f8), ("y", f8), ("v", f8), ("clearance", f8), ("obs", i4), ("ob_type", i4),
+                 ("behavior", i4), ("marks", i4)])
+ScoreTraceInfo = _dt([("n_written", i4), ("state", i4), ("trigger_k", i4), ("trigger", i4), ("post_left", i4), ("n_trigger_ticks", i4), ("_pad", i4, (2,))])
 
 # one scene, one call (pp_tick_io): the pinned block that carries the inputs, the state and the outputs of the latency path
 PP_OK, PP_ERR_ARG, PP_ERR_HIP, PP_ERR_CAPACITY, PP_ERR_STATE = 0, -1, -2, -3, -4
@@ -174,6 +182,9 @@ _FEATURES = [
     ("pp_set_episode_traffic", {"pp_set_episode_traffic": ([_vp, _ci, _vp], _ci), "pp_get_episode_traffic_resets": ([_vp, _vp, _ci], _ci)}, {33: TrafficStart}),
     ("pp_set_episode_log", {"pp_set_episode_log": ([_vp, _ci], _ci), "pp_read_episode_log": ([_vp, _vp, _ci, _pll], _ci),
                             "pp_get_episode_log_info": ([_vp, _pll, _pll], _ci)}, {34: EpisodeRecord}),
+    ("pp_set_score_trace", {"pp_default_score_trace": ([_vp], None), "pp_set_score_trace": ([_vp, _vp], _ci),
+                            "pp_get_score_trace_info": ([_vp, _vp, _ci], _ci), "pp_read_score_trace": ([_vp, _ci, _vp, _ci, _vp, _ci], _ci)},
+     {35: ScoreTraceModel, 36: ScoreTick, 37: ScoreTraceInfo}),
 ]
 
 _lib = None
@@ -325,6 +336,12 @@ def default_episode_spawn():
     """EpisodeSpawn record of the episode spawn model (pp_default_episode_spawn): seed 1, clearance 2 m, n_starts 1, order 0 (hashed),
     contact 1, check 3 (the obstacle slice and the egos of the world)."""
     return _default(EpisodeSpawn, "pp_default_episode_spawn")
+
+
+def default_score_trace():
+    """ScoreTraceModel record of the score trace (pp_default_score_trace): depth 64, post 8, trigger TRACE_COLLISION, flag_mask 0,
+    near 0.5 m, brake 6 m/s^2."""
+    return _default(ScoreTraceModel, "pp_default_score_trace")
 
 
 def default_traffic_follow():
@@ -534,6 +551,35 @@ class Planner:
         out = np.zeros(self.n, RolloutScore)
         _check(self.lib.pp_get_rollout_score(self.h, _ptr(out), self.n))
         return out
+
+    # ---- score trace: the last scored ticks of every scene, frozen on an incident ------------------
+    def set_score_trace(self, model=None, off=False):
+        """pp_set_score_trace, before or after score_begin: every scene gets a ring of model.depth ScoreTick records
+        on the device; while the scorecard is on every scored tick stores one, and a ring freezes model.post ticks after a tick that
+        meets a cause of model.trigger.  model None: the default model.  A second call starts again.  off=True: the recorder off;
+        rings and headers stay readable."""
+        if off:
+            _check(self.lib.pp_set_score_trace(self.h, None))
+            return
+        m = default_score_trace() if model is None else np.array(model, ScoreTraceModel).reshape(1).copy()
+        _check(self.lib.pp_set_score_trace(self.h, _ptr(m)))
+        self.score_trace_depth = int(m["depth"][0])
+
+    def score_trace_info(self):
+        """pp_get_score_trace_info: the ScoreTraceInfo headers, the last enqueued tick included (host wait)."""
+        out = np.zeros(self.n, ScoreTraceInfo)
+        _check(self.lib.pp_get_score_trace_info(self.h, _ptr(out), self.n))
+        return out
+
+    def read_score_trace(self, scene, rearm=False, cap=None):
+        """pp_read_score_trace: (the ScoreTick records of the scene's ring, oldest first, the ScoreTraceInfo header they were read
+        under); rearm: the header goes back to armed behind the read, the ring and n_written stay (host wait)."""
+        want = getattr(self, "score_trace_depth", 0) if cap is None else int(cap)
+        out, info = np.zeros(max(want, 1), ScoreTick), np.zeros(1, ScoreTraceInfo)
+        n = self.lib.pp_read_score_trace(self.h, int(scene), _ptr(out), want, _ptr(info), 1 if rearm else 0)
+        if n < 0:
+            _check(n)
+        return out[:n].copy(), info[0].copy()
 
     # ---- fleet coupling: the egos of one world are each other's obstacles ------------------
     def set_fleet(self, world_first=None, fm=None):

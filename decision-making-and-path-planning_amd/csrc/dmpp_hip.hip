@@ -239,6 +239,14 @@ struct EpisodeLogState {
     bool on = false, ever = false; int cap = 0, seq = 0; long long read = 0, lost = 0;
     DevBuf<EpisodeRecord> d_ring; DevBuf<long long> d_total; DevBuf<int32_t> d_start_of; DevBuf<RolloutScore> d_score;
 };
+// score trace (first pp_set_score_trace): the model, caps.max_scenes rings of tm.depth records and one header per
+// scene.  It lives inside the scorecard's life cycle - no rollout feature, no set call retires it: while it AND the scorecard are on,
+// a scored tick runs k_score_ego<., true>, and whatever restarts the scorecard (reset_scores) restarts the headers.  Rings and
+// headers stay readable after it went off
+struct ScoreTraceState {
+    bool on = false, ever = false; ScoreTraceModel tm = {};
+    DevBuf<ScoreTick> d_ring; DevBuf<ScoreTraceInfo> d_info;
+};
 
 }  // namespace
 
@@ -333,6 +341,7 @@ struct pp_planner {
     SpawnState spawn;
     TrafficResetState treset;
     EpisodeLogState elog;
+    ScoreTraceState strace;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
@@ -879,6 +888,16 @@ static int reset_ego_flags(pp_handle h)
     return PP_OK;
 }
 
+// The headers of the score trace at their starting values (§4o), on the handle's stream: behind join_all, as reset_scores.
+static int reset_score_trace(pp_handle h)
+{
+    if (!h->strace.d_info) return PP_OK;
+    const int ns = h->caps.max_scenes;
+    hipLaunchKernelGGL(dmpp::k_score_trace_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->strace.d_info);
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+
 // The scorecard's starting values, on the handle's stream behind join_all (every scoring kernel enqueued so far has finished
 // before it); the caller's host wait follows.
 static int reset_scores(pp_handle h)
@@ -892,6 +911,7 @@ static int reset_scores(pp_handle h)
         hipLaunchKernelGGL(dmpp::k_score_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->elog.d_score);
         HIP_TRY(hipGetLastError());
     }
+    if (h->strace.on) PP_TRY(reset_score_trace(h));       // the score trace restarts where the scorecard does (§4o)
     return PP_OK;
 }
 
@@ -1299,12 +1319,17 @@ int pp_plan_tick(pp_handle h)
             hipStream_t su = h->stream_up;
             HIP_TRY(hipStreamWaitEvent(su, rec.ev_front, 0));
             const dim3 sgrid((unsigned)((n + dmpp::kScScenes - 1) / dmpp::kScScenes));
-            if (h->elog.on && h->elog.d_score)      // episode log: the tick is folded into the scorecards of the running episodes too (§4n 3.)
-                hipLaunchKernelGGL(dmpp::k_score_ego<true>, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total,
-                                   h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, h->elog.d_score);
-            else
-                hipLaunchKernelGGL(dmpp::k_score_ego<false>, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total,
-                                   h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, (RolloutScore*)nullptr);
+            // episode log: the tick is folded into the scorecards of the running episodes too (§4n 3.); score trace: lane 0 stores the
+            // tick's record into the scene's ring in front of the fold (§4o) - EpisodeStats only while episodes are on
+            const bool log = h->elog.on && h->elog.d_score, trace = h->strace.on;
+            RolloutScore* ep_score = log ? h->elog.d_score.get() : nullptr;
+            const EpisodeStats* ep_stats = trace && h->episode.on ? h->episode.d_stats.get() : nullptr;
+            ScoreTraceInfo* tinfo = trace ? h->strace.d_info.get() : nullptr;
+            ScoreTick* tring = trace ? h->strace.d_ring.get() : nullptr;
+            auto* kern = log ? (trace ? dmpp::k_score_ego<true, true> : dmpp::k_score_ego<true, false>) : (trace ? dmpp::k_score_ego<false, true> : dmpp::k_score_ego<false, false>);
+            hipLaunchKernelGGL(kern, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total,
+                               h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, ep_score,
+                               h->tick_seq, h->strace.tm, ep_stats, tinfo, tring);
             PP_TRY(h->score.ego.record(su));
         }
     }
@@ -1727,6 +1752,74 @@ int pp_get_rollout_score(pp_handle h, RolloutScore* out, int n)
             for (int k = 0; k < DMPP_G_STATUS_COUNT; k++) out[s].grid_status_ticks[k] += p.status[k];
         }
     return PP_OK;
+}
+
+// Score trace.  Everything is checked on the host before anything changes.
+void pp_default_score_trace(ScoreTraceModel* m)
+{
+    if (!m) return;
+    m->depth = 64; m->post = 8; m->trigger = DMPP_TRACE_COLLISION; m->flag_mask = 0; m->near = 0.5; m->brake = 6.0;
+}
+
+int pp_set_score_trace(pp_handle h, const ScoreTraceModel* m)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!m) { h->strace.on = false; return PP_OK; }      // (what was recorded stays readable)
+    if (m->depth < 1 || m->depth > DMPP_SCORE_TRACE_MAX) return fail(PP_ERR_ARG, "pp_set_score_trace: depth must be 1 .. DMPP_SCORE_TRACE_MAX");
+    if (m->post < 0 || m->post > m->depth - 1) return fail(PP_ERR_ARG, "pp_set_score_trace: post must be 0 .. depth - 1");
+    if ((m->trigger & ~15) != 0) return fail(PP_ERR_ARG, "pp_set_score_trace: trigger holds bits outside the four DMPP_TRACE_* causes (15)");
+    if ((m->flag_mask & ~31) != 0) return fail(PP_ERR_ARG, "pp_set_score_trace: flag_mask holds bits outside the five DMPP_EGO_* flags (31)");
+    if (!std::isfinite(m->near)) return fail(PP_ERR_ARG, "pp_set_score_trace: near must be finite");
+    if (!std::isfinite(m->brake) || !(m->brake > 0)) return fail(PP_ERR_ARG, "pp_set_score_trace: brake must be finite and > 0");
+    PP_TRY(quiesce(h, false));                            // every scored tick so far is in front of the handle's stream
+    const size_t ns = (size_t)h->caps.max_scenes;         // room first, the headers (allocated once) in front of the ring: a failed allocation changes nothing in force
+    PP_TRY(h->strace.d_info.reserve(ns)); PP_TRY(h->strace.d_ring.reserve(ns * (size_t)m->depth));
+    PP_TRY(reset_score_trace(h));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the upload stream reads all of it from its next launch on
+    h->strace.tm = *m; h->strace.on = true; h->strace.ever = true;
+    return PP_OK;
+}
+
+// the headers behind every scored tick, waiting as pp_get_rollout_score does (host wait)
+static int fetch_trace_info(pp_handle h, ScoreTraceInfo* out, int first, int n)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(join_all(h));
+    if (h->episode.on) PP_TRY(h->rollout.adv.wait(h->stream));
+    HIP_TRY(hipMemcpyAsync(out, h->strace.d_info + first, (size_t)n * sizeof(ScoreTraceInfo), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return PP_OK;
+}
+
+int pp_get_score_trace_info(pp_handle h, ScoreTraceInfo* out, int n_scenes)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->strace.ever) return fail(PP_ERR_STATE, "pp_get_score_trace_info: pp_set_score_trace was never called on this handle");
+    if (n_scenes < 0 || n_scenes > h->n_scenes) return fail(PP_ERR_ARG, "n_scenes exceeds the resident scenes");
+    if (n_scenes == 0) return PP_OK;
+    return fetch_trace_info(h, out, 0, n_scenes);
+}
+
+int pp_read_score_trace(pp_handle h, int scene, ScoreTick* out, int cap, ScoreTraceInfo* info, int rearm)
+{
+    if (!h || cap < 0 || (!out && cap > 0)) return fail(PP_ERR_ARG, "pp_read_score_trace: null argument or negative count");
+    if (!h->strace.ever) return fail(PP_ERR_STATE, "pp_read_score_trace: pp_set_score_trace was never called on this handle");
+    if (scene < 0 || scene >= h->n_scenes) return fail(PP_ERR_ARG, "pp_read_score_trace: no such resident scene");
+    ScoreTraceInfo hd;
+    PP_TRY(fetch_trace_info(h, &hd, scene, 1));
+    const long long depth = h->strace.tm.depth, written = (long long)(uint32_t)hd.n_written, n = std::min(written, depth);      // (unsigned, as the kernel's slot)
+    if (n > (long long)cap) return fail(PP_ERR_CAPACITY, "pp_read_score_trace: the ring holds " + std::to_string(n) + " records, cap is " + std::to_string(cap));
+    const ScoreTick* ring = h->strace.d_ring + (size_t)scene * (size_t)depth;
+    const long long i0 = (written - n) % depth, n0 = std::min(n, depth - i0);      // the run up to the end of the ring, then the run from its start
+    if (n0 > 0) HIP_TRY(hipMemcpyAsync(out, ring + i0, (size_t)n0 * sizeof(ScoreTick), hipMemcpyDeviceToHost, h->stream));
+    if (n > n0) HIP_TRY(hipMemcpyAsync(out + n0, ring, (size_t)(n - n0) * sizeof(ScoreTick), hipMemcpyDeviceToHost, h->stream));
+    if (info) *info = hd;                                 // (the header the records were read under: before a rearm)
+    if (rearm) {      // armed again; the ring and n_written stay, so the next incident keeps its lead-in.  Pageable source: the copy has left `hd` on return
+        hd.state = 0; hd.trigger_k = -1; hd.trigger = 0; hd.post_left = 0;
+        HIP_TRY(hipMemcpyAsync(h->strace.d_info + scene, &hd, sizeof(ScoreTraceInfo), hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return (int)n;
 }
 
 // Every resident scene's OWN obstacle entries (obs_off, obs_n): of the resident records, or - fleet on - the ones pinned then
@@ -2616,6 +2709,7 @@ size_t pp_sizeof(int which)
     case 29: return sizeof(EpisodeModel); case 30: return sizeof(EpisodeStats);
     case 31: return sizeof(EpisodeSpawn); case 32: return sizeof(EpisodeSpawnStats); case 33: return sizeof(TrafficStart);
     case 34: return sizeof(EpisodeRecord);
+    case 35: return sizeof(ScoreTraceModel); case 36: return sizeof(ScoreTick); case 37: return sizeof(ScoreTraceInfo);
     default: return 0;
     }
 }

@@ -80,14 +80,84 @@ __device__ __forceinline__ void score_fold(RolloutScore* __restrict__ score, int
     r.n_ticks = k + 1;
 }
 
+// §4o: the headers of the score trace at their starting values (armed, nothing written, no triggering tick)
+__global__ void __launch_bounds__(kBlock)
+k_score_trace_reset(int n_scenes, ScoreTraceInfo* __restrict__ info)
+{
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_scenes) return;
+    ScoreTraceInfo hd;
+    hd.n_written = 0; hd.state = 0; hd.trigger_k = -1; hd.trigger = 0; hd.post_left = 0; hd.n_trigger_ticks = 0; hd._pad[0] = 0; hd._pad[1] = 0;
+    info[s] = hd;
+}
+
+static_assert(sizeof(ScoreTick) == 64 && offsetof(ScoreTick, k) == 0 && offsetof(ScoreTick, flags) == 4 && offsetof(ScoreTick, tick) == 8 && offsetof(ScoreTick, x) == 16 &&
+              offsetof(ScoreTick, y) == 24 && offsetof(ScoreTick, v) == 32 && offsetof(ScoreTick, clearance) == 40 && offsetof(ScoreTick, obs) == 48 &&
+              offsetof(ScoreTick, ob_type) == 52 && offsetof(ScoreTick, behavior) == 56 && offsetof(ScoreTick, marks) == 60, "ScoreTick layout (DESIGN.md §4o)");
+static_assert(sizeof(ScoreTraceModel) == 32 && sizeof(ScoreTraceInfo) == 32, "ScoreTraceModel / ScoreTraceInfo layout (DESIGN.md §4o)");
+typedef unsigned int TickPiece __attribute__((ext_vector_type(4)));        // (a native vector: one 16-byte store, which the compiler does not take apart)
+struct TickPieces { TickPiece p[4]; };
+static_assert(sizeof(TickPieces) == sizeof(ScoreTick), "the pieces of a record");
+
+// §4o 1. - 4.: one scored tick of scene s into its ring and header (lane 0 of the scene's wave), IN FRONT of score_fold: k and last_speed
+// are those of record s of `score` before the fold.  x, y, v, (md, mi), plan, state, flags: as score_fold; ob_type: the type of the
+// snapshot entry mi names (0 without one); ep_stats: EpisodeStats while episodes are on, else null.
+__device__ __forceinline__ void trace_step(const ScoreTraceModel& tm, ScoreTraceInfo* __restrict__ info, ScoreTick* __restrict__ ring, long long tick,
+                                           const EpisodeStats* __restrict__ ep_stats, const RolloutScore* __restrict__ score, int s, double x, double y, double v,
+                                           double md, int mi, int ob_type, double half_width, double dt_score, const PlanOut* __restrict__ plan,
+                                           const SceneState* __restrict__ state, const int32_t* __restrict__ flags)
+{
+    // 1. the record
+    const PlanOut& po = plan[s];
+    ScoreTick R;
+    R.k = score[s].n_ticks; R.flags = flags ? flags[s] : 0; R.tick = tick; R.x = x; R.y = y; R.v = v;
+    R.clearance = mi >= 0 ? md - half_width : __builtin_huge_val();
+    R.obs = mi >= 0 ? mi : -1; R.ob_type = mi >= 0 ? ob_type : 0;
+    R.behavior = po.dec.behavior;
+    int marks = 0;
+    if (state[s].afresh_planning != 0) marks |= DMPP_TICK_REPLAN;
+    if (po.ob_flag != 0) marks |= DMPP_TICK_OB_FLAG;
+    if (po.result.desaccVd != 0) marks |= DMPP_TICK_DESACC;
+    if (ep_stats && ep_stats[s].age == 0) marks |= DMPP_TICK_START;
+    // 2. the cause word: a NaN compares false everywhere
+    int c = 0;
+    if (mi >= 0 && R.clearance <= 0) c |= DMPP_TRACE_COLLISION;
+    if (mi >= 0 && R.clearance <= tm.near) c |= DMPP_TRACE_NEAR;
+    if ((R.flags & tm.flag_mask) != 0) c |= DMPP_TRACE_FLAG;
+    if (R.k > 0) {
+        const double a = (v - score[s].last_speed) / 3.6 / dt_score, fall = -a;
+        if (fall >= tm.brake) c |= DMPP_TRACE_BRAKE;
+    }
+    c &= tm.trigger;
+    R.marks = marks | (c << 8);
+    // 3., 4. the header and the ring
+    ScoreTraceInfo hd = info[s];
+    if (c != 0) hd.n_trigger_ticks = hd.n_trigger_ticks + 1;
+    if (hd.state != 2) {
+        // 64 B divide into four 16-byte pieces, and a device allocation starts on a 16-byte boundary: so does every record
+        const TickPieces q = __builtin_bit_cast(TickPieces, R);
+        // (unsigned: the slot stays inside the scene's ring whatever the header holds)
+        TickPiece* dst = reinterpret_cast<TickPiece*>(ring + ((size_t)s * (size_t)tm.depth + (size_t)((unsigned)hd.n_written % (unsigned)tm.depth)));
+#pragma unroll
+        for (int i = 0; i < 4; i++) dst[i] = q.p[i];
+        hd.n_written = hd.n_written + 1;
+        if (hd.state == 0 && c != 0) { hd.trigger_k = R.k; hd.trigger = c; hd.post_left = tm.post; hd.state = tm.post > 0 ? 1 : 2; }
+        else if (hd.state == 1) { hd.post_left = hd.post_left - 1; if (hd.post_left == 0) hd.state = 2; }
+    }
+    info[s] = hd;
+}
+
 // obs_cap: entries of a snapshot set; a slice outside it (no set call and no update lets one through) counts as empty.
 // kLog: the episode log is on and the tick is folded a second time, into the scorecard of the scene's running
 // episode, ep_score[s]; without it ep_score is null and never read.
-template <bool kLog>
+// kTrace: the score trace is on and lane 0 stores the tick's record into the scene's ring in front of the fold; without
+// it tick, tm, ep_stats, tinfo and tring are never read, and the kernel is the one without them.
+template <bool kLog, bool kTrace>
 __global__ void __launch_bounds__(kBlock)
 k_score_ego(double half_width, double dt_score, int n_scenes, int obs_cap, const SceneIn* __restrict__ in, const PlanOut* __restrict__ plan,
             const SceneState* __restrict__ state, const ObPoint* __restrict__ now, const int32_t* __restrict__ flags,
-            RolloutScore* __restrict__ score, RolloutScore* __restrict__ ep_score)
+            RolloutScore* __restrict__ score, RolloutScore* __restrict__ ep_score,
+            long long tick, ScoreTraceModel tm, const EpisodeStats* __restrict__ ep_stats, ScoreTraceInfo* __restrict__ tinfo, ScoreTick* __restrict__ tring)
 {
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * kScScenes + (threadIdx.x >> 6);
@@ -107,6 +177,7 @@ k_score_ego(double half_width, double dt_score, int n_scenes, int obs_cap, const
     }
     wave_first_min(md, mi);
     if (lane != 0) return;
+    if (kTrace) trace_step(tm, tinfo, tring, tick, ep_stats, score, s, x, y, v, md, mi, mi >= 0 ? now[off + mi].type : 0, half_width, dt_score, plan, state, flags);
     score_fold(score, s, x, y, v, md, mi, half_width, dt_score, plan, state, flags);
     if (kLog) score_fold(ep_score, s, x, y, v, md, mi, half_width, dt_score, plan, state, flags);
 }

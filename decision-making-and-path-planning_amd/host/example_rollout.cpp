@@ -31,6 +31,9 @@
 // With --route --episodes --log N the episode log is on (pp_set_episode_log): a ring of N records on the device, one
 // record appended per ended episode, drained once behind the run; the scorecard is on, so every record carries its episode's own.
 // The host prints an outcome table per start record: episodes, causes, mean age and metres, worst clearance, episodes with a collision.
+// With --score-trace DEPTH[,POST] the score trace is on (pp_set_score_trace with the default model): every scene keeps its
+// last DEPTH scored ticks in a ring on the device, which freezes POST ticks behind the scene's first contact; behind the run the host
+// prints every frozen scene's triggering tick and, for the first three, the records before it.  Any mode; a routed run gets the scorecard.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <cmath>
@@ -41,10 +44,48 @@
 
 #define CHECK(expr) do { int rc__ = (expr); if (rc__) { std::fprintf(stderr, "%s: %s\n", #expr, pp_last_error()); return 2; } } while (0)
 
+// --score-trace DEPTH[,POST]: the recorder on with the default model (a ring freezes POST ticks behind its first contact)
+static int set_score_trace(pp_handle h, int depth, int post)
+{
+    ScoreTraceModel tm; pp_default_score_trace(&tm);
+    tm.depth = depth; tm.post = post >= 0 ? post : (tm.post < depth ? tm.post : depth - 1);
+    CHECK(pp_set_score_trace(h, &tm));
+    return 0;
+}
+
+// ... and behind the run: every frozen scene's triggering tick, and - for the first three - the records before it
+static int print_score_trace(pp_handle h, int n, int depth)
+{
+    std::vector<ScoreTraceInfo> info((size_t)n); std::vector<ScoreTick> ring((size_t)depth);
+    CHECK(pp_get_score_trace_info(h, info.data(), n));
+    int frozen = 0, shown = 0;
+    for (int s = 0; s < n; s++) frozen += info[(size_t)s].state == 2;
+    std::printf("score trace: %d of %d rings frozen (depth %d)\n", frozen, n, depth);
+    for (int s = 0; s < n; s++) {
+        if (info[(size_t)s].state != 2) continue;
+        ScoreTraceInfo hd;
+        const int got = pp_read_score_trace(h, s, ring.data(), depth, &hd, 0);
+        if (got < 0) { std::fprintf(stderr, "pp_read_score_trace: %s\n", pp_last_error()); return 2; }
+        for (int i = 0; i < got; i++) {
+            const ScoreTick& r = ring[(size_t)i];
+            if (r.k != hd.trigger_k) continue;
+            std::printf("score trace:   scene %d froze on scored tick %d (tick id %lld, cause %d): clearance %.3f m to obstacle %d (type %d) at %.1f km/h, %d records in the ring\n",
+                        s, r.k, (long long)r.tick, hd.trigger, r.clearance, r.obs, r.ob_type, r.v, got);
+        }
+        if (shown++ >= 3) continue;
+        for (int i = 0; i < got && ring[(size_t)i].k <= hd.trigger_k; i++) {
+            const ScoreTick& r = ring[(size_t)i];
+            std::printf("score trace:     k %d  (%.2f, %.2f)  %.1f km/h  clearance %.3f m  behavior %d  marks %d%s\n", r.k, r.x, r.y, r.v, r.clearance, r.behavior,
+                        r.marks & 255, (r.marks & DMPP_TICK_START) ? "  (start record)" : "");
+        }
+    }
+    return 0;
+}
+
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post)
 {
     const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
     if (contact) traffic = true;                      // (the vehicle to touch)
@@ -159,7 +200,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         if (react) { TrafficFollow tf; pp_default_traffic_follow(&tf); CHECK(pp_set_traffic_follow(h, &tf)); }
         CHECK(pp_score_begin(h, model.dt));
     }
-    if (log_cap && !traffic) CHECK(pp_score_begin(h, model.dt));      // (the records carry their episode's scorecard)
+    if ((log_cap || trace_depth) && !traffic) CHECK(pp_score_begin(h, model.dt));      // (the records carry their episode's scorecard; the trace records scored ticks)
     if (episodes) { EpisodeModel em; pp_default_episode_model(&em); CHECK(pp_set_episodes(h, &em)); }      // last: it captures what the calls above set up
     if (spawn) {                                      // M start records per ego: record k stands 5 k lane points behind record 0, on the same lane
         EpisodeSpawn sp; pp_default_episode_spawn(&sp); sp.n_starts = M; sp.contact = contact ? 1 : 0;
@@ -181,9 +222,11 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         CHECK(pp_set_episode_traffic(h, M, M > 1 ? sets.data() : nullptr));
     }
     if (log_cap) CHECK(pp_set_episode_log(h, log_cap));      // last of all
+    if (trace_depth && set_score_trace(h, trace_depth, trace_post)) return 2;      // (no feature: anywhere)
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
+    if (trace_depth && print_score_trace(h, n, trace_depth)) return 2;
     if (log_cap) {
         std::vector<EpisodeRecord> rec((size_t)log_cap);
         long long lost = 0, total = 0;
@@ -293,7 +336,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0, log_cap = 0;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0, log_cap = 0, trace_depth = 0, trace_post = -1;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -306,7 +349,8 @@ int main(int argc, char** argv)
         else if (std::strcmp(argv[a], "--reset-traffic") == 0) reset = true;
         else if (std::strcmp(argv[a], "--starts") == 0 && a + 1 < argc) starts = std::atoi(argv[++a]);
         else if (std::strcmp(argv[a], "--log") == 0 && a + 1 < argc) log_cap = std::atoi(argv[++a]);
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--score-trace") == 0 && a + 1 < argc) { if (std::sscanf(argv[++a], "%d,%d", &trace_depth, &trace_post) < 1) trace_depth = -1; }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow] [--score-trace DEPTH[,POST]]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
@@ -320,7 +364,8 @@ int main(int argc, char** argv)
     if (reset && shared) { std::fprintf(stderr, "--reset-traffic resets per-scene traffic: a vehicle of --shared belongs to a whole world\n"); return 2; }
     if (log_cap && !(route && episodes)) { std::fprintf(stderr, "--log records how episodes ended: use it with --route --episodes\n"); return 2; }
     if (log_cap < 0 || log_cap > DMPP_EPISODE_LOG_MAX) { std::fprintf(stderr, "--log takes 1 .. %d records\n", DMPP_EPISODE_LOG_MAX); return 2; }
-    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap);
+    if (trace_depth < 0 || trace_depth > DMPP_SCORE_TRACE_MAX || (trace_depth && trace_post >= trace_depth)) { std::fprintf(stderr, "--score-trace takes DEPTH 1 .. %d and POST 0 .. DEPTH - 1\n", DMPP_SCORE_TRACE_MAX); return 2; }
+    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;
@@ -350,8 +395,10 @@ int main(int argc, char** argv)
     if (!trace) { std::fprintf(stderr, "pp_host_alloc: %s\n", pp_last_error()); return 2; }
     long long last = 0;
     CHECK(pp_score_begin(h, model.dt));
+    if (trace_depth && set_score_trace(h, trace_depth, trace_post)) return 2;
     CHECK(pp_rollout(h, ticks, &model, trace, &last));
     CHECK(pp_sync(h));
+    if (trace_depth && print_score_trace(h, n, trace_depth)) return 2;
     std::vector<int32_t> flags(n);
     CHECK(pp_get_ego_flags(h, flags.data(), n));
 

@@ -210,6 +210,35 @@ int  pp_score_begin(pp_handle h, double dt_score);
 int  pp_score_end(pp_handle h);
 int  pp_get_rollout_score(pp_handle h, RolloutScore* out, int n_scenes);
 
+/* ---- score trace: the last scored ticks of every scene, frozen on an incident ---------------------------------------
+ * The scorecard says THAT scene 713 first collided at scored tick 4180; the trace says what happened before.  pp_set_score_trace gives
+ * every scene a ring of m->depth ScoreTick records (64 B) and a ScoreTraceInfo header on the device.  While it AND the scorecard are on,
+ * k_score_ego stores one record per scene and scored tick - the ego, its clearance and the obstacle that gave it, the flag word, the
+ * plan's behaviour and counters, the causes the tick met - and a ring whose tick meets a cause of m->trigger takes m->post more ticks
+ * and freezes: the approach is still there when the host comes to read it.  trigger 0: a plain ring that never freezes.  One more
+ * 64-byte store per scene and tick in a kernel that already runs; no kernel, no launch and no host wait is added.
+ * It belongs to the scorecard's life cycle and is no rollout feature: no set call retires it, and what restarts the totals -
+ * pp_score_begin, pp_set_scenes / pp_set_egos / pp_set_n_scenes while scoring is on - puts the headers of a recorder that is on back
+ * to their starting values (armed, n_written 0).  An episode restart does not touch it: k runs on and the tick behind the restart
+ * carries DMPP_TICK_START.
+ * pp_default_score_trace: depth 64, post 8, trigger DMPP_TRACE_COLLISION, flag_mask 0, near 0.5 m, brake 6 m/s^2.
+ * pp_set_score_trace: legal before or after pp_score_begin.  Allocates caps.max_scenes * depth records and the headers, sets every
+ * header to its starting values (a second call starts again) and turns the recorder on; one host wait, behind every tick and advance
+ * enqueued so far.  m == NULL: the recorder off; rings and headers stay readable and no longer change.  PP_ERR_ARG, with nothing
+ * changed: depth outside 1 .. DMPP_SCORE_TRACE_MAX, post outside 0 .. depth - 1, bits outside 15 in trigger or outside 31 in flag_mask,
+ * a near that is not finite, a brake that is not finite and > 0.  A handle that never makes the call allocates and launches
+ * exactly what it did without it.
+ * pp_get_score_trace_info: the headers of the first n_scenes scenes, the last enqueued tick included; waits as pp_get_rollout_score.
+ * pp_read_score_trace: the records of one scene's ring, min(n_written, depth) of them, oldest first (at most two copies), and - info
+ * may be NULL - the header they were read under; returns their number (>= 0; an error code is negative).  PP_ERR_CAPACITY when cap is
+ * smaller than that number, PP_ERR_ARG for a scene outside the resident ones; nothing changes on either.  rearm != 0: the header goes
+ * back to armed (state 0, trigger_k -1, trigger 0, post_left 0) behind the read; the ring and n_written stay, so the next incident
+ * keeps its lead-in.  Both reads: PP_ERR_STATE on a handle that never made the set call. */
+void pp_default_score_trace(ScoreTraceModel* m);
+int  pp_set_score_trace(pp_handle h, const ScoreTraceModel* m);
+int  pp_get_score_trace_info(pp_handle h, ScoreTraceInfo* out, int n_scenes);
+int  pp_read_score_trace(pp_handle h, int scene, ScoreTick* out, int cap, ScoreTraceInfo* info, int rearm);
+
 /* ---- fleet coupling: the egos of one world see each other during a rollout -----------------------------------
  * pp_set_fleet groups the resident scenes into WORLDS: world w is the contiguous run of scenes [world_first[w], world_first[w+1]);
  * world_first has n_worlds + 1 entries, starts at 0, ends at the resident scene count and is strictly increasing (host pointer).
@@ -539,7 +568,8 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 10 DecisionOutPod, 11 LaneView, 12 PlanningOut, 13 PlanningStatus, 14 AimPoint, 15 MapLane, 16 MapJunction,
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
  * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
- * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord */
+ * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord, 35 ScoreTraceModel, 36 ScoreTick,
+ * 37 ScoreTraceInfo */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -416,6 +416,45 @@ typedef struct EpisodeRecord {
     RolloutScore score;         /* the episode's own scorecard: the front half of §4d over the episode's scored ticks; starting values without pp_score_begin */
 } EpisodeRecord;                                                            /* 240 B */
 
+/* ---- score trace (build-defined), inside the scorecard's life cycle ---------------------------------------
+ * pp_set_score_trace gives every scene a ring of `depth` ScoreTick records on the device: while the scorecard is on, every scored
+ * tick stores one compact record, and the ring stops by itself `post` ticks after an incident - contact, a near miss, a hard
+ * brake, an ego flag - so that the approach is still there when the host reads it (pp_read_score_trace). */
+#define DMPP_SCORE_TRACE_MAX 256          /* records per scene */
+/* cause bits (ScoreTraceModel.trigger, ScoreTraceInfo.trigger, ScoreTick.marks >> 8) */
+#define DMPP_TRACE_COLLISION 1   /* the tick has a clearance and clearance <= 0            */
+#define DMPP_TRACE_NEAR      2   /* the tick has a clearance and clearance <= near         */
+#define DMPP_TRACE_FLAG      4   /* (flag word of the tick & flag_mask) != 0               */
+#define DMPP_TRACE_BRAKE     8   /* k > 0 and -a >= brake, a as in §4d 3.                  */
+/* low bits of ScoreTick.marks */
+#define DMPP_TICK_REPLAN 1       /* st.afresh_planning != 0 */
+#define DMPP_TICK_OB_FLAG 2      /* po.ob_flag != 0         */
+#define DMPP_TICK_DESACC 4       /* po.result.desaccVd != 0 */
+#define DMPP_TICK_START 8        /* episodes on and EpisodeStats.age == 0: the tick read a start record */
+typedef struct ScoreTraceModel {
+    int32_t depth;       /* 1 .. DMPP_SCORE_TRACE_MAX records per scene                         */
+    int32_t post;        /* 0 .. depth - 1: ticks recorded after the triggering one             */
+    int32_t trigger;     /* DMPP_TRACE_* that freeze a ring; 0: never freezes (a plain ring)    */
+    int32_t flag_mask;   /* DMPP_EGO_* bits (1 .. 16) for DMPP_TRACE_FLAG                       */
+    double  near;        /* m, finite                                                           */
+    double  brake;       /* m/s^2, finite, > 0                                                  */
+} ScoreTraceModel;                                                          /* 32 B */
+typedef struct ScoreTick {
+    int32_t k, flags;        /* index among the scored ticks (RolloutScore.n_ticks before the fold); ego flag word */
+    int64_t tick;            /* pp_tick_id of the tick */
+    double  x, y, v;         /* si.loc.globalpoint.x / .y, si.loc.velocity (km/h) */
+    double  clearance;       /* §4d 1.; +inf when the tick has none */
+    int32_t obs, ob_type;    /* j* and snapshot[obs_off + j*].type (DMPP_OB_PEER | scene for a peer); -1, 0 without a clearance */
+    int32_t behavior, marks; /* po.dec.behavior as it is; DMPP_TICK_* | cause word of this tick << 8 */
+} ScoreTick;                                                                /* 64 B */
+typedef struct ScoreTraceInfo {
+    int32_t n_written;       /* records written since the start; slot of record i: i % depth */
+    int32_t state;           /* 0 armed, 1 counting post, 2 frozen */
+    int32_t trigger_k, trigger;   /* k and cause word of the triggering tick; -1, 0 while armed */
+    int32_t post_left, n_trigger_ticks;   /* n_trigger_ticks: scored ticks with a cause != 0, frozen or not */
+    int32_t _pad[2];
+} ScoreTraceInfo;                                                           /* 32 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

@@ -32,7 +32,11 @@ into the vehicle that drove on over their start pose (the egos with an episode o
 what a kernel trace of the ONE_ROLLOUT leg gives.
 EPISODES=1 LOG=cap: both legs are the ring rollout with episodes on, and the second leg has the episode log on as well
 (pp_set_episode_log(cap), DESIGN.md §4n: k_log_episodes behind k_respawn_egos); it is drained once behind the timed rollout, outside the
-timing.  SCORE=1 puts the scorecard on in both legs (k_score_ego<true> in the second).  With ONE_ROLLOUT one more leg with the log on alone."""
+timing.  SCORE=1 puts the scorecard on in both legs (k_score_ego<true> in the second).  With ONE_ROLLOUT one more leg with the log on alone.
+SCORE=1 TRACE=depth: every run has a scored rollout leg without and one with the score trace (pp_set_score_trace: the default model with
+`depth` records per scene, DESIGN.md §4o: k_score_ego<false, true> in the place of <false, false>), alternating; headers and one ring are
+read behind the timed rollout, outside the timing.  TRACE_TRIGGER=mask replaces the model's trigger (0: rings that never freeze, so every
+scene stores every tick).  With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels."""
 import os
 import statistics
 import sys
@@ -272,12 +276,21 @@ def follow_run(on):
     return n * steps / dt, off_grid
 
 
-def rollout_run(score=SCORE == "1", follow=False):
+TRACE = int(os.environ.get("TRACE", "0"))
+
+
+def rollout_run(score=SCORE == "1", follow=False, trace=0):
     pl, _ = fresh()
     if follow:
         pl.set_grid_follow(dm.default_grid_follow())
     if score:
         pl.score_begin()
+    if trace > 0:
+        tm = dm.default_score_trace()
+        tm["depth"], tm["post"] = trace, min(int(tm["post"][0]), trace - 1)
+        if os.environ.get("TRACE_TRIGGER"):          # TRACE_TRIGGER=0: plain rings that never freeze - every scene stores every tick
+            tm["trigger"] = int(os.environ["TRACE_TRIGGER"])
+        pl.set_score_trace(tm)
     pl.rollout(warm, model)
     pl.sync()
     t0 = time.perf_counter()
@@ -289,6 +302,12 @@ def rollout_run(score=SCORE == "1", follow=False):
         sc = pl.rollout_score()
         rollout_run.summary = "%d ticks scored, %d scenes with a collision, worst clearance %.3f m, mean distance %.2f m" % (
             int(sc["n_ticks"][0]), int((sc["n_collision_ticks"] > 0).sum()), float(sc["min_clearance"].min()), float(sc["dist"].mean()))
+    if trace > 0:                             # outside the timing: the headers, and the ring of the first frozen scene
+        info = pl.score_trace_info()
+        frozen_rings = np.flatnonzero(info["state"] == 2)
+        got = len(pl.read_score_trace(int(frozen_rings[0]))[0]) if len(frozen_rings) else 0
+        rollout_run.traced = "%d rings frozen, %d counting, %d armed; %d records written in all; the first frozen ring holds %d" % (
+            len(frozen_rings), int((info["state"] == 1).sum()), int((info["state"] == 0).sum()), int(info["n_written"].sum()), got)
     pl.close()
     return n * steps / dt, frozen
 
@@ -440,6 +459,20 @@ if os.environ.get("FOLLOW", "0") == "1":
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more following rollout alone
         follow_run(True)
+    sys.exit(0)
+if SCORE == "1" and TRACE > 0:
+    off, on = [], []
+    for r in range(runs):
+        a, _ = rollout_run(True)
+        b, _ = rollout_run(True, trace=TRACE)
+        off.append(a), on.append(b)
+        print("run %d  %d scenes, scorecard on  trace off %.3f M ticks/s   trace on (depth %d) %.3f M ticks/s (%s)" % (r, n, a / 1e6, TRACE, b / 1e6, rollout_run.traced), flush=True)
+    print("median  %d scenes, scorecard on  trace off %.3f M ticks/s (spread %.3f)   trace on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: both kernels in one trace
+        rollout_run(True)
+        rollout_run(True, trace=TRACE)
     sys.exit(0)
 if SCORE == "ab":
     off, on = [], []
