@@ -131,6 +131,10 @@ ScoreTraceModel = _dt([("depth", i4), ("post", i4), ("trigger", i4), ("flag_mask
 ScoreTick = _dt([("k", i4), ("flags", i4), ("tick", np.int64), ("x", f8), ("y", f8), ("v", f8), ("clearance", f8), ("obs", i4), ("ob_type", i4),
                  ("behavior", i4), ("marks", i4)])
 ScoreTraceInfo = _dt([("n_written", i4), ("state", i4), ("trigger_k", i4), ("trigger", i4), ("post_left", i4), ("n_trigger_ticks", i4), ("_pad", i4, (2,))])
+# scenario schedule: the start record of a restart drawn by weights from per-record outcome counts kept on the device
+EpisodeSchedule = _dt([("scope", i4), ("fail_mask", i4), ("pass_mask", i4), ("min_samples", i4), ("window", i4), ("floor_w", i4), ("gain", i4),
+                       ("target", i4), ("prior", i4), ("_pad", i4)])
+EpisodeScheduleRow = _dt([("n_end", i4, (EPISODE_MAX_STARTS,)), ("n_fail", i4, (EPISODE_MAX_STARTS,))])
 
 # one scene, one call (pp_tick_io): the pinned block that carries the inputs, the state and the outputs of the latency path
 PP_OK, PP_ERR_ARG, PP_ERR_HIP, PP_ERR_CAPACITY, PP_ERR_STATE = 0, -1, -2, -3, -4
@@ -185,6 +189,9 @@ _FEATURES = [
     ("pp_set_score_trace", {"pp_default_score_trace": ([_vp], None), "pp_set_score_trace": ([_vp, _vp], _ci),
                             "pp_get_score_trace_info": ([_vp, _vp, _ci], _ci), "pp_read_score_trace": ([_vp, _ci, _vp, _ci, _vp, _ci], _ci)},
      {35: ScoreTraceModel, 36: ScoreTick, 37: ScoreTraceInfo}),
+    ("pp_set_episode_schedule", {"pp_default_episode_schedule": ([_vp], None), "pp_set_episode_schedule": ([_vp, _vp], _ci),
+                                 "pp_get_episode_schedule": ([_vp, _vp, _ci], _ci), "pp_episode_schedule_weights": ([_vp, _vp, _ci, _vp], _ci)},
+     {38: EpisodeSchedule, 39: EpisodeScheduleRow}),
 ]
 
 _lib = None
@@ -336,6 +343,22 @@ def default_episode_spawn():
     """EpisodeSpawn record of the episode spawn model (pp_default_episode_spawn): seed 1, clearance 2 m, n_starts 1, order 0 (hashed),
     contact 1, check 3 (the obstacle slice and the egos of the world)."""
     return _default(EpisodeSpawn, "pp_default_episode_spawn")
+
+
+def default_episode_schedule():
+    """EpisodeSchedule record of the scenario schedule (pp_default_episode_schedule): scope 1 (pooled), fail_mask 207, pass_mask 16
+    (every cause but ROUTE_END fails), min_samples 4, window 256, floor_w 4096, gain 61440, target and prior 32768 (a 50 % failure rate)."""
+    return _default(EpisodeSchedule, "pp_default_episode_schedule")
+
+
+def episode_schedule_weights(model, row, n_starts):
+    """pp_episode_schedule_weights: the weights of start records 0 .. n_starts - 1 that the next draw would use for the
+    EpisodeScheduleRow `row` under `model` - pure host code from the function the kernel calls, no handle, no device."""
+    m = np.array(model, EpisodeSchedule).reshape(1).copy()
+    r = np.array(row, EpisodeScheduleRow).reshape(1).copy()
+    w = np.zeros(EPISODE_MAX_STARTS, np.int32)
+    _check(load_library().pp_episode_schedule_weights(_ptr(m), _ptr(r), int(n_starts), _ptr(w)))
+    return w[:int(n_starts)].copy()
 
 
 def default_score_trace():
@@ -696,6 +719,25 @@ class Planner:
         """pp_get_episode_spawn_stats: one EpisodeSpawnStats record per scene, a staged advance included (host wait)."""
         out = np.zeros(self.n, EpisodeSpawnStats)
         _check(self.lib.pp_get_episode_spawn_stats(self.h, _ptr(out), self.n))
+        return out
+
+    def set_episode_schedule(self, model=None, off=False):
+        """pp_set_episode_schedule, after set_episode_spawn with order 0: from the next advance on the first choice
+        of a restart is drawn by weights from the outcome counts per start record (model None: default_episode_schedule()).  The
+        schedule is part of the spawn model in force: set_episode_spawn and whatever retires the spawn model leave none.
+        off=True: the schedule off, the rows stay readable."""
+        if off:
+            _check(self.lib.pp_set_episode_schedule(self.h, None))
+            return
+        m = default_episode_schedule() if model is None else np.array(model, EpisodeSchedule).reshape(1).copy()
+        _check(self.lib.pp_set_episode_schedule(self.h, _ptr(m)))
+        self.episode_schedule_scope = int(m["scope"][0])
+
+    def episode_schedule(self):
+        """pp_get_episode_schedule: the EpisodeScheduleRow records - one in pooled scope, one per scene in per-scene scope -, a
+        staged advance included (host wait)."""
+        out = np.zeros(1 if getattr(self, "episode_schedule_scope", 1) == 1 else self.n, EpisodeScheduleRow)
+        _check(self.lib.pp_get_episode_schedule(self.h, _ptr(out), len(out)))
         return out
 
     def set_episode_traffic(self, n_sets, starts=None):

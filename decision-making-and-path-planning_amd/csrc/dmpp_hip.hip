@@ -25,6 +25,7 @@
 #include "kernels_rt.hpp"
 #include "kernels_ep.hpp"
 #include "kernels_es.hpp"
+#include "kernels_ev.hpp"
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
 #include "kernels_el.hpp"
@@ -217,6 +218,11 @@ struct EpisodeState {
 struct SpawnState {
     bool on = false, ever = false; EpisodeSpawn sp = {}; int stride = 0, cur = 0;      // ever: a set call succeeded on this handle (the stats are readable)
     DevBuf<SceneIn> d_in[2]; DevBuf<SceneState> d_state[2]; DevBuf<EpisodeSpawnStats> d_stats[2];
+    // scenario schedule (first pp_set_episode_schedule): part of the spawn model in force - on only while `on` is, gone
+    // with whatever switches `on` off or sets a new pool.  While on, pp_advance_async launches k_respawn_sched in the place of
+    // k_respawn_spawn and, in pooled scope, k_fold_schedule behind it.  The rows stay readable after it went off
+    bool sched_on = false, sched_ever = false; EpisodeSchedule sched = {};
+    DevBuf<EpisodeScheduleRow> d_rows; DevBuf<int32_t> d_fold_word;      // scope 0: a row per scene; scope 1: one row and a word per scene
 };
 struct FollowState {
     bool on = false; TrafficFollow tf = {};
@@ -612,7 +618,7 @@ void switch_features(pp_planner* h, unsigned m, bool on)
     if (m & (h->traffic.world ? kWorldTraffic : kTraffic)) h->traffic.on = on;
     if (m & kFollow) h->follow.on = on;
     if (m & kEpisodes) h->episode.on = on;
-    if (m & kSpawn) h->spawn.on = on;
+    if (m & kSpawn) { h->spawn.on = on; if (!on) h->spawn.sched_on = false; }      // (the schedule of §4p is part of the spawn model: it goes with it and does not come back)
     if (m & kTrafficReset) h->treset.on = on;
     if (m & kEpisodeLog) h->elog.on = on;
     static_assert(dmpp::kFeatureCount == 9, "a new feature bit needs its flag here and in feature_mask");
@@ -1593,7 +1599,16 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         else
             hipLaunchKernelGGL(dmpp::k_advance_egos, agrid, dim3(dmpp::kBlock), 0, su,
                                h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace);
-        if (h->episode.on && h->spawn.on)      // ... with the spawn model of §4l: contact ends an episode, the start record is drawn from a pool and checked for clearance
+        if (h->episode.on && h->spawn.on && h->spawn.sched_on) {      // ... with the spawn model and a schedule over its start records (§4p): the first choice is drawn by weights
+            EpisodeScheduleRow* rows = h->spawn.d_rows;
+            hipLaunchKernelGGL(dmpp::k_respawn_sched, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
+                               h->episode.em, h->spawn.sp, h->spawn.sched, 0.5 * h->cfg.Vehicle_Width, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state,
+                               h->spawn.d_in[h->spawn.cur], h->spawn.d_state[h->spawn.cur], h->fleet.on ? h->fleet.d_world_first.get() : nullptr,
+                               h->fleet.on ? h->fleet.d_world_of.get() : nullptr, h->rollout.d_flags, h->episode.d_stats, h->spawn.d_stats[h->spawn.cur],
+                               src.trace, h->score.on ? h->score.d_score.get() : nullptr, rows, h->spawn.d_fold_word);
+            if (h->spawn.sched.scope == 1)      // the endings of this advance into the handle's one row, behind every draw
+                hipLaunchKernelGGL(dmpp::k_fold_schedule, dim3(1), dim3(dmpp::kFoldBlock), 0, su, n, h->spawn.sched.window, h->episode.d_stats, h->spawn.d_fold_word, rows);
+        } else if (h->episode.on && h->spawn.on)      // ... with the spawn model of §4l: contact ends an episode, the start record is drawn from a pool and checked for clearance
             hipLaunchKernelGGL(dmpp::k_respawn_spawn, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
                                h->episode.em, h->spawn.sp, 0.5 * h->cfg.Vehicle_Width, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state,
                                h->spawn.d_in[h->spawn.cur], h->spawn.d_state[h->spawn.cur], h->fleet.on ? h->fleet.d_world_first.get() : nullptr,
@@ -2149,7 +2164,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     PP_TRY(refuse_if_staged(h, "pp_set_episode_spawn", "the spawn model"));
-    if (!sp) { h->spawn.on = false; retire(h, dmpp::kSetSpawn); return features_ok(h, "pp_set_episode_spawn"); }
+    if (!sp) { h->spawn.on = false; h->spawn.sched_on = false; retire(h, dmpp::kSetSpawn); return features_ok(h, "pp_set_episode_spawn"); }
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_spawn: episodes are off (pp_set_episodes comes first: its capture is start record 0)");
     const int n = h->n_scenes, M = sp->n_starts;
     if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts must be 1 .. DMPP_EPISODE_MAX_STARTS");
@@ -2196,6 +2211,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
         h->spawn.d_in[h->spawn.cur] = DevBuf<SceneIn>(); h->spawn.d_state[h->spawn.cur] = DevBuf<SceneState>();
     }
     h->spawn.sp = *sp; h->spawn.stride = stride; h->spawn.cur = o; h->spawn.on = true; h->spawn.ever = true;
+    h->spawn.sched_on = false;                            // (a new spawn model starts with no schedule: §4p)
     return features_ok(h, "pp_set_episode_spawn");
 }
 
@@ -2205,6 +2221,69 @@ int pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n)
     if (!h->spawn.ever) return fail(PP_ERR_STATE, "pp_get_episode_spawn_stats: pp_set_episode_spawn was never called on this handle");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
     return fetch_behind_advance(h, out, h->spawn.d_stats[h->spawn.cur], (size_t)n * sizeof(EpisodeSpawnStats), false);      // a staged advance included, as pp_get_episode_stats
+}
+
+// Scenario schedule.  Everything is checked on the host before anything changes.
+void pp_default_episode_schedule(EpisodeSchedule* m)
+{
+    if (!m) return;
+    *m = EpisodeSchedule{ 1, DMPP_EGO_PATH_END | DMPP_EGO_BAD_PATH | DMPP_EGO_LANE_END | DMPP_EGO_OFF_GRID | DMPP_EGO_TIMEOUT | DMPP_EGO_CONTACT, DMPP_EGO_ROUTE_END,
+                          4, 256, 4096, 61440, 32768, 32768, 0 };
+}
+
+static int check_episode_schedule(const EpisodeSchedule* m, const char* fn)
+{
+    const int causes = 31 | DMPP_EGO_TIMEOUT | DMPP_EGO_CONTACT;
+    const std::string f(fn);
+    if (m->scope != 0 && m->scope != 1) return fail(PP_ERR_ARG, f + ": scope must be 0 (a row per scene) or 1 (one pooled row)");
+    if ((m->fail_mask & ~causes) != 0 || (m->pass_mask & ~causes) != 0) return fail(PP_ERR_ARG, f + ": fail_mask / pass_mask hold bits outside 31 | 64 | 128");
+    if (m->min_samples < 1) return fail(PP_ERR_ARG, f + ": min_samples must be >= 1");
+    if (m->window != 0 && m->window < 2) return fail(PP_ERR_ARG, f + ": window must be 0 (no decay) or >= 2");
+    if (m->floor_w < 1 || m->floor_w > 65535) return fail(PP_ERR_ARG, f + ": floor_w must be 1 .. 65535");
+    if (m->gain < 0 || m->gain > 65535) return fail(PP_ERR_ARG, f + ": gain must be 0 .. 65535");
+    if (m->target < 0 || m->target > 65536 || m->prior < 0 || m->prior > 65536) return fail(PP_ERR_ARG, f + ": target and prior must be 0 .. 65536");
+    if (m->_pad != 0) return fail(PP_ERR_ARG, f + ": _pad must be 0");
+    return PP_OK;
+}
+
+int pp_set_episode_schedule(pp_handle h, const EpisodeSchedule* m)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    PP_TRY(refuse_if_staged(h, "pp_set_episode_schedule", "the schedule"));
+    if (!m) { h->spawn.sched_on = false; return features_ok(h, "pp_set_episode_schedule"); }
+    if (!h->episode.on || !h->spawn.on) return fail(PP_ERR_STATE, "pp_set_episode_schedule: the spawn model is off (pp_set_episode_spawn comes first: the schedule draws its start records)");
+    if (h->spawn.sp.order != 0) return fail(PP_ERR_STATE, "pp_set_episode_schedule: the spawn model in force is round robin (order 1): a schedule replaces the HASHED choice");
+    PP_TRY(check_episode_schedule(m, "pp_set_episode_schedule"));
+    PP_TRY(quiesce(h, false));                            // (the upload stream, which reads and folds the rows, is behind the last advance)
+    const size_t ns = (size_t)h->caps.max_scenes, n_rows = m->scope == 0 ? ns : 1;      // room first: a failed allocation changes nothing
+    if (m->scope == 1) PP_TRY(h->spawn.d_fold_word.reserve(ns));
+    PP_TRY(h->spawn.d_rows.reserve(n_rows));
+    HIP_TRY(hipMemsetAsync(h->spawn.d_rows, 0, n_rows * sizeof(EpisodeScheduleRow), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the upload stream reads the rows from its next launch on
+    h->spawn.sched = *m; h->spawn.sched_on = true; h->spawn.sched_ever = true;
+    return features_ok(h, "pp_set_episode_schedule");
+}
+
+int pp_get_episode_schedule(pp_handle h, EpisodeScheduleRow* rows, int n)
+{
+    if (!h || !rows) return fail(PP_ERR_ARG, "null argument");
+    if (!h->spawn.sched_ever) return fail(PP_ERR_STATE, "pp_get_episode_schedule: pp_set_episode_schedule was never called on this handle");
+    if (h->spawn.sched.scope == 1 ? n != 1 : (n < 0 || n > h->n_scenes || (size_t)n > h->spawn.d_rows.capacity()))
+        return fail(PP_ERR_ARG, "pp_get_episode_schedule: n must be 1 in pooled scope and at most the resident scenes in per-scene scope");
+    if (n == 0) return PP_OK;
+    return fetch_behind_advance(h, rows, h->spawn.d_rows, (size_t)n * sizeof(EpisodeScheduleRow), false);      // a staged advance included, as pp_get_episode_spawn_stats
+}
+
+// pure host code: the weights the next draw would use for a row (the function k_respawn_sched calls)
+int pp_episode_schedule_weights(const EpisodeSchedule* m, const EpisodeScheduleRow* row, int M, int32_t* w)
+{
+    if (!m || !row || !w) return fail(PP_ERR_ARG, "null argument");
+    if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_episode_schedule_weights: M must be 1 .. DMPP_EPISODE_MAX_STARTS");
+    PP_TRY(check_episode_schedule(m, "pp_episode_schedule_weights"));
+    for (int k = 0; k < M; k++)
+        if (row->n_fail[k] < 0 || row->n_fail[k] > row->n_end[k]) return fail(PP_ERR_ARG, "pp_episode_schedule_weights: a row has 0 <= n_fail <= n_end for every record");
+    for (int k = 0; k < DMPP_EPISODE_MAX_STARTS; k++) w[k] = k < M ? dmpp::schedule_weight(*m, row->n_end[k], row->n_fail[k]) : 0;
+    return PP_OK;
 }
 
 // Episode traffic reset.  Everything is checked on the host before anything changes; the new table and its counters
@@ -2710,6 +2789,7 @@ size_t pp_sizeof(int which)
     case 31: return sizeof(EpisodeSpawn); case 32: return sizeof(EpisodeSpawnStats); case 33: return sizeof(TrafficStart);
     case 34: return sizeof(EpisodeRecord);
     case 35: return sizeof(ScoreTraceModel); case 36: return sizeof(ScoreTick); case 37: return sizeof(ScoreTraceInfo);
+    case 38: return sizeof(EpisodeSchedule); case 39: return sizeof(EpisodeScheduleRow);
     default: return 0;
     }
 }

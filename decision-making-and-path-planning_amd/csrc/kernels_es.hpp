@@ -57,6 +57,97 @@ __device__ __forceinline__ bool wave_world_within(const SceneIn* __restrict__ pr
     return false;
 }
 
+// What steps 1 - 2 of §4l leave for the steps behind them: the flag word, the age and the metres of the ending episode, its cause word
+// and the scene's slice of the pool the advance read.
+struct SpawnEnd { int f, age, c, on; double dist; const ObPoint* slice; };
+
+// The steps of §4l as device functions: k_respawn_spawn and k_respawn_sched (kernels_ev.hpp, §4p) are made of the same ones, and differ
+// in how k0 is drawn.  (The pointers are the kernels' own __restrict__ arguments.  The test E.c == 0 and the early return stay in the
+// kernel: folded into a function that also stores, the compiler merges the uniform test with the lane test into one divergent branch.)
+// §4l 1., 1a., 2.: age and distance of the running episode, contact, cause word
+__device__ __forceinline__ void spawn_episode_end(const EpisodeModel& em, const EpisodeSpawn& sp, double hw, int s, int lane, const SceneIn* prev, const ObPoint* obs,
+                                                  int n_obs, const SceneIn* staged, const int32_t* flags, const EpisodeStats* stats, SpawnEnd& E)
+{
+    // 1. age and distance of the running episode
+    E.f = flags[s];
+    E.age = stats[s].age + 1;
+    const double px = prev[s].loc.globalpoint.x, py = prev[s].loc.globalpoint.y;
+    const double ex = staged[s].loc.globalpoint.x - px, ey = staged[s].loc.globalpoint.y - py;
+    E.dist = stats[s].dist + sqrt(ex * ex + ey * ey);
+    // the slice of the record the advance read (a sanitised record: inside the pool; anything else is taken as empty)
+    int off = prev[s].obs_off, on = prev[s].obs_n;
+    if (on <= 0 || off < 0 || (long long)off + on > (long long)n_obs) { off = 0; on = 0; }
+    E.slice = obs + off; E.on = on;
+    // 1a. contact
+    const bool touch = sp.contact != 0 && wave_slice_within(E.slice, on, px, py, hw, 0.0, lane);
+    // 2. cause word
+    E.c = (E.f & em.end_mask) | ((em.max_ticks > 0 && E.age >= em.max_ticks) ? DMPP_EGO_TIMEOUT : 0) | (touch ? DMPP_EGO_CONTACT : 0);
+}
+// §4l 2., cause word 0: a scene that goes on costs lane 0 two stores
+__device__ __forceinline__ void spawn_go_on(int s, int lane, const SpawnEnd& E, EpisodeStats* stats)
+{
+    if (lane == 0) { stats[s].age = E.age; stats[s].dist = E.dist; }
+}
+
+// §4l 3a.: the hash of scene s for its e-th ended episode
+__device__ __forceinline__ unsigned long long spawn_hash(const EpisodeSpawn& sp, int s, int e)
+{
+    return spawn_mix(spawn_mix(sp.seed + (unsigned long long)s) + (unsigned long long)e);
+}
+
+// §4l 3a. from k0 on, 3. - 6.: the clearance walk, the restart onto the record it took, stats, trace and scorecard words (lane 0)
+__device__ __forceinline__ void spawn_restart(const EpisodeSpawn& sp, double hw, int s, int lane, int stride, int k0, int e, const SpawnEnd& E,
+                                              const SceneIn* prev, SceneIn* staged, SceneState* state, const SceneIn* pool_in, const SceneState* pool_state,
+                                              const int32_t* world_first, const int32_t* world_of, int32_t* flags,
+                                              EpisodeStats* stats, EpisodeSpawnStats* sstats, EgoTrace* trace, RolloutScore* score)
+{
+    const int M = sp.n_starts, c = E.c, age = E.age;
+    const double dist = E.dist;
+    int p0 = 0, p1 = 0;
+    if ((sp.check & 2) && world_of) { const int w = world_of[s]; p0 = world_first[w]; p1 = world_first[w + 1]; }
+    int k = k0, rejected = M, blocked = 1;
+    for (int i = 0; i < M; i++) {
+        const int cand = (k0 + i) % M;
+        const GlobalPoint3D P = pool_in[(size_t)cand * stride + s].loc.globalpoint;
+        if ((sp.check & 1) && wave_slice_within(E.slice, E.on, P.x, P.y, hw, sp.clearance, lane)) continue;
+        if (wave_world_within(prev, p0, p1, s, P.x, P.y, hw, sp.clearance, lane)) continue;
+        k = cand; rejected = i; blocked = 0;
+        break;
+    }
+    // 4. restart: SceneIn and SceneState of the scene become start record k, every byte
+    const SceneIn* start_in = pool_in + (size_t)k * stride;
+    wave_copy_record(&staged[s], &start_in[s], lane);
+    wave_copy_record(&state[s], &pool_state[(size_t)k * stride + s], lane);
+    if (lane != 0) return;
+    // 3. stats
+    EpisodeStats S0 = stats[s];
+    S0.n_episodes = e;
+    for (int b = 0; b < 5; b++) if (c & (1 << b)) S0.n_end[b] = S0.n_end[b] + 1;
+    if (c & DMPP_EGO_TIMEOUT) S0.n_end[5] = S0.n_end[5] + 1;
+    S0.last_cause = c; S0.last_age = age;
+    if (S0.min_age < 0 || age < S0.min_age) S0.min_age = age;
+    if (S0.max_age < 0 || age > S0.max_age) S0.max_age = age;
+    S0.ticks_total = S0.ticks_total + (int64_t)age;
+    S0.last_dist = dist; S0.dist_total = S0.dist_total + dist;
+    S0.age = 0; S0.dist = 0;
+    stats[s] = S0;
+    flags[s] = 0;
+    EpisodeSpawnStats& S = sstats[s];
+    if (c & DMPP_EGO_CONTACT) S.n_contact = S.n_contact + 1;
+    S.n_blocked = S.n_blocked + blocked; S.n_rejected = S.n_rejected + rejected;
+    S.cur_start = k; S.n_used[k] = S.n_used[k] + 1;
+    // 5. trace of the start record   6. the scorecard's last ego is the one of the start record
+    const LocationOut& L = start_in[s].loc;
+    if (trace) {
+        EgoTrace t;
+        t.pose = L.globalpoint; t.velocity = L.velocity;
+        t.id_cur = L.id[clampi(L.lane_num - 1, 0, DMPP_LANESUM - 1)]; t.lane_num = L.lane_num;
+        t.flags = E.f | DMPP_EGO_RESPAWNED | (c & (DMPP_EGO_TIMEOUT | DMPP_EGO_CONTACT)); t._pad = 0;
+        trace[s] = t;
+    }
+    if (score) { score[s].last_pos.x = L.globalpoint.x; score[s].last_pos.y = L.globalpoint.y; score[s].last_speed = L.velocity; }
+}
+
 // prev / obs: the SceneIn records and the obstacle pool (n_obs entries) of the input set the advance read; staged, state, flags, stats,
 // trace, score: as k_respawn_egos.  pool_in / pool_state: the start records, record k of scene s at k * stride + s.  world_first /
 // world_of: the fleet's tables, or null without a fleet.  hw = 0.5 * Vehicle_Width (rounded once, on the host: exact).
@@ -69,75 +160,16 @@ k_respawn_spawn(EpisodeModel em, EpisodeSpawn sp, double hw, int n_scenes, int s
     const int lane = threadIdx.x & 63;
     const int s = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kEpScenes + (threadIdx.x >> 6)));
     if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
-    // 1. age and distance of the running episode
-    const int f = flags[s];
-    const int age = stats[s].age + 1;
-    const double px = prev[s].loc.globalpoint.x, py = prev[s].loc.globalpoint.y;
-    const double ex = staged[s].loc.globalpoint.x - px, ey = staged[s].loc.globalpoint.y - py;
-    const double dist = stats[s].dist + sqrt(ex * ex + ey * ey);
-    // the slice of the record the advance read (a sanitised record: inside the pool; anything else is taken as empty)
-    int off = prev[s].obs_off, on = prev[s].obs_n;
-    if (on <= 0 || off < 0 || (long long)off + on > (long long)n_obs) { off = 0; on = 0; }
-    const ObPoint* slice = obs + off;
-    // 1a. contact
-    const bool touch = sp.contact != 0 && wave_slice_within(slice, on, px, py, hw, 0.0, lane);
-    // 2. cause word
-    const int c = (f & em.end_mask) | ((em.max_ticks > 0 && age >= em.max_ticks) ? DMPP_EGO_TIMEOUT : 0) | (touch ? DMPP_EGO_CONTACT : 0);
-    if (c == 0) {
-        if (lane == 0) { stats[s].age = age; stats[s].dist = dist; }
-        return;
-    }
+    SpawnEnd E;
+    spawn_episode_end(em, sp, hw, s, lane, prev, obs, n_obs, staged, flags, stats, E);
+    if (E.c == 0) { spawn_go_on(s, lane, E, stats); return; }
     // 3a. start record
     const int M = sp.n_starts;
     const int e = stats[s].n_episodes + 1;
     int k0;
-    if (sp.order == 0) {
-        const unsigned long long u = spawn_mix(spawn_mix(sp.seed + (unsigned long long)s) + (unsigned long long)e);
-        k0 = (int)(((u >> 32) * (unsigned long long)M) >> 32);
-    } else k0 = e % M;
-    int p0 = 0, p1 = 0;
-    if ((sp.check & 2) && world_of) { const int w = world_of[s]; p0 = world_first[w]; p1 = world_first[w + 1]; }
-    int k = k0, rejected = M, blocked = 1;
-    for (int i = 0; i < M; i++) {
-        const int cand = (k0 + i) % M;
-        const GlobalPoint3D P = pool_in[(size_t)cand * stride + s].loc.globalpoint;
-        if ((sp.check & 1) && wave_slice_within(slice, on, P.x, P.y, hw, sp.clearance, lane)) continue;
-        if (wave_world_within(prev, p0, p1, s, P.x, P.y, hw, sp.clearance, lane)) continue;
-        k = cand; rejected = i; blocked = 0;
-        break;
-    }
-    // 4. restart: SceneIn and SceneState of the scene become start record k, every byte
-    const SceneIn* start_in = pool_in + (size_t)k * stride;
-    wave_copy_record(&staged[s], &start_in[s], lane);
-    wave_copy_record(&state[s], &pool_state[(size_t)k * stride + s], lane);
-    if (lane != 0) return;
-    // 3. stats
-    EpisodeStats E = stats[s];
-    E.n_episodes = e;
-    for (int b = 0; b < 5; b++) if (c & (1 << b)) E.n_end[b] = E.n_end[b] + 1;
-    if (c & DMPP_EGO_TIMEOUT) E.n_end[5] = E.n_end[5] + 1;
-    E.last_cause = c; E.last_age = age;
-    if (E.min_age < 0 || age < E.min_age) E.min_age = age;
-    if (E.max_age < 0 || age > E.max_age) E.max_age = age;
-    E.ticks_total = E.ticks_total + (int64_t)age;
-    E.last_dist = dist; E.dist_total = E.dist_total + dist;
-    E.age = 0; E.dist = 0;
-    stats[s] = E;
-    flags[s] = 0;
-    EpisodeSpawnStats& S = sstats[s];
-    if (c & DMPP_EGO_CONTACT) S.n_contact = S.n_contact + 1;
-    S.n_blocked = S.n_blocked + blocked; S.n_rejected = S.n_rejected + rejected;
-    S.cur_start = k; S.n_used[k] = S.n_used[k] + 1;
-    // 5. trace of the start record   6. the scorecard's last ego is the one of the start record
-    const LocationOut& L = start_in[s].loc;
-    if (trace) {
-        EgoTrace t;
-        t.pose = L.globalpoint; t.velocity = L.velocity;
-        t.id_cur = L.id[clampi(L.lane_num - 1, 0, DMPP_LANESUM - 1)]; t.lane_num = L.lane_num;
-        t.flags = f | DMPP_EGO_RESPAWNED | (c & (DMPP_EGO_TIMEOUT | DMPP_EGO_CONTACT)); t._pad = 0;
-        trace[s] = t;
-    }
-    if (score) { score[s].last_pos.x = L.globalpoint.x; score[s].last_pos.y = L.globalpoint.y; score[s].last_speed = L.velocity; }
+    if (sp.order == 0) k0 = (int)(((spawn_hash(sp, s, e) >> 32) * (unsigned long long)M) >> 32);
+    else k0 = e % M;
+    spawn_restart(sp, hw, s, lane, stride, k0, e, E, prev, staged, state, pool_in, pool_state, world_first, world_of, flags, stats, sstats, trace, score);
 }
 
 // obs_off / obs_n of start records 1 .. M - 1 become those of the scene's record 0 (one thread per record)

@@ -31,6 +31,10 @@
 // With --route --episodes --log N the episode log is on (pp_set_episode_log): a ring of N records on the device, one
 // record appended per ended episode, drained once behind the run; the scorecard is on, so every record carries its episode's own.
 // The host prints an outcome table per start record: episodes, causes, mean age and metres, worst clearance, episodes with a collision.
+// With --route --episodes --starts M --schedule [pooled|scene] a scenario schedule is on (pp_set_episode_schedule with the default model in
+// that scope): the start record of a restart is drawn by weights from the outcome counts per record that the device keeps -
+// with --contact the records whose episodes meet the vehicle about half the time get the most restarts.  The host prints the rows - counted
+// episodes, failures and the weight of the next draw per record - beside the restarts per record of the spawn statistics.
 // With --score-trace DEPTH[,POST] the score trace is on (pp_set_score_trace with the default model): every scene keeps its
 // last DEPTH scored ticks in a ring on the device, which freezes POST ticks behind the scene's first contact; behind the run the host
 // prints every frozen scene's triggering tick and, for the first three, the records before it.  Any mode; a routed run gets the scorecard.
@@ -85,7 +89,7 @@ static int print_score_trace(pp_handle h, int n, int depth)
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post, int sched)
 {
     const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
     if (contact) traffic = true;                      // (the vehicle to touch)
@@ -222,6 +226,8 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         CHECK(pp_set_episode_traffic(h, M, M > 1 ? sets.data() : nullptr));
     }
     if (log_cap) CHECK(pp_set_episode_log(h, log_cap));      // last of all
+    EpisodeSchedule sm; pp_default_episode_schedule(&sm); sm.scope = sched == 2 ? 0 : 1;
+    if (sched) CHECK(pp_set_episode_schedule(h, &sm));       // (part of the spawn model in force: it retires nothing, anywhere behind pp_set_episode_spawn)
     if (trace_depth && set_score_trace(h, trace_depth, trace_post)) return 2;      // (no feature: anywhere)
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
@@ -281,6 +287,19 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         for (int k = 0; k < M; k++) std::printf(" %lld", used[k]);
         std::printf("\n");
     }
+    if (sched) {                                      // the rows (per-scene scope: summed over the scenes for the print) and the weights of the next draw
+        std::vector<EpisodeScheduleRow> rows(sm.scope == 1 ? 1 : (size_t)n);
+        CHECK(pp_get_episode_schedule(h, rows.data(), (int)rows.size()));
+        EpisodeScheduleRow sum = {};
+        for (const EpisodeScheduleRow& r : rows) for (int k = 0; k < M; k++) { sum.n_end[k] += r.n_end[k]; sum.n_fail[k] += r.n_fail[k]; }
+        int32_t wt[DMPP_EPISODE_MAX_STARTS];
+        CHECK(pp_episode_schedule_weights(&sm, &rows[0], M, wt));
+        std::printf("schedule (%s): counted episodes / failures per record%s:", sm.scope == 1 ? "pooled" : "per scene", sm.scope == 1 ? "" : ", all scenes");
+        for (int k = 0; k < M; k++) std::printf(" %d/%d", sum.n_end[k], sum.n_fail[k]);
+        std::printf("; weights of the next draw%s:", sm.scope == 1 ? "" : " of scene 0");
+        for (int k = 0; k < M; k++) std::printf(" %d", wt[k]);
+        std::printf("\n");
+    }
     if (reset) {
         std::vector<int32_t> nr(n); std::vector<EpisodeStats> es(n);
         CHECK(pp_get_episode_traffic_resets(h, nr.data(), n));
@@ -336,7 +355,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0, log_cap = 0, trace_depth = 0, trace_post = -1;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0, log_cap = 0, trace_depth = 0, trace_post = -1, sched = 0;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -348,9 +367,14 @@ int main(int argc, char** argv)
         else if (std::strcmp(argv[a], "--contact") == 0) contact = true;
         else if (std::strcmp(argv[a], "--reset-traffic") == 0) reset = true;
         else if (std::strcmp(argv[a], "--starts") == 0 && a + 1 < argc) starts = std::atoi(argv[++a]);
+        else if (std::strcmp(argv[a], "--schedule") == 0) {
+            sched = 1;                                    // pooled unless the next word says otherwise
+            if (a + 1 < argc && std::strcmp(argv[a + 1], "scene") == 0) { sched = 2; a++; }
+            else if (a + 1 < argc && std::strcmp(argv[a + 1], "pooled") == 0) a++;
+        }
         else if (std::strcmp(argv[a], "--log") == 0 && a + 1 < argc) log_cap = std::atoi(argv[++a]);
         else if (std::strcmp(argv[a], "--score-trace") == 0 && a + 1 < argc) { if (std::sscanf(argv[++a], "%d,%d", &trace_depth, &trace_post) < 1) trace_depth = -1; }
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow] [--score-trace DEPTH[,POST]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow] [--score-trace DEPTH[,POST]]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
@@ -360,12 +384,13 @@ int main(int argc, char** argv)
     if (starts < 0 || starts > DMPP_EPISODE_MAX_STARTS) { std::fprintf(stderr, "--starts takes 1 .. %d\n", DMPP_EPISODE_MAX_STARTS); return 2; }
     if (contact && (react || shared)) { std::fprintf(stderr, "--contact brings its own oncoming vehicle: not with --react / --shared\n"); return 2; }
     if (starts && shared) { std::fprintf(stderr, "--starts places its records behind each ego on its lane: not with the platoons of --shared\n"); return 2; }
+    if (sched && !(route && episodes && starts > 0)) { std::fprintf(stderr, "--schedule draws among start records: use it with --route --episodes --starts M\n"); return 2; }
     if (reset && !(route && episodes && (traffic || contact))) { std::fprintf(stderr, "--reset-traffic puts a restarted ego's vehicle back: use it with --route --episodes --traffic (or --contact)\n"); return 2; }
     if (reset && shared) { std::fprintf(stderr, "--reset-traffic resets per-scene traffic: a vehicle of --shared belongs to a whole world\n"); return 2; }
     if (log_cap && !(route && episodes)) { std::fprintf(stderr, "--log records how episodes ended: use it with --route --episodes\n"); return 2; }
     if (log_cap < 0 || log_cap > DMPP_EPISODE_LOG_MAX) { std::fprintf(stderr, "--log takes 1 .. %d records\n", DMPP_EPISODE_LOG_MAX); return 2; }
     if (trace_depth < 0 || trace_depth > DMPP_SCORE_TRACE_MAX || (trace_depth && trace_post >= trace_depth)) { std::fprintf(stderr, "--score-trace takes DEPTH 1 .. %d and POST 0 .. DEPTH - 1\n", DMPP_SCORE_TRACE_MAX); return 2; }
-    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post);
+    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post, sched);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

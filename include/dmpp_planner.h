@@ -431,6 +431,33 @@ void pp_default_episode_spawn(EpisodeSpawn* sp);     /* seed 1, clearance 2 m, n
 int  pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* starts_in, const SceneState* starts_state);
 int  pp_get_episode_spawn_stats(pp_handle h, EpisodeSpawnStats* out, int n_scenes);
 
+/* ---- scenario schedule: start records drawn by their outcomes, on the device --------------------------------------
+ * Start record k plus traffic set k is scenario k; the hashed choice of §4l plays them uniformly, however the episodes on each went.
+ * While a schedule is in force, k_respawn_sched runs in the place of k_respawn_spawn and draws the FIRST CHOICE k0 of a restart by
+ * weights: the device keeps, per start record, how many counted episodes ran on it (n_end) and how many of them failed (n_fail: the
+ * cause word meets fail_mask and not pass_mask), a record's failure rate r = n_fail * 65536 / n_end (prior below min_samples), and
+ *     w_k = floor_w + ((gain * (65536 - |r - target|)) >> 16),
+ * k0 = the lowest k whose running sum of weights exceeds ((u >> 32) * sum) >> 32, u the hash of §4l.  Integers only; every draw of
+ * an advance reads the counts as they stood before that advance's endings are folded in; window >= 2 halves a record's two counts
+ * whenever n_end reaches it.  Everything else - contact, the clearance walk from k0, the restart, stats, trace - is §4l unchanged,
+ * and gain == 0 gives the bytes of §4l with order 0.  scope 0: one row per scene, folded by the scene itself; scope 1: one row for the
+ * handle, folded by one more kernel (k_fold_schedule, one workgroup) behind k_respawn_sched and in front of k_log_episodes.
+ * The schedule is PART OF THE SPAWN MODEL IN FORCE: it needs one with order 0 (PP_ERR_STATE otherwise), and every successful
+ * pp_set_episode_spawn - NULL included - and whatever retires the spawn model (§7, "Feature life cycle") leaves no schedule; it
+ * retires nothing itself.  m NULL: the schedule off, k_respawn_spawn runs again.  A staged update: PP_ERR_STATE.  PP_ERR_ARG: a field
+ * outside its range (dmpp_types.h), mask bits outside 31 | 64 | 128.  Nothing changes on a refusal.  A successful call zeroes the
+ * rows; one host wait, behind every tick and advance enqueued so far.  A handle that never makes the call allocates and launches none of this.
+ * pp_get_episode_schedule: the rows - n == 1 in pooled scope, n <= the resident scenes in per-scene scope -, a staged advance
+ * included (host wait, as pp_get_episode_spawn_stats); readable after the schedule went off.  PP_ERR_STATE on a handle that never
+ * made the set call.
+ * pp_episode_schedule_weights: pure host code, no handle, no device - the weights w[0 .. M) the next draw would use for `row`, from
+ * the function the kernel calls (w[M .. 16) = 0).  PP_ERR_ARG: M outside 1 .. 16, a model out of range, a row with n_fail outside
+ * 0 .. n_end. */
+void pp_default_episode_schedule(EpisodeSchedule* m);     /* scope 1, fail_mask 207, pass_mask 16, min_samples 4, window 256, floor_w 4096, gain 61440, target 32768, prior 32768 */
+int  pp_set_episode_schedule(pp_handle h, const EpisodeSchedule* m);
+int  pp_get_episode_schedule(pp_handle h, EpisodeScheduleRow* rows, int n);
+int  pp_episode_schedule_weights(const EpisodeSchedule* m, const EpisodeScheduleRow* row, int M, int32_t w[16]);
+
 /* ---- episode traffic reset: a restarted scene puts its traffic back on a start state ------------------------------
  * Without it a restart restores SceneIn and SceneState and leaves the scene's actors (pp_set_traffic) wherever the last episode
  * drove them: later episodes do not repeat the first.  pp_set_episode_traffic gives every actor n_sets START STATES and switches the
@@ -569,7 +596,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
  * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
  * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord, 35 ScoreTraceModel, 36 ScoreTick,
- * 37 ScoreTraceInfo */
+ * 37 ScoreTraceInfo, 38 EpisodeSchedule, 39 EpisodeScheduleRow */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

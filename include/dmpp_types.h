@@ -455,6 +455,27 @@ typedef struct ScoreTraceInfo {
     int32_t _pad[2];
 } ScoreTraceInfo;                                                           /* 32 B */
 
+/* ---- scenario schedule (build-defined), part of the spawn model in force --------------------------------
+ * pp_set_episode_schedule makes the hashed start choice of §4l a WEIGHTED one: the device keeps, per start record, how many
+ * episodes ended on it and how many of those failed, and a record's weight peaks where its failure rate meets `target`.
+ * Integers only: rates and weights are 16.16 fixed point. */
+typedef struct EpisodeSchedule {
+    int32_t scope;        /* 0: one row per scene; 1: one row for the handle, pooled over all scenes */
+    int32_t fail_mask;    /* cause bits that make an ended episode a FAILURE (bits of 31 | 64 | 128) */
+    int32_t pass_mask;    /* ... unless the cause also has one of these (same bit range) */
+    int32_t min_samples;  /* >= 1: below this many counted episodes a record's rate is `prior` */
+    int32_t window;       /* 0: counts never decay; >= 2: halve a record's two counts whenever n_end >= window */
+    int32_t floor_w;      /* 1 .. 65535: every record keeps this weight */
+    int32_t gain;         /* 0 .. 65535 */
+    int32_t target;       /* 0 .. 65536: the failure rate (x 65536) that gets the largest weight */
+    int32_t prior;        /* 0 .. 65536 */
+    int32_t _pad;         /* 0 */
+} EpisodeSchedule;                                                          /* 40 B */
+typedef struct EpisodeScheduleRow {
+    int32_t n_end[DMPP_EPISODE_MAX_STARTS];    /* counted episodes that ran on record k  */
+    int32_t n_fail[DMPP_EPISODE_MAX_STARTS];   /* ... of which failures                  */
+} EpisodeScheduleRow;                                                       /* 128 B */
+
 /* ---- every macro the reference uses but never defines ------------------ */
 typedef struct PlannerConfig {
     double ROAD_FARAIM_MAX, ROAD_FARAIM_MIN;      /* Planning.cpp:260,264 */

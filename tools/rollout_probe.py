@@ -33,6 +33,10 @@ what a kernel trace of the ONE_ROLLOUT leg gives.
 EPISODES=1 LOG=cap: both legs are the ring rollout with episodes on, and the second leg has the episode log on as well
 (pp_set_episode_log(cap), DESIGN.md §4n: k_log_episodes behind k_respawn_egos); it is drained once behind the timed rollout, outside the
 timing.  SCORE=1 puts the scorecard on in both legs (k_score_ego<true> in the second).  With ONE_ROLLOUT one more leg with the log on alone.
+EPISODES=1 SPAWN=M SCHEDULE=pooled|scene (with CONTACT=1 / RESET=1 as above): both legs have that spawn model on (and the reset, if asked
+for), and the second leg the scenario schedule as well (pp_set_episode_schedule, DESIGN.md §4p: k_respawn_sched in the place of
+k_respawn_spawn, in pooled scope k_fold_schedule behind it) - the default model in that scope, contact the failure.  The rows are read
+behind the timed rollout, outside the timing.  With ONE_ROLLOUT one more leg with the schedule on alone.
 SCORE=1 TRACE=depth: every run has a scored rollout leg without and one with the score trace (pp_set_score_trace: the default model with
 `depth` records per scene, DESIGN.md §4o: k_score_ego<false, true> in the place of <false, false>), alternating; headers and one ring are
 read behind the timed rollout, outside the timing.  TRACE_TRIGGER=mask replaces the model's trigger (0: rings that never freeze, so every
@@ -195,9 +199,10 @@ def episodes_run(on, log=0):
 SPAWN = int(os.environ.get("SPAWN", "0"))
 CONTACT = os.environ.get("CONTACT", "0") == "1"
 RESET = os.environ.get("RESET", "0") == "1"
+SCHEDULE = os.environ.get("SCHEDULE", "")
 
 
-def spawn_run(on, reset=False):
+def spawn_run(on, reset=False, sched=""):
     import route_scenes as rs
     import traffic_model as tm
     import traffic_scenes as ts
@@ -239,6 +244,10 @@ def spawn_run(on, reset=False):
                     loc = sc["scene_in"]["loc"][(s + k) % n]
                     sets["s"][k - 1, s] = cums[rows[s][4]][ts.SEG * (int(loc["road_num"]) - 1) + int(loc["id"][int(loc["lane_num"]) - 1])] + 20.0
         pl.set_episode_traffic(M if on else 1, sets)
+    if sched:
+        sm = dm.default_episode_schedule()
+        sm["scope"] = 1 if sched == "pooled" else 0
+        pl.set_episode_schedule(sm)
     pl.rollout(warm, model)
     pl.sync()
     t0 = time.perf_counter()
@@ -249,6 +258,9 @@ def spawn_run(on, reset=False):
     ss = pl.episode_spawn_stats() if on else None
     spawn_run.resets = int(pl.episode_traffic_resets().sum()) if reset else 0
     spawn_run.age1 = int((pl.episode_stats()["min_age"] == 1).sum())
+    if sched:
+        rows = pl.episode_schedule()
+        spawn_run.rows = (int(rows["n_end"].sum()), int(rows["n_fail"].sum()))
     pl.close()
     return n * steps / dt, ended, (0, 0, 0) if ss is None else (int(ss["n_contact"].sum()), int(ss["n_blocked"].sum()), int(ss["n_rejected"].sum()))
 
@@ -368,6 +380,22 @@ if TRAFFIC > 0:
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with traffic alone
         traffic_run(True)
+    sys.exit(0)
+if os.environ.get("EPISODES", "0") == "1" and SCHEDULE:
+    assert SCHEDULE in ("pooled", "scene") and SPAWN > 0
+    off, on = [], []
+    for r in range(runs):
+        a, ea, _ = spawn_run(True, reset=RESET)
+        b, eb, (nc, _, _) = spawn_run(True, reset=RESET, sched=SCHEDULE)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos with traffic, spawn model on (M %d, contact %d, reset %d)  schedule off %.3f M ticks/s (%d episodes ended)   "
+              "schedule on (%s) %.3f M ticks/s (%d episodes ended, %d on contact; rows: %d counted, %d failures)" %
+              ((r, n, SPAWN, int(CONTACT), int(RESET), a / 1e6, ea, SCHEDULE, b / 1e6, eb, nc) + spawn_run.rows), flush=True)
+    print("median  %d ring egos  schedule off %.3f M ticks/s (spread %.3f)   schedule on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with the schedule alone
+        spawn_run(True, reset=RESET, sched=SCHEDULE)
     sys.exit(0)
 if os.environ.get("EPISODES", "0") == "1" and RESET:
     off, on = [], []
