@@ -101,6 +101,10 @@ RouteModel = _dt([("pre_points", i4), ("_pad", i4)])
 EGO_ROUTE_END = 16            # the ego came to the end of the last leg of its route (DMPP_EGO_ROUTE_END)
 # a grid that follows the ego: the advance step re-centres grid_origin and goal
 GridFollow = _dt([("goal_point", i4), ("margin_cells", i4)])
+# ego tracking model: rollout egos keep a pose of their own and steer a bicycle model along the plan
+EgoTracker = _dt([("look_min", f8), ("look_gain", f8), ("max_curv", f8), ("curv_rate", f8), ("curv_bias", f8), ("n_sub", i4), ("_pad", i4)])
+EgoTrackState = _dt([("hx", f8), ("hy", f8), ("kappa", f8), ("key_x", u8), ("key_y", u8), ("key_dir", u8), ("max_kappa", f8),
+                     ("valid", i4), ("n_init", i4), ("n_sat", i4), ("_pad", i4)])
 # lane traffic: scripted vehicles that drive a polyline and sit in their scene's own obstacle entries
 TrafficTrack = _dt([("point_off", i4), ("n_points", i4), ("closed", i4), ("_pad", i4)])
 TrafficActor = _dt([("s0", f8), ("speed", f8), ("scene", i4), ("slot", i4), ("track", i4), ("type", i4), ("radius", f4), ("_pad", i4)])
@@ -192,6 +196,8 @@ _FEATURES = [
     ("pp_set_episode_schedule", {"pp_default_episode_schedule": ([_vp], None), "pp_set_episode_schedule": ([_vp, _vp], _ci),
                                  "pp_get_episode_schedule": ([_vp, _vp, _ci], _ci), "pp_episode_schedule_weights": ([_vp, _vp, _ci, _vp], _ci)},
      {38: EpisodeSchedule, 39: EpisodeScheduleRow}),
+    ("pp_set_ego_tracker", {"pp_default_ego_tracker": ([_vp], None), "pp_set_ego_tracker": ([_vp, _vp], _ci),
+                            "pp_get_ego_track_state": ([_vp, _vp, _ci], _ci)}, {40: EgoTracker, 41: EgoTrackState}),
 ]
 
 _lib = None
@@ -332,6 +338,12 @@ def default_route_model():
 def default_grid_follow():
     """GridFollow record of the grid that follows the ego (pp_default_grid_follow): the path point the goal is taken from, the margin in cells."""
     return _default(GridFollow, "pp_default_grid_follow")
+
+
+def default_ego_tracker():
+    """EgoTracker record of the ego tracking model (pp_default_ego_tracker): look-ahead 3 m + 0.5 s, |curvature| <= 0.2 1/m,
+    0.3 1/(m s) curvature rate, no bias, 2 substeps."""
+    return _default(EgoTracker, "pp_default_ego_tracker")
 
 
 def default_episode_model():
@@ -639,6 +651,23 @@ class Planner:
             return
         m = np.array(gf, GridFollow).reshape(1).copy()
         _check(self.lib.pp_set_grid_follow(self.h, _ptr(m)))
+
+    # ---- ego tracking model: the egos steer a bicycle model along the plan ---------------------
+    def set_ego_tracker(self, tk=None):
+        """pp_set_ego_tracker: from the next advance on every ego keeps a pose of its own - position, unit heading, curvature - and
+        chases its planned path by pure pursuit instead of being put on it.  The model belongs to the handle: it
+        survives set_scenes / set_egos / set_map (the per-scene states are re-derived).  tk None: tracking off."""
+        if tk is None:
+            _check(self.lib.pp_set_ego_tracker(self.h, None))
+            return
+        m = np.array(tk, EgoTracker).reshape(1).copy()
+        _check(self.lib.pp_set_ego_tracker(self.h, _ptr(m)))
+
+    def ego_track_state(self):
+        """pp_get_ego_track_state: one EgoTrackState record per scene, a staged advance included (host wait)."""
+        out = np.zeros(self.n, EgoTrackState)
+        _check(self.lib.pp_get_ego_track_state(self.h, _ptr(out), self.n))
+        return out
 
     # ---- lane traffic: scripted vehicles in the scenes' own obstacle entries -----------------
     def set_traffic(self, tracks=None, points=None, actors=None):

@@ -351,6 +351,10 @@ struct pp_planner {
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
+    // ego tracking model (first pp_set_ego_tracker): the model and one EgoTrackState per scene.  Like the grid follow it
+    // belongs to the handle - no rollout feature, no set call retires it; while on, pp_advance_async launches k_advance_*<true>.
+    // A call that replaces the resident scenes zeroes the states (resident_replaced); they stay readable after it went off
+    struct TrackerState { bool on = false; EgoTracker tk = {}; DevBuf<EgoTrackState> d_state; } tracker;
     // profiling
     int profile = 0;             // 0 off, 1 every kernel of a tick between HIP events, 2 only the search kernel
     std::vector<EvPair> pending; std::vector<hipEvent_t> free_events;
@@ -959,6 +963,8 @@ static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad
 {
     h->resident_mode = mode; retire(h, dmpp::kResidentReplaced); note_current_set(h);
     PP_TRY(reset_ego_flags(h));
+    if (h->tracker.d_state)                              // every tracked pose is re-derived from the new records (§4q 1.)
+        HIP_TRY(hipMemsetAsync(h->tracker.d_state, 0, (size_t)h->caps.max_scenes * sizeof(EgoTrackState), h->stream));
     if (h->score.on) PP_TRY(reset_scores(h));
     if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
     PP_TRY(validate_resident(h, h->n_scenes, who));
@@ -1592,13 +1598,23 @@ static int stage_inputs(pp_handle h, const StageSource& src)
     SceneIn* d_in = I.d_in; ObPoint* d_obs = I.d_obs; ObMotion* d_mot = have_motion ? I.d_mot.get() : nullptr;
     if (advance) {
         const dim3 agrid((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes));
-        if (h->route.on)                  // routed egos cross junctions; the scenes without a route advance as below
-            hipLaunchKernelGGL(dmpp::k_advance_route, agrid, dim3(dmpp::kBlock), 0, su,
+        // with an ego tracker the pose step is the bicycle model of DESIGN.md §4q: the <true> form of the same kernel; the episode stats
+        // it reads are those the respawn kernel of the advance BEFORE left (same stream)
+        const dmpp::AdvTrack trk = { h->tracker.tk, h->tracker.d_state, h->episode.on ? h->episode.d_stats.get() : nullptr };
+        if (h->route.on && h->tracker.on)
+            hipLaunchKernelGGL(dmpp::k_advance_route<true>, agrid, dim3(dmpp::kBlock), 0, su,
                                h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
-                               h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace);
+                               h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace, trk);
+        else if (h->route.on)             // routed egos cross junctions; the scenes without a route advance as below
+            hipLaunchKernelGGL(dmpp::k_advance_route<false>, agrid, dim3(dmpp::kBlock), 0, su,
+                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
+                               h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace, 0);
+        else if (h->tracker.on)
+            hipLaunchKernelGGL(dmpp::k_advance_egos<true>, agrid, dim3(dmpp::kBlock), 0, su,
+                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace, trk);
         else
-            hipLaunchKernelGGL(dmpp::k_advance_egos, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace);
+            hipLaunchKernelGGL(dmpp::k_advance_egos<false>, agrid, dim3(dmpp::kBlock), 0, su,
+                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace, 0);
         if (h->episode.on && h->spawn.on && h->spawn.sched_on) {      // ... with the spawn model and a schedule over its start records (§4p): the first choice is drawn by weights
             EpisodeScheduleRow* rows = h->spawn.d_rows;
             hipLaunchKernelGGL(dmpp::k_respawn_sched, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
@@ -2413,6 +2429,41 @@ int pp_set_grid_follow(pp_handle h, const GridFollow* gf)
     return features_ok(h, "pp_set_grid_follow");
 }
 
+// Ego tracking model: host checks; the model is a kernel argument of the next advance, the per-scene states are
+// allocated and zeroed by the first call that brings a model.
+void pp_default_ego_tracker(EgoTracker* tk)
+{
+    if (!tk) return;
+    tk->look_min = 3.0; tk->look_gain = 0.5; tk->max_curv = 0.2; tk->curv_rate = 0.3; tk->curv_bias = 0.0; tk->n_sub = 2; tk->_pad = 0;
+}
+
+int pp_set_ego_tracker(pp_handle h, const EgoTracker* tk)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!tk) { h->tracker.on = false; return PP_OK; }
+    if (!std::isfinite(tk->look_min) || !std::isfinite(tk->look_gain) || !std::isfinite(tk->max_curv) || !std::isfinite(tk->curv_rate) || !std::isfinite(tk->curv_bias))
+        return fail(PP_ERR_ARG, "pp_set_ego_tracker: every field must be finite");
+    if (!(tk->look_min > 0) || !(tk->look_gain >= 0) || !(tk->max_curv > 0) || !(tk->curv_rate > 0))
+        return fail(PP_ERR_ARG, "pp_set_ego_tracker: look_min, max_curv and curv_rate must be > 0, look_gain >= 0");
+    if (tk->n_sub < 1 || tk->n_sub > 8) return fail(PP_ERR_ARG, "pp_set_ego_tracker: n_sub must be 1 .. 8");
+    if (!h->tracker.d_state) {
+        HIP_TRY(hipSetDevice(h->device));
+        PP_TRY(h->tracker.d_state.reserve((size_t)h->caps.max_scenes));
+        HIP_TRY(hipMemsetAsync(h->tracker.d_state, 0, (size_t)h->caps.max_scenes * sizeof(EgoTrackState), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));       // (the first advance runs on the upload stream)
+    }
+    h->tracker.tk = *tk; h->tracker.tk._pad = 0; h->tracker.on = true;
+    return PP_OK;
+}
+
+int pp_get_ego_track_state(pp_handle h, EgoTrackState* out, int n)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->tracker.d_state) return fail(PP_ERR_STATE, "pp_get_ego_track_state: pp_set_ego_tracker was never called on this handle");
+    if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
+    return fetch_behind_advance(h, out, h->tracker.d_state, (size_t)n * sizeof(EgoTrackState), false);      // a staged advance included, as pp_get_ego_flags
+}
+
 int pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap)
 {
     if (!h || (!out && cap > 0)) return fail(PP_ERR_ARG, "null argument");
@@ -2790,6 +2841,7 @@ size_t pp_sizeof(int which)
     case 34: return sizeof(EpisodeRecord);
     case 35: return sizeof(ScoreTraceModel); case 36: return sizeof(ScoreTick); case 37: return sizeof(ScoreTraceInfo);
     case 38: return sizeof(EpisodeSchedule); case 39: return sizeof(EpisodeScheduleRow);
+    case 40: return sizeof(EgoTracker); case 41: return sizeof(EgoTrackState);
     default: return 0;
     }
 }

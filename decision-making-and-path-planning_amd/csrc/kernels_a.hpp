@@ -8,6 +8,9 @@
 // handful of segments at 0.5 m spacing).  The three id searches are (value, index) wave minima that keep the first minimum
 // (wave_first_min, the reduction of GetVhclLocalState in k_planning).  The steps are device functions: the routed form of the kernel
 // (k_advance_route, kernels_rt.hpp) shares the speed, pose, id-search and grid code and replaces §4c 4. - 5. for routed scenes.
+// Both kernels are templates on kTrack: <false> puts the ego on its path (§4c 3., adv_speed_pose), <true> - a handle with an
+// EgoTracker - moves it as a kinematic bicycle that chases the path (§4q, adv_speed_pose_tracked) and keeps one EgoTrackState per
+// scene.  The two pose steps share the speed step (adv_speed) and the arc walk (adv_walk).
 #pragma once
 #include "dev_geom.hpp"
 
@@ -44,12 +47,11 @@ static_assert(offsetof(LocationOut, globalpoint) == 0 && offsetof(LocationOut, v
 __device__ __forceinline__ int adv_get_id(int w, int slot) { return __shfl(w, kIdWord + slot, 64); }      // (a shuffle: every lane takes part)
 __device__ __forceinline__ void adv_set_id(int& w, int lane, int slot, int v) { if (lane == kIdWord + slot) w = v; }
 
-// §4c 1. - 3.: the new speed and pose of one scene (the same in every lane).  bad: BAD_PATH, nothing else is defined.
-struct AdvPose { double x, y, dir, vn; bool bad, path_end; };
-__device__ __forceinline__ AdvPose adv_speed_pose(const PlannerConfig& c, const EgoModel& m, const SceneIn& si, const PlanOut& po, const SceneState& st, int lane)
+// §4c 1. - 2.: the new speed (km/h) and the distance of this advance (m); the same in every lane
+struct AdvSpeed { double v, vn, dist; };
+__device__ __forceinline__ AdvSpeed adv_speed(const EgoModel& m, const SceneIn& si, const PlanOut& po)
 {
     const PlanningOut& R = po.result;
-    const GlobalPoint2D* __restrict__ P = po.road_points;
     // 1. speed (km/h)
     const double v = si.loc.velocity;
     double vn;
@@ -61,15 +63,20 @@ __device__ __forceinline__ AdvPose adv_speed_pose(const PlannerConfig& c, const 
         else { vn = v - m.max_dec * m.dt * 3.6; if (vn < tgt) vn = tgt; }
     }
     // 2. distance (m)
-    const double dist = 0.5 * (v + vn) / 3.6 * m.dt;
-    // 3. pose
-    // (path_near_id is the ego's index on the path the tick LOCALISED on; a tick that replanned published a new path that starts at the ego)
-    const int k0 = st.afresh_planning ? 0 : clampi(st.path_near_id, 0, DMPP_PATH_POINTS - 1);
-    const GlobalPoint2D p0 = P[k0];
-    bool bad = !finite_f64(dist) || !finite_f64(p0.x) || !finite_f64(p0.y);
-    double x = p0.x, y = p0.y, dir = si.loc.globalpoint.dir;
-    bool path_end = false;
-    if (!bad && dist > 0) {
+    AdvSpeed r; r.v = v; r.vn = vn; r.dist = 0.5 * (v + vn) / 3.6 * m.dt;
+    return r;
+}
+// The arc walk of §4c 3. (and of the target of §4q 2.): the point d metres along the path from P[k0], the sum of the segment lengths
+// taken in index order.  ran_out: no segment reached d, the point is P[199]; bad: a length that is not finite came first (nothing
+// else is defined).  d <= 0 (or NaN): P[k0].  kDir: dir is GetRoadAngle of the segment the walk ended on - or, ran out, of the last
+// one of non-zero length it passed - and dir0 where there is none.  The same in every lane.
+struct AdvWalk { double x, y, dir; bool bad, ran_out; };
+template <bool kDir>
+__device__ __forceinline__ AdvWalk adv_walk(const PlannerConfig& c, const GlobalPoint2D* __restrict__ P, int k0, double dist, double dir0, int lane)
+{
+    double x = P[k0].x, y = P[k0].y, dir = dir0;
+    bool bad = false, path_end = false;
+    if (dist > 0) {
         double acc = 0; bool done = false; int last_seg = -1;
         for (int c0 = k0; c0 < DMPP_PATH_POINTS - 1 && !done && !bad; c0 += 64) {
             const int i = c0 + lane;
@@ -85,7 +92,7 @@ __device__ __forceinline__ AdvPose adv_speed_pose(const PlannerConfig& c, const 
                     const GlobalPoint2D a = P[last_seg], b = P[last_seg + 1];
                     const double t = (dist - acc) / Lj;
                     x = a.x + t * (b.x - a.x); y = a.y + t * (b.y - a.y);
-                    dir = GetRoadAngle(c, a, b);
+                    if constexpr (kDir) dir = GetRoadAngle(c, a, b);
                     done = true; break;
                 }
                 acc = acc + Lj;
@@ -94,10 +101,136 @@ __device__ __forceinline__ AdvPose adv_speed_pose(const PlannerConfig& c, const 
         if (!bad && !done) {
             path_end = true;
             x = P[DMPP_PATH_POINTS - 1].x; y = P[DMPP_PATH_POINTS - 1].y;
-            if (last_seg >= 0) dir = GetRoadAngle(c, P[last_seg], P[last_seg + 1]);
+            if constexpr (kDir) if (last_seg >= 0) dir = GetRoadAngle(c, P[last_seg], P[last_seg + 1]);
         }
     }
-    AdvPose r; r.x = x; r.y = y; r.dir = dir; r.vn = vn; r.bad = bad; r.path_end = path_end;
+    AdvWalk r; r.x = x; r.y = y; r.dir = dir; r.bad = bad; r.ran_out = path_end;
+    return r;
+}
+// (path_near_id is the ego's index on the path the tick LOCALISED on; a tick that replanned published a new path that starts at the ego)
+__device__ __forceinline__ int adv_k0(const SceneState& st) { return st.afresh_planning ? 0 : clampi(st.path_near_id, 0, DMPP_PATH_POINTS - 1); }
+
+// §4c 1. - 3.: the new speed and pose of one scene on its path (the same in every lane).  bad: BAD_PATH, nothing else is defined.
+struct AdvPose { double x, y, dir, vn; bool bad, path_end; };
+__device__ __forceinline__ AdvPose adv_speed_pose(const PlannerConfig& c, const EgoModel& m, const SceneIn& si, const PlanOut& po, const SceneState& st, int lane)
+{
+    const GlobalPoint2D* __restrict__ P = po.road_points;
+    const AdvSpeed sp = adv_speed(m, si, po);
+    // 3. pose: the ego is put on its path
+    const int k0 = adv_k0(st);
+    const GlobalPoint2D p0 = P[k0];
+    AdvPose r; r.x = p0.x; r.y = p0.y; r.dir = si.loc.globalpoint.dir; r.vn = sp.vn; r.path_end = false;
+    r.bad = !finite_f64(sp.dist) || !finite_f64(p0.x) || !finite_f64(p0.y);
+    if (!r.bad) {
+        const AdvWalk w = adv_walk<true>(c, P, k0, sp.dist, r.dir, lane);
+        r.x = w.x; r.y = w.y; r.dir = w.dir; r.bad = w.bad; r.path_end = w.ran_out;
+    }
+    return r;
+}
+
+// ---- §4q: the tracked pose.  The ego keeps a pose of its own - (x, y) of its record, a unit heading and a curvature in its
+// EgoTrackState - and chases the path by pure pursuit.  Every operand below is the same in all lanes of the wave; the arithmetic is
+// + - * / sqrt (and floor, fabs) in the order §4q writes it, so every bit of the state and of x, y is the model's.
+struct AdvTrack { EgoTracker tk; EgoTrackState* state; const EpisodeStats* ep; };       // ep: nullptr while episodes are off
+template <bool kTrack> struct AdvTrackArg { using type = int; };                           // (<false>: one unused word)
+template <> struct AdvTrackArg<true> { using type = AdvTrack; };
+// §4q 1.: the unit heading of an angle in degrees by a fixed polynomial (no sin / cos call: their last bit is the library's)
+__device__ __forceinline__ void trk_heading(double dir, double& hx, double& hy)
+{
+    hx = 1; hy = 0;
+    if (!finite_f64(dir)) return;
+    const double q = floor((dir + 45.0) / 90.0);
+    const double r = dir - q * 90.0;
+    const int qi = (int)(q - 4.0 * floor(q / 4.0));
+    const double x = r * 0.017453292519943295;
+    const double x2 = x * x;
+    double ps = 2.8114572543455206e-15;
+    ps = ps * x2 + -7.6471637318198164e-13;
+    ps = ps * x2 + 1.6059043836821613e-10;
+    ps = ps * x2 + -2.505210838544172e-08;
+    ps = ps * x2 + 2.7557319223985893e-06;
+    ps = ps * x2 + -0.00019841269841269841;
+    ps = ps * x2 + 0.0083333333333333332;
+    ps = ps * x2 + -0.16666666666666666;
+    ps = ps * x2 + 1.0;
+    const double sn = ps * x;
+    double pc = 4.7794773323873853e-14;
+    pc = pc * x2 + -1.1470745597729725e-11;
+    pc = pc * x2 + 2.08767569878681e-09;
+    pc = pc * x2 + -2.7557319223985888e-07;
+    pc = pc * x2 + 2.4801587301587302e-05;
+    pc = pc * x2 + -0.0013888888888888889;
+    pc = pc * x2 + 0.041666666666666664;
+    pc = pc * x2 + -0.5;
+    pc = pc * x2 + 1.0;
+    const double cs = pc;
+    double ax, ay;
+    if (qi == 0) { ax = cs; ay = sn; } else if (qi == 1) { ax = -sn; ay = cs; } else if (qi == 2) { ax = -cs; ay = -sn; } else { ax = sn; ay = -cs; }
+    const double n = sqrt(ax * ax + ay * ay);
+    hx = ax / n; hy = ay / n;
+}
+__device__ __forceinline__ unsigned long long f64_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
+// §4q for one scene: speed and distance as §4c 1. - 2., then validity, target, steering, motion.  BAD_PATH: neither the record nor
+// the state is touched.  Lane 0 stores the new state.
+__device__ __forceinline__ AdvPose adv_speed_pose_tracked(const PlannerConfig& c, const EgoModel& m, const AdvTrack& a, const SceneIn& si, const PlanOut& po,
+                                                          const SceneState& st, int s, int lane)
+{
+    const GlobalPoint2D* __restrict__ P = po.road_points;
+    const EgoTracker& tk = a.tk;
+    const AdvSpeed sp = adv_speed(m, si, po);
+    const int k0 = adv_k0(st);
+    const GlobalPoint2D p0 = P[k0];
+    AdvPose r; r.x = si.loc.globalpoint.x; r.y = si.loc.globalpoint.y; r.dir = si.loc.globalpoint.dir; r.vn = sp.vn; r.path_end = false;
+    r.bad = !finite_f64(sp.dist) || !finite_f64(p0.x) || !finite_f64(p0.y);
+    if (r.bad) return r;
+    // 2. the walk for s gives the flags of §4c 3. only; the target is the point ld metres along the path
+    const AdvWalk ws = adv_walk<false>(c, P, k0, sp.dist, 0.0, lane);
+    if (ws.bad) { r.bad = true; return r; }
+    const double ld = tk.look_min + tk.look_gain * sp.vn / 3.6;
+    const AdvWalk wt = adv_walk<false>(c, P, k0, ld, 0.0, lane);
+    if (wt.bad || !finite_f64(wt.x) || !finite_f64(wt.y)) { r.bad = true; return r; }
+    r.path_end = ws.ran_out;
+    // 1. the state, re-derived when it is stale
+    EgoTrackState S = a.state[s];
+    const bool stale = S.valid == 0 || S.key_x != f64_bits(r.x) || S.key_y != f64_bits(r.y) || S.key_dir != f64_bits(r.dir) || (a.ep && a.ep[s].age == 0);
+    if (stale) { trk_heading(r.dir, S.hx, S.hy); S.kappa = 0; S.n_init = S.n_init + 1; }
+    // 3. steering: pure pursuit in curvature, clamped, rate-limited
+    const double ex = wt.x - r.x, ey = wt.y - r.y;
+    const double ly = ey * S.hx - ex * S.hy, d2 = ex * ex + ey * ey;
+    double kc = 0;
+    if (d2 != 0) kc = 2.0 * ly / d2;
+    if (kc != kc) kc = 0;
+    int sat = 0;
+    if (kc >= tk.max_curv) { kc = tk.max_curv; sat = 1; }
+    if (kc <= -tk.max_curv) { kc = -tk.max_curv; sat = 1; }
+    const double dk = tk.curv_rate * m.dt, k_lo = S.kappa - dk, k_hi = S.kappa + dk;
+    double kn = kc;
+    if (kn > k_hi) kn = k_hi;
+    if (kn < k_lo) kn = k_lo;
+    S.kappa = kn; S.n_sat = S.n_sat + sat;
+    const double ak = fabs(kn);
+    if (ak > S.max_kappa) S.max_kappa = ak;
+    const double ka = kn + tk.curv_bias;
+    // 4. motion: n_sub substeps of half turn, move, half turn, renormalise
+    double px = r.x, py = r.y, hx = S.hx, hy = S.hy;
+    if (sp.dist > 0) {
+        const double ds = sp.dist / (double)tk.n_sub;
+        const double t = 0.25 * ka * ds, t2 = t * t, den = 1.0 + t2;
+        const double rc = (1.0 - t2) / den, rs = 2.0 * t / den;
+#pragma unroll 1
+        for (int k = 0; k < tk.n_sub; k++) {
+            const double mx = rc * hx - rs * hy, my = rs * hx + rc * hy;
+            px = px + ds * mx; py = py + ds * my;
+            const double nx = rc * mx - rs * my, ny = rs * mx + rc * my;
+            const double n = sqrt(nx * nx + ny * ny);
+            hx = nx / n; hy = ny / n;
+        }
+    }
+    // 5. output
+    GlobalPoint2D o, h; o.x = 0; o.y = 0; h.x = hx; h.y = hy;
+    r.x = px; r.y = py; r.dir = GetRoadAngle(c, o, h);
+    S.hx = hx; S.hy = hy; S.key_x = f64_bits(r.x); S.key_y = f64_bits(r.y); S.key_dir = f64_bits(r.dir); S.valid = 1; S._pad = 0;
+    if (lane == 0) a.state[s] = S;
     return r;
 }
 __device__ __forceinline__ void adv_store_pose(int& w, int lane, const AdvPose& p)
@@ -207,10 +340,12 @@ __device__ __forceinline__ void adv_lane_step(const GlobalPoint3D* __restrict__ 
     }
 }
 
+// kTrack: the pose step is §4q's (a handle with an EgoTracker); <false> is the kernel of a handle without one and takes one unused word
+template <bool kTrack>
 __global__ void __launch_bounds__(kBlock)
 k_advance_egos(PlannerConfig c, EgoModel m, GridFollow gf, int n_scenes, int map_mode, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
                const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const GlobalPoint3D* __restrict__ lane_pool,
-               int32_t* __restrict__ flags, EgoTrace* __restrict__ trace)
+               int32_t* __restrict__ flags, EgoTrace* __restrict__ trace, typename AdvTrackArg<kTrack>::type trk)
 {
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * kAdvScenes + (threadIdx.x >> 6);
@@ -221,7 +356,9 @@ k_advance_egos(PlannerConfig c, EgoModel m, GridFollow gf, int n_scenes, int map
     const int ln = si.loc.lane_num;
     int f = f_in, ln_new = ln;
     if (f_in == 0) {
-        const AdvPose p = adv_speed_pose(c, m, si, plan[s], state[s], lane);
+        AdvPose p;
+        if constexpr (kTrack) p = adv_speed_pose_tracked(c, m, trk, si, plan[s], state[s], s, lane);
+        else p = adv_speed_pose(c, m, si, plan[s], state[s], lane);
         if (p.bad) f |= DMPP_EGO_BAD_PATH;
         else {
             if (p.path_end) f |= DMPP_EGO_PATH_END;

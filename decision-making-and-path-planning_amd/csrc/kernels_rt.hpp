@@ -37,11 +37,13 @@ __device__ __forceinline__ int wave_find_junction(const MapJunction* __restrict_
 
 __device__ __forceinline__ void rt_zero_ids(int& w, int lane) { if (lane >= kIdWord && lane < kIdWord + DMPP_LANESUM) w = 0; }
 
+template <bool kTrack>
 __global__ void __launch_bounds__(kBlock)
 k_advance_route(PlannerConfig c, EgoModel m, RouteModel rm, GridFollow gf, int n_scenes, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
                 const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const GlobalPoint3D* __restrict__ lane_pool,
                 const GlobalPoint2D* __restrict__ ref_pool, int n_junctions, const MapJunction* __restrict__ junctions,
-                const RouteLeg* __restrict__ legs, const int32_t* __restrict__ route_first, int32_t* __restrict__ flags, EgoTrace* __restrict__ trace)
+                const RouteLeg* __restrict__ legs, const int32_t* __restrict__ route_first, int32_t* __restrict__ flags, EgoTrace* __restrict__ trace,
+                typename AdvTrackArg<kTrack>::type trk)
 {
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * kAdvScenes + (threadIdx.x >> 6);
@@ -52,7 +54,9 @@ k_advance_route(PlannerConfig c, EgoModel m, RouteModel rm, GridFollow gf, int n
     const int ln = si.loc.lane_num;
     int f = f_in, ln_new = ln;
     if (f_in == 0) {
-        const AdvPose p = adv_speed_pose(c, m, si, plan[s], state[s], lane);
+        AdvPose p;
+        if constexpr (kTrack) p = adv_speed_pose_tracked(c, m, trk, si, plan[s], state[s], s, lane);
+        else p = adv_speed_pose(c, m, si, plan[s], state[s], lane);
         if (p.bad) f |= DMPP_EGO_BAD_PATH;
         else {
             if (p.path_end) f |= DMPP_EGO_PATH_END;

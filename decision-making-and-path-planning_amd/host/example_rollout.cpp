@@ -9,6 +9,9 @@
 // With --follow the grid follows the ego (pp_set_grid_follow): the advance step re-centres grid_origin and goal.
 // Combined with --route the ring is driven with the grid stage ON, on a grid of 64 m, and the host prints how many egos carry
 // OFF_GRID at the end (without --follow a routed run keeps the grid stage off: every ego would leave its grid on its first road).
+// With --track [BIAS] the egos do not sit on their planned paths: every ego keeps a pose of its own and steers a bicycle model along
+// the plan (pp_set_ego_tracker with the default model and curv_bias BIAS); the host prints how hard the egos steered
+// and how often the planner replanned.  It works with --route and every other flag.
 // With --route --traffic every ring ego has a slower vehicle 20 m ahead of it (pp_set_traffic): a scripted actor at
 // 1.5 m/s on the closed track of the ego's lane, written into the ego's one obstacle entry on every staged input set; the run is
 // scored, and the host prints how many egos saw their vehicle, the worst clearance and the distance travelled.
@@ -40,6 +43,7 @@
 // prints every frozen scene's triggering tick and, for the first three, the records before it.  Any mode; a routed run gets the scorecard.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -83,6 +87,27 @@ static int print_score_trace(pp_handle h, int n, int depth)
                         r.marks & 255, (r.marks & DMPP_TICK_START) ? "  (start record)" : "");
         }
     }
+    return 0;
+}
+
+// --track [BIAS]: the ego tracker, set right behind the resident scenes; read back after the rollout
+static bool g_track = false; static double g_track_bias = 0;
+static int set_tracker(pp_handle h)
+{
+    if (!g_track) return 0;
+    EgoTracker tk; pp_default_ego_tracker(&tk); tk.curv_bias = g_track_bias;
+    CHECK(pp_set_ego_tracker(h, &tk));
+    return 0;
+}
+static int print_tracker(pp_handle h, int n)
+{
+    if (!g_track) return 0;
+    std::vector<EgoTrackState> ts((size_t)n);
+    CHECK(pp_get_ego_track_state(h, ts.data(), n));
+    double max_kappa = 0; long long n_init = 0, n_sat = 0;
+    for (const EgoTrackState& t : ts) { max_kappa = std::max(max_kappa, t.max_kappa); n_init += t.n_init; n_sat += t.n_sat; }
+    std::printf("track: %d egos steered a bicycle model along their plans (curv_bias %g 1/m): largest |curvature| %.4f 1/m, %lld advances met max_curv, %lld states derived\n",
+                n, g_track_bias, max_kappa, n_sat, n_init);
     return 0;
 }
 
@@ -192,6 +217,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
     RouteModel rm; CHECK(pp_default_route_model(&rm));
     CHECK(pp_set_route(h, (int)legs.size(), legs.data(), route_first.data(), &rm));
     if (follow) { GridFollow gf; pp_default_grid_follow(&gf); CHECK(pp_set_grid_follow(h, &gf)); }
+    if (set_tracker(h)) return 2;
     EgoModel model; pp_default_ego_model(&model);
     if (traffic) {
         if (shared) {
@@ -348,6 +374,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
     std::printf("\nroute: %d egos on a ring of 4 roads for %d ticks (last tick id %lld): %d legs completed, %d arrived (ROUTE_END), %d missed an exit, %d with another flag\n",
                 n, ticks, last, legs_done, arrived, missed, other);
     if (follow) std::printf("follow: the grid stage ran on %d x %d cells that followed the ego: %d of %d egos carry OFF_GRID\n", cfg.grid_w, cfg.grid_h, off_grid, n);
+    if (print_tracker(h, n)) return 2;
     pp_destroy(h);
     std::printf("example_rollout ok\n");
     return 0;
@@ -360,6 +387,11 @@ int main(int argc, char** argv)
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
         else if (std::strcmp(argv[a], "--follow") == 0) follow = true;
+        else if (std::strcmp(argv[a], "--track") == 0) {
+            g_track = true;                               // a number behind it is the steering bias
+            char* e = nullptr;
+            if (a + 1 < argc) { const double b = std::strtod(argv[a + 1], &e); if (e != argv[a + 1] && *e == 0) { g_track_bias = b; a++; } }
+        }
         else if (std::strcmp(argv[a], "--traffic") == 0) traffic = true;
         else if (std::strcmp(argv[a], "--react") == 0) react = true;
         else if (std::strcmp(argv[a], "--shared") == 0) shared = true;
@@ -374,7 +406,7 @@ int main(int argc, char** argv)
         }
         else if (std::strcmp(argv[a], "--log") == 0 && a + 1 < argc) log_cap = std::atoi(argv[++a]);
         else if (std::strcmp(argv[a], "--score-trace") == 0 && a + 1 < argc) { if (std::sscanf(argv[++a], "%d,%d", &trace_depth, &trace_post) < 1) trace_depth = -1; }
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow] [--score-trace DEPTH[,POST]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
@@ -414,6 +446,7 @@ int main(int argc, char** argv)
     CHECK(pp_set_state(h, st.data(), n));
     if (fleet) { const int32_t world_first[2] = { 0, n }; CHECK(pp_set_fleet(h, 1, world_first, &fm)); }      // one world of all egos
     if (follow) { GridFollow gf; pp_default_grid_follow(&gf); CHECK(pp_set_grid_follow(h, &gf)); }              // OFF_GRID below: the egos the frame could not hold
+    if (set_tracker(h)) return 2;
 
     EgoModel model; pp_default_ego_model(&model);
     EgoTrace* trace = (EgoTrace*)pp_host_alloc(sizeof(EgoTrace) * (size_t)ticks * n);      // pinned: the kernel writes it over PCIe
@@ -455,6 +488,7 @@ int main(int argc, char** argv)
     std::printf("scorecard: worst clearance %.3f m, scene %d, tick %d, obstacle %d\n", score[(size_t)worst].min_clearance, worst,
                 score[(size_t)worst].min_clearance_tick, score[(size_t)worst].min_clearance_obs);
     std::printf("scorecard: mean distance %.2f m (the trace's odometer above: %.2f m)\n", sdist / n, dist / n);
+    if (print_tracker(h, n)) return 2;
     if (fleet) {
         // Ego-ego contact: a nearest obstacle at or beyond the scene's own entries is a peer slot.  The scorecard keeps ONE nearest
         // obstacle per scene (where its smallest clearance occurred), so the ticks counted are those of the scenes whose closest

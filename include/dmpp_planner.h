@@ -306,6 +306,31 @@ int  pp_set_route(pp_handle h, int n_legs_total, const RouteLeg* legs, const int
 void pp_default_grid_follow(GridFollow* gf);         /* goal_point 199 (the end of the planned path), margin_cells 32 (8 m at 0.25 m) */
 int  pp_set_grid_follow(pp_handle h, const GridFollow* gf);
 
+/* ---- ego tracking model: rollout egos steer a bicycle model along the plan -------------------------------------
+ * Without it every advance puts the ego ON point k0 of its planned path and walks s metres along it (§4c 3.): the lateral error
+ * is dropped, and the planner's replan causes 2 (|path_lat_dis| > 0.2 m) and 3 (|path_dir_err| > 45 deg) can never occur in a
+ * rollout.  pp_set_ego_tracker gives every ego a pose of its own: one EgoTrackState per scene (unit heading, curvature) is kept on
+ * the device, and every advance (k_advance_egos<true> / k_advance_route<true>) steers towards the path point
+ * ld = look_min + look_gain * v' / 3.6 metres ahead of k0 by pure pursuit in curvature - clamped to +-max_curv, rate-limited by
+ * curv_rate * dt, curv_bias added - and moves the ego s metres from where it STANDS in n_sub substeps.  Speed, distance and
+ * everything behind the pose (ids, lane number, route step, grid follow, flags, trace) are unchanged.  Every bit of EgoTrackState
+ * and of the staged x, y, velocity is specified (§4q); dir is GetRoadAngle of the heading vector.
+ * A state is re-derived (kappa 0, heading from loc.globalpoint.dir, n_init + 1) when it is not valid, when the pose bits of the
+ * record the advance reads are not the ones this model stored last (pp_update_async, pp_tick_io, a respawn), or - episodes on -
+ * when EpisodeStats.age is 0.  The model belongs to the HANDLE, like GridFollow: no rollout feature bit, no set call retires it,
+ * it survives pp_set_scenes / pp_set_egos / pp_set_n_scenes / pp_set_map (which clear the per-scene states).  It takes effect
+ * from the next pp_advance_async.  tk == NULL: off - the advance is then the one of a handle that never set it, byte for byte;
+ * the states stay as they are and stay readable (switched on again, a state whose ego moved meanwhile is re-derived by the key
+ * rule).  The states are allocated and zeroed by the first successful call with a model (one host wait, that call only; every
+ * other call does no device work); a handle that never calls it allocates and launches nothing new.
+ * PP_ERR_ARG, with nothing changed: a non-finite field, look_min <= 0, look_gain < 0, max_curv <= 0, curv_rate <= 0, n_sub
+ * outside 1 .. 8.
+ * pp_get_ego_track_state: the states of the first n scenes, a staged advance included (host wait, as pp_get_ego_flags);
+ * PP_ERR_STATE when the tracker was never set on this handle. */
+void pp_default_ego_tracker(EgoTracker* tk);         /* look_min 3 m, look_gain 0.5 s, max_curv 0.2, curv_rate 0.3, bias 0, n_sub 2 */
+int  pp_set_ego_tracker(pp_handle h, const EgoTracker* tk);
+int  pp_get_ego_track_state(pp_handle h, EgoTrackState* out, int n);
+
 /* ---- lane traffic: scripted vehicles that drive the map during a rollout ------------------------------------------
  * pp_set_traffic gives the handle n_tracks TRACKS (polylines: slices of `points`, host pointers; a closed track has one more
  * segment from its last point back to its first) and n_actors ACTORS.  Actor a drives tracks[a.track] at a.speed m/s from arc
@@ -596,7 +621,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
  * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
  * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord, 35 ScoreTraceModel, 36 ScoreTick,
- * 37 ScoreTraceInfo, 38 EpisodeSchedule, 39 EpisodeScheduleRow */
+ * 37 ScoreTraceInfo, 38 EpisodeSchedule, 39 EpisodeScheduleRow, 40 EgoTracker, 41 EgoTrackState */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

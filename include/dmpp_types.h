@@ -318,6 +318,30 @@ typedef struct GridFollow {
     int32_t margin_cells;  /* the frame is held while ego and goal lie at least this many cells inside it      */
 } GridFollow;              /* 8 B */
 
+/* ---- ego tracking model (build-defined) -------------------------------------------------------
+ * pp_set_ego_tracker gives every rollout ego a pose of its own: the advance step no longer puts the ego ON its planned path
+ * but integrates position, heading and curvature as a kinematic bicycle that chases the path by pure pursuit.  The look-ahead
+ * is ld = look_min + look_gain * v / 3.6 metres (v: the new speed, km/h). */
+typedef struct EgoTracker {
+    double  look_min;      /* m; > 0                                                                          */
+    double  look_gain;     /* s; >= 0                                                                         */
+    double  max_curv;      /* 1/m; the bound on the commanded |curvature|; > 0                                */
+    double  curv_rate;     /* 1/(m s); the most the curvature state changes per second; > 0                   */
+    double  curv_bias;     /* 1/m; a steering misalignment, added to the applied curvature after the limits   */
+    int32_t n_sub;         /* substeps of the motion per advance, 1 .. 8                                      */
+    int32_t _pad;
+} EgoTracker;              /* 48 B */
+typedef struct EgoTrackState {          /* one per scene; every byte is specified (§4q) */
+    double   hx, hy;                    /* unit heading vector                                                         */
+    double   kappa;                     /* curvature state, 1/m (without curv_bias)                                    */
+    uint64_t key_x, key_y, key_dir;     /* the bits of loc.globalpoint this model last stored into SceneIn             */
+    double   max_kappa;                 /* the largest |kappa| seen                                                    */
+    int32_t  valid;                     /* 0: the state is re-derived from SceneIn by the next advance                 */
+    int32_t  n_init;                    /* how many times the state was re-derived                                     */
+    int32_t  n_sat;                     /* advances whose commanded curvature met +-max_curv                           */
+    int32_t  _pad;
+} EgoTrackState;                        /* 72 B */
+
 /* ---- lane traffic (build-defined: scripted vehicles that drive a polyline during a rollout) ------
  * pp_set_traffic gives the handle TRACKS - polylines, each a slice of one point array, closed ones with one more segment
  * from the last point back to the first - and ACTORS: each drives one track at its own constant speed and is written, on

@@ -40,7 +40,11 @@ behind the timed rollout, outside the timing.  With ONE_ROLLOUT one more leg wit
 SCORE=1 TRACE=depth: every run has a scored rollout leg without and one with the score trace (pp_set_score_trace: the default model with
 `depth` records per scene, DESIGN.md §4o: k_score_ego<false, true> in the place of <false, false>), alternating; headers and one ring are
 read behind the timed rollout, outside the timing.  TRACE_TRIGGER=mask replaces the model's trigger (0: rings that never freeze, so every
-scene stores every tick).  With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels."""
+scene stores every tick).  With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels.
+TRACK=1 [TRACK_BIAS=b]: every run has a rollout leg of routed ring egos (grid stage off, scorecard on for its replan count) without and
+one with the ego tracker (pp_set_ego_tracker: the default model with curv_bias b, DESIGN.md §4q: k_advance_route<true> in the place of
+<false>), alternating.  The workloads differ once tracked egos replan on lateral error: the replan counts are printed beside the rates.
+With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels."""
 import os
 import statistics
 import sys
@@ -288,6 +292,36 @@ def follow_run(on):
     return n * steps / dt, off_grid
 
 
+def track_run(on, bias):
+    """The ring of follow_run with the grid stage off and the scorecard on (for its replan count); on: the ego tracker of
+    DESIGN.md §4q with the default model and curv_bias = bias."""
+    import route_scenes as rs
+    rcfg = dm.default_config(128)
+    rcfg["grid_stage"] = 0
+    m = rs.build_ring(dm)
+    sc, legs, rf = rs.make_egos(dm, rcfg, m, n, seed=5, ids=(10, 250), legs=(6, 10))
+    pl = dm.Planner(rcfg, device=0, **rs.caps(m, n))
+    pl.set_map(m)
+    pl.set_egos(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    pl.set_route(legs, rf)
+    if on:
+        tk = dm.default_ego_tracker()
+        tk["curv_bias"] = bias
+        pl.set_ego_tracker(tk)
+    pl.score_begin()
+    pl.rollout(warm, model)
+    pl.sync()
+    t0 = time.perf_counter()
+    pl.rollout(steps, model)
+    pl.sync()
+    dt = time.perf_counter() - t0
+    replans, frozen = int(pl.rollout_score()["n_replans"].sum()), int((pl.ego_flags() != 0).sum())
+    track_run.max_kappa = float(pl.ego_track_state()["max_kappa"].max()) if on else 0.0
+    pl.close()
+    return n * steps / dt, replans, frozen
+
+
 TRACE = int(os.environ.get("TRACE", "0"))
 
 
@@ -468,6 +502,22 @@ if os.environ.get("ROUTE", "0") == "1":
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more routed rollout alone
         route_run(True)
+    sys.exit(0)
+if os.environ.get("TRACK", "0") == "1":
+    bias = float(os.environ.get("TRACK_BIAS", "0"))
+    off, on = [], []
+    for r in range(runs):
+        a, ra, fa = track_run(False, bias)
+        b, rb, fb = track_run(True, bias)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos, scorecard on  tracker off %.3f M ticks/s (%d replans, %d frozen)   tracker on, bias %g: %.3f M ticks/s (%d replans, %d frozen, max |kappa| %.4f)" %
+              (r, n, a / 1e6, ra, fa, bias, b / 1e6, rb, fb, track_run.max_kappa), flush=True)
+    print("median  %d ring egos  tracker off %.3f M ticks/s (spread %.3f)   tracker on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: k_advance_route<false> and <true> in one trace
+        track_run(False, bias)
+        track_run(True, bias)
     sys.exit(0)
 if os.environ.get("FOLLOW", "0").startswith("trace_"):
     on = os.environ["FOLLOW"] == "trace_on"
