@@ -39,7 +39,24 @@ pp_handle CShare::Device()
     Lock g(p.m_mu);
     return p.handle(false, false);
 }
-pp_handle CShare::op_handle() { return m_h ? m_h : handle(m_decision_object, false); }
+// A stand-alone operator reads PlannerConfig too (the remain distances, EPSILON, the WGS84 frame ...): it runs with the current
+// Config(), as a tick does.  The stage switches stay as the object's last tick applied them, so that a helper call between
+// two ticks flips nothing on the handle; the path plan() / decide() take (handle, tick_io) is not involved.
+pp_handle CShare::op_handle()
+{
+    if (!m_h || !m_have_applied) return handle(m_decision_object, false);
+    PlannerConfig c = Config();
+    c.decision_stage = m_applied.decision_stage; c.grid_stage = m_applied.grid_stage;
+    if (std::memcmp(&m_applied, &c, sizeof(c)) == 0) return m_h;
+    int rc = pp_set_config(m_h, &c);
+    if ((rc == PP_ERR_CAPACITY || rc == PP_ERR_STATE) && c.grid_stage) {   // a grid the context was not made for: no operator reads it
+        c.grid_stage = 0;
+        rc = pp_set_config(m_h, &c);
+    }
+    if (rc) { note(rc); return nullptr; }
+    m_applied = c;
+    return m_h;
+}
 void CShare::SetMap(const LaneMap& map)
 {
     Lock g(m_mu);
@@ -184,13 +201,17 @@ GPSPoint2D CShare::GlobalToWGS84(GlobalPoint2D p)
     return g;
 }
 int CShare::NearestId(GlobalPoint2D p, vector<GlobalPoint2D> path)
-{   // the argmin loop of Planning.cpp:640-650 (first minimum); distances from the device
+{   // the argmin loop of Planning.cpp:640-650: the FIRST minimum of the distances (from the device), a NaN distance is never
+    // the minimum (the rule of every arg-min on the device); an empty path, or one whose distances are all NaN, gives 0
     if (path.empty()) return 0;
     Lock g(m_mu);
     vector<GlobalPoint2D> a(path.size(), p);
     vector<double> d(path.size());
     note(pp_geom_batch(op_handle(), 3, (int)path.size(), a.data(), path.data(), nullptr, d.data()));
-    return (int)(std::min_element(d.begin(), d.end()) - d.begin());
+    size_t best = 0; bool have = false;
+    for (size_t i = 0; i < d.size(); i++)
+        if (d[i] == d[i] && (!have || d[i] < d[best])) { best = i; have = true; }
+    return (int)best;
 }
 double CShare::LatDis(GlobalPoint2D p, GlobalPoint2D a, GlobalPoint2D b)
 { Lock g(m_mu); double v = 0; note(pp_geom_batch(op_handle(), 0, 1, &p, &a, &b, &v)); return v; }
@@ -232,7 +253,8 @@ void CPlanning::plan(const DecisionOut& decision, const LocationOut& location, c
 }
 
 // The stage methods below run the device tick on a SCRATCH copy of the state and return the stage's own
-// outputs (each of these stages stores its outputs in SceneState untouched by later stages).
+// outputs (each of these stages stores its outputs in SceneState untouched by later stages: held on scenes that replan by every
+// cause in tests/test_class_stages.py).  m_state itself is left as it was.
 void CPlanning::Calculate_aim_dis(DecisionOut dec, LocationOut loc, VehStatus, FLOAT& far_, FLOAT& near_)
 {
     Lock g(m_mu);

@@ -26,6 +26,10 @@ public:
 
     void Calculate_aim_dis(DecisionOut decision_result, LocationOut vhcl_location, VehStatus vhcl_status,
                            FLOAT& faraim_dis, FLOAT& nearaim_dis);
+    // Deviation from the reference: its SearchAimPoint reads the MEMBER faraim_dis that the last Calculate_aim_dis left
+    // (Planning.cpp:118,121); this one recomputes the aim distance from the vhcl_location it is given, so a call does not
+    // depend on which location Calculate_aim_dis saw last.  The aim points are in/out: a branch that assigns nothing keeps
+    // the caller's values.
     void SearchAimPoint(DecisionOut decision_result, LocationOut vhcl_location, VehStatus vhcl_status,
                         AimPoint& aimpoint_far, AimPoint& aimpoint_near);
     void InitialPlanning(DecisionOut decision_result, LocationOut vhcl_location, VehStatus vhcl_status,

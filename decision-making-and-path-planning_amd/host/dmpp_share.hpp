@@ -51,7 +51,7 @@ struct DmppStatus { int code = 0; const char* text = ""; };
 // by its own thread only.  Here every object owns its GPU context - a pp_handle with its resident lane map and one pinned
 // PpSceneIo block - behind its own mutex: decide() and plan() may run concurrently on two threads, and two threads sharing
 // ONE object are serialised call by call.  The last status is per thread.  Config() is process-wide and read when a context
-// is (re)created and on every tick: set it before the threads start (the reference's macros are compile-time constants).
+// is (re)created, on every tick and by every helper call: set it before the threads start (the reference's macros are compile-time constants).
 class CShare {
 public:
     CShare();
@@ -71,6 +71,8 @@ public:
     double CalcDistance(GlobalPoint2D a, GlobalPoint2D b);                                           // Planning.cpp:509
     double CalcGlobalDir(GlobalPoint2D a, GlobalPoint2D b);                                          // Planning.cpp:519
     GPSPoint2D GlobalToWGS84(GlobalPoint2D p);                                                       // Planning.cpp:209
+    // index of the FIRST minimum of the distances from p to the path's points; a NaN distance is never the minimum; an empty
+    // path and one whose distances are all NaN give 0
     int    NearestId(GlobalPoint2D p, vector<GlobalPoint2D> path);                                   // Decision.cpp:1889
     double LatDis(GlobalPoint2D p, GlobalPoint2D a, GlobalPoint2D b);                                // Decision.cpp:1895
     void   SetMap(const LaneMap& map);             // planning_MapData / decision_MapData of this object: uploaded once, resident
@@ -83,7 +85,8 @@ protected:
     int tick_io(bool decision_stage, const LocationOut& loc, const DecisionOutPod& dec, const vector<GlobalPoint2D>& ref,
                 const vector<ObPoint>& obs, int stub_attribute, double period_last_ms, const GlobalPoint2D* origin, const GlobalPoint2D* goal,
                 SceneState& st, PlanOut& out, GridOut* grid, vector<GlobalPoint2D>* refpath_out);
-    pp_handle op_handle();                                     // this object's context for a stand-alone operator (created when absent)
+    pp_handle op_handle();                                     // this object's context for a stand-alone operator (created when absent), with
+                                                               // the current Config() applied and the stage switches of the last tick kept
     std::recursive_mutex m_mu;
     LaneMap m_map;
     bool m_grid_capable = false;                               // the context is created with the buffers of the grid stage (CPlanning)

@@ -41,10 +41,12 @@ int main()
     GlobalPoint2D a{0, 0}, b{1, 1}, c{0, 1};
     const double ang = pl.GetRoadAngle(a, b), err = pl.GetAngleErr(350, 10), lat = pl.GetLatDis(c, a, b), dist = pl.CalcDistance(a, b);
     int cause = 0; const bool judge = pl.UpdatePlanJudge(DecisionOut(), in.loc, 7, cause);
+    const double radius = pl.CalculateRadius();
     std::printf("GetRoadAngle %.6f GetAngleErr %.1f GetLatDis %.6f CalcDistance %.6f UpdatePlanJudge %d/%d CalculateRadius %.3f\n",
-                ang, err, lat, dist, (int)judge, cause, pl.CalculateRadius());
+                ang, err, lat, dist, (int)judge, cause, radius);
     const bool ok = std::fabs(ang - 45.0) < 1e-9 && err == 20.0 && std::fabs(lat - std::sqrt(0.5)) < 1e-12 &&
-                    std::fabs(dist - std::sqrt(2.0)) < 1e-15 && judge && cause == 1 && std::isfinite(result.desspd);
+                    std::fabs(dist - std::sqrt(2.0)) < 1e-15 && judge && cause == 1 && std::isfinite(result.desspd) &&
+                    std::isfinite(radius) && radius > 0;
     std::printf(ok ? "example ok\n" : "example FAILED\n");
     return ok ? 0 : 1;
 }

@@ -59,13 +59,23 @@ static void planning_thread(const Inputs& I, int n, Trace& T)
         T.res.push_back(result);
     }
 }
-static void helper_thread(int n, Trace& T)
+// CalcDistance, and GetVhclLocalState - a whole tick on a scratch copy of the planning object's state - while plan() runs on the
+// other thread: its five outputs depend on its arguments alone, whatever state the copy was taken from.
+static void helper_thread(const Inputs& I, int n, Trace& T)
 {
     CPlanning& p = CPlanning::Instance();
+    GlobalPoint2D path[DMPP_PATH_POINTS];
+    for (int i = 0; i < DMPP_PATH_POINTS; i++) path[i] = GlobalPoint2D{I.in.loc.globalpoint.x - 5 + 0.25 * i, I.in.loc.globalpoint.y + 0.01 * i};
     for (int t = 0; t < n; t++) {
         GlobalPoint2D a{0, 0}, b{1.0 + t, 1};
         T.helper.push_back(p.CalcDistance(a, b));
         if (CShare::LastStatus().code) T.errors++;
+        LocationOut loc = I.in.loc;
+        loc.globalpoint.x += 0.3 * t;
+        double lat = 0, dir_err = 0, remain = 0; int near_id = 0, front_id = 0;
+        p.GetVhclLocalState(loc, path, lat, dir_err, near_id, front_id, remain);
+        if (CShare::LastStatus().code) T.errors++;
+        for (double v : {lat, dir_err, (double)near_id, (double)front_id, remain}) T.helper.push_back(v);
     }
 }
 
@@ -80,17 +90,17 @@ int main(int argc, char** argv)
     // reference: the same calls, one thread at a time
     Trace ref;
     if (have_gpu) {
-        decision_thread(I, n, ref); planning_thread(I, n, ref); helper_thread(n, ref);
+        decision_thread(I, n, ref); planning_thread(I, n, ref); helper_thread(I, n, ref);
         CDecision::Instance().Reset(); CPlanning::Instance().Reset();
     }
     Trace a, b, c;
     std::thread t1(decision_thread, std::cref(I), n, std::ref(a));
     std::thread t2(planning_thread, std::cref(I), n, std::ref(b));
-    std::thread t3(helper_thread, n, std::ref(c));
+    std::thread t3(helper_thread, std::cref(I), n, std::ref(c));
     t1.join(); t2.join(); t3.join();
     if (!have_gpu) {
         // no GPU: every call must have failed cleanly (and the sanitizer has watched the host side)
-        const bool ok = a.errors == n && b.errors == n && c.errors == n;
+        const bool ok = a.errors == n && b.errors == n && c.errors == 2 * n;      // the helper thread makes two calls per round
         std::printf(ok ? "host_threads ok (no GPU: %d + %d + %d calls refused)\n" : "host_threads FAILED (no GPU) %d %d %d\n", a.errors, b.errors, c.errors);
         return ok ? 0 : 1;
     }

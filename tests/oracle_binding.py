@@ -38,6 +38,9 @@ class Oracle:
         L.orc_Calculate_aim_dis.argtypes = [vp, vp, vp, vp]
         L.orc_GetVhclLocalState.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.orc_UpdatePlanJudge.argtypes = [vp, vp, vp, ci, vp, vp]
+        L.orc_SearchAimPoint.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.orc_GlobalToWGS84.restype = P2            # GPSPoint2D {lat, lng}
+        L.orc_GlobalToWGS84.argtypes = [vp, P2]
         L.orc_SpeedPlanning.argtypes = [ci, vp, vp, cd, cd, C.c_float, vp, vp, vp]
         L.orc_CalculateRadius.restype = cd
         L.orc_CalculateRadius.argtypes = [vp, ci, ci]
@@ -69,6 +72,35 @@ class Oracle:
 
     def CalculateRadius(self, pts, near_id, front_id):
         return self.L.orc_CalculateRadius(_p(pts), near_id, front_id)
+
+    def CalcDistance(self, a, b):
+        return self.L.orc_CalcDistance(P2(*a), P2(*b))
+
+    def GlobalToWGS84(self, cfg, p):
+        """(lat, lng)"""
+        g = self.L.orc_GlobalToWGS84(_p(cfg), P2(*p))
+        return g.x, g.y
+
+    def UpdatePlanJudge(self, cfg, behavior, pos, last_behavior, lat, derr, rem):
+        """(afresh_planning, afresh_cause) from the three members the reference's method reads (Planning.cpp:810-821)"""
+        dec, loc, st = np.zeros(1, dm.DecisionOutPod), np.zeros(1, dm.LocationOut), np.zeros(1, dm.SceneState)
+        dec["behavior"], loc["pos"] = behavior, pos
+        st["path_lat_dis"], st["path_dir_err"], st["remain_dis"] = lat, derr, rem
+        cause = np.zeros(1, np.int32)
+        afresh = self.L.orc_UpdatePlanJudge(_p(cfg), _p(dec), _p(loc), last_behavior, _p(st), _p(cause))
+        return int(afresh), int(cause[0])
+
+    def SearchAimPoint(self, cfg, scene_in, dec, refpath, lane_pool, far, near, faraim_dis, nearaim_dis):
+        """One SceneIn record (its lane views index lane_pool), DecisionOutPod, refpath points, the aim points coming in
+        and the two aim distances Calculate_aim_dis left: returns the (far, near) AimPoint records going out."""
+        st = np.zeros(1, dm.SceneState)
+        st["aimpoint_far"], st["aimpoint_near"] = far, near
+        st["faraim_dis"], st["nearaim_dis"] = faraim_dis, nearaim_dis
+        si = np.ascontiguousarray(scene_in).reshape(1)
+        d = np.array(dec, dm.DecisionOutPod).reshape(1)
+        ref = np.ascontiguousarray(refpath) if len(refpath) else np.zeros(1, dm.GlobalPoint2D)
+        self.L.orc_SearchAimPoint(_p(cfg), _p(si), _p(d), _p(ref), _p(lane_pool), _p(st))
+        return st["aimpoint_far"][0].copy(), st["aimpoint_near"][0].copy()
 
     def Calculate_aim_dis(self, cfg, loc):
         far, near = np.zeros(1, np.float32), np.zeros(1, np.float32)
