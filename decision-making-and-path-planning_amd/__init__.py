@@ -20,7 +20,7 @@ GEN_LANE_PTS, GEN_REF_PTS = 320, 128
 
 G_FOUND, G_NO_PATH, G_LIMIT, G_OVERFLOW, G_GOAL_BLOCKED, G_PATH_TRUNC, G_INTERNAL, G_COST_RANGE = range(8)
 G_STATUS_COUNT = 8
-K_NAMES = ["k_effective_obstacles", "k_decision", "k_planning", "k_search", "k_score"]
+K_NAMES = ["k_effective_obstacles", "k_decision", "k_planning", "k_search", "k_score", "k_pack_plan", "k_pack_grid"]
 (BUF_SCENE_IN, BUF_LANE_POOL, BUF_REF_POOL, BUF_OBS_POOL, BUF_MOT_POOL, BUF_STATE, BUF_PLAN_OUT, BUF_GRID_OUT,
  BUF_GRID, BUF_PATH, BUF_ORDER, BUF_LANE_ATTR, BUF_OBS_NOW) = range(13)
 
@@ -139,6 +139,16 @@ ScoreTraceInfo = _dt([("n_written", i4), ("state", i4), ("trigger_k", i4), ("tri
 EpisodeSchedule = _dt([("scope", i4), ("fail_mask", i4), ("pass_mask", i4), ("min_samples", i4), ("window", i4), ("floor_w", i4), ("gain", i4),
                        ("target", i4), ("prior", i4), ("_pad", i4)])
 EpisodeScheduleRow = _dt([("n_end", i4, (EPISODE_MAX_STARTS,)), ("n_fail", i4, (EPISODE_MAX_STARTS,))])
+# packed streamed fetch: a tick's results packed on the device into 1744 + 248 B per scene, unpacked on the host
+PACKED_NONE, PACKED_LATTICE, PACKED_PATH, PACKED_BAD = 0, 1, 2, 4          # PackedGrid.kind (DMPP_PACKED_*)
+PackedPlan = _dt([("brakedis", f8), ("brake_speed", f8), ("desacc", f8), ("desspd", f8), ("desstr", f8), ("radius", f8),
+                  ("cnt", i4), ("APA", i4), ("desaccVd", i4), ("desstrVd", i4), ("light", i4), ("road_type", i4), ("sstop", i4),
+                  ("afresh_cause", i4), ("near_ob_dist", f8), ("planspeed", f8), ("planacc", f8), ("trafficlight", i4), ("ob_flag", i4),
+                  ("dec", DecisionOutPod), ("path_points", GlobalPoint2D, (OUT_POINTS,))])
+PackedGrid = _dt([("order_digest", u8), ("status", i4), ("n_expanded", i4), ("n_pushed", i4), ("n_rounds", i4), ("path_len", i4),
+                  ("path_cost", i4), ("start_cell", i4), ("goal_cell", i4), ("best_candidate", i4), ("n_candidates", i4),
+                  ("best_cost", f8), ("best_col", f8), ("best_curv", f8), ("best_prog", f8), ("kind", i4), ("n_steps", i4),
+                  ("geo", f8, (8,)), ("planes", u8, (12,))])
 
 # one scene, one call (pp_tick_io): the pinned block that carries the inputs, the state and the outputs of the latency path
 PP_OK, PP_ERR_ARG, PP_ERR_HIP, PP_ERR_CAPACITY, PP_ERR_STATE = 0, -1, -2, -3, -4
@@ -198,6 +208,9 @@ _FEATURES = [
      {38: EpisodeSchedule, 39: EpisodeScheduleRow}),
     ("pp_set_ego_tracker", {"pp_default_ego_tracker": ([_vp], None), "pp_set_ego_tracker": ([_vp, _vp], _ci),
                             "pp_get_ego_track_state": ([_vp, _vp, _ci], _ci)}, {40: EgoTracker, 41: EgoTrackState}),
+    ("pp_set_packed_fetch", {"pp_set_packed_fetch": ([_vp, _ci], _ci), "pp_fetch_packed_async": ([_vp, _vp, _vp, _pll], _ci),
+                             "pp_unpack_plan": ([_vp, _vp, _ci, _vp, _vp, _vp], _ci), "pp_unpack_grid": ([_vp, _vp, _ci, _vp], _ci)},
+     {43: PackedPlan, 44: PackedGrid}),          # (pp_sizeof id 42 stays unassigned)
 ]
 
 _lib = None
@@ -371,6 +384,30 @@ def episode_schedule_weights(model, row, n_starts):
     w = np.zeros(EPISODE_MAX_STARTS, np.int32)
     _check(load_library().pp_episode_schedule_weights(_ptr(m), _ptr(r), int(n_starts), _ptr(w)))
     return w[:int(n_starts)].copy()
+
+
+def unpack_plan(cfg, packed, result=True, show=True, dec=True):
+    """pp_unpack_plan: (PlanningOut, PlanningStatus, DecisionOutPod) arrays rebuilt from PackedPlan records under the configuration
+    their tick ran with - pure host code, no handle, no device.  An output switched off comes back as None."""
+    pk = np.ascontiguousarray(packed, PackedPlan).reshape(-1)
+    n = len(pk)
+    out = [np.zeros(n, dt) if want else None for dt, want in ((PlanningOut, result), (PlanningStatus, show), (DecisionOutPod, dec))]
+    c = np.array(cfg, PlannerConfig).reshape(1).copy()          # (kept in a local: the call reads it)
+    _check(load_library().pp_unpack_plan(_ptr(c), _ptr(pk), n, *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def unpack_grid(cfg, packed, out=None):
+    """pp_unpack_grid: GridOut records rebuilt from PackedGrid records - pure host code, no handle, no device.  Equal to the device's in
+    every byte except cand_*[k] for k != best_candidate, which are 0.  Raises PlannerError when a record is none a tick packs (that
+    scene's GridOut is left zeroed; `out`, when given, receives the records either way)."""
+    pk = np.ascontiguousarray(packed, PackedGrid).reshape(-1)
+    if out is None:
+        out = np.zeros(len(pk), GridOut)
+    assert out.dtype == GridOut and len(out) >= len(pk)
+    c = np.array(cfg, PlannerConfig).reshape(1).copy()          # (kept in a local: the call reads it)
+    _check(load_library().pp_unpack_grid(_ptr(c), _ptr(pk), len(pk), _ptr(out)))
+    return out
 
 
 def default_score_trace():
@@ -850,6 +887,23 @@ class Planner:
         _check(self.lib.pp_fetch_published_async(self.h, _ptr(result), _ptr(show), _ptr(grid), C.byref(t)))
         return t.value
 
+    def set_packed_fetch(self, on=True):
+        """pp_set_packed_fetch: arm (or disarm) the packed streamed fetch - every later tick packs its results on the device."""
+        _check(self.lib.pp_set_packed_fetch(self.h, int(bool(on))))
+
+    def fetch_packed_async(self, plan=None, grid=None):
+        """pp_fetch_packed_async: PackedPlan / PackedGrid arrays (pinned, self.n records) of the last tick. Returns the tick id;
+        unpack_plan / unpack_grid rebuild what fetch_async would have delivered."""
+        t = C.c_longlong()
+        _check(self.lib.pp_fetch_packed_async(self.h, _ptr(plan), _ptr(grid), C.byref(t)))
+        return t.value
+
+    def unpack_plan(self, packed, **kw):
+        return unpack_plan(self.cfg, packed, **kw)
+
+    def unpack_grid(self, packed, out=None):
+        return unpack_grid(self.cfg, packed, out)
+
     def wait_tick(self, tick_id, allow_poisoned=False):
         """pp_wait_tick: host wait for that tick's downloads. Returns the number of poisoned scenes (raises on any unless allowed)."""
         bad = C.c_int()
@@ -968,7 +1022,8 @@ class Planner:
 
     def kernel_ms(self):
         out = {}
-        for k, name in enumerate(K_NAMES):
+        names = K_NAMES if hasattr(self.lib, "pp_set_packed_fetch") else K_NAMES[:5]      # (an older build named through DMPP_LIB)
+        for k, name in enumerate(names):
             ms, cnt = C.c_float(), C.c_int()
             _check(self.lib.pp_get_kernel_ms(self.h, k, C.byref(ms), C.byref(cnt)))
             out[name] = (ms.value, cnt.value)

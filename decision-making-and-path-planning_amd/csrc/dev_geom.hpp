@@ -60,7 +60,7 @@ __device__ __forceinline__ void wave_first_min(double& v, int& idx)
 // Planning.h:54
 __device__ __forceinline__ int Sgn(double a) { return a > 0 ? 1 : -1; }
 
-__device__ __forceinline__ double CalcDistance(GlobalPoint2D a, GlobalPoint2D b)
+__host__ __device__ __forceinline__ double CalcDistance(GlobalPoint2D a, GlobalPoint2D b)
 {
     double dx = a.x - b.x, dy = a.y - b.y;
     return sqrt(dx * dx + dy * dy);
@@ -134,7 +134,7 @@ __device__ __forceinline__ Bezier bezier_setup(const PlannerConfig& c, GlobalPoi
     b.x2 = e.x - d * cos(th1); b.y2 = e.y - d * sin(th1);
     return b;
 }
-__device__ __forceinline__ GlobalPoint2D bezier_point(const Bezier& b, int i, int n)
+__host__ __device__ __forceinline__ GlobalPoint2D bezier_point(const Bezier& b, int i, int n)
 {
     double t = (n > 1) ? (double)i / (double)(n - 1) : 0.0;
     double u = 1 - t;
@@ -143,6 +143,61 @@ __device__ __forceinline__ GlobalPoint2D bezier_point(const Bezier& b, int i, in
     p.x = b0 * b.x0 + b1 * b.x1 + b2 * b.x2 + b3 * b.x3;
     p.y = b0 * b.y0 + b1 * b.y1 + b2 * b.y2 + b3 * b.y3;
     return p;
+}
+
+// The centre of grid cell `cell` (row-major in a grid W cells wide) in metres: what the scoring pass makes of a path cell, and
+// what the host makes of it again when it unpacks a PackedGrid
+__host__ __device__ __forceinline__ GlobalPoint2D cell_centre(const PlannerConfig& c, GlobalPoint2D org, int cell, int W)
+{
+    const int px = cell % W, py = cell / W;
+    GlobalPoint2D p;
+    p.x = org.x + ((double)px + 0.5) * c.cell;
+    p.y = org.y + ((double)py + 0.5) * c.cell;
+    return p;
+}
+
+// CShare::GlobalToWGS84 (Planning.cpp:205-212): .x = lat, .y = lng.  Planning publishes it; pp_unpack_plan rebuilds result.pnts with it.
+__host__ __device__ __forceinline__ GlobalPoint2D global_to_wgs84(const PlannerConfig& c, GlobalPoint2D p)
+{
+    GlobalPoint2D g;
+    g.x = c.wgs_lat0 + p.y * c.wgs_deg_per_m_lat;
+    g.y = c.wgs_lng0 + p.x * c.wgs_deg_per_m_lng;
+    return g;
+}
+
+// The lattice of the scoring pass: what all candidates share, and candidate k itself.  score_body and k_pack_grid
+// both call these, on the same inputs, so the control points the pack kernel ships are the doubles the scoring pass evaluated.
+// Terminal pose: with a grid path the last cell of its prefix, heading along the baseline from four cells before it (pa0, pa: the
+// centres of the cells a0 = max(a - 4, 0) and a of the prefix); without one the goal, heading from the ego towards it.
+__device__ __forceinline__ double lattice_terminal(const PlannerConfig& c, GlobalPoint3D ego, GlobalPoint2D goal, bool have_path, int a,
+                                                   GlobalPoint2D pa0, GlobalPoint2D pa, GlobalPoint2D& T)
+{
+    double thT;
+    if (have_path) {
+        const int a0 = max(a - 4, 0);
+        T = pa;
+        if (a0 == a) thT = ego.dir;
+        else thT = GetRoadAngle(c, pa0, T);
+    } else {
+        T = goal;
+        GlobalPoint2D e2 = { ego.x, ego.y };
+        thT = GetRoadAngle(c, e2, goal);
+    }
+    return thT;
+}
+// Candidate `k` of `nl`: the cubic Bezier of BezierPlanning(ego -> terminal shifted sideways by its offset) (as bezier_setup);
+// c0, s0 / cs, sn: cosine and sine of the start / terminal heading.
+__device__ __forceinline__ Bezier lattice_bezier(const PlannerConfig& c, GlobalPoint3D ego, GlobalPoint2D T, double c0, double s0,
+                                                 double cs, double sn, int k, int nl)
+{
+    const double off = (double)(k - (nl - 1) / 2) * c.lattice_step;
+    Bezier bz;
+    bz.x0 = ego.x; bz.y0 = ego.y; bz.x3 = T.x + off * sn; bz.y3 = T.y + off * (-cs);
+    const double dx = bz.x3 - bz.x0, dy = bz.y3 - bz.y0;
+    const double d = sqrt(dx * dx + dy * dy) / 3;
+    bz.x1 = bz.x0 + d * c0; bz.y1 = bz.y0 + d * s0;
+    bz.x2 = bz.x3 - d * cs; bz.y2 = bz.y3 - d * sn;
+    return bz;
 }
 
 // CShare::CreateNewPath, one output point (path may be LDS or global)
@@ -161,7 +216,7 @@ __device__ __forceinline__ GlobalPoint2D offset_point(const PlannerConfig& c, co
 
 // CShare::MeanPoints given the cumulative arc length cum[0..n_in) (summed left to right
 // by ONE lane so the rounding matches a sequential host loop).
-__device__ __forceinline__ GlobalPoint2D mean_point(const PlannerConfig& c, const GlobalPoint2D* in, const double* cum,
+__host__ __device__ __forceinline__ GlobalPoint2D mean_point(const PlannerConfig& c, const GlobalPoint2D* in, const double* cum,
                                                     int n_in, int k, int n_out)
 {
     GlobalPoint2D o;
@@ -191,7 +246,7 @@ __device__ __forceinline__ GlobalPoint2D mean_point(const PlannerConfig& c, cons
 // team_search_obstacle - still builds a whole prefix (serial_prefix_inplace).
 
 // in place: v[i] <- v[lo] + ... + v[i] for i in [lo, hi), starting from `acc`; returns the total.  One lane.
-__device__ __forceinline__ double serial_prefix_inplace(double* v, int lo, int hi, double acc)
+__host__ __device__ __forceinline__ double serial_prefix_inplace(double* v, int lo, int hi, double acc)
 {
     int i = lo;
     for (; i + 8 <= hi; i += 8) {

@@ -32,6 +32,7 @@
 #include "kernels_f.hpp"
 #include "kernels_t.hpp"
 #include "kernels_op.hpp"
+#include "kernels_pk.hpp"
 #include "search_budget.hpp"
 #include "rollout_features.hpp"
 
@@ -159,6 +160,13 @@ struct PendingFetch {
     PlanOut* plan_dst; const PlanOut* plan_src; int plan_set; bool plan_issued;
     PlanningOut* res_dst; PlanningStatus* show_dst;      // pp_fetch_published_async: only what the reference publishes (strided copies out of PlanOut)
     GridOut* grid_dst; const GridOut* grid_src; int grid_set; bool grid_issued;
+    // pp_fetch_packed_async: the packed records of the same tick (PackedPlan set plan_set, PackedGrid set of GridOut set grid_set),
+    // behind the same events, on the same two download streams
+    PackedPlan* pkp_dst; const PackedPlan* pkp_src; bool pkp_issued;
+    PackedGrid* pkg_dst; const PackedGrid* pkg_src; bool pkg_issued;
+    bool want_plan() const { return plan_dst || res_dst || show_dst; }
+    bool plan_side_open() const { return (want_plan() && !plan_issued) || (pkp_dst && !pkp_issued); }
+    bool grid_side_open() const { return (grid_dst && !grid_issued) || (pkg_dst && !pkg_issued); }
     hipEvent_t ev_front, ev_tail;      // own references: taken out of the tick's TickRec so that they are not recycled early
     size_t n;
 };
@@ -252,6 +260,16 @@ struct EpisodeLogState {
 struct ScoreTraceState {
     bool on = false, ever = false; ScoreTraceModel tm = {};
     DevBuf<ScoreTick> d_ring; DevBuf<ScoreTraceInfo> d_info;
+};
+// packed streamed fetch (first pp_set_packed_fetch(h, 1)): one PackedPlan set per PlanOut set and one PackedGrid
+// set per GridOut group position (an armed handle is a streamed one: groups of 1, tick slot 0 only), each written by its tick's pack
+// kernel in stream order behind the kernel that wrote the PlanOut / GridOut set of the same index - so a set is rewritten only
+// behind its last download, by the waits that already guard those (fetched_plan / fetched_grid).  No rollout feature: no set call
+// retires it, and the sets hold caps.max_scenes records, so nothing that changes the resident scenes re-allocates.  plan_tick /
+// grid_tick: the last tick whose k_pack_plan / k_pack_grid was launched (what pp_fetch_packed_async may name)
+struct PackedState {
+    bool on = false; long long plan_tick = 0, grid_tick = 0;
+    DevBuf<PackedPlan> d_plan[kPlan]; DevBuf<PackedGrid> d_grid[kGoutRing];
 };
 
 }  // namespace
@@ -348,6 +366,7 @@ struct pp_planner {
     TrafficResetState treset;
     EpisodeLogState elog;
     ScoreTraceState strace;
+    PackedState packed;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
     GridFollow grid_follow = { 0, 0 };
@@ -511,27 +530,33 @@ int build_follow(pp_planner* h)
 int pump_fetches(pp_planner* h, long long force_tick = -1, int force_plan_set = -1, int force_grid_set = -1)
 {
     for (PendingFetch& f : h->fetches) {
-        if ((f.plan_dst || f.res_dst || f.show_dst) && !f.plan_issued) {
+        if (f.plan_side_open()) {
             const bool ready = hipEventQuery(f.ev_front) == hipSuccess;
             if (ready || f.tick == force_tick || f.plan_set == force_plan_set) {
                 (void)hipGetLastError();
                 if (!ready) HIP_TRY(hipStreamWaitEvent(h->stream_dp, f.ev_front, 0));
-                if (f.plan_dst) HIP_TRY(hipMemcpyAsync(f.plan_dst, f.plan_src, f.n * sizeof(PlanOut), hipMemcpyDefault, h->stream_dp));
-                const char* base = reinterpret_cast<const char*>(f.plan_src);
-                if (f.res_dst) HIP_TRY(hipMemcpy2DAsync(f.res_dst, sizeof(PlanningOut), base + offsetof(PlanOut, result), sizeof(PlanOut), sizeof(PlanningOut), f.n, hipMemcpyDefault, h->stream_dp));
-                if (f.show_dst) HIP_TRY(hipMemcpy2DAsync(f.show_dst, sizeof(PlanningStatus), base + offsetof(PlanOut, show), sizeof(PlanOut), sizeof(PlanningStatus), f.n, hipMemcpyDefault, h->stream_dp));
+                if (f.pkp_dst && !f.pkp_issued) HIP_TRY(hipMemcpyAsync(f.pkp_dst, f.pkp_src, f.n * sizeof(PackedPlan), hipMemcpyDefault, h->stream_dp));
+                f.pkp_issued = true;
+                if (f.want_plan() && !f.plan_issued) {
+                    if (f.plan_dst) HIP_TRY(hipMemcpyAsync(f.plan_dst, f.plan_src, f.n * sizeof(PlanOut), hipMemcpyDefault, h->stream_dp));
+                    const char* base = reinterpret_cast<const char*>(f.plan_src);
+                    if (f.res_dst) HIP_TRY(hipMemcpy2DAsync(f.res_dst, sizeof(PlanningOut), base + offsetof(PlanOut, result), sizeof(PlanOut), sizeof(PlanningOut), f.n, hipMemcpyDefault, h->stream_dp));
+                    if (f.show_dst) HIP_TRY(hipMemcpy2DAsync(f.show_dst, sizeof(PlanningStatus), base + offsetof(PlanOut, show), sizeof(PlanOut), sizeof(PlanningStatus), f.n, hipMemcpyDefault, h->stream_dp));
+                }
                 PP_TRY(h->fetched_plan[f.plan_set].record(h->stream_dp));
                 PP_TRY(h->done_p[f.slot].record(h->stream_dp));
                 f.plan_issued = true;
             }
         }
-        if (f.grid_dst && !f.grid_issued) {
+        if (f.grid_side_open()) {
             hipEvent_t dep = f.ev_tail ? f.ev_tail : f.ev_front;
             const bool ready = hipEventQuery(dep) == hipSuccess;
             if (ready || f.tick == force_tick || f.grid_set == force_grid_set) {
                 (void)hipGetLastError();
                 if (!ready) HIP_TRY(hipStreamWaitEvent(h->stream_dg, dep, 0));
-                HIP_TRY(hipMemcpyAsync(f.grid_dst, f.grid_src, f.n * sizeof(GridOut), hipMemcpyDefault, h->stream_dg));
+                if (f.pkg_dst && !f.pkg_issued) HIP_TRY(hipMemcpyAsync(f.pkg_dst, f.pkg_src, f.n * sizeof(PackedGrid), hipMemcpyDefault, h->stream_dg));
+                f.pkg_issued = true;
+                if (f.grid_dst && !f.grid_issued) HIP_TRY(hipMemcpyAsync(f.grid_dst, f.grid_src, f.n * sizeof(GridOut), hipMemcpyDefault, h->stream_dg));
                 PP_TRY(h->fetched_grid[f.grid_set].record(h->stream_dg));
                 PP_TRY(h->done_g[f.slot].record(h->stream_dg));
                 f.grid_issued = true;
@@ -540,8 +565,7 @@ int pump_fetches(pp_planner* h, long long force_tick = -1, int force_plan_set = 
     }
     (void)hipGetLastError();                  // hipErrorNotReady is not an error here
     size_t k = 0;                             // completed requests leave from the front (prune_inflight looks at the first one left)
-    while (k < h->fetches.size() && ((!h->fetches[k].plan_dst && !h->fetches[k].res_dst && !h->fetches[k].show_dst) || h->fetches[k].plan_issued) &&
-           (!h->fetches[k].grid_dst || h->fetches[k].grid_issued)) k++;
+    while (k < h->fetches.size() && !h->fetches[k].plan_side_open() && !h->fetches[k].grid_side_open()) k++;
     h->fetches.erase(h->fetches.begin(), h->fetches.begin() + (long)k);
     return PP_OK;
 }
@@ -1196,7 +1220,12 @@ int flush_group(pp_planner* h)
                            n, std::min(c.n_lattice, DMPP_MAX_LATTICE - 1), h->d_gout[h->grp_gs[G - 1]], h->score.d_grid[p]);
         h->score.grp_scored = false;
     }
-    for (int i = 0; i < G; i++) {                    // the group's scoring pass is the last reader of its G snapshot sets
+    if (h->packed.on && h->packed.d_grid[0]) {             // packed fetch, grid half: behind the tick's k_score in stream order, in front of scored[] / the tick's ev_tail (an armed handle runs groups of 1)
+        Timed t(h, PP_K_PACK_GRID, ss);
+        hipLaunchKernelGGL(dmpp::k_pack_grid, dim3((unsigned)((n + dmpp::kPkGridWaves - 1) / dmpp::kPkGridWaves)), dim3(dmpp::kPkGridWaves * DMPP_WAVE), 0, ss,
+                           c, n, tg, G - 1, h->packed.d_grid[h->grp_gs[G - 1] / kGroupMax].get());
+    }
+    for (int i = 0; i < G; i++) {                 // the group's scoring pass is the last reader of its G snapshot sets
         if (piped) PP_TRY(h->scored[h->grp_set[i]].record(ss));
         else h->scored[h->grp_set[i]].forget();
     }
@@ -1309,6 +1338,16 @@ int pp_plan_tick(pp_handle h)
         Timed t(h, PP_K_PLANNING, sr);
         hipLaunchKernelGGL(dmpp::k_planning, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::PlanShared), sr, c, n, h->d_in, h->d_lane,
                            h->d_ref, h->d_dec_ref, obs_now, h->d_state, h->d_plan);
+    }
+    if (h->packed.on) {          // packed fetch, plan half: behind the Planning kernel in stream order, in front of `join` and the tick's ev_front
+        {
+            Timed t(h, PP_K_PACK_PLAN, sr);
+            const long long chunks = (long long)n * dmpp::kPkPlanChunks;
+            hipLaunchKernelGGL(dmpp::k_pack_plan, dim3((unsigned)((chunks + dmpp::kPkBlock - 1) / dmpp::kPkBlock)), dim3(dmpp::kPkBlock), 0, sr,
+                               n, h->d_plan, h->packed.d_plan[h->plan_cur].get());
+        }
+        h->packed.plan_tick = h->tick_seq + 1;
+        if (c.grid_stage) h->packed.grid_tick = h->tick_seq + 1;      // (its group - of 1 - is launched below)
     }
     if (sr != h->stream) { PP_TRY(h->join.record(sr)); h->front_unjoined = piped; }
     h->obs_set = po;
@@ -2483,12 +2522,18 @@ int pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap)
     return sl[1];
 }
 
-static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id)
+static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id,
+                       PackedPlan* pk_plan = nullptr, PackedGrid* pk_grid = nullptr)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    if (!plan && !grid && !result && !show) return fail(PP_ERR_ARG, "nothing to fetch");
+    if (!plan && !grid && !result && !show && !pk_plan && !pk_grid) return fail(PP_ERR_ARG, "nothing to fetch");
     if (h->tick_seq == 0 || h->n_scenes <= 0) return fail(PP_ERR_STATE, "pp_fetch_async: no tick has been enqueued");
-    if (grid && !h->cfg.grid_stage) return fail(PP_ERR_STATE, "pp_fetch_async: the last tick ran without the grid stage");
+    if ((grid || pk_grid) && !h->cfg.grid_stage) return fail(PP_ERR_STATE, "pp_fetch_async: the last tick ran without the grid stage");
+    if (pk_plan || pk_grid) {
+        if (!h->packed.on) return fail(PP_ERR_STATE, "pp_fetch_packed_async: the packed fetch is not armed (pp_set_packed_fetch)");
+        if (h->packed.plan_tick != h->tick_seq || (pk_grid && h->packed.grid_tick != h->tick_seq))
+            return fail(PP_ERR_STATE, "pp_fetch_packed_async: the last tick ran before the packed fetch was armed");
+    }
     HIP_TRY(hipSetDevice(h->device));
     { int r = flush_group(h); if (r) return r; }          // the downloads follow the last tick's scoring pass: it must be enqueued
     { int r = ensure_streaming(h); if (r) return r; }
@@ -2510,13 +2555,22 @@ static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, Planning
     f.tick = T; f.slot = slot; f.n = (size_t)n; f.ev_front = R.ev_front; f.ev_tail = R.ev_tail;
     if (want_plan) { f.plan_dst = plan; f.res_dst = result; f.show_dst = show; f.plan_src = h->d_plan; f.plan_set = h->plan_cur; }
     if (grid) { f.grid_dst = grid; f.grid_src = h->d_gout[h->gout_set]; f.grid_set = h->gout_set; }
-    // a second request for the same tick (PlanOut and GridOut asked for separately) joins the first
-    bool joined = false;
+    if (pk_plan) { f.pkp_dst = pk_plan; f.pkp_src = h->packed.d_plan[h->plan_cur]; f.plan_set = h->plan_cur; }
+    if (pk_grid) { f.pkg_dst = pk_grid; f.pkg_src = h->packed.d_grid[h->gout_set / kGroupMax]; f.grid_set = h->gout_set; }
+    // a second request for the same tick (PlanOut and GridOut asked for separately; a packed request beside a full or published
+    // one) joins the first: the sets of a tick are the same whoever names them.  Each of the request's four parts joins the first
+    // pending entry of the tick that has that part free and leaves f; whatever found no room stays in f and becomes an entry of
+    // its own, so no destination a call accepted is ever dropped.
     for (PendingFetch& g : h->fetches) if (g.tick == T) {
-        if (want_plan && !g.plan_dst && !g.res_dst && !g.show_dst) { g.plan_dst = f.plan_dst; g.res_dst = f.res_dst; g.show_dst = f.show_dst; g.plan_src = f.plan_src; g.plan_set = f.plan_set; g.plan_issued = false; joined = true; }
-        if (grid && !g.grid_dst) { g.grid_dst = f.grid_dst; g.grid_src = f.grid_src; g.grid_set = f.grid_set; g.grid_issued = false; joined = true; }
+        if (f.want_plan() && !g.want_plan()) {
+            g.plan_dst = f.plan_dst; g.res_dst = f.res_dst; g.show_dst = f.show_dst; g.plan_src = f.plan_src; g.plan_set = f.plan_set; g.plan_issued = false;
+            f.plan_dst = nullptr; f.res_dst = nullptr; f.show_dst = nullptr;
+        }
+        if (f.grid_dst && !g.grid_dst) { g.grid_dst = f.grid_dst; g.grid_src = f.grid_src; g.grid_set = f.grid_set; g.grid_issued = false; f.grid_dst = nullptr; }
+        if (f.pkp_dst && !g.pkp_dst) { g.pkp_dst = f.pkp_dst; g.pkp_src = f.pkp_src; g.plan_set = f.plan_set; g.pkp_issued = false; f.pkp_dst = nullptr; }
+        if (f.pkg_dst && !g.pkg_dst) { g.pkg_dst = f.pkg_dst; g.pkg_src = f.pkg_src; g.grid_set = f.grid_set; g.pkg_issued = false; f.pkg_dst = nullptr; }
     }
-    if (!joined) h->fetches.push_back(f);
+    if (f.want_plan() || f.grid_dst || f.pkp_dst || f.pkg_dst) h->fetches.push_back(f);
     { int r = pump_fetches(h); if (r) return r; }
     if (tick_id) *tick_id = T;
     return PP_OK;
@@ -2525,6 +2579,44 @@ static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, Planning
 int pp_fetch_async(pp_handle h, PlanOut* plan, GridOut* grid, long long* tick_id) { return fetch_async(h, plan, nullptr, nullptr, grid, tick_id); }
 int pp_fetch_published_async(pp_handle h, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id)
 { return fetch_async(h, nullptr, result, show, grid, tick_id); }
+
+
+// ---------------------------------------------------------------------------------------
+// Packed streamed fetch
+int pp_set_packed_fetch(pp_handle h, int on)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!on) { h->packed.on = false; return PP_OK; }          // the sets stay; a pending download of an earlier tick still reads them
+    if (h->packed.on) return PP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(flush_group(h));                                   // the ticks before arming are launched as they stand, unpacked
+    PP_TRY(ensure_streaming(h));
+    const size_t ns = (size_t)h->caps.max_scenes;
+    for (int q = 0; q < kPlan; q++) PP_TRY(h->packed.d_plan[q].reserve(ns));
+    if (h->d_grid) for (int q = 0; q < kGoutRing; q++) PP_TRY(h->packed.d_grid[q].reserve(ns));      // (a handle created with the grid stage)
+    h->packed.on = true;
+    return PP_OK;
+}
+int pp_fetch_packed_async(pp_handle h, PackedPlan* plan, PackedGrid* grid, long long* tick_id)
+{
+    if (h && !plan && !grid) return fail(PP_ERR_ARG, "pp_fetch_packed_async: nothing to fetch");
+    return fetch_async(h, nullptr, nullptr, nullptr, nullptr, tick_id, plan, grid);
+}
+int pp_unpack_plan(const PlannerConfig* cfg, const PackedPlan* in, int n, PlanningOut* result, PlanningStatus* show, DecisionOutPod* dec)
+{
+    if (!cfg || !in || n < 0) return fail(PP_ERR_ARG, "pp_unpack_plan: null argument or negative count");
+    for (int s = 0; s < n; s++) dmpp::unpack_plan_one(*cfg, in[s], result ? result + s : nullptr, show ? show + s : nullptr, dec ? dec + s : nullptr);
+    return PP_OK;
+}
+int pp_unpack_grid(const PlannerConfig* cfg, const PackedGrid* in, int n, GridOut* out)
+{
+    if (!cfg || !in || !out || n < 0) return fail(PP_ERR_ARG, "pp_unpack_grid: null argument or negative count");
+    int bad = 0, first = -1;
+    for (int s = 0; s < n; s++) if (!dmpp::unpack_grid_one(*cfg, in[s], out + s)) { if (bad++ == 0) first = s; }
+    if (bad) return fail(PP_ERR_ARG, "pp_unpack_grid: " + std::to_string(bad) + " record(s) no tick packs (first: scene " + std::to_string(first) +
+                                     "): n_steps outside 0 .. 199, an unknown kind or DMPP_PACKED_BAD, best_candidate outside 0 .. 16, or a walk that leaves the grid; their GridOut is zeroed");
+    return PP_OK;
+}
 
 long long pp_tick_id(pp_handle h) { return h ? h->tick_seq : -1; }
 
@@ -2842,6 +2934,7 @@ size_t pp_sizeof(int which)
     case 35: return sizeof(ScoreTraceModel); case 36: return sizeof(ScoreTick); case 37: return sizeof(ScoreTraceInfo);
     case 38: return sizeof(EpisodeSchedule); case 39: return sizeof(EpisodeScheduleRow);
     case 40: return sizeof(EgoTracker); case 41: return sizeof(EgoTrackState);
+    case 43: return sizeof(PackedPlan); case 44: return sizeof(PackedGrid);      // (42 stays unassigned)
     default: return 0;
     }
 }

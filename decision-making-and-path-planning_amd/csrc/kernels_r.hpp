@@ -1081,10 +1081,7 @@ k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const 
         if ((tid & 1) == 0) {
             const int k = tid >> 1;
             po.show.path_points[k] = p;                                     // Planning.cpp:180-183
-            GlobalPoint2D g;                                                // GlobalToWGS84, Planning.cpp:205-212
-            g.x = c.wgs_lat0 + p.y * c.wgs_deg_per_m_lat;
-            g.y = c.wgs_lng0 + p.x * c.wgs_deg_per_m_lng;
-            po.result.pnts[k] = g;
+            po.result.pnts[k] = global_to_wgs84(c, p);                      // GlobalToWGS84, Planning.cpp:205-212
         }
     }
     FRONT_MARK(5)

@@ -119,8 +119,7 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
         int cx0 = 0x7fffffff, cx1 = -1, cy0 = 0x7fffffff, cy1 = -1;
         if (tid <= a) {                    // (a < path_len <= max_path: the cell was read)
             const int px = pc_mine % W, py = pc_mine / W;
-            sh.pts[tid].x = org.x + ((double)px + 0.5) * c.cell;
-            sh.pts[tid].y = org.y + ((double)py + 0.5) * c.cell;
+            sh.pts[tid] = cell_centre(c, org, pc_mine, W);
             cx0 = px; cx1 = px; cy0 = py; cy1 = py;
         }
         if (wave < kBoxWaves) {            // DMPP_PATH_POINTS <= 256 points: only the first four waves hold any
@@ -140,19 +139,10 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
     // start heading, lane 1 the terminal one, so one pass through sincos yields all four values) - and then the lattice.
     if (have_path && wave == 0) wave_cumlen(sh.pts, a + 1, sh.cum, lane);
     if (wave == NW - 1) {
-        GlobalPoint2D T; double thT;
-        if (have_path) {
-            // the terminal is the prefix's last cell and the baseline starts four cells before it: sh.pts holds both, by the
-            // expressions that would convert the cells here
-            const int a0 = max(a - 4, 0);
-            T = sh.pts[a];
-            if (a0 == a) thT = ego.dir;
-            else thT = GetRoadAngle(c, sh.pts[a0], T);
-        } else {
-            T = goal;
-            GlobalPoint2D e2 = { ego.x, ego.y };
-            thT = GetRoadAngle(c, e2, goal);
-        }
+        // the terminal is the prefix's last cell and the baseline starts four cells before it: sh.pts holds both, by the
+        // expressions that would convert the cells here (lattice_terminal, shared with k_pack_grid)
+        GlobalPoint2D T;
+        const double thT = lattice_terminal(c, ego, goal, have_path, a, sh.pts[max(a - 4, 0)], sh.pts[a], T);
         const double ang = (lane == 0 ? ego.dir : thT) * c.PI / 180;
         double sv, cv;
         sincos(ang, &sv, &cv);
@@ -165,14 +155,7 @@ __device__ __forceinline__ void score_body(const PlannerConfig& c, const SceneIn
         double X0 = __builtin_inf(), X1 = -__builtin_inf(), Y0 = __builtin_inf(), Y1 = -__builtin_inf();
         if (lane < nl) {
             const double c0 = sh.trig[0], s0 = sh.trig[1], cs = sh.trig[2], sn = sh.trig[3];
-            const GlobalPoint2D T = sh.T;
-            const double off = (double)(lane - (nl - 1) / 2) * c.lattice_step;
-            Bezier bz;
-            bz.x0 = ego.x; bz.y0 = ego.y; bz.x3 = T.x + off * sn; bz.y3 = T.y + off * (-cs);
-            const double dx = bz.x3 - bz.x0, dy = bz.y3 - bz.y0;
-            const double d = sqrt(dx * dx + dy * dy) / 3;
-            bz.x1 = bz.x0 + d * c0; bz.y1 = bz.y0 + d * s0;
-            bz.x2 = bz.x3 - d * cs; bz.y2 = bz.y3 - d * sn;
+            const Bezier bz = lattice_bezier(c, ego, sh.T, c0, s0, cs, sn, lane, nl);
             sh.bz[lane] = bz;
             X0 = fmin(fmin(bz.x0, bz.x1), fmin(bz.x2, bz.x3)); X1 = fmax(fmax(bz.x0, bz.x1), fmax(bz.x2, bz.x3));
             Y0 = fmin(fmin(bz.y0, bz.y1), fmin(bz.y2, bz.y3)); Y1 = fmax(fmax(bz.y0, bz.y1), fmax(bz.y2, bz.y3));

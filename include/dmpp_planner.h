@@ -45,8 +45,9 @@ typedef struct PlannerCaps {
     int32_t _pad;
 } PlannerCaps;
 
-/* kernels of one tick, in launch order; index into pp_get_kernel_ms */
-enum { PP_K_OBSTACLES = 0, PP_K_DECISION, PP_K_PLANNING, PP_K_SEARCH, PP_K_SCORE, PP_K_COUNT };
+/* kernels of one tick, in launch order; index into pp_get_kernel_ms.  PP_K_PACK_PLAN / PP_K_PACK_GRID: the two pack kernels of
+ * the packed streamed fetch (launched only while pp_set_packed_fetch is on) */
+enum { PP_K_OBSTACLES = 0, PP_K_DECISION, PP_K_PLANNING, PP_K_SEARCH, PP_K_SCORE, PP_K_PACK_PLAN, PP_K_PACK_GRID, PP_K_COUNT };
 /* device buffers addressable through pp_device_ptr (for RCCL scatter/gather by the caller); PP_BUF_OBS_NOW: the last tick's
  * obstacle snapshot (max_obs_total records, only the slots some scene's slice covers are written) */
 enum { PP_BUF_SCENE_IN = 0, PP_BUF_LANE_POOL, PP_BUF_REF_POOL, PP_BUF_OBS_POOL, PP_BUF_MOT_POOL, PP_BUF_STATE,
@@ -160,6 +161,28 @@ int  pp_fetch_async(pp_handle h, PlanOut* plan, GridOut* grid, long long* tick_i
  * PlanningStatus (SetPlanningStatus, Planning.cpp:186) of every scene, as two contiguous arrays (strided copies out of the
  * PlanOut records: 3.3 of their 6.9 KB) - and / or GridOut.  Any of the three may be NULL. */
 int  pp_fetch_published_async(pp_handle h, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id);
+/* ---- packed streamed fetch ----------------------------------------------------------------------------------
+ * pp_set_packed_fetch(h, 1) arms the handle: it becomes a streamed one (ticks in groups of 1, as after the first pp_fetch_async),
+ * allocates one PackedPlan set per PlanOut set and one PackedGrid set per GridOut group position, and from the next tick on every
+ * pp_plan_tick launches k_pack_plan behind its Planning kernel and - with the grid stage on - k_pack_grid behind its scoring pass,
+ * in stream order (no event, no wait).  pp_set_packed_fetch(h, 0) disarms: the sets stay allocated, nothing more is launched.  It is no
+ * rollout feature: no set call retires it, and it survives pp_set_scenes / pp_set_egos / pp_set_n_scenes / pp_set_config.  A handle
+ * that never arms allocates and launches nothing.
+ * pp_fetch_packed_async downloads the packed records of the LAST enqueued tick (either pointer may be NULL): 1744 + 248 B per scene
+ * in the place of the 6896 + 3792 B of pp_fetch_async.  Same ordering rules, same pp_wait_tick; a request joins a pp_fetch_async /
+ * pp_fetch_published_async of the same tick (part by part; a part that finds no room in a pending request is queued by itself: every
+ * destination a call accepted is filled).  PP_ERR_STATE: not armed; the last tick ran before arming; `grid` with the grid stage
+ * off.  PP_ERR_ARG: both pointers NULL.
+ * pp_unpack_plan / pp_unpack_grid: pure host code, no handle, no device, built from the kernels' own functions - they rebuild
+ * PlanningOut (pnts through the WGS84 line of cfg), PlanningStatus, DecisionOutPod (each output may be NULL) and GridOut, equal in
+ * every byte to what pp_fetch_async of the same tick delivers, except GridOut.cand_*[k] for k != best_candidate, which are 0.
+ * cfg: the configuration the tick ran with.  A hostile record - n_steps outside 0 .. 199, an unknown kind, DMPP_PACKED_BAD, a
+ * best_candidate outside 0 .. 16, a walk that leaves grid_w x grid_h - leaves that scene's GridOut zeroed; the call goes on with the
+ * other scenes and returns PP_ERR_ARG.  Neither reads or writes outside its arrays, whatever a record holds. */
+int  pp_set_packed_fetch(pp_handle h, int on);
+int  pp_fetch_packed_async(pp_handle h, PackedPlan* plan, PackedGrid* grid, long long* tick_id);
+int  pp_unpack_plan(const PlannerConfig* cfg, const PackedPlan* in, int n, PlanningOut* result, PlanningStatus* show, DecisionOutPod* dec);
+int  pp_unpack_grid(const PlannerConfig* cfg, const PackedGrid* in, int n, GridOut* out);
 /* Host wait for the downloads of one tick (at most 32 ticks back).  *n_poisoned (may be NULL): scenes of that tick's update
  * that were poisoned; PP_ERR_ARG when there were any (the other scenes' results are valid), PP_OK otherwise. */
 int  pp_wait_tick(pp_handle h, long long tick_id, int* n_poisoned);

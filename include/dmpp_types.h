@@ -255,6 +255,35 @@ typedef struct PlanOut {
     int32_t        navi_lanechg_times;       /* CalcNaviLaneChgTimes, Decision.cpp:498-538 */
 } PlanOut;
 
+/* ---- packed streamed fetch (build-defined) --------------------------------------------------------
+ * pp_set_packed_fetch makes every tick pack its results on the device into one PackedPlan (and, with the grid stage, one
+ * PackedGrid) per scene; pp_fetch_packed_async downloads those, and pp_unpack_plan / pp_unpack_grid - pure host code - rebuild
+ * PlanningOut, PlanningStatus, DecisionOutPod and GridOut from them, byte for byte.  Every byte of both records is specified. */
+typedef struct PackedPlan {
+    double  brakedis, brake_speed, desacc, desspd, desstr, radius;     /* PlanOut.result, its six doubles ...              */
+    int32_t cnt, APA, desaccVd, desstrVd, light, road_type, sstop;     /* ... and its seven ints                           */
+    int32_t afresh_cause;             /* PlanOut.show.afresh_cause, in the place of result._pad (always 0 on the device)  */
+    double  near_ob_dist, planspeed, planacc;                          /* PlanOut.show                                     */
+    int32_t trafficlight;             /* PlanOut.show.trafficlight                                                         */
+    int32_t ob_flag;                  /* PlanOut.ob_flag                                                                   */
+    DecisionOutPod dec;               /* PlanOut.dec                                                                       */
+    GlobalPoint2D path_points[DMPP_OUT_POINTS];   /* PlanOut.show.path_points; result.pnts is their WGS84 image (unpacker) */
+} PackedPlan;                                                               /* 1744 B */
+
+#define DMPP_PACKED_NONE    0   /* PackedGrid.kind: no candidate, best_path is zeros                                      */
+#define DMPP_PACKED_LATTICE 1   /* a lattice candidate won: geo = its four control points                                 */
+#define DMPP_PACKED_PATH    2   /* the grid-path candidate won: geo[0..1] = grid origin, planes = the steps of the prefix  */
+#define DMPP_PACKED_BAD     4   /* bit 2 of kind: the path cells were no chain of neighbours from start_cell (never expected) */
+typedef struct PackedGrid {
+    uint64_t order_digest;            /* the first 48 B of GridOut as they stand ...                                       */
+    int32_t  status, n_expanded, n_pushed, n_rounds, path_len, path_cost, start_cell, goal_cell, best_candidate, n_candidates;
+    double   best_cost, best_col, best_curv, best_prog;   /* cand_*[best_candidate]; 0 when n_candidates == 0              */
+    int32_t  kind;                    /* DMPP_PACKED_NONE / LATTICE / PATH, | DMPP_PACKED_BAD                              */
+    int32_t  n_steps;                 /* kind PATH: min(path_len - 1, lookahead_cells, 199); otherwise 0                   */
+    double   geo[8];                  /* LATTICE: x0 y0 x1 y1 x2 y2 x3 y3; PATH: grid_origin.x, .y, then 0; NONE: 0        */
+    uint64_t planes[12];              /* PATH: bit i & 63 of planes[3 (i >> 6) + b] = bit b of the direction of step i     */
+} PackedGrid;                                                               /* 248 B */
+
 /* ---- rollout scorecard (build-defined) ------------------------------------------------------
  * One record per scene, folded on the device over the ticks scored between pp_score_begin and pp_score_end, in tick
  * order.  Tick indices are 0-based counts of scored ticks; obstacle indices count within the scene's slice.  Every field is

@@ -45,6 +45,48 @@ ress = [dm.pinned_empty(n, dm.PlanningOut) for _ in range(depth)]
 shows = [dm.pinned_empty(n, dm.PlanningStatus) for _ in range(depth)]
 plans = [dm.pinned_empty(n, dm.PlanOut) for _ in range(depth)]
 grids = [dm.pinned_empty(n, dm.GridOut) for _ in range(depth)]
+PACKED = bool(os.environ.get("PACKED"))  # the packed records (PackedPlan + PackedGrid, pp_fetch_packed_async), unpacked on the host after each wait
+if PACKED:
+    pl.set_packed_fetch(True)
+    # (with worker threads twice the buffers, and outputs of their own: a tick is unpacked while the next `depth` ticks are fetched)
+    NB = depth * (2 if int(os.environ.get("UNPACK_THREADS", "0")) else 1)
+    pkps = [dm.pinned_empty(n, dm.PackedPlan) for _ in range(NB)]
+    pkgs = [dm.pinned_empty(n, dm.PackedGrid) for _ in range(NB)]
+    un_plans = [[np.zeros(n, dt) for dt in (dm.PlanningOut, dm.PlanningStatus, dm.DecisionOutPod)] for _ in range(NB)]
+    un_grids = [np.zeros(n, dm.GridOut) for _ in range(NB)]
+    UNPACK = not os.environ.get("NO_UNPACK")
+print("bytes down per tick: full %d, published %d, packed %d" % (n * (dm.PlanOut.itemsize + dm.GridOut.itemsize),
+      n * (dm.PlanningOut.itemsize + dm.PlanningStatus.itemsize + dm.GridOut.itemsize), n * (dm.PackedPlan.itemsize + dm.PackedGrid.itemsize)), flush=True)
+
+
+# UNPACK_THREADS=k: the unpackers run on k worker threads, scenes lo .. hi each (they are pure functions of (cfg, record), and
+# ctypes releases the interpreter lock for the call), beside the enqueueing thread; a slot's workers are waited for before the
+# slot is fetched into again.  Default 0: on the enqueueing thread, between the wait and the next update.
+THREADS = int(os.environ.get("UNPACK_THREADS", "0"))
+if PACKED and THREADS:
+    from concurrent.futures import ThreadPoolExecutor
+    workers, unpacking = ThreadPoolExecutor(THREADS), {}
+
+
+def unpack_part(slot, lo, hi, dp, dg):
+    if dp:
+        dm._check(pl.lib.pp_unpack_plan(pl.cfg.ctypes.data, pkps[slot][lo:hi].ctypes.data, hi - lo, *[a[lo:hi].ctypes.data for a in un_plans[slot]]))
+    if dg:
+        dm._check(pl.lib.pp_unpack_grid(pl.cfg.ctypes.data, pkgs[slot][lo:hi].ctypes.data, hi - lo, un_grids[slot][lo:hi].ctypes.data))
+
+
+def unpack(slot, dp, dg):
+    if not THREADS:
+        return unpack_part(slot, 0, n, dp, dg)
+    cuts = [n * k // THREADS for k in range(THREADS + 1)]
+    unpacking[slot] = [workers.submit(unpack_part, slot, cuts[k], cuts[k + 1], dp, dg) for k in range(THREADS)]
+
+
+def settle(slot=None):
+    if PACKED and THREADS:
+        for s in ([slot] if slot is not None else list(unpacking)):
+            for f in unpacking.pop(s, []):
+                f.result()
 
 
 def run(k_steps, up, dp, dg, acc=None):
@@ -53,6 +95,8 @@ def run(k_steps, up, dp, dg, acc=None):
         if len(ids) == depth:
             a0 = time.perf_counter()
             pl.wait_tick(ids.pop(0))
+            if PACKED and UNPACK and (dp or dg):
+                unpack((t - depth) % NB, dp, dg)
             if acc is not None:
                 acc["wait"] += time.perf_counter() - a0
         a0 = time.perf_counter()
@@ -62,7 +106,10 @@ def run(k_steps, up, dp, dg, acc=None):
         pl.tick()
         a2 = time.perf_counter()
         if dp or dg:
-            if WIRE:
+            if PACKED:
+                settle(t % NB)
+                ids.append(pl.fetch_packed_async(pkps[t % NB] if dp else None, pkgs[t % NB] if dg else None))
+            elif WIRE:
                 ids.append(pl.fetch_published_async(ress[t % depth] if dp else None, shows[t % depth] if dp else None, grids[t % depth] if dg else None))
             else:
                 ids.append(pl.fetch_async(plans[t % depth] if dp else None, grids[t % depth] if dg else None))
@@ -71,8 +118,11 @@ def run(k_steps, up, dp, dg, acc=None):
             acc["update"] += a1 - a0
             acc["tick"] += a2 - a1
             acc["fetch"] += a3 - a2
-    for i in ids:
+    for j, i in enumerate(ids):
         pl.wait_tick(i)
+        if PACKED and UNPACK and (dp or dg):
+            unpack((k_steps - len(ids) + j) % NB, dp, dg)
+    settle()
 
 
 CASES = (("plain ticks", (0, 0, 0)), ("upload only", (1, 0, 0)), ("PlanOut down only", (0, 1, 0)), ("GridOut down only", (0, 0, 1)),
@@ -97,7 +147,7 @@ for name, (up, dp, dg) in CASES:
         pl.reset_kernel_ms()
         run(steps, up, dp, dg)
         pl.sync()
-        print("      kernels us:", " ".join("%s=%.0f" % (k.replace("k_", ""), v[0] / max(v[1], 1) * 1e3) for k, v in pl.kernel_ms().items()), flush=True)
+        print("      kernels us:", " ".join("%s=%.0f" % (k[2:], v[0] / max(v[1], 1) * 1e3) for k, v in pl.kernel_ms().items()), flush=True)
         pl.set_profile(0)
 
 if os.environ.get("NO_RAW"):
