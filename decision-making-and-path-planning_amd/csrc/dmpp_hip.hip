@@ -146,6 +146,7 @@ struct InputSet {
     DevBuf<SceneIn> d_in; DevBuf<ObPoint> d_obs; DevBuf<ObMotion> d_mot;
     bool have_motion = false; int n_obs_total = 0;
     SyncPoint up;                                     // behind the kernels that staged the set (upload stream)
+    ObMotion* mot() const { return have_motion ? d_mot.get() : nullptr; }      // the velocities, if the set carries any
 };
 // one tick in flight: which input set it reads, and the events that close its front chain and its last kernel
 struct TickRec { long long tick; int in_set; hipEvent_t ev_front, ev_tail; };
@@ -155,21 +156,35 @@ struct TickRec { long long tick; int in_set; hipEvent_t ev_front, ev_tail; };
 // streams that share that queue - there are more HIP streams here than hardware queues - stall behind it (measured: the
 // front chain's kernels took 2 - 6 times as long with the GridOut copy of each tick enqueued three ticks ahead of its
 // scoring pass).
-struct PendingFetch {
-    long long tick; int slot;
-    PlanOut* plan_dst; const PlanOut* plan_src; int plan_set; bool plan_issued;
-    PlanningOut* res_dst; PlanningStatus* show_dst;      // pp_fetch_published_async: only what the reference publishes (strided copies out of PlanOut)
-    GridOut* grid_dst; const GridOut* grid_src; int grid_set; bool grid_issued;
-    // pp_fetch_packed_async: the packed records of the same tick (PackedPlan set plan_set, PackedGrid set of GridOut set grid_set),
-    // behind the same events, on the same two download streams
-    PackedPlan* pkp_dst; const PackedPlan* pkp_src; bool pkp_issued;
-    PackedGrid* pkg_dst; const PackedGrid* pkg_src; bool pkg_issued;
-    bool want_plan() const { return plan_dst || res_dst || show_dst; }
-    bool plan_side_open() const { return (want_plan() && !plan_issued) || (pkp_dst && !pkp_issued); }
-    bool grid_side_open() const { return (grid_dst && !grid_issued) || (pkg_dst && !pkg_issued); }
-    hipEvent_t ev_front, ev_tail;      // own references: taken out of the tick's TickRec so that they are not recycled early
-    size_t n;
+//
+// One record is one SIDE of one call: the plan side reads the tick's PlanOut set (or the PackedPlan set of the same index) behind
+// the tick's ev_front, the grid side its GridOut set (or the PackedGrid set of its group position) behind ev_tail - ev_front for a
+// tick without one.  Requests do not join: a second request for a tick is more records, issued behind the same event on the same
+// stream, so every destination a call accepted is filled.
+struct FetchCopy { void* dst; const void* src; size_t bytes, stride; };      // per scene: `bytes` out of every `stride` (stride == bytes: one contiguous copy)
+struct FetchRec {
+    long long tick; int slot, set;      // slot: tick % kDone; set: the PlanOut / GridOut set the copies read
+    hipEvent_t dep;                     // the tick's event (prune_inflight keeps the TickRec that owns it until the record is issued)
+    size_t n; bool issued;
+    int n_copies; FetchCopy copy[2];    // plan side: PlanOut, or result + show, or PackedPlan; grid side: GridOut or PackedGrid
+    void add(void* dst, const void* src, size_t bytes, size_t stride) { if (dst) copy[n_copies++] = { dst, src, bytes, stride }; }
 };
+// What a side owns: its download stream, its records in the order they were asked for, and the points "behind the last download
+// that read device set q" (what the tick that rewrites the set waits for) and "behind the downloads of tick done_tick[slot]".
+enum { kPlanSide = 0, kGridSide = 1 };
+struct FetchSide {
+    hipStream_t stream = nullptr;
+    SyncPoint fetched[kGout > kPlan ? kGout : kPlan];      // plan side: kPlan sets in use, grid side: kGout
+    SyncPoint done[kDone];
+    std::vector<FetchRec> queue;
+};
+// What one fetch call asks for, built by the three typed entry points (pp_fetch_async, pp_fetch_published_async,
+// pp_fetch_packed_async): at most two copies on the plan side and one on the grid side (a copy with a null destination is not asked
+// for), and whether they read the packed sets.  fetch_async turns it into at most one record per side, appended to that side's queue.
+struct FetchAsk { bool packed; FetchCopy plan[2]; FetchCopy grid; };
+template <class T> FetchCopy whole_records(T* dst, const T* src) { return { dst, src, sizeof(T), sizeof(T) }; }
+template <class T> FetchCopy plan_slice(T* dst, const PlanOut* src, size_t off)      // one member out of every PlanOut record
+{ return { dst, reinterpret_cast<const char*>(src) + off, sizeof(T), sizeof(PlanOut) }; }
 
 // closed-loop rollout (first pp_advance_async): the sticky DMPP_EGO_* word of every scene; adv follows the last advance kernel;
 // staged_by_advance: the staged input set was produced on the device; set_tick: tick_seq when the resident scenes were last set
@@ -264,7 +279,7 @@ struct ScoreTraceState {
 // packed streamed fetch (first pp_set_packed_fetch(h, 1)): one PackedPlan set per PlanOut set and one PackedGrid
 // set per GridOut group position (an armed handle is a streamed one: groups of 1, tick slot 0 only), each written by its tick's pack
 // kernel in stream order behind the kernel that wrote the PlanOut / GridOut set of the same index - so a set is rewritten only
-// behind its last download, by the waits that already guard those (fetched_plan / fetched_grid).  No rollout feature: no set call
+// behind its last download, by the waits that already guard those (FetchSide::fetched).  No rollout feature: no set call
 // retires it, and the sets hold caps.max_scenes records, so nothing that changes the resident scenes re-allocates.  plan_tick /
 // grid_tick: the last tick whose k_pack_plan / k_pack_grid was launched (what pp_fetch_packed_async may name)
 struct PackedState {
@@ -282,8 +297,11 @@ struct pp_planner {
     int device = 0;
     int n_scenes = 0;
     hipStream_t stream = nullptr;
-    // inputs: d_in / d_obs / d_mot / have_motion / n_obs_total are views of in_sets[in_cur]
-    SceneIn* d_in = nullptr; ObPoint* d_obs = nullptr; ObMotion* d_mot = nullptr; bool have_motion = false; int n_obs_total = 0;
+    // inputs: the SceneIn records, the obstacle and motion pools and their sizes are those of the current input set, cur_in(); one
+    // set (pp_create) until streamed ticks begin
+    InputSet in_sets[kIn]; int in_cur = 0, in_staged = -1;
+    InputSet& cur_in() { return in_sets[in_cur]; }
+    const InputSet& cur_in() const { return in_sets[in_cur]; }
     DevBuf<GlobalPoint3D> d_lane; DevBuf<uint8_t> d_attr; bool have_attr = false; DevBuf<GlobalPoint2D> d_ref;
     int n_lane_pts = 0, n_ref_pts = 0;   // pool sizes of the resident scenes (slice validation)
     int resident_mode = 0;       // 0: scenes with their own slices (pp_set_scenes), 1: egos on the resident map (pp_set_egos)
@@ -293,7 +311,9 @@ struct pp_planner {
     DevBuf<int> d_map_bad; int map_roads = 0, map_lanes = 0, map_junctions = 0; bool have_map = false;
     // state / outputs.  The obstacle snapshot, GridOut and the path cells are rings of sets: one allocation per group position
     // (*_mem), the sets of its tick slots at a fixed stride inside it (dmpp::TickGroup; slots beyond gcap: none)
-    DevBuf<SceneState> d_state; PlanOut* d_plan = nullptr;       // d_plan: a view of d_plan_ring[plan_cur]
+    DevBuf<SceneState> d_state;
+    DevBuf<PlanOut> d_plan_ring[kPlan]; int plan_cur = 0;        // PlanOut sets: one (pp_create) until streamed ticks begin
+    PlanOut* plan_out() const { return d_plan_ring[plan_cur]; }  // the last tick's
     DevBuf<ObPoint> obs_now_mem[kRing]; ObPoint* d_obs_now[kObs] = {};
     DevBuf<GridOut> gout_mem[kGoutRing]; GridOut* d_gout[kGout] = {}; int gout_set = 0;   // kGout sets (a download of tick t must not hold up the searches after it); gout_set: the last grid tick's
     DevBuf<GlobalPoint2D> d_dec_ref;
@@ -341,18 +361,15 @@ struct pp_planner {
     bool r_on_main = false;      // the last tick ran Decision + Planning on the handle's stream (grid stage off)
     // op scratch (stand-alone operators), in bytes
     DevBuf<char> d_scratch;
-    // streamed ticks (allocated by the first pp_update_async / pp_fetch_async)
+    // streamed ticks (the other input and PlanOut sets and the streams are allocated by the first pp_update_async / pp_fetch_async)
     bool streaming = false;
-    InputSet in_sets[kIn]; int in_cur = 0, in_staged = -1;
-    DevBuf<PlanOut> d_plan_ring[kPlan]; int plan_cur = 0;
-    hipStream_t stream_up = nullptr, stream_dp = nullptr, stream_dg = nullptr;   // upload; download of PlanOut; download of GridOut
-    SyncPoint fetched_plan[kPlan], fetched_grid[kGout];       // behind the last download that read that PlanOut / GridOut set
-    SyncPoint done_p[kDone], done_g[kDone]; long long done_tick[kDone];      // behind the downloads of tick done_tick[slot]
-    HostPin<int32_t> h_bad;      // pinned, [kDone]: poisoned scenes of the tick (copied down with its PlanOut)
+    hipStream_t stream_up = nullptr;                          // upload
+    FetchSide dl[2];                                          // downloads: [kPlanSide] of PlanOut / PackedPlan, [kGridSide] of GridOut / PackedGrid
+    long long done_tick[kDone];                               // the tick whose downloads dl[.].done[slot] stand behind
+    HostPin<int32_t> h_bad;     // pinned, [kDone]: poisoned scenes of the tick (copied down with its PlanOut)
     long long tick_seq = 0;      // ticks enqueued so far on this handle (the id of the last one)
     TickRec rec_last = { -1, 0, nullptr, nullptr };
     std::vector<TickRec> inflight; std::vector<hipEvent_t> sync_events;   // sync_events: a pool of timing-disabled events
-    std::vector<PendingFetch> fetches;
     // one block per rollout feature.  Which call switches which feature off, and what holds between the `on` flags, is the table of
     // rollout_features.hpp; a set call writes its own flag, retire() every other one, features_ok() checks the result
     RolloutState rollout;
@@ -414,16 +431,8 @@ hipEvent_t get_sync_event(pp_planner* h)
     return e;
 }
 
-// h->d_in / d_obs / d_mot / have_motion / n_obs_total are the input set the next tick reads
-void adopt_input_set(pp_planner* h, int s)
-{
-    const InputSet& I = h->in_sets[s];
-    h->in_cur = s; h->d_in = I.d_in; h->d_obs = I.d_obs; h->d_mot = I.d_mot; h->have_motion = I.have_motion; h->n_obs_total = I.n_obs_total;
-}
 void note_current_set(pp_planner* h)          // after a pp_set_* call changed what the current set holds
 {
-    InputSet& I = h->in_sets[h->in_cur];
-    I.have_motion = h->have_motion; I.n_obs_total = h->n_obs_total;
     h->in_staged = -1;                        // an update staged before it is superseded
     h->rollout.staged_by_advance = false; h->rollout.set_tick = h->tick_seq;
 }
@@ -529,44 +538,32 @@ int build_follow(pp_planner* h)
 // PlanOut / GridOut set (the next tick is about to overwrite it).
 int pump_fetches(pp_planner* h, long long force_tick = -1, int force_plan_set = -1, int force_grid_set = -1)
 {
-    for (PendingFetch& f : h->fetches) {
-        if (f.plan_side_open()) {
-            const bool ready = hipEventQuery(f.ev_front) == hipSuccess;
-            if (ready || f.tick == force_tick || f.plan_set == force_plan_set) {
-                (void)hipGetLastError();
-                if (!ready) HIP_TRY(hipStreamWaitEvent(h->stream_dp, f.ev_front, 0));
-                if (f.pkp_dst && !f.pkp_issued) HIP_TRY(hipMemcpyAsync(f.pkp_dst, f.pkp_src, f.n * sizeof(PackedPlan), hipMemcpyDefault, h->stream_dp));
-                f.pkp_issued = true;
-                if (f.want_plan() && !f.plan_issued) {
-                    if (f.plan_dst) HIP_TRY(hipMemcpyAsync(f.plan_dst, f.plan_src, f.n * sizeof(PlanOut), hipMemcpyDefault, h->stream_dp));
-                    const char* base = reinterpret_cast<const char*>(f.plan_src);
-                    if (f.res_dst) HIP_TRY(hipMemcpy2DAsync(f.res_dst, sizeof(PlanningOut), base + offsetof(PlanOut, result), sizeof(PlanOut), sizeof(PlanningOut), f.n, hipMemcpyDefault, h->stream_dp));
-                    if (f.show_dst) HIP_TRY(hipMemcpy2DAsync(f.show_dst, sizeof(PlanningStatus), base + offsetof(PlanOut, show), sizeof(PlanOut), sizeof(PlanningStatus), f.n, hipMemcpyDefault, h->stream_dp));
-                }
-                PP_TRY(h->fetched_plan[f.plan_set].record(h->stream_dp));
-                PP_TRY(h->done_p[f.slot].record(h->stream_dp));
-                f.plan_issued = true;
+    const int force_set[2] = { force_plan_set, force_grid_set };
+    // The grid side first: a tick's scoring pass ends ticks behind its Planning kernel, so the grid record that has become ready
+    // belongs to an OLDER tick than the plan record that has - the tick pp_wait_tick is called for next.  Its copy goes out ahead of
+    // the newer tick's (measured: plan side first, the streamed leg of bench.py lost 7 - 9 %: profiles/r35_streamed_io.txt)
+    for (int side : { kGridSide, kPlanSide }) {
+        FetchSide& S = h->dl[side];
+        for (FetchRec& f : S.queue) {
+            if (f.issued) continue;
+            const bool ready = hipEventQuery(f.dep) == hipSuccess;
+            if (!ready && f.tick != force_tick && f.set != force_set[side]) continue;
+            (void)hipGetLastError();
+            if (!ready) HIP_TRY(hipStreamWaitEvent(S.stream, f.dep, 0));
+            for (int i = 0; i < f.n_copies; i++) {
+                const FetchCopy& c = f.copy[i];
+                if (c.stride == c.bytes) HIP_TRY(hipMemcpyAsync(c.dst, c.src, f.n * c.bytes, hipMemcpyDefault, S.stream));
+                else HIP_TRY(hipMemcpy2DAsync(c.dst, c.bytes, c.src, c.stride, c.bytes, f.n, hipMemcpyDefault, S.stream));
             }
+            PP_TRY(S.fetched[f.set].record(S.stream));
+            PP_TRY(S.done[f.slot].record(S.stream));
+            f.issued = true;
         }
-        if (f.grid_side_open()) {
-            hipEvent_t dep = f.ev_tail ? f.ev_tail : f.ev_front;
-            const bool ready = hipEventQuery(dep) == hipSuccess;
-            if (ready || f.tick == force_tick || f.grid_set == force_grid_set) {
-                (void)hipGetLastError();
-                if (!ready) HIP_TRY(hipStreamWaitEvent(h->stream_dg, dep, 0));
-                if (f.pkg_dst && !f.pkg_issued) HIP_TRY(hipMemcpyAsync(f.pkg_dst, f.pkg_src, f.n * sizeof(PackedGrid), hipMemcpyDefault, h->stream_dg));
-                f.pkg_issued = true;
-                if (f.grid_dst && !f.grid_issued) HIP_TRY(hipMemcpyAsync(f.grid_dst, f.grid_src, f.n * sizeof(GridOut), hipMemcpyDefault, h->stream_dg));
-                PP_TRY(h->fetched_grid[f.grid_set].record(h->stream_dg));
-                PP_TRY(h->done_g[f.slot].record(h->stream_dg));
-                f.grid_issued = true;
-            }
-        }
+        size_t k = 0;                         // issued records leave from the front (prune_inflight looks at the first one left)
+        while (k < S.queue.size() && S.queue[k].issued) k++;
+        S.queue.erase(S.queue.begin(), S.queue.begin() + (long)k);
     }
     (void)hipGetLastError();                  // hipErrorNotReady is not an error here
-    size_t k = 0;                             // completed requests leave from the front (prune_inflight looks at the first one left)
-    while (k < h->fetches.size() && !h->fetches[k].plan_side_open() && !h->fetches[k].grid_side_open()) k++;
-    h->fetches.erase(h->fetches.begin(), h->fetches.begin() + (long)k);
     return PP_OK;
 }
 
@@ -575,10 +572,12 @@ int pump_fetches(pp_planner* h, long long force_tick = -1, int force_plan_set = 
 // events of the last tick, which are recorded again by the next tick at the earliest - and then rec_last names that one.
 int prune_inflight(pp_planner* h)
 {
+    long long named = h->tick_seq + 1;        // the oldest tick whose events a download not issued yet still names: the older of the two front records
+    for (const FetchSide& S : h->dl) if (!S.queue.empty()) named = std::min(named, S.queue.front().tick);
     size_t k = 0;
     while (k < h->inflight.size()) {
         const TickRec& r = h->inflight[k];
-        if (!h->fetches.empty() && r.tick >= h->fetches.front().tick) break;      // its events are still named by a download not issued yet
+        if (r.tick >= named) break;
         if (hipEventQuery(r.ev_front) != hipSuccess || (r.ev_tail && hipEventQuery(r.ev_tail) != hipSuccess)) break;
         h->sync_events.push_back(r.ev_front); if (r.ev_tail) h->sync_events.push_back(r.ev_tail);
         k++;
@@ -829,8 +828,7 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     if ((r = h->d_ref.reserve((size_t)caps->max_ref_pts_total))) return bail(r);
     if ((r = h->in_sets[0].d_obs.reserve((size_t)caps->max_obs_total))) return bail(r);
     if ((r = h->in_sets[0].d_mot.reserve((size_t)caps->max_obs_total))) return bail(r);
-    adopt_input_set(h, 0);
-    if (hipMemsetAsync(h->d_mot, 0, (size_t)(caps->max_obs_total > 0 ? caps->max_obs_total : 1) * sizeof(ObMotion), h->stream) != hipSuccess)
+    if (hipMemsetAsync(h->in_sets[0].d_mot, 0, (size_t)(caps->max_obs_total > 0 ? caps->max_obs_total : 1) * sizeof(ObMotion), h->stream) != hipSuccess)
         return bail(fail(PP_ERR_HIP, "memset failed"));     // velocities nobody uploaded are zero, never uninitialised
     if ((r = h->d_bad.reserve((size_t)1))) return bail(r);
     // the sets of the tick slots of a group position lie at a fixed stride in one allocation (dmpp::TickGroup); slots beyond gcap: none
@@ -841,8 +839,7 @@ int pp_create(const PlannerConfig* cfg, int device, const PlannerCaps* caps, pp_
     }
     if ((r = h->d_state.reserve(ns))) return bail(r);
     if ((r = h->d_plan_ring[0].reserve(ns))) return bail(r);
-    h->d_plan = h->d_plan_ring[0];
-    if (hipMemsetAsync(h->d_plan, 0, ns * sizeof(PlanOut), h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "memset failed"));
+    if (hipMemsetAsync(h->d_plan_ring[0], 0, ns * sizeof(PlanOut), h->stream) != hipSuccess) return bail(fail(PP_ERR_HIP, "memset failed"));
     for (int q = 0; q < kDone; q++) h->done_tick[q] = -1;
     for (int q = 0; q < kGout; q += kGroupMax) {
         if ((r = h->gout_mem[q / kGroupMax].reserve(h->gcap * ns))) return bail(r);
@@ -883,7 +880,7 @@ int pp_destroy(pp_handle h)
     (void)hipSetDevice(h->device);
     (void)flush_group(h);                     // (the open group's work buffers go with the handle: its launches are enqueued and waited for)
     // every stream is idle before the first buffer is released (the buffers go last, with the handle)
-    std::vector<hipStream_t> streams = { h->stream, h->stream_r, h->stream_up, h->stream_dp, h->stream_dg };
+    std::vector<hipStream_t> streams = { h->stream, h->stream_r, h->stream_up, h->dl[kPlanSide].stream, h->dl[kGridSide].stream };
     for (int q = 1; q < kBuf; q++) streams.push_back(h->stream_m[q]);      // (stream_m[0] is the handle's stream)
     for (hipStream_t st : streams) if (st) (void)hipStreamSynchronize(st);
     for (auto& p : h->pending) { h->free_events.push_back(p.a); h->free_events.push_back(p.b); }
@@ -956,7 +953,7 @@ static int validate_resident(pp_handle h, int n_scenes, const char* who)
     if (n_scenes > 0) {
         HIP_TRY(hipMemsetAsync(h->d_bad, 0, sizeof(int), h->stream));
         hipLaunchKernelGGL(dmpp::k_validate_scenes, dim3((unsigned)((n_scenes + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream,
-                           n_scenes, h->d_in, h->n_obs_total, h->n_lane_pts, h->n_ref_pts, h->d_bad);
+                           n_scenes, h->cur_in().d_in, h->cur_in().n_obs_total, h->n_lane_pts, h->n_ref_pts, h->d_bad);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&bad, h->d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     }
@@ -971,11 +968,12 @@ static int validate_resident(pp_handle h, int n_scenes, const char* who)
 // The obstacle and motion pools of new resident scenes, into the current input set (handle's stream).
 static int upload_pools(pp_handle h, const ObPoint* obs_pool, const ObMotion* mot_pool, int n_obs_total)
 {
-    if (n_obs_total && obs_pool) HIP_TRY(hipMemcpyAsync(h->d_obs, obs_pool, (size_t)n_obs_total * sizeof(ObPoint), hipMemcpyDefault, h->stream));
-    h->have_motion = false;
+    InputSet& I = h->cur_in();
+    if (n_obs_total && obs_pool) HIP_TRY(hipMemcpyAsync(I.d_obs, obs_pool, (size_t)n_obs_total * sizeof(ObPoint), hipMemcpyDefault, h->stream));
+    I.have_motion = false;
     if (n_obs_total && mot_pool) {
-        HIP_TRY(hipMemcpyAsync(h->d_mot, mot_pool, (size_t)n_obs_total * sizeof(ObMotion), hipMemcpyDefault, h->stream));
-        h->have_motion = true;
+        HIP_TRY(hipMemcpyAsync(I.d_mot, mot_pool, (size_t)n_obs_total * sizeof(ObMotion), hipMemcpyDefault, h->stream));
+        I.have_motion = true;
     }
     return PP_OK;
 }
@@ -1004,7 +1002,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
         return fail(PP_ERR_CAPACITY, "pool larger than the capacity given to pp_create");
     if (n_lane_pts < 0 || n_ref_pts < 0 || n_obs_total < 0) return fail(PP_ERR_ARG, "negative size");
     PP_TRY(quiesce(h, false));
-    HIP_TRY(hipMemcpyAsync(h->d_in, in, (size_t)n_scenes * sizeof(SceneIn), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->cur_in().d_in, in, (size_t)n_scenes * sizeof(SceneIn), hipMemcpyDefault, h->stream));
     if (n_lane_pts && lane_pool) HIP_TRY(hipMemcpyAsync(h->d_lane, lane_pool, (size_t)n_lane_pts * sizeof(GlobalPoint3D), hipMemcpyDefault, h->stream));
     h->have_attr = false;
     if (n_lane_pts && lane_attr_pool) {
@@ -1013,7 +1011,7 @@ int pp_set_scenes(pp_handle h, int n_scenes, const SceneIn* in, const GlobalPoin
     }
     if (n_ref_pts && ref_pool) HIP_TRY(hipMemcpyAsync(h->d_ref, ref_pool, (size_t)n_ref_pts * sizeof(GlobalPoint2D), hipMemcpyDefault, h->stream));
     PP_TRY(upload_pools(h, obs_pool, mot_pool, n_obs_total));
-    h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
+    h->n_scenes = n_scenes; h->cur_in().n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
     return resident_replaced(h, 0, "pp_set_scenes");
 }
 
@@ -1068,18 +1066,18 @@ int pp_set_egos(pp_handle h, int n_scenes, const SceneIn* in, const ObPoint* obs
     if (n_scenes < 0 || n_scenes > h->caps.max_scenes) return fail(PP_ERR_CAPACITY, "n_scenes exceeds caps.max_scenes");
     if (n_obs_total < 0 || n_obs_total > h->caps.max_obs_total) return fail(PP_ERR_CAPACITY, "obstacle pool larger than caps.max_obs_total");
     PP_TRY(quiesce(h, false));
-    HIP_TRY(hipMemcpyAsync(h->d_in, in, (size_t)n_scenes * sizeof(SceneIn), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->cur_in().d_in, in, (size_t)n_scenes * sizeof(SceneIn), hipMemcpyDefault, h->stream));
     PP_TRY(upload_pools(h, obs_pool, mot_pool, n_obs_total));
     HIP_TRY(hipMemsetAsync(h->d_map_bad, 0, sizeof(int), h->stream));
     if (n_scenes)
         hipLaunchKernelGGL(dmpp::k_resolve_map, dim3((unsigned)((n_scenes + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream,
-                           n_scenes, h->d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
+                           n_scenes, h->cur_in().d_in, h->map_roads, h->d_map_first, h->d_map_lanes, h->d_attr, h->d_map_width,
                            h->map_junctions, h->d_map_junc, h->d_map_bad);
     HIP_TRY(hipGetLastError());
     int bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, h->d_map_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->n_scenes = n_scenes; h->n_obs_total = n_obs_total;
+    h->n_scenes = n_scenes; h->cur_in().n_obs_total = n_obs_total;
     return resident_replaced(h, 1, "pp_set_egos", bad);         // (the obstacle slices are still the caller's: checked there)
 }
 
@@ -1092,7 +1090,7 @@ int pp_get_scene_in(pp_handle h, SceneIn* out, int n)
         PP_TRY(h->in_sets[h->in_staged].up.wait(h->stream));
         return fetch(h, out, h->in_sets[h->in_staged].d_in, (size_t)n * sizeof(SceneIn));
     }
-    return fetch(h, out, h->d_in, (size_t)n * sizeof(SceneIn));
+    return fetch(h, out, h->cur_in().d_in, (size_t)n * sizeof(SceneIn));
 }
 
 int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, int n_obs_total, int have_motion, int have_lane_attr)
@@ -1103,8 +1101,8 @@ int pp_set_n_scenes(pp_handle h, int n_scenes, int n_lane_pts, int n_ref_pts, in
     if (n_lane_pts > h->caps.max_lane_pts_total || n_ref_pts > h->caps.max_ref_pts_total || n_obs_total > h->caps.max_obs_total)
         return fail(PP_ERR_CAPACITY, "pool larger than the capacity given to pp_create");
     PP_TRY(quiesce(h, false));
-    h->n_scenes = n_scenes; h->n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
-    h->have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
+    h->n_scenes = n_scenes; h->cur_in().n_obs_total = n_obs_total; h->n_lane_pts = n_lane_pts; h->n_ref_pts = n_ref_pts;
+    h->cur_in().have_motion = have_motion != 0; h->have_attr = have_lane_attr != 0;
     return resident_replaced(h, 0, "pp_set_n_scenes");
 }
 
@@ -1169,7 +1167,7 @@ int flush_group(pp_planner* h)
         for (int q = 0; q < kBuf; q++) if (q != p) PP_TRY(h->searched[q].wait(sm));
     if (T.front != sm) PP_TRY(h->raster.wait(sm));
     for (int i = 0; i < G; i++)
-        if (h->streaming) PP_TRY(h->fetched_grid[h->grp_gs[i]].wait_unless_done(sm));   // GridOut set still being downloaded
+        if (h->streaming) PP_TRY(h->dl[kGridSide].fetched[h->grp_gs[i]].wait_unless_done(sm));   // GridOut set still being downloaded
     dmpp::TickGroup tg;                                                // slot i: sets grp_set[0] + i, grp_gs[0] + i
     tg.n = n; tg.in = h->grp_in;
     tg.obs_now = h->d_obs_now[set0]; tg.obs_stride = std::max(h->caps.max_obs_total, 1);
@@ -1252,7 +1250,7 @@ void open_group(pp_planner* h, int n, bool piped)
         for (int q = 0; q < kBuf; q++) need = std::max(need, (int)reinterpret_cast<volatile int32_t*>(h->h_need.get())[((h->ring + kRing - 1 - q) % kRing) * kGroupMax]);     // the last kBuf groups' sets
         if (need >= 0) h->need_seen = need;
     }
-    const dmpp::SearchBudget b = dmpp::search_budget(h->search_static_lds, h->search_meta_bytes, h->gbm_lds, h->lds_budget_max, h->n_cus, n, h->grp_G, h->n_obs_total,
+    const dmpp::SearchBudget b = dmpp::search_budget(h->search_static_lds, h->search_meta_bytes, h->gbm_lds, h->lds_budget_max, h->n_cus, n, h->grp_G, h->cur_in().n_obs_total,
                                                      need, h->lds_budget, h->budget_from_need, h->lds_budget_fixed, h->search_force_gbm);
     h->lds_budget = b.budget; h->budget_from_need = b.from_need; h->search_slots = b.slots;
 }
@@ -1273,7 +1271,7 @@ int pp_plan_tick(pp_handle h)
     const bool piped = tick_piped(h);                                  // the chains and their streams: tick_streams
     // streamed inputs: the update staged by pp_update_async becomes the set this tick (and the following ones) read
     bool adopted = false;
-    if (h->in_staged >= 0) { adopt_input_set(h, h->in_staged); h->in_staged = -1; h->rollout.staged_by_advance = false; adopted = true; }
+    if (h->in_staged >= 0) { h->in_cur = h->in_staged; h->in_staged = -1; h->rollout.staged_by_advance = false; adopted = true; }
     if (h->grp_ticks == 0) open_group(h, n, piped);
     const int slot = h->grp_ticks, G = h->grp_G;
     const int po = h->ring * kGroupMax + slot;                                        // this tick's snapshot set
@@ -1282,7 +1280,7 @@ int pp_plan_tick(pp_handle h)
         // downloads whose kernels have finished are issued now; one that still reads a set this tick overwrites is issued whatever
         int r = pump_fetches(h, -1, (h->plan_cur + 1) % kPlan, c.grid_stage ? gs : -1); if (r) return r;
         r = prune_inflight(h); if (r) return r;
-        h->plan_cur = (h->plan_cur + 1) % kPlan; h->d_plan = h->d_plan_ring[h->plan_cur];
+        h->plan_cur = (h->plan_cur + 1) % kPlan;
         if (!adopted) h->h_bad[(h->tick_seq + 1) % kDone] = 0;
     }
     const TickStreams T = tick_streams(h, piped, c.grid_stage != 0, h->parity);
@@ -1298,10 +1296,11 @@ int pp_plan_tick(pp_handle h)
         PP_TRY(h->fork.record(h->stream)); PP_TRY(h->fork.wait(sf));
     }
     h->r_on_main = sr == h->stream;
-    const SyncPoint& up = h->in_sets[h->in_cur].up;
+    const InputSet& I = h->cur_in(); PlanOut* d_plan = h->plan_out();      // the sets this tick reads and writes
+    const SyncPoint& up = I.up;
     const bool behind_upload = adopted && up.recorded();
     if (behind_upload) PP_TRY(up.wait_unless_done(sf));                   // every kernel of the tick follows the snapshot kernel
-    if (h->streaming) PP_TRY(h->fetched_plan[h->plan_cur].wait_unless_done(sr));   // PlanOut set still being downloaded (kPlan ticks ago)
+    if (h->streaming) PP_TRY(h->dl[kPlanSide].fetched[h->plan_cur].wait_unless_done(sr));   // PlanOut set still being downloaded (kPlan ticks ago)
     // Scorecard: k_score_ego of the last scored tick (upload stream) reads the SceneState this front chain rewrites, and sets of the
     // PlanOut and snapshot rings that a later one does.  A tick that adopts an update or an advance waits for that set's `up`,
     // recorded behind the kernel on the same stream (staging always follows the tick it follows); any other tick waits here.
@@ -1316,10 +1315,10 @@ int pp_plan_tick(pp_handle h)
     // Streamed handles keep the separate launch: their groups are single ticks, every search waits for its own tick's `raster`, and
     // starting each one k_decision later cost the streamed leg 1.3 %, more than its spread (same file).
     const bool snap_fused = h->front_snapshot && c.decision_stage && sf == sr && !h->streaming;
-    const ObMotion* mot = h->have_motion ? h->d_mot : nullptr;
+    const ObMotion* mot = I.mot();
     if (!snap_fused) {
         Timed t(h, PP_K_OBSTACLES, sf);
-        hipLaunchKernelGGL(dmpp::k_effective_obstacles, dim3(n), dim3(dmpp::kBlock), 0, sf, c, n, h->d_in, h->d_state, h->d_obs, mot, obs_now);
+        hipLaunchKernelGGL(dmpp::k_effective_obstacles, dim3(n), dim3(dmpp::kBlock), 0, sf, c, n, I.d_in, h->d_state, I.d_obs, mot, obs_now);
     }
     if (sr != sf) { PP_TRY(h->fork.record(sf)); PP_TRY(h->fork.wait(sr)); }   // small batches: Decision + Planning beside the grid engine
     const bool search_waits = c.grid_stage && sf != T.search;                // the search rasterises for itself: it only needs the obstacle snapshot
@@ -1327,24 +1326,24 @@ int pp_plan_tick(pp_handle h)
     if (c.decision_stage) {
         Timed t(h, PP_K_DECISION, sr);
         if (snap_fused)
-            hipLaunchKernelGGL(dmpp::k_decision<true>, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, h->d_in, h->d_lane,
-                               h->d_attr, h->d_ref, h->d_obs, mot, obs_now, h->d_state, h->d_plan, h->d_dec_ref);
+            hipLaunchKernelGGL(dmpp::k_decision<true>, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, I.d_in, h->d_lane,
+                               h->d_attr, h->d_ref, I.d_obs, mot, obs_now, h->d_state, d_plan, h->d_dec_ref);
         else
-            hipLaunchKernelGGL(dmpp::k_decision<false>, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, h->d_in, h->d_lane,
-                               h->d_attr, h->d_ref, h->d_obs, mot, obs_now, h->d_state, h->d_plan, h->d_dec_ref);
+            hipLaunchKernelGGL(dmpp::k_decision<false>, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, I.d_in, h->d_lane,
+                               h->d_attr, h->d_ref, I.d_obs, mot, obs_now, h->d_state, d_plan, h->d_dec_ref);
     }
     if (search_waits && snap_fused) PP_TRY(h->raster.record(sf));
     {
         Timed t(h, PP_K_PLANNING, sr);
-        hipLaunchKernelGGL(dmpp::k_planning, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::PlanShared), sr, c, n, h->d_in, h->d_lane,
-                           h->d_ref, h->d_dec_ref, obs_now, h->d_state, h->d_plan);
+        hipLaunchKernelGGL(dmpp::k_planning, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::PlanShared), sr, c, n, I.d_in, h->d_lane,
+                           h->d_ref, h->d_dec_ref, obs_now, h->d_state, d_plan);
     }
     if (h->packed.on) {          // packed fetch, plan half: behind the Planning kernel in stream order, in front of `join` and the tick's ev_front
         {
             Timed t(h, PP_K_PACK_PLAN, sr);
             const long long chunks = (long long)n * dmpp::kPkPlanChunks;
             hipLaunchKernelGGL(dmpp::k_pack_plan, dim3((unsigned)((chunks + dmpp::kPkBlock - 1) / dmpp::kPkBlock)), dim3(dmpp::kPkBlock), 0, sr,
-                               n, h->d_plan, h->packed.d_plan[h->plan_cur].get());
+                               n, d_plan, h->packed.d_plan[h->plan_cur].get());
         }
         h->packed.plan_tick = h->tick_seq + 1;
         if (c.grid_stage) h->packed.grid_tick = h->tick_seq + 1;      // (its group - of 1 - is launched below)
@@ -1352,7 +1351,7 @@ int pp_plan_tick(pp_handle h)
     if (sr != h->stream) { PP_TRY(h->join.record(sr)); h->front_unjoined = piped; }
     h->obs_set = po;
     if (c.grid_stage) {
-        h->grp_set[slot] = po; h->grp_gs[slot] = gs; h->grp_in = h->d_in;
+        h->grp_set[slot] = po; h->grp_gs[slot] = gs; h->grp_in = I.d_in;
         h->grp_ticks = slot + 1;
         h->gout_set = gs; h->path_set = po;
         h->score.grp_scored = h->score.on;
@@ -1378,8 +1377,8 @@ int pp_plan_tick(pp_handle h)
             ScoreTraceInfo* tinfo = trace ? h->strace.d_info.get() : nullptr;
             ScoreTick* tring = trace ? h->strace.d_ring.get() : nullptr;
             auto* kern = log ? (trace ? dmpp::k_score_ego<true, true> : dmpp::k_score_ego<true, false>) : (trace ? dmpp::k_score_ego<false, true> : dmpp::k_score_ego<false, false>);
-            hipLaunchKernelGGL(kern, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, h->n_obs_total,
-                               h->d_in, h->d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, ep_score,
+            hipLaunchKernelGGL(kern, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, I.n_obs_total,
+                               I.d_in, d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, ep_score,
                                h->tick_seq, h->strace.tm, ep_stats, tinfo, tring);
             PP_TRY(h->score.ego.record(su));
         }
@@ -1403,7 +1402,7 @@ int pp_sync(pp_handle h)
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->streaming) {          // staged updates and downloads too (everything has finished: every pending copy is issued)
         int r = pump_fetches(h); if (r) return r;
-        for (hipStream_t st : { h->stream_up, h->stream_dp, h->stream_dg }) HIP_TRY(hipStreamSynchronize(st));
+        for (hipStream_t st : { h->stream_up, h->dl[kPlanSide].stream, h->dl[kGridSide].stream }) HIP_TRY(hipStreamSynchronize(st));
     }
     return PP_OK;
 }
@@ -1438,7 +1437,7 @@ int pp_get_plan(pp_handle h, PlanOut* out, int n)
 {
     if (!h || !out) return fail(PP_ERR_ARG, "null argument");
     if (n < 0 || n > h->n_scenes) return fail(PP_ERR_ARG, "n exceeds the resident scenes");
-    return fetch(h, out, h->d_plan, (size_t)n * sizeof(PlanOut));
+    return fetch(h, out, h->plan_out(), (size_t)n * sizeof(PlanOut));
 }
 int pp_get_state(pp_handle h, SceneState* st, int n)
 {
@@ -1473,9 +1472,9 @@ int pp_get_grid(pp_handle h, int scene, uint8_t* grid)
     const int budget = h->search_force_gbm ? 1 : h->lds_budget_max;      // (1 word: nothing fits, the span-by-span path)
     const size_t dyn = (size_t)h->search_meta_bytes + 8 * (size_t)budget;
     switch (h->search_kind) {
-    case 0: hipLaunchKernelGGL(dmpp::k_export_grid<0>, dim3(1), dim3(dmpp::kSearchBlock), dyn, h->stream, c, scene, budget, h->d_in, obs_now, h->d_grid, h->d_gridbad); break;
-    case 1: hipLaunchKernelGGL(dmpp::k_export_grid<1>, dim3(1), dim3(dmpp::kSearchBlock), dyn, h->stream, c, scene, budget, h->d_in, obs_now, h->d_grid, h->d_gridbad); break;
-    default: hipLaunchKernelGGL(dmpp::k_export_grid<2>, dim3(1), dim3(dmpp::kSearchBlock), dyn, h->stream, c, scene, budget, h->d_in, obs_now, h->d_grid, h->d_gridbad); break;
+    case 0: hipLaunchKernelGGL(dmpp::k_export_grid<0>, dim3(1), dim3(dmpp::kSearchBlock), dyn, h->stream, c, scene, budget, h->cur_in().d_in, obs_now, h->d_grid, h->d_gridbad); break;
+    case 1: hipLaunchKernelGGL(dmpp::k_export_grid<1>, dim3(1), dim3(dmpp::kSearchBlock), dyn, h->stream, c, scene, budget, h->cur_in().d_in, obs_now, h->d_grid, h->d_gridbad); break;
+    default: hipLaunchKernelGGL(dmpp::k_export_grid<2>, dim3(1), dim3(dmpp::kSearchBlock), dyn, h->stream, c, scene, budget, h->cur_in().d_in, obs_now, h->d_grid, h->d_gridbad); break;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(bad, h->d_gridbad, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1568,15 +1567,14 @@ static int ensure_streaming(pp_handle h)
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     // the upload carries two small kernels (map views, slice check) that the next front chain waits for: top priority
     if (!h->stream_up) HIP_TRY(hipStreamCreateWithPriority(&h->stream_up, hipStreamNonBlocking, prio_greatest));
-    if (!h->stream_dp) HIP_TRY(hipStreamCreateWithPriority(&h->stream_dp, hipStreamNonBlocking, prio_least));
-    if (!h->stream_dg) HIP_TRY(hipStreamCreateWithPriority(&h->stream_dg, hipStreamNonBlocking, prio_least));
+    for (FetchSide& S : h->dl) if (!S.stream) HIP_TRY(hipStreamCreateWithPriority(&S.stream, hipStreamNonBlocking, prio_least));
     if (!h->h_bad) { int r2 = h->h_bad.alloc(kDone); if (r2) return r2; for (int q = 0; q < kDone; q++) h->h_bad[q] = 0; }
     // everything enqueued before streaming began (ticks, the memsets above) is ordered before the three new streams
     { int r2 = join_all(h); if (r2) return r2; }
     hipEvent_t e = get_sync_event(h);
     if (!e) return fail(PP_ERR_HIP, "event creation failed");
     HIP_TRY(hipEventRecord(e, h->stream));
-    for (hipStream_t st : { h->stream_up, h->stream_dp, h->stream_dg }) HIP_TRY(hipStreamWaitEvent(st, e, 0));
+    for (hipStream_t st : { h->stream_up, h->dl[kPlanSide].stream, h->dl[kGridSide].stream }) HIP_TRY(hipStreamWaitEvent(st, e, 0));
     HIP_TRY(hipStreamSynchronize(h->stream));      // (once per handle) so that e can go back to the pool
     h->sync_events.push_back(e);
     h->streaming = true;
@@ -1642,18 +1640,18 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         const dmpp::AdvTrack trk = { h->tracker.tk, h->tracker.d_state, h->episode.on ? h->episode.d_stats.get() : nullptr };
         if (h->route.on && h->tracker.on)
             hipLaunchKernelGGL(dmpp::k_advance_route<true>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
+                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
                                h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace, trk);
         else if (h->route.on)             // routed egos cross junctions; the scenes without a route advance as below
             hipLaunchKernelGGL(dmpp::k_advance_route<false>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
+                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
                                h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace, 0);
         else if (h->tracker.on)
             hipLaunchKernelGGL(dmpp::k_advance_egos<true>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace, trk);
+                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->rollout.d_flags, src.trace, trk);
         else
             hipLaunchKernelGGL(dmpp::k_advance_egos<false>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->d_plan, h->d_state, h->d_lane, h->rollout.d_flags, src.trace, 0);
+                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->rollout.d_flags, src.trace, 0);
         if (h->episode.on && h->spawn.on && h->spawn.sched_on) {      // ... with the spawn model and a schedule over its start records (§4p): the first choice is drawn by weights
             EpisodeScheduleRow* rows = h->spawn.d_rows;
             hipLaunchKernelGGL(dmpp::k_respawn_sched, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
@@ -1900,7 +1898,7 @@ static std::vector<dmpp::FleetPin> own_slices(pp_handle h, int* rc)
     if (h->fleet.on) return h->fleet.pin;
     const size_t n = (size_t)h->n_scenes;
     std::vector<SceneIn> rec(n);
-    hipError_t e = hipMemcpyAsync(rec.data(), h->d_in, n * sizeof(SceneIn), hipMemcpyDeviceToHost, h->stream);
+    hipError_t e = hipMemcpyAsync(rec.data(), h->cur_in().d_in, n * sizeof(SceneIn), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { *rc = fail(PP_ERR_HIP, std::string("reading the resident SceneIn records: ") + hipGetErrorString(e)); return {}; }
     std::vector<dmpp::FleetPin> pin(n);
@@ -1918,12 +1916,12 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     if (n_worlds == 0) {
         if (!h->fleet.on) return PP_OK;
         PP_TRY(quiesce(h, false));
-        hipLaunchKernelGGL(dmpp::k_fleet_restore, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, n, h->fleet.d_pin, h->d_in);
+        hipLaunchKernelGGL(dmpp::k_fleet_restore, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, n, h->fleet.d_pin, h->cur_in().d_in);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(h->stream));
         // (the slices are the pinned ones again; they were inside fleet.base when they were pinned)
         const int back = std::max(h->fleet.base, h->fleet.own_end);
-        h->fleet.on = false; h->n_obs_total = back; h->in_sets[h->in_cur].n_obs_total = back;
+        h->fleet.on = false; h->cur_in().n_obs_total = back;
         retire(h, dmpp::kSetFleet);                       // (the worlds that world traffic was pinned to are gone: §4j)
         return features_ok(h, "pp_set_fleet");
     }
@@ -1938,7 +1936,7 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     PP_TRY(quiesce(h, false));
     int rc;
     std::vector<dmpp::FleetPin> pin = own_slices(h, &rc); if (rc) return rc;
-    const int base = h->fleet.on ? h->fleet.base : h->n_obs_total;
+    const int base = h->fleet.on ? h->fleet.base : h->cur_in().n_obs_total;
     std::vector<std::pair<long long, long long>> ext;       // non-empty extended slices [off, off + n_own + K)
     long long end_max = base, own_end = 0;
     for (int s = 0; s < n; s++) {
@@ -1965,8 +1963,8 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     h->fleet.pin.swap(pin); h->fleet.fm = *fm; h->fleet.base = base; h->fleet.end = (int)end_max; h->fleet.own_end = (int)std::min(own_end, (long long)h->caps.max_obs_total); h->fleet.on = true;
     h->fleet.n_worlds = n_worlds;
     retire(h, dmpp::kSetFleet);                           // world traffic was pinned to the worlds this call replaces (§4j)
-    h->n_obs_total = (int)end_max; h->in_sets[h->in_cur].n_obs_total = (int)end_max;
-    couple_fleet(h, h->stream, h->d_in, h->d_obs, h->have_motion ? h->d_mot : nullptr);      // the resident set: the next tick sees the peers
+    h->cur_in().n_obs_total = (int)end_max;
+    couple_fleet(h, h->stream, h->cur_in().d_in, h->cur_in().d_obs, h->cur_in().mot());      // the resident set: the next tick sees the peers
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
     return features_ok(h, "pp_set_fleet");
@@ -2065,7 +2063,7 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     if (world) HIP_TRY(hipMemcpyAsync(h->traffic.d_world, scene_of.data(), (size_t)n_actors * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     h->traffic.actors = n_actors; h->traffic.end = (int)end_max; h->traffic.cur = 0; h->traffic.world = world;
     h->traffic.scene_of.swap(scene_of); h->traffic.track_of.swap(track_of);
-    move_traffic(h, h->stream, h->d_obs, h->have_motion ? h->d_mot : nullptr, 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
+    move_traffic(h, h->stream, h->cur_in().d_obs, h->cur_in().mot(), 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
     if (h->follow.on) PP_TRY(build_follow(h));           // following is on: its tables for these actors, v = speed (§4i)
@@ -2190,7 +2188,7 @@ int pp_set_episodes(pp_handle h, const EpisodeModel* em)
     PP_TRY(h->episode.d_start_in.reserve(ns)); PP_TRY(h->episode.d_start_state.reserve(ns)); PP_TRY(h->episode.d_stats.reserve(ns));
     h->episode.on = false;                                // (until the copies below have landed: a failed copy leaves episodes off, not half a capture)
     retire(h, dmpp::kSetEpisodes);                        // (record 0 of the spawn model's pool was the old capture, set 0 of the traffic reset went with it, and so did the episodes the log numbered: §4l - §4n)
-    HIP_TRY(hipMemcpyAsync(h->episode.d_start_in, h->d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->episode.d_start_in, h->cur_in().d_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->episode.d_start_state, h->d_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(dmpp::k_episode_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, (int)ns, h->episode.d_stats);
     HIP_TRY(hipGetLastError());
@@ -2522,23 +2520,22 @@ int pp_get_obstacles(pp_handle h, int scene, ObPoint* out, int cap)
     return sl[1];
 }
 
-static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id,
-                       PackedPlan* pk_plan = nullptr, PackedGrid* pk_grid = nullptr)
+// One request for the last tick's results (FetchAsk), from one of the three typed entry points below.
+static int fetch_async(pp_handle h, const FetchAsk& ask, long long* tick_id)
 {
-    if (!h) return fail(PP_ERR_ARG, "null handle");
-    if (!plan && !grid && !result && !show && !pk_plan && !pk_grid) return fail(PP_ERR_ARG, "nothing to fetch");
+    if (!ask.plan[0].dst && !ask.plan[1].dst && !ask.grid.dst) return fail(PP_ERR_ARG, "nothing to fetch");
     if (h->tick_seq == 0 || h->n_scenes <= 0) return fail(PP_ERR_STATE, "pp_fetch_async: no tick has been enqueued");
-    if ((grid || pk_grid) && !h->cfg.grid_stage) return fail(PP_ERR_STATE, "pp_fetch_async: the last tick ran without the grid stage");
-    if (pk_plan || pk_grid) {
+    if (ask.grid.dst && !h->cfg.grid_stage) return fail(PP_ERR_STATE, "pp_fetch_async: the last tick ran without the grid stage");
+    if (ask.packed) {
         if (!h->packed.on) return fail(PP_ERR_STATE, "pp_fetch_packed_async: the packed fetch is not armed (pp_set_packed_fetch)");
-        if (h->packed.plan_tick != h->tick_seq || (pk_grid && h->packed.grid_tick != h->tick_seq))
+        if (h->packed.plan_tick != h->tick_seq || (ask.grid.dst && h->packed.grid_tick != h->tick_seq))
             return fail(PP_ERR_STATE, "pp_fetch_packed_async: the last tick ran before the packed fetch was armed");
     }
     HIP_TRY(hipSetDevice(h->device));
     { int r = flush_group(h); if (r) return r; }          // the downloads follow the last tick's scoring pass: it must be enqueued
     { int r = ensure_streaming(h); if (r) return r; }
     const long long T = h->tick_seq;
-    const int slot = (int)(T % kDone), n = h->n_scenes;
+    const int slot = (int)(T % kDone);
     if (h->rec_last.tick != T) {
         // the last tick was enqueued before streaming began: one event behind everything stands in for its two
         { int r = join_all(h); if (r) return r; }
@@ -2549,36 +2546,32 @@ static int fetch_async(pp_handle h, PlanOut* plan, PlanningOut* result, Planning
         h->inflight.push_back(rec); h->rec_last = rec;
     }
     const TickRec& R = h->rec_last;
-    if (h->done_tick[slot] != T) { h->done_tick[slot] = T; h->done_g[slot].forget(); h->done_p[slot].forget(); }      // (an earlier tick's downloads)
-    const bool want_plan = plan || result || show;
-    PendingFetch f{};
-    f.tick = T; f.slot = slot; f.n = (size_t)n; f.ev_front = R.ev_front; f.ev_tail = R.ev_tail;
-    if (want_plan) { f.plan_dst = plan; f.res_dst = result; f.show_dst = show; f.plan_src = h->d_plan; f.plan_set = h->plan_cur; }
-    if (grid) { f.grid_dst = grid; f.grid_src = h->d_gout[h->gout_set]; f.grid_set = h->gout_set; }
-    if (pk_plan) { f.pkp_dst = pk_plan; f.pkp_src = h->packed.d_plan[h->plan_cur]; f.plan_set = h->plan_cur; }
-    if (pk_grid) { f.pkg_dst = pk_grid; f.pkg_src = h->packed.d_grid[h->gout_set / kGroupMax]; f.grid_set = h->gout_set; }
-    // a second request for the same tick (PlanOut and GridOut asked for separately; a packed request beside a full or published
-    // one) joins the first: the sets of a tick are the same whoever names them.  Each of the request's four parts joins the first
-    // pending entry of the tick that has that part free and leaves f; whatever found no room stays in f and becomes an entry of
-    // its own, so no destination a call accepted is ever dropped.
-    for (PendingFetch& g : h->fetches) if (g.tick == T) {
-        if (f.want_plan() && !g.want_plan()) {
-            g.plan_dst = f.plan_dst; g.res_dst = f.res_dst; g.show_dst = f.show_dst; g.plan_src = f.plan_src; g.plan_set = f.plan_set; g.plan_issued = false;
-            f.plan_dst = nullptr; f.res_dst = nullptr; f.show_dst = nullptr;
-        }
-        if (f.grid_dst && !g.grid_dst) { g.grid_dst = f.grid_dst; g.grid_src = f.grid_src; g.grid_set = f.grid_set; g.grid_issued = false; f.grid_dst = nullptr; }
-        if (f.pkp_dst && !g.pkp_dst) { g.pkp_dst = f.pkp_dst; g.pkp_src = f.pkp_src; g.plan_set = f.plan_set; g.pkp_issued = false; f.pkp_dst = nullptr; }
-        if (f.pkg_dst && !g.pkg_dst) { g.pkg_dst = f.pkg_dst; g.pkg_src = f.pkg_src; g.grid_set = f.grid_set; g.pkg_issued = false; f.pkg_dst = nullptr; }
-    }
-    if (f.want_plan() || f.grid_dst || f.pkp_dst || f.pkg_dst) h->fetches.push_back(f);
+    if (h->done_tick[slot] != T) { h->done_tick[slot] = T; for (FetchSide& S : h->dl) S.done[slot].forget(); }      // (an earlier tick's downloads)
+    FetchRec p = { T, slot, h->plan_cur, R.ev_front, (size_t)h->n_scenes, false, 0, {} };
+    FetchRec g = { T, slot, h->gout_set, R.ev_tail ? R.ev_tail : R.ev_front, (size_t)h->n_scenes, false, 0, {} };
+    for (const FetchCopy& c : ask.plan) p.add(c.dst, c.src, c.bytes, c.stride);
+    g.add(ask.grid.dst, ask.grid.src, ask.grid.bytes, ask.grid.stride);
+    if (p.n_copies) h->dl[kPlanSide].queue.push_back(p);
+    if (g.n_copies) h->dl[kGridSide].queue.push_back(g);
     { int r = pump_fetches(h); if (r) return r; }
     if (tick_id) *tick_id = T;
     return PP_OK;
 }
 
-int pp_fetch_async(pp_handle h, PlanOut* plan, GridOut* grid, long long* tick_id) { return fetch_async(h, plan, nullptr, nullptr, grid, tick_id); }
+// The sources are those of the last enqueued tick: PlanOut set plan_cur, GridOut set gout_set
+int pp_fetch_async(pp_handle h, PlanOut* plan, GridOut* grid, long long* tick_id)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    const GridOut* gout = h->d_gout[h->gout_set];
+    return fetch_async(h, { false, { whole_records(plan, (const PlanOut*)h->plan_out()), {} }, whole_records(grid, gout) }, tick_id);
+}
 int pp_fetch_published_async(pp_handle h, PlanningOut* result, PlanningStatus* show, GridOut* grid, long long* tick_id)
-{ return fetch_async(h, nullptr, result, show, grid, tick_id); }
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    const GridOut* gout = h->d_gout[h->gout_set];
+    return fetch_async(h, { false, { plan_slice(result, h->plan_out(), offsetof(PlanOut, result)), plan_slice(show, h->plan_out(), offsetof(PlanOut, show)) },
+                            whole_records(grid, gout) }, tick_id);
+}
 
 
 // ---------------------------------------------------------------------------------------
@@ -2599,8 +2592,11 @@ int pp_set_packed_fetch(pp_handle h, int on)
 }
 int pp_fetch_packed_async(pp_handle h, PackedPlan* plan, PackedGrid* grid, long long* tick_id)
 {
-    if (h && !plan && !grid) return fail(PP_ERR_ARG, "pp_fetch_packed_async: nothing to fetch");
-    return fetch_async(h, nullptr, nullptr, nullptr, nullptr, tick_id, plan, grid);
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!plan && !grid) return fail(PP_ERR_ARG, "pp_fetch_packed_async: nothing to fetch");
+    // the packed records of the same tick: PackedPlan set plan_cur, PackedGrid set of the GridOut set's group position (null until armed: refused before use)
+    const PackedPlan* pkp = h->packed.d_plan[h->plan_cur]; const PackedGrid* pkg = h->packed.d_grid[h->gout_set / kGroupMax];
+    return fetch_async(h, { true, { whole_records(plan, pkp), {} }, whole_records(grid, pkg) }, tick_id);
 }
 int pp_unpack_plan(const PlannerConfig* cfg, const PackedPlan* in, int n, PlanningOut* result, PlanningStatus* show, DecisionOutPod* dec)
 {
@@ -2631,8 +2627,7 @@ int pp_wait_tick(pp_handle h, long long tick_id, int* n_poisoned)
     HIP_TRY(hipSetDevice(h->device));
     { int r = flush_group(h); if (r) return r; }
     { int r = pump_fetches(h, tick_id); if (r) return r; }
-    PP_TRY(h->done_p[slot].host_wait());                  // (recorded by pump_fetches above, behind the copies it issued - if any were asked for)
-    PP_TRY(h->done_g[slot].host_wait());
+    for (const FetchSide& S : h->dl) PP_TRY(S.done[slot].host_wait());      // (recorded by pump_fetches above, behind the copies it issued - if any were asked for)
     const int bad = (int)reinterpret_cast<volatile int32_t*>(h->h_bad.get())[slot];
     if (n_poisoned) *n_poisoned = bad;
     if (bad) return fail(PP_ERR_ARG, "tick " + std::to_string(tick_id) + ": " + std::to_string(bad) + " scene(s) of its update had a slice outside its pool (or a road / lane outside the map) and ran with empty inputs");
@@ -2662,9 +2657,9 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
         PP_TRY(h->score.ego.wait(h->stream));             // ... and the scorecard of the last tick
     }
     h->in_staged = -1; h->rollout.staged_by_advance = false;
-    hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->d_in, h->d_state, h->d_obs, h->d_ref);
+    hipLaunchKernelGGL(dmpp::k_io_in, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, max_obs, max_ref, h->n_lane_pts, h->cur_in().d_in, h->d_state, h->cur_in().d_obs, h->d_ref);
     HIP_TRY(hipGetLastError());
-    h->n_obs_total = n_obs; h->have_motion = false;
+    h->cur_in().n_obs_total = n_obs; h->cur_in().have_motion = false;
     h->n_ref_pts = std::max(h->n_ref_pts, max_ref);
     note_current_set(h);
     // A piped tick (one scene: grid stage on and DMPP_PIPELINE_MIN <= 1) starts its front chain on another stream, which nothing
@@ -2675,7 +2670,7 @@ int pp_tick_io(pp_handle h, PpSceneIo* io)
     }
     { int r = pp_plan_tick(h); if (r) return r; }
     if (h->last_piped) { int r = join_all(h); if (r) return r; }      // (a one-scene tick ends on the handle's stream, as a rule: nothing to join)
-    hipLaunchKernelGGL(dmpp::k_io_out, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, (int)io->want, h->d_plan, h->d_state,
+    hipLaunchKernelGGL(dmpp::k_io_out, dim3(1), dim3(dmpp::kBlock), 0, h->stream, io, (int)io->want, h->plan_out(), h->d_state,
                        h->cfg.grid_stage ? h->d_gout[h->gout_set] : nullptr, h->d_dec_ref);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2866,13 +2861,13 @@ void* pp_device_ptr(pp_handle h, int which, size_t* bytes)
     const size_t ns = (size_t)h->caps.max_scenes;
     void* p = nullptr; size_t b = 0;
     switch (which) {
-    case PP_BUF_SCENE_IN: p = h->d_in; b = ns * sizeof(SceneIn); break;
+    case PP_BUF_SCENE_IN: p = h->cur_in().d_in; b = ns * sizeof(SceneIn); break;
     case PP_BUF_LANE_POOL: p = h->d_lane; b = (size_t)h->caps.max_lane_pts_total * sizeof(GlobalPoint3D); break;
     case PP_BUF_REF_POOL: p = h->d_ref; b = (size_t)h->caps.max_ref_pts_total * sizeof(GlobalPoint2D); break;
-    case PP_BUF_OBS_POOL: p = h->d_obs; b = (size_t)h->caps.max_obs_total * sizeof(ObPoint); break;
-    case PP_BUF_MOT_POOL: p = h->d_mot; b = (size_t)h->caps.max_obs_total * sizeof(ObMotion); break;
+    case PP_BUF_OBS_POOL: p = h->cur_in().d_obs; b = (size_t)h->caps.max_obs_total * sizeof(ObPoint); break;
+    case PP_BUF_MOT_POOL: p = h->cur_in().d_mot; b = (size_t)h->caps.max_obs_total * sizeof(ObMotion); break;
     case PP_BUF_STATE: p = h->d_state; b = ns * sizeof(SceneState); break;
-    case PP_BUF_PLAN_OUT: p = h->d_plan; b = ns * sizeof(PlanOut); break;
+    case PP_BUF_PLAN_OUT: p = h->plan_out(); b = ns * sizeof(PlanOut); break;
     case PP_BUF_GRID_OUT: p = h->d_gout[h->gout_set]; b = ns * sizeof(GridOut); break;      // the buffers of the last tick
     case PP_BUF_GRID: p = nullptr; b = 0; break;      // no occupancy grid is kept after a tick (the search builds it in LDS): use pp_get_grid
     case PP_BUF_PATH: p = h->d_path[h->path_set]; b = ns * (size_t)h->max_path0 * 4; break;

@@ -169,10 +169,10 @@ int  pp_fetch_published_async(pp_handle h, PlanningOut* result, PlanningStatus* 
  * rollout feature: no set call retires it, and it survives pp_set_scenes / pp_set_egos / pp_set_n_scenes / pp_set_config.  A handle
  * that never arms allocates and launches nothing.
  * pp_fetch_packed_async downloads the packed records of the LAST enqueued tick (either pointer may be NULL): 1744 + 248 B per scene
- * in the place of the 6896 + 3792 B of pp_fetch_async.  Same ordering rules, same pp_wait_tick; a request joins a pp_fetch_async /
- * pp_fetch_published_async of the same tick (part by part; a part that finds no room in a pending request is queued by itself: every
- * destination a call accepted is filled).  PP_ERR_STATE: not armed; the last tick ran before arming; `grid` with the grid stage
- * off.  PP_ERR_ARG: both pointers NULL.
+ * in the place of the 6896 + 3792 B of pp_fetch_async.  Same ordering rules, same pp_wait_tick.  Several requests - of any of the
+ * three fetch calls - may name one tick: all return its id, every destination a call accepted is filled, and pp_wait_tick of that id
+ * covers all of them.  PP_ERR_STATE: not armed; the last tick ran before arming; `grid` with the grid stage off.  PP_ERR_ARG: both
+ * pointers NULL.
  * pp_unpack_plan / pp_unpack_grid: pure host code, no handle, no device, built from the kernels' own functions - they rebuild
  * PlanningOut (pnts through the WGS84 line of cfg), PlanningStatus, DecisionOutPod (each output may be NULL) and GridOut, equal in
  * every byte to what pp_fetch_async of the same tick delivers, except GridOut.cand_*[k] for k != best_candidate, which are 0.

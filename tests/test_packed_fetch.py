@@ -502,8 +502,8 @@ def test_an_unarmed_handle_computes_the_same_and_launches_no_pack_kernel(dm):
 
 @pytest.mark.gpu
 def test_requests_that_join_only_in_part_lose_no_destination(dm):
-    """Several requests for one tick, each finding only some of its parts free in the pending entry: every destination a call
-    accepted is filled (a part that finds no room becomes an entry of its own)."""
+    """Several requests for one tick, overlapping in what they ask for (the same side, the same record kind, twice): every
+    destination a call accepted is filled - each call is download records of its own, one per side, none joins another."""
     cfg, sc, pl = _small(dm, n=300, n_obs=24)
     pl.set_packed_fetch(True)
     n = pl.n
@@ -513,9 +513,9 @@ def test_requests_that_join_only_in_part_lose_no_destination(dm):
             for x in bufs:
                 x.view(np.uint8)[:] = 0xA5
         pl.tick()
-        ids = [pl.fetch_async(a[0], None), pl.fetch_packed_async(a[2], None),      # entry: plan, then its packed plan joins
-               pl.fetch_async(b[0], b[1]),                                         # grid may join, plan finds no room
-               pl.fetch_packed_async(b[2], b[3]),                                  # packed grid may join, packed plan finds no room
+        ids = [pl.fetch_async(a[0], None), pl.fetch_packed_async(a[2], None),      # plan side: PlanOut, then PackedPlan
+               pl.fetch_async(b[0], b[1]),                                         # both sides: a second PlanOut, the first GridOut
+               pl.fetch_packed_async(b[2], b[3]),                                  # both sides: a second PackedPlan, the first PackedGrid
                pl.fetch_packed_async(None, a[3]), pl.fetch_async(None, a[1])]
         assert len(set(ids)) == 1
         assert pl.wait_tick(ids[0]) == 0

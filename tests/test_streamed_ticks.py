@@ -41,10 +41,23 @@ def _mutate(sc, rng, t, n_obs, world):
     sc["scene_in"]["period_last"][:] = 90.0 + 10.0 * (t % 4)
 
 
-@pytest.mark.parametrize("n,grid,n_obs,dynamic", [(320, 128, 24, 0), (304, 512, 64, 0), (40, 128, 24, 0), (288, 128, 32, 1)])
-def test_streamed_ticks_every_tick_matches_oracle(dm, oracle, n, grid, n_obs, dynamic):
+# The ring sizes of the streamed path, as csrc/dmpp_hip.hip has them (no export gives them: when one of them grows there, T of the
+# lagging rows below has to grow past it): kDone = 32 ticks whose downloads pp_wait_tick can still name, kIn = 12 input sets,
+# kPlan = 12 PlanOut sets, kGoutRing = 4 * kBuf = 12 GridOut group positions.
+K_DONE = 32
+
+
+@pytest.mark.parametrize("n,grid,n_obs,dynamic,T,lag", [
+    pytest.param(320, 128, 24, 0, 14, None, id="320-128-24-0"), pytest.param(304, 512, 64, 0, 14, None, id="304-512-64-0"),
+    pytest.param(40, 128, 24, 0, 14, None, id="40-128-24-0"), pytest.param(288, 128, 32, 1, 14, None, id="288-128-32-1"),
+    pytest.param(300, 128, 24, 0, 45, 6, id="300-128-24-0-45-6"), pytest.param(40, 128, 24, 0, 45, 6, id="40-128-24-0-45-6")])
+def test_streamed_ticks_every_tick_matches_oracle(dm, oracle, n, grid, n_obs, dynamic, T, lag):
     """>= 12 ticks at n >= 300 (the three-stream tick) and at n = 40 (one-stream tick): new egos and obstacles every tick,
-    no pp_sync in between, every tick's PlanOut + GridOut fetched asynchronously."""
+    no pp_sync in between, every tick's PlanOut + GridOut fetched asynchronously.  lag None: every tick is waited for at the
+    end, in reverse.  lag k: tick t - k is waited for right after tick t is fetched (at most k + 1 ticks in flight) and the
+    rest at the end; 45 such ticks wrap every ring of the streamed path at least once - the wait slots (kDone), the PlanOut
+    sets (kPlan), the input sets (kIn) and the GridOut positions (kGoutRing), see K_DONE above - and the first tick's id can no
+    longer be waited for."""
     cfg = dm.default_config(grid)
     cfg["force_replan"] = 1
     cfg["dynamic_obstacles"] = dynamic
@@ -54,7 +67,6 @@ def test_streamed_ticks_every_tick_matches_oracle(dm, oracle, n, grid, n_obs, dy
     pl.set_scenes(sc, with_motion=bool(dynamic))
     pl.set_state(sc["state"])
     rng = np.random.default_rng(77)
-    T = 14
     ins, ids = [], []
     plans = [dm.pinned_empty(n, dm.PlanOut) for _ in range(T)]
     grids = [dm.pinned_empty(n, dm.GridOut) for _ in range(T)]
@@ -66,9 +78,13 @@ def test_streamed_ticks_every_tick_matches_oracle(dm, oracle, n, grid, n_obs, dy
         pl.update_async(in_t, ob_t, mo_t)
         pl.tick()
         ids.append(pl.fetch_async(plans[t], grids[t]))
+        if lag is not None and t >= lag:
+            assert pl.wait_tick(ids[t - lag]) == 0
     assert ids == list(range(ids[0], ids[0] + T))
-    for t in reversed(range(T)):                       # any order: each wait covers its own tick only
+    for t in reversed(range(T) if lag is None else range(T - lag, T)):      # any order: each wait covers its own tick only
         assert pl.wait_tick(ids[t]) == 0
+    if T > K_DONE:                                     # its wait slot has been taken by a later tick
+        assert pl.lib.pp_wait_tick(pl.h, ids[0], None) == dm.PP_ERR_ARG
     st_o = sc["state"].copy()
     for t in range(T):
         sc_t = dict(sc, scene_in=np.array(ins[t][0]), obs_pool=np.array(ins[t][1]), mot_pool=np.array(ins[t][2]) if dynamic else None)
@@ -79,6 +95,41 @@ def test_streamed_ticks_every_tick_matches_oracle(dm, oracle, n, grid, n_obs, dy
     assert not bad, "\n".join(bad[:20])
     # the synchronous getters still see the last tick
     _check_tick(pl.get_plan(), pl.get_grid_out(), plan_o, gout_o, "getters after the stream")
+    if T > K_DONE:                                     # ... and the handle still works: one more tick of the last inputs
+        pl.tick()
+        assert pl.wait_tick(pl.fetch_async(plans[0], grids[0])) == 0
+        plan_o, gout_o, _ = oracle.plan_tick_batch(cfg, sc_t, st_o, n_threads=8)
+        _check_tick(plans[0], grids[0], plan_o, gout_o, "a tick after the refused wait")
+    pl.close()
+
+
+def test_a_tick_fetched_again_after_its_wait(dm):
+    """A tick whose downloads were waited for is fetched again - in full, as published records and packed: every request
+    returns the tick's id, and a second wait delivers the same bytes as the first and as the synchronous getters."""
+    from test_packed_fetch import _assert_unpacks_to
+    n, n_obs = 40, 24
+    cfg = dm.default_config(128)
+    cfg["force_replan"] = 1
+    sc = dm.gen_scenes(cfg, 9600, n, n_obs, junction_every=8)
+    pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=n * n_obs)
+    pl.set_scenes(sc, with_motion=False)
+    pl.set_state(sc["state"])
+    pl.set_packed_fetch(True)
+    p1, g1, p2, g2 = (dm.pinned_empty(n, dt) for dt in (dm.PlanOut, dm.GridOut, dm.PlanOut, dm.GridOut))
+    res, show = dm.pinned_empty(n, dm.PlanningOut), dm.pinned_empty(n, dm.PlanningStatus)
+    pkp, pkg = dm.pinned_empty(n, dm.PackedPlan), dm.pinned_empty(n, dm.PackedGrid)
+    for a in (p1, g1, p2, g2, res, show, pkp, pkg):
+        a.view(np.uint8)[:] = 0xA5
+    pl.tick()
+    tid = pl.fetch_async(p1, g1)
+    assert pl.wait_tick(tid) == 0
+    assert [pl.fetch_async(p2, g2), pl.fetch_published_async(res, show, None), pl.fetch_packed_async(pkp, pkg)] == [tid] * 3
+    assert pl.wait_tick(tid) == 0
+    same = lambda a, b: np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+    assert same(p2, p1) and same(g2, g1), "the second full fetch"
+    assert same(p1, pl.get_plan()) and same(g1, pl.get_grid_out()), "the synchronous getters"
+    assert same(res, p1["result"]) and same(show, p1["show"]), "the published slices"
+    _assert_unpacks_to(dm, cfg, (p1, g1, pkp, pkg), "fetched again")
     pl.close()
 
 
