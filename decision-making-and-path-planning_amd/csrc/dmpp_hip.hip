@@ -500,6 +500,63 @@ void reset_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mo
                        h->treset.d_resets[h->treset.cur], d_obs, d_mot);
 }
 
+// The advance kernel of the input set an advance stages, in the place of the copy of its SceneIn records: reads the
+// records `prev` of the current set, the last tick's PlanOut and SceneState, writes d_in.  Routed egos cross junctions (§4f:
+// k_advance_route; the scenes without a route advance as in k_advance_egos).
+template <bool kTrack>
+void launch_advance(pp_planner* h, hipStream_t st, const EgoModel& ego, const SceneIn* prev, SceneIn* d_in, EgoTrace* trace, typename dmpp::AdvTrackArg<kTrack>::type trk)
+{
+    const int n = h->n_scenes;
+    const dim3 grid((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes)), block(dmpp::kBlock);
+    if (h->route.on)
+        hipLaunchKernelGGL(dmpp::k_advance_route<kTrack>, grid, block, 0, st,
+                           h->cfg, ego, h->route.rm, h->grid_follow, n, prev, d_in, h->plan_out(), h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
+                           h->route.d_legs, h->route.d_first, h->rollout.d_flags, trace, trk);
+    else
+        hipLaunchKernelGGL(dmpp::k_advance_egos<kTrack>, grid, block, 0, st,
+                           h->cfg, ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, prev, d_in, h->plan_out(), h->d_state, h->d_lane, h->rollout.d_flags, trace, trk);
+}
+// with an ego tracker the pose step is the bicycle model of DESIGN.md §4q: the <true> form of the same kernel; the episode stats
+// it reads are those the episode step of the advance BEFORE left (same stream)
+void advance_egos(pp_planner* h, hipStream_t st, const EgoModel& ego, const SceneIn* prev, SceneIn* d_in, EgoTrace* trace)
+{
+    if (h->tracker.on) launch_advance<true>(h, st, ego, prev, d_in, trace, { h->tracker.tk, h->tracker.d_state, h->episode.on ? h->episode.d_stats.get() : nullptr });
+    else launch_advance<false>(h, st, ego, prev, d_in, trace, 0);
+}
+
+// The episode step of the input set an advance stages, directly behind the advance kernel: ended egos restart from their start
+// records, so the traffic, the peers and the views behind it see the restarted ego.  P: the set the advance read.
+void step_episodes(pp_planner* h, hipStream_t st, const InputSet& P, SceneIn* d_in, EgoTrace* trace)
+{
+    const int n = h->n_scenes, cur = h->spawn.cur;
+    const dim3 grid((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), block(dmpp::kBlock);
+    const double hw = 0.5 * h->cfg.Vehicle_Width;
+    const int32_t* world_first = h->fleet.on ? h->fleet.d_world_first.get() : nullptr;
+    const int32_t* world_of = h->fleet.on ? h->fleet.d_world_of.get() : nullptr;
+    RolloutScore* score = h->score.on ? h->score.d_score.get() : nullptr;
+    if (!h->spawn.on)
+        hipLaunchKernelGGL(dmpp::k_respawn_egos, grid, block, 0, st,
+                           h->episode.em, n, P.d_in, d_in, h->d_state, h->episode.d_start_in, h->episode.d_start_state, h->rollout.d_flags, h->episode.d_stats, trace, score);
+    else if (!h->spawn.sched_on)      // the spawn model of §4l: contact ends an episode, the start record is drawn from a pool and checked for clearance
+        hipLaunchKernelGGL(dmpp::k_respawn_spawn, grid, block, 0, st,
+                           h->episode.em, h->spawn.sp, hw, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state, h->spawn.d_in[cur], h->spawn.d_state[cur],
+                           world_first, world_of, h->rollout.d_flags, h->episode.d_stats, h->spawn.d_stats[cur], trace, score);
+    else {                            // ... and a schedule over its start records (§4p): the first choice is drawn by weights
+        EpisodeScheduleRow* rows = h->spawn.d_rows;
+        hipLaunchKernelGGL(dmpp::k_respawn_sched, grid, block, 0, st,
+                           h->episode.em, h->spawn.sp, h->spawn.sched, hw, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state, h->spawn.d_in[cur],
+                           h->spawn.d_state[cur], world_first, world_of, h->rollout.d_flags, h->episode.d_stats, h->spawn.d_stats[cur], trace, score, rows, h->spawn.d_fold_word);
+        if (h->spawn.sched.scope == 1)      // the endings of this advance into the handle's one row, behind every draw
+            hipLaunchKernelGGL(dmpp::k_fold_schedule, dim3(1), dim3(dmpp::kFoldBlock), 0, st, n, h->spawn.sched.window, h->episode.d_stats, h->spawn.d_fold_word, rows);
+    }
+    if (h->elog.on) {      // one record per episode the kernel above ended, in the order of the scenes; the kernels behind it do not read it
+        hipLaunchKernelGGL(dmpp::k_log_episodes, dim3(1), dim3(dmpp::kLogBlock), 0, st,
+                           n, h->elog.cap, h->elog.seq, h->tick_seq, P.d_in, h->episode.d_stats, h->spawn.on ? h->spawn.d_stats[cur].get() : nullptr,
+                           h->elog.d_ring, h->elog.d_total, h->elog.d_start_of, h->elog.d_score);
+        h->elog.seq++;
+    }
+}
+
 // The buffers of following for the actors pp_set_traffic has just uploaded, and v = speed.  The caller has joined the chains and
 // the handle's stream is idle; traffic.cur stays.  On failure the caller switches traffic off.
 int build_follow(pp_planner* h)
@@ -1594,7 +1651,8 @@ struct StageSource {
 // staged - and puts k_advance_egos / k_advance_route in the place of the copy of the SceneIn records: the kernel reads what the
 // last tick's Planning kernel wrote (PlanOut, SceneState), so the upload stream waits for that tick's front-chain event, not for
 // its search; the next tick's front chain, the only writer of SceneState, waits for the set's `up` in turn.
-// Order on the upload stream: SceneIn records and obstacle pool -> k_move_traffic (-> k_reset_traffic, §4m) -> k_couple_fleet (the two write disjoint pool
+// Order on the upload stream ("The upload stream of one advance"): SceneIn records - an advance: advance_egos -> step_episodes - and obstacle
+// pool -> k_move_traffic / follow_traffic (-> k_reset_traffic, §4m) -> k_couple_fleet (the two write disjoint pool
 // entries: traffic a scene's own, the fleet the peer slots behind them, at the poses just staged) -> k_resolve_map ->
 // k_sanitise_scenes -> `up`, which the tick that adopts the set waits for.
 static int stage_inputs(pp_handle h, const StageSource& src)
@@ -1634,49 +1692,8 @@ static int stage_inputs(pp_handle h, const StageSource& src)
     }
     SceneIn* d_in = I.d_in; ObPoint* d_obs = I.d_obs; ObMotion* d_mot = have_motion ? I.d_mot.get() : nullptr;
     if (advance) {
-        const dim3 agrid((unsigned)((n + dmpp::kAdvScenes - 1) / dmpp::kAdvScenes));
-        // with an ego tracker the pose step is the bicycle model of DESIGN.md §4q: the <true> form of the same kernel; the episode stats
-        // it reads are those the respawn kernel of the advance BEFORE left (same stream)
-        const dmpp::AdvTrack trk = { h->tracker.tk, h->tracker.d_state, h->episode.on ? h->episode.d_stats.get() : nullptr };
-        if (h->route.on && h->tracker.on)
-            hipLaunchKernelGGL(dmpp::k_advance_route<true>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
-                               h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace, trk);
-        else if (h->route.on)             // routed egos cross junctions; the scenes without a route advance as below
-            hipLaunchKernelGGL(dmpp::k_advance_route<false>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->route.rm, h->grid_follow, n, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->d_ref, h->map_junctions, h->d_map_junc,
-                               h->route.d_legs, h->route.d_first, h->rollout.d_flags, src.trace, 0);
-        else if (h->tracker.on)
-            hipLaunchKernelGGL(dmpp::k_advance_egos<true>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->rollout.d_flags, src.trace, trk);
-        else
-            hipLaunchKernelGGL(dmpp::k_advance_egos<false>, agrid, dim3(dmpp::kBlock), 0, su,
-                               h->cfg, *src.ego, h->grid_follow, n, h->resident_mode == 1 ? 1 : 0, P.d_in, d_in, h->plan_out(), h->d_state, h->d_lane, h->rollout.d_flags, src.trace, 0);
-        if (h->episode.on && h->spawn.on && h->spawn.sched_on) {      // ... with the spawn model and a schedule over its start records (§4p): the first choice is drawn by weights
-            EpisodeScheduleRow* rows = h->spawn.d_rows;
-            hipLaunchKernelGGL(dmpp::k_respawn_sched, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
-                               h->episode.em, h->spawn.sp, h->spawn.sched, 0.5 * h->cfg.Vehicle_Width, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state,
-                               h->spawn.d_in[h->spawn.cur], h->spawn.d_state[h->spawn.cur], h->fleet.on ? h->fleet.d_world_first.get() : nullptr,
-                               h->fleet.on ? h->fleet.d_world_of.get() : nullptr, h->rollout.d_flags, h->episode.d_stats, h->spawn.d_stats[h->spawn.cur],
-                               src.trace, h->score.on ? h->score.d_score.get() : nullptr, rows, h->spawn.d_fold_word);
-            if (h->spawn.sched.scope == 1)      // the endings of this advance into the handle's one row, behind every draw
-                hipLaunchKernelGGL(dmpp::k_fold_schedule, dim3(1), dim3(dmpp::kFoldBlock), 0, su, n, h->spawn.sched.window, h->episode.d_stats, h->spawn.d_fold_word, rows);
-        } else if (h->episode.on && h->spawn.on)      // ... with the spawn model of §4l: contact ends an episode, the start record is drawn from a pool and checked for clearance
-            hipLaunchKernelGGL(dmpp::k_respawn_spawn, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
-                               h->episode.em, h->spawn.sp, 0.5 * h->cfg.Vehicle_Width, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state,
-                               h->spawn.d_in[h->spawn.cur], h->spawn.d_state[h->spawn.cur], h->fleet.on ? h->fleet.d_world_first.get() : nullptr,
-                               h->fleet.on ? h->fleet.d_world_of.get() : nullptr, h->rollout.d_flags, h->episode.d_stats, h->spawn.d_stats[h->spawn.cur],
-                               src.trace, h->score.on ? h->score.d_score.get() : nullptr);
-        else if (h->episode.on)           // ended egos restart from their start records: the traffic, the peers and the views below see the restarted ego
-            hipLaunchKernelGGL(dmpp::k_respawn_egos, dim3((unsigned)((n + dmpp::kEpScenes - 1) / dmpp::kEpScenes)), dim3(dmpp::kBlock), 0, su,
-                               h->episode.em, n, P.d_in, d_in, h->d_state, h->episode.d_start_in, h->episode.d_start_state, h->rollout.d_flags, h->episode.d_stats,
-                               src.trace, h->score.on ? h->score.d_score.get() : nullptr);
-        if (h->episode.on && h->elog.on) {      // one record per episode the kernel above ended, in the order of the scenes; the kernels below do not read it
-            hipLaunchKernelGGL(dmpp::k_log_episodes, dim3(1), dim3(dmpp::kLogBlock), 0, su,
-                               n, h->elog.cap, h->elog.seq, h->tick_seq, P.d_in, h->episode.d_stats, h->spawn.on ? h->spawn.d_stats[h->spawn.cur].get() : nullptr,
-                               h->elog.d_ring, h->elog.d_total, h->elog.d_start_of, h->elog.d_score);
-            h->elog.seq++;
-        }
+        advance_egos(h, su, *src.ego, P.d_in, d_in, src.trace);
+        if (h->episode.on) step_episodes(h, su, P, d_in, src.trace);
     }
     if (h->traffic.on) {                  // an advance moves the actors one step on - by the car-following law while that is on (§4i) -, an update places them where they are
         if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }

@@ -6,8 +6,8 @@
 // path segments ahead of k0 side by side; the sum is then taken in index order - by every lane alike, on values broadcast out
 // of the lane that holds them, so the walk is wave-uniform and its rounding is that of a scalar loop - and stops at s (a
 // handful of segments at 0.5 m spacing).  The three id searches are (value, index) wave minima that keep the first minimum
-// (wave_first_min, the reduction of GetVhclLocalState in k_planning).  The steps are device functions: the routed form of the kernel
-// (k_advance_route, kernels_rt.hpp) shares the speed, pose, id-search and grid code and replaces §4c 4. - 5. for routed scenes.
+// (wave_first_min, the reduction of GetVhclLocalState in k_planning).  The steps are device functions and adv_scene holds them in
+// §4c's order: the routed form of the kernel (k_advance_route, kernels_rt.hpp) is the same adv_scene with §4f at §4c 4. - 5.
 // Both kernels are templates on kTrack: <false> puts the ego on its path (§4c 3., adv_speed_pose), <true> - a handle with an
 // EgoTracker - moves it as a kinematic bicycle that chases the path (§4q, adv_speed_pose_tracked) and keeps one EgoTrackState per
 // scene.  The two pose steps share the speed step (adv_speed) and the arc walk (adv_walk).
@@ -323,6 +323,8 @@ __device__ __forceinline__ void adv_store_trace(EgoTrace* __restrict__ trace, in
         trace[s] = t;
     }
 }
+// §4c 4.: the search window from id idc reaches the end of the current view
+__device__ __forceinline__ bool adv_lane_ends(const LaneView& lv, int idc, int window) { return (long long)idc + window >= (long long)lv.cur_n; }
 // §4c 4. - 5. for a scene that follows no route: ids, LANE_END, lane number
 __device__ __forceinline__ void adv_lane_step(const GlobalPoint3D* __restrict__ lane_pool, const LaneView& lv, int ln, int window, int map_mode,
                                               double x, double y, int lane, int& w, int& f, int& ln_new)
@@ -330,7 +332,7 @@ __device__ __forceinline__ void adv_lane_step(const GlobalPoint3D* __restrict__ 
     const AdvIds r = adv_search_ids(lane_pool, lv, ln, window, x, y, lane, w);
     if (r.has_c) {
         const int idc = r.ic >= 0 ? r.ic : adv_get_id(w, ln - 1);
-        if ((long long)idc + window >= (long long)lv.cur_n) f |= DMPP_EGO_LANE_END;
+        if (adv_lane_ends(lv, idc, window)) f |= DMPP_EGO_LANE_END;
     }
     adv_store_ids(w, lane, ln, r);
     // 5. lane number: only on a resident map, where k_resolve_map derives the new views
@@ -340,12 +342,13 @@ __device__ __forceinline__ void adv_lane_step(const GlobalPoint3D* __restrict__ 
     }
 }
 
-// kTrack: the pose step is §4q's (a handle with an EgoTracker); <false> is the kernel of a handle without one and takes one unused word
-template <bool kTrack>
-__global__ void __launch_bounds__(kBlock)
-k_advance_egos(PlannerConfig c, EgoModel m, GridFollow gf, int n_scenes, int map_mode, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
-               const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const GlobalPoint3D* __restrict__ lane_pool,
-               int32_t* __restrict__ flags, EgoTrace* __restrict__ trace, typename AdvTrackArg<kTrack>::type trk)
+// One scene of an advance, §4c from the record load to the flag word: the frame k_advance_egos and k_advance_route share.  step(s, si,
+// ln, p, lane, w, f, ln_new) is what stands at §4c 4. - 5.: ids, LANE_END and lane number at the new pose p.  kTrack: the pose step is
+// §4q's (a handle with an EgoTracker); <false> is the kernel of a handle without one and takes one unused word.
+template <bool kTrack, class Step>
+__device__ __forceinline__ void adv_scene(const PlannerConfig& c, const EgoModel& m, const GridFollow& gf, int n_scenes, const SceneIn* __restrict__ in,
+                                          SceneIn* __restrict__ out, const PlanOut* __restrict__ plan, const SceneState* __restrict__ state,
+                                          int32_t* __restrict__ flags, EgoTrace* __restrict__ trace, const typename AdvTrackArg<kTrack>::type& trk, Step step)
 {
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * kAdvScenes + (threadIdx.x >> 6);
@@ -363,7 +366,7 @@ k_advance_egos(PlannerConfig c, EgoModel m, GridFollow gf, int n_scenes, int map
         else {
             if (p.path_end) f |= DMPP_EGO_PATH_END;
             adv_store_pose(w, lane, p);
-            adv_lane_step(lane_pool, si.lanes, ln, m.window, map_mode, p.x, p.y, lane, w, f, ln_new);
+            step(s, si, ln, p, lane, w, f, ln_new);
             if (gf.goal_point > 0 ? adv_follow_grid(c, gf, si, plan[s], p.x, p.y, lane, w) : (c.grid_stage && adv_off_grid(c, si, p.x, p.y)))
                 f |= DMPP_EGO_OFF_GRID;
         }
@@ -371,6 +374,18 @@ k_advance_egos(PlannerConfig c, EgoModel m, GridFollow gf, int n_scenes, int map
     if (lane < kSiWords) reinterpret_cast<int*>(&out[s])[lane] = w;
     if (trace) adv_store_trace(trace, s, lane, w, ln_new, f);
     if (lane == 0) flags[s] = f;
+}
+
+template <bool kTrack>
+__global__ void __launch_bounds__(kBlock)
+k_advance_egos(PlannerConfig c, EgoModel m, GridFollow gf, int n_scenes, int map_mode, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
+               const PlanOut* __restrict__ plan, const SceneState* __restrict__ state, const GlobalPoint3D* __restrict__ lane_pool,
+               int32_t* __restrict__ flags, EgoTrace* __restrict__ trace, typename AdvTrackArg<kTrack>::type trk)
+{
+    adv_scene<kTrack>(c, m, gf, n_scenes, in, out, plan, state, flags, trace, trk,
+                      [&](int, const SceneIn& si, int ln, const AdvPose& p, int lane, int& w, int& f, int& ln_new) {
+                          adv_lane_step(lane_pool, si.lanes, ln, m.window, map_mode, p.x, p.y, lane, w, f, ln_new);
+                      });
 }
 
 // h_bad slot reset in stream order (pp_update_async on top of an update already staged: see the owner rule there)

@@ -57,36 +57,27 @@ __device__ __forceinline__ bool wave_world_within(const SceneIn* __restrict__ pr
     return false;
 }
 
-// What steps 1 - 2 of §4l leave for the steps behind them: the flag word, the age and the metres of the ending episode, its cause word
-// and the scene's slice of the pool the advance read.
-struct SpawnEnd { int f, age, c, on; double dist; const ObPoint* slice; };
+// What steps 1 - 2 of §4l leave for the steps behind them: what §4k's leave (EpisodeEnd; c with CONTACT on top) and the scene's slice
+// of the pool the advance read.
+struct SpawnEnd : EpisodeEnd { int on; const ObPoint* slice; };
 
 // The steps of §4l as device functions: k_respawn_spawn and k_respawn_sched (kernels_ev.hpp, §4p) are made of the same ones, and differ
-// in how k0 is drawn.  (The pointers are the kernels' own __restrict__ arguments.  The test E.c == 0 and the early return stay in the
-// kernel: folded into a function that also stores, the compiler merges the uniform test with the lane test into one divergent branch.)
+// in how k0 is drawn.  Steps 1., 2., 3., 5. and 6. are §4k's and live in kernels_ep.hpp (episode_age_dist, episode_cause / episode_go_on,
+// episode_close, episode_start_words); 1a. and 3a. are here.
 // §4l 1., 1a., 2.: age and distance of the running episode, contact, cause word
 __device__ __forceinline__ void spawn_episode_end(const EpisodeModel& em, const EpisodeSpawn& sp, double hw, int s, int lane, const SceneIn* prev, const ObPoint* obs,
                                                   int n_obs, const SceneIn* staged, const int32_t* flags, const EpisodeStats* stats, SpawnEnd& E)
 {
-    // 1. age and distance of the running episode
     E.f = flags[s];
-    E.age = stats[s].age + 1;
     const double px = prev[s].loc.globalpoint.x, py = prev[s].loc.globalpoint.y;
-    const double ex = staged[s].loc.globalpoint.x - px, ey = staged[s].loc.globalpoint.y - py;
-    E.dist = stats[s].dist + sqrt(ex * ex + ey * ey);
+    episode_age_dist(stats[s], px, py, staged[s].loc.globalpoint.x, staged[s].loc.globalpoint.y, E);
     // the slice of the record the advance read (a sanitised record: inside the pool; anything else is taken as empty)
     int off = prev[s].obs_off, on = prev[s].obs_n;
     if (on <= 0 || off < 0 || (long long)off + on > (long long)n_obs) { off = 0; on = 0; }
     E.slice = obs + off; E.on = on;
     // 1a. contact
     const bool touch = sp.contact != 0 && wave_slice_within(E.slice, on, px, py, hw, 0.0, lane);
-    // 2. cause word
-    E.c = (E.f & em.end_mask) | ((em.max_ticks > 0 && E.age >= em.max_ticks) ? DMPP_EGO_TIMEOUT : 0) | (touch ? DMPP_EGO_CONTACT : 0);
-}
-// §4l 2., cause word 0: a scene that goes on costs lane 0 two stores
-__device__ __forceinline__ void spawn_go_on(int s, int lane, const SpawnEnd& E, EpisodeStats* stats)
-{
-    if (lane == 0) { stats[s].age = E.age; stats[s].dist = E.dist; }
+    E.c = episode_cause(em, E.f, E.age) | (touch ? DMPP_EGO_CONTACT : 0);
 }
 
 // §4l 3a.: the hash of scene s for its e-th ended episode
@@ -96,13 +87,12 @@ __device__ __forceinline__ unsigned long long spawn_hash(const EpisodeSpawn& sp,
 }
 
 // §4l 3a. from k0 on, 3. - 6.: the clearance walk, the restart onto the record it took, stats, trace and scorecard words (lane 0)
-__device__ __forceinline__ void spawn_restart(const EpisodeSpawn& sp, double hw, int s, int lane, int stride, int k0, int e, const SpawnEnd& E,
+__device__ __forceinline__ void spawn_restart(const EpisodeSpawn& sp, double hw, int s, int lane, int stride, int k0, const SpawnEnd& E,
                                               const SceneIn* prev, SceneIn* staged, SceneState* state, const SceneIn* pool_in, const SceneState* pool_state,
                                               const int32_t* world_first, const int32_t* world_of, int32_t* flags,
                                               EpisodeStats* stats, EpisodeSpawnStats* sstats, EgoTrace* trace, RolloutScore* score)
 {
-    const int M = sp.n_starts, c = E.c, age = E.age;
-    const double dist = E.dist;
+    const int M = sp.n_starts;
     int p0 = 0, p1 = 0;
     if ((sp.check & 2) && world_of) { const int w = world_of[s]; p0 = world_first[w]; p1 = world_first[w + 1]; }
     int k = k0, rejected = M, blocked = 1;
@@ -119,33 +109,13 @@ __device__ __forceinline__ void spawn_restart(const EpisodeSpawn& sp, double hw,
     wave_copy_record(&staged[s], &start_in[s], lane);
     wave_copy_record(&state[s], &pool_state[(size_t)k * stride + s], lane);
     if (lane != 0) return;
-    // 3. stats
-    EpisodeStats S0 = stats[s];
-    S0.n_episodes = e;
-    for (int b = 0; b < 5; b++) if (c & (1 << b)) S0.n_end[b] = S0.n_end[b] + 1;
-    if (c & DMPP_EGO_TIMEOUT) S0.n_end[5] = S0.n_end[5] + 1;
-    S0.last_cause = c; S0.last_age = age;
-    if (S0.min_age < 0 || age < S0.min_age) S0.min_age = age;
-    if (S0.max_age < 0 || age > S0.max_age) S0.max_age = age;
-    S0.ticks_total = S0.ticks_total + (int64_t)age;
-    S0.last_dist = dist; S0.dist_total = S0.dist_total + dist;
-    S0.age = 0; S0.dist = 0;
-    stats[s] = S0;
+    episode_close(stats[s], E);
     flags[s] = 0;
     EpisodeSpawnStats& S = sstats[s];
-    if (c & DMPP_EGO_CONTACT) S.n_contact = S.n_contact + 1;
+    if (E.c & DMPP_EGO_CONTACT) S.n_contact = S.n_contact + 1;
     S.n_blocked = S.n_blocked + blocked; S.n_rejected = S.n_rejected + rejected;
     S.cur_start = k; S.n_used[k] = S.n_used[k] + 1;
-    // 5. trace of the start record   6. the scorecard's last ego is the one of the start record
-    const LocationOut& L = start_in[s].loc;
-    if (trace) {
-        EgoTrace t;
-        t.pose = L.globalpoint; t.velocity = L.velocity;
-        t.id_cur = L.id[clampi(L.lane_num - 1, 0, DMPP_LANESUM - 1)]; t.lane_num = L.lane_num;
-        t.flags = E.f | DMPP_EGO_RESPAWNED | (c & (DMPP_EGO_TIMEOUT | DMPP_EGO_CONTACT)); t._pad = 0;
-        trace[s] = t;
-    }
-    if (score) { score[s].last_pos.x = L.globalpoint.x; score[s].last_pos.y = L.globalpoint.y; score[s].last_speed = L.velocity; }
+    episode_start_words(start_in[s].loc, E, s, trace, score);
 }
 
 // prev / obs: the SceneIn records and the obstacle pool (n_obs entries) of the input set the advance read; staged, state, flags, stats,
@@ -162,14 +132,14 @@ k_respawn_spawn(EpisodeModel em, EpisodeSpawn sp, double hw, int n_scenes, int s
     if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
     SpawnEnd E;
     spawn_episode_end(em, sp, hw, s, lane, prev, obs, n_obs, staged, flags, stats, E);
-    if (E.c == 0) { spawn_go_on(s, lane, E, stats); return; }
+    if (E.c == 0) { episode_go_on(s, lane, E, stats); return; }
     // 3a. start record
     const int M = sp.n_starts;
     const int e = stats[s].n_episodes + 1;
     int k0;
     if (sp.order == 0) k0 = (int)(((spawn_hash(sp, s, e) >> 32) * (unsigned long long)M) >> 32);
     else k0 = e % M;
-    spawn_restart(sp, hw, s, lane, stride, k0, e, E, prev, staged, state, pool_in, pool_state, world_first, world_of, flags, stats, sstats, trace, score);
+    spawn_restart(sp, hw, s, lane, stride, k0, E, prev, staged, state, pool_in, pool_state, world_first, world_of, flags, stats, sstats, trace, score);
 }
 
 // obs_off / obs_n of start records 1 .. M - 1 become those of the scene's record 0 (one thread per record)

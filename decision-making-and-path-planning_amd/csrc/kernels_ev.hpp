@@ -1,7 +1,8 @@
 // kernels_ev.hpp — scenario schedule (build-defined): while pp_set_episode_schedule is in force, k_respawn_sched runs in
 // the place of k_respawn_spawn - same point of the upload stream, same shape: one 64-lane wave per scene, four scenes per 256-thread
 // block, wave-uniform scene index, no LDS, no barrier - and draws the first choice k0 of §4l 3a. by weights computed from outcome
-// counts per start record.  Every other step is the device function k_respawn_spawn calls (kernels_es.hpp): one copy of each.
+// counts per start record.  Every other step is the device function k_respawn_spawn calls, one copy of each: contact, the clearance
+// walk and the restart in kernels_es.hpp (spawn_episode_end, spawn_restart), the steps of §4k under them in kernels_ep.hpp.
 //
 // Integers only.  Lane k < M computes the weight of record k from its two counts (one 64-bit division per lane, side by side); the sum
 // and the running sum are at most 16 scalar iterations each over v_readlane.  Every draw of a launch reads the rows as the launch
@@ -48,7 +49,7 @@ k_respawn_sched(EpisodeModel em, EpisodeSpawn sp, EpisodeSchedule sm, double hw,
     if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
     SpawnEnd E;
     spawn_episode_end(em, sp, hw, s, lane, prev, obs, n_obs, staged, flags, stats, E);
-    if (E.c == 0) { spawn_go_on(s, lane, E, stats); return; }
+    if (E.c == 0) { episode_go_on(s, lane, E, stats); return; }
     // §4p 1. weights: lane k holds w_k
     const int M = sp.n_starts;
     const int e = stats[s].n_episodes + 1;
@@ -66,7 +67,7 @@ k_respawn_sched(EpisodeModel em, EpisodeSpawn sp, EpisodeSchedule sm, double hw,
         if (run > t) { k0 = k; break; }
     }
     const int k_prev = sstats[s].cur_start & (DMPP_EPISODE_MAX_STARTS - 1);      // the record the ENDED episode ran on (written by this kernel: 0 .. M - 1)
-    spawn_restart(sp, hw, s, lane, stride, k0, e, E, prev, staged, state, pool_in, pool_state, world_first, world_of, flags, stats, sstats, trace, score);
+    spawn_restart(sp, hw, s, lane, stride, k0, E, prev, staged, state, pool_in, pool_state, world_first, world_of, flags, stats, sstats, trace, score);
     if (lane != 0) return;
     // §4p 4. fold: the scene's own row here, the handle's row in k_fold_schedule
     const int fail = schedule_fails(sm, E.c);

@@ -1,6 +1,6 @@
 // kernels_rt.hpp — route following: k_advance_route is k_advance_egos for a handle with routes set (build-defined: the
-// simulated localisation module of a rollout).  Speed, pose, the id searches and the grid test are the device functions of
-// kernels_a.hpp; a scene that follows no route takes §4c 4. - 5. through them unchanged.  For a routed scene §4f stands in the place
+// simulated localisation module of a rollout).  The frame - record load, pose, grid test, stores - is adv_scene of kernels_a.hpp, the
+// id searches its device functions; a scene that follows no route takes §4c 4. - 5. through them unchanged.  For a routed scene §4f stands in the place
 // of those two steps: the ego goes road -> pre-junction (pos 1) -> junction (pos 2) -> next road (pos 0) on the junction table and
 // the polylines of the resident map.
 //
@@ -37,6 +37,80 @@ __device__ __forceinline__ int wave_find_junction(const MapJunction* __restrict_
 
 __device__ __forceinline__ void rt_zero_ids(int& w, int lane) { if (lane >= kIdWord && lane < kIdWord + DMPP_LANESUM) w = 0; }
 
+// §4f in the place of §4c 4. - 5. for one scene at its new pose p (a scene that follows no route takes those two steps unchanged)
+__device__ __forceinline__ void rt_route_step(const RouteModel& rm, int window, int s, const SceneIn& si, int ln, const AdvPose& p,
+                                              const GlobalPoint3D* __restrict__ lane_pool, const GlobalPoint2D* __restrict__ ref_pool, int n_junctions,
+                                              const MapJunction* __restrict__ junctions, const RouteLeg* __restrict__ legs, const int32_t* __restrict__ route_first,
+                                              int lane, int& w, int& f, int& ln_new)
+{
+    const int pos = si.loc.pos, leg = si.loc.path_num;
+    const int r0 = route_first[s], n_legs = route_first[s + 1] - r0;
+    const bool routed = n_legs > 0 && leg >= 0 && leg < n_legs && pos >= 0 && pos <= 2;
+    if (!routed) adv_lane_step(lane_pool, si.lanes, ln, window, 1, p.x, p.y, lane, w, f, ln_new);       // (routes live on a resident map)
+    else if (pos != 2) {
+        // ---- on a lane: ids as §4c 4.; the lane number as §4c 5. on the road, held in the pre-junction ----
+        const LaneView& lv = si.lanes;
+        const AdvIds r = adv_search_ids(lane_pool, lv, ln, window, p.x, p.y, lane, w);
+        adv_store_ids(w, lane, ln, r);
+        if (pos == 0 && r.ic >= 0) {
+            ln_new = adv_lane_number(lv, ln, r);
+            if (lane == kLaneNumWord) w = ln_new;
+        }
+        if (r.has_c) {
+            const int idc = r.ic >= 0 ? r.ic : adv_get_id(w, ln - 1);
+            const bool has_next = leg + 1 < n_legs;
+            int next_road = 0, jn = -1, jn_next_lane = 0;
+            if (has_next && !(pos == 1 && si.ref_n <= 0)) {
+                next_road = legs[r0 + leg + 1].road_num;
+                jn = wave_find_junction(junctions, n_junctions, si.loc.road_num, next_road, ln_new, lane);
+                if (jn >= 0) jn_next_lane = junctions[jn].next_lane;
+            }
+            if (adv_lane_ends(lv, idc, window)) {
+                if (!has_next) f |= DMPP_EGO_LANE_END | DMPP_EGO_ROUTE_END;       // the last leg: arrived
+                else if (jn < 0) f |= DMPP_EGO_LANE_END;                          // missed its exit lane
+            }
+            if (pos == 0 && jn >= 0 && (long long)lv.cur_n - 1 - idc <= (long long)rm.pre_points) {      // 0 -> 1
+                if (lane == kPosWord) w = 1;
+                if (lane == kLastRoadWord) w = si.loc.road_num;
+                if (lane == kNextRoadWord) w = next_road;
+                if (lane == kLastLaneWord) w = ln_new;
+                if (lane == kNextLaneWord) w = jn_next_lane;
+            }
+            if (pos == 1 && idc == lv.cur_n - 1 && si.ref_n > 0) {                                         // 1 -> 2
+                double d2; int jid;
+                wave_view_nearest(ref_pool + si.ref_off, si.ref_n, 0, window, p.x, p.y, lane, d2, jid);
+                rt_zero_ids(w, lane);
+                adv_set_id(w, lane, clampi(si.loc.last_lanenum - 1, 0, DMPP_LANESUM - 1), jid >= 0 ? jid : 0);
+                ln_new = si.loc.next_lanenum;
+                if (lane == kPosWord) w = 2;
+                if (lane == kRoadWord) w = si.loc.next_roadnum;
+                if (lane == kLaneNumWord) w = ln_new;
+            }
+        }
+    } else {
+        // ---- in the junction: the id of the polyline; no lane ids, no lane-end test, the lane number is held ----
+        const int slot = clampi(si.loc.last_lanenum - 1, 0, DMPP_LANESUM - 1);
+        const int j = adv_get_id(w, slot);
+        double d2; int jid;
+        wave_view_nearest(ref_pool + si.ref_off, si.ref_n, j, window, p.x, p.y, lane, d2, jid);
+        const int jn = jid >= 0 ? jid : j;
+        adv_set_id(w, lane, slot, jn);
+        if (jn >= si.ref_n - 1) {                                                                          // 2 -> 0
+            if (leg + 1 >= n_legs) f |= DMPP_EGO_ROUTE_END;       // (a caller error: a junction behind the last leg; everything is held)
+            else {
+                const int* __restrict__ L = reinterpret_cast<const int*>(&legs[r0 + leg + 1]);
+                if (lane == kPosWord) w = 0;
+                if (lane == kPathNumWord) w = leg + 1;
+                if (lane == kStubWord) w = L[1];
+                if (lane >= kOutLaneWord && lane < kOutLaneWord + kOutLaneWords) w = L[2 + lane - kOutLaneWord];
+                rt_zero_ids(w, lane);
+                const AdvIds r = adv_search_ids(lane_pool, si.lanes, ln, window, p.x, p.y, lane, w);     // (the views are those of the new road)
+                adv_store_ids(w, lane, ln, r);
+            }
+        }
+    }
+}
+
 template <bool kTrack>
 __global__ void __launch_bounds__(kBlock)
 k_advance_route(PlannerConfig c, EgoModel m, RouteModel rm, GridFollow gf, int n_scenes, const SceneIn* __restrict__ in, SceneIn* __restrict__ out,
@@ -45,96 +119,10 @@ k_advance_route(PlannerConfig c, EgoModel m, RouteModel rm, GridFollow gf, int n
                 const RouteLeg* __restrict__ legs, const int32_t* __restrict__ route_first, int32_t* __restrict__ flags, EgoTrace* __restrict__ trace,
                 typename AdvTrackArg<kTrack>::type trk)
 {
-    const int lane = threadIdx.x & 63;
-    const int s = blockIdx.x * kAdvScenes + (threadIdx.x >> 6);
-    if (s >= n_scenes) return;                          // (whole waves leave: no barrier below)
-    const SceneIn& si = in[s];
-    int w = lane < kSiWords ? reinterpret_cast<const int*>(&si)[lane] : 0;
-    const int f_in = flags[s];
-    const int ln = si.loc.lane_num;
-    int f = f_in, ln_new = ln;
-    if (f_in == 0) {
-        AdvPose p;
-        if constexpr (kTrack) p = adv_speed_pose_tracked(c, m, trk, si, plan[s], state[s], s, lane);
-        else p = adv_speed_pose(c, m, si, plan[s], state[s], lane);
-        if (p.bad) f |= DMPP_EGO_BAD_PATH;
-        else {
-            if (p.path_end) f |= DMPP_EGO_PATH_END;
-            adv_store_pose(w, lane, p);
-            const int window = m.window;
-            const int pos = si.loc.pos, leg = si.loc.path_num;
-            const int r0 = route_first[s], n_legs = route_first[s + 1] - r0;
-            const bool routed = n_legs > 0 && leg >= 0 && leg < n_legs && pos >= 0 && pos <= 2;
-            if (!routed) adv_lane_step(lane_pool, si.lanes, ln, window, 1, p.x, p.y, lane, w, f, ln_new);       // (routes live on a resident map)
-            else if (pos != 2) {
-                // ---- on a lane: ids as §4c 4.; the lane number as §4c 5. on the road, held in the pre-junction ----
-                const LaneView& lv = si.lanes;
-                const AdvIds r = adv_search_ids(lane_pool, lv, ln, window, p.x, p.y, lane, w);
-                adv_store_ids(w, lane, ln, r);
-                if (pos == 0 && r.ic >= 0) {
-                    ln_new = adv_lane_number(lv, ln, r);
-                    if (lane == kLaneNumWord) w = ln_new;
-                }
-                if (r.has_c) {
-                    const int idc = r.ic >= 0 ? r.ic : adv_get_id(w, ln - 1);
-                    const bool has_next = leg + 1 < n_legs;
-                    int next_road = 0, jn = -1, jn_next_lane = 0;
-                    if (has_next && !(pos == 1 && si.ref_n <= 0)) {
-                        next_road = legs[r0 + leg + 1].road_num;
-                        jn = wave_find_junction(junctions, n_junctions, si.loc.road_num, next_road, ln_new, lane);
-                        if (jn >= 0) jn_next_lane = junctions[jn].next_lane;
-                    }
-                    if ((long long)idc + window >= (long long)lv.cur_n) {
-                        if (!has_next) f |= DMPP_EGO_LANE_END | DMPP_EGO_ROUTE_END;       // the last leg: arrived
-                        else if (jn < 0) f |= DMPP_EGO_LANE_END;                          // missed its exit lane
-                    }
-                    if (pos == 0 && jn >= 0 && (long long)lv.cur_n - 1 - idc <= (long long)rm.pre_points) {      // 0 -> 1
-                        if (lane == kPosWord) w = 1;
-                        if (lane == kLastRoadWord) w = si.loc.road_num;
-                        if (lane == kNextRoadWord) w = next_road;
-                        if (lane == kLastLaneWord) w = ln_new;
-                        if (lane == kNextLaneWord) w = jn_next_lane;
-                    }
-                    if (pos == 1 && idc == lv.cur_n - 1 && si.ref_n > 0) {                                         // 1 -> 2
-                        double d2; int jid;
-                        wave_view_nearest(ref_pool + si.ref_off, si.ref_n, 0, window, p.x, p.y, lane, d2, jid);
-                        rt_zero_ids(w, lane);
-                        adv_set_id(w, lane, clampi(si.loc.last_lanenum - 1, 0, DMPP_LANESUM - 1), jid >= 0 ? jid : 0);
-                        ln_new = si.loc.next_lanenum;
-                        if (lane == kPosWord) w = 2;
-                        if (lane == kRoadWord) w = si.loc.next_roadnum;
-                        if (lane == kLaneNumWord) w = ln_new;
-                    }
-                }
-            } else {
-                // ---- in the junction: the id of the polyline; no lane ids, no lane-end test, the lane number is held ----
-                const int slot = clampi(si.loc.last_lanenum - 1, 0, DMPP_LANESUM - 1);
-                const int j = adv_get_id(w, slot);
-                double d2; int jid;
-                wave_view_nearest(ref_pool + si.ref_off, si.ref_n, j, window, p.x, p.y, lane, d2, jid);
-                const int jn = jid >= 0 ? jid : j;
-                adv_set_id(w, lane, slot, jn);
-                if (jn >= si.ref_n - 1) {                                                                          // 2 -> 0
-                    if (leg + 1 >= n_legs) f |= DMPP_EGO_ROUTE_END;       // (a caller error: a junction behind the last leg; everything is held)
-                    else {
-                        const int* __restrict__ L = reinterpret_cast<const int*>(&legs[r0 + leg + 1]);
-                        if (lane == kPosWord) w = 0;
-                        if (lane == kPathNumWord) w = leg + 1;
-                        if (lane == kStubWord) w = L[1];
-                        if (lane >= kOutLaneWord && lane < kOutLaneWord + kOutLaneWords) w = L[2 + lane - kOutLaneWord];
-                        rt_zero_ids(w, lane);
-                        const AdvIds r = adv_search_ids(lane_pool, si.lanes, ln, window, p.x, p.y, lane, w);     // (the views are those of the new road)
-                        adv_store_ids(w, lane, ln, r);
-                    }
-                }
-            }
-            if (gf.goal_point > 0 ? adv_follow_grid(c, gf, si, plan[s], p.x, p.y, lane, w) : (c.grid_stage && adv_off_grid(c, si, p.x, p.y)))
-                f |= DMPP_EGO_OFF_GRID;
-        }
-    }
-    if (lane < kSiWords) reinterpret_cast<int*>(&out[s])[lane] = w;
-    if (trace) adv_store_trace(trace, s, lane, w, ln_new, f);
-    if (lane == 0) flags[s] = f;
+    adv_scene<kTrack>(c, m, gf, n_scenes, in, out, plan, state, flags, trace, trk,
+                      [&](int s, const SceneIn& si, int ln, const AdvPose& p, int lane, int& w, int& f, int& ln_new) {
+                          rt_route_step(rm, m.window, s, si, ln, p, lane_pool, ref_pool, n_junctions, junctions, legs, route_first, lane, w, f, ln_new);
+                      });
 }
 
 }  // namespace dmpp

@@ -185,7 +185,31 @@ def batched(log, sizes_wanted=(5, 7)):
                 cases.append(group[k % len(group)])
                 k += 1
             sizes.append(_batch(cases))
+    sizes.append(_batch(routed_calls()))
     return sizes
+
+
+def routed_calls():
+    """Five routed one-scene calls on the device (k_advance_route<true>), each held against the model by the Runner, as one more
+    input of batched(): the inputs of the known answers of tests/test_route.py with the ego ON the start of its path, heading along
+    it - road -> pre-junction, pre-junction -> junction, junction -> next road, arrival on the last leg, a missed exit lane."""
+    import test_route as tr
+    m, tk, log = tr._tiny_map(dm), dm.default_ego_tracker(), []
+    tk["curv_bias"] = 0.04
+    cfg = dm.default_config(128)
+    cfg["grid_stage"] = 0
+    in_junction = tr._ego(dm, m, pos=2, road=2, lane=1, ego_id=0, four=(1, 2, 2, 1))
+    in_junction["loc"]["id"][0, 1] = 6
+    calls = [(tr._ego(dm, m), 118.5, 0.0, 2, (1, 0)), (tr._ego(dm, m, pos=1, ego_id=90, four=(1, 2, 2, 1)), 149.5, 0.0, 2, (2, 0)), (in_junction, 154.6, 0.0, 2, (0, 0)),
+             (tr._ego(dm, m, ego_id=60), 133.0, 0.0, 1, (0, ab.em.LANE_END | ab.rmod.ROUTE_END)), (tr._ego(dm, m, lane=1, ego_id=60), 133.0, 3.75, 2, (0, ab.em.LANE_END))]
+    run = Runner("device", tk, log)
+    for si, x0, y, n_legs, want in calls:
+        g = si["loc"]["globalpoint"]
+        g["x"], g["y"], g["dir"] = x0, y, 0.0
+        legs = tr._legs(dm, n_legs)
+        r = run(cfg, dm.default_ego_model(), si, [(tr._path(dm, x0, y), np.zeros(1, dm.SceneState))], dict(map=m), (legs, np.array([0, len(legs)], np.int32), dm.default_route_model()))[0]
+        assert (int(r.out["loc"]["pos"][0]), int(r.flags[0])) == want, f"routed call from x = {x0}: pos, flags"
+    return log
 
 
 def _batch(cases):

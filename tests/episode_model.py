@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 PATH_END, BAD_PATH, LANE_END, OFF_GRID, ROUTE_END = 1, 2, 4, 8, 16
-RESPAWNED, TIMEOUT = 32, 64
+RESPAWNED, TIMEOUT, CONTACT = 32, 64, 128
 ALL_FLAGS = 31
 LANESUM = 8
 
@@ -36,22 +36,20 @@ def trace_record(dtype, rec, flags):
     return t
 
 
-def step_scene(em, e, start_in, start_state, p, q, flag, state, trace=None, k=0, score=None):
-    """One scene, one advance.  e: its EpisodeStats record, score: its RolloutScore record or None (numpy voids that write
-    through); trace: the EgoTrace array of the advance or None, k the scene's index in it.  Returns (staged SceneIn record,
-    SceneState record, flag word, cause word)."""
-    end_mask, max_ticks = int(em["end_mask"][0]), int(em["max_ticks"][0])
-    # 1.
-    age = int(e["age"]) + 1
+def age_dist(e, p, q):
+    """§4k 1.: age and distance of the running episode of stats record e; p the record the advance read, q the one it staged."""
     ex = float(q["loc"]["globalpoint"]["x"]) - float(p["loc"]["globalpoint"]["x"])
     ey = float(q["loc"]["globalpoint"]["y"]) - float(p["loc"]["globalpoint"]["y"])
-    dist = float(e["dist"]) + math.sqrt(ex * ex + ey * ey)
-    # 2.
-    c = cause(flag, age, end_mask, max_ticks)
-    if c == 0:
-        e["age"], e["dist"] = age, dist
-        return q, state, int(flag), 0
-    # 3.
+    return int(e["age"]) + 1, float(e["dist"]) + math.sqrt(ex * ex + ey * ey)
+
+
+def go_on(e, age, dist):
+    """§4k 2., cause word 0: the episode goes on."""
+    e["age"], e["dist"] = age, dist
+
+
+def close(e, c, age, dist):
+    """§4k 3.: the running episode is closed in the stats record e with cause word c."""
     e["n_episodes"] += 1
     for b in range(5):
         if c & (1 << b):
@@ -67,13 +65,31 @@ def step_scene(em, e, start_in, start_state, p, q, flag, state, trace=None, k=0,
     e["last_dist"] = dist
     e["dist_total"] = float(e["dist_total"]) + dist
     e["age"], e["dist"] = 0, 0.0
-    # 5.
+
+
+def start_words(start_in, flag, c, trace=None, k=0, score=None):
+    """§4k 5. - 6.: the trace record (record k of `trace`) and the scorecard words of a restart onto start_in.  CONTACT is §4l's cause
+    bit: §4k's cause word never holds it (end_mask lies inside 31)."""
     if trace is not None:
-        trace[k] = trace_record(trace.dtype, start_in, int(flag) | RESPAWNED | (c & TIMEOUT))
-    # 6.
+        trace[k] = trace_record(trace.dtype, start_in, int(flag) | RESPAWNED | (c & (TIMEOUT | CONTACT)))
     if score is not None:
         score["last_pos"]["x"], score["last_pos"]["y"] = start_in["loc"]["globalpoint"]["x"], start_in["loc"]["globalpoint"]["y"]
         score["last_speed"] = start_in["loc"]["velocity"]
+
+
+def step_scene(em, e, start_in, start_state, p, q, flag, state, trace=None, k=0, score=None):
+    """One scene, one advance.  e: its EpisodeStats record, score: its RolloutScore record or None (numpy voids that write
+    through); trace: the EgoTrace array of the advance or None, k the scene's index in it.  Returns (staged SceneIn record,
+    SceneState record, flag word, cause word)."""
+    # 1. 2.
+    age, dist = age_dist(e, p, q)
+    c = cause(flag, age, int(em["end_mask"][0]), int(em["max_ticks"][0]))
+    if c == 0:
+        go_on(e, age, dist)
+        return q, state, int(flag), 0
+    # 3. 5. 6.
+    close(e, c, age, dist)
+    start_words(start_in, flag, c, trace, k, score)
     # 4.
     return start_in, start_state, 0, c
 

@@ -12,7 +12,7 @@ import numpy as np
 
 import episode_model as epm
 
-CONTACT = 128
+CONTACT = epm.CONTACT
 MAX_STARTS = 16
 _M64 = (1 << 64) - 1
 
@@ -61,38 +61,21 @@ def step_scene(em, sp, s, e, se, pool_in, pool_state, p, q, flag, state, O, hw, 
     """One scene, one advance.  e / se: its EpisodeStats / EpisodeSpawnStats records (numpy voids that write through); p: the whole
     SceneIn array the advance read (the world test reads the other scenes of it); q, state: the scene's staged record and state;
     members: the scenes of its world or None.  Returns (staged SceneIn record, SceneState record, flag word, cause word)."""
-    end_mask, max_ticks = int(em["end_mask"][0]), int(em["max_ticks"][0])
     M, order, check, clearance = int(sp["n_starts"][0]), int(sp["order"][0]), int(sp["check"][0]), float(sp["clearance"][0])
     ps = p[s]
     px, py = float(ps["loc"]["globalpoint"]["x"]), float(ps["loc"]["globalpoint"]["y"])
     # 1.
-    age = int(e["age"]) + 1
-    ex, ey = float(q["loc"]["globalpoint"]["x"]) - px, float(q["loc"]["globalpoint"]["y"]) - py
-    dist = float(e["dist"]) + math.sqrt(ex * ex + ey * ey)
+    age, dist = epm.age_dist(e, ps, q)
     off, n = int(ps["obs_off"]), int(ps["obs_n"])
     # 1a.
     touch = int(sp["contact"][0]) != 0 and slice_within(O, off, n, px, py, hw, 0.0)
     # 2.
-    c = epm.cause(flag, age, end_mask, max_ticks) | (CONTACT if touch else 0)
+    c = epm.cause(flag, age, int(em["end_mask"][0]), int(em["max_ticks"][0])) | (CONTACT if touch else 0)
     if c == 0:
-        e["age"], e["dist"] = age, dist
+        epm.go_on(e, age, dist)
         return q, state, int(flag), 0
     # 3.
-    e["n_episodes"] += 1
-    for b in range(5):
-        if c & (1 << b):
-            e["n_end"][b] += 1
-    if c & epm.TIMEOUT:
-        e["n_end"][5] += 1
-    e["last_cause"], e["last_age"] = c, age
-    if int(e["min_age"]) < 0 or age < int(e["min_age"]):
-        e["min_age"] = age
-    if int(e["max_age"]) < 0 or age > int(e["max_age"]):
-        e["max_age"] = age
-    e["ticks_total"] += age
-    e["last_dist"] = dist
-    e["dist_total"] = float(e["dist_total"]) + dist
-    e["age"], e["dist"] = 0, 0.0
+    epm.close(e, c, age, dist)
     if c & CONTACT:
         se["n_contact"] += 1
     # 3a.
@@ -114,13 +97,8 @@ def step_scene(em, sp, s, e, se, pool_in, pool_state, p, q, flag, state, O, hw, 
     se["cur_start"] = k
     se["n_used"][k] += 1
     start_in, start_state = pool_in[k][s], pool_state[k][s]
-    # 5.
-    if trace is not None:
-        trace[s] = epm.trace_record(trace.dtype, start_in, int(flag) | epm.RESPAWNED | (c & (epm.TIMEOUT | CONTACT)))
-    # 6.
-    if score is not None:
-        score["last_pos"]["x"], score["last_pos"]["y"] = start_in["loc"]["globalpoint"]["x"], start_in["loc"]["globalpoint"]["y"]
-        score["last_speed"] = start_in["loc"]["velocity"]
+    # 5. 6.
+    epm.start_words(start_in, flag, c, trace, s, score)
     # 4.
     return start_in, start_state, 0, c
 
