@@ -6,16 +6,10 @@ records, a list of steps - each the PlanOut[N] and SceneState[N] one advance rea
 the map store) and an optional route; it returns one Result per step: the SceneIn records the advance staged, the flag words and
 the EgoTrace records.
 
-The device cannot be handed PlanOut, SceneState or flag words, so they are injected: the handle ticks once (a tick is what an
-advance follows), the host waits, the crafted records are copied over the tick's PlanOut and SceneState buffers
-(Planner.write_device) and pp_advance_async runs on them.  A flag word that is set on the way in is reached the honest way: an
-earlier step of the same call sets it, the handle ticks, and the next step is injected (the model chains its own steps alike).
-The tick's own results are overwritten before anything reads them; the scenes keep every slice inside its pool, so the slice check
-behind the advance changes nothing and the model needs no rule for it."""
-import hashlib
-
+PlanOut, SceneState and flag words are injected on the device: tests/advance_harness.py (inject_advance) on how and why."""
 import numpy as np
 
+import advance_harness as ah
 import dmpp_amd as dm
 import ego_model as em
 import route_model as rmod
@@ -40,11 +34,7 @@ def trace_of(out, flags):
     return tr
 
 
-def _route(route, n):
-    if route is None:
-        return None, np.zeros(n + 1, np.int32), dm.default_route_model()
-    legs, rf, rm = route
-    return legs, np.ascontiguousarray(rf, np.int32), dm.default_route_model() if rm is None else rm
+_route = ah.route_of
 
 
 def model_step(cfg, model, si, po, st, flags, world, route=None):
@@ -71,32 +61,14 @@ class ModelBackend:
 class DeviceBackend:
     name = "device"
 
+    def __init__(self, first=None):
+        self.first = first          # set calls of a feature that come before the records (advance_harness.open_planner)
+
     def run(self, cfg, model, si, steps, world, route=None):
-        n = len(si)
-        sc = dict(scene_in=si, obs_pool=np.zeros(1, dm.ObPoint), mot_pool=np.zeros(1, dm.ObMotion), n_obs=0)
-        if "map" in world:
-            m = world["map"]
-            pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=1, max_lane_pts_total=len(m["points"]), max_ref_pts_total=max(len(m["jpoints"]), 1))
-            pl.set_map(m)
-            pl.set_egos(sc, with_motion=False)
-            if route is not None:
-                legs, rf, rm = _route(route, n)
-                pl.set_route(legs, rf, rm)
-        else:
-            pool, ref = world["lane_pool"], world.get("ref_pool", np.zeros(1, dm.GlobalPoint2D))
-            sc.update(lane_pool=pool, attr_pool=np.zeros(len(pool), np.uint8), ref_pool=ref)
-            pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=1, max_lane_pts_total=len(pool), max_ref_pts_total=len(ref))
-            pl.set_scenes(sc, with_motion=False)
-        state = np.zeros(n, dm.SceneState)
-        pl.lib.pp_init_state(state.ctypes.data, n)
-        pl.set_state(state)
-        assert pl.get_scene_in().tobytes() == si.tobytes(), "the resident records are the crafted ones (views resolved, slices inside the pools)"
-        trace, res = dm.pinned_empty(n, dm.EgoTrace), []
+        pl = ah.open_planner(cfg, si, world, mot_pool=np.zeros(1, dm.ObMotion), route=route, first=self.first)
+        trace, res = dm.pinned_empty(len(si), dm.EgoTrace), []
         for po, st in steps:
-            pl.tick()                                     # the tick an advance follows; what it wrote is replaced below
-            pl.write_device(dm.BUF_PLAN_OUT, po)
-            pl.write_device(dm.BUF_STATE, st)
-            pl.advance_async(model, trace)
+            ah.inject_advance(pl, model, po, st, trace)
             out, f = pl.get_scene_in(), pl.ego_flags()
             pl.sync()
             res.append(Result(out, f, np.array(trace)))
@@ -150,32 +122,44 @@ STATS = {}
 
 class Runner:
     """What a known answer calls.  On the device every step is also held against the model applied to the device's own records
-    of the step before (compare), and every call is logged for batched()."""
-    def __init__(self, backend, log=None):
-        self.backend, self.name, self.log = backend, backend.name, log
+    of the step before (compare), and every call is logged for batched().  The families on the same call signature (grid follow,
+    ego tracker) pass their own step(cfg, model, records, step, flags, world, route, **carried) and check(got, want, what), what the model carries
+    from step to step (carried(n)) and what they add to a logged case (feature: gf=..., tk=...)."""
+    def __init__(self, backend, log=None, step=None, check=None, carried=None, **feature):
+        self.backend, self.name, self.log, self.carried, self.feature = backend, backend.name, log, carried, feature
+        self.step = step or (lambda cfg, model, cur, s, flags, world, route: model_step(cfg, model, cur, s[0], s[1], flags, world, route))
+        self.check = check or (lambda r, want, what: compare(r, want, what, STATS))
 
     def __call__(self, cfg, model, si, steps, world, route=None):
         res = self.backend.run(cfg, model, si, steps, world, route)
-        cur, flags = si, np.zeros(len(si), np.int32)
-        for k, r in enumerate(res):
-            check_trace(r, f"{self.name} step {k}")
-            if self.name == "device":
-                compare(r, model_step(cfg, model, cur, steps[k][0], steps[k][1], flags, world, route), f"step {k}", STATS)
-            cur, flags = r.out, r.flags
+        ah.hold_run(self.name, res, si, lambda k, cur, flags, **kept: self.step(cfg, model, cur, steps[k], flags, world, route, **kept), self.check,
+                    self.carried and self.carried(len(si)), check_trace)
         if self.log is not None:
-            self.log.append(dict(cfg=cfg.copy(), model=model.copy(), si=si.copy(), steps=[(po.copy(), st.copy()) for po, st in steps], world=world,
-                                 route=route, res=res))
+            self.log.append(ah.Call(ah.case_of(steps, cfg=cfg, model=model, si=si, world=world, route=route, **self.feature), res))
         return res
 
 
-def _key(case):
-    h = hashlib.sha1()
-    h.update(case["cfg"].tobytes() + case["model"].tobytes() + bytes([len(case["steps"])]))
-    if "map" in case["world"]:
-        for k in sorted(case["world"]["map"]):
-            h.update(np.ascontiguousarray(case["world"]["map"][k]).tobytes())
-        h.update(b"-" if case["route"] is None else _route(case["route"], 1)[2].tobytes())
-    return h.hexdigest()
+def same_launch(a, b):
+    """Same configuration, ego model, number of steps and world kind; in map mode the same map and route model."""
+    if a.cfg.tobytes() != b.cfg.tobytes() or a.model.tobytes() != b.model.tobytes() or len(a.steps) != len(b.steps) or ("map" in a.world) != ("map" in b.world):
+        return False
+    if "map" not in a.world:
+        return True
+    ma, mb = a.world["map"], b.world["map"]
+    same_map = sorted(ma) == sorted(mb) and all(np.ascontiguousarray(ma[k]).tobytes() == np.ascontiguousarray(mb[k]).tobytes() for k in ma)
+    return same_map and ah.same_route_model(a.route, b.route)
+
+
+def batch(backend, calls, attrs=("out", "flags", "trace"), join_steps=lambda cases, moved: ah.join_steps(cases)):
+    """The one-scene calls as the scenes of one launch on `backend` (a DeviceBackend of this family).  Slice-mode lane pools are laid
+    one behind the other and the views moved by their pool's offset.  Every scene must give the bytes it gave alone: `attrs`."""
+    n, c0 = len(calls), calls[0].case
+    assert n % 4 != 0 and n > 4
+    world, route, moved = ah.join_world([c.case for c in calls])
+    res = backend.run(c0.cfg, c0.model, moved(np.concatenate([c.case.si for c in calls])), join_steps([c.case for c in calls], moved), world, route)
+    for t, r in enumerate(res):
+        ah.same_alone(r, t, calls, attrs, moved=moved)
+    return n
 
 
 def batched(backend, log, min_scenes=5):
@@ -183,53 +167,11 @@ def batched(backend, log, min_scenes=5):
     ego model, world kind, map, route model and number of steps) form one batch of at least `min_scenes` scenes - more than one
     block of four - and never a multiple of four (the first calls are repeated to get there).  Slice-mode lane pools are laid one
     behind the other and the views moved by their pool's offset.  Every scene must give the bytes it gave alone.  Returns the batch sizes."""
-    groups = {}
-    for case in log:
-        assert len(case["si"]) == 1
-        groups.setdefault(_key(case), []).append(case)
     sizes = []
-    for cases in groups.values():
-        cases = list(cases)
+    for calls in ah.group_calls(log, same_launch):
         k = 0
-        while len(cases) < min_scenes or len(cases) % 4 == 0:
-            cases.append(cases[k])
+        while len(calls) < min_scenes or len(calls) % 4 == 0:
+            calls.append(calls[k])
             k += 1
-        n, c0 = len(cases), cases[0]
-        si = np.concatenate([c["si"] for c in cases])
-        steps = [(np.concatenate([c["steps"][t][0] for c in cases]), np.concatenate([c["steps"][t][1] for c in cases])) for t in range(len(c0["steps"]))]
-        route, offs = None, np.zeros(n, np.int64)
-        if "map" in c0["world"]:
-            world = c0["world"]
-            if c0["route"] is not None:
-                legs, rf = [], [0]
-                for c in cases:
-                    lg, f1, _ = _route(c["route"], 1)
-                    legs.append(lg[int(f1[0]):int(f1[1])])
-                    rf.append(rf[-1] + len(legs[-1]))
-                route = (np.concatenate(legs), np.array(rf, np.int32), _route(c0["route"], 1)[2])
-        else:
-            pools, where, total = [], {}, 0
-            for k, c in enumerate(cases):
-                p = c["world"]["lane_pool"]
-                d = p.tobytes()
-                if d not in where:
-                    where[d] = total
-                    pools.append(p)
-                    total += len(p)
-                offs[k] = where[d]
-            world = dict(lane_pool=np.concatenate(pools))
-            for name in ("cur_off", "left_off", "right_off"):
-                si["lanes"][name] += offs.astype(np.int32)
-        res = backend.run(c0["cfg"], c0["model"], si, steps, world, route)
-        for t, r in enumerate(res):
-            out = r.out.copy()
-            for name in ("cur_off", "left_off", "right_off"):
-                out["lanes"][name] -= offs.astype(np.int32)
-            for k, c in enumerate(cases):
-                alone = c["res"][t]
-                what = f"batch of {n}, scene {k}, step {t}"
-                assert out[k].tobytes() == alone.out[0].tobytes(), what + ": SceneIn"
-                assert int(r.flags[k]) == int(alone.flags[0]), what + ": flags"
-                assert r.trace[k].tobytes() == alone.trace[0].tobytes(), what + ": trace"
-        sizes.append(n)
+        sizes.append(batch(backend, calls))
     return sizes

@@ -8,8 +8,8 @@ one advance reads - the world (a map) and an optional route; it returns one Resu
 next tick, the flag words, the EgoTrace records, the SceneState array and the EpisodeStats after the advance - and, with
 score=True, the RolloutScore records (the tick before every advance is scored, and one closing tick after the last).
 
-PlanOut and SceneState are injected on the device as advance_backends.py does it: the handle ticks, the host waits, the crafted
-records are copied over the tick's buffers and pp_advance_async runs on them.  So the scorecard on the device has folded the
+PlanOut and SceneState are injected on the device as advance_backends.py does it (advance_harness.inject_advance): the handle ticks,
+the host waits, the crafted records are copied over the tick's buffers and pp_advance_async runs on them.  So the scorecard on the device has folded the
 tick's own PlanOut, not the crafted one: a known answer asserts only what the scorecard takes from SceneIn (dist, max_acc, max_dec,
 max_speed, last_pos, last_speed, n_ticks); the whole record is held against the model in the closed loop of tests/test_episodes.py.
 
@@ -19,6 +19,7 @@ staged one in every byte the test chose.  The captured records are never ticked:
 import numpy as np
 
 import advance_backends as ab
+import advance_harness as ah
 import dmpp_amd as dm
 import episode_model as epm
 import map_scenes as ms
@@ -61,35 +62,25 @@ class DeviceBackend:
     name = "device"
 
     def run(self, cfg, model, em, si, state0, steps, world, route=None, score=False, capture=None):
-        n, m = len(si), world["map"]
-        sc = dict(scene_in=si if capture is None else capture[0], obs_pool=np.zeros(1, dm.ObPoint), mot_pool=np.zeros(1, dm.ObMotion), n_obs=0)
-        pl = dm.Planner(cfg, device=0, max_scenes=n, max_obs_total=1, max_lane_pts_total=len(m["points"]), max_ref_pts_total=max(len(m["jpoints"]), 1))
-        pl.set_map(m)
-        pl.set_egos(sc, with_motion=False)
-        if route is not None:
-            legs, rf, rm = ab._route(route, n)
-            pl.set_route(legs, rf, rm)
-        pl.set_state(state0 if capture is None else capture[1])
-        pl.set_episodes(em)
-        keep = None
+        n = len(si)
+        first_in, first_state = (si, state0) if capture is None else capture
+        pl = ah.open_planner(cfg, first_in, world, mot_pool=np.zeros(1, dm.ObMotion), route=route, state=first_state, then=lambda pl: pl.set_episodes(em),
+                             check=capture is None)
+        keep, adopted = None, None
         if capture is not None:
             assert len(steps) == 1, "the captured records are never ticked"
-            assert pl.get_scene_in().tobytes() == ms.resolve(dm, m, capture[0]).tobytes(), "the captured records are the crafted ones, resolved"
+            assert pl.get_scene_in().tobytes() == ms.resolve(dm, world["map"], capture[0]).tobytes(), "the captured records are the crafted ones, resolved"
             pl.set_state(state0)
             keep = dm.pinned_copy(si)
             pl.update_async(scene_in=keep)
-        else:
-            assert pl.get_scene_in().tobytes() == si.tobytes(), "the resident records are the crafted ones (views resolved, slices inside the pools)"
+
+            def adopted(pl):
+                assert pl.get_scene_in().tobytes() == si.tobytes(), "the records of the update are the crafted ones"
         if score:
             pl.score_begin(float(model["dt"][0]))
         trace, res = dm.pinned_empty(n, dm.EgoTrace), []
         for po, st in steps:
-            pl.tick()                                     # the tick an advance follows; what it wrote is replaced below
-            if capture is not None:
-                assert pl.get_scene_in().tobytes() == si.tobytes(), "the records of the update are the crafted ones"
-            pl.write_device(dm.BUF_PLAN_OUT, po)
-            pl.write_device(dm.BUF_STATE, st)
-            pl.advance_async(model, trace)
+            ah.inject_advance(pl, model, po, st, trace, after_tick=adopted)
             out, f, stats = pl.get_scene_in(), pl.ego_flags(), pl.episode_stats()
             state = pl.get_state()                        # behind the staged advance: the restored state
             sco = pl.rollout_score() if score else None
@@ -140,6 +131,13 @@ def compare(got, want, what):
     assert same_stats(got.stats, want.stats), f"{what}: EpisodeStats {got.stats.tolist()} against {want.stats.tolist()}"
 
 
+def check_trace(r, what):
+    """advance_backends.check_trace with episodes: the trace of a restored record keeps the flag word that ended the episode."""
+    restored = (r.trace["flags"] & epm.RESPAWNED) != 0
+    want_tr = ab.trace_of(r.out, np.where(restored, r.trace["flags"], r.flags).astype(np.int32))
+    assert r.trace.tobytes() == want_tr.tobytes(), f"{what}: the EgoTrace records are not the staged records"
+
+
 class Runner:
     """What a known answer calls.  On the device every step is also held against the model applied to the device's own records
     of the step before (compare), and every call is logged for batched()."""
@@ -148,28 +146,20 @@ class Runner:
 
     def __call__(self, cfg, model, em, si, state0, steps, world, route=None, score=False, capture=None):
         res = self.backend.run(cfg, model, em, si, state0, steps, world, route, score, capture)
-        n = len(si)
         start_in, start_state = (si, state0) if capture is None else (ms.resolve(dm, world["map"], capture[0]), capture[1])
-        cur, flags, stats = si, np.zeros(n, np.int32), epm.new_stats(dm.EpisodeStats, n)
-        for k, r in enumerate(res):
-            restored = (r.trace["flags"] & epm.RESPAWNED) != 0
-            want_tr = ab.trace_of(r.out, np.where(restored, r.trace["flags"], r.flags).astype(np.int32))
-            assert r.trace.tobytes() == want_tr.tobytes(), f"{self.name} step {k}: the EgoTrace records are not the staged records"
-            if self.name == "device":
-                stats = stats if k == 0 else res[k - 1].stats.copy()
-                compare(r, model_step(cfg, model, em, stats, start_in, start_state, cur, steps[k][0], steps[k][1], flags, world, route), f"step {k}")
-            cur, flags = r.out, r.flags
+
+        def step(k, cur, flags, stats):
+            return model_step(cfg, model, em, stats, start_in, start_state, cur, steps[k][0], steps[k][1], flags, world, route)
+        ah.hold_run(self.name, res, si, step, compare, dict(stats=epm.new_stats(dm.EpisodeStats, len(si))), check_trace)
         if self.log is not None:
             assert capture is None and not score
-            self.log.append(dict(cfg=cfg.copy(), model=model.copy(), em=em.copy(), si=si.copy(), state0=state0.copy(),
-                                 steps=[(po.copy(), st.copy()) for po, st in steps], world=world, route=route, res=res))
+            self.log.append(ah.Call(ah.case_of(steps, cfg=cfg, model=model, em=em, si=si, state0=state0, world=world, route=route), res))
         return res
 
 
 def _same_launch(a, b):
-    return (a["cfg"].tobytes() == b["cfg"].tobytes() and a["model"].tobytes() == b["model"].tobytes() and a["em"].tobytes() == b["em"].tobytes() and
-            len(a["steps"]) == len(b["steps"]) and a["world"] is b["world"] and
-            (a["route"] is None) == (b["route"] is None) and (a["route"] is None or ab._route(a["route"], 1)[2].tobytes() == ab._route(b["route"], 1)[2].tobytes()))
+    return (a.cfg.tobytes() == b.cfg.tobytes() and a.model.tobytes() == b.model.tobytes() and a.em.tobytes() == b.em.tobytes() and
+            len(a.steps) == len(b.steps) and a.world is b.world and ah.same_route_model(a.route, b.route))
 
 
 def batched(backend, log, sizes=(5, 9)):
@@ -178,46 +168,12 @@ def batched(backend, log, sizes=(5, 9)):
     `sizes` - more than one block of four waves, never a multiple of four.  The group's calls are rotated so that a scene that
     ENDS an episode sits first, last and on either side of the block edge 4 | 5 where the group has both kinds (the filler repeats
     the group's calls).  Every scene must give the bytes it gave alone.  Returns (size, indices of the ending scenes) per batch."""
-    groups = []
-    for case in log:
-        assert len(case["si"]) == 1
-        for g in groups:
-            if _same_launch(g[0], case):
-                g.append(case)
-                break
-        else:
-            groups.append([case])
     ran = []
-    for cases in groups:
-        ends = [c for c in cases if any(int(r.stats["n_episodes"][0]) > (int(c["res"][t - 1].stats["n_episodes"][0]) if t else 0) for t, r in enumerate(c["res"]))]
-        goes = [c for c in cases if not any(c is e for e in ends)]
-        for n in sizes:
-            assert n > 4 and n % 4 != 0
-            want_end = {0, 3, 4, n - 1} if ends else set()
-            e, g, batch = 0, 0, []
-            for k in range(n):
-                pool, idx = (ends, e) if (k in want_end or not goes) else (goes, g)
-                batch.append(pool[idx % len(pool)])
-                e, g = (e + 1, g) if pool is ends else (e, g + 1)
-            c0 = batch[0]
-            si, state0 = np.concatenate([c["si"] for c in batch]), np.concatenate([c["state0"] for c in batch])
-            steps = [(np.concatenate([c["steps"][t][0] for c in batch]), np.concatenate([c["steps"][t][1] for c in batch])) for t in range(len(c0["steps"]))]
-            route = None
-            if c0["route"] is not None:
-                legs, rf = [], [0]
-                for c in batch:
-                    lg, f1, _ = ab._route(c["route"], 1)
-                    legs.append(lg[int(f1[0]):int(f1[1])])
-                    rf.append(rf[-1] + len(legs[-1]))
-                route = (np.concatenate(legs), np.array(rf, np.int32), ab._route(c0["route"], 1)[2])
-            res = backend.run(c0["cfg"], c0["model"], c0["em"], si, state0, steps, c0["world"], route)
-            for t, r in enumerate(res):
-                for k, c in enumerate(batch):
-                    alone, what = c["res"][t], f"batch of {n}, scene {k}, step {t}"
-                    assert r.out[k].tobytes() == alone.out[0].tobytes(), what + ": SceneIn"
-                    assert int(r.flags[k]) == int(alone.flags[0]), what + ": flags"
-                    assert r.trace[k].tobytes() == alone.trace[0].tobytes(), what + ": trace"
-                    assert r.state[k].tobytes() == alone.state[0].tobytes(), what + ": SceneState"
-                    assert r.stats[k].tobytes() == alone.stats[0].tobytes(), what + ": EpisodeStats"
-            ran.append((n, sorted(k for k in range(n) if any(batch[k] is e for e in ends))))
+    for n, batch, at in ah.batches(log, _same_launch, ah.ends_episode, sizes):
+        cases = [c.case for c in batch]
+        res = backend.run(cases[0].cfg, cases[0].model, cases[0].em, np.concatenate([c.si for c in cases]), np.concatenate([c.state0 for c in cases]),
+                          ah.join_steps(cases), cases[0].world, ah.join_routes([c.route for c in cases]))
+        for t, r in enumerate(res):
+            ah.same_alone(r, t, batch, ("out", "flags", "trace", "state", "stats"))
+        ran.append((n, at))
     return ran

@@ -13,10 +13,10 @@ and `Runner` holds every read of the device against the replay of the device's O
 scorecard included, since the device's records carry the tick's own PlanOut (episode_backends.py on what a crafted PlanOut cannot do)."""
 import numpy as np
 
-import advance_backends as ab
+import advance_backends as ab          # (tests reach ab._route through this module)
+import advance_harness as ah
 import dmpp_amd as dm
 import episode_log_model as elm
-import episode_model as epm
 import episode_spawn_backends as esb
 import episode_spawn_model as esm
 
@@ -63,9 +63,7 @@ class ModelBackend:
 
     def run(self, case, cap, drain="each", max_records=None):
         n = case.n
-        si, pool, _ = case.laid_out()
-        pin, pst = case.pools(si)
-        stats, sstats, flags, data = epm.new_stats(dm.EpisodeStats, n), esm.new_stats(dm.EpisodeSpawnStats, n), np.zeros(n, np.int32), []
+        (si, pool, pin, pst, stats, sstats), flags, data = case.start(), np.zeros(n, np.int32), []
         for k, (po, st) in enumerate(case.steps):
             r = esb.model_step(case, stats, sstats, pin, pst, pool, si, po, st, flags)
             data.append(Data(si, flags, r.stats, r.sstats, k + 1, pool, po, st))
@@ -75,36 +73,25 @@ class ModelBackend:
 
 def open_planner(case, cap=None):
     """The set-up of episode_spawn_backends.DeviceBackend, then - last - pp_set_episode_log.  Returns (planner, SceneIn, pool)."""
-    n, m = case.n, case.world["map"]
-    si, pool, W = case.laid_out()
-    sc = dict(scene_in=si, obs_pool=pool, mot_pool=None, n_obs=W)
-    pl = dm.Planner(case.cfg, device=0, max_scenes=n, max_obs_total=len(pool), max_lane_pts_total=len(m["points"]), max_ref_pts_total=max(len(m["jpoints"]), 1))
-    pl.set_map(m)
-    pl.set_egos(sc, with_motion=False)
-    if case.route is not None:
-        pl.set_route(*ab._route(case.route, n))
-    pl.set_state(case.state0)
-    pl.set_episodes(case.em)
-    if case.sp is not None:
-        pl.set_episode_spawn(case.sp, *(case.starts if case.starts is not None else (None, None)))
-    if case.score:
-        pl.score_begin(float(case.model["dt"][0]))
-    if cap is not None:
-        pl.set_episode_log(cap)
-    return pl, si, pool
+    def then(pl):
+        pl.set_episodes(case.em)
+        if case.sp is not None:
+            esb.set_spawn(pl, case)
+        if case.score:
+            pl.score_begin(float(case.model["dt"][0]))
+        if cap is not None:
+            pl.set_episode_log(cap)
+    return esb.open_case(case, then, check=False)[:3]
 
 
 def advance(pl, case, po, st, si, flags, pool):
-    """One tick and one advance on crafted PlanOut / SceneState records, as episode_backends.DeviceBackend injects them.  Returns
-    (the Data of the advance, the staged SceneIn records, the flag words)."""
-    pl.tick()
-    plan, state = (pl.get_plan(), pl.get_state()) if case.score else (None, None)      # what the scorecard folded: the tick's own
-    pl.write_device(dm.BUF_PLAN_OUT, po)
-    pl.write_device(dm.BUF_STATE, st)
-    tick = pl.tick_id()
-    pl.advance_async(case.model)
+    """One tick and one advance on crafted PlanOut / SceneState records (advance_harness.inject_advance).  Returns (the Data of the
+    advance, the staged SceneIn records, the flag words)."""
+    seen = dict(plan=None, state=None)
+    folded = (lambda pl: seen.update(plan=pl.get_plan(), state=pl.get_state())) if case.score else None      # what the scorecard folded: the tick's own
+    ah.inject_advance(pl, case.model, po, st, after_tick=folded, before_advance=lambda pl: seen.update(tick=pl.tick_id()))
     sstats = pl.episode_spawn_stats() if case.sp is not None else esm.new_stats(dm.EpisodeSpawnStats, case.n)
-    return Data(si, flags, pl.episode_stats(), sstats, tick, pool, plan, state), pl.get_scene_in(), pl.ego_flags()
+    return Data(si, flags, pl.episode_stats(), sstats, seen["tick"], pool, seen["plan"], seen["state"]), pl.get_scene_in(), pl.ego_flags()
 
 
 class DeviceBackend:

@@ -7,11 +7,10 @@ runs).  A Result is what episode_spawn_backends.Result holds and the EpisodeSche
 import numpy as np
 
 import advance_backends as ab
+import advance_harness as ah
 import dmpp_amd as dm
-import episode_model as epm
 import episode_schedule_model as evm
 import episode_spawn_backends as esb
-import episode_spawn_model as esm
 
 
 class Case(esb.Case):
@@ -46,36 +45,11 @@ class ModelBackend:
     def run(self, case):
         assert not case.score
         n = case.n
-        si, pool, _ = case.laid_out()
-        pin, pst = case.pools(si)
-        rows, stats, sstats, flags, res = _rows(case), epm.new_stats(dm.EpisodeStats, n), esm.new_stats(dm.EpisodeSpawnStats, n), np.zeros(n, np.int32), []
+        (si, pool, pin, pst, stats, sstats), rows, flags, res = case.start(), _rows(case), np.zeros(n, np.int32), []
         for po, st in case.steps:
             res.append(model_step(case, rows, stats, sstats, pin, pst, pool, si, po, st, flags))
             si, flags = res[-1].out, res[-1].flags
         return res
-
-
-def planner(case):
-    """A handle with everything of the Case in force, the schedule last; and the resident records."""
-    n, m = case.n, case.world["map"]
-    si, pool, W = case.laid_out()
-    sc = dict(scene_in=si, obs_pool=pool, mot_pool=None, n_obs=W)
-    pl = dm.Planner(case.cfg, device=0, max_scenes=n, max_obs_total=len(pool), max_lane_pts_total=len(m["points"]), max_ref_pts_total=max(len(m["jpoints"]), 1))
-    pl.set_map(m)
-    pl.set_egos(sc, with_motion=False)
-    if case.route is not None:
-        legs, rf, rm = ab._route(case.route, n)
-        pl.set_route(legs, rf, rm)
-    pl.set_state(case.state0)
-    if case.world_first is not None:
-        fm = dm.default_fleet_model()
-        fm["max_peers"] = 0
-        pl.set_fleet(case.world_first, fm)
-    pl.set_episodes(case.em)
-    pl.set_episode_spawn(case.sp, *(case.starts if case.starts is not None else (None, None)))
-    if case.sm is not None:
-        pl.set_episode_schedule(case.sm)
-    return pl, si
 
 
 class DeviceBackend:
@@ -83,17 +57,18 @@ class DeviceBackend:
 
     def run(self, case, light=False):
         """light: only flags, stats and rows are fetched per step (the big batches)."""
+        def then(pl):                                     # everything of the Case in force, the schedule last
+            esb.set_worlds(pl, case)
+            pl.set_episodes(case.em)
+            esb.set_spawn(pl, case)
+            if case.sm is not None:
+                pl.set_episode_schedule(case.sm)
         assert not case.score
         n = case.n
-        pl, si = planner(case)
-        if not light:
-            assert pl.get_scene_in().tobytes() == si.tobytes(), "the resident records are the crafted ones (views resolved, slices inside the pools)"
+        pl = esb.open_case(case, then, check=not light)[0]
         trace, res = dm.pinned_empty(n, dm.EgoTrace), []
         for po, st in case.steps:
-            pl.tick()                                     # the tick an advance follows; what it wrote is replaced below
-            pl.write_device(dm.BUF_PLAN_OUT, po)
-            pl.write_device(dm.BUF_STATE, st)
-            pl.advance_async(case.model, trace)
+            ah.inject_advance(pl, case.model, po, st, trace)
             f, stats, sstats = pl.ego_flags(), pl.episode_stats(), pl.episode_spawn_stats()
             out, state = (None, None) if light else (pl.get_scene_in(), pl.get_state())
             rows = pl.episode_schedule() if case.sm is not None else np.zeros(1, dm.EpisodeScheduleRow)
@@ -116,15 +91,9 @@ class Runner:
 
     def __call__(self, case):
         res = self.backend.run(case)
-        if self.name != "device":
-            return res
-        n = case.n
-        si, pool, _ = case.laid_out()
-        pin, pst = case.pools(si)
-        cur, flags, rows, stats, sstats = si, np.zeros(n, np.int32), _rows(case), epm.new_stats(dm.EpisodeStats, n), esm.new_stats(dm.EpisodeSpawnStats, n)
-        for k, r in enumerate(res):
-            if k:
-                rows, stats, sstats = res[k - 1].rows.copy(), res[k - 1].stats.copy(), res[k - 1].sstats.copy()
-            compare(r, model_step(case, rows, stats, sstats, pin, pst, pool, cur, case.steps[k][0], case.steps[k][1], flags), f"step {k}")
-            cur, flags = r.out, r.flags
+        si, pool, pin, pst, stats, sstats = case.start()
+
+        def step(k, cur, flags, rows, stats, sstats):
+            return model_step(case, rows, stats, sstats, pin, pst, pool, cur, case.steps[k][0], case.steps[k][1], flags)
+        ah.hold_run(self.name, res, si, step, compare, dict(rows=_rows(case), stats=stats, sstats=sstats))
         return res

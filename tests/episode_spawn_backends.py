@@ -12,6 +12,7 @@ episode_backends.Result holds and the EpisodeSpawnStats.  PlanOut and SceneState
 import numpy as np
 
 import advance_backends as ab
+import advance_harness as ah
 import dmpp_amd as dm
 import episode_backends as eb
 import episode_model as epm
@@ -42,6 +43,12 @@ class Case:
             pool[s * W:s * W + len(o)] = o
             si["obs_off"][s], si["obs_n"][s] = s * W, len(o)
         return ms.resolve(dm, self.world["map"], si), pool, W
+
+    def start(self):
+        """What a model run starts from: (SceneIn laid out, the obstacle pool, the start records of pools(), EpisodeStats and
+        EpisodeSpawnStats before the first step)."""
+        si, pool, _ = self.laid_out()
+        return (si, pool) + self.pools(si) + (epm.new_stats(dm.EpisodeStats, self.n), esm.new_stats(dm.EpisodeSpawnStats, self.n))
 
     def pools(self, si):
         """The start records as §4l prepares them: record 0 the capture, the others resolved on the map with record 0's slice."""
@@ -82,9 +89,7 @@ class ModelBackend:
 
     def run(self, case):
         n = case.n
-        si, pool, _ = case.laid_out()
-        pin, pst = case.pools(si)
-        stats, sstats, flags, res = epm.new_stats(dm.EpisodeStats, n), esm.new_stats(dm.EpisodeSpawnStats, n), np.zeros(n, np.int32), []
+        (si, pool, pin, pst, stats, sstats), flags, res = case.start(), np.zeros(n, np.int32), []
         scores = rsm.new_scores(dm.RolloutScore, n) if case.score else None
         dt = float(case.model["dt"][0])
         for po, st in case.steps:
@@ -98,36 +103,41 @@ class ModelBackend:
         return res
 
 
+def open_case(case, then, mot_pool=None, check=True):
+    """advance_harness.open_planner for a Case - its laid-out records and obstacle slots, route and start state - with the feature
+    set calls `then(pl)` behind them; a motion pool makes the input sets carry one.  Returns (handle, SceneIn, obstacle pool, slot width)."""
+    si, pool, W = case.laid_out()
+    return ah.open_planner(case.cfg, si, case.world, (pool, W), mot_pool, mot_pool is not None, case.route, case.state0, then=then, check=check), si, pool, W
+
+
+def set_worlds(pl, case):
+    """The fleet of a Case with world_first: worlds only, no peer slots."""
+    if case.world_first is not None:
+        fm = dm.default_fleet_model()
+        fm["max_peers"] = 0
+        pl.set_fleet(case.world_first, fm)
+
+
+def set_spawn(pl, case):
+    pl.set_episode_spawn(case.sp, *(case.starts if case.starts is not None else (None, None)))
+
+
 class DeviceBackend:
     name = "device"
 
     def run(self, case):
-        n, m = case.n, case.world["map"]
-        si, pool, W = case.laid_out()
-        sc = dict(scene_in=si, obs_pool=pool, mot_pool=None, n_obs=W)
-        pl = dm.Planner(case.cfg, device=0, max_scenes=n, max_obs_total=len(pool), max_lane_pts_total=len(m["points"]), max_ref_pts_total=max(len(m["jpoints"]), 1))
-        pl.set_map(m)
-        pl.set_egos(sc, with_motion=False)
-        if case.route is not None:
-            legs, rf, rm = ab._route(case.route, n)
-            pl.set_route(legs, rf, rm)
-        pl.set_state(case.state0)
-        if case.world_first is not None:
-            fm = dm.default_fleet_model()
-            fm["max_peers"] = 0
-            pl.set_fleet(case.world_first, fm)
-        pl.set_episodes(case.em)
-        if case.sp is not None:
-            pl.set_episode_spawn(case.sp, *(case.starts if case.starts is not None else (None, None)))
-        assert pl.get_scene_in().tobytes() == si.tobytes(), "the resident records are the crafted ones (views resolved, slices inside the pools)"
+        def then(pl):
+            set_worlds(pl, case)
+            pl.set_episodes(case.em)
+            if case.sp is not None:
+                set_spawn(pl, case)
+        n = case.n
+        pl = open_case(case, then)[0]
         if case.score:
             pl.score_begin(float(case.model["dt"][0]))
         trace, res = dm.pinned_empty(n, dm.EgoTrace), []
         for po, st in case.steps:
-            pl.tick()                                     # the tick an advance follows; what it wrote is replaced below
-            pl.write_device(dm.BUF_PLAN_OUT, po)
-            pl.write_device(dm.BUF_STATE, st)
-            pl.advance_async(case.model, trace)
+            ah.inject_advance(pl, case.model, po, st, trace)
             out, f, stats = pl.get_scene_in(), pl.ego_flags(), pl.episode_stats()
             sstats = pl.episode_spawn_stats() if case.sp is not None else esm.new_stats(dm.EpisodeSpawnStats, n)
             state = pl.get_state()                        # behind the staged advance: the restored state
@@ -155,33 +165,27 @@ class Runner:
 
     def __call__(self, case, log=True):
         res = self.backend.run(case)
-        n = case.n
-        si, pool, _ = case.laid_out()
-        pin, pst = case.pools(si)
-        cur, flags, stats, sstats = si, np.zeros(n, np.int32), epm.new_stats(dm.EpisodeStats, n), esm.new_stats(dm.EpisodeSpawnStats, n)
-        for k, r in enumerate(res):
-            restored = (r.trace["flags"] & epm.RESPAWNED) != 0
-            want_tr = ab.trace_of(r.out, np.where(restored, r.trace["flags"], r.flags).astype(np.int32))
-            assert r.trace.tobytes() == want_tr.tobytes(), f"{self.name} step {k}: the EgoTrace records are not the staged records"
-            if self.name == "device":
-                if k:
-                    stats, sstats = res[k - 1].stats.copy(), res[k - 1].sstats.copy()
-                compare(r, model_step(case, stats, sstats, pin, pst, pool, cur, case.steps[k][0], case.steps[k][1], flags), f"step {k}")
-            cur, flags = r.out, r.flags
+        si, pool, pin, pst, stats, sstats = case.start()
+
+        def step(k, cur, flags, stats, sstats):
+            return model_step(case, stats, sstats, pin, pst, pool, cur, case.steps[k][0], case.steps[k][1], flags)
+        ah.hold_run(self.name, res, si, step, compare, dict(stats=stats, sstats=sstats), eb.check_trace)
         if self.log is not None and log:
-            assert n == 1 and not case.score and case.world_first is None
-            self.log.append((case, res))
+            assert case.n == 1 and not case.score and case.world_first is None
+            self.log.append(ah.Call(case, res))
         return res
 
 
 def _same_launch(a, b):
-    return (a.cfg.tobytes() == b.cfg.tobytes() and a.model.tobytes() == b.model.tobytes() and a.em.tobytes() == b.em.tobytes() and
-            (a.sp is None) == (b.sp is None) and (a.sp is None or a.sp.tobytes() == b.sp.tobytes()) and len(a.steps) == len(b.steps) and a.world is b.world and
-            (a.route is None) == (b.route is None) and (a.route is None or ab._route(a.route, 1)[2].tobytes() == ab._route(b.route, 1)[2].tobytes()))
+    return eb._same_launch(a, b) and (a.sp is None) == (b.sp is None) and (a.sp is None or a.sp.tobytes() == b.sp.tobytes())
 
 
-def _ended(res):
-    return any(int(r.stats["n_episodes"][0]) > (int(res[t - 1].stats["n_episodes"][0]) if t else 0) for t, r in enumerate(res))
+def joined(cases):
+    """(SceneIn, obs, state0, steps, route, starts) of one-scene cases as the scenes of one Case."""
+    M = cases[0].M
+    starts = None if M == 1 else tuple(np.concatenate([c.starts[i][k - 1:k] for k in range(1, M) for c in cases]) for i in (0, 1))
+    return (np.concatenate([c.si for c in cases]), [c.obs[0] for c in cases], np.concatenate([c.state0 for c in cases]), ah.join_steps(cases),
+            ah.join_routes([c.route for c in cases]), starts)
 
 
 def batched(log, sizes=(5, 9)):
@@ -191,57 +195,16 @@ def batched(log, sizes=(5, 9)):
     so a batch is held against the MODEL run on the same batch (compare: every byte but an advanced heading); a scene whose
     choice does not depend on its index (M = 1 or round robin) must also give the bytes it gave alone.  Returns (size, indices of
     the ending scenes) per batch."""
-    groups = []
-    for case, res in log:
-        for g in groups:
-            if _same_launch(g[0][0], case):
-                g.append((case, res))
-                break
-        else:
-            groups.append([(case, res)])
     ran = []
-    for cases in groups:
-        ends = [c for c in cases if _ended(c[1])]
-        goes = [c for c in cases if not _ended(c[1])]
-        for n in sizes:
-            assert n > 4 and n % 4 != 0
-            want_end = {0, 3, 4, n - 1} if ends else set()
-            e, g, batch = 0, 0, []
-            for k in range(n):
-                pool, idx = (ends, e) if (k in want_end or not goes) else (goes, g)
-                batch.append(pool[idx % len(pool)])
-                e, g = (e + 1, g) if pool is ends else (e, g + 1)
-            c0, M = batch[0][0], batch[0][0].M
-            steps = [(np.concatenate([c.steps[t][0] for c, _ in batch]), np.concatenate([c.steps[t][1] for c, _ in batch])) for t in range(len(c0.steps))]
-            route = None
-            if c0.route is not None:
-                legs, rf = [], [0]
-                for c, _ in batch:
-                    lg, f1, _r = ab._route(c.route, 1)
-                    legs.append(lg[int(f1[0]):int(f1[1])])
-                    rf.append(rf[-1] + len(legs[-1]))
-                route = (np.concatenate(legs), np.array(rf, np.int32), ab._route(c0.route, 1)[2])
-            starts = None
-            if M > 1:
-                starts = (np.concatenate([c.starts[0][k - 1:k] for k in range(1, M) for c, _ in batch]),
-                          np.concatenate([c.starts[1][k - 1:k] for k in range(1, M) for c, _ in batch]))
-            big = Case(c0.cfg, c0.model, c0.em, c0.sp, np.concatenate([c.si for c, _ in batch]), [c.obs[0] for c, _ in batch],
-                       np.concatenate([c.state0 for c, _ in batch]), steps, c0.world, route, starts)
-            got, want = DeviceBackend().run(big), ModelBackend().run(big)
-            W = big.laid_out()[2]
-            for t, (r, w) in enumerate(zip(got, want)):
-                compare(r, w, f"batch of {n}, step {t}")
-                if c0.sp is not None and M > 1 and int(c0.sp["order"][0]) == 0:
-                    continue
-                for k, (c, res) in enumerate(batch):
-                    alone, what = res[t], f"batch of {n}, scene {k}, step {t}"
-                    a = alone.out[0].copy()
-                    a["obs_off"] = k * W
-                    assert r.out[k].tobytes() == a.tobytes(), what + ": SceneIn"
-                    assert int(r.flags[k]) == int(alone.flags[0]), what + ": flags"
-                    assert r.trace[k].tobytes() == alone.trace[0].tobytes(), what + ": trace"
-                    assert r.state[k].tobytes() == alone.state[0].tobytes(), what + ": SceneState"
-                    assert r.stats[k].tobytes() == alone.stats[0].tobytes(), what + ": EpisodeStats"
-                    assert r.sstats[k].tobytes() == alone.sstats[0].tobytes(), what + ": EpisodeSpawnStats"
-            ran.append((n, sorted(k for k in range(n) if any(batch[k] is x for x in ends))))
+    for n, batch, at in ah.batches(log, _same_launch, ah.ends_episode, sizes):
+        c0 = batch[0].case
+        si, obs, state0, steps, route, starts = joined([c.case for c in batch])
+        big = Case(c0.cfg, c0.model, c0.em, c0.sp, si, obs, state0, steps, c0.world, route, starts)
+        got, want = DeviceBackend().run(big), ModelBackend().run(big)
+        W = big.laid_out()[2]
+        for t, (r, w) in enumerate(zip(got, want)):
+            compare(r, w, f"batch of {n}, step {t}")
+            if c0.sp is None or c0.M == 1 or int(c0.sp["order"][0]) != 0:
+                ah.same_alone(r, t, batch, ("out", "flags", "trace", "state", "stats", "sstats"), obs_width=W)
+        ran.append((n, at))
     return ran

@@ -13,9 +13,8 @@ On the device the slices are read through pp_get_obstacles from the staged set a
 next tick has adopted it."""
 import numpy as np
 
-import advance_backends as ab
+import advance_harness as ah
 import dmpp_amd as dm
-import episode_model as epm
 import episode_spawn_backends as esb
 import episode_spawn_model as esm
 import episode_traffic_model as etm
@@ -61,13 +60,12 @@ class ModelBackend:
 
     def run(self, case):
         n = case.n
-        si, pool, _ = case.laid_out()
-        pin, pst = case.pools(si)
+        si, pool, pin, pst, stats, sstats = case.start()
         tracks, pts, act = case.traffic()
         tr = (fm.Follow if case.follow is not None else tm.Traffic)(tracks, pts, act, si["obs_off"])
         pool, mot = tr.place(pool, _mot0(case, pool), 0.0)                    # pp_set_traffic
         reset = etm.Reset(tr, case.n_sets, case.tstarts, case.follow is not None) if case.n_sets else None
-        stats, sstats, flags, res = epm.new_stats(dm.EpisodeStats, n), esm.new_stats(dm.EpisodeSpawnStats, n), np.zeros(n, np.int32), []
+        flags, res = np.zeros(n, np.int32), []
         dt = float(case.model["dt"][0])
         for po, st in case.steps:
             r = esb.model_step(case, stats, sstats, pin, pst, pool, si, po, st, flags)          # (contact and clearance read the pool the advance READ)
@@ -85,40 +83,26 @@ class ModelBackend:
 class DeviceBackend:
     name = "device"
 
-    def planner(self, case):
-        n, m = case.n, case.world["map"]
-        si, pool, W = case.laid_out()
-        sc = dict(scene_in=si, obs_pool=pool, mot_pool=_mot0(case, pool), n_obs=W)
-        pl = dm.Planner(case.cfg, device=0, max_scenes=n, max_obs_total=len(pool), max_lane_pts_total=len(m["points"]), max_ref_pts_total=max(len(m["jpoints"]), 1))
-        pl.set_map(m)
-        pl.set_egos(sc, with_motion=case.motion)
-        if case.route is not None:
-            legs, rf, rm = ab._route(case.route, n)
-            pl.set_route(legs, rf, rm)
-        pl.set_state(case.state0)
-        pl.set_traffic(*case.traffic())
-        if case.follow is not None:
-            pl.set_traffic_follow(case.follow)
-        pl.set_episodes(case.em)
-        if case.sp is not None:
-            pl.set_episode_spawn(case.sp, *(case.starts if case.starts is not None else (None, None)))
-        if case.n_sets:
-            pl.set_episode_traffic(case.n_sets, case.tstarts)
-        return pl, si, pool, W
-
     def run(self, case):
-        n = case.n
-        pl, si, pool, W = self.planner(case)
-        assert pl.get_scene_in().tobytes() == si.tobytes(), "the resident records are the crafted ones (views resolved, slices inside the pools)"
-        trace, res = dm.pinned_empty(n, dm.EgoTrace), []
-        for po, st in case.steps:
-            pl.tick()                                     # the tick an advance follows; what it wrote is replaced below
-            if case.motion and res:                       # the set the last advance staged is the current one now
+        def then(pl):
+            pl.set_traffic(*case.traffic())
+            if case.follow is not None:
+                pl.set_traffic_follow(case.follow)
+            pl.set_episodes(case.em)
+            if case.sp is not None:
+                esb.set_spawn(pl, case)
+            if case.n_sets:
+                pl.set_episode_traffic(case.n_sets, case.tstarts)
+
+        def adopted(pl):                                  # the set the last advance staged is the current one now
+            if case.motion and res:
                 res[-1].mot = pl.read_device(dm.BUF_MOT_POOL, dm.ObMotion, len(pool))
                 assert pl.read_device(dm.BUF_OBS_POOL, dm.ObPoint, len(pool)).tobytes() == res[-1].pool.tobytes(), "the slices are the pool"
-            pl.write_device(dm.BUF_PLAN_OUT, po)
-            pl.write_device(dm.BUF_STATE, st)
-            pl.advance_async(case.model, trace)
+        n = case.n
+        pl, si, pool, W = esb.open_case(case, then, _mot0(case, case.laid_out()[1]))
+        trace, res = dm.pinned_empty(n, dm.EgoTrace), []
+        for po, st in case.steps:
+            ah.inject_advance(pl, case.model, po, st, trace, after_tick=adopted)
             out, f, stats = pl.get_scene_in(), pl.ego_flags(), pl.episode_stats()
             sstats = pl.episode_spawn_stats() if case.sp is not None else esm.new_stats(dm.EpisodeSpawnStats, n)
             base = esb.Result(out, f, np.array(trace), pl.get_state(), stats, sstats)
@@ -160,7 +144,7 @@ class Runner:
                 compare(r, w, f"step {k}")
         if self.log is not None:
             assert case.n == 1
-            self.log.append((case, res))
+            self.log.append(ah.Call(case, res))
         return res
 
 
@@ -176,20 +160,8 @@ def _restarts(res):
 def batch_of(cases):
     """Single-scene cases that can share a launch as the scenes of one case: scenes, slices, start records, tracks, actors and
     start states concatenated, track and scene indices moved."""
-    c0, M = cases[0], cases[0].M
-    n = len(cases)
-    steps = [(np.concatenate([c.steps[t][0] for c in cases]), np.concatenate([c.steps[t][1] for c in cases])) for t in range(len(c0.steps))]
-    route = None
-    if c0.route is not None:
-        legs, rf = [], [0]
-        for c in cases:
-            lg, f1, _r = ab._route(c.route, 1)
-            legs.append(lg[int(f1[0]):int(f1[1])])
-            rf.append(rf[-1] + len(legs[-1]))
-        route = (np.concatenate(legs), np.array(rf, np.int32), ab._route(c0.route, 1)[2])
-    starts = None
-    if M > 1:
-        starts = (np.concatenate([c.starts[0][k - 1:k] for k in range(1, M) for c in cases]), np.concatenate([c.starts[1][k - 1:k] for k in range(1, M) for c in cases]))
+    c0 = cases[0]
+    si, obs, state0, steps, route, starts = esb.joined(cases)
     polylines, rows, first = [], [], []
     for k, c in enumerate(cases):
         first.append(len(rows))
@@ -198,9 +170,8 @@ def batch_of(cases):
     tstarts = None
     if c0.n_sets > 1:
         tstarts = np.concatenate([np.asarray(c.tstarts).reshape(c0.n_sets - 1, len(c.rows))[k] for k in range(c0.n_sets - 1) for c in cases])
-    big = Case(c0.cfg, c0.model, c0.em, c0.sp, np.concatenate([c.si for c in cases]), [c.obs[0] for c in cases], np.concatenate([c.state0 for c in cases]),
-               steps, c0.world, route, starts, polylines, rows, c0.n_sets, tstarts, c0.follow, c0.motion)
-    return big, first + [len(rows)], n
+    big = Case(c0.cfg, c0.model, c0.em, c0.sp, si, obs, state0, steps, c0.world, route, starts, polylines, rows, c0.n_sets, tstarts, c0.follow, c0.motion)
+    return big, first + [len(rows)], len(cases)
 
 
 def batched(log, sizes=(5, 9), backend=None):
@@ -210,45 +181,24 @@ def batched(log, sizes=(5, 9), backend=None):
     the same batch, and that against the bytes the model gave for every scene alone (`log` is a model runner's) - the start choice
     of the cases logged here is round robin or M = 1, so it does not depend on the scene index.  Returns (size, indices of the
     restarting scenes) per batch."""
-    groups = []
-    for case, res in log:
-        assert case.sp is None or case.M == 1 or int(case.sp["order"][0]) == 1
-        for g in groups:
-            if _same_launch(g[0][0], case):
-                g.append((case, res))
-                break
-        else:
-            groups.append([(case, res)])
+    assert all(c.case.sp is None or c.case.M == 1 or int(c.case.sp["order"][0]) == 1 for c in log)
     ran = []
-    for cases in groups:
-        ends = [c for c in cases if _restarts(c[1])]
-        goes = [c for c in cases if not _restarts(c[1])]
-        for n in sizes:
-            assert n > 4 and n % 4 != 0
-            want_end = {0, 3, 4, n - 1} if ends else set()
-            e, g, batch = 0, 0, []
-            for k in range(n):
-                pool, idx = (ends, e) if (k in want_end or not goes) else (goes, g)
-                batch.append(pool[idx % len(pool)])
-                e, g = (e + 1, g) if pool is ends else (e, g + 1)
-            big, first, _ = batch_of([c for c, _ in batch])
-            got, want = (backend or DeviceBackend()).run(big), ModelBackend().run(big)
-            W = big.laid_out()[2]
-            for t, (r, w) in enumerate(zip(got, want)):
-                compare(r, w, f"batch of {n}, step {t}")
-                r = w                                     # (the log is the MODEL's: an advanced heading is the host's atan on both sides)
-                for k, (c, res) in enumerate(batch):
-                    alone, what = res[t], f"batch of {n}, scene {k}, step {t}"
-                    a = alone.out[0].copy()
-                    a["obs_off"] = k * W
-                    assert r.out[k].tobytes() == a.tobytes(), what + ": SceneIn"
-                    assert r.stats[k].tobytes() == alone.stats[0].tobytes() and r.sstats[k].tobytes() == alone.sstats[0].tobytes(), what + ": stats"
-                    acts = slice(first[k], first[k + 1])
-                    assert r.s[acts].tobytes() == alone.s.tobytes(), what + ": s"
-                    assert r.pool[k * W:k * W + len(c.obs[0])].tobytes() == alone.pool[:len(c.obs[0])].tobytes(), what + ": slice"
-                    if alone.v is not None:
-                        assert r.v[acts].tobytes() == alone.v.tobytes(), what + ": v"
-                    if alone.resets is not None:
-                        assert r.resets[acts].tobytes() == alone.resets.tobytes(), what + ": n_resets"
-            ran.append((n, sorted(k for k in range(n) if any(batch[k] is x for x in ends))))
+    for n, batch, at in ah.batches(log, _same_launch, _restarts, sizes):
+        big, first, _ = batch_of([c.case for c in batch])
+        got, want = (backend or DeviceBackend()).run(big), ModelBackend().run(big)
+        W = big.laid_out()[2]
+        for t, (r, w) in enumerate(zip(got, want)):
+            compare(r, w, f"batch of {n}, step {t}")
+            ah.same_alone(w, t, batch, ("out",), obs_width=W)          # (the log is the MODEL's: an advanced heading is the host's atan on both sides)
+            for k, c in enumerate(batch):
+                alone, what, own = c.res[t], f"batch of {n}, scene {k}, step {t}", len(c.case.obs[0])
+                assert w.stats[k].tobytes() == alone.stats[0].tobytes() and w.sstats[k].tobytes() == alone.sstats[0].tobytes(), what + ": stats"
+                acts = slice(first[k], first[k + 1])
+                assert w.s[acts].tobytes() == alone.s.tobytes(), what + ": s"
+                assert w.pool[k * W:k * W + own].tobytes() == alone.pool[:own].tobytes(), what + ": slice"
+                if alone.v is not None:
+                    assert w.v[acts].tobytes() == alone.v.tobytes(), what + ": v"
+                if alone.resets is not None:
+                    assert w.resets[acts].tobytes() == alone.resets.tobytes(), what + ": n_resets"
+        ran.append((n, at))
     return ran

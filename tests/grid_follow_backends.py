@@ -1,13 +1,12 @@
 """The two backends of tests/advance_backends.py for a handle with a GridFollow model (pp_set_grid_follow).
 
 Everything is reused by import: the device backend is advance_backends.DeviceBackend - the same injection of crafted PlanOut /
-SceneState through a real tick - on a Planner that switches following on as soon as it exists, so before the first advance (and
-before set_map / set_egos / set_scenes, which the model must survive); the model backend is tests/grid_follow_model.py around the
+SceneState through a real tick - on a Planner that switches following on as soon as it exists (the `first` hook of
+advance_harness.open_planner), so before the first advance (and before set_map / set_egos / set_scenes, which the model must
+survive); the model backend is tests/grid_follow_model.py around the
 models advance_backends uses.  Runner holds every device step against that model on the device's own records of the step before,
 as advance_backends.Runner does, and `batched` runs advance_backends.batched once per GridFollow model (a model is a kernel
 argument: only calls with the same one can share a launch)."""
-from unittest import mock
-
 import numpy as np
 
 import advance_backends as ab
@@ -46,48 +45,29 @@ class ModelBackend:
 class DeviceBackend(ab.DeviceBackend):
     def __init__(self, gf):
         self.gf = _gf(gf)
-
-    def run(self, cfg, model, si, steps, world, route=None):
-        gf = self.gf
-
-        class FollowingPlanner(dm.Planner):
-            def __init__(self, *a, **kw):
-                super().__init__(*a, **kw)
-                self.set_grid_follow(gf)
-
-        with mock.patch.object(ab.dm, "Planner", FollowingPlanner):
-            return super().run(cfg, model, si, steps, world, route)
+        super().__init__(lambda pl: pl.set_grid_follow(self.gf))
 
 
-class Runner:
+def compare(got, want, what):
+    ab.compare(got, want, what, ab.STATS)
+    for name in ("grid_origin", "goal"):          # §4g: to the last bit
+        assert got.out[name].tobytes() == want.out[name].tobytes(), f"{what}: {name} {got.out[name]} against {want.out[name]}"
+
+
+class Runner(ab.Runner):
     """advance_backends.Runner with the GridFollow model: what a known answer calls."""
     def __init__(self, name, gf, log=None):
-        self.gf, self.name, self.log = _gf(gf), name, log
-        self.backend = ModelBackend(gf) if name == "model" else DeviceBackend(gf)
-
-    def __call__(self, cfg, model, si, steps, world, route=None):
-        res = self.backend.run(cfg, model, si, steps, world, route)
-        cur, flags = si, np.zeros(len(si), np.int32)
-        for k, r in enumerate(res):
-            ab.check_trace(r, f"{self.name} step {k}")
-            if self.name == "device":
-                want = model_step(cfg, model, self.gf, cur, steps[k][0], steps[k][1], flags, world, route)
-                ab.compare(r, want, f"step {k}", ab.STATS)
-                for name in ("grid_origin", "goal"):          # §4g: to the last bit
-                    assert r.out[name].tobytes() == want.out[name].tobytes(), f"step {k}: {name} {r.out[name]} against {want.out[name]}"
-            cur, flags = r.out, r.flags
-        if self.log is not None:
-            self.log.append(dict(cfg=cfg.copy(), model=model.copy(), si=si.copy(), steps=[(po.copy(), st.copy()) for po, st in steps], world=world,
-                                 route=route, res=res, gf=self.gf))
-        return res
+        self.gf = gf = _gf(gf)
+        super().__init__(ModelBackend(gf) if name == "model" else DeviceBackend(gf), log, check=compare, gf=gf,
+                         step=lambda cfg, model, cur, s, flags, world, route: model_step(cfg, model, gf, cur, s[0], s[1], flags, world, route))
 
 
 def batched(log, min_scenes=5):
     """advance_backends.batched on the device, once per GridFollow model of the logged calls.  Returns the batch sizes."""
     by_gf = {}
-    for case in log:
-        by_gf.setdefault(b"" if case["gf"] is None else case["gf"].tobytes(), []).append(case)
+    for call in log:
+        by_gf.setdefault(b"" if call.case.gf is None else call.case.gf.tobytes(), []).append(call)
     sizes = []
-    for cases in by_gf.values():
-        sizes += ab.batched(DeviceBackend(cases[0]["gf"]), cases, min_scenes)
+    for calls in by_gf.values():
+        sizes += ab.batched(DeviceBackend(calls[0].case.gf), calls, min_scenes)
     return sizes
