@@ -121,6 +121,7 @@ EPISODE_MAX_STARTS = 16
 EpisodeSpawn = _dt([("seed", np.uint64), ("clearance", f8), ("n_starts", i4), ("order", i4), ("contact", i4), ("check", i4)])
 EpisodeSpawnStats = _dt([("n_contact", i4), ("n_blocked", i4), ("n_rejected", i4), ("cur_start", i4), ("n_used", i4, (EPISODE_MAX_STARTS,))])
 EGO_CONTACT = 128             # cause words only: the ego touched an obstacle of its slice (DMPP_EGO_CONTACT)
+EGO_WORLD = 256               # cause words only: another ego of the scene's world ended on this advance (DMPP_EGO_WORLD, §4s)
 # episode traffic reset: the actors of a restarted scene go back to a start state, one set per start record
 TrafficStart = _dt([("s", f8), ("v", f8)])
 # episode log: one record per ended episode, appended on the device in the order of the scenes
@@ -211,6 +212,8 @@ _FEATURES = [
     ("pp_set_packed_fetch", {"pp_set_packed_fetch": ([_vp, _ci], _ci), "pp_fetch_packed_async": ([_vp, _vp, _vp, _pll], _ci),
                              "pp_unpack_plan": ([_vp, _vp, _ci, _vp, _vp, _vp], _ci), "pp_unpack_grid": ([_vp, _vp, _ci, _vp], _ci)},
      {43: PackedPlan, 44: PackedGrid}),          # (pp_sizeof id 42 stays unassigned)
+    ("pp_set_episode_worlds", {"pp_set_episode_worlds": ([_vp, _ci], _ci), "pp_set_episode_world_traffic": ([_vp, _ci, _vp], _ci),
+                               "pp_get_episode_world_traffic_resets": ([_vp, _vp, _ci], _ci)}, {}),
 ]
 
 _lib = None
@@ -824,6 +827,32 @@ class Planner:
         advance included (host wait)."""
         out = np.zeros(getattr(self, "n_traffic_reset", 0), np.int32)
         _check(self.lib.pp_get_episode_traffic_resets(self.h, _ptr(out), len(out)))
+        return out
+
+    # ---- world episodes: the egos of a world restart together, with its vehicles -------------------
+    def set_episode_worlds(self, on=True):
+        """pp_set_episode_worlds, after set_episode_spawn: from the next advance on the WORLD (set_fleet; without a
+        fleet: the scene) is the unit of an episode - when any ego of a world ends, every ego of it restarts on the same start record
+        index.  Part of the spawn model in force: a later set_episode_spawn switches it off.  on False: off."""
+        _check(self.lib.pp_set_episode_worlds(self.h, 1 if on else 0))
+
+    def set_episode_world_traffic(self, n_sets, starts=None):
+        """pp_set_episode_world_traffic, after set_world_traffic, set_traffic_follow and set_episode_worlds:
+        set_episode_traffic for the vehicles of a world.  starts: TrafficStart records of sets 1 .. n_sets - 1, set k of vehicle a at
+        (k - 1) * n_actors + a.  0: the reset off, the counters stay readable."""
+        st = None if starts is None else np.ascontiguousarray(starts, TrafficStart).reshape(-1)
+        want = (int(n_sets) - 1) * getattr(self, "n_traffic", 0)
+        if st is not None and int(n_sets) >= 1 and len(st) != want:          # (the library refuses the other counts)
+            raise ValueError(f"starts: {len(st)} records, n_sets and the vehicles ask for {want}")
+        _check(self.lib.pp_set_episode_world_traffic(self.h, int(n_sets), _ptr(st)))
+        if int(n_sets) > 0:
+            self.n_world_traffic_reset = getattr(self, "n_traffic", 0)
+
+    def episode_world_traffic_resets(self):
+        """pp_get_episode_world_traffic_resets: how often every vehicle was put back on a start state since
+        set_episode_world_traffic, a staged advance included (host wait)."""
+        out = np.zeros(getattr(self, "n_world_traffic_reset", 0), np.int32)
+        _check(self.lib.pp_get_episode_world_traffic_resets(self.h, _ptr(out), len(out)))
         return out
 
     # ---- episode log: one record per ended episode, appended on the device ------------------------

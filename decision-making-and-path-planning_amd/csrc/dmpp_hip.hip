@@ -26,6 +26,7 @@
 #include "kernels_ep.hpp"
 #include "kernels_es.hpp"
 #include "kernels_ev.hpp"
+#include "kernels_ew.hpp"
 #include "kernels_g.hpp"
 #include "kernels_sc.hpp"
 #include "kernels_el.hpp"
@@ -246,6 +247,10 @@ struct SpawnState {
     // k_respawn_spawn and, in pooled scope, k_fold_schedule behind it.  The rows stay readable after it went off
     bool sched_on = false, sched_ever = false; EpisodeSchedule sched = {};
     DevBuf<EpisodeScheduleRow> d_rows; DevBuf<int32_t> d_fold_word;      // scope 0: a row per scene; scope 1: one row and a word per scene
+    // world episodes (first pp_set_episode_worlds): part of the spawn model in force like the schedule - cleared wherever
+    // sched_on is, never on beside it.  While on, pp_advance_async launches k_respawn_world in the place of k_respawn_spawn, one
+    // workgroup per world of the fleet in force AT THAT ADVANCE (no fleet: per scene); d_world_end is the kernel's per-scene scratch
+    bool worlds_on = false; DevBuf<dmpp::WorldEnd> d_world_end;
 };
 struct FollowState {
     bool on = false; TrafficFollow tf = {};
@@ -258,6 +263,15 @@ struct FollowState {
 struct TrafficResetState {
     bool on = false, ever = false; int n_sets = 0, actors = 0, cur = 0;      // ever: a set call succeeded on this handle (the counters are readable)
     DevBuf<int32_t> d_scene; DevBuf<TrafficStart> d_starts[2]; DevBuf<int32_t> d_resets[2];
+};
+// world traffic reset (first pp_set_episode_world_traffic): §4m's table and counters for the vehicles of
+// pp_set_world_traffic, two sets of each as there.  No feature bit: it lives inside the life cycles of what its table was captured from -
+// switch_features clears `on` whenever the traffic reset, world traffic, the spawn model or episodes are switched off, and
+// pp_set_episode_worlds(h, 0) does.  While on (only with world traffic and world episodes on), pp_advance_async launches
+// k_reset_world_traffic behind its world-traffic kernel.  The counters stay readable after it went off
+struct WorldTrafficResetState {
+    bool on = false, ever = false; int n_sets = 0, actors = 0, cur = 0;
+    DevBuf<TrafficStart> d_starts[2]; DevBuf<int32_t> d_resets[2];
 };
 // episode log (first pp_set_episode_log): the ring of `cap` records, the count of records appended since the set call,
 // every scene's start record and - only on a handle with a scorecard - the scorecard of its running episode; on the host the number
@@ -381,6 +395,7 @@ struct pp_planner {
     EpisodeState episode;
     SpawnState spawn;
     TrafficResetState treset;
+    WorldTrafficResetState wreset;
     EpisodeLogState elog;
     ScoreTraceState strace;
     PackedState packed;
@@ -500,6 +515,18 @@ void reset_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mo
                        h->treset.d_resets[h->treset.cur], d_obs, d_mot);
 }
 
+// World traffic reset of the input set an advance stages: reset_traffic for the vehicles of a world that has just
+// restarted, written into every member scene
+void reset_world_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot)
+{
+    const int n = h->wreset.actors, cur = h->traffic.cur;
+    hipLaunchKernelGGL(dmpp::k_reset_world_traffic, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
+                       n, h->wreset.n_sets, h->traffic.d_pin, h->traffic.d_world, h->fleet.d_world_first, h->fleet.d_pin, h->episode.d_stats,
+                       h->wreset.n_sets > 1 ? h->spawn.d_stats[h->spawn.cur].get() : nullptr, h->wreset.d_starts[h->wreset.cur],
+                       h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], h->follow.on ? h->follow.d_v[cur].get() : nullptr,
+                       h->wreset.d_resets[h->wreset.cur], d_obs, d_mot);
+}
+
 // The advance kernel of the input set an advance stages, in the place of the copy of its SceneIn records: reads the
 // records `prev` of the current set, the last tick's PlanOut and SceneState, writes d_in.  Routed egos cross junctions (§4f:
 // k_advance_route; the scenes without a route advance as in k_advance_egos).
@@ -537,6 +564,11 @@ void step_episodes(pp_planner* h, hipStream_t st, const InputSet& P, SceneIn* d_
     if (!h->spawn.on)
         hipLaunchKernelGGL(dmpp::k_respawn_egos, grid, block, 0, st,
                            h->episode.em, n, P.d_in, d_in, h->d_state, h->episode.d_start_in, h->episode.d_start_state, h->rollout.d_flags, h->episode.d_stats, trace, score);
+    else if (h->spawn.worlds_on)      // world episodes (§4s): one workgroup per world of the fleet in force, or per scene without one
+        hipLaunchKernelGGL(dmpp::k_respawn_world, dim3((unsigned)(h->fleet.on ? h->fleet.n_worlds : n)), block, 0, st,
+                           h->episode.em, h->spawn.sp, hw, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state, h->spawn.d_in[cur], h->spawn.d_state[cur],
+                           world_first, h->fleet.on ? h->fleet.d_pin.get() : nullptr, h->rollout.d_flags, h->episode.d_stats, h->spawn.d_stats[cur], trace, score,
+                           h->spawn.d_world_end);
     else if (!h->spawn.sched_on)      // the spawn model of §4l: contact ends an episode, the start record is drawn from a pool and checked for clearance
         hipLaunchKernelGGL(dmpp::k_respawn_spawn, grid, block, 0, st,
                            h->episode.em, h->spawn.sp, hw, n, h->spawn.stride, P.d_in, P.d_obs, P.n_obs_total, d_in, h->d_state, h->spawn.d_in[cur], h->spawn.d_state[cur],
@@ -702,7 +734,8 @@ void switch_features(pp_planner* h, unsigned m, bool on)
     if (m & (h->traffic.world ? kWorldTraffic : kTraffic)) h->traffic.on = on;
     if (m & kFollow) h->follow.on = on;
     if (m & kEpisodes) h->episode.on = on;
-    if (m & kSpawn) { h->spawn.on = on; if (!on) h->spawn.sched_on = false; }      // (the schedule of §4p is part of the spawn model: it goes with it and does not come back)
+    if (m & kSpawn) { h->spawn.on = on; if (!on) h->spawn.sched_on = h->spawn.worlds_on = false; }      // (the schedule of §4p and the world episodes of §4s are part of the spawn model: they go with it and do not come back)
+    if (!on && (m & (kTrafficReset | kWorldTraffic | kSpawn | kEpisodes))) h->wreset.on = false;      // (the world traffic reset of §4t has no bit: it goes with whatever its table was captured from, whether or not that was on)
     if (m & kTrafficReset) h->treset.on = on;
     if (m & kEpisodeLog) h->elog.on = on;
     static_assert(dmpp::kFeatureCount == 9, "a new feature bit needs its flag here and in feature_mask");
@@ -1700,6 +1733,7 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         else move_traffic(h, su, d_obs, d_mot, advance ? src.ego->dt : 0.0);
     }
     if (advance && h->treset.on) reset_traffic(h, su, d_obs, d_mot);      // the actors of a scene that has just restarted go back to a start state (§4m)
+    if (advance && h->wreset.on) reset_world_traffic(h, su, d_obs, d_mot);      // ... and the vehicles of a world that has (§4t)
     if (h->fleet.on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
         if (!advance) n_obs = std::max(n_obs, h->fleet.end);      // (an advance inherits the count of the current set)
         couple_fleet(h, su, d_in, d_obs, d_mot);
@@ -2234,7 +2268,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     PP_TRY(refuse_if_staged(h, "pp_set_episode_spawn", "the spawn model"));
-    if (!sp) { h->spawn.on = false; h->spawn.sched_on = false; retire(h, dmpp::kSetSpawn); return features_ok(h, "pp_set_episode_spawn"); }
+    if (!sp) { h->spawn.on = false; h->spawn.sched_on = h->spawn.worlds_on = false; retire(h, dmpp::kSetSpawn); return features_ok(h, "pp_set_episode_spawn"); }
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_spawn: episodes are off (pp_set_episodes comes first: its capture is start record 0)");
     const int n = h->n_scenes, M = sp->n_starts;
     if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts must be 1 .. DMPP_EPISODE_MAX_STARTS");
@@ -2251,7 +2285,12 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     const size_t recs = (size_t)M * (size_t)stride;       // room first: a failed allocation changes nothing
     PP_TRY(h->spawn.d_in[o].reserve(recs)); PP_TRY(h->spawn.d_state[o].reserve(recs)); PP_TRY(h->spawn.d_stats[o].reserve((size_t)h->caps.max_scenes));
     const unsigned was = feature_mask(h) & (dmpp::kSpawn | dmpp::retires(dmpp::kSetSpawn));
+    // (The world traffic reset of §4t has no bit in `was`: its flag is kept beside the mask and goes back with it.  PAIRING: retire() below
+    // clears it, and the ONLY path that puts it back is the `bad` refusal, beside switch_features(h, was, true).  Every other early return
+    // between the two - a failed copy or launch - leaves the spawn model off, and with it everything that lives inside it, this flag included.)
+    const bool wreset_was = h->wreset.on;
     h->spawn.on = false;                                  // (until everything below has landed: a failed copy leaves the spawn model off, not half a pool)
+    const bool worlds_was = h->spawn.worlds_on; h->spawn.worlds_on = false;      // (... and no world episodes on a spawn model that is off; back with the `bad` refusal)
     retire(h, dmpp::kSetSpawn);                           // (the traffic reset of §4m and the episode log of §4n read cur_start of the model in force: they go with it)
     SceneIn* pin = h->spawn.d_in[o]; SceneState* pst = h->spawn.d_state[o];
     HIP_TRY(hipMemcpyAsync(pin, h->episode.d_start_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
@@ -2275,13 +2314,14 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's arrays may go; the upload stream reads the pool from its next launch on
     if (bad) {
         switch_features(h, was, true);                    // (nothing in force was touched: spawn model, traffic reset and log are as they were)
+        h->spawn.worlds_on = worlds_was; h->wreset.on = wreset_was;
         return fail(PP_ERR_ARG, "pp_set_episode_spawn: " + std::to_string(bad) + " start record(s) name a road or lane outside the map");
     }
     if (o != h->spawn.cur) {                              // the pool that was in force goes (nobody reads it: joined and waited above); its stats are 80 B a scene and stay
         h->spawn.d_in[h->spawn.cur] = DevBuf<SceneIn>(); h->spawn.d_state[h->spawn.cur] = DevBuf<SceneState>();
     }
     h->spawn.sp = *sp; h->spawn.stride = stride; h->spawn.cur = o; h->spawn.on = true; h->spawn.ever = true;
-    h->spawn.sched_on = false;                            // (a new spawn model starts with no schedule: §4p)
+    h->spawn.sched_on = h->spawn.worlds_on = false;       // (a new spawn model starts with no schedule and no world episodes: §4p, §4s)
     return features_ok(h, "pp_set_episode_spawn");
 }
 
@@ -2322,6 +2362,7 @@ int pp_set_episode_schedule(pp_handle h, const EpisodeSchedule* m)
     PP_TRY(refuse_if_staged(h, "pp_set_episode_schedule", "the schedule"));
     if (!m) { h->spawn.sched_on = false; return features_ok(h, "pp_set_episode_schedule"); }
     if (!h->episode.on || !h->spawn.on) return fail(PP_ERR_STATE, "pp_set_episode_schedule: the spawn model is off (pp_set_episode_spawn comes first: the schedule draws its start records)");
+    if (h->spawn.worlds_on) return fail(PP_ERR_STATE, "pp_set_episode_schedule: world episodes are on (pp_set_episode_worlds: one draw per world, a schedule keeps rows per scene)");
     if (h->spawn.sp.order != 0) return fail(PP_ERR_STATE, "pp_set_episode_schedule: the spawn model in force is round robin (order 1): a schedule replaces the HASHED choice");
     PP_TRY(check_episode_schedule(m, "pp_set_episode_schedule"));
     PP_TRY(quiesce(h, false));                            // (the upload stream, which reads and folds the rows, is behind the last advance)
@@ -2403,6 +2444,66 @@ int pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n)
     if (n < 0 || n > h->treset.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
     return fetch_behind_advance(h, n_resets, h->treset.d_resets[h->treset.cur], (size_t)n * sizeof(int32_t), true);      // waits as pp_get_traffic_state does
+}
+
+// World episodes: part of the spawn model in force.  Captures nothing from the fleet: the step reads the fleet in force
+// at each advance.
+int pp_set_episode_worlds(pp_handle h, int on)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    PP_TRY(refuse_if_staged(h, "pp_set_episode_worlds", "the world episodes"));
+    if (!h->episode.on || !h->spawn.on) return fail(PP_ERR_STATE, "pp_set_episode_worlds: the spawn model is off (pp_set_episode_spawn comes first: a world restarts on its start records)");
+    if (h->spawn.sched_on) return fail(PP_ERR_STATE, "pp_set_episode_worlds: a schedule is in force (pp_set_episode_schedule keeps rows per scene, a world draws once)");
+    PP_TRY(quiesce(h, false));                            // (the upload stream, which runs the episode step, is behind the last advance)
+    if (on) PP_TRY(h->spawn.d_world_end.reserve((size_t)h->caps.max_scenes));      // room first: a failed allocation changes nothing
+    h->spawn.worlds_on = on != 0;
+    if (!on) h->wreset.on = false;                        // (the world reset of §4t keys on every member restarting together: it goes with the mode)
+    return features_ok(h, "pp_set_episode_worlds");
+}
+
+// World traffic reset: pp_set_episode_traffic for the vehicles of pp_set_world_traffic.
+int pp_set_episode_world_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    PP_TRY(refuse_if_staged(h, "pp_set_episode_world_traffic", "the world traffic reset"));
+    if (n_sets == 0) { h->wreset.on = false; return features_ok(h, "pp_set_episode_world_traffic"); }
+    if (!h->traffic.on || !h->traffic.world) return fail(PP_ERR_STATE, "pp_set_episode_world_traffic: no world traffic is set (pp_set_world_traffic comes first)");
+    if (!h->episode.on || !h->spawn.on || !h->spawn.worlds_on)
+        return fail(PP_ERR_STATE, "pp_set_episode_world_traffic: world episodes are off (pp_set_episode_worlds comes first: a vehicle resets when its whole world restarts)");
+    const int M = h->spawn.sp.n_starts;
+    if (n_sets < 0 || (n_sets != 1 && n_sets != M))
+        return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: n_sets must be 1 or the n_starts of the spawn model in force (" + std::to_string(M) + ")");
+    if (n_sets > 1 && !starts) return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: n_sets > 1 needs the start states");
+    const size_t n = (size_t)h->traffic.actors, given = starts ? (size_t)(n_sets - 1) * n : 0;
+    for (size_t i = 0; i < given; i++) {
+        if (!std::isfinite(starts[i].s)) return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: start state " + std::to_string(i) + " has a non-finite s");
+        if (!std::isfinite(starts[i].v) || starts[i].v < 0) return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: start state " + std::to_string(i) + ": v must be finite and >= 0");
+    }
+    PP_TRY(quiesce(h, false));                            // (the upload stream, which writes s / v, is behind the last advance)
+    const int o = h->wreset.ever ? 1 - h->wreset.cur : h->wreset.cur;
+    PP_TRY(h->wreset.d_starts[o].reserve((size_t)n_sets * n)); PP_TRY(h->wreset.d_resets[o].reserve(n));      // room first: a failed allocation changes nothing
+    TrafficStart* tab = h->wreset.d_starts[o];
+    // set 0, the capture: s of the current array; v of the current array while following is on, else the speed of every pin
+    HIP_TRY(hipMemcpy2DAsync(&tab->s, sizeof(TrafficStart), h->traffic.d_s[h->traffic.cur], sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
+    if (h->follow.on)
+        HIP_TRY(hipMemcpy2DAsync(&tab->v, sizeof(TrafficStart), h->follow.d_v[h->traffic.cur], sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
+    else
+        HIP_TRY(hipMemcpy2DAsync(&tab->v, sizeof(TrafficStart), h->traffic.d_pin, sizeof(dmpp::TrafficPin), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
+    if (given) HIP_TRY(hipMemcpyAsync(tab + n, starts, given * sizeof(TrafficStart), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->wreset.d_resets[o], 0, n * sizeof(int32_t), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's array may go; the upload stream reads the table from its next launch on
+    if (o != h->wreset.cur) h->wreset.d_starts[h->wreset.cur] = DevBuf<TrafficStart>();      // the table that was in force goes; its counters stay
+    h->wreset.n_sets = n_sets; h->wreset.actors = (int)n; h->wreset.cur = o; h->wreset.on = true; h->wreset.ever = true;
+    return features_ok(h, "pp_set_episode_world_traffic");
+}
+
+int pp_get_episode_world_traffic_resets(pp_handle h, int32_t* n_resets, int n)
+{
+    if (!h || (!n_resets && n > 0)) return fail(PP_ERR_ARG, "null argument");
+    if (!h->wreset.ever) return fail(PP_ERR_STATE, "pp_get_episode_world_traffic_resets: pp_set_episode_world_traffic was never called on this handle");
+    if (n < 0 || n > h->wreset.actors) return fail(PP_ERR_ARG, "n exceeds the vehicles");
+    if (n == 0) return PP_OK;
+    return fetch_behind_advance(h, n_resets, h->wreset.d_resets[h->wreset.cur], (size_t)n * sizeof(int32_t), true);      // waits as pp_get_traffic_state does
 }
 
 // Episode log.  Everything is checked on the host before anything changes.

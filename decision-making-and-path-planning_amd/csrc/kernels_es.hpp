@@ -86,7 +86,27 @@ __device__ __forceinline__ unsigned long long spawn_hash(const EpisodeSpawn& sp,
     return spawn_mix(spawn_mix(sp.seed + (unsigned long long)s) + (unsigned long long)e);
 }
 
-// §4l 3a. from k0 on, 3. - 6.: the clearance walk, the restart onto the record it took, stats, trace and scorecard words (lane 0)
+// §4l 3. - 6. behind the walk: the restart onto record k, stats, the words of the walk, trace and scorecard words (lane 0).  Shared with
+// k_respawn_world (kernels_ew.hpp, §4s), whose walk is the world's
+__device__ __forceinline__ void spawn_take_record(int s, int lane, int stride, int k, int rejected, int blocked, const SpawnEnd& E,
+                                                  SceneIn* staged, SceneState* state, const SceneIn* pool_in, const SceneState* pool_state, int32_t* flags,
+                                                  EpisodeStats* stats, EpisodeSpawnStats* sstats, EgoTrace* trace, RolloutScore* score)
+{
+    // 4. restart: SceneIn and SceneState of the scene become start record k, every byte
+    const SceneIn* start_in = pool_in + (size_t)k * stride;
+    wave_copy_record(&staged[s], &start_in[s], lane);
+    wave_copy_record(&state[s], &pool_state[(size_t)k * stride + s], lane);
+    if (lane != 0) return;
+    episode_close(stats[s], E);
+    flags[s] = 0;
+    EpisodeSpawnStats& S = sstats[s];
+    if (E.c & DMPP_EGO_CONTACT) S.n_contact = S.n_contact + 1;
+    S.n_blocked = S.n_blocked + blocked; S.n_rejected = S.n_rejected + rejected;
+    S.cur_start = k; S.n_used[k] = S.n_used[k] + 1;
+    episode_start_words(start_in[s].loc, E, s, trace, score);
+}
+
+// §4l 3a. from k0 on, 3. - 6.: the clearance walk and the restart onto the record it took
 __device__ __forceinline__ void spawn_restart(const EpisodeSpawn& sp, double hw, int s, int lane, int stride, int k0, const SpawnEnd& E,
                                               const SceneIn* prev, SceneIn* staged, SceneState* state, const SceneIn* pool_in, const SceneState* pool_state,
                                               const int32_t* world_first, const int32_t* world_of, int32_t* flags,
@@ -104,18 +124,7 @@ __device__ __forceinline__ void spawn_restart(const EpisodeSpawn& sp, double hw,
         k = cand; rejected = i; blocked = 0;
         break;
     }
-    // 4. restart: SceneIn and SceneState of the scene become start record k, every byte
-    const SceneIn* start_in = pool_in + (size_t)k * stride;
-    wave_copy_record(&staged[s], &start_in[s], lane);
-    wave_copy_record(&state[s], &pool_state[(size_t)k * stride + s], lane);
-    if (lane != 0) return;
-    episode_close(stats[s], E);
-    flags[s] = 0;
-    EpisodeSpawnStats& S = sstats[s];
-    if (E.c & DMPP_EGO_CONTACT) S.n_contact = S.n_contact + 1;
-    S.n_blocked = S.n_blocked + blocked; S.n_rejected = S.n_rejected + rejected;
-    S.cur_start = k; S.n_used[k] = S.n_used[k] + 1;
-    episode_start_words(start_in[s].loc, E, s, trace, score);
+    spawn_take_record(s, lane, stride, k, rejected, blocked, E, staged, state, pool_in, pool_state, flags, stats, sstats, trace, score);
 }
 
 // prev / obs: the SceneIn records and the obstacle pool (n_obs entries) of the input set the advance read; staged, state, flags, stats,

@@ -374,4 +374,40 @@ k_follow_world_traffic(int n_actors, double dt, TrafficFollow tf, double half_w,
     world_store(obs, mot, fpin, lane, p0, p1, pin.pool, traffic_pose(t, pts, pin, s1));
 }
 
+// ---- world traffic reset: k_reset_world_traffic is k_reset_traffic for the vehicles of pp_set_world_traffic, in an
+// advance behind k_move_world_traffic / k_follow_world_traffic while pp_set_episode_world_traffic is in force.  A vehicle goes back
+// to a start state when its WORLD restarted in this advance: with world episodes (§4s) every member restarts together, so the world's
+// first scene stands for it - EpisodeStats.age == 0 there, and its cur_start names the set.
+//
+// One wave per vehicle, four per block, no LDS, no barrier, no scratch: the shape of k_move_world_traffic.  A wave whose world goes
+// on leaves after three scalar loads (its world, the world's first scene, that scene's age).  v_arr: nullptr while following is
+// off; sstats: read only with n_sets > 1.
+__global__ void __launch_bounds__(kBlock)
+k_reset_world_traffic(int n_actors, int n_sets, const TrafficPin* __restrict__ actors, const int32_t* __restrict__ world,
+                      const int32_t* __restrict__ world_first, const FleetPin* __restrict__ fpin, const EpisodeStats* __restrict__ stats,
+                      const EpisodeSpawnStats* __restrict__ sstats, const TrafficStart* __restrict__ starts, const TrafficTrackDev* __restrict__ tracks,
+                      const double* __restrict__ cum, const GlobalPoint2D* __restrict__ pts, double* __restrict__ s_arr, double* __restrict__ v_arr,
+                      int32_t* __restrict__ n_resets, ObPoint* __restrict__ obs, ObMotion* __restrict__ mot)
+{
+    const int lane = threadIdx.x & 63;
+    const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * kTrafficWaves + (threadIdx.x >> 6));
+    if (a >= n_actors) return;                          // (whole waves leave: no barrier below)
+    const int w = world[a];
+    const int p0 = world_first[w];
+    if (stats[p0].age != 0) return;                     // the world goes on: its vehicles stay as the traffic kernel wrote them
+    const int p1 = world_first[w + 1];
+    int k = 0;
+    if (n_sets > 1) { k = sstats[p0].cur_start; if (k < 0 || k >= n_sets) k = 0; }      // (the set call checked n_sets == n_starts: never taken)
+    const TrafficStart st = starts[(size_t)k * (size_t)n_actors + (size_t)a];
+    const TrafficPin pin = actors[a];
+    const TrackView t = traffic_view(tracks, cum, pin.track);
+    const double s = traffic_wrap(st.s, t.L, t.closed);
+    if (lane == 0) {
+        s_arr[a] = s;
+        if (v_arr) v_arr[a] = pin.speed > 0 ? st.v : pin.speed;      // (§4i: a parked or reversing vehicle keeps v = speed)
+        n_resets[a] = n_resets[a] + 1;
+    }
+    world_store(obs, mot, fpin, lane, p0, p1, pin.pool, traffic_pose(t, pts, pin, s));
+}
+
 }  // namespace dmpp

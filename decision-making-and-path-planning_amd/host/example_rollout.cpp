@@ -34,6 +34,12 @@
 // With --route --episodes --log N the episode log is on (pp_set_episode_log): a ring of N records on the device, one
 // record appended per ended episode, drained once behind the run; the scorecard is on, so every record carries its episode's own.
 // The host prints an outcome table per start record: episodes, causes, mean age and metres, worst clearance, episodes with a collision.
+// With --route --fleet --traffic --shared [--react] --episodes [--starts M] --contact --worlds [--reset-traffic] the WORLD is the unit of an episode
+// (pp_set_episode_worlds): whenever one ego of a world ends its episode, all 8 egos of the world restart on that advance on one
+// start record index; --reset-traffic puts the world's vehicle back as well (pp_set_episode_world_traffic, §4t), so every world episode
+// repeats.  The routes of this example have one leg: the front ego of a platoon arrives (LANE_END | ROUTE_END) after 7 - 10 advances, before it
+// reaches the oncoming vehicle 20 m ahead, so the episodes the run prints end on arrival, not on contact - contact ends a world in the closed
+// loop of tests/test_episode_world_loop.py.
 // With --route --episodes --starts M --schedule [pooled|scene] a scenario schedule is on (pp_set_episode_schedule with the default model in
 // that scope): the start record of a restart is drawn by weights from the outcome counts per record that the device keeps -
 // with --contact the records whose episodes meet the vehicle about half the time get the most restarts.  The host prints the rows - counted
@@ -114,7 +120,7 @@ static int print_tracker(pp_handle h, int n)
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post, int sched)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post, int sched, bool worlds)
 {
     const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
     if (contact) traffic = true;                      // (the vehicle to touch)
@@ -201,6 +207,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
             e.obs_off = s * stride; e.obs_n = 1;
             obs[(size_t)s * stride] = ObPoint{ 0, 0, 0, 0.9f };    // (placed by pp_set_traffic / pp_set_world_traffic)
             if (shared) {                                 // one vehicle per world: behind its rear ego (member 0), or ahead of its front ego (member W - 1)
+                if (contact) { if (s % W == W - 1) actors.push_back(TrafficActor{ here + 20.0, -3.0, s / W, 0, lane - 1, 1, 0.9f, 0 }); continue; }      // --worlds: oncoming, ahead of the front ego
                 if (react && s % W == 0) actors.push_back(TrafficActor{ here - 15.0, 8.0, s / W, 0, lane - 1, 1, 0.9f, 0 });
                 if (!react && s % W == W - 1) actors.push_back(TrafficActor{ here + 20.0, 1.5, s / W, 0, lane - 1, 1, 0.9f, 0 });
                 continue;
@@ -243,6 +250,15 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         }
         CHECK(pp_set_episode_spawn(h, &sp, M > 1 ? in_k.data() : nullptr, M > 1 ? st_k.data() : nullptr));
     }
+    if (worlds) CHECK(pp_set_episode_worlds(h, 1));   // (part of the spawn model in force: behind pp_set_episode_spawn; the worlds are those of the fleet)
+    if (reset && shared) {                            // the world reset of §4t: set k puts a world's vehicle at its offset from start record k of the world's front ego
+        std::vector<TrafficStart> sets;
+        for (int k = 1; k < M; k++) for (int a = 0; a < n / W; a++) {
+            const SceneIn& e = in[(size_t)a * W + W - 1]; const int lane = e.loc.lane_num, id = e.loc.id[0] > 5 * k ? e.loc.id[0] - 5 * k : 0;
+            sets.push_back(TrafficStart{ arc_of(lane, e.loc.road_num, id) + 20.0, 0.0 });
+        }
+        CHECK(pp_set_episode_world_traffic(h, M, M > 1 ? sets.data() : nullptr));
+    } else
     if (reset) {                                      // last of all: set 0 is captured here; set k puts the vehicle at its offset from start record k (5 k points back)
         std::vector<TrafficStart> sets;
         for (int k = 1; k < M; k++) for (int s = 0; s < n; s++) {
@@ -326,6 +342,22 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         for (int k = 0; k < M; k++) std::printf(" %d", wt[k]);
         std::printf("\n");
     }
+    if (worlds) {
+        std::vector<EpisodeStats> es(n);
+        CHECK(pp_get_episode_stats(h, es.data(), n));
+        int with_world = 0, together = 0;
+        for (int s = 0; s < n; s++) with_world += (es[(size_t)s].last_cause & DMPP_EGO_WORLD) != 0;
+        for (int a = 0; a < n / W; a++) { bool same = true; for (int j = 1; j < W; j++) same = same && es[(size_t)a * W + j].n_episodes == es[(size_t)a * W].n_episodes; together += same; }
+        std::printf("worlds: the world is the unit of an episode: %d of %d worlds have the same episode count in every member, %d egos last ended because a partner did (DMPP_EGO_WORLD)\n",
+                    together, n / W, with_world);
+    }
+    if (reset && shared) {
+        const int nv = (int)actors.size();
+        std::vector<int32_t> nr((size_t)nv);
+        CHECK(pp_get_episode_world_traffic_resets(h, nr.data(), nv));
+        long long resets = 0; for (int a = 0; a < nv; a++) resets += nr[(size_t)a];
+        std::printf("reset-traffic: %d set(s) of start states per world vehicle, %lld vehicle resets\n", M, resets);
+    } else
     if (reset) {
         std::vector<int32_t> nr(n); std::vector<EpisodeStats> es(n);
         CHECK(pp_get_episode_traffic_resets(h, nr.data(), n));
@@ -382,7 +414,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
 
 int main(int argc, char** argv)
 {
-    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false; int starts = 0, log_cap = 0, trace_depth = 0, trace_post = -1, sched = 0;
+    bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false, worlds = false; int starts = 0, log_cap = 0, trace_depth = 0, trace_post = -1, sched = 0;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -398,6 +430,7 @@ int main(int argc, char** argv)
         else if (std::strcmp(argv[a], "--episodes") == 0) episodes = true;
         else if (std::strcmp(argv[a], "--contact") == 0) contact = true;
         else if (std::strcmp(argv[a], "--reset-traffic") == 0) reset = true;
+        else if (std::strcmp(argv[a], "--worlds") == 0) worlds = true;
         else if (std::strcmp(argv[a], "--starts") == 0 && a + 1 < argc) starts = std::atoi(argv[++a]);
         else if (std::strcmp(argv[a], "--schedule") == 0) {
             sched = 1;                                    // pooled unless the next word says otherwise
@@ -406,7 +439,7 @@ int main(int argc, char** argv)
         }
         else if (std::strcmp(argv[a], "--log") == 0 && a + 1 < argc) log_cap = std::atoi(argv[++a]);
         else if (std::strcmp(argv[a], "--score-trace") == 0 && a + 1 < argc) { if (std::sscanf(argv[++a], "%d,%d", &trace_depth, &trace_post) < 1) trace_depth = -1; }
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react] [--episodes [--starts M] --contact --worlds [--reset-traffic]]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
@@ -414,15 +447,17 @@ int main(int argc, char** argv)
     if (episodes && !route) { std::fprintf(stderr, "--episodes restarts egos that arrive: use it with --route\n"); return 2; }
     if ((starts || contact) && !episodes) { std::fprintf(stderr, "--starts / --contact shape the restarts: use them with --route --episodes\n"); return 2; }
     if (starts < 0 || starts > DMPP_EPISODE_MAX_STARTS) { std::fprintf(stderr, "--starts takes 1 .. %d\n", DMPP_EPISODE_MAX_STARTS); return 2; }
-    if (contact && (react || shared)) { std::fprintf(stderr, "--contact brings its own oncoming vehicle: not with --react / --shared\n"); return 2; }
-    if (starts && shared) { std::fprintf(stderr, "--starts places its records behind each ego on its lane: not with the platoons of --shared\n"); return 2; }
+    if (worlds && !(shared && episodes && contact)) { std::fprintf(stderr, "--worlds restarts a world as a whole: use it with --route --fleet --traffic --shared --episodes --contact\n"); return 2; }
+    if (worlds && sched) { std::fprintf(stderr, "--worlds draws once per world: not with --schedule\n"); return 2; }
+    if (contact && ((react && !worlds) || (shared && !worlds))) { std::fprintf(stderr, "--contact brings its own oncoming vehicle: not with --react / --shared\n"); return 2; }
+    if (starts && shared && !worlds) { std::fprintf(stderr, "--starts places its records behind each ego on its lane: not with the platoons of --shared\n"); return 2; }
     if (sched && !(route && episodes && starts > 0)) { std::fprintf(stderr, "--schedule draws among start records: use it with --route --episodes --starts M\n"); return 2; }
     if (reset && !(route && episodes && (traffic || contact))) { std::fprintf(stderr, "--reset-traffic puts a restarted ego's vehicle back: use it with --route --episodes --traffic (or --contact)\n"); return 2; }
-    if (reset && shared) { std::fprintf(stderr, "--reset-traffic resets per-scene traffic: a vehicle of --shared belongs to a whole world\n"); return 2; }
+    if (reset && shared && !worlds) { std::fprintf(stderr, "--reset-traffic resets per-scene traffic: a vehicle of --shared belongs to a whole world\n"); return 2; }
     if (log_cap && !(route && episodes)) { std::fprintf(stderr, "--log records how episodes ended: use it with --route --episodes\n"); return 2; }
     if (log_cap < 0 || log_cap > DMPP_EPISODE_LOG_MAX) { std::fprintf(stderr, "--log takes 1 .. %d records\n", DMPP_EPISODE_LOG_MAX); return 2; }
     if (trace_depth < 0 || trace_depth > DMPP_SCORE_TRACE_MAX || (trace_depth && trace_post >= trace_depth)) { std::fprintf(stderr, "--score-trace takes DEPTH 1 .. %d and POST 0 .. DEPTH - 1\n", DMPP_SCORE_TRACE_MAX); return 2; }
-    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post, sched);
+    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post, sched, worlds);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;

@@ -525,7 +525,7 @@ int  pp_episode_schedule_weights(const EpisodeSchedule* m, const EpisodeSchedule
  * CALL IT LAST: every successful pp_set_traffic / pp_set_world_traffic / pp_set_traffic_follow / pp_set_episodes /
  * pp_set_episode_spawn (NULL or n = 0 included), and pp_set_scenes / pp_set_egos / pp_set_n_scenes through them, switches the reset
  * off - each invalidates what the table was captured from (§7, "Feature life cycle").
- * Refused with nothing changed - PP_ERR_STATE: no per-scene traffic on (world traffic, §4j, has no owning scene: out of scope),
+ * Refused with nothing changed - PP_ERR_STATE: no per-scene traffic on (world traffic, §4j, has no owning scene: pp_set_episode_world_traffic below),
  * episodes off, an update staged for the next tick.  PP_ERR_ARG: n_sets < 0 or neither 1 nor n_starts, NULL starts with n_sets > 1,
  * an s that is not finite, a v that is not finite or is < 0.  One host wait, behind every tick and advance enqueued so far.
  * A handle that never makes the call allocates and launches none of this.
@@ -534,6 +534,37 @@ int  pp_episode_schedule_weights(const EpisodeSchedule* m, const EpisodeSchedule
  * outside 0 .. n_actors. */
 int  pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts);
 int  pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n);
+
+/* ---- world episodes: the egos of a world restart together ----------------------------------------------------------
+ * With the spawn model alone every scene ends and restarts on its own: on a fleet (pp_set_fleet) the partner of an ended ego drives on
+ * through the next "episode".  pp_set_episode_worlds(h, 1) makes the WORLD the unit of an episode: from then on every pp_advance_async
+ * runs k_respawn_world in the place of k_respawn_spawn.  When any ego of a world has a cause of its own (a flag of end_mask, TIMEOUT,
+ * CONTACT - contact with a peer slot included), EVERY ego of that world ends on this advance: cause word = its own | DMPP_EGO_WORLD
+ * when another member had a cause (a sole ender carries no WORLD bit; a member with no cause of its own ends with exactly 256).  The
+ * world draws ONE start record index k - the hash / round robin of §4l on the world's first scene -, walks the candidates with the
+ * clearance test against the OWN obstacle entries of every member (EpisodeSpawn.check bit 0; bit 1 is ignored: every ego of the world
+ * moves), and every member restarts on its record k; the EpisodeSpawnStats words of the step are the same in every member.  WORLD,
+ * like CONTACT, has no n_end slot.  Worlds are those of the fleet in force AT EACH ADVANCE; without a fleet every scene is a world
+ * of one and every byte is §4l's.  The per-scene traffic reset (§4m), the episode log (§4n: cause carries 256), the score trace and
+ * the ego tracker run unchanged behind it.
+ * Part of the spawn model in force, like the schedule: every successful pp_set_episode_spawn (NULL included) and whatever switches
+ * the spawn model off switches it off; it retires nothing itself.  on == 0: off (k_respawn_spawn runs again; the world traffic reset
+ * below goes off with it).  Refused with nothing changed - PP_ERR_STATE: an update staged, the spawn model off, a schedule in force
+ * (pp_set_episode_schedule is refused in turn while world episodes are on).  No host wait.
+ *
+ * ---- world traffic reset: the vehicles of a restarted world go back to a start state ---------------------------------
+ * pp_set_episode_world_traffic is pp_set_episode_traffic for the vehicles of pp_set_world_traffic: set 0 is captured by the call,
+ * sets 1 .. n_sets - 1 come from `starts` (set k of vehicle a at (k - 1) * n_actors + a), n_sets is 1 or n_starts.  From then on every
+ * pp_advance_async runs k_reset_world_traffic behind its world-traffic kernel: a vehicle of world w resets iff EpisodeStats.age == 0
+ * at the world's FIRST scene behind the episode step, onto set cur_start of that scene (n_sets > 1) or set 0; s', v', the ObPoint in
+ * every member scene and the counter as §4m.  n_sets == 0: off.  Switched off by everything that switches the per-scene reset off,
+ * by world traffic, the spawn model or episodes going off or being set again, by pp_set_fleet, and by pp_set_episode_worlds(h, 0).
+ * Refused with nothing changed - PP_ERR_STATE: world traffic not on, episodes / spawn model / world episodes not on, an update staged;
+ * PP_ERR_ARG: as pp_set_episode_traffic.  One host wait.  pp_get_episode_world_traffic_resets: one counter per vehicle since the last
+ * successful set call, readable after the reset went off; waits as pp_get_traffic_state does. */
+int  pp_set_episode_worlds(pp_handle h, int on);
+int  pp_set_episode_world_traffic(pp_handle h, int n_sets, const TrafficStart* starts);
+int  pp_get_episode_world_traffic_resets(pp_handle h, int32_t* n_resets, int n);
 
 /* ---- episode log: one record per ended episode, appended on the device ---------------------------------------------
  * EpisodeStats is an aggregate per scene and RolloutScore runs across restarts: neither says which episode ended how.  pp_set_episode_log

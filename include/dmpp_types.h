@@ -429,6 +429,7 @@ typedef struct EpisodeStats {
  * egos of the scene's world before a restart takes it. */
 #define DMPP_EPISODE_MAX_STARTS 16
 #define DMPP_EGO_CONTACT 128    /* cause words only (last_cause, EgoTrace.flags of a restart): the ego touched an obstacle */
+#define DMPP_EGO_WORLD 256      /* cause words only (EpisodeStats.last_cause, EpisodeRecord.cause): another ego of the scene's world ended on this advance (§4s) */
 typedef struct EpisodeSpawn {
     uint64_t seed;              /* of the hashed start choice                                              */
     double   clearance;         /* metres, finite, >= 0: a start record this close to an obstacle or ego is blocked */
@@ -460,7 +461,7 @@ typedef struct TrafficStart {
 #define DMPP_EPISODE_LOG_MAX (1 << 20)
 typedef struct EpisodeRecord {
     int32_t scene, episode;     /* scene index; number of this episode within the scene, 0-based (EpisodeStats.n_episodes - 1 behind the restart) */
-    int32_t start, cause;       /* start record the ENDED episode ran on (0 without a spawn model); cause word (DMPP_EGO_* | TIMEOUT | CONTACT) */
+    int32_t start, cause;       /* start record the ENDED episode ran on (0 without a spawn model); cause word (DMPP_EGO_* | TIMEOUT | CONTACT | WORLD) */
     int32_t age, seq;           /* advances of the episode; number of the advance that ended it, counted from pp_set_episode_log (first = 0) */
     int64_t tick;               /* pp_tick_id of the last tick of the episode: the tick the ending advance read */
     double  dist;               /* EpisodeStats.last_dist */

@@ -37,6 +37,12 @@ EPISODES=1 SPAWN=M SCHEDULE=pooled|scene (with CONTACT=1 / RESET=1 as above): bo
 for), and the second leg the scenario schedule as well (pp_set_episode_schedule, DESIGN.md §4p: k_respawn_sched in the place of
 k_respawn_spawn, in pooled scope k_fold_schedule behind it) - the default model in that scope, contact the failure.  The rows are read
 behind the timed rollout, outside the timing.  With ONE_ROLLOUT one more leg with the schedule on alone.
+EPISODES=1 WORLDS=1 (with FLEET=K, FLEET_WORLD=<scenes per world>, SPAWN=M, CONTACT=1, RESET=1 as above): both legs have the fleet - K peer
+slots behind every scene's OBS own entries, worlds of FLEET_WORLD consecutive scenes (0 or unset: 16) - and that spawn model on, and the
+second leg world episodes as well (pp_set_episode_worlds, DESIGN.md §4s: k_respawn_world in the place of k_respawn_spawn): when one ego
+of a world ends, its whole world restarts.  RESET=1 keeps the per-scene reset of §4m on in both legs.  The workloads differ - a world
+restarts as often as ALL its members end -: the episodes ended and the members that ended with DMPP_EGO_WORLD are printed beside the
+rates.  With ONE_ROLLOUT one more leg with world episodes on alone.
 SCORE=1 TRACE=depth: every run has a scored rollout leg without and one with the score trace (pp_set_score_trace: the default model with
 `depth` records per scene, DESIGN.md §4o: k_score_ego<false, true> in the place of <false, false>), alternating; headers and one ring are
 read behind the timed rollout, outside the timing.  TRACE_TRIGGER=mask replaces the model's trigger (0: rings that never freeze, so every
@@ -206,7 +212,10 @@ RESET = os.environ.get("RESET", "0") == "1"
 SCHEDULE = os.environ.get("SCHEDULE", "")
 
 
-def spawn_run(on, reset=False, sched=""):
+WORLDS = os.environ.get("WORLDS", "0") == "1"
+
+
+def spawn_run(on, reset=False, sched="", worlds=None):
     import route_scenes as rs
     import traffic_model as tm
     import traffic_scenes as ts
@@ -218,6 +227,11 @@ def spawn_run(on, reset=False, sched=""):
     sc["mot_pool"] = None
     sc["obs_pool"]["x"], sc["obs_pool"]["y"], sc["obs_pool"]["radius"] = 1e6, 1e6, 0.5
     sc["scene_in"]["obs_n"] = k_obs
+    stride = k_obs + (FLEET if worlds is not None else 0)
+    if stride != k_obs:                   # room for the peer slots behind every scene's own entries
+        pool = np.zeros((n, stride), dm.ObPoint)
+        pool["x"], pool["y"], pool["radius"] = 1e6, 1e6, 0.5
+        sc["obs_pool"], sc["scene_in"]["obs_off"], sc["n_obs"] = pool.reshape(-1), np.arange(n) * stride, stride
     polylines = [(ts.ring_track(dm, m, 1), True), (ts.ring_track(dm, m, 2), True)]
     tracks, pts = ts.pack(dm, polylines)
     cums = [tm.cumulative(p["x"], p["y"], True) for p, _ in polylines]
@@ -227,11 +241,15 @@ def spawn_run(on, reset=False, sched=""):
         lane = int(loc["lane_num"])
         here = cums[lane - 1][ts.SEG * (int(loc["road_num"]) - 1) + int(loc["id"][lane - 1])]
         rows.append((here + 20.0, -3.0, s, 0, lane - 1, 7, 0.9))
-    pl = dm.Planner(rcfg, device=0, **rs.caps(m, n, k_obs))
+    pl = dm.Planner(rcfg, device=0, **rs.caps(m, n, stride))
     pl.set_map(m)
     pl.set_egos(sc, with_motion=False)
     pl.set_state(sc["state"])
     pl.set_route(legs, rf)
+    if worlds is not None:
+        fm = dm.default_fleet_model()
+        fm["max_peers"] = FLEET
+        pl.set_fleet(list(range(0, n, FLEET_WORLD if FLEET_WORLD > 0 else 16)) + [n], fm)
     pl.set_traffic(tracks, pts, ts.actors(dm, rows))
     pl.set_episodes()
     if on:
@@ -239,6 +257,8 @@ def spawn_run(on, reset=False, sched=""):
         sp["n_starts"], sp["contact"] = M, int(CONTACT)
         roll = lambda a: np.concatenate([np.roll(a, -k, axis=0) for k in range(1, M)]) if M > 1 else None
         pl.set_episode_spawn(sp, roll(sc["scene_in"]), roll(sc["state"]))
+    if worlds:
+        pl.set_episode_worlds()
     if reset:                             # last: set 0 is captured here; set k puts the vehicle 20 m ahead of start record k along its OWN track
         sets = None
         if on and M > 1:
@@ -262,6 +282,7 @@ def spawn_run(on, reset=False, sched=""):
     ss = pl.episode_spawn_stats() if on else None
     spawn_run.resets = int(pl.episode_traffic_resets().sum()) if reset else 0
     spawn_run.age1 = int((pl.episode_stats()["min_age"] == 1).sum())
+    spawn_run.world_ends = int(((pl.episode_stats()["last_cause"] & dm.EGO_WORLD) != 0).sum())
     if sched:
         rows = pl.episode_schedule()
         spawn_run.rows = (int(rows["n_end"].sum()), int(rows["n_fail"].sum()))
@@ -387,6 +408,22 @@ def streamed_run():
     return n * steps / dt
 
 
+if os.environ.get("EPISODES", "0") == "1" and WORLDS:
+    off, on = [], []
+    for r in range(runs):
+        a, ea, _ = spawn_run(True, reset=RESET, worlds=False)
+        b, eb, (nc, nb, nr) = spawn_run(True, reset=RESET, worlds=True)
+        off.append(a), on.append(b)
+        print("run %d  %d ring egos with traffic in worlds of %d (K %d), spawn model on (M %d, contact %d, reset %d)  worlds off %.3f M ticks/s (%d episodes ended)   "
+              "world episodes on %.3f M ticks/s (%d episodes ended, %d on contact, %d egos whose last cause has WORLD, %d blocked, %d rejected)" %
+              (r, n, FLEET_WORLD if FLEET_WORLD > 0 else 16, FLEET, max(SPAWN, 1), int(CONTACT), int(RESET), a / 1e6, ea, b / 1e6, eb, nc, spawn_run.world_ends, nb, nr), flush=True)
+    print("median  %d ring egos  world episodes off %.3f M ticks/s (spread %.3f)   on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout of each, so that one trace holds both kernels
+        spawn_run(True, reset=RESET, worlds=False)
+        spawn_run(True, reset=RESET, worlds=True)
+    sys.exit(0)
 if FLEET > 0:
     off, on = [], []
     for r in range(runs):
