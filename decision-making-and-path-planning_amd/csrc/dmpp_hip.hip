@@ -344,6 +344,7 @@ struct pp_planner {
     int bucket_cap0 = 0, max_path0 = 0;
     // search: k_search_lds<kind> with `lds_budget` data words per view in LDS; scenes that need more go to k_search_gbm
     int search_kind = 0; int search_meta_bytes = 0; int lds_budget = 0, lds_budget_max = 0; bool lds_budget_fixed = false, search_force_gbm = false, budget_from_need = false;
+    int lds_budget_launch = 0; bool coresident = true;     // the budget the group's search is launched with (dmpp::coresident_budget of lds_budget; DMPP_CORESIDENT=0: the same)
     int gbm_lds = 0; int search_slots = 512; size_t search_static_lds = 0;   // static LDS of k_search<kind>
     DevBuf<int32_t> d_ovf[kBuf], d_need[kObs]; HostPin<int32_t> h_need;   // h_need: pinned, [kObs], written by k_score (-1: nothing yet)
     int need_seen = 0;
@@ -694,6 +695,12 @@ int group_cap(int max_scenes, int pipeline_min, int forced, size_t item_bytes)
 // Ticks per group for a batch of n scenes: the knob if set (DMPP_TICK_GROUP), else the smallest G whose G * n work items are at
 // least twice the search's workgroup slots (the slots freed by the short scenes then have work while the long ones run);
 // at most the slots the handle's buffers hold (gcap <= kGroupMax).
+// The workgroup that should fit beside the searching workgroups of a CU (dmpp::coresident_budget): the larger of k_planning's and
+// k_score<4>'s, both all dynamic LDS.  (k_decision's 16 granules start in what a retiring search frees.)
+constexpr size_t kBesideSearchLds = std::max(sizeof(dmpp::PlanShared), sizeof(dmpp::ScoreShared<4>));
+static_assert(dmpp::lds_granules(sizeof(dmpp::SearchLds<dmpp::closed_log_of<0>()>) + 64 + 4096 + 8 * 1600) * 6 + dmpp::lds_granules(kBesideSearchLds) <= (int)(dmpp::kLdsPerCu / dmpp::kLdsGranule),
+              "512 x 512, 1,600 words per view: six searching workgroups of 19 granules and a k_planning or k_score workgroup on one CU");
+
 int group_size(int n, int search_slots, int gcap, int forced)
 {
     int g = forced;
@@ -841,6 +848,8 @@ int setup_grid_launch(pp_planner* h)
     if (const char* e = std::getenv("DMPP_LDS_BUDGET")) {                                                // ... a fixed budget (words per view)
         h->lds_budget = std::max(1, std::min(std::atoi(e), h->lds_budget_max)); h->lds_budget_fixed = true;
     } else h->lds_budget = 0;                                                                            // chosen at the first tick (obstacle density), then adaptive
+    h->lds_budget_launch = h->lds_budget;
+    if (const char* e = std::getenv("DMPP_CORESIDENT")) h->coresident = std::atoi(e) != 0;               // A/B knob: 0 = launch with the policy's budget as it is
     const size_t items = (size_t)h->gcap * h->caps.max_scenes;          // work items of a search set
     auto zeroed_once = [&](DevBuf<int32_t>& b, size_t count) {           // allocated - and cleared - by the first configuration with the grid stage
         if (b) return (int)PP_OK;
@@ -1271,7 +1280,7 @@ int flush_group(pp_planner* h)
         hipLaunchKernelGGL(dmpp::k_order, dim3(1), dim3(dmpp::kOrderBlock), 0, sm, items, h->d_cost[piped ? p : h->grp_p_prev], h->d_perm[p]);
     int32_t* need = h->d_need[set0];                                   // the group's LDS need and retry count
     {
-        const int budget = h->search_force_gbm ? 0 : h->lds_budget;
+        const int budget = h->search_force_gbm ? 0 : h->lds_budget_launch;
         const bool wide = items <= kScoreWideMaxScenes;       // a few scenes: sixteen waves set each scene up (the latency-bound tick)
         const size_t dyn = std::max((size_t)h->search_meta_bytes + 8 * (size_t)budget, (size_t)h->gbm_lds);
         const bool use_spill = h->d_ospill[p] != nullptr && c.bucket_cap > DMPP_OPEN_CAP;     // scenes whose open list outgrows LDS are searched again, spilling
@@ -1343,6 +1352,11 @@ void open_group(pp_planner* h, int n, bool piped)
     const dmpp::SearchBudget b = dmpp::search_budget(h->search_static_lds, h->search_meta_bytes, h->gbm_lds, h->lds_budget_max, h->n_cus, n, h->grp_G, h->cur_in().n_obs_total,
                                                      need, h->lds_budget, h->budget_from_need, h->lds_budget_fixed, h->search_force_gbm);
     h->lds_budget = b.budget; h->budget_from_need = b.from_need; h->search_slots = b.slots;
+    // what the launch gets: room for a front or scoring workgroup beside the searches, where a tighter budget buys it.  The
+    // policy's own budget stays in lds_budget for the next group's hysteresis; G and search_slots keep the policy's count.
+    h->lds_budget_launch = h->coresident ? dmpp::coresident_budget(h->search_static_lds, h->search_meta_bytes, h->gbm_lds, h->lds_budget_max, h->n_cus, h->grp_G * n, need,
+                                                                    b.budget, h->lds_budget_fixed, h->search_force_gbm, kBesideSearchLds)
+                                         : b.budget;
 }
 
 }  // namespace
@@ -1578,7 +1592,7 @@ int pp_get_search_info(pp_handle h, int32_t* lds_budget_words, int32_t* need_wor
     if (!h->d_ovf[0]) return fail(PP_ERR_STATE, "handle was created without the grid stage");
     HIP_TRY(hipSetDevice(h->device));
     { int r = flush_group(h); if (r) return r; }          // parity / item_off / need_set name the last tick only once its group is launched
-    if (lds_budget_words) *lds_budget_words = h->search_force_gbm ? 0 : h->lds_budget;
+    if (lds_budget_words) *lds_budget_words = h->search_force_gbm ? 0 : h->lds_budget_launch;
     if (need_words) {                      // what the densest scene of the last tick needed (its scoring pass has stored it by now)
         { int r = join_all(h); if (r) return r; }
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -3021,6 +3035,12 @@ int pp_search_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget
     if (budget_out) *budget_out = b.budget;
     if (from_need_out) *from_need_out = b.from_need;
     if (slots_out) *slots_out = b.slots;
+    return PP_OK;
+}
+int pp_coresident_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget_max, int n_cus, int items, int need, int budget, int mode, int32_t* budget_out)
+{
+    if (!budget_out) return fail(PP_ERR_ARG, "null output");
+    *budget_out = dmpp::coresident_budget((size_t)static_lds, meta_bytes, gbm_lds, lds_budget_max, n_cus, items, need, budget, (mode & 1) != 0, (mode & 2) != 0, kBesideSearchLds);
     return PP_OK;
 }
 // the rollout feature table (rollout_features.hpp), without a device: the feature bits a cause retires (-1: no such cause), and

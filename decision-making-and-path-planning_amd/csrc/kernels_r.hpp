@@ -154,7 +154,7 @@ struct DecShared {                                 // 19 KB: small enough to sit
     int rem_go, rem_flags;                        // remaining lane-change length tests (lane-change rule tree)
     int rem_w[2][kBlock / 64]; double rem_s[2][kBlock / 64];   // ... their per-wave run ends and partial sums
 };
-static_assert(sizeof(DecShared) <= 16 * 1280, "k_decision sits beside five searching workgroups with 16 LDS granules of 1,280 bytes");
+static_assert(sizeof(DecShared) <= 16 * 1280, "k_decision sits beside five searching workgroups with 16 LDS granules of 1,280 bytes; two fit the 19 + 14 = 33 a retiring search of the configs[1] launch budget frees");
 
 
 __device__ inline int dev_load_front(const PlannerConfig& c, const GlobalPoint3D* lane, int IdSum, int Id, GlobalPoint2D* out)
@@ -816,7 +816,7 @@ struct PlanShared {
     double sh_sum;
     int sh_found, afresh, near_id, na;
 };
-static_assert(sizeof(PlanShared) <= 12 * 1280, "k_planning: 12 LDS granules of 1,280 bytes");
+static_assert(sizeof(PlanShared) <= 12 * 1280, "k_planning: 12 LDS granules of 1,280 bytes - what dmpp::coresident_budget keeps free beside six searching workgroups of 19");
 
 __global__ void __launch_bounds__(kBlock)
 k_planning(PlannerConfig c, int n_scenes, const SceneIn* __restrict__ in, const GlobalPoint3D* __restrict__ lane_pool,

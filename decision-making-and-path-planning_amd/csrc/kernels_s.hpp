@@ -733,19 +733,56 @@ constexpr uint32_t kCodeStart = start_row();
 }  // namespace rules
 
 // ---------------------------------------------------------------------------------------
+// A slot of the closed-set hash.  While the hash is in use the expansion number of a cell is below kClosedMax, so for CL = 9
+// (grids up to 1024 x 1024: cell + 1 needs 21 bits) it rides in the top bits of the cell's own word and the hash needs no array
+// of numbers: 1 KB of LDS less, which is what lets a searching workgroup of the headline budget into 19 granules.
+//   packed:   cell + 1 in bits 0 .. 22 (0 = empty), the expansion number in bits 23 .. 31; kSeqNone = inserted but never expanded
+//             (the search ended in that step).  The CAS inserts the bare cell; the lane that inserted it adds the number.
+//   unpacked: (CL = 10, 2048 x 2048: 23 + 10 bits do not fit) the word is cell + 1, the number lies in c_seq.
 template <int CL>
-struct SearchLds {                               // the static LDS of a searching workgroup (8.2 KB at CL = 9)
+struct ClosedWord {
+    static constexpr bool kPacked = CL <= 9;
+    static constexpr int kCellBits = kPacked ? 23 : 32, kSeqBits = kPacked ? 32 - kCellBits : 16;
+    static constexpr uint32_t kCellMask = kPacked ? (1u << 23) - 1u : 0xFFFFFFFFu;
+    static constexpr uint32_t kSeqNone = (1u << kSeqBits) - 1u;
+    __host__ __device__ static constexpr uint32_t key(uint32_t e) { return e & kCellMask; }                       // cell + 1 of a slot (0: empty)
+    __host__ __device__ static constexpr uint32_t seq(uint32_t e) { return kPacked ? e >> (kCellBits & 31) : 0u; }  // (packed) its expansion number
+    __host__ __device__ static constexpr uint32_t pack(uint32_t keyc, uint32_t sq) { return kPacked ? keyc | (sq << (kCellBits & 31)) : keyc; }
+};
+// the largest grid of each kind of search (K = 0 / 1 / 2: lines of <= 16 / 32 / 64 words of 32 cells): cell + 1 beside the number
+template <int K> constexpr uint64_t search_cells_max() { return K == 0 ? 512ull * 512ull : (K == 1 ? 1024ull * 1024ull : 2048ull * 2048ull); }
+struct NoClosedSeq {};
+template <int CL>
+struct SearchLds {                               // the static LDS of a searching workgroup (7.2 KB at CL = 9)
+    using CW = ClosedWord<CL>;
     static constexpr int kClosedLog = CL, kClosedTab = 1 << CL, kClosedMax = 3 << (CL - 2);
-    alignas(8) uint32_t o_ent[kOpenCap];       // (8: the set-up stages footprints here, RasterStage)  x | y << 12 | arriving direction << 24 | kEntry* flags << 28
+    static_assert((uint32_t)kClosedMax <= CW::kSeqNone, "every expansion number of the hash lies below the never-expanded marker");
+    alignas(16) uint32_t o_ent[kOpenCap];      // (the set-up stages footprints here, RasterStage, which needs 8; 16: sizeof is what the kernel is charged, the dynamic LDS follows on 16)  x | y << 12 | arriving direction << 24 | kEntry* flags << 28
     uint16_t o_f2[kOpenCap];        // f / 2, 0xFFFF = dead slot
     uint16_t o_run[kOpenCap];       // run length of the move that reached the cell
-    uint32_t c_tab[kClosedTab];     // closed cells (cell + 1, 0 = empty): open addressing, linear probing
+    uint32_t c_tab[kClosedTab];     // closed cells (ClosedWord: cell + 1, 0 = empty; packed: its expansion number above it): open addressing, linear probing
     uint16_t c_info[kClosedTab];    // arriving direction | run length << 4 of the cell in the same slot
-    uint16_t c_seq[kClosedTab];     // its expansion number (0xFFFF: inserted but never expanded - the search ended in that step)
+    [[no_unique_address]] std::conditional_t<CW::kPacked, NoClosedSeq, uint16_t[kClosedTab]> c_seq;     // (unpacked only) its expansion number, kSeqNone: never expanded
     uint32_t job[kMaxDiag + 8];     // the jumps of the current step, x | y << 12 | s << 24: diagonal ones (<= 16), then straight ones (<= 8)
     int s_wave[kSearchSetupWavesWide + 1];
     int s_flag;
+    // the expansion number of the cell inserted in `slot`, by the lane that inserted it
+    __device__ __forceinline__ void set_seq(uint32_t slot, uint32_t sq)
+    {
+        // (packed: an OR into the bare cell the CAS left - one LDS instruction without a result, and the cell need not be kept for it)
+        if constexpr (CW::kPacked) { __hip_atomic_fetch_or(&c_tab[slot], CW::pack(0u, sq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+        else c_seq[slot] = (uint16_t)sq;
+    }
+    __device__ __forceinline__ uint32_t seq_of(uint32_t slot, uint32_t e) const
+    {
+        if constexpr (CW::kPacked) return CW::seq(e); else return c_seq[slot];
+    }
 };
+static_assert(search_cells_max<0>() + 1 <= ClosedWord<closed_log_of<0>()>::kCellMask && search_cells_max<1>() + 1 <= ClosedWord<closed_log_of<1>()>::kCellMask &&
+              search_cells_max<2>() + 1 <= ClosedWord<closed_log_of<2>()>::kCellMask, "cell + 1 of the largest grid of each kind fits the cell bits of a hash word");
+static_assert(ClosedWord<closed_log_of<0>()>::kCellBits + ClosedWord<closed_log_of<0>()>::kSeqBits <= 32 && ClosedWord<closed_log_of<1>()>::kPacked,
+              "kinds 0 and 1: cell bits + number bits in one 32-bit word");
+static_assert(sizeof(SearchLds<closed_log_of<0>()>) == 7344, "static LDS of k_search<0 | 1>: with 4,096 B of metas and 1,600 words per view, 19 granules of 1,280 B");
 
 struct SearchOut { int status, n_exp, n_push, n_rounds, path_cost, path_len; uint64_t digest; };
 
@@ -755,8 +792,8 @@ __device__ __forceinline__ uint64_t hash_digest(const LDS& L, int lane)
 {
     uint64_t dg = 0;
     for (int i = lane; i < LDS::kClosedTab; i += DMPP_WAVE) {
-        const uint32_t e = L.c_tab[i]; const uint32_t sq = L.c_seq[i];
-        if (e && sq != 0xFFFFu) dg += mix64(((uint64_t)sq << 32) | (uint64_t)(e - 1u));
+        const uint32_t e = L.c_tab[i]; const uint32_t sq = L.seq_of((uint32_t)i, e);
+        if (e && sq != LDS::CW::kSeqNone) dg += mix64(((uint64_t)sq << 32) | (uint64_t)(LDS::CW::key(e) - 1u));
     }
     return dg;
 }
@@ -920,6 +957,7 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
 #define DBG_MARK(slot)
 #endif
     constexpr int kClosedLog = LDS::kClosedLog, kClosedTab = LDS::kClosedTab, kClosedMax = LDS::kClosedMax;
+    using CW = typename LDS::CW;
     const int W = c.grid_w, H = c.grid_h, N = W * H;
     const int gx = goal % W, gy = goal / W;
     // live entries allowed: the specification's bucket_cap; without a spill area (a handle made for bucket_cap <= kOpenCap) what LDS holds
@@ -1040,14 +1078,14 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
             uint32_t hh = ((uint32_t)cell * 2654435761u) >> (32 - kClosedLog);
             uint32_t old = 0u;
             if (valid) old = atomicCAS(&L.c_tab[hh], 0u, keyc);
-            if (old == keyc) valid = false;                               // already closed
+            if (CW::key(old) == keyc) valid = false;                      // already closed (the slot may carry its number by now)
             bool collide = valid && old != 0u;
             for (int probe = 1; probe < kClosedTab && wave_ballot(collide); probe++) {
                 if (collide) {
                     hh = (hh + 1) & (kClosedTab - 1);
                     old = atomicCAS(&L.c_tab[hh], 0u, keyc);
-                    if (old == keyc) valid = false;
-                    collide = old != 0u && old != keyc;
+                    if (CW::key(old) == keyc) valid = false;
+                    collide = old != 0u && CW::key(old) != keyc;
                 }
             }
             my_slot = hh;                                                 // valid: inserted here (its direction | run and number follow below)
@@ -1064,7 +1102,7 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
                 wave_sync();
                 for (int i = lane; i < kClosedTab; i += DMPP_WAVE) {
                     const uint32_t e2 = L.c_tab[i];
-                    if (e2) { const int cc = (int)e2 - 1; atomicOr(&closed[cc >> 5], 1u << (cc & 31)); pin[cc] = L.c_info[i]; }
+                    if (e2) { const int cc = (int)CW::key(e2) - 1; atomicOr(&closed[cc >> 5], 1u << (cc & 31)); pin[cc] = L.c_info[i]; }
                 }
                 __threadfence();
                 wave_sync();
@@ -1090,13 +1128,15 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
         }
         {
             const int seq = n_exp + __popc(vm & ((1u << node) - 1u));
-            // the hash entry of every cell inserted in this step: direction | run, and its expansion number (0xFFFF for one that
+            // the hash entry of every cell inserted in this step: direction | run, and its expansion number (kSeqNone for one that
             // was inserted but cut off by the end of the search) - the digest is summed from the hash at the end, off the chain of steps
-            if (inserted && __builtin_expect(hash_complete, 1)) { L.c_info[my_slot] = (uint16_t)(d | (run_in << 4)); L.c_seq[my_slot] = valid ? (uint16_t)seq : (uint16_t)0xFFFFu; }
+            if (inserted && __builtin_expect(hash_complete, 1)) L.c_info[my_slot] = (uint16_t)(d | (run_in << 4));
             if (valid) {
                 if (__builtin_expect(!hash_complete, 0)) { pin[cell] = (uint16_t)(d | (run_in << 4)); digest += mix64(((uint64_t)(uint32_t)seq << 32) | (uint32_t)cell); }
                 if (order && seq < order_cap) order[seq] = cell;
             }
+            // (the number behind the stores above: in front of them the loop takes two more VGPRs)
+            if (inserted && __builtin_expect(hash_complete, 1)) L.set_seq(my_slot, valid ? (uint32_t)seq : CW::kSeqNone);
         }
         if (vm && f > fmax) { fmax = f; n_rounds++; }
         n_exp += __popc(vm);
@@ -1253,7 +1293,7 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
                 int v = -1;
                 for (int probe = 0; probe < kClosedTab; probe++) {
                     const uint32_t e2 = L.c_tab[hh]; const int inf = L.c_info[hh];
-                    if (e2 == (uint32_t)cur + 1u) { v = inf; break; }
+                    if (CW::key(e2) == (uint32_t)cur + 1u) { v = inf; break; }
                     if (e2 == 0u) break;
                     hh = (hh + 1) & (kClosedTab - 1);
                 }
@@ -1277,7 +1317,7 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
             (void)c4;
             for (int i = lane; i < kClosedTab; i += DMPP_WAVE) {
                 const uint32_t e2 = L.c_tab[i];
-                if (e2) pin[(int)e2 - 1] = L.c_info[i];
+                if (e2) pin[(int)CW::key(e2) - 1] = L.c_info[i];
             }
             __threadfence();
             wave_sync();

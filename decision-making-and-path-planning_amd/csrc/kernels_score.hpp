@@ -58,9 +58,10 @@ struct ScoreShared {
     int best, n_rel;
 };
 static_assert(sizeof(ScorePart) * 4 <= sizeof(ScoreLists), "k_score<4>: the partial sums of the left-over candidate fit over the obstacle lists and buckets");
-// A searching workgroup of the configs[1] budget holds 21 LDS granules of 1,280 bytes and six of them leave 2 of a CU's 128 free:
-// a retiring search frees room for 23 granules, which is TWO scoring workgroups at 11 granules each (one at 12 or more).
-static_assert(sizeof(ScoreShared<4>) <= 11 * 1280, "k_score<4>: two workgroups per freed search slot at the configs[1] budget");
+// A searching workgroup of the configs[1] launch budget holds 19 LDS granules of 1,280 bytes and six of them leave 14 of a CU's
+// 128 free (dmpp::coresident_budget): one scoring workgroup starts beside six searches, and a retiring search frees room for 33
+// granules, which is THREE scoring workgroups at 11 granules each.  (At 21 + 2 = 23, the policy's own budget, it is two.)
+static_assert(sizeof(ScoreShared<4>) <= 11 * 1280, "k_score<4>: one workgroup in the 14 granules beside six searches, two per freed search slot even at the policy's budget");
 
 // The value of the lane below / above in the wave; lane 0 / lane 63 keep their own.  A whole-wave DPP shift (wave_shr:1: lane l
 // reads lane l - 1; wave_shl:1: lane l + 1) is one v_mov per dword, against an LDS-crossbar permute with its address and its wait.

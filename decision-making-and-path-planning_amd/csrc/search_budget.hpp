@@ -66,4 +66,32 @@ inline SearchBudget search_budget(size_t static_lds, int meta_bytes, int gbm_lds
     return { budget, from_need, search_wgs_per_cu_unrounded(per_wg) * cus };
 }
 
+// LDS granules a workgroup of `bytes` holds, and those that stay free on a CU beside `wgs` workgroups of per_wg bytes
+constexpr int lds_granules(size_t bytes) { return (int)((bytes + kLdsGranule - 1) / kLdsGranule); }
+constexpr int lds_granules_free(int wgs, size_t per_wg) { return (int)(kLdsPerCu / kLdsGranule) - wgs * lds_granules(per_wg); }
+
+// The co-residency step behind the policy: the budget a group's search is LAUNCHED with, given the one search_budget() chose.
+// While the work items outnumber the slots every CU holds `wgs` searching workgroups all the time, and a front or scoring
+// workgroup starts only in what they leave free.  When that is less than a workgroup of `beside_lds` bytes needs (the larger of
+// k_planning's and k_score<4>'s) and a smaller budget - not below the tight one, need + max(need / 32, 96), and with the same
+// `wgs` - leaves enough, the largest such multiple of 64 words is taken: 64 obstacles at 512 x 512 need 1,498 words, the policy
+// keeps 1,792 = 21 granules, six per CU, 2 free; at 1,600 a workgroup is 19 granules and 14 stay free beside six of them.
+// Nothing changes with a slot for every item, a fixed or dense budget, no need yet, or when no such budget exists.  The caller
+// keeps the policy's budget for its next call of search_budget(): the hysteresis there must not see this step's output.
+inline int coresident_budget(size_t static_lds, int meta_bytes, int gbm_lds, int budget_max, int n_cus, int items, int need, int budget,
+                             bool fixed, bool dense, size_t beside_lds)
+{
+    if (fixed || dense || need < 0 || budget <= 0) return budget;
+    auto per_wg = [&](int b) { return static_lds + 64 + std::max((size_t)meta_bytes + 8 * (size_t)b, (size_t)gbm_lds); };
+    const int wgs = search_wgs_per_cu(per_wg(budget)), want = lds_granules(beside_lds);
+    if (items <= wgs * std::max(1, n_cus) || lds_granules_free(wgs, per_wg(budget)) >= want) return budget;
+    const int tight = std::min(budget_max, (need + std::max(need / 32, 96) + 63) / 64 * 64);
+    for (int b = budget / 64 * 64; b >= tight && b > 0; b -= 64) {
+        if (b == budget) continue;
+        if (search_wgs_per_cu(per_wg(b)) != wgs) break;              // (a smaller budget never holds fewer workgroups)
+        if (lds_granules_free(wgs, per_wg(b)) >= want) return b;
+    }
+    return budget;
+}
+
 }  // namespace dmpp

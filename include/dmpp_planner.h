@@ -692,6 +692,14 @@ int pp_tick_group_const(int which);
  * Out (any may be NULL): the new budget, whether it now comes from a need, the slots.  No device needed. */
 int pp_search_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget_max, int n_cus, int n_scenes, int group, int n_obs_total,
                      int need, int budget, int from_need, int mode, int32_t* budget_out, int32_t* from_need_out, int32_t* slots_out);
+/* The co-residency step behind that policy ("LDS budget and the dense form"): the budget a group's search is launched
+ * with, given the one pp_search_budget chose (`budget`), the work items of the group (scenes x ticks) and the need.  It is lowered -
+ * to the largest multiple of 64 words that is not below need + max(need / 32, 96) - only when the items outnumber the workgroup
+ * slots, the policy's budget leaves less LDS free on a CU than a k_planning or k_score workgroup holds, and the lower one leaves
+ * that much with as many searching workgroups per CU; mode as above (either bit: unchanged).  env DMPP_CORESIDENT=0 switches the
+ * step off in a handle.  pp_get_search_info reports the budget the launch used.  No device needed. */
+int pp_coresident_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_budget_max, int n_cus, int items, int need, int budget,
+                         int mode, int32_t* budget_out);
 /* The rollout feature table ("Feature life cycle"): which features a successful set call switches off, and what holds
  * between the features that are on.  Feature bits: 1 fleet, 2 route, 4 traffic per scene, 8 world traffic, 16 traffic follow,
  * 32 episodes, 64 spawn model, 128 traffic reset, 256 episode log.  Causes: 0 pp_set_scenes / pp_set_egos / pp_set_n_scenes, 1 pp_set_map,
