@@ -37,11 +37,24 @@ __device__ __forceinline__ uint64_t mix64(uint64_t v)
     return z ^ (z >> 31);
 }
 
+// DESIGN §5 "Values outside the grid's range": q = floor((v - origin) / cell) is compared in double and converted afterwards.
+// Here it is first brought into [-2^30, 2^30] - a NaN to -2^30 - against two literals (the grid's own bounds as doubles would be
+// held in registers through the whole set-up); the -1 / +1 of a box bound and the clamp to the grid then are int arithmetic on a
+// value that cannot overflow, with the result of the rule: a grid has far fewer than 2^30 lines.
+__device__ __forceinline__ int index_near(double q)
+{
+    return (int)fmin(fmax(q, -0x1p30), 0x1p30);               // fmax(NaN, c) = c: the maximum of IEEE drops a NaN
+}
+__device__ __forceinline__ int index_near_hi(double q)        // the same with a NaN brought to +2^30
+{
+    return (int)fmax(fmin(q, 0x1p30), -0x1p30);
+}
+
 __device__ __forceinline__ int cell_of(const PlannerConfig& c, GlobalPoint2D origin, double x, double y)
 {
-    int ix = (int)floor((x - origin.x) / c.cell);
-    int iy = (int)floor((y - origin.y) / c.cell);
-    ix = clampi(ix, 0, c.grid_w - 1); iy = clampi(iy, 0, c.grid_h - 1);
+    // the index rule: 0 when !(q >= 0), a NaN included (index_near brings it to -2^30), n - 1 when q > n - 1
+    const int ix = clampi(index_near(floor((x - origin.x) / c.cell)), 0, c.grid_w - 1);
+    const int iy = clampi(index_near(floor((y - origin.y) / c.cell)), 0, c.grid_h - 1);
     return iy * c.grid_w + ix;
 }
 
@@ -256,7 +269,7 @@ __device__ __forceinline__ int jump_lane(const V& vw, const L& m0, const L& mP, 
 
 // ---------------------------------------------------------------------------------------
 // G1 inside the search: the footprint of one obstacle, exactly as oracle/dmpp_grid_oracle.c defines it - cell (ix, iy)
-// is occupied iff  dx*dx + dy*dy <= R*R  for its centre, R = radius + inflate - but produced span by span.
+// is occupied iff  R >= 0 and dx*dx + dy*dy <= R*R  for its centre, R = radius + inflate - but produced span by span.
 // For a fixed row the predicate is true on a contiguous run of columns (every step of its evaluation is monotone in the
 // distance of the column from the obstacle, rounding included), so a row is described by its first and last true column;
 // both are found from a sqrt estimate and then MOVED BY THE PREDICATE ITSELF until exact.  Columns likewise.
@@ -267,11 +280,17 @@ __device__ __forceinline__ Footprint footprint_of(const PlannerConfig& c, Global
     Footprint f;
     const double R = (double)o.radius + c.inflate;
     f.ox = o.x; f.oy = o.y; f.R2 = R * R;
-    // the conservative box of the oracle's rasteriser, clipped to the grid
-    f.ix0 = max((int)floor((o.x - R - origin.x) / c.cell) - 1, 0);
-    f.ix1 = min((int)floor((o.x + R - origin.x) / c.cell) + 1, W - 1);
-    f.iy0 = max((int)floor((o.y - R - origin.y) / c.cell) - 1, 0);
-    f.iy1 = min((int)floor((o.y + R - origin.y) / c.cell) + 1, H - 1);
+    // the conservative box of the oracle's rasteriser, clipped to the grid; no int arithmetic meets a value outside int
+    // (index_near / index_near_hi).  A NaN bound is the widest one, 0 or n - 1: with R = +inf a centre at -inf or +inf makes one
+    // bound inf - inf, and the predicate is true in every cell (R2 = +inf makes every predicate of exact_span true as well).
+    f.ix0 = max(index_near(floor((o.x - R - origin.x) / c.cell)) - 1, 0);
+    f.ix1 = min(index_near_hi(floor((o.x + R - origin.x) / c.cell)) + 1, W - 1);
+    f.iy0 = max(index_near(floor((o.y - R - origin.y) / c.cell)) - 1, 0);
+    f.iy1 = min(index_near_hi(floor((o.y + R - origin.y) / c.cell)) + 1, H - 1);
+    // Nothing is occupied - an empty box - by R < 0 or a NaN R (the oracle's blocked_by), and by a centre whose offset from the
+    // origin is a NaN (a NaN centre or origin, or both infinite with one sign): dx or dy of the predicate is a NaN in every cell
+    const bool some = (R >= 0) & !__builtin_isunordered(o.x - origin.x, o.y - origin.y);
+    f.ix1 = some ? f.ix1 : -1;
     return f;
 }
 
@@ -398,7 +417,7 @@ constexpr uint32_t kNoSpan = 0xFFFFu;                   // a | b << 16 of an emp
 struct RasterStage {
     double ox[kRasterChunk], oy[kRasterChunk], R2[kRasterChunk];
     int ix0[kRasterChunk], ix1[kRasterChunk], iy0[kRasterChunk], iy1[kRasterChunk];      // the clipped box
-    int icx[kRasterChunk], icy[kRasterChunk];                                            // the cell of the centre (may lie outside the grid)
+    int icx[kRasterChunk], icy[kRasterChunk];                                            // the cell of the centre, within one cell of the grid (-1 .. n)
     int first[kRasterChunk + 1];
 };
 struct ItemRec { double ox, oy, R2; int ix0, ix1, iy0, iy1, icx, icy; };
@@ -428,8 +447,10 @@ __device__ __forceinline__ int stage_footprints(const PlannerConfig& c, const Sc
         const Footprint f = footprint_of(c, origin, obs[base + tid], W, H);
         S->ox[tid] = f.ox; S->oy[tid] = f.oy; S->R2[tid] = f.R2;
         S->ix0[tid] = f.ix0; S->ix1[tid] = f.ix1; S->iy0[tid] = f.iy0; S->iy1[tid] = f.iy1;
-        S->icx[tid] = (int)floor((f.ox - origin.x) / c.cell);
-        S->icy[tid] = (int)floor((f.oy - origin.y) / c.cell);
+        // the cell of the centre, kept within one cell of the grid: exact_span evaluates the predicate at ic - 1 .. ic + 1, and a
+        // run that reaches the window [lo, hi] from a centre beyond n contains n as well (the run is contiguous)
+        S->icx[tid] = clampi(index_near(floor((f.ox - origin.x) / c.cell)), -1, W);
+        S->icy[tid] = clampi(index_near(floor((f.oy - origin.y) / c.cell)), -1, H);
         if (f.ix1 >= f.ix0 && f.iy1 >= f.iy0) cnt = (f.iy1 - f.iy0 + 1) + (f.ix1 - f.ix0 + 1);
     }
     const int off = block_excl_scan<SW>(cnt, tid, s_wave);

@@ -27,12 +27,20 @@ void orc_effective_obstacles(const PlannerConfig* c, const ObPoint* obs, const O
     }
 }
 
+/* DESIGN §5 "Values outside the grid's range": the index of q = floor((v - origin) / cell) on an axis of n cells, compared in
+ * double and converted afterwards - 0 when !(q >= 0) (a NaN included), n - 1 when q > n - 1.  [lo, hi] = [0, n - 1] for a cell;
+ * the bounds of an obstacle's box use [0, n] and [-1, n - 1], so that a box that lies wholly outside the grid is empty. */
+static int index_in(double q, int lo, int hi)
+{
+    if (!(q >= (double)lo)) return lo;
+    if (q > (double)hi) return hi;
+    return (int)q;
+}
+
 int orc_cell_of(const PlannerConfig* c, GlobalPoint2D origin, double x, double y)
 {
-    int ix = (int)floor((x - origin.x) / c->cell);
-    int iy = (int)floor((y - origin.y) / c->cell);
-    if (ix < 0) ix = 0; if (ix > c->grid_w - 1) ix = c->grid_w - 1;
-    if (iy < 0) iy = 0; if (iy > c->grid_h - 1) iy = c->grid_h - 1;
+    int ix = index_in(floor((x - origin.x) / c->cell), 0, c->grid_w - 1);
+    int iy = index_in(floor((y - origin.y) / c->cell), 0, c->grid_h - 1);
     return iy * c->grid_w + ix;
 }
 
@@ -42,11 +50,12 @@ static int blocked_by(const PlannerConfig* c, GlobalPoint2D origin, int ix, int 
     double cy = origin.y + ((double)iy + 0.5) * c->cell;
     double R = (double)o->radius + c->inflate;
     double dx = cx - o->x, dy = cy - o->y;
-    return dx * dx + dy * dy <= R * R;
+    return R >= 0 && dx * dx + dy * dy <= R * R;
 }
 
-/* G1 definition: a cell is occupied (1) iff its centre lies within radius+inflate of
- * some obstacle centre. */
+/* G1 definition: a cell is occupied (1) iff its centre lies within R = radius+inflate of some obstacle centre and R >= 0: a
+ * comparison with a NaN is false, so an obstacle with a NaN x, y or radius occupies nothing, and neither does one with R < 0;
+ * R = +inf occupies every cell, around a finite centre and around one at -inf or +inf (inf <= inf holds). */
 void orc_rasterise_bruteforce(const PlannerConfig* c, GlobalPoint2D origin, const ObPoint* obs, int m, uint8_t* grid)
 {
     for (int iy = 0; iy < c->grid_h; iy++)
@@ -63,13 +72,16 @@ void orc_rasterise(const PlannerConfig* c, GlobalPoint2D origin, const ObPoint* 
     memset(grid, 0, (size_t)c->grid_w * (size_t)c->grid_h);
     for (int j = 0; j < m; j++) {
         double R = (double)obs[j].radius + c->inflate;
-        int ix0 = (int)floor((obs[j].x - R - origin.x) / c->cell) - 1;
-        int ix1 = (int)floor((obs[j].x + R - origin.x) / c->cell) + 1;
-        int iy0 = (int)floor((obs[j].y - R - origin.y) / c->cell) - 1;
-        int iy1 = (int)floor((obs[j].y + R - origin.y) / c->cell) + 1;
-        if (ix0 < 0) ix0 = 0; if (iy0 < 0) iy0 = 0;
-        if (ix1 > c->grid_w - 1) ix1 = c->grid_w - 1;
-        if (iy1 > c->grid_h - 1) iy1 = c->grid_h - 1;
+        if (!(R >= 0)) continue;                                      /* occupies nothing (blocked_by) */
+        /* a centre whose offset from the origin is a NaN (a NaN centre or origin, or both infinite with one sign) makes dx or dy
+         * of the predicate a NaN in every cell: nothing */
+        if (isnan(obs[j].x - origin.x) || isnan(obs[j].y - origin.y)) continue;
+        /* the -1 / +1 in double, then the clamp: no int arithmetic on a value that may lie outside int.  A NaN bound is the
+         * widest one: with R = +inf a centre at -inf or +inf makes one bound inf - inf, and the predicate holds in every cell */
+        double qx0 = floor((obs[j].x - R - origin.x) / c->cell) - 1.0, qx1 = floor((obs[j].x + R - origin.x) / c->cell) + 1.0;
+        double qy0 = floor((obs[j].y - R - origin.y) / c->cell) - 1.0, qy1 = floor((obs[j].y + R - origin.y) / c->cell) + 1.0;
+        int ix0 = index_in(qx0, 0, c->grid_w), ix1 = isnan(qx1) ? c->grid_w - 1 : index_in(qx1, -1, c->grid_w - 1);
+        int iy0 = index_in(qy0, 0, c->grid_h), iy1 = isnan(qy1) ? c->grid_h - 1 : index_in(qy1, -1, c->grid_h - 1);
         for (int iy = iy0; iy <= iy1; iy++)
             for (int ix = ix0; ix <= ix1; ix++)
                 if (blocked_by(c, origin, ix, iy, &obs[j])) grid[(size_t)iy * c->grid_w + ix] = 1;

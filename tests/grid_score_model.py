@@ -22,6 +22,13 @@ The specification, as this file reads it:
     cost = w_col col + w_curv curv + w_prog prog + w_off |off|; the smallest cost wins, ties to the lowest index; no
     candidate at all: winner 0, 200 zero points.
 
+  * obstacles whose values are not finite or out of range ("Values outside the grid's range"): the plain loop as it
+    stands - clearance starts at +inf, an obstacle with d2 > cutoff^2 is skipped, v = d - r replaces the clearance when v < clearance,
+    and a comparison with a NaN is false.  So a NaN x, y or radius contributes nothing, an infinite distance is skipped by every
+    finite cutoff, radius = +inf gives every point at a finite distance the clearance -inf, radius = -inf gives +inf, and a negative
+    cutoff - squared - admits the obstacle within |cutoff| with v = d + |r|.  `collision` evaluates exactly this; nothing is
+    decided beforehand (a point whose clearance stays +inf has no penalty).
+
 The specification has two discontinuities - clearance <= 0 and sinA < 0.001 - so every result carries how close the case
 comes to them: `min_abs_clearance` (metres, over all points with a finite clearance) and `min_fence` (|sinA - 0.001| / 0.001
 over the interior points that have a sinA).  A committed case keeps away from both (tests/test_score_edges.py)."""
@@ -142,12 +149,18 @@ def collision(cfg, pts, P, obs):
     pens, first_hit, min_abs_clear = [], N, math.inf
     if len(obs):
         ox, oy, orad = obs["x"].astype(np.float64), obs["y"].astype(np.float64), obs["radius"].astype(np.float64)
-        dist = np.hypot(P[:, 0:1] - ox[None, :], P[:, 1:2] - oy[None, :])
-        sel = dist <= (orad + float(half_w) + float(d_safe) + PREFILTER_MARGIN)[None, :]
+        # The pre-selection only drops what the plain loop certainly skips - a finite or infinite distance beyond |cutoff| + margin
+        # (the cutoff is squared in the loop, so its sign does not matter there).  A NaN distance or cutoff, and inf against inf,
+        # compare false here and go to the loop below, which is the rule itself: clear starts at +inf, `d2 > thr * thr`
+        # skips, `v < clear` replaces - and a comparison with a NaN is false.
+        with np.errstate(all="ignore"):
+            dist = np.hypot(P[:, 0:1] - ox[None, :], P[:, 1:2] - oy[None, :])
+            sel = ~(dist > (np.abs(orad + float(half_w) + float(d_safe)) + PREFILTER_MARGIN)[None, :])
         o_mp = [(_num(ox[j]), _num(oy[j]), _num(orad[j])) for j in range(len(obs))]
+        inf = _num(math.inf)
         for i in np.flatnonzero(sel.any(axis=1)):
             x, y = pts[i]
-            clear = None
+            clear = inf
             for j in np.flatnonzero(sel[i]):
                 qx, qy, r = o_mp[j]
                 d2 = (x - qx) ** 2 + (y - qy) ** 2
@@ -155,9 +168,9 @@ def collision(cfg, pts, P, obs):
                 if d2 > thr * thr:
                     continue
                 v = _sqrt(d2) - r
-                if clear is None or v < clear:
+                if v < clear:
                     clear = v
-            if clear is None:
+            if clear == inf:
                 continue
             clear = clear - half_w
             min_abs_clear = min(min_abs_clear, float(abs(clear)))
@@ -179,9 +192,10 @@ def _relevant(cfg, P, obs):
     """The obstacles within their cutoff + PREFILTER_MARGIN of any point of the candidate (float64), in list order."""
     if not len(obs):
         return np.ascontiguousarray(obs)
-    reach = obs["radius"].astype(np.float64) + 0.5 * float(cfg["Vehicle_Width"][0]) + float(cfg["d_safe"][0]) + PREFILTER_MARGIN
-    dist = np.hypot(P[:, 0:1] - obs["x"][None, :], P[:, 1:2] - obs["y"][None, :])
-    return np.ascontiguousarray(obs[(dist <= reach[None, :]).any(axis=0)])
+    with np.errstate(all="ignore"):              # (only what the plain loop certainly skips is dropped: see `collision`)
+        reach = np.abs(obs["radius"].astype(np.float64) + 0.5 * float(cfg["Vehicle_Width"][0]) + float(cfg["d_safe"][0])) + PREFILTER_MARGIN
+        dist = np.hypot(P[:, 0:1] - obs["x"][None, :], P[:, 1:2] - obs["y"][None, :])
+        return np.ascontiguousarray(obs[(~(dist > reach[None, :])).any(axis=0)])
 
 
 def _candidate(cfg, gkey, make, obs):

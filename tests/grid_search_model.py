@@ -40,6 +40,9 @@ list -> OVERFLOW (for both only the status is defined).  An empty list at the st
 Path: from the goal back, every closed cell knows its arriving direction and run length; all cells start .. goal.  Longer
 than `max_path` cells: PATH_TRUNC, the last `max_path` cells (`path_len = max_path`; every other field as for FOUND).
 
+Start and goal cell of a position, and G1 itself, for every IEEE value ("Values outside the grid's range"): `cell_index`,
+`cell_of` and `occupancy` below, in numpy float64 - the comparison is made on the float, the conversion afterwards.
+
 Besides the outputs the model keeps what the coverage checks of tests/test_search_edges.py need - facts of the specified
 search, not of any implementation: per step the live entries before the pop and after the push, the entries taken, those
 dropped as closed earlier and those dropped as the same cell twice in the batch; the hops of the path; and for every jump
@@ -55,6 +58,42 @@ F_LIMIT = 131070
 VEC = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))
 DIR_OF = {v: i for i, v in enumerate(VEC)}
 M64 = (1 << 64) - 1
+
+
+def cell_index(v, origin, cell, n):
+    """DESIGN §5 "Values outside the grid's range": the index of coordinate `v` on an axis of `n` cells.  q = floor((v - origin) /
+    cell) in double; 0 when not q >= 0 (a NaN included), n - 1 when q > n - 1, else q.  Compared as floats, converted afterwards."""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        q = np.floor((np.float64(v) - np.float64(origin)) / np.float64(cell))
+    if not q >= 0:
+        return 0
+    if q > n - 1:
+        return n - 1
+    return int(q)
+
+
+def cell_of(W, H, cell, origin, x, y):
+    """The cell `y * W + x` of a position (the start cell of the ego, the goal cell)."""
+    return cell_index(y, origin[1], cell, H) * W + cell_index(x, origin[0], cell, W)
+
+
+def occupancy(W, H, cell, inflate, origin, obs):
+    """G1 by its definition, for every IEEE value: cell (ix, iy) is occupied iff for some obstacle R >= 0 and dx*dx + dy*dy <= R*R,
+    R = (double)radius + inflate, (dx, dy) from the cell's centre origin + (i + 0.5) * cell.  A comparison with a NaN is false.
+    `obs`: ObPoint records.  Returns H x W bytes."""
+    import numpy as np
+    grid = np.zeros((H, W), np.uint8)
+    with np.errstate(all="ignore"):
+        cx = np.float64(origin[0]) + (np.arange(W, dtype=np.float64) + 0.5) * np.float64(cell)
+        cy = np.float64(origin[1]) + (np.arange(H, dtype=np.float64) + 0.5) * np.float64(cell)
+        for o in obs:
+            R = np.float64(o["radius"]) + np.float64(inflate)
+            if not R >= 0:
+                continue
+            dx, dy = cx - np.float64(o["x"]), cy - np.float64(o["y"])
+            grid |= (dx * dx)[None, :] + (dy * dy)[:, None] <= R * R
+    return grid
 
 
 def mix64(v):

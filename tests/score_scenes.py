@@ -194,8 +194,10 @@ def forms(cfg, si, obs, path, status, k=None):
         cnt = np.zeros((nb, nb), np.int64)
         ibx = nb / (X1 - X0) if X1 > X0 else 0.0
         iby = nb / (Y1 - Y0) if Y1 > Y0 else 0.0
-        bx = lambda v: min(max(int(math.floor((v - X0) * ibx)), 0), nb - 1)
-        by = lambda v: min(max(int(math.floor((v - Y0) * iby)), 0), nb - 1)
+        def sat(q):                       # the device's conversion: a NaN is 0, beyond int the nearest end - then the clamp
+            return 0 if q != q else int(min(max(q, 0.0), nb - 1.0))
+        bx = lambda v: sat(math.floor((v - X0) * ibx) if math.isfinite((v - X0) * ibx) else (v - X0) * ibx)
+        by = lambda v: sat(math.floor((v - Y0) * iby) if math.isfinite((v - Y0) * iby) else (v - Y0) * iby)
         for j in (np.flatnonzero(near) if culled else range(m)):
             t = thr[j] * (1.0 + 1e-9) + 1e-9
             if not (ox[j] >= X0 - t and ox[j] <= X1 + t and oy[j] >= Y0 - t and oy[j] <= Y1 + t):
