@@ -814,19 +814,26 @@ class Planner:
         the next advance on the actors of a scene whose ego restarts go back to a start state.  Set 0 is captured by the call (the
         current s and v of every actor); starts: TrafficStart records of sets 1 .. n_sets - 1, set k of actor a at
         (k - 1) * n_actors + a.  n_sets is 1 or the n_starts of the spawn model in force; 0: the reset off, the counters stay readable."""
-        st = None if starts is None else np.ascontiguousarray(starts, TrafficStart).reshape(-1)
-        want = (int(n_sets) - 1) * getattr(self, "n_traffic", 0)
-        if st is not None and int(n_sets) >= 1 and len(st) != want:          # (the library refuses the other counts)
-            raise ValueError(f"starts: {len(st)} records, n_sets and the actors ask for {want}")
-        _check(self.lib.pp_set_episode_traffic(self.h, int(n_sets), _ptr(st)))
-        if int(n_sets) > 0:
-            self.n_traffic_reset = getattr(self, "n_traffic", 0)          # (the counters outlive the traffic they counted)
+        self._set_traffic_reset(self.lib.pp_set_episode_traffic, "n_traffic_reset", "actors", n_sets, starts)
 
     def episode_traffic_resets(self):
         """pp_get_episode_traffic_resets: how often every actor was put back on a start state since set_episode_traffic, a staged
         advance included (host wait)."""
-        out = np.zeros(getattr(self, "n_traffic_reset", 0), np.int32)
-        _check(self.lib.pp_get_episode_traffic_resets(self.h, _ptr(out), len(out)))
+        return self._traffic_resets(self.lib.pp_get_episode_traffic_resets, "n_traffic_reset")
+
+    def _set_traffic_reset(self, call, count, who, n_sets, starts):
+        """The set call of a traffic reset, per scene or per world; `count`: the attribute that keeps how many counters it has."""
+        st = None if starts is None else np.ascontiguousarray(starts, TrafficStart).reshape(-1)
+        want = (int(n_sets) - 1) * getattr(self, "n_traffic", 0)
+        if st is not None and int(n_sets) >= 1 and len(st) != want:          # (the library refuses the other counts)
+            raise ValueError(f"starts: {len(st)} records, n_sets and the {who} ask for {want}")
+        _check(call(self.h, int(n_sets), _ptr(st)))
+        if int(n_sets) > 0:
+            setattr(self, count, getattr(self, "n_traffic", 0))          # (the counters outlive the traffic they counted)
+
+    def _traffic_resets(self, call, count):
+        out = np.zeros(getattr(self, count, 0), np.int32)
+        _check(call(self.h, _ptr(out), len(out)))
         return out
 
     # ---- world episodes: the egos of a world restart together, with its vehicles -------------------
@@ -840,20 +847,12 @@ class Planner:
         """pp_set_episode_world_traffic, after set_world_traffic, set_traffic_follow and set_episode_worlds:
         set_episode_traffic for the vehicles of a world.  starts: TrafficStart records of sets 1 .. n_sets - 1, set k of vehicle a at
         (k - 1) * n_actors + a.  0: the reset off, the counters stay readable."""
-        st = None if starts is None else np.ascontiguousarray(starts, TrafficStart).reshape(-1)
-        want = (int(n_sets) - 1) * getattr(self, "n_traffic", 0)
-        if st is not None and int(n_sets) >= 1 and len(st) != want:          # (the library refuses the other counts)
-            raise ValueError(f"starts: {len(st)} records, n_sets and the vehicles ask for {want}")
-        _check(self.lib.pp_set_episode_world_traffic(self.h, int(n_sets), _ptr(st)))
-        if int(n_sets) > 0:
-            self.n_world_traffic_reset = getattr(self, "n_traffic", 0)
+        self._set_traffic_reset(self.lib.pp_set_episode_world_traffic, "n_world_traffic_reset", "vehicles", n_sets, starts)
 
     def episode_world_traffic_resets(self):
         """pp_get_episode_world_traffic_resets: how often every vehicle was put back on a start state since
         set_episode_world_traffic, a staged advance included (host wait)."""
-        out = np.zeros(getattr(self, "n_world_traffic_reset", 0), np.int32)
-        _check(self.lib.pp_get_episode_world_traffic_resets(self.h, _ptr(out), len(out)))
-        return out
+        return self._traffic_resets(self.lib.pp_get_episode_world_traffic_resets, "n_world_traffic_reset")
 
     # ---- episode log: one record per ended episode, appended on the device ------------------------
     def set_episode_log(self, cap):

@@ -242,14 +242,14 @@ struct EpisodeState {
 struct SpawnState {
     bool on = false, ever = false; EpisodeSpawn sp = {}; int stride = 0, cur = 0;      // ever: a set call succeeded on this handle (the stats are readable)
     DevBuf<SceneIn> d_in[2]; DevBuf<SceneState> d_state[2]; DevBuf<EpisodeSpawnStats> d_stats[2];
-    // scenario schedule (first pp_set_episode_schedule): part of the spawn model in force - on only while `on` is, gone
-    // with whatever switches `on` off or sets a new pool.  While on, pp_advance_async launches k_respawn_sched in the place of
-    // k_respawn_spawn and, in pooled scope, k_fold_schedule behind it.  The rows stay readable after it went off
+    // scenario schedule (first pp_set_episode_schedule): feature kSchedule, on only while `on` is.  While on,
+    // pp_advance_async launches k_respawn_sched in the place of k_respawn_spawn and, in pooled scope, k_fold_schedule behind it.
+    // The rows stay readable after it went off
     bool sched_on = false, sched_ever = false; EpisodeSchedule sched = {};
     DevBuf<EpisodeScheduleRow> d_rows; DevBuf<int32_t> d_fold_word;      // scope 0: a row per scene; scope 1: one row and a word per scene
-    // world episodes (first pp_set_episode_worlds): part of the spawn model in force like the schedule - cleared wherever
-    // sched_on is, never on beside it.  While on, pp_advance_async launches k_respawn_world in the place of k_respawn_spawn, one
-    // workgroup per world of the fleet in force AT THAT ADVANCE (no fleet: per scene); d_world_end is the kernel's per-scene scratch
+    // world episodes (first pp_set_episode_worlds): feature kWorldEpisodes, on only while `on` is and never beside
+    // the schedule.  While on, pp_advance_async launches k_respawn_world in the place of k_respawn_spawn, one workgroup per world
+    // of the fleet in force AT THAT ADVANCE (no fleet: per scene); d_world_end is the kernel's per-scene scratch
     bool worlds_on = false; DevBuf<dmpp::WorldEnd> d_world_end;
 };
 struct FollowState {
@@ -259,19 +259,12 @@ struct FollowState {
 // episode traffic reset (first pp_set_episode_traffic): every actor's scene, the table of start states - set k of
 // actor a at k * actors + a - and the counters; two sets of table and counters, so that a failed call leaves the ones in force
 // untouched (cur: the ones in force, or the last that were).  While on (only with per-scene traffic and episodes on),
-// pp_advance_async launches k_reset_traffic behind its traffic kernel.  The counters stay readable after the reset went off
+// pp_advance_async launches k_reset_traffic behind its traffic kernel.  The counters stay readable after the reset went off.
+// A second instance is the world traffic reset (first pp_set_episode_world_traffic): the same for the vehicles of
+// pp_set_world_traffic, without d_scene; while on (only with world traffic and world episodes on), k_reset_world_traffic
 struct TrafficResetState {
     bool on = false, ever = false; int n_sets = 0, actors = 0, cur = 0;      // ever: a set call succeeded on this handle (the counters are readable)
     DevBuf<int32_t> d_scene; DevBuf<TrafficStart> d_starts[2]; DevBuf<int32_t> d_resets[2];
-};
-// world traffic reset (first pp_set_episode_world_traffic): §4m's table and counters for the vehicles of
-// pp_set_world_traffic, two sets of each as there.  No feature bit: it lives inside the life cycles of what its table was captured from -
-// switch_features clears `on` whenever the traffic reset, world traffic, the spawn model or episodes are switched off, and
-// pp_set_episode_worlds(h, 0) does.  While on (only with world traffic and world episodes on), pp_advance_async launches
-// k_reset_world_traffic behind its world-traffic kernel.  The counters stay readable after it went off
-struct WorldTrafficResetState {
-    bool on = false, ever = false; int n_sets = 0, actors = 0, cur = 0;
-    DevBuf<TrafficStart> d_starts[2]; DevBuf<int32_t> d_resets[2];
 };
 // episode log (first pp_set_episode_log): the ring of `cap` records, the count of records appended since the set call,
 // every scene's start record and - only on a handle with a scorecard - the scorecard of its running episode; on the host the number
@@ -395,8 +388,7 @@ struct pp_planner {
     FollowState follow;
     EpisodeState episode;
     SpawnState spawn;
-    TrafficResetState treset;
-    WorldTrafficResetState wreset;
+    TrafficResetState treset, wreset;                         // per scene (§4m), per world (§4t)
     EpisodeLogState elog;
     ScoreTraceState strace;
     PackedState packed;
@@ -506,26 +498,21 @@ int follow_traffic(pp_planner* h, hipStream_t st, const SceneIn* d_in, ObPoint* 
 // Episode traffic reset of the input set an advance stages: behind the episode step, whose EpisodeStats.age and
 // EpisodeSpawnStats.cur_start it reads, and behind the traffic kernel of the advance, whose arrays - the current ones: with
 // following the pair follow_traffic has just flipped to - and pool entries it overwrites for the actors of restarted scenes.
-void reset_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot)
+// world: the same for the vehicles of a world that has just restarted, written into every member scene.
+void reset_traffic(pp_planner* h, bool world, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot)
 {
-    const int n = h->treset.actors, cur = h->traffic.cur;
-    hipLaunchKernelGGL(dmpp::k_reset_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
-                       n, h->treset.n_sets, h->traffic.d_pin, h->treset.d_scene, h->episode.d_stats,
-                       h->treset.n_sets > 1 ? h->spawn.d_stats[h->spawn.cur].get() : nullptr, h->treset.d_starts[h->treset.cur],
-                       h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], h->follow.on ? h->follow.d_v[cur].get() : nullptr,
-                       h->treset.d_resets[h->treset.cur], d_obs, d_mot);
-}
-
-// World traffic reset of the input set an advance stages: reset_traffic for the vehicles of a world that has just
-// restarted, written into every member scene
-void reset_world_traffic(pp_planner* h, hipStream_t st, ObPoint* d_obs, ObMotion* d_mot)
-{
-    const int n = h->wreset.actors, cur = h->traffic.cur;
-    hipLaunchKernelGGL(dmpp::k_reset_world_traffic, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
-                       n, h->wreset.n_sets, h->traffic.d_pin, h->traffic.d_world, h->fleet.d_world_first, h->fleet.d_pin, h->episode.d_stats,
-                       h->wreset.n_sets > 1 ? h->spawn.d_stats[h->spawn.cur].get() : nullptr, h->wreset.d_starts[h->wreset.cur],
-                       h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], h->follow.on ? h->follow.d_v[cur].get() : nullptr,
-                       h->wreset.d_resets[h->wreset.cur], d_obs, d_mot);
+    const TrafficResetState& R = world ? h->wreset : h->treset;
+    const int n = R.actors, cur = h->traffic.cur;
+    const EpisodeSpawnStats* sstats = R.n_sets > 1 ? h->spawn.d_stats[h->spawn.cur].get() : nullptr;
+    double* v_arr = h->follow.on ? h->follow.d_v[cur].get() : nullptr;
+    if (world)
+        hipLaunchKernelGGL(dmpp::k_reset_world_traffic, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
+                           n, R.n_sets, h->traffic.d_pin, h->traffic.d_world, h->fleet.d_world_first, h->fleet.d_pin, h->episode.d_stats, sstats, R.d_starts[R.cur],
+                           h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], v_arr, R.d_resets[R.cur], d_obs, d_mot);
+    else
+        hipLaunchKernelGGL(dmpp::k_reset_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
+                           n, R.n_sets, h->traffic.d_pin, R.d_scene, h->episode.d_stats, sstats, R.d_starts[R.cur],
+                           h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], v_arr, R.d_resets[R.cur], d_obs, d_mot);
 }
 
 // The advance kernel of the input set an advance stages, in the place of the copy of its SceneIn records: reads the
@@ -730,7 +717,8 @@ unsigned feature_mask(const pp_planner* h)
 {
     using namespace dmpp;
     return (h->fleet.on ? kFleet : 0u) | (h->route.on ? kRoute : 0u) | (h->traffic.on ? (h->traffic.world ? kWorldTraffic : kTraffic) : 0u) | (h->follow.on ? kFollow : 0u) |
-           (h->episode.on ? kEpisodes : 0u) | (h->spawn.on ? kSpawn : 0u) | (h->treset.on ? kTrafficReset : 0u) | (h->elog.on ? kEpisodeLog : 0u);
+           (h->episode.on ? kEpisodes : 0u) | (h->spawn.on ? kSpawn : 0u) | (h->treset.on ? kTrafficReset : 0u) | (h->elog.on ? kEpisodeLog : 0u) |
+           (h->spawn.sched_on ? kSchedule : 0u) | (h->spawn.worlds_on ? kWorldEpisodes : 0u) | (h->wreset.on ? kWorldReset : 0u);
 }
 // ... and the bits as flags: the ONLY code that writes the flag of a feature other than the caller's own
 void switch_features(pp_planner* h, unsigned m, bool on)
@@ -741,11 +729,13 @@ void switch_features(pp_planner* h, unsigned m, bool on)
     if (m & (h->traffic.world ? kWorldTraffic : kTraffic)) h->traffic.on = on;
     if (m & kFollow) h->follow.on = on;
     if (m & kEpisodes) h->episode.on = on;
-    if (m & kSpawn) { h->spawn.on = on; if (!on) h->spawn.sched_on = h->spawn.worlds_on = false; }      // (the schedule of §4p and the world episodes of §4s are part of the spawn model: they go with it and do not come back)
-    if (!on && (m & (kTrafficReset | kWorldTraffic | kSpawn | kEpisodes))) h->wreset.on = false;      // (the world traffic reset of §4t has no bit: it goes with whatever its table was captured from, whether or not that was on)
+    if (m & kSpawn) h->spawn.on = on;
     if (m & kTrafficReset) h->treset.on = on;
     if (m & kEpisodeLog) h->elog.on = on;
-    static_assert(dmpp::kFeatureCount == 9, "a new feature bit needs its flag here and in feature_mask");
+    if (m & kSchedule) h->spawn.sched_on = on;
+    if (m & kWorldEpisodes) h->spawn.worlds_on = on;
+    if (m & kWorldReset) h->wreset.on = on;
+    static_assert(dmpp::kFeatureCount == 12, "a new feature bit needs its flag here and in feature_mask");
 }
 void retire(pp_planner* h, int cause) { switch_features(h, dmpp::retires(cause), false); }
 // the common success exit of every set call
@@ -1746,8 +1736,8 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }
         else move_traffic(h, su, d_obs, d_mot, advance ? src.ego->dt : 0.0);
     }
-    if (advance && h->treset.on) reset_traffic(h, su, d_obs, d_mot);      // the actors of a scene that has just restarted go back to a start state (§4m)
-    if (advance && h->wreset.on) reset_world_traffic(h, su, d_obs, d_mot);      // ... and the vehicles of a world that has (§4t)
+    if (advance && h->treset.on) reset_traffic(h, false, su, d_obs, d_mot);      // the actors of a scene that has just restarted go back to a start state (§4m)
+    if (advance && h->wreset.on) reset_traffic(h, true, su, d_obs, d_mot);      // ... and the vehicles of a world that has (§4t)
     if (h->fleet.on) {                    // the peers of this set, at the poses it carries; the pinned slices replace the incoming ones
         if (!advance) n_obs = std::max(n_obs, h->fleet.end);      // (an advance inherits the count of the current set)
         couple_fleet(h, su, d_in, d_obs, d_mot);
@@ -2282,7 +2272,7 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
     PP_TRY(refuse_if_staged(h, "pp_set_episode_spawn", "the spawn model"));
-    if (!sp) { h->spawn.on = false; h->spawn.sched_on = h->spawn.worlds_on = false; retire(h, dmpp::kSetSpawn); return features_ok(h, "pp_set_episode_spawn"); }
+    if (!sp) { h->spawn.on = false; retire(h, dmpp::kSetSpawn); return features_ok(h, "pp_set_episode_spawn"); }
     if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_spawn: episodes are off (pp_set_episodes comes first: its capture is start record 0)");
     const int n = h->n_scenes, M = sp->n_starts;
     if (M < 1 || M > DMPP_EPISODE_MAX_STARTS) return fail(PP_ERR_ARG, "pp_set_episode_spawn: n_starts must be 1 .. DMPP_EPISODE_MAX_STARTS");
@@ -2299,13 +2289,8 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     const size_t recs = (size_t)M * (size_t)stride;       // room first: a failed allocation changes nothing
     PP_TRY(h->spawn.d_in[o].reserve(recs)); PP_TRY(h->spawn.d_state[o].reserve(recs)); PP_TRY(h->spawn.d_stats[o].reserve((size_t)h->caps.max_scenes));
     const unsigned was = feature_mask(h) & (dmpp::kSpawn | dmpp::retires(dmpp::kSetSpawn));
-    // (The world traffic reset of §4t has no bit in `was`: its flag is kept beside the mask and goes back with it.  PAIRING: retire() below
-    // clears it, and the ONLY path that puts it back is the `bad` refusal, beside switch_features(h, was, true).  Every other early return
-    // between the two - a failed copy or launch - leaves the spawn model off, and with it everything that lives inside it, this flag included.)
-    const bool wreset_was = h->wreset.on;
     h->spawn.on = false;                                  // (until everything below has landed: a failed copy leaves the spawn model off, not half a pool)
-    const bool worlds_was = h->spawn.worlds_on; h->spawn.worlds_on = false;      // (... and no world episodes on a spawn model that is off; back with the `bad` refusal)
-    retire(h, dmpp::kSetSpawn);                           // (the traffic reset of §4m and the episode log of §4n read cur_start of the model in force: they go with it)
+    retire(h, dmpp::kSetSpawn);                           // (the traffic reset of §4m and the episode log of §4n read cur_start of the model in force, schedule, world episodes and world reset are part of it: they go with it)
     SceneIn* pin = h->spawn.d_in[o]; SceneState* pst = h->spawn.d_state[o];
     HIP_TRY(hipMemcpyAsync(pin, h->episode.d_start_in, (size_t)n * sizeof(SceneIn), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(pst, h->episode.d_start_state, (size_t)n * sizeof(SceneState), hipMemcpyDeviceToDevice, h->stream));
@@ -2327,15 +2312,13 @@ int pp_set_episode_spawn(pp_handle h, const EpisodeSpawn* sp, const SceneIn* sta
     }
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's arrays may go; the upload stream reads the pool from its next launch on
     if (bad) {
-        switch_features(h, was, true);                    // (nothing in force was touched: spawn model, traffic reset and log are as they were)
-        h->spawn.worlds_on = worlds_was; h->wreset.on = wreset_was;
+        switch_features(h, was, true);                    // (nothing in force was touched: the spawn model and everything the call retires are as they were)
         return fail(PP_ERR_ARG, "pp_set_episode_spawn: " + std::to_string(bad) + " start record(s) name a road or lane outside the map");
     }
     if (o != h->spawn.cur) {                              // the pool that was in force goes (nobody reads it: joined and waited above); its stats are 80 B a scene and stay
         h->spawn.d_in[h->spawn.cur] = DevBuf<SceneIn>(); h->spawn.d_state[h->spawn.cur] = DevBuf<SceneState>();
     }
     h->spawn.sp = *sp; h->spawn.stride = stride; h->spawn.cur = o; h->spawn.on = true; h->spawn.ever = true;
-    h->spawn.sched_on = h->spawn.worlds_on = false;       // (a new spawn model starts with no schedule and no world episodes: §4p, §4s)
     return features_ok(h, "pp_set_episode_spawn");
 }
 
@@ -2412,30 +2395,40 @@ int pp_episode_schedule_weights(const EpisodeSchedule* m, const EpisodeScheduleR
 }
 
 // Episode traffic reset.  Everything is checked on the host before anything changes; the new table and its counters
-// are built beside the ones in force and take their place only once every copy has landed.
-int pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
+// are built beside the ones in force and take their place only once every copy has landed.  world: pp_set_episode_world_traffic
+//  - the same for the vehicles of pp_set_world_traffic, which reset when their whole world restarts.
+static int set_traffic_reset(pp_handle h, bool world, int n_sets, const TrafficStart* starts)
 {
     if (!h) return fail(PP_ERR_ARG, "null handle");
-    PP_TRY(refuse_if_staged(h, "pp_set_episode_traffic", "the traffic reset"));
-    if (n_sets == 0) { h->treset.on = false; return features_ok(h, "pp_set_episode_traffic"); }
-    if (!h->traffic.on) return fail(PP_ERR_STATE, "pp_set_episode_traffic: no traffic is set (pp_set_traffic comes first)");
-    if (h->traffic.world) return fail(PP_ERR_STATE, "pp_set_episode_traffic: world traffic is in force (one vehicle belongs to many egos: a reset has no owner)");
-    if (!h->episode.on) return fail(PP_ERR_STATE, "pp_set_episode_traffic: episodes are off (pp_set_episodes comes first)");
+    const std::string fn = world ? "pp_set_episode_world_traffic" : "pp_set_episode_traffic";
+    TrafficResetState& R = world ? h->wreset : h->treset;
+    PP_TRY(refuse_if_staged(h, fn, world ? "the world traffic reset" : "the traffic reset"));
+    if (n_sets == 0) { R.on = false; return features_ok(h, fn.c_str()); }
+    if (world) {
+        if (!h->traffic.on || !h->traffic.world) return fail(PP_ERR_STATE, fn + ": no world traffic is set (pp_set_world_traffic comes first)");
+        if (!h->episode.on || !h->spawn.on || !h->spawn.worlds_on)
+            return fail(PP_ERR_STATE, fn + ": world episodes are off (pp_set_episode_worlds comes first: a vehicle resets when its whole world restarts)");
+    } else {
+        if (!h->traffic.on) return fail(PP_ERR_STATE, fn + ": no traffic is set (pp_set_traffic comes first)");
+        if (h->traffic.world) return fail(PP_ERR_STATE, fn + ": world traffic is in force (one vehicle belongs to many egos: a reset has no owner)");
+        if (!h->episode.on) return fail(PP_ERR_STATE, fn + ": episodes are off (pp_set_episodes comes first)");
+    }
     const int M = h->spawn.on ? h->spawn.sp.n_starts : 1;
     if (n_sets < 0 || (n_sets != 1 && n_sets != M))
-        return fail(PP_ERR_ARG, "pp_set_episode_traffic: n_sets must be 1 or the n_starts of the spawn model in force (" + std::to_string(M) + ")");
-    if (n_sets > 1 && !starts) return fail(PP_ERR_ARG, "pp_set_episode_traffic: n_sets > 1 needs the start states");
+        return fail(PP_ERR_ARG, fn + ": n_sets must be 1 or the n_starts of the spawn model in force (" + std::to_string(M) + ")");
+    if (n_sets > 1 && !starts) return fail(PP_ERR_ARG, fn + ": n_sets > 1 needs the start states");
     const size_t n = (size_t)h->traffic.actors, given = starts ? (size_t)(n_sets - 1) * n : 0;
     for (size_t i = 0; i < given; i++) {
-        if (!std::isfinite(starts[i].s)) return fail(PP_ERR_ARG, "pp_set_episode_traffic: start state " + std::to_string(i) + " has a non-finite s");
-        if (!std::isfinite(starts[i].v) || starts[i].v < 0) return fail(PP_ERR_ARG, "pp_set_episode_traffic: start state " + std::to_string(i) + ": v must be finite and >= 0");
+        if (!std::isfinite(starts[i].s)) return fail(PP_ERR_ARG, fn + ": start state " + std::to_string(i) + " has a non-finite s");
+        if (!std::isfinite(starts[i].v) || starts[i].v < 0) return fail(PP_ERR_ARG, fn + ": start state " + std::to_string(i) + ": v must be finite and >= 0");
     }
     PP_TRY(quiesce(h, false));                            // (the upload stream, which writes s / v, is behind the last advance)
-    const int o = h->treset.ever ? 1 - h->treset.cur : h->treset.cur;
-    PP_TRY(h->treset.d_scene.reserve(n)); PP_TRY(h->treset.d_starts[o].reserve((size_t)n_sets * n)); PP_TRY(h->treset.d_resets[o].reserve(n));      // room first: a failed allocation changes nothing
+    const int o = R.ever ? 1 - R.cur : R.cur;
+    if (!world) PP_TRY(R.d_scene.reserve(n));
+    PP_TRY(R.d_starts[o].reserve((size_t)n_sets * n)); PP_TRY(R.d_resets[o].reserve(n));      // room first: a failed allocation changes nothing
     // (d_scene is single: while the reset is on it holds the scenes of the traffic in force, which is what is written again)
-    HIP_TRY(hipMemcpyAsync(h->treset.d_scene, h->traffic.scene_of.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    TrafficStart* tab = h->treset.d_starts[o];
+    if (!world) HIP_TRY(hipMemcpyAsync(R.d_scene, h->traffic.scene_of.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    TrafficStart* tab = R.d_starts[o];
     static_assert(sizeof(TrafficStart) == 16 && offsetof(TrafficStart, s) == 0 && offsetof(TrafficStart, v) == 8, "set 0 is gathered field by field");
     // set 0, the capture: s of the current array; v of the current array while following is on, else the speed of every pin
     HIP_TRY(hipMemcpy2DAsync(&tab->s, sizeof(TrafficStart), h->traffic.d_s[h->traffic.cur], sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
@@ -2444,21 +2437,29 @@ int pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
     else
         HIP_TRY(hipMemcpy2DAsync(&tab->v, sizeof(TrafficStart), h->traffic.d_pin, sizeof(dmpp::TrafficPin), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
     if (given) HIP_TRY(hipMemcpyAsync(tab + n, starts, given * sizeof(TrafficStart), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->treset.d_resets[o], 0, n * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(R.d_resets[o], 0, n * sizeof(int32_t), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's array may go; the upload stream reads the table from its next launch on
-    if (o != h->treset.cur) h->treset.d_starts[h->treset.cur] = DevBuf<TrafficStart>();      // the table that was in force goes; its counters are 4 B an actor and stay
-    h->treset.n_sets = n_sets; h->treset.actors = (int)n; h->treset.cur = o; h->treset.on = true; h->treset.ever = true;
-    return features_ok(h, "pp_set_episode_traffic");
+    if (o != R.cur) R.d_starts[R.cur] = DevBuf<TrafficStart>();      // the table that was in force goes; its counters are 4 B an actor and stay
+    R.n_sets = n_sets; R.actors = (int)n; R.cur = o; R.on = true; R.ever = true;
+    return features_ok(h, fn.c_str());
 }
 
-int pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n)
+static int get_traffic_resets(pp_handle h, bool world, int32_t* n_resets, int n)
 {
     if (!h || (!n_resets && n > 0)) return fail(PP_ERR_ARG, "null argument");
-    if (!h->treset.ever) return fail(PP_ERR_STATE, "pp_get_episode_traffic_resets: pp_set_episode_traffic was never called on this handle");
-    if (n < 0 || n > h->treset.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
+    const TrafficResetState& R = world ? h->wreset : h->treset;
+    if (!R.ever)
+        return fail(PP_ERR_STATE, world ? "pp_get_episode_world_traffic_resets: pp_set_episode_world_traffic was never called on this handle"
+                                        : "pp_get_episode_traffic_resets: pp_set_episode_traffic was never called on this handle");
+    if (n < 0 || n > R.actors) return fail(PP_ERR_ARG, world ? "n exceeds the vehicles" : "n exceeds the actors");
     if (n == 0) return PP_OK;
-    return fetch_behind_advance(h, n_resets, h->treset.d_resets[h->treset.cur], (size_t)n * sizeof(int32_t), true);      // waits as pp_get_traffic_state does
+    return fetch_behind_advance(h, n_resets, R.d_resets[R.cur], (size_t)n * sizeof(int32_t), true);      // waits as pp_get_traffic_state does
 }
+
+int pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts) { return set_traffic_reset(h, false, n_sets, starts); }
+int pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n) { return get_traffic_resets(h, false, n_resets, n); }
+int pp_set_episode_world_traffic(pp_handle h, int n_sets, const TrafficStart* starts) { return set_traffic_reset(h, true, n_sets, starts); }
+int pp_get_episode_world_traffic_resets(pp_handle h, int32_t* n_resets, int n) { return get_traffic_resets(h, true, n_resets, n); }
 
 // World episodes: part of the spawn model in force.  Captures nothing from the fleet: the step reads the fleet in force
 // at each advance.
@@ -2470,54 +2471,9 @@ int pp_set_episode_worlds(pp_handle h, int on)
     if (h->spawn.sched_on) return fail(PP_ERR_STATE, "pp_set_episode_worlds: a schedule is in force (pp_set_episode_schedule keeps rows per scene, a world draws once)");
     PP_TRY(quiesce(h, false));                            // (the upload stream, which runs the episode step, is behind the last advance)
     if (on) PP_TRY(h->spawn.d_world_end.reserve((size_t)h->caps.max_scenes));      // room first: a failed allocation changes nothing
-    h->spawn.worlds_on = on != 0;
-    if (!on) h->wreset.on = false;                        // (the world reset of §4t keys on every member restarting together: it goes with the mode)
+    if (on) h->spawn.worlds_on = true;
+    else switch_features(h, dmpp::kWorldEpisodes | dmpp::dependants(dmpp::kWorldEpisodes), false);      // (the world reset of §4t keys on every member restarting together: it goes with the mode)
     return features_ok(h, "pp_set_episode_worlds");
-}
-
-// World traffic reset: pp_set_episode_traffic for the vehicles of pp_set_world_traffic.
-int pp_set_episode_world_traffic(pp_handle h, int n_sets, const TrafficStart* starts)
-{
-    if (!h) return fail(PP_ERR_ARG, "null handle");
-    PP_TRY(refuse_if_staged(h, "pp_set_episode_world_traffic", "the world traffic reset"));
-    if (n_sets == 0) { h->wreset.on = false; return features_ok(h, "pp_set_episode_world_traffic"); }
-    if (!h->traffic.on || !h->traffic.world) return fail(PP_ERR_STATE, "pp_set_episode_world_traffic: no world traffic is set (pp_set_world_traffic comes first)");
-    if (!h->episode.on || !h->spawn.on || !h->spawn.worlds_on)
-        return fail(PP_ERR_STATE, "pp_set_episode_world_traffic: world episodes are off (pp_set_episode_worlds comes first: a vehicle resets when its whole world restarts)");
-    const int M = h->spawn.sp.n_starts;
-    if (n_sets < 0 || (n_sets != 1 && n_sets != M))
-        return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: n_sets must be 1 or the n_starts of the spawn model in force (" + std::to_string(M) + ")");
-    if (n_sets > 1 && !starts) return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: n_sets > 1 needs the start states");
-    const size_t n = (size_t)h->traffic.actors, given = starts ? (size_t)(n_sets - 1) * n : 0;
-    for (size_t i = 0; i < given; i++) {
-        if (!std::isfinite(starts[i].s)) return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: start state " + std::to_string(i) + " has a non-finite s");
-        if (!std::isfinite(starts[i].v) || starts[i].v < 0) return fail(PP_ERR_ARG, "pp_set_episode_world_traffic: start state " + std::to_string(i) + ": v must be finite and >= 0");
-    }
-    PP_TRY(quiesce(h, false));                            // (the upload stream, which writes s / v, is behind the last advance)
-    const int o = h->wreset.ever ? 1 - h->wreset.cur : h->wreset.cur;
-    PP_TRY(h->wreset.d_starts[o].reserve((size_t)n_sets * n)); PP_TRY(h->wreset.d_resets[o].reserve(n));      // room first: a failed allocation changes nothing
-    TrafficStart* tab = h->wreset.d_starts[o];
-    // set 0, the capture: s of the current array; v of the current array while following is on, else the speed of every pin
-    HIP_TRY(hipMemcpy2DAsync(&tab->s, sizeof(TrafficStart), h->traffic.d_s[h->traffic.cur], sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
-    if (h->follow.on)
-        HIP_TRY(hipMemcpy2DAsync(&tab->v, sizeof(TrafficStart), h->follow.d_v[h->traffic.cur], sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
-    else
-        HIP_TRY(hipMemcpy2DAsync(&tab->v, sizeof(TrafficStart), h->traffic.d_pin, sizeof(dmpp::TrafficPin), sizeof(double), n, hipMemcpyDeviceToDevice, h->stream));
-    if (given) HIP_TRY(hipMemcpyAsync(tab + n, starts, given * sizeof(TrafficStart), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->wreset.d_resets[o], 0, n * sizeof(int32_t), h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the caller's array may go; the upload stream reads the table from its next launch on
-    if (o != h->wreset.cur) h->wreset.d_starts[h->wreset.cur] = DevBuf<TrafficStart>();      // the table that was in force goes; its counters stay
-    h->wreset.n_sets = n_sets; h->wreset.actors = (int)n; h->wreset.cur = o; h->wreset.on = true; h->wreset.ever = true;
-    return features_ok(h, "pp_set_episode_world_traffic");
-}
-
-int pp_get_episode_world_traffic_resets(pp_handle h, int32_t* n_resets, int n)
-{
-    if (!h || (!n_resets && n > 0)) return fail(PP_ERR_ARG, "null argument");
-    if (!h->wreset.ever) return fail(PP_ERR_STATE, "pp_get_episode_world_traffic_resets: pp_set_episode_world_traffic was never called on this handle");
-    if (n < 0 || n > h->wreset.actors) return fail(PP_ERR_ARG, "n exceeds the vehicles");
-    if (n == 0) return PP_OK;
-    return fetch_behind_advance(h, n_resets, h->wreset.d_resets[h->wreset.cur], (size_t)n * sizeof(int32_t), true);      // waits as pp_get_traffic_state does
 }
 
 // Episode log.  Everything is checked on the host before anything changes.

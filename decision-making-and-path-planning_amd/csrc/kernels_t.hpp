@@ -175,15 +175,26 @@ k_move_traffic(int n_actors, double step, const TrafficPin* __restrict__ actors,
     traffic_store(obs, mot, pin.pool, traffic_pose(t, pts, pin, s));
 }
 
-// ---- episode traffic reset: k_reset_traffic runs in an advance behind k_move_traffic / k_follow_traffic while
-// pp_set_episode_traffic is in force and puts the actors of every scene that RESTARTED in this advance - EpisodeStats.age == 0
-// behind the episode step - back on a start state: set cur_start of the scene's spawn record (n_sets > 1) or set 0.
-//
+// ---- episode traffic reset.  What both reset kernels share: the start state actor a goes back to - set
+// cur_start of scene c's spawn record (n_sets > 1) or set 0; set k of actor a at k * n_actors + a -, its pin and its track:
+// s' = wrap(s*) and v' = v* (speed > 0) or speed (§4i: a parked or reversing actor keeps v = speed).  sstats: read only with n_sets > 1
+struct TrafficRestart { TrafficPin pin; TrackView t; double s, v; };
+__device__ __forceinline__ TrafficRestart traffic_restart(int a, int c, int n_actors, int n_sets, const TrafficPin* __restrict__ actors, const EpisodeSpawnStats* __restrict__ sstats,
+                                                          const TrafficStart* __restrict__ starts, const TrafficTrackDev* __restrict__ tracks, const double* __restrict__ cum)
+{
+    int k = 0;
+    if (n_sets > 1) { k = sstats[c].cur_start; if (k < 0 || k >= n_sets) k = 0; }      // (the set call checked n_sets == n_starts: never taken)
+    const TrafficStart st = starts[(size_t)k * (size_t)n_actors + (size_t)a];
+    const TrafficPin pin = actors[a]; const TrackView t = traffic_view(tracks, cum, pin.track);
+    return { pin, t, traffic_wrap(st.s, t.L, t.closed), pin.speed > 0 ? st.v : pin.speed };
+}
+
+// k_reset_traffic runs in an advance behind k_move_traffic / k_follow_traffic while pp_set_episode_traffic is in force and puts the
+// actors of every scene that RESTARTED in this advance - EpisodeStats.age == 0 behind the episode step - back on a start state.
 // One thread per actor, 256-thread blocks, no LDS, no barrier, no scratch: the shape of k_move_traffic.  A thread whose scene
 // goes on leaves after two loads (its scene, the scene's age).  The others discard the step the traffic kernel has just made:
-// s' = wrap(s*) and - following on - v' = v* (speed > 0) or speed go into the CURRENT arrays (the ones that kernel wrote), the
-// pose of s' into the pinned pool entry with a zero ObMotion, and the actor's counter goes up by one.  Table: set k of actor a
-// at k * n_actors + a.  v_arr: nullptr while following is off; sstats: read only with n_sets > 1.
+// s' and - following on - v' go into the CURRENT arrays (the ones that kernel wrote), the pose of s' into the pinned pool entry
+// with a zero ObMotion, and the actor's counter goes up by one.  v_arr: nullptr while following is off.
 __global__ void __launch_bounds__(kBlock)
 k_reset_traffic(int n_actors, int n_sets, const TrafficPin* __restrict__ actors, const int32_t* __restrict__ scene_of,
                 const EpisodeStats* __restrict__ stats, const EpisodeSpawnStats* __restrict__ sstats, const TrafficStart* __restrict__ starts,
@@ -194,15 +205,10 @@ k_reset_traffic(int n_actors, int n_sets, const TrafficPin* __restrict__ actors,
     if (a >= n_actors) return;
     const int c = scene_of[a];
     if (stats[c].age != 0) return;                      // the scene goes on: its actors stay as the traffic kernel wrote them
-    int k = 0;
-    if (n_sets > 1) { k = sstats[c].cur_start; if (k < 0 || k >= n_sets) k = 0; }      // (the set call checked n_sets == n_starts: never taken)
-    const TrafficStart st = starts[(size_t)k * (size_t)n_actors + (size_t)a];
-    const TrafficPin pin = actors[a];
-    const TrackView t = traffic_view(tracks, cum, pin.track);
-    const double s = traffic_wrap(st.s, t.L, t.closed);
-    s_arr[a] = s;
-    if (v_arr) v_arr[a] = pin.speed > 0 ? st.v : pin.speed;      // (§4i: a parked or reversing actor keeps v = speed)
-    traffic_store(obs, mot, pin.pool, traffic_pose(t, pts, pin, s));
+    const TrafficRestart r = traffic_restart(a, c, n_actors, n_sets, actors, sstats, starts, tracks, cum);
+    s_arr[a] = r.s;
+    if (v_arr) v_arr[a] = r.v;
+    traffic_store(obs, mot, r.pin.pool, traffic_pose(r.t, pts, r.pin, r.s));
     n_resets[a] = n_resets[a] + 1;
 }
 
@@ -380,8 +386,7 @@ k_follow_world_traffic(int n_actors, double dt, TrafficFollow tf, double half_w,
 // first scene stands for it - EpisodeStats.age == 0 there, and its cur_start names the set.
 //
 // One wave per vehicle, four per block, no LDS, no barrier, no scratch: the shape of k_move_world_traffic.  A wave whose world goes
-// on leaves after three scalar loads (its world, the world's first scene, that scene's age).  v_arr: nullptr while following is
-// off; sstats: read only with n_sets > 1.
+// on leaves after three scalar loads (its world, the world's first scene, that scene's age).
 __global__ void __launch_bounds__(kBlock)
 k_reset_world_traffic(int n_actors, int n_sets, const TrafficPin* __restrict__ actors, const int32_t* __restrict__ world,
                       const int32_t* __restrict__ world_first, const FleetPin* __restrict__ fpin, const EpisodeStats* __restrict__ stats,
@@ -396,18 +401,13 @@ k_reset_world_traffic(int n_actors, int n_sets, const TrafficPin* __restrict__ a
     const int p0 = world_first[w];
     if (stats[p0].age != 0) return;                     // the world goes on: its vehicles stay as the traffic kernel wrote them
     const int p1 = world_first[w + 1];
-    int k = 0;
-    if (n_sets > 1) { k = sstats[p0].cur_start; if (k < 0 || k >= n_sets) k = 0; }      // (the set call checked n_sets == n_starts: never taken)
-    const TrafficStart st = starts[(size_t)k * (size_t)n_actors + (size_t)a];
-    const TrafficPin pin = actors[a];
-    const TrackView t = traffic_view(tracks, cum, pin.track);
-    const double s = traffic_wrap(st.s, t.L, t.closed);
+    const TrafficRestart r = traffic_restart(a, p0, n_actors, n_sets, actors, sstats, starts, tracks, cum);
     if (lane == 0) {
-        s_arr[a] = s;
-        if (v_arr) v_arr[a] = pin.speed > 0 ? st.v : pin.speed;      // (§4i: a parked or reversing vehicle keeps v = speed)
+        s_arr[a] = r.s;
+        if (v_arr) v_arr[a] = r.v;
         n_resets[a] = n_resets[a] + 1;
     }
-    world_store(obs, mot, fpin, lane, p0, p1, pin.pool, traffic_pose(t, pts, pin, s));
+    world_store(obs, mot, fpin, lane, p0, p1, r.pin.pool, traffic_pose(r.t, pts, r.pin, r.s));
 }
 
 }  // namespace dmpp

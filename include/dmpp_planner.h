@@ -702,9 +702,10 @@ int pp_coresident_budget(int static_lds, int meta_bytes, int gbm_lds, int lds_bu
                          int mode, int32_t* budget_out);
 /* The rollout feature table ("Feature life cycle"): which features a successful set call switches off, and what holds
  * between the features that are on.  Feature bits: 1 fleet, 2 route, 4 traffic per scene, 8 world traffic, 16 traffic follow,
- * 32 episodes, 64 spawn model, 128 traffic reset, 256 episode log.  Causes: 0 pp_set_scenes / pp_set_egos / pp_set_n_scenes, 1 pp_set_map,
+ * 32 episodes, 64 spawn model, 128 traffic reset, 256 episode log, 512 scenario schedule, 1024 world episodes, 2048 world traffic reset
+ * (the set calls of the last three have no cause: they retire nothing).  Causes: 0 pp_set_scenes / pp_set_egos / pp_set_n_scenes, 1 pp_set_map,
  * 2 pp_set_fleet, 3 pp_set_route, 4 pp_set_traffic, 5 pp_set_world_traffic, 6 pp_set_traffic_follow, 7 pp_set_episodes,
- * 8 pp_set_episode_spawn, 9 pp_set_episode_traffic, 10 pp_set_episode_log (2 + i: the set call of feature bit i), 11 pp_set_traffic /
+ * 8 pp_set_episode_spawn, 9 pp_set_episode_traffic, 10 pp_set_episode_log (2 + i: the set call of feature bit i, i < 9), 11 pp_set_traffic /
  * pp_set_world_traffic with no actors, 12 pp_set_grid_follow, 13 pp_score_begin / pp_score_end.  pp_feature_retires: the bits the cause switches off, -1 for no such cause.
  * pp_feature_consistent: 1 when the features in `mask` may be on together on a handle with / without a resident map and with that
  * resident mode (0 pp_set_scenes, 1 pp_set_egos), else 0.  No device needed. */

@@ -561,6 +561,37 @@ def test_off_means_off(dm, oracle):
 
 
 @gpu
+def test_a_refused_spawn_model_leaves_the_schedule_drawing(dm):
+    """pp_set_episode_spawn retires the schedule before it knows whether its records are on the map; a start record off the map is refused and
+    the schedule is back: rows (one per scene), spawn stats and the run are those of a reference handle, and the rows go on changing."""
+    r = _loop_scene(dm)
+    r["sm"] = r["sm"].copy()
+    r["sm"]["scope"] = 0
+
+    def fresh():
+        p = _planner(dm, r)
+        p.rollout(60)
+        p.sync()
+        return p
+    pl, ref = fresh(), fresh()
+    before = pl.episode_schedule()
+    assert before.shape == (tt.F_N,) and int(before["n_end"].sum()) > 0
+    off_map = (r["starts"][0].copy(), r["starts"][1])
+    off_map[0]["loc"]["road_num"][1] = 99
+    with pytest.raises(dm.PlannerError, match="error -1:"):
+        pl.set_episode_spawn(r["sp"], *off_map)
+    for p in (pl, ref):
+        p.rollout(60)
+        p.sync()
+    for a, b, name in zip(_last(pl), _last(ref), _NAMES):
+        assert a.tobytes() == b.tobytes(), name
+    ref.close()
+    rows = pl.episode_schedule()
+    assert rows.tobytes() != before.tobytes() and int(rows["n_end"].sum()) > int(before["n_end"].sum())
+    pl.close()
+
+
+@gpu
 def test_errors_and_lifetime(dm, oracle):
     r = _cpu_loop(dm, oracle, True)
     n, sm = tt.F_N, r["sm"]

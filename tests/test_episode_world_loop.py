@@ -444,6 +444,28 @@ def test_error_paths_change_nothing(dm, oracle):
 
 
 @gpu
+def test_a_refused_spawn_model_puts_world_episodes_and_the_reset_back(dm, oracle):
+    """pp_set_episode_spawn retires world episodes and the world reset before it knows whether its records are on the map; a start record off
+    the map is refused and both are back: the run goes on like the reference run, byte for byte, and the reset goes on counting."""
+    r = _scene(dm, "sizes")
+    pl, ref = _planner(dm, r), _planner(dm, r)
+    off_map = (r["starts"][0].copy(), r["starts"][1])
+    off_map[0]["loc"]["road_num"][r["n"] + 3] = 99
+    with pytest.raises(dm.PlannerError, match="error -1:"):
+        pl.set_episode_spawn(r["sp"], *off_map)
+    c0 = pl.episode_world_traffic_resets().copy()
+    for p in (pl, ref):
+        p.rollout(40)
+        p.sync()
+    for a, b, what in zip(_last(pl, r), _last(ref, r), _LAST):
+        assert a.tobytes() == b.tobytes(), what
+    ref.close()
+    assert (pl.episode_world_traffic_resets() > c0).all()
+    assert _worlds_on(dm, pl)
+    pl.close()
+
+
+@gpu
 @pytest.mark.parametrize("call", ["spawn", "episodes", "fleet", "world_traffic", "follow", "egos", "worlds_off"])
 def test_life_cycle(dm, oracle, call):
     """What each set call leaves (§4s, §4t): world episodes go with the spawn model; the world reset goes with everything its table was

@@ -145,7 +145,7 @@ def test_header_declares_the_new_symbols(dm):
     lib = dm.load_library()
     for sym in ("pp_set_episode_worlds", "pp_set_episode_world_traffic", "pp_get_episode_world_traffic_resets"):
         assert getattr(lib, sym)
-    # the feature table is as it was: no bit, no cause, no row
+    # the feature table has no new cause
     assert lib.pp_feature_retires(14) == -1
 
 

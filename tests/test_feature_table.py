@@ -8,25 +8,26 @@ import itertools
 
 import pytest
 
-FLEET, ROUTE, TRAFFIC, WORLD, FOLLOW, EPISODES, SPAWN, TRESET, ELOG = (1 << i for i in range(9))
-ALL = (1 << 9) - 1
+FLEET, ROUTE, TRAFFIC, WORLD, FOLLOW, EPISODES, SPAWN, TRESET, ELOG, SCHEDULE, WORLDS, WRESET = (1 << i for i in range(12))
+ALL = (1 << 12) - 1
 NAMES = {FLEET: "fleet", ROUTE: "route", TRAFFIC: "traffic", WORLD: "world traffic", FOLLOW: "follow", EPISODES: "episodes", SPAWN: "spawn",
-         TRESET: "traffic reset", ELOG: "episode log"}
+         TRESET: "traffic reset", ELOG: "episode log", SCHEDULE: "schedule", WORLDS: "world episodes", WRESET: "world reset"}
 # causes, by number (include/dmpp_planner.h)
 (RESIDENT, MAP, SET_FLEET, SET_ROUTE, SET_TRAFFIC, SET_WORLD, SET_FOLLOW, SET_EPISODES, SET_SPAWN, SET_TRESET, SET_ELOG, TRAFFIC_OFF,
  SET_GRID_FOLLOW, SCORE) = range(14)
 TABLE = {
-    RESIDENT: FLEET | ROUTE | TRAFFIC | WORLD | EPISODES | SPAWN | TRESET | ELOG,          # pp_set_scenes, pp_set_egos, pp_set_n_scenes
+    RESIDENT: FLEET | ROUTE | TRAFFIC | WORLD | EPISODES | SPAWN | TRESET | ELOG | SCHEDULE | WORLDS | WRESET,          # pp_set_scenes, pp_set_egos, pp_set_n_scenes
     MAP: ROUTE,
-    SET_FLEET: WORLD,
-    SET_TRAFFIC: TRESET,
-    SET_WORLD: TRESET,
-    TRAFFIC_OFF: TRAFFIC | WORLD | TRESET,                                                 # either traffic call with no actors: traffic itself too
-    SET_FOLLOW: TRESET,
-    SET_EPISODES: SPAWN | TRESET | ELOG,
-    SET_SPAWN: TRESET | ELOG,
+    SET_FLEET: WORLD | WRESET,
+    SET_TRAFFIC: TRESET | WRESET,
+    SET_WORLD: TRESET | WRESET,
+    TRAFFIC_OFF: TRAFFIC | WORLD | TRESET | WRESET,                                        # either traffic call with no actors: traffic itself too
+    SET_FOLLOW: TRESET | WRESET,
+    SET_EPISODES: SPAWN | TRESET | ELOG | SCHEDULE | WORLDS | WRESET,
+    SET_SPAWN: TRESET | ELOG | SCHEDULE | WORLDS | WRESET,
     SET_ROUTE: 0, SET_TRESET: 0, SET_ELOG: 0, SET_GRID_FOLLOW: 0, SCORE: 0,
 }
+# the nine features with a set cause; the set calls of SCHEDULE, WORLDS and WRESET have none: they retire nothing
 SET_CAUSE = {FLEET: SET_FLEET, ROUTE: SET_ROUTE, TRAFFIC: SET_TRAFFIC, WORLD: SET_WORLD, FOLLOW: SET_FOLLOW, EPISODES: SET_EPISODES, SPAWN: SET_SPAWN,
              TRESET: SET_TRESET, ELOG: SET_ELOG}
 ENVS = list(itertools.product((0, 1), (0, 1)))          # (have_map, resident_mode)
@@ -39,6 +40,10 @@ def want_consistent(m, have_map, mode):
            (not (m & ELOG) or bool(m & EPISODES)) and \
            (not (m & WORLD) or bool(m & FLEET)) and \
            (not (m & ROUTE) or bool(have_map and mode == 1)) and \
+           (not (m & SCHEDULE) or bool(m & SPAWN)) and \
+           (not (m & WORLDS) or bool(m & SPAWN)) and \
+           not (m & SCHEDULE and m & WORLDS) and \
+           (not (m & WRESET) or bool(m & WORLD and m & EPISODES and m & SPAWN and m & WORLDS)) and \
            not (m & TRAFFIC and m & WORLD)          # (one TrafficState: per scene or per world)
 
 
@@ -64,7 +69,17 @@ def test_consistent_is_the_documented_invariants(table):
             assert got == int(want_consistent(m, have_map, mode)), (bin(m), have_map, mode)
             n_ok += got
     assert 0 < n_ok < 4 * (ALL + 1) and table.pp_feature_consistent(0, 0, 0) == 1
-    assert table.pp_feature_consistent(ALL & ~WORLD, 1, 1) == 1          # everything per-scene at once is a legal handle
+    assert table.pp_feature_consistent(ALL & ~(WORLD | WORLDS | WRESET), 1, 1) == 1          # everything per-scene at once is a legal handle
+    assert table.pp_feature_consistent(ALL & ~(TRAFFIC | TRESET | SCHEDULE), 1, 1) == 1          # ... and everything per-world
+
+
+def dependants(table, f):
+    """The features that are on in no consistent mask without f."""
+    free = 0
+    for m in range(ALL + 1):
+        if not m & f and table.pp_feature_consistent(m, 1, 1):
+            free |= m
+    return ALL & ~free & ~f
 
 
 def test_every_cause_keeps_a_consistent_state_consistent(table):
@@ -72,6 +87,8 @@ def test_every_cause_keeps_a_consistent_state_consistent(table):
     off form of a set call, which clears its own bit as well."""
     own = {c: f for f, c in SET_CAUSE.items()}
     own[TRAFFIC_OFF] = 0
+    deps = {f: dependants(table, f) for f in (SCHEDULE, WORLDS, WRESET)}
+    assert deps == {SCHEDULE: 0, WORLDS: WRESET, WRESET: 0}          # pp_set_episode_worlds(h, 0) takes the world reset off
     for m in range(ALL + 1):
         for have_map, mode in ENVS:
             if not table.pp_feature_consistent(m, have_map, mode):
@@ -82,6 +99,8 @@ def test_every_cause_keeps_a_consistent_state_consistent(table):
                 for e in envs:
                     assert table.pp_feature_consistent(after, *e), (bin(m), c, e)
                     assert table.pp_feature_consistent(after & ~own.get(c, 0), *e), (bin(m), c, e, "off form")
+            for f, d in deps.items():          # no cause: the off form of the set call takes the feature and its dependants off
+                assert table.pp_feature_consistent(m & ~(f | d), have_map, mode), (bin(m), NAMES[f])
 
 
 def test_masks_are_transitively_closed(table):
@@ -92,7 +111,7 @@ def test_masks_are_transitively_closed(table):
     exempt = []
     for c in range(14):
         r = table.pp_feature_retires(c)
-        for x in NAMES:
+        for x in SET_CAUSE:
             for y in NAMES:
                 if r & x and table.pp_feature_retires(SET_CAUSE[x]) & y and not r & y:
                     assert not together(x, y), f"cause {c} retires {NAMES[x]} and not {NAMES[y]}"
