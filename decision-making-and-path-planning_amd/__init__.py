@@ -136,6 +136,11 @@ ScoreTraceModel = _dt([("depth", i4), ("post", i4), ("trigger", i4), ("flag_mask
 ScoreTick = _dt([("k", i4), ("flags", i4), ("tick", np.int64), ("x", f8), ("y", f8), ("v", f8), ("clearance", f8), ("obs", i4), ("ob_type", i4),
                  ("behavior", i4), ("marks", i4)])
 ScoreTraceInfo = _dt([("n_written", i4), ("state", i4), ("trigger_k", i4), ("trigger", i4), ("post_left", i4), ("n_trigger_ticks", i4), ("_pad", i4, (2,))])
+# conflict score: time to collision and braking demand per scene from the snapshots of consecutive scored ticks
+ConflictModel = _dt([("ttc_warn", f8), ("ttc_crit", f8), ("v_max", f8), ("min_closing", f8)])
+ConflictScore = _dt([("min_ttc", f8), ("max_drac", f8), ("tit_warn", f8), ("last_pos", GlobalPoint2D), ("n_ticks", i4), ("n_conflict_ticks", i4),
+                     ("n_warn_ticks", i4), ("n_crit_ticks", i4), ("min_ttc_tick", i4), ("min_ttc_obs", i4), ("min_ttc_type", i4), ("first_crit_tick", i4),
+                     ("max_drac_tick", i4), ("n_no_history_ticks", i4), ("prev_off", i4), ("prev_n", i4)])
 # scenario schedule: the start record of a restart drawn by weights from per-record outcome counts kept on the device
 EpisodeSchedule = _dt([("scope", i4), ("fail_mask", i4), ("pass_mask", i4), ("min_samples", i4), ("window", i4), ("floor_w", i4), ("gain", i4),
                        ("target", i4), ("prior", i4), ("_pad", i4)])
@@ -214,6 +219,8 @@ _FEATURES = [
      {43: PackedPlan, 44: PackedGrid}),          # (pp_sizeof id 42 stays unassigned)
     ("pp_set_episode_worlds", {"pp_set_episode_worlds": ([_vp, _ci], _ci), "pp_set_episode_world_traffic": ([_vp, _ci, _vp], _ci),
                                "pp_get_episode_world_traffic_resets": ([_vp, _vp, _ci], _ci)}, {}),
+    ("pp_set_conflict_score", {"pp_default_conflict": ([_vp], None), "pp_set_conflict_score": ([_vp, _vp], _ci),
+                               "pp_get_conflict_score": ([_vp, _vp, _ci], _ci)}, {45: ConflictModel, 46: ConflictScore}),
 ]
 
 _lib = None
@@ -411,6 +418,11 @@ def unpack_grid(cfg, packed, out=None):
     c = np.array(cfg, PlannerConfig).reshape(1).copy()          # (kept in a local: the call reads it)
     _check(load_library().pp_unpack_grid(_ptr(c), _ptr(pk), len(pk), _ptr(out)))
     return out
+
+
+def default_conflict():
+    """ConflictModel record of the conflict score (pp_default_conflict): ttc_warn 3 s, ttc_crit 1.5 s, v_max 70 m/s, min_closing 0."""
+    return _default(ConflictModel, "pp_default_conflict")
 
 
 def default_score_trace():
@@ -655,6 +667,23 @@ class Planner:
         if n < 0:
             _check(n)
         return out[:n].copy(), info[0].copy()
+
+    def set_conflict_score(self, model):
+        """pp_set_conflict_score, before or after score_begin: while the scorecard is on, every scored tick differences
+        the obstacle snapshot against the one of the scored tick before and folds the tick's smallest time to collision and largest
+        braking demand into one ConflictScore record per scene.  model: a ConflictModel record (default_conflict()); a second call
+        starts again.  None: the step off; the records stay readable."""
+        if model is None:
+            _check(self.lib.pp_set_conflict_score(self.h, None))
+            return
+        m = np.array(model, ConflictModel).reshape(1).copy()
+        _check(self.lib.pp_set_conflict_score(self.h, _ptr(m)))
+
+    def conflict_score(self):
+        """pp_get_conflict_score: the ConflictScore records, the last enqueued tick included (host wait)."""
+        out = np.zeros(self.n, ConflictScore)
+        _check(self.lib.pp_get_conflict_score(self.h, _ptr(out), self.n))
+        return out
 
     # ---- fleet coupling: the egos of one world are each other's obstacles ------------------
     def set_fleet(self, world_first=None, fm=None):

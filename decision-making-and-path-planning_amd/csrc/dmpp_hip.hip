@@ -283,6 +283,14 @@ struct ScoreTraceState {
     bool on = false, ever = false; ScoreTraceModel tm = {};
     DevBuf<ScoreTick> d_ring; DevBuf<ScoreTraceInfo> d_info;
 };
+// conflict score (first pp_set_conflict_score): the model, caps.max_scenes records and two previous-snapshot buffers of
+// caps.max_obs_total entries - a scored tick reads d_prev[cur] and writes d_prev[cur ^ 1], then cur flips.  Inside the scorecard's life
+// cycle like the trace: while it AND the scorecard are on, a scored tick runs k_score_ego<., ., true>, and reset_scores restarts the
+// records.  They stay readable after it went off
+struct ConflictState {
+    bool on = false, ever = false; int cur = 0; ConflictModel cm = {};
+    DevBuf<ConflictScore> d_score; DevBuf<ObPoint> d_prev[2];
+};
 // packed streamed fetch (first pp_set_packed_fetch(h, 1)): one PackedPlan set per PlanOut set and one PackedGrid
 // set per GridOut group position (an armed handle is a streamed one: groups of 1, tick slot 0 only), each written by its tick's pack
 // kernel in stream order behind the kernel that wrote the PlanOut / GridOut set of the same index - so a set is rewritten only
@@ -391,6 +399,7 @@ struct pp_planner {
     TrafficResetState treset, wreset;                         // per scene (§4m), per world (§4t)
     EpisodeLogState elog;
     ScoreTraceState strace;
+    ConflictState conflict;
     PackedState packed;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
@@ -1018,6 +1027,16 @@ static int reset_score_trace(pp_handle h)
     return PP_OK;
 }
 
+// The records of the conflict score at their starting values (§4u 0.), on the handle's stream: behind join_all, as reset_scores.
+static int reset_conflict(pp_handle h)
+{
+    if (!h->conflict.d_score) return PP_OK;
+    const int ns = h->caps.max_scenes;
+    hipLaunchKernelGGL(dmpp::k_conflict_reset, dim3((unsigned)((ns + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, ns, h->conflict.d_score);
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+
 // The scorecard's starting values, on the handle's stream behind join_all (every scoring kernel enqueued so far has finished
 // before it); the caller's host wait follows.
 static int reset_scores(pp_handle h)
@@ -1032,6 +1051,7 @@ static int reset_scores(pp_handle h)
         HIP_TRY(hipGetLastError());
     }
     if (h->strace.on) PP_TRY(reset_score_trace(h));       // the score trace restarts where the scorecard does (§4o)
+    if (h->conflict.on) PP_TRY(reset_conflict(h));        // ... and the conflict score (§4u)
     return PP_OK;
 }
 
@@ -1465,15 +1485,24 @@ int pp_plan_tick(pp_handle h)
             const dim3 sgrid((unsigned)((n + dmpp::kScScenes - 1) / dmpp::kScScenes));
             // episode log: the tick is folded into the scorecards of the running episodes too (§4n 3.); score trace: lane 0 stores the
             // tick's record into the scene's ring in front of the fold (§4o) - EpisodeStats only while episodes are on
-            const bool log = h->elog.on && h->elog.d_score, trace = h->strace.on;
+            // conflict score: every lane differences its entries against the snapshot of the scored tick before and stores them for the
+            // next one, lane 0 folds the tick's TTC and DRAC in front of both (§4u); the two buffers change places behind every launch
+            const bool log = h->elog.on && h->elog.d_score, trace = h->strace.on, conflict = h->conflict.on;
             RolloutScore* ep_score = log ? h->elog.d_score.get() : nullptr;
-            const EpisodeStats* ep_stats = trace && h->episode.on ? h->episode.d_stats.get() : nullptr;
+            const EpisodeStats* ep_stats = (trace || conflict) && h->episode.on ? h->episode.d_stats.get() : nullptr;
             ScoreTraceInfo* tinfo = trace ? h->strace.d_info.get() : nullptr;
             ScoreTick* tring = trace ? h->strace.d_ring.get() : nullptr;
-            auto* kern = log ? (trace ? dmpp::k_score_ego<true, true> : dmpp::k_score_ego<true, false>) : (trace ? dmpp::k_score_ego<false, true> : dmpp::k_score_ego<false, false>);
+            ConflictScore* cscore = conflict ? h->conflict.d_score.get() : nullptr;
+            const ObPoint* prev = conflict ? h->conflict.d_prev[h->conflict.cur].get() : nullptr;
+            ObPoint* prev_next = conflict ? h->conflict.d_prev[h->conflict.cur ^ 1].get() : nullptr;
+            auto* kern = conflict ? (log ? (trace ? dmpp::k_score_ego<true, true, true> : dmpp::k_score_ego<true, false, true>)
+                                         : (trace ? dmpp::k_score_ego<false, true, true> : dmpp::k_score_ego<false, false, true>))
+                                  : (log ? (trace ? dmpp::k_score_ego<true, true, false> : dmpp::k_score_ego<true, false, false>)
+                                         : (trace ? dmpp::k_score_ego<false, true, false> : dmpp::k_score_ego<false, false, false>));
             hipLaunchKernelGGL(kern, sgrid, dim3(dmpp::kBlock), 0, su, 0.5 * c.Vehicle_Width, h->score.dt, n, I.n_obs_total,
                                I.d_in, d_plan, h->d_state, obs_now, h->rollout.d_flags, h->score.d_score, ep_score,
-                               h->tick_seq, h->strace.tm, ep_stats, tinfo, tring);
+                               h->tick_seq, h->strace.tm, ep_stats, tinfo, tring, h->conflict.cm, cscore, prev, prev_next);
+            if (conflict) h->conflict.cur ^= 1;
             PP_TRY(h->score.ego.record(su));
         }
     }
@@ -1943,6 +1972,44 @@ int pp_read_score_trace(pp_handle h, int scene, ScoreTick* out, int cap, ScoreTr
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     return (int)n;
+}
+
+// Conflict score.  Everything is checked on the host before anything changes.
+void pp_default_conflict(ConflictModel* m)
+{
+    if (!m) return;
+    m->ttc_warn = 3.0; m->ttc_crit = 1.5; m->v_max = 70.0; m->min_closing = 0.0;
+}
+
+int pp_set_conflict_score(pp_handle h, const ConflictModel* m)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (!m) { h->conflict.on = false; return PP_OK; }    // (the records stay readable)
+    if (!std::isfinite(m->ttc_warn) || !(m->ttc_warn > 0)) return fail(PP_ERR_ARG, "pp_set_conflict_score: ttc_warn must be finite and > 0");
+    if (!std::isfinite(m->ttc_crit) || !(m->ttc_crit > 0) || !(m->ttc_crit <= m->ttc_warn)) return fail(PP_ERR_ARG, "pp_set_conflict_score: ttc_crit must be finite, > 0 and <= ttc_warn");
+    if (!std::isfinite(m->v_max) || !(m->v_max > 0)) return fail(PP_ERR_ARG, "pp_set_conflict_score: v_max must be finite and > 0");
+    if (!std::isfinite(m->min_closing) || !(m->min_closing >= 0)) return fail(PP_ERR_ARG, "pp_set_conflict_score: min_closing must be finite and >= 0");
+    PP_TRY(quiesce(h, false));                            // every scored tick so far is in front of the handle's stream
+    const size_t ns = (size_t)h->caps.max_scenes, no = (size_t)std::max(h->caps.max_obs_total, 1);      // room first: a failed allocation changes nothing in force
+    PP_TRY(h->conflict.d_score.reserve(ns)); PP_TRY(h->conflict.d_prev[0].reserve(no)); PP_TRY(h->conflict.d_prev[1].reserve(no));
+    PP_TRY(reset_conflict(h));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the upload stream reads all of it from its next launch on
+    h->conflict.cm = *m; h->conflict.on = true; h->conflict.ever = true;
+    return PP_OK;
+}
+
+int pp_get_conflict_score(pp_handle h, ConflictScore* out, int n_scenes)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->conflict.ever) return fail(PP_ERR_STATE, "pp_get_conflict_score: pp_set_conflict_score was never called on this handle");
+    if (n_scenes < 0 || n_scenes > h->n_scenes) return fail(PP_ERR_ARG, "n_scenes exceeds the resident scenes");
+    if (n_scenes == 0) return PP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    PP_TRY(join_all(h));                                  // behind score.ego, as pp_get_rollout_score
+    if (h->episode.on) PP_TRY(h->rollout.adv.wait(h->stream));
+    HIP_TRY(hipMemcpyAsync(out, h->conflict.d_score, (size_t)n_scenes * sizeof(ConflictScore), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return PP_OK;
 }
 
 // Every resident scene's OWN obstacle entries (obs_off, obs_n): of the resident records, or - fleet on - the ones pinned then
@@ -3024,6 +3091,7 @@ size_t pp_sizeof(int which)
     case 38: return sizeof(EpisodeSchedule); case 39: return sizeof(EpisodeScheduleRow);
     case 40: return sizeof(EgoTracker); case 41: return sizeof(EgoTrackState);
     case 43: return sizeof(PackedPlan); case 44: return sizeof(PackedGrid);      // (42 stays unassigned)
+    case 45: return sizeof(ConflictModel); case 46: return sizeof(ConflictScore);
     default: return 0;
     }
 }

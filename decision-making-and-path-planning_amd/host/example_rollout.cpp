@@ -47,6 +47,10 @@
 // With --score-trace DEPTH[,POST] the score trace is on (pp_set_score_trace with the default model): every scene keeps its
 // last DEPTH scored ticks in a ring on the device, which freezes POST ticks behind the scene's first contact; behind the run the host
 // prints every frozen scene's triggering tick and, for the first three, the records before it.  Any mode; a routed run gets the scorecard.
+// With --conflict [WARN[,CRIT]] the conflict score is on (pp_set_conflict_score with the default model, ttc_warn / ttc_crit replaced; DESIGN.md
+// §4u): the device differences the obstacle snapshots of consecutive scored ticks and keeps every scene's smallest time to collision and largest
+// braking demand; behind the run the host prints min_ttc, n_crit_ticks and max_drac per scene, and the worst scene.  Any mode; a routed run gets
+// the scorecard.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <algorithm>
@@ -57,6 +61,36 @@
 #include <vector>
 
 #define CHECK(expr) do { int rc__ = (expr); if (rc__) { std::fprintf(stderr, "%s: %s\n", #expr, pp_last_error()); return 2; } } while (0)
+
+// --conflict [WARN[,CRIT]]: the conflict score on with the default model, its two thresholds replaced (0: the default)
+struct ConflictArg { bool on = false; double warn = 0, crit = 0; };
+static int set_conflict(pp_handle h, const ConflictArg& a)
+{
+    ConflictModel cm; pp_default_conflict(&cm);
+    if (a.warn > 0) { cm.ttc_warn = a.warn; if (cm.ttc_crit > a.warn) cm.ttc_crit = a.warn; }
+    if (a.crit > 0) cm.ttc_crit = a.crit;
+    CHECK(pp_set_conflict_score(h, &cm));
+    return 0;
+}
+
+// ... and behind the run: every scene's record in short, and the worst scene
+static int print_conflict(pp_handle h, int n)
+{
+    std::vector<ConflictScore> cs((size_t)n);
+    CHECK(pp_get_conflict_score(h, cs.data(), n));
+    int worst = -1;
+    for (int s = 0; s < n; s++) {
+        const ConflictScore& c = cs[(size_t)s];
+        std::printf("conflict: scene %d  min_ttc %.3f s  n_crit_ticks %d  max_drac %.3f m/s^2  (%d of %d ticks with a conflict, %d without history)\n", s, c.min_ttc,
+                    c.n_crit_ticks, c.max_drac, c.n_conflict_ticks, c.n_ticks, c.n_no_history_ticks);
+        if (c.min_ttc_tick >= 0 && (worst < 0 || c.min_ttc < cs[(size_t)worst].min_ttc)) worst = s;
+    }
+    if (worst < 0) { std::printf("conflict: no scene had a conflict\n"); return 0; }
+    const ConflictScore& c = cs[(size_t)worst];
+    std::printf("conflict: worst scene %d: min_ttc %.3f s on scored tick %d against entry %d (type %d), first critical tick %d, time-integrated TTC %.3f s^2, max_drac %.3f m/s^2 on tick %d\n",
+                worst, c.min_ttc, c.min_ttc_tick, c.min_ttc_obs, c.min_ttc_type, c.first_crit_tick, c.tit_warn, c.max_drac, c.max_drac_tick);
+    return 0;
+}
 
 // --score-trace DEPTH[,POST]: the recorder on with the default model (a ring freezes POST ticks behind its first contact)
 static int set_score_trace(pp_handle h, int depth, int post)
@@ -120,7 +154,7 @@ static int print_tracker(pp_handle h, int n)
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
-static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post, int sched, bool worlds)
+static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post, int sched, bool worlds, const ConflictArg& conflict)
 {
     const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
     if (contact) traffic = true;                      // (the vehicle to touch)
@@ -237,7 +271,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         if (react) { TrafficFollow tf; pp_default_traffic_follow(&tf); CHECK(pp_set_traffic_follow(h, &tf)); }
         CHECK(pp_score_begin(h, model.dt));
     }
-    if ((log_cap || trace_depth) && !traffic) CHECK(pp_score_begin(h, model.dt));      // (the records carry their episode's scorecard; the trace records scored ticks)
+    if ((log_cap || trace_depth || conflict.on) && !traffic) CHECK(pp_score_begin(h, model.dt));      // (the records carry their episode's scorecard; the trace and the conflict score see scored ticks)
     if (episodes) { EpisodeModel em; pp_default_episode_model(&em); CHECK(pp_set_episodes(h, &em)); }      // last: it captures what the calls above set up
     if (spawn) {                                      // M start records per ego: record k stands 5 k lane points behind record 0, on the same lane
         EpisodeSpawn sp; pp_default_episode_spawn(&sp); sp.n_starts = M; sp.contact = contact ? 1 : 0;
@@ -271,10 +305,12 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
     EpisodeSchedule sm; pp_default_episode_schedule(&sm); sm.scope = sched == 2 ? 0 : 1;
     if (sched) CHECK(pp_set_episode_schedule(h, &sm));       // (part of the spawn model in force: it retires nothing, anywhere behind pp_set_episode_spawn)
     if (trace_depth && set_score_trace(h, trace_depth, trace_post)) return 2;      // (no feature: anywhere)
+    if (conflict.on && set_conflict(h, conflict)) return 2;                        // (likewise)
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
     if (trace_depth && print_score_trace(h, n, trace_depth)) return 2;
+    if (conflict.on && print_conflict(h, n)) return 2;
     if (log_cap) {
         std::vector<EpisodeRecord> rec((size_t)log_cap);
         long long lost = 0, total = 0;
@@ -415,6 +451,7 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
 int main(int argc, char** argv)
 {
     bool fleet = false, route = false, follow = false, traffic = false, react = false, shared = false, episodes = false, contact = false, reset = false, worlds = false; int starts = 0, log_cap = 0, trace_depth = 0, trace_post = -1, sched = 0;
+    ConflictArg conflict;
     for (int a = 1; a < argc; a++) {
         if (std::strcmp(argv[a], "--fleet") == 0) fleet = true;
         else if (std::strcmp(argv[a], "--route") == 0) route = true;
@@ -439,7 +476,11 @@ int main(int argc, char** argv)
         }
         else if (std::strcmp(argv[a], "--log") == 0 && a + 1 < argc) log_cap = std::atoi(argv[++a]);
         else if (std::strcmp(argv[a], "--score-trace") == 0 && a + 1 < argc) { if (std::sscanf(argv[++a], "%d,%d", &trace_depth, &trace_post) < 1) trace_depth = -1; }
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react] [--episodes [--starts M] --contact --worlds [--reset-traffic]]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--conflict") == 0) {
+            conflict.on = true;
+            if (a + 1 < argc && argv[a + 1][0] != '-' && std::sscanf(argv[++a], "%lf,%lf", &conflict.warn, &conflict.crit) < 1) conflict.warn = -1;
+        }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react] [--episodes [--starts M] --contact --worlds [--reset-traffic]]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]] [--conflict [WARN[,CRIT]]]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
@@ -457,7 +498,9 @@ int main(int argc, char** argv)
     if (log_cap && !(route && episodes)) { std::fprintf(stderr, "--log records how episodes ended: use it with --route --episodes\n"); return 2; }
     if (log_cap < 0 || log_cap > DMPP_EPISODE_LOG_MAX) { std::fprintf(stderr, "--log takes 1 .. %d records\n", DMPP_EPISODE_LOG_MAX); return 2; }
     if (trace_depth < 0 || trace_depth > DMPP_SCORE_TRACE_MAX || (trace_depth && trace_post >= trace_depth)) { std::fprintf(stderr, "--score-trace takes DEPTH 1 .. %d and POST 0 .. DEPTH - 1\n", DMPP_SCORE_TRACE_MAX); return 2; }
-    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post, sched, worlds);
+    if (conflict.on && (conflict.warn < 0 || conflict.crit < 0 || !std::isfinite(conflict.warn) || !std::isfinite(conflict.crit) || (conflict.warn > 0 && conflict.crit > conflict.warn)))
+        { std::fprintf(stderr, "--conflict takes WARN > 0 and 0 < CRIT <= WARN, in seconds\n"); return 2; }
+    if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post, sched, worlds, conflict);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
     PlannerCaps caps{}; caps.max_scenes = n; caps.max_obs_total = n * n_obs; caps.max_lane_pts_total = n * 3 * PP_GEN_LANE_PTS; caps.max_ref_pts_total = n * PP_GEN_REF_PTS;
@@ -489,9 +532,11 @@ int main(int argc, char** argv)
     long long last = 0;
     CHECK(pp_score_begin(h, model.dt));
     if (trace_depth && set_score_trace(h, trace_depth, trace_post)) return 2;
+    if (conflict.on && set_conflict(h, conflict)) return 2;
     CHECK(pp_rollout(h, ticks, &model, trace, &last));
     CHECK(pp_sync(h));
     if (trace_depth && print_score_trace(h, n, trace_depth)) return 2;
+    if (conflict.on && print_conflict(h, n)) return 2;
     std::vector<int32_t> flags(n);
     CHECK(pp_get_ego_flags(h, flags.data(), n));
 

@@ -262,6 +262,31 @@ int  pp_set_score_trace(pp_handle h, const ScoreTraceModel* m);
 int  pp_get_score_trace_info(pp_handle h, ScoreTraceInfo* out, int n_scenes);
 int  pp_read_score_trace(pp_handle h, int scene, ScoreTick* out, int cap, ScoreTraceInfo* info, int rearm);
 
+/* ---- conflict score: time to collision and braking demand per scene -------------------------------------------------
+ * The scorecard judges a run by disc clearance alone: it cannot tell an ego that passed a parked car at 0.4 m from one that was 0.4 s
+ * from a head-on hit.  pp_set_conflict_score keeps the obstacle snapshot of the scored tick before on the device.  While it AND the
+ * scorecard are on, k_score_ego gives every entry of the scene's slice a velocity by differencing the two snapshots - per-scene traffic,
+ * world traffic, peers, moving own obstacles and plain pp_update_async feeds alike, no producer of obstacles changes - and the ego one by
+ * differencing its own positions, and folds the smallest time to collision t* of the tick and the largest braking demand into one
+ * ConflictScore record per scene: the minimum, where and against what, the warn and critical ticks, the time-integrated TTC.  An entry
+ * whose slot changed hands (another type or radius, a moved or grown slice, a jump above v_max * dt_score) and an ego that restarted
+ * have one tick without a velocity, never a wrong one.  No kernel, no launch and no host wait is added to a tick.
+ * Like the score trace it belongs to the scorecard's life cycle and is no rollout feature: no set call retires it, and what restarts
+ * the totals - pp_score_begin, pp_set_scenes / pp_set_egos / pp_set_n_scenes while scoring is on - puts the records of a step that is
+ * on back to their starting values.
+ * pp_default_conflict: ttc_warn 3 s, ttc_crit 1.5 s, v_max 70 m/s, min_closing 0.
+ * pp_set_conflict_score: legal before or after pp_score_begin.  Allocates caps.max_scenes records and the previous-snapshot buffers
+ * (two of caps.max_obs_total ObPoint: one is read while the other is written), sets every record to its starting values (a second
+ * call starts again) and turns the step on; one host wait, behind every tick and advance enqueued so far.  m == NULL: the step off;
+ * the records stay readable and no longer change.  PP_ERR_ARG, with nothing changed: a field that is not finite, ttc_warn, ttc_crit or
+ * v_max not > 0, ttc_crit > ttc_warn, min_closing < 0.  A handle that never makes the call allocates and launches exactly what it did
+ * without it.
+ * pp_get_conflict_score: the records of the first n_scenes scenes, the last enqueued tick included; waits as pp_get_rollout_score.
+ * PP_ERR_STATE on a handle that never made the set call. */
+void pp_default_conflict(ConflictModel* m);
+int  pp_set_conflict_score(pp_handle h, const ConflictModel* m);
+int  pp_get_conflict_score(pp_handle h, ConflictScore* out, int n_scenes);
+
 /* ---- fleet coupling: the egos of one world see each other during a rollout -----------------------------------
  * pp_set_fleet groups the resident scenes into WORLDS: world w is the contiguous run of scenes [world_first[w], world_first[w+1]);
  * world_first has n_worlds + 1 entries, starts at 0, ends at the resident scene count and is strictly increasing (host pointer).
@@ -675,7 +700,8 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 17 MapDesc, 18 PpSceneIo, 19 EgoModel, 20 EgoTrace, 21 RolloutScore, 22 FleetModel, 23 RouteLeg, 24 RouteModel,
  * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
  * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord, 35 ScoreTraceModel, 36 ScoreTick,
- * 37 ScoreTraceInfo, 38 EpisodeSchedule, 39 EpisodeScheduleRow, 40 EgoTracker, 41 EgoTrackState */
+ * 37 ScoreTraceInfo, 38 EpisodeSchedule, 39 EpisodeScheduleRow, 40 EgoTracker, 41 EgoTrackState,
+ * (42 unassigned) 43 PackedPlan, 44 PackedGrid, 45 ConflictModel, 46 ConflictScore */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -509,6 +509,30 @@ typedef struct ScoreTraceInfo {
     int32_t _pad[2];
 } ScoreTraceInfo;                                                           /* 32 B */
 
+/* ---- conflict score (build-defined), inside the scorecard's life cycle -------------------------------------
+ * pp_set_conflict_score keeps the obstacle snapshot of the scored tick before on the device: while the scorecard is on, every
+ * scored tick gives every entry of the scene's slice a velocity by differencing, and the smallest time to collision (discs of
+ * radius + half the vehicle width, constant relative velocity) and the largest braking demand are folded into one record per scene. */
+typedef struct ConflictModel {
+    double ttc_warn;     /* s, finite, > 0: a tick with t* <= ttc_warn is a warn tick                  */
+    double ttc_crit;     /* s, finite, 0 < ttc_crit <= ttc_warn                                        */
+    double v_max;        /* m/s, finite, > 0: a displacement above v_max * dt_score gives no velocity  */
+    double min_closing;  /* m/s, finite, >= 0: a closing speed must be > min_closing                   */
+} ConflictModel;                                                            /* 32 B */
+typedef struct ConflictScore {
+    double  min_ttc;                 /* s; +inf while no tick had a conflict */
+    double  max_drac;                /* m/s^2: the largest deceleration rate to avoid a crash, vc^2 / (2 gap) */
+    double  tit_warn;                /* s^2: sum of (ttc_warn - t*) * dt_score over the warn ticks (time-integrated TTC) */
+    GlobalPoint2D last_pos;          /* the ego of the scored tick before */
+    int32_t n_ticks;                 /* scored ticks while the step was on */
+    int32_t n_conflict_ticks, n_warn_ticks, n_crit_ticks;
+    int32_t min_ttc_tick, min_ttc_obs, min_ttc_type;   /* k, j* and snapshot[obs_off + j*].type of min_ttc; -1, -1, 0 without one */
+    int32_t first_crit_tick;         /* k of the first tick with t* <= ttc_crit; -1 */
+    int32_t max_drac_tick;           /* k of max_drac; -1 */
+    int32_t n_no_history_ticks;      /* ticks k > 0 whose ego had no usable tick before: a restart, or a jump above v_max * dt_score */
+    int32_t prev_off, prev_n;        /* state of the step: the slice the previous-snapshot buffer holds for this scene */
+} ConflictScore;                                                            /* 88 B */
+
 /* ---- scenario schedule (build-defined), part of the spawn model in force --------------------------------
  * pp_set_episode_schedule makes the hashed start choice of §4l a WEIGHTED one: the device keeps, per start record, how many
  * episodes ended on it and how many of those failed, and a record's weight peaks where its failure rate meets `target`.

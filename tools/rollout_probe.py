@@ -50,7 +50,10 @@ scene stores every tick).  With ONE_ROLLOUT one more leg of each, so that one ke
 TRACK=1 [TRACK_BIAS=b]: every run has a rollout leg of routed ring egos (grid stage off, scorecard on for its replan count) without and
 one with the ego tracker (pp_set_ego_tracker: the default model with curv_bias b, DESIGN.md §4q: k_advance_route<true> in the place of
 <false>), alternating.  The workloads differ once tracked egos replan on lateral error: the replan counts are printed beside the rates.
-With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels."""
+With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels.
+CONFLICT=1 (implies SCORE=1): every run has a scored rollout leg without and one with the conflict score (pp_set_conflict_score: the default
+model, DESIGN.md §4u: k_score_ego<false, false, true> in the place of <false, false, false>), alternating; the records are read behind the
+timed rollout, outside the timing.  With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels."""
 import os
 import statistics
 import sys
@@ -80,7 +83,8 @@ def fresh():
     return pl, sc
 
 
-SCORE = os.environ.get("SCORE", "0")
+CONFLICT = os.environ.get("CONFLICT", "0") == "1"
+SCORE = "1" if CONFLICT else os.environ.get("SCORE", "0")
 FLEET = int(os.environ.get("FLEET", "0"))
 FLEET_WORLD = int(os.environ.get("FLEET_WORLD", "0"))
 
@@ -346,7 +350,7 @@ def track_run(on, bias):
 TRACE = int(os.environ.get("TRACE", "0"))
 
 
-def rollout_run(score=SCORE == "1", follow=False, trace=0):
+def rollout_run(score=SCORE == "1", follow=False, trace=0, conflict=False):
     pl, _ = fresh()
     if follow:
         pl.set_grid_follow(dm.default_grid_follow())
@@ -358,6 +362,8 @@ def rollout_run(score=SCORE == "1", follow=False, trace=0):
         if os.environ.get("TRACE_TRIGGER"):          # TRACE_TRIGGER=0: plain rings that never freeze - every scene stores every tick
             tm["trigger"] = int(os.environ["TRACE_TRIGGER"])
         pl.set_score_trace(tm)
+    if conflict:
+        pl.set_conflict_score(dm.default_conflict())
     pl.rollout(warm, model)
     pl.sync()
     t0 = time.perf_counter()
@@ -375,6 +381,11 @@ def rollout_run(score=SCORE == "1", follow=False, trace=0):
         got = len(pl.read_score_trace(int(frozen_rings[0]))[0]) if len(frozen_rings) else 0
         rollout_run.traced = "%d rings frozen, %d counting, %d armed; %d records written in all; the first frozen ring holds %d" % (
             len(frozen_rings), int((info["state"] == 1).sum()), int((info["state"] == 0).sum()), int(info["n_written"].sum()), got)
+    if conflict:                              # outside the timing
+        c = pl.conflict_score()
+        rollout_run.conflicts = "%d ticks, %d scenes with a conflict, %d with a critical tick, smallest TTC %.3f s, largest DRAC %.3f m/s^2, %d ticks without history" % (
+            int(c["n_ticks"][0]), int((c["n_conflict_ticks"] > 0).sum()), int((c["n_crit_ticks"] > 0).sum()), float(c["min_ttc"].min()), float(c["max_drac"].max()),
+            int(c["n_no_history_ticks"].sum()))
     pl.close()
     return n * steps / dt, frozen
 
@@ -574,6 +585,20 @@ if os.environ.get("FOLLOW", "0") == "1":
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more following rollout alone
         follow_run(True)
+    sys.exit(0)
+if CONFLICT:
+    off, on = [], []
+    for r in range(runs):
+        a, _ = rollout_run(True)
+        b, _ = rollout_run(True, conflict=True)
+        off.append(a), on.append(b)
+        print("run %d  %d scenes, scorecard on  conflict off %.3f M ticks/s   conflict on %.3f M ticks/s (%s)" % (r, n, a / 1e6, b / 1e6, rollout_run.conflicts), flush=True)
+    print("median  %d scenes, scorecard on  conflict off %.3f M ticks/s (spread %.3f)   conflict on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: both kernels in one trace
+        rollout_run(True)
+        rollout_run(True, conflict=True)
     sys.exit(0)
 if SCORE == "1" and TRACE > 0:
     off, on = [], []
