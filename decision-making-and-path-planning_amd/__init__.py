@@ -124,6 +124,12 @@ EGO_CONTACT = 128             # cause words only: the ego touched an obstacle of
 EGO_WORLD = 256               # cause words only: another ego of the scene's world ended on this advance (DMPP_EGO_WORLD, §4s)
 # episode traffic reset: the actors of a restarted scene go back to a start state, one set per start record
 TrafficStart = _dt([("s", f8), ("v", f8)])
+# traffic manoeuvres: triggered lane changes, lateral offsets and speed changes of the actors of set_traffic
+MANOEUVRE_MAX = 8
+TRIG_ADVANCES, TRIG_EGO_DIST, TRIG_EGO_TIME = 0, 1, 2          # TrafficManoeuvre.trigger = kind | side << 8 (side 1: ego behind, 2: ego ahead)
+TrafficManoeuvre = _dt([("dist", f8), ("time", f8), ("lat_end", f8), ("speed", f8), ("actor", i4), ("trigger", i4), ("after", i4), ("track", i4),
+                        ("n_steps", i4), ("_pad", i4)])
+TrafficManoeuvreState = _dt([("lat", f8), ("lat0", f8), ("v0", f8), ("track", i4), ("next", i4), ("k", i4), ("clock", i4), ("n_done", i4), ("_pad", i4)])
 # episode log: one record per ended episode, appended on the device in the order of the scenes
 EPISODE_LOG_MAX = 1 << 20
 EpisodeRecord = _dt([("scene", i4), ("episode", i4), ("start", i4), ("cause", i4), ("age", i4), ("seq", i4), ("tick", np.int64),
@@ -221,6 +227,8 @@ _FEATURES = [
                                "pp_get_episode_world_traffic_resets": ([_vp, _vp, _ci], _ci)}, {}),
     ("pp_set_conflict_score", {"pp_default_conflict": ([_vp], None), "pp_set_conflict_score": ([_vp, _vp], _ci),
                                "pp_get_conflict_score": ([_vp, _vp, _ci], _ci)}, {45: ConflictModel, 46: ConflictScore}),
+    ("pp_set_traffic_manoeuvres", {"pp_set_traffic_manoeuvres": ([_vp, _ci, _vp], _ci), "pp_get_traffic_manoeuvre_state": ([_vp, _vp, _ci], _ci),
+                                   "pp_check_traffic_manoeuvres": ([_ci, _ci, _ci, _vp], _ci)}, {47: TrafficManoeuvre, 48: TrafficManoeuvreState}),
 ]
 
 _lib = None
@@ -909,6 +917,19 @@ class Planner:
         total, lost = C.c_longlong(), C.c_longlong()
         _check(self.lib.pp_get_episode_log_info(self.h, C.byref(total), C.byref(lost)))
         return total.value, lost.value
+
+    def set_traffic_manoeuvres(self, records=None):
+        """pp_set_traffic_manoeuvres, after set_traffic and before set_episode_traffic: TrafficManoeuvre records, those
+        of one actor contiguous and in list order, the actors non-decreasing.  records None (or none): off - every actor goes on as
+        a plain actor of the track it is on."""
+        m = np.zeros(0, TrafficManoeuvre) if records is None else np.ascontiguousarray(records, TrafficManoeuvre).reshape(-1)
+        _check(self.lib.pp_set_traffic_manoeuvres(self.h, len(m), _ptr(m) if len(m) else None))
+
+    def get_traffic_manoeuvre_state(self):
+        """pp_get_traffic_manoeuvre_state: the TrafficManoeuvreState of every actor, as traffic_state gives the arc lengths (host wait)."""
+        out = np.zeros(getattr(self, "n_traffic", 0), TrafficManoeuvreState)
+        _check(self.lib.pp_get_traffic_manoeuvre_state(self.h, _ptr(out), len(out)))
+        return out
 
     def traffic_speed(self):
         """pp_get_traffic_speed: the speed (m/s) of every actor, as traffic_state gives the arc lengths (host wait)."""

@@ -32,6 +32,7 @@
 #include "kernels_el.hpp"
 #include "kernels_f.hpp"
 #include "kernels_t.hpp"
+#include "kernels_tm.hpp"
 #include "kernels_op.hpp"
 #include "kernels_pk.hpp"
 #include "search_budget.hpp"
@@ -218,7 +219,7 @@ struct RouteState { bool on = false; RouteModel rm = { 0, 0 }; DevBuf<RouteLeg> 
 // world (pp_set_world_traffic): one vehicle per WORLD of the fleet in force - d_pin[a].pool is then the SLOT, d_world
 // (allocated by that call only) every vehicle's world, scene_of the worlds, and the pins are the fleet's FleetPin table
 struct TrafficState {
-    bool on = false, world = false; int actors = 0, end = 0;
+    bool on = false, world = false; int actors = 0, end = 0, n_tracks = 0;
     DevBuf<int32_t> d_world;
     DevBuf<dmpp::TrafficPin> d_pin; DevBuf<dmpp::TrafficTrackDev> d_tracks; DevBuf<double> d_cum; DevBuf<GlobalPoint2D> d_pts; DevBuf<double> d_s[2];
     std::vector<int32_t> scene_of, track_of;      // host: what a later pp_set_traffic_follow groups the actors by
@@ -255,6 +256,16 @@ struct SpawnState {
 struct FollowState {
     bool on = false; TrafficFollow tf = {};
     DevBuf<double> d_v[2]; DevBuf<dmpp::TrafficRef> d_ref; DevBuf<int32_t> d_first, d_members;
+};
+// traffic manoeuvres (pp_set_traffic_manoeuvres): part of the per-scene traffic set - no feature bit, no cause: `on`
+// never outlives traffic.on (drop_manoeuvres).  The records and every actor's run of them, every actor's scene and the actor
+// indices by (scene, index), and the states twice: while on, TrafficState::d_s[1] exists as well, every advance reads set
+// traffic.cur of (s, v, state) and writes the other one (manoeuvre_traffic), with following or without.  All of it is allocated
+// by the first successful set call, never before
+struct ManoeuvreState {
+    bool on = false;
+    DevBuf<TrafficManoeuvre> d_recs; DevBuf<int32_t> d_rec_first, d_scene_of, d_scene_first, d_members;
+    DevBuf<TrafficManoeuvreState> d_state[2];
 };
 // episode traffic reset (first pp_set_episode_traffic): every actor's scene, the table of start states - set k of
 // actor a at k * actors + a - and the counters; two sets of table and counters, so that a failed call leaves the ones in force
@@ -394,6 +405,7 @@ struct pp_planner {
     RouteState route;
     TrafficState traffic;
     FollowState follow;
+    ManoeuvreState man;                                       // inside the per-scene traffic set (§4v): no feature bit
     EpisodeState episode;
     SpawnState spawn;
     TrafficResetState treset, wreset;                         // per scene (§4m), per world (§4t)
@@ -504,6 +516,35 @@ int follow_traffic(pp_planner* h, hipStream_t st, const SceneIn* d_in, ObPoint* 
     return PP_OK;
 }
 
+// Traffic with manoeuvres of one input set, in the place of move_traffic and follow_traffic while
+// pp_set_traffic_manoeuvres is in force.  step = 0 (an update, the set call) places every actor at its current (s, lat) and writes
+// no state; an advance reads the current (s, v, state) set, writes the other one and - once the launch is accepted - makes that the
+// current one.  d_in: the SceneIn records being staged (read by an advance only).
+int manoeuvre_traffic(pp_planner* h, hipStream_t st, const SceneIn* d_in, ObPoint* d_obs, ObMotion* d_mot, double step)
+{
+    const int n = h->traffic.actors, cur = h->traffic.cur, nxt = step != 0 ? cur ^ 1 : cur;
+    const ManoeuvreState& M = h->man;
+    if (h->follow.on)
+        hipLaunchKernelGGL(dmpp::k_manoeuvre_traffic<true>, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
+                           n, step, h->follow.tf, 0.5 * h->cfg.Vehicle_Width, h->traffic.d_pin, M.d_scene_of, M.d_scene_first, M.d_members, M.d_recs, M.d_rec_first,
+                           h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], h->follow.d_v[cur], M.d_state[cur],
+                           h->traffic.d_s[nxt], h->follow.d_v[nxt], M.d_state[nxt], d_in, h->rollout.d_flags, d_obs, d_mot);
+    else
+        hipLaunchKernelGGL(dmpp::k_manoeuvre_traffic<false>, dim3(traffic_wave_blocks(n)), dim3(dmpp::kBlock), 0, st,
+                           n, step, h->follow.tf, 0.5 * h->cfg.Vehicle_Width, h->traffic.d_pin, M.d_scene_of, M.d_scene_first, M.d_members, M.d_recs, M.d_rec_first,
+                           h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], nullptr, M.d_state[cur],
+                           h->traffic.d_s[nxt], nullptr, M.d_state[nxt], d_in, h->rollout.d_flags, d_obs, d_mot);
+    HIP_TRY(hipGetLastError());
+    h->traffic.cur = nxt;
+    return PP_OK;
+}
+// Whatever ends or replaces the per-scene traffic frees the manoeuvres with it ("Feature life cycle")
+void drop_manoeuvres(pp_planner* h)
+{
+    if (!h->man.on) return;
+    h->man = ManoeuvreState();
+}
+
 // Episode traffic reset of the input set an advance stages: behind the episode step, whose EpisodeStats.age and
 // EpisodeSpawnStats.cur_start it reads, and behind the traffic kernel of the advance, whose arrays - the current ones: with
 // following the pair follow_traffic has just flipped to - and pool entries it overwrites for the actors of restarted scenes.
@@ -522,6 +563,9 @@ void reset_traffic(pp_planner* h, bool world, hipStream_t st, ObPoint* d_obs, Ob
         hipLaunchKernelGGL(dmpp::k_reset_traffic, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
                            n, R.n_sets, h->traffic.d_pin, R.d_scene, h->episode.d_stats, sstats, R.d_starts[R.cur],
                            h->traffic.d_tracks, h->traffic.d_cum, h->traffic.d_pts, h->traffic.d_s[cur], v_arr, R.d_resets[R.cur], d_obs, d_mot);
+    if (!world && h->man.on)              // ... and their manoeuvres back to the state of the set call (§4v)
+        hipLaunchKernelGGL(dmpp::k_reset_manoeuvres, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, st,
+                           n, h->traffic.d_pin, h->man.d_scene_of, h->episode.d_stats, h->man.d_state[cur]);
 }
 
 // The advance kernel of the input set an advance stages, in the place of the copy of its SceneIn records: reads the
@@ -735,7 +779,7 @@ void switch_features(pp_planner* h, unsigned m, bool on)
     using namespace dmpp;
     if (m & kFleet) h->fleet.on = on;
     if (m & kRoute) h->route.on = on;
-    if (m & (h->traffic.world ? kWorldTraffic : kTraffic)) h->traffic.on = on;
+    if (m & (h->traffic.world ? kWorldTraffic : kTraffic)) { h->traffic.on = on; if (!on) drop_manoeuvres(h); }      // (§4v: the manoeuvres live inside the traffic set)
     if (m & kFollow) h->follow.on = on;
     if (m & kEpisodes) h->episode.on = on;
     if (m & kSpawn) h->spawn.on = on;
@@ -1762,7 +1806,8 @@ static int stage_inputs(pp_handle h, const StageSource& src)
         if (h->episode.on) step_episodes(h, su, P, d_in, src.trace);
     }
     if (h->traffic.on) {                  // an advance moves the actors one step on - by the car-following law while that is on (§4i) -, an update places them where they are
-        if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }
+        if (h->man.on) { int r = manoeuvre_traffic(h, su, d_in, d_obs, d_mot, advance ? src.ego->dt : 0.0); if (r) return r; }      // (§4v: in the place of either)
+        else if (advance && h->follow.on) { int r = follow_traffic(h, su, d_in, d_obs, d_mot, src.ego->dt); if (r) return r; }
         else move_traffic(h, su, d_obs, d_mot, advance ? src.ego->dt : 0.0);
     }
     if (advance && h->treset.on) reset_traffic(h, false, su, d_obs, d_mot);      // the actors of a scene that has just restarted go back to a start state (§4m)
@@ -2175,7 +2220,8 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     retire(h, world ? dmpp::kSetWorldTraffic : dmpp::kSetTraffic);      // (the start states of §4m were captured from the actors this call replaces)
     if ((rc = h->traffic.d_pin.reserve((size_t)n_actors)) || (rc = h->traffic.d_s[0].reserve((size_t)n_actors)) || (rc = h->traffic.d_tracks.reserve((size_t)n_tracks)) ||
         (rc = h->traffic.d_cum.reserve(cum.size())) || (rc = h->traffic.d_pts.reserve(pts.size())) ||
-        (world && (rc = h->traffic.d_world.reserve((size_t)n_actors)))) { h->traffic.on = false; return rc; }
+        (world && (rc = h->traffic.d_world.reserve((size_t)n_actors)))) { h->traffic.on = false; drop_manoeuvres(h); return rc; }
+    drop_manoeuvres(h);                                   // (a set that replaces world traffic retires no per-scene bit: §4v's list goes here)
     h->traffic.on = false;                                // (until everything below has landed: a device error leaves traffic off, never half a set)
     HIP_TRY(hipMemcpyAsync(h->traffic.d_pin, pin.data(), (size_t)n_actors * sizeof(dmpp::TrafficPin), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_s[0], s0.data(), (size_t)n_actors * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -2183,7 +2229,7 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     HIP_TRY(hipMemcpyAsync(h->traffic.d_cum, cum.data(), cum.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->traffic.d_pts, pts.data(), pts.size() * sizeof(GlobalPoint2D), hipMemcpyHostToDevice, h->stream));
     if (world) HIP_TRY(hipMemcpyAsync(h->traffic.d_world, scene_of.data(), (size_t)n_actors * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    h->traffic.actors = n_actors; h->traffic.end = (int)end_max; h->traffic.cur = 0; h->traffic.world = world;
+    h->traffic.actors = n_actors; h->traffic.end = (int)end_max; h->traffic.cur = 0; h->traffic.world = world; h->traffic.n_tracks = n_tracks;
     h->traffic.scene_of.swap(scene_of); h->traffic.track_of.swap(track_of);
     move_traffic(h, h->stream, h->cur_in().d_obs, h->cur_in().mot(), 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
     HIP_TRY(hipGetLastError());
@@ -2233,6 +2279,7 @@ int pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf)
     }
     PP_TRY(quiesce(h, true));                             // nobody reads the arrays
     if (!tf) {                                            // off: the arc lengths go back to the one array of §4h
+        if (h->man.on) { h->follow.on = false; return features_ok(h, "pp_set_traffic_follow"); }      // (§4v keeps both sets of s and its states: cur stays)
         if (h->follow.on && h->traffic.cur == 1) {
             HIP_TRY(hipMemcpyAsync(h->traffic.d_s[0], h->traffic.d_s[1], (size_t)h->traffic.actors * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2241,6 +2288,12 @@ int pp_set_traffic_follow(pp_handle h, const TrafficFollow* tf)
         return features_ok(h, "pp_set_traffic_follow");
     }
     PP_TRY(build_follow(h));                              // (a failed allocation or copy leaves the model that was set, or none)
+    if (h->man.on) {                                      // §4v: the states stay, v = v0 - the desired speed a manoeuvre may have changed
+        static_assert(offsetof(TrafficManoeuvreState, v0) == 16, "the desired speeds are copied out of the states at their stride");
+        HIP_TRY(hipMemcpy2DAsync(h->follow.d_v[h->traffic.cur], sizeof(double), &h->man.d_state[h->traffic.cur].get()->v0, sizeof(TrafficManoeuvreState), sizeof(double),
+                                 (size_t)h->traffic.actors, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
     h->follow.tf = *tf; h->follow.on = true;
     return features_ok(h, "pp_set_traffic_follow");
 }
@@ -2252,6 +2305,139 @@ int pp_get_traffic_speed(pp_handle h, double* v, int n)
     if (n < 0 || n > h->traffic.actors) return fail(PP_ERR_ARG, "n exceeds the actors");
     if (n == 0) return PP_OK;
     return fetch_behind_advance(h, v, h->follow.d_v[h->traffic.cur], (size_t)n * sizeof(double), true);
+}
+
+// Traffic manoeuvres.  The list is checked on the host, by the function any caller may use without a handle.
+static const char* manoeuvre_fault(int n_actors, int n_tracks, const TrafficManoeuvre& M, int prev_actor, int run)
+{
+    if (M.actor < 0 || M.actor >= n_actors) return "names an actor that the traffic does not have";
+    if (M.actor < prev_actor) return "is out of order (the records of an actor are contiguous, the actors non-decreasing)";
+    if (run >= DMPP_MANOEUVRE_MAX) return "is more than DMPP_MANOEUVRE_MAX records for one actor";
+    if (M.track < -1 || M.track >= n_tracks) return "names a track that was not given";
+    const int kind = M.trigger & 255, side = M.trigger >> 8;
+    if (M.trigger < 0 || kind > DMPP_TRIG_EGO_TIME) return "has an unknown trigger kind";
+    if (side > 2 || (side != 0 && kind == DMPP_TRIG_ADVANCES)) return "has an unknown side (sides 1 and 2 belong to the EGO kinds)";
+    if (kind == DMPP_TRIG_EGO_DIST && !(std::isfinite(M.dist) && M.dist >= 0)) return ": dist must be finite and >= 0";
+    if (kind == DMPP_TRIG_EGO_TIME && !(std::isfinite(M.time) && M.time >= 0)) return ": time must be finite and >= 0";
+    if (!std::isfinite(M.lat_end)) return "has a non-finite lat_end";
+    if (std::isinf(M.speed)) return "has an infinite speed (NaN keeps the speed)";
+    if (M.after < 0) return ": after must be >= 0";
+    if (M.n_steps < 1 || M.n_steps > 4096) return ": n_steps must be 1 .. 4096";
+    if (M._pad != 0) return ": _pad must be 0";
+    return nullptr;
+}
+static int check_manoeuvres(int n_actors, int n_tracks, int n, const TrafficManoeuvre* m, const char** why)
+{
+    int prev = 0, run = 0;
+    for (int i = 0; i < n; i++) {
+        if (i > 0 && m[i].actor != prev) run = 0;
+        if (const char* f = manoeuvre_fault(n_actors, n_tracks, m[i], i > 0 ? prev : 0, run)) { if (why) *why = f; return i; }
+        prev = m[i].actor; run++;
+    }
+    return -1;
+}
+int pp_check_traffic_manoeuvres(int n_actors, int n_tracks, int n, const TrafficManoeuvre* m)
+{
+    if (n == 0) return -1;
+    if (n < 0 || !m) return 0;                            // (no list to read: what pp_set_traffic_manoeuvres refuses is not legal here either)
+    return check_manoeuvres(n_actors, n_tracks, n, m, nullptr);
+}
+
+// The states of every actor as the set call makes them, from the pins and tracks the host keeps
+static std::vector<TrafficManoeuvreState> initial_manoeuvre_states(const pp_planner* h, const std::vector<dmpp::TrafficPin>& pin)
+{
+    std::vector<TrafficManoeuvreState> st(pin.size());
+    for (size_t a = 0; a < pin.size(); a++) { st[a] = TrafficManoeuvreState(); st[a].v0 = pin[a].speed; st[a].track = pin[a].track; }
+    return st;
+}
+
+int pp_set_traffic_manoeuvres(pp_handle h, int n, const TrafficManoeuvre* m)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    const std::string fn = "pp_set_traffic_manoeuvres";
+    if (n < 0 || (n > 0 && !m)) return fail(PP_ERR_ARG, fn + ": n records need the records");
+    PP_TRY(refuse_if_staged(h, fn, "the manoeuvres"));
+    if (!h->traffic.on) return fail(PP_ERR_STATE, fn + ": no traffic is set (pp_set_traffic comes first)");
+    if (h->traffic.world) return fail(PP_ERR_STATE, fn + ": world traffic is in force (manoeuvres belong to the actors of pp_set_traffic)");
+    if (h->treset.on) return fail(PP_ERR_STATE, fn + ": the episode traffic reset is on (the call comes before pp_set_episode_traffic)");
+    const size_t na = (size_t)h->traffic.actors;
+    const int n_tracks = (int)h->traffic.n_tracks;
+    const char* why = nullptr;
+    const int bad = check_manoeuvres((int)na, n_tracks, n, m, &why);
+    if (bad >= 0) return fail(PP_ERR_ARG, fn + ": record " + std::to_string(bad) + " " + why);
+    if (n == 0 && !h->man.on) return features_ok(h, fn.c_str());
+    PP_TRY(quiesce(h, true));                             // nobody reads or writes the arrays
+    const int cur = h->traffic.cur;
+    std::vector<dmpp::TrafficPin> pin(na);
+    HIP_TRY(hipMemcpy(pin.data(), h->traffic.d_pin, na * sizeof(dmpp::TrafficPin), hipMemcpyDeviceToHost));
+    std::vector<int32_t> track_now(h->traffic.track_of);
+    if (h->man.on) {
+        // a list in force ends first: every actor becomes a plain actor of the track it is on, at the speed it wants (the off form).
+        // Host copies only, up to here: the pins and track_of are written once the room below is there
+        std::vector<TrafficManoeuvreState> was(na);
+        HIP_TRY(hipMemcpy(was.data(), h->man.d_state[cur], na * sizeof(TrafficManoeuvreState), hipMemcpyDeviceToHost));
+        for (size_t a = 0; a < na; a++) { pin[a].track = was[a].track; pin[a].speed = was[a].v0; track_now[a] = was[a].track; }
+    }
+    auto plain_actors = [&]() -> int {                    // the off form's write: nothing can be refused behind it
+        if (!h->man.on) return PP_OK;
+        h->traffic.track_of = track_now;
+        HIP_TRY(hipMemcpy(h->traffic.d_pin, pin.data(), na * sizeof(dmpp::TrafficPin), hipMemcpyHostToDevice));
+        return PP_OK;
+    };
+    if (n == 0) {
+        PP_TRY(plain_actors());
+        if (h->follow.on) {                               // the groups of the tracks the actors are on now; v stays
+            std::vector<double> v(na);
+            HIP_TRY(hipMemcpy(v.data(), h->follow.d_v[cur], na * sizeof(double), hipMemcpyDeviceToHost));
+            PP_TRY(build_follow(h));
+            HIP_TRY(hipMemcpy(h->follow.d_v[cur], v.data(), na * sizeof(double), hipMemcpyHostToDevice));
+        } else if (cur == 1) {                            // the arc lengths go back to the one array of §4h
+            HIP_TRY(hipMemcpy(h->traffic.d_s[0], h->traffic.d_s[1], na * sizeof(double), hipMemcpyDeviceToDevice));
+            h->traffic.cur = 0;
+        }
+        drop_manoeuvres(h);
+        return features_ok(h, fn.c_str());
+    }
+    // the tables: every actor's run of records, every actor's scene, the actors by (scene, index)
+    std::vector<int32_t> rec_first(na + 1, 0), members(na), scene_first((size_t)h->n_scenes + 1, 0);
+    for (int i = 0; i < n; i++) rec_first[(size_t)m[i].actor + 1]++;
+    for (size_t a = 0; a < na; a++) rec_first[a + 1] += rec_first[a];
+    const std::vector<int32_t>& sc = h->traffic.scene_of;
+    for (size_t a = 0; a < na; a++) scene_first[(size_t)sc[a] + 1]++;
+    for (size_t c = 0; c < (size_t)h->n_scenes; c++) scene_first[c + 1] += scene_first[c];
+    { std::vector<int32_t> at(scene_first.begin(), scene_first.end() - 1); for (size_t a = 0; a < na; a++) members[(size_t)at[(size_t)sc[a]]++] = (int32_t)a; }
+    const std::vector<TrafficManoeuvreState> st = initial_manoeuvre_states(h, pin);
+    ManoeuvreState& M = h->man;
+    int rc;
+    if ((rc = M.d_recs.reserve((size_t)n)) || (rc = M.d_rec_first.reserve(na + 1)) || (rc = M.d_scene_of.reserve(na)) || (rc = M.d_scene_first.reserve(scene_first.size())) ||
+        (rc = M.d_members.reserve(na)) || (rc = M.d_state[0].reserve(na)) || (rc = M.d_state[1].reserve(na))) { if (!M.on) M = ManoeuvreState(); return rc; }
+    if (!h->traffic.d_s[1] || h->traffic.d_s[1].capacity() < na) {      // the second array of arc lengths (following has it already)
+        if (cur == 1) return fail(PP_ERR_STATE, fn + ": internal: the current arc lengths are in an array that does not exist");
+        if ((rc = h->traffic.d_s[1].reserve(na))) { if (!M.on) M = ManoeuvreState(); return rc; }
+    }
+    PP_TRY(plain_actors());                               // room first (above), then the writes
+    HIP_TRY(hipMemcpy(M.d_recs, m, (size_t)n * sizeof(TrafficManoeuvre), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(M.d_rec_first, rec_first.data(), rec_first.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(M.d_scene_of, sc.data(), na * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(M.d_scene_first, scene_first.data(), scene_first.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(M.d_members, members.data(), na * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(M.d_state[cur], st.data(), na * sizeof(TrafficManoeuvreState), hipMemcpyHostToDevice));
+    const bool was_on = M.on;
+    M.on = true;
+    if (was_on) {                                         // the offsets of the list that ended are dropped: the resident set carries the plain poses
+        PP_TRY(manoeuvre_traffic(h, h->stream, h->cur_in().d_in, h->cur_in().d_obs, h->cur_in().mot(), 0.0));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return features_ok(h, fn.c_str());
+}
+
+int pp_get_traffic_manoeuvre_state(pp_handle h, TrafficManoeuvreState* out, int n_actors)
+{
+    if (!h || (!out && n_actors > 0)) return fail(PP_ERR_ARG, "null argument");
+    if (!h->traffic.on || !h->man.on) return fail(PP_ERR_STATE, "pp_get_traffic_manoeuvre_state: no manoeuvres are set");
+    if (n_actors < 0 || n_actors > h->traffic.actors) return fail(PP_ERR_ARG, "n_actors exceeds the actors");
+    if (n_actors == 0) return PP_OK;
+    return fetch_behind_advance(h, out, h->man.d_state[h->traffic.cur], (size_t)n_actors * sizeof(TrafficManoeuvreState), true);      // waits as pp_get_traffic_state does
 }
 
 // Route following.  Everything is checked on the host before anything changes; the resident records are not touched.
@@ -2490,6 +2676,17 @@ static int set_traffic_reset(pp_handle h, bool world, int n_sets, const TrafficS
         if (!std::isfinite(starts[i].v) || starts[i].v < 0) return fail(PP_ERR_ARG, fn + ": start state " + std::to_string(i) + ": v must be finite and >= 0");
     }
     PP_TRY(quiesce(h, false));                            // (the upload stream, which writes s / v, is behind the last advance)
+    if (!world && h->man.on) {                            // §4v: set 0 is an arc length on the INITIAL track, so every actor must still have the set call's state
+        std::vector<dmpp::TrafficPin> pin(n); std::vector<TrafficManoeuvreState> st(n);
+        HIP_TRY(hipMemcpyAsync(pin.data(), h->traffic.d_pin, n * sizeof(dmpp::TrafficPin), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(st.data(), h->man.d_state[h->traffic.cur], n * sizeof(TrafficManoeuvreState), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        const std::vector<TrafficManoeuvreState> want = initial_manoeuvre_states(h, pin);
+        for (size_t a = 0; a < n; a++) {
+            if (std::memcmp(&want[a], &st[a], sizeof st[a]) != 0)
+                return fail(PP_ERR_STATE, fn + ": actor " + std::to_string(a) + " has left the state pp_set_traffic_manoeuvres gave it (set the manoeuvres again, then the reset)");
+        }
+    }
     const int o = R.ever ? 1 - R.cur : R.cur;
     if (!world) PP_TRY(R.d_scene.reserve(n));
     PP_TRY(R.d_starts[o].reserve((size_t)n_sets * n)); PP_TRY(R.d_resets[o].reserve(n));      // room first: a failed allocation changes nothing
@@ -3092,6 +3289,7 @@ size_t pp_sizeof(int which)
     case 40: return sizeof(EgoTracker); case 41: return sizeof(EgoTrackState);
     case 43: return sizeof(PackedPlan); case 44: return sizeof(PackedGrid);      // (42 stays unassigned)
     case 45: return sizeof(ConflictModel); case 46: return sizeof(ConflictScore);
+    case 47: return sizeof(TrafficManoeuvre); case 48: return sizeof(TrafficManoeuvreState);
     default: return 0;
     }
 }

@@ -98,15 +98,19 @@ __device__ __forceinline__ void world_store(ObPoint* __restrict__ obs, ObMotion*
 }
 
 // §4i 1. the actor ahead: the smallest (g, b) over the members of `group`, the same in every lane; i < 0: none
+// kOnTrack (§4v, manoeuvres): the group is the actor's whole SCENE and a member counts only while its current track, st[b].track, is `track`
 struct TrafficAhead { double g; int i; };
 
+template <bool kOnTrack = false>
 __device__ __forceinline__ TrafficAhead follow_actor_ahead(const TrackView& t, int group, int a, double s, double look, const int32_t* __restrict__ group_first,
-                                                           const int32_t* __restrict__ members, const double* __restrict__ s_in, int lane)
+                                                           const int32_t* __restrict__ members, const double* __restrict__ s_in, int lane,
+                                                           const TrafficManoeuvreState* __restrict__ st = nullptr, int track = 0)
 {
     double bg = 0; int bi = -1;
     for (int m = group_first[group] + lane, m1 = group_first[group + 1]; m < m1; m += 64) {
         const int b = members[m];
         if (b == a) continue;
+        if (kOnTrack) { if (st[b].track != track) continue; }
         double g = s_in[b] - s;
         bool ok = true;
         if (t.closed) { if (g < 0 || (g == 0 && b > a)) g = g + t.L; }

@@ -18,6 +18,8 @@
 // With --route --traffic --react the vehicle starts 15 m BEHIND its ego at a desired 8 m/s instead and the car-following law is on
 // (pp_set_traffic_follow with the default model): it closes up, finds the ego as its leader and keeps a gap; the host
 // prints the smallest ego-actor clearance of the run and the vehicles' mean speed at the end.
+// With --route --traffic [--react] --cut-in every vehicle starts 9 m ahead on the NEIGHBOURING lane and carries one manoeuvre (pp_set_traffic_manoeuvres,
+// DESIGN.md §4v): when its ego is within 12 m behind it, it changes onto the ego's lane in 20 advances - the planner sees it arrive and brakes.
 // With --route --fleet --traffic --shared (and --react for following) the 64 egos form 8 worlds of 8 - each world a platoon on one lane,
 // 12 m apart, 4 peer slots per scene - and there is ONE vehicle per world in the place of one per scene (pp_set_world_traffic,
 // DESIGN.md §4j): it is written into slot 0 of all 8 member scenes and follows the nearest of the world's 8 egos.
@@ -154,6 +156,10 @@ static int print_tracker(pp_handle h, int n)
 // --route: a ring of four left-hand arcs of 70 degrees (two lanes, 260 points, lane 2 at 0.5 m) joined by junction arcs of 20
 // degrees (40-point polylines), 64 obstacle-free egos with routes of 3 .. 6 legs, 1200 ticks with the grid stage off - or, with
 // follow, on: 256 x 256 cells that follow the ego.
+// --cut-in (with --route --traffic [--react]): every vehicle starts 9 m ahead of its ego on the NEIGHBOURING lane's track at the
+// planner's cruising speed and carries one manoeuvre: once the ego is within 12 m behind it, onto the ego's lane in 20 advances
+static bool g_cut_in = false;
+
 static int run_route(bool follow, bool traffic, bool react, bool shared, bool episodes, int starts, bool contact, bool reset, int log_cap, int trace_depth, int trace_post, int sched, bool worlds, const ConflictArg& conflict)
 {
     const bool spawn = starts > 0 || contact; const int M = starts > 0 ? starts : 1;
@@ -246,7 +252,11 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
                 if (!react && s % W == W - 1) actors.push_back(TrafficActor{ here + 20.0, 1.5, s / W, 0, lane - 1, 1, 0.9f, 0 });
                 continue;
             }
-            if (react) actors.push_back(TrafficActor{ here - 15.0, 8.0, s, 0, lane - 1, 1, 0.9f, 0 });      // (a closed track: a negative s0 wraps)
+            if (g_cut_in) {
+                const int other = lane == 1 ? 2 : 1;
+                actors.push_back(TrafficActor{ arc_of(other, e.loc.road_num, e.loc.id[lane - 1]) + 9.0, 10.0 / 3.6, s, 0, other - 1, 1, 0.9f, 0 });
+            }
+            else if (react) actors.push_back(TrafficActor{ here - 15.0, 8.0, s, 0, lane - 1, 1, 0.9f, 0 });      // (a closed track: a negative s0 wraps)
             else actors.push_back(TrafficActor{ here + 20.0, contact ? -3.0 : 1.5, s, 0, lane - 1, 1, 0.9f, 0 });
         }
     }
@@ -269,6 +279,12 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
         } else
         CHECK(pp_set_traffic(h, (int)tracks.size(), tracks.data(), tpts.data(), (int)tpts.size(), n, actors.data()));
         if (react) { TrafficFollow tf; pp_default_traffic_follow(&tf); CHECK(pp_set_traffic_follow(h, &tf)); }
+        if (g_cut_in) {                                   // one record per vehicle: EGO_DIST, the ego behind it (side 1), onto the ego's lane, no offset at the end
+            std::vector<TrafficManoeuvre> mv;
+            for (int s = 0; s < n; s++) mv.push_back(TrafficManoeuvre{ 12.0, 0.0, 0.0, NAN, s, DMPP_TRIG_EGO_DIST | 1 << 8, 0, in[(size_t)s].loc.lane_num - 1, 20, 0 });
+            if (pp_check_traffic_manoeuvres(n, (int)tracks.size(), n, mv.data()) != -1) { std::fprintf(stderr, "the cut-in list is not legal\n"); return 2; }
+            CHECK(pp_set_traffic_manoeuvres(h, n, mv.data()));
+        }
         CHECK(pp_score_begin(h, model.dt));
     }
     if ((log_cap || trace_depth || conflict.on) && !traffic) CHECK(pp_score_begin(h, model.dt));      // (the records carry their episode's scorecard; the trace and the conflict score see scored ticks)
@@ -417,7 +433,13 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
             saw += r.n_ob_flag > 0; hit += r.n_collision_ticks > 0; dist += r.dist; if (r.min_clearance < worst) worst = r.min_clearance;
         }
         for (int a = 0; a < nv; a++) driven += arc[(size_t)a];
-        if (react) {
+        if (g_cut_in) {
+            std::vector<TrafficManoeuvreState> ms((size_t)nv); int done = 0, home = 0;
+            CHECK(pp_get_traffic_manoeuvre_state(h, ms.data(), nv));
+            for (int a = 0; a < nv; a++) { done += ms[(size_t)a].n_done; home += ms[(size_t)a].track == in[(size_t)a].loc.lane_num - 1 && ms[(size_t)a].lat == 0; }
+            std::printf("cut-in: %d vehicles 9 m ahead on the neighbouring lane at %.2f m/s%s: %d moves finished, %d vehicles on their ego's lane with no offset; %d of %d egos saw "
+                        "theirs (ob_flag), %d touched it, worst clearance %.2f m, mean distance travelled %.1f m\n", nv, actors[0].speed, react ? ", following on" : "", done, home, saw, n, hit, worst, dist / n);
+        } else if (react) {
             std::vector<double> v((size_t)nv); double vsum = 0;
             CHECK(pp_get_traffic_speed(h, v.data(), nv));
             for (int a = 0; a < nv; a++) vsum += v[(size_t)a];
@@ -463,6 +485,7 @@ int main(int argc, char** argv)
         }
         else if (std::strcmp(argv[a], "--traffic") == 0) traffic = true;
         else if (std::strcmp(argv[a], "--react") == 0) react = true;
+        else if (std::strcmp(argv[a], "--cut-in") == 0) g_cut_in = true;
         else if (std::strcmp(argv[a], "--shared") == 0) shared = true;
         else if (std::strcmp(argv[a], "--episodes") == 0) episodes = true;
         else if (std::strcmp(argv[a], "--contact") == 0) contact = true;
@@ -480,9 +503,10 @@ int main(int argc, char** argv)
             conflict.on = true;
             if (a + 1 < argc && argv[a + 1][0] != '-' && std::sscanf(argv[++a], "%lf,%lf", &conflict.warn, &conflict.crit) < 1) conflict.warn = -1;
         }
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] | --fleet --traffic --shared [--react] [--episodes [--starts M] --contact --worlds [--reset-traffic]]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]] [--conflict [WARN[,CRIT]]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] [--cut-in] | --fleet --traffic --shared [--react] [--episodes [--starts M] --contact --worlds [--reset-traffic]]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]] [--conflict [WARN[,CRIT]]]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
+    if (g_cut_in && !(route && traffic && !shared && !contact)) { std::fprintf(stderr, "--cut-in scripts the per-scene traffic: use it with --route --traffic [--react]\n"); return 2; }
     if (react && !traffic) { std::fprintf(stderr, "--react makes the traffic follow: use it with --traffic\n"); return 2; }
     if (shared && !(route && fleet && traffic)) { std::fprintf(stderr, "--shared puts one vehicle into every world: use it with --route --fleet --traffic\n"); return 2; }
     if (episodes && !route) { std::fprintf(stderr, "--episodes restarts egos that arrive: use it with --route\n"); return 2; }

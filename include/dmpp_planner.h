@@ -560,6 +560,35 @@ int  pp_episode_schedule_weights(const EpisodeSchedule* m, const EpisodeSchedule
 int  pp_set_episode_traffic(pp_handle h, int n_sets, const TrafficStart* starts);
 int  pp_get_episode_traffic_resets(pp_handle h, int32_t* n_resets, int n);
 
+/* ---- traffic manoeuvres: triggered lane changes, lateral offsets and speed changes -----------------------------
+ * An actor of pp_set_traffic drives one track for its whole life.  pp_set_traffic_manoeuvres gives actors a list of MOVES, each
+ * started by a trigger - the actor's own clock (advances), or the ego of its scene coming within `dist` metres or within `time`
+ * seconds at the ego's own speed, optionally only from behind or from ahead - and made of: a new desired / scripted speed, a
+ * change onto another track (the pose is projected onto it and the actor belongs to it AT ONCE: a cut-in is a cut-in for the
+ * followers behind) and a lateral offset that runs from where the actor is to `lat_end` in n_steps advances along a smoothstep.
+ * The records of one actor are contiguous, the actors non-decreasing; an actor's records run one after the other.  While a list
+ * is in force k_manoeuvre_traffic takes the place of k_move_traffic / k_follow_traffic on every staged set; every step is specified
+ * to the last bit (§4v; tests/traffic_manoeuvre_model.py).  pp_update_async places the actors at their current (s, offset): no step,
+ * no trigger, no clock.  pp_set_traffic_follow leaves the states alone and sets v = v0.  While pp_set_episode_traffic is on as well
+ * the actors of a restarted scene go back to the state of this call (n_done is kept).
+ * The list lives inside the traffic set: it has no feature bit; every successful pp_set_traffic (no actors included),
+ * pp_set_world_traffic and whatever gives the handle new resident scenes frees it.  n = 0: off - every actor becomes a plain actor
+ * of the track it is on at the speed it wants, the offset is dropped at the next staged set.  A call while a list is in force
+ * ends that list the same way first and places the actors without their offsets into the resident set.
+ * Refused with nothing changed - PP_ERR_STATE: no per-scene traffic, world traffic, an update staged, the episode traffic reset on
+ * (this call comes BEFORE pp_set_episode_traffic, which - while a list is in force - is refused unless every actor still has the
+ * state this call gave it); PP_ERR_ARG: whatever pp_check_traffic_manoeuvres refuses.  One host wait.  A handle that never makes
+ * the call allocates and launches none of this.
+ * pp_get_traffic_manoeuvre_state: the states of actors 0 .. n_actors - 1; waits as pp_get_traffic_state does; PP_ERR_STATE while no
+ * list is in force.
+ * pp_check_traffic_manoeuvres: pure host, no handle, no device: -1 when the list is legal for n_actors actors and n_tracks tracks
+ * (n = 0 is), else the index of the first record that is not (0 for n < 0 or a NULL list with n > 0) - an actor or track out of range, records out of order or more than
+ * DMPP_MANOEUVRE_MAX for one actor, an unknown kind or side (sides belong to the EGO kinds), a dist / time that is not finite or
+ * is negative for its kind, a non-finite lat_end, an infinite speed, after < 0, n_steps outside 1 .. 4096, _pad != 0. */
+int  pp_set_traffic_manoeuvres(pp_handle h, int n, const TrafficManoeuvre* m);   /* n = 0: off */
+int  pp_get_traffic_manoeuvre_state(pp_handle h, TrafficManoeuvreState* out, int n_actors);
+int  pp_check_traffic_manoeuvres(int n_actors, int n_tracks, int n, const TrafficManoeuvre* m);
+
 /* ---- world episodes: the egos of a world restart together ----------------------------------------------------------
  * With the spawn model alone every scene ends and restarts on its own: on a fleet (pp_set_fleet) the partner of an ended ego drives on
  * through the next "episode".  pp_set_episode_worlds(h, 1) makes the WORLD the unit of an episode: from then on every pp_advance_async
@@ -701,7 +730,8 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 25 GridFollow, 26 TrafficTrack, 27 TrafficActor, 28 TrafficFollow, 29 EpisodeModel, 30 EpisodeStats,
  * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord, 35 ScoreTraceModel, 36 ScoreTick,
  * 37 ScoreTraceInfo, 38 EpisodeSchedule, 39 EpisodeScheduleRow, 40 EgoTracker, 41 EgoTrackState,
- * (42 unassigned) 43 PackedPlan, 44 PackedGrid, 45 ConflictModel, 46 ConflictScore */
+ * (42 unassigned) 43 PackedPlan, 44 PackedGrid, 45 ConflictModel, 46 ConflictScore, 47 TrafficManoeuvre,
+ * 48 TrafficManoeuvreState */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

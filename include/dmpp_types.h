@@ -454,6 +454,33 @@ typedef struct TrafficStart {
     double s, v;                /* arc length (m, wrapped / clamped onto the actor's track); speed (m/s, finite, >= 0) */
 } TrafficStart;                                                             /* 16 B */
 
+/* ---- traffic manoeuvres (build-defined), on top of pp_set_traffic ------------------------------------------
+ * pp_set_traffic_manoeuvres gives actors of the per-scene traffic a list of triggered moves: a lateral offset from the track, a
+ * change onto another track (cut-in, cut-out) and a change of the desired / scripted speed, started by the actor's own clock or
+ * by the ego of its scene coming within a distance or a time.  The records of one actor are contiguous, in non-decreasing `actor`
+ * order, and run one after the other in list order. */
+#define DMPP_MANOEUVRE_MAX 8          /* records per actor */
+#define DMPP_TRIG_ADVANCES 0          /* the actor's clock alone */
+#define DMPP_TRIG_EGO_DIST 1          /* ego of the actor's scene within `dist` metres of the actor */
+#define DMPP_TRIG_EGO_TIME 2          /* ... within `time` seconds at the ego's own speed */
+typedef struct TrafficManoeuvre {
+    double  dist, time;         /* m, s: finite and >= 0 for the kind that reads them */
+    double  lat_end;            /* m, left of the direction of travel positive: offset from the (target) track when the move ends */
+    double  speed;              /* m/s: the actor's desired / scripted speed from the trigger on; NaN: keep */
+    int32_t actor;
+    int32_t trigger;            /* kind | side << 8; side 0 any, 1 ego behind the actor, 2 ego ahead (EGO kinds only) */
+    int32_t after;              /* >= 0: advances on the actor's clock before the trigger is looked at at all */
+    int32_t track;              /* target track, or -1: stay on the current one */
+    int32_t n_steps;            /* 1 .. 4096: advances the lateral move takes */
+    int32_t _pad;               /* 0 */
+} TrafficManoeuvre;                                                         /* 56 B */
+typedef struct TrafficManoeuvreState {
+    double  lat, lat0, v0;      /* current offset; offset at the trigger; current desired speed */
+    int32_t track, next;        /* current track; index of the actor's next record within its own run */
+    int32_t k, clock;           /* steps of the running move done (0: idle); advances since the clock was started */
+    int32_t n_done, _pad;       /* moves finished since the set call */
+} TrafficManoeuvreState;                                                    /* 48 B */
+
 /* ---- episode log (build-defined), on top of pp_set_episodes ------------------------------------------
  * pp_set_episode_log makes every advance append one record per episode it ended to a ring on the device - in the order of the
  * scene indices, whatever the scheduling - which the host drains whenever it likes (pp_read_episode_log).  No heading: it is

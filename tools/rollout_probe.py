@@ -17,6 +17,9 @@ generated scenes (k_advance_egos), both with following on / both with it off, an
 TRAFFIC=A: every run has a rollout leg with lane traffic on (pp_set_traffic: A actors per scene, default 8 for TRAFFIC=1, in the first
 A of the scene's own obstacle entries, driving the scene's current lane as an open track at 1 .. 8 m/s) and one with it off: the same
 scenes after the same pp_set_traffic, switched off again, so both legs start from the same pool with the same obs_n - alternating.
+MANOEUVRE=1 (with TRAFFIC, and REACT for following): traffic (and following) stay on in both legs; the leg "on" also has a manoeuvre list
+(pp_set_traffic_manoeuvres, DESIGN.md §4v: k_manoeuvre_traffic in the place of k_move_traffic / k_follow_traffic) - every actor swings
+1 m to the left and back, eight records of 10 advances, the first when the ego is within 60 m.
 EPISODES=1: every run has a rollout leg of routed ring egos with ONE-leg routes and episodes on (pp_set_episodes, default model:
 k_respawn_egos behind k_advance_route, arrived egos restart) and one with them off on the same scenes (arrived egos freeze),
 alternating; with ONE_ROLLOUT one more leg with episodes on alone, for rocprofv3 --kernel-trace --stats.
@@ -123,6 +126,7 @@ TRAFFIC = int(os.environ.get("TRAFFIC", "0"))
 if TRAFFIC == 1:
     TRAFFIC = 8
 REACT = os.environ.get("REACT", "0") == "1"
+MANOEUVRE = os.environ.get("MANOEUVRE", "0") == "1"          # with TRAFFIC (and REACT): traffic (and following) stay on in both legs; "on" = a manoeuvre list too
 
 
 def traffic_run(on):
@@ -136,7 +140,16 @@ def traffic_run(on):
     actors["scene"], actors["slot"], actors["track"] = k // TRAFFIC, k % TRAFFIC, k // TRAFFIC
     actors["s0"], actors["speed"], actors["type"], actors["radius"] = 10.0 + 12.0 * (k % TRAFFIC), 1.0 + (k % 8), 1, 0.9
     pl.set_traffic(tracks, pts, actors)
-    if REACT:                         # REACT=1: traffic stays on in both legs; "on" = the car-following law too
+    if MANOEUVRE:                     # every actor swings 1 m to the left and back, over and over: eight records of 10 advances each, the first when the ego is within 60 m
+        if REACT:
+            pl.set_traffic_follow(dm.default_traffic_follow())
+        if on:
+            recs = np.zeros((n * TRAFFIC, dm.MANOEUVRE_MAX), dm.TrafficManoeuvre)
+            recs["actor"], recs["track"], recs["n_steps"], recs["speed"] = k[:, None], -1, 10, np.nan
+            recs["lat_end"] = np.where(np.arange(dm.MANOEUVRE_MAX) % 2 == 0, 1.0, 0.0)[None, :]
+            recs["trigger"][:, 0], recs["dist"][:, 0] = dm.TRIG_EGO_DIST, 60.0
+            pl.set_traffic_manoeuvres(recs.reshape(-1))
+    elif REACT:                       # REACT=1: traffic stays on in both legs; "on" = the car-following law too
         if on:
             pl.set_traffic_follow(dm.default_traffic_follow())
     elif not on:
@@ -458,7 +471,8 @@ if TRAFFIC > 0:
         print("run %d  %d scenes, obs_n %d  traffic off %.3f M ticks/s (%d frozen at the end)   traffic on (%d actors per scene) %.3f M ticks/s (%d frozen)" %
               (r, n, n_obs, a / 1e6, fa, TRAFFIC, b / 1e6, fb), flush=True)
     print("median  %d scenes  %s off %.3f M ticks/s (spread %.3f)   %s on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
-          (n, "following (traffic on)" if REACT else "traffic", statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, "following" if REACT else "traffic", statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+          (n, ("manoeuvres (traffic%s on)" % (" and following" if REACT else "")) if MANOEUVRE else "following (traffic on)" if REACT else "traffic", statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6,
+           "manoeuvres" if MANOEUVRE else "following" if REACT else "traffic", statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
            statistics.median(on) / statistics.median(off)), flush=True)
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: one more rollout with traffic alone
         traffic_run(True)
