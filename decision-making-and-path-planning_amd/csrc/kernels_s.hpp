@@ -104,6 +104,30 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// inclusive prefix sum over the 64 lanes, by the same six DPP steps (a lane without a source adds 0): lane 63 holds the total
+__device__ __forceinline__ int wave_scan_i32(int v)
+{
+#define DMPP_DPP_ADD(ctrl, rowmask) v += __builtin_amdgcn_update_dpp(0, v, ctrl, rowmask, 0xf, false);
+    DMPP_DPP_ADD(0x111, 0xf) DMPP_DPP_ADD(0x112, 0xf) DMPP_DPP_ADD(0x114, 0xf) DMPP_DPP_ADD(0x118, 0xf)
+    DMPP_DPP_ADD(0x142, 0xa) DMPP_DPP_ADD(0x143, 0xc)
+#undef DMPP_DPP_ADD
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_scan_i32(v), 63); }
+// sum of a 64-bit word over the 64 lanes (mod 2^64), returned in every lane: both halves travel by DPP, the add carries
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v)
+{
+#define DMPP_DPP_ADD64(ctrl, rowmask)                                                                             \
+    { const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, ctrl, rowmask, 0xf, false);      \
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), ctrl, rowmask, 0xf, false); \
+      v += ((uint64_t)hi << 32) | lo; }
+    DMPP_DPP_ADD64(0x111, 0xf) DMPP_DPP_ADD64(0x112, 0xf) DMPP_DPP_ADD64(0x114, 0xf) DMPP_DPP_ADD64(0x118, 0xf)
+    DMPP_DPP_ADD64(0x142, 0xa) DMPP_DPP_ADD64(0x143, 0xc)
+#undef DMPP_DPP_ADD64
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 __device__ __forceinline__ int popc_m(uint32_t v) { return __popc(v); }
 __device__ __forceinline__ int popc_m(uint64_t v) { return __popcll(v); }
 __device__ __forceinline__ int lsb_m(uint32_t v) { return __ffs((int)v) - 1; }
@@ -974,6 +998,7 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
 #ifdef DMPP_DEBUG_SEARCH
 #define DBG_MARK(slot) { const long long t__ = clock64(); dbg_t[slot] += t__ - dbg_last; dbg_last = t__; }
     long long dbg_last = clock64();
+    int hops_dbg = 0;                                    // hops of the path walk in LDS (0: another walk, or no path)
 #else
 #define DBG_MARK(slot)
 #endif
@@ -989,6 +1014,7 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
     int my_pushes = 0;                                   // per lane (a counter nobody reads inside the loop need not be a scalar register)
     uint64_t digest = 0;
     bool hash_complete = true;                 // every closed cell is in the LDS hash (with its direction and run)
+    uint32_t goal_slot = 0;                    // (FOUND, hash_complete) the goal's slot in it
     int n_open = 1, live = 1, fmax = -1;
     // lane = node * 8 + s: the eight directions of each of the (<= 4) nodes of a step
     const int s = lane & 7;
@@ -1161,7 +1187,14 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
         }
         if (vm && f > fmax) { fmax = f; n_rounds++; }
         n_exp += __popc(vm);
-        if (__builtin_expect(wave_ballot(valid && cell == goal) != 0, 0)) { status = DMPP_G_FOUND; path_cost = f; break; }
+        {
+            const unsigned long long at_goal = wave_ballot(valid && cell == goal);
+            if (__builtin_expect(at_goal != 0, 0)) {
+                status = DMPP_G_FOUND; path_cost = f;
+                goal_slot = (uint32_t)__builtin_amdgcn_readlane((int)my_slot, __ffsll((long long)at_goal) - 1);      // where the path walk begins
+                break;
+            }
+        }
         if (__builtin_expect(n_exp >= c.max_expansions, 0)) { status = DMPP_G_LIMIT; break; }
         if (__builtin_expect(vm == 0, 0)) continue;
         DBG_MARK(1)
@@ -1290,47 +1323,99 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
     }
     DBG_MARK(5)
 
-    // ---- the digest (from the hash unless the scene spilled), reduced over the wave; then the path from the runs ----
-    if (hash_complete) digest += hash_digest(L, lane);
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) {
-        uint32_t lo = (uint32_t)digest, hi = (uint32_t)(digest >> 32);
-        lo = __shfl_xor((int)lo, sft, 64); hi = __shfl_xor((int)hi, sft, 64);
-        digest += ((uint64_t)hi << 32) | lo;
-    }
+    // ---- the tail: one pass over the hash gives the digest and, for a found path, every closed cell's PARENT SLOT; lane 0 then
+    //      follows slot numbers from the goal's slot to the start's (one LDS read per hop), and the hops are expanded to cells by
+    //      one lane each.  Nothing reads the open list any more: the parent slots lie over o_ent, the hop list over o_f2. ----
     int path_len = 0;
     bool slow_walk = !hash_complete;           // the HBM copy of direction | run answers instead of the LDS hash
-    if (status == DMPP_G_FOUND && hash_complete) {
-        // Walk the runs back from the goal: lane 0 looks each closed cell up in the LDS hash (direction and run sit in
-        // the same slot) and lists the hops in the LDS arrays of the dead open list.  The length is then known before
-        // a cell is written, so every cell goes straight to its final place, path[keep-1-k] for the k-th cell counted
-        // from the goal: one lane per hop, offsets from a wave prefix sum of the run lengths.
-        int Lc = 1, hops = 0, bad = 0;         // bad: 1 = inconsistent closed set, 2 = more hops than the LDS list holds
-        if (lane == 0) {
-            int cur = goal;
-            while (cur != start) {
-                if (hops >= kOpenCap) { bad = 2; break; }
-                uint32_t hh = ((uint32_t)cur * 2654435761u) >> (32 - kClosedLog);
-                int v = -1;
-                for (int probe = 0; probe < kClosedTab; probe++) {
-                    const uint32_t e2 = L.c_tab[hh]; const int inf = L.c_info[hh];
-                    if (CW::key(e2) == (uint32_t)cur + 1u) { v = inf; break; }
-                    if (e2 == 0u) break;
-                    hh = (hh + 1) & (kClosedTab - 1);
-                }
-                const int pd = v & 15, rn = v >> 4;
-                if (v < 0 || rn == 0 || pd > 7) { bad = 1; break; }
+    // a parent slot that is no slot number: the parent is the start (the chain ends) | the slot's own direction | run names no parent
+    // (an inconsistent entry) | the parent cell is not in the hash
+    constexpr uint32_t kParStart = 0xFFFDu, kParInvalid = 0xFFFEu, kParMissing = 0xFFFFu;
+    typedef uint16_t __attribute__((may_alias)) u16_alias;
+    u16_alias* const par = reinterpret_cast<u16_alias*>(L.o_ent);       // [kClosedTab] parent slots
+    u16_alias* const occ = reinterpret_cast<u16_alias*>(L.o_f2);        // [<= kClosedTab] the occupied slots, over o_f2 | o_run; the hop list follows it in o_f2
+    static_assert(kClosedTab < (int)kParStart && sizeof(L.o_ent) >= kClosedTab * sizeof(uint16_t) && sizeof(L.o_f2) >= kOpenCap * sizeof(uint16_t) &&
+                  offsetof(LDS, o_run) == offsetof(LDS, o_f2) + sizeof(L.o_f2) && sizeof(L.o_f2) + sizeof(L.o_run) >= kClosedTab * sizeof(uint16_t),
+                  "parent slots over o_ent, occupied slots over o_f2 | o_run, the hop list over o_f2");
+    const bool chain = status == DMPP_G_FOUND && hash_complete;
+    // the start was the first cell inserted, into an empty table: it lies in its home slot
+    const uint32_t start_slot = ((uint32_t)start * 2654435761u) >> (32 - kClosedLog);
+    if (hash_complete) {
+        // (1) the occupied slots, squeezed into a list: the work below then takes one round per 64 closed cells, not one per 64 slots
+        int n_occ = 0;
+        {
+            constexpr int NS = kClosedTab / DMPP_WAVE;
+            uint32_t E[NS];
+#pragma unroll
+            for (int k = 0; k < NS; k++) E[k] = L.c_tab[lane + k * DMPP_WAVE];
+            wave_order();                                       // the open list is dead from here
+#pragma unroll
+            for (int k = 0; k < NS; k++) {
+                const bool o = E[k] != 0u;
+                const unsigned long long bm = wave_ballot(o);
+                if (o) occ[n_occ + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u))] = (uint16_t)(lane + k * DMPP_WAVE);
+                n_occ += __popcll(bm);
+            }
+            wave_order();
+        }
+        // (2) per closed cell: its digest term (the same terms as hash_digest: the sum does not depend on the order), and for a found
+        //     path the slot of its parent cell - first probe in straight-line code, collision chains in a wave-uniform loop, as the insert
+        for (int r0 = 0; r0 < n_occ; r0 += DMPP_WAVE) {
+            const bool act = r0 + lane < n_occ;
+            const uint32_t sl = act ? (uint32_t)occ[r0 + lane] : 0u;
+            const uint32_t e = L.c_tab[sl], inf = L.c_info[sl]; const uint32_t sq = L.seq_of(sl, e);
+            if (act && sq != CW::kSeqNone) digest += mix64(((uint64_t)sq << 32) | (uint64_t)(CW::key(e) - 1u));
+            if (chain) {
+                const int pd = (int)(inf & 15u), rn = (int)(inf >> 4);
                 // dx, dy of direction pd from two packed tables (2 bits each, value + 1)
-                const int dx = (int)((0x901Au >> (2 * pd)) & 3u) - 1, dy = (int)((0x01A9u >> (2 * pd)) & 3u) - 1;
-                const int step = dy * W + dx;
-                L.o_ent[hops] = (uint32_t)cur; L.o_run[hops] = (uint16_t)rn; L.o_f2[hops] = (uint16_t)pd;
-                hops++; Lc += rn; cur -= rn * step;
+                const int dx = (int)((0x901Au >> (2 * (pd & 7))) & 3u) - 1, dy = (int)((0x01A9u >> (2 * (pd & 7))) & 3u) - 1;
+                const bool want = act && pd <= 7 && rn > 0;
+                const uint32_t keyc = CW::key(e) - (uint32_t)(rn * (dy * W + dx));          // the parent's cell + 1
+                uint32_t hh = ((keyc - 1u) * 2654435761u) >> (32 - kClosedLog);
+                uint32_t e2 = L.c_tab[hh];
+                bool miss = want && CW::key(e2) != keyc && e2 == 0u, coll = want && CW::key(e2) != keyc && e2 != 0u;
+                for (int probe = 1; probe < kClosedTab && wave_ballot(coll); probe++) {
+                    if (coll) {
+                        hh = (hh + 1u) & (uint32_t)(kClosedTab - 1);
+                        e2 = L.c_tab[hh];
+                        if (CW::key(e2) == keyc) coll = false;
+                        else if (e2 == 0u) { coll = false; miss = true; }
+                    }
+                }
+                miss |= coll;                                   // (a full turn without the cell or a hole: the table is never full)
+                if (act) par[sl] = (uint16_t)(!want ? kParInvalid : (miss ? kParMissing : (hh == start_slot ? kParStart : hh)));
             }
         }
-        Lc = __builtin_amdgcn_readfirstlane(Lc);
+        wave_order();
+    }
+    DBG_MARK(12)
+    digest = wave_sum_u64(digest);
+    DBG_MARK(15)
+    if (chain) {
+        // The length is known before a cell is written, so every cell goes straight to its final place, path[keep-1-k] for the
+        // k-th cell counted from the goal: one lane per hop, offsets from a wave prefix sum of the run lengths.
+        int Lc = 1, hops = 0, bad = 0;         // bad: 1 = inconsistent closed set, 2 = more hops than the LDS list holds
+        // lane 0 follows the parent slots from the goal's slot (the lane that closed the goal left it) until one says "the start": per hop
+        // one dependent LDS read and one store; slot number, hop count and the tests are scalar (the slot read comes back through
+        // readfirstlane)
+        if (lane == 0 && goal_slot != start_slot) {
+            uint32_t cur = goal_slot;
+            for (;;) {
+                L.o_f2[hops] = (uint16_t)cur;
+                hops++;
+                const uint32_t up = (uint32_t)__builtin_amdgcn_readfirstlane((int)par[cur]);
+                if (up >= kParStart) { bad = up == kParStart ? 0 : 1; break; }
+                if (hops >= kOpenCap) { bad = 2; break; }          // (the parent is a further hop, and the list is full)
+                cur = up;
+            }
+        }
         hops = __builtin_amdgcn_readfirstlane(hops);
         bad = __builtin_amdgcn_readfirstlane(bad);
         wave_sync();
+        DBG_MARK(13)
+#ifdef DMPP_DEBUG_SEARCH
+        hops_dbg = hops;
+#endif
         if (bad == 1) status = DMPP_G_INTERNAL;
         else if (bad == 2) {
             // more hops than the LDS list holds: spill the hash to HBM and take the chunked walk below
@@ -1344,24 +1429,27 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
             wave_sync();
             slow_walk = true;
         } else {
+            // hop j's lane reads cell, direction and run of its slot itself; the first 64 hops stay in registers for the stores below
+            uint32_t e_first = 0, i_first = 0;
+            if (lane < hops) { const int sl = L.o_f2[lane]; e_first = L.c_tab[sl]; i_first = L.c_info[sl]; }
+            int runs = (int)(i_first >> 4);
+            for (int j = DMPP_WAVE + lane; j < hops; j += DMPP_WAVE) runs += (int)(L.c_info[L.o_f2[j]] >> 4);
+            Lc = 1 + wave_sum_i32(runs);
             int keep = Lc;
             if (Lc > c.max_path) { keep = c.max_path; status = DMPP_G_PATH_TRUNC; }
             path_len = keep;
             int kbase = 0;
             for (int j0 = 0; j0 < hops; j0 += DMPP_WAVE) {
                 const int j = j0 + lane;
-                const int rn = j < hops ? (int)L.o_run[j] : 0;
-                int incl = rn;
-#pragma unroll
-                for (int sft = 1; sft < DMPP_WAVE; sft <<= 1) { const int t = __shfl_up(incl, sft, 64); if (lane >= sft) incl += t; }
-                int ec = 0, step = 0;
+                uint32_t e2 = e_first, inf = i_first;
+                if (j0) { e2 = 0; inf = 0; if (j < hops) { const int sl = L.o_f2[j]; e2 = L.c_tab[sl]; inf = L.c_info[sl]; } }
+                const int rn = (int)(inf >> 4), pd = (int)(inf & 15u);
+                // (DPP gives the scan in six register steps; the six __shfl_up rounds it replaces were LDS-crossbar round trips)
+                const int incl = wave_scan_i32(rn);
                 const int idx0 = kbase + incl - rn;
-                if (rn) {
-                    const int pd = L.o_f2[j];
-                    ec = (int)L.o_ent[j];
-                    const int dx = (int)((0x901Au >> (2 * pd)) & 3u) - 1, dy = (int)((0x01A9u >> (2 * pd)) & 3u) - 1;
-                    step = dy * W + dx;
-                }
+                const int ec = (int)CW::key(e2) - 1;
+                const int dx = (int)((0x901Au >> (2 * pd)) & 3u) - 1, dy = (int)((0x01A9u >> (2 * pd)) & 3u) - 1;
+                const int step = dy * W + dx;
                 // short runs (diagonal jumps, hops between close jump points): the hop's lane writes its cells; long
                 // straight runs: the whole wave writes one run together
                 constexpr int kLongRun = 12;
@@ -1370,12 +1458,14 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
                 while (lm) {
                     const int src = __ffsll((long long)lm) - 1;
                     lm &= lm - 1;
-                    const int h_ec = __shfl(ec, src, 64), h_step = __shfl(step, src, 64), h_rn = __shfl(rn, src, 64), h_idx = __shfl(idx0, src, 64);
+                    const int h_ec = __builtin_amdgcn_readlane(ec, src), h_step = __builtin_amdgcn_readlane(step, src);
+                    const int h_rn = __builtin_amdgcn_readlane(rn, src), h_idx = __builtin_amdgcn_readlane(idx0, src);
                     for (int r = lane; r < h_rn; r += DMPP_WAVE) if (h_idx + r < keep) path[keep - 1 - (h_idx + r)] = h_ec - r * h_step;
                 }
-                kbase += __shfl(incl, DMPP_WAVE - 1, 64);
+                kbase += __builtin_amdgcn_readlane(incl, DMPP_WAVE - 1);
             }
             if (lane == 0 && keep == Lc) path[0] = start;
+            DBG_MARK(14)
         }
     }
     if (status == DMPP_G_FOUND && slow_walk) {
@@ -1431,10 +1521,12 @@ __device__ __forceinline__ SearchOut search_core(const PlannerConfig& c, LDS& L,
         }
     }
     DBG_MARK(6)
-    int n_push = my_pushes;
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) n_push += __shfl_xor(n_push, sft, 64);
-    n_push += 1;                                         // the start node
+    const int n_push = wave_sum_i32(my_pushes) + 1;      // + 1: the start node
+    DBG_MARK(15)
+#ifdef DMPP_DEBUG_SEARCH
+    dbg_t[6] += dbg_t[12] + dbg_t[13] + dbg_t[14] + dbg_t[15];      // slot 6 stays the whole tail; 12 .. 15 split it
+    dbg_c[5] = hops_dbg;
+#endif
     R.status = status; R.n_exp = n_exp; R.n_push = n_push; R.n_rounds = n_rounds; R.path_cost = path_cost; R.path_len = path_len; R.digest = digest;
     return R;
 #undef DBG_MARK
@@ -1471,7 +1563,8 @@ __device__ __forceinline__ void publish_debug(int32_t* path, int max_path, const
     dbg[10] = (int)(t[6] >> 4); dbg[11] = (int)((t[0] + t[1] + t[2] + t[3] + t[4] + t[5] + t[6]) >> 4); dbg[12] = (int)(t_setup >> 4); dbg[13] = (int)(t_total >> 4);
     dbg[14] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_ID: wave 3:0, simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13
     dbg[15] = (int)__builtin_amdgcn_s_getreg((31 << 11) | 20);      // XCC_ID
-    for (int i = 7; i < 16; i++) path[max_path - 64 + i] = (int)(t[i] >> 4);
+    for (int i = 7; i < 16; i++) path[max_path - 64 + i] = (int)(t[i] >> 4);      // (12 .. 15: the tail's split - hash pass, chain, path cells, reductions)
+    path[max_path - 64 + 6] = cn[5];                                              // hops of the path walk
 }
 #endif
 

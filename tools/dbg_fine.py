@@ -5,7 +5,7 @@ import sys
 sys.path.insert(0,'.'); sys.path.insert(0,'tests')
 import os
 import numpy as np, dmpp_amd as dm
-dm.load_library(os.path.join(os.path.dirname(dm.LIB_PATH), 'libdmpp_dbg.so'))
+dm.load_library(os.path.join(os.path.dirname(dm.LIB_PATH), os.environ.get('DMPP_DBG_LIB', 'libdmpp_dbg.so')))
 cfg = dm.default_config(512)
 n=1024
 sc = dm.gen_scenes(cfg, 0, n, 64, 8)
@@ -18,7 +18,7 @@ for s in range(n):
     pp_=pl.get_path(s, mp)
     rows.append(pp_[-16:].tolist()+pp_[-64+7:-64+16].tolist())
 rows=np.array(rows)[g['status']==0]
-names=['iter','popped','jump_iters','diag_jobs','rounds','pop','probe','cand','results','push','walk','sum','setup','kernel','hw','xcc','post','jobread+metas','celltests','jump_lane','rules','t12','t13','t14','t15']
+names=['iter','popped','jump_iters','diag_jobs','rounds','pop','probe','cand','results','push','walk','sum','setup','kernel','hw','xcc','post','jobread+metas','celltests','jump_lane','rules','tail_hash_pass','tail_chain','tail_path_cells','tail_reductions']
 idx=np.argsort(-rows[:,13])[:4]
 for i in idx: print(dict(zip(names, rows[i].tolist())))
 tot=rows.sum(axis=0)
