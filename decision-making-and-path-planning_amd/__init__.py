@@ -20,9 +20,9 @@ GEN_LANE_PTS, GEN_REF_PTS = 320, 128
 
 G_FOUND, G_NO_PATH, G_LIMIT, G_OVERFLOW, G_GOAL_BLOCKED, G_PATH_TRUNC, G_INTERNAL, G_COST_RANGE = range(8)
 G_STATUS_COUNT = 8
-K_NAMES = ["k_effective_obstacles", "k_decision", "k_planning", "k_search", "k_score", "k_pack_plan", "k_pack_grid"]
+K_NAMES = ["k_effective_obstacles", "k_decision", "k_planning", "k_search", "k_score", "k_pack_plan", "k_pack_grid", "k_perceive"]
 (BUF_SCENE_IN, BUF_LANE_POOL, BUF_REF_POOL, BUF_OBS_POOL, BUF_MOT_POOL, BUF_STATE, BUF_PLAN_OUT, BUF_GRID_OUT,
- BUF_GRID, BUF_PATH, BUF_ORDER, BUF_LANE_ATTR, BUF_OBS_NOW) = range(13)
+ BUF_GRID, BUF_PATH, BUF_ORDER, BUF_LANE_ATTR, BUF_OBS_NOW, BUF_OBS_SEEN) = range(14)
 
 
 def _dt(fields):
@@ -147,6 +147,14 @@ ConflictModel = _dt([("ttc_warn", f8), ("ttc_crit", f8), ("v_max", f8), ("min_cl
 ConflictScore = _dt([("min_ttc", f8), ("max_drac", f8), ("tit_warn", f8), ("last_pos", GlobalPoint2D), ("n_ticks", i4), ("n_conflict_ticks", i4),
                      ("n_warn_ticks", i4), ("n_crit_ticks", i4), ("min_ttc_tick", i4), ("min_ttc_obs", i4), ("min_ttc_type", i4), ("first_crit_tick", i4),
                      ("max_drac_tick", i4), ("n_no_history_ticks", i4), ("prev_off", i4), ("prev_n", i4)])
+# perception model: the planner reads a perceived snapshot - range, field of view, occlusion, misses, noise, tracks
+PERCEPT_HIDDEN_XY = 1.0e12          # x = y of the hidden record (DMPP_PERCEPT_HIDDEN_XY); its type is the truth's, its radius 0
+PerceptionModel = _dt([("range", f8), ("cos_half_fov", f8), ("sigma0", f8), ("sigma_gain", f8), ("p_miss", np.uint32), ("seed", np.uint32),
+                       ("occlusion", i4), ("confirm", i4), ("coast", i4), ("_pad", i4)])
+PerceptTrack = _dt([("last", ObPoint), ("hits", np.uint16), ("misses", np.uint16), ("confirmed", np.uint8), ("_pad", np.uint8, (3,))])
+PerceptionStats = _dt([("n_ticks", np.int64), ("n_entries", np.int64), ("n_out", np.int64), ("n_occluded", np.int64), ("n_missed", np.int64),
+                       ("n_detected", np.int64), ("n_fresh", np.int64), ("n_coasted", np.int64), ("n_hidden", np.int64),
+                       ("min_hidden_clearance", f8), ("min_hidden_tick", np.int64), ("min_hidden_obs", i4), ("min_hidden_type", i4)])
 # scenario schedule: the start record of a restart drawn by weights from per-record outcome counts kept on the device
 EpisodeSchedule = _dt([("scope", i4), ("fail_mask", i4), ("pass_mask", i4), ("min_samples", i4), ("window", i4), ("floor_w", i4), ("gain", i4),
                        ("target", i4), ("prior", i4), ("_pad", i4)])
@@ -229,6 +237,9 @@ _FEATURES = [
                                "pp_get_conflict_score": ([_vp, _vp, _ci], _ci)}, {45: ConflictModel, 46: ConflictScore}),
     ("pp_set_traffic_manoeuvres", {"pp_set_traffic_manoeuvres": ([_vp, _ci, _vp], _ci), "pp_get_traffic_manoeuvre_state": ([_vp, _vp, _ci], _ci),
                                    "pp_check_traffic_manoeuvres": ([_ci, _ci, _ci, _vp], _ci)}, {47: TrafficManoeuvre, 48: TrafficManoeuvreState}),
+    ("pp_set_perception", {"pp_default_perception": ([_vp], None), "pp_set_perception": ([_vp, _vp], _ci),
+                           "pp_get_perception_stats": ([_vp, _vp, _ci], _ci), "pp_get_perception_tracks": ([_vp, _vp, _ci, _ci], _ci)},
+     {50: PerceptionModel, 51: PerceptTrack, 52: PerceptionStats}),          # (pp_sizeof id 49 stays unassigned)
 ]
 
 _lib = None
@@ -431,6 +442,19 @@ def unpack_grid(cfg, packed, out=None):
 def default_conflict():
     """ConflictModel record of the conflict score (pp_default_conflict): ttc_warn 3 s, ttc_crit 1.5 s, v_max 70 m/s, min_closing 0."""
     return _default(ConflictModel, "pp_default_conflict")
+
+
+def default_perception():
+    """PerceptionModel record of the perception model (pp_default_perception): range 60 m, cos_half_fov cos 60 deg, sigma0 0.1 m,
+    sigma_gain 0.005, p_miss 2 % of 2^32, seed 1, occlusion on, confirm 2, coast 3 - a starting point, not tuned values."""
+    return _default(PerceptionModel, "pp_default_perception")
+
+
+def transparent_perception():
+    """The PerceptionModel that hides nothing and changes nothing: the perceived snapshot is the truth's bytes for every finite entry."""
+    m = np.zeros(1, PerceptionModel)
+    m["range"], m["cos_half_fov"] = np.inf, -1.0
+    return m
 
 
 def default_score_trace():
@@ -691,6 +715,30 @@ class Planner:
         """pp_get_conflict_score: the ConflictScore records, the last enqueued tick included (host wait)."""
         out = np.zeros(self.n, ConflictScore)
         _check(self.lib.pp_get_conflict_score(self.h, _ptr(out), self.n))
+        return out
+
+    def set_perception(self, model):
+        """pp_set_perception: from the next tick on k_perceive takes the place of the snapshot kernel; Decision,
+        Planning, the search and its scoring read the perceived snapshot (BUF_OBS_SEEN), every judge keeps the truth (BUF_OBS_NOW).
+        model: a PerceptionModel record (default_perception()); every call restarts tracks and stats.  None: off, they stay readable."""
+        if model is None:
+            _check(self.lib.pp_set_perception(self.h, None))
+            return
+        m = np.array(model, PerceptionModel).reshape(1).copy()
+        _check(self.lib.pp_set_perception(self.h, _ptr(m)))
+
+    def perception_stats(self):
+        """pp_get_perception_stats: the PerceptionStats records, the last enqueued tick included (host wait)."""
+        out = np.zeros(self.n, PerceptionStats)
+        _check(self.lib.pp_get_perception_stats(self.h, _ptr(out), self.n))
+        return out
+
+    def perception_tracks(self, first=0, count=None):
+        """pp_get_perception_tracks: `count` PerceptTrack records from pool entry `first` on (default: the obstacle pool of the
+        resident set), the last enqueued tick included (host wait)."""
+        n = int(self.n_obs_total if count is None else count)
+        out = np.zeros(n, PerceptTrack)
+        _check(self.lib.pp_get_perception_tracks(self.h, _ptr(out), int(first), n))
         return out
 
     # ---- fleet coupling: the egos of one world are each other's obstacles ------------------
@@ -1100,7 +1148,7 @@ class Planner:
 
     def kernel_ms(self):
         out = {}
-        names = K_NAMES if hasattr(self.lib, "pp_set_packed_fetch") else K_NAMES[:5]      # (an older build named through DMPP_LIB)
+        names = K_NAMES if hasattr(self.lib, "pp_set_perception") else K_NAMES[:7] if hasattr(self.lib, "pp_set_packed_fetch") else K_NAMES[:5]      # (an older build named through DMPP_LIB)
         for k, name in enumerate(names):
             ms, cnt = C.c_float(), C.c_int()
             _check(self.lib.pp_get_kernel_ms(self.h, k, C.byref(ms), C.byref(cnt)))

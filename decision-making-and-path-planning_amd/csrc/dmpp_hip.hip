@@ -35,6 +35,7 @@
 #include "kernels_tm.hpp"
 #include "kernels_op.hpp"
 #include "kernels_pk.hpp"
+#include "kernels_pc.hpp"
 #include "search_budget.hpp"
 #include "rollout_features.hpp"
 
@@ -302,6 +303,17 @@ struct ConflictState {
     bool on = false, ever = false; int cur = 0; ConflictModel cm = {};
     DevBuf<ConflictScore> d_score; DevBuf<ObPoint> d_prev[2];
 };
+// perception model (first pp_set_perception): the model, the perceived snapshot ring - the layout of obs_now_mem /
+// d_obs_now, slot stride included, so that TickGroup.obs_now + slot * obs_stride works on it -, one track per pool entry and one
+// stats record per scene (single copies: only k_perceive of consecutive ticks touches them, and front chains are serial).  While
+// on, a tick launches k_perceive in the place of the snapshot kernel and hands the perceived set to Decision, Planning, the search,
+// its scoring pass and pp_get_grid.  Belongs to the handle like the ego tracker: no rollout feature, no set call retires it; what
+// replaces the resident scenes or moves slices restarts tracks and stats (reset_perception).  They stay readable after it went off
+struct PerceptionState {
+    bool on = false, ever = false; PerceptionModel pm = {};
+    DevBuf<ObPoint> seen_mem[kRing]; ObPoint* d_seen[kObs] = {};
+    DevBuf<PerceptTrack> d_track; DevBuf<PerceptionStats> d_stats;
+};
 // packed streamed fetch (first pp_set_packed_fetch(h, 1)): one PackedPlan set per PlanOut set and one PackedGrid
 // set per GridOut group position (an armed handle is a streamed one: groups of 1, tick slot 0 only), each written by its tick's pack
 // kernel in stream order behind the kernel that wrote the PlanOut / GridOut set of the same index - so a set is rewritten only
@@ -412,6 +424,7 @@ struct pp_planner {
     EpisodeLogState elog;
     ScoreTraceState strace;
     ConflictState conflict;
+    PerceptionState percept;
     PackedState packed;
     // a grid that follows the ego: the model travels to both advance kernels as an argument; goal_point 0 = off.
     // It belongs to the handle and holds no per-scene data: nothing that replaces the scenes or the map resets it
@@ -1081,6 +1094,18 @@ static int reset_conflict(pp_handle h)
     return PP_OK;
 }
 
+// Tracks and stats of the perception model at their starting values (§4w 4., 5.), on the handle's stream: behind join_all - every
+// k_perceive enqueued so far has finished before it, and the next front chain starts behind the caller's host wait.
+static int reset_perception(pp_handle h)
+{
+    if (!h->percept.d_stats) return PP_OK;
+    const int ns = h->caps.max_scenes, nt = std::max(h->caps.max_obs_total, 1), nn = std::max(ns, nt);
+    hipLaunchKernelGGL(dmpp::k_percept_reset, dim3((unsigned)((nn + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream,
+                       ns, h->percept.d_stats.get(), nt, h->percept.d_track.get());
+    HIP_TRY(hipGetLastError());
+    return PP_OK;
+}
+
 // The scorecard's starting values, on the handle's stream behind join_all (every scoring kernel enqueued so far has finished
 // before it); the caller's host wait follows.
 static int reset_scores(pp_handle h)
@@ -1141,6 +1166,7 @@ static int resident_replaced(pp_handle h, int mode, const char* who, int map_bad
     if (h->tracker.d_state)                              // every tracked pose is re-derived from the new records (§4q 1.)
         HIP_TRY(hipMemsetAsync(h->tracker.d_state, 0, (size_t)h->caps.max_scenes * sizeof(EgoTrackState), h->stream));
     if (h->score.on) PP_TRY(reset_scores(h));
+    PP_TRY(reset_perception(h));      // no track outlives the scenes it followed (§4w)
     if (map_bad) { h->n_scenes = 0; return fail(PP_ERR_ARG, std::string(who) + ": " + std::to_string(map_bad) + " scene(s) name a road or lane outside the map"); }
     PP_TRY(validate_resident(h, h->n_scenes, who));
     return features_ok(h, who);
@@ -1323,7 +1349,7 @@ int flush_group(pp_planner* h)
         if (h->streaming) PP_TRY(h->dl[kGridSide].fetched[h->grp_gs[i]].wait_unless_done(sm));   // GridOut set still being downloaded
     dmpp::TickGroup tg;                                                // slot i: sets grp_set[0] + i, grp_gs[0] + i
     tg.n = n; tg.in = h->grp_in;
-    tg.obs_now = h->d_obs_now[set0]; tg.obs_stride = std::max(h->caps.max_obs_total, 1);
+    tg.obs_now = h->percept.on ? h->percept.d_seen[set0] : h->d_obs_now[set0]; tg.obs_stride = std::max(h->caps.max_obs_total, 1);
     tg.paths = h->d_path[set0]; tg.path_stride = (long long)h->caps.max_scenes * h->max_path0;
     tg.gout = h->d_gout[h->grp_gs[0]]; tg.gout_stride = h->caps.max_scenes;
     // launch order of the search (heaviest work items first) - pointless while every item is resident at once.  Keyed by the
@@ -1465,6 +1491,10 @@ int pp_plan_tick(pp_handle h)
     if (h->score.ego.done()) h->score.ego.forget();
     else if (!behind_upload) PP_TRY(h->score.ego.wait(sf));
     ObPoint* obs_now = h->d_obs_now[po];
+    // Perception (§4w): k_perceive writes the truth into obs_now and what the planner may see into the set of the same index of the
+    // perceived ring - same writer, same readers as obs_now[po], so scored[po] above covers both.  Planners get obs_plan, judges obs_now.
+    const bool perceive = h->percept.on;
+    const ObPoint* obs_plan = perceive ? h->percept.d_seen[po] : obs_now;
     // Snapshot and Decision on one stream (piped ticks, ticks without the grid stage): the snapshot is the head of k_decision<true>,
     // one launch less per tick.  Every reader of the set waits for something behind that kernel: the searches for `raster`,
     // recorded behind it; Planning, k_score_ego (ev_front) and join_all for stream order on sr.  (`raster` behind k_planning
@@ -1472,9 +1502,14 @@ int pp_plan_tick(pp_handle h)
     // 20-step leg loses 2 % to the later start of its searches - profiles/r25_front_two_launch.txt.)
     // Streamed handles keep the separate launch: their groups are single ticks, every search waits for its own tick's `raster`, and
     // starting each one k_decision later cost the streamed leg 1.3 %, more than its spread (same file).
-    const bool snap_fused = h->front_snapshot && c.decision_stage && sf == sr && !h->streaming;
+    const bool snap_fused = h->front_snapshot && c.decision_stage && sf == sr && !h->streaming && !perceive;
     const ObMotion* mot = I.mot();
-    if (!snap_fused) {
+    if (perceive) {
+        Timed t(h, PP_K_PERCEIVE, sf);
+        hipLaunchKernelGGL(dmpp::k_perceive, dim3((unsigned)((n + dmpp::kPcScenes - 1) / dmpp::kPcScenes)), dim3(dmpp::kBlock), 0, sf, c, h->percept.pm, n,
+                           std::min(I.n_obs_total, h->caps.max_obs_total), h->tick_seq + 1, I.d_in, h->d_state, I.d_obs, mot,
+                           h->episode.on ? h->episode.d_stats.get() : nullptr, obs_now, h->percept.d_seen[po], h->percept.d_track.get(), h->percept.d_stats.get());
+    } else if (!snap_fused) {
         Timed t(h, PP_K_OBSTACLES, sf);
         hipLaunchKernelGGL(dmpp::k_effective_obstacles, dim3(n), dim3(dmpp::kBlock), 0, sf, c, n, I.d_in, h->d_state, I.d_obs, mot, obs_now);
     }
@@ -1488,13 +1523,13 @@ int pp_plan_tick(pp_handle h)
                                h->d_attr, h->d_ref, I.d_obs, mot, obs_now, h->d_state, d_plan, h->d_dec_ref);
         else
             hipLaunchKernelGGL(dmpp::k_decision<false>, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::DecShared), sr, c, n, I.d_in, h->d_lane,
-                               h->d_attr, h->d_ref, I.d_obs, mot, obs_now, h->d_state, d_plan, h->d_dec_ref);
+                               h->d_attr, h->d_ref, I.d_obs, mot, const_cast<ObPoint*>(obs_plan), h->d_state, d_plan, h->d_dec_ref);
     }
     if (search_waits && snap_fused) PP_TRY(h->raster.record(sf));
     {
         Timed t(h, PP_K_PLANNING, sr);
         hipLaunchKernelGGL(dmpp::k_planning, dim3(n), dim3(dmpp::kBlock), sizeof(dmpp::PlanShared), sr, c, n, I.d_in, h->d_lane,
-                           h->d_ref, h->d_dec_ref, obs_now, h->d_state, d_plan);
+                           h->d_ref, h->d_dec_ref, obs_plan, h->d_state, d_plan);
     }
     if (h->packed.on) {          // packed fetch, plan half: behind the Planning kernel in stream order, in front of `join` and the tick's ev_front
         {
@@ -1633,7 +1668,7 @@ int pp_get_grid(pp_handle h, int scene, uint8_t* grid)
     // the column-major view against the row-major one (unless the scene is too dense for one workgroup's LDS).
     HIP_TRY(hipSetDevice(h->device));
     { int r = join_all(h); if (r) return r; }       // the snapshot of the last tick was written on another stream
-    const ObPoint* obs_now = h->d_obs_now[h->obs_set];
+    const ObPoint* obs_now = h->percept.on ? h->percept.d_seen[h->obs_set] : h->d_obs_now[h->obs_set];      // what the search rasterised (§4w)
     int bad[2] = { 0, 0 };
     HIP_TRY(hipMemsetAsync(h->d_gridbad, 0, 2 * sizeof(int), h->stream));
     const int budget = h->search_force_gbm ? 1 : h->lds_budget_max;      // (1 word: nothing fits, the span-by-span path)
@@ -2057,6 +2092,71 @@ int pp_get_conflict_score(pp_handle h, ConflictScore* out, int n_scenes)
     return PP_OK;
 }
 
+// Perception model.  Everything is checked on the host before anything changes.
+void pp_default_perception(PerceptionModel* m)
+{
+    if (!m) return;
+    m->range = 60.0; m->cos_half_fov = 0.5; m->sigma0 = 0.1; m->sigma_gain = 0.005;      // (cos 60 deg; a starting point, not tuned values)
+    m->p_miss = 85899346u; m->seed = 1u; m->occlusion = 1; m->confirm = 2; m->coast = 3; m->_pad = 0;      // p_miss: 2 % of 2^32
+}
+
+static const char* check_perception(const PerceptionModel* m)
+{
+    if (!(m->range > 0)) return "range must be > 0 (+inf is allowed)";
+    if (!(m->cos_half_fov >= -1.0 && m->cos_half_fov <= 1.0)) return "cos_half_fov must lie in [-1, 1]";
+    if (!std::isfinite(m->sigma0) || !(m->sigma0 >= 0)) return "sigma0 must be finite and >= 0";
+    if (!std::isfinite(m->sigma_gain) || !(m->sigma_gain >= 0)) return "sigma_gain must be finite and >= 0";
+    if (m->occlusion != 0 && m->occlusion != 1) return "occlusion must be 0 or 1";
+    if (m->confirm < 0 || m->confirm > 255) return "confirm must lie in 0 .. 255";
+    if (m->coast < 0 || m->coast > 255) return "coast must lie in 0 .. 255";
+    if (m->_pad != 0) return "_pad must be 0";
+    return nullptr;
+}
+
+int pp_set_perception(pp_handle h, const PerceptionModel* m)
+{
+    if (!h) return fail(PP_ERR_ARG, "null handle");
+    if (m) if (const char* why = check_perception(m)) return fail(PP_ERR_ARG, std::string("pp_set_perception: ") + why);
+    // (no refuse_if_staged: the call reads nothing of the resident set - tracks follow pool entries of whatever set a tick reads - so an
+    // update or an advance staged for the next tick stays staged, and that tick is the first one perceived)
+    PP_TRY(quiesce(h, false));                           // every tick so far is in front of the handle's stream (an open group is launched with the old setting)
+    if (!m) { h->percept.on = false; return PP_OK; }      // (tracks and stats stay readable)
+    PerceptionState& P = h->percept;
+    const size_t obs_stride = (size_t)std::max(h->caps.max_obs_total, 1);      // room first: a failed allocation changes nothing in force
+    for (int q = 0; q < kObs; q += kGroupMax) {
+        PP_TRY(P.seen_mem[q / kGroupMax].reserve(h->gcap * obs_stride));
+        for (int i = 0; i < h->gcap; i++) P.d_seen[q + i] = P.seen_mem[q / kGroupMax] + i * obs_stride;
+    }
+    PP_TRY(P.d_track.reserve(obs_stride)); PP_TRY(P.d_stats.reserve((size_t)h->caps.max_scenes));
+    // the perceived ring starts as a copy of the truth ring: until the first perceived tick pp_get_grid and PP_BUF_OBS_SEEN show
+    // what the last tick's search rasterised, never memory nobody wrote
+    for (int q = 0; q < kRing; q++)
+        HIP_TRY(hipMemcpyAsync(P.seen_mem[q].get(), h->obs_now_mem[q].get(), h->gcap * obs_stride * sizeof(ObPoint), hipMemcpyDeviceToDevice, h->stream));
+    PP_TRY(reset_perception(h));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the one host wait: the front chain of the next tick may start on another stream
+    P.pm = *m; P.on = true; P.ever = true;
+    return PP_OK;
+}
+
+// (k_perceive runs on the front chain: behind join_all)
+int pp_get_perception_stats(pp_handle h, PerceptionStats* out, int n_scenes)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->percept.ever) return fail(PP_ERR_STATE, "pp_get_perception_stats: pp_set_perception was never called on this handle");
+    if (n_scenes < 0 || n_scenes > h->n_scenes) return fail(PP_ERR_ARG, "n_scenes exceeds the resident scenes");
+    if (n_scenes == 0) return PP_OK;
+    return fetch(h, out, h->percept.d_stats, (size_t)n_scenes * sizeof(PerceptionStats));
+}
+
+int pp_get_perception_tracks(pp_handle h, PerceptTrack* out, int first, int n)
+{
+    if (!h || !out) return fail(PP_ERR_ARG, "null argument");
+    if (!h->percept.ever) return fail(PP_ERR_STATE, "pp_get_perception_tracks: pp_set_perception was never called on this handle");
+    if (first < 0 || n < 0 || (long long)first + n > (long long)h->caps.max_obs_total) return fail(PP_ERR_ARG, "pp_get_perception_tracks: the range lies outside the obstacle pool (caps.max_obs_total)");
+    if (n == 0) return PP_OK;
+    return fetch(h, out, h->percept.d_track + first, (size_t)n * sizeof(PerceptTrack));
+}
+
 // Every resident scene's OWN obstacle entries (obs_off, obs_n): of the resident records, or - fleet on - the ones pinned then
 // (obs_n counts the peers now).  Behind join_all; waits on the host.  *rc: PP_OK, or the error (the vector is empty then).
 static std::vector<dmpp::FleetPin> own_slices(pp_handle h, int* rc)
@@ -2085,6 +2185,7 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
         PP_TRY(quiesce(h, false));
         hipLaunchKernelGGL(dmpp::k_fleet_restore, dim3((unsigned)((n + dmpp::kBlock - 1) / dmpp::kBlock)), dim3(dmpp::kBlock), 0, h->stream, n, h->fleet.d_pin, h->cur_in().d_in);
         HIP_TRY(hipGetLastError());
+        PP_TRY(reset_perception(h));   // the slices move (§4w)
         HIP_TRY(hipStreamSynchronize(h->stream));
         // (the slices are the pinned ones again; they were inside fleet.base when they were pinned)
         const int back = std::max(h->fleet.base, h->fleet.own_end);
@@ -2133,6 +2234,7 @@ int pp_set_fleet(pp_handle h, int n_worlds, const int32_t* world_first, const Fl
     h->cur_in().n_obs_total = (int)end_max;
     couple_fleet(h, h->stream, h->cur_in().d_in, h->cur_in().d_obs, h->cur_in().mot());      // the resident set: the next tick sees the peers
     HIP_TRY(hipGetLastError());
+    PP_TRY(reset_perception(h));      // the slices grow by their peer slots (§4w)
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
     return features_ok(h, "pp_set_fleet");
 }
@@ -2146,7 +2248,13 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     const std::string fn = world ? "pp_set_world_traffic" : "pp_set_traffic";
     if (n_tracks < 0 || n_points < 0 || n_actors < 0) return fail(PP_ERR_ARG, fn + ": negative count");
     PP_TRY(refuse_if_staged(h, fn, "the traffic"));
-    if (n_actors == 0) { retire(h, dmpp::kTrafficOff); return features_ok(h, fn.c_str()); }
+    if (n_actors == 0) {
+        retire(h, dmpp::kTrafficOff);
+        if (h->percept.d_stats) {                         // the vehicles leave their slots: tracks and stats of the perception model start again (§4w)
+            PP_TRY(quiesce(h, false)); PP_TRY(reset_perception(h)); HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        return features_ok(h, fn.c_str());
+    }
     const int n = h->n_scenes;
     if (n <= 0) return fail(PP_ERR_STATE, fn + ": no resident scenes");
     if (world && !h->fleet.on) return fail(PP_ERR_STATE, fn + ": no fleet is set (the worlds are those of pp_set_fleet; max_peers = 0 is a legal fleet)");
@@ -2233,6 +2341,7 @@ static int set_traffic(pp_handle h, bool world, int n_tracks, const TrafficTrack
     h->traffic.scene_of.swap(scene_of); h->traffic.track_of.swap(track_of);
     move_traffic(h, h->stream, h->cur_in().d_obs, h->cur_in().mot(), 0.0);      // s = wrap(s0), and the resident set: the next tick sees the traffic
     HIP_TRY(hipGetLastError());
+    PP_TRY(reset_perception(h));      // other vehicles own the slots from here on (§4w)
     HIP_TRY(hipStreamSynchronize(h->stream));            // (the host arrays above go out of scope)
     if (h->follow.on) PP_TRY(build_follow(h));           // following is on: its tables for these actors, v = speed (§4i)
     h->traffic.on = true;
@@ -3225,6 +3334,7 @@ void* pp_device_ptr(pp_handle h, int which, size_t* bytes)
     case PP_BUF_PATH: p = h->d_path[h->path_set]; b = ns * (size_t)h->max_path0 * 4; break;
     case PP_BUF_LANE_ATTR: p = h->d_attr; b = (size_t)h->caps.max_lane_pts_total; break;
     case PP_BUF_OBS_NOW: p = h->d_obs_now[h->obs_set]; b = (size_t)h->caps.max_obs_total * sizeof(ObPoint); break;   // the last tick's snapshot
+    case PP_BUF_OBS_SEEN: p = h->percept.d_seen[h->obs_set]; b = p ? (size_t)h->caps.max_obs_total * sizeof(ObPoint) : 0; break;   // ... and its perceived one (§4w)
     case PP_BUF_ORDER: p = h->d_order[h->parity] ? h->d_order[h->parity] + (size_t)h->item_off * h->caps.order_cap : nullptr; b = ns * (size_t)h->caps.order_cap * 4; break;
     default: break;
     }
@@ -3290,6 +3400,7 @@ size_t pp_sizeof(int which)
     case 43: return sizeof(PackedPlan); case 44: return sizeof(PackedGrid);      // (42 stays unassigned)
     case 45: return sizeof(ConflictModel); case 46: return sizeof(ConflictScore);
     case 47: return sizeof(TrafficManoeuvre); case 48: return sizeof(TrafficManoeuvreState);
+    case 50: return sizeof(PerceptionModel); case 51: return sizeof(PerceptTrack); case 52: return sizeof(PerceptionStats);      // (49 stays unassigned)
     default: return 0;
     }
 }

@@ -53,6 +53,9 @@
 // §4u): the device differences the obstacle snapshots of consecutive scored ticks and keeps every scene's smallest time to collision and largest
 // braking demand; behind the run the host prints min_ttc, n_crit_ticks and max_drac per scene, and the worst scene.  Any mode; a routed run gets
 // the scorecard.
+// With --perception [RANGE[,CONFIRM]] the planner reads what a sensor would report (pp_set_perception with the default model, range / confirm
+// replaced) while the scorecard and the conflict score keep the truth; behind the run the host prints the entry-ticks by cause
+// and by output and the closest thing no planner saw, beside the scorecard.  Any mode.
 // Exit code 0 = ran on the GPU.
 #include "../../include/dmpp_planner.h"
 #include <algorithm>
@@ -72,6 +75,41 @@ static int set_conflict(pp_handle h, const ConflictArg& a)
     if (a.warn > 0) { cm.ttc_warn = a.warn; if (cm.ttc_crit > a.warn) cm.ttc_crit = a.warn; }
     if (a.crit > 0) cm.ttc_crit = a.crit;
     CHECK(pp_set_conflict_score(h, &cm));
+    return 0;
+}
+
+// --perception [RANGE[,CONFIRM]]: the perception model on with the default model, range (m, 0: the default) and confirm (-1: the default) replaced
+struct PerceptArg { bool on = false; double range = 0; int confirm = -1; };
+static PerceptArg g_percept;
+static int set_percept(pp_handle h)
+{
+    if (!g_percept.on) return 0;
+    PerceptionModel pm; pp_default_perception(&pm);
+    if (g_percept.range > 0) pm.range = g_percept.range;
+    if (g_percept.confirm >= 0) pm.confirm = g_percept.confirm;
+    CHECK(pp_set_perception(h, &pm));
+    return 0;
+}
+// ... and behind the run: the totals over the scenes, and the scene with the closest hidden entry
+static int print_percept(pp_handle h, int n)
+{
+    if (!g_percept.on) return 0;
+    std::vector<PerceptionStats> ps((size_t)n);
+    CHECK(pp_get_perception_stats(h, ps.data(), n));
+    PerceptionStats t = {}; int worst = -1;
+    for (int s = 0; s < n; s++) {
+        const PerceptionStats& p = ps[(size_t)s];
+        t.n_entries += p.n_entries; t.n_out += p.n_out; t.n_occluded += p.n_occluded; t.n_missed += p.n_missed; t.n_detected += p.n_detected;
+        t.n_fresh += p.n_fresh; t.n_coasted += p.n_coasted; t.n_hidden += p.n_hidden;
+        if (p.min_hidden_obs >= 0 && (worst < 0 || p.min_hidden_clearance < ps[(size_t)worst].min_hidden_clearance)) worst = s;
+    }
+    std::printf("perception: %lld entry-ticks over %lld ticks: %lld out of view, %lld occluded, %lld missed, %lld detected; %lld fresh, %lld coasted, %lld hidden\n",
+                (long long)t.n_entries, (long long)ps[0].n_ticks, (long long)t.n_out, (long long)t.n_occluded, (long long)t.n_missed, (long long)t.n_detected,
+                (long long)t.n_fresh, (long long)t.n_coasted, (long long)t.n_hidden);
+    if (worst < 0) { std::printf("perception: no entry was ever hidden\n"); return 0; }
+    const PerceptionStats& w = ps[(size_t)worst];
+    std::printf("perception: the closest thing no planner saw: scene %d, entry %d (type %d) at %.3f m clearance on tick %lld\n", worst, w.min_hidden_obs, w.min_hidden_type,
+                w.min_hidden_clearance, (long long)w.min_hidden_tick);
     return 0;
 }
 
@@ -322,11 +360,13 @@ static int run_route(bool follow, bool traffic, bool react, bool shared, bool ep
     if (sched) CHECK(pp_set_episode_schedule(h, &sm));       // (part of the spawn model in force: it retires nothing, anywhere behind pp_set_episode_spawn)
     if (trace_depth && set_score_trace(h, trace_depth, trace_post)) return 2;      // (no feature: anywhere)
     if (conflict.on && set_conflict(h, conflict)) return 2;                        // (likewise)
+    if (set_percept(h)) return 2;                                                  // (likewise: the model belongs to the handle)
     long long last = 0;
     CHECK(pp_rollout(h, ticks, &model, nullptr, &last));
     CHECK(pp_sync(h));
     if (trace_depth && print_score_trace(h, n, trace_depth)) return 2;
     if (conflict.on && print_conflict(h, n)) return 2;
+    if (print_percept(h, n)) return 2;
     if (log_cap) {
         std::vector<EpisodeRecord> rec((size_t)log_cap);
         long long lost = 0, total = 0;
@@ -503,7 +543,11 @@ int main(int argc, char** argv)
             conflict.on = true;
             if (a + 1 < argc && argv[a + 1][0] != '-' && std::sscanf(argv[++a], "%lf,%lf", &conflict.warn, &conflict.crit) < 1) conflict.warn = -1;
         }
-        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] [--cut-in] | --fleet --traffic --shared [--react] [--episodes [--starts M] --contact --worlds [--reset-traffic]]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]] [--conflict [WARN[,CRIT]]]\n"); return 2; }
+        else if (std::strcmp(argv[a], "--perception") == 0) {
+            g_percept.on = true;
+            if (a + 1 < argc && argv[a + 1][0] != '-' && std::sscanf(argv[++a], "%lf,%d", &g_percept.range, &g_percept.confirm) < 1) g_percept.range = -1;
+        }
+        else { std::fprintf(stderr, "usage: example_rollout [--fleet | --route [--episodes [--starts M] [--contact] [--schedule [pooled|scene]] [--reset-traffic] [--log N]] [--traffic [--react] [--cut-in] | --fleet --traffic --shared [--react] [--episodes [--starts M] --contact --worlds [--reset-traffic]]]] [--follow] [--track [BIAS]] [--score-trace DEPTH[,POST]] [--conflict [WARN[,CRIT]]] [--perception [RANGE[,CONFIRM]]]\n"); return 2; }
     }
     if (traffic && !route) { std::fprintf(stderr, "--traffic drives the ring: use it with --route\n"); return 2; }
     if (g_cut_in && !(route && traffic && !shared && !contact)) { std::fprintf(stderr, "--cut-in scripts the per-scene traffic: use it with --route --traffic [--react]\n"); return 2; }
@@ -524,6 +568,8 @@ int main(int argc, char** argv)
     if (trace_depth < 0 || trace_depth > DMPP_SCORE_TRACE_MAX || (trace_depth && trace_post >= trace_depth)) { std::fprintf(stderr, "--score-trace takes DEPTH 1 .. %d and POST 0 .. DEPTH - 1\n", DMPP_SCORE_TRACE_MAX); return 2; }
     if (conflict.on && (conflict.warn < 0 || conflict.crit < 0 || !std::isfinite(conflict.warn) || !std::isfinite(conflict.crit) || (conflict.warn > 0 && conflict.crit > conflict.warn)))
         { std::fprintf(stderr, "--conflict takes WARN > 0 and 0 < CRIT <= WARN, in seconds\n"); return 2; }
+    if (g_percept.on && (!(g_percept.range >= 0) || g_percept.confirm > 255))
+        { std::fprintf(stderr, "--perception takes RANGE > 0 in metres (0: the default) and CONFIRM 0 .. 255\n"); return 2; }
     if (route) return run_route(follow, traffic, react, shared, episodes, starts, contact, reset, log_cap, trace_depth, trace_post, sched, worlds, conflict);
     const int n = 256, n_obs = 24, ticks = 50;
     PlannerConfig cfg; pp_default_config(&cfg, 256, 256);
@@ -557,10 +603,12 @@ int main(int argc, char** argv)
     CHECK(pp_score_begin(h, model.dt));
     if (trace_depth && set_score_trace(h, trace_depth, trace_post)) return 2;
     if (conflict.on && set_conflict(h, conflict)) return 2;
+    if (set_percept(h)) return 2;
     CHECK(pp_rollout(h, ticks, &model, trace, &last));
     CHECK(pp_sync(h));
     if (trace_depth && print_score_trace(h, n, trace_depth)) return 2;
     if (conflict.on && print_conflict(h, n)) return 2;
+    if (print_percept(h, n)) return 2;
     std::vector<int32_t> flags(n);
     CHECK(pp_get_ego_flags(h, flags.data(), n));
 

@@ -46,12 +46,14 @@ typedef struct PlannerCaps {
 } PlannerCaps;
 
 /* kernels of one tick, in launch order; index into pp_get_kernel_ms.  PP_K_PACK_PLAN / PP_K_PACK_GRID: the two pack kernels of
- * the packed streamed fetch (launched only while pp_set_packed_fetch is on) */
-enum { PP_K_OBSTACLES = 0, PP_K_DECISION, PP_K_PLANNING, PP_K_SEARCH, PP_K_SCORE, PP_K_PACK_PLAN, PP_K_PACK_GRID, PP_K_COUNT };
+ * the packed streamed fetch (launched only while pp_set_packed_fetch is on); PP_K_PERCEIVE: k_perceive, launched in the place of the
+ * snapshot kernel while pp_set_perception is on (PP_K_OBSTACLES counts nothing then) */
+enum { PP_K_OBSTACLES = 0, PP_K_DECISION, PP_K_PLANNING, PP_K_SEARCH, PP_K_SCORE, PP_K_PACK_PLAN, PP_K_PACK_GRID, PP_K_PERCEIVE, PP_K_COUNT };
 /* device buffers addressable through pp_device_ptr (for RCCL scatter/gather by the caller); PP_BUF_OBS_NOW: the last tick's
- * obstacle snapshot (max_obs_total records, only the slots some scene's slice covers are written) */
+ * obstacle snapshot (max_obs_total records, only the slots some scene's slice covers are written); PP_BUF_OBS_SEEN: the perceived
+ * snapshot of the same tick, same layout (NULL, 0 bytes on a handle that never called pp_set_perception) */
 enum { PP_BUF_SCENE_IN = 0, PP_BUF_LANE_POOL, PP_BUF_REF_POOL, PP_BUF_OBS_POOL, PP_BUF_MOT_POOL, PP_BUF_STATE,
-       PP_BUF_PLAN_OUT, PP_BUF_GRID_OUT, PP_BUF_GRID, PP_BUF_PATH, PP_BUF_ORDER, PP_BUF_LANE_ATTR, PP_BUF_OBS_NOW, PP_BUF_COUNT };
+       PP_BUF_PLAN_OUT, PP_BUF_GRID_OUT, PP_BUF_GRID, PP_BUF_PATH, PP_BUF_ORDER, PP_BUF_LANE_ATTR, PP_BUF_OBS_NOW, PP_BUF_OBS_SEEN, PP_BUF_COUNT };
 
 const char* pp_last_error(void);
 
@@ -286,6 +288,36 @@ int  pp_read_score_trace(pp_handle h, int scene, ScoreTick* out, int cap, ScoreT
 void pp_default_conflict(ConflictModel* m);
 int  pp_set_conflict_score(pp_handle h, const ConflictModel* m);
 int  pp_get_conflict_score(pp_handle h, ConflictScore* out, int n_scenes);
+
+/* ---- perception model: the planner sees what a sensor would -------------------------------------------------------------
+ * Without it the planner is handed the obstacle snapshot as it is: every entry from the first tick, exact, through other vehicles, behind
+ * the ego and at any distance.  While a model is set, ONE kernel, k_perceive, takes the place of the snapshot kernel on every tick of the
+ * handle - plain ticks, tick groups, streamed ticks, rollout ticks, pp_tick_io.  It stores the truth snapshot as before and, beside it, a
+ * PERCEIVED snapshot of the same layout: per entry in view (range, field of view about the ego's heading), not occluded (the sight line
+ * to its centre clears the disc of every nearer entry of the slice), not missed (a hash of seed, scene, entry and tick id against
+ * p_miss), then through a track per pool entry that reports only after `confirm` + 1 detections in a row, adds position noise that
+ * grows with distance, and coasts on its last report through `coast` missing ticks.  Decision, Planning, the search, its scoring pass
+ * and pp_get_grid read the perceived snapshot; the scorecard, the score trace, the conflict score, PP_BUF_OBS_NOW, the episode and
+ * traffic kernels keep the truth.  Entry j of the perceived slice is entry j of the truth (PlanOut.ob, around[] and min_clearance_obs
+ * name the same object); an unseen entry is the hidden record { 1e12, 1e12, type, 0 }, which no stage of the tick reacts to.
+ * The model belongs to the handle like the ego tracker: no rollout feature, no set call retires it.  PerceptionStats counts per scene
+ * the entry-ticks by cause and by output, and keeps the closest thing the planner did not see.
+ * pp_default_perception: range 60 m, cos_half_fov cos 60 deg, sigma0 0.1 m, sigma_gain 0.005, p_miss 2 % of 2^32, seed 1, occlusion on,
+ * confirm 2, coast 3 - a starting point, not tuned values.
+ * pp_set_perception: allocates the perceived ring, caps.max_obs_total tracks and caps.max_scenes stats at the first call, restarts
+ * tracks and stats at every call, one host wait behind every tick and advance enqueued so far.  m == NULL: off, the next tick runs
+ * exactly the kernels of a handle that never made the call; tracks and stats stay readable.  PP_ERR_ARG, with nothing changed:
+ * !(range > 0), cos_half_fov outside [-1, 1], sigma0 / sigma_gain not finite or < 0, occlusion not 0 | 1, confirm or coast outside
+ * 0 .. 255, _pad != 0.  Legal while an update or an advance is staged (the call reads nothing of the resident set: the staged tick is the
+ * first one perceived).  Every call that replaces the resident scenes or moves
+ * slices - pp_set_scenes, pp_set_egos, pp_set_n_scenes, pp_set_fleet, pp_set_traffic, pp_set_world_traffic (with or without actors) - restarts
+ * tracks and stats, also while the model is switched off.  The set call starts the perceived ring as a copy of the truth ring.
+ * pp_get_perception_stats: the records of the first n_scenes scenes, the last enqueued tick included (host wait).
+ * pp_get_perception_tracks: n tracks from pool entry `first` on.  Both: PP_ERR_STATE on a handle that never made the set call. */
+void pp_default_perception(PerceptionModel* m);
+int  pp_set_perception(pp_handle h, const PerceptionModel* m);
+int  pp_get_perception_stats(pp_handle h, PerceptionStats* out, int n_scenes);
+int  pp_get_perception_tracks(pp_handle h, PerceptTrack* out, int first, int n);
 
 /* ---- fleet coupling: the egos of one world see each other during a rollout -----------------------------------
  * pp_set_fleet groups the resident scenes into WORLDS: world w is the contiguous run of scenes [world_first[w], world_first[w+1]);
@@ -731,7 +763,7 @@ void* pp_stream(pp_handle h);       /* hipStream_t; ordered after the ticks only
  * 31 EpisodeSpawn, 32 EpisodeSpawnStats, 33 TrafficStart, 34 EpisodeRecord, 35 ScoreTraceModel, 36 ScoreTick,
  * 37 ScoreTraceInfo, 38 EpisodeSchedule, 39 EpisodeScheduleRow, 40 EgoTracker, 41 EgoTrackState,
  * (42 unassigned) 43 PackedPlan, 44 PackedGrid, 45 ConflictModel, 46 ConflictScore, 47 TrafficManoeuvre,
- * 48 TrafficManoeuvreState */
+ * 48 TrafficManoeuvreState, (49 unassigned) 50 PerceptionModel, 51 PerceptTrack, 52 PerceptionStats */
 size_t pp_sizeof(int which);
 /* Tick groups (pp_plan_tick): a piped tick defers its search and scoring until G ticks are enqueued, then launches them for
  * all G at once.  G for n scenes per tick, given the search's workgroup slots and the tick slots the handle holds (gcap);

@@ -560,6 +560,40 @@ typedef struct ConflictScore {
     int32_t prev_off, prev_n;        /* state of the step: the slice the previous-snapshot buffer holds for this scene */
 } ConflictScore;                                                            /* 88 B */
 
+/* ---- perception model (build-defined), belongs to the handle ---------------------------------------------
+ * pp_set_perception splits the tick's obstacle snapshot in two: the truth, as before, and what a sensor on the ego would report -
+ * range, field of view, occlusion by nearer discs, hashed misses, position noise, a track per pool entry that confirms and coasts.
+ * Decision, Planning, the search and its scoring read the perceived snapshot; everything that judges the run keeps the truth.
+ * Entry j of the perceived slice is entry j of the truth; an entry the planner must not see is the HIDDEN record
+ * { x = y = DMPP_PERCEPT_HIDDEN_XY, type = the truth's, radius = 0 }. */
+#define DMPP_PERCEPT_HIDDEN_XY 1.0e12
+typedef struct PerceptionModel {
+    double   range;          /* m, > 0, may be +inf: in view needs dx dx + dy dy <= range * range                 */
+    double   cos_half_fov;   /* -1 .. 1: in view needs (d . heading) >= cos_half_fov * |d|; <= -1: all round       */
+    double   sigma0;         /* m, finite, >= 0: position noise at the ego ...                                    */
+    double   sigma_gain;     /* finite, >= 0: ... plus this much per metre of distance                            */
+    uint32_t p_miss;         /* an in-view, unoccluded entry is missed when the high word of its hash is < p_miss */
+    uint32_t seed;
+    int32_t  occlusion;      /* 0 | 1: the sight line to the centre must clear the disc of every nearer entry     */
+    int32_t  confirm;        /* 0 .. 255: a track is confirmed by more than this many detections in a row         */
+    int32_t  coast;          /* 0 .. 255: a confirmed track is reported through this many missing ticks           */
+    int32_t  _pad;           /* 0 */
+} PerceptionModel;                                                          /* 56 B */
+typedef struct PerceptTrack {        /* one per POOL entry */
+    ObPoint  last;           /* the last FRESH report; type and radius: the truth's of the last tick (a change restarts the track) */
+    uint16_t hits, misses;   /* detections in a row; missing ticks in a row while confirmed */
+    uint8_t  confirmed, _pad[3];
+} PerceptTrack;                                                             /* 32 B */
+typedef struct PerceptionStats {     /* one per scene; both groups of counters sum to n_entries */
+    int64_t n_ticks, n_entries;                          /* ticks; entry-ticks */
+    int64_t n_out, n_occluded, n_missed, n_detected;     /* by cause, the first that applies */
+    int64_t n_fresh, n_coasted, n_hidden;                /* by output */
+    double  min_hidden_clearance;    /* m: the closest thing the planner did not see, sqrt(d2) - radius - Vehicle_Width / 2; +inf */
+    int64_t min_hidden_tick;         /* its tick id (the first minimum by tick, then by entry); -1 */
+    int32_t min_hidden_obs;          /* its entry j; -1 */
+    int32_t min_hidden_type;         /* its type; 0 */
+} PerceptionStats;                                                          /* 96 B */
+
 /* ---- scenario schedule (build-defined), part of the spawn model in force --------------------------------
  * pp_set_episode_schedule makes the hashed start choice of §4l a WEIGHTED one: the device keeps, per start record, how many
  * episodes ended on it and how many of those failed, and a record's weight peaks where its failure rate meets `target`.

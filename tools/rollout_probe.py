@@ -54,6 +54,8 @@ TRACK=1 [TRACK_BIAS=b]: every run has a rollout leg of routed ring egos (grid st
 one with the ego tracker (pp_set_ego_tracker: the default model with curv_bias b, DESIGN.md §4q: k_advance_route<true> in the place of
 <false>), alternating.  The workloads differ once tracked egos replan on lateral error: the replan counts are printed beside the rates.
 With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels.
+PERCEPT=1: every run has a rollout leg without and one with the default perception model (pp_set_perception), and
+prints the entry-ticks by cause and by output.
 CONFLICT=1 (implies SCORE=1): every run has a scored rollout leg without and one with the conflict score (pp_set_conflict_score: the default
 model, DESIGN.md §4u: k_score_ego<false, false, true> in the place of <false, false, false>), alternating; the records are read behind the
 timed rollout, outside the timing.  With ONE_ROLLOUT one more leg of each, so that one kernel trace holds both kernels."""
@@ -73,7 +75,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 10
 runs = int(sys.argv[4]) if len(sys.argv) > 4 else 3
-n_obs, depth = 64, 4
+n_obs, depth = int(os.environ.get("N_OBS", "64")), 4          # N_OBS: obstacles per generated scene
 cfg = dm.default_config(512)
 model = dm.default_ego_model()
 
@@ -87,6 +89,7 @@ def fresh():
 
 
 CONFLICT = os.environ.get("CONFLICT", "0") == "1"
+PERCEPT = os.environ.get("PERCEPT", "0") == "1"          # a rollout leg without and one with the default perception model
 SCORE = "1" if CONFLICT else os.environ.get("SCORE", "0")
 FLEET = int(os.environ.get("FLEET", "0"))
 FLEET_WORLD = int(os.environ.get("FLEET_WORLD", "0"))
@@ -363,7 +366,7 @@ def track_run(on, bias):
 TRACE = int(os.environ.get("TRACE", "0"))
 
 
-def rollout_run(score=SCORE == "1", follow=False, trace=0, conflict=False):
+def rollout_run(score=SCORE == "1", follow=False, trace=0, conflict=False, percept=False):
     pl, _ = fresh()
     if follow:
         pl.set_grid_follow(dm.default_grid_follow())
@@ -377,6 +380,8 @@ def rollout_run(score=SCORE == "1", follow=False, trace=0, conflict=False):
         pl.set_score_trace(tm)
     if conflict:
         pl.set_conflict_score(dm.default_conflict())
+    if percept:
+        pl.set_perception(dm.default_perception())
     pl.rollout(warm, model)
     pl.sync()
     t0 = time.perf_counter()
@@ -394,6 +399,10 @@ def rollout_run(score=SCORE == "1", follow=False, trace=0, conflict=False):
         got = len(pl.read_score_trace(int(frozen_rings[0]))[0]) if len(frozen_rings) else 0
         rollout_run.traced = "%d rings frozen, %d counting, %d armed; %d records written in all; the first frozen ring holds %d" % (
             len(frozen_rings), int((info["state"] == 1).sum()), int((info["state"] == 0).sum()), int(info["n_written"].sum()), got)
+    if percept:                               # outside the timing
+        c = pl.perception_stats()
+        rollout_run.percepts = "%d entry-ticks: %d out, %d occluded, %d missed, %d detected; %d fresh, %d coasted, %d hidden; closest hidden %.3f m" % tuple(
+            [int(c[f].sum()) for f in ("n_entries", "n_out", "n_occluded", "n_missed", "n_detected", "n_fresh", "n_coasted", "n_hidden")] + [float(c["min_hidden_clearance"].min())])
     if conflict:                              # outside the timing
         c = pl.conflict_score()
         rollout_run.conflicts = "%d ticks, %d scenes with a conflict, %d with a critical tick, smallest TTC %.3f s, largest DRAC %.3f m/s^2, %d ticks without history" % (
@@ -613,6 +622,20 @@ if CONFLICT:
     if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: both kernels in one trace
         rollout_run(True)
         rollout_run(True, conflict=True)
+    sys.exit(0)
+if PERCEPT:
+    off, on = [], []
+    for r in range(runs):
+        a, _ = rollout_run()
+        b, _ = rollout_run(percept=True)
+        off.append(a), on.append(b)
+        print("run %d  %d scenes  perception off %.3f M ticks/s   perception on %.3f M ticks/s (%s)" % (r, n, a / 1e6, b / 1e6, rollout_run.percepts), flush=True)
+    print("median  %d scenes  perception off %.3f M ticks/s (spread %.3f)   perception on %.3f M ticks/s (spread %.3f)   ratio %.3f" %
+          (n, statistics.median(off) / 1e6, (max(off) - min(off)) / 1e6, statistics.median(on) / 1e6, (max(on) - min(on)) / 1e6,
+           statistics.median(on) / statistics.median(off)), flush=True)
+    if os.environ.get("ONE_ROLLOUT"):        # for rocprofv3 --kernel-trace --stats: both snapshot kernels in one trace
+        rollout_run()
+        rollout_run(percept=True)
     sys.exit(0)
 if SCORE == "1" and TRACE > 0:
     off, on = [], []
